@@ -2,13 +2,21 @@
 """Headline benchmark: Mpixel-iters/s of one full SIREN fit step (forward + MSE + backward + Adam)
 at hidden 256 x depth 8 on a synthetic 4096x4096x3 grid (BASELINE.json `metric`).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU; each rank fits its own image —
    per-image sharding, no data-path collective, weak scaling.)
 
-Prints ONE JSON line on rank 0 with the contract keys plus
+A plain run sets up, warms up, times K steps and prints ONE JSON line on rank 0 with the contract keys
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full additionally records per-kernel
+HIP events in the timed region and prints
   roofline      MFMA roofline of the dominant kernel (algorithmic GEMM FLOPs / HIP-event duration)
+  kernels       per-kernel ms / TFLOP/s / GB/s of one step
+  psnr_after_run
+  by_scratch_format  the same workload with every backward scratch format forced
   cpu_baseline  the CPU oracle (fp32 restatement of the reference step) timed on the host cores
+--dump-outputs DIR writes what the last timed step left for its caller (rank 0): params, grads, exp_avg,
+exp_avg_sq (float32; a fixed seeded sample of entries where an array exceeds DUMP_MAX_ELEMS) and loss
+(float64 [1], that step's MSE) as DIR/<name>.npy.  Inputs are seeded: equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -24,6 +32,7 @@ for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
 import torch  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16/fp16 MFMA peak of MI355X (MI355X_MICROARCH.md chip table)
+DUMP_MAX_ELEMS = 3 << 20    # per dumped array: four of them stay under 64 MB in all
 
 
 def kernel_sources():
@@ -113,6 +122,21 @@ def cpu_baseline(hidden, depth, size, warm=1, timed=3):
                       f"oracle, {dt * 1e3:.0f} ms/step"}
 
 
+def dump_outputs(eng, out_dir):
+    """The state one timed step hands back to its caller, as float32 / float64 .npy files (see the module doc)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    m, v, _ = eng.get_adam_state()
+    arrays = {"params": eng.get_params(), "grads": eng.get_grads(), "exp_avg": m, "exp_avg_sq": v}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    loss = eng.sse_view().double().cpu().numpy() / (eng.out_features * eng.npix)
+    np.save(os.path.join(out_dir, "loss.npy"), loss)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -125,9 +149,14 @@ def main():
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--scratch", type=int, default=0, choices=[0, 8, 12, 16],
                     help="sf_config.scratch_format: 0 = auto (fp16, hidden <= 512: 8 = phase bytes + fp8 deltas from 2^20 pixels; below that 12 = phase bytes + 16-bit deltas at hidden <= 256), 16 = round-1 format")
-    ap.add_argument("--no-formats", action="store_true", help="skip the by_scratch_format leg (5 warm-up + 10 timed steps per format after the headline region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel HIP events in the timed region (roofline, kernels), psnr_after_run, the "
+                         "by_scratch_format leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's params / grads / Adam moments / loss as DIR/<name>.npy")
+    ap.add_argument("--no-formats", action="store_true", help="--full: skip the by_scratch_format leg (5 warm-up + 10 timed steps per format after the headline region)")
     ap.add_argument("--cpu-size", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse the multi-process "
                          "path with several ranks on one GPU)")
@@ -139,6 +168,8 @@ def main():
                     help="N>1: per-image = one independent fit per GPU (weak scaling, no collective); "
                          "pixel-split = ONE image, rows sharded over ranks, gradient all-reduce over RCCL (strong scaling)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -195,8 +226,9 @@ def main():
 
     run_steps(args.warmup)
     barrier()
-    eng.profile(True)
-    eng.profile_reset()
+    if args.full:                   # per-kernel HIP events: two per launch, recorded inside the timed region
+        eng.profile(True)
+        eng.profile_reset()
     t0 = time.perf_counter()
     run_steps(args.steps)
     barrier()
@@ -205,26 +237,21 @@ def main():
         t = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-    rep = eng.profile_report()
-    eng.profile(False)
-    _, sse = eng.forward(want_pred=False)
-    if split:
-        t = torch.tensor([sse], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t)
-        sse = t.item()
-    psnr = 10 * torch.log10(torch.tensor(3.0 * H * W / sse)).item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+    if args.full:
+        rep = eng.profile_report()
+        eng.profile(False)
+        _, sse = eng.forward(want_pred=False)
+        if split:
+            t = torch.tensor([sse], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(t)
+            sse = t.item()
+        psnr = 10 * torch.log10(torch.tensor(3.0 * H * W / sse)).item()
 
     if rank == 0:
         F = flops_per_pixel_iter(args.hidden, args.depth)
         value = (1 if split else world) * H * W * args.steps / dt / 1e6
-        kern = {k: v for k, v in rep.items() if v["launches"]}
-        dom = max((k for k in kern if kern[k]["flops_per_launch"] > 0), key=lambda k: kern[k]["total_ms"])
-        d = kern[dom]
-        avg_ms = d["total_ms"] / d["launches"]
-        # HBM bytes per launch of the dominant kernel: PMC counters cannot be collected inside this process, so the
-        # value comes from the committed rocprofv3 --pmc passes - only if they were taken on these kernel sources
-        traffic, traffic_source = pmc_traffic(dom, args, eng.npix)
-        ach = d["flops_per_launch"] / (avg_ms * 1e-3) / 1e12
         out = {
             "metric": f"Mpixel-iters/s (fwd+bwd+Adam) @ SIREN-{args.hidden}x{args.depth}",
             "value": value, "unit": "Mpixel-iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -238,6 +265,17 @@ def main():
                        "chunk_pixels": min(eng.npix, args.chunk or (1 << 22) // max(1, args.hidden // 256)),
                        "scratch_format": eng.scratch_format},   # 8 = phase bytes + fp8 deltas, 12 = + 16-bit deltas, 16 = unorm16 / 16-bit
             "step_mfma_frac": value / world * 1e6 * F / (PEAK_BF16_TFLOPS * 1e12),   # per GPU
+        }
+    if rank == 0 and args.full:
+        kern = {k: v for k, v in rep.items() if v["launches"]}
+        dom = max((k for k in kern if kern[k]["flops_per_launch"] > 0), key=lambda k: kern[k]["total_ms"])
+        d = kern[dom]
+        avg_ms = d["total_ms"] / d["launches"]
+        # HBM bytes per launch of the dominant kernel: PMC counters cannot be collected inside this process, so the
+        # value comes from the committed rocprofv3 --pmc passes - only if they were taken on these kernel sources
+        traffic, traffic_source = pmc_traffic(dom, args, eng.npix)
+        ach = d["flops_per_launch"] / (avg_ms * 1e-3) / 1e12
+        out.update({
             "psnr_after_run": psnr,
             "roofline": {"bound": "mfma", "kernel": dom, "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                          "frac": ach / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
@@ -253,7 +291,7 @@ def main():
                             if v["total_ms"] > 0 else 0.0,
                             "algorithmic_GBps": (v["bytes_per_launch"] * v["launches"] / (v["total_ms"] * 1e-3) / 1e9)
                             if v["total_ms"] > 0 else 0.0} for k, v in kern.items()},
-        }
+        })
         if world == 1 and not args.no_formats and args.hidden <= 256 and args.dtype == "f16":
             # the same workload with every backward scratch format forced, timed by the same clock AFTER the headline
             # region (5 warm-up + 10 timed steps each): the 16-bit-scratch throughput next to the fp8 one
@@ -277,6 +315,7 @@ def main():
                 torch.cuda.empty_cache()
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.hidden, args.depth, args.cpu_size)
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()
