@@ -11,6 +11,7 @@
 #include "siren_fwd16.hip"
 #include "siren_wide.hip"
 #include "siren_kmeans.hip"
+#include "fourier_kernels.hip"
 
 #include <math.h>
 #include <stdio.h>
@@ -149,6 +150,15 @@ struct sf_engine {
   double prof_ms[K_COUNT] = {0};
   int64_t prof_n[K_COUNT] = {0};
   double prof_flops[K_COUNT] = {0}, prof_bytes[K_COUNT] = {0};
+  // FourierNet handle (sf_fourier_create, fourier_kernels.hip): D = number of Linear layers, WD = hidden width
+  bool fourier = false;
+  int MS = 0;                   // map_size (encoding width)
+  float* ffB = nullptr;         // encoding.B [in_features][MS/2] (sf_set_encoding)
+  bool have_B = false;
+  u32x4* ffimg = nullptr;       // fp16 weight images (forward of every layer, backward of layers >= 1)
+  long ff_img_f[kFfMaxLinear] = {0}, ff_img_b[kFfMaxLinear] = {0}, ff_img_n = 0;   // offsets / size in 16-byte units
+  _Float16 *ffH = nullptr, *ffG = nullptr, *ffZ = nullptr;   // [D-1][WD][chunk] ReLU outputs, gradients; [3][chunk] dL/dz
+  int ff_dw_wgs = 0;            // max weight-gradient workgroups along the pixels (slab rows)
 };
 
 namespace {
@@ -471,9 +481,11 @@ int launch_fwd(sf_engine* h, const FwdArgs& a, int n_super, bool train) {
   return fail(SF_ERR_INVALID, "unsupported hidden width");
 }
 int refresh_images_wide(sf_engine* h);
+int refresh_images_fourier(sf_engine* h);
 int refresh_images(sf_engine* h) {
   if (!h->images_dirty) return SF_OK;
   if (h->wide) return refresh_images_wide(h);
+  if (h->fourier) return refresh_images_fourier(h);
   ImgArgs a;
   memset(&a, 0, sizeof(a));
   a.params = h->params;
@@ -846,9 +858,152 @@ int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
   return SF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// FourierNet (fourier_kernels.hip): per chunk k_ff_fwd -> k_ff_bwd -> k_ff_dw per layer, each followed by the
+// fixed-order slab reduction into the flat gradient; Adam, graph replay and the rest are shared with SIREN
+// ---------------------------------------------------------------------------------------------------------
+int refresh_images_fourier(sf_engine* h) {
+  FfImgArgs a;
+  memset(&a, 0, sizeof(a));
+  a.params = h->params; a.nlin = h->D; a.img = h->ffimg;
+  for (int l = 0; l < h->D; ++l) {
+    a.off_w[l] = h->off_w[l];
+    a.in[l] = l == 0 ? h->MS : h->WD;
+    a.out[l] = l == h->D - 1 ? h->cfg.out_features : h->WD;
+    // segments in memory order: f0, (b0: empty), f1, b1, f2, b2, ...
+    a.start[2 * l] = h->ff_img_f[l];
+    a.start[2 * l + 1] = l == 0 ? h->ff_img_f[1] : h->ff_img_b[l];
+  }
+  a.start[2 * h->D] = h->ff_img_n;
+  Launch L(h, K_IMAGES, 0, (double)h->ff_img_n * 16.0);
+  hipLaunchKernelGGL(k_ff_images, dim3((unsigned)((h->ff_img_n + 255) / 256)), dim3(256), 0, h->stream, a);
+  L.done();
+  HIPCHK(hipGetLastError());
+  h->images_dirty = false;
+  return SF_OK;
+}
+
+template <int NI, bool E0>
+int launch_ff_dw(sf_engine* h, const FfDwArgs& a, int gx) {
+  hipLaunchKernelGGL((k_ff_dw<NI, E0>), dim3(gx, (a.n_groups + 3) / 4), dim3(256), 0, h->stream, a);
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
+
+template <int WD>
+int launch_ff_chain(sf_engine* h, const FfArgs& a, int n_super, int which) {   // 0 eval forward, 1 training forward, 2 backward
+  int rc = SF_OK;
+  if (which == 0) { rc = set_lds(k_ff_fwd<WD, false>, kFfLdsBytes); if (!rc) hipLaunchKernelGGL((k_ff_fwd<WD, false>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a); }
+  else if (which == 1) { rc = set_lds(k_ff_fwd<WD, true>, kFfLdsBytes); if (!rc) hipLaunchKernelGGL((k_ff_fwd<WD, true>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a); }
+  else { rc = set_lds(k_ff_bwd<WD>, kFfLdsBytes); if (!rc) hipLaunchKernelGGL((k_ff_bwd<WD>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a); }
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
+int launch_ff(sf_engine* h, const FfArgs& a, int n_super, int which) {
+  switch (h->WD) {
+    case 32: return launch_ff_chain<32>(h, a, n_super, which);
+    case 64: return launch_ff_chain<64>(h, a, n_super, which);
+    case 128: return launch_ff_chain<128>(h, a, n_super, which);
+    case 256: return launch_ff_chain<256>(h, a, n_super, which);
+  }
+  return fail(SF_ERR_INVALID, "unsupported hidden width");
+}
+
+int run_pass_fourier(sf_engine* h, bool train, float* pred, bool want_sse) {
+  if (!h->have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
+  int rc = refresh_images(h);
+  if (rc) return rc;
+  const int WD = h->WD, D = h->D, MS = h->MS;
+  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
+  long sse_off = 0;
+  for (long c = 0; c < n_chunks; ++c) {
+    const long pix0 = c * h->chunk_px;
+    long px = h->npix - pix0;
+    if (px > h->chunk_px) px = h->chunk_px;
+    const int n_super = (int)((px + kSuper - 1) / kSuper);
+    const double npx = (double)n_super * kSuper;
+    FfArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.pix0 = pix0; fa.npix = h->npix; fa.cp = h->chunk_px;
+    fa.Btab = h->ffB; fa.MS = MS; fa.nlin = D; fa.img = h->ffimg; fa.params = h->params;
+    for (int l = 0; l < D; ++l) { fa.img_f[l] = h->ff_img_f[l]; fa.img_b[l] = h->ff_img_b[l]; fa.off_b[l] = h->off_b[l]; }
+    fa.H = h->ffH; fa.G = h->ffG; fa.Z = h->ffZ;
+    fa.tgt = h->img; fa.pred = pred; fa.sse_part = h->sse_part + sse_off;
+    fa.gscale = (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total));
+    sse_off += n_super;
+    const double f_hidden = (double)(D - 2) * WD * WD;
+    {
+      Launch L(h, K_FWD, 2.0 * ((double)MS * WD + f_hidden + 32.0 * WD) * npx,
+               npx * (12.0 + (train ? (D - 1) * WD * 2.0 + 6.0 : 0.0)));
+      rc = launch_ff(h, fa, n_super, train ? 1 : 0);
+      L.done();
+      if (rc) return rc;
+    }
+    if (!train) continue;
+    {
+      Launch L(h, K_BWD_HIDDEN, 2.0 * (f_hidden + 16.0 * WD) * npx, npx * (6.0 + (D - 1) * WD * 4.0));
+      rc = launch_ff(h, fa, n_super, 2);
+      L.done();
+      if (rc) return rc;
+    }
+    // weight gradients, last layer first: per-workgroup slabs over contiguous pixel ranges, then k_reduce*
+    int gx = (int)(npx / kSuper);
+    if (gx > h->ff_dw_wgs) gx = h->ff_dw_wgs;
+    long ppw = ((long)npx + gx - 1) / gx;
+    ppw = (ppw + 15) / 16 * 16;
+    gx = (int)(((long)npx + ppw - 1) / ppw);
+    for (int l = D - 1; l >= 0; --l) {
+      const bool last = l == D - 1;
+      FfDwArgs da;
+      memset(&da, 0, sizeof(da));
+      da.rows = last ? h->cfg.out_features : WD;
+      da.A = last ? h->ffZ : h->ffG + (size_t)l * WD * h->chunk_px;
+      da.Bm = l == 0 ? nullptr : h->ffH + (size_t)(l - 1) * WD * h->chunk_px;
+      da.in = l == 0 ? MS : WD;
+      da.n_it = da.in / 32;
+      const int NI = da.n_it < 4 ? da.n_it : 4;
+      da.n_groups = ((da.rows + 31) / 32) * (da.n_it / NI);
+      da.cp = h->chunk_px; da.n_px = (long)npx; da.ppw = ppw; da.slab = h->slab; da.e = fa;
+      {
+        Launch L(h, l == 0 ? K_DW_FIRST : last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * 32.0 * ((da.rows + 31) / 32) * da.in * npx,
+                 npx * 2.0 * (32.0 * ((da.rows + 31) / 32) + (l == 0 ? 0.0 : da.in)));
+        if (l == 0) rc = NI == 1 ? launch_ff_dw<1, true>(h, da, gx) : NI == 2 ? launch_ff_dw<2, true>(h, da, gx) : launch_ff_dw<4, true>(h, da, gx);
+        else rc = NI == 1 ? launch_ff_dw<1, false>(h, da, gx) : NI == 2 ? launch_ff_dw<2, false>(h, da, gx) : launch_ff_dw<4, false>(h, da, gx);
+        L.done();
+        if (rc) return rc;
+      }
+      const long n = (long)da.rows * da.in + da.rows;
+      Launch L(h, K_REDUCE, 0, (double)gx * n * 4.0);
+      if (!last) {   // slab layout [W rows*in | b rows] == flat gradient layout of the layer
+        const int n4 = (int)(n / 4);
+        hipLaunchKernelGGL(k_reduce_vec, dim3((n4 + 7) / 8), dim3(256), 0, h->stream, (const float*)h->slab, gx, n, n4,
+                           h->grads + h->off_w[l], (int)(c > 0), 1.0f / h->gpre, (const float*)nullptr, (const float*)nullptr);
+      } else {
+        ReduceArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.slab = h->slab; ra.n_wg = gx; ra.slab_rows = da.rows; ra.slab_cols = da.in; ra.rows_out = da.rows; ra.cols_out = da.in;
+        ra.mode = 0; ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l]; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
+        hipLaunchKernelGGL(k_reduce, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, h->stream, ra);
+      }
+      L.done();
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if (want_sse || train) {
+    Launch L(h, K_SSE, 0, (double)sse_off * 4);
+    hipLaunchKernelGGL(k_sse_reduce, dim3(1), dim3(256), 0, h->stream, (const float*)h->sse_part, (int)sse_off,
+                       h->sse_dev, h->replay ? h->loss_tab : h->loss_dst, (const int*)(h->replay ? h->iter_dev : h->iter_dev + 2));
+    L.done();
+    HIPCHK(hipGetLastError());
+  }
+  return SF_OK;
+}
+
 int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   if ((train || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
+  if (h->fourier) return run_pass_fourier(h, train, pred, want_sse);
   if (train && (!h->Pbuf || !h->Dbuf)) return fail(SF_ERR_STATE, "the handle has no backward scratch");   // (never a null store on the GPU)
   if (h->wide) return run_pass_wide(h, train, pred, want_sse);
   int rc = refresh_images(h);
@@ -1191,6 +1346,110 @@ int sf_create(const sf_config* cfg, sf_handle** out) try {
   return SF_OK;
 } SF_CATCH
 
+// FourierNet handle: the same sf_engine, run by fourier_kernels.hip (run_pass_fourier); every other entry point is shared
+int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
+  if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
+  if (cfg->in_features != 2) return fail(SF_ERR_INVALID, "in_features must be 2 (coordinate grid)");
+  if (cfg->out_features != 3) return fail(SF_ERR_INVALID, "out_features must be 3 (the fused sigmoid / loss epilogue is RGB)");
+  if (cfg->hidden != 32 && cfg->hidden != 64 && cfg->hidden != 128 && cfg->hidden != 256)
+    return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128 or 256 for FourierNet (other widths: zero-pad on the host)");
+  if (cfg->map_size != 64 && cfg->map_size != 128 && cfg->map_size != 256 && cfg->map_size != 512)
+    return fail(SF_ERR_INVALID, "map_size must be 64, 128, 256 or 512");
+  if (cfg->n_linear < 2 || cfg->n_linear > kFfMaxLinear) return fail(SF_ERR_INVALID, "n_linear must be 2..12");
+  if (cfg->compute_dtype != SF_F16) return fail(SF_ERR_INVALID, "FourierNet runs fp16 operands only (compute_dtype SF_F16)");
+  if (cfg->height < 1 || cfg->width < 1) return fail(SF_ERR_INVALID, "bad image size");
+  if ((double)cfg->height * (double)cfg->width >= 2147483648.0) return fail(SF_ERR_INVALID, "image too large: height * width must stay below 2^31");
+  if (cfg->chunk_pixels < 0) return fail(SF_ERR_INVALID, "chunk_pixels must be >= 0");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SF_ERR_NO_DEVICE, "no HIP device visible");
+  if (cfg->device < 0 || cfg->device >= ndev) return fail(SF_ERR_INVALID, "bad device ordinal");
+  DevGuard dev_guard(cfg->device);
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(SF_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950");
+
+  sf_engine* h = new sf_engine();
+  h->fourier = true;
+  memset(&h->cfg, 0, sizeof(h->cfg));
+  h->cfg.abi_version = cfg->abi_version;
+  h->cfg.height = cfg->height; h->cfg.width = cfg->width; h->cfg.row_begin = 0; h->cfg.row_end = cfg->height;
+  h->cfg.in_features = cfg->in_features; h->cfg.out_features = cfg->out_features; h->cfg.hidden = cfg->hidden;
+  h->cfg.depth = cfg->n_linear; h->cfg.compute_dtype = cfg->compute_dtype;
+  h->cfg.beta1 = cfg->beta1; h->cfg.beta2 = cfg->beta2; h->cfg.eps = cfg->eps;
+  if (h->cfg.beta1 == 0.f && h->cfg.beta2 == 0.f && h->cfg.eps == 0.f) { h->cfg.beta1 = 0.9f; h->cfg.beta2 = 0.999f; h->cfg.eps = 1e-8f; }
+  h->cfg.device = cfg->device; h->cfg.stream = cfg->stream; h->cfg.chunk_pixels = cfg->chunk_pixels;
+  h->cfg.scratch_format = 16;
+  h->beta1_d = shortest_double(h->cfg.beta1);
+  h->beta2_d = shortest_double(h->cfg.beta2);
+  h->D = cfg->n_linear; h->WD = cfg->hidden; h->MS = cfg->map_size;
+  h->stream = (hipStream_t)cfg->stream;
+  h->npix = (long)cfg->height * cfg->width;
+  h->n_total = (double)cfg->height * (double)cfg->width;
+  const int WD = h->WD, D = h->D, MS = h->MS;
+  // flat parameters: layers.{2l}.weight, layers.{2l}.bias (encoding.B is frozen and lives outside)
+  int64_t off = 0;
+  long img = 0;
+  for (int l = 0; l < D; ++l) {
+    const int in = l == 0 ? MS : WD, outn = l == D - 1 ? cfg->out_features : WD;
+    h->off_w[l] = off; off += (int64_t)in * outn;
+    h->off_b[l] = off; off += outn;
+    h->ff_img_f[l] = img; img += (long)((outn + 31) / 32) * (in / 16) * 64;
+    if (l > 0) { h->ff_img_b[l] = img; img += (long)(in / 32) * ((outn + 15) / 16) * 64; }
+  }
+  h->P = off;
+  h->ff_img_n = img;
+  h->gpre = (float)exp2(ceil(log2((double)cfg->out_features * (double)cfg->height * (double)cfg->width)) + 2.0);
+  // chunking: 4 Mi pixels, or fewer when the activation + gradient planes of a chunk would pass 16 GiB
+  const double px_bytes = (double)(D - 1) * WD * 4.0 + 8.0;
+  long chunk = cfg->chunk_pixels > 0 ? (long)cfg->chunk_pixels : (long)fmin((double)(1L << 22), 17179869184.0 / px_bytes);
+  chunk = (chunk + kSuper - 1) / kSuper * kSuper;
+  const long npix_pad = (h->npix + kSuper - 1) / kSuper * kSuper;
+  if (chunk > (1L << 22)) chunk = 1L << 22;   // the kernels address a [WD][chunk] plane with 32-bit offsets
+  if (chunk > npix_pad) chunk = npix_pad;
+  h->chunk_px = chunk;
+  h->dw_wg = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  h->ff_dw_wgs = 4 * h->dw_wg;
+  long slab_row = (long)WD * MS + WD;
+  if ((long)WD * WD + WD > slab_row) slab_row = (long)WD * WD + WD;
+  auto alloc = [&](void** p, size_t bytes) -> int {
+    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+    return SF_OK;
+  };
+  int rc = SF_OK;
+#define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
+  ALLOC(h->params, h->P * 4); ALLOC(h->grads, h->P * 4); ALLOC(h->m, h->P * 4); ALLOC(h->v, h->P * 4);
+  ALLOC(h->mask, h->P * 4);
+  ALLOC(h->ffimg, (size_t)h->ff_img_n * 16);
+  ALLOC(h->ffB, (size_t)cfg->in_features * (MS / 2) * 4);
+  ALLOC(h->gh, (size_t)cfg->height * 4); ALLOC(h->gw, (size_t)cfg->width * 4);
+  ALLOC(h->ffH, (size_t)(D - 1) * WD * chunk * 2); ALLOC(h->ffG, (size_t)(D - 1) * WD * chunk * 2);
+  ALLOC(h->ffZ, (size_t)4 * chunk * 2);
+  ALLOC(h->slab, (size_t)h->ff_dw_wgs * slab_row * 4);
+  h->n_sse = npix_pad / kSuper + (h->npix + chunk - 1) / chunk + 8;
+  ALLOC(h->sse_part, (h->n_sse + 64) * 4); ALLOC(h->sse_dev, 8);
+#undef ALLOC
+  if (rc) { sf_destroy(h); return rc; }
+  hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
+  hipMemsetAsync(h->grads, 0, h->P * 4, h->stream);
+  hipMemsetAsync(h->m, 0, h->P * 4, h->stream);
+  hipMemsetAsync(h->v, 0, h->P * 4, h->stream);
+  *out = h;
+  return SF_OK;
+} SF_CATCH
+
+int sf_set_encoding(sf_handle* h, const float* B_dev) try {
+  if (!h || !B_dev) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->fourier) return fail(SF_ERR_INVALID, "sf_set_encoding: not a FourierNet handle (sf_fourier_create)");
+  DevGuard dev_guard(h->cfg.device);
+  HIPCHK(hipMemcpyAsync(h->ffB, B_dev, (size_t)h->cfg.in_features * (h->MS / 2) * 4, hipMemcpyDeviceToDevice, h->stream));
+  h->have_B = true;
+  return SF_OK;
+} SF_CATCH
+
 int sf_destroy(sf_handle* h) try {
   if (!h) return SF_OK;
   DevGuard dev_guard(h->cfg.device);
@@ -1248,7 +1507,8 @@ int sf_destroy(sf_handle* h) try {
   for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
   void* ptrs[] = {h->params, h->grads, h->m, h->v, h->mask, h->wf, h->wf_last, h->wb, h->wb_last, h->l0tab, h->l0img,
                   h->gh, h->gw, h->Pbuf, h->Dbuf, h->Dlast, h->slab, h->sse_part, h->biasw, h->Abuf,
-                  h->sse_dev, h->scale_dev, h->pad8, h->km_ws, h->wf16, h->wf16_last, h->l0img16, h->lsc};
+                  h->sse_dev, h->scale_dev, h->pad8, h->km_ws, h->wf16, h->wf16_last, h->l0img16, h->lsc,
+                  h->ffB, h->ffimg, h->ffH, h->ffG, h->ffZ};
   for (void* p : ptrs) if (p) hipFree(p);
   if (h->gexec) hipGraphExecDestroy(h->gexec);
   if (h->gstream) { hipStreamSynchronize(h->gstream); hipStreamDestroy(h->gstream); hipEventDestroy(h->gev_in); hipEventDestroy(h->gev_out); }
@@ -1379,6 +1639,7 @@ int sf_sse_ptr(sf_handle* h, double** p) try {
 
 int sf_debug_scratch(sf_handle* h, int32_t which, void** p, int64_t* bytes) try {
   if (!h || !p || !bytes) return fail(SF_ERR_INVALID, "null argument");
+  if (h->fourier) return fail(SF_ERR_INVALID, "sf_debug_scratch: a FourierNet handle has no phase / delta scratch");
   const int D = h->D;
   switch (which) {
     case 0: *p = h->Pbuf; *bytes = (int64_t)(D - 1) * h->p_stride * 16; return SF_OK;

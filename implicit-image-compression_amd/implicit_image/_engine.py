@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SIREN_FIT_LIB: developer override to A/B kernel variants built side by side (same C ABI)
 _LIB_PATH = os.environ.get("SIREN_FIT_LIB") or os.path.normpath(os.path.join(_HERE, "..", "csrc", "libsiren_fit.so"))
 
-SF_ABI_VERSION = 2
+SF_ABI_VERSION = 3
 DTYPES = {"bf16": 0, "f16": 1}
 
 
@@ -28,6 +28,16 @@ class sf_config(C.Structure):
         ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
         ("device", C.c_int32), ("stream", C.c_void_p), ("chunk_pixels", C.c_int64),
         ("scratch_format", C.c_int32),
+    ]
+
+
+class sf_fourier_config(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+        ("in_features", C.c_int32), ("out_features", C.c_int32), ("map_size", C.c_int32), ("hidden", C.c_int32),
+        ("n_linear", C.c_int32), ("compute_dtype", C.c_int32),
+        ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("device", C.c_int32), ("stream", C.c_void_p), ("chunk_pixels", C.c_int64),
     ]
 
 
@@ -48,6 +58,8 @@ def load_library():
     proto = {
         "sf_create": [C.POINTER(sf_config), C.POINTER(H)],
         "sf_destroy": [H],
+        "sf_fourier_create": [C.POINTER(sf_fourier_config), C.POINTER(H)],
+        "sf_set_encoding": [H, F],
         "sf_abi_version": [],
         "sf_num_params": [H, C.POINTER(I64)],
         "sf_scratch_format": [H, C.POINTER(C.c_int32)],
@@ -293,3 +305,35 @@ class SirenEngine:
             rep[name.value.decode()] = {"total_ms": ms.value, "launches": cnt.value,
                                         "flops_per_launch": fl.value, "bytes_per_launch": by.value}
         return rep
+
+
+class FourierEngine(SirenEngine):
+    """FourierNet fit on one HIP stream: an sf_handle made by sf_fourier_create (fourier_kernels.hip).  Every method of
+    SirenEngine applies; the frozen encoding goes in through set_encoding before the first pass."""
+
+    def __init__(self, height: int, width: int, hidden: int, n_linear: int, map_size: int, out_features: int = 3,
+                 device: int = 0, chunk_pixels: int = 0, betas=(0.9, 0.999), eps: float = 1e-8):
+        self.lib = load_library()
+        if not torch.cuda.is_available():
+            raise RuntimeError("FourierEngine needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
+        self.device = torch.device("cuda", device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        cfg = sf_fourier_config(SF_ABI_VERSION, height, width, 2, out_features, map_size, hidden, n_linear, DTYPES["f16"],
+                                betas[0], betas[1], eps, device, stream, chunk_pixels)
+        self.h = C.c_void_p()
+        _check(self.lib.sf_fourier_create(C.byref(cfg), C.byref(self.h)))
+        n = C.c_int64()
+        _check(self.lib.sf_num_params(self.h, C.byref(n)))
+        self.num_params = n.value
+        self.height, self.width, self.hidden, self.depth = height, width, hidden, n_linear
+        self.map_size = map_size
+        self.row_begin, self.row_end = 0, height
+        self.npix = height * width
+        self.out_features = out_features
+        self._target = None
+        self._views = {}
+
+    def set_encoding(self, B: torch.Tensor):
+        """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
+        _check(self.lib.sf_set_encoding(self.h, _f32_cuda(B.detach().contiguous(), 2 * (self.map_size // 2)).data_ptr()))

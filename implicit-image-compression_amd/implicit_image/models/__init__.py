@@ -1,4 +1,5 @@
+from .fourier import FourierNet
 from .siren import Siren
 
-# reference: implicit_image/models/__init__.py:5 (fourier / wavelet_siren are outside the hot path)
-registry = {"siren": Siren}
+# reference: implicit_image/models/__init__.py:5 (wavelet_siren needs pytorch_wavelets / kornia: outside the hot path)
+registry = {"siren": Siren, "fourier": FourierNet}

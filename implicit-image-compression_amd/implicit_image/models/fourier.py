@@ -1,0 +1,139 @@
+"""FourierNet with the reference's constructor, parameter names, state_dict keys and random-draw order
+(reference: implicit_image/models/fourier.py:8-72), executed by the gfx950 engine (csrc/fourier_kernels.hip).
+
+`encoding.B` is a frozen Parameter handed to the engine once per bind; every `layers.{2k}.{weight,bias}`
+(the nn.Linear layers of the Sequential) is, once bound, a zero-copy view of the engine's flat fp32 state,
+as in `Siren`.  forward() runs the fused HIP kernels; there is no PyTorch arithmetic fallback.
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from .siren import Siren
+
+# the reference's Masking puts the frozen encoding.B into its mask_dict and its first update_connections() fails on
+# B.grad being None (reference pipeline/masking/funcs/grow.py:87): there is no reference behaviour to reproduce
+MASKING_UNSUPPORTED = ("mask-based sparsity (RigL / SNFS / SET / Pruning) is not supported on FourierNet: the reference's "
+                       "Masking registers the frozen encoding.B and its first update_connections() fails with "
+                       "AttributeError ('NoneType' object has no attribute 'dtype', pipeline/masking/funcs/grow.py:87). "
+                       "Use masking=none or masking=Small_Dense")
+
+
+class Encoding(nn.Module):
+    """[sin(2 pi x B), cos(2 pi x B)] (reference fourier.py:8-24); evaluated inside the engine's forward kernel."""
+
+    def __init__(self, input_size: int = 2, map_size: int = 256, map_scale: float = 10.0):
+        super().__init__()
+        assert map_size % 2 == 0, "Need even map size"
+        self.B = nn.Parameter(torch.randn(input_size, map_size // 2) * map_scale, requires_grad=False)
+
+    def forward(self, x):  # pragma: no cover - the encoding never runs on its own
+        raise RuntimeError("Encoding is evaluated by the fused engine; call FourierNet.forward(grid)")
+
+
+class FourierNet(Siren):
+    # engine widths: Small_Dense's int(hidden * sqrt(density)) runs zero-padded to the next one (padded neurons have zero
+    # weights and bias, output relu(0) = 0 and receive exactly zero gradients)
+    WIDTHS = (32, 64, 128, 256)
+    mask_unsupported = MASKING_UNSUPPORTED
+
+    def __init__(self, input_size: int = 2, output_size: int = 3, depth: int = 8, hidden_size: int = 128,
+                 map_size: int = 128, map_scale: float = 10.0, small_dense_density: float = 1.0,
+                 compute_dtype: str = "f16", chunk_pixels: int = 0, **kwargs):
+        nn.Module.__init__(self)
+        if compute_dtype != "f16":
+            raise NotImplementedError("FourierNet runs fp16 MFMA operands only (engine.compute_dtype=f16)")
+        hidden_size = int(hidden_size * np.sqrt(small_dense_density))   # Small_Dense (reference fourier.py:40)
+        # the nn.Linear default inits run first, in layer order; the encoding's randn comes after them
+        layers = [nn.Linear(map_size, hidden_size), nn.ReLU(inplace=True)]
+        for _ in range(depth - 3):
+            layers += [nn.Linear(hidden_size, hidden_size), nn.ReLU(inplace=True)]
+        layers += [nn.Linear(hidden_size, output_size), nn.Sigmoid()]
+        self.encoding = Encoding(input_size, map_size, map_scale)        # registered before `layers` (state_dict order)
+        self.layers = nn.Sequential(*layers)
+        self.simulate_quantization = False
+        n_linear = len(layers) // 2
+        self.cfg = dict(input_size=input_size, output_size=output_size, depth=depth, hidden_size=hidden_size,
+                        map_size=int(map_size), map_scale=float(map_scale), n_linear=n_linear,
+                        compute_dtype=compute_dtype, chunk_pixels=chunk_pixels, scratch_format=16)
+        self.pre_pass_callbacks = []
+        self.post_backward_callbacks = []
+        self._engine_width = next((w for w in self.WIDTHS if w >= hidden_size), None)
+        if self._engine_width is None:
+            raise NotImplementedError(f"hidden_size {hidden_size} > 256 is not supported for FourierNet by the gfx950 engine")
+        if input_size != 2 or output_size != 3 or map_size not in (64, 128, 256, 512) or not 2 <= n_linear <= 12:
+            raise NotImplementedError("FourierNet on the gfx950 engine: input_size 2, output_size 3, map_size 64 / 128 / "
+                                      f"256 / 512 and 2..12 Linear layers (got {input_size}, {output_size}, {map_size}, {n_linear})")
+        self._padded = self._engine_width != hidden_size
+        self._adam = ((0.9, 0.999), 1e-8)
+        self._pad_index = None
+        self._engine = None
+        self._engine_key = None
+        self._grid_key = None
+        self._target_key = None
+        self._enc_key = None
+
+    # ---- engine binding (shared with Siren; these hooks differ) ----------------------------------
+    def set_scratch_format(self, fmt: int):
+        """FourierNet has one scratch format (16-bit); nothing to switch."""
+
+    def _param_list(self):
+        out = []
+        for m in self.layers:
+            if isinstance(m, nn.Linear):
+                out += [m.weight, m.bias]
+        return out
+
+    def _new_engine(self, H: int, w: int, row_begin: int, row_end: int, device: int):
+        from .._engine import FourierEngine
+        c = self.cfg
+        self._enc_key = None
+        return FourierEngine(H, w, self._engine_width, c["n_linear"], c["map_size"], c["output_size"], device=device,
+                             chunk_pixels=c["chunk_pixels"], betas=self._adam[0], eps=self._adam[1])
+
+    def engine(self, grid: torch.Tensor, img=None, row_begin: int = 0, row_end: int = 0, full_height=None):
+        if row_begin or (row_end and row_end != grid.shape[0]) or (full_height and full_height != grid.shape[0]):
+            raise NotImplementedError("pixel-split (row ranges) is not supported for FourierNet")
+        eng = super().engine(grid, img)
+        B = self.encoding.B
+        key = (id(eng), B.data_ptr(), B._version)
+        if self._enc_key != key:
+            eng.set_encoding(B.data.to(eng.device, torch.float32))
+            self._enc_key = key
+        return eng
+
+    def _padded_index(self, device):
+        if self._pad_index is None or self._pad_index.device != device:
+            c, wp = self.cfg, self._engine_width
+            idx, off = [], 0
+            for l in range(c["n_linear"]):
+                last = l == c["n_linear"] - 1
+                fin = c["map_size"] if l == 0 else c["hidden_size"]
+                fout = c["output_size"] if last else c["hidden_size"]
+                fin_p = c["map_size"] if l == 0 else wp
+                fout_p = c["output_size"] if last else wp
+                r = torch.arange(fout, device=device)[:, None] * fin_p + torch.arange(fin, device=device)[None, :]
+                idx.append((off + r).reshape(-1))
+                off += fin_p * fout_p
+                idx.append(off + torch.arange(fout, device=device))
+                off += fout_p
+            self._pad_index = torch.cat(idx)
+        return self._pad_index
+
+    def __deepcopy__(self, memo):
+        c = self.cfg
+        new = FourierNet(c["input_size"], c["output_size"], c["depth"], c["hidden_size"], c["map_size"], c["map_scale"],
+                         compute_dtype=c["compute_dtype"], chunk_pixels=c["chunk_pixels"])
+        new.to(next(self.parameters()).device)
+        new._adam = self._adam
+        with torch.no_grad():
+            for a, b in zip(new._param_list(), self._param_list()):
+                a.copy_(b)
+            new.encoding.B.copy_(self.encoding.B)
+        new.train(self.training)
+        return new
+
+    def forward(self, grid: torch.Tensor) -> torch.Tensor:
+        """[H, W, 2] grid -> [H, W, 3] prediction in [0, 1] (reference fourier.py:63-72)."""
+        pred, _ = self.engine(grid).forward(want_pred=True, want_sse=False)
+        return pred

@@ -104,14 +104,12 @@ class Siren(nn.Module):
     def engine(self, grid: torch.Tensor, img: Optional[torch.Tensor] = None, row_begin: int = 0, row_end: int = 0,
                full_height: Optional[int] = None):
         """Engine bound to this model for `grid` (created on first use / when the image size changes)."""
-        from .._engine import SirenEngine
         if not grid.is_cuda:
             raise RuntimeError("Siren runs on the gfx950 engine only: move model, grid and image to 'cuda'")
         h, w, _ = grid.shape
         H = full_height or h
         key = (H, w, row_begin, row_end, grid.device.index, self._adam, self.cfg["scratch_format"])
         if self._engine is None or self._engine_key != key:
-            c = self.cfg
             carry = None
             if self._engine is not None:
                 old = self._engine
@@ -119,11 +117,7 @@ class Siren(nn.Module):
                 masks = old.view("masks").clone() if getattr(self, "_has_engine_mask", False) else None
                 carry = (m, v, st, masks, old.num_params, (old.height, old.width, old.row_begin, old.row_end))
                 self._unbind()
-            self._engine = SirenEngine(H, w, self._engine_width, c["depth"], c["first_omega_0"], c["hidden_omega_0"],
-                                       c["outermost_linear"], c["output_size"], c["compute_dtype"],
-                                       device=grid.device.index or 0, row_begin=row_begin, row_end=row_end,
-                                       chunk_pixels=c["chunk_pixels"], betas=self._adam[0], eps=self._adam[1],
-                                       scratch_format=c["scratch_format"])
+            self._engine = self._new_engine(H, w, row_begin, row_end, grid.device.index or 0)
             self._engine_key, self._grid_key, self._target_key = key, None, None
             new = self._engine
             if carry is not None and carry[4] == new.num_params and carry[5] == (new.height, new.width, new.row_begin, new.row_end):
@@ -155,6 +149,15 @@ class Siren(nn.Module):
             cb()
         self._sync_to_engine()
         return eng
+
+    def _new_engine(self, H: int, w: int, row_begin: int, row_end: int, device: int):
+        from .._engine import SirenEngine
+        c = self.cfg
+        return SirenEngine(H, w, self._engine_width, c["depth"], c["first_omega_0"], c["hidden_omega_0"],
+                           c["outermost_linear"], c["output_size"], c["compute_dtype"],
+                           device=device, row_begin=row_begin, row_end=row_end,
+                           chunk_pixels=c["chunk_pixels"], betas=self._adam[0], eps=self._adam[1],
+                           scratch_format=c["scratch_format"])
 
     def _padded_index(self, device):
         """flat index of every logical parameter element inside the engine's (wider) flat layout"""

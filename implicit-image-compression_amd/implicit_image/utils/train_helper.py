@@ -109,6 +109,8 @@ def setup_mask(model: Module, optim: Optimizer, masking_cfg=None) -> Masking:
     """Masking instance wrapping `model`, or None for dense fits (reference :89-129)."""
     if not masking_cfg or _cfg_get(masking_cfg, "dense"):
         return None
+    if getattr(model, "mask_unsupported", None):      # FourierNet: the reference itself fails here (models/fourier.py)
+        raise NotImplementedError(model.mask_unsupported)
     schedule = _cfg_get(masking_cfg, "decay_schedule")
     if schedule not in decay_registry:
         raise NotImplementedError(f"decay_schedule '{schedule}' is outside the accelerated RigL path")

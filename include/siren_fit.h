@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 2
+#define SF_ABI_VERSION 3   /* 3: FourierNet handles (sf_fourier_create, sf_set_encoding) */
 
 typedef enum sf_status {
   SF_OK = 0,
@@ -84,9 +84,32 @@ typedef struct sf_config {
 
 typedef struct sf_engine sf_handle;
 
+/* FourierNet (reference implicit_image/models/fourier.py): encoding [sin(2 pi x B), cos(2 pi x B)] of width map_size,
+ * then Linear(map_size, hidden) + ReLU, (n_linear - 2) x [Linear(hidden, hidden) + ReLU], Linear(hidden, 3) + Sigmoid.
+ * The handle is an ordinary sf_handle: every call below works on it, with these differences
+ *   - the flat parameter vector holds the Linear layers only (layers.{2l}.weight, layers.{2l}.bias); encoding.B is frozen
+ *     and goes in through sf_set_encoding, once per bind, before the first pass;
+ *   - sf_scratch_format reports 16; sf_debug_scratch returns SF_ERR_INVALID; the whole image is fitted (no pixel split). */
+typedef struct sf_fourier_config {
+  int32_t abi_version;      /* SF_ABI_VERSION                              */
+  int32_t height, width;    /* image H, W: the loss mean is over 3*H*W     */
+  int32_t in_features;      /* 2                                           */
+  int32_t out_features;     /* 3                                           */
+  int32_t map_size;         /* 64, 128, 256 or 512 (fourier.py:13)         */
+  int32_t hidden;           /* 32, 64, 128 or 256 (Small_Dense widths: zero-pad on the host) */
+  int32_t n_linear;         /* Linear layers, 2..12 (depth 8 of conf/mlp/fourier.yaml = 7)  */
+  int32_t compute_dtype;    /* SF_F16 only                                 */
+  float beta1, beta2, eps;  /* Adam                                        */
+  int32_t device;           /* HIP device ordinal                          */
+  void* stream;             /* hipStream_t (NULL = null stream)            */
+  int64_t chunk_pixels;     /* pixels per kernel sweep (0 = auto)          */
+} sf_fourier_config;
+
 /* lifecycle */
 int sf_create(const sf_config* cfg, sf_handle** out);
 int sf_destroy(sf_handle* h);
+int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out);
+int sf_set_encoding(sf_handle* h, const float* B_dev /* [in_features][map_size/2] fp32, copied */);
 const char* sf_last_error(void);            /* thread-local message of the last failure */
 int sf_abi_version(void);
 
