@@ -12,12 +12,14 @@
 #include "siren_wide.hip"
 #include "siren_kmeans.hip"
 #include "fourier_kernels.hip"
+#include "feather_kernels.hip"
 
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <new>
@@ -60,9 +62,12 @@ static constexpr float kResScale = 1024.0f;
 
 // (k_bwd_layer1: the backward of layer 1, whose input phases are re-derived from the coordinates - another kernel form than
 //  the hidden layers', so it gets its own line in the per-kernel report)
-enum KernelId { K_FWD = 0, K_BWD_HIDDEN, K_BWD_LAST, K_DW_FIRST, K_REDUCE, K_SSE, K_ADAM, K_IMAGES, K_BWD_L1, K_COUNT };
+// (k_feather_*: the Feathermap update of sf_adam_step on a handle with sf_feather_attach, feather_kernels.hip)
+enum KernelId { K_FWD = 0, K_BWD_HIDDEN, K_BWD_LAST, K_DW_FIRST, K_REDUCE, K_SSE, K_ADAM, K_IMAGES, K_BWD_L1,
+                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_COUNT };
 static const char* kKernelNames[K_COUNT] = {"k_fwd",    "k_bwd_hidden", "k_bwd_last", "k_dw_first",
-                                            "k_reduce", "k_sse",        "k_adam",     "k_images", "k_bwd_layer1"};
+                                            "k_reduce", "k_sse",        "k_adam",     "k_images", "k_bwd_layer1",
+                                            "k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat"};
 
 struct ProfRec {
   int id;
@@ -159,6 +164,16 @@ struct sf_engine {
   long ff_img_f[kFfMaxLinear] = {0}, ff_img_b[kFfMaxLinear] = {0}, ff_img_n = 0;   // offsets / size in 16-byte units
   _Float16 *ffH = nullptr, *ffG = nullptr, *ffZ = nullptr;   // [D-1][WD][chunk] ReLU outputs, gradients; [3][chunk] dL/dz
   int ff_dw_wgs = 0;            // max weight-gradient workgroups along the pixels (slab rows)
+  // Feathermap (sf_feather_attach, feather_kernels.hip): the weights are materialised from [V1 | V2 | scalers], and
+  // sf_adam_step runs adjoint -> Adam on the feather vector -> materialise instead of Adam on W
+  bool feather = false;
+  bool fth_fresh = false;       // fth_g holds the adjoint of the current dL/dW (cleared by every training pass)
+  FthArgs fth;
+  long fth_nf = 0;              // 2 n m + 2 D
+  float *fth_p = nullptr, *fth_g = nullptr, *fth_m = nullptr, *fth_v = nullptr;
+  float *fth_V = nullptr, *fth_G = nullptr, *fth_part = nullptr;
+  long* fth_chunks = nullptr;
+  int* fth_chunk0 = nullptr;
 };
 
 namespace {
@@ -1001,6 +1016,7 @@ int run_pass_fourier(sf_engine* h, bool train, float* pred, bool want_sse) {
 }
 
 int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
+  if (train) h->fth_fresh = false;
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   if ((train || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
   if (h->fourier) return run_pass_fourier(h, train, pred, want_sse);
@@ -1180,6 +1196,38 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
 int read_sse(sf_engine* h, double* out) {
   HIPCHK(hipMemcpyAsync(out, h->sse_dev, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return SF_OK;
+}
+
+// Feathermap: V = V1 V2 and W = scaler * V into the engine's flat parameters; the weight images follow at the next
+// refresh_images
+int feather_materialise(sf_engine* h) {
+  const FthArgs& a = h->fth;
+  const dim3 grid((unsigned)((a.rows_used + kFthTile - 1) / kFthTile), (unsigned)((a.n + kFthTile - 1) / kFthTile));
+  Launch L(h, K_FTH_MAT, 2.0 * a.rows_used * a.n * a.m, 4.0 * (2.0 * a.n * a.m + 2.0 * a.P));
+  hipLaunchKernelGGL(k_fth_mat, grid, dim3(256), 0, h->stream, a);
+  L.done();
+  HIPCHK(hipGetLastError());
+  h->images_dirty = true;
+  return SF_OK;
+}
+
+// Feathermap adjoint of the engine's dense gradient: dV1, dV2 and dscaler into fth_g (two launches)
+int feather_adjoint(sf_engine* h) {
+  const FthArgs& a = h->fth;
+  {
+    Launch L(h, K_FTH_GRAD, 2.0 * a.P, 4.0 * 4.0 * a.P);
+    hipLaunchKernelGGL(k_fth_grad, dim3((unsigned)(a.g_blocks + a.nchunks)), dim3(256), 0, h->stream, a);
+    L.done();
+  }
+  {
+    const int t2 = (a.m + kFthTile - 1) / kFthTile * a.t2n;
+    Launch L(h, K_FTH_DV, 2.0 * (double)a.n * a.m * (a.n + a.rows_used), 4.0 * ((double)a.n * a.n + 4.0 * a.n * a.m));
+    hipLaunchKernelGGL(k_fth_dv, dim3((unsigned)(a.t1 + t2 + 1)), dim3(256), 0, h->stream, a);
+    L.done();
+  }
+  HIPCHK(hipGetLastError());
+  h->fth_fresh = true;
   return SF_OK;
 }
 
@@ -1508,7 +1556,8 @@ int sf_destroy(sf_handle* h) try {
   void* ptrs[] = {h->params, h->grads, h->m, h->v, h->mask, h->wf, h->wf_last, h->wb, h->wb_last, h->l0tab, h->l0img,
                   h->gh, h->gw, h->Pbuf, h->Dbuf, h->Dlast, h->slab, h->sse_part, h->biasw, h->Abuf,
                   h->sse_dev, h->scale_dev, h->pad8, h->km_ws, h->wf16, h->wf16_last, h->l0img16, h->lsc,
-                  h->ffB, h->ffimg, h->ffH, h->ffG, h->ffZ};
+                  h->ffB, h->ffimg, h->ffH, h->ffG, h->ffZ, h->fth_p, h->fth_g, h->fth_m, h->fth_v, h->fth_V, h->fth_G,
+                  h->fth_part, h->fth_chunks, h->fth_chunk0};
   for (void* p : ptrs) if (p) hipFree(p);
   if (h->gexec) hipGraphExecDestroy(h->gexec);
   if (h->gstream) { hipStreamSynchronize(h->gstream); hipStreamDestroy(h->gstream); hipEventDestroy(h->gev_in); hipEventDestroy(h->gev_out); }
@@ -1554,7 +1603,10 @@ int sf_set_params(sf_handle* h, const float* p) try {
 } SF_CATCH
 int sf_get_params(sf_handle* h, float* p) try { return copy_out(h, p, h ? h->params : nullptr); } SF_CATCH
 int sf_get_grads(sf_handle* h, float* p) try { return copy_out(h, p, h ? h->grads : nullptr); } SF_CATCH
-int sf_set_grads(sf_handle* h, const float* p) try { return copy_in(h, h ? h->grads : nullptr, p); } SF_CATCH
+int sf_set_grads(sf_handle* h, const float* p) try {
+  if (h) h->fth_fresh = false;
+  return copy_in(h, h ? h->grads : nullptr, p);
+} SF_CATCH
 // layer strides of the phase / delta scratch for the handle's current format
 static void set_scratch_strides(sf_engine* h) {
   const long chunk = h->chunk_px;
@@ -1595,6 +1647,7 @@ int sf_set_masks(sf_handle* h, const float* p) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
   DevGuard dev_guard(h->cfg.device);
   if (!p) { h->has_mask = false; return SF_OK; }
+  if (h->feather) return fail(SF_ERR_INVALID, "sf_set_masks: a Feathermap handle is dense (masking.dense: True)");
   if (h->fmt_auto && h->cfg.scratch_format != 16) {
     const int rs = switch_scratch_format(h, 16);
     if (rs) return rs;
@@ -1726,6 +1779,17 @@ int sf_adam_step(sf_handle* h, float lr) try {
   const double bc2 = 1.0 - pow(h->beta2_d, (double)h->step);
   a.step_size = (float)((double)lr / bc1);
   a.bc2_sqrt = (float)sqrt(bc2);
+  if (h->feather) {   // adjoint -> Adam on [V1 | V2 | scalers] -> materialise: four launches
+    if (!h->fth_fresh) { const int rc = feather_adjoint(h); if (rc) return rc; }
+    a.p = h->fth_p; a.g = h->fth_g; a.m = h->fth_m; a.v = h->fth_v; a.mask = nullptr; a.n = h->fth_nf;
+    Launch L(h, K_FTH_ADAM, 0, (double)h->fth_nf * 28);
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)((h->fth_nf + 255) / 256)), dim3(256), 0, h->stream, a);
+    L.done();
+    HIPCHK(hipGetLastError());
+    const int rc = feather_materialise(h);
+    if (rc) return rc;
+    return refresh_images(h);
+  }
   Launch L(h, K_ADAM, 0, (double)h->P * 28);
   hipLaunchKernelGGL(k_adam, dim3((unsigned)((h->P + 255) / 256)), dim3(256), 0, h->stream, a);
   L.done();
@@ -1918,6 +1982,111 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
                        (const KmWs*)h->km_ws, (long long*)labels_dev, new_weight_dev);
   HIPCHK(hipGetLastError());
   return SF_OK;
+} SF_CATCH
+
+// ---- Feathermap (structured multi-hashing, feather_kernels.hip) ---------------------------------------------------
+int sf_feather_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, const int32_t* logical_out,
+                      const int32_t* logical_in) try {
+  if (!h || !logical_out || !logical_in) return fail(SF_ERR_INVALID, "null argument");
+  if (h->fourier) return fail(SF_ERR_INVALID, "sf_feather_attach: Feathermap runs on SIREN handles only");
+  if (h->feather) return fail(SF_ERR_INVALID, "sf_feather_attach: the handle already has a feather state");
+  if (h->cfg.row_begin != 0 || h->cfg.row_end != h->cfg.height)
+    return fail(SF_ERR_INVALID, "sf_feather_attach: Feathermap fits the whole image (no pixel split)");
+  if (h->has_mask) return fail(SF_ERR_INVALID, "sf_feather_attach: the handle has a mask (Feathermap is dense)");
+  if (n_layers != h->D) return fail(SF_ERR_INVALID, "sf_feather_attach: n_layers must equal the handle's depth");
+  FthArgs a;
+  memset(&a, 0, sizeof(a));
+  const int D = h->D;
+  long P = 0;
+  for (int l = 0; l < D; ++l) {
+    const int in_p = l == 0 ? h->cfg.in_features : h->WD, out_p = l == D - 1 ? h->cfg.out_features : h->WD;
+    const int in = logical_in[l], outn = logical_out[l];
+    if (in < 1 || outn < 1 || in > in_p || outn > out_p || (l == 0 && in != in_p) || (l == D - 1 && outn != out_p))
+      return fail(SF_ERR_INVALID, "sf_feather_attach: logical layer sizes do not fit the handle");
+    a.seg.start[2 * l] = P; a.seg.base[2 * l] = h->off_w[l]; a.seg.cols[2 * l] = in; a.seg.stride[2 * l] = in_p;
+    P += (long)in * outn;
+    a.seg.start[2 * l + 1] = P; a.seg.base[2 * l + 1] = h->off_b[l]; a.seg.cols[2 * l + 1] = outn;
+    a.seg.stride[2 * l + 1] = outn;
+    P += outn;
+  }
+  a.seg.nseg = 2 * D;
+  a.seg.start[2 * D] = P;
+  if (n < 1 || m < 1 || n > 46340 || m > n || n * n < P)
+    return fail(SF_ERR_INVALID, "sf_feather_attach: need 1 <= m <= n <= 46340 and n^2 >= the parameter count");
+  a.n = (int)n; a.m = (int)m; a.P = P;
+  a.rows_used = (int)((P + n - 1) / n);
+  std::vector<long> chunks;
+  std::vector<int> chunk0;
+  for (int k = 0; k < a.seg.nseg; ++k) {
+    chunk0.push_back((int)(chunks.size() / 3));
+    for (long b = a.seg.start[k]; b < a.seg.start[k + 1]; b += kFthChunk) {
+      chunks.push_back(k); chunks.push_back(b); chunks.push_back(std::min(b + kFthChunk, a.seg.start[k + 1]));
+    }
+  }
+  chunk0.push_back((int)(chunks.size() / 3));
+  a.nchunks = (int)(chunks.size() / 3);
+  a.g_blocks = (int)std::min<long>((P + 255) / 256, 8L * h->dw_wg);
+  a.t1n = (a.m + kFthTile - 1) / kFthTile;
+  a.t1 = (a.n + kFthTile - 1) / kFthTile * a.t1n;
+  a.t2n = (a.n + kFthTile - 1) / kFthTile;
+  const long nf = 2 * n * m + 2L * D;
+  DevGuard dev_guard(h->cfg.device);
+  float *fp = nullptr, *fg = nullptr, *fm = nullptr, *fv = nullptr, *fV = nullptr, *fG = nullptr, *fpart = nullptr;
+  long* fch = nullptr;
+  int* fc0 = nullptr;
+  bool ok = hipMalloc((void**)&fp, nf * 4) == hipSuccess && hipMalloc((void**)&fg, nf * 4) == hipSuccess &&
+            hipMalloc((void**)&fm, nf * 4) == hipSuccess && hipMalloc((void**)&fv, nf * 4) == hipSuccess &&
+            hipMalloc((void**)&fV, P * 4) == hipSuccess && hipMalloc((void**)&fG, n * n * 4) == hipSuccess &&
+            hipMalloc((void**)&fpart, (size_t)a.nchunks * 4) == hipSuccess &&
+            hipMalloc((void**)&fch, chunks.size() * sizeof(long)) == hipSuccess &&
+            hipMalloc((void**)&fc0, chunk0.size() * sizeof(int)) == hipSuccess;
+  if (!ok) {
+    void* ps[] = {fp, fg, fm, fv, fV, fG, fpart, fch, fc0};
+    for (void* q : ps) if (q) hipFree(q);
+    (void)hipGetLastError();
+    return fail(SF_ERR_NOMEM, "hipMalloc failed (feather state)");
+  }
+  h->fth_p = fp; h->fth_g = fg; h->fth_m = fm; h->fth_v = fv; h->fth_V = fV; h->fth_G = fG; h->fth_part = fpart;
+  h->fth_chunks = fch; h->fth_chunk0 = fc0;
+  HIPCHK(hipMemcpy(fch, chunks.data(), chunks.size() * sizeof(long), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(fc0, chunk0.data(), chunk0.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(fp, 0, nf * 4, h->stream)); HIPCHK(hipMemsetAsync(fg, 0, nf * 4, h->stream));
+  HIPCHK(hipMemsetAsync(fm, 0, nf * 4, h->stream)); HIPCHK(hipMemsetAsync(fv, 0, nf * 4, h->stream));
+  HIPCHK(hipMemsetAsync(fV, 0, P * 4, h->stream)); HIPCHK(hipMemsetAsync(fG, 0, n * n * 4, h->stream));
+  HIPCHK(hipMemsetAsync(h->params, 0, h->P * 4, h->stream));   // padded slots stay exactly 0
+  a.fp = fp; a.fg = fg; a.V = fV; a.G = fG; a.W = h->params; a.dW = h->grads;
+  a.chunks = fch; a.seg_chunk0 = fc0; a.part = fpart;
+  h->fth = a;
+  h->fth_nf = nf;
+  h->feather = true;
+  h->fth_fresh = false;
+  if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }   // a captured step holds the dense Adam
+  h->images_dirty = true;
+  return SF_OK;
+} SF_CATCH
+
+int sf_feather_state_ptr(sf_handle* h, int32_t which, float** dev_ptr, int64_t* len) try {
+  if (!h || !dev_ptr) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->feather) return fail(SF_ERR_STATE, "sf_feather_state_ptr: no feather state (sf_feather_attach)");
+  float* ps[] = {h->fth_p, h->fth_g, h->fth_m, h->fth_v, h->fth_V};
+  if (which < 0 || which > 4) return fail(SF_ERR_INVALID, "bad feather state selector");
+  *dev_ptr = ps[which];
+  if (len) *len = which == 4 ? h->fth.P : h->fth_nf;
+  return SF_OK;
+} SF_CATCH
+
+int sf_feather_materialise(sf_handle* h) try {
+  if (!h) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->feather) return fail(SF_ERR_STATE, "sf_feather_materialise: no feather state (sf_feather_attach)");
+  DevGuard dev_guard(h->cfg.device);
+  return feather_materialise(h);
+} SF_CATCH
+
+int sf_feather_adjoint(sf_handle* h) try {
+  if (!h) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->feather) return fail(SF_ERR_STATE, "sf_feather_adjoint: no feather state (sf_feather_attach)");
+  DevGuard dev_guard(h->cfg.device);
+  return feather_adjoint(h);
 } SF_CATCH
 
 /* test aid: throws inside the boundary on purpose (0: std::bad_alloc, 1: std::runtime_error, 2: a non-std exception) */

@@ -87,12 +87,29 @@ def load_library():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
+    # Feathermap entry points: bound only when present, so a library built before them still loads (FeatherNet then
+    # fails with a message naming the rebuild instead of the whole engine failing)
+    feather = {
+        "sf_feather_attach": [H, I64, I64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+        "sf_feather_state_ptr": [H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(I64)],
+        "sf_feather_materialise": [H], "sf_feather_adjoint": [H],
+    }
+    for name, args in feather.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
     lib.sf_last_error.argtypes = []
     lib.sf_last_error.restype = C.c_char_p
     if lib.sf_abi_version() != SF_ABI_VERSION:
         raise RuntimeError("libsiren_fit.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def has_feather(lib) -> bool:
+    return all(hasattr(lib, s) for s in ("sf_feather_attach", "sf_feather_state_ptr", "sf_feather_materialise",
+                                         "sf_feather_adjoint"))
 
 
 def exported_symbols() -> Sequence[str]:
@@ -283,6 +300,43 @@ class SirenEngine:
         _check(self.lib.sf_step(self.h, arr, n, out))
         return list(out) if want_loss else None
 
+    # ---- Feathermap (sf_feather_*) ----------------------------------------------------------
+    FEATHER = {"params": 0, "grads": 1, "exp_avg": 2, "exp_avg_sq": 3, "V": 4}
+
+    def feather_attach(self, n: int, m: int, logical_out: Sequence[int], logical_in: Sequence[int]):
+        if not has_feather(self.lib):
+            raise RuntimeError(f"{_LIB_PATH} has no sf_feather_* entry points (built before Feathermap): rebuild it with "
+                               "`python __graft_entry__.py build`")
+        D = len(logical_out)
+        outs, ins = (C.c_int32 * D)(*logical_out), (C.c_int32 * D)(*logical_in)
+        _check(self.lib.sf_feather_attach(self.h, n, m, D, outs, ins))
+
+    def feather_view(self, which: str) -> torch.Tensor:
+        """Flat fp32 view (no copy) of the feather state: params | grads | exp_avg | exp_avg_sq ([V1 | V2 | scalers]),
+        or V (the unscaled V[0, P) of the last materialisation)."""
+        key = "feather/" + which
+        if key not in self._views:
+            p, n = C.c_void_p(), C.c_int64()
+            _check(self.lib.sf_feather_state_ptr(self.h, self.FEATHER[which], C.byref(p), C.byref(n)))
+            self._views[key] = torch.as_tensor(_DevView(p.value, n.value), device=self.device)
+        return self._views[key]
+
+    def feather_materialise(self):
+        _check(self.lib.sf_feather_materialise(self.h))
+
+    def feather_adjoint(self):
+        _check(self.lib.sf_feather_adjoint(self.h))
+
+    @property
+    def adam_steps(self) -> int:
+        step = C.c_int64()
+        _check(self.lib.sf_get_adam_state(self.h, None, None, C.byref(step)))
+        return step.value
+
+    @adam_steps.setter
+    def adam_steps(self, step: int):
+        _check(self.lib.sf_set_adam_state(self.h, None, None, int(step)))
+
     def set_graph_replay(self, on: bool):
         """step(): replay a captured hipGraph per training step instead of launching kernel by kernel"""
         _check(self.lib.sf_set_graph_replay(self.h, int(on)))
@@ -337,3 +391,21 @@ class FourierEngine(SirenEngine):
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
         _check(self.lib.sf_set_encoding(self.h, _f32_cuda(B.detach().contiguous(), 2 * (self.map_size // 2)).data_ptr()))
+
+
+class FeatherEngine:
+    """A SIREN handle with a feather state (sf_feather_attach), as the optimiser seams see it: view('params' | 'grads' |
+    'exp_avg' | 'exp_avg_sq') are the feather vector [V1 | V2 | scalers] and its gradient and Adam moments, so EngineAdam
+    binds to them unchanged.  Everything else (forward, step, adam_step, profile, dense views through .base) is the
+    SirenEngine's."""
+
+    def __init__(self, base: SirenEngine):
+        self.base = base
+
+    def __getattr__(self, name):
+        return getattr(self.base, name)
+
+    def view(self, which: str) -> torch.Tensor:
+        if which in ("params", "grads", "exp_avg", "exp_avg_sq"):
+            return self.base.feather_view(which)
+        return self.base.view(which)

@@ -22,6 +22,8 @@ from .data import get_grid, load_img
 from .models import registry as model_registry
 from .parallel import shard_jobs
 from .pipeline import entropy_coding
+from .pipeline.feathermap import FeatherNet
+from .pipeline.feathermap.feathernet import DEEPCOPY_UNSUPPORTED
 from .pipeline.quant import Quantize
 from .utils.train_helper import (eval_epoch, get_device, get_optimizer_lr_scheduler, setup_mask, train_epoch,
                                  train_steps)
@@ -31,12 +33,19 @@ REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)),
 
 def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
     """One fit; returns dict(loss, PSNR, PSNR_8bit, steps, seconds)."""
+    feather = bool(cfg.get("masking") and cfg.masking.get("name") == "Feathermap")
+    if feather and cfg.mlp.name != "siren":
+        raise NotImplementedError("masking=Feathermap runs on the SIREN engine only (mlp=siren)")
+    if feather and cfg.get("quant"):
+        raise NotImplementedError(f"masking=Feathermap with quant={cfg.quant.get('name', cfg.quant)}: {DEEPCOPY_UNSUPPORTED}")
     torch.manual_seed(cfg.seed)                                                   # compress.py:58
     img = load_img(**cfg.img)                                                      # compress.py:64
     grid = get_grid(cfg.img.height, cfg.img.width)                                 # compress.py:67
     small = cfg.masking.density if (cfg.get("masking") and cfg.masking.get("name") == "Small_Dense") else 1.0
     eng_kw = dict(cfg.get("engine") or {})
     model = model_registry[cfg.mlp.name](**cfg.mlp, small_dense_density=small, **eng_kw)   # compress.py:77
+    if feather:                                                                    # compress.py:80-81
+        model = FeatherNet(model, compress=cfg.masking.density)
     model, grid, img = model.to(device), grid.to(device), img.to(device)          # compress.py:84-86
     model.train()
     optim, lr_scheduler = get_optimizer_lr_scheduler(model, cfg.optim)             # compress.py:105
@@ -70,6 +79,8 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
                 msg += f" | Prune Rate: {mask.prune_rate:.4f} | Density: {mask.stats.total_density:.4f}"
             logging.info(msg)
     last.update(steps=num_steps, seconds=time.time() - t0)
+    if feather:
+        last.update({"Stored Params": model.num_stored(), "Dense Params": model.get_num_WandB()})
     quantized_model = None
     if cfg.get("quant"):                                                           # compress.py:172-240
         qcfg = copy.deepcopy(cfg.quant)

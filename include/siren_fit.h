@@ -178,6 +178,27 @@ int sf_step(sf_handle* h, const float* lr, int32_t n_steps, float* loss_out);
  * on 256x256), so replay stays opt-in. */
 int sf_set_graph_replay(sf_handle* h, int32_t on);
 
+/* Feathermap (reference implicit_image/pipeline/feathermap/feathernet.py): structured multi-hashing of a SIREN handle.
+ * The P logical weights and biases, in flat order, are the first P entries of V = V1 V2 (V1 [n][m], V2 [m][n], fp32,
+ * row-major), each tensor k scaled by its own scalar: W_k = scaler_k * V.view(-1)[seg_k].  The feather vector is
+ * [V1 | V2 | scaler of layers.0.weight, layers.0.bias, layers.1.weight, ...], length 2 n m + 2 depth (the reference's
+ * named_parameters() order).  After sf_feather_attach
+ *   - sf_adam_step (and with it sf_step and graph replay) runs adjoint -> Adam on the feather vector -> materialise, in four
+ *     launches; sf_get_grads still returns dL/dW of the last pass;
+ *   - sf_set_masks with a mask returns SF_ERR_INVALID (Feathermap is dense), as does attaching to a pixel-split or
+ *     FourierNet handle;
+ *   - the parameters are W: sf_feather_materialise rewrites them from the feather vector (padded slots stay 0). */
+/* logical_out / logical_in [n_layers]: each Linear's logical size (a width the engine zero-pads maps onto strided rows) */
+int sf_feather_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, const int32_t* logical_out,
+                      const int32_t* logical_in);
+/* which: 0 feather params, 1 grads, 2 exp_avg, 3 exp_avg_sq (length 2nm + 2 depth), 4 unscaled V[0, P) of the last
+ * materialisation (length P) */
+int sf_feather_state_ptr(sf_handle* h, int32_t which, float** dev_ptr, int64_t* len);
+/* V = V1 V2 and W = scaler * V into the parameters (call after editing the feather vector; enqueued, no sync) */
+int sf_feather_materialise(sf_handle* h);
+/* dV1, dV2 and the scalar gradients from the current dL/dW into the feather gradient (sf_adam_step reuses them) */
+int sf_feather_adjoint(sf_handle* h);
+
 /* measurement: per-kernel HIP-event timing on the handle's stream */
 int sf_profile_enable(sf_handle* h, int32_t on);
 int sf_profile_reset(sf_handle* h);
