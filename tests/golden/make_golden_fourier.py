@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Golden vectors for FourierNet (mlp=fourier), minted by running the REAL reference on the CPU.
 
-    python tests/golden/make_golden_fourier.py [init] [grads] [plateau]
+    python tests/golden/make_golden_fourier.py [init] [grads] [plateau] [shapes]
 
 The reference's implicit_image/models/fourier.py is imported by file path and trained with its own
 train_epoch (utils/train_helper.py:132-185), with the stubs of make_golden_masking.py.  Data only:
@@ -13,6 +13,9 @@ train_epoch (utils/train_helper.py:132-185), with the stubs of make_golden_maski
   fourier_plateau.npz    yaml model, 300 steps of train_epoch with Adam lr 3e-4 on the 256x256 synthetic_image (seed 5)
                          and nonsmooth_image: loss curve and final eval PSNR, with 8 and with 2 torch threads (the
                          reference's own run-to-run spread)
+  fourier_shapes.npz     for every model of SHAPES (the widths, map sizes, depths and Small_Dense paddings the two
+                         models above leave out), seed 0: sha256 of every init tensor (pins the draw order), and on a
+                         ragged 24x20 grid (synthetic_image seed 5) prediction, loss and per-tensor gradient norms
 """
 import hashlib
 import importlib.util
@@ -30,6 +33,15 @@ OUT = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(OUT))
 YAML = dict(depth=8, hidden_size=128, map_size=256, map_scale=16.0)
 SMALL = dict(depth=4, hidden_size=64, map_size=128, map_scale=10.0)
+# tag -> FourierNet kwargs; tests/_fourier_shapes_child.py runs the same table on the engine
+SHAPES = {
+    "h32_m64_d3": dict(depth=3, hidden_size=32, map_size=64, map_scale=10.0),
+    "h45p_m512_d13": dict(depth=13, hidden_size=64, map_size=512, map_scale=10.0, small_dense_density=0.5),
+    "h128_m512_d4": dict(depth=4, hidden_size=128, map_size=512, map_scale=10.0),
+    "h256_m256_d4": dict(depth=4, hidden_size=256, map_size=256, map_scale=10.0),
+    "h256_m512_d8": dict(depth=8, hidden_size=256, map_size=512, map_scale=16.0),
+    "h198p_m64_d5": dict(depth=5, hidden_size=256, map_size=64, map_scale=10.0, small_dense_density=0.6),
+}
 
 
 def _stub(name, **attrs):
@@ -95,6 +107,26 @@ def make_grads(fourier, so):
     np.savez(os.path.join(OUT, "fourier_grads.npz"), **out)
 
 
+def make_shapes(fourier, so):
+    H, W = 24, 20
+    img, grid = so.synthetic_image(H, W, seed=5), so.get_grid(H, W)
+    out = {"tags": np.array(list(SHAPES))}
+    for tag, kw in SHAPES.items():
+        m = model(fourier, 0, **kw)
+        for n, p in m.state_dict().items():
+            out[f"{tag}/sha/{n}"] = np.array(sha(p))
+        out[f"{tag}/names"] = np.array(list(m.state_dict()))
+        pred = m(grid)
+        loss = F.mse_loss(pred, img)
+        loss.backward()
+        out[f"{tag}/pred"] = pred.detach().numpy()
+        out[f"{tag}/loss"] = np.float64(loss.item())
+        for n, p in m.named_parameters():
+            if p.grad is not None:
+                out[f"{tag}/gradnorm/{n}"] = np.float64(p.grad.double().norm().item())
+    np.savez_compressed(os.path.join(OUT, "fourier_shapes.npz"), **out)
+
+
 def make_plateau(th, fourier, so, steps=300):
     S = 256
     grid = so.get_grid(S, S)
@@ -115,12 +147,14 @@ def make_plateau(th, fourier, so, steps=300):
 
 def main():
     th, fourier, so = _ref()
-    what = set(sys.argv[1:]) or {"init", "grads", "plateau"}
+    what = set(sys.argv[1:]) or {"init", "grads", "plateau", "shapes"}
     torch.set_num_threads(8)
     if "init" in what:
         make_init(fourier)
     if "grads" in what:
         make_grads(fourier, so)
+    if "shapes" in what:
+        make_shapes(fourier, so)
     if "plateau" in what:
         make_plateau(th, fourier, so)
 
