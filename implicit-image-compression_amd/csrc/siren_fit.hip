@@ -13,6 +13,7 @@
 #include "siren_kmeans.hip"
 #include "fourier_kernels.hip"
 #include "feather_kernels.hip"
+#include "wavelet_kernels.hip"
 
 #include <math.h>
 #include <stdio.h>
@@ -64,10 +65,12 @@ static constexpr float kResScale = 1024.0f;
 //  the hidden layers', so it gets its own line in the per-kernel report)
 // (k_feather_*: the Feathermap update of sf_adam_step on a handle with sf_feather_attach, feather_kernels.hip)
 enum KernelId { K_FWD = 0, K_BWD_HIDDEN, K_BWD_LAST, K_DW_FIRST, K_REDUCE, K_SSE, K_ADAM, K_IMAGES, K_BWD_L1,
-                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_COUNT };
+                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_COUNT };
+// (k_wv_*: the image-space composition of a WaveletSiren handle and its adjoint, wavelet_kernels.hip)
 static const char* kKernelNames[K_COUNT] = {"k_fwd",    "k_bwd_hidden", "k_bwd_last", "k_dw_first",
                                             "k_reduce", "k_sse",        "k_adam",     "k_images", "k_bwd_layer1",
-                                            "k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat"};
+                                            "k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat",
+                                            "k_wv_compose", "k_wv_adjoint", "k_wv_inject"};
 
 struct ProfRec {
   int id;
@@ -174,6 +177,17 @@ struct sf_engine {
   float *fth_V = nullptr, *fth_G = nullptr, *fth_part = nullptr;
   long* fth_chunks = nullptr;
   int* fth_chunk0 = nullptr;
+  // WaveletSiren (sf_wavelet_create, wavelet_kernels.hip): two SIREN sub-handles whose parameter, gradient, moment and
+  // mask buffers are slices of this handle's; this handle owns the composition, the loss and the optimiser
+  bool wavelet = false;
+  sf_engine* wv_sub[2] = {nullptr, nullptr};   // LF, HF
+  bool borrowed_state = false;  // sub-handle: params / grads / m / v / mask belong to the WaveletSiren handle
+  bool ext_dout = false;        // sub-handle: the training forward runs without a target, dL/dout comes from k_wv_adjoint
+  int wv_n = 0;                 // coefficient side
+  float wv_up = 0.f;            // bilinear source-index scale
+  float* wv_pred = nullptr;     // [2][n*n][3] sub-network predictions
+  float* wv_g = nullptr;        // [H*H][3] dL/d(Y, Cb, Cr)
+  float* wv_gl = nullptr;       // two-pass only: [2][n*n][3] fp32 dL/dout of the sub-networks
 };
 
 namespace {
@@ -497,10 +511,28 @@ int launch_fwd(sf_engine* h, const FwdArgs& a, int n_super, bool train) {
 }
 int refresh_images_wide(sf_engine* h);
 int refresh_images_fourier(sf_engine* h);
+// WaveletSiren: the sub-handles launch on the handle's current stream (graph capture swaps it) and report to its profiler
+void wv_sync(sf_engine* h) {
+  for (sf_engine* s : h->wv_sub) {
+    s->stream = h->stream;
+    s->prof = h->prof;
+    s->replay = h->replay;
+  }
+}
 int refresh_images(sf_engine* h) {
   if (!h->images_dirty) return SF_OK;
   if (h->wide) return refresh_images_wide(h);
   if (h->fourier) return refresh_images_fourier(h);
+  if (h->wavelet) {   // the joint parameters changed: both sub-networks' weight images follow
+    wv_sync(h);
+    for (sf_engine* s : h->wv_sub) {
+      s->images_dirty = true;
+      const int rc = refresh_images(s);
+      if (rc) return rc;
+    }
+    h->images_dirty = false;
+    return SF_OK;
+  }
   ImgArgs a;
   memset(&a, 0, sizeof(a));
   a.params = h->params;
@@ -1015,10 +1047,16 @@ int run_pass_fourier(sf_engine* h, bool train, float* pred, bool want_sse) {
   return SF_OK;
 }
 
-int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
+int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse);
+// phases (WaveletSiren sub-handles only; every other pass runs both): bit 0 the forward of each chunk, bit 1 the backward;
+// chunks [c_begin, c_end) (c_end < 0: to the last)
+enum { kPassFwd = 1, kPassBwd = 2, kPassAll = 3 };
+int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = kPassAll, long c_begin = 0,
+             long c_end = -1) {
   if (train) h->fth_fresh = false;
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
-  if ((train || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
+  if (((train && !h->ext_dout) || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
+  if (h->wavelet) return run_pass_wavelet(h, train, pred, want_sse);
   if (h->fourier) return run_pass_fourier(h, train, pred, want_sse);
   if (train && (!h->Pbuf || !h->Dbuf)) return fail(SF_ERR_STATE, "the handle has no backward scratch");   // (never a null store on the GPU)
   if (h->wide) return run_pass_wide(h, train, pred, want_sse);
@@ -1027,7 +1065,7 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
   const int WD = h->WD, D = h->D, KS = WD / 16;
   const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
   long sse_off = 0;
-  for (long c = 0; c < n_chunks; ++c) {
+  for (long c = c_begin; c < (c_end < 0 ? n_chunks : c_end); ++c) {
     const long pix0 = c * h->chunk_px;
     long px = h->npix - pix0;
     if (px > h->chunk_px) px = h->chunk_px;
@@ -1058,14 +1096,14 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
     fa.dbg = h->sse_part + h->n_sse;   // 64 spare floats behind the partials
 #endif
     sse_off += n_fwd_wg;
-    {
+    if (phases & kPassFwd) {
       Launch L(h, K_FWD, flops_fwd_px(h) * n_pb * 32.0,
                n_pb * 32.0 * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
       rc = launch_fwd(h, fa, n_fwd_wg, train);
       L.done();
       if (rc) return rc;
     }
-    if (!train) continue;
+    if (!train || !(phases & kPassBwd)) continue;
     // backward, last layer first; every layer kernel is followed by the fixed-order slab reduction
     const int PBS = 2;   // k_dw stages two pixel blocks at a time; k_bwd accepts any block count
     int n_wg = (int)((n_pb + PBS - 1) / PBS);
@@ -1183,9 +1221,84 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
     }
     (void)KS;
   }
-  if (want_sse || train) {
+  if ((want_sse || train) && !h->ext_dout) {
     Launch L(h, K_SSE, 0, (double)sse_off * 4);
     hipLaunchKernelGGL(k_sse_reduce, dim3(1), dim3(256), 0, h->stream, (const float*)h->sse_part, (int)sse_off,
+                       h->sse_dev, h->replay ? h->loss_tab : h->loss_dst, (const int*)(h->replay ? h->iter_dev : h->iter_dev + 2));
+    L.done();
+    HIPCHK(hipGetLastError());
+  }
+  return SF_OK;
+}
+
+// WaveletSiren pass.  One chunk (the coefficient grid fits one sweep of the sub-networks):
+//   training forward of LF and HF (no target: phases, predictions, zero dL/dout) -> k_wv_compose -> k_wv_adjoint (dL/dout
+//   straight into both Dlast) -> the backward chain of LF, then of HF (slab reductions into each half of the gradient).
+// Two passes (more than one chunk): inference forward of both over every chunk -> compose -> adjoint into an fp32 buffer
+//   -> per chunk and sub-network: training forward, k_wv_inject, backward.
+// Then the fixed-order reduction of the compose partials into the handle's SSE.
+int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
+  int rc = refresh_images(h);   // (also points the sub-handles at the current stream)
+  if (rc) return rc;
+  wv_sync(h);
+  sf_engine* const sub[2] = {h->wv_sub[0], h->wv_sub[1]};
+  const long nn = sub[0]->npix, HH = h->npix;
+  const bool one = nn <= sub[0]->chunk_px;
+  float* const p_sub[2] = {h->wv_pred, h->wv_pred + nn * 3};
+  for (int s = 0; s < 2; ++s) {
+    rc = train && one ? run_pass(sub[s], true, p_sub[s], false, kPassFwd) : run_pass(sub[s], false, p_sub[s], false);
+    if (rc) return rc;
+  }
+  WvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.H = h->cfg.height; a.n = h->wv_n; a.up = h->wv_up;
+  a.lf = p_sub[0]; a.hf = p_sub[1];
+  a.img = h->img; a.pred = pred; a.g = train ? h->wv_g : nullptr;
+  a.sse_part = h->sse_part;
+  a.gscale = (float)(2.0 / (3.0 * h->n_total));
+  a.dscale = 0.5f * sub[0]->gpre;
+  const unsigned n_cwg = (unsigned)((HH + kWvThreads - 1) / kWvThreads);
+  {
+    Launch L(h, K_WV_COMPOSE, 0, (double)HH * 4.0 * (3.0 + (a.img ? 3.0 : 0.0) + (pred ? 3.0 : 0.0) + (train ? 3.0 : 0.0)));
+    hipLaunchKernelGGL(k_wv_compose, dim3(n_cwg), dim3(kWvThreads), 0, h->stream, a);
+    L.done();
+    HIPCHK(hipGetLastError());
+  }
+  if (train) {
+    if (one) { a.dl_lf = sub[0]->Dlast; a.dl_hf = sub[1]->Dlast; }
+    else { a.gl_lf = h->wv_gl; a.gl_hf = h->wv_gl + nn * 3; }
+    {
+      Launch L(h, K_WV_ADJOINT, 0, (double)nn * (52.0 * 8.0 + (one ? 32.0 : 24.0)));
+      hipLaunchKernelGGL(k_wv_adjoint, dim3((unsigned)((nn + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0, h->stream, a);
+      L.done();
+      HIPCHK(hipGetLastError());
+    }
+    if (one) {
+      for (int s = 0; s < 2; ++s) {
+        rc = run_pass(sub[s], true, nullptr, false, kPassBwd);
+        if (rc) return rc;
+      }
+    } else {
+      const long n_chunks = (nn + sub[0]->chunk_px - 1) / sub[0]->chunk_px;
+      for (long c = 0; c < n_chunks; ++c) {
+        const long pix0 = c * sub[0]->chunk_px, px = std::min(sub[0]->chunk_px, nn - pix0);
+        for (int s = 0; s < 2; ++s) {
+          rc = run_pass(sub[s], true, nullptr, false, kPassFwd, c, c + 1);
+          if (rc) return rc;
+          Launch L(h, K_WV_INJECT, 0, (double)px * 28.0);
+          hipLaunchKernelGGL(k_wv_inject, dim3((unsigned)((px + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0,
+                             h->stream, (const float*)(h->wv_gl + (size_t)s * nn * 3), pix0, px, sub[s]->Dlast);
+          L.done();
+          HIPCHK(hipGetLastError());
+          rc = run_pass(sub[s], true, nullptr, false, kPassBwd, c, c + 1);
+          if (rc) return rc;
+        }
+      }
+    }
+  }
+  if (want_sse || train) {
+    Launch L(h, K_SSE, 0, (double)n_cwg * 4);
+    hipLaunchKernelGGL(k_sse_reduce, dim3(1), dim3(256), 0, h->stream, (const float*)h->sse_part, (int)n_cwg,
                        h->sse_dev, h->replay ? h->loss_tab : h->loss_dst, (const int*)(h->replay ? h->iter_dev : h->iter_dev + 2));
     L.done();
     HIPCHK(hipGetLastError());
@@ -1489,6 +1602,121 @@ int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
   return SF_OK;
 } SF_CATCH
 
+// WaveletSiren handle: two SIREN sub-handles (sf_create, format 16) whose state buffers are slices of this handle's joint
+// [LF | HF] vectors, so that sf_state_ptr, sf_get/set_*, sf_adam_step (one k_adam over the joint vector), sf_step and graph
+// replay work unchanged; run_pass_wavelet drives the sub-handles around the composition kernels
+int sf_wavelet_create(const sf_wavelet_config* cfg, sf_handle** out) try {
+  if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
+  if (cfg->in_features != 2) return fail(SF_ERR_INVALID, "in_features must be 2 (coordinate grid)");
+  if (cfg->out_features != 3) return fail(SF_ERR_INVALID, "out_features must be 3 (Y, Cb, Cr / the three detail bands)");
+  if (cfg->wavelet_levels != 1)
+    return fail(SF_ERR_INVALID, "wavelet_levels must be 1: the reference's single-level inverse DWT receives 3 * levels bands "
+                                "and fails for more");
+  if (cfg->hidden != 32 && cfg->hidden != 64 && cfg->hidden != 128 && cfg->hidden != 256)
+    return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128 or 256 for WaveletSiren (other widths: zero-pad on the host)");
+  if (cfg->depth < 2 || cfg->depth > 16) return fail(SF_ERR_INVALID, "depth must be 2..16");
+  if (cfg->compute_dtype != SF_F16) return fail(SF_ERR_INVALID, "WaveletSiren runs fp16 operands only (compute_dtype SF_F16)");
+  if (cfg->scratch_format != 0 && cfg->scratch_format != 16)
+    return fail(SF_ERR_INVALID, "WaveletSiren runs scratch format 16 (0 = auto resolves to it): format 8 takes its fp8 delta "
+                                "scale from the fused residual, which a WaveletSiren pass does not form");
+  if (cfg->height != cfg->width || cfg->height < 2 || cfg->height % 2)
+    return fail(SF_ERR_INVALID, "WaveletSiren needs an even, square image: the reference's inverse DWT (2n - 4 rows) and its "
+                                "torch.cat of Y with the upsampled Cb / Cr stop matching otherwise");
+  if ((double)cfg->height * (double)cfg->width >= 2147483648.0) return fail(SF_ERR_INVALID, "image too large");
+  if (cfg->chunk_pixels < 0) return fail(SF_ERR_INVALID, "chunk_pixels must be >= 0");
+  const int H = cfg->height, n = (H + 5) / 2;   // pywt.dwt_coeff_len(H, 6, "zero")
+  sf_config sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.abi_version = SF_ABI_VERSION; sc.height = n; sc.width = n; sc.row_begin = 0; sc.row_end = n;
+  sc.in_features = 2; sc.out_features = 3; sc.hidden = cfg->hidden; sc.depth = cfg->depth;
+  sc.first_omega_0 = cfg->first_omega_0; sc.hidden_omega_0 = cfg->hidden_omega_0; sc.outermost_linear = cfg->outermost_linear;
+  sc.compute_dtype = SF_F16; sc.beta1 = cfg->beta1; sc.beta2 = cfg->beta2; sc.eps = cfg->eps;
+  sc.device = cfg->device; sc.stream = cfg->stream; sc.chunk_pixels = cfg->chunk_pixels; sc.scratch_format = 16;
+  sf_handle* sub[2] = {nullptr, nullptr};
+  for (int s = 0; s < 2; ++s) {
+    const int rc = sf_create(&sc, &sub[s]);
+    if (rc) { if (s) sf_destroy(sub[0]); return rc; }
+  }
+  DevGuard dev_guard(cfg->device);
+  sf_engine* h = new sf_engine();
+  h->wavelet = true;
+  h->wv_sub[0] = sub[0]; h->wv_sub[1] = sub[1];
+  h->cfg = sub[0]->cfg;
+  h->cfg.height = H; h->cfg.width = H; h->cfg.row_begin = 0; h->cfg.row_end = H;
+  h->beta1_d = sub[0]->beta1_d; h->beta2_d = sub[0]->beta2_d;
+  h->D = 2 * cfg->depth; h->WD = cfg->hidden;
+  h->dw_wg = sub[0]->dw_wg;
+  h->stream = (hipStream_t)cfg->stream;
+  h->npix = (long)H * H;
+  h->n_total = (double)H * (double)H;
+  h->wv_n = n;
+  h->wv_up = (float)(1.0 / ((double)H / (double)n));   // torch: scale_factor = H / n, source scale 1 / scale_factor
+  const long nn = sub[0]->npix;
+  const bool one = nn <= sub[0]->chunk_px;
+  h->chunk_px = one ? h->npix : 1;   // (sf_step's graph replay covers single-chunk fits only)
+  const int64_t P0 = sub[0]->P;
+  h->P = 2 * P0;
+  // the sub-networks' dL/dout pre-scale comes from the 3 H^2 values of the full image (what the loss mean divides by)
+  const float gpre = (float)exp2(ceil(log2(3.0 * h->n_total)) + 2.0);
+  for (sf_engine* s : h->wv_sub) { s->gpre = gpre; s->ext_dout = true; }
+  auto alloc = [&](void** p, size_t bytes) -> int {
+    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+    return SF_OK;
+  };
+  int rc = SF_OK;
+#define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
+  ALLOC(h->params, h->P * 4); ALLOC(h->grads, h->P * 4); ALLOC(h->m, h->P * 4); ALLOC(h->v, h->P * 4);
+  ALLOC(h->mask, h->P * 4);
+  ALLOC(h->wv_pred, (size_t)2 * nn * 3 * 4);
+  ALLOC(h->wv_g, (size_t)h->npix * 3 * 4);
+  if (!one) ALLOC(h->wv_gl, (size_t)2 * nn * 3 * 4);
+  h->n_sse = (h->npix + kWvThreads - 1) / kWvThreads;
+  ALLOC(h->sse_part, (h->n_sse + 64) * 4); ALLOC(h->sse_dev, 8);
+#undef ALLOC
+  if (rc) { sf_destroy(h); return rc; }
+  for (int s = 0; s < 2; ++s) {   // the sub-handles' state becomes the two halves of the joint vectors
+    sf_engine* e = h->wv_sub[s];
+    hipStreamSynchronize(e->stream);
+    for (float** p : {&e->params, &e->grads, &e->m, &e->v, &e->mask}) { hipFree(*p); *p = nullptr; }
+    e->params = h->params + s * P0; e->grads = h->grads + s * P0; e->m = h->m + s * P0; e->v = h->v + s * P0;
+    e->mask = h->mask + s * P0;
+    e->borrowed_state = true;
+  }
+  hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
+  hipMemsetAsync(h->grads, 0, h->P * 4, h->stream);
+  hipMemsetAsync(h->m, 0, h->P * 4, h->stream);
+  hipMemsetAsync(h->v, 0, h->P * 4, h->stream);
+  *out = h;
+  return SF_OK;
+} SF_CATCH
+
+int sf_wavelet_debug(sf_handle* h, int32_t which, const float* in0, const float* in1, const float* img, float* out0,
+                     float* out1) try {
+  if (!h || !in0 || !out0 || !out1 || (which == 0 && !in1)) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->wavelet) return fail(SF_ERR_INVALID, "sf_wavelet_debug: not a WaveletSiren handle (sf_wavelet_create)");
+  if (which != 0 && which != 1) return fail(SF_ERR_INVALID, "sf_wavelet_debug: which must be 0 or 1");
+  DevGuard dev_guard(h->cfg.device);
+  WvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.H = h->cfg.height; a.n = h->wv_n; a.up = h->wv_up;
+  a.gscale = (float)(2.0 / (3.0 * h->n_total));
+  a.dscale = 1.0f;
+  if (which == 0) {
+    a.lf = in0; a.hf = in1; a.img = img; a.pred = out0; a.g = img ? out1 : nullptr; a.sse_part = h->sse_part;
+    hipLaunchKernelGGL(k_wv_compose, dim3((unsigned)((h->npix + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0,
+                       h->stream, a);
+  } else {
+    a.g = const_cast<float*>(in0); a.gl_lf = out0; a.gl_hf = out1;
+    const long nn = (long)h->wv_n * h->wv_n;
+    hipLaunchKernelGGL(k_wv_adjoint, dim3((unsigned)((nn + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0, h->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+} SF_CATCH
+
 int sf_set_encoding(sf_handle* h, const float* B_dev) try {
   if (!h || !B_dev) return fail(SF_ERR_INVALID, "null argument");
   if (!h->fourier) return fail(SF_ERR_INVALID, "sf_set_encoding: not a FourierNet handle (sf_fourier_create)");
@@ -1553,11 +1781,13 @@ int sf_destroy(sf_handle* h) try {
 #endif
   for (auto& r : h->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
+  for (sf_engine* s : h->wv_sub) if (s) sf_destroy(s);
+  if (h->borrowed_state) { h->params = h->grads = h->m = h->v = h->mask = nullptr; }   // the WaveletSiren handle's
   void* ptrs[] = {h->params, h->grads, h->m, h->v, h->mask, h->wf, h->wf_last, h->wb, h->wb_last, h->l0tab, h->l0img,
                   h->gh, h->gw, h->Pbuf, h->Dbuf, h->Dlast, h->slab, h->sse_part, h->biasw, h->Abuf,
                   h->sse_dev, h->scale_dev, h->pad8, h->km_ws, h->wf16, h->wf16_last, h->l0img16, h->lsc,
                   h->ffB, h->ffimg, h->ffH, h->ffG, h->ffZ, h->fth_p, h->fth_g, h->fth_m, h->fth_v, h->fth_V, h->fth_G,
-                  h->fth_part, h->fth_chunks, h->fth_chunk0};
+                  h->fth_part, h->fth_chunks, h->fth_chunk0, h->wv_pred, h->wv_g, h->wv_gl};
   for (void* p : ptrs) if (p) hipFree(p);
   if (h->gexec) hipGraphExecDestroy(h->gexec);
   if (h->gstream) { hipStreamSynchronize(h->gstream); hipStreamDestroy(h->gstream); hipEventDestroy(h->gev_in); hipEventDestroy(h->gev_out); }
@@ -1579,6 +1809,14 @@ int sf_scratch_format(const sf_handle* h, int32_t* format) try {
 } SF_CATCH
 int sf_param_offset(const sf_handle* h, int32_t layer, int64_t* w, int64_t* b) try {
   if (!h || layer < 0 || layer >= h->D) return fail(SF_ERR_INVALID, "bad layer");
+  if (h->wavelet) {   // layers 0 .. depth-1: LF, then HF in the second half of the flat vector
+    const sf_engine* s = h->wv_sub[layer >= h->wv_sub[0]->D];
+    const int64_t base = layer >= h->wv_sub[0]->D ? h->wv_sub[0]->P : 0;
+    const int l = layer >= h->wv_sub[0]->D ? layer - h->wv_sub[0]->D : layer;
+    if (w) *w = base + s->off_w[l];
+    if (b) *b = base + s->off_b[l];
+    return SF_OK;
+  }
   if (w) *w = h->off_w[layer];
   if (b) *b = h->off_b[layer];
   return SF_OK;
@@ -1693,6 +1931,7 @@ int sf_sse_ptr(sf_handle* h, double** p) try {
 int sf_debug_scratch(sf_handle* h, int32_t which, void** p, int64_t* bytes) try {
   if (!h || !p || !bytes) return fail(SF_ERR_INVALID, "null argument");
   if (h->fourier) return fail(SF_ERR_INVALID, "sf_debug_scratch: a FourierNet handle has no phase / delta scratch");
+  if (h->wavelet) return fail(SF_ERR_INVALID, "sf_debug_scratch: the scratch of a WaveletSiren handle lives in its sub-networks");
   const int D = h->D;
   switch (which) {
     case 0: *p = h->Pbuf; *bytes = (int64_t)(D - 1) * h->p_stride * 16; return SF_OK;
@@ -1712,6 +1951,15 @@ int sf_params_changed(sf_handle* h) try {
 int sf_set_coords(sf_handle* h, const float* rows, const float* cols) try {
   if (!h || !rows || !cols) return fail(SF_ERR_INVALID, "null argument");
   DevGuard dev_guard(h->cfg.device);
+  if (h->wavelet) {   // both sub-networks run on the n x n coefficient grid (wavelet_siren.py:76-80)
+    wv_sync(h);
+    for (sf_engine* s : h->wv_sub) {
+      const int rc = sf_set_coords(s, rows, cols);
+      if (rc) return rc;
+    }
+    h->have_coords = true;
+    return SF_OK;
+  }
   HIPCHK(hipMemcpyAsync(h->gh, rows, (size_t)h->cfg.height * 4, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->gw, cols, (size_t)h->cfg.width * 4, hipMemcpyDeviceToDevice, h->stream));
   // The forward indexes these vectors; the gradient kernels of layer 0 / layer 1 re-derive the coordinate of a
@@ -1925,6 +2173,7 @@ int sf_profile_enable(sf_handle* h, int32_t on) try {
   DevGuard dev_guard(h->cfg.device);
   if (!on) { int rc = prof_flush(h); if (rc) return rc; }
   h->prof = on != 0;
+  for (sf_engine* s : h->wv_sub) if (s) { int rc = sf_profile_enable(s, on); if (rc) return rc; }
   return SF_OK;
 } SF_CATCH
 int sf_profile_reset(sf_handle* h) try {
@@ -1933,6 +2182,7 @@ int sf_profile_reset(sf_handle* h) try {
   int rc = prof_flush(h);
   if (rc) return rc;
   for (int i = 0; i < K_COUNT; ++i) { h->prof_ms[i] = 0; h->prof_n[i] = 0; h->prof_flops[i] = 0; h->prof_bytes[i] = 0; }
+  for (sf_engine* s : h->wv_sub) if (s) { rc = sf_profile_reset(s); if (rc) return rc; }
   return SF_OK;
 } SF_CATCH
 int sf_profile_num_kernels(const sf_handle* h, int32_t* n) try {
@@ -1946,12 +2196,20 @@ int sf_profile_get(sf_handle* h, int32_t idx, const char** name, double* total_m
   DevGuard dev_guard(h->cfg.device);
   int rc = prof_flush(h);
   if (rc) return rc;
+  double ms = h->prof_ms[idx], fl = h->prof_flops[idx], by = h->prof_bytes[idx];
+  int64_t cnt = h->prof_n[idx];
+  for (sf_engine* s : h->wv_sub) {   // WaveletSiren: the sub-networks' launches count as the handle's
+    if (!s) continue;
+    rc = prof_flush(s);
+    if (rc) return rc;
+    ms += s->prof_ms[idx]; fl += s->prof_flops[idx]; by += s->prof_bytes[idx]; cnt += s->prof_n[idx];
+  }
   if (name) *name = kKernelNames[idx];
-  if (total_ms) *total_ms = h->prof_ms[idx];
-  if (launches) *launches = h->prof_n[idx];
-  const double nl = h->prof_n[idx] > 0 ? (double)h->prof_n[idx] : 1.0;
-  if (flops_per_launch) *flops_per_launch = h->prof_flops[idx] / nl;
-  if (bytes_per_launch) *bytes_per_launch = h->prof_bytes[idx] / nl;
+  if (total_ms) *total_ms = ms;
+  if (launches) *launches = cnt;
+  const double nl = cnt > 0 ? (double)cnt : 1.0;
+  if (flops_per_launch) *flops_per_launch = fl / nl;
+  if (bytes_per_launch) *bytes_per_launch = by / nl;
   return SF_OK;
 } SF_CATCH
 
@@ -1988,7 +2246,7 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
 int sf_feather_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, const int32_t* logical_out,
                       const int32_t* logical_in) try {
   if (!h || !logical_out || !logical_in) return fail(SF_ERR_INVALID, "null argument");
-  if (h->fourier) return fail(SF_ERR_INVALID, "sf_feather_attach: Feathermap runs on SIREN handles only");
+  if (h->fourier || h->wavelet) return fail(SF_ERR_INVALID, "sf_feather_attach: Feathermap runs on SIREN handles only");
   if (h->feather) return fail(SF_ERR_INVALID, "sf_feather_attach: the handle already has a feather state");
   if (h->cfg.row_begin != 0 || h->cfg.row_end != h->cfg.height)
     return fail(SF_ERR_INVALID, "sf_feather_attach: Feathermap fits the whole image (no pixel split)");

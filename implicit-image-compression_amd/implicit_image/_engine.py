@@ -41,6 +41,17 @@ class sf_fourier_config(C.Structure):
     ]
 
 
+class sf_wavelet_config(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+        ("in_features", C.c_int32), ("out_features", C.c_int32), ("hidden", C.c_int32), ("depth", C.c_int32),
+        ("wavelet_levels", C.c_int32), ("first_omega_0", C.c_float), ("hidden_omega_0", C.c_float),
+        ("outermost_linear", C.c_int32), ("compute_dtype", C.c_int32),
+        ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("device", C.c_int32), ("stream", C.c_void_p), ("chunk_pixels", C.c_int64), ("scratch_format", C.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -94,7 +105,12 @@ def load_library():
         "sf_feather_state_ptr": [H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(I64)],
         "sf_feather_materialise": [H], "sf_feather_adjoint": [H],
     }
-    for name, args in feather.items():
+    # WaveletSiren entry points: the same rule
+    wavelet = {
+        "sf_wavelet_create": [C.POINTER(sf_wavelet_config), C.POINTER(H)],
+        "sf_wavelet_debug": [H, C.c_int32, F, F, F, F, F],
+    }
+    for name, args in list(feather.items()) + list(wavelet.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.argtypes = args
@@ -110,6 +126,10 @@ def load_library():
 def has_feather(lib) -> bool:
     return all(hasattr(lib, s) for s in ("sf_feather_attach", "sf_feather_state_ptr", "sf_feather_materialise",
                                          "sf_feather_adjoint"))
+
+
+def has_wavelet(lib) -> bool:
+    return all(hasattr(lib, s) for s in ("sf_wavelet_create", "sf_wavelet_debug"))
 
 
 def exported_symbols() -> Sequence[str]:
@@ -391,6 +411,62 @@ class FourierEngine(SirenEngine):
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
         _check(self.lib.sf_set_encoding(self.h, _f32_cuda(B.detach().contiguous(), 2 * (self.map_size // 2)).data_ptr()))
+
+
+class WaveletEngine(SirenEngine):
+    """WaveletSiren fit on one HIP stream: an sf_handle made by sf_wavelet_create (two SIREN sub-networks on the n x n
+    coefficient grid, wavelet_kernels.hip for the image).  Every method of SirenEngine applies: the flat vectors are
+    [LF | HF], forward() returns the H x H x 3 RGB prediction."""
+
+    def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
+                 hidden_omega_0: float = 30.0, outermost_linear: bool = True, device: int = 0, chunk_pixels: int = 0,
+                 betas=(0.9, 0.999), eps: float = 1e-8, wavelet_levels: int = 1):
+        self.lib = load_library()
+        if not has_wavelet(self.lib):
+            raise RuntimeError(f"{_LIB_PATH} has no sf_wavelet_* entry points (built before WaveletSiren): rebuild it with "
+                               "`python __graft_entry__.py build`")
+        if not torch.cuda.is_available():
+            raise RuntimeError("WaveletEngine needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
+        self.device = torch.device("cuda", device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        cfg = sf_wavelet_config(SF_ABI_VERSION, height, width, 2, 3, hidden, depth, wavelet_levels, first_omega_0,
+                                hidden_omega_0, int(bool(outermost_linear)), DTYPES["f16"], betas[0], betas[1], eps, device,
+                                stream, chunk_pixels, 16)
+        self.h = C.c_void_p()
+        _check(self.lib.sf_wavelet_create(C.byref(cfg), C.byref(self.h)))
+        n = C.c_int64()
+        _check(self.lib.sf_num_params(self.h, C.byref(n)))
+        self.num_params = n.value
+        self.height, self.width, self.hidden, self.depth = height, width, hidden, depth
+        self.n = (height + 5) // 2
+        self.row_begin, self.row_end = 0, height
+        self.npix = height * width
+        self.out_features = 3
+        self._target = None
+        self._views = {}
+
+    def set_coords(self, rows: torch.Tensor, cols: torch.Tensor):
+        """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""
+        _check(self.lib.sf_set_coords(self.h, _f32_cuda(rows, self.n).data_ptr(), _f32_cuda(cols, self.n).data_ptr()))
+
+    def debug_compose(self, lf: torch.Tensor, hf: torch.Tensor, img: Optional[torch.Tensor] = None):
+        """k_wv_compose on [n, n, 3] sub-network predictions: (RGB [H, H, 3], dL/d(Y, Cb, Cr) [H, H, 3] or None)"""
+        nn3, hh3 = self.n * self.n * 3, self.npix * 3
+        pred = torch.empty(self.height, self.width, 3, device=self.device)
+        g = torch.zeros(self.height, self.width, 3, device=self.device)
+        _check(self.lib.sf_wavelet_debug(self.h, 0, _f32_cuda(lf, nn3).data_ptr(), _f32_cuda(hf, nn3).data_ptr(),
+                                         None if img is None else _f32_cuda(img, hh3).data_ptr(), pred.data_ptr(),
+                                         g.data_ptr()))
+        return pred, (g if img is not None else None)
+
+    def debug_adjoint(self, g: torch.Tensor):
+        """k_wv_adjoint (unscaled) of dL/d(Y, Cb, Cr) [H, H, 3]: (dL/dp of LF, of HF), [n, n, 3] each"""
+        lf = torch.empty(self.n, self.n, 3, device=self.device)
+        hf = torch.empty(self.n, self.n, 3, device=self.device)
+        _check(self.lib.sf_wavelet_debug(self.h, 1, _f32_cuda(g, self.npix * 3).data_ptr(), None, None, lf.data_ptr(),
+                                         hf.data_ptr()))
+        return lf, hf
 
 
 class FeatherEngine:

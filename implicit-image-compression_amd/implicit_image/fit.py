@@ -20,6 +20,7 @@ import torch
 from .config import Cfg, expand_sweeps, load_config
 from .data import get_grid, load_img
 from .models import registry as model_registry
+from .models.wavelet_siren import check_image as check_wavelet_image
 from .parallel import shard_jobs
 from .pipeline import entropy_coding
 from .pipeline.feathermap import FeatherNet
@@ -38,6 +39,11 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
         raise NotImplementedError("masking=Feathermap runs on the SIREN engine only (mlp=siren)")
     if feather and cfg.get("quant"):
         raise NotImplementedError(f"masking=Feathermap with quant={cfg.quant.get('name', cfg.quant)}: {DEEPCOPY_UNSUPPORTED}")
+    if cfg.mlp.name == "wavelet_siren":
+        if cfg.get("quant"):
+            raise NotImplementedError(f"quant={cfg.quant.get('name', cfg.quant)} on WaveletSiren is not built on the engine: "
+                                      "use quant=none")
+        check_wavelet_image(cfg.img.height, cfg.img.width)                          # before any GPU work
     torch.manual_seed(cfg.seed)                                                   # compress.py:58
     img = load_img(**cfg.img)                                                      # compress.py:64
     grid = get_grid(cfg.img.height, cfg.img.width)                                 # compress.py:67

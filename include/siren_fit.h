@@ -105,10 +105,45 @@ typedef struct sf_fourier_config {
   int64_t chunk_pixels;     /* pixels per kernel sweep (0 = auto)          */
 } sf_fourier_config;
 
+/* WaveletSiren (reference implicit_image/models/wavelet_siren.py): two SIRENs, LF (Y_LL, Cb, Cr) and HF (the detail bands
+ * LH, HL, HH), on one n x n coefficient grid, n = (H + 5) / 2; the image is the db3 / zero-mode inverse DWT for Y, bilinear
+ * upsampling of Cb and Cr, and YCbCr -> RGB (wavelet_kernels.hip).  The handle is an ordinary sf_handle: every call above
+ * and below works on it, with these differences
+ *   - the flat vector is [LF layers | HF layers] in the reference's named_parameters() order (LF_siren.layers.{i}.linear.*,
+ *     then HF_siren.*); sf_param_offset numbers the layers 0 .. 2 depth - 1 the same way;
+ *   - sf_set_coords takes the two linspace(0, 1, n) vectors of the coefficient grid; sf_set_target the H x H x 3 image;
+ *     sf_forward writes the H x H x 3 RGB prediction and the SSE over 3 H^2 values;
+ *   - sf_scratch_format reports 16; sf_debug_scratch and sf_feather_attach return SF_ERR_INVALID. */
+typedef struct sf_wavelet_config {
+  int32_t abi_version;      /* SF_ABI_VERSION                                              */
+  int32_t height, width;    /* image H = W, even (the reference's shapes stop matching otherwise) */
+  int32_t in_features;      /* 2                                                           */
+  int32_t out_features;     /* 3                                                           */
+  int32_t hidden;           /* 32, 64, 128 or 256 (Small_Dense widths: zero-pad on the host) */
+  int32_t depth;            /* Linear layers of each sub-network, 2..16                    */
+  int32_t wavelet_levels;   /* 1                                                           */
+  float first_omega_0, hidden_omega_0;
+  int32_t outermost_linear;
+  int32_t compute_dtype;    /* SF_F16 only                                                 */
+  float beta1, beta2, eps;  /* Adam                                                        */
+  int32_t device;           /* HIP device ordinal                                          */
+  void* stream;             /* hipStream_t (NULL = null stream)                            */
+  int64_t chunk_pixels;     /* coefficient-grid pixels per sweep of a sub-network (0 = auto, 4 Mi): a grid of more
+                             * pixels than one chunk runs in two passes */
+  int32_t scratch_format;   /* 0 (auto) or 16                                              */
+} sf_wavelet_config;
+
 /* lifecycle */
 int sf_create(const sf_config* cfg, sf_handle** out);
 int sf_destroy(sf_handle* h);
 int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out);
+int sf_wavelet_create(const sf_wavelet_config* cfg, sf_handle** out);
+/* test aid: one composition kernel of a WaveletSiren handle on caller buffers, enqueued on the handle's stream.
+ * which 0 (k_wv_compose): in0 / in1 the LF / HF predictions [n*n][3], img [H*H][3] (may be NULL) -> out0 the RGB prediction
+ *   [H*H][3], out1 dL/d(Y, Cb, Cr) [H*H][3] (written when img is given; the SSE partials stay in the handle);
+ * which 1 (k_wv_adjoint, unscaled): in0 dL/d(Y, Cb, Cr) [H*H][3] -> out0 / out1 dL/dp of LF / HF [n*n][3] (fp32) */
+int sf_wavelet_debug(sf_handle* h, int32_t which, const float* in0, const float* in1, const float* img, float* out0,
+                     float* out1);
 int sf_set_encoding(sf_handle* h, const float* B_dev /* [in_features][map_size/2] fp32, copied */);
 const char* sf_last_error(void);            /* thread-local message of the last failure */
 int sf_abi_version(void);
