@@ -188,6 +188,8 @@ struct sf_engine {
   float* wv_pred = nullptr;     // [2][n*n][3] sub-network predictions
   float* wv_g = nullptr;        // [H*H][3] dL/d(Y, Cb, Cr)
   float* wv_gl = nullptr;       // two-pass only: [2][n*n][3] fp32 dL/dout of the sub-networks
+  float* wv_dfac = nullptr;     // outermost_linear=False only: [2][n*n][3] d sin(om z)/dz of the sub-networks' outputs
+  float* dfac_out = nullptr;    // sub-handle, sine output layer: its slice of wv_dfac (FwdArgs::dfac of training forwards)
 };
 
 namespace {
@@ -1084,6 +1086,7 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = 
     fa.sc_last = 1.0f / h->wscale;
     if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / two_pi); }
     fa.P = h->Pbuf; fa.p_stride = h->p_stride; fa.Dlast = h->Dlast;
+    fa.dfac = train ? h->dfac_out : nullptr;
     fa.img = h->img;
     fa.nout = h->cfg.out_features;
     fa.gscale = h->d8 ? kResScale : (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total));
@@ -1257,6 +1260,7 @@ int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
   a.sse_part = h->sse_part;
   a.gscale = (float)(2.0 / (3.0 * h->n_total));
   a.dscale = 0.5f * sub[0]->gpre;
+  a.dfac_lf = sub[0]->dfac_out; a.dfac_hf = sub[1]->dfac_out;   // (null for a linear output layer)
   const unsigned n_cwg = (unsigned)((HH + kWvThreads - 1) / kWvThreads);
   {
     Launch L(h, K_WV_COMPOSE, 0, (double)HH * 4.0 * (3.0 + (a.img ? 3.0 : 0.0) + (pred ? 3.0 : 0.0) + (train ? 3.0 : 0.0)));
@@ -1287,7 +1291,8 @@ int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
           if (rc) return rc;
           Launch L(h, K_WV_INJECT, 0, (double)px * 28.0);
           hipLaunchKernelGGL(k_wv_inject, dim3((unsigned)((px + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0,
-                             h->stream, (const float*)(h->wv_gl + (size_t)s * nn * 3), pix0, px, sub[s]->Dlast);
+                             h->stream, (const float*)(h->wv_gl + (size_t)s * nn * 3), (const float*)sub[s]->dfac_out, pix0,
+                             px, sub[s]->Dlast);
           L.done();
           HIPCHK(hipGetLastError());
           rc = run_pass(sub[s], true, nullptr, false, kPassBwd, c, c + 1);
@@ -1673,6 +1678,7 @@ int sf_wavelet_create(const sf_wavelet_config* cfg, sf_handle** out) try {
   ALLOC(h->wv_pred, (size_t)2 * nn * 3 * 4);
   ALLOC(h->wv_g, (size_t)h->npix * 3 * 4);
   if (!one) ALLOC(h->wv_gl, (size_t)2 * nn * 3 * 4);
+  if (!cfg->outermost_linear) ALLOC(h->wv_dfac, (size_t)2 * nn * 3 * 4);
   h->n_sse = (h->npix + kWvThreads - 1) / kWvThreads;
   ALLOC(h->sse_part, (h->n_sse + 64) * 4); ALLOC(h->sse_dev, 8);
 #undef ALLOC
@@ -1684,6 +1690,7 @@ int sf_wavelet_create(const sf_wavelet_config* cfg, sf_handle** out) try {
     e->params = h->params + s * P0; e->grads = h->grads + s * P0; e->m = h->m + s * P0; e->v = h->v + s * P0;
     e->mask = h->mask + s * P0;
     e->borrowed_state = true;
+    if (h->wv_dfac) e->dfac_out = h->wv_dfac + (size_t)s * nn * 3;
   }
   hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
   hipMemsetAsync(h->grads, 0, h->P * 4, h->stream);
@@ -1787,7 +1794,7 @@ int sf_destroy(sf_handle* h) try {
                   h->gh, h->gw, h->Pbuf, h->Dbuf, h->Dlast, h->slab, h->sse_part, h->biasw, h->Abuf,
                   h->sse_dev, h->scale_dev, h->pad8, h->km_ws, h->wf16, h->wf16_last, h->l0img16, h->lsc,
                   h->ffB, h->ffimg, h->ffH, h->ffG, h->ffZ, h->fth_p, h->fth_g, h->fth_m, h->fth_v, h->fth_V, h->fth_G,
-                  h->fth_part, h->fth_chunks, h->fth_chunk0, h->wv_pred, h->wv_g, h->wv_gl};
+                  h->fth_part, h->fth_chunks, h->fth_chunk0, h->wv_pred, h->wv_g, h->wv_gl, h->wv_dfac};
   for (void* p : ptrs) if (p) hipFree(p);
   if (h->gexec) hipGraphExecDestroy(h->gexec);
   if (h->gstream) { hipStreamSynchronize(h->gstream); hipStreamDestroy(h->gstream); hipEventDestroy(h->gev_in); hipEventDestroy(h->gev_out); }

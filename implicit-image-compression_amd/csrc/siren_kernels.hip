@@ -265,6 +265,8 @@ struct FwdArgs {
   float* pred;             // optional [npix][nout]
   float* sse_part;         // [gridDim.x] per-workgroup sum of squared residuals
   float* dbg;              // SF_EXPERIMENT_STAMP builds only
+  float* dfac;             // optional [npix][nout]: a training pass with a sine output layer writes d sin(om z)/dz here
+                           // (WaveletSiren sub-handles: their dL/dout comes from k_wv_adjoint / k_wv_inject, which apply it)
 };
 
 // Forward weight image of one hidden layer, as stored in HBM and copied verbatim into LDS:
@@ -299,6 +301,7 @@ DEV float fwd_residual(const FwdArgs& a, const f32x16& acc, const float (&tgt)[3
         const float tt = o * a.last_om_rev;
         o = __builtin_amdgcn_sinf(tt);
         dfac = a.last_om * __builtin_amdgcn_cosf(tt);
+        if (TRAIN && a.dfac) a.dfac[pix * a.nout + c] = dfac;
       }
       const float p = o * 0.5f + 0.5f;  // siren.py:131
       if (a.pred) a.pred[pix * a.nout + c] = p;

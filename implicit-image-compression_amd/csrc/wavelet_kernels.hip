@@ -17,6 +17,9 @@
 //                  pre-scale goes straight into each sub-network's dL/dout (Dlast, F-layout) or, when the coefficient
 //                  grid takes more than one chunk, into an fp32 buffer
 //   k_wv_inject    two-pass form: one chunk of that fp32 buffer -> Dlast
+// With a sine output layer (outermost_linear=False) dL/dout is dL/dz of the last pre-activation: the sub-networks' training
+// forward writes d sin(om z)/dz = om cos(om z) per coefficient and channel (FwdArgs::dfac), and k_wv_adjoint (one chunk) or
+// k_wv_inject (two passes) multiplies by it before the single fp16 rounding.  The two-pass buffer holds dL/dp times dscale.
 //
 // Synthesis (pytorch_wavelets lowlevel.sfb1d, zero mode): per axis y[o] = sum_i lo[i] g0[o + 4 - 2 i] + hi[i] g1[o + 4 - 2 i]
 // over 0 <= o + 4 - 2 i < 6 (conv_transpose with stride 2, padding L - 2 = 4), the column filter along the height first.
@@ -55,6 +58,8 @@ struct WvArgs {
   u32x4* dl_hf;
   float* gl_lf;          // two-pass: [n*n][3] fp32 dL/dout (already scaled by dscale) of LF / HF
   float* gl_hf;
+  const float* dfac_lf;  // one chunk, sine output layer: [n*n][3] d sin(om z)/dz of LF / HF (null: linear output)
+  const float* dfac_hf;
 };
 
 // torch's bilinear source index (upsample_bilinear2d, align_corners=False): the same arithmetic serves the forward and,
@@ -208,7 +213,12 @@ __global__ __launch_bounds__(kWvThreads) void k_wv_adjoint(WvArgs a) {
     dcr += wr * sr;
   }
   const float s = a.dscale;
-  if (a.dl_lf) {
+  if (a.dl_lf && a.dfac_lf) {
+    const float* fl = a.dfac_lf + q * 3;
+    const float* fh = a.dfac_hf + q * 3;
+    wv_store_dlast(a.dl_lf, q, dll * s * fl[0], dcb * s * fl[1], dcr * s * fl[2]);
+    wv_store_dlast(a.dl_hf, q, dlh * s * fh[0], dhl * s * fh[1], dhh * s * fh[2]);
+  } else if (a.dl_lf) {
     wv_store_dlast(a.dl_lf, q, dll * s, dcb * s, dcr * s);
     wv_store_dlast(a.dl_hf, q, dlh * s, dhl * s, dhh * s);
   } else {
@@ -217,12 +227,18 @@ __global__ __launch_bounds__(kWvThreads) void k_wv_adjoint(WvArgs a) {
   }
 }
 
-// two-pass form: coefficients [pix0, pix0 + px) of one sub-network's fp32 dL/dout into its (chunk-local) Dlast
-__global__ __launch_bounds__(kWvThreads) void k_wv_inject(const float* gl, long pix0, long px, u32x4* dl) {
+// two-pass form: coefficients [pix0, pix0 + px) of one sub-network's fp32 dL/dout into its (chunk-local) Dlast; dfac
+// ([n*n][3], sine output layer, written by the chunk's training forward just before) or null
+__global__ __launch_bounds__(kWvThreads) void k_wv_inject(const float* gl, const float* dfac, long pix0, long px, u32x4* dl) {
   const long t = (long)blockIdx.x * kWvThreads + threadIdx.x;
   if (t >= px) return;
   const float* s = gl + (pix0 + t) * 3;
-  wv_store_dlast(dl, t, s[0], s[1], s[2]);
+  if (dfac) {
+    const float* f = dfac + (pix0 + t) * 3;
+    wv_store_dlast(dl, t, s[0] * f[0], s[1] * f[1], s[2] * f[2]);
+  } else {
+    wv_store_dlast(dl, t, s[0], s[1], s[2]);
+  }
 }
 
 }  // namespace sf

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Golden vectors for WaveletSiren (mlp=wavelet_siren).
 
-    python tests/golden/make_golden_wavelet.py [idwt] [bilinear] [init] [grads] [traj] [plateau]
+    python tests/golden/make_golden_wavelet.py [idwt] [bilinear] [init] [grads] [traj] [plateau] [shapes]
 
   wavelet_idwt.npz       PyWavelets 1.1.1 (run as a separate interpreter that has pywt, `pywt` mode of this script): db3
                          rec_lo / rec_hi and idwt2(mode="zero") of random coefficient sets at n = 6, 34, 52, 130 (fp32 inputs;
@@ -22,6 +22,12 @@ tests/_wavelet_ref.py for pytorch_wavelets and kornia, and trained with its own 
   wavelet_traj.npz       small model, 20 steps of train_epoch with Adam lr 1e-3 on that image: losses and final parameters
   wavelet_plateau.npz    yaml model, 300 steps of train_epoch with Adam lr 3e-4 on the 256x256 synthetic_image (seed 5) and
                          nonsmooth_image: loss curve and final eval PSNR, with 8 and with 2 torch threads
+  wavelet_shapes.npz     for every model of SHAPES (the widths, depths, output layers, omegas, Small_Dense padding and
+                         image sizes the models above leave out: every sub-network kernel path, a sine output layer,
+                         first / hidden omega 30 / 50, H = 2 / 4 / 6), seed 0: sha256 of every init tensor, and on
+                         synthetic_image(H, H, seed 5) the prediction, the loss and per-tensor gradient norms (sha and
+                         norms in the order of the names).  Not in the
+                         default set: `python tests/golden/make_golden_wavelet.py shapes`
 """
 import hashlib
 import importlib.util
@@ -40,6 +46,21 @@ PYWT_PYTHON = os.environ.get("PYWT_PYTHON", "python3")   # an interpreter with n
 SMALL = dict(depth=4, hidden_size=64, first_omega_0=50.0, hidden_omega_0=30.0)
 YAML = dict(depth=8, hidden_size=128, wavelet_levels=1, first_omega_0=50.0, hidden_omega_0=30.0, outermost_linear=True,
             simulate_quantization=False)
+# tag -> (WaveletSiren kwargs, image side H); tests/_wavelet_shapes_child.py runs the same table on the engine
+SHAPES = {
+    "h32_d3_s24": (dict(depth=3, hidden_size=32, hidden_omega_0=30.0), 24),
+    "h64_d2_s10": (dict(depth=2, hidden_size=64, hidden_omega_0=30.0), 10),
+    "h128_d5_sin_s40": (dict(depth=5, hidden_size=128, hidden_omega_0=30.0, outermost_linear=False), 40),
+    "h256_d2_s30": (dict(depth=2, hidden_size=256, hidden_omega_0=30.0), 30),
+    "h256_d6_s64": (dict(depth=6, hidden_size=256, hidden_omega_0=30.0), 64),
+    "h256_d4_sin_om_s48": (dict(depth=4, hidden_size=256, first_omega_0=30.0, hidden_omega_0=50.0, outermost_linear=False),
+                           48),
+    "h181p_d4_s48": (dict(depth=4, hidden_size=256, hidden_omega_0=30.0, small_dense_density=0.5), 48),
+    "h32_d16_s20": (dict(depth=16, hidden_size=32, hidden_omega_0=30.0), 20),
+    "h64_d3_s2": (dict(depth=3, hidden_size=64, hidden_omega_0=30.0), 2),
+    "h64_d3_s4": (dict(depth=3, hidden_size=64, hidden_omega_0=30.0), 4),
+    "h64_d3_s6": (dict(depth=3, hidden_size=64, hidden_omega_0=30.0), 6),
+}
 
 
 def make_pywt():   # runs under an interpreter with numpy + pywt (no torch)
@@ -184,6 +205,24 @@ def make_plateau(th, ws, so, steps=300):
     np.savez(os.path.join(OUT, "wavelet_plateau.npz"), **out)
 
 
+def make_shapes(ws, so):
+    import torch.nn.functional as F
+    out = {"tags": np.array(list(SHAPES))}
+    for tag, (kw, H) in SHAPES.items():
+        img, grid = so.synthetic_image(H, H, seed=5), so.get_grid(H, H)
+        m = model(ws, 0, **kw)
+        names = [n for n, _ in m.named_parameters()]
+        out[f"{tag}/names"] = np.array(names)
+        out[f"{tag}/sha"] = np.array([sha(p) for _, p in m.named_parameters()], dtype="S64")
+        pred = m(grid)
+        loss = F.mse_loss(pred, img)
+        loss.backward()
+        out[f"{tag}/pred"] = pred.detach().numpy()
+        out[f"{tag}/loss"] = np.float64(loss.item())
+        out[f"{tag}/gradnorm"] = np.array([p.grad.double().norm().item() for _, p in m.named_parameters()])
+    np.savez_compressed(os.path.join(OUT, "wavelet_shapes.npz"), **out)
+
+
 def main():
     what = set(sys.argv[1:]) or {"idwt", "bilinear", "init", "grads", "traj", "plateau"}
     if what == {"pywt"}:
@@ -196,7 +235,7 @@ def main():
     torch.set_num_threads(8)
     if "bilinear" in what:
         make_bilinear()
-    if what & {"init", "grads", "traj", "plateau"}:
+    if what & {"init", "grads", "traj", "plateau", "shapes"}:
         th, ws, so = _ref()
         if "init" in what:
             make_init(ws, so)
@@ -206,6 +245,8 @@ def main():
             make_traj(th, ws, so)
         if "plateau" in what:
             make_plateau(th, ws, so)
+        if "shapes" in what:
+            make_shapes(ws, so)
 
 
 if __name__ == "__main__":

@@ -223,3 +223,128 @@ def test_wavelet_create_rejects_bad_configs_without_a_gpu(bad, word):
     assert word in lib.sf_last_error() and not h.value
     assert lib.sf_wavelet_create(None, C.byref(h)) == -1
     assert lib.sf_wavelet_debug(None, 0, None, None, None, None, None) == -1
+
+
+# ---- wavelet_shapes.npz: every sub-network kernel path the GPU shape matrix runs (tests/_wavelet_shapes_child.py) ----
+@pytest.fixture(scope="module")
+def shapes_fixture():
+    return np.load(os.path.join(ROOT, "tests", "golden", "wavelet_shapes.npz"), allow_pickle=False)
+
+
+def _shapes():
+    import _wavelet_shapes_child as ch
+    return ch.SHAPES
+
+
+def _engine_flat(m):
+    """a host model's parameters in the engine layout ([LF | HF] at the engine width, padded slots 0)"""
+    import _wavelet_ref as wr
+    flat = torch.zeros(2 * m._sub_engine_params())
+    flat[m._padded_index(torch.device("cpu"))] = wr.model_flat(m)
+    return flat
+
+
+def test_shapes_fixture_covers_the_gpu_matrix(shapes_fixture):
+    assert [str(t) for t in shapes_fixture["tags"]] == list(_shapes())
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "wavelet_shapes.npz")) < 256 * 1024
+    kws = [kw for kw, _ in _shapes().values()]
+    assert any(kw.get("outermost_linear") is False for kw in kws)
+    assert any(kw.get("first_omega_0", 50.0) != 50.0 or kw.get("hidden_omega_0", 50.0) != 30.0 for kw in kws)
+
+
+@pytest.mark.parametrize("tag", ["h32_d3_s24", "h64_d2_s10", "h128_d5_sin_s40", "h256_d2_s30", "h256_d6_s64",
+                                 "h256_d4_sin_om_s48", "h181p_d4_s48", "h32_d16_s20", "h64_d3_s2", "h64_d3_s4",
+                                 "h64_d3_s6"])
+def test_shapes_init_and_mirror_match_the_reference(shapes_fixture, tag):
+    """Seed-0 init at every shape of the GPU matrix is bit-exact against the reference (sha256 per tensor: widths 32 / 256,
+    depths 2 / 16, Small_Dense 181, a sine output layer, omegas 30 / 50).  The mirror, run in fp32 as the reference is,
+    reproduces its prediction, loss and gradient norms (measured: bit-identical); in fp64 it is within 4.0e-6 (prediction,
+    the sine-output shapes), 1.8e-7 (loss) and 1.1e-6 (gradient norms), which is what the GPU tests compare with."""
+    import _wavelet_ref as wr
+    from oracle import siren_oracle as so
+    g = shapes_fixture
+    kw, H = _shapes()[tag]
+    m = _wavelet(**kw)
+    names = [n for n, _ in m.named_parameters()]
+    assert names == [str(n) for n in g[f"{tag}/names"]]
+    for (n, p), ref in zip(m.named_parameters(), g[f"{tag}/sha"]):
+        assert hashlib.sha256(p.detach().numpy().astype(np.float32).tobytes()).hexdigest() == ref.decode(), (tag, n)
+    img = so.synthetic_image(H, H, seed=5)
+    c = m.cfg
+    for dtype, pbar, lbar, gbar in ((torch.float32, 1e-6, 1e-6, 1e-5), (torch.float64, 1e-5, 1e-6, 5e-6)):
+        pred, loss, grad = wr.loss_and_grads(wr.model_flat(m), c["hidden_size"], c["depth"], img, c["first_omega_0"],
+                                             c["hidden_omega_0"], dtype, c["outermost_linear"])
+        assert (pred.double() - torch.tensor(g[f"{tag}/pred"]).double()).abs().max().item() <= pbar, (tag, dtype)
+        assert abs(loss - float(g[f"{tag}/loss"])) <= lbar * float(g[f"{tag}/loss"]), (tag, dtype)
+        off = 0
+        for (n, p), ref in zip(m.named_parameters(), g[f"{tag}/gradnorm"]):
+            gr = grad[off:off + p.numel()]
+            off += p.numel()
+            assert abs(gr.double().norm().item() - ref) <= gbar * ref, (tag, dtype, n)
+
+
+def test_mirror_without_outermost_linear_is_not_the_linear_mirror(shapes_fixture):
+    """the sine output layer changes the mirror's prediction (the fixture of a sine-output shape is not met by the
+    linear-output mirror), so the test above pins outermost_linear=False"""
+    import _wavelet_ref as wr
+    from oracle import siren_oracle as so
+    kw, H = _shapes()["h128_d5_sin_s40"]
+    m = _wavelet(**kw)
+    pred, _, _ = wr.loss_and_grads(wr.model_flat(m), 128, 5, so.synthetic_image(H, H, seed=5), 50.0, 30.0)
+    assert (pred - torch.tensor(shapes_fixture["h128_d5_sin_s40/pred"]).double()).abs().max().item() > 1e-2
+
+
+def test_engine_model_sub_network_is_engine_model_split_at_dlast():
+    """sub_forward16 + sub_backward16, fed the SIREN's own fp16 dL/dout at engine_model's 2^20 scale, are
+    oracle/engine_model.loss_and_grads(scratch=16) bit for bit: the WaveletSiren model reuses its rounding points"""
+    import _wavelet_ref as wr
+    from oracle import engine_model as em
+    from oracle import siren_oracle as so
+    for hidden, depth in ((64, 4), (32, 2)):
+        p = so.siren_init(hidden, depth, seed=0)
+        H = 24
+        grid, img = so.get_grid(H, H), so.synthetic_image(H, H, seed=5)
+        _, sse, grads, pred = em.loss_and_grads(p, grid, img, scratch=16)
+        pp, dfac, state = wr.sub_forward16(p, grid, 50.0, 30.0)
+        assert dfac is None and torch.equal(pp.reshape(H, H, 3), pred)
+        dl = em._rt((pp - img.reshape(-1, 3)) * torch.tensor(1.0 / (3 * H * H), dtype=torch.float32) * 2.0 ** 20, "f16")
+        for a, b in zip(grads, wr.sub_backward16(p, state, dl, 2.0 ** 20, 50.0, 30.0)):
+            assert torch.equal(a, b)
+
+
+def test_engine_model_prescale_comes_from_the_image():
+    import _wavelet_ref as wr
+    assert wr.gpre_of(4096) == 2.0 ** 28 and wr.gpre_of(24) == 2.0 ** 13 and wr.gpre_of(2) == 2.0 ** 6
+
+
+@pytest.mark.parametrize("tag", ["h32_d3_s24", "h128_d5_sin_s40", "h256_d4_sin_om_s48", "h181p_d4_s48", "h32_d16_s20",
+                                 "h64_d3_s2"])
+def test_engine_model_sits_at_the_fp16_gap_from_fp64(tag):
+    """engine_model_loss_and_grads (the engine's rounding points) against the fp64 mirror on the engine layout.  Measured:
+    prediction <= 5.9e-5 max abs with a linear output, 1.2e-3 with a sine output (omega 30 / 50 times the fp16 output
+    weights); loss <= 6.3e-5 relative; per-tensor gradient max |err| / max |ref| 1.0e-4 .. 3.7e-3 (h32_d16_s20).  Both
+    sides are bounded: a model that lost its fp16 roundings would sit near 0, one with a wrong rounding point or a missing
+    dfac far above."""
+    import _wavelet_ref as wr
+    from oracle import siren_oracle as so
+    kw, H = _shapes()[tag]
+    m = _wavelet(**kw)
+    c, W = m.cfg, m._engine_width
+    flat = _engine_flat(m)
+    img = so.synthetic_image(H, H, seed=5)
+    args = (c["first_omega_0"], c["hidden_omega_0"])
+    p64, l64, g64 = wr.loss_and_grads(flat, W, c["depth"], img, *args, outermost_linear=c["outermost_linear"])
+    pm, sm, gm = wr.engine_model_loss_and_grads(flat, W, c["depth"], img, *args, c["outermost_linear"])
+    assert pm.dtype == gm.dtype == torch.float64
+    assert 1e-6 < (pm - p64).abs().max().item() < (2.5e-3 if not c["outermost_linear"] else 1.5e-4), tag
+    assert abs(sm / (3 * H * H) - l64) < 1.5e-4 * l64, tag
+    worst = 0.0
+    for a, b in zip(wr.split_flat(gm, W, c["depth"])[0] + wr.split_flat(gm, W, c["depth"])[1],
+                    wr.split_flat(g64, W, c["depth"])[0] + wr.split_flat(g64, W, c["depth"])[1]):
+        if b.abs().max() == 0:   # padded-only rows / columns: exactly zero on both sides
+            assert a.abs().max() == 0, tag
+            continue
+        e = _rel(a, b)
+        assert e < 8e-3, (tag, e)
+        worst = max(worst, e)
+    assert worst > 5e-5, (tag, worst)
