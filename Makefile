@@ -4,7 +4,7 @@ PYTHON ?= python
 PKG := implicit-image-compression_amd
 KWARGS ?=
 
-.PHONY: build fit test test-gpu bench clean
+.PHONY: build fit decode test test-gpu bench clean
 
 ## build: compile libsiren_fit.so for gfx950
 build:
@@ -13,6 +13,10 @@ build:
 ## fit: implicit MLP image fitting, e.g. make fit KWARGS="mlp.hidden_size=256 img.height=1024 img.width=1024"
 fit: build
 	PYTHONPATH=$(PKG) $(PYTHON) -m implicit_image.fit $(KWARGS)
+
+## decode: render a run directory written by fit to a PPM, e.g. make decode KWARGS="decode.dir=outputs/synthetic/siren_synthetic/default decode.truth=synthetic"
+decode: build
+	PYTHONPATH=$(PKG) $(PYTHON) -m implicit_image.decode $(KWARGS)
 
 ## fit8: one fit per GPU over a comma sweep (per-image sharding), e.g. KWARGS="img.seed=0,1,2,3,4,5,6,7"
 fit8: build

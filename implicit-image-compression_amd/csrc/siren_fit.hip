@@ -65,12 +65,12 @@ static constexpr float kResScale = 1024.0f;
 //  the hidden layers', so it gets its own line in the per-kernel report)
 // (k_feather_*: the Feathermap update of sf_adam_step on a handle with sf_feather_attach, feather_kernels.hip)
 enum KernelId { K_FWD = 0, K_BWD_HIDDEN, K_BWD_LAST, K_DW_FIRST, K_REDUCE, K_SSE, K_ADAM, K_IMAGES, K_BWD_L1,
-                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_COUNT };
+                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_RENDER, K_COUNT };
 // (k_wv_*: the image-space composition of a WaveletSiren handle and its adjoint, wavelet_kernels.hip)
 static const char* kKernelNames[K_COUNT] = {"k_fwd",    "k_bwd_hidden", "k_bwd_last", "k_dw_first",
                                             "k_reduce", "k_sse",        "k_adam",     "k_images", "k_bwd_layer1",
                                             "k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat",
-                                            "k_wv_compose", "k_wv_adjoint", "k_wv_inject"};
+                                            "k_wv_compose", "k_wv_adjoint", "k_wv_inject", "k_render"};
 
 struct ProfRec {
   int id;
@@ -190,6 +190,9 @@ struct sf_engine {
   float* wv_gl = nullptr;       // two-pass only: [2][n*n][3] fp32 dL/dout of the sub-networks
   float* wv_dfac = nullptr;     // outermost_linear=False only: [2][n*n][3] d sin(om z)/dz of the sub-networks' outputs
   float* dfac_out = nullptr;    // sub-handle, sine output layer: its slice of wv_dfac (FwdArgs::dfac of training forwards)
+  // render handle (sf_render_create, siren_render.hip): parameters, forward images and coordinates only - no gradient, no
+  // optimiser state, no mask, no backward scratch; every training entry point refuses it
+  bool render = false;
 };
 
 namespace {
@@ -498,6 +501,27 @@ bool fwd_is_pipe(const sf_engine* h) {
 }
 // forward workgroups of a chunk with n_super 256-pixel groups (= the chunk's SSE partials)
 int fwd_grid(const sf_engine* h, int n_super) { return fwd_is_pipe(h) && n_super > h->dw_wg ? h->dw_wg : n_super; }
+
+// what every forward of a SIREN handle (width <= 256) is given for the chunk that starts at local pixel pix0: coordinates,
+// geometry, weight images and scales; the caller adds its outputs (scratch, target, prediction, partials)
+FwdArgs fwd_args_base(const sf_engine* h, long pix0, int n_super) {
+  FwdArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.row_begin = h->cfg.row_begin;
+  fa.pix0 = pix0; fa.npix = h->npix; fa.depth = h->D;
+  fa.l0tab = h->l0tab; fa.l0img = reinterpret_cast<const u32x4*>(h->l0img);
+  fa.wf = reinterpret_cast<const u32x4*>(h->wf);
+  fa.wf_last = reinterpret_cast<const u32x4*>(h->wf_last);
+  const double two_pi = 6.283185307179586476925286766559;
+  fa.sc_first = (float)((double)h->cfg.first_omega_0 / two_pi);
+  fa.sc_hidden = (float)((double)h->cfg.hidden_omega_0 / two_pi / (double)h->wscale);
+  fa.sc_last = 1.0f / h->wscale;
+  if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / two_pi); }
+  fa.nout = h->cfg.out_features;
+  fa.n_super = n_super;
+  fa.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
+  return fa;
+}
 
 int launch_fwd(sf_engine* h, const FwdArgs& a, int n_super, bool train) {
   switch (h->WD) {
@@ -1055,6 +1079,7 @@ int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse);
 enum { kPassFwd = 1, kPassBwd = 2, kPassAll = 3 };
 int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = kPassAll, long c_begin = 0,
              long c_end = -1) {
+  if (h->render) return fail(SF_ERR_INVALID, "a render handle (sf_render_create) runs sf_render only");
   if (train) h->fth_fresh = false;
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   if (((train && !h->ext_dout) || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
@@ -1073,27 +1098,13 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = 
     if (px > h->chunk_px) px = h->chunk_px;
     const int n_super = (int)((px + kSuper - 1) / kSuper);
     const long n_pb = (long)n_super * kWavesFwd;
-    FwdArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.row_begin = h->cfg.row_begin;
-    fa.pix0 = pix0; fa.npix = h->npix; fa.depth = D;
-    fa.l0tab = h->l0tab; fa.l0img = reinterpret_cast<const u32x4*>(h->l0img);
-    fa.wf = reinterpret_cast<const u32x4*>(h->wf);
-    fa.wf_last = reinterpret_cast<const u32x4*>(h->wf_last);
-    const double two_pi = 6.283185307179586476925286766559;
-    fa.sc_first = (float)((double)h->cfg.first_omega_0 / two_pi);
-    fa.sc_hidden = (float)((double)h->cfg.hidden_omega_0 / two_pi / (double)h->wscale);
-    fa.sc_last = 1.0f / h->wscale;
-    if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / two_pi); }
+    FwdArgs fa = fwd_args_base(h, pix0, n_super);
     fa.P = h->Pbuf; fa.p_stride = h->p_stride; fa.Dlast = h->Dlast;
     fa.dfac = train ? h->dfac_out : nullptr;
     fa.img = h->img;
-    fa.nout = h->cfg.out_features;
     fa.gscale = h->d8 ? kResScale : (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total));
     fa.pred = pred;
     fa.sse_part = h->sse_part + sse_off;
-    fa.n_super = n_super;
-    fa.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
     const int n_fwd_wg = fwd_grid(h, n_super);
 #ifdef SF_EXPERIMENT_STAMP
     fa.dbg = h->sse_part + h->n_sse;   // 64 spare floats behind the partials
@@ -1368,7 +1379,9 @@ int sf_abi_version(void) { return SF_ABI_VERSION; }
 const char* sf_last_error(void) { return g_err.c_str(); }
 
 static void set_scratch_strides(sf_engine* h);
-int sf_create(const sf_config* cfg, sf_handle** out) try {
+// sf_create and sf_render_create (siren_render.hip): one validation, one geometry; a render handle allocates the forward's
+// inputs only
+static int create_handle(const sf_config* cfg, sf_handle** out, bool render) {
   if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
@@ -1379,6 +1392,9 @@ int sf_create(const sf_config* cfg, sf_handle** out) try {
       cfg->hidden != 1024)
     return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128, 256, 512 or 1024 in this build");
   if (cfg->hidden > 256 && cfg->depth < 3) return fail(SF_ERR_INVALID, "hidden > 256 needs depth >= 3");
+  if (render && cfg->hidden > 256)
+    return fail(SF_ERR_INVALID, "sf_render_create: the render kernel is not built for the wide path (hidden 512 / 1024): "
+                                "run the model's own forward on the host side");
   if (cfg->compute_dtype != SF_BF16 && cfg->compute_dtype != SF_F16)
     return fail(SF_ERR_INVALID, "compute_dtype must be SF_BF16 or SF_F16");
   if (cfg->height < 1 || cfg->width < 1) return fail(SF_ERR_INVALID, "bad image size");
@@ -1415,6 +1431,7 @@ int sf_create(const sf_config* cfg, sf_handle** out) try {
   h->D = cfg->depth;
   h->WD = cfg->hidden;
   h->wide = cfg->hidden > 256;
+  h->render = render;
   {
     // auto (fp16 operands, hidden <= 256): phase bytes always; fp8 deltas (format 8) when the image has >= 2^20 pixels - a
     // gradient then sums the zero-mean fp8 rounding over >= 10^6 terms (within the 0.05 dB criterion on every reference
@@ -1427,6 +1444,7 @@ int sf_create(const sf_config* cfg, sf_handle** out) try {
     // width 512, where a reference-minted fixture at 2^20 pixels pins them (tests/golden/plateau_ns_512x4_1024.npz: -0.0002 dB);
     // phase bytes only above)
     if (fmt == 0) fmt = cfg->compute_dtype != SF_F16 ? 16 : h->wide ? (mega ? (cfg->hidden <= 512 ? 8 : 12) : 16) : (mega ? 8 : 12);
+    if (render) { fmt = 16; h->fmt_auto = false; }   // no scratch at all: nothing of the byte formats applies
     h->cfg.scratch_format = fmt;
     h->s8 = fmt == 8 || fmt == 12;
     h->d8 = fmt == 8;
@@ -1470,6 +1488,17 @@ int sf_create(const sf_config* cfg, sf_handle** out) try {
   };
   int rc = SF_OK;
 #define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
+  if (render) {   // parameters, forward weight images, layer-0 table / image, the two coordinate vectors
+    ALLOC(h->params, h->P * 4);
+    ALLOC(h->wf, (size_t)(D - 2 > 0 ? D - 2 : 1) * FwdGeom(WD).PIECES * 1024); ALLOC(h->wf_last, (size_t)(WD / 16 + 1) * 1024);
+    ALLOC(h->l0tab, (size_t)WD * 16);
+    if (WD == 256) ALLOC(h->l0img, (size_t)(WD / 32) * 1024);
+    ALLOC(h->gh, (size_t)cfg->height * 4); ALLOC(h->gw, (size_t)cfg->width * 4);
+    if (rc) { sf_destroy(h); return rc; }
+    hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
+    *out = h;
+    return SF_OK;
+  }
   ALLOC(h->params, h->P * 4); ALLOC(h->grads, h->P * 4); ALLOC(h->m, h->P * 4); ALLOC(h->v, h->P * 4);
   ALLOC(h->mask, h->P * 4);
   const size_t img_elems = (size_t)(D - 2 > 0 ? D - 2 : 1) * WD * WD;
@@ -1510,7 +1539,8 @@ int sf_create(const sf_config* cfg, sf_handle** out) try {
   hipMemsetAsync(h->v, 0, h->P * 4, h->stream);
   *out = h;
   return SF_OK;
-} SF_CATCH
+}
+int sf_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, false); } SF_CATCH
 
 // FourierNet handle: the same sf_engine, run by fourier_kernels.hip (run_pass_fourier); every other entry point is shared
 int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
@@ -1829,6 +1859,13 @@ int sf_param_offset(const sf_handle* h, int32_t layer, int64_t* w, int64_t* b) t
   return SF_OK;
 } SF_CATCH
 
+// training entry points on a render handle: an argument error, before anything is touched
+static int refuse_render(const char* fn) {
+  return fail(SF_ERR_INVALID, std::string(fn) + ": a render handle (sf_render_create) holds parameters and forward images "
+                                                "only - no gradient, optimiser state, mask or backward scratch");
+}
+#define SF_NO_RENDER(h, fn) do { if ((h) && (h)->render) return refuse_render(fn); } while (0)
+
 static int copy_in(sf_engine* h, float* dst, const float* src) {
   if (!h || !src) return fail(SF_ERR_INVALID, "null argument");
   DevGuard dev_guard(h->cfg.device);
@@ -1847,8 +1884,12 @@ int sf_set_params(sf_handle* h, const float* p) try {
   return rc;
 } SF_CATCH
 int sf_get_params(sf_handle* h, float* p) try { return copy_out(h, p, h ? h->params : nullptr); } SF_CATCH
-int sf_get_grads(sf_handle* h, float* p) try { return copy_out(h, p, h ? h->grads : nullptr); } SF_CATCH
+int sf_get_grads(sf_handle* h, float* p) try {
+  SF_NO_RENDER(h, "sf_get_grads");
+  return copy_out(h, p, h ? h->grads : nullptr);
+} SF_CATCH
 int sf_set_grads(sf_handle* h, const float* p) try {
+  SF_NO_RENDER(h, "sf_set_grads");
   if (h) h->fth_fresh = false;
   return copy_in(h, h ? h->grads : nullptr, p);
 } SF_CATCH
@@ -1890,6 +1931,7 @@ static int switch_scratch_format(sf_engine* h, int fmt) {
 }
 int sf_set_masks(sf_handle* h, const float* p) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_set_masks");
   DevGuard dev_guard(h->cfg.device);
   if (!p) { h->has_mask = false; return SF_OK; }
   if (h->feather) return fail(SF_ERR_INVALID, "sf_set_masks: a Feathermap handle is dense (masking.dense: True)");
@@ -1903,6 +1945,7 @@ int sf_set_masks(sf_handle* h, const float* p) try {
 } SF_CATCH
 int sf_get_adam_state(sf_handle* h, float* m, float* v, int64_t* step) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_get_adam_state");
   DevGuard dev_guard(h->cfg.device);
   if (m) { int rc = copy_out(h, m, h->m); if (rc) return rc; }
   if (v) { int rc = copy_out(h, v, h->v); if (rc) return rc; }
@@ -1911,6 +1954,7 @@ int sf_get_adam_state(sf_handle* h, float* m, float* v, int64_t* step) try {
 } SF_CATCH
 int sf_set_adam_state(sf_handle* h, const float* m, const float* v, int64_t step) try {
   if (!h || step < 0) return fail(SF_ERR_INVALID, "bad argument");
+  SF_NO_RENDER(h, "sf_set_adam_state");
   DevGuard dev_guard(h->cfg.device);
   if (m) { int rc = copy_in(h, h->m, m); if (rc) return rc; }
   if (v) { int rc = copy_in(h, h->v, v); if (rc) return rc; }
@@ -1919,6 +1963,7 @@ int sf_set_adam_state(sf_handle* h, const float* m, const float* v, int64_t step
 } SF_CATCH
 int sf_state_ptr(sf_handle* h, int32_t which, float** p) try {
   if (!h || !p) return fail(SF_ERR_INVALID, "null argument");
+  if (h->render && which >= 1 && which <= 4) return refuse_render("sf_state_ptr");
   switch (which) {
     case 0: *p = h->params; return SF_OK;
     case 1: *p = h->grads; return SF_OK;
@@ -1931,12 +1976,14 @@ int sf_state_ptr(sf_handle* h, int32_t which, float** p) try {
 
 int sf_sse_ptr(sf_handle* h, double** p) try {
   if (!h || !p) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_sse_ptr");
   *p = h->sse_dev;
   return SF_OK;
 } SF_CATCH
 
 int sf_debug_scratch(sf_handle* h, int32_t which, void** p, int64_t* bytes) try {
   if (!h || !p || !bytes) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_debug_scratch");
   if (h->fourier) return fail(SF_ERR_INVALID, "sf_debug_scratch: a FourierNet handle has no phase / delta scratch");
   if (h->wavelet) return fail(SF_ERR_INVALID, "sf_debug_scratch: the scratch of a WaveletSiren handle lives in its sub-networks");
   const int D = h->D;
@@ -1971,8 +2018,9 @@ int sf_set_coords(sf_handle* h, const float* rows, const float* cols) try {
   HIPCHK(hipMemcpyAsync(h->gw, cols, (size_t)h->cfg.width * 4, hipMemcpyDeviceToDevice, h->stream));
   // The forward indexes these vectors; the gradient kernels of layer 0 / layer 1 re-derive the coordinate of a
   // pixel as i/(n-1) instead of loading it.  Both agree only for get_grid()'s linspace(0,1,n) (data.py:82-83):
-  // anything else is rejected here instead of training on inconsistent coordinates.
-  {
+  // anything else is rejected here instead of training on inconsistent coordinates.  A render handle only indexes them
+  // (a window of a grid is a slice of the two vectors), so it takes whatever it is given.
+  if (!h->render) {
     std::vector<float> hv((size_t)h->cfg.height + h->cfg.width);
     HIPCHK(hipMemcpyAsync(hv.data(), h->gh, (size_t)h->cfg.height * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(hv.data() + h->cfg.height, h->gw, (size_t)h->cfg.width * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1992,6 +2040,7 @@ int sf_set_coords(sf_handle* h, const float* rows, const float* cols) try {
 } SF_CATCH
 int sf_set_target(sf_handle* h, const float* img) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_set_target");
   h->img = img;
   return SF_OK;
 } SF_CATCH
@@ -2010,6 +2059,7 @@ int sf_forward(sf_handle* h, float* pred, double* sse_out) try {
 
 int sf_forward_backward(sf_handle* h, double* sse_out) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_forward_backward");
   DevGuard dev_guard(h->cfg.device);
   int rc = run_pass(h, true, nullptr, true);
   if (rc) return rc;
@@ -2019,6 +2069,7 @@ int sf_forward_backward(sf_handle* h, double* sse_out) try {
 
 int sf_adam_step(sf_handle* h, float lr) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_adam_step");
   DevGuard dev_guard(h->cfg.device);
   h->step += 1;
   AdamArgs a;
@@ -2133,6 +2184,7 @@ static int step_replay(sf_engine* h, const float* lr, int n, float* loss_out) {
 
 int sf_step(sf_handle* h, const float* lr, int32_t n_steps, float* loss_out) try {
   if (!h || !lr || n_steps < 0) return fail(SF_ERR_INVALID, "bad argument");
+  SF_NO_RENDER(h, "sf_step");
   DevGuard dev_guard(h->cfg.device);
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   if (!h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
@@ -2171,6 +2223,7 @@ int sf_step(sf_handle* h, const float* lr, int32_t n_steps, float* loss_out) try
 
 int sf_set_graph_replay(sf_handle* h, int32_t on) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_set_graph_replay");
   h->want_replay = on != 0;
   return SF_OK;
 } SF_CATCH
@@ -2225,6 +2278,7 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
                   float* centroids_dev, int32_t centroids_cap, int32_t* n_centroids_dev, int64_t* labels_dev,
                   float* new_weight_dev) try {
   if (!h || !w_dev || !centers_dev || !centroids_dev) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_kmeans_fit");
   if (n <= 0 || K < 1 || K >= kKmMaxK || centroids_cap < K + 1 || iter_limit < 0)
     return fail(SF_ERR_INVALID, "sf_kmeans_fit: need n > 0, 1 <= K < 512, centroids_cap >= K + 1");
   DevGuard dev_guard(h->cfg.device);
@@ -2253,6 +2307,7 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
 int sf_feather_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, const int32_t* logical_out,
                       const int32_t* logical_in) try {
   if (!h || !logical_out || !logical_in) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_feather_attach");
   if (h->fourier || h->wavelet) return fail(SF_ERR_INVALID, "sf_feather_attach: Feathermap runs on SIREN handles only");
   if (h->feather) return fail(SF_ERR_INVALID, "sf_feather_attach: the handle already has a feather state");
   if (h->cfg.row_begin != 0 || h->cfg.row_end != h->cfg.height)
@@ -2332,6 +2387,7 @@ int sf_feather_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, cons
 
 int sf_feather_state_ptr(sf_handle* h, int32_t which, float** dev_ptr, int64_t* len) try {
   if (!h || !dev_ptr) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_feather_state_ptr");
   if (!h->feather) return fail(SF_ERR_STATE, "sf_feather_state_ptr: no feather state (sf_feather_attach)");
   float* ps[] = {h->fth_p, h->fth_g, h->fth_m, h->fth_v, h->fth_V};
   if (which < 0 || which > 4) return fail(SF_ERR_INVALID, "bad feather state selector");
@@ -2342,6 +2398,7 @@ int sf_feather_state_ptr(sf_handle* h, int32_t which, float** dev_ptr, int64_t* 
 
 int sf_feather_materialise(sf_handle* h) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_feather_materialise");
   if (!h->feather) return fail(SF_ERR_STATE, "sf_feather_materialise: no feather state (sf_feather_attach)");
   DevGuard dev_guard(h->cfg.device);
   return feather_materialise(h);
@@ -2349,6 +2406,7 @@ int sf_feather_materialise(sf_handle* h) try {
 
 int sf_feather_adjoint(sf_handle* h) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_feather_adjoint");
   if (!h->feather) return fail(SF_ERR_STATE, "sf_feather_adjoint: no feather state (sf_feather_attach)");
   DevGuard dev_guard(h->cfg.device);
   return feather_adjoint(h);
@@ -2363,3 +2421,5 @@ int sf_debug_throw(int32_t kind) try {
 } SF_CATCH
 
 }  // extern "C"
+
+#include "siren_render.hip"

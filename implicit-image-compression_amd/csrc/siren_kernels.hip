@@ -267,6 +267,7 @@ struct FwdArgs {
   float* dbg;              // SF_EXPERIMENT_STAMP builds only
   float* dfac;             // optional [npix][nout]: a training pass with a sine output layer writes d sin(om z)/dz here
                            // (WaveletSiren sub-handles: their dL/dout comes from k_wv_adjoint / k_wv_inject, which apply it)
+  uint8_t* rgb8;           // RENDER kernels only: optional [npix][nout] bytes, min(max((int)(pred * 255), 0), 255)
 };
 
 // Forward weight image of one hidden layer, as stored in HBM and copied verbatim into LDS:
@@ -334,8 +335,14 @@ DEV void fwd_sse_partial(const FwdArgs& a, float sse, int lane, int wave, int ti
   }
 }
 
-template <int WD, typename OP, bool TRAIN, bool S8 = false>
+// last-layer accumulator -> fp32 prediction and / or packed bytes of one pixel block (siren_render.hip): the epilogue of the
+// RENDER instantiations, which read no target and write no phases, no dL/dout and no SSE partial
+DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, bool valid, int lane, int h);
+
+// RENDER (inference only, sf_render): TRAIN = false with fwd_render_out in place of the residual epilogue
+template <int WD, typename OP, bool TRAIN, bool S8 = false, bool RENDER = false>
 __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
+  static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
   using IM = FwdImg<WD>;
   constexpr int NT = IM::NT, KS = IM::KS, H0 = IM::H0;
   constexpr int SPT = S8 ? 1 : 2;   // phase stores per tile epilogue (what the counted vmcnt waits leave in flight)
@@ -360,9 +367,11 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
   const float x0 = (a.gh[a.row_begin + row] - 0.5f) * 2.0f;  // siren.py:128
   const float x1 = (a.gw[col] - 0.5f) * 2.0f;
   float tgt[3] = {0.f, 0.f, 0.f};
-  if (a.img && h == 0 && valid) {
+  if constexpr (!RENDER) {
+    if (a.img && h == 0 && valid) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) if (c < a.nout) tgt[c] = a.img[pix * a.nout + c];
+      for (int c = 0; c < 3; ++c) if (c < a.nout) tgt[c] = a.img[pix * a.nout + c];
+    }
   }
   // the ordinary loads above are consumed before the first DMA is issued, so the compiler's
   // vmcnt(0) for them does not drain the weight prefetch
@@ -514,7 +523,12 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
 #pragma unroll
   for (int s = 0; s < KS; ++s) acc = OP::mfma(sW[s * 64 + lane], B[s], acc);
 
-  fwd_sse_partial(a, fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h), lane, wave, tid, sRed);
+  if constexpr (RENDER) {
+    fwd_render_out(a, acc, pix, pb, valid, lane, h);
+    (void)sRed;
+  } else {
+    fwd_sse_partial(a, fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h), lane, wave, tid, sRed);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -561,8 +575,9 @@ DEV uint32_t pack_h2(_Float16 a, _Float16 b) {
 #ifndef SF_FWD_PD
 #define SF_FWD_PD 4
 #endif
-template <typename OP, bool TRAIN, bool S8, int PD = SF_FWD_PD>
+template <typename OP, bool TRAIN, bool S8, int PD = SF_FWD_PD, bool RENDER = false>
 __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
+  static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
   constexpr int WD = 256;
   using IM = FwdImg<WD>;
   constexpr int NT = IM::NT, KS = IM::KS, H0 = IM::H0, NG = NT * KS;
@@ -611,9 +626,11 @@ __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
     const unsigned col = (unsigned)(pcl - (long)row * a.W);
     f.gh = a.gh[a.row_begin + (int)row];
     f.gw = a.gw[col];
-    if (a.img && h == 0 && ok) {
+    if constexpr (!RENDER) {
+      if (a.img && h == 0 && ok) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) if (c < a.nout) f.t[c] = a.img[px * a.nout + c];
+        for (int c = 0; c < 3; ++c) if (c < a.nout) f.t[c] = a.img[px * a.nout + c];
+      }
     }
     return f;
   };
@@ -880,9 +897,10 @@ __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
 #ifdef SF_EXPERIMENT_STAMP
     st_pipe += __builtin_amdgcn_s_memtime() - t_x1;
 #endif
-    sse_acc += fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h);
+    if constexpr (RENDER) fwd_render_out(a, acc, pix, pb, valid, lane, h);
+    else sse_acc += fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h);
   }
-  fwd_sse_partial(a, sse_acc, lane, wave, tid, sRed);
+  if constexpr (!RENDER) fwd_sse_partial(a, sse_acc, lane, wave, tid, sRed);
 #ifdef SF_EXPERIMENT_STAMP
   if (a.dbg && lane == 0 && (wave == 0 || wave == 5) && (blockIdx.x == 3 || blockIdx.x == 200)) {
     float* o = a.dbg + ((blockIdx.x == 3 ? 0 : 2) + (wave == 0 ? 0 : 1)) * 8;
@@ -1566,7 +1584,7 @@ __global__ void k_images(ImgArgs a) {
     const float wbwd = Wl[(long)(16 * s + pi_perm(h, j)) * WD + 32 * tile + r] * bsc;
     const long dst = ((long)(l - 1) * G.PIECES + G.tile_piece(tile) + s) * 512 + lane * 8 + j;
     a.wf[dst] = a.fwd_is_f16 ? to_f16(wfwd) : to_bf16(wfwd);
-    a.wb[gid] = a.fwd_is_f16 ? to_f16(wbwd) : to_bf16(wbwd);
+    if (a.wb) a.wb[gid] = a.fwd_is_f16 ? to_f16(wbwd) : to_bf16(wbwd);   // (render handles keep no backward images)
   }
   if (gid < (long)(a.depth - 2) * WD) {  // hidden biases into the bias pieces (fp32, pre-scaled)
     const int l = (int)(gid / WD) + 1, n = (int)(gid % WD), nt = n / 32;
@@ -1588,7 +1606,7 @@ __global__ void k_images(ImgArgs a) {
     float* piece = reinterpret_cast<float*>(a.wf_last + (long)KS * 512);
     piece[gid] = (gid < a.out_features) ? a.params[a.off_b[L] + gid] * a.wscale : 0.f;
   }
-  if (gid < (long)NT * 64 * 8) {  // last layer backward image: NT tiles x 1 k-step
+  if (a.wb_last && gid < (long)NT * 64 * 8) {  // last layer backward image: NT tiles x 1 k-step
     long e = gid;
     const int j = e & 7; e >>= 3;
     const int lane = e & 63; e >>= 6;

@@ -1,0 +1,141 @@
+// siren_render.hip — the inference-only path of the engine: sf_render_create / sf_render (include/siren_fit.h).
+//
+// A decoder needs the picture, not a training step.  The kernels are the RENDER instantiations of k_fwd<WD> and k_fwd_pipe
+// (siren_kernels.hip): the evaluation forward (no phase stores, so the pipeline's counted waits are those of TRAIN = false)
+// without the target fetch, the residual, the SSE partial and its workgroup reduction, and with fwd_render_out below as the
+// last-layer epilogue.  Up to the fp32 prediction nothing differs from the training forward - the same weight images, the
+// same MFMA chain, the same v_sin_f32 - so sf_render's pred is bit-identical to sf_forward's (tests/test_gpu_render.py).
+//
+// Bytes: u8 = min(max((int)(pred * 255.0f), 0), 255), the product in fp32 and truncated toward zero - the reference's
+// (pred * 255).int() (implicit_image/utils/train_helper.py:52, eval_epoch), clamped to what a file can hold.  A wave owns
+// 32 consecutive pixels = 32 * out_features consecutive bytes, which start on a dword boundary (32 divides the pixel
+// index): every lane packs its own pixel's bytes into one register, lane d gathers dword d of the block with four
+// ds_bpermute and stores it, so a wave writes 8 * out_features whole dwords (24 for RGB) in one store instruction.  Only the
+// picture's last, ragged dword is written byte by byte.
+//
+// This file is included at the end of siren_fit.hip (one translation unit, as every kernel file of the library).
+
+namespace sf {
+
+DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, bool valid, int lane, int h) {
+  const int nout = a.nout;
+  uint32_t mine = 0u;   // this lane's pixel: channel c in byte c (lanes of the upper half hold padded rows: never selected)
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (c >= nout) break;
+    // exactly fwd_residual's prediction
+    float o = acc[c] * a.sc_last;
+    if (a.last_om_rev != 0.f) {
+      const float tt = o * a.last_om_rev;
+      o = __builtin_amdgcn_sinf(tt);
+    }
+    const float p = o * 0.5f + 0.5f;  // siren.py:131
+    if (a.pred && h == 0 && valid) a.pred[pix * nout + c] = p;
+    int q = (int)(p * 255.0f);        // v_cvt_i32_f32: toward zero
+    q = q < 0 ? 0 : (q > 255 ? 255 : q);
+    mine |= (uint32_t)q << (8 * c);
+  }
+  if (!a.rgb8) return;
+  const long px0 = a.pix0 + pb * 32;                       // first pixel of this wave's block (a multiple of 32)
+  const long left = a.npix - px0;
+  const int nbytes = left >= 32 ? 32 * nout : (left > 0 ? (int)left * nout : 0);   // bytes of the block inside the picture
+  uint32_t word = 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = 4 * lane + j;                            // byte k of the block = pixel k / nout, channel k % nout
+    const int src = nout == 3 ? k / 3 : (nout == 2 ? k >> 1 : k);
+    const int ch = k - src * nout;
+    const uint32_t v = (uint32_t)__shfl((int)mine, src & 31);   // (lanes >= 8 * nout gather nothing they store)
+    word |= ((v >> (8 * ch)) & 0xffu) << (8 * j);
+  }
+  if (lane < 8 * nout) {
+    uint8_t* blk = a.rgb8 + px0 * nout;                    // dword aligned: sf_render checks the base, 32 | px0
+    if (4 * lane + 4 <= nbytes) {
+      reinterpret_cast<uint32_t*>(blk)[lane] = word;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * lane + j < nbytes) blk[4 * lane + j] = (uint8_t)(word >> (8 * j));
+    }
+  }
+}
+
+}  // namespace sf
+
+namespace {
+
+template <int WD>
+int launch_render_t(sf_engine* h, const FwdArgs& a, int n_super) {
+  const size_t lds = fwd_lds_bytes(WD);
+  if (h->cfg.compute_dtype == SF_F16) {
+    int rc = set_lds(k_fwd<WD, OpF16, false, false, true>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_fwd<WD, OpF16, false, false, true>), dim3(n_super), dim3(512), lds, h->stream, a);
+  } else {
+    int rc = set_lds(k_fwd<WD, OpBF16, false, false, true>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_fwd<WD, OpBF16, false, false, true>), dim3(n_super), dim3(512), lds, h->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
+int launch_render_pipe(sf_engine* h, const FwdArgs& a, int n_wg) {
+  const size_t lds = (size_t)FwdGeom(256).PIECES * 1024 + (size_t)(256 / 32) * 1024 + 64;   // as launch_fwd_pipe
+  if (h->cfg.compute_dtype == SF_F16) {
+    int rc = set_lds(k_fwd_pipe<OpF16, false, false, SF_FWD_PD, true>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_fwd_pipe<OpF16, false, false, SF_FWD_PD, true>), dim3(n_wg), dim3(512), lds, h->stream, a);
+  } else {
+    int rc = set_lds(k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, true>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, true>), dim3(n_wg), dim3(512), lds, h->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
+// the kernel family sf_forward picks for the handle (fwd_is_pipe), in its RENDER form
+int launch_render(sf_engine* h, const FwdArgs& a, int n_wg) {
+  switch (h->WD) {
+    case 32: return launch_render_t<32>(h, a, n_wg);
+    case 64: return launch_render_t<64>(h, a, n_wg);
+    case 128: return launch_render_t<128>(h, a, n_wg);
+    case 256: return fwd_is_pipe(h) ? launch_render_pipe(h, a, n_wg) : launch_render_t<256>(h, a, n_wg);
+  }
+  return fail(SF_ERR_INVALID, "unsupported hidden width");
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_render_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, true); } SF_CATCH
+
+int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try {
+  if (!h) return fail(SF_ERR_INVALID, "null argument");
+  if (!rgb8 && !pred) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev and pred_dev are both NULL");
+  if (h->wide || h->fourier || h->wavelet)
+    return fail(SF_ERR_INVALID, "sf_render: built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create)");
+  if (((uintptr_t)rgb8 & 3u) != 0) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev must be 4-byte aligned");
+  if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
+  DevGuard dev_guard(h->cfg.device);
+  int rc = refresh_images(h);
+  if (rc) return rc;
+  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
+  for (long c = 0; c < n_chunks; ++c) {
+    const long pix0 = c * h->chunk_px;   // a multiple of 256: every wave's 32-pixel block starts on a dword of rgb8
+    long px = h->npix - pix0;
+    if (px > h->chunk_px) px = h->chunk_px;
+    const int n_super = (int)((px + kSuper - 1) / kSuper);
+    FwdArgs fa = fwd_args_base(h, pix0, n_super);
+    fa.pred = pred;
+    fa.rgb8 = rgb8;
+    const double out_bytes = (pred ? 4.0 : 0.0) + (rgb8 ? 1.0 : 0.0);
+    Launch L(h, K_RENDER, flops_fwd_px(h) * n_super * (double)kSuper, n_super * (double)kSuper * h->cfg.out_features * out_bytes);
+    rc = launch_render(h, fa, fwd_grid(h, n_super));
+    L.done();
+    if (rc) return rc;
+  }
+  return SF_OK;
+} SF_CATCH
+
+}  // extern "C"

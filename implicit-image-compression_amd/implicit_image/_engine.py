@@ -110,7 +110,12 @@ def load_library():
         "sf_wavelet_create": [C.POINTER(sf_wavelet_config), C.POINTER(H)],
         "sf_wavelet_debug": [H, C.c_int32, F, F, F, F, F],
     }
-    for name, args in list(feather.items()) + list(wavelet.items()):
+    # inference-only entry points (csrc/siren_render.hip): the same rule
+    render = {
+        "sf_render_create": [C.POINTER(sf_config), C.POINTER(H)],
+        "sf_render": [H, C.c_void_p, F],
+    }
+    for name, args in list(feather.items()) + list(wavelet.items()) + list(render.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.argtypes = args
@@ -130,6 +135,10 @@ def has_feather(lib) -> bool:
 
 def has_wavelet(lib) -> bool:
     return all(hasattr(lib, s) for s in ("sf_wavelet_create", "sf_wavelet_debug"))
+
+
+def has_render(lib) -> bool:
+    return all(hasattr(lib, s) for s in ("sf_render_create", "sf_render"))
 
 
 def exported_symbols() -> Sequence[str]:
@@ -179,7 +188,7 @@ class SirenEngine:
                         first_omega_0, hidden_omega_0, int(bool(outermost_linear)), DTYPES[compute_dtype],
                         betas[0], betas[1], eps, device, stream, chunk_pixels, scratch_format)
         self.h = C.c_void_p()
-        _check(self.lib.sf_create(C.byref(cfg), C.byref(self.h)))
+        _check(self._create(cfg))
         n = C.c_int64()
         _check(self.lib.sf_num_params(self.h, C.byref(n)))
         self.num_params = n.value
@@ -189,6 +198,23 @@ class SirenEngine:
         self.out_features = out_features
         self._target = None
         self._views = {}
+
+    def _create(self, cfg) -> int:
+        return self.lib.sf_create(C.byref(cfg), C.byref(self.h))
+
+    def render(self, want_u8: bool = True, want_pred: bool = False):
+        """sf_render on this handle's rows, no host sync: (rgb8 [rows, W, C] uint8 or None, pred [rows, W, C] fp32 or None).
+        u8 = min(max((int)(pred * 255), 0), 255); pred is bit-identical to forward()'s."""
+        if not has_render(self.lib):
+            raise RuntimeError(f"{_LIB_PATH} has no sf_render entry point (built before the render path): rebuild it with "
+                               "`python __graft_entry__.py build`")
+        if not (want_u8 or want_pred):
+            raise ValueError("render: ask for bytes, the fp32 prediction, or both")
+        shape = (self.row_end - self.row_begin, self.width, self.out_features)
+        u8 = torch.empty(shape, dtype=torch.uint8, device=self.device) if want_u8 else None
+        pred = torch.empty(shape, device=self.device) if want_pred else None
+        _check(self.lib.sf_render(self.h, u8.data_ptr() if want_u8 else None, pred.data_ptr() if want_pred else None))
+        return u8, pred
 
     @property
     def scratch_format(self) -> int:
@@ -379,6 +405,25 @@ class SirenEngine:
             rep[name.value.decode()] = {"total_ms": ms.value, "launches": cnt.value,
                                         "flops_per_launch": fl.value, "bytes_per_launch": by.value}
         return rep
+
+
+class RenderEngine(SirenEngine):
+    """Inference-only handle (sf_render_create): parameters, forward weight images and the two coordinate vectors - no
+    gradient, optimiser state, mask or backward scratch.  set_params / get_params / set_coords / render / the profiling
+    calls work; every training call raises with the library's message.  set_coords takes any two vectors (a window of a
+    grid is a slice of its linspace vectors); hidden 512 / 1024 is refused (no render kernel on the wide path)."""
+
+    def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
+                 hidden_omega_0: float = 30.0, outermost_linear: bool = True, out_features: int = 3,
+                 compute_dtype: str = "f16", device: int = 0, row_begin: int = 0, row_end: int = 0, chunk_pixels: int = 0):
+        super().__init__(height, width, hidden, depth, first_omega_0, hidden_omega_0, outermost_linear, out_features,
+                         compute_dtype, device, row_begin, row_end, chunk_pixels)
+
+    def _create(self, cfg) -> int:
+        if not has_render(self.lib):
+            raise RuntimeError(f"{_LIB_PATH} has no sf_render_create entry point (built before the render path): rebuild it "
+                               "with `python __graft_entry__.py build`")
+        return self.lib.sf_render_create(C.byref(cfg), C.byref(self.h))
 
 
 class FourierEngine(SirenEngine):

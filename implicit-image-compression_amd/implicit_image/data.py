@@ -71,6 +71,17 @@ def read_ppm(path: str) -> torch.Tensor:
     return torch.from_numpy(arr.astype(np.int32))
 
 
+def write_ppm(path: str, img) -> None:
+    """[H, W, 3] uint8 (tensor or ndarray) -> binary P6 PPM, maxval 255: what read_ppm reads back exactly."""
+    import numpy as np
+    arr = img.detach().cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+    if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError(f"write_ppm expects uint8 [H, W, 3], got {arr.dtype} {tuple(arr.shape)}")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (arr.shape[1], arr.shape[0]))
+        f.write(np.ascontiguousarray(arr).tobytes())
+
+
 def load_img(path: str, height: int = 256, width: int = 256, bits: int = 8, plot: bool = False,
              crop_mode: str = "centre-crop", save_gt: bool = False, seed: int = 1234, **kwargs) -> torch.Tensor:
     """[H, W, 3] float32 image in [0,1] (reference signature).  `path` = "synthetic" (or

@@ -1,0 +1,328 @@
+"""`make decode` entry: turn a run directory written by `fit` back into a picture.
+
+    python -m implicit_image.decode decode.dir=outputs/<image>/<experiment>/<tag> [key=value ...]
+
+Loads `model_quantized/` (compressed_weights.data + meta_data.json, through decompress_state_dict: codebook layers come
+back dense, fp16 values widened to fp32) when present, else `model.pth`; `decode.source=container|pth` forces one.  The
+model shape comes from `decode.json`, which `fit` writes next to them; the same key=value overrides as `fit` replace any
+of it, so a container written before that file existed (or by the reference) decodes with `mlp.hidden_size=... mlp.depth=...
+img.height=... img.width=...` on the command line.
+
+decode.* keys
+  decode.dir        the run directory (required)
+  decode.source     container | pth (default: the container when there is one)
+  decode.height, decode.width   output size (default: the fitted size); any other size renders the same unit square at
+                    that resolution (torch.linspace(0, 1, n) per axis, the reference's get_grid)
+  decode.rows=a:b decode.cols=c:d   a window of that grid (the coordinate vectors are sliced on the host)
+  decode.band_rows  rows rendered per kernel call (default: as many as keep one band's bytes under 256 MiB)
+  decode.out        the PPM to write (default <decode.dir>/decoded.ppm; binary P6, 8 bit)
+  decode.truth      <ppm> or synthetic[:seed]: print loss / PSNR / PSNR_8bit with eval_epoch's formulas
+  decode.device     cuda ordinal (default 0)
+
+SIREN of hidden width 32 / 64 / 128 / 256 runs the engine's render kernel (sf_render: bytes straight from the last-layer
+epilogue, no training state on the device).  Everything else - mlp=fourier, mlp=wavelet_siren, SIREN 512 / 1024, widths the
+engine zero-pads - builds the registry model, loads the state dict, runs its own forward and converts with the same
+formula in torch.  `render_path` decides and the log names the path that ran.
+"""
+import json
+import logging
+import math
+import os
+import sys
+from collections import OrderedDict
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from .config import Cfg, _load_yaml, _parse_scalar, _set_path, _wrap
+from .data import load_img, read_ppm, write_ppm
+
+REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+DECODE_JSON = "decode.json"
+BAND_BYTES = 256 << 20            # one band's byte output stays under this
+ROW_LIMIT = 1 << 40               # a handle decodes (row, col) exactly while rows * width^2 < 2^40 (sf_create)
+KERNEL_WIDTHS = (32, 64, 128, 256)
+SHAPE_KEYS = ("mlp.depth", "mlp.hidden_size")
+
+
+# ---- decode.json ------------------------------------------------------------------------------------------
+def write_decode_json(out_dir: str, cfg, state_dict_keys: Sequence[str]) -> str:
+    """What a decoder needs to rebuild the network of a fit: the resolved mlp section, the fitted size, the entropy_coding
+    section, the masking that shaped the stored network (name; Small_Dense density) and the state-dict key list."""
+    masking = cfg.get("masking") or {}
+    rec = {
+        "mlp": dict(cfg["mlp"]),
+        "img": {"height": int(cfg["img"]["height"]), "width": int(cfg["img"]["width"])},
+        "entropy_coding": dict(cfg.get("entropy_coding") or {}),
+        "engine": dict(cfg.get("engine") or {}),
+        "masking_name": masking.get("name"),
+        "small_dense_density": float(masking["density"]) if masking.get("name") == "Small_Dense" else None,
+        "state_dict_keys": [str(k) for k in state_dict_keys],
+    }
+    path = os.path.join(out_dir, DECODE_JSON)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=2, sort_keys=True)
+    return path
+
+
+def read_decode_json(run_dir: str) -> Optional[dict]:
+    path = os.path.join(run_dir, DECODE_JSON)
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        return json.load(f)
+
+
+def split_overrides(argv: Sequence[str]) -> Tuple[Dict[str, str], List[str]]:
+    """decode.* keys (raw strings: `a:b` ranges are not YAML scalars) and the fit-style overrides"""
+    dec, rest = {}, []
+    for ov in argv:
+        key, eq, val = ov.partition("=")
+        if not eq:
+            raise ValueError(f"override '{ov}' is not key=value")
+        if key.startswith("decode."):
+            dec[key[len("decode."):]] = val
+        else:
+            rest.append(ov)
+    return dec, rest
+
+
+def resolve_shape(run_dir: str, overrides: Sequence[str] = (), conf_dir: Optional[str] = None) -> Cfg:
+    """decode.json of the run directory with `key=value` overrides on top (overrides win; `mlp=fourier` /
+    `entropy_coding=lzma` select a conf/ group file as in fit).  Without decode.json the overrides must name the network."""
+    conf_dir = conf_dir or os.environ.get("IIC_CONF", os.path.join(REPO, "conf"))
+    rec = read_decode_json(run_dir)
+    given = set()
+    if rec is None:
+        rec = {"mlp": {"name": "siren", "first_omega_0": 50, "hidden_omega_0": 30, "outermost_linear": True},
+               "img": {}, "entropy_coding": {"stream_name": "plain"}, "engine": {}, "masking_name": None,
+               "small_dense_density": None, "state_dict_keys": None}
+        missing_file = True
+    else:
+        missing_file = False
+    for ov in overrides:
+        key, _, val = ov.partition("=")
+        key = key.lstrip("+")
+        if "." not in key and os.path.isdir(os.path.join(conf_dir, key)):
+            if key in ("mlp", "entropy_coding"):
+                rec[key] = _load_yaml(os.path.join(conf_dir, key, f"{val}.yaml"))
+            elif key == "masking":
+                rec["masking_name"] = None if val == "none" else val
+                sec = _load_yaml(os.path.join(conf_dir, key, f"{val}.yaml"))
+                rec["small_dense_density"] = float(sec["density"]) if val == "Small_Dense" else None
+            continue                                   # other groups (img, optim, quant) say nothing about the stored network
+        if key == "masking.density":
+            if rec.get("masking_name") == "Small_Dense":
+                rec["small_dense_density"] = float(val)
+            continue
+        given.add(key)
+        _set_path(rec, key, _parse_scalar(val))
+    if missing_file:
+        need = [k for k in SHAPE_KEYS if k not in given]
+        if need:
+            raise FileNotFoundError(
+                f"{os.path.join(run_dir, DECODE_JSON)} not found (a run written before `fit` recorded the model shape, or by the "
+                f"reference): pass {' '.join(k + '=...' for k in need)} (and mlp=<name>, mlp.first_omega_0=..., "
+                "mlp.hidden_omega_0=..., img.height=... img.width=... when they differ from the defaults) on the command line")
+    return _wrap(rec)
+
+
+# ---- weights ----------------------------------------------------------------------------------------------
+def load_weights(run_dir: str, shape: Cfg, source: Optional[str] = None) -> Tuple["OrderedDict[str, torch.Tensor]", str]:
+    """(fp32 state dict on the CPU, 'container' | 'pth').  The container is preferred when the run has one."""
+    from .pipeline import entropy_coding
+    if shape.get("masking_name") == "Feathermap":
+        from .pipeline.feathermap.feathernet import DEPLOY_UNSUPPORTED
+        raise NotImplementedError("a masking=Feathermap run saves no deployable weights (model.pth holds the feather vector, not "
+                                  f"the network): {DEPLOY_UNSUPPORTED}")
+    qdir = os.path.join(run_dir, "model_quantized")
+    have_q = os.path.exists(os.path.join(qdir, "meta_data.json")) and os.path.exists(os.path.join(qdir, "compressed_weights.data"))
+    pth = os.path.join(run_dir, "model.pth")
+    if source not in (None, "", "container", "pth"):
+        raise ValueError(f"decode.source must be container or pth, got {source!r}")
+    if source == "container" and not have_q:
+        raise FileNotFoundError(f"decode.source=container: {qdir} holds no compressed_weights.data / meta_data.json")
+    if source == "pth" and not os.path.exists(pth):
+        raise FileNotFoundError(f"decode.source=pth: {pth} not found")
+    if source == "container" or (not source and have_q):
+        ec = dict(shape.get("entropy_coding") or {})
+        stream = ec.pop("stream_name", "plain")
+        sd = entropy_coding.decompress_state_dict(qdir, stream_name=stream, **ec)
+        used = "container"
+    elif os.path.exists(pth):
+        blob = torch.load(pth, map_location="cpu")
+        sd = blob["state_dict"] if isinstance(blob, dict) and "state_dict" in blob else blob
+        used = "pth"
+    else:
+        raise FileNotFoundError(f"{run_dir} holds neither model_quantized/ nor model.pth")
+    sd = OrderedDict((k, v.detach().float().cpu()) for k, v in sd.items())
+    want = shape.get("state_dict_keys")
+    if want:   # the dense names the fit recorded (a quantised copy adds centroids / labeled_weight, which come back as weight)
+        dense = [k for k in want if "centroids" not in k and "labeled_weight" not in k]
+        if sorted(dense) != sorted(sd.keys()):
+            raise ValueError(f"{used}: tensors {sorted(sd.keys())} do not match the fit's state dict {sorted(dense)}")
+    return sd, used
+
+
+# ---- bytes ------------------------------------------------------------------------------------------------
+def to_u8(pred: torch.Tensor) -> torch.Tensor:
+    """min(max(trunc(pred * 255), 0), 255) as uint8: eval_epoch's (pred * 255).int(), clamped to what a file can hold.
+    (the product in fp32; the float clamp to [-1, 256] only keeps huge values inside int32 and changes no result)"""
+    return (pred.float() * 255).clamp(-1, 256).int().clamp(0, 255).to(torch.uint8)
+
+
+def plan_bands(height: int, width: int, channels: int = 3, band_rows: Optional[int] = None,
+               band_bytes: int = BAND_BYTES) -> List[Tuple[int, int]]:
+    """Row bands [r0, r1) that cover [0, height): each satisfies rows * width^2 < 2^40 (the engine's row decode) and
+    rows * width * channels < band_bytes; band_rows lowers the size further."""
+    if height < 1 or width < 1:
+        raise ValueError("bad picture size")
+    cap = min((ROW_LIMIT - 1) // (width * width), (band_bytes - 1) // (width * channels))
+    if cap < 1:
+        raise ValueError(f"width {width}: one row does not fit a band")
+    rows = min(height, cap if not band_rows else max(1, min(cap, int(band_rows))))
+    return [(r, min(r + rows, height)) for r in range(0, height, rows)]
+
+
+def _span(spec: Optional[str], n: int, what: str) -> Tuple[int, int]:
+    if not spec:
+        return 0, n
+    a, _, b = spec.partition(":")
+    lo, hi = (int(a) if a else 0), (int(b) if b else n)
+    if not (0 <= lo < hi <= n):
+        raise ValueError(f"decode.{what}={spec}: need 0 <= a < b <= {n}")
+    return lo, hi
+
+
+# ---- the two paths ----------------------------------------------------------------------------------------
+def engine_width(shape: Cfg) -> int:
+    import numpy as np
+    return int(shape.mlp.hidden_size * np.sqrt(shape.get("small_dense_density") or 1.0))   # siren.py:88
+
+
+def render_path(shape: Cfg) -> Tuple[str, str]:
+    """('kernel' | 'torch', why): the one place that decides how a model is rendered"""
+    name = shape.mlp.get("name", "siren")
+    if name != "siren":
+        return "torch", f"mlp={name} has no render kernel"
+    w = engine_width(shape)
+    if w not in KERNEL_WIDTHS:
+        return "torch", (f"SIREN width {w} is " + ("on the wide path" if w in (512, 1024) else "zero-padded by the engine")
+                         + ": no render kernel")
+    return "kernel", f"SIREN {w}x{shape.mlp.depth}: sf_render"
+
+
+def flat_params(sd: Dict[str, torch.Tensor], depth: int) -> torch.Tensor:
+    parts = []
+    for l in range(depth):
+        parts += [sd[f"layers.{l}.linear.weight"].reshape(-1), sd[f"layers.{l}.linear.bias"].reshape(-1)]
+    return torch.cat(parts).float().contiguous()
+
+
+def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
+                  want_pred: bool = False, device: int = 0):
+    """uint8 [h, w, C] on the CPU (and the fp32 prediction when asked) of the grid rows x cols, band by band on ONE render
+    handle: a band is a slice of `rows` (the last, shorter one is padded with its final row and cut after the render)."""
+    from ._engine import RenderEngine
+    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
+    C = int(m.get("output_size", 3))
+    h, w = rows.numel(), cols.numel()
+    bands = plan_bands(h, w, C, band_rows)
+    nb = bands[0][1] - bands[0][0]
+    eng = RenderEngine(nb, w, engine_width(shape), int(m.depth), float(m.get("first_omega_0", 50.0)),
+                       float(m.get("hidden_omega_0", 30.0)), bool(m.get("outermost_linear", True)), C,
+                       eng_kw.get("compute_dtype", "f16"), device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
+    try:
+        dev = eng.device
+        eng.set_params(flat_params(sd, int(m.depth)).to(dev))
+        cols_d = cols.float().contiguous().to(dev)
+        out = torch.empty(h, w, C, dtype=torch.uint8)
+        pred = torch.empty(h, w, C) if want_pred else None
+        for r0, r1 in bands:
+            rb = rows[r0:r1].float()
+            if r1 - r0 < nb:
+                rb = torch.cat([rb, rb[-1:].expand(nb - (r1 - r0))])
+            eng.set_coords(rb.contiguous().to(dev), cols_d)
+            u8, p = eng.render(want_u8=True, want_pred=want_pred)
+            out[r0:r1] = u8[:r1 - r0].cpu()
+            if want_pred:
+                pred[r0:r1] = p[:r1 - r0].cpu()
+    finally:
+        eng.close()
+    return out, pred
+
+
+def render_torch(sd, shape: Cfg, height: int, width: int, r: Tuple[int, int], c: Tuple[int, int], device: int = 0):
+    """the registry model's own forward on the full height x width grid, cut to the window, bytes by to_u8"""
+    from .data import get_grid
+    from .models import registry
+    m = dict(shape.mlp)
+    name = m.get("name", "siren")
+    dev = torch.device("cuda", device)
+    model = registry[name](**m, small_dense_density=shape.get("small_dense_density") or 1.0, **dict(shape.get("engine") or {}))
+    model.load_state_dict(sd)
+    model = model.to(dev).eval()
+    with torch.no_grad():
+        pred = model(get_grid(height, width).to(dev))
+    pred = pred[r[0]:r[1], c[0]:c[1]].contiguous()
+    return to_u8(pred).cpu(), pred.cpu()
+
+
+def metrics(pred: torch.Tensor, u8: torch.Tensor, img: torch.Tensor) -> Dict[str, float]:
+    """eval_epoch's figures (train_helper.py:41-59) for a prediction and the bytes written for it"""
+    loss = float(((pred.double() - img.double()) ** 2).sum().item() / img.numel())
+    mse8 = (((img * 255).int() - u8.int()) ** 2).float().mean()
+    return {"loss": loss, "PSNR": 10 * math.log10(1 / loss), "PSNR_8bit": (10 * torch.log10(255 ** 2 / mse8)).item()}
+
+
+def load_truth(spec: str, height: int, width: int) -> torch.Tensor:
+    if spec.startswith("synthetic"):
+        return load_img(spec, height=height, width=width)
+    raw = read_ppm(spec)
+    maxval = 65535 if int(raw.max()) > 255 else 255
+    return (raw.double() / maxval).float()
+
+
+def decode(argv: Sequence[str]) -> Dict[str, object]:
+    dec, rest = split_overrides(argv)
+    run_dir = dec.get("dir")
+    if not run_dir:
+        raise ValueError("decode.dir=<run directory written by fit> is required")
+    shape = resolve_shape(run_dir, rest)
+    sd, source = load_weights(run_dir, shape, dec.get("source"))
+    H = int(dec.get("height") or shape.img.get("height") or 0)
+    W = int(dec.get("width") or shape.img.get("width") or 0)
+    if H < 1 or W < 1:
+        raise ValueError("output size unknown: pass decode.height=... decode.width=... (or img.height / img.width)")
+    r, c = _span(dec.get("rows"), H, "rows"), _span(dec.get("cols"), W, "cols")
+    device = int(dec.get("device") or 0)
+    truth = dec.get("truth")
+    path, why = render_path(shape)
+    logging.info(f"decode: weights from {source}; {path} path ({why}); {r[1] - r[0]}x{c[1] - c[0]} of a {H}x{W} grid")
+    if path == "kernel":
+        rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
+        u8, pred = render_kernel(sd, shape, rows, cols, int(dec["band_rows"]) if dec.get("band_rows") else None,
+                                 want_pred=bool(truth), device=device)
+    else:
+        u8, pred = render_torch(sd, shape, H, W, r, c, device=device)
+    if u8.shape[-1] != 3:
+        raise NotImplementedError(f"PPM holds 3 channels, the model has {u8.shape[-1]}")
+    out = dec.get("out") or os.path.join(run_dir, "decoded.ppm")
+    write_ppm(out, u8)
+    res = {"out": out, "path": path, "source": source, "height": int(u8.shape[0]), "width": int(u8.shape[1])}
+    if truth:
+        img = load_truth(truth, H, W)[r[0]:r[1], c[0]:c[1]]
+        res.update(metrics(pred, u8, img))
+        logging.info("Decode | " + " | ".join(f"{k}: {res[k]:.4f}" for k in ("loss", "PSNR", "PSNR_8bit")))
+        print(json.dumps({k: res[k] for k in ("loss", "PSNR", "PSNR_8bit")}))
+    logging.info(f"decode: wrote {out}")
+    return res
+
+
+def main(argv=None):
+    logging.basicConfig(level=logging.INFO, format="[%(asctime)s] %(message)s")
+    return decode(list(sys.argv[1:] if argv is None else argv))
+
+
+if __name__ == "__main__":
+    main()

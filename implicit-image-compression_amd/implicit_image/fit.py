@@ -130,6 +130,8 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
             logging.info(f"Compressed bytes {nbytes}")
         with open(os.path.join(out_dir, "result.json"), "w") as f:
             json.dump(last, f)
+        from .decode import write_decode_json                                      # what `make decode` rebuilds the network from
+        write_decode_json(out_dir, cfg, list(model.state_dict().keys()))
     return last
 
 

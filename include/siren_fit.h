@@ -202,6 +202,20 @@ int sf_forward(sf_handle* h, float* pred_dev, double* sse_out);
 /* forward + loss + backward: leaves the dense gradient (already scaled by 1/(3*H*W)) in the
  * engine; sse_out as above */
 int sf_forward_backward(sf_handle* h, double* sse_out);
+/* Inference only (csrc/siren_render.hip): what a decoder needs and nothing of a training step.
+ * sf_render_create takes sf_create's config and validation (height / width: the picture to render, any size) for hidden
+ * 32 / 64 / 128 / 256 and allocates the parameters, the forward weight images, the layer-0 table / image and the two
+ * coordinate vectors - no gradient, Adam moments, mask, phase / delta scratch or slabs (hidden 512 / 1024: SF_ERR_INVALID,
+ * the render kernel is not built for the wide path).  On such a handle sf_set_params, sf_get_params, sf_params_changed,
+ * sf_set_coords (any two vectors: a window of a grid is a slice of them), sf_num_params, sf_param_offset, sf_state_ptr(0),
+ * sf_destroy and the profiling calls work; every training entry point returns SF_ERR_INVALID.
+ * sf_render writes rows [row_begin, row_end) of the handle - a render handle or an ordinary SIREN training handle of hidden
+ * <= 256 - on the handle's stream, no host synchronisation.  Either output may be NULL, not both:
+ *   pred_dev [npix][out_features] fp32, bit-identical to what sf_forward writes for the same parameters and coordinates;
+ *   rgb8_dev [npix][out_features] bytes (4-byte aligned), u8 = min(max((int)(pred * 255.0f), 0), 255): the product in fp32,
+ *            truncated toward zero (eval_epoch's (pred * 255).int(), train_helper.py:52), clamped to what a file can hold. */
+int sf_render_create(const sf_config* cfg, sf_handle** out);
+int sf_render(sf_handle* h, uint8_t* rgb8_dev, float* pred_dev);
 /* Adam (+ mask) on the current gradient with learning rate lr; refreshes the low-precision weight images */
 int sf_adam_step(sf_handle* h, float lr);
 /* n_steps x (forward_backward + adam_step) with learning rates lr[0..n_steps) (host array);

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Render time and device memory of the inference-only path (sf_render on a render handle) against the training handle's
+forward, on one MI355X.
+
+    python scripts/render_bench.py [--sizes 2048 4096] [--calls 30] [--out profiles/render_bench.json]
+
+Per model (SIREN 256x8, 128x8) and size, HIP-event time per call after warm-up, median and spread over --calls calls, of
+  (a) sf_forward with pred on a training handle plus the torch byte conversion the host needs after it (the only way to
+      render before sf_render existed), the forward alone also reported;
+  (b) sf_render to bytes on a render handle.
+The legs alternate in blocks (a b a b) inside one process, so both see the same device state; the spread of each leg
+is reported next to its median.  Device memory held by each handle: torch.cuda.mem_get_info before / after creation in
+a fresh child process per handle.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
+    sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+MODELS = [(256, 8), (128, 8)]
+
+
+def device_note():
+    note = {"device": torch.cuda.get_device_name(0)}
+    # (both as torch reports them: SM clock in MHz, power_draw in the management library's own unit)
+    for k, fn in (("clock_mhz", getattr(torch.cuda, "clock_rate", None)), ("power_draw", getattr(torch.cuda, "power_draw", None))):
+        try:
+            note[k] = fn(0)
+        except Exception as e:   # (the management library is optional: say so rather than guess)
+            note[k] = f"unavailable ({type(e).__name__})"
+    return note
+
+
+def timed(fn, n):
+    out = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def stats(ms):
+    s = sorted(ms)
+    return {"median_ms": statistics.median(s), "min_ms": s[0], "max_ms": s[-1], "p10_ms": s[len(s) // 10],
+            "p90_ms": s[(len(s) * 9) // 10], "calls": len(s)}
+
+
+def time_leg(hidden, depth, S, calls, warmup):
+    from implicit_image._engine import RenderEngine, SirenEngine
+    from implicit_image.decode import to_u8
+    from oracle import siren_oracle as so
+    flat = torch.tensor(so.flatten(so.siren_init(hidden, depth, seed=0))).cuda()
+    gh, gw = (v.cuda() for v in so.grid_vectors(S, S))
+    tr, rn = SirenEngine(S, S, hidden, depth), RenderEngine(S, S, hidden, depth)
+    for e in (tr, rn):
+        e.set_coords(gh, gw)
+        e.set_params(flat)
+    pred = torch.empty(S, S, 3, device="cuda")
+    u8 = torch.empty(S, S, 3, dtype=torch.uint8, device="cuda")
+
+    def fwd_only():
+        tr.lib.sf_forward(tr.h, pred.data_ptr(), None)
+
+    def fwd_bytes():
+        tr.lib.sf_forward(tr.h, pred.data_ptr(), None)
+        return to_u8(pred)
+
+    def render():
+        rn.lib.sf_render(rn.h, u8.data_ptr(), None)
+
+    legs = {"forward_pred": fwd_only, "forward_pred_plus_torch_bytes": fwd_bytes, "render_bytes": render}
+    for fn in legs.values():
+        timed(fn, warmup)
+    ms = {k: [] for k in legs}
+    half = max(calls // 2, 1)
+    for _ in range(2):                      # a b c a b c: no leg owns the warm (or the throttled) end of the run
+        for k, fn in legs.items():
+            ms[k] += timed(fn, half)
+    same = bool(torch.equal(fwd_bytes(), u8))
+    tr.close()
+    rn.close()
+    del pred, u8
+    torch.cuda.empty_cache()
+    r = {k: stats(v) for k, v in ms.items()}
+    a, b = r["forward_pred_plus_torch_bytes"], r["render_bytes"]
+    r["bytes_identical"] = same
+    r["render_over_forward_plus_bytes"] = b["median_ms"] / a["median_ms"]
+    r["render_over_forward_alone"] = b["median_ms"] / r["forward_pred"]["median_ms"]
+    r["render_not_slower_beyond_spread_of_a"] = bool(b["median_ms"] <= a["median_ms"] + (a["p90_ms"] - a["p10_ms"]))
+    return r
+
+
+def mem_child(kind, hidden, depth, S):
+    from implicit_image._engine import RenderEngine, SirenEngine
+    torch.cuda.init()
+    torch.zeros(1, device="cuda")
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info()
+    eng = (RenderEngine if kind == "render" else SirenEngine)(S, S, hidden, depth)
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info()
+    eng.close()
+    print(json.dumps({"bytes": int(free0 - free1)}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[2048, 4096])
+    ap.add_argument("--calls", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "render_bench.json"))
+    ap.add_argument("--mem-child", nargs=4, metavar=("KIND", "HIDDEN", "DEPTH", "SIZE"))
+    args = ap.parse_args()
+    if args.mem_child:
+        k, h, d, s = args.mem_child
+        return mem_child(k, int(h), int(d), int(s))
+    if args.calls < 20:
+        ap.error("--calls must be at least 20")
+    res = {"what": "HIP-event ms per call; (a) sf_forward(pred) on a training handle + torch byte conversion, (b) sf_render to bytes "
+                   "on a render handle; handle memory from torch.cuda.mem_get_info in a fresh process per handle",
+           "before": device_note(), "models": {}}
+    for hidden, depth in MODELS:
+        for S in args.sizes:
+            r = time_leg(hidden, depth, S, args.calls, args.warmup)
+            mem = {}
+            for kind in ("train", "render"):
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--mem-child", kind, str(hidden), str(depth), str(S)],
+                                     stdout=subprocess.PIPE, timeout=180, check=True).stdout.decode().strip().splitlines()[-1]
+                mem[f"{kind}_handle_bytes"] = json.loads(out)["bytes"]
+            r["memory"] = mem
+            res["models"][f"{hidden}x{depth}@{S}"] = r
+            print(json.dumps({f"{hidden}x{depth}@{S}": {"a_ms": r["forward_pred_plus_torch_bytes"]["median_ms"],
+                                                        "fwd_ms": r["forward_pred"]["median_ms"],
+                                                        "b_ms": r["render_bytes"]["median_ms"], **mem}}), flush=True)
+    res["after"] = device_note()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
