@@ -65,12 +65,12 @@ static constexpr float kResScale = 1024.0f;
 //  the hidden layers', so it gets its own line in the per-kernel report)
 // (k_feather_*: the Feathermap update of sf_adam_step on a handle with sf_feather_attach, feather_kernels.hip)
 enum KernelId { K_FWD = 0, K_BWD_HIDDEN, K_BWD_LAST, K_DW_FIRST, K_REDUCE, K_SSE, K_ADAM, K_IMAGES, K_BWD_L1,
-                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_RENDER, K_COUNT };
+                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_RENDER, K_WV_RENDER, K_COUNT };
 // (k_wv_*: the image-space composition of a WaveletSiren handle and its adjoint, wavelet_kernels.hip)
 static const char* kKernelNames[K_COUNT] = {"k_fwd",    "k_bwd_hidden", "k_bwd_last", "k_dw_first",
                                             "k_reduce", "k_sse",        "k_adam",     "k_images", "k_bwd_layer1",
                                             "k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat",
-                                            "k_wv_compose", "k_wv_adjoint", "k_wv_inject", "k_render"};
+                                            "k_wv_compose", "k_wv_adjoint", "k_wv_inject", "k_render", "k_wv_render"};
 
 struct ProfRec {
   int id;
@@ -193,6 +193,10 @@ struct sf_engine {
   // render handle (sf_render_create, siren_render.hip): parameters, forward images and coordinates only - no gradient, no
   // optimiser state, no mask, no backward scratch; every training entry point refuses it
   bool render = false;
+  // WaveletSiren render handle (sf_wavelet_render_create, wavelet_render.hip): wavelet and render both set.  Two render
+  // sub-handles on the joint parameter vector, wv_pred as the one pair of coefficient buffers of the largest window, and
+  // gh / gw the caller's FULL coefficient-grid vectors, which every sf_wavelet_render call slices
+  int wv_max_rows = 0, wv_max_cols = 0;   // the largest pixel window one call draws
 };
 
 namespace {
@@ -1733,6 +1737,7 @@ int sf_wavelet_create(const sf_wavelet_config* cfg, sf_handle** out) try {
 int sf_wavelet_debug(sf_handle* h, int32_t which, const float* in0, const float* in1, const float* img, float* out0,
                      float* out1) try {
   if (!h || !in0 || !out0 || !out1 || (which == 0 && !in1)) return fail(SF_ERR_INVALID, "null argument");
+  if (h->render) return fail(SF_ERR_INVALID, "sf_wavelet_debug: a render handle (sf_wavelet_render_create) runs sf_wavelet_render only");
   if (!h->wavelet) return fail(SF_ERR_INVALID, "sf_wavelet_debug: not a WaveletSiren handle (sf_wavelet_create)");
   if (which != 0 && which != 1) return fail(SF_ERR_INVALID, "sf_wavelet_debug: which must be 0 or 1");
   DevGuard dev_guard(h->cfg.device);
@@ -2005,6 +2010,12 @@ int sf_params_changed(sf_handle* h) try {
 int sf_set_coords(sf_handle* h, const float* rows, const float* cols) try {
   if (!h || !rows || !cols) return fail(SF_ERR_INVALID, "null argument");
   DevGuard dev_guard(h->cfg.device);
+  if (h->wavelet && h->render) {   // kept whole and unchecked: sf_wavelet_render points the sub-networks at slices of them
+    HIPCHK(hipMemcpyAsync(h->gh, rows, (size_t)h->wv_n * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->gw, cols, (size_t)h->wv_n * 4, hipMemcpyDeviceToDevice, h->stream));
+    h->have_coords = true;
+    return SF_OK;
+  }
   if (h->wavelet) {   // both sub-networks run on the n x n coefficient grid (wavelet_siren.py:76-80)
     wv_sync(h);
     for (sf_engine* s : h->wv_sub) {
@@ -2423,3 +2434,4 @@ int sf_debug_throw(int32_t kind) try {
 }  // extern "C"
 
 #include "siren_render.hip"
+#include "wavelet_render.hip"

@@ -113,6 +113,8 @@ int sf_render_create(const sf_config* cfg, sf_handle** out) try { return create_
 int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
   if (!rgb8 && !pred) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev and pred_dev are both NULL");
+  if (h->wavelet && h->render)
+    return fail(SF_ERR_INVALID, "sf_render: a WaveletSiren render handle (sf_wavelet_render_create) is drawn by sf_wavelet_render");
   if (h->wide || h->fourier || h->wavelet)
     return fail(SF_ERR_INVALID, "sf_render: built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create)");
   if (((uintptr_t)rgb8 & 3u) != 0) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev must be 4-byte aligned");

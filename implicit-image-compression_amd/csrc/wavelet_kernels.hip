@@ -17,6 +17,7 @@
 //                  pre-scale goes straight into each sub-network's dL/dout (Dlast, F-layout) or, when the coefficient
 //                  grid takes more than one chunk, into an fp32 buffer
 //   k_wv_inject    two-pass form: one chunk of that fp32 buffer -> Dlast
+//   k_wv_render    (wavelet_render.hip) the inference form of k_wv_compose: a pixel window, fp32 and / or bytes, no loss
 // With a sine output layer (outermost_linear=False) dL/dout is dL/dz of the last pre-activation: the sub-networks' training
 // forward writes d sin(om z)/dz = om cos(om z) per coefficient and channel (FwdArgs::dfac), and k_wv_adjoint (one chunk) or
 // k_wv_inject (two passes) multiplies by it before the single fp16 rounding.  The two-pass buffer holds dL/dp times dscale.
@@ -91,6 +92,71 @@ __device__ __forceinline__ uint32_t wv_pack_f16(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h2));
 }
 
+// One output pixel of the composition: RGB of pixel (r, c) of the H x H picture, stored at pred[p] (when given); with a
+// target, the squared residual (returned) and dL/d(Y, Cb, Cr) at g[p] (when given).  lf / hf hold the coefficient rows
+// [i0, ..) x columns [j0, ..) in rows of cc coefficients (the whole grid: i0 = j0 = 0, cc = n); n and up are those of the
+// full picture.
+// This is the body k_wv_compose and k_wv_render (wavelet_render.hip) share, and it is NOT inlined, on purpose: hipcc
+// contracts a * b + c into fma and pairs operations into packed instructions depending on the code around them, and two
+// inlined copies of the same expressions came out of the two kernels with different roundings (the render prediction
+// differed from sf_forward's in the last bit).  One compiled body called by both is bit-identical by construction; the
+// four values come back in registers.
+struct WvPixel { float rgb[3]; float sse; };
+__device__ __noinline__ WvPixel wv_compose_pixel(const float* lf, const float* hf, const float* img, float* pred, float* g,
+                                                 float gscale, long p, int r, int c, int n, float up, int i0, int j0, int cc) {
+  WvPixel out;
+  float (&rgb)[3] = out.rgb;
+  float sse = 0.f;
+  // inverse DWT, gather form: 3 x 3 coefficients per band
+  float y = 0.f;
+#pragma unroll
+  for (int ar = 0; ar < 3; ++ar) {
+    const int i = (r >> 1) + ar - i0, kr = (r & 1) + 4 - 2 * ar;
+    const float g0r = kWvG0[kr], g1r = kWvG1[kr];
+    const float* lrow = lf + (size_t)i * cc * 3;
+    const float* hrow = hf + (size_t)i * cc * 3;
+#pragma unroll
+    for (int ac = 0; ac < 3; ++ac) {
+      const int j = (c >> 1) + ac - j0, kc = (c & 1) + 4 - 2 * ac;
+      const float g0c = kWvG0[kc], g1c = kWvG1[kc];
+      y += lrow[j * 3 + 0] * (g0r * g0c) + hrow[j * 3 + 0] * (g1r * g0c) + hrow[j * 3 + 1] * (g0r * g1c) +
+           hrow[j * 3 + 2] * (g1r * g1c);
+    }
+  }
+  // Cb, Cr: bilinear upsampling of LF channels 1, 2 (torch's operation order)
+  const WvTap tr = wv_tap(r, up, n), tc = wv_tap(c, up, n);
+  const float* q00 = lf + ((size_t)(tr.i0 - i0) * cc + (tc.i0 - j0)) * 3;
+  const float* q01 = lf + ((size_t)(tr.i0 - i0) * cc + (tc.i1 - j0)) * 3;
+  const float* q10 = lf + ((size_t)(tr.i1 - i0) * cc + (tc.i0 - j0)) * 3;
+  const float* q11 = lf + ((size_t)(tr.i1 - i0) * cc + (tc.i1 - j0)) * 3;
+  const float cb = tr.l0 * (tc.l0 * q00[1] + tc.l1 * q01[1]) + tr.l1 * (tc.l0 * q10[1] + tc.l1 * q11[1]);
+  const float cr = tr.l0 * (tc.l0 * q00[2] + tc.l1 * q01[2]) + tr.l1 * (tc.l0 * q10[2] + tc.l1 * q11[2]);
+  const float cbs = cb - 0.5f, crs = cr - 0.5f;
+  rgb[0] = y + 1.403f * crs;
+  rgb[1] = y - 0.714f * crs - 0.344f * cbs;
+  rgb[2] = y + 1.773f * cbs;
+  if (pred) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) pred[p * 3 + k] = rgb[k];
+  }
+  if (img) {
+    float d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float e = rgb[k] - img[p * 3 + k];
+      sse += e * e;
+      d[k] = e * gscale;
+    }
+    if (g) {   // adjoint of the colour transform: dY, dCb, dCr
+      g[p * 3 + 0] = d[0] + d[1] + d[2];
+      g[p * 3 + 1] = 1.773f * d[2] - 0.344f * d[1];
+      g[p * 3 + 2] = 1.403f * d[0] - 0.714f * d[1];
+    }
+  }
+  out.sse = sse;
+  return out;
+}
+
 __global__ __launch_bounds__(kWvThreads) void k_wv_compose(WvArgs a) {
   __shared__ float sRed[kWvThreads / 64];
   const long p = (long)blockIdx.x * kWvThreads + threadIdx.x;
@@ -98,53 +164,7 @@ __global__ __launch_bounds__(kWvThreads) void k_wv_compose(WvArgs a) {
   float sse = 0.f;
   if (p < (long)H * H) {
     const int r = (int)(p / H), c = (int)(p - (long)r * H);
-    // inverse DWT, gather form: 3 x 3 coefficients per band
-    float y = 0.f;
-#pragma unroll
-    for (int ar = 0; ar < 3; ++ar) {
-      const int i = (r >> 1) + ar, kr = (r & 1) + 4 - 2 * ar;
-      const float g0r = kWvG0[kr], g1r = kWvG1[kr];
-      const float* lrow = a.lf + (size_t)i * n * 3;
-      const float* hrow = a.hf + (size_t)i * n * 3;
-#pragma unroll
-      for (int ac = 0; ac < 3; ++ac) {
-        const int j = (c >> 1) + ac, kc = (c & 1) + 4 - 2 * ac;
-        const float g0c = kWvG0[kc], g1c = kWvG1[kc];
-        y += lrow[j * 3 + 0] * (g0r * g0c) + hrow[j * 3 + 0] * (g1r * g0c) + hrow[j * 3 + 1] * (g0r * g1c) +
-             hrow[j * 3 + 2] * (g1r * g1c);
-      }
-    }
-    // Cb, Cr: bilinear upsampling of LF channels 1, 2 (torch's operation order)
-    const WvTap tr = wv_tap(r, a.up, n), tc = wv_tap(c, a.up, n);
-    const float* q00 = a.lf + ((size_t)tr.i0 * n + tc.i0) * 3;
-    const float* q01 = a.lf + ((size_t)tr.i0 * n + tc.i1) * 3;
-    const float* q10 = a.lf + ((size_t)tr.i1 * n + tc.i0) * 3;
-    const float* q11 = a.lf + ((size_t)tr.i1 * n + tc.i1) * 3;
-    const float cb = tr.l0 * (tc.l0 * q00[1] + tc.l1 * q01[1]) + tr.l1 * (tc.l0 * q10[1] + tc.l1 * q11[1]);
-    const float cr = tr.l0 * (tc.l0 * q00[2] + tc.l1 * q01[2]) + tr.l1 * (tc.l0 * q10[2] + tc.l1 * q11[2]);
-    const float cbs = cb - 0.5f, crs = cr - 0.5f;
-    float rgb[3];
-    rgb[0] = y + 1.403f * crs;
-    rgb[1] = y - 0.714f * crs - 0.344f * cbs;
-    rgb[2] = y + 1.773f * cbs;
-    if (a.pred) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a.pred[p * 3 + k] = rgb[k];
-    }
-    if (a.img) {
-      float d[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float e = rgb[k] - a.img[p * 3 + k];
-        sse += e * e;
-        d[k] = e * a.gscale;
-      }
-      if (a.g) {   // adjoint of the colour transform: dY, dCb, dCr
-        a.g[p * 3 + 0] = d[0] + d[1] + d[2];
-        a.g[p * 3 + 1] = 1.773f * d[2] - 0.344f * d[1];
-        a.g[p * 3 + 2] = 1.403f * d[0] - 0.714f * d[1];
-      }
-    }
+    sse = wv_compose_pixel(a.lf, a.hf, a.img, a.pred, a.g, a.gscale, p, r, c, n, a.up, 0, 0, n).sse;
   }
   // workgroup SSE partial, fixed order: lanes by xor-shuffle, then waves 0..3
 #pragma unroll

@@ -1,0 +1,252 @@
+// wavelet_render.hip — the inference-only path of WaveletSiren: sf_wavelet_render_create / sf_wavelet_render
+// (include/siren_fit.h).
+//
+// A decoder needs the picture, not a training step.  One call draws a pixel window [row0, row1) x [col0, col1) of the
+// H x H picture:
+//   the coefficient window [i0, i1) x [j0, j1) that window reads (wv_coeff_span below)
+//   -> the RENDER forward (siren_render.hip: k_fwd<WD> / k_fwd_pipe, pred only) of LF and of HF over that sub-grid, whose
+//      coordinates are the slices [i0, i1) / [j0, j1) of the caller's two full coefficient-grid vectors
+//   -> k_wv_render: k_wv_compose (wavelet_kernels.hip) without the target, the residual, the SSE partial and its workgroup
+//      barrier, with bytes.  The per-pixel body (wv_compose_pixel) is ONE compiled function that both kernels call, so the
+//      fp32 prediction is bit-identical to what
+//      sf_forward writes on a WaveletSiren training handle, and a window is bit-identical to that region of the full
+//      picture: coefficient (i, j) sees rows[i], cols[j] whatever the window (tests/test_gpu_wavelet_render.py).
+//
+// Bytes: u8 = min(max((int)(v * 255.0f), 0), 255), the product in fp32 and truncated toward zero (fwd_render_out,
+// decode.to_u8).  A wave owns 64 consecutive pixels of the dense rows x cols output = 192 consecutive bytes, which start on
+// a dword boundary (64 divides the wave's first pixel index): every lane packs its own pixel's three bytes into one
+// register, lane d < 48 gathers dword d from three neighbours with four ds_bpermute, and the wave stores 48 whole dwords in
+// one store instruction.  Only the output's last, ragged dword is written byte by byte.
+//
+// This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit).
+
+namespace sf {
+
+struct WvRenderArgs {
+  int H, n;              // FULL picture side, coefficient side
+  float up;              // bilinear source-index scale of the full picture
+  int row0, col0;        // pixel window origin
+  int cols;              // pixel window width (row length of the dense outputs)
+  long npx;              // pixels of the window
+  int i0, j0, cc;        // coefficient window origin and row length of lf / hf
+  const float* lf;       // [cr * cc][3]
+  const float* hf;
+  float* pred;           // [npx][3] or null
+  uint8_t* rgb8;         // [npx][3] or null (4-byte aligned)
+};
+
+__global__ __launch_bounds__(kWvThreads) void k_wv_render(WvRenderArgs a) {
+  const long p = (long)blockIdx.x * kWvThreads + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  uint32_t mine = 0u;   // this lane's pixel: channel k in byte k
+  if (p < a.npx) {
+    const int pr = (int)(p / a.cols);
+    const int r = a.row0 + pr, c = a.col0 + (int)(p - (long)pr * a.cols);
+    // (no target: no fetch, no residual; pred, when asked for, is the plain 12-byte store of k_wv_compose)
+    const WvPixel px = wv_compose_pixel(a.lf, a.hf, nullptr, a.pred, nullptr, 0.f, p, r, c, a.n, a.up, a.i0, a.j0, a.cc);
+    const float (&rgb)[3] = px.rgb;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      int q = (int)(rgb[k] * 255.0f);   // v_cvt_i32_f32: toward zero
+      q = q < 0 ? 0 : (q > 255 ? 255 : q);
+      mine |= (uint32_t)q << (8 * k);
+    }
+  }
+  if (!a.rgb8) return;   // (uniform)
+  uint32_t word = 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = 4 * lane + j;           // byte k of the wave's 192 = pixel k / 3, channel k % 3
+    const int src = k / 3, ch = k - src * 3;
+    const uint32_t v = (uint32_t)__shfl((int)mine, src & 63);   // (lanes >= 48 gather nothing they store)
+    word |= ((v >> (8 * ch)) & 0xffu) << (8 * j);
+  }
+  const long p0 = p - lane;               // first pixel of this wave: a multiple of 64
+  const long left = a.npx - p0;
+  const int nbytes = left >= 64 ? 192 : (left > 0 ? (int)left * 3 : 0);   // bytes of the wave inside the output
+  if (lane < 48) {
+    uint8_t* blk = a.rgb8 + p0 * 3;       // dword aligned: sf_wavelet_render checks the base, 64 | p0
+    if (4 * lane + 4 <= nbytes) {
+      reinterpret_cast<uint32_t*>(blk)[lane] = word;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * lane + j < nbytes) blk[4 * lane + j] = (uint8_t)(word >> (8 * j));
+    }
+  }
+}
+
+}  // namespace sf
+
+namespace {
+
+// wv_tap's source indices (wavelet_kernels.hip) on the host, operation for operation in fp32 (one rounding per
+// statement: no contraction)
+void wv_tap_host(int o, float up, int n, int* i0, int* i1) {
+  const float a = (float)o + 0.5f;
+  const float m = up * a;
+  float s = m - 0.5f;
+  if (s < 0.f) s = 0.f;
+  *i0 = (int)s;
+  *i1 = *i0 + (*i0 < n - 1 ? 1 : 0);
+}
+// Coefficient rows (or columns) [lo, hi) that output rows [o0, o1) of an H-row picture read.  Row o reads, for Y,
+// coefficients o/2 .. o/2 + 2 (k_wv_compose's gather) and, for Cb / Cr, wv_tap(o).i0 and .i1; all are monotone in o, so
+// the span is the minimum at o0 and the maximum at o1 - 1.  (Python mirror: implicit_image.decode.wavelet_coeff_span)
+void wv_coeff_span(int o0, int o1, int H, int* lo, int* hi) {
+  const int n = (H + 5) / 2;
+  const float up = (float)(1.0 / ((double)H / (double)n));
+  int a0, a1, b0, b1;
+  wv_tap_host(o0, up, n, &a0, &a1);
+  wv_tap_host(o1 - 1, up, n, &b0, &b1);
+  *lo = std::min(o0 / 2, a0);
+  *hi = std::max((o1 - 1) / 2 + 2, b1) + 1;
+}
+
+int create_wavelet_render(const sf_wavelet_render_config* cfg, sf_handle** out) {
+  if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
+  if (cfg->hidden != 32 && cfg->hidden != 64 && cfg->hidden != 128 && cfg->hidden != 256)
+    return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128 or 256 for WaveletSiren (other widths: zero-pad on the host)");
+  if (cfg->depth < 2 || cfg->depth > 16) return fail(SF_ERR_INVALID, "depth must be 2..16");
+  if (cfg->compute_dtype != SF_F16) return fail(SF_ERR_INVALID, "WaveletSiren runs fp16 operands only (compute_dtype SF_F16)");
+  if (cfg->height < 2 || cfg->height % 2)
+    return fail(SF_ERR_INVALID, "WaveletSiren needs an even, square image: the reference's inverse DWT (2n - 4 rows) and its "
+                                "torch.cat of Y with the upsampled Cb / Cr stop matching otherwise");
+  if ((double)cfg->height * (double)cfg->height >= 2147483648.0) return fail(SF_ERR_INVALID, "image too large");
+  if (cfg->chunk_pixels < 0) return fail(SF_ERR_INVALID, "chunk_pixels must be >= 0");
+  const int H = cfg->height, n = (H + 5) / 2;
+  const int max_rows = cfg->max_rows ? cfg->max_rows : H, max_cols = cfg->max_cols ? cfg->max_cols : H;
+  if (max_rows < 1 || max_rows > H || max_cols < 1 || max_cols > H)
+    return fail(SF_ERR_INVALID, "sf_wavelet_render_create: max_rows / max_cols must be 0 (the whole picture) or 1 .. height");
+  // the largest coefficient window of any max_rows x max_cols pixel window (the span's length depends on where it sits)
+  auto max_span = [&](int len) {
+    int best = 0;
+    for (int o = 0; o + len <= H; ++o) {
+      int lo, hi;
+      wv_coeff_span(o, o + len, H, &lo, &hi);
+      best = std::max(best, hi - lo);
+    }
+    return best;
+  };
+  const int cr = max_span(max_rows), cc = max_span(max_cols);
+  sf_config sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.abi_version = SF_ABI_VERSION; sc.height = cr; sc.width = cc; sc.row_begin = 0; sc.row_end = cr;
+  sc.in_features = 2; sc.out_features = 3; sc.hidden = cfg->hidden; sc.depth = cfg->depth;
+  sc.first_omega_0 = cfg->first_omega_0; sc.hidden_omega_0 = cfg->hidden_omega_0; sc.outermost_linear = cfg->outermost_linear;
+  sc.compute_dtype = SF_F16; sc.device = cfg->device; sc.stream = cfg->stream; sc.chunk_pixels = cfg->chunk_pixels;
+  sf_handle* sub[2] = {nullptr, nullptr};
+  for (int s = 0; s < 2; ++s) {
+    const int rc = create_handle(&sc, &sub[s], true);   // (refuses cr * cc^2 >= 2^40: draw such a picture in bands)
+    if (rc) { if (s) sf_destroy(sub[0]); return rc; }
+  }
+  DevGuard dev_guard(cfg->device);
+  sf_engine* h = new sf_engine();
+  h->wavelet = true;
+  h->render = true;
+  h->wv_sub[0] = sub[0]; h->wv_sub[1] = sub[1];
+  h->cfg = sub[0]->cfg;
+  h->cfg.height = H; h->cfg.width = H; h->cfg.row_begin = 0; h->cfg.row_end = H;
+  h->D = 2 * cfg->depth; h->WD = cfg->hidden;
+  h->dw_wg = sub[0]->dw_wg;
+  h->stream = (hipStream_t)cfg->stream;
+  h->npix = (long)H * H;
+  h->n_total = (double)H * (double)H;
+  h->wv_n = n;
+  h->wv_up = (float)(1.0 / ((double)H / (double)n));
+  h->wv_max_rows = max_rows; h->wv_max_cols = max_cols;
+  const int64_t P0 = sub[0]->P;
+  h->P = 2 * P0;
+  auto alloc = [&](void** p, size_t bytes) -> int {
+    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+    return SF_OK;
+  };
+  int rc = SF_OK;
+#define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
+  ALLOC(h->params, h->P * 4);
+  ALLOC(h->wv_pred, (size_t)2 * cr * cc * 3 * 4);   // the one pair of coefficient buffers
+  ALLOC(h->gh, (size_t)n * 4); ALLOC(h->gw, (size_t)n * 4);   // the caller's FULL coefficient-grid vectors
+#undef ALLOC
+  if (rc) { sf_destroy(h); return rc; }
+  for (int s = 0; s < 2; ++s) {   // the sub-handles' parameters become the two halves of the joint vector
+    sf_engine* e = h->wv_sub[s];
+    hipStreamSynchronize(e->stream);
+    hipFree(e->params);
+    e->params = h->params + s * P0;
+    e->borrowed_state = true;
+  }
+  hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
+  *out = h;
+  return SF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_wavelet_render_create(const sf_wavelet_render_config* cfg, sf_handle** out) try {
+  return create_wavelet_render(cfg, out);
+} SF_CATCH
+
+int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, uint8_t* rgb8, float* pred) try {
+  if (!h) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->wavelet)
+    return fail(SF_ERR_INVALID, "sf_wavelet_render: not a WaveletSiren handle (sf_wavelet_render_create / sf_wavelet_create)");
+  if (!rgb8 && !pred) return fail(SF_ERR_INVALID, "sf_wavelet_render: rgb8_dev and pred_dev are both NULL");
+  if (((uintptr_t)rgb8 & 3u) != 0) return fail(SF_ERR_INVALID, "sf_wavelet_render: rgb8_dev must be 4-byte aligned");
+  const int H = h->cfg.height;
+  if (row0 < 0 || row1 > H || row0 >= row1 || col0 < 0 || col1 > H || col0 >= col1)
+    return fail(SF_ERR_INVALID, "sf_wavelet_render: need 0 <= row0 < row1 <= height and 0 <= col0 < col1 <= height");
+  if (h->render && (row1 - row0 > h->wv_max_rows || col1 - col0 > h->wv_max_cols))
+    return fail(SF_ERR_INVALID, "sf_wavelet_render: the window is larger than the max_rows x max_cols the handle was created for");
+  if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
+  DevGuard dev_guard(h->cfg.device);
+  int rc = refresh_images(h);   // (also points the sub-handles at the current stream and profiler)
+  if (rc) return rc;
+  wv_sync(h);
+  int i0, i1, j0, j1;
+  wv_coeff_span(row0, row1, H, &i0, &i1);
+  wv_coeff_span(col0, col1, H, &j0, &j1);
+  const int cr = i1 - i0, cc = j1 - j0;
+  const long nn = (long)cr * cc;
+  // the full coordinate vectors: a render handle keeps them itself, a training handle in its sub-networks
+  const float* gh = h->render ? h->gh : h->wv_sub[0]->gh;
+  const float* gw = h->render ? h->gw : h->wv_sub[0]->gw;
+  float* const p_sub[2] = {h->wv_pred, h->wv_pred + nn * 3};
+  for (int s = 0; s < 2; ++s) {
+    sf_engine* e = h->wv_sub[s];
+    const long n_chunks = (nn + e->chunk_px - 1) / e->chunk_px;
+    for (long c = 0; c < n_chunks; ++c) {
+      const long pix0 = c * e->chunk_px;
+      const long px = std::min(e->chunk_px, nn - pix0);
+      const int n_super = (int)((px + kSuper - 1) / kSuper);
+      FwdArgs fa = fwd_args_base(e, pix0, n_super);
+      // the sub-grid of this window: its rows / columns are slices of the full vectors, its row length is cc
+      fa.gh = gh + i0; fa.gw = gw + j0; fa.row_begin = 0; fa.W = cc; fa.npix = nn;
+      fa.w_magic = ((1ULL << 40) + (unsigned long long)cc - 1) / (unsigned long long)cc;
+      fa.pred = p_sub[s];
+      Launch L(e, K_RENDER, flops_fwd_px(e) * n_super * (double)kSuper, n_super * (double)kSuper * 3 * 4.0);
+      rc = launch_render(e, fa, fwd_grid(e, n_super));
+      L.done();
+      if (rc) return rc;
+    }
+  }
+  WvRenderArgs a;
+  memset(&a, 0, sizeof(a));
+  a.H = H; a.n = h->wv_n; a.up = h->wv_up;
+  a.row0 = row0; a.col0 = col0; a.cols = col1 - col0;
+  a.npx = (long)(row1 - row0) * (col1 - col0);
+  a.i0 = i0; a.j0 = j0; a.cc = cc;
+  a.lf = p_sub[0]; a.hf = p_sub[1];
+  a.pred = pred; a.rgb8 = rgb8;
+  Launch L(h, K_WV_RENDER, 0, (double)a.npx * ((pred ? 12.0 : 0.0) + (rgb8 ? 3.0 : 0.0)) + (double)nn * 24.0);
+  hipLaunchKernelGGL(k_wv_render, dim3((unsigned)((a.npx + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0, h->stream, a);
+  L.done();
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+} SF_CATCH
+
+}  // extern "C"

@@ -52,6 +52,15 @@ class sf_wavelet_config(C.Structure):
     ]
 
 
+class sf_wavelet_render_config(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32), ("height", C.c_int32), ("max_rows", C.c_int32), ("max_cols", C.c_int32),
+        ("hidden", C.c_int32), ("depth", C.c_int32), ("first_omega_0", C.c_float), ("hidden_omega_0", C.c_float),
+        ("outermost_linear", C.c_int32), ("compute_dtype", C.c_int32), ("device", C.c_int32),
+        ("stream", C.c_void_p), ("chunk_pixels", C.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -114,6 +123,8 @@ def load_library():
     render = {
         "sf_render_create": [C.POINTER(sf_config), C.POINTER(H)],
         "sf_render": [H, C.c_void_p, F],
+        "sf_wavelet_render_create": [C.POINTER(sf_wavelet_render_config), C.POINTER(H)],
+        "sf_wavelet_render": [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, F],
     }
     for name, args in list(feather.items()) + list(wavelet.items()) + list(render.items()):
         if hasattr(lib, name):
@@ -139,6 +150,10 @@ def has_wavelet(lib) -> bool:
 
 def has_render(lib) -> bool:
     return all(hasattr(lib, s) for s in ("sf_render_create", "sf_render"))
+
+
+def has_wavelet_render(lib) -> bool:
+    return all(hasattr(lib, s) for s in ("sf_wavelet_render_create", "sf_wavelet_render"))
 
 
 def exported_symbols() -> Sequence[str]:
@@ -411,7 +426,8 @@ class RenderEngine(SirenEngine):
     """Inference-only handle (sf_render_create): parameters, forward weight images and the two coordinate vectors - no
     gradient, optimiser state, mask or backward scratch.  set_params / get_params / set_coords / render / the profiling
     calls work; every training call raises with the library's message.  set_coords takes any two vectors (a window of a
-    grid is a slice of its linspace vectors); hidden 512 / 1024 is refused (no render kernel on the wide path)."""
+    grid is a slice of its linspace vectors); hidden 512 / 1024 is refused (no render kernel on the wide path; FourierNet
+    has none either, WaveletSiren has WaveletRenderEngine)."""
 
     def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
                  hidden_omega_0: float = 30.0, outermost_linear: bool = True, out_features: int = 3,
@@ -495,6 +511,11 @@ class WaveletEngine(SirenEngine):
         """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""
         _check(self.lib.sf_set_coords(self.h, _f32_cuda(rows, self.n).data_ptr(), _f32_cuda(cols, self.n).data_ptr()))
 
+    def render_window(self, r0: int, r1: int, c0: int, c1: int, want_u8: bool = True, want_pred: bool = False):
+        """sf_wavelet_render of pixel rows [r0, r1) x columns [c0, c1) on this handle, no host sync:
+        (rgb8 [r1 - r0, c1 - c0, 3] uint8 or None, pred fp32 or None)"""
+        return _wavelet_render(self, r0, r1, c0, c1, want_u8, want_pred)
+
     def debug_compose(self, lf: torch.Tensor, hf: torch.Tensor, img: Optional[torch.Tensor] = None):
         """k_wv_compose on [n, n, 3] sub-network predictions: (RGB [H, H, 3], dL/d(Y, Cb, Cr) [H, H, 3] or None)"""
         nn3, hh3 = self.n * self.n * 3, self.npix * 3
@@ -512,6 +533,65 @@ class WaveletEngine(SirenEngine):
         _check(self.lib.sf_wavelet_debug(self.h, 1, _f32_cuda(g, self.npix * 3).data_ptr(), None, None, lf.data_ptr(),
                                          hf.data_ptr()))
         return lf, hf
+
+
+def _wavelet_render(eng, r0: int, r1: int, c0: int, c1: int, want_u8: bool, want_pred: bool):
+    if not has_wavelet_render(eng.lib):
+        raise RuntimeError(f"{_LIB_PATH} has no sf_wavelet_render entry point (built before the WaveletSiren render path): "
+                           "rebuild it with `python __graft_entry__.py build`")
+    if not (want_u8 or want_pred):
+        raise ValueError("render: ask for bytes, the fp32 prediction, or both")
+    shape = (max(r1 - r0, 0), max(c1 - c0, 0), 3)
+    u8 = torch.empty(shape, dtype=torch.uint8, device=eng.device) if want_u8 else None
+    pred = torch.empty(shape, device=eng.device) if want_pred else None
+    _check(eng.lib.sf_wavelet_render(eng.h, r0, r1, c0, c1, u8.data_ptr() if want_u8 else None,
+                                     pred.data_ptr() if want_pred else None))
+    return u8, pred
+
+
+class WaveletRenderEngine(WaveletEngine):
+    """Inference-only WaveletSiren handle (sf_wavelet_render_create, csrc/wavelet_render.hip): the joint parameters [LF | HF],
+    two render sub-handles, the two full coefficient-grid vectors and one pair of coefficient buffers sized for a
+    max_rows x max_cols pixel window (0 = the whole picture) - no gradient, optimiser state, mask, backward scratch or
+    image-space gradient.  set_params / get_params / set_coords (the linspace(0, 1, n) vectors of the FULL coefficient
+    grid) / render / the profiling calls work; every training call raises with the library's message."""
+
+    def __init__(self, height: int, hidden: int, depth: int, first_omega_0: float = 50.0, hidden_omega_0: float = 30.0,
+                 outermost_linear: bool = True, compute_dtype: str = "f16", max_rows: int = 0, max_cols: int = 0,
+                 device: int = 0, chunk_pixels: int = 0):
+        self.lib = load_library()
+        if not has_wavelet_render(self.lib):
+            raise RuntimeError(f"{_LIB_PATH} has no sf_wavelet_render_create entry point (built before the WaveletSiren render "
+                               "path): rebuild it with `python __graft_entry__.py build`")
+        if not torch.cuda.is_available():
+            raise RuntimeError("WaveletRenderEngine needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
+        self.device = torch.device("cuda", device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        cfg = sf_wavelet_render_config(SF_ABI_VERSION, height, max_rows, max_cols, hidden, depth, first_omega_0,
+                                       hidden_omega_0, int(bool(outermost_linear)), DTYPES[compute_dtype], device, stream,
+                                       chunk_pixels)
+        self.h = C.c_void_p()
+        _check(self.lib.sf_wavelet_render_create(C.byref(cfg), C.byref(self.h)))
+        n = C.c_int64()
+        _check(self.lib.sf_num_params(self.h, C.byref(n)))
+        self.num_params = n.value
+        self.height, self.width, self.hidden, self.depth = height, height, hidden, depth
+        self.n = (height + 5) // 2
+        self.max_rows, self.max_cols = max_rows or height, max_cols or height
+        self.row_begin, self.row_end = 0, height
+        self.npix = height * height
+        self.out_features = 3
+        self._target = None
+        self._views = {}
+
+    def render(self, r0: int = 0, r1: Optional[int] = None, c0: int = 0, c1: Optional[int] = None, want_u8: bool = True,
+               want_pred: bool = False):
+        """pixel rows [r0, r1) x columns [c0, c1) of the height x height picture (default: all of it), no host sync:
+        (rgb8 [rows, cols, 3] uint8 or None, pred [rows, cols, 3] fp32 or None).  u8 = min(max((int)(pred * 255), 0), 255);
+        pred is bit-identical to WaveletEngine.forward()'s for the same pixels."""
+        return _wavelet_render(self, r0, self.height if r1 is None else r1, c0, self.height if c1 is None else c1,
+                               want_u8, want_pred)
 
 
 class FeatherEngine:

@@ -19,10 +19,12 @@ decode.* keys
   decode.truth      <ppm> or synthetic[:seed]: print loss / PSNR / PSNR_8bit with eval_epoch's formulas
   decode.device     cuda ordinal (default 0)
 
-SIREN of hidden width 32 / 64 / 128 / 256 runs the engine's render kernel (sf_render: bytes straight from the last-layer
-epilogue, no training state on the device).  Everything else - mlp=fourier, mlp=wavelet_siren, SIREN 512 / 1024, widths the
-engine zero-pads - builds the registry model, loads the state dict, runs its own forward and converts with the same
-formula in torch.  `render_path` decides and the log names the path that ran.
+SIREN of engine width 32 / 64 / 128 / 256 runs the engine's render kernel (sf_render: bytes straight from the last-layer
+epilogue, no training state on the device), and mlp=wavelet_siren of those widths on an even, square picture runs
+sf_wavelet_render (the render forward of both sub-networks over the coefficient window a band of pixel rows needs, then
+k_wv_render).  A Small_Dense width the engine zero-pads (90 -> 128, 181 -> 256) runs at the padded width.  Everything else -
+mlp=fourier, SIREN 512 / 1024 - builds the registry model, loads the state dict, runs its own forward and converts with the
+same formula in torch.  `render_path` decides and the log names the path that ran.
 """
 import json
 import logging
@@ -200,16 +202,58 @@ def engine_width(shape: Cfg) -> int:
     return int(shape.mlp.hidden_size * np.sqrt(shape.get("small_dense_density") or 1.0))   # siren.py:88
 
 
-def render_path(shape: Cfg) -> Tuple[str, str]:
-    """('kernel' | 'torch', why): the one place that decides how a model is rendered"""
-    name = shape.mlp.get("name", "siren")
-    if name != "siren":
-        return "torch", f"mlp={name} has no render kernel"
+def padded_width(shape: Cfg) -> Optional[int]:
+    """the width the engine runs the network at: the logical width, or the next kernel width when it zero-pads (the
+    models' own rule, Siren._engine_width); None above 1024"""
     w = engine_width(shape)
-    if w not in KERNEL_WIDTHS:
-        return "torch", (f"SIREN width {w} is " + ("on the wide path" if w in (512, 1024) else "zero-padded by the engine")
-                         + ": no render kernel")
-    return "kernel", f"SIREN {w}x{shape.mlp.depth}: sf_render"
+    return next((k for k in KERNEL_WIDTHS + (512, 1024) if k >= w), None)
+
+
+def render_path(shape: Cfg, height: Optional[int] = None, width: Optional[int] = None) -> Tuple[str, str]:
+    """('kernel' | 'torch', why): the one place that decides how a model is rendered.  height / width: the picture to draw
+    (default: the fitted size), which matters to WaveletSiren only"""
+    name = shape.mlp.get("name", "siren")
+    if name not in ("siren", "wavelet_siren"):
+        return "torch", f"mlp={name} has no render kernel"
+    w, wp = engine_width(shape), padded_width(shape)
+    pad = "" if wp == w else f" (width {w} zero-padded)"
+    if name == "wavelet_siren":
+        img = shape.get("img") or {}
+        H, W = int(height or img.get("height") or 0), int(width or img.get("width") or 0)
+        if wp not in KERNEL_WIDTHS:
+            return "torch", f"WaveletSiren width {w} is above 256: no render kernel"
+        if H != W or H < 2 or H % 2:
+            return "torch", f"WaveletSiren needs an even, square picture (got {H}x{W}): no render kernel"
+        return "kernel", f"WaveletSiren {wp}x{shape.mlp.depth}{pad}: sf_wavelet_render"
+    if wp not in KERNEL_WIDTHS:
+        return "torch", f"SIREN width {w} is on the wide path: no render kernel"
+    return "kernel", f"SIREN {wp}x{shape.mlp.depth}{pad}: sf_render"
+
+
+def registry_model(sd, shape: Cfg):
+    """the registry model of `shape` with `sd` loaded, on the CPU (names, shapes and the padding rule; no engine yet)"""
+    from .models import registry
+    m = dict(shape.mlp)
+    with torch.random.fork_rng(devices=[]):       # the constructor draws an initialisation nobody needs
+        model = registry[m.get("name", "siren")](**m, small_dense_density=shape.get("small_dense_density") or 1.0,
+                                                 **dict(shape.get("engine") or {}))
+    model.load_state_dict(sd)
+    return model
+
+
+def engine_flat_params(sd, shape: Cfg, num_params: int) -> torch.Tensor:
+    """The flat parameter vector of an engine handle with num_params slots: the model's tensors in flat order, scattered
+    through the model's own _padded_index (zeros in the padding) when the engine runs a wider network - what
+    Siren._sync_to_engine hands a training handle."""
+    model = registry_model(sd, shape)
+    logical = torch.cat([p.data.reshape(-1).float() for p in model._param_list()])
+    if not model._padded:
+        if logical.numel() != num_params:
+            raise ValueError(f"the state dict holds {logical.numel()} parameters, the engine handle {num_params}")
+        return logical.contiguous()
+    flat = torch.zeros(num_params)
+    flat[model._padded_index(torch.device("cpu"))] = logical
+    return flat
 
 
 def flat_params(sd: Dict[str, torch.Tensor], depth: int) -> torch.Tensor:
@@ -229,12 +273,14 @@ def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_r
     h, w = rows.numel(), cols.numel()
     bands = plan_bands(h, w, C, band_rows)
     nb = bands[0][1] - bands[0][0]
-    eng = RenderEngine(nb, w, engine_width(shape), int(m.depth), float(m.get("first_omega_0", 50.0)),
+    eng = RenderEngine(nb, w, padded_width(shape), int(m.depth), float(m.get("first_omega_0", 50.0)),
                        float(m.get("hidden_omega_0", 30.0)), bool(m.get("outermost_linear", True)), C,
                        eng_kw.get("compute_dtype", "f16"), device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
     try:
         dev = eng.device
-        eng.set_params(flat_params(sd, int(m.depth)).to(dev))
+        flat = (flat_params(sd, int(m.depth)) if padded_width(shape) == engine_width(shape)
+                else engine_flat_params(sd, shape, eng.num_params))
+        eng.set_params(flat.to(dev))
         cols_d = cols.float().contiguous().to(dev)
         out = torch.empty(h, w, C, dtype=torch.uint8)
         pred = torch.empty(h, w, C) if want_pred else None
@@ -247,6 +293,80 @@ def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_r
             out[r0:r1] = u8[:r1 - r0].cpu()
             if want_pred:
                 pred[r0:r1] = p[:r1 - r0].cpu()
+    finally:
+        eng.close()
+    return out, pred
+
+
+# ---- WaveletSiren: which coefficients a window needs, bands, the kernel path -----------------------------------
+def _wv_tap(o, H: int):
+    """(i0, i1) of wv_tap (csrc/wavelet_kernels.hip) for output index o (int or array), its fp32 arithmetic operation for
+    operation"""
+    import numpy as np
+    n = (H + 5) // 2
+    up = np.float32(1.0 / (float(H) / float(n)))
+    s = up * (np.asarray(o).astype(np.float32) + np.float32(0.5)) - np.float32(0.5)
+    s = np.where(s < 0, np.float32(0), s).astype(np.float32)
+    i0 = s.astype(np.int64)
+    return i0, i0 + (i0 < n - 1)
+
+
+def wavelet_coeff_span(o0: int, o1: int, H: int) -> Tuple[int, int]:
+    """Coefficient rows (or columns) [lo, hi) that output rows [o0, o1) of an H-row WaveletSiren picture read: for Y rows
+    o/2 .. o/2 + 2 (the inverse DWT's gather), for Cb / Cr the two bilinear source rows.  All are monotone in o, so the
+    span is the minimum at o0 and the maximum at o1 - 1 (the library's wv_coeff_span, csrc/wavelet_render.hip)."""
+    if not (0 <= o0 < o1 <= H) or H < 2 or H % 2:
+        raise ValueError(f"need 0 <= o0 < o1 <= H, H even (got [{o0}, {o1}) of {H})")
+    a0, _ = _wv_tap(o0, H)
+    _, b1 = _wv_tap(o1 - 1, H)
+    return min(o0 // 2, int(a0)), max((o1 - 1) // 2 + 2, int(b1)) + 1
+
+
+def plan_wavelet_bands(H: int, r: Tuple[int, int], c: Tuple[int, int], band_rows: Optional[int] = None,
+                       band_bytes: int = BAND_BYTES) -> List[Tuple[int, int]]:
+    """Bands [r0, r1) of pixel rows that cover r = [ra, rb): each keeps rows * cols * 3 < band_bytes and its coefficient
+    window within the render sub-handles' row decode, cr * cc^2 < 2^40 (cc: the coefficient columns of the column window
+    c); band_rows lowers the size further."""
+    cols = c[1] - c[0]
+    j0, j1 = wavelet_coeff_span(c[0], c[1], H)
+    cc = j1 - j0
+    cr_cap = (ROW_LIMIT - 1) // (cc * cc)
+    cap = (band_bytes - 1) // (cols * 3)
+    if cap < 1 or cr_cap < 4:
+        raise ValueError(f"{cols} columns: one row does not fit a band")
+    cap = min(cap, 2 * (cr_cap - 3))              # rows pixel rows read at most rows / 2 + 3 coefficient rows
+    rows = min(r[1] - r[0], cap if not band_rows else max(1, min(cap, int(band_rows))))
+    bands = [(a, min(a + rows, r[1])) for a in range(r[0], r[1], rows)]
+    for a, b in bands:
+        i0, i1 = wavelet_coeff_span(a, b, H)
+        assert (i1 - i0) * cc * cc < ROW_LIMIT
+    return bands
+
+
+def render_wavelet(sd, shape: Cfg, H: int, r: Tuple[int, int], c: Tuple[int, int], band_rows: Optional[int] = None,
+                   want_pred: bool = False, device: int = 0):
+    """uint8 [rows, cols, 3] on the CPU (and the fp32 prediction when asked) of the window r x c of the H x H picture of a
+    WaveletSiren, band by band on ONE render handle (max_rows = the band height, max_cols = the window's): every band runs
+    the two sub-networks over the coefficient window it needs and nothing else."""
+    from ._engine import WaveletRenderEngine
+    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
+    bands = plan_wavelet_bands(H, r, c, band_rows)
+    eng = WaveletRenderEngine(H, padded_width(shape), int(m.depth), float(m.get("first_omega_0", 50.0)),
+                              float(m.get("hidden_omega_0", 50.0)), bool(m.get("outermost_linear", True)),
+                              eng_kw.get("compute_dtype", "f16"), max_rows=bands[0][1] - bands[0][0], max_cols=c[1] - c[0],
+                              device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
+    try:
+        dev = eng.device
+        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(dev))
+        lin = torch.linspace(0, 1, eng.n).to(dev)             # LF_grid = HF_grid = get_grid(n, n) (wavelet_siren.py:76-80)
+        eng.set_coords(lin, lin)
+        out = torch.empty(r[1] - r[0], c[1] - c[0], 3, dtype=torch.uint8)
+        pred = torch.empty(r[1] - r[0], c[1] - c[0], 3) if want_pred else None
+        for a, b in bands:
+            u8, p = eng.render(a, b, c[0], c[1], want_u8=True, want_pred=want_pred)
+            out[a - r[0]:b - r[0]] = u8.cpu()
+            if want_pred:
+                pred[a - r[0]:b - r[0]] = p.cpu()
     finally:
         eng.close()
     return out, pred
@@ -297,9 +417,16 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
     r, c = _span(dec.get("rows"), H, "rows"), _span(dec.get("cols"), W, "cols")
     device = int(dec.get("device") or 0)
     truth = dec.get("truth")
-    path, why = render_path(shape)
+    name = shape.mlp.get("name", "siren")
+    if name == "wavelet_siren":
+        from .models.wavelet_siren import check_image
+        check_image(H, W)                          # the "even, square" refusal, before anything touches the device
+    path, why = render_path(shape, H, W)
     logging.info(f"decode: weights from {source}; {path} path ({why}); {r[1] - r[0]}x{c[1] - c[0]} of a {H}x{W} grid")
-    if path == "kernel":
+    if path == "kernel" and name == "wavelet_siren":
+        u8, pred = render_wavelet(sd, shape, H, r, c, int(dec["band_rows"]) if dec.get("band_rows") else None,
+                                  want_pred=bool(truth), device=device)
+    elif path == "kernel":
         rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
         u8, pred = render_kernel(sd, shape, rows, cols, int(dec["band_rows"]) if dec.get("band_rows") else None,
                                  want_pred=bool(truth), device=device)

@@ -216,6 +216,40 @@ int sf_forward_backward(sf_handle* h, double* sse_out);
  *            truncated toward zero (eval_epoch's (pred * 255).int(), train_helper.py:52), clamped to what a file can hold. */
 int sf_render_create(const sf_config* cfg, sf_handle** out);
 int sf_render(sf_handle* h, uint8_t* rgb8_dev, float* pred_dev);
+/* Inference only, WaveletSiren (csrc/wavelet_render.hip).  sf_wavelet_render_create validates what sf_wavelet_create
+ * validates and allocates the joint parameter vector [LF | HF], two render sub-handles (parameters as views into it, forward
+ * weight images, layer-0 table / image), the two FULL coefficient-grid vectors and ONE pair of fp32 coefficient buffers
+ * sized for the coefficient window of a max_rows x max_cols pixel window - no gradient, Adam moments, mask, phase / delta
+ * scratch, slabs or image-space gradient.  On such a handle sf_set_params, sf_get_params, sf_params_changed, sf_num_params,
+ * sf_param_offset, sf_state_ptr(0), sf_set_coords, sf_destroy and the profiling calls work as on a WaveletSiren training
+ * handle; every training entry point, sf_render and sf_set_target return SF_ERR_INVALID.  sf_set_coords takes the two
+ * linspace(0, 1, n) vectors of the FULL coefficient grid (n = (height + 5) / 2; unchecked, as on a SIREN render handle) and
+ * keeps them: coefficient (i, j) is evaluated at rows[i], cols[j] whatever the window, so a window is bit-identical to the
+ * same region of the full picture. */
+typedef struct sf_wavelet_render_config {
+  int32_t abi_version;      /* SF_ABI_VERSION                                                            */
+  int32_t height;           /* side H of the FULL picture (even, square): fixes n and the bilinear scale */
+  int32_t max_rows, max_cols; /* the largest pixel window one sf_wavelet_render call will draw (0 = H)   */
+  int32_t hidden, depth;    /* as sf_wavelet_config                                                      */
+  float first_omega_0, hidden_omega_0;
+  int32_t outermost_linear;
+  int32_t compute_dtype;    /* SF_F16 only                                                               */
+  int32_t device;           /* HIP device ordinal                                                        */
+  void* stream;             /* hipStream_t (NULL = null stream)                                          */
+  int64_t chunk_pixels;     /* coefficient-grid pixels per sweep of a sub-network (0 = auto)             */
+} sf_wavelet_render_config;
+int sf_wavelet_render_create(const sf_wavelet_render_config* cfg, sf_handle** out);
+/* Draws pixel rows [row0, row1) x columns [col0, col1) of the H x H picture on the handle's stream, no host
+ * synchronisation: the RENDER forward of LF and HF over the coefficient window those pixels read (Y: rows o/2 .. o/2 + 2 of
+ * output row o; Cb / Cr: the two bilinear source rows; likewise for columns), then k_wv_render.  h is a WaveletSiren render
+ * handle or a WaveletSiren training handle (sf_wavelet_create, which uses its own prediction buffers).  Either output may be
+ * NULL, not both, dense [row1 - row0][col1 - col0][3]:
+ *   pred_dev fp32, bit-identical to what sf_forward writes for those pixels on a training handle with the same parameters;
+ *   rgb8_dev bytes (4-byte aligned), u8 = min(max((int)(pred * 255.0f), 0), 255) as sf_render.
+ * Empty windows, windows outside [0, H) or larger than max_rows x max_cols return SF_ERR_INVALID; a call before
+ * sf_set_coords returns SF_ERR_STATE. */
+int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, uint8_t* rgb8_dev,
+                      float* pred_dev);
 /* Adam (+ mask) on the current gradient with learning rate lr; refreshes the low-precision weight images */
 int sf_adam_step(sf_handle* h, float lr);
 /* n_steps x (forward_backward + adam_step) with learning rates lr[0..n_steps) (host array);

@@ -1,0 +1,203 @@
+"""Host side of the WaveletSiren render path, no GPU needed: which coefficients a pixel window reads, how decode picks the
+path and plans bands, the padded parameter layout, and the C ABI's declarations."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from implicit_image import _engine  # noqa: E402
+from implicit_image import decode as dec  # noqa: E402
+from implicit_image.config import _wrap  # noqa: E402
+from implicit_image.models import registry  # noqa: E402
+
+CSRC = os.path.join(ROOT, "implicit-image-compression_amd", "csrc")
+
+
+def tap_fp32(o, H):
+    """numpy-fp32 mirror of wv_tap (csrc/wavelet_kernels.hip), written out independently of decode._wv_tap: every
+    operation rounds to fp32 once"""
+    n = (H + 5) // 2
+    up = np.float32(1.0 / (float(H) / float(n)))
+    a = np.float32(np.float32(o) + np.float32(0.5))
+    m = np.float32(up * a)
+    s = np.float32(m - np.float32(0.5))
+    if s < 0:
+        s = np.float32(0)
+    i0 = int(s)
+    return i0, i0 + (1 if i0 < n - 1 else 0)
+
+
+@pytest.mark.parametrize("H", [2, 4, 6, 8, 10, 64, 250, 1024, 4096])
+def test_coeff_span_against_brute_force(H):
+    """wavelet_coeff_span(o0, o1, H) == [min, max] over o in [o0, o1) of {o/2, o/2 + 2, tap(o).i0, tap(o).i1}: all single
+    rows, a few hundred random windows and the full window, inside [0, n); the full window needs all of [0, n)"""
+    n = (H + 5) // 2
+    idx = np.array([[o // 2, o // 2 + 2, *tap_fp32(o, H)] for o in range(H)])
+    assert (np.diff(idx, axis=0) >= 0).all()                 # monotone in o: what lets the library look at two rows only
+    rng = np.random.default_rng(H)
+    wins = [(o, o + 1) for o in range(H)] + [(0, H)]
+    for _ in range(300):
+        a = int(rng.integers(0, H))
+        wins.append((a, int(rng.integers(a + 1, H + 1))))
+    for o0, o1 in wins:
+        lo, hi = dec.wavelet_coeff_span(o0, o1, H)
+        assert (lo, hi) == (int(idx[o0:o1].min()), int(idx[o0:o1].max()) + 1), (H, o0, o1)
+        assert 0 <= lo < hi <= n
+    assert dec.wavelet_coeff_span(0, H, H) == (0, n)
+    for bad in ((0, 0), (-1, 1), (0, H + 1), (3, 2)):
+        with pytest.raises(ValueError):
+            dec.wavelet_coeff_span(*bad, H)
+
+
+def test_the_librarys_span_function_mirrors_the_python_one():
+    """csrc/wavelet_render.hip states the same rule (the GPU window tests exercise it; here: the text has not drifted)"""
+    src = open(os.path.join(CSRC, "wavelet_render.hip")).read()
+    body = src[src.index("void wv_coeff_span("):]
+    body = body[:body.index("\n}\n")]
+    assert "std::min(o0 / 2, a0)" in body and "std::max((o1 - 1) / 2 + 2, b1) + 1" in body
+    assert "(float)(1.0 / ((double)H / (double)n))" in body
+
+
+def shape_of(name, hidden, depth=8, density=None, H=64, W=64):
+    return _wrap({"mlp": {"name": name, "depth": depth, "hidden_size": hidden, "first_omega_0": 50, "hidden_omega_0": 30,
+                          "outermost_linear": True},
+                  "img": {"height": H, "width": W}, "engine": {}, "small_dense_density": density})
+
+
+def test_render_path():
+    path, why = dec.render_path(shape_of("wavelet_siren", 128))
+    assert path == "kernel" and why == "WaveletSiren 128x8: sf_wavelet_render"
+    sd = shape_of("wavelet_siren", 128, density=0.5)
+    assert dec.engine_width(sd) == 90 and dec.padded_width(sd) == 128
+    path, why = dec.render_path(sd)
+    assert path == "kernel" and why.startswith("WaveletSiren 128x8") and why.endswith("sf_wavelet_render")
+    s181 = shape_of("siren", 256, density=0.5)
+    assert dec.engine_width(s181) == 181 and dec.padded_width(s181) == registry["siren"](
+        depth=8, hidden_size=256, small_dense_density=0.5)._engine_width == 256
+    path, why = dec.render_path(s181)
+    assert path == "kernel" and why.startswith("SIREN 256x8") and why.endswith("sf_render")
+    assert dec.render_path(shape_of("siren", 64)) == ("kernel", "SIREN 64x8: sf_render")
+    # pinned by tests/test_decode_host.py, restated
+    assert dec.render_path(shape_of("fourier", 64))[0] == "torch"
+    assert dec.render_path(shape_of("siren", 512))[0] == "torch"
+    assert dec.render_path(shape_of("siren", 1024))[0] == "torch"
+    assert dec.render_path(shape_of("siren", 1024, density=0.5))[0] == "torch"      # 724 -> 1024
+    assert dec.render_path(shape_of("wavelet_siren", 512))[0] == "torch"
+    # odd or non-square WaveletSiren pictures
+    for H, W in ((63, 63), (64, 32), (0, 0)):
+        path, why = dec.render_path(shape_of("wavelet_siren", 128, H=H, W=W))
+        assert path == "torch" and "even, square" in why
+    path, why = dec.render_path(shape_of("wavelet_siren", 128), 63, 63)              # decode.height / decode.width
+    assert path == "torch" and "even, square" in why
+    assert dec.render_path(shape_of("wavelet_siren", 128, H=63, W=63), 128, 128)[0] == "kernel"
+
+
+def test_decode_refuses_an_odd_wavelet_picture_before_any_gpu_work(tmp_path):
+    torch.manual_seed(0)
+    m = registry["wavelet_siren"](depth=3, hidden_size=32)
+    torch.save({"state_dict": m.state_dict()}, tmp_path / "model.pth")
+    over = ["mlp=wavelet_siren", "mlp.depth=3", "mlp.hidden_size=32"]
+    for size in (["decode.height=63", "decode.width=63"], ["decode.height=64", "decode.width=32"]):
+        with pytest.raises(NotImplementedError, match="even, square"):
+            dec.decode([f"decode.dir={tmp_path}"] + size + over)
+
+
+@pytest.mark.parametrize("H,band_rows,r,c", [(64, 7, (0, 64), (0, 64)), (16384, None, (0, 16384), (0, 16384)),
+                                              (64, 7, (10, 50), (3, 64)), (16384, 5000, (1, 16383), (0, 16384))])
+def test_wavelet_band_planning(H, band_rows, r, c):
+    bands = dec.plan_wavelet_bands(H, r, c, band_rows)
+    assert bands[0][0] == r[0] and bands[-1][1] == r[1]
+    assert all(a[1] == b[0] for a, b in zip(bands, bands[1:])) and all(a < b for a, b in bands)
+    j0, j1 = dec.wavelet_coeff_span(c[0], c[1], H)
+    for a, b in bands:
+        assert (b - a) * (c[1] - c[0]) * 3 < dec.BAND_BYTES
+        i0, i1 = dec.wavelet_coeff_span(a, b, H)
+        assert (i1 - i0) * (j1 - j0) ** 2 < dec.ROW_LIMIT
+        if band_rows:
+            assert b - a <= band_rows
+    if H == 16384 and not band_rows:
+        assert len(bands) > 1                               # 768 MiB of bytes do not fit one band
+    if H == 64 and r == (0, 64):
+        assert bands[:2] == [(0, 7), (7, 14)] and bands[-1] == (63, 64)
+
+
+@pytest.mark.parametrize("name,hidden,depth,density", [("wavelet_siren", 128, 3, 0.5), ("siren", 256, 3, 0.5),
+                                                       ("wavelet_siren", 64, 4, None), ("siren", 64, 4, None)])
+def test_engine_flat_params_is_the_models_own_padding(name, hidden, depth, density):
+    """zeros in the padding, the logical tensors at the slots the model's _padded_index names, in flat order"""
+    shape = shape_of(name, hidden, depth, density)
+    torch.manual_seed(1)
+    m = registry[name](depth=depth, hidden_size=hidden, small_dense_density=density or 1.0)
+    wp, w = dec.padded_width(shape), dec.engine_width(shape)
+    sub = 3 * wp + (depth - 2) * (wp * wp + wp) + 3 * wp + 3
+    P = sub * (2 if name == "wavelet_siren" else 1)
+    state = torch.random.get_rng_state()
+    flat = dec.engine_flat_params(m.state_dict(), shape, P)
+    assert torch.equal(torch.random.get_rng_state(), state)         # the throw-away model's draws leave the generator alone
+    logical = torch.cat([p.data.reshape(-1) for p in m._param_list()])
+    assert flat.shape == (P,) and int((flat != 0).sum()) == int((logical != 0).sum())
+    if wp == w:
+        assert torch.equal(flat, logical)
+    else:
+        assert torch.equal(flat[m._padded_index(torch.device("cpu"))], logical)
+        # layer 1 of the first sub-network: rows / columns beyond the logical width are zero
+        W1 = flat[3 * wp:3 * wp + wp * wp].view(wp, wp)
+        assert torch.equal(W1[:w, :w], m._param_list()[2].data) and not W1[w:].any() and not W1[:, w:].any()
+    if wp == w:
+        with pytest.raises(ValueError):
+            dec.engine_flat_params(m.state_dict(), shape, P + 1)
+
+
+def test_header_and_entry_points():
+    """include/siren_fit.h declares the struct and both functions; both definitions are function-try-blocks inside the
+    extern "C" block (the regular expressions of tests/test_abi_and_host.py); the library exports them; ABI stays 3"""
+    hdr = open(os.path.join(ROOT, "include", "siren_fit.h")).read()
+    assert re.search(r"typedef struct sf_wavelet_render_config \{.*?\} sf_wavelet_render_config;", hdr, flags=re.S)
+    for field in ("abi_version", "height", "max_rows, max_cols", "hidden, depth", "first_omega_0, hidden_omega_0",
+                  "outermost_linear", "compute_dtype", "device", "stream", "chunk_pixels"):
+        assert field in hdr[hdr.index("typedef struct sf_wavelet_render_config"):hdr.index("} sf_wavelet_render_config;")]
+    assert "#define SF_ABI_VERSION 3" in hdr
+    names = _engine.exported_symbols()
+    assert "sf_wavelet_render_create" in names and "sf_wavelet_render" in names
+    src = open(os.path.join(CSRC, "wavelet_render.hip")).read()
+    body = src[src.index('extern "C" {'):src.index('}  // extern "C"')]
+    entry = re.findall(r"^(?:int|const char\*) (sf_\w+)\(", body, flags=re.M)
+    guarded = re.findall(r"^int (sf_\w+)\([^{]*\) try \{", body, flags=re.M)
+    assert sorted(entry) == sorted(guarded) == ["sf_wavelet_render", "sf_wavelet_render_create"]
+    assert '#include "wavelet_render.hip"' in open(os.path.join(CSRC, "siren_fit.hip")).read()
+    lib = _engine.load_library()
+    assert _engine.has_wavelet_render(lib) and lib.sf_abi_version() == 3
+    # the ctypes struct is the header's, field for field
+    assert [f[0] for f in _engine.sf_wavelet_render_config._fields_] == [
+        "abi_version", "height", "max_rows", "max_cols", "hidden", "depth", "first_omega_0", "hidden_omega_0",
+        "outermost_linear", "compute_dtype", "device", "stream", "chunk_pixels"]
+
+
+def test_create_rejects_bad_config_without_gpu():
+    """argument errors come before the device probe, with sf_wavelet_create's messages where the rule is the same"""
+    import ctypes as C
+    lib = _engine.load_library()
+    h = C.c_void_p()
+
+    def create(**kw):
+        f = dict(abi_version=_engine.SF_ABI_VERSION, height=64, max_rows=0, max_cols=0, hidden=64, depth=4, first_omega_0=50.0,
+                 hidden_omega_0=30.0, outermost_linear=1, compute_dtype=1, device=0, stream=None, chunk_pixels=0)
+        f.update(kw)
+        cfg = _engine.sf_wavelet_render_config(**f)
+        return lib.sf_wavelet_render_create(C.byref(cfg), C.byref(h)), lib.sf_last_error().decode()
+    for kw, word in ((dict(height=63), "even, square"), (dict(height=0), "even, square"), (dict(hidden=90), "zero-pad on the host"),
+                     (dict(depth=17), "depth must be 2..16"), (dict(compute_dtype=0), "fp16 operands only"),
+                     (dict(chunk_pixels=-1), "chunk_pixels"), (dict(max_rows=65), "max_rows"), (dict(max_cols=-1), "max_rows"),
+                     (dict(abi_version=2), "abi_version mismatch")):
+        rc, msg = create(**kw)
+        assert rc == -1 and word in msg and not h.value, (kw, rc, msg)
+    assert lib.sf_wavelet_render_create(None, C.byref(h)) == -1
+    assert lib.sf_wavelet_render(None, 0, 1, 0, 1, None, None) == -1
