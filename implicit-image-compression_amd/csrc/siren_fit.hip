@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -56,6 +57,10 @@ static int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                          \
       return fail(SF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
   } while (0)
+#define SF_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// the kernels take phases in revolutions: omega / 2 pi, formed in double
+static constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 // 8-bit scratch: dL/dout is stored as residual * 2^10 in fp16 (residuals of 6e-8 .. 64 stay normal numbers); the
 // adaptive part of the gradient pre-scale is applied by k_bwd8<LAST> (siren_s8.hip)
@@ -98,6 +103,7 @@ struct sf_engine {
   int64_t P = 0;
   int64_t off_w[16], off_b[16];
   hipStream_t stream = nullptr;
+  std::vector<void*> owned;   // every device buffer this handle allocated (dev_alloc); sf_destroy frees exactly these
   long npix = 0;          // local pixels
   double n_total = 0;     // H*W of the full image
   // state
@@ -178,10 +184,10 @@ struct sf_engine {
   long* fth_chunks = nullptr;
   int* fth_chunk0 = nullptr;
   // WaveletSiren (sf_wavelet_create, wavelet_kernels.hip): two SIREN sub-handles whose parameter, gradient, moment and
-  // mask buffers are slices of this handle's; this handle owns the composition, the loss and the optimiser
+  // mask buffers are slices of this handle's (never on the sub-handles' owned lists); this handle owns the composition,
+  // the loss and the optimiser
   bool wavelet = false;
   sf_engine* wv_sub[2] = {nullptr, nullptr};   // LF, HF
-  bool borrowed_state = false;  // sub-handle: params / grads / m / v / mask belong to the WaveletSiren handle
   bool ext_dout = false;        // sub-handle: the training forward runs without a target, dL/dout comes from k_wv_adjoint
   int wv_n = 0;                 // coefficient side
   float wv_up = 0.f;            // bilinear source-index scale
@@ -516,11 +522,10 @@ FwdArgs fwd_args_base(const sf_engine* h, long pix0, int n_super) {
   fa.l0tab = h->l0tab; fa.l0img = reinterpret_cast<const u32x4*>(h->l0img);
   fa.wf = reinterpret_cast<const u32x4*>(h->wf);
   fa.wf_last = reinterpret_cast<const u32x4*>(h->wf_last);
-  const double two_pi = 6.283185307179586476925286766559;
-  fa.sc_first = (float)((double)h->cfg.first_omega_0 / two_pi);
-  fa.sc_hidden = (float)((double)h->cfg.hidden_omega_0 / two_pi / (double)h->wscale);
+  fa.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  fa.sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
   fa.sc_last = 1.0f / h->wscale;
-  if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / two_pi); }
+  if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
   fa.nout = h->cfg.out_features;
   fa.n_super = n_super;
   fa.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
@@ -574,12 +579,12 @@ int refresh_images(sf_engine* h) {
     a.off_b[l] = h->off_b[l];
   }
   a.wscale = h->wscale;
-  a.hscale = (float)((double)h->cfg.hidden_omega_0 / 6.283185307179586476925286766559);
+  a.hscale = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
   a.om_first = h->cfg.first_omega_0; a.om_hidden = h->cfg.hidden_omega_0;
   a.fwd_is_f16 = h->cfg.compute_dtype == SF_F16;
   a.wf = h->wf; a.wf_last = h->wf_last; a.wb = h->wb; a.wb_last = h->wb_last;
   a.l0tab = h->l0tab;
-  a.l0img = h->l0img; a.sc_first = (float)((double)h->cfg.first_omega_0 / 6.283185307179586476925286766559);
+  a.l0img = h->l0img; a.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
   long n = (long)(h->D - 2) * h->WD * h->WD;
   const long n_min = (long)h->WD / 16 * 64 * 8;  // also covers the small tables
   if (n < n_min) n = n_min;
@@ -631,7 +636,7 @@ int refresh_images_wide(sf_engine* h) {
     t.params = h->params; t.depth = D; t.WD = WD; t.out_features = h->cfg.out_features;
     t.off_w0 = h->off_w[0]; t.off_b0 = h->off_b[0];
     for (int l = 0; l < D; ++l) t.off_b[l] = h->off_b[l];
-    t.wscale = h->wscale; t.hscale = (float)((double)h->cfg.hidden_omega_0 / 6.283185307179586476925286766559);
+    t.wscale = h->wscale; t.hscale = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
     t.l0tab = h->l0tab; t.bias = h->biasw;
     long n = (long)(D - 2) * WD;
     if (n < WD) n = WD;
@@ -658,7 +663,7 @@ int refresh_images_wide(sf_engine* h) {
     hipLaunchKernelGGL(k_wimage, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a);
   };
   for (int l = 1; l <= D - 2; ++l) {
-    image(l, false, 8, NBLK, KS / 4, (float)((double)h->cfg.hidden_omega_0 / 6.283185307179586476925286766559),
+    image(l, false, 8, NBLK, KS / 4, (float)((double)h->cfg.hidden_omega_0 / kTwoPi),
           h->wf + (size_t)(l - 1) * WD * WD);
     image(l, true, 8, NBLK, KS / 4, l - 1 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb + (size_t)(l - 1) * WD * WD);
   }
@@ -763,9 +768,8 @@ int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
   if (rc) return rc;
   const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
   const bool f16 = h->cfg.compute_dtype == SF_F16;
-  const double two_pi = 6.283185307179586476925286766559;
-  const float sc_first = (float)((double)h->cfg.first_omega_0 / two_pi);
-  const float sc_hidden = (float)((double)h->cfg.hidden_omega_0 / two_pi / (double)h->wscale);
+  const float sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  const float sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
   const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
   const size_t blk_pieces = (size_t)(KS / 4) * 32;   // pieces of one [256 x WD] block of a hidden image
   long sse_off = 0;
@@ -812,7 +816,7 @@ int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
       a.img = h->img; a.pred = pred; a.nout = h->cfg.out_features;
       a.gscale = (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total));
       a.sse_part = h->sse_part + sse_off; a.Dlast = train ? h->Dlast : nullptr; a.pix0 = pix0; a.npix = h->npix;
-      if (!h->cfg.outermost_linear) { a.last_om = h->cfg.hidden_omega_0; a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / two_pi); }
+      if (!h->cfg.outermost_linear) { a.last_om = h->cfg.hidden_omega_0; a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
       sse_off += n_super;
       Launch L(h, K_FWD, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + 12.0 + 64.0));
       rc = launch_wgemm<1>(h, a, n_super, 1);
@@ -1364,6 +1368,85 @@ int feather_adjoint(sf_engine* h) {
   return SF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// building and freeing a handle: the steps every creator shares
+// ---------------------------------------------------------------------------------------------------------
+// Device memory of a handle.  dev_alloc is the library's one hipMalloc: it records the buffer on h->owned and stores it in
+// the typed field, and sf_destroy frees that list - a new buffer is one dev_alloc line and cannot be leaked.  A view into
+// another handle's buffer (the state of a WaveletSiren's sub-networks) is a plain assignment and never on a list.
+template <typename T>
+int dev_alloc(sf_engine* h, T*& field, size_t bytes) {
+  h->owned.push_back(nullptr);   // the slot first: a std::bad_alloc of the list must not strand a device buffer
+  const hipError_t e = hipMalloc(&h->owned.back(), bytes ? bytes : 16);
+  if (e != hipSuccess) {
+    h->owned.pop_back();
+    return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+  }
+  field = static_cast<T*>(h->owned.back());
+  return SF_OK;
+}
+// frees one owned buffer and forgets it: for the buffers that get replaced (scratch of another format, longer step tables)
+void dev_free(sf_engine* h, void* p) {
+  const auto it = std::find(h->owned.begin(), h->owned.end(), p);
+  if (!p || it == h->owned.end()) return;
+  hipFree(p);
+  h->owned.erase(it);
+}
+// a handle under construction: an early return (or an exception) destroys it with everything it owns so far
+struct HandleDeleter { void operator()(sf_engine* h) const { sf_destroy(h); } };
+using HandlePtr = std::unique_ptr<sf_engine, HandleDeleter>;
+
+// the device of a new handle exists and is a gfx950 (the creator makes it current with a DevGuard afterwards)
+template <typename Config>
+int check_device(const Config* cfg, hipDeviceProp_t& prop) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SF_ERR_NO_DEVICE, "no HIP device visible");
+  if (cfg->device < 0 || cfg->device >= ndev) return fail(SF_ERR_INVALID, "bad device ordinal");
+  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(SF_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950");
+  return SF_OK;
+}
+// Adam: all-zero betas / eps mean torch.optim.Adam's defaults; the doubles behind the float betas (shortest_double)
+void adam_defaults(sf_engine* h) {
+  sf_config& c = h->cfg;
+  if (c.beta1 == 0.f && c.beta2 == 0.f && c.eps == 0.f) { c.beta1 = 0.9f; c.beta2 = 0.999f; c.eps = 1e-8f; }
+  h->beta1_d = shortest_double(c.beta1);
+  h->beta2_d = shortest_double(c.beta2);
+}
+// the flat fp32 state of a training handle: parameters, gradient and Adam moments (zeroed on the handle's stream), mask
+int alloc_train_state(sf_engine* h) {
+  const size_t bytes = (size_t)h->P * 4;
+  for (float** p : {&h->params, &h->grads, &h->m, &h->v, &h->mask}) SF_TRY(dev_alloc(h, *p, bytes));
+  for (float* p : {h->params, h->grads, h->m, h->v}) hipMemsetAsync(p, 0, bytes, h->stream);
+  return SF_OK;
+}
+// chunk length of a handle: whole 256-pixel groups, at most the padded local image
+long round_super(long px) { return (px + kSuper - 1) / kSuper * kSuper; }
+long chunk_pixels(long want, long npix) { return std::min(round_super(want), round_super(npix)); }
+// SSE partials of a chunked pass (one per 256-pixel group, then one per chunk) and the scalar they reduce to
+long chunked_sse_parts(const sf_engine* h) {
+  return round_super(h->npix) / kSuper + (h->npix + h->chunk_px - 1) / h->chunk_px + 8;
+}
+int alloc_sse(sf_engine* h, long n_sse) {
+  h->n_sse = n_sse;
+  SF_TRY(dev_alloc(h, h->sse_part, (size_t)(n_sse + 64) * 4));
+  return dev_alloc(h, h->sse_dev, 8);
+}
+// what the forward reads, on a training and on a render handle alike: the forward weight images (width <= 256; the wide
+// path has its own blocked images), the layer-0 table / image and the two coordinate vectors
+int alloc_forward_inputs(sf_engine* h) {
+  const int WD = h->WD, D = h->D;
+  if (!h->wide) {
+    SF_TRY(dev_alloc(h, h->wf, (size_t)(D - 2 > 0 ? D - 2 : 1) * FwdGeom(WD).PIECES * 1024));
+    SF_TRY(dev_alloc(h, h->wf_last, (size_t)(WD / 16 + 1) * 1024));
+  }
+  SF_TRY(dev_alloc(h, h->l0tab, (size_t)WD * 16));
+  if (WD == 256) SF_TRY(dev_alloc(h, h->l0img, (size_t)(WD / 32) * 1024));
+  SF_TRY(dev_alloc(h, h->gh, (size_t)h->cfg.height * 4));
+  return dev_alloc(h, h->gw, (size_t)h->cfg.width * 4);
+}
+
 }  // namespace
 
 // No exception crosses the C ABI (include/siren_fit.h): every entry point is a function-try-block.  std::bad_alloc becomes
@@ -1377,15 +1460,18 @@ static int fail_nomem() noexcept {
   catch (const std::exception& e) { try { return fail(SF_ERR_INVALID, std::string("unexpected exception: ") + e.what()); } catch (...) { return fail_nomem(); } } \
   catch (...) { try { return fail(SF_ERR_INVALID, "unexpected exception"); } catch (...) { return fail_nomem(); } }
 
-extern "C" {
-
-int sf_abi_version(void) { return SF_ABI_VERSION; }
-const char* sf_last_error(void) { return g_err.c_str(); }
-
-static void set_scratch_strides(sf_engine* h);
+// layer strides of the phase / delta scratch for the handle's current format
+static void set_scratch_strides(sf_engine* h) {
+  const long chunk = h->chunk_px;
+  const int WD = h->WD;
+  h->p_stride = chunk / 32 * (h->s8 ? WD / 32 : WD / 16) * 64 + 37 * 64;
+  h->d_stride = chunk / 32 * (h->d8 ? WD / 32 : WD / 16) * 64 + 37 * 64;
+  h->a_stride = chunk / 32 * (WD / 16) * 64 + 37 * 64;
+}
 // sf_create and sf_render_create (siren_render.hip): one validation, one geometry; a render handle allocates the forward's
-// inputs only
-static int create_handle(const sf_config* cfg, sf_handle** out, bool render) {
+// inputs only.  sub_network: the handle is one of the two SIRENs of a WaveletSiren handle, which points params / grads / m /
+// v / mask at slices of its own joint vectors - nothing is allocated for them here
+static int create_handle(const sf_config* cfg, sf_handle** out, bool render, bool sub_network = false) {
   if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
@@ -1414,24 +1500,16 @@ static int create_handle(const sf_config* cfg, sf_handle** out, bool render) {
   if ((double)(r1 - r0) * (double)cfg->width * (double)cfg->width >= 1099511627776.0)
     return fail(SF_ERR_INVALID, "grid too large for one handle: (row_end - row_begin) * width^2 must stay below 2^40 "
                                 "(shard the rows over more handles)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SF_ERR_NO_DEVICE, "no HIP device visible");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(SF_ERR_INVALID, "bad device ordinal");
-  DevGuard dev_guard(cfg->device);   // the caller's current device is restored on return
   hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(SF_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950");
+  SF_TRY(check_device(cfg, prop));
+  DevGuard dev_guard(cfg->device);   // the caller's current device is restored on return
 
-  sf_engine* h = new sf_engine();
+  HandlePtr owner(new sf_engine());
+  sf_engine* h = owner.get();
   h->cfg = *cfg;
   h->cfg.row_begin = r0;
   h->cfg.row_end = r1;
-  if (h->cfg.beta1 == 0.f && h->cfg.beta2 == 0.f && h->cfg.eps == 0.f) {
-    h->cfg.beta1 = 0.9f; h->cfg.beta2 = 0.999f; h->cfg.eps = 1e-8f;
-  }
-  h->beta1_d = shortest_double(h->cfg.beta1);
-  h->beta2_d = shortest_double(h->cfg.beta2);
+  adam_defaults(h);
   h->D = cfg->depth;
   h->WD = cfg->hidden;
   h->wide = cfg->hidden > 256;
@@ -1471,10 +1549,7 @@ static int create_handle(const sf_config* cfg, sf_handle** out, bool render) {
   if (cfg->compute_dtype == SF_F16) h->gpre = (float)exp2(ceil(log2((double)cfg->out_features * (double)cfg->height * (double)cfg->width)) + 2.0);
   // chunking
   // default: 4 Mi pixels at width <= 256 (29 GB of scratch at 256x8); the same scratch budget for wider layers
-  long chunk = cfg->chunk_pixels > 0 ? cfg->chunk_pixels : (1L << 22) / (h->wide ? cfg->hidden / 256 : 1);
-  chunk = (chunk + kSuper - 1) / kSuper * kSuper;
-  const long npix_pad = (h->npix + kSuper - 1) / kSuper * kSuper;
-  if (chunk > npix_pad) chunk = npix_pad;
+  const long chunk = chunk_pixels(cfg->chunk_pixels > 0 ? cfg->chunk_pixels : (1L << 22) / (h->wide ? cfg->hidden / 256 : 1), h->npix);
   h->chunk_px = chunk;
   const int WD = h->WD, D = h->D;
   // layer stride of the scratch tensors, padded so that the three streams a kernel touches at once are
@@ -1485,65 +1560,110 @@ static int create_handle(const sf_config* cfg, sf_handle** out, bool render) {
   h->dw_wg = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   if (const char* e = getenv("SIREN_FIT_BWD_WGS")) { const int v = atoi(e); if (v >= 8 && v <= h->dw_wg) h->dw_wg = v; }   // experiment knob
 
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    return SF_OK;
-  };
-  int rc = SF_OK;
-#define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
   if (render) {   // parameters, forward weight images, layer-0 table / image, the two coordinate vectors
-    ALLOC(h->params, h->P * 4);
-    ALLOC(h->wf, (size_t)(D - 2 > 0 ? D - 2 : 1) * FwdGeom(WD).PIECES * 1024); ALLOC(h->wf_last, (size_t)(WD / 16 + 1) * 1024);
-    ALLOC(h->l0tab, (size_t)WD * 16);
-    if (WD == 256) ALLOC(h->l0img, (size_t)(WD / 32) * 1024);
-    ALLOC(h->gh, (size_t)cfg->height * 4); ALLOC(h->gw, (size_t)cfg->width * 4);
-    if (rc) { sf_destroy(h); return rc; }
-    hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
-    *out = h;
+    if (!sub_network) {
+      SF_TRY(dev_alloc(h, h->params, h->P * 4));
+      hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
+    }
+    SF_TRY(alloc_forward_inputs(h));
+    *out = owner.release();
     return SF_OK;
   }
-  ALLOC(h->params, h->P * 4); ALLOC(h->grads, h->P * 4); ALLOC(h->m, h->P * 4); ALLOC(h->v, h->P * 4);
-  ALLOC(h->mask, h->P * 4);
+  if (!sub_network) SF_TRY(alloc_train_state(h));
+  SF_TRY(alloc_forward_inputs(h));
   const size_t img_elems = (size_t)(D - 2 > 0 ? D - 2 : 1) * WD * WD;
+  SF_TRY(dev_alloc(h, h->wb, img_elems * 2));
   if (h->wide) {   // blocked images of siren_wide.hip
-    ALLOC(h->wf, img_elems * 2); ALLOC(h->wb, img_elems * 2);
-    ALLOC(h->wf_last, (size_t)(WD / 16) * 1024); ALLOC(h->wb_last, (size_t)(WD / 256) * 32 * 1024);
-    ALLOC(h->biasw, ((size_t)(D - 2) * WD + 32) * 4);
+    SF_TRY(dev_alloc(h, h->wf, img_elems * 2));
+    SF_TRY(dev_alloc(h, h->wf_last, (size_t)(WD / 16) * 1024));
+    SF_TRY(dev_alloc(h, h->wb_last, (size_t)(WD / 256) * 32 * 1024));
+    SF_TRY(dev_alloc(h, h->biasw, ((size_t)(D - 2) * WD + 32) * 4));
   } else {
-    ALLOC(h->wf, (size_t)(D - 2 > 0 ? D - 2 : 1) * FwdGeom(WD).PIECES * 1024); ALLOC(h->wb, img_elems * 2);
-    ALLOC(h->wf_last, (size_t)(WD / 16 + 1) * 1024); ALLOC(h->wb_last, (size_t)WD / 32 * 64 * 16);
+    SF_TRY(dev_alloc(h, h->wb_last, (size_t)WD / 32 * 64 * 16));
   }
-  ALLOC(h->l0tab, (size_t)WD * 16);
-  if (WD == 256) ALLOC(h->l0img, (size_t)(WD / 32) * 1024);
   if (WD == 256 && D >= 3 && !h->wide && cfg->compute_dtype == SF_F16 && getenv("SIREN_FIT_FWD16") && atoi(getenv("SIREN_FIT_FWD16")) == 1) {
-    ALLOC(h->wf16, (size_t)(D - 2) * FwdGeom(WD).PIECES * 1024); ALLOC(h->wf16_last, (size_t)(WD / 16 + 1) * 1024);
-    ALLOC(h->l0img16, (size_t)(WD / 32) * 1024);
+    SF_TRY(dev_alloc(h, h->wf16, (size_t)(D - 2) * FwdGeom(WD).PIECES * 1024));
+    SF_TRY(dev_alloc(h, h->wf16_last, (size_t)(WD / 16 + 1) * 1024));
+    SF_TRY(dev_alloc(h, h->l0img16, (size_t)(WD / 32) * 1024));
   }
-  ALLOC(h->gh, (size_t)cfg->height * 4); ALLOC(h->gw, (size_t)cfg->width * 4);
-  ALLOC(h->Pbuf, (size_t)(D - 1) * h->p_stride * 16); ALLOC(h->Dbuf, (size_t)(D - 1) * h->d_stride * 16);
-  if (h->wide) ALLOC(h->Abuf, (size_t)(D - 1) * h->a_stride * 16);
-  ALLOC(h->Dlast, (size_t)chunk / 32 * 2 * 64 * 16);
-  { const size_t sw = WD > 256 ? 256 : WD; ALLOC(h->slab, (size_t)h->dw_wg * (sw * sw + sw) * 4 + 4096); }
-  h->n_sse = npix_pad / kSuper + (h->npix + chunk - 1) / chunk + 8;
-  ALLOC(h->sse_part, (h->n_sse + 64) * 4); ALLOC(h->sse_dev, 8); ALLOC(h->scale_dev, 16); ALLOC(h->pad8, 16384); ALLOC(h->lsc, 32 * 4 + 16 * 8);
-  if (!rc && hipMemset(h->pad8, 0, 16384) != hipSuccess) rc = fail(SF_ERR_NOMEM, "hipMemset failed");
-#undef ALLOC
-  if (rc) { sf_destroy(h); return rc; }
-  {
-    const float sc[2] = {(float)((double)h->gpre / ((double)cfg->out_features * h->n_total)), 1.0f / h->gpre};
-    if (hipMemcpy(h->scale_dev, sc, sizeof(sc), hipMemcpyHostToDevice) != hipSuccess) {
-      sf_destroy(h);
-      return fail(SF_ERR_HIP, "hipMemcpy(scale) failed");
-    }
-  }
-  hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->grads, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->m, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->v, 0, h->P * 4, h->stream);
-  *out = h;
+  SF_TRY(dev_alloc(h, h->Pbuf, (size_t)(D - 1) * h->p_stride * 16));
+  SF_TRY(dev_alloc(h, h->Dbuf, (size_t)(D - 1) * h->d_stride * 16));
+  if (h->wide) SF_TRY(dev_alloc(h, h->Abuf, (size_t)(D - 1) * h->a_stride * 16));
+  SF_TRY(dev_alloc(h, h->Dlast, (size_t)chunk / 32 * 2 * 64 * 16));
+  { const size_t sw = WD > 256 ? 256 : WD; SF_TRY(dev_alloc(h, h->slab, (size_t)h->dw_wg * (sw * sw + sw) * 4 + 4096)); }
+  SF_TRY(alloc_sse(h, chunked_sse_parts(h)));
+  SF_TRY(dev_alloc(h, h->scale_dev, 16));
+  SF_TRY(dev_alloc(h, h->pad8, 16384));
+  SF_TRY(dev_alloc(h, h->lsc, 32 * 4 + 16 * 8));
+  if (hipMemset(h->pad8, 0, 16384) != hipSuccess) return fail(SF_ERR_NOMEM, "hipMemset failed");
+  const float sc[2] = {(float)((double)h->gpre / ((double)cfg->out_features * h->n_total)), 1.0f / h->gpre};
+  if (hipMemcpy(h->scale_dev, sc, sizeof(sc), hipMemcpyHostToDevice) != hipSuccess) return fail(SF_ERR_HIP, "hipMemcpy(scale) failed");
+  *out = owner.release();
   return SF_OK;
 }
+// ---- WaveletSiren: what sf_wavelet_create and sf_wavelet_render_create (wavelet_render.hip) share ------------------
+// the argument checks both creators word identically, in the order both run them
+template <typename Config>
+static int wavelet_check_network(const Config* cfg) {
+  if (cfg->hidden != 32 && cfg->hidden != 64 && cfg->hidden != 128 && cfg->hidden != 256)
+    return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128 or 256 for WaveletSiren (other widths: zero-pad on the host)");
+  if (cfg->depth < 2 || cfg->depth > 16) return fail(SF_ERR_INVALID, "depth must be 2..16");
+  if (cfg->compute_dtype != SF_F16) return fail(SF_ERR_INVALID, "WaveletSiren runs fp16 operands only (compute_dtype SF_F16)");
+  return SF_OK;
+}
+static int wavelet_check_image(int height, int width, int64_t chunk_pixels) {
+  if (height != width || height < 2 || height % 2)
+    return fail(SF_ERR_INVALID, "WaveletSiren needs an even, square image: the reference's inverse DWT (2n - 4 rows) and its "
+                                "torch.cat of Y with the upsampled Cb / Cr stop matching otherwise");
+  if ((double)height * (double)width >= 2147483648.0) return fail(SF_ERR_INVALID, "image too large");
+  if (chunk_pixels < 0) return fail(SF_ERR_INVALID, "chunk_pixels must be >= 0");
+  return SF_OK;
+}
+// config of the two sub-networks: SIRENs of the creator's shape on a rows x cols coefficient grid, scratch format 16
+template <typename Config>
+static sf_config wavelet_sub_config(const Config* cfg, int rows, int cols) {
+  sf_config sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.abi_version = SF_ABI_VERSION; sc.height = rows; sc.width = cols; sc.row_begin = 0; sc.row_end = rows;
+  sc.in_features = 2; sc.out_features = 3; sc.hidden = cfg->hidden; sc.depth = cfg->depth;
+  sc.first_omega_0 = cfg->first_omega_0; sc.hidden_omega_0 = cfg->hidden_omega_0; sc.outermost_linear = cfg->outermost_linear;
+  sc.compute_dtype = SF_F16; sc.device = cfg->device; sc.stream = cfg->stream; sc.chunk_pixels = cfg->chunk_pixels;
+  sc.scratch_format = 16;
+  return sc;
+}
+// the two sub-networks (LF, HF; their flat state stays unallocated: the creator points it at slices of the joint vectors
+// it allocates), then the handle itself with the geometry of an H x H picture
+static int wavelet_begin(const sf_config& sc, bool render, int H, HandlePtr& owner) {
+  HandlePtr sub[2];
+  for (HandlePtr& s : sub) {
+    sf_handle* e = nullptr;
+    SF_TRY(create_handle(&sc, &e, render, true));   // (render: refuses rows * cols^2 >= 2^40: draw such a picture in bands)
+    s.reset(e);
+  }
+  owner.reset(new sf_engine());
+  sf_engine* h = owner.get();
+  h->wavelet = true;
+  h->render = render;
+  h->cfg = sub[0]->cfg;
+  h->cfg.height = H; h->cfg.width = H; h->cfg.row_begin = 0; h->cfg.row_end = H;
+  h->beta1_d = sub[0]->beta1_d; h->beta2_d = sub[0]->beta2_d;
+  h->D = 2 * sc.depth; h->WD = sc.hidden;
+  h->dw_wg = sub[0]->dw_wg;
+  h->stream = (hipStream_t)sc.stream;
+  h->npix = (long)H * H;
+  h->n_total = (double)H * (double)H;
+  h->wv_n = (H + 5) / 2;   // pywt.dwt_coeff_len(H, 6, "zero")
+  h->wv_up = (float)(1.0 / ((double)H / (double)h->wv_n));   // torch: scale_factor = H / n, source scale 1 / scale_factor
+  h->P = 2 * sub[0]->P;
+  h->wv_sub[0] = sub[0].release(); h->wv_sub[1] = sub[1].release();
+  return SF_OK;
+}
+
+extern "C" {
+
+int sf_abi_version(void) { return SF_ABI_VERSION; }
+const char* sf_last_error(void) { return g_err.c_str(); }
+
 int sf_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, false); } SF_CATCH
 
 // FourierNet handle: the same sf_engine, run by fourier_kernels.hip (run_pass_fourier); every other entry point is shared
@@ -1562,16 +1682,12 @@ int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
   if (cfg->height < 1 || cfg->width < 1) return fail(SF_ERR_INVALID, "bad image size");
   if ((double)cfg->height * (double)cfg->width >= 2147483648.0) return fail(SF_ERR_INVALID, "image too large: height * width must stay below 2^31");
   if (cfg->chunk_pixels < 0) return fail(SF_ERR_INVALID, "chunk_pixels must be >= 0");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SF_ERR_NO_DEVICE, "no HIP device visible");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(SF_ERR_INVALID, "bad device ordinal");
-  DevGuard dev_guard(cfg->device);
   hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(SF_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950");
+  SF_TRY(check_device(cfg, prop));
+  DevGuard dev_guard(cfg->device);
 
-  sf_engine* h = new sf_engine();
+  HandlePtr owner(new sf_engine());
+  sf_engine* h = owner.get();
   h->fourier = true;
   memset(&h->cfg, 0, sizeof(h->cfg));
   h->cfg.abi_version = cfg->abi_version;
@@ -1579,11 +1695,9 @@ int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
   h->cfg.in_features = cfg->in_features; h->cfg.out_features = cfg->out_features; h->cfg.hidden = cfg->hidden;
   h->cfg.depth = cfg->n_linear; h->cfg.compute_dtype = cfg->compute_dtype;
   h->cfg.beta1 = cfg->beta1; h->cfg.beta2 = cfg->beta2; h->cfg.eps = cfg->eps;
-  if (h->cfg.beta1 == 0.f && h->cfg.beta2 == 0.f && h->cfg.eps == 0.f) { h->cfg.beta1 = 0.9f; h->cfg.beta2 = 0.999f; h->cfg.eps = 1e-8f; }
   h->cfg.device = cfg->device; h->cfg.stream = cfg->stream; h->cfg.chunk_pixels = cfg->chunk_pixels;
   h->cfg.scratch_format = 16;
-  h->beta1_d = shortest_double(h->cfg.beta1);
-  h->beta2_d = shortest_double(h->cfg.beta2);
+  adam_defaults(h);
   h->D = cfg->n_linear; h->WD = cfg->hidden; h->MS = cfg->map_size;
   h->stream = (hipStream_t)cfg->stream;
   h->npix = (long)cfg->height * cfg->width;
@@ -1604,40 +1718,25 @@ int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
   h->gpre = (float)exp2(ceil(log2((double)cfg->out_features * (double)cfg->height * (double)cfg->width)) + 2.0);
   // chunking: 4 Mi pixels, or fewer when the activation + gradient planes of a chunk would pass 16 GiB
   const double px_bytes = (double)(D - 1) * WD * 4.0 + 8.0;
-  long chunk = cfg->chunk_pixels > 0 ? (long)cfg->chunk_pixels : (long)fmin((double)(1L << 22), 17179869184.0 / px_bytes);
-  chunk = (chunk + kSuper - 1) / kSuper * kSuper;
-  const long npix_pad = (h->npix + kSuper - 1) / kSuper * kSuper;
-  if (chunk > (1L << 22)) chunk = 1L << 22;   // the kernels address a [WD][chunk] plane with 32-bit offsets
-  if (chunk > npix_pad) chunk = npix_pad;
+  // (never more than 4 Mi: the kernels address a [WD][chunk] plane with 32-bit offsets)
+  const long want = cfg->chunk_pixels > 0 ? (long)cfg->chunk_pixels : (long)fmin((double)(1L << 22), 17179869184.0 / px_bytes);
+  const long chunk = chunk_pixels(std::min(want, 1L << 22), h->npix);
   h->chunk_px = chunk;
   h->dw_wg = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   h->ff_dw_wgs = 4 * h->dw_wg;
   long slab_row = (long)WD * MS + WD;
   if ((long)WD * WD + WD > slab_row) slab_row = (long)WD * WD + WD;
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    return SF_OK;
-  };
-  int rc = SF_OK;
-#define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
-  ALLOC(h->params, h->P * 4); ALLOC(h->grads, h->P * 4); ALLOC(h->m, h->P * 4); ALLOC(h->v, h->P * 4);
-  ALLOC(h->mask, h->P * 4);
-  ALLOC(h->ffimg, (size_t)h->ff_img_n * 16);
-  ALLOC(h->ffB, (size_t)cfg->in_features * (MS / 2) * 4);
-  ALLOC(h->gh, (size_t)cfg->height * 4); ALLOC(h->gw, (size_t)cfg->width * 4);
-  ALLOC(h->ffH, (size_t)(D - 1) * WD * chunk * 2); ALLOC(h->ffG, (size_t)(D - 1) * WD * chunk * 2);
-  ALLOC(h->ffZ, (size_t)4 * chunk * 2);
-  ALLOC(h->slab, (size_t)h->ff_dw_wgs * slab_row * 4);
-  h->n_sse = npix_pad / kSuper + (h->npix + chunk - 1) / chunk + 8;
-  ALLOC(h->sse_part, (h->n_sse + 64) * 4); ALLOC(h->sse_dev, 8);
-#undef ALLOC
-  if (rc) { sf_destroy(h); return rc; }
-  hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->grads, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->m, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->v, 0, h->P * 4, h->stream);
-  *out = h;
+  SF_TRY(alloc_train_state(h));
+  SF_TRY(dev_alloc(h, h->ffimg, (size_t)h->ff_img_n * 16));
+  SF_TRY(dev_alloc(h, h->ffB, (size_t)cfg->in_features * (MS / 2) * 4));
+  SF_TRY(dev_alloc(h, h->gh, (size_t)cfg->height * 4));
+  SF_TRY(dev_alloc(h, h->gw, (size_t)cfg->width * 4));
+  SF_TRY(dev_alloc(h, h->ffH, (size_t)(D - 1) * WD * chunk * 2));
+  SF_TRY(dev_alloc(h, h->ffG, (size_t)(D - 1) * WD * chunk * 2));
+  SF_TRY(dev_alloc(h, h->ffZ, (size_t)4 * chunk * 2));
+  SF_TRY(dev_alloc(h, h->slab, (size_t)h->ff_dw_wgs * slab_row * 4));
+  SF_TRY(alloc_sse(h, chunked_sse_parts(h)));
+  *out = owner.release();
   return SF_OK;
 } SF_CATCH
 
@@ -1653,84 +1752,38 @@ int sf_wavelet_create(const sf_wavelet_config* cfg, sf_handle** out) try {
   if (cfg->wavelet_levels != 1)
     return fail(SF_ERR_INVALID, "wavelet_levels must be 1: the reference's single-level inverse DWT receives 3 * levels bands "
                                 "and fails for more");
-  if (cfg->hidden != 32 && cfg->hidden != 64 && cfg->hidden != 128 && cfg->hidden != 256)
-    return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128 or 256 for WaveletSiren (other widths: zero-pad on the host)");
-  if (cfg->depth < 2 || cfg->depth > 16) return fail(SF_ERR_INVALID, "depth must be 2..16");
-  if (cfg->compute_dtype != SF_F16) return fail(SF_ERR_INVALID, "WaveletSiren runs fp16 operands only (compute_dtype SF_F16)");
+  SF_TRY(wavelet_check_network(cfg));
   if (cfg->scratch_format != 0 && cfg->scratch_format != 16)
     return fail(SF_ERR_INVALID, "WaveletSiren runs scratch format 16 (0 = auto resolves to it): format 8 takes its fp8 delta "
                                 "scale from the fused residual, which a WaveletSiren pass does not form");
-  if (cfg->height != cfg->width || cfg->height < 2 || cfg->height % 2)
-    return fail(SF_ERR_INVALID, "WaveletSiren needs an even, square image: the reference's inverse DWT (2n - 4 rows) and its "
-                                "torch.cat of Y with the upsampled Cb / Cr stop matching otherwise");
-  if ((double)cfg->height * (double)cfg->width >= 2147483648.0) return fail(SF_ERR_INVALID, "image too large");
-  if (cfg->chunk_pixels < 0) return fail(SF_ERR_INVALID, "chunk_pixels must be >= 0");
-  const int H = cfg->height, n = (H + 5) / 2;   // pywt.dwt_coeff_len(H, 6, "zero")
-  sf_config sc;
-  memset(&sc, 0, sizeof(sc));
-  sc.abi_version = SF_ABI_VERSION; sc.height = n; sc.width = n; sc.row_begin = 0; sc.row_end = n;
-  sc.in_features = 2; sc.out_features = 3; sc.hidden = cfg->hidden; sc.depth = cfg->depth;
-  sc.first_omega_0 = cfg->first_omega_0; sc.hidden_omega_0 = cfg->hidden_omega_0; sc.outermost_linear = cfg->outermost_linear;
-  sc.compute_dtype = SF_F16; sc.beta1 = cfg->beta1; sc.beta2 = cfg->beta2; sc.eps = cfg->eps;
-  sc.device = cfg->device; sc.stream = cfg->stream; sc.chunk_pixels = cfg->chunk_pixels; sc.scratch_format = 16;
-  sf_handle* sub[2] = {nullptr, nullptr};
-  for (int s = 0; s < 2; ++s) {
-    const int rc = sf_create(&sc, &sub[s]);
-    if (rc) { if (s) sf_destroy(sub[0]); return rc; }
-  }
+  SF_TRY(wavelet_check_image(cfg->height, cfg->width, cfg->chunk_pixels));
+  const int H = cfg->height, n = (H + 5) / 2;
+  sf_config sc = wavelet_sub_config(cfg, n, n);
+  sc.beta1 = cfg->beta1; sc.beta2 = cfg->beta2; sc.eps = cfg->eps;
+  HandlePtr owner;
+  SF_TRY(wavelet_begin(sc, false, H, owner));
   DevGuard dev_guard(cfg->device);
-  sf_engine* h = new sf_engine();
-  h->wavelet = true;
-  h->wv_sub[0] = sub[0]; h->wv_sub[1] = sub[1];
-  h->cfg = sub[0]->cfg;
-  h->cfg.height = H; h->cfg.width = H; h->cfg.row_begin = 0; h->cfg.row_end = H;
-  h->beta1_d = sub[0]->beta1_d; h->beta2_d = sub[0]->beta2_d;
-  h->D = 2 * cfg->depth; h->WD = cfg->hidden;
-  h->dw_wg = sub[0]->dw_wg;
-  h->stream = (hipStream_t)cfg->stream;
-  h->npix = (long)H * H;
-  h->n_total = (double)H * (double)H;
-  h->wv_n = n;
-  h->wv_up = (float)(1.0 / ((double)H / (double)n));   // torch: scale_factor = H / n, source scale 1 / scale_factor
-  const long nn = sub[0]->npix;
-  const bool one = nn <= sub[0]->chunk_px;
+  sf_engine* h = owner.get();
+  const long nn = h->wv_sub[0]->npix;
+  const bool one = nn <= h->wv_sub[0]->chunk_px;
   h->chunk_px = one ? h->npix : 1;   // (sf_step's graph replay covers single-chunk fits only)
-  const int64_t P0 = sub[0]->P;
-  h->P = 2 * P0;
+  const int64_t P0 = h->wv_sub[0]->P;
   // the sub-networks' dL/dout pre-scale comes from the 3 H^2 values of the full image (what the loss mean divides by)
   const float gpre = (float)exp2(ceil(log2(3.0 * h->n_total)) + 2.0);
   for (sf_engine* s : h->wv_sub) { s->gpre = gpre; s->ext_dout = true; }
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    return SF_OK;
-  };
-  int rc = SF_OK;
-#define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
-  ALLOC(h->params, h->P * 4); ALLOC(h->grads, h->P * 4); ALLOC(h->m, h->P * 4); ALLOC(h->v, h->P * 4);
-  ALLOC(h->mask, h->P * 4);
-  ALLOC(h->wv_pred, (size_t)2 * nn * 3 * 4);
-  ALLOC(h->wv_g, (size_t)h->npix * 3 * 4);
-  if (!one) ALLOC(h->wv_gl, (size_t)2 * nn * 3 * 4);
-  if (!cfg->outermost_linear) ALLOC(h->wv_dfac, (size_t)2 * nn * 3 * 4);
-  h->n_sse = (h->npix + kWvThreads - 1) / kWvThreads;
-  ALLOC(h->sse_part, (h->n_sse + 64) * 4); ALLOC(h->sse_dev, 8);
-#undef ALLOC
-  if (rc) { sf_destroy(h); return rc; }
-  for (int s = 0; s < 2; ++s) {   // the sub-handles' state becomes the two halves of the joint vectors
+  SF_TRY(alloc_train_state(h));
+  SF_TRY(dev_alloc(h, h->wv_pred, (size_t)2 * nn * 3 * 4));
+  SF_TRY(dev_alloc(h, h->wv_g, (size_t)h->npix * 3 * 4));
+  if (!one) SF_TRY(dev_alloc(h, h->wv_gl, (size_t)2 * nn * 3 * 4));
+  if (!cfg->outermost_linear) SF_TRY(dev_alloc(h, h->wv_dfac, (size_t)2 * nn * 3 * 4));
+  SF_TRY(alloc_sse(h, (h->npix + kWvThreads - 1) / kWvThreads));
+  for (int s = 0; s < 2; ++s) {   // the sub-handles' state: the two halves of the joint vectors
     sf_engine* e = h->wv_sub[s];
-    hipStreamSynchronize(e->stream);
-    for (float** p : {&e->params, &e->grads, &e->m, &e->v, &e->mask}) { hipFree(*p); *p = nullptr; }
     e->params = h->params + s * P0; e->grads = h->grads + s * P0; e->m = h->m + s * P0; e->v = h->v + s * P0;
     e->mask = h->mask + s * P0;
-    e->borrowed_state = true;
     if (h->wv_dfac) e->dfac_out = h->wv_dfac + (size_t)s * nn * 3;
   }
-  hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->grads, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->m, 0, h->P * 4, h->stream);
-  hipMemsetAsync(h->v, 0, h->P * 4, h->stream);
-  *out = h;
+  *out = owner.release();
   return SF_OK;
 } SF_CATCH
 
@@ -1771,7 +1824,7 @@ int sf_set_encoding(sf_handle* h, const float* B_dev) try {
 int sf_destroy(sf_handle* h) try {
   if (!h) return SF_OK;
   DevGuard dev_guard(h->cfg.device);
-  if (h->stream || true) hipStreamSynchronize(h->stream);
+  hipStreamSynchronize(h->stream);
 #ifdef SF_WEXP_STAMP
   if (h->wide) {
     float dbg[64];
@@ -1824,17 +1877,9 @@ int sf_destroy(sf_handle* h) try {
   for (auto& r : h->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
   for (sf_engine* s : h->wv_sub) if (s) sf_destroy(s);
-  if (h->borrowed_state) { h->params = h->grads = h->m = h->v = h->mask = nullptr; }   // the WaveletSiren handle's
-  void* ptrs[] = {h->params, h->grads, h->m, h->v, h->mask, h->wf, h->wf_last, h->wb, h->wb_last, h->l0tab, h->l0img,
-                  h->gh, h->gw, h->Pbuf, h->Dbuf, h->Dlast, h->slab, h->sse_part, h->biasw, h->Abuf,
-                  h->sse_dev, h->scale_dev, h->pad8, h->km_ws, h->wf16, h->wf16_last, h->l0img16, h->lsc,
-                  h->ffB, h->ffimg, h->ffH, h->ffG, h->ffZ, h->fth_p, h->fth_g, h->fth_m, h->fth_v, h->fth_V, h->fth_G,
-                  h->fth_part, h->fth_chunks, h->fth_chunk0, h->wv_pred, h->wv_g, h->wv_gl, h->wv_dfac};
-  for (void* p : ptrs) if (p) hipFree(p);
   if (h->gexec) hipGraphExecDestroy(h->gexec);
   if (h->gstream) { hipStreamSynchronize(h->gstream); hipStreamDestroy(h->gstream); hipEventDestroy(h->gev_in); hipEventDestroy(h->gev_out); }
-  void* gptrs[] = {h->step_tab, h->loss_tab, h->iter_dev};
-  for (void* p : gptrs) if (p) hipFree(p);
+  for (void* p : h->owned) hipFree(p);
   delete h;
   return SF_OK;
 } SF_CATCH
@@ -1898,14 +1943,6 @@ int sf_set_grads(sf_handle* h, const float* p) try {
   if (h) h->fth_fresh = false;
   return copy_in(h, h ? h->grads : nullptr, p);
 } SF_CATCH
-// layer strides of the phase / delta scratch for the handle's current format
-static void set_scratch_strides(sf_engine* h) {
-  const long chunk = h->chunk_px;
-  const int WD = h->WD;
-  h->p_stride = chunk / 32 * (h->s8 ? WD / 32 : WD / 16) * 64 + 37 * 64;
-  h->d_stride = chunk / 32 * (h->d8 ? WD / 32 : WD / 16) * 64 + 37 * 64;
-  h->a_stride = chunk / 32 * (WD / 16) * 64 + 37 * 64;
-}
 // An auto-format handle that receives a mask leaves the 8-bit scratch: fp8 deltas under one scale per chunk underflow in
 // a 90 %-sparse network, and topology updates rank small gradients that phase bytes blur.
 // (the new buffers are allocated BEFORE anything of the handle changes: a failed hipMalloc leaves the handle exactly as it
@@ -1919,17 +1956,16 @@ static int switch_scratch_format(sf_engine* h, int fmt) {
   h->d8 = fmt == 8;
   set_scratch_strides(h);
   u32x4 *newP = nullptr, *newD = nullptr;
-  if (hipMalloc((void**)&newP, (size_t)(h->D - 1) * h->p_stride * 16) != hipSuccess ||
-      hipMalloc((void**)&newD, (size_t)(h->D - 1) * h->d_stride * 16) != hipSuccess) {
-    if (newP) hipFree(newP);
+  if (dev_alloc(h, newP, (size_t)(h->D - 1) * h->p_stride * 16) || dev_alloc(h, newD, (size_t)(h->D - 1) * h->d_stride * 16)) {
+    dev_free(h, newP);
     (void)hipGetLastError();
     h->cfg = cfg0; h->s8 = s8_0; h->d8 = d8_0;
     set_scratch_strides(h);
     return fail(SF_ERR_NOMEM, "hipMalloc failed while moving the scratch to format 16 (the handle keeps its format)");
   }
   if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-  if (h->Pbuf) hipFree(h->Pbuf);
-  if (h->Dbuf) hipFree(h->Dbuf);
+  dev_free(h, h->Pbuf);
+  dev_free(h, h->Dbuf);
   h->Pbuf = newP; h->Dbuf = newD;
   h->images_dirty = true;      // (the backward images carry the fp8 per-layer scales only under format 8)
   return SF_OK;
@@ -2125,15 +2161,15 @@ static int graph_prepare(sf_engine* h, int n) {
     HIPCHK(hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&h->gev_in, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->gev_out, hipEventDisableTiming));
-    HIPCHK(hipMalloc((void**)&h->iter_dev, 16));
+    SF_TRY(dev_alloc(h, h->iter_dev, 16));
     HIPCHK(hipMemset(h->iter_dev, 0, 16));   // [0] replay step index, [2] constant 0 (eager table index)
   }
   if (n > h->tab_cap) {
-    if (h->step_tab) hipFree(h->step_tab);
-    if (h->loss_tab) hipFree(h->loss_tab);
+    dev_free(h, h->step_tab);
+    dev_free(h, h->loss_tab);
     h->step_tab = nullptr; h->loss_tab = nullptr; h->tab_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->step_tab, (size_t)n * 8));
-    HIPCHK(hipMalloc((void**)&h->loss_tab, (size_t)n * 8));
+    SF_TRY(dev_alloc(h, h->step_tab, (size_t)n * 8));
+    SF_TRY(dev_alloc(h, h->loss_tab, (size_t)n * 8));
     h->tab_cap = n;
     if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }   // the graph holds the old table pointers
   }
@@ -2294,7 +2330,7 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
     return fail(SF_ERR_INVALID, "sf_kmeans_fit: need n > 0, 1 <= K < 512, centroids_cap >= K + 1");
   DevGuard dev_guard(h->cfg.device);
   if (!h->km_ws) {
-    if (hipMalloc((void**)&h->km_ws, sizeof(KmWs)) != hipSuccess) return fail(SF_ERR_NOMEM, "hipMalloc failed (k-means workspace)");
+    if (dev_alloc(h, h->km_ws, sizeof(KmWs))) return fail(SF_ERR_NOMEM, "hipMalloc failed (k-means workspace)");
     HIPCHK(hipMemsetAsync(h->km_ws, 0, sizeof(KmWs), h->stream));
   }
   long blocks = (n + 255) / 256;
@@ -2362,31 +2398,22 @@ int sf_feather_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, cons
   a.t2n = (a.n + kFthTile - 1) / kFthTile;
   const long nf = 2 * n * m + 2L * D;
   DevGuard dev_guard(h->cfg.device);
-  float *fp = nullptr, *fg = nullptr, *fm = nullptr, *fv = nullptr, *fV = nullptr, *fG = nullptr, *fpart = nullptr;
-  long* fch = nullptr;
-  int* fc0 = nullptr;
-  bool ok = hipMalloc((void**)&fp, nf * 4) == hipSuccess && hipMalloc((void**)&fg, nf * 4) == hipSuccess &&
-            hipMalloc((void**)&fm, nf * 4) == hipSuccess && hipMalloc((void**)&fv, nf * 4) == hipSuccess &&
-            hipMalloc((void**)&fV, P * 4) == hipSuccess && hipMalloc((void**)&fG, n * n * 4) == hipSuccess &&
-            hipMalloc((void**)&fpart, (size_t)a.nchunks * 4) == hipSuccess &&
-            hipMalloc((void**)&fch, chunks.size() * sizeof(long)) == hipSuccess &&
-            hipMalloc((void**)&fc0, chunk0.size() * sizeof(int)) == hipSuccess;
-  if (!ok) {
-    void* ps[] = {fp, fg, fm, fv, fV, fG, fpart, fch, fc0};
-    for (void* q : ps) if (q) hipFree(q);
+  // (a failure part-way leaves a handle without feather state: h->feather stays false, nothing reads the fth_* fields, and
+  //  what was allocated stays on the owned list until sf_destroy)
+  if (dev_alloc(h, h->fth_p, nf * 4) || dev_alloc(h, h->fth_g, nf * 4) || dev_alloc(h, h->fth_m, nf * 4) ||
+      dev_alloc(h, h->fth_v, nf * 4) || dev_alloc(h, h->fth_V, P * 4) || dev_alloc(h, h->fth_G, n * n * 4) ||
+      dev_alloc(h, h->fth_part, (size_t)a.nchunks * 4) || dev_alloc(h, h->fth_chunks, chunks.size() * sizeof(long)) ||
+      dev_alloc(h, h->fth_chunk0, chunk0.size() * sizeof(int))) {
     (void)hipGetLastError();
     return fail(SF_ERR_NOMEM, "hipMalloc failed (feather state)");
   }
-  h->fth_p = fp; h->fth_g = fg; h->fth_m = fm; h->fth_v = fv; h->fth_V = fV; h->fth_G = fG; h->fth_part = fpart;
-  h->fth_chunks = fch; h->fth_chunk0 = fc0;
-  HIPCHK(hipMemcpy(fch, chunks.data(), chunks.size() * sizeof(long), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(fc0, chunk0.data(), chunk0.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(fp, 0, nf * 4, h->stream)); HIPCHK(hipMemsetAsync(fg, 0, nf * 4, h->stream));
-  HIPCHK(hipMemsetAsync(fm, 0, nf * 4, h->stream)); HIPCHK(hipMemsetAsync(fv, 0, nf * 4, h->stream));
-  HIPCHK(hipMemsetAsync(fV, 0, P * 4, h->stream)); HIPCHK(hipMemsetAsync(fG, 0, n * n * 4, h->stream));
+  HIPCHK(hipMemcpy(h->fth_chunks, chunks.data(), chunks.size() * sizeof(long), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->fth_chunk0, chunk0.data(), chunk0.size() * sizeof(int), hipMemcpyHostToDevice));
+  for (float* p : {h->fth_p, h->fth_g, h->fth_m, h->fth_v}) HIPCHK(hipMemsetAsync(p, 0, nf * 4, h->stream));
+  HIPCHK(hipMemsetAsync(h->fth_V, 0, P * 4, h->stream)); HIPCHK(hipMemsetAsync(h->fth_G, 0, n * n * 4, h->stream));
   HIPCHK(hipMemsetAsync(h->params, 0, h->P * 4, h->stream));   // padded slots stay exactly 0
-  a.fp = fp; a.fg = fg; a.V = fV; a.G = fG; a.W = h->params; a.dW = h->grads;
-  a.chunks = fch; a.seg_chunk0 = fc0; a.part = fpart;
+  a.fp = h->fth_p; a.fg = h->fth_g; a.V = h->fth_V; a.G = h->fth_G; a.W = h->params; a.dW = h->grads;
+  a.chunks = h->fth_chunks; a.seg_chunk0 = h->fth_chunk0; a.part = h->fth_part;
   h->fth = a;
   h->fth_nf = nf;
   h->feather = true;

@@ -107,15 +107,8 @@ int create_wavelet_render(const sf_wavelet_render_config* cfg, sf_handle** out) 
   if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
-  if (cfg->hidden != 32 && cfg->hidden != 64 && cfg->hidden != 128 && cfg->hidden != 256)
-    return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128 or 256 for WaveletSiren (other widths: zero-pad on the host)");
-  if (cfg->depth < 2 || cfg->depth > 16) return fail(SF_ERR_INVALID, "depth must be 2..16");
-  if (cfg->compute_dtype != SF_F16) return fail(SF_ERR_INVALID, "WaveletSiren runs fp16 operands only (compute_dtype SF_F16)");
-  if (cfg->height < 2 || cfg->height % 2)
-    return fail(SF_ERR_INVALID, "WaveletSiren needs an even, square image: the reference's inverse DWT (2n - 4 rows) and its "
-                                "torch.cat of Y with the upsampled Cb / Cr stop matching otherwise");
-  if ((double)cfg->height * (double)cfg->height >= 2147483648.0) return fail(SF_ERR_INVALID, "image too large");
-  if (cfg->chunk_pixels < 0) return fail(SF_ERR_INVALID, "chunk_pixels must be >= 0");
+  SF_TRY(wavelet_check_network(cfg));
+  SF_TRY(wavelet_check_image(cfg->height, cfg->height, cfg->chunk_pixels));
   const int H = cfg->height, n = (H + 5) / 2;
   const int max_rows = cfg->max_rows ? cfg->max_rows : H, max_cols = cfg->max_cols ? cfg->max_cols : H;
   if (max_rows < 1 || max_rows > H || max_cols < 1 || max_cols > H)
@@ -131,55 +124,18 @@ int create_wavelet_render(const sf_wavelet_render_config* cfg, sf_handle** out) 
     return best;
   };
   const int cr = max_span(max_rows), cc = max_span(max_cols);
-  sf_config sc;
-  memset(&sc, 0, sizeof(sc));
-  sc.abi_version = SF_ABI_VERSION; sc.height = cr; sc.width = cc; sc.row_begin = 0; sc.row_end = cr;
-  sc.in_features = 2; sc.out_features = 3; sc.hidden = cfg->hidden; sc.depth = cfg->depth;
-  sc.first_omega_0 = cfg->first_omega_0; sc.hidden_omega_0 = cfg->hidden_omega_0; sc.outermost_linear = cfg->outermost_linear;
-  sc.compute_dtype = SF_F16; sc.device = cfg->device; sc.stream = cfg->stream; sc.chunk_pixels = cfg->chunk_pixels;
-  sf_handle* sub[2] = {nullptr, nullptr};
-  for (int s = 0; s < 2; ++s) {
-    const int rc = create_handle(&sc, &sub[s], true);   // (refuses cr * cc^2 >= 2^40: draw such a picture in bands)
-    if (rc) { if (s) sf_destroy(sub[0]); return rc; }
-  }
+  HandlePtr owner;
+  SF_TRY(wavelet_begin(wavelet_sub_config(cfg, cr, cc), true, H, owner));
   DevGuard dev_guard(cfg->device);
-  sf_engine* h = new sf_engine();
-  h->wavelet = true;
-  h->render = true;
-  h->wv_sub[0] = sub[0]; h->wv_sub[1] = sub[1];
-  h->cfg = sub[0]->cfg;
-  h->cfg.height = H; h->cfg.width = H; h->cfg.row_begin = 0; h->cfg.row_end = H;
-  h->D = 2 * cfg->depth; h->WD = cfg->hidden;
-  h->dw_wg = sub[0]->dw_wg;
-  h->stream = (hipStream_t)cfg->stream;
-  h->npix = (long)H * H;
-  h->n_total = (double)H * (double)H;
-  h->wv_n = n;
-  h->wv_up = (float)(1.0 / ((double)H / (double)n));
+  sf_engine* h = owner.get();
   h->wv_max_rows = max_rows; h->wv_max_cols = max_cols;
-  const int64_t P0 = sub[0]->P;
-  h->P = 2 * P0;
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    return SF_OK;
-  };
-  int rc = SF_OK;
-#define ALLOC(ptr, bytes) if (!rc) rc = alloc((void**)&(ptr), (bytes))
-  ALLOC(h->params, h->P * 4);
-  ALLOC(h->wv_pred, (size_t)2 * cr * cc * 3 * 4);   // the one pair of coefficient buffers
-  ALLOC(h->gh, (size_t)n * 4); ALLOC(h->gw, (size_t)n * 4);   // the caller's FULL coefficient-grid vectors
-#undef ALLOC
-  if (rc) { sf_destroy(h); return rc; }
-  for (int s = 0; s < 2; ++s) {   // the sub-handles' parameters become the two halves of the joint vector
-    sf_engine* e = h->wv_sub[s];
-    hipStreamSynchronize(e->stream);
-    hipFree(e->params);
-    e->params = h->params + s * P0;
-    e->borrowed_state = true;
-  }
+  SF_TRY(dev_alloc(h, h->params, h->P * 4));
+  SF_TRY(dev_alloc(h, h->wv_pred, (size_t)2 * cr * cc * 3 * 4));   // the one pair of coefficient buffers
+  SF_TRY(dev_alloc(h, h->gh, (size_t)n * 4));   // the caller's FULL coefficient-grid vectors
+  SF_TRY(dev_alloc(h, h->gw, (size_t)n * 4));
+  for (int s = 0; s < 2; ++s) h->wv_sub[s]->params = h->params + s * h->wv_sub[s]->P;   // the two halves of the joint vector
   hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
-  *out = h;
+  *out = owner.release();
   return SF_OK;
 }
 

@@ -1,0 +1,47 @@
+"""sf_destroy gives back every byte a handle took, for every creator, on an MI355X.  The cases run in one child process
+(tests/_handle_memory_child.py) under a time limit."""
+import json
+import math
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD = os.path.join(ROOT, "tests", "_handle_memory_child.py")
+
+# What a create .. destroy cycle may leave behind that is not the handle's: the largest shortfall the same child shows
+# against the library of the commit before the owned list (SIREN_FIT_LIB=<that build> python tests/_handle_memory_child.py
+# OUT.json), which freed every buffer by hand - so whatever it leaves is the runtime's own pools, not a leak - plus one
+# allocation granule (hipMalloc hands out device memory in 2 MiB blocks).
+# NOT YET MEASURED: no MI355X run could be had when this test was written, so the figure stands at 0, the least it can
+# be, and the bound is one granule.  A measured figure can only widen it; put it here with the date of the run.
+PARENT_SHORTFALL = 0
+GRANULE = 2 << 20
+SLACK = PARENT_SHORTFALL + GRANULE
+
+CREATORS = ["sf_create", "sf_create+sf_feather_attach", "sf_fourier_create", "sf_wavelet_create", "sf_render_create",
+            "sf_wavelet_render_create"]
+
+
+def test_destroy_returns_what_the_handle_took(tmp_path):
+    """In one fresh process, for each of sf_create, sf_fourier_create, sf_wavelet_create, sf_render_create and
+    sf_wavelet_render_create: create, sf_set_coords, (training handles) one sf_step of two steps with graph replay on,
+    sf_destroy.  The SIREN handle is an auto-format fit of 2^20 pixels that also takes a mask (its scratch moves from
+    format 8 to 16), three more steps (longer step tables, a new graph) and sf_kmeans_fit; a second SIREN handle takes
+    sf_feather_attach.  After every destroy torch.cuda.mem_get_info() reports the free memory read before that handle's
+    create, within SLACK.  The child's first round (the process's first use of each kernel) is not measured."""
+    out = tmp_path / "handle_memory.json"
+    r = subprocess.run([sys.executable, CHILD, str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    assert r.returncode == 0, r.stdout.decode()[-4000:]
+    cases = [c for c in json.load(open(out))["cases"] if c["round"] == 1]
+    for c in cases:
+        print(c)
+    assert [c["creator"] for c in cases] == CREATORS
+    siren = cases[0]
+    assert siren["format_at_create"] == 8 and siren["format_with_mask"] == 16      # the switch did happen
+    for c in cases:
+        assert all(math.isfinite(x) for x in c.get("loss", []) + c.get("loss_masked", [])), c      # the steps did run
+        assert c["shortfall"] <= SLACK, c
