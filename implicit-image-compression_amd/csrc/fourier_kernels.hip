@@ -17,6 +17,8 @@
 //   k_ff_fwd<WD, TRAIN>  encoding computed in registers from the coordinates (phase reduced in revolutions), every layer
 //                        on MFMA with the weight image staged through LDS in k slices, residual, SSE partial,
 //                        dL/dz_out = 2 (s - y) s (1 - s) / (3 H W) (pre-scaled, fp16).  TRAIN spills every ReLU output h_l.
+//                        RENDER (inference only, sf_render / fourier_render.hip): the same chain and sigmoid without
+//                        the target, the residual, dz, the scratch stores and the SSE reduction; fp32 and / or bytes.
 //   k_ff_bwd<WD>         data-gradient chain g_{l-1} = (W_l^T g_l) * [h_{l-1} > 0], l = L-1 .. 1, spilling every g_l.
 //   k_ff_dw<NI, E0>      dW_l = g_l h_{l-1}^T and db_l = sum g_l over the workgroup's pixels into a per-workgroup slab
 //                        (E0: layer 0, whose input, the encoding, is recomputed from the coordinates); k_reduce* of
@@ -49,6 +51,7 @@ struct FfArgs {
   _Float16* Z;                        // [3][cp] dL/dz of the output layer (pre-scaled)
   const float* tgt;                   // target image rows [npix][3] (may be null: prediction only)
   float* pred;                        // [npix][3] or null
+  uint8_t* rgb8;                      // RENDER only: [npix][3] bytes or null (4-byte aligned), min(max((int)(pred * 255), 0), 255)
   float* sse_part;                    // one partial per workgroup
   float gscale;                       // gpre / (3 H W)
 };
@@ -121,11 +124,14 @@ DEV float ff_block_sum(float v, float* sh) {
   return s;
 }
 
-template <int WD, bool TRAIN>
+// the byte tail of the render kernels (siren_render.hip): lane d gathers dword d of the wave's 32-pixel block and stores it
+DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32_t mine, int lane);
+
+template <int WD, bool TRAIN, bool RENDER = false>
 __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
+  static_assert(!(TRAIN && RENDER), "the render form spills nothing");
   constexpr int NT = WD / 32, KS = WD / 16, KSL = ff_ksl(WD);
   extern __shared__ u32x4 lds[];
-  __shared__ float sh_sse[kFfThreads / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 31, hh = lane >> 5;
   const long pl = (long)blockIdx.x * 256 + wave * 32 + m;   // chunk-local pixel of this lane's column
   const long p = a.pix0 + pl;
@@ -194,26 +200,46 @@ __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < KS; ++s) o[0] = OpF16::mfma(lds[s * 64 + lane], fr[s], o[0]);
-  float sse = 0.f;
-  if (hh == 0) {   // rows 0..2 sit in registers 0..2 of the lower lane half
+  if constexpr (RENDER) {
+    // no target, no residual, no dz, no Z store, no workgroup sum: the sigmoid of k_ff_fwd<WD, false>, then bytes
+    uint32_t mine = 0u;   // this lane's pixel: channel t in byte t (the upper lane half holds padded rows: never selected)
+    if (hh == 0) {
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const float z = o[0][t];
-      const float sg = 1.0f / (1.0f + __expf(-z));
-      float dz = 0.f;
-      if (valid) {
-        if (a.pred) a.pred[p * 3 + t] = sg;
-        if (a.tgt) {
-          const float r = sg - a.tgt[p * 3 + t];
-          sse += r * r;
-          dz = 2.0f * r * sg * (1.0f - sg) * a.gscale;
-        }
+      for (int t = 0; t < 3; ++t) {
+        const float z = o[0][t];
+        const float sg = 1.0f / (1.0f + __expf(-z));
+        if (valid && a.pred) a.pred[p * 3 + t] = sg;
+        int q = (int)(sg * 255.0f);   // v_cvt_i32_f32: toward zero
+        q = q < 0 ? 0 : (q > 255 ? 255 : q);
+        mine |= (uint32_t)q << (8 * t);
       }
-      if (TRAIN) a.Z[(uint32_t)t * cp32 + (uint32_t)pl] = (_Float16)dz;
     }
+    // (all 64 lanes: the gather is a cross-lane read.)  pix0 is a multiple of 256 and the wave's first pixel one of 32:
+    // the 96-byte block starts on a dword; pixels >= npix store nothing
+    if (a.rgb8) render_store_block(a.rgb8, a.pix0 + (long)blockIdx.x * 256 + wave * 32, a.npix, 3, mine, lane);
+  } else {
+    __shared__ float sh_sse[kFfThreads / 64];
+    float sse = 0.f;
+    if (hh == 0) {   // rows 0..2 sit in registers 0..2 of the lower lane half
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const float z = o[0][t];
+        const float sg = 1.0f / (1.0f + __expf(-z));
+        float dz = 0.f;
+        if (valid) {
+          if (a.pred) a.pred[p * 3 + t] = sg;
+          if (a.tgt) {
+            const float r = sg - a.tgt[p * 3 + t];
+            sse += r * r;
+            dz = 2.0f * r * sg * (1.0f - sg) * a.gscale;
+          }
+        }
+        if (TRAIN) a.Z[(uint32_t)t * cp32 + (uint32_t)pl] = (_Float16)dz;
+      }
+    }
+    const float s = ff_block_sum(sse, sh_sse);
+    if (threadIdx.x == 0) a.sse_part[blockIdx.x] = s;
   }
-  const float s = ff_block_sum(sse, sh_sse);
-  if (threadIdx.x == 0) a.sse_part[blockIdx.x] = s;
 }
 
 // data-gradient chain, last layer first

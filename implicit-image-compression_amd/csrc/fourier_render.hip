@@ -1,0 +1,76 @@
+// fourier_render.hip — the inference-only path of FourierNet: sf_fourier_render_create, and sf_render on a FourierNet handle
+// (include/siren_fit.h).
+//
+// A decoder needs the picture, not a training step.  The kernel is the RENDER instantiation of k_ff_fwd<WD>
+// (fourier_kernels.hip): the evaluation forward - the encoding in registers, the MFMA chain, the weight staging and the
+// sigmoid are the source lines of k_ff_fwd<WD, false> - without the target fetch, the residual, dz, the Z / H stores, the
+// workgroup sum with its barrier and the SSE partial, and with bytes from the last-layer epilogue.  So sf_render's pred is
+// bit-identical to sf_forward's on a FourierNet training handle (tests/test_gpu_fourier_render.py), and a window or a
+// band is bit-identical to that region of the full picture: pixel (r, c) sees rows[r], cols[c] whatever the grid.
+//
+// Bytes: u8 = min(max((int)(pred * 255.0f), 0), 255), fwd_render_out's formula; the pack / gather / store tail is
+// render_store_block (siren_render.hip): a wave owns 32 consecutive pixels = 96 consecutive bytes on a dword boundary,
+// lane d < 24 stores dword d, only the picture's last ragged dword goes out byte by byte.
+//
+// A render handle (create_fourier(.., render = true), siren_fit.hip) holds the parameters, the weight images, encoding.B
+// and the two coordinate vectors: none of the [D-1][WD][chunk] activation / gradient planes, the slab, gradients, Adam
+// moments, mask or SSE partials of sf_fourier_create.
+//
+// This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit).
+
+namespace {
+
+template <int WD>
+int launch_ff_render_t(sf_engine* h, const FfArgs& a, int n_super) {
+  int rc = set_lds(k_ff_fwd<WD, false, true>, kFfLdsBytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL((k_ff_fwd<WD, false, true>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a);
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
+int launch_ff_render(sf_engine* h, const FfArgs& a, int n_super) {
+  switch (h->WD) {
+    case 32: return launch_ff_render_t<32>(h, a, n_super);
+    case 64: return launch_ff_render_t<64>(h, a, n_super);
+    case 128: return launch_ff_render_t<128>(h, a, n_super);
+    case 256: return launch_ff_render_t<256>(h, a, n_super);
+  }
+  return fail(SF_ERR_INVALID, "unsupported hidden width");
+}
+
+// sf_render on a FourierNet handle (render or training), after its argument checks: chunked as run_pass_fourier
+int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred) {
+  if (!h->have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
+  DevGuard dev_guard(h->cfg.device);
+  int rc = refresh_images(h);
+  if (rc) return rc;
+  const int WD = h->WD, D = h->D, MS = h->MS;
+  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
+  for (long c = 0; c < n_chunks; ++c) {
+    const long pix0 = c * h->chunk_px;   // a multiple of 256: every wave's 32-pixel block starts on a dword of rgb8
+    long px = h->npix - pix0;
+    if (px > h->chunk_px) px = h->chunk_px;
+    const int n_super = (int)((px + kSuper - 1) / kSuper);
+    const double npx = (double)n_super * kSuper;
+    FfArgs fa;
+    memset(&fa, 0, sizeof(fa));   // H / G / Z / tgt / sse_part stay null: the RENDER form touches none of them
+    fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.pix0 = pix0; fa.npix = h->npix; fa.cp = h->chunk_px;
+    fa.Btab = h->ffB; fa.MS = MS; fa.nlin = D; fa.img = h->ffimg; fa.params = h->params;
+    for (int l = 0; l < D; ++l) { fa.img_f[l] = h->ff_img_f[l]; fa.img_b[l] = h->ff_img_b[l]; fa.off_b[l] = h->off_b[l]; }
+    fa.pred = pred; fa.rgb8 = rgb8;
+    Launch L(h, K_FF_RENDER, 2.0 * ((double)MS * WD + (double)(D - 2) * WD * WD + 32.0 * WD) * npx,
+             npx * ((pred ? 12.0 : 0.0) + (rgb8 ? 3.0 : 0.0)));
+    rc = launch_ff_render(h, fa, n_super);
+    L.done();
+    if (rc) return rc;
+  }
+  return SF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_fourier_render_create(const sf_fourier_config* cfg, sf_handle** out) try { return create_fourier(cfg, out, true); } SF_CATCH
+
+}  // extern "C"

@@ -70,12 +70,12 @@ static constexpr float kResScale = 1024.0f;
 //  the hidden layers', so it gets its own line in the per-kernel report)
 // (k_feather_*: the Feathermap update of sf_adam_step on a handle with sf_feather_attach, feather_kernels.hip)
 enum KernelId { K_FWD = 0, K_BWD_HIDDEN, K_BWD_LAST, K_DW_FIRST, K_REDUCE, K_SSE, K_ADAM, K_IMAGES, K_BWD_L1,
-                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_RENDER, K_WV_RENDER, K_COUNT };
+                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_RENDER, K_WV_RENDER, K_FF_RENDER, K_COUNT };
 // (k_wv_*: the image-space composition of a WaveletSiren handle and its adjoint, wavelet_kernels.hip)
 static const char* kKernelNames[K_COUNT] = {"k_fwd",    "k_bwd_hidden", "k_bwd_last", "k_dw_first",
                                             "k_reduce", "k_sse",        "k_adam",     "k_images", "k_bwd_layer1",
                                             "k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat",
-                                            "k_wv_compose", "k_wv_adjoint", "k_wv_inject", "k_render", "k_wv_render"};
+                                            "k_wv_compose", "k_wv_adjoint", "k_wv_inject", "k_render", "k_wv_render", "k_ff_render"};
 
 struct ProfRec {
   int id;
@@ -196,6 +196,8 @@ struct sf_engine {
   float* wv_gl = nullptr;       // two-pass only: [2][n*n][3] fp32 dL/dout of the sub-networks
   float* wv_dfac = nullptr;     // outermost_linear=False only: [2][n*n][3] d sin(om z)/dz of the sub-networks' outputs
   float* dfac_out = nullptr;    // sub-handle, sine output layer: its slice of wv_dfac (FwdArgs::dfac of training forwards)
+  // (a FourierNet render handle, sf_fourier_render_create / fourier_render.hip, sets fourier and render: parameters, ffimg,
+  //  ffB and the two coordinate vectors)
   // render handle (sf_render_create, siren_render.hip): parameters, forward images and coordinates only - no gradient, no
   // optimiser state, no mask, no backward scratch; every training entry point refuses it
   bool render = false;
@@ -1666,8 +1668,11 @@ const char* sf_last_error(void) { return g_err.c_str(); }
 
 int sf_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, false); } SF_CATCH
 
-// FourierNet handle: the same sf_engine, run by fourier_kernels.hip (run_pass_fourier); every other entry point is shared
-int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
+// FourierNet handle: the same sf_engine, run by fourier_kernels.hip (run_pass_fourier); every other entry point is shared.
+// sf_fourier_create and sf_fourier_render_create (fourier_render.hip): one validation, one geometry; a render handle
+// allocates the parameters, the weight images (forward and backward: k_ff_images writes both, a few MB at most),
+// encoding.B and the two coordinate vectors
+static int create_fourier(const sf_fourier_config* cfg, sf_handle** out, bool render) {
   if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
@@ -1689,6 +1694,7 @@ int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
   HandlePtr owner(new sf_engine());
   sf_engine* h = owner.get();
   h->fourier = true;
+  h->render = render;
   memset(&h->cfg, 0, sizeof(h->cfg));
   h->cfg.abi_version = cfg->abi_version;
   h->cfg.height = cfg->height; h->cfg.width = cfg->width; h->cfg.row_begin = 0; h->cfg.row_end = cfg->height;
@@ -1726,11 +1732,20 @@ int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
   h->ff_dw_wgs = 4 * h->dw_wg;
   long slab_row = (long)WD * MS + WD;
   if ((long)WD * WD + WD > slab_row) slab_row = (long)WD * WD + WD;
-  SF_TRY(alloc_train_state(h));
+  if (render) {   // no gradient, moments or mask
+    SF_TRY(dev_alloc(h, h->params, h->P * 4));
+    hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
+  } else {
+    SF_TRY(alloc_train_state(h));
+  }
   SF_TRY(dev_alloc(h, h->ffimg, (size_t)h->ff_img_n * 16));
   SF_TRY(dev_alloc(h, h->ffB, (size_t)cfg->in_features * (MS / 2) * 4));
   SF_TRY(dev_alloc(h, h->gh, (size_t)cfg->height * 4));
   SF_TRY(dev_alloc(h, h->gw, (size_t)cfg->width * 4));
+  if (render) {   // no activation / gradient planes, slab or SSE partials: k_ff_fwd's RENDER form spills nothing
+    *out = owner.release();
+    return SF_OK;
+  }
   SF_TRY(dev_alloc(h, h->ffH, (size_t)(D - 1) * WD * chunk * 2));
   SF_TRY(dev_alloc(h, h->ffG, (size_t)(D - 1) * WD * chunk * 2));
   SF_TRY(dev_alloc(h, h->ffZ, (size_t)4 * chunk * 2));
@@ -1738,7 +1753,8 @@ int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try {
   SF_TRY(alloc_sse(h, chunked_sse_parts(h)));
   *out = owner.release();
   return SF_OK;
-} SF_CATCH
+}
+int sf_fourier_create(const sf_fourier_config* cfg, sf_handle** out) try { return create_fourier(cfg, out, false); } SF_CATCH
 
 // WaveletSiren handle: two SIREN sub-handles (sf_create, format 16) whose state buffers are slices of this handle's joint
 // [LF | HF] vectors, so that sf_state_ptr, sf_get/set_*, sf_adam_step (one k_adam over the joint vector), sf_step and graph
@@ -1814,7 +1830,7 @@ int sf_wavelet_debug(sf_handle* h, int32_t which, const float* in0, const float*
 
 int sf_set_encoding(sf_handle* h, const float* B_dev) try {
   if (!h || !B_dev) return fail(SF_ERR_INVALID, "null argument");
-  if (!h->fourier) return fail(SF_ERR_INVALID, "sf_set_encoding: not a FourierNet handle (sf_fourier_create)");
+  if (!h->fourier) return fail(SF_ERR_INVALID, "sf_set_encoding: not a FourierNet handle (sf_fourier_create / sf_fourier_render_create)");
   DevGuard dev_guard(h->cfg.device);
   HIPCHK(hipMemcpyAsync(h->ffB, B_dev, (size_t)h->cfg.in_features * (h->MS / 2) * 4, hipMemcpyDeviceToDevice, h->stream));
   h->have_B = true;
@@ -2462,3 +2478,4 @@ int sf_debug_throw(int32_t kind) try {
 
 #include "siren_render.hip"
 #include "wavelet_render.hip"
+#include "fourier_render.hip"

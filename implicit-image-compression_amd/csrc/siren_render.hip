@@ -1,4 +1,5 @@
 // siren_render.hip — the inference-only path of the engine: sf_render_create / sf_render (include/siren_fit.h).
+// (sf_render on a FourierNet handle: fourier_render.hip.)
 //
 // A decoder needs the picture, not a training step.  The kernels are the RENDER instantiations of k_fwd<WD> and k_fwd_pipe
 // (siren_kernels.hip): the evaluation forward (no phase stores, so the pipeline's counted waits are those of TRAIN = false)
@@ -36,8 +37,15 @@ DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, 
     mine |= (uint32_t)q << (8 * c);
   }
   if (!a.rgb8) return;
-  const long px0 = a.pix0 + pb * 32;                       // first pixel of this wave's block (a multiple of 32)
-  const long left = a.npix - px0;
+  render_store_block(a.rgb8, a.pix0 + pb * 32, a.npix, nout, mine, lane);   // the block's first pixel: a multiple of 32
+}
+
+// The byte tail every 32-pixel-per-wave render kernel shares (k_fwd / k_fwd_pipe above, k_ff_fwd's RENDER form in
+// fourier_kernels.hip).  mine: the lane's pixel of the block starting at pixel px0, channel c in byte c (lanes 0..31; the
+// upper half is never selected).  Called by all 64 lanes; rgb8 + px0 * nout is dword aligned (the entry point checks the
+// base, 32 | px0).
+DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32_t mine, int lane) {
+  const long left = npix - px0;
   const int nbytes = left >= 32 ? 32 * nout : (left > 0 ? (int)left * nout : 0);   // bytes of the block inside the picture
   uint32_t word = 0u;
 #pragma unroll
@@ -49,7 +57,7 @@ DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, 
     word |= ((v >> (8 * ch)) & 0xffu) << (8 * j);
   }
   if (lane < 8 * nout) {
-    uint8_t* blk = a.rgb8 + px0 * nout;                    // dword aligned: sf_render checks the base, 32 | px0
+    uint8_t* blk = rgb8 + px0 * nout;
     if (4 * lane + 4 <= nbytes) {
       reinterpret_cast<uint32_t*>(blk)[lane] = word;
     } else {
@@ -104,6 +112,8 @@ int launch_render(sf_engine* h, const FwdArgs& a, int n_wg) {
   return fail(SF_ERR_INVALID, "unsupported hidden width");
 }
 
+int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred);   // fourier_render.hip: the RENDER form of k_ff_fwd
+
 }  // namespace
 
 extern "C" {
@@ -115,10 +125,12 @@ int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try {
   if (!rgb8 && !pred) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev and pred_dev are both NULL");
   if (h->wavelet && h->render)
     return fail(SF_ERR_INVALID, "sf_render: a WaveletSiren render handle (sf_wavelet_render_create) is drawn by sf_wavelet_render");
-  if (h->wide || h->fourier || h->wavelet)
-    return fail(SF_ERR_INVALID, "sf_render: built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create)");
+  if (h->wide || h->wavelet)
+    return fail(SF_ERR_INVALID, "sf_render: built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create) "
+                                "and FourierNet handles (sf_fourier_create / sf_fourier_render_create)");
   if (((uintptr_t)rgb8 & 3u) != 0) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev must be 4-byte aligned");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
+  if (h->fourier) return render_fourier(h, rgb8, pred);
   DevGuard dev_guard(h->cfg.device);
   int rc = refresh_images(h);
   if (rc) return rc;

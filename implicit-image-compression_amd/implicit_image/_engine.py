@@ -125,6 +125,7 @@ def load_library():
         "sf_render": [H, C.c_void_p, F],
         "sf_wavelet_render_create": [C.POINTER(sf_wavelet_render_config), C.POINTER(H)],
         "sf_wavelet_render": [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, F],
+        "sf_fourier_render_create": [C.POINTER(sf_fourier_config), C.POINTER(H)],
     }
     for name, args in list(feather.items()) + list(wavelet.items()) + list(render.items()):
         if hasattr(lib, name):
@@ -154,6 +155,11 @@ def has_render(lib) -> bool:
 
 def has_wavelet_render(lib) -> bool:
     return all(hasattr(lib, s) for s in ("sf_wavelet_render_create", "sf_wavelet_render"))
+
+
+def has_fourier_render(lib) -> bool:
+    """sf_fourier_render_create, and with it sf_render on FourierNet handles (csrc/fourier_render.hip)"""
+    return has_render(lib) and hasattr(lib, "sf_fourier_render_create")
 
 
 def exported_symbols() -> Sequence[str]:
@@ -427,7 +433,7 @@ class RenderEngine(SirenEngine):
     gradient, optimiser state, mask or backward scratch.  set_params / get_params / set_coords / render / the profiling
     calls work; every training call raises with the library's message.  set_coords takes any two vectors (a window of a
     grid is a slice of its linspace vectors); hidden 512 / 1024 is refused (no render kernel on the wide path; FourierNet
-    has none either, WaveletSiren has WaveletRenderEngine)."""
+    has FourierRenderEngine, WaveletSiren has WaveletRenderEngine)."""
 
     def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
                  hidden_omega_0: float = 30.0, outermost_linear: bool = True, out_features: int = 3,
@@ -444,20 +450,21 @@ class RenderEngine(SirenEngine):
 
 class FourierEngine(SirenEngine):
     """FourierNet fit on one HIP stream: an sf_handle made by sf_fourier_create (fourier_kernels.hip).  Every method of
-    SirenEngine applies; the frozen encoding goes in through set_encoding before the first pass."""
+    SirenEngine applies (render() included: sf_render's RENDER form of k_ff_fwd); the frozen encoding goes in through
+    set_encoding before the first pass."""
 
     def __init__(self, height: int, width: int, hidden: int, n_linear: int, map_size: int, out_features: int = 3,
                  device: int = 0, chunk_pixels: int = 0, betas=(0.9, 0.999), eps: float = 1e-8):
         self.lib = load_library()
         if not torch.cuda.is_available():
-            raise RuntimeError("FourierEngine needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
+            raise RuntimeError(f"{type(self).__name__} needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
         self.device = torch.device("cuda", device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
         cfg = sf_fourier_config(SF_ABI_VERSION, height, width, 2, out_features, map_size, hidden, n_linear, DTYPES["f16"],
                                 betas[0], betas[1], eps, device, stream, chunk_pixels)
         self.h = C.c_void_p()
-        _check(self.lib.sf_fourier_create(C.byref(cfg), C.byref(self.h)))
+        _check(self._create(cfg))
         n = C.c_int64()
         _check(self.lib.sf_num_params(self.h, C.byref(n)))
         self.num_params = n.value
@@ -469,9 +476,36 @@ class FourierEngine(SirenEngine):
         self._target = None
         self._views = {}
 
+    def _create(self, cfg) -> int:
+        return self.lib.sf_fourier_create(C.byref(cfg), C.byref(self.h))
+
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
         _check(self.lib.sf_set_encoding(self.h, _f32_cuda(B.detach().contiguous(), 2 * (self.map_size // 2)).data_ptr()))
+
+    def render(self, want_u8: bool = True, want_pred: bool = False):
+        if not has_fourier_render(self.lib):
+            raise RuntimeError(f"{_LIB_PATH} has no sf_fourier_render_create entry point (built before the FourierNet render "
+                               "path): rebuild it with `python __graft_entry__.py build`")
+        return super().render(want_u8, want_pred)
+
+
+class FourierRenderEngine(FourierEngine):
+    """Inference-only FourierNet handle (sf_fourier_render_create, csrc/fourier_render.hip): parameters, the fp16 weight
+    images, encoding.B and the two coordinate vectors - none of the activation / gradient planes, slabs, gradient, optimiser
+    state, mask or SSE partials of FourierEngine.  set_params / get_params / set_encoding / set_coords / render / the
+    profiling calls work; every training call raises with the library's message.  set_coords takes any two vectors (a
+    window or a band of a grid is a slice of its linspace vectors)."""
+
+    def __init__(self, height: int, width: int, hidden: int, n_linear: int, map_size: int, out_features: int = 3,
+                 device: int = 0, chunk_pixels: int = 0):
+        super().__init__(height, width, hidden, n_linear, map_size, out_features, device, chunk_pixels)
+
+    def _create(self, cfg) -> int:
+        if not has_fourier_render(self.lib):
+            raise RuntimeError(f"{_LIB_PATH} has no sf_fourier_render_create entry point (built before the FourierNet render "
+                               "path): rebuild it with `python __graft_entry__.py build`")
+        return self.lib.sf_fourier_render_create(C.byref(cfg), C.byref(self.h))
 
 
 class WaveletEngine(SirenEngine):

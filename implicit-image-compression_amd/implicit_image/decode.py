@@ -18,6 +18,10 @@ decode.* keys
   decode.out        the PPM to write (default <decode.dir>/decoded.ppm; binary P6, 8 bit)
   decode.truth      <ppm> or synthetic[:seed]: print loss / PSNR / PSNR_8bit with eval_epoch's formulas
   decode.device     cuda ordinal (default 0)
+  decode.render     auto | kernel | torch (default auto).  auto: what `render_path` answers, below.  torch: the registry
+                    model's own forward for any model.  kernel: a render kernel or a ValueError that says why there is
+                    none for this model and picture (`kernel_available`), raised before the device is touched; this is
+                    how mlp=fourier decodes on its render kernel
 
 SIREN of engine width 32 / 64 / 128 / 256 runs the engine's render kernel (sf_render: bytes straight from the last-layer
 epilogue, no training state on the device), and mlp=wavelet_siren of those widths on an even, square picture runs
@@ -25,6 +29,11 @@ sf_wavelet_render (the render forward of both sub-networks over the coefficient 
 k_wv_render).  A Small_Dense width the engine zero-pads (90 -> 128, 181 -> 256) runs at the padded width.  Everything else -
 mlp=fourier, SIREN 512 / 1024 - builds the registry model, loads the state dict, runs its own forward and converts with the
 same formula in torch.  `render_path` decides and the log names the path that ran.
+
+mlp=fourier of engine width <= 256 has a render kernel too (sf_render on an sf_fourier_render_create handle: the RENDER
+form of k_ff_fwd, `render_fourier`): windows are slices of the coordinate vectors, decode.band_rows applies, and no
+activation plane or full fp32 prediction is allocated.  `render_path` still answers torch for it, so it runs under
+decode.render=kernel only; the bytes of the two paths are the same.
 """
 import json
 import logging
@@ -44,6 +53,8 @@ DECODE_JSON = "decode.json"
 BAND_BYTES = 256 << 20            # one band's byte output stays under this
 ROW_LIMIT = 1 << 40               # a handle decodes (row, col) exactly while rows * width^2 < 2^40 (sf_create)
 KERNEL_WIDTHS = (32, 64, 128, 256)
+RENDER_MODES = ("auto", "kernel", "torch")
+FOURIER_MAPS = (64, 128, 256, 512)
 SHAPE_KEYS = ("mlp.depth", "mlp.hidden_size")
 
 
@@ -230,6 +241,45 @@ def render_path(shape: Cfg, height: Optional[int] = None, width: Optional[int] =
     return "kernel", f"SIREN {wp}x{shape.mlp.depth}{pad}: sf_render"
 
 
+def kernel_available(shape: Cfg, height: Optional[int] = None, width: Optional[int] = None) -> Tuple[bool, str]:
+    """(is there a render kernel for this model and picture, why): what decode.render=kernel asks.  SIREN and WaveletSiren:
+    render_path's answer; FourierNet: the shapes sf_fourier_render_create takes.  No device is touched."""
+    name = shape.mlp.get("name", "siren")
+    if name != "fourier":
+        path, why = render_path(shape, height, width)
+        return path == "kernel", why
+    m = shape.mlp
+    w, wp = engine_width(shape), padded_width(shape)
+    n_linear, ms = int(m.get("depth", 8)) - 1, int(m.get("map_size", 128))
+    if wp not in KERNEL_WIDTHS:
+        return False, f"FourierNet width {w} is above 256: no render kernel"
+    if ms not in FOURIER_MAPS or not 2 <= n_linear <= 12 or int(m.get("input_size", 2)) != 2 or int(m.get("output_size", 3)) != 3:
+        return False, (f"FourierNet with map_size {ms}, {n_linear} Linear layers, input_size {m.get('input_size', 2)}, "
+                       f"output_size {m.get('output_size', 3)}: the engine takes map_size 64 / 128 / 256 / 512, 2..12 layers, 2 -> 3")
+    pad = "" if wp == w else f" (width {w} zero-padded)"
+    return True, f"FourierNet {wp}x{n_linear} map {ms}{pad}: sf_render"
+
+
+def render_mode(dec: Dict[str, str]) -> str:
+    """decode.render of the decode.* keys: auto (default) | kernel | torch"""
+    mode = dec.get("render") or "auto"
+    if mode not in RENDER_MODES:
+        raise ValueError(f"decode.render must be one of {', '.join(RENDER_MODES)}, got {mode!r}")
+    return mode
+
+
+def choose_path(shape: Cfg, mode: str, height: int, width: int) -> Tuple[str, str]:
+    """('kernel' | 'torch', why) for a decode.render mode; kernel without a render kernel raises ValueError"""
+    if mode == "torch":
+        return "torch", "decode.render=torch"
+    if mode == "kernel":
+        ok, why = kernel_available(shape, height, width)
+        if not ok:
+            raise ValueError(f"decode.render=kernel: {why}")
+        return "kernel", why
+    return render_path(shape, height, width)
+
+
 def registry_model(sd, shape: Cfg):
     """the registry model of `shape` with `sd` loaded, on the CPU (names, shapes and the padding rule; no engine yet)"""
     from .models import registry
@@ -284,6 +334,39 @@ def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_r
         cols_d = cols.float().contiguous().to(dev)
         out = torch.empty(h, w, C, dtype=torch.uint8)
         pred = torch.empty(h, w, C) if want_pred else None
+        for r0, r1 in bands:
+            rb = rows[r0:r1].float()
+            if r1 - r0 < nb:
+                rb = torch.cat([rb, rb[-1:].expand(nb - (r1 - r0))])
+            eng.set_coords(rb.contiguous().to(dev), cols_d)
+            u8, p = eng.render(want_u8=True, want_pred=want_pred)
+            out[r0:r1] = u8[:r1 - r0].cpu()
+            if want_pred:
+                pred[r0:r1] = p[:r1 - r0].cpu()
+    finally:
+        eng.close()
+    return out, pred
+
+
+def render_fourier(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
+                   want_pred: bool = False, device: int = 0):
+    """render_kernel for mlp=fourier: uint8 [h, w, 3] on the CPU (and the fp32 prediction when asked) of the grid rows x cols,
+    band by band on ONE FourierNet render handle.  Bands come from plan_bands, whose limits are stricter than the
+    height * width < 2^31 the handle needs; the last, shorter band is padded with its final row and cut after the render."""
+    from ._engine import FourierRenderEngine
+    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
+    h, w = rows.numel(), cols.numel()
+    bands = plan_bands(h, w, 3, band_rows)
+    nb = bands[0][1] - bands[0][0]
+    eng = FourierRenderEngine(nb, w, padded_width(shape), int(m.get("depth", 8)) - 1, int(m.get("map_size", 128)), 3,
+                              device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
+    try:
+        dev = eng.device
+        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(dev))
+        eng.set_encoding(sd["encoding.B"].float().contiguous().to(dev))
+        cols_d = cols.float().contiguous().to(dev)
+        out = torch.empty(h, w, 3, dtype=torch.uint8)
+        pred = torch.empty(h, w, 3) if want_pred else None
         for r0, r1 in bands:
             rb = rows[r0:r1].float()
             if r1 - r0 < nb:
@@ -405,13 +488,16 @@ def load_truth(spec: str, height: int, width: int) -> torch.Tensor:
 
 def decode(argv: Sequence[str]) -> Dict[str, object]:
     dec, rest = split_overrides(argv)
+    mode = render_mode(dec)
     run_dir = dec.get("dir")
     if not run_dir:
         raise ValueError("decode.dir=<run directory written by fit> is required")
     shape = resolve_shape(run_dir, rest)
-    sd, source = load_weights(run_dir, shape, dec.get("source"))
     H = int(dec.get("height") or shape.img.get("height") or 0)
     W = int(dec.get("width") or shape.img.get("width") or 0)
+    if mode == "kernel":                           # no render kernel: refused before a file is read or the device touched
+        choose_path(shape, mode, H, W)
+    sd, source = load_weights(run_dir, shape, dec.get("source"))
     if H < 1 or W < 1:
         raise ValueError("output size unknown: pass decode.height=... decode.width=... (or img.height / img.width)")
     r, c = _span(dec.get("rows"), H, "rows"), _span(dec.get("cols"), W, "cols")
@@ -421,10 +507,14 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
     if name == "wavelet_siren":
         from .models.wavelet_siren import check_image
         check_image(H, W)                          # the "even, square" refusal, before anything touches the device
-    path, why = render_path(shape, H, W)
+    path, why = choose_path(shape, mode, H, W)
     logging.info(f"decode: weights from {source}; {path} path ({why}); {r[1] - r[0]}x{c[1] - c[0]} of a {H}x{W} grid")
     if path == "kernel" and name == "wavelet_siren":
         u8, pred = render_wavelet(sd, shape, H, r, c, int(dec["band_rows"]) if dec.get("band_rows") else None,
+                                  want_pred=bool(truth), device=device)
+    elif path == "kernel" and name == "fourier":
+        rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
+        u8, pred = render_fourier(sd, shape, rows, cols, int(dec["band_rows"]) if dec.get("band_rows") else None,
                                   want_pred=bool(truth), device=device)
     elif path == "kernel":
         rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]

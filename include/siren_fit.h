@@ -89,7 +89,10 @@ typedef struct sf_engine sf_handle;
  * The handle is an ordinary sf_handle: every call below works on it, with these differences
  *   - the flat parameter vector holds the Linear layers only (layers.{2l}.weight, layers.{2l}.bias); encoding.B is frozen
  *     and goes in through sf_set_encoding, once per bind, before the first pass;
- *   - sf_scratch_format reports 16; sf_debug_scratch returns SF_ERR_INVALID; the whole image is fitted (no pixel split). */
+ *   - sf_scratch_format reports 16; sf_debug_scratch returns SF_ERR_INVALID; the whole image is fitted (no pixel split);
+ *   - sf_render draws it (bytes and / or fp32), on a training handle and on the inference-only handle of
+ *     sf_fourier_render_create, which takes this config too (height / width: the picture to render; the Adam fields are
+ *     ignored). */
 typedef struct sf_fourier_config {
   int32_t abi_version;      /* SF_ABI_VERSION                              */
   int32_t height, width;    /* image H, W: the loss mean is over 3*H*W     */
@@ -209,13 +212,20 @@ int sf_forward_backward(sf_handle* h, double* sse_out);
  * the render kernel is not built for the wide path).  On such a handle sf_set_params, sf_get_params, sf_params_changed,
  * sf_set_coords (any two vectors: a window of a grid is a slice of them), sf_num_params, sf_param_offset, sf_state_ptr(0),
  * sf_destroy and the profiling calls work; every training entry point returns SF_ERR_INVALID.
- * sf_render writes rows [row_begin, row_end) of the handle - a render handle or an ordinary SIREN training handle of hidden
- * <= 256 - on the handle's stream, no host synchronisation.  Either output may be NULL, not both:
+ * sf_fourier_render_create (csrc/fourier_render.hip) is the same for FourierNet: sf_fourier_create's config, validation and
+ * geometry; it allocates the parameters, the fp16 weight images, encoding.B and the two coordinate vectors - none of the
+ * [n_linear - 1][hidden][chunk] activation / gradient planes, slabs, gradient, Adam moments, mask or SSE partials.  The same
+ * calls work on it, plus sf_set_encoding; every training entry point returns SF_ERR_INVALID.
+ * sf_render writes rows [row_begin, row_end) of the handle - a SIREN render handle, an ordinary SIREN training handle of
+ * hidden <= 256, a FourierNet render handle or a FourierNet training handle (WaveletSiren: sf_wavelet_render) - on the
+ * handle's stream, no host synchronisation.  A call before sf_set_coords (FourierNet: or before sf_set_encoding) returns
+ * SF_ERR_STATE.  Either output may be NULL, not both:
  *   pred_dev [npix][out_features] fp32, bit-identical to what sf_forward writes for the same parameters and coordinates;
  *   rgb8_dev [npix][out_features] bytes (4-byte aligned), u8 = min(max((int)(pred * 255.0f), 0), 255): the product in fp32,
  *            truncated toward zero (eval_epoch's (pred * 255).int(), train_helper.py:52), clamped to what a file can hold. */
 int sf_render_create(const sf_config* cfg, sf_handle** out);
 int sf_render(sf_handle* h, uint8_t* rgb8_dev, float* pred_dev);
+int sf_fourier_render_create(const sf_fourier_config* cfg, sf_handle** out);
 /* Inference only, WaveletSiren (csrc/wavelet_render.hip).  sf_wavelet_render_create validates what sf_wavelet_create
  * validates and allocates the joint parameter vector [LF | HF], two render sub-handles (parameters as views into it, forward
  * weight images, layer-0 table / image), the two FULL coefficient-grid vectors and ONE pair of fp32 coefficient buffers

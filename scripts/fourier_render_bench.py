@@ -1,0 +1,169 @@
+#!/usr/bin/env python3
+"""Decode time and device memory of the FourierNet render path (sf_render on an sf_fourier_render_create handle) against the
+decode path it replaces, on one MI355X.
+
+    python scripts/fourier_render_bench.py [--sizes 2048 4096] [--calls 30] [--out profiles/fourier_render_bench.json]
+
+Model: conf/mlp/fourier.yaml (hidden 128, depth 8 = 7 Linear layers, map_size 256, map_scale 16).  Per size, HIP-event time
+per call after warm-up, median and p10..p90 over --calls calls, of
+  (a) FourierNet.forward in eval mode (a training handle: sf_forward with pred) + decode.to_u8 on the device - what
+      decode.render_torch runs for mlp=fourier;
+  (b) sf_forward(pred) alone on that training handle, into a buffer allocated once;
+  (c) sf_render to bytes on a render handle.
+The legs alternate in blocks (a b c a b c) inside one process, so all see the same device state.  Device memory held by
+each kind of handle: torch.cuda.mem_get_info before / after creation in a fresh child process per handle.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
+    sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+YAML = dict(depth=8, hidden_size=128, map_size=256, map_scale=16.0)
+N_LINEAR = YAML["depth"] - 1
+
+
+def device_note():
+    note = {"device": torch.cuda.get_device_name(0)}
+    for k, fn in (("clock_mhz", getattr(torch.cuda, "clock_rate", None)), ("power_draw", getattr(torch.cuda, "power_draw", None))):
+        try:
+            note[k] = fn(0)
+        except Exception as e:   # (the management library is optional: say so rather than guess)
+            note[k] = f"unavailable ({type(e).__name__})"
+    return note
+
+
+def timed(fn, n):
+    out = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def stats(ms):
+    s = sorted(ms)
+    return {"median_ms": statistics.median(s), "min_ms": s[0], "max_ms": s[-1], "p10_ms": s[len(s) // 10],
+            "p90_ms": s[(len(s) * 9) // 10], "calls": len(s)}
+
+
+def time_leg(S, calls, warmup):
+    from implicit_image._engine import FourierRenderEngine
+    from implicit_image.data import get_grid
+    from implicit_image.decode import to_u8
+    from implicit_image.models import registry
+    torch.manual_seed(0)
+    model = registry["fourier"](**YAML).cuda().eval()
+    grid = get_grid(S, S).cuda()
+    tr = model.engine(grid)
+    flat = torch.cat([p.data.reshape(-1).float() for p in model._param_list()]).contiguous().cuda()
+    rn = FourierRenderEngine(S, S, YAML["hidden_size"], N_LINEAR, YAML["map_size"])
+    lin = torch.linspace(0, 1, S).cuda()
+    rn.set_coords(lin, lin)
+    rn.set_params(flat)
+    rn.set_encoding(model.encoding.B.data.float())
+    u8 = torch.empty(S, S, 3, dtype=torch.uint8, device="cuda")
+    pred = torch.empty(S, S, 3, device="cuda")
+
+    def model_bytes():
+        with torch.no_grad():
+            return to_u8(model(grid))
+
+    def forward_pred():
+        tr.lib.sf_forward(tr.h, pred.data_ptr(), None)
+
+    def render():
+        rn.lib.sf_render(rn.h, u8.data_ptr(), None)
+
+    legs = {"model_forward_plus_torch_bytes": model_bytes, "sf_forward_pred": forward_pred, "sf_render_bytes": render}
+    for fn in legs.values():
+        timed(fn, warmup)
+    ms = {k: [] for k in legs}
+    half = max(calls // 2, 1)
+    for _ in range(2):                      # a b c a b c: no leg owns the warm (or the throttled) end of the run
+        for k, fn in legs.items():
+            ms[k] += timed(fn, half)
+    same = bool(torch.equal(model_bytes(), u8))
+    rn.profile(True)
+    rn.profile_reset()
+    for _ in range(calls):
+        render()
+    rep = rn.profile_report()
+    rn.profile(False)
+    rn.close()
+    model._unbind()
+    del u8, pred, grid
+    torch.cuda.empty_cache()
+    r = {k: stats(v) for k, v in ms.items()}
+    a, c = r["model_forward_plus_torch_bytes"], r["sf_render_bytes"]
+    r["k_ff_render_ms"] = rep["k_ff_render"]["total_ms"] / max(rep["k_ff_render"]["launches"], 1)
+    r["bytes_identical"] = same
+    r["render_over_model_plus_bytes"] = c["median_ms"] / a["median_ms"]
+    r["render_over_sf_forward"] = c["median_ms"] / r["sf_forward_pred"]["median_ms"]
+    r["render_median_below_p10_of_a"] = bool(c["median_ms"] < a["p10_ms"])
+    return r
+
+
+def mem_child(kind, S):
+    from implicit_image._engine import FourierEngine, FourierRenderEngine
+    torch.cuda.init()
+    torch.zeros(1, device="cuda")
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info()
+    eng = (FourierRenderEngine if kind == "render" else FourierEngine)(S, S, YAML["hidden_size"], N_LINEAR, YAML["map_size"])
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info()
+    eng.close()
+    print(json.dumps({"bytes": int(free0 - free1)}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[2048, 4096])
+    ap.add_argument("--calls", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fourier_render_bench.json"))
+    ap.add_argument("--mem-child", nargs=2, metavar=("KIND", "SIZE"))
+    args = ap.parse_args()
+    if args.mem_child:
+        return mem_child(args.mem_child[0], int(args.mem_child[1]))
+    if args.calls < 20:
+        ap.error("--calls must be at least 20")
+    res = {"what": "FourierNet 128 x 7 Linear, map 256, HIP-event ms per call; (a) FourierNet.forward (training handle) + torch "
+                   "byte conversion, (b) sf_forward(pred) alone on that handle, (c) sf_render to bytes on a render handle; "
+                   "k_ff_render from the render handle's profile; handle memory from torch.cuda.mem_get_info in a fresh "
+                   "process per handle",
+           "before": device_note(), "sizes": {}}
+    for S in args.sizes:
+        r = time_leg(S, args.calls, args.warmup)
+        mem = {}
+        for kind in ("train", "render"):
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--mem-child", kind, str(S)],
+                                 stdout=subprocess.PIPE, timeout=180, check=True).stdout.decode().strip().splitlines()[-1]
+            mem[f"{kind}_handle_bytes"] = json.loads(out)["bytes"]
+        r["memory"] = mem
+        res["sizes"][str(S)] = r
+        print(json.dumps({S: {"a_ms": r["model_forward_plus_torch_bytes"]["median_ms"],
+                              "a_p90_ms": r["model_forward_plus_torch_bytes"]["p90_ms"],
+                              "b_ms": r["sf_forward_pred"]["median_ms"], "c_ms": r["sf_render_bytes"]["median_ms"],
+                              "bytes_identical": r["bytes_identical"], **mem}}),
+              flush=True)
+    res["after"] = device_note()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,145 @@
+"""Host side of the FourierNet render path, no GPU needed: the C ABI's declarations and build list, the decode.render
+key, which models have a render kernel, the padded parameter layout, and the refusal before the device."""
+import os
+import sys
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from implicit_image import _engine  # noqa: E402
+from implicit_image import decode as dec  # noqa: E402
+from implicit_image.config import _wrap  # noqa: E402
+from implicit_image.models import registry  # noqa: E402
+
+CSRC = os.path.join(ROOT, "implicit-image-compression_amd", "csrc")
+
+
+def shape_of(name, hidden, depth=8, density=None, H=64, W=64, **mlp):
+    m = {"name": name, "depth": depth, "hidden_size": hidden}
+    if name == "fourier":
+        m.update({"map_size": 256, "map_scale": 16})
+    else:
+        m.update({"first_omega_0": 50, "hidden_omega_0": 30, "outermost_linear": True})
+    m.update(mlp)
+    return _wrap({"mlp": m, "img": {"height": H, "width": W}, "engine": {}, "small_dense_density": density})
+
+
+def test_symbols_and_build_list():
+    hdr = open(os.path.join(ROOT, "include", "siren_fit.h")).read()
+    assert "int sf_fourier_render_create(const sf_fourier_config* cfg, sf_handle** out);" in hdr
+    assert "int sf_render(sf_handle* h, uint8_t* rgb8_dev, float* pred_dev);" in hdr       # unchanged signature
+    assert _engine.SF_ABI_VERSION == 3
+    assert "sf_fourier_render_create" in _engine.exported_symbols()
+    assert callable(_engine.has_fourier_render)
+    assert hasattr(_engine, "FourierRenderEngine") and issubclass(_engine.FourierRenderEngine, _engine.FourierEngine)
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    prereq = next(l for l in mk.splitlines() if l.startswith("libsiren_fit.so:"))
+    assert "fourier_render.hip" in prereq.split()
+    fit = open(os.path.join(CSRC, "siren_fit.hip")).read()
+    assert fit.rstrip().endswith('#include "fourier_render.hip"')
+    assert '"k_wv_render", "k_ff_render"}' in fit                # appended to the profile name list
+
+
+def test_has_fourier_render_looks_for_the_symbol():
+    class Old:
+        sf_render_create = sf_render = object()
+
+    class New(Old):
+        sf_fourier_render_create = object()
+    assert not _engine.has_fourier_render(Old()) and _engine.has_fourier_render(New())
+    lib_path = os.path.join(CSRC, "libsiren_fit.so")
+    if os.path.exists(lib_path):                                 # a built tree exports it (build() checks the whole header)
+        assert _engine.has_fourier_render(_engine.load_library())
+
+
+def test_decode_render_key_parsing():
+    d, rest = dec.split_overrides(["decode.dir=x", "decode.render=kernel", "mlp=fourier"])
+    assert d == {"dir": "x", "render": "kernel"} and rest == ["mlp=fourier"]
+    assert dec.render_mode({}) == "auto" and dec.render_mode({"render": ""}) == "auto"
+    for v in ("auto", "kernel", "torch"):
+        assert dec.render_mode({"render": v}) == v
+    for bad in ("Kernel", "gpu", "1", "none"):
+        with pytest.raises(ValueError, match="decode.render"):
+            dec.render_mode({"render": bad})
+    with pytest.raises(ValueError, match="decode.render"):      # before the run directory is looked at
+        dec.decode(["decode.dir=/nonexistent", "decode.render=hip"])
+
+
+@pytest.mark.parametrize("hidden", [32, 64, 128, 256])
+def test_kernel_available_for_fourier(hidden):
+    ok, why = dec.kernel_available(shape_of("fourier", hidden))
+    assert ok and why == f"FourierNet {hidden}x7 map 256: sf_render"
+    for ms in (64, 128, 512):
+        assert dec.kernel_available(shape_of("fourier", hidden, map_size=ms))[0]
+
+
+def test_kernel_available_small_dense_and_refusals():
+    sd = shape_of("fourier", 128, density=0.5)
+    assert dec.engine_width(sd) == 90 and dec.padded_width(sd) == 128
+    assert registry["fourier"](depth=8, hidden_size=128, map_size=256, small_dense_density=0.5)._engine_width == 128
+    ok, why = dec.kernel_available(sd)
+    assert ok and "128x7" in why and "zero-padded" in why
+    for shape, word in ((shape_of("siren", 512), "wide path"), (shape_of("siren", 1024), "wide path"),
+                        (shape_of("fourier", 512), "above 256"), (shape_of("fourier", 128, map_size=96), "map_size"),
+                        (shape_of("fourier", 128, depth=2), "Linear layers"),
+                        (shape_of("wavelet_siren", 128, H=64, W=32), "even, square")):
+        ok, why = dec.kernel_available(shape)
+        assert not ok and word in why, (ok, why)
+    ok, why = dec.kernel_available(shape_of("wavelet_siren", 128), 64, 32)      # the picture to draw, not the fitted one
+    assert not ok and "even, square" in why
+    # what has a kernel under auto has one under kernel
+    assert dec.kernel_available(shape_of("siren", 64)) == (True, "SIREN 64x8: sf_render")
+    assert dec.kernel_available(shape_of("wavelet_siren", 128))[0]
+
+
+def test_render_path_is_unchanged_for_fourier():
+    """the default path does not change here: auto is render_path, and render_path still answers torch for mlp=fourier"""
+    for hidden in (32, 64, 128, 256):
+        assert dec.render_path(shape_of("fourier", hidden)) == ("torch", "mlp=fourier has no render kernel")
+        assert dec.choose_path(shape_of("fourier", hidden), "auto", 64, 64)[0] == "torch"
+    assert dec.choose_path(shape_of("fourier", 128), "kernel", 64, 64)[0] == "kernel"
+    assert dec.choose_path(shape_of("siren", 64), "torch", 64, 64)[0] == "torch"
+    assert dec.choose_path(shape_of("siren", 64), "auto", 64, 64) == dec.render_path(shape_of("siren", 64), 64, 64)
+
+
+def test_padded_fourier_parameters_land_in_the_engine_layout():
+    """engine_flat_params for a Small_Dense FourierNet (90 -> 128): every logical weight sits at row * padded_in + col of
+    its layer, biases behind the weights, zeros in the padding"""
+    torch.manual_seed(1)
+    m = registry["fourier"](depth=4, hidden_size=128, map_size=64, small_dense_density=0.5)
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    shape = shape_of("fourier", 128, depth=4, density=0.5, map_size=64)
+    P = 128 * 64 + 128 + 128 * 128 + 128 + 3 * 128 + 3
+    flat = dec.engine_flat_params(sd, shape, P)
+    assert flat.numel() == P
+    W0 = flat[:128 * 64].reshape(128, 64)
+    assert torch.equal(W0[:90], sd["layers.0.weight"]) and not W0[90:].any()
+    b0 = flat[128 * 64:128 * 64 + 128]
+    assert torch.equal(b0[:90], sd["layers.0.bias"]) and not b0[90:].any()
+    off = 128 * 64 + 128
+    W1 = flat[off:off + 128 * 128].reshape(128, 128)
+    assert torch.equal(W1[:90, :90], sd["layers.2.weight"]) and not W1[90:].any() and not W1[:, 90:].any()
+    off += 128 * 128 + 128
+    W2 = flat[off:off + 3 * 128].reshape(3, 128)
+    assert torch.equal(W2[:, :90], sd["layers.4.weight"]) and not W2[:, 90:].any()
+    assert torch.equal(flat[off + 3 * 128:], sd["layers.4.bias"])
+
+
+def test_kernel_mode_refuses_a_model_without_a_kernel_before_the_device(tmp_path):
+    """decode.render=kernel on SIREN 512 (and on a non-square WaveletSiren picture): ValueError with the reason.  The run
+    directory holds no weights and this machine may have no GPU - neither is reached."""
+    over = [f"decode.dir={tmp_path}", "decode.render=kernel", "img.height=64", "img.width=64"]
+    with pytest.raises(ValueError, match="decode.render=kernel: SIREN width 512 is on the wide path"):
+        dec.decode(over + ["mlp.hidden_size=512", "mlp.depth=4"])
+    with pytest.raises(ValueError, match="decode.render=kernel: .*even, square"):
+        dec.decode(over + ["mlp=wavelet_siren", "mlp.hidden_size=64", "mlp.depth=4", "decode.width=32"])
+    # with weights present the answer is the same, and still not the engine's "needs a gfx950 GPU"
+    torch.manual_seed(0)
+    torch.save({"state_dict": registry["siren"](depth=3, hidden_size=512).state_dict()}, tmp_path / "model.pth")
+    with pytest.raises(ValueError, match="wide path"):
+        dec.decode(over + ["mlp.hidden_size=512", "mlp.depth=3"])
