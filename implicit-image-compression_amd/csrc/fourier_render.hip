@@ -20,49 +20,20 @@
 
 namespace {
 
-template <int WD>
-int launch_ff_render_t(sf_engine* h, const FfArgs& a, int n_super) {
-  int rc = set_lds(k_ff_fwd<WD, false, true>, kFfLdsBytes);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_ff_fwd<WD, false, true>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-int launch_ff_render(sf_engine* h, const FfArgs& a, int n_super) {
-  switch (h->WD) {
-    case 32: return launch_ff_render_t<32>(h, a, n_super);
-    case 64: return launch_ff_render_t<64>(h, a, n_super);
-    case 128: return launch_ff_render_t<128>(h, a, n_super);
-    case 256: return launch_ff_render_t<256>(h, a, n_super);
-  }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
-}
-
 // sf_render on a FourierNet handle (render or training), after its argument checks: chunked as run_pass_fourier
 int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred) {
   if (!h->have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
   DevGuard dev_guard(h->cfg.device);
-  int rc = refresh_images(h);
-  if (rc) return rc;
+  SF_TRY(refresh_images(h));
   const int WD = h->WD, D = h->D, MS = h->MS;
-  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
-  for (long c = 0; c < n_chunks; ++c) {
-    const long pix0 = c * h->chunk_px;   // a multiple of 256: every wave's 32-pixel block starts on a dword of rgb8
-    long px = h->npix - pix0;
-    if (px > h->chunk_px) px = h->chunk_px;
-    const int n_super = (int)((px + kSuper - 1) / kSuper);
-    const double npx = (double)n_super * kSuper;
-    FfArgs fa;
-    memset(&fa, 0, sizeof(fa));   // H / G / Z / tgt / sse_part stay null: the RENDER form touches none of them
-    fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.pix0 = pix0; fa.npix = h->npix; fa.cp = h->chunk_px;
-    fa.Btab = h->ffB; fa.MS = MS; fa.nlin = D; fa.img = h->ffimg; fa.params = h->params;
-    for (int l = 0; l < D; ++l) { fa.img_f[l] = h->ff_img_f[l]; fa.img_b[l] = h->ff_img_b[l]; fa.off_b[l] = h->off_b[l]; }
+  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
+    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+    const double npx = (double)k.n_super * kSuper;
+    FfArgs fa = ff_args_base(h, k.pix0);
     fa.pred = pred; fa.rgb8 = rgb8;
     Launch L(h, K_FF_RENDER, 2.0 * ((double)MS * WD + (double)(D - 2) * WD * WD + 32.0 * WD) * npx,
              npx * ((pred ? 12.0 : 0.0) + (rgb8 ? 3.0 : 0.0)));
-    rc = launch_ff_render(h, fa, n_super);
-    L.done();
-    if (rc) return rc;
+    SF_TRY(launch_ff(h, fa, k.n_super, kFfRender));
   }
   return SF_OK;
 }

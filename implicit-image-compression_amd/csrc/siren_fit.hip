@@ -34,6 +34,122 @@
 
 using namespace sf;
 
+// hidden 256, 16-bit scratch (k_bwd): 8 waves (two per SIMD), all weight rows in registers, 5 x 32 KiB ring = 160 KiB: 96 KiB
+// in flight; the P0 variant needs more registers and keeps the 4-wave / 4-slot form
+#ifdef SF_EXPERIMENT_P0W8
+constexpr int kBwd16P0WC = 4;
+#else
+constexpr int kBwd16P0WC = 2;
+#endif
+#ifdef SF_EXPERIMENT_NB4
+constexpr int kBwd16NB = 4;
+#else
+constexpr int kBwd16NB = 5;
+#endif
+constexpr int kBwd16P0NB = 4;
+#ifndef SF_BWD8H_PARK
+#define SF_BWD8H_PARK 4
+#endif
+
+// Every template kernel of the library, in the order the code object holds them.  The compiler emits instantiations in the
+// order of their first use, so this list - their first use - keeps the device code byte for byte what it was measured as,
+// however the host code below is arranged: a host-only change leaves the sha256 of the device object alone.  A kernel the
+// launch code asks for and this list lacks is still built (behind these); one listed and never launched is built too: today
+// that is k_bwd8<32, 256, 1, 8, true, false, OpF16, 8, 0, 0, true>, the 8-slot last-layer form the 4-slot rings replaced.
+// It can go, with its line here, in a change that is allowed to alter device code.
+#define SF_K(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+[[maybe_unused]] static const void* const kKernelOrder[] = {
+    SF_K(k_fwd_pipe16<true, SF_FWD_PD>), SF_K(k_fwd_pipe16<false, SF_FWD_PD>),
+    SF_K(k_fwd_pipe<OpF16, true, true, SF_FWD_PD, false>), SF_K(k_fwd_pipe<OpF16, true, false, SF_FWD_PD, false>),
+    SF_K(k_fwd_pipe<OpF16, false, false, SF_FWD_PD, false>), SF_K(k_fwd_pipe<OpBF16, true, false, SF_FWD_PD, false>),
+    SF_K(k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, false>), SF_K(k_bwd<32, 32, 1, 1, true, true, OpF16, 8>),
+    SF_K(k_bwd<32, 32, 1, 1, true, true, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, true, false, OpF16, 8>),
+    SF_K(k_bwd<32, 32, 1, 1, true, false, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, false, true, OpF16, 8>),
+    SF_K(k_bwd<32, 32, 1, 1, false, true, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, false, false, OpF16, 8>),
+    SF_K(k_bwd<32, 32, 1, 1, false, false, OpBF16, 8>), SF_K(k_bwd<32, 64, 1, 2, true, true, OpF16, 8>),
+    SF_K(k_bwd<32, 64, 1, 2, true, true, OpBF16, 8>), SF_K(k_bwd<32, 64, 1, 2, true, false, OpF16, 8>),
+    SF_K(k_bwd<32, 64, 1, 2, true, false, OpBF16, 8>), SF_K(k_bwd<64, 64, 2, 1, false, true, OpF16, 8>),
+    SF_K(k_bwd<64, 64, 2, 1, false, true, OpBF16, 8>), SF_K(k_bwd<64, 64, 2, 1, false, false, OpF16, 8>),
+    SF_K(k_bwd<64, 64, 2, 1, false, false, OpBF16, 8>), SF_K(k_bwd<32, 128, 1, 4, true, true, OpF16, 8>),
+    SF_K(k_bwd<32, 128, 1, 4, true, true, OpBF16, 8>), SF_K(k_bwd<32, 128, 1, 4, true, false, OpF16, 8>),
+    SF_K(k_bwd<32, 128, 1, 4, true, false, OpBF16, 8>), SF_K(k_bwd<128, 128, 2, 2, false, true, OpF16, 8>),
+    SF_K(k_bwd<128, 128, 2, 2, false, true, OpBF16, 8>), SF_K(k_bwd<128, 128, 2, 2, false, false, OpF16, 8>),
+    SF_K(k_bwd<128, 128, 2, 2, false, false, OpBF16, 8>), SF_K(k_bwd<32, 256, 1, 8, true, true, OpF16, 8>),
+    SF_K(k_bwd<32, 256, 1, 8, true, true, OpBF16, 8>), SF_K(k_bwd<32, 256, 1, 8, true, false, OpF16, 8>),
+    SF_K(k_bwd<32, 256, 1, 8, true, false, OpBF16, 8>),
+    SF_K(k_bwd<256, 256, 2, kBwd16P0WC, false, true, OpF16, kBwd16P0NB>),
+    SF_K(k_bwd<256, 256, 2, kBwd16P0WC, false, true, OpBF16, kBwd16P0NB>),
+    SF_K(k_bwd<256, 256, 2, 4, false, false, OpF16, kBwd16NB>),
+    SF_K(k_bwd<256, 256, 2, 4, false, false, OpBF16, kBwd16NB>),
+    SF_K(k_bwd8<32, 32, 1, 1, true, true, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 32, 1, 1, true, false, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 32, 1, 1, false, true, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 32, 1, 1, false, false, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 64, 1, 2, true, true, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 64, 1, 2, true, false, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<64, 64, 2, 1, false, true, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<64, 64, 2, 1, false, false, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 128, 1, 4, true, true, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 128, 1, 4, true, false, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<128, 128, 2, 2, false, true, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<128, 128, 2, 2, false, false, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 256, 1, 8, true, true, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 8, 0, 0, false>),
+    SF_K(k_bwd8<256, 256, 2, 4, false, true, OpF16, 5, 4, 0, false>),
+    SF_K(k_bwd8<256, 256, 2, 4, false, false, OpF16, 5, 2, 3, false>), SF_K(k_bwd8h<SF_BWD8H_PARK>),
+    SF_K(k_bwd8<32, 32, 1, 1, true, true, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 32, 1, 1, true, false, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 32, 1, 1, false, true, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 32, 1, 1, false, false, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 64, 1, 2, true, true, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 64, 1, 2, true, false, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<64, 64, 2, 1, false, true, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<64, 64, 2, 1, false, false, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 128, 1, 4, true, true, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 128, 1, 4, true, false, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<128, 128, 2, 2, false, true, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<128, 128, 2, 2, false, false, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 256, 1, 8, true, true, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 8, 0, 0, true>),
+    SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 4, 0, 4, true>),
+    SF_K(k_bwd8<256, 256, 2, 4, false, true, OpF16, 6, 5, 0, true>),
+    SF_K(k_bwd8<256, 256, 2, 4, false, false, OpF16, 5, 2, 4, true>), SF_K(k_dw0_8<32, OpF16, 8>),
+    SF_K(k_dw0_8<64, OpF16, 8>), SF_K(k_dw0_8<128, OpF16, 8>), SF_K(k_dw0_8<256, OpF16, 4>), SF_K(k_dw0<32, OpF16>),
+    SF_K(k_dw0<32, OpBF16>), SF_K(k_dw0<64, OpF16>), SF_K(k_dw0<64, OpBF16>), SF_K(k_dw0<128, OpF16>),
+    SF_K(k_dw0<128, OpBF16>), SF_K(k_fwd<32, OpF16, true, true, false>), SF_K(k_fwd<32, OpF16, true, false, false>),
+    SF_K(k_fwd<32, OpF16, false, false, false>), SF_K(k_fwd<32, OpBF16, true, false, false>),
+    SF_K(k_fwd<32, OpBF16, false, false, false>), SF_K(k_fwd<64, OpF16, true, true, false>),
+    SF_K(k_fwd<64, OpF16, true, false, false>), SF_K(k_fwd<64, OpF16, false, false, false>),
+    SF_K(k_fwd<64, OpBF16, true, false, false>), SF_K(k_fwd<64, OpBF16, false, false, false>),
+    SF_K(k_fwd<128, OpF16, true, true, false>), SF_K(k_fwd<128, OpF16, true, false, false>),
+    SF_K(k_fwd<128, OpF16, false, false, false>), SF_K(k_fwd<128, OpBF16, true, false, false>),
+    SF_K(k_fwd<128, OpBF16, false, false, false>), SF_K(k_fwd<256, OpF16, true, true, false>),
+    SF_K(k_fwd<256, OpF16, true, false, false>), SF_K(k_fwd<256, OpF16, false, false, false>),
+    SF_K(k_fwd<256, OpBF16, true, false, false>), SF_K(k_fwd<256, OpBF16, false, false, false>),
+    SF_K(k_wlayer0<OpF16, true>), SF_K(k_wlayer0<OpF16, false>), SF_K(k_wlayer0<OpBF16, false>), SF_K(k_wgemm3<32>),
+    SF_K(k_wgemm3<64>), SF_K(k_wgemm2<0, OpF16, true, 4, false, false>), SF_K(k_wgemm2<0, OpF16, false, 4, false, false>),
+    SF_K(k_wgemm2<0, OpF16, true, 8, false, false>), SF_K(k_wgemm2<0, OpF16, false, 8, false, false>),
+    SF_K(k_wgemm2<0, OpBF16, false, 8, false, false>), SF_K(k_wgemm<1, OpF16>), SF_K(k_wgemm<1, OpBF16>),
+    SF_K(k_wdw<32, OpF16, false>), SF_K(k_wdw<32, OpBF16, false>), SF_K(k_wdw<256, OpF16, true>),
+    SF_K(k_wdw<256, OpF16, false>), SF_K(k_wdw<256, OpBF16, false>), SF_K(k_wgemm2<2, OpF16, true, 8, false, true>),
+    SF_K(k_wgemm2<2, OpF16, true, 8, true, true>), SF_K(k_wgemm2<2, OpF16, true, 4, false, false>),
+    SF_K(k_wgemm2<2, OpF16, false, 4, false, false>), SF_K(k_wgemm2<2, OpF16, true, 8, false, false>),
+    SF_K(k_wgemm2<2, OpF16, false, 8, false, false>), SF_K(k_wgemm2<2, OpBF16, false, 8, false, false>),
+    SF_K(k_dw0<256, OpF16>), SF_K(k_dw0<256, OpBF16>), SF_K(k_ff_fwd<32, false, false>), SF_K(k_ff_fwd<32, true, false>),
+    SF_K(k_ff_bwd<32>), SF_K(k_ff_fwd<64, false, false>), SF_K(k_ff_fwd<64, true, false>), SF_K(k_ff_bwd<64>),
+    SF_K(k_ff_fwd<128, false, false>), SF_K(k_ff_fwd<128, true, false>), SF_K(k_ff_bwd<128>),
+    SF_K(k_ff_fwd<256, false, false>), SF_K(k_ff_fwd<256, true, false>), SF_K(k_ff_bwd<256>), SF_K(k_ff_dw<1, true>),
+    SF_K(k_ff_dw<2, true>), SF_K(k_ff_dw<4, true>), SF_K(k_ff_dw<1, false>), SF_K(k_ff_dw<2, false>),
+    SF_K(k_ff_dw<4, false>), SF_K(k_fwd_pipe<OpF16, false, false, SF_FWD_PD, true>),
+    SF_K(k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, true>), SF_K(k_fwd<32, OpF16, false, false, true>),
+    SF_K(k_fwd<32, OpBF16, false, false, true>), SF_K(k_fwd<64, OpF16, false, false, true>),
+    SF_K(k_fwd<64, OpBF16, false, false, true>), SF_K(k_fwd<128, OpF16, false, false, true>),
+    SF_K(k_fwd<128, OpBF16, false, false, true>), SF_K(k_fwd<256, OpF16, false, false, true>),
+    SF_K(k_fwd<256, OpBF16, false, false, true>), SF_K(k_ff_fwd<32, false, true>), SF_K(k_ff_fwd<64, false, true>),
+    SF_K(k_ff_fwd<128, false, true>), SF_K(k_ff_fwd<256, false, true>),
+};
+#undef SF_K
+
 static thread_local std::string g_err;
 
 // sf_config carries the Adam betas as floats; torch.optim.Adam computes 1 - beta and beta^t on the Python double
@@ -209,30 +325,32 @@ struct sf_engine {
 
 namespace {
 
-struct Launch {  // RAII-less helper: brackets a kernel launch with events when profiling
+// Timing scope of one profile record: while it lives, what the handle launches lies between two events (when profiling).
+// Several kernels under one scope are one record (k_fp8_norms + k_fp8_links + k_images + k_images16 under K_IMAGES).
+struct Launch {
   sf_engine* h;
-  int id;
+  bool on;
   ProfRec r;
-  Launch(sf_engine* h_, int id_, double flops, double bytes) : h(h_), id(id_) {
-    if (h->prof) {
-      r.id = id;
-      auto get = [&](hipEvent_t* e) {
-        if (!h->ev_pool.empty()) { *e = h->ev_pool.back(); h->ev_pool.pop_back(); }
-        else hipEventCreate(e);
-      };
-      get(&r.e0);
-      get(&r.e1);
-      hipEventRecord(r.e0, h->stream);
-      h->prof_flops[id] += flops;   // totals; sf_profile_get reports the per-launch average
-      h->prof_bytes[id] += bytes;
-    }
+  Launch(sf_engine* h_, int id, double flops, double bytes) : h(h_), on(h_->prof) {
+    if (!on) return;
+    r.id = id;
+    auto get = [&](hipEvent_t* e) {
+      if (!h->ev_pool.empty()) { *e = h->ev_pool.back(); h->ev_pool.pop_back(); }
+      else hipEventCreate(e);
+    };
+    get(&r.e0);
+    get(&r.e1);
+    hipEventRecord(r.e0, h->stream);
+    h->prof_flops[id] += flops;   // totals; sf_profile_get reports the per-launch average
+    h->prof_bytes[id] += bytes;
   }
-  void done() {
-    if (h->prof) {
-      hipEventRecord(r.e1, h->stream);
-      h->recs.push_back(r);
-    }
+  ~Launch() {
+    if (!on) return;
+    hipEventRecord(r.e1, h->stream);
+    try { h->recs.push_back(r); } catch (...) {}   // out of memory: this record is lost, its two events with it
   }
+  Launch(const Launch&) = delete;
+  Launch& operator=(const Launch&) = delete;
 };
 
 int prof_flush(sf_engine* h) {
@@ -267,42 +385,105 @@ int set_lds(K kernel, size_t bytes) {
   return SF_OK;
 }
 
-size_t fwd_lds_bytes(int WD) { return (size_t)FwdGeom(WD).PIECES * 1024 + (size_t)WD * 16 + 64; }
-
-template <int WD>
-int launch_fwd_t(sf_engine* h, const FwdArgs& a, int n_super, bool train) {
-  const size_t lds = fwd_lds_bytes(WD);
-  const bool f16 = h->cfg.compute_dtype == SF_F16;
-#define SF_FWD(OP, TR)                                                   \
-  do {                                                                   \
-    int rc = set_lds(k_fwd<WD, OP, TR>, lds);                            \
-    if (rc) return rc;                                                   \
-    hipLaunchKernelGGL((k_fwd<WD, OP, TR>), dim3(n_super), dim3(512), lds, h->stream, a); \
-  } while (0)
-  if (f16 && train && h->s8) {
-    int rc = set_lds(k_fwd<WD, OpF16, true, true>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_fwd<WD, OpF16, true, true>), dim3(n_super), dim3(512), lds, h->stream, a);
-  } else if (f16) {
-    if (train) SF_FWD(OpF16, true); else SF_FWD(OpF16, false);
-  } else {
-    if (train) SF_FWD(OpBF16, true); else SF_FWD(OpBF16, false);
-  }
-#undef SF_FWD
+// The one kernel launch of the library: the kernel's dynamic-LDS limit (set_lds), the launch on the handle's stream, the
+// launch error.  The kernel is named once per call site, so the limit cannot go to one kernel and the launch to another.
+template <typename... P, typename... A>
+int launch(sf_engine* h, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A&... args) {
+  if (lds) SF_TRY(set_lds(kernel, lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, static_cast<P>(args)...);
   HIPCHK(hipGetLastError());
   return SF_OK;
 }
 
+// The one hidden-width dispatch (width <= 256), the one operand-type dispatch and a run-time bool as a type: f receives
+// std::integral_constant<int, WD>, an OpF16 / OpBF16 tag or std::true_type / std::false_type, so one generic lambda stands for
+// the kernel instantiations of all of them.
+template <typename F>
+int with_width(const sf_engine* h, F&& f) {
+  using std::integral_constant;
+  const int w = h->WD;
+  return w == 32    ? f(integral_constant<int, 32>{})
+         : w == 64  ? f(integral_constant<int, 64>{})
+         : w == 128 ? f(integral_constant<int, 128>{})
+         : w == 256 ? f(integral_constant<int, 256>{})
+                    : fail(SF_ERR_INVALID, "unsupported hidden width");
+}
+template <typename F>
+int with_op(const sf_engine* h, F&& f) { return h->cfg.compute_dtype == SF_F16 ? f(OpF16{}) : f(OpBF16{}); }
+template <typename F>
+int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F>
+int with_bool(bool b0, bool b1, F&& f) {
+  return with_bool(b0, [&](auto x) { return with_bool(b1, [&](auto y) { return f(x, y); }); });
+}
+
+// ---- what the argument structs of the chunked kernels share ---------------------------------------------------------
+// One chunk of a handle's local pixels: first pixel, length, 256-pixel groups, 32-pixel blocks
+struct Chunk {
+  long pix0, px;
+  int n_super;
+  long n_pb;
+};
+long n_chunks(long npix, long chunk_px) { return (npix + chunk_px - 1) / chunk_px; }
+Chunk chunk_at(long c, long npix, long chunk_px) {
+  Chunk k;
+  k.pix0 = c * chunk_px;   // a multiple of 256: every wave's 32-pixel block starts on a dword of a byte picture
+  k.px = std::min(chunk_px, npix - k.pix0);
+  k.n_super = (int)((k.px + kSuper - 1) / kSuper);
+  k.n_pb = (long)k.n_super * kWavesFwd;
+  return k;
+}
+// pixel geometry of the chunk at local pixel pix0, for any argument struct that decodes (row, col) from a pixel index
+template <typename Args>
+void fill_pixels(const sf_engine* h, long pix0, Args& a) {
+  a.pix0 = pix0; a.npix = h->npix; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin;
+  a.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
+}
+// ... and for the backward structs, which also re-derive the coordinates from (row, col)
+template <typename Args>
+void fill_grid(const sf_engine* h, long pix0, Args& a) {
+  fill_pixels(h, pix0, a);
+  a.inv_hm1 = h->cfg.height > 1 ? 1.0f / (float)(h->cfg.height - 1) : 0.f;
+  a.inv_wm1 = h->cfg.width > 1 ? 1.0f / (float)(h->cfg.width - 1) : 0.f;
+}
+// dL/dout = residual * gscale: the mean over all values of the image, under the power-of-two pre-scale
+float gscale(const sf_engine* h) { return (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total)); }
+
+// the fixed-order sum of a pass's SSE partials into the handle's scalar (and this step's slot of the loss table)
+int launch_sse_reduce(sf_engine* h, long n_parts) {
+  Launch L(h, K_SSE, 0, (double)n_parts * 4);
+  return launch(h, k_sse_reduce, 1, 256, 0, h->sse_part, n_parts, h->sse_dev, h->replay ? h->loss_tab : h->loss_dst,
+                h->replay ? h->iter_dev : h->iter_dev + 2);
+}
+// per-layer fp8 delta scales (link[16] | inv[16] | norms in h->lsc), rebuilt with the weight images
+int launch_fp8_scales(sf_engine* h) {
+  Fp8ScaleArgs f;
+  memset(&f, 0, sizeof(f));
+  f.params = h->params; f.depth = h->D; f.WD = h->WD; f.out_features = h->cfg.out_features;
+  for (int l = 0; l < h->D; ++l) f.off_w[l] = h->off_w[l];
+  f.om_first = h->cfg.first_omega_0; f.om_hidden = h->cfg.hidden_omega_0; f.link = h->lsc; f.inv = h->lsc + 16;
+  f.nrm = reinterpret_cast<double*>(h->lsc + 32);
+  SF_TRY(launch(h, k_fp8_norms, h->D - 1, 1024, 0, f));
+  return launch(h, k_fp8_links, 1, 64, 0, f);
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------
+size_t fwd_lds_bytes(int WD) { return (size_t)FwdGeom(WD).PIECES * 1024 + (size_t)WD * 16 + 64; }
+// k_fwd_pipe / k_fwd_pipe16: weight image halves + layer-0 image + SSE partials
+size_t fwd_pipe_lds_bytes() { return (size_t)FwdGeom(256).PIECES * 1024 + (size_t)(256 / 32) * 1024 + 64; }
+
+// hidden = 256, depth >= 3 run the persistent pipeline kernel (k_fwd_pipe): one workgroup per CU walks the chunk
+bool fwd_is_pipe(const sf_engine* h) {
+  static const bool no_pipe = getenv("SIREN_FIT_FWD_PIPE") && atoi(getenv("SIREN_FIT_FWD_PIPE")) == 0;   // A/B knob
+  return h->WD == 256 && h->D >= 3 && !no_pipe && !h->wide;
+}
+// forward workgroups of a chunk with n_super 256-pixel groups (= the chunk's SSE partials)
+int fwd_grid(const sf_engine* h, int n_super) { return fwd_is_pipe(h) && n_super > h->dw_wg ? h->dw_wg : n_super; }
+
 // hidden = 256, depth >= 3: the hand-scheduled software pipeline over all layers (k_fwd_pipe)
 int launch_fwd_pipe(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
-  const size_t lds = (size_t)FwdGeom(256).PIECES * 1024 + (size_t)(256 / 32) * 1024 + 64;   // weight image halves + layer-0 image + SSE partials
+  const size_t lds = fwd_pipe_lds_bytes();
   const bool f16 = h->cfg.compute_dtype == SF_F16;
-#define SF_FWDP(OP, TR, S8)                                              \
-  do {                                                                   \
-    int rc = set_lds(k_fwd_pipe<OP, TR, S8>, lds);                       \
-    if (rc) return rc;                                                   \
-    hipLaunchKernelGGL((k_fwd_pipe<OP, TR, S8>), dim3(n_wg), dim3(512), lds, h->stream, a); \
-  } while (0)
   // The 16x16x32 re-tile of the pipeline (siren_fwd16.hip) is built, parity-tested and measured 3 % SLOWER than k_fwd_pipe on
   // the same box (+9 % clock, +11 % cycles: DESIGN.md section 4c): it runs only when SIREN_FIT_FWD16=1 asks for it.
   static const bool use16 = getenv("SIREN_FIT_FWD16") && atoi(getenv("SIREN_FIT_FWD16")) == 1;
@@ -310,191 +491,156 @@ int launch_fwd_pipe(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
     FwdArgs b = a;
     b.wf = reinterpret_cast<const u32x4*>(h->wf16); b.wf_last = reinterpret_cast<const u32x4*>(h->wf16_last);
     b.l0img = reinterpret_cast<const u32x4*>(h->l0img16);
-    if (train) {
-      int rc = set_lds(k_fwd_pipe16<true>, lds);
-      if (rc) return rc;
-      hipLaunchKernelGGL((k_fwd_pipe16<true>), dim3(n_wg), dim3(512), lds, h->stream, b);
-    } else {
-      int rc = set_lds(k_fwd_pipe16<false>, lds);
-      if (rc) return rc;
-      hipLaunchKernelGGL((k_fwd_pipe16<false>), dim3(n_wg), dim3(512), lds, h->stream, b);
-    }
-  } else if (f16 && train && h->s8) SF_FWDP(OpF16, true, true);
-  else if (f16 && train) SF_FWDP(OpF16, true, false);
-  else if (f16) SF_FWDP(OpF16, false, false);
-  else if (train) SF_FWDP(OpBF16, true, false);
-  else SF_FWDP(OpBF16, false, false);
-#undef SF_FWDP
-  HIPCHK(hipGetLastError());
-  return SF_OK;
+    return train ? launch(h, k_fwd_pipe16<true>, n_wg, 512, lds, b) : launch(h, k_fwd_pipe16<false>, n_wg, 512, lds, b);
+  }
+  if (f16 && train && h->s8) return launch(h, k_fwd_pipe<OpF16, true, true>, n_wg, 512, lds, a);
+  return with_op(h, [&](auto op) {
+    using OP = decltype(op);
+    return train ? launch(h, k_fwd_pipe<OP, true, false>, n_wg, 512, lds, a) : launch(h, k_fwd_pipe<OP, false, false>, n_wg, 512, lds, a);
+  });
+}
+// the forward of a chunk on n_wg workgroups (fwd_grid): phase bytes (fp16 operands only), training or evaluation form
+int launch_fwd(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
+  if (fwd_is_pipe(h)) return launch_fwd_pipe(h, a, n_wg, train);
+  return with_width(h, [&](auto wd) {
+    constexpr int WD = decltype(wd)::value;
+    const size_t lds = fwd_lds_bytes(WD);
+    if (h->cfg.compute_dtype == SF_F16 && train && h->s8) return launch(h, k_fwd<WD, OpF16, true, true>, n_wg, 512, lds, a);
+    return with_op(h, [&](auto op) {
+      using OP = decltype(op);
+      return train ? launch(h, k_fwd<WD, OP, true>, n_wg, 512, lds, a) : launch(h, k_fwd<WD, OP, false>, n_wg, 512, lds, a);
+    });
+  });
 }
 
-template <int JW, int IW, int WR, int WC, bool LAST, bool P0, typename OP, int NB>
-int launch_bwd_k(sf_engine* h, const BwdLayerArgs& a, int n_wg) {
+// what every forward of a SIREN handle (width <= 256) is given for the chunk that starts at local pixel pix0: coordinates,
+// geometry, weight images and scales; the caller adds its outputs (scratch, target, prediction, partials)
+FwdArgs fwd_args_base(const sf_engine* h, long pix0, int n_super) {
+  FwdArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fill_pixels(h, pix0, fa);
+  fa.gh = h->gh; fa.gw = h->gw; fa.depth = h->D;
+  fa.l0tab = h->l0tab; fa.l0img = reinterpret_cast<const u32x4*>(h->l0img);
+  fa.wf = reinterpret_cast<const u32x4*>(h->wf);
+  fa.wf_last = reinterpret_cast<const u32x4*>(h->wf_last);
+  fa.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  fa.sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
+  fa.sc_last = 1.0f / h->wscale;
+  if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
+  fa.nout = h->cfg.out_features;
+  fa.n_super = n_super;
+  return fa;
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------
+// The one tile table of the fused layer backward, <JW, IW, WR, WC> of (width, last): the last layer's out_features (<= 3,
+// padded to 32) rows against one wave per 32 inputs; a hidden layer's WD x WD block on 1, 2, 4 or 8 waves.
+template <int WD, bool LAST>
+struct BwdTile {
+  static constexpr int JW = LAST ? 32 : WD, IW = WD;
+  static constexpr int WR = LAST || WD == 32 ? 1 : 2, WC = LAST ? WD / 32 : WD == 32 ? 1 : WD / 64;
+};
+
+// 16-bit scratch (k_bwd).  Ring depths are chosen to fill the 160 KiB of LDS.
+template <int WD, bool LAST, bool P0, typename OP>
+int launch_bwd16(sf_engine* h, const BwdLayerArgs& a, int n_wg) {
+  using T = BwdTile<WD, LAST>;
+  constexpr bool H256 = WD == 256 && !LAST;
+  constexpr int WC = H256 && P0 ? kBwd16P0WC : T::WC, NB = H256 ? (P0 ? kBwd16P0NB : kBwd16NB) : 8;   // (the constants at the kernel list)
   // NB-slot block ring + (when the stationary weight rows do not fit in registers) their parked part
   // + (P0) the layer-0 table
-  constexpr int NWV = WR * WC, XT = (IW / 32) / NWV, KSX = LAST ? 1 : JW / 16;
+  constexpr int JW = T::JW, IW = T::IW, WR = T::WR, NWV = WR * WC, XT = (IW / 32) / NWV, KSX = LAST ? 1 : JW / 16;
   constexpr int WSP = (XT * KSX > 24) ? (P0 ? 3 : 4) : 0;
   const size_t lds = (size_t)NB * (JW / 16 + IW / 16) * 1024 + (size_t)NWV * XT * WSP * 1024 + (P0 ? (size_t)IW * 16 : 0);
-  int rc = set_lds(k_bwd<JW, IW, WR, WC, LAST, P0, OP, NB>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_bwd<JW, IW, WR, WC, LAST, P0, OP, NB>), dim3(n_wg), dim3(WR * WC * 64), lds, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return SF_OK;
+  return launch(h, k_bwd<JW, IW, WR, WC, LAST, P0, OP, NB>, n_wg, NWV * 64, lds, a);
 }
-template <int JW, int IW, int WR, int WC, bool LAST, bool P0, int NB>
-int launch_bwd_tp(sf_engine* h, const BwdLayerArgs& a, int n_wg) {
-  return h->cfg.compute_dtype == SF_F16 ? launch_bwd_k<JW, IW, WR, WC, LAST, P0, OpF16, NB>(h, a, n_wg)
-                                        : launch_bwd_k<JW, IW, WR, WC, LAST, P0, OpBF16, NB>(h, a, n_wg);
-}
-template <int JW, int IW, int WR, int WC, bool LAST, int NB>
-int launch_bwd_t(sf_engine* h, const BwdLayerArgs& a, int n_wg, bool p0) {
-  return p0 ? launch_bwd_tp<JW, IW, WR, WC, LAST, true, NB>(h, a, n_wg) : launch_bwd_tp<JW, IW, WR, WC, LAST, false, NB>(h, a, n_wg);
-}
-
 // fused backward of one layer: last = the out_features(<=3, padded to 32)-row layer; p0 = its input layer is
-// layer 0, whose phases are re-derived from the coordinates.  Ring depths are chosen to fill the 160 KiB of LDS.
+// layer 0, whose phases are re-derived from the coordinates.
 int launch_bwd(sf_engine* h, bool last, bool p0, const BwdLayerArgs& a, int n_wg) {
-  switch (h->WD) {
-    case 32: return last ? launch_bwd_t<32, 32, 1, 1, true, 8>(h, a, n_wg, p0) : launch_bwd_t<32, 32, 1, 1, false, 8>(h, a, n_wg, p0);
-    case 64: return last ? launch_bwd_t<32, 64, 1, 2, true, 8>(h, a, n_wg, p0) : launch_bwd_t<64, 64, 2, 1, false, 8>(h, a, n_wg, p0);
-    case 128: return last ? launch_bwd_t<32, 128, 1, 4, true, 8>(h, a, n_wg, p0) : launch_bwd_t<128, 128, 2, 2, false, 8>(h, a, n_wg, p0);
-    case 256:
-      if (last) return launch_bwd_t<32, 256, 1, 8, true, 8>(h, a, n_wg, p0);
-      // 8 waves (two per SIMD), all weight rows in registers, 5 x 32 KiB ring = 160 KiB: 96 KiB in flight;
-      // the P0 variant needs more registers and keeps the 4-wave / 4-slot form
-#ifdef SF_EXPERIMENT_P0W8
-      return p0 ? launch_bwd_tp<256, 256, 2, 4, false, true, 4>(h, a, n_wg)
-#else
-      return p0 ? launch_bwd_tp<256, 256, 2, 2, false, true, 4>(h, a, n_wg)
-#endif
-#ifdef SF_EXPERIMENT_NB4
-                : launch_bwd_tp<256, 256, 2, 4, false, false, 4>(h, a, n_wg);
-#else
-                : launch_bwd_tp<256, 256, 2, 4, false, false, 5>(h, a, n_wg);
-#endif
-  }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
+  return with_width(h, [&](auto wd) {
+    return with_bool(last, p0, [&](auto l, auto p) {
+      return with_op(h, [&](auto op) { return launch_bwd16<decltype(wd)::value, decltype(l)::value, decltype(p)::value, decltype(op)>(h, a, n_wg); });
+    });
+  });
 }
 
-// 8-bit scratch path (siren_s8.hip): fp16 operands only
-template <int JW, int IW, int WR, int WC, bool LAST, bool P0, int NB, int PARK = 0, int NBP = 0, bool D8 = true>
-int launch_bwd8_k(sf_engine* h, const Bwd8Args& a, int n_wg) {
-  constexpr size_t lds = bwd8_lds_bytes<JW, IW, WR * WC, LAST, P0, NB, PARK, NBP, D8>();
-  static_assert(lds <= 160 * 1024, "k_bwd8 LDS budget");
-  int rc = set_lds(k_bwd8<JW, IW, WR, WC, LAST, P0, OpF16, NB, PARK, NBP, D8>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_bwd8<JW, IW, WR, WC, LAST, P0, OpF16, NB, PARK, NBP, D8>), dim3(n_wg), dim3(WR * WC * 64), lds, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-template <int JW, int IW, int WR, int WC, bool LAST, int NB, int NB0>
-int launch_bwd8_t(sf_engine* h, const Bwd8Args& a, int n_wg, bool p0) {
-  return p0 ? launch_bwd8_k<JW, IW, WR, WC, LAST, true, NB0>(h, a, n_wg) : launch_bwd8_k<JW, IW, WR, WC, LAST, false, NB>(h, a, n_wg);
-}
-// scratch_format 12: phase bytes, 16-bit float deltas (k_bwd8<.., D8 = false>).  Ring depths / parked W^T k-steps of the
-// 256-wide 8-wave forms are the combinations hipcc allocates WITHOUT a scratch reload inside the block loop (a reload's
-// vmcnt(0) also waits for every LDS-DMA in flight, i.e. it serialises the loop on HBM latency): DESIGN.md section 4.
-template <int JW, int IW, int WR, int WC, bool LAST, int NB>
-int launch_bwd12_t(sf_engine* h, const Bwd8Args& a, int n_wg, bool p0) {
-  return p0 ? launch_bwd8_k<JW, IW, WR, WC, LAST, true, NB, 0, 0, false>(h, a, n_wg)
-            : launch_bwd8_k<JW, IW, WR, WC, LAST, false, NB, 0, 0, false>(h, a, n_wg);
-}
-int launch_bwd12(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
-  switch (h->WD) {
-    case 32: return last ? launch_bwd12_t<32, 32, 1, 1, true, 8>(h, a, n_wg, p0) : launch_bwd12_t<32, 32, 1, 1, false, 8>(h, a, n_wg, p0);
-    case 64: return last ? launch_bwd12_t<32, 64, 1, 2, true, 8>(h, a, n_wg, p0) : launch_bwd12_t<64, 64, 2, 1, false, 8>(h, a, n_wg, p0);
-    case 128: return last ? launch_bwd12_t<32, 128, 1, 4, true, 8>(h, a, n_wg, p0) : launch_bwd12_t<128, 128, 2, 2, false, 8>(h, a, n_wg, p0);
-    case 256:
-      if (last) return launch_bwd12_t<32, 256, 1, 8, true, 8>(h, a, n_wg, p0);
-      // hidden: 5 delta slots (80 KiB) + 3 phase slots (24) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
-      // layer 1 (P0, no phase ring): 5 delta slots + sines + 4 parked k-steps + layer-0 table = 148 KiB
-      if (p0) return launch_bwd8_k<256, 256, 2, 4, false, true, 5, 4, 0, false>(h, a, n_wg);
-      return launch_bwd8_k<256, 256, 2, 4, false, false, 5, 2, 3, false>(h, a, n_wg);
+// 8-bit scratch path (siren_s8.hip, k_bwd8): fp16 operands only.  D8: fp8 deltas (scratch_format 8); else phase bytes with
+// 16-bit float deltas (scratch_format 12).  Ring depth NB, parked W^T k-steps PARK and phase-ring depth NBP:
+struct Ring8 { int NB, PARK, NBP; };
+template <int WD, bool LAST, bool P0, bool D8>
+constexpr Ring8 bwd8_ring() {
+  if (WD != 256) return {8, 0, 0};
+  // Ring depths / parked W^T k-steps of the 256-wide 8-wave forms are the combinations hipcc allocates WITHOUT a scratch
+  // reload inside the block loop (a reload's vmcnt(0) also waits for every LDS-DMA in flight, i.e. it serialises the loop on
+  // HBM latency): DESIGN.md section 4.
+  if (!D8) {
+    if (LAST) return {8, 0, 0};
+    // hidden: 5 delta slots (80 KiB) + 3 phase slots (24) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
+    // layer 1 (P0, no phase ring): 5 delta slots + sines + 4 parked k-steps + layer-0 table = 148 KiB
+    return P0 ? Ring8{5, 4, 0} : Ring8{5, 2, 3};
   }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
+  // 8 waves (two per SIMD); the ring slots hold the fp8 bytes (8 KiB per block): phase W converts in registers, phase X
+  // reads a 16-bit image expanded once per block (2 x 16 KiB).
+  // last layer: 3 MFMAs per block, bound by the latency of a step once its delta output is bytes - rings of 4 slots
+  // (72 KiB) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
+  // HBM-bound at 5.4 TB/s and the shallower rings cost 0.3 ms: format 12 keeps one workgroup per CU)
+  if (LAST) return P0 ? Ring8{8, 0, 0} : Ring8{4, 0, 4};
+  // hidden: 5 delta slots (40 KiB) + 4 phase slots (32) + X16 (32) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
+  //         (the round-2 kernel: launch_bwd8 runs k_bwd8h instead unless SIREN_FIT_BWD8H=0)
+  // layer 1 (P0, no phase ring): 6 delta slots (48) + X16 (32) + sines (32) + 5 parked (40) + layer-0 table = 156 KiB
+  return P0 ? Ring8{6, 5, 0} : Ring8{5, 2, 4};
 }
-#ifndef SF_BWD8H_PARK
-#define SF_BWD8H_PARK 4
-#endif
+template <int WD, bool LAST, bool P0, bool D8>
+int launch_bwd8_k(sf_engine* h, const Bwd8Args& a, int n_wg) {
+  using T = BwdTile<WD, LAST>;
+  constexpr int NB = bwd8_ring<WD, LAST, P0, D8>().NB, PARK = bwd8_ring<WD, LAST, P0, D8>().PARK, NBP = bwd8_ring<WD, LAST, P0, D8>().NBP;
+  constexpr size_t lds = bwd8_lds_bytes<T::JW, T::IW, T::WR * T::WC, LAST, P0, NB, PARK, NBP, D8>();
+  static_assert(lds <= 160 * 1024, "k_bwd8 LDS budget");
+  return launch(h, k_bwd8<T::JW, T::IW, T::WR, T::WC, LAST, P0, OpF16, NB, PARK, NBP, D8>, n_wg, T::WR * T::WC * 64, lds, a);
+}
 int launch_bwd8h(sf_engine* h, const Bwd8Args& a, int n_wg) {
   constexpr size_t lds = bwd8h_lds_bytes<SF_BWD8H_PARK>();
   static_assert(lds <= 160 * 1024, "k_bwd8h LDS budget");
-  int rc = set_lds(k_bwd8h<SF_BWD8H_PARK>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_bwd8h<SF_BWD8H_PARK>), dim3(n_wg), dim3(512), lds, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return SF_OK;
+  return launch(h, k_bwd8h<SF_BWD8H_PARK>, n_wg, 512, lds, a);
 }
 int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
-  if (!h->d8) return launch_bwd12(h, last, p0, a, n_wg);
-  switch (h->WD) {
-    case 32: return last ? launch_bwd8_t<32, 32, 1, 1, true, 8, 8>(h, a, n_wg, p0) : launch_bwd8_t<32, 32, 1, 1, false, 8, 8>(h, a, n_wg, p0);
-    case 64: return last ? launch_bwd8_t<32, 64, 1, 2, true, 8, 8>(h, a, n_wg, p0) : launch_bwd8_t<64, 64, 2, 1, false, 8, 8>(h, a, n_wg, p0);
-    case 128: return last ? launch_bwd8_t<32, 128, 1, 4, true, 8, 8>(h, a, n_wg, p0) : launch_bwd8_t<128, 128, 2, 2, false, 8, 8>(h, a, n_wg, p0);
-    case 256:
-      // 8 waves (two per SIMD); the ring slots hold the fp8 bytes (8 KiB per block): phase W converts in registers, phase X
-      // reads a 16-bit image expanded once per block (2 x 16 KiB).  Ring depth / parked W^T k-steps: combinations hipcc
-      // allocates without a scratch reload inside the block loop (as for format 12).
-      // hidden: 5 delta slots (40 KiB) + 4 phase slots (32) + X16 (32) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
-      // layer 1 (P0, no phase ring): 6 delta slots (48) + X16 (32) + sines (32) + 5 parked (40) + layer-0 table = 156 KiB
-      // last layer: 3 MFMAs per block, bound by the latency of a step once its delta output is bytes - rings of 4 slots
-      // (72 KiB) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
-      // HBM-bound at 5.4 TB/s and the shallower rings cost 0.3 ms: format 12 keeps one workgroup per CU)
-      if (last) return p0 ? launch_bwd8_t<32, 256, 1, 8, true, 8, 8>(h, a, n_wg, p0)
-                          : launch_bwd8_k<32, 256, 1, 8, true, false, 4, 0, 4>(h, a, n_wg);
-      if (p0) return launch_bwd8_k<256, 256, 2, 4, false, true, 6, 5, 0>(h, a, n_wg);
-      {   // hidden layers: the slot-per-MFMA pipeline (siren_s8h.hip); SIREN_FIT_BWD8H=0 selects the round-2 kernel (A/B knob)
-        static const bool old_form = getenv("SIREN_FIT_BWD8H") && atoi(getenv("SIREN_FIT_BWD8H")) == 0;
-        if (!old_form) return launch_bwd8h(h, a, n_wg);
-      }
-      return launch_bwd8_k<256, 256, 2, 4, false, false, 5, 2, 4>(h, a, n_wg);
+  if (h->d8 && h->WD == 256 && !last && !p0) {
+    // hidden layers: the slot-per-MFMA pipeline (siren_s8h.hip); SIREN_FIT_BWD8H=0 selects the round-2 kernel (A/B knob)
+    static const bool old_form = getenv("SIREN_FIT_BWD8H") && atoi(getenv("SIREN_FIT_BWD8H")) == 0;
+    if (!old_form) return launch_bwd8h(h, a, n_wg);
   }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
-}
-// two MFMAs per wave and block behind a workgroup barrier: bound by the latency of a step.  At width 256 a 4-slot ring
-// (64.5 KiB) lets two workgroups share a CU.
-constexpr int dw0_8_ring(int JW) { return JW == 256 ? 4 : 8; }
-template <int JW>
-int launch_dw0_8_t(sf_engine* h, const Dw0Args& a, int n_wg) {
-  constexpr int NB = dw0_8_ring(JW);
-  const size_t lds = (size_t)(NB * (JW / 32) + 2 * (JW / 16)) * 1024 + 512;   // byte ring + two fp16 images + coordinate table
-  int rc = set_lds(k_dw0_8<JW, OpF16, NB>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_dw0_8<JW, OpF16, NB>), dim3(n_wg), dim3(JW * 2), lds, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-int launch_dw_first8(sf_engine* h, const Dw0Args& a, int n_wg) {
-  switch (h->WD) {
-    case 32: return launch_dw0_8_t<32>(h, a, n_wg);
-    case 64: return launch_dw0_8_t<64>(h, a, n_wg);
-    case 128: return launch_dw0_8_t<128>(h, a, n_wg);
-    case 256: return launch_dw0_8_t<256>(h, a, n_wg);
-  }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
+  return with_width(h, [&](auto wd) {
+    return with_bool(last, p0, [&](auto l, auto p) {
+      return with_bool(h->d8, [&](auto d) { return launch_bwd8_k<decltype(wd)::value, decltype(l)::value, decltype(p)::value, decltype(d)::value>(h, a, n_wg); });
+    });
+  });
 }
 
 // weight gradient of layer 0 (no data gradient needed): contraction of delta_0 with the coordinates
 template <int JW>
-int launch_dw0_t(sf_engine* h, const Dw0Args& a, int n_wg) {
+int launch_dw0(sf_engine* h, const Dw0Args& a, int n_wg) {
   const size_t lds = (size_t)8 * (JW / 16) * 1024 + 512;   // ring + coordinate table
-  const bool f16 = h->cfg.compute_dtype == SF_F16;
-  int rc = f16 ? set_lds(k_dw0<JW, OpF16>, lds) : set_lds(k_dw0<JW, OpBF16>, lds);
-  if (rc) return rc;
-  if (f16) hipLaunchKernelGGL((k_dw0<JW, OpF16>), dim3(n_wg), dim3(JW * 2), lds, h->stream, a);
-  else hipLaunchKernelGGL((k_dw0<JW, OpBF16>), dim3(n_wg), dim3(JW * 2), lds, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return SF_OK;
+  return with_op(h, [&](auto op) { return launch(h, k_dw0<JW, decltype(op)>, n_wg, JW * 2, lds, a); });
+}
+// ... from fp8 deltas: two MFMAs per wave and block behind a workgroup barrier: bound by the latency of a step.  At width
+// 256 a 4-slot ring (64.5 KiB) lets two workgroups share a CU.
+constexpr int dw0_8_ring(int JW) { return JW == 256 ? 4 : 8; }
+template <int JW>
+int launch_dw0_8(sf_engine* h, const Dw0Args& a, int n_wg) {
+  constexpr int NB = dw0_8_ring(JW);
+  const size_t lds = (size_t)(NB * (JW / 32) + 2 * (JW / 16)) * 1024 + 512;   // byte ring + two fp16 images + coordinate table
+  return launch(h, k_dw0_8<JW, OpF16, NB>, n_wg, JW * 2, lds, a);
+}
+template <int JW>
+int launch_dw_first_t(sf_engine* h, const Dw0Args& a, int n_wg) {
+  return h->d8 ? launch_dw0_8<JW>(h, a, n_wg) : launch_dw0<JW>(h, a, n_wg);
 }
 int launch_dw_first(sf_engine* h, const Dw0Args& a, int n_wg) {
-  switch (h->WD) {
-    case 32: return launch_dw0_t<32>(h, a, n_wg);
-    case 64: return launch_dw0_t<64>(h, a, n_wg);
-    case 128: return launch_dw0_t<128>(h, a, n_wg);
-    case 256: return launch_dw0_t<256>(h, a, n_wg);
-  }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
+  return with_width(h, [&](auto wd) { return launch_dw_first_t<decltype(wd)::value>(h, a, n_wg); });
+}
+// the fixed-order slab reduction of one layer's weight and bias gradient into the flat gradient
+int launch_reduce(sf_engine* h, const ReduceArgs& ra) {
+  return launch(h, k_reduce, (ra.rows_out * ra.cols_out + ra.rows_out + 15) / 16, 256, 0, ra);
 }
 
 // rms the chunk's residual is scaled to before the deltas become fp8 (k_bwd8<LAST>: G = 2^floor(log2(target / rms))).
@@ -506,48 +652,7 @@ float fp8_target() {
   static const float t = getenv("SIREN_FIT_FP8_TARGET") ? (float)atof(getenv("SIREN_FIT_FP8_TARGET")) : kFp8Target;
   return t;
 }
-// hidden = 256, depth >= 3 run the persistent pipeline kernel (k_fwd_pipe): one workgroup per CU walks the chunk
-bool fwd_is_pipe(const sf_engine* h) {
-  static const bool no_pipe = getenv("SIREN_FIT_FWD_PIPE") && atoi(getenv("SIREN_FIT_FWD_PIPE")) == 0;   // A/B knob
-  return h->WD == 256 && h->D >= 3 && !no_pipe && !h->wide;
-}
-// forward workgroups of a chunk with n_super 256-pixel groups (= the chunk's SSE partials)
-int fwd_grid(const sf_engine* h, int n_super) { return fwd_is_pipe(h) && n_super > h->dw_wg ? h->dw_wg : n_super; }
 
-// what every forward of a SIREN handle (width <= 256) is given for the chunk that starts at local pixel pix0: coordinates,
-// geometry, weight images and scales; the caller adds its outputs (scratch, target, prediction, partials)
-FwdArgs fwd_args_base(const sf_engine* h, long pix0, int n_super) {
-  FwdArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.row_begin = h->cfg.row_begin;
-  fa.pix0 = pix0; fa.npix = h->npix; fa.depth = h->D;
-  fa.l0tab = h->l0tab; fa.l0img = reinterpret_cast<const u32x4*>(h->l0img);
-  fa.wf = reinterpret_cast<const u32x4*>(h->wf);
-  fa.wf_last = reinterpret_cast<const u32x4*>(h->wf_last);
-  fa.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
-  fa.sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
-  fa.sc_last = 1.0f / h->wscale;
-  if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
-  fa.nout = h->cfg.out_features;
-  fa.n_super = n_super;
-  fa.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
-  return fa;
-}
-
-int launch_fwd(sf_engine* h, const FwdArgs& a, int n_super, bool train) {
-  switch (h->WD) {
-    case 32: return launch_fwd_t<32>(h, a, n_super, train);
-    case 64: return launch_fwd_t<64>(h, a, n_super, train);
-    case 128: return launch_fwd_t<128>(h, a, n_super, train);
-    case 256: {
-      if (fwd_is_pipe(h)) return launch_fwd_pipe(h, a, n_super, train);
-      return launch_fwd_t<256>(h, a, n_super, train);
-    }
-  }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
-}
-int refresh_images_wide(sf_engine* h);
-int refresh_images_fourier(sf_engine* h);
 // WaveletSiren: the sub-handles launch on the handle's current stream (graph capture swaps it) and report to its profiler
 void wv_sync(sf_engine* h) {
   for (sf_engine* s : h->wv_sub) {
@@ -556,6 +661,255 @@ void wv_sync(sf_engine* h) {
     s->replay = h->replay;
   }
 }
+
+// algorithmic GEMM FLOPs per pixel (SURVEY.md §8d): forward 2*P_w, backward 4*P_w - 4*WD
+double flops_fwd_px(const sf_engine* h) {
+  const double W = h->WD;
+  return 2.0 * (2 * W + (h->D - 2) * W * W + h->cfg.out_features * W);
+}
+// ---------------------------------------------------------------------------------------------------------
+// wide path (hidden 512 / 1024): layer-at-a-time kernels of siren_wide.hip
+// ---------------------------------------------------------------------------------------------------------
+int refresh_images_wide(sf_engine* h) {
+  if (!h->images_dirty) return SF_OK;
+  const int WD = h->WD, D = h->D, NBLK = WD / 256, KS = WD / 16;
+  const bool f16 = h->cfg.compute_dtype == SF_F16;
+  Launch L(h, K_IMAGES, 0, (double)(D - 2) * WD * WD * 8.0);
+  {
+    WTabArgs t;
+    memset(&t, 0, sizeof(t));
+    t.params = h->params; t.depth = D; t.WD = WD; t.out_features = h->cfg.out_features;
+    t.off_w0 = h->off_w[0]; t.off_b0 = h->off_b[0];
+    for (int l = 0; l < D; ++l) t.off_b[l] = h->off_b[l];
+    t.wscale = h->wscale; t.hscale = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
+    t.l0tab = h->l0tab; t.bias = h->biasw;
+    long n = (long)(D - 2) * WD;
+    if (n < WD) n = WD;
+    SF_TRY(launch(h, k_wtables, (n + 255) / 256, 256, 0, t));
+  }
+  if (h->d8 && h->lsc) SF_TRY(launch_fp8_scales(h));   // per-layer fp8 delta scales, as at width <= 256
+  auto image = [&](int l, bool transpose, int OT, int n_ob, int n_chunk, float scale, uint16_t* dst) {
+    WImgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.link = (transpose && h->d8 && h->lsc) ? h->lsc + l : nullptr;
+    a.W = h->params + h->off_w[l];
+    a.rows = l == D - 1 ? h->cfg.out_features : WD; a.cols = WD;
+    a.transpose = transpose; a.OT = OT; a.n_ob = n_ob; a.n_chunk = n_chunk; a.scale = scale; a.f16 = f16; a.dst = dst;
+    const long total = (long)n_ob * n_chunk * OT * 4 * 512;
+    return launch(h, k_wimage, (total + 255) / 256, 256, 0, a);
+  };
+  for (int l = 1; l <= D - 2; ++l) {
+    SF_TRY(image(l, false, 8, NBLK, KS / 4, (float)((double)h->cfg.hidden_omega_0 / kTwoPi), h->wf + (size_t)(l - 1) * WD * WD));
+    SF_TRY(image(l, true, 8, NBLK, KS / 4, l - 1 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb + (size_t)(l - 1) * WD * WD));
+  }
+  SF_TRY(image(D - 1, false, 1, 1, KS / 4, h->wscale, h->wf_last));
+  SF_TRY(image(D - 1, true, 8, NBLK, 1, D - 2 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb_last));
+  h->images_dirty = false;
+  return SF_OK;
+}
+
+// persistent grid of the wide GEMMs: per_cu workgroups per CU, a multiple of 8 * n_ob (so XCD and output block are loop
+// invariants), at most one workgroup per tile
+unsigned wgemm_grid(const sf_engine* h, int per_cu, int n_ob, unsigned tiles) {
+  const unsigned pg = (unsigned)(per_cu * h->dw_wg / (8 * n_ob) * (8 * n_ob));
+  return pg == 0 || pg > tiles ? tiles : pg;
+}
+template <int MODE>
+int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob) {
+  const bool f16 = h->cfg.compute_dtype == SF_F16;
+  WGemmArgs b = a;
+  b.n_super = n_super; b.n_ob = n_ob;
+  auto tiles = [&](int units) { return (unsigned)((units + 7) / 8 * 8 * n_ob); };
+  const unsigned grid = tiles(n_super);
+  if constexpr (MODE == 1) {
+    return with_op(h, [&](auto op) { return launch(h, k_wgemm<1, decltype(op)>, grid, 512, (size_t)4 * 4 * 1024 + 64, b); });
+  } else {
+    if constexpr (MODE == 2) {
+      if (h->d8) {   // fp8 deltas (format 8): out always, in for every launch below the last layer's
+        const size_t lds8 = (size_t)4 * 32 * 1024;
+        const unsigned pg8 = wgemm_grid(h, 1, n_ob, grid);
+        return a.fscale ? launch(h, k_wgemm2<2, OpF16, true, 8, false, true>, pg8, 512, lds8, b)
+                        : launch(h, k_wgemm2<2, OpF16, true, 8, true, true>, pg8, 512, lds8, b);
+      }
+    }
+    if constexpr (MODE == 0) {
+      // k_wgemm3 (epilogue pipelined under the next tile, stores spread evenly) is correct and measured EQUAL to the tile loop below
+      // (DESIGN.md section 4b): opt-in
+      static const bool g3 = getenv("SIREN_FIT_WGEMM3") && atoi(getenv("SIREN_FIT_WGEMM3")) == 1;
+      if (g3 && f16 && h->s8 && (a.ks_in == 32 || a.ks_in == 64)) {   // forward hidden layers with the epilogue pipelined under the next tile
+        b.n_super = 2 * n_super;                            // 128-pixel units
+        b.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
+        const size_t lds3 = (size_t)4 * 24 * 1024 + 1024;
+        const unsigned pg = wgemm_grid(h, 1, n_ob, tiles(b.n_super));
+        return a.ks_in == 32 ? launch(h, k_wgemm3<32>, pg, 512, lds3, b) : launch(h, k_wgemm3<64>, pg, 512, lds3, b);
+      }
+    }
+    static const bool w4 = getenv("SIREN_FIT_WGEMM4") && atoi(getenv("SIREN_FIT_WGEMM4")) == 1;   // A/B knob: four-wave workgroups, two per CU
+    if (w4 && f16 && a.ks_in >= 8) {
+      b.n_super = 2 * n_super;                              // 128-pixel units
+      const size_t lds4 = (size_t)3 * 24 * 1024;
+      const unsigned pg = wgemm_grid(h, 2, n_ob, tiles(b.n_super));
+      return h->s8 ? launch(h, k_wgemm2<MODE, OpF16, true, 4>, pg, 256, lds4, b) : launch(h, k_wgemm2<MODE, OpF16, false, 4>, pg, 256, lds4, b);
+    }
+#ifdef SF_WEXP_STAMP
+    b.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
+#endif
+    const size_t lds = (size_t)4 * 32 * 1024;
+    const unsigned pgrid = wgemm_grid(h, 1, n_ob, grid);    // persistent: one workgroup per CU
+    if (h->s8 && (MODE == 0 || b.Pprev))                    // phase bytes (format 12; fp16 only: sf_create)
+      return launch(h, k_wgemm2<MODE, OpF16, true>, pgrid, 512, lds, b);
+    return with_op(h, [&](auto op) { return launch(h, k_wgemm2<MODE, decltype(op)>, pgrid, 512, lds, b); });
+  }
+}
+int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
+  SF_TRY(refresh_images_wide(h));
+  const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
+  const bool f16 = h->cfg.compute_dtype == SF_F16;
+  const float sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  const float sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
+  const size_t blk_pieces = (size_t)(KS / 4) * 32;   // pieces of one [256 x WD] block of a hidden image
+  long sse_off = 0;
+  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
+    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+    const int n_super = k.n_super;
+    const long n_pb = k.n_pb;
+    const double npx = n_pb * 32.0;
+    // ---- forward ----
+    {
+      WL0Args a;
+      memset(&a, 0, sizeof(a));
+      a.gh = h->gh; a.gw = h->gw; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin; a.pix0 = k.pix0; a.npix = h->npix;
+      a.l0tab = h->l0tab; a.sc_first = sc_first; a.KS = KS; a.n_pieces = n_pb * KS; a.P = h->Pbuf; a.Act = h->Abuf;
+      Launch L(h, K_FWD, 4.0 * WD * npx, npx * (WD * (h->s8 ? 3.0 : 4.0)));
+      if (h->s8) SF_TRY(launch(h, k_wlayer0<OpF16, true>, (a.n_pieces / 2 + 3) / 4, 256, 0, a));
+      else SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op)>, (a.n_pieces + 3) / 4, 256, 0, a); }));
+    }
+    for (int l = 1; l <= D - 2; ++l) {
+      WGemmArgs a;
+      memset(&a, 0, sizeof(a));
+      a.A = reinterpret_cast<const u32x4*>(h->wf + (size_t)(l - 1) * WD * WD);
+      a.a_block_pieces = (long)blk_pieces; a.n_chunk = KS / 4;
+      a.Bin = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ks_in = KS;
+      a.bias = h->biasw + (size_t)(l - 1) * WD; a.sc = sc_hidden;
+      a.Out = h->Pbuf + (size_t)l * h->p_stride; a.OutAct = h->Abuf + (size_t)l * h->a_stride; a.ks_out = KS; a.kp_out = WD / 32;
+      Launch L(h, K_FWD, 2.0 * WD * WD * npx, npx * (WD * ((h->s8 ? 3.0 : 4.0) + 2.0 * NBLK)));
+      SF_TRY(launch_wgemm<0>(h, a, n_super, NBLK));
+    }
+    {
+      WGemmArgs a;
+      memset(&a, 0, sizeof(a));
+      a.A = reinterpret_cast<const u32x4*>(h->wf_last);
+      a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
+      a.Bin = h->Abuf + (size_t)(D - 2) * h->a_stride; a.ks_in = KS;
+      a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
+      a.img = h->img; a.pred = pred; a.nout = h->cfg.out_features;
+      a.gscale = gscale(h);
+      a.sse_part = h->sse_part + sse_off; a.Dlast = train ? h->Dlast : nullptr; a.pix0 = k.pix0; a.npix = h->npix;
+      if (!h->cfg.outermost_linear) { a.last_om = h->cfg.hidden_omega_0; a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
+      sse_off += n_super;
+      Launch L(h, K_FWD, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + 12.0 + 64.0));
+      SF_TRY(launch_wgemm<1>(h, a, n_super, 1));
+    }
+    if (!train) continue;
+    // ---- backward ----
+    const int n_wg = (int)(n_pb < (long)h->dw_wg ? n_pb : (long)h->dw_wg);
+    if (h->d8)   // fp8 deltas: this chunk's power-of-two factor from its own residual
+      SF_TRY(launch(h, k_wchunk_scale, 1, 256, 0, h->sse_part + sse_off - n_super, n_super,
+                    1.0 / ((double)h->cfg.out_features * (double)k.px), gscale(h), h->gpre, fp8_target(), h->scale_dev));
+    for (int l = D - 1; l >= 1; --l) {
+      const bool last = l == D - 1;
+      const bool dl8 = h->d8 && !last;                      // this layer's incoming deltas are fp8 byte pieces
+      const u32x4* Dl = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
+      const u32x4* Pprev = h->Pbuf + (size_t)(l - 1) * h->p_stride;
+      const double rows = last ? h->cfg.out_features : WD;
+      {   // weight gradient: every [256 x 256] (last layer: [32 x 256]) block in one launch, blockIdx.y = block
+        const int nby = (last ? 1 : NBLK) * NBLK;
+        int gx = h->dw_wg / nby / 8 * 8;            // multiple of 8: same-pixel workgroups share an XCD
+        if (gx < 8) gx = 8;
+        if ((long)gx > n_pb) gx = (int)n_pb;
+        WDwArgs a;
+        memset(&a, 0, sizeof(a));
+        a.D = Dl; a.ksd_total = last ? 2 : (dl8 ? WD / 32 : KS); a.P = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ksp_total = KS; a.nblk_i = NBLK;
+        a.n_pb = n_pb; a.slab = h->slab;
+        {
+          Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx, npx * ((last ? 64.0 : WD * 2.0) + WD * 2.0));
+          const dim3 grid(gx, nby);
+          const size_t lds = (size_t)4 * ((last ? 2 : 16) + 16) * 1024;
+          if (dl8) SF_TRY(launch(h, k_wdw<256, OpF16, true>, grid, 512, (size_t)4 * (8 + 16) * 1024, a));
+          else SF_TRY(with_op(h, [&](auto op) {
+            using OP = decltype(op);
+            return last ? launch(h, k_wdw<32, OP>, grid, 512, lds, a) : launch(h, k_wdw<256, OP>, grid, 512, lds, a);
+          }));
+        }
+        WReduceArgs r;
+        memset(&r, 0, sizeof(r));
+        r.slab = h->slab; r.n_wg = gx; r.slab_rows = last ? 32 : 256; r.rows_out = last ? h->cfg.out_features : 256;
+        r.nblk_i = NBLK; r.gW = h->grads + h->off_w[l]; r.ldw = WD; r.gb = h->grads + h->off_b[l];
+        r.accumulate = c > 0; r.scale = 1.0f / h->gpre;
+        if (dl8) { r.s1 = h->scale_dev; r.s2 = h->lsc + 16 + l; }
+        const int n = r.rows_out * 256 + r.rows_out;
+        Launch L(h, K_REDUCE, 0, (double)gx * nby * n * 4.0);
+        SF_TRY(launch(h, k_wreduce, dim3((n + 255) / 256, nby), 256, 0, r));
+      }
+      // data gradient: delta_{l-1} = (delta_l W_l) * omega cos(P_{l-1})
+      WGemmArgs a;
+      memset(&a, 0, sizeof(a));
+      a.A = last ? reinterpret_cast<const u32x4*>(h->wb_last) : reinterpret_cast<const u32x4*>(h->wb + (size_t)(l - 1) * WD * WD);
+      a.a_block_pieces = last ? 32 : (long)blk_pieces; a.n_chunk = last ? 1 : KS / 4;
+      a.Bin = Dl; a.ks_in = last ? 2 : KS;
+      a.Out = h->Dbuf + (size_t)(l - 1) * h->d_stride; a.ks_out = KS; a.kp_out = WD / 32; a.Pprev = Pprev;
+      a.fscale = (h->d8 && last) ? h->scale_dev : nullptr;
+      Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx,
+               npx * ((last ? 64.0 : WD * 2.0 * NBLK) + WD * (h->s8 ? 3.0 : 4.0)));
+      SF_TRY(launch_wgemm<2>(h, a, n_super, NBLK));
+    }
+    for (int jb = 0; jb < NBLK; ++jb) {   // layer 0: contraction of delta_0 with the coordinates
+      Dw0Args da;
+      memset(&da, 0, sizeof(da));
+      fill_grid(h, k.pix0, da);
+      da.D = h->Dbuf; da.ks_total = KS; da.ks_off = 16 * jb; da.n_pb = n_pb; da.slab = h->slab;
+      {
+        Launch L(h, K_DW_FIRST, 4.0 * 256 * npx, (h->d8 ? 256.0 : 512.0) * npx);
+        SF_TRY(launch_dw_first_t<256>(h, da, n_wg));
+      }
+      ReduceArgs ra;
+      memset(&ra, 0, sizeof(ra));
+      ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre; ra.scale_dev = nullptr;
+      if (h->d8) { ra.scale_dev = h->scale_dev; ra.scale2_dev = h->lsc + 16; }     // 1 / (chunk factor * gpre), 1 / cumulative layer scale
+      ra.gW = h->grads + h->off_w[0] + 512 * jb; ra.gb = h->grads + h->off_b[0] + 256 * jb;
+      ra.slab_rows = 256; ra.slab_cols = 32; ra.rows_out = 256; ra.cols_out = 2; ra.mode = 1;
+      Launch L(h, K_REDUCE, 0, (double)n_wg * (256 * 3) * 4.0);
+      SF_TRY(launch_reduce(h, ra));
+    }
+  }
+  if (want_sse || train) SF_TRY(launch_sse_reduce(h, sse_off));
+  return SF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// FourierNet (fourier_kernels.hip): per chunk k_ff_fwd -> k_ff_bwd -> k_ff_dw per layer, each followed by the
+// fixed-order slab reduction into the flat gradient; Adam, graph replay and the rest are shared with SIREN
+// ---------------------------------------------------------------------------------------------------------
+int refresh_images_fourier(sf_engine* h) {
+  FfImgArgs a;
+  memset(&a, 0, sizeof(a));
+  a.params = h->params; a.nlin = h->D; a.img = h->ffimg;
+  for (int l = 0; l < h->D; ++l) {
+    a.off_w[l] = h->off_w[l];
+    a.in[l] = l == 0 ? h->MS : h->WD;
+    a.out[l] = l == h->D - 1 ? h->cfg.out_features : h->WD;
+    // segments in memory order: f0, (b0: empty), f1, b1, f2, b2, ...
+    a.start[2 * l] = h->ff_img_f[l];
+    a.start[2 * l + 1] = l == 0 ? h->ff_img_f[1] : h->ff_img_b[l];
+  }
+  a.start[2 * h->D] = h->ff_img_n;
+  Launch L(h, K_IMAGES, 0, (double)h->ff_img_n * 16.0);
+  SF_TRY(launch(h, k_ff_images, (h->ff_img_n + 255) / 256, 256, 0, a));
+  h->images_dirty = false;
+  return SF_OK;
+}
+
+// the weight images of any handle follow its parameters
 int refresh_images(sf_engine* h) {
   if (!h->images_dirty) return SF_OK;
   if (h->wide) return refresh_images_wide(h);
@@ -564,8 +918,7 @@ int refresh_images(sf_engine* h) {
     wv_sync(h);
     for (sf_engine* s : h->wv_sub) {
       s->images_dirty = true;
-      const int rc = refresh_images(s);
-      if (rc) return rc;
+      SF_TRY(refresh_images(s));
     }
     h->images_dirty = false;
     return SF_OK;
@@ -593,17 +946,10 @@ int refresh_images(sf_engine* h) {
   if (n < 1024) n = 1024;
   Launch L(h, K_IMAGES, 0, (double)n * 8);
   if (h->d8 && h->lsc) {   // per-layer delta scales first: k_images folds them into the backward images
-    Fp8ScaleArgs f;
-    memset(&f, 0, sizeof(f));
-    f.params = h->params; f.depth = h->D; f.WD = h->WD; f.out_features = h->cfg.out_features;
-    for (int l = 0; l < h->D; ++l) f.off_w[l] = h->off_w[l];
-    f.om_first = a.om_first; f.om_hidden = a.om_hidden; f.link = h->lsc; f.inv = h->lsc + 16;
-    f.nrm = reinterpret_cast<double*>(h->lsc + 32);
-    hipLaunchKernelGGL(k_fp8_norms, dim3(h->D - 1), dim3(1024), 0, h->stream, f);
-    hipLaunchKernelGGL(k_fp8_links, dim3(1), dim3(64), 0, h->stream, f);
+    SF_TRY(launch_fp8_scales(h));
     a.link = h->lsc;
   }
-  hipLaunchKernelGGL(k_images, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a);
+  SF_TRY(launch(h, k_images, (n + 255) / 256, 256, 0, a));
   if (h->wf16) {
     Img16Args b;
     memset(&b, 0, sizeof(b));
@@ -611,424 +957,56 @@ int refresh_images(sf_engine* h) {
     for (int l = 0; l < h->D; ++l) { b.off_w[l] = h->off_w[l]; b.off_b[l] = h->off_b[l]; }
     b.wscale = a.wscale; b.hscale = a.hscale; b.sc_first = a.sc_first;
     b.wf = h->wf16; b.wf_last = h->wf16_last; b.l0img = h->l0img16;
-    hipLaunchKernelGGL(k_images16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, b);
+    SF_TRY(launch(h, k_images16, (n + 255) / 256, 256, 0, b));
   }
-  L.done();
-  HIPCHK(hipGetLastError());
   h->images_dirty = false;
   return SF_OK;
 }
 
-// algorithmic GEMM FLOPs per pixel (SURVEY.md §8d): forward 2*P_w, backward 4*P_w - 4*WD
-double flops_fwd_px(const sf_engine* h) {
-  const double W = h->WD;
-  return 2.0 * (2 * W + (h->D - 2) * W * W + h->cfg.out_features * W);
+// what every kernel of the FourierNet chain is given for the chunk at pixel pix0: coordinates, encoding, weight images,
+// biases; the caller adds its planes and outputs (the RENDER form of k_ff_fwd touches none of H / G / Z / tgt / sse_part)
+FfArgs ff_args_base(const sf_engine* h, long pix0) {
+  FfArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.pix0 = pix0; fa.npix = h->npix; fa.cp = h->chunk_px;
+  fa.Btab = h->ffB; fa.MS = h->MS; fa.nlin = h->D; fa.img = h->ffimg; fa.params = h->params;
+  for (int l = 0; l < h->D; ++l) { fa.img_f[l] = h->ff_img_f[l]; fa.img_b[l] = h->ff_img_b[l]; fa.off_b[l] = h->off_b[l]; }
+  return fa;
 }
-// ---------------------------------------------------------------------------------------------------------
-// wide path (hidden 512 / 1024): layer-at-a-time kernels of siren_wide.hip
-// ---------------------------------------------------------------------------------------------------------
-int refresh_images_wide(sf_engine* h) {
-  if (!h->images_dirty) return SF_OK;
-  const int WD = h->WD, D = h->D, NBLK = WD / 256, KS = WD / 16;
-  const bool f16 = h->cfg.compute_dtype == SF_F16;
-  Launch L(h, K_IMAGES, 0, (double)(D - 2) * WD * WD * 8.0);
-  {
-    WTabArgs t;
-    memset(&t, 0, sizeof(t));
-    t.params = h->params; t.depth = D; t.WD = WD; t.out_features = h->cfg.out_features;
-    t.off_w0 = h->off_w[0]; t.off_b0 = h->off_b[0];
-    for (int l = 0; l < D; ++l) t.off_b[l] = h->off_b[l];
-    t.wscale = h->wscale; t.hscale = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
-    t.l0tab = h->l0tab; t.bias = h->biasw;
-    long n = (long)(D - 2) * WD;
-    if (n < WD) n = WD;
-    hipLaunchKernelGGL(k_wtables, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t);
-  }
-  if (h->d8 && h->lsc) {   // per-layer fp8 delta scales (k_fp8_norms / k_fp8_links, as at width <= 256)
-    Fp8ScaleArgs f;
-    memset(&f, 0, sizeof(f));
-    f.params = h->params; f.depth = h->D; f.WD = h->WD; f.out_features = h->cfg.out_features;
-    for (int l = 0; l < h->D; ++l) f.off_w[l] = h->off_w[l];
-    f.om_first = h->cfg.first_omega_0; f.om_hidden = h->cfg.hidden_omega_0; f.link = h->lsc; f.inv = h->lsc + 16;
-    f.nrm = reinterpret_cast<double*>(h->lsc + 32);
-    hipLaunchKernelGGL(k_fp8_norms, dim3(h->D - 1), dim3(1024), 0, h->stream, f);
-    hipLaunchKernelGGL(k_fp8_links, dim3(1), dim3(64), 0, h->stream, f);
-  }
-  auto image = [&](int l, bool transpose, int OT, int n_ob, int n_chunk, float scale, uint16_t* dst) {
-    WImgArgs a;
-    memset(&a, 0, sizeof(a));
-    a.link = (transpose && h->d8 && h->lsc) ? h->lsc + l : nullptr;
-    a.W = h->params + h->off_w[l];
-    a.rows = l == D - 1 ? h->cfg.out_features : WD; a.cols = WD;
-    a.transpose = transpose; a.OT = OT; a.n_ob = n_ob; a.n_chunk = n_chunk; a.scale = scale; a.f16 = f16; a.dst = dst;
-    const long total = (long)n_ob * n_chunk * OT * 4 * 512;
-    hipLaunchKernelGGL(k_wimage, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a);
-  };
-  for (int l = 1; l <= D - 2; ++l) {
-    image(l, false, 8, NBLK, KS / 4, (float)((double)h->cfg.hidden_omega_0 / kTwoPi),
-          h->wf + (size_t)(l - 1) * WD * WD);
-    image(l, true, 8, NBLK, KS / 4, l - 1 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb + (size_t)(l - 1) * WD * WD);
-  }
-  image(D - 1, false, 1, 1, KS / 4, h->wscale, h->wf_last);
-  image(D - 1, true, 8, NBLK, 1, D - 2 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb_last);
-  L.done();
-  HIPCHK(hipGetLastError());
-  h->images_dirty = false;
-  return SF_OK;
-}
-
-template <int MODE>
-int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob) {
-  const bool f16 = h->cfg.compute_dtype == SF_F16;
-  WGemmArgs b = a;
-  b.n_super = n_super; b.n_ob = n_ob;
-  const unsigned grid = (unsigned)((n_super + 7) / 8 * 8 * n_ob);
-  if constexpr (MODE == 1) {
-    const size_t lds = (size_t)4 * 4 * 1024 + 64;
-    int rc = f16 ? set_lds(k_wgemm<1, OpF16>, lds) : set_lds(k_wgemm<1, OpBF16>, lds);
-    if (rc) return rc;
-    if (f16) hipLaunchKernelGGL((k_wgemm<1, OpF16>), dim3(grid), dim3(512), lds, h->stream, b);
-    else hipLaunchKernelGGL((k_wgemm<1, OpBF16>), dim3(grid), dim3(512), lds, h->stream, b);
-  } else {
-    if constexpr (MODE == 2) {
-      if (h->d8) {   // fp8 deltas (format 8): out always, in for every launch below the last layer's
-        const size_t lds8 = (size_t)4 * 32 * 1024;
-        unsigned pg8 = (unsigned)(h->dw_wg / (8 * n_ob) * (8 * n_ob));
-        if (pg8 == 0 || pg8 > grid) pg8 = grid;
-        int rc;
-        if (a.fscale) {
-          rc = set_lds(k_wgemm2<2, OpF16, true, 8, false, true>, lds8);
-          if (rc) return rc;
-          hipLaunchKernelGGL((k_wgemm2<2, OpF16, true, 8, false, true>), dim3(pg8), dim3(512), lds8, h->stream, b);
-        } else {
-          rc = set_lds(k_wgemm2<2, OpF16, true, 8, true, true>, lds8);
-          if (rc) return rc;
-          hipLaunchKernelGGL((k_wgemm2<2, OpF16, true, 8, true, true>), dim3(pg8), dim3(512), lds8, h->stream, b);
-        }
-        HIPCHK(hipGetLastError());
-        return SF_OK;
-      }
-    }
-    if constexpr (MODE == 0) {
-      // k_wgemm3 (epilogue pipelined under the next tile, stores spread evenly) is correct and measured EQUAL to the tile loop below
-      // (DESIGN.md section 4b): opt-in
-      static const bool g3 = getenv("SIREN_FIT_WGEMM3") && atoi(getenv("SIREN_FIT_WGEMM3")) == 1;
-      if (g3 && f16 && h->s8 && (a.ks_in == 32 || a.ks_in == 64)) {   // forward hidden layers with the epilogue pipelined under the next tile
-        b.n_super = 2 * n_super;                            // 128-pixel units
-        b.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
-        const size_t lds3 = (size_t)4 * 24 * 1024 + 1024;
-        const unsigned grid3 = (unsigned)((b.n_super + 7) / 8 * 8 * n_ob);
-        unsigned pg = (unsigned)(h->dw_wg / (8 * n_ob) * (8 * n_ob));
-        if (pg == 0 || pg > grid3) pg = grid3;
-        int rc = a.ks_in == 32 ? set_lds(k_wgemm3<32>, lds3) : set_lds(k_wgemm3<64>, lds3);
-        if (rc) return rc;
-        if (a.ks_in == 32) hipLaunchKernelGGL((k_wgemm3<32>), dim3(pg), dim3(512), lds3, h->stream, b);
-        else hipLaunchKernelGGL((k_wgemm3<64>), dim3(pg), dim3(512), lds3, h->stream, b);
-        HIPCHK(hipGetLastError());
-        return SF_OK;
-      }
-    }
-    static const bool w4 = getenv("SIREN_FIT_WGEMM4") && atoi(getenv("SIREN_FIT_WGEMM4")) == 1;   // A/B knob: four-wave workgroups, two per CU
-    if (w4 && f16 && a.ks_in >= 8) {
-      b.n_super = 2 * n_super;                              // 128-pixel units
-      const size_t lds4 = (size_t)3 * 24 * 1024;
-      const unsigned grid4 = (unsigned)((b.n_super + 7) / 8 * 8 * n_ob);
-      unsigned pg = (unsigned)(2 * h->dw_wg / (8 * n_ob) * (8 * n_ob));
-      if (pg == 0 || pg > grid4) pg = grid4;
-      int rc;
-      if (h->s8) {
-        rc = set_lds(k_wgemm2<MODE, OpF16, true, 4>, lds4);
-        if (rc) return rc;
-        hipLaunchKernelGGL((k_wgemm2<MODE, OpF16, true, 4>), dim3(pg), dim3(256), lds4, h->stream, b);
-      } else {
-        rc = set_lds(k_wgemm2<MODE, OpF16, false, 4>, lds4);
-        if (rc) return rc;
-        hipLaunchKernelGGL((k_wgemm2<MODE, OpF16, false, 4>), dim3(pg), dim3(256), lds4, h->stream, b);
-      }
-      HIPCHK(hipGetLastError());
-      return SF_OK;
-    }
-#ifdef SF_WEXP_STAMP
-    b.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
-#endif
-    const size_t lds = (size_t)4 * 32 * 1024;
-    const bool p8 = h->s8 && (MODE == 0 || b.Pprev);        // phase bytes (format 12; fp16 only: sf_create)
-    int rc = p8 ? set_lds(k_wgemm2<MODE, OpF16, true>, lds) : f16 ? set_lds(k_wgemm2<MODE, OpF16>, lds) : set_lds(k_wgemm2<MODE, OpBF16>, lds);
-    if (rc) return rc;
-    // persistent: one workgroup per CU (a multiple of 8 * n_ob, so XCD and output block are loop invariants)
-    unsigned pgrid = (unsigned)(h->dw_wg / (8 * n_ob) * (8 * n_ob));
-    if (pgrid == 0 || pgrid > grid) pgrid = grid;
-    if (p8) hipLaunchKernelGGL((k_wgemm2<MODE, OpF16, true>), dim3(pgrid), dim3(512), lds, h->stream, b);
-    else if (f16) hipLaunchKernelGGL((k_wgemm2<MODE, OpF16>), dim3(pgrid), dim3(512), lds, h->stream, b);
-    else hipLaunchKernelGGL((k_wgemm2<MODE, OpBF16>), dim3(pgrid), dim3(512), lds, h->stream, b);
-  }
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
-  int rc = refresh_images_wide(h);
-  if (rc) return rc;
-  const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
-  const bool f16 = h->cfg.compute_dtype == SF_F16;
-  const float sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
-  const float sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
-  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
-  const size_t blk_pieces = (size_t)(KS / 4) * 32;   // pieces of one [256 x WD] block of a hidden image
-  long sse_off = 0;
-  for (long c = 0; c < n_chunks; ++c) {
-    const long pix0 = c * h->chunk_px;
-    long px = h->npix - pix0;
-    if (px > h->chunk_px) px = h->chunk_px;
-    const int n_super = (int)((px + kSuper - 1) / kSuper);
-    const long n_pb = (long)n_super * kWavesFwd;
-    const double npx = n_pb * 32.0;
-    // ---- forward ----
-    {
-      WL0Args a;
-      memset(&a, 0, sizeof(a));
-      a.gh = h->gh; a.gw = h->gw; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin; a.pix0 = pix0; a.npix = h->npix;
-      a.l0tab = h->l0tab; a.sc_first = sc_first; a.KS = KS; a.n_pieces = n_pb * KS; a.P = h->Pbuf; a.Act = h->Abuf;
-      Launch L(h, K_FWD, 4.0 * WD * npx, npx * (WD * (h->s8 ? 3.0 : 4.0)));
-      if (h->s8) hipLaunchKernelGGL((k_wlayer0<OpF16, true>), dim3((unsigned)((a.n_pieces / 2 + 3) / 4)), dim3(256), 0, h->stream, a);
-      else if (f16) hipLaunchKernelGGL(k_wlayer0<OpF16>, dim3((unsigned)((a.n_pieces + 3) / 4)), dim3(256), 0, h->stream, a);
-      else hipLaunchKernelGGL(k_wlayer0<OpBF16>, dim3((unsigned)((a.n_pieces + 3) / 4)), dim3(256), 0, h->stream, a);
-      L.done();
-      HIPCHK(hipGetLastError());
-    }
-    for (int l = 1; l <= D - 2; ++l) {
-      WGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.A = reinterpret_cast<const u32x4*>(h->wf + (size_t)(l - 1) * WD * WD);
-      a.a_block_pieces = (long)blk_pieces; a.n_chunk = KS / 4;
-      a.Bin = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ks_in = KS;
-      a.bias = h->biasw + (size_t)(l - 1) * WD; a.sc = sc_hidden;
-      a.Out = h->Pbuf + (size_t)l * h->p_stride; a.OutAct = h->Abuf + (size_t)l * h->a_stride; a.ks_out = KS; a.kp_out = WD / 32;
-      Launch L(h, K_FWD, 2.0 * WD * WD * npx, npx * (WD * ((h->s8 ? 3.0 : 4.0) + 2.0 * NBLK)));
-      rc = launch_wgemm<0>(h, a, n_super, NBLK);
-      L.done();
-      if (rc) return rc;
-    }
-    {
-      WGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.A = reinterpret_cast<const u32x4*>(h->wf_last);
-      a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
-      a.Bin = h->Abuf + (size_t)(D - 2) * h->a_stride; a.ks_in = KS;
-      a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
-      a.img = h->img; a.pred = pred; a.nout = h->cfg.out_features;
-      a.gscale = (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total));
-      a.sse_part = h->sse_part + sse_off; a.Dlast = train ? h->Dlast : nullptr; a.pix0 = pix0; a.npix = h->npix;
-      if (!h->cfg.outermost_linear) { a.last_om = h->cfg.hidden_omega_0; a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
-      sse_off += n_super;
-      Launch L(h, K_FWD, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + 12.0 + 64.0));
-      rc = launch_wgemm<1>(h, a, n_super, 1);
-      L.done();
-      if (rc) return rc;
-    }
-    if (!train) continue;
-    // ---- backward ----
-    int n_wg = (int)(n_pb < (long)h->dw_wg ? n_pb : (long)h->dw_wg);
-    if (h->d8)   // fp8 deltas: this chunk's power-of-two factor from its own residual
-      hipLaunchKernelGGL(k_wchunk_scale, dim3(1), dim3(256), 0, h->stream, (const float*)(h->sse_part + sse_off - n_super), n_super,
-                         1.0 / ((double)h->cfg.out_features * (double)px), (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total)),
-                         h->gpre, fp8_target(), h->scale_dev);
-    for (int l = D - 1; l >= 1; --l) {
-      const bool last = l == D - 1;
-      const bool dl8 = h->d8 && !last;                      // this layer's incoming deltas are fp8 byte pieces
-      const u32x4* Dl = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
-      const u32x4* Pprev = h->Pbuf + (size_t)(l - 1) * h->p_stride;
-      {   // weight gradient: every [256 x 256] (last layer: [32 x 256]) block in one launch, blockIdx.y = block
-        const int nby = (last ? 1 : NBLK) * NBLK;
-        int gx = h->dw_wg / nby / 8 * 8;            // multiple of 8: same-pixel workgroups share an XCD
-        if (gx < 8) gx = 8;
-        if ((long)gx > n_pb) gx = (int)n_pb;
-        WDwArgs a;
-        memset(&a, 0, sizeof(a));
-        a.D = Dl; a.ksd_total = last ? 2 : (dl8 ? WD / 32 : KS); a.P = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ksp_total = KS; a.nblk_i = NBLK;
-        a.n_pb = n_pb; a.slab = h->slab;
-        const double rows = last ? h->cfg.out_features : WD;
-        {
-          Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx, npx * ((last ? 64.0 : WD * 2.0) + WD * 2.0));
-          const size_t lds = (size_t)4 * ((last ? 2 : 16) + 16) * 1024;
-#define SF_WDW(JWv, OPv)                                                                         \
-  do {                                                                                           \
-    rc = set_lds(k_wdw<JWv, OPv>, lds);                                                          \
-    if (rc) return rc;                                                                           \
-    hipLaunchKernelGGL((k_wdw<JWv, OPv>), dim3(gx, nby), dim3(512), lds, h->stream, a);          \
-  } while (0)
-          if (last) { if (f16) SF_WDW(32, OpF16); else SF_WDW(32, OpBF16); }
-          else if (dl8) {
-            const size_t lds8 = (size_t)4 * (8 + 16) * 1024;
-            rc = set_lds(k_wdw<256, OpF16, true>, lds8);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_wdw<256, OpF16, true>), dim3(gx, nby), dim3(512), lds8, h->stream, a);
-          }
-          else { if (f16) SF_WDW(256, OpF16); else SF_WDW(256, OpBF16); }
-#undef SF_WDW
-          L.done();
-          HIPCHK(hipGetLastError());
-        }
-        WReduceArgs r;
-        memset(&r, 0, sizeof(r));
-        r.slab = h->slab; r.n_wg = gx; r.slab_rows = last ? 32 : 256; r.rows_out = last ? h->cfg.out_features : 256;
-        r.nblk_i = NBLK; r.gW = h->grads + h->off_w[l]; r.ldw = WD; r.gb = h->grads + h->off_b[l];
-        r.accumulate = c > 0; r.scale = 1.0f / h->gpre;
-        if (dl8) { r.s1 = h->scale_dev; r.s2 = h->lsc + 16 + l; }
-        const int n = r.rows_out * 256 + r.rows_out;
-        Launch L(h, K_REDUCE, 0, (double)gx * nby * n * 4.0);
-        hipLaunchKernelGGL(k_wreduce, dim3((n + 255) / 256, nby), dim3(256), 0, h->stream, r);
-        L.done();
-        HIPCHK(hipGetLastError());
-      }
-      // data gradient: delta_{l-1} = (delta_l W_l) * omega cos(P_{l-1})
-      WGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.A = last ? reinterpret_cast<const u32x4*>(h->wb_last) : reinterpret_cast<const u32x4*>(h->wb + (size_t)(l - 1) * WD * WD);
-      a.a_block_pieces = last ? 32 : (long)blk_pieces; a.n_chunk = last ? 1 : KS / 4;
-      a.Bin = Dl; a.ks_in = last ? 2 : KS;
-      a.Out = h->Dbuf + (size_t)(l - 1) * h->d_stride; a.ks_out = KS; a.kp_out = WD / 32; a.Pprev = Pprev;
-      a.fscale = (h->d8 && last) ? h->scale_dev : nullptr;
-      const double rows = last ? h->cfg.out_features : WD;
-      Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx,
-               npx * ((last ? 64.0 : WD * 2.0 * NBLK) + WD * (h->s8 ? 3.0 : 4.0)));
-      rc = launch_wgemm<2>(h, a, n_super, NBLK);
-      L.done();
-      if (rc) return rc;
-    }
-    for (int jb = 0; jb < NBLK; ++jb) {   // layer 0: contraction of delta_0 with the coordinates
-      Dw0Args da;
-      memset(&da, 0, sizeof(da));
-      da.D = h->Dbuf; da.ks_total = KS; da.ks_off = 16 * jb; da.n_pb = n_pb; da.slab = h->slab; da.pix0 = pix0; da.npix = h->npix;
-      da.W = h->cfg.width; da.row_begin = h->cfg.row_begin;
-      da.inv_hm1 = h->cfg.height > 1 ? 1.0f / (float)(h->cfg.height - 1) : 0.f;
-      da.inv_wm1 = h->cfg.width > 1 ? 1.0f / (float)(h->cfg.width - 1) : 0.f;
-      da.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
-      if (h->d8) {
-        Launch L(h, K_DW_FIRST, 4.0 * 256 * npx, 256.0 * npx);
-        rc = launch_dw0_8_t<256>(h, da, n_wg);
-        L.done();
-        if (rc) return rc;
-      } else {
-        Launch L(h, K_DW_FIRST, 4.0 * 256 * npx, 512.0 * npx);
-        const size_t lds = (size_t)8 * 16 * 1024 + 512;
-        rc = f16 ? set_lds(k_dw0<256, OpF16>, lds) : set_lds(k_dw0<256, OpBF16>, lds);
-        if (rc) return rc;
-        if (f16) hipLaunchKernelGGL((k_dw0<256, OpF16>), dim3(n_wg), dim3(512), lds, h->stream, da);
-        else hipLaunchKernelGGL((k_dw0<256, OpBF16>), dim3(n_wg), dim3(512), lds, h->stream, da);
-        L.done();
-        HIPCHK(hipGetLastError());
-      }
-      ReduceArgs ra;
-      memset(&ra, 0, sizeof(ra));
-      ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre; ra.scale_dev = nullptr;
-      if (h->d8) { ra.scale_dev = h->scale_dev; ra.scale2_dev = h->lsc + 16; }     // 1 / (chunk factor * gpre), 1 / cumulative layer scale
-      ra.gW = h->grads + h->off_w[0] + 512 * jb; ra.gb = h->grads + h->off_b[0] + 256 * jb;
-      ra.slab_rows = 256; ra.slab_cols = 32; ra.rows_out = 256; ra.cols_out = 2; ra.mode = 1;
-      const int n = 256 * 3;
-      Launch L(h, K_REDUCE, 0, (double)n_wg * n * 4.0);
-      hipLaunchKernelGGL(k_reduce, dim3((n + 15) / 16), dim3(256), 0, h->stream, ra);
-      L.done();
-      HIPCHK(hipGetLastError());
-    }
-  }
-  if (want_sse || train) {
-    Launch L(h, K_SSE, 0, (double)sse_off * 4);
-    hipLaunchKernelGGL(k_sse_reduce, dim3(1), dim3(256), 0, h->stream, (const float*)h->sse_part, (int)sse_off, h->sse_dev,
-                       h->replay ? h->loss_tab : h->loss_dst, (const int*)(h->replay ? h->iter_dev : h->iter_dev + 2));
-    L.done();
-    HIPCHK(hipGetLastError());
-  }
-  return SF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// FourierNet (fourier_kernels.hip): per chunk k_ff_fwd -> k_ff_bwd -> k_ff_dw per layer, each followed by the
-// fixed-order slab reduction into the flat gradient; Adam, graph replay and the rest are shared with SIREN
-// ---------------------------------------------------------------------------------------------------------
-int refresh_images_fourier(sf_engine* h) {
-  FfImgArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = h->params; a.nlin = h->D; a.img = h->ffimg;
-  for (int l = 0; l < h->D; ++l) {
-    a.off_w[l] = h->off_w[l];
-    a.in[l] = l == 0 ? h->MS : h->WD;
-    a.out[l] = l == h->D - 1 ? h->cfg.out_features : h->WD;
-    // segments in memory order: f0, (b0: empty), f1, b1, f2, b2, ...
-    a.start[2 * l] = h->ff_img_f[l];
-    a.start[2 * l + 1] = l == 0 ? h->ff_img_f[1] : h->ff_img_b[l];
-  }
-  a.start[2 * h->D] = h->ff_img_n;
-  Launch L(h, K_IMAGES, 0, (double)h->ff_img_n * 16.0);
-  hipLaunchKernelGGL(k_ff_images, dim3((unsigned)((h->ff_img_n + 255) / 256)), dim3(256), 0, h->stream, a);
-  L.done();
-  HIPCHK(hipGetLastError());
-  h->images_dirty = false;
-  return SF_OK;
-}
-
-template <int NI, bool E0>
-int launch_ff_dw(sf_engine* h, const FfDwArgs& a, int gx) {
-  hipLaunchKernelGGL((k_ff_dw<NI, E0>), dim3(gx, (a.n_groups + 3) / 4), dim3(256), 0, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-
-template <int WD>
-int launch_ff_chain(sf_engine* h, const FfArgs& a, int n_super, int which) {   // 0 eval forward, 1 training forward, 2 backward
-  int rc = SF_OK;
-  if (which == 0) { rc = set_lds(k_ff_fwd<WD, false>, kFfLdsBytes); if (!rc) hipLaunchKernelGGL((k_ff_fwd<WD, false>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a); }
-  else if (which == 1) { rc = set_lds(k_ff_fwd<WD, true>, kFfLdsBytes); if (!rc) hipLaunchKernelGGL((k_ff_fwd<WD, true>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a); }
-  else { rc = set_lds(k_ff_bwd<WD>, kFfLdsBytes); if (!rc) hipLaunchKernelGGL((k_ff_bwd<WD>), dim3(n_super), dim3(kFfThreads), kFfLdsBytes, h->stream, a); }
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-int launch_ff(sf_engine* h, const FfArgs& a, int n_super, int which) {
-  switch (h->WD) {
-    case 32: return launch_ff_chain<32>(h, a, n_super, which);
-    case 64: return launch_ff_chain<64>(h, a, n_super, which);
-    case 128: return launch_ff_chain<128>(h, a, n_super, which);
-    case 256: return launch_ff_chain<256>(h, a, n_super, which);
-  }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
+enum FfKernel { kFfEval, kFfTrain, kFfBwd, kFfRender };   // k_ff_fwd<WD, false>, k_ff_fwd<WD, true>, k_ff_bwd<WD>, k_ff_fwd<WD, false, true>
+int launch_ff(sf_engine* h, const FfArgs& a, int n_super, FfKernel which) {
+  return with_width(h, [&](auto wd) {
+    constexpr int WD = decltype(wd)::value;
+    auto go = [&](auto kernel) { return launch(h, kernel, n_super, kFfThreads, kFfLdsBytes, a); };
+    return which == kFfEval ? go(k_ff_fwd<WD, false>) : which == kFfTrain ? go(k_ff_fwd<WD, true>)
+           : which == kFfBwd ? go(k_ff_bwd<WD>) : go(k_ff_fwd<WD, false, true>);
+  });
 }
 
 int run_pass_fourier(sf_engine* h, bool train, float* pred, bool want_sse) {
   if (!h->have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
-  int rc = refresh_images(h);
-  if (rc) return rc;
+  SF_TRY(refresh_images(h));
   const int WD = h->WD, D = h->D, MS = h->MS;
-  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
   long sse_off = 0;
-  for (long c = 0; c < n_chunks; ++c) {
-    const long pix0 = c * h->chunk_px;
-    long px = h->npix - pix0;
-    if (px > h->chunk_px) px = h->chunk_px;
-    const int n_super = (int)((px + kSuper - 1) / kSuper);
+  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
+    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+    const int n_super = k.n_super;
     const double npx = (double)n_super * kSuper;
-    FfArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.gh = h->gh; fa.gw = h->gw; fa.W = h->cfg.width; fa.pix0 = pix0; fa.npix = h->npix; fa.cp = h->chunk_px;
-    fa.Btab = h->ffB; fa.MS = MS; fa.nlin = D; fa.img = h->ffimg; fa.params = h->params;
-    for (int l = 0; l < D; ++l) { fa.img_f[l] = h->ff_img_f[l]; fa.img_b[l] = h->ff_img_b[l]; fa.off_b[l] = h->off_b[l]; }
+    FfArgs fa = ff_args_base(h, k.pix0);
     fa.H = h->ffH; fa.G = h->ffG; fa.Z = h->ffZ;
     fa.tgt = h->img; fa.pred = pred; fa.sse_part = h->sse_part + sse_off;
-    fa.gscale = (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total));
+    fa.gscale = gscale(h);
     sse_off += n_super;
     const double f_hidden = (double)(D - 2) * WD * WD;
     {
       Launch L(h, K_FWD, 2.0 * ((double)MS * WD + f_hidden + 32.0 * WD) * npx,
                npx * (12.0 + (train ? (D - 1) * WD * 2.0 + 6.0 : 0.0)));
-      rc = launch_ff(h, fa, n_super, train ? 1 : 0);
-      L.done();
-      if (rc) return rc;
+      SF_TRY(launch_ff(h, fa, n_super, train ? kFfTrain : kFfEval));
     }
     if (!train) continue;
     {
       Launch L(h, K_BWD_HIDDEN, 2.0 * (f_hidden + 16.0 * WD) * npx, npx * (6.0 + (D - 1) * WD * 4.0));
-      rc = launch_ff(h, fa, n_super, 2);
-      L.done();
-      if (rc) return rc;
+      SF_TRY(launch_ff(h, fa, n_super, kFfBwd));
     }
     // weight gradients, last layer first: per-workgroup slabs over contiguous pixel ranges, then k_reduce*
     int gx = (int)(npx / kSuper);
@@ -1051,35 +1029,29 @@ int run_pass_fourier(sf_engine* h, bool train, float* pred, bool want_sse) {
       {
         Launch L(h, l == 0 ? K_DW_FIRST : last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * 32.0 * ((da.rows + 31) / 32) * da.in * npx,
                  npx * 2.0 * (32.0 * ((da.rows + 31) / 32) + (l == 0 ? 0.0 : da.in)));
-        if (l == 0) rc = NI == 1 ? launch_ff_dw<1, true>(h, da, gx) : NI == 2 ? launch_ff_dw<2, true>(h, da, gx) : launch_ff_dw<4, true>(h, da, gx);
-        else rc = NI == 1 ? launch_ff_dw<1, false>(h, da, gx) : NI == 2 ? launch_ff_dw<2, false>(h, da, gx) : launch_ff_dw<4, false>(h, da, gx);
-        L.done();
-        if (rc) return rc;
+        const dim3 grid(gx, (da.n_groups + 3) / 4);
+        SF_TRY(with_bool(l == 0, [&](auto e0) {
+          constexpr bool E0 = decltype(e0)::value;
+          return NI == 1 ? launch(h, k_ff_dw<1, E0>, grid, 256, 0, da) : NI == 2 ? launch(h, k_ff_dw<2, E0>, grid, 256, 0, da)
+                                                                                 : launch(h, k_ff_dw<4, E0>, grid, 256, 0, da);
+        }));
       }
       const long n = (long)da.rows * da.in + da.rows;
       Launch L(h, K_REDUCE, 0, (double)gx * n * 4.0);
       if (!last) {   // slab layout [W rows*in | b rows] == flat gradient layout of the layer
         const int n4 = (int)(n / 4);
-        hipLaunchKernelGGL(k_reduce_vec, dim3((n4 + 7) / 8), dim3(256), 0, h->stream, (const float*)h->slab, gx, n, n4,
-                           h->grads + h->off_w[l], (int)(c > 0), 1.0f / h->gpre, (const float*)nullptr, (const float*)nullptr);
+        SF_TRY(launch(h, k_reduce_vec, (n4 + 7) / 8, 256, 0, h->slab, gx, n, n4, h->grads + h->off_w[l], c > 0, 1.0f / h->gpre,
+                      nullptr, nullptr));
       } else {
         ReduceArgs ra;
         memset(&ra, 0, sizeof(ra));
         ra.slab = h->slab; ra.n_wg = gx; ra.slab_rows = da.rows; ra.slab_cols = da.in; ra.rows_out = da.rows; ra.cols_out = da.in;
         ra.mode = 0; ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l]; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
-        hipLaunchKernelGGL(k_reduce, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, h->stream, ra);
+        SF_TRY(launch_reduce(h, ra));
       }
-      L.done();
-      HIPCHK(hipGetLastError());
     }
   }
-  if (want_sse || train) {
-    Launch L(h, K_SSE, 0, (double)sse_off * 4);
-    hipLaunchKernelGGL(k_sse_reduce, dim3(1), dim3(256), 0, h->stream, (const float*)h->sse_part, (int)sse_off,
-                       h->sse_dev, h->replay ? h->loss_tab : h->loss_dst, (const int*)(h->replay ? h->iter_dev : h->iter_dev + 2));
-    L.done();
-    HIPCHK(hipGetLastError());
-  }
+  if (want_sse || train) SF_TRY(launch_sse_reduce(h, sse_off));
   return SF_OK;
 }
 
@@ -1097,35 +1069,29 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = 
   if (h->fourier) return run_pass_fourier(h, train, pred, want_sse);
   if (train && (!h->Pbuf || !h->Dbuf)) return fail(SF_ERR_STATE, "the handle has no backward scratch");   // (never a null store on the GPU)
   if (h->wide) return run_pass_wide(h, train, pred, want_sse);
-  int rc = refresh_images(h);
-  if (rc) return rc;
-  const int WD = h->WD, D = h->D, KS = WD / 16;
-  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
+  SF_TRY(refresh_images(h));
+  const int WD = h->WD, D = h->D;
   long sse_off = 0;
-  for (long c = c_begin; c < (c_end < 0 ? n_chunks : c_end); ++c) {
-    const long pix0 = c * h->chunk_px;
-    long px = h->npix - pix0;
-    if (px > h->chunk_px) px = h->chunk_px;
-    const int n_super = (int)((px + kSuper - 1) / kSuper);
-    const long n_pb = (long)n_super * kWavesFwd;
-    FwdArgs fa = fwd_args_base(h, pix0, n_super);
+  for (long c = c_begin; c < (c_end < 0 ? n_chunks(h->npix, h->chunk_px) : c_end); ++c) {
+    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+    const long n_pb = k.n_pb;
+    const double npx = n_pb * 32.0;
+    FwdArgs fa = fwd_args_base(h, k.pix0, k.n_super);
     fa.P = h->Pbuf; fa.p_stride = h->p_stride; fa.Dlast = h->Dlast;
     fa.dfac = train ? h->dfac_out : nullptr;
     fa.img = h->img;
-    fa.gscale = h->d8 ? kResScale : (float)((double)h->gpre / ((double)h->cfg.out_features * h->n_total));
+    fa.gscale = h->d8 ? kResScale : gscale(h);
     fa.pred = pred;
     fa.sse_part = h->sse_part + sse_off;
-    const int n_fwd_wg = fwd_grid(h, n_super);
+    const int n_fwd_wg = fwd_grid(h, k.n_super);
 #ifdef SF_EXPERIMENT_STAMP
     fa.dbg = h->sse_part + h->n_sse;   // 64 spare floats behind the partials
 #endif
     sse_off += n_fwd_wg;
     if (phases & kPassFwd) {
-      Launch L(h, K_FWD, flops_fwd_px(h) * n_pb * 32.0,
-               n_pb * 32.0 * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
-      rc = launch_fwd(h, fa, n_fwd_wg, train);
-      L.done();
-      if (rc) return rc;
+      Launch L(h, K_FWD, flops_fwd_px(h) * npx,
+               npx * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
+      SF_TRY(launch_fwd(h, fa, n_fwd_wg, train));
     }
     if (!train || !(phases & kPassBwd)) continue;
     // backward, last layer first; every layer kernel is followed by the fixed-order slab reduction
@@ -1136,122 +1102,81 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = 
     pb_per_wg = (pb_per_wg + PBS - 1) / PBS * PBS;
     n_wg = (int)((n_pb + pb_per_wg - 1) / pb_per_wg);
     const size_t img_pieces = (size_t)WD * WD / 8;
+    // what Bwd8Args and BwdLayerArgs share for layer l >= 1: deltas in and out, phases of the layer below, the backward image
+    auto fill_layer = [&](auto& ba, int l) {
+      const bool last = l == D - 1;
+      memset(&ba, 0, sizeof(ba));
+      fill_grid(h, k.pix0, ba);
+      ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
+      ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
+      ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
+      ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
+                   : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
+      ba.n_pb = n_pb; ba.slab = h->slab; ba.l0tab = h->l0tab; ba.sc_first = fa.sc_first;
+    };
     for (int l = D - 1; l >= 0; --l) {
+      const bool last = l == D - 1;
+      const double rows = last ? h->cfg.out_features : WD;
       ReduceArgs ra;
       memset(&ra, 0, sizeof(ra));
       ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
       if (h->d8) {   // last layer: dW from the statically scaled residual; layers below: the chunk's adaptive pre-scale
         ra.scale = (float)(1.0 / ((double)kResScale * (double)h->cfg.out_features * h->n_total));
-        ra.scale_dev = l == D - 1 ? nullptr : h->scale_dev;
-        ra.scale2_dev = (l == D - 1 || !h->lsc) ? nullptr : h->lsc + 16 + l;
+        ra.scale_dev = last ? nullptr : h->scale_dev;
+        ra.scale2_dev = (last || !h->lsc) ? nullptr : h->lsc + 16 + l;
       }
       ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l];
+      // a layer above 0: rows x WD weight gradient from slabs of (last: 32, else WD) rows
+      ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD; ra.rows_out = (int)rows; ra.cols_out = WD; ra.mode = 0;
       if (l > 0 && h->s8) {
         // layer 1: with fp8 deltas at width 256 the pipeline forward also spills layer 0's phase bytes, so this layer runs the
         // hidden-layer kernel (k_bwd8h) like the others; else the form that re-derives the layer-0 phases from the coordinates
         static const bool l1_old = getenv("SIREN_FIT_BWD8H") && atoi(getenv("SIREN_FIT_BWD8H")) == 0;
-        const bool last = l == D - 1, l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h) && !l1_old, p0 = l - 1 == 0 && !(l0_bytes && !last);
+        const bool l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h) && !l1_old, p0 = l - 1 == 0 && !(l0_bytes && !last);
         Bwd8Args ba;
-        memset(&ba, 0, sizeof(ba));
-        ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
-        ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
-        ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
-        ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
-                     : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
-        ba.n_pb = n_pb; ba.slab = h->slab;
-        ba.l0tab = h->l0tab; ba.pix0 = pix0; ba.npix = h->npix; ba.W = h->cfg.width; ba.row_begin = h->cfg.row_begin;
-        ba.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
-        ba.inv_hm1 = h->cfg.height > 1 ? 1.0f / (float)(h->cfg.height - 1) : 0.f;
-        ba.inv_wm1 = h->cfg.width > 1 ? 1.0f / (float)(h->cfg.width - 1) : 0.f;
-        ba.sc_first = fa.sc_first;
+        fill_layer(ba, l);
         ba.sse_part = fa.sse_part; ba.n_part = n_fwd_wg;
-        ba.inv_chunk_values = 1.0 / ((double)h->cfg.out_features * (double)px);
+        ba.inv_chunk_values = 1.0 / ((double)h->cfg.out_features * (double)k.px);
         ba.n_values = (double)h->cfg.out_features * h->n_total;
         ba.res_scale = kResScale; ba.target = fp8_target(); ba.scale_out = h->scale_dev;
         ba.zeros = reinterpret_cast<const u32x4*>(h->pad8); ba.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
 #ifdef SF_EXPERIMENT_STAMP
         ba.dbg = h->sse_part + h->n_sse;
 #endif
-        const double rows = last ? h->cfg.out_features : WD;
-        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * n_pb * 32.0,
-                 n_pb * 32.0 * ((last ? 32.0 : WD * (h->d8 ? 1.0 : 2.0)) + WD * (h->d8 ? 1.0 : 2.0) + (p0 ? 0.0 : WD * 1.0)));
         // hidden 256: the last-layer kernel keeps two workgroups per CU (its slab rows are 32 wide: the slab has room)
-        int n_wg_l = n_wg;
-        if (last && !p0 && WD == 256 && h->d8) {
-          n_wg_l = (int)((n_pb + PBS - 1) / PBS);
-          if (n_wg_l > 2 * h->dw_wg) n_wg_l = 2 * h->dw_wg;
-        }
-        rc = launch_bwd8(h, last, p0, ba, n_wg_l);
-        L.done();
-        if (rc) return rc;
-        ra.n_wg = n_wg_l;
-        ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD;
-        ra.rows_out = last ? h->cfg.out_features : WD; ra.cols_out = WD; ra.mode = 0;
+        if (last && !p0 && WD == 256 && h->d8) ra.n_wg = (int)std::min<long>((n_pb + PBS - 1) / PBS, 2L * h->dw_wg);
+        const double db = h->d8 ? 1.0 : 2.0;   // bytes per delta
+        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
+                 npx * ((last ? 32.0 : WD * db) + WD * db + (p0 ? 0.0 : WD * 1.0)));
+        SF_TRY(launch_bwd8(h, last, p0, ba, ra.n_wg));
       } else if (l > 0) {
-        const bool last = l == D - 1;
-        BwdLayerArgs ba;
-        memset(&ba, 0, sizeof(ba));
-        ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
-        ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
-        ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
-        ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
-                     : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
-        ba.n_pb = n_pb; ba.pb_per_wg = (int)pb_per_wg;
-        ba.slab = h->slab;
         const bool p0 = l - 1 == 0;
-        ba.l0tab = h->l0tab; ba.pix0 = pix0; ba.npix = h->npix; ba.W = h->cfg.width; ba.row_begin = h->cfg.row_begin;
-        ba.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
-        ba.inv_hm1 = h->cfg.height > 1 ? 1.0f / (float)(h->cfg.height - 1) : 0.f;
-        ba.inv_wm1 = h->cfg.width > 1 ? 1.0f / (float)(h->cfg.width - 1) : 0.f;
-        ba.sc_first = fa.sc_first;
-        const double rows = last ? h->cfg.out_features : WD;
-        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * n_pb * 32.0,
-                 n_pb * 32.0 * ((last ? 64.0 : WD * 2.0) + WD * (p0 ? 2.0 : 4.0)));
-        rc = launch_bwd(h, last, p0, ba, n_wg);
-        L.done();
-        if (rc) return rc;
-        ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD;
-        ra.rows_out = last ? h->cfg.out_features : WD; ra.cols_out = WD; ra.mode = 0;
+        BwdLayerArgs ba;
+        fill_layer(ba, l);
+        ba.pb_per_wg = (int)pb_per_wg;
+        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
+                 npx * ((last ? 64.0 : WD * 2.0) + WD * (p0 ? 2.0 : 4.0)));
+        SF_TRY(launch_bwd(h, last, p0, ba, n_wg));
       } else {
         Dw0Args da;
         memset(&da, 0, sizeof(da));
-        da.D = h->Dbuf; da.ks_total = KS; da.ks_off = 0; da.n_pb = n_pb; da.slab = h->slab; da.pix0 = pix0; da.npix = h->npix;
-        da.W = h->cfg.width; da.row_begin = h->cfg.row_begin;
-        da.inv_hm1 = h->cfg.height > 1 ? 1.0f / (float)(h->cfg.height - 1) : 0.f;
-        da.inv_wm1 = h->cfg.width > 1 ? 1.0f / (float)(h->cfg.width - 1) : 0.f;
-        da.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
-        Launch L(h, K_DW_FIRST, 4.0 * WD * n_pb * 32.0, WD * (h->d8 ? 1.0 : 2.0) * n_pb * 32.0);
+        fill_grid(h, k.pix0, da);
+        da.D = h->Dbuf; da.ks_total = WD / 16; da.ks_off = 0; da.n_pb = n_pb; da.slab = h->slab;
         const long cap0 = (h->d8 && WD == 256) ? 2L * h->dw_wg : (long)h->dw_wg;      // k_dw0_8<256>: two workgroups per CU
-        int n_wg0 = (int)(n_pb < cap0 ? n_pb : cap0);
-        rc = h->d8 ? launch_dw_first8(h, da, n_wg0) : launch_dw_first(h, da, n_wg0);
-        L.done();
-        if (rc) return rc;
-        ra.n_wg = n_wg0;
+        ra.n_wg = (int)(n_pb < cap0 ? n_pb : cap0);
         ra.slab_rows = WD; ra.slab_cols = 32; ra.rows_out = WD; ra.cols_out = 2; ra.mode = 1;
+        Launch L(h, K_DW_FIRST, 4.0 * WD * npx, WD * (h->d8 ? 1.0 : 2.0) * npx);
+        SF_TRY(launch_dw_first(h, da, ra.n_wg));
       }
-      {
-        const int n = ra.rows_out * ra.cols_out + ra.rows_out;
-        Launch L(h, K_REDUCE, 0, (double)n_wg * n * 4.0);
-        if (l > 0 && l < D - 1) {   // slab layout == flat gradient layout [W | b]
-          const int n4 = n / 4;
-          hipLaunchKernelGGL(k_reduce_vec, dim3((n4 + 7) / 8), dim3(256), 0, h->stream, (const float*)h->slab,
-                             n_wg, (long)n, n4, h->grads + h->off_w[l], (int)ra.accumulate, ra.scale, ra.scale_dev, ra.scale2_dev);
-        } else {
-          hipLaunchKernelGGL(k_reduce, dim3((n + 15) / 16), dim3(256), 0, h->stream, ra);
-        }
-        L.done();
-        HIPCHK(hipGetLastError());
-      }
+      const int n = ra.rows_out * ra.cols_out + ra.rows_out;
+      Launch L(h, K_REDUCE, 0, (double)n_wg * n * 4.0);
+      if (l > 0 && !last)   // slab layout == flat gradient layout [W | b]
+        SF_TRY(launch(h, k_reduce_vec, (n / 4 + 7) / 8, 256, 0, h->slab, n_wg, n, n / 4, h->grads + h->off_w[l], ra.accumulate,
+                      ra.scale, ra.scale_dev, ra.scale2_dev));
+      else SF_TRY(launch_reduce(h, ra));
     }
-    (void)KS;
   }
-  if ((want_sse || train) && !h->ext_dout) {
-    Launch L(h, K_SSE, 0, (double)sse_off * 4);
-    hipLaunchKernelGGL(k_sse_reduce, dim3(1), dim3(256), 0, h->stream, (const float*)h->sse_part, (int)sse_off,
-                       h->sse_dev, h->replay ? h->loss_tab : h->loss_dst, (const int*)(h->replay ? h->iter_dev : h->iter_dev + 2));
-    L.done();
-    HIPCHK(hipGetLastError());
-  }
+  if ((want_sse || train) && !h->ext_dout) SF_TRY(launch_sse_reduce(h, sse_off));
   return SF_OK;
 }
 
@@ -1262,17 +1187,14 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = 
 //   -> per chunk and sub-network: training forward, k_wv_inject, backward.
 // Then the fixed-order reduction of the compose partials into the handle's SSE.
 int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
-  int rc = refresh_images(h);   // (also points the sub-handles at the current stream)
-  if (rc) return rc;
+  SF_TRY(refresh_images(h));   // (also points the sub-handles at the current stream)
   wv_sync(h);
   sf_engine* const sub[2] = {h->wv_sub[0], h->wv_sub[1]};
   const long nn = sub[0]->npix, HH = h->npix;
   const bool one = nn <= sub[0]->chunk_px;
   float* const p_sub[2] = {h->wv_pred, h->wv_pred + nn * 3};
-  for (int s = 0; s < 2; ++s) {
-    rc = train && one ? run_pass(sub[s], true, p_sub[s], false, kPassFwd) : run_pass(sub[s], false, p_sub[s], false);
-    if (rc) return rc;
-  }
+  for (int s = 0; s < 2; ++s)
+    SF_TRY(train && one ? run_pass(sub[s], true, p_sub[s], false, kPassFwd) : run_pass(sub[s], false, p_sub[s], false));
   WvArgs a;
   memset(&a, 0, sizeof(a));
   a.H = h->cfg.height; a.n = h->wv_n; a.up = h->wv_up;
@@ -1282,53 +1204,37 @@ int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
   a.gscale = (float)(2.0 / (3.0 * h->n_total));
   a.dscale = 0.5f * sub[0]->gpre;
   a.dfac_lf = sub[0]->dfac_out; a.dfac_hf = sub[1]->dfac_out;   // (null for a linear output layer)
-  const unsigned n_cwg = (unsigned)((HH + kWvThreads - 1) / kWvThreads);
+  auto wv_grid = [](long n) { return (unsigned)((n + kWvThreads - 1) / kWvThreads); };
+  const unsigned n_cwg = wv_grid(HH);
   {
     Launch L(h, K_WV_COMPOSE, 0, (double)HH * 4.0 * (3.0 + (a.img ? 3.0 : 0.0) + (pred ? 3.0 : 0.0) + (train ? 3.0 : 0.0)));
-    hipLaunchKernelGGL(k_wv_compose, dim3(n_cwg), dim3(kWvThreads), 0, h->stream, a);
-    L.done();
-    HIPCHK(hipGetLastError());
+    SF_TRY(launch(h, k_wv_compose, n_cwg, kWvThreads, 0, a));
   }
   if (train) {
     if (one) { a.dl_lf = sub[0]->Dlast; a.dl_hf = sub[1]->Dlast; }
     else { a.gl_lf = h->wv_gl; a.gl_hf = h->wv_gl + nn * 3; }
     {
       Launch L(h, K_WV_ADJOINT, 0, (double)nn * (52.0 * 8.0 + (one ? 32.0 : 24.0)));
-      hipLaunchKernelGGL(k_wv_adjoint, dim3((unsigned)((nn + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0, h->stream, a);
-      L.done();
-      HIPCHK(hipGetLastError());
+      SF_TRY(launch(h, k_wv_adjoint, wv_grid(nn), kWvThreads, 0, a));
     }
     if (one) {
-      for (int s = 0; s < 2; ++s) {
-        rc = run_pass(sub[s], true, nullptr, false, kPassBwd);
-        if (rc) return rc;
-      }
+      for (int s = 0; s < 2; ++s) SF_TRY(run_pass(sub[s], true, nullptr, false, kPassBwd));
     } else {
-      const long n_chunks = (nn + sub[0]->chunk_px - 1) / sub[0]->chunk_px;
-      for (long c = 0; c < n_chunks; ++c) {
-        const long pix0 = c * sub[0]->chunk_px, px = std::min(sub[0]->chunk_px, nn - pix0);
+      for (long c = 0; c < n_chunks(nn, sub[0]->chunk_px); ++c) {
+        const Chunk k = chunk_at(c, nn, sub[0]->chunk_px);
         for (int s = 0; s < 2; ++s) {
-          rc = run_pass(sub[s], true, nullptr, false, kPassFwd, c, c + 1);
-          if (rc) return rc;
-          Launch L(h, K_WV_INJECT, 0, (double)px * 28.0);
-          hipLaunchKernelGGL(k_wv_inject, dim3((unsigned)((px + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0,
-                             h->stream, (const float*)(h->wv_gl + (size_t)s * nn * 3), (const float*)sub[s]->dfac_out, pix0,
-                             px, sub[s]->Dlast);
-          L.done();
-          HIPCHK(hipGetLastError());
-          rc = run_pass(sub[s], true, nullptr, false, kPassBwd, c, c + 1);
-          if (rc) return rc;
+          SF_TRY(run_pass(sub[s], true, nullptr, false, kPassFwd, c, c + 1));
+          {
+            Launch L(h, K_WV_INJECT, 0, (double)k.px * 28.0);
+            SF_TRY(launch(h, k_wv_inject, wv_grid(k.px), kWvThreads, 0, h->wv_gl + (size_t)s * nn * 3, sub[s]->dfac_out, k.pix0,
+                          k.px, sub[s]->Dlast));
+          }
+          SF_TRY(run_pass(sub[s], true, nullptr, false, kPassBwd, c, c + 1));
         }
       }
     }
   }
-  if (want_sse || train) {
-    Launch L(h, K_SSE, 0, (double)n_cwg * 4);
-    hipLaunchKernelGGL(k_sse_reduce, dim3(1), dim3(256), 0, h->stream, (const float*)h->sse_part, (int)n_cwg,
-                       h->sse_dev, h->replay ? h->loss_tab : h->loss_dst, (const int*)(h->replay ? h->iter_dev : h->iter_dev + 2));
-    L.done();
-    HIPCHK(hipGetLastError());
-  }
+  if (want_sse || train) SF_TRY(launch_sse_reduce(h, n_cwg));
   return SF_OK;
 }
 
@@ -1344,9 +1250,7 @@ int feather_materialise(sf_engine* h) {
   const FthArgs& a = h->fth;
   const dim3 grid((unsigned)((a.rows_used + kFthTile - 1) / kFthTile), (unsigned)((a.n + kFthTile - 1) / kFthTile));
   Launch L(h, K_FTH_MAT, 2.0 * a.rows_used * a.n * a.m, 4.0 * (2.0 * a.n * a.m + 2.0 * a.P));
-  hipLaunchKernelGGL(k_fth_mat, grid, dim3(256), 0, h->stream, a);
-  L.done();
-  HIPCHK(hipGetLastError());
+  SF_TRY(launch(h, k_fth_mat, grid, 256, 0, a));
   h->images_dirty = true;
   return SF_OK;
 }
@@ -1356,16 +1260,13 @@ int feather_adjoint(sf_engine* h) {
   const FthArgs& a = h->fth;
   {
     Launch L(h, K_FTH_GRAD, 2.0 * a.P, 4.0 * 4.0 * a.P);
-    hipLaunchKernelGGL(k_fth_grad, dim3((unsigned)(a.g_blocks + a.nchunks)), dim3(256), 0, h->stream, a);
-    L.done();
+    SF_TRY(launch(h, k_fth_grad, a.g_blocks + a.nchunks, 256, 0, a));
   }
   {
     const int t2 = (a.m + kFthTile - 1) / kFthTile * a.t2n;
     Launch L(h, K_FTH_DV, 2.0 * (double)a.n * a.m * (a.n + a.rows_used), 4.0 * ((double)a.n * a.n + 4.0 * a.n * a.m));
-    hipLaunchKernelGGL(k_fth_dv, dim3((unsigned)(a.t1 + t2 + 1)), dim3(256), 0, h->stream, a);
-    L.done();
+    SF_TRY(launch(h, k_fth_dv, a.t1 + t2 + 1, 256, 0, a));
   }
-  HIPCHK(hipGetLastError());
   h->fth_fresh = true;
   return SF_OK;
 }
@@ -1817,15 +1718,11 @@ int sf_wavelet_debug(sf_handle* h, int32_t which, const float* in0, const float*
   a.dscale = 1.0f;
   if (which == 0) {
     a.lf = in0; a.hf = in1; a.img = img; a.pred = out0; a.g = img ? out1 : nullptr; a.sse_part = h->sse_part;
-    hipLaunchKernelGGL(k_wv_compose, dim3((unsigned)((h->npix + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0,
-                       h->stream, a);
-  } else {
-    a.g = const_cast<float*>(in0); a.gl_lf = out0; a.gl_hf = out1;
-    const long nn = (long)h->wv_n * h->wv_n;
-    hipLaunchKernelGGL(k_wv_adjoint, dim3((unsigned)((nn + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0, h->stream, a);
+    return launch(h, k_wv_compose, (h->npix + kWvThreads - 1) / kWvThreads, kWvThreads, 0, a);
   }
-  HIPCHK(hipGetLastError());
-  return SF_OK;
+  a.g = const_cast<float*>(in0); a.gl_lf = out0; a.gl_hf = out1;
+  const long nn = (long)h->wv_n * h->wv_n;
+  return launch(h, k_wv_adjoint, (nn + kWvThreads - 1) / kWvThreads, kWvThreads, 0, a);
 } SF_CATCH
 
 int sf_set_encoding(sf_handle* h, const float* B_dev) try {
@@ -2151,18 +2048,17 @@ int sf_adam_step(sf_handle* h, float lr) try {
   if (h->feather) {   // adjoint -> Adam on [V1 | V2 | scalers] -> materialise: four launches
     if (!h->fth_fresh) { const int rc = feather_adjoint(h); if (rc) return rc; }
     a.p = h->fth_p; a.g = h->fth_g; a.m = h->fth_m; a.v = h->fth_v; a.mask = nullptr; a.n = h->fth_nf;
-    Launch L(h, K_FTH_ADAM, 0, (double)h->fth_nf * 28);
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((h->fth_nf + 255) / 256)), dim3(256), 0, h->stream, a);
-    L.done();
-    HIPCHK(hipGetLastError());
-    const int rc = feather_materialise(h);
-    if (rc) return rc;
+    {
+      Launch L(h, K_FTH_ADAM, 0, (double)h->fth_nf * 28);
+      SF_TRY(launch(h, k_adam, (h->fth_nf + 255) / 256, 256, 0, a));
+    }
+    SF_TRY(feather_materialise(h));
     return refresh_images(h);
   }
-  Launch L(h, K_ADAM, 0, (double)h->P * 28);
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)((h->P + 255) / 256)), dim3(256), 0, h->stream, a);
-  L.done();
-  HIPCHK(hipGetLastError());
+  {
+    Launch L(h, K_ADAM, 0, (double)h->P * 28);
+    SF_TRY(launch(h, k_adam, (h->P + 255) / 256, 256, 0, a));
+  }
   h->images_dirty = true;
   return refresh_images(h);
 } SF_CATCH
@@ -2220,7 +2116,7 @@ static int step_replay(sf_engine* h, const float* lr, int n, float* loss_out) {
     const int64_t step0 = h->step;
     rc = run_pass(h, true, nullptr, true);
     if (!rc) rc = sf_adam_step(h, 0.f);
-    if (!rc) hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, h->gstream, h->iter_dev);
+    if (!rc) rc = launch(h, k_tick, 1, 1, 0, h->iter_dev);   // (h->stream is the capturing stream here)
     h->step = step0;
     h->replay = false;
     const hipError_t e = hipStreamEndCapture(h->gstream, &graph);
@@ -2352,17 +2248,14 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
   long blocks = (n + 255) / 256;
   const long cap = 4L * h->dw_wg;
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(k_km_init, dim3(1), dim3(kKmMaxK), 0, h->stream, (const float*)centers_dev, (int)K, (long)n, h->km_ws);
+  SF_TRY(launch(h, k_km_init, 1, kKmMaxK, 0, centers_dev, K, n, h->km_ws));
   for (int it = 0; it < iter_limit; ++it) {
-    hipLaunchKernelGGL(k_km_assign, dim3((unsigned)blocks), dim3(256), 0, h->stream, w_dev, (long)n, (const float*)centers_dev, (int)K, h->km_ws);
-    hipLaunchKernelGGL(k_km_update, dim3(1), dim3(kKmMaxK), 0, h->stream, centers_dev, (int)K, h->km_ws, tol);
+    SF_TRY(launch(h, k_km_assign, blocks, 256, 0, w_dev, n, centers_dev, K, h->km_ws));
+    SF_TRY(launch(h, k_km_update, 1, kKmMaxK, 0, centers_dev, K, h->km_ws, tol));
   }
-  hipLaunchKernelGGL(k_km_finish, dim3(1), dim3(kKmMaxK), 0, h->stream, (const float*)centers_dev, (int)K, h->km_ws, centroids_dev,
-                     (int)centroids_cap, n_centroids_dev);
+  SF_TRY(launch(h, k_km_finish, 1, kKmMaxK, 0, centers_dev, K, h->km_ws, centroids_dev, centroids_cap, n_centroids_dev));
   if (labels_dev || new_weight_dev)
-    hipLaunchKernelGGL(k_km_predict, dim3((unsigned)blocks), dim3(256), 0, h->stream, w_dev, (long)n, (const float*)centroids_dev,
-                       (const KmWs*)h->km_ws, (long long*)labels_dev, new_weight_dev);
-  HIPCHK(hipGetLastError());
+    SF_TRY(launch(h, k_km_predict, blocks, 256, 0, w_dev, n, centroids_dev, h->km_ws, (long long*)labels_dev, new_weight_dev));
   return SF_OK;
 } SF_CATCH
 

@@ -1,5 +1,5 @@
 // siren_render.hip — the inference-only path of the engine: sf_render_create / sf_render (include/siren_fit.h).
-// (sf_render on a FourierNet handle: fourier_render.hip.)
+// (sf_render on a FourierNet handle: render_fourier, fourier_render.hip.)
 //
 // A decoder needs the picture, not a training step.  The kernels are the RENDER instantiations of k_fwd<WD> and k_fwd_pipe
 // (siren_kernels.hip): the evaluation forward (no phase stores, so the pipeline's counted waits are those of TRAIN = false)
@@ -72,47 +72,19 @@ DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32
 
 namespace {
 
-template <int WD>
-int launch_render_t(sf_engine* h, const FwdArgs& a, int n_super) {
-  const size_t lds = fwd_lds_bytes(WD);
-  if (h->cfg.compute_dtype == SF_F16) {
-    int rc = set_lds(k_fwd<WD, OpF16, false, false, true>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_fwd<WD, OpF16, false, false, true>), dim3(n_super), dim3(512), lds, h->stream, a);
-  } else {
-    int rc = set_lds(k_fwd<WD, OpBF16, false, false, true>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_fwd<WD, OpBF16, false, false, true>), dim3(n_super), dim3(512), lds, h->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-int launch_render_pipe(sf_engine* h, const FwdArgs& a, int n_wg) {
-  const size_t lds = (size_t)FwdGeom(256).PIECES * 1024 + (size_t)(256 / 32) * 1024 + 64;   // as launch_fwd_pipe
-  if (h->cfg.compute_dtype == SF_F16) {
-    int rc = set_lds(k_fwd_pipe<OpF16, false, false, SF_FWD_PD, true>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_fwd_pipe<OpF16, false, false, SF_FWD_PD, true>), dim3(n_wg), dim3(512), lds, h->stream, a);
-  } else {
-    int rc = set_lds(k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, true>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, true>), dim3(n_wg), dim3(512), lds, h->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  return SF_OK;
-}
-// the kernel family sf_forward picks for the handle (fwd_is_pipe), in its RENDER form
+// the kernel family sf_forward picks for the handle (fwd_is_pipe), in its RENDER form, on n_wg workgroups (fwd_grid)
 int launch_render(sf_engine* h, const FwdArgs& a, int n_wg) {
-  switch (h->WD) {
-    case 32: return launch_render_t<32>(h, a, n_wg);
-    case 64: return launch_render_t<64>(h, a, n_wg);
-    case 128: return launch_render_t<128>(h, a, n_wg);
-    case 256: return fwd_is_pipe(h) ? launch_render_pipe(h, a, n_wg) : launch_render_t<256>(h, a, n_wg);
-  }
-  return fail(SF_ERR_INVALID, "unsupported hidden width");
+  return with_op(h, [&](auto op) {
+    using OP = decltype(op);
+    if (fwd_is_pipe(h)) return launch(h, k_fwd_pipe<OP, false, false, SF_FWD_PD, true>, n_wg, 512, fwd_pipe_lds_bytes(), a);
+    return with_width(h, [&](auto wd) {
+      constexpr int WD = decltype(wd)::value;
+      return launch(h, k_fwd<WD, OP, false, false, true>, n_wg, 512, fwd_lds_bytes(WD), a);
+    });
+  });
 }
 
-int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred);   // fourier_render.hip: the RENDER form of k_ff_fwd
+int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred);   // fourier_render.hip, included last: the RENDER form of k_ff_fwd
 
 }  // namespace
 
@@ -132,22 +104,16 @@ int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try {
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   if (h->fourier) return render_fourier(h, rgb8, pred);
   DevGuard dev_guard(h->cfg.device);
-  int rc = refresh_images(h);
-  if (rc) return rc;
-  const long n_chunks = (h->npix + h->chunk_px - 1) / h->chunk_px;
-  for (long c = 0; c < n_chunks; ++c) {
-    const long pix0 = c * h->chunk_px;   // a multiple of 256: every wave's 32-pixel block starts on a dword of rgb8
-    long px = h->npix - pix0;
-    if (px > h->chunk_px) px = h->chunk_px;
-    const int n_super = (int)((px + kSuper - 1) / kSuper);
-    FwdArgs fa = fwd_args_base(h, pix0, n_super);
+  SF_TRY(refresh_images(h));
+  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
+    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+    const int n_super = k.n_super;
+    FwdArgs fa = fwd_args_base(h, k.pix0, n_super);
     fa.pred = pred;
     fa.rgb8 = rgb8;
     const double out_bytes = (pred ? 4.0 : 0.0) + (rgb8 ? 1.0 : 0.0);
     Launch L(h, K_RENDER, flops_fwd_px(h) * n_super * (double)kSuper, n_super * (double)kSuper * h->cfg.out_features * out_bytes);
-    rc = launch_render(h, fa, fwd_grid(h, n_super));
-    L.done();
-    if (rc) return rc;
+    SF_TRY(launch_render(h, fa, fwd_grid(h, n_super)));
   }
   return SF_OK;
 } SF_CATCH

@@ -160,8 +160,7 @@ int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, in
     return fail(SF_ERR_INVALID, "sf_wavelet_render: the window is larger than the max_rows x max_cols the handle was created for");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   DevGuard dev_guard(h->cfg.device);
-  int rc = refresh_images(h);   // (also points the sub-handles at the current stream and profiler)
-  if (rc) return rc;
+  SF_TRY(refresh_images(h));   // (also points the sub-handles at the current stream and profiler)
   wv_sync(h);
   int i0, i1, j0, j1;
   wv_coeff_span(row0, row1, H, &i0, &i1);
@@ -174,20 +173,16 @@ int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, in
   float* const p_sub[2] = {h->wv_pred, h->wv_pred + nn * 3};
   for (int s = 0; s < 2; ++s) {
     sf_engine* e = h->wv_sub[s];
-    const long n_chunks = (nn + e->chunk_px - 1) / e->chunk_px;
-    for (long c = 0; c < n_chunks; ++c) {
-      const long pix0 = c * e->chunk_px;
-      const long px = std::min(e->chunk_px, nn - pix0);
-      const int n_super = (int)((px + kSuper - 1) / kSuper);
-      FwdArgs fa = fwd_args_base(e, pix0, n_super);
+    for (long c = 0; c < n_chunks(nn, e->chunk_px); ++c) {
+      const Chunk k = chunk_at(c, nn, e->chunk_px);
+      const int n_super = k.n_super;
+      FwdArgs fa = fwd_args_base(e, k.pix0, n_super);
       // the sub-grid of this window: its rows / columns are slices of the full vectors, its row length is cc
       fa.gh = gh + i0; fa.gw = gw + j0; fa.row_begin = 0; fa.W = cc; fa.npix = nn;
       fa.w_magic = ((1ULL << 40) + (unsigned long long)cc - 1) / (unsigned long long)cc;
       fa.pred = p_sub[s];
       Launch L(e, K_RENDER, flops_fwd_px(e) * n_super * (double)kSuper, n_super * (double)kSuper * 3 * 4.0);
-      rc = launch_render(e, fa, fwd_grid(e, n_super));
-      L.done();
-      if (rc) return rc;
+      SF_TRY(launch_render(e, fa, fwd_grid(e, n_super)));
     }
   }
   WvRenderArgs a;
@@ -199,10 +194,7 @@ int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, in
   a.lf = p_sub[0]; a.hf = p_sub[1];
   a.pred = pred; a.rgb8 = rgb8;
   Launch L(h, K_WV_RENDER, 0, (double)a.npx * ((pred ? 12.0 : 0.0) + (rgb8 ? 3.0 : 0.0)) + (double)nn * 24.0);
-  hipLaunchKernelGGL(k_wv_render, dim3((unsigned)((a.npx + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0, h->stream, a);
-  L.done();
-  HIPCHK(hipGetLastError());
-  return SF_OK;
+  return launch(h, k_wv_render, (a.npx + kWvThreads - 1) / kWvThreads, kWvThreads, 0, a);
 } SF_CATCH
 
 }  // extern "C"
