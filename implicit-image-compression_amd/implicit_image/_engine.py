@@ -63,6 +63,62 @@ class sf_wavelet_render_config(C.Structure):
 
 _lib = None
 
+H, F, I32, I64, P = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER      # H: sf_handle*, F: device float*
+# Every entry point of include/siren_fit.h, once: name -> (group, argtypes, restype).  Every "core" symbol must be there;
+# the other groups are bound only when present, so a library built before them still loads (the feature then fails with a
+# message naming the rebuild instead of the whole engine failing).
+PROTOTYPES = {}
+
+
+def _declare(group: str, protos: dict, restype=C.c_int):
+    PROTOTYPES.update({name: (group, args, restype) for name, args in protos.items()})
+
+
+_declare("core", {"sf_last_error": []}, C.c_char_p)
+_declare("core", {
+    "sf_abi_version": [],
+    "sf_create": [P(sf_config), P(H)],
+    "sf_destroy": [H],
+    "sf_fourier_create": [P(sf_fourier_config), P(H)],
+    "sf_set_encoding": [H, F],
+    "sf_num_params": [H, P(I64)],
+    "sf_scratch_format": [H, P(I32)],
+    "sf_param_offset": [H, I32, P(I64), P(I64)],
+    "sf_set_params": [H, F], "sf_get_params": [H, F], "sf_set_masks": [H, F],
+    "sf_get_grads": [H, F], "sf_set_grads": [H, F],
+    "sf_get_adam_state": [H, F, F, P(I64)], "sf_set_adam_state": [H, F, F, I64],
+    "sf_state_ptr": [H, I32, P(C.c_void_p)],
+    "sf_sse_ptr": [H, P(C.c_void_p)],
+    "sf_debug_scratch": [H, I32, P(C.c_void_p), P(I64)],
+    "sf_debug_throw": [I32],
+    "sf_kmeans_fit": [H, F, I64, F, I32, I32, C.c_float, F, I32, C.c_void_p, C.c_void_p, F],
+    "sf_params_changed": [H],
+    "sf_set_coords": [H, F, F], "sf_set_target": [H, F],
+    "sf_forward": [H, F, P(C.c_double)],
+    "sf_forward_backward": [H, P(C.c_double)],
+    "sf_adam_step": [H, C.c_float],
+    "sf_step": [H, P(C.c_float), I32, P(C.c_float)],
+    "sf_profile_enable": [H, I32], "sf_profile_reset": [H], "sf_set_graph_replay": [H, I32],
+    "sf_profile_num_kernels": [H, P(I32)],
+    "sf_profile_get": [H, I32, P(C.c_char_p), P(C.c_double), P(I64), P(C.c_double), P(C.c_double)],
+})
+_declare("feather", {
+    "sf_feather_attach": [H, I64, I64, I32, P(I32), P(I32)],
+    "sf_feather_state_ptr": [H, I32, P(C.c_void_p), P(I64)],
+    "sf_feather_materialise": [H], "sf_feather_adjoint": [H],
+})
+_declare("wavelet", {
+    "sf_wavelet_create": [P(sf_wavelet_config), P(H)],
+    "sf_wavelet_debug": [H, I32, F, F, F, F, F],
+})
+# inference-only entry points (csrc/siren_render.hip, wavelet_render.hip, fourier_render.hip)
+_declare("render", {"sf_render_create": [P(sf_config), P(H)], "sf_render": [H, C.c_void_p, F]})
+_declare("wavelet_render", {
+    "sf_wavelet_render_create": [P(sf_wavelet_render_config), P(H)],
+    "sf_wavelet_render": [H, I32, I32, I32, I32, C.c_void_p, F],
+})
+_declare("fourier_render", {"sf_fourier_render_create": [P(sf_fourier_config), P(H)]})
+
 
 def load_library():
     """Load libsiren_fit.so once and declare the prototypes of include/siren_fit.h."""
@@ -74,92 +130,47 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python __graft_entry__.py build` (hipcc "
             "--offload-arch=gfx950). The SIREN engine has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
-    H, F, I64 = C.c_void_p, C.c_void_p, C.c_int64  # F: device float*
-    proto = {
-        "sf_create": [C.POINTER(sf_config), C.POINTER(H)],
-        "sf_destroy": [H],
-        "sf_fourier_create": [C.POINTER(sf_fourier_config), C.POINTER(H)],
-        "sf_set_encoding": [H, F],
-        "sf_abi_version": [],
-        "sf_num_params": [H, C.POINTER(I64)],
-        "sf_scratch_format": [H, C.POINTER(C.c_int32)],
-        "sf_param_offset": [H, C.c_int32, C.POINTER(I64), C.POINTER(I64)],
-        "sf_set_params": [H, F], "sf_get_params": [H, F], "sf_set_masks": [H, F],
-        "sf_get_grads": [H, F], "sf_set_grads": [H, F],
-        "sf_get_adam_state": [H, F, F, C.POINTER(I64)], "sf_set_adam_state": [H, F, F, I64],
-        "sf_state_ptr": [H, C.c_int32, C.POINTER(C.c_void_p)],
-        "sf_sse_ptr": [H, C.POINTER(C.c_void_p)],
-        "sf_debug_scratch": [H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(I64)],
-        "sf_debug_throw": [C.c_int32],
-        "sf_kmeans_fit": [H, F, I64, F, C.c_int32, C.c_int32, C.c_float, F, C.c_int32, C.c_void_p, C.c_void_p, F],
-        "sf_params_changed": [H],
-        "sf_set_coords": [H, F, F], "sf_set_target": [H, F],
-        "sf_forward": [H, F, C.POINTER(C.c_double)],
-        "sf_forward_backward": [H, C.POINTER(C.c_double)],
-        "sf_adam_step": [H, C.c_float],
-        "sf_step": [H, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)],
-        "sf_profile_enable": [H, C.c_int32], "sf_profile_reset": [H], "sf_set_graph_replay": [H, C.c_int32],
-        "sf_profile_num_kernels": [H, C.POINTER(C.c_int32)],
-        "sf_profile_get": [H, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(I64),
-                           C.POINTER(C.c_double), C.POINTER(C.c_double)],
-    }
-    for name, args in proto.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
-    # Feathermap entry points: bound only when present, so a library built before them still loads (FeatherNet then
-    # fails with a message naming the rebuild instead of the whole engine failing)
-    feather = {
-        "sf_feather_attach": [H, I64, I64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
-        "sf_feather_state_ptr": [H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(I64)],
-        "sf_feather_materialise": [H], "sf_feather_adjoint": [H],
-    }
-    # WaveletSiren entry points: the same rule
-    wavelet = {
-        "sf_wavelet_create": [C.POINTER(sf_wavelet_config), C.POINTER(H)],
-        "sf_wavelet_debug": [H, C.c_int32, F, F, F, F, F],
-    }
-    # inference-only entry points (csrc/siren_render.hip): the same rule
-    render = {
-        "sf_render_create": [C.POINTER(sf_config), C.POINTER(H)],
-        "sf_render": [H, C.c_void_p, F],
-        "sf_wavelet_render_create": [C.POINTER(sf_wavelet_render_config), C.POINTER(H)],
-        "sf_wavelet_render": [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, F],
-        "sf_fourier_render_create": [C.POINTER(sf_fourier_config), C.POINTER(H)],
-    }
-    for name, args in list(feather.items()) + list(wavelet.items()) + list(render.items()):
-        if hasattr(lib, name):
+    for name, (group, args, restype) in PROTOTYPES.items():
+        if group == "core" or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.argtypes = args
-            fn.restype = C.c_int
-    lib.sf_last_error.argtypes = []
-    lib.sf_last_error.restype = C.c_char_p
+            fn.restype = restype
     if lib.sf_abi_version() != SF_ABI_VERSION:
         raise RuntimeError("libsiren_fit.so ABI version mismatch")
     _lib = lib
     return lib
 
 
+def _has(lib, group: str) -> bool:
+    return all(hasattr(lib, name) for name, proto in PROTOTYPES.items() if proto[0] == group)
+
+
 def has_feather(lib) -> bool:
-    return all(hasattr(lib, s) for s in ("sf_feather_attach", "sf_feather_state_ptr", "sf_feather_materialise",
-                                         "sf_feather_adjoint"))
+    return _has(lib, "feather")
 
 
 def has_wavelet(lib) -> bool:
-    return all(hasattr(lib, s) for s in ("sf_wavelet_create", "sf_wavelet_debug"))
+    return _has(lib, "wavelet")
 
 
 def has_render(lib) -> bool:
-    return all(hasattr(lib, s) for s in ("sf_render_create", "sf_render"))
+    return _has(lib, "render")
 
 
 def has_wavelet_render(lib) -> bool:
-    return all(hasattr(lib, s) for s in ("sf_wavelet_render_create", "sf_wavelet_render"))
+    return _has(lib, "wavelet_render")
 
 
 def has_fourier_render(lib) -> bool:
     """sf_fourier_render_create, and with it sf_render on FourierNet handles (csrc/fourier_render.hip)"""
-    return has_render(lib) and hasattr(lib, "sf_fourier_render_create")
+    return has_render(lib) and _has(lib, "fourier_render")
+
+
+def _require(lib, has, entry: str, since: str):
+    """a library that lacks an optional group: say which entry point is missing and how to get it"""
+    if not has(lib):
+        raise RuntimeError(f"{_LIB_PATH} has no {entry} (built before {since}): rebuild it with "
+                           "`python __graft_entry__.py build`")
 
 
 def exported_symbols() -> Sequence[str]:
@@ -194,22 +205,36 @@ class SirenEngine:
     """One per-image fit on one HIP stream (one sf_handle)."""
 
     STATE = {"params": 0, "grads": 1, "exp_avg": 2, "exp_avg_sq": 3, "masks": 4}
+    # the create entry point of this class and, when it belongs to an optional group, what _require says without it
+    _CREATE, _CREATE_NEEDS = "sf_create", None
 
     def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
                  hidden_omega_0: float = 30.0, outermost_linear: bool = True, out_features: int = 3,
                  compute_dtype: str = "f16", device: int = 0, row_begin: int = 0, row_end: int = 0,
                  chunk_pixels: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, scratch_format: int = 0):
+        cfg = sf_config(height=height, width=width, row_begin=row_begin, row_end=row_end, in_features=2,
+                        out_features=out_features, hidden=hidden, depth=depth, first_omega_0=first_omega_0,
+                        hidden_omega_0=hidden_omega_0, outermost_linear=int(bool(outermost_linear)), beta1=betas[0],
+                        beta2=betas[1], eps=eps, chunk_pixels=chunk_pixels, scratch_format=scratch_format)
+        self._open(cfg, device, height, width, hidden, depth, out_features, row_begin, row_end, compute_dtype,
+                   who="SirenEngine")
+
+    def _open(self, cfg, device: int, height: int, width: int, hidden: int, depth: int, out_features: int = 3,
+              row_begin: int = 0, row_end: int = 0, compute_dtype: str = "f16", who: Optional[str] = None):
+        """The one constructor path: library, GPU, device and stream, then the handle (type(self)._CREATE on `cfg`, whose
+        abi_version / compute_dtype / device / stream are filled in here), sf_num_params and the attributes every handle has."""
         self.lib = load_library()
         if not torch.cuda.is_available():
-            raise RuntimeError("SirenEngine needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
+            raise RuntimeError(f"{who or type(self).__name__} needs a gfx950 GPU (torch.cuda.is_available() is False); "
+                               "no CPU fallback")
         self.device = torch.device("cuda", device)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        cfg = sf_config(SF_ABI_VERSION, height, width, row_begin, row_end, 2, out_features, hidden, depth,
-                        first_omega_0, hidden_omega_0, int(bool(outermost_linear)), DTYPES[compute_dtype],
-                        betas[0], betas[1], eps, device, stream, chunk_pixels, scratch_format)
+            cfg.stream = torch.cuda.current_stream(self.device).cuda_stream
+        cfg.abi_version, cfg.compute_dtype, cfg.device = SF_ABI_VERSION, DTYPES[compute_dtype], device
         self.h = C.c_void_p()
-        _check(self._create(cfg))
+        if self._CREATE_NEEDS:
+            _require(self.lib, *self._CREATE_NEEDS)
+        _check(getattr(self.lib, self._CREATE)(C.byref(cfg), C.byref(self.h)))
         n = C.c_int64()
         _check(self.lib.sf_num_params(self.h, C.byref(n)))
         self.num_params = n.value
@@ -220,21 +245,29 @@ class SirenEngine:
         self._target = None
         self._views = {}
 
-    def _create(self, cfg) -> int:
-        return self.lib.sf_create(C.byref(cfg), C.byref(self.h))
+    def _outputs(self, shape, want_u8: bool, want_pred: bool):
+        """(rgb8, pred, their device pointers) of a render call: `shape` uint8 / fp32 on this device, None where not asked"""
+        if not (want_u8 or want_pred):
+            raise ValueError("render: ask for bytes, the fp32 prediction, or both")
+        u8 = torch.empty(shape, dtype=torch.uint8, device=self.device) if want_u8 else None
+        pred = torch.empty(shape, device=self.device) if want_pred else None
+        return u8, pred, (u8.data_ptr() if want_u8 else None), (pred.data_ptr() if want_pred else None)
+
+    def _view(self, key: str, fn, *args, n: Optional[int] = None, typestr: str = "<f4") -> torch.Tensor:
+        """Cached zero-copy view of engine-owned memory: fn(h, *args, &ptr[, &count]); an entry point that reports no count
+        gets `n`"""
+        if key not in self._views:
+            p, cnt = C.c_void_p(), C.c_int64(n or 0)
+            _check(fn(self.h, *args, C.byref(p), *(() if n else (C.byref(cnt),))))
+            self._views[key] = torch.as_tensor(_DevView(p.value, cnt.value, typestr), device=self.device)
+        return self._views[key]
 
     def render(self, want_u8: bool = True, want_pred: bool = False):
         """sf_render on this handle's rows, no host sync: (rgb8 [rows, W, C] uint8 or None, pred [rows, W, C] fp32 or None).
         u8 = min(max((int)(pred * 255), 0), 255); pred is bit-identical to forward()'s."""
-        if not has_render(self.lib):
-            raise RuntimeError(f"{_LIB_PATH} has no sf_render entry point (built before the render path): rebuild it with "
-                               "`python __graft_entry__.py build`")
-        if not (want_u8 or want_pred):
-            raise ValueError("render: ask for bytes, the fp32 prediction, or both")
-        shape = (self.row_end - self.row_begin, self.width, self.out_features)
-        u8 = torch.empty(shape, dtype=torch.uint8, device=self.device) if want_u8 else None
-        pred = torch.empty(shape, device=self.device) if want_pred else None
-        _check(self.lib.sf_render(self.h, u8.data_ptr() if want_u8 else None, pred.data_ptr() if want_pred else None))
+        _require(self.lib, has_render, "sf_render entry point", "the render path")
+        u8, pred, u8_p, pred_p = self._outputs((self.row_end - self.row_begin, self.width, self.out_features), want_u8, want_pred)
+        _check(self.lib.sf_render(self.h, u8_p, pred_p))
         return u8, pred
 
     @property
@@ -263,11 +296,8 @@ class SirenEngine:
 
     def view(self, which: str) -> torch.Tensor:
         """Flat fp32 torch view (no copy) of engine state: params | grads | exp_avg | exp_avg_sq | masks."""
-        if which not in self._views:
-            p = C.c_void_p()
-            _check(self.lib.sf_state_ptr(self.h, self.STATE[which], C.byref(p)))
-            self._views[which] = torch.as_tensor(_DevView(p.value, self.num_params), device=self.device)
-        return self._views[which]
+        return self._views[which] if which in self._views else self._view(
+            which, self.lib.sf_state_ptr, self.STATE[which], n=self.num_params)
 
     def grad_view(self) -> torch.Tensor:
         """The engine's own flat fp32 gradient (zero-copy): what pixel-split ranks all-reduce in place."""
@@ -275,11 +305,7 @@ class SirenEngine:
 
     def sse_view(self) -> torch.Tensor:
         """1-element float64 view of the device scalar the last pass wrote its sum of squared residuals to."""
-        if "sse" not in self._views:
-            p = C.c_void_p()
-            _check(self.lib.sf_sse_ptr(self.h, C.byref(p)))
-            self._views["sse"] = torch.as_tensor(_DevView(p.value, 1, "<f8"), device=self.device)
-        return self._views["sse"]
+        return self._view("sse", self.lib.sf_sse_ptr, n=1, typestr="<f8")
 
     def debug_scratch(self, which: str) -> torch.Tensor:
         """uint8 view of an engine scratch tensor of the last pass: phases | deltas | dlast | slabs (tests only)."""
@@ -371,9 +397,7 @@ class SirenEngine:
     FEATHER = {"params": 0, "grads": 1, "exp_avg": 2, "exp_avg_sq": 3, "V": 4}
 
     def feather_attach(self, n: int, m: int, logical_out: Sequence[int], logical_in: Sequence[int]):
-        if not has_feather(self.lib):
-            raise RuntimeError(f"{_LIB_PATH} has no sf_feather_* entry points (built before Feathermap): rebuild it with "
-                               "`python __graft_entry__.py build`")
+        _require(self.lib, has_feather, "sf_feather_* entry points", "Feathermap")
         D = len(logical_out)
         outs, ins = (C.c_int32 * D)(*logical_out), (C.c_int32 * D)(*logical_in)
         _check(self.lib.sf_feather_attach(self.h, n, m, D, outs, ins))
@@ -382,11 +406,8 @@ class SirenEngine:
         """Flat fp32 view (no copy) of the feather state: params | grads | exp_avg | exp_avg_sq ([V1 | V2 | scalers]),
         or V (the unscaled V[0, P) of the last materialisation)."""
         key = "feather/" + which
-        if key not in self._views:
-            p, n = C.c_void_p(), C.c_int64()
-            _check(self.lib.sf_feather_state_ptr(self.h, self.FEATHER[which], C.byref(p), C.byref(n)))
-            self._views[key] = torch.as_tensor(_DevView(p.value, n.value), device=self.device)
-        return self._views[key]
+        return self._views[key] if key in self._views else self._view(
+            key, self.lib.sf_feather_state_ptr, self.FEATHER[which])
 
     def feather_materialise(self):
         _check(self.lib.sf_feather_materialise(self.h))
@@ -441,11 +462,10 @@ class RenderEngine(SirenEngine):
         super().__init__(height, width, hidden, depth, first_omega_0, hidden_omega_0, outermost_linear, out_features,
                          compute_dtype, device, row_begin, row_end, chunk_pixels)
 
-    def _create(self, cfg) -> int:
-        if not has_render(self.lib):
-            raise RuntimeError(f"{_LIB_PATH} has no sf_render_create entry point (built before the render path): rebuild it "
-                               "with `python __graft_entry__.py build`")
-        return self.lib.sf_render_create(C.byref(cfg), C.byref(self.h))
+    _CREATE, _CREATE_NEEDS = "sf_render_create", (has_render, "sf_render_create entry point", "the render path")
+
+
+_FOURIER_RENDER = (has_fourier_render, "sf_fourier_render_create entry point", "the FourierNet render path")
 
 
 class FourierEngine(SirenEngine):
@@ -455,38 +475,20 @@ class FourierEngine(SirenEngine):
 
     def __init__(self, height: int, width: int, hidden: int, n_linear: int, map_size: int, out_features: int = 3,
                  device: int = 0, chunk_pixels: int = 0, betas=(0.9, 0.999), eps: float = 1e-8):
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{type(self).__name__} needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
-        self.device = torch.device("cuda", device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        cfg = sf_fourier_config(SF_ABI_VERSION, height, width, 2, out_features, map_size, hidden, n_linear, DTYPES["f16"],
-                                betas[0], betas[1], eps, device, stream, chunk_pixels)
-        self.h = C.c_void_p()
-        _check(self._create(cfg))
-        n = C.c_int64()
-        _check(self.lib.sf_num_params(self.h, C.byref(n)))
-        self.num_params = n.value
-        self.height, self.width, self.hidden, self.depth = height, width, hidden, n_linear
+        cfg = sf_fourier_config(height=height, width=width, in_features=2, out_features=out_features, map_size=map_size,
+                                hidden=hidden, n_linear=n_linear, beta1=betas[0], beta2=betas[1], eps=eps,
+                                chunk_pixels=chunk_pixels)
+        self._open(cfg, device, height, width, hidden, n_linear, out_features)
         self.map_size = map_size
-        self.row_begin, self.row_end = 0, height
-        self.npix = height * width
-        self.out_features = out_features
-        self._target = None
-        self._views = {}
 
-    def _create(self, cfg) -> int:
-        return self.lib.sf_fourier_create(C.byref(cfg), C.byref(self.h))
+    _CREATE = "sf_fourier_create"
 
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
         _check(self.lib.sf_set_encoding(self.h, _f32_cuda(B.detach().contiguous(), 2 * (self.map_size // 2)).data_ptr()))
 
     def render(self, want_u8: bool = True, want_pred: bool = False):
-        if not has_fourier_render(self.lib):
-            raise RuntimeError(f"{_LIB_PATH} has no sf_fourier_render_create entry point (built before the FourierNet render "
-                               "path): rebuild it with `python __graft_entry__.py build`")
+        _require(self.lib, *_FOURIER_RENDER)
         return super().render(want_u8, want_pred)
 
 
@@ -501,11 +503,7 @@ class FourierRenderEngine(FourierEngine):
                  device: int = 0, chunk_pixels: int = 0):
         super().__init__(height, width, hidden, n_linear, map_size, out_features, device, chunk_pixels)
 
-    def _create(self, cfg) -> int:
-        if not has_fourier_render(self.lib):
-            raise RuntimeError(f"{_LIB_PATH} has no sf_fourier_render_create entry point (built before the FourierNet render "
-                               "path): rebuild it with `python __graft_entry__.py build`")
-        return self.lib.sf_fourier_render_create(C.byref(cfg), C.byref(self.h))
+    _CREATE, _CREATE_NEEDS = "sf_fourier_render_create", _FOURIER_RENDER
 
 
 class WaveletEngine(SirenEngine):
@@ -516,30 +514,15 @@ class WaveletEngine(SirenEngine):
     def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
                  hidden_omega_0: float = 30.0, outermost_linear: bool = True, device: int = 0, chunk_pixels: int = 0,
                  betas=(0.9, 0.999), eps: float = 1e-8, wavelet_levels: int = 1):
-        self.lib = load_library()
-        if not has_wavelet(self.lib):
-            raise RuntimeError(f"{_LIB_PATH} has no sf_wavelet_* entry points (built before WaveletSiren): rebuild it with "
-                               "`python __graft_entry__.py build`")
-        if not torch.cuda.is_available():
-            raise RuntimeError("WaveletEngine needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
-        self.device = torch.device("cuda", device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        cfg = sf_wavelet_config(SF_ABI_VERSION, height, width, 2, 3, hidden, depth, wavelet_levels, first_omega_0,
-                                hidden_omega_0, int(bool(outermost_linear)), DTYPES["f16"], betas[0], betas[1], eps, device,
-                                stream, chunk_pixels, 16)
-        self.h = C.c_void_p()
-        _check(self.lib.sf_wavelet_create(C.byref(cfg), C.byref(self.h)))
-        n = C.c_int64()
-        _check(self.lib.sf_num_params(self.h, C.byref(n)))
-        self.num_params = n.value
-        self.height, self.width, self.hidden, self.depth = height, width, hidden, depth
+        _require(load_library(), has_wavelet, "sf_wavelet_* entry points", "WaveletSiren")      # before the GPU is asked for
+        cfg = sf_wavelet_config(height=height, width=width, in_features=2, out_features=3, hidden=hidden, depth=depth,
+                                wavelet_levels=wavelet_levels, first_omega_0=first_omega_0, hidden_omega_0=hidden_omega_0,
+                                outermost_linear=int(bool(outermost_linear)), beta1=betas[0], beta2=betas[1], eps=eps,
+                                chunk_pixels=chunk_pixels, scratch_format=16)
+        self._open(cfg, device, height, width, hidden, depth, who="WaveletEngine")
         self.n = (height + 5) // 2
-        self.row_begin, self.row_end = 0, height
-        self.npix = height * width
-        self.out_features = 3
-        self._target = None
-        self._views = {}
+
+    _CREATE = "sf_wavelet_create"
 
     def set_coords(self, rows: torch.Tensor, cols: torch.Tensor):
         """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""
@@ -570,16 +553,9 @@ class WaveletEngine(SirenEngine):
 
 
 def _wavelet_render(eng, r0: int, r1: int, c0: int, c1: int, want_u8: bool, want_pred: bool):
-    if not has_wavelet_render(eng.lib):
-        raise RuntimeError(f"{_LIB_PATH} has no sf_wavelet_render entry point (built before the WaveletSiren render path): "
-                           "rebuild it with `python __graft_entry__.py build`")
-    if not (want_u8 or want_pred):
-        raise ValueError("render: ask for bytes, the fp32 prediction, or both")
-    shape = (max(r1 - r0, 0), max(c1 - c0, 0), 3)
-    u8 = torch.empty(shape, dtype=torch.uint8, device=eng.device) if want_u8 else None
-    pred = torch.empty(shape, device=eng.device) if want_pred else None
-    _check(eng.lib.sf_wavelet_render(eng.h, r0, r1, c0, c1, u8.data_ptr() if want_u8 else None,
-                                     pred.data_ptr() if want_pred else None))
+    _require(eng.lib, has_wavelet_render, "sf_wavelet_render entry point", "the WaveletSiren render path")
+    u8, pred, u8_p, pred_p = eng._outputs((max(r1 - r0, 0), max(c1 - c0, 0), 3), want_u8, want_pred)
+    _check(eng.lib.sf_wavelet_render(eng.h, r0, r1, c0, c1, u8_p, pred_p))
     return u8, pred
 
 
@@ -593,31 +569,15 @@ class WaveletRenderEngine(WaveletEngine):
     def __init__(self, height: int, hidden: int, depth: int, first_omega_0: float = 50.0, hidden_omega_0: float = 30.0,
                  outermost_linear: bool = True, compute_dtype: str = "f16", max_rows: int = 0, max_cols: int = 0,
                  device: int = 0, chunk_pixels: int = 0):
-        self.lib = load_library()
-        if not has_wavelet_render(self.lib):
-            raise RuntimeError(f"{_LIB_PATH} has no sf_wavelet_render_create entry point (built before the WaveletSiren render "
-                               "path): rebuild it with `python __graft_entry__.py build`")
-        if not torch.cuda.is_available():
-            raise RuntimeError("WaveletRenderEngine needs a gfx950 GPU (torch.cuda.is_available() is False); no CPU fallback")
-        self.device = torch.device("cuda", device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        cfg = sf_wavelet_render_config(SF_ABI_VERSION, height, max_rows, max_cols, hidden, depth, first_omega_0,
-                                       hidden_omega_0, int(bool(outermost_linear)), DTYPES[compute_dtype], device, stream,
-                                       chunk_pixels)
-        self.h = C.c_void_p()
-        _check(self.lib.sf_wavelet_render_create(C.byref(cfg), C.byref(self.h)))
-        n = C.c_int64()
-        _check(self.lib.sf_num_params(self.h, C.byref(n)))
-        self.num_params = n.value
-        self.height, self.width, self.hidden, self.depth = height, height, hidden, depth
+        _require(load_library(), has_wavelet_render, "sf_wavelet_render_create entry point", "the WaveletSiren render path")
+        cfg = sf_wavelet_render_config(height=height, max_rows=max_rows, max_cols=max_cols, hidden=hidden, depth=depth,
+                                       first_omega_0=first_omega_0, hidden_omega_0=hidden_omega_0,
+                                       outermost_linear=int(bool(outermost_linear)), chunk_pixels=chunk_pixels)
+        self._open(cfg, device, height, height, hidden, depth, compute_dtype=compute_dtype)
         self.n = (height + 5) // 2
         self.max_rows, self.max_cols = max_rows or height, max_cols or height
-        self.row_begin, self.row_end = 0, height
-        self.npix = height * height
-        self.out_features = 3
-        self._target = None
-        self._views = {}
+
+    _CREATE = "sf_wavelet_render_create"
 
     def render(self, r0: int = 0, r1: Optional[int] = None, c0: int = 0, c1: Optional[int] = None, want_u8: bool = True,
                want_pred: bool = False):

@@ -47,6 +47,7 @@ import torch
 
 from .config import Cfg, _load_yaml, _parse_scalar, _set_path, _wrap
 from .data import load_img, read_ppm, write_ppm
+from .models.siren import next_kernel_width
 
 REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 DECODE_JSON = "decode.json"
@@ -216,8 +217,7 @@ def engine_width(shape: Cfg) -> int:
 def padded_width(shape: Cfg) -> Optional[int]:
     """the width the engine runs the network at: the logical width, or the next kernel width when it zero-pads (the
     models' own rule, Siren._engine_width); None above 1024"""
-    w = engine_width(shape)
-    return next((k for k in KERNEL_WIDTHS + (512, 1024) if k >= w), None)
+    return next_kernel_width(engine_width(shape), KERNEL_WIDTHS + (512, 1024))
 
 
 def render_path(shape: Cfg, height: Optional[int] = None, width: Optional[int] = None) -> Tuple[str, str]:
@@ -313,6 +313,43 @@ def flat_params(sd: Dict[str, torch.Tensor], depth: int) -> torch.Tensor:
     return torch.cat(parts).float().contiguous()
 
 
+def _render_bands(eng, load, bands: List[Tuple[int, int]], row0: int, cols: int, draw, want_pred: bool):
+    """The open / load / assemble / close skeleton of the three kernel renderers, on a handle the caller opened: load(eng)
+    puts the parameters (and what else the handle needs) in, draw(a, b) returns (u8, pred) of pixel rows [a, b) on the
+    device; every band is copied to the CPU as it comes and the handle is closed whatever happens.  uint8
+    [rows from row0 to the last band's end, cols, C] (and the fp32 prediction when asked)."""
+    try:
+        load(eng)
+        shape = (bands[-1][1] - row0, cols, eng.out_features)
+        out = torch.empty(shape, dtype=torch.uint8)
+        pred = torch.empty(shape) if want_pred else None
+        for a, b in bands:
+            u8, p = draw(a, b)
+            out[a - row0:b - row0] = u8.cpu()
+            if want_pred:
+                pred[a - row0:b - row0] = p.cpu()
+    finally:
+        eng.close()
+    return out, pred
+
+
+def _render_grid(eng, load, rows: torch.Tensor, cols: torch.Tensor, bands: List[Tuple[int, int]], want_pred: bool):
+    """Row bands of the grid rows x cols on an open sf_render handle (RenderEngine / FourierRenderEngine) made for the first
+    band's height: a band is a slice of `rows`, the last, shorter one padded with its final row and cut after the render."""
+    nb = bands[0][1] - bands[0][0]
+    cols_d = cols.float().contiguous().to(eng.device)
+
+    def draw(r0, r1):
+        rb = rows[r0:r1].float()
+        if r1 - r0 < nb:
+            rb = torch.cat([rb, rb[-1:].expand(nb - (r1 - r0))])
+        eng.set_coords(rb.contiguous().to(eng.device), cols_d)
+        u8, p = eng.render(want_u8=True, want_pred=want_pred)
+        return u8[:r1 - r0], (p[:r1 - r0] if want_pred else None)
+
+    return _render_bands(eng, load, bands, 0, cols.numel(), draw, want_pred)
+
+
 def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
                   want_pred: bool = False, device: int = 0):
     """uint8 [h, w, C] on the CPU (and the fp32 prediction when asked) of the grid rows x cols, band by band on ONE render
@@ -320,32 +357,18 @@ def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_r
     from ._engine import RenderEngine
     m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
     C = int(m.get("output_size", 3))
-    h, w = rows.numel(), cols.numel()
-    bands = plan_bands(h, w, C, band_rows)
-    nb = bands[0][1] - bands[0][0]
-    eng = RenderEngine(nb, w, padded_width(shape), int(m.depth), float(m.get("first_omega_0", 50.0)),
-                       float(m.get("hidden_omega_0", 30.0)), bool(m.get("outermost_linear", True)), C,
-                       eng_kw.get("compute_dtype", "f16"), device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
-    try:
-        dev = eng.device
+    bands = plan_bands(rows.numel(), cols.numel(), C, band_rows)
+    eng = RenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.depth),
+                       float(m.get("first_omega_0", 50.0)), float(m.get("hidden_omega_0", 30.0)),
+                       bool(m.get("outermost_linear", True)), C, eng_kw.get("compute_dtype", "f16"), device=device,
+                       chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
+
+    def load(eng):
         flat = (flat_params(sd, int(m.depth)) if padded_width(shape) == engine_width(shape)
                 else engine_flat_params(sd, shape, eng.num_params))
-        eng.set_params(flat.to(dev))
-        cols_d = cols.float().contiguous().to(dev)
-        out = torch.empty(h, w, C, dtype=torch.uint8)
-        pred = torch.empty(h, w, C) if want_pred else None
-        for r0, r1 in bands:
-            rb = rows[r0:r1].float()
-            if r1 - r0 < nb:
-                rb = torch.cat([rb, rb[-1:].expand(nb - (r1 - r0))])
-            eng.set_coords(rb.contiguous().to(dev), cols_d)
-            u8, p = eng.render(want_u8=True, want_pred=want_pred)
-            out[r0:r1] = u8[:r1 - r0].cpu()
-            if want_pred:
-                pred[r0:r1] = p[:r1 - r0].cpu()
-    finally:
-        eng.close()
-    return out, pred
+        eng.set_params(flat.to(eng.device))
+
+    return _render_grid(eng, load, rows, cols, bands, want_pred)
 
 
 def render_fourier(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
@@ -355,30 +378,16 @@ def render_fourier(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_
     height * width < 2^31 the handle needs; the last, shorter band is padded with its final row and cut after the render."""
     from ._engine import FourierRenderEngine
     m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
-    h, w = rows.numel(), cols.numel()
-    bands = plan_bands(h, w, 3, band_rows)
-    nb = bands[0][1] - bands[0][0]
-    eng = FourierRenderEngine(nb, w, padded_width(shape), int(m.get("depth", 8)) - 1, int(m.get("map_size", 128)), 3,
-                              device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
-    try:
-        dev = eng.device
-        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(dev))
-        eng.set_encoding(sd["encoding.B"].float().contiguous().to(dev))
-        cols_d = cols.float().contiguous().to(dev)
-        out = torch.empty(h, w, 3, dtype=torch.uint8)
-        pred = torch.empty(h, w, 3) if want_pred else None
-        for r0, r1 in bands:
-            rb = rows[r0:r1].float()
-            if r1 - r0 < nb:
-                rb = torch.cat([rb, rb[-1:].expand(nb - (r1 - r0))])
-            eng.set_coords(rb.contiguous().to(dev), cols_d)
-            u8, p = eng.render(want_u8=True, want_pred=want_pred)
-            out[r0:r1] = u8[:r1 - r0].cpu()
-            if want_pred:
-                pred[r0:r1] = p[:r1 - r0].cpu()
-    finally:
-        eng.close()
-    return out, pred
+    bands = plan_bands(rows.numel(), cols.numel(), 3, band_rows)
+    eng = FourierRenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.get("depth", 8)) - 1,
+                              int(m.get("map_size", 128)), 3, device=device,
+                              chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
+
+    def load(eng):
+        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(eng.device))
+        eng.set_encoding(sd["encoding.B"].float().contiguous().to(eng.device))
+
+    return _render_grid(eng, load, rows, cols, bands, want_pred)
 
 
 # ---- WaveletSiren: which coefficients a window needs, bands, the kernel path -----------------------------------
@@ -438,33 +447,21 @@ def render_wavelet(sd, shape: Cfg, H: int, r: Tuple[int, int], c: Tuple[int, int
                               float(m.get("hidden_omega_0", 50.0)), bool(m.get("outermost_linear", True)),
                               eng_kw.get("compute_dtype", "f16"), max_rows=bands[0][1] - bands[0][0], max_cols=c[1] - c[0],
                               device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
-    try:
-        dev = eng.device
-        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(dev))
-        lin = torch.linspace(0, 1, eng.n).to(dev)             # LF_grid = HF_grid = get_grid(n, n) (wavelet_siren.py:76-80)
+
+    def load(eng):
+        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(eng.device))
+        lin = torch.linspace(0, 1, eng.n).to(eng.device)      # LF_grid = HF_grid = get_grid(n, n) (wavelet_siren.py:76-80)
         eng.set_coords(lin, lin)
-        out = torch.empty(r[1] - r[0], c[1] - c[0], 3, dtype=torch.uint8)
-        pred = torch.empty(r[1] - r[0], c[1] - c[0], 3) if want_pred else None
-        for a, b in bands:
-            u8, p = eng.render(a, b, c[0], c[1], want_u8=True, want_pred=want_pred)
-            out[a - r[0]:b - r[0]] = u8.cpu()
-            if want_pred:
-                pred[a - r[0]:b - r[0]] = p.cpu()
-    finally:
-        eng.close()
-    return out, pred
+
+    return _render_bands(eng, load, bands, r[0], c[1] - c[0],
+                         lambda a, b: eng.render(a, b, c[0], c[1], want_u8=True, want_pred=want_pred), want_pred)
 
 
 def render_torch(sd, shape: Cfg, height: int, width: int, r: Tuple[int, int], c: Tuple[int, int], device: int = 0):
     """the registry model's own forward on the full height x width grid, cut to the window, bytes by to_u8"""
     from .data import get_grid
-    from .models import registry
-    m = dict(shape.mlp)
-    name = m.get("name", "siren")
     dev = torch.device("cuda", device)
-    model = registry[name](**m, small_dense_density=shape.get("small_dense_density") or 1.0, **dict(shape.get("engine") or {}))
-    model.load_state_dict(sd)
-    model = model.to(dev).eval()
+    model = registry_model(sd, shape).to(dev).eval()
     with torch.no_grad():
         pred = model(get_grid(height, width).to(dev))
     pred = pred[r[0]:r[1], c[0]:c[1]].contiguous()
@@ -509,17 +506,14 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
         check_image(H, W)                          # the "even, square" refusal, before anything touches the device
     path, why = choose_path(shape, mode, H, W)
     logging.info(f"decode: weights from {source}; {path} path ({why}); {r[1] - r[0]}x{c[1] - c[0]} of a {H}x{W} grid")
-    if path == "kernel" and name == "wavelet_siren":
-        u8, pred = render_wavelet(sd, shape, H, r, c, int(dec["band_rows"]) if dec.get("band_rows") else None,
-                                  want_pred=bool(truth), device=device)
-    elif path == "kernel" and name == "fourier":
-        rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
-        u8, pred = render_fourier(sd, shape, rows, cols, int(dec["band_rows"]) if dec.get("band_rows") else None,
-                                  want_pred=bool(truth), device=device)
-    elif path == "kernel":
-        rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
-        u8, pred = render_kernel(sd, shape, rows, cols, int(dec["band_rows"]) if dec.get("band_rows") else None,
-                                 want_pred=bool(truth), device=device)
+    if path == "kernel":
+        band_rows = int(dec["band_rows"]) if dec.get("band_rows") else None
+        if name == "wavelet_siren":
+            u8, pred = render_wavelet(sd, shape, H, r, c, band_rows, want_pred=bool(truth), device=device)
+        else:
+            rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
+            u8, pred = (render_fourier if name == "fourier" else render_kernel)(
+                sd, shape, rows, cols, band_rows, want_pred=bool(truth), device=device)
     else:
         u8, pred = render_torch(sd, shape, H, W, r, c, device=device)
     if u8.shape[-1] != 3:

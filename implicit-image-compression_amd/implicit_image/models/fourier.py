@@ -9,7 +9,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .siren import Siren
+from .siren import Siren, next_kernel_width
 
 # the reference's Masking puts the frozen encoding.B into its mask_dict and its first update_connections() fails on
 # B.grad being None (reference pipeline/masking/funcs/grow.py:87): there is no reference behaviour to reproduce
@@ -58,7 +58,7 @@ class FourierNet(Siren):
                         compute_dtype=compute_dtype, chunk_pixels=chunk_pixels, scratch_format=16)
         self.pre_pass_callbacks = []
         self.post_backward_callbacks = []
-        self._engine_width = next((w for w in self.WIDTHS if w >= hidden_size), None)
+        self._engine_width = next_kernel_width(hidden_size, self.WIDTHS)
         if self._engine_width is None:
             raise NotImplementedError(f"hidden_size {hidden_size} > 256 is not supported for FourierNet by the gfx950 engine")
         if input_size != 2 or output_size != 3 or map_size not in (64, 128, 256, 512) or not 2 <= n_linear <= 12:
@@ -102,23 +102,10 @@ class FourierNet(Siren):
             self._enc_key = key
         return eng
 
-    def _padded_index(self, device):
-        if self._pad_index is None or self._pad_index.device != device:
-            c, wp = self.cfg, self._engine_width
-            idx, off = [], 0
-            for l in range(c["n_linear"]):
-                last = l == c["n_linear"] - 1
-                fin = c["map_size"] if l == 0 else c["hidden_size"]
-                fout = c["output_size"] if last else c["hidden_size"]
-                fin_p = c["map_size"] if l == 0 else wp
-                fout_p = c["output_size"] if last else wp
-                r = torch.arange(fout, device=device)[:, None] * fin_p + torch.arange(fin, device=device)[None, :]
-                idx.append((off + r).reshape(-1))
-                off += fin_p * fout_p
-                idx.append(off + torch.arange(fout, device=device))
-                off += fout_p
-            self._pad_index = torch.cat(idx)
-        return self._pad_index
+    def _layer_fans(self):
+        c = self.cfg
+        fans = [c["map_size"]] + [c["hidden_size"]] * (c["n_linear"] - 1) + [c["output_size"]]
+        return [(fans[l], fans[l + 1], l > 0, l < c["n_linear"] - 1) for l in range(c["n_linear"])]
 
     def __deepcopy__(self, memo):
         c = self.cfg

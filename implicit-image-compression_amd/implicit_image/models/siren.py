@@ -18,6 +18,13 @@ from torch import nn
 from ..data import grid_vectors
 
 
+def next_kernel_width(hidden: int, widths) -> Optional[int]:
+    """The width the engine runs a network of logical width `hidden` at: the narrowest of `widths` (ascending: the widths
+    the kernels are instantiated for) that holds it, None above the last.  The one statement of the zero-padding rule:
+    Siren, FourierNet and decode.padded_width call it, each with its own widths."""
+    return next((w for w in widths if w >= hidden), None)
+
+
 class SineLayer(nn.Module):
     """Linear -> sin(omega_0 * z) (reference siren.py:9-68).  Holds the nn.Linear so that
     `isinstance(m, nn.Linear)` scans (masking, k-means, entropy coding) find it under `.linear`."""
@@ -40,6 +47,8 @@ class SineLayer(nn.Module):
 
 
 class Siren(nn.Module):
+    WIDTHS = (32, 64, 128, 256, 512, 1024)
+
     def __init__(self, input_size: int = 2, output_size: int = 3, depth: int = 8, hidden_size: int = 128,
                  first_omega_0: float = 50.0, hidden_omega_0: float = 50.0, outermost_linear: bool = True,
                  simulate_quantization: bool = False, small_dense_density: float = 1.0,
@@ -66,7 +75,7 @@ class Siren(nn.Module):
         # kernels); any other width (e.g. Small_Dense's int(hidden * sqrt(density)), reference siren.py:88) runs
         # zero-padded to the next one: padded neurons have zero weights and bias, output sin(0) = 0 and receive
         # exactly zero gradients, so they stay zero
-        self._engine_width = next((w for w in (32, 64, 128, 256, 512, 1024) if w >= hidden_size), None)
+        self._engine_width = next_kernel_width(hidden_size, self.WIDTHS)
         if self._engine_width is None:
             raise NotImplementedError(f"hidden_size {hidden_size} > 1024 is not supported by the gfx950 engine")
         if self._engine_width > 256 and depth < 3:
@@ -159,16 +168,20 @@ class Siren(nn.Module):
                            chunk_pixels=c["chunk_pixels"], betas=self._adam[0], eps=self._adam[1],
                            scratch_format=c["scratch_format"])
 
+    def _layer_fans(self):
+        """(fan_in, fan_out, fan_in is padded, fan_out is padded) of every layer, logical sizes: all that _padded_index
+        needs to know of a network (the hidden side of a layer runs at the engine width, the network's ends do not)"""
+        c = self.cfg
+        fans = [c["input_size"]] + [c["hidden_size"]] * (c["depth"] - 1) + [c["output_size"]]
+        return [(fans[l], fans[l + 1], l > 0, l < c["depth"] - 1) for l in range(c["depth"])]
+
     def _padded_index(self, device):
         """flat index of every logical parameter element inside the engine's (wider) flat layout"""
         if self._pad_index is None or self._pad_index.device != device:
-            c, wp = self.cfg, self._engine_width
+            wp = self._engine_width
             idx, off = [], 0
-            for l in range(c["depth"]):
-                fin = c["input_size"] if l == 0 else c["hidden_size"]
-                fout = c["output_size"] if l == c["depth"] - 1 else c["hidden_size"]
-                fin_p = c["input_size"] if l == 0 else wp
-                fout_p = c["output_size"] if l == c["depth"] - 1 else wp
+            for fin, fout, pad_in, pad_out in self._layer_fans():
+                fin_p, fout_p = (wp if pad_in else fin), (wp if pad_out else fout)
                 r = torch.arange(fout, device=device)[:, None] * fin_p + torch.arange(fin, device=device)[None, :]
                 idx.append((off + r).reshape(-1))
                 off += fin_p * fout_p

@@ -15,46 +15,12 @@ a fresh child process per handle.
 import argparse
 import json
 import os
-import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
-    sys.path.insert(0, p)
+import torch
 
-import torch  # noqa: E402
+from render_bench_common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
 
 MODELS = [(256, 8), (128, 8)]
-
-
-def device_note():
-    note = {"device": torch.cuda.get_device_name(0)}
-    # (both as torch reports them: SM clock in MHz, power_draw in the management library's own unit)
-    for k, fn in (("clock_mhz", getattr(torch.cuda, "clock_rate", None)), ("power_draw", getattr(torch.cuda, "power_draw", None))):
-        try:
-            note[k] = fn(0)
-        except Exception as e:   # (the management library is optional: say so rather than guess)
-            note[k] = f"unavailable ({type(e).__name__})"
-    return note
-
-
-def timed(fn, n):
-    out = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return out
-
-
-def stats(ms):
-    s = sorted(ms)
-    return {"median_ms": statistics.median(s), "min_ms": s[0], "max_ms": s[-1], "p10_ms": s[len(s) // 10],
-            "p90_ms": s[(len(s) * 9) // 10], "calls": len(s)}
 
 
 def time_leg(hidden, depth, S, calls, warmup):
@@ -81,13 +47,7 @@ def time_leg(hidden, depth, S, calls, warmup):
         rn.lib.sf_render(rn.h, u8.data_ptr(), None)
 
     legs = {"forward_pred": fwd_only, "forward_pred_plus_torch_bytes": fwd_bytes, "render_bytes": render}
-    for fn in legs.values():
-        timed(fn, warmup)
-    ms = {k: [] for k in legs}
-    half = max(calls // 2, 1)
-    for _ in range(2):                      # a b c a b c: no leg owns the warm (or the throttled) end of the run
-        for k, fn in legs.items():
-            ms[k] += timed(fn, half)
+    ms = alternate(legs, calls, warmup)
     same = bool(torch.equal(fwd_bytes(), u8))
     tr.close()
     rn.close()
@@ -104,15 +64,7 @@ def time_leg(hidden, depth, S, calls, warmup):
 
 def mem_child(kind, hidden, depth, S):
     from implicit_image._engine import RenderEngine, SirenEngine
-    torch.cuda.init()
-    torch.zeros(1, device="cuda")
-    torch.cuda.synchronize()
-    free0, _ = torch.cuda.mem_get_info()
-    eng = (RenderEngine if kind == "render" else SirenEngine)(S, S, hidden, depth)
-    torch.cuda.synchronize()
-    free1, _ = torch.cuda.mem_get_info()
-    eng.close()
-    print(json.dumps({"bytes": int(free0 - free1)}))
+    print_handle_bytes(lambda: (RenderEngine if kind == "render" else SirenEngine)(S, S, hidden, depth))
 
 
 def main():
@@ -134,12 +86,7 @@ def main():
     for hidden, depth in MODELS:
         for S in args.sizes:
             r = time_leg(hidden, depth, S, args.calls, args.warmup)
-            mem = {}
-            for kind in ("train", "render"):
-                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--mem-child", kind, str(hidden), str(depth), str(S)],
-                                     stdout=subprocess.PIPE, timeout=180, check=True).stdout.decode().strip().splitlines()[-1]
-                mem[f"{kind}_handle_bytes"] = json.loads(out)["bytes"]
-            r["memory"] = mem
+            mem = r["memory"] = handle_memory(__file__, hidden, depth, S)
             res["models"][f"{hidden}x{depth}@{S}"] = r
             print(json.dumps({f"{hidden}x{depth}@{S}": {"a_ms": r["forward_pred_plus_torch_bytes"]["median_ms"],
                                                         "fwd_ms": r["forward_pred"]["median_ms"],

@@ -16,45 +16,12 @@ path's handle: torch.cuda.mem_get_info before / after creation in a fresh child 
 import argparse
 import json
 import os
-import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
-    sys.path.insert(0, p)
+import torch
 
-import torch  # noqa: E402
+from render_bench_common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
 
 YAML = dict(depth=8, hidden_size=128, wavelet_levels=1, first_omega_0=50.0, hidden_omega_0=30.0, outermost_linear=True)
-
-
-def device_note():
-    note = {"device": torch.cuda.get_device_name(0)}
-    for k, fn in (("clock_mhz", getattr(torch.cuda, "clock_rate", None)), ("power_draw", getattr(torch.cuda, "power_draw", None))):
-        try:
-            note[k] = fn(0)
-        except Exception as e:   # (the management library is optional: say so rather than guess)
-            note[k] = f"unavailable ({type(e).__name__})"
-    return note
-
-
-def timed(fn, n):
-    out = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return out
-
-
-def stats(ms):
-    s = sorted(ms)
-    return {"median_ms": statistics.median(s), "min_ms": s[0], "max_ms": s[-1], "p10_ms": s[len(s) // 10],
-            "p90_ms": s[(len(s) * 9) // 10], "calls": len(s)}
 
 
 def time_leg(S, calls, warmup):
@@ -80,13 +47,7 @@ def time_leg(S, calls, warmup):
         rn.lib.sf_wavelet_render(rn.h, 0, S, 0, S, u8.data_ptr(), None)
 
     legs = {"model_forward_plus_torch_bytes": model_bytes, "wavelet_render_bytes": render}
-    for fn in legs.values():
-        timed(fn, warmup)
-    ms = {k: [] for k in legs}
-    half = max(calls // 2, 1)
-    for _ in range(2):                      # a b a b: no leg owns the warm (or the throttled) end of the run
-        for k, fn in legs.items():
-            ms[k] += timed(fn, half)
+    ms = alternate(legs, calls, warmup)
     same = bool(torch.equal(model_bytes(), u8))
     rn.profile(True)
     rn.profile_reset()
@@ -110,15 +71,7 @@ def time_leg(S, calls, warmup):
 
 def mem_child(kind, S):
     from implicit_image._engine import WaveletEngine, WaveletRenderEngine
-    torch.cuda.init()
-    torch.zeros(1, device="cuda")
-    torch.cuda.synchronize()
-    free0, _ = torch.cuda.mem_get_info()
-    eng = WaveletRenderEngine(S, 128, 8) if kind == "render" else WaveletEngine(S, S, 128, 8)
-    torch.cuda.synchronize()
-    free1, _ = torch.cuda.mem_get_info()
-    eng.close()
-    print(json.dumps({"bytes": int(free0 - free1)}))
+    print_handle_bytes(lambda: WaveletRenderEngine(S, 128, 8) if kind == "render" else WaveletEngine(S, S, 128, 8))
 
 
 def main():
@@ -139,12 +92,7 @@ def main():
            "before": device_note(), "sizes": {}}
     for S in args.sizes:
         r = time_leg(S, args.calls, args.warmup)
-        mem = {}
-        for kind in ("train", "render"):
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--mem-child", kind, str(S)],
-                                 stdout=subprocess.PIPE, timeout=180, check=True).stdout.decode().strip().splitlines()[-1]
-            mem[f"{kind}_handle_bytes"] = json.loads(out)["bytes"]
-        r["memory"] = mem
+        mem = r["memory"] = handle_memory(__file__, S)
         res["sizes"][str(S)] = r
         print(json.dumps({S: {"a_ms": r["model_forward_plus_torch_bytes"]["median_ms"],
                               "a_p90_ms": r["model_forward_plus_torch_bytes"]["p90_ms"],
