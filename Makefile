@@ -14,7 +14,7 @@ build:
 fit: build
 	PYTHONPATH=$(PKG) $(PYTHON) -m implicit_image.fit $(KWARGS)
 
-## decode: render a run directory written by fit to a PPM, e.g. make decode KWARGS="decode.dir=outputs/synthetic/siren_synthetic/default decode.truth=synthetic"
+## decode: render a run directory written by fit to a PPM, e.g. make decode KWARGS="decode.dir=outputs/synthetic/siren_synthetic/default decode.truth=synthetic" (decode.bits=16: 16 bits per sample, P6 with maxval 65535)
 decode: build
 	PYTHONPATH=$(PKG) $(PYTHON) -m implicit_image.decode $(KWARGS)
 

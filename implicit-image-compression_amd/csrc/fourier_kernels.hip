@@ -51,7 +51,10 @@ struct FfArgs {
   _Float16* Z;                        // [3][cp] dL/dz of the output layer (pre-scaled)
   const float* tgt;                   // target image rows [npix][3] (may be null: prediction only)
   float* pred;                        // [npix][3] or null
-  uint8_t* rgb8;                      // RENDER only: [npix][3] bytes or null (4-byte aligned), min(max((int)(pred * 255), 0), 255)
+  union {                             // RENDER only: [npix][3] samples or null (4-byte aligned)
+    uint8_t* rgb8;                    //   BITS = 8:  bytes, min(max((int)(pred * 255), 0), 255)
+    uint16_t* rgb16;                  //   BITS = 16: native-endian uint16_t, min(max((int)(pred * 65535), 0), 65535)
+  };
   float* sse_part;                    // one partial per workgroup
   float gscale;                       // gpre / (3 H W)
 };
@@ -126,10 +129,13 @@ DEV float ff_block_sum(float v, float* sh) {
 
 // the byte tail of the render kernels (siren_render.hip): lane d gathers dword d of the wave's 32-pixel block and stores it
 DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32_t mine, int lane);
+// its 16-bit form: the lane's pixel in two registers (channel 0 | channel 1 << 16, channel 2), lane d stores dword d
+DEV void render_store_block16(uint16_t* rgb16, long px0, long npix, int nout, uint32_t mine0, uint32_t mine1, int lane);
 
-template <int WD, bool TRAIN, bool RENDER = false>
+template <int WD, bool TRAIN, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
   static_assert(!(TRAIN && RENDER), "the render form spills nothing");
+  static_assert(BITS == 8 || (RENDER && BITS == 16), "BITS: the sample width of the RENDER form, 8 or 16");
   constexpr int NT = WD / 32, KS = WD / 16, KSL = ff_ksl(WD);
   extern __shared__ u32x4 lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 31, hh = lane >> 5;
@@ -201,22 +207,36 @@ __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
 #pragma unroll
   for (int s = 0; s < KS; ++s) o[0] = OpF16::mfma(lds[s * 64 + lane], fr[s], o[0]);
   if constexpr (RENDER) {
-    // no target, no residual, no dz, no Z store, no workgroup sum: the sigmoid of k_ff_fwd<WD, false>, then bytes
+    // no target, no residual, no dz, no Z store, no workgroup sum: the sigmoid of k_ff_fwd<WD, false>, then bytes (BITS = 8)
+    // or 16-bit samples (BITS = 16)
     uint32_t mine = 0u;   // this lane's pixel: channel t in byte t (the upper lane half holds padded rows: never selected)
+    uint32_t mine1 = 0u;  // BITS = 16: channels 0 and 1 in the halves of `mine`, channel 2 here
     if (hh == 0) {
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         const float z = o[0][t];
         const float sg = 1.0f / (1.0f + __expf(-z));
         if (valid && a.pred) a.pred[p * 3 + t] = sg;
-        int q = (int)(sg * 255.0f);   // v_cvt_i32_f32: toward zero
-        q = q < 0 ? 0 : (q > 255 ? 255 : q);
-        mine |= (uint32_t)q << (8 * t);
+        if constexpr (BITS == 16) {
+          int q = (int)(sg * 65535.0f);   // v_cvt_i32_f32: toward zero
+          q = q < 0 ? 0 : (q > 65535 ? 65535 : q);
+          if (t < 2) mine |= (uint32_t)q << (16 * t); else mine1 = (uint32_t)q;
+        } else {
+          int q = (int)(sg * 255.0f);   // v_cvt_i32_f32: toward zero
+          q = q < 0 ? 0 : (q > 255 ? 255 : q);
+          mine |= (uint32_t)q << (8 * t);
+        }
       }
     }
     // (all 64 lanes: the gather is a cross-lane read.)  pix0 is a multiple of 256 and the wave's first pixel one of 32:
-    // the 96-byte block starts on a dword; pixels >= npix store nothing
-    if (a.rgb8) render_store_block(a.rgb8, a.pix0 + (long)blockIdx.x * 256 + wave * 32, a.npix, 3, mine, lane);
+    // the 96-byte (192-byte) block starts on a dword; pixels >= npix store nothing
+    const long px0 = a.pix0 + (long)blockIdx.x * 256 + wave * 32;
+    if constexpr (BITS == 16) {
+      if (a.rgb16) render_store_block16(a.rgb16, px0, a.npix, 3, mine, mine1, lane);
+    } else {
+      (void)mine1;
+      if (a.rgb8) render_store_block(a.rgb8, px0, a.npix, 3, mine, lane);
+    }
   } else {
     __shared__ float sh_sse[kFfThreads / 64];
     float sse = 0.f;

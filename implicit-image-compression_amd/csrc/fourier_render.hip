@@ -10,7 +10,8 @@
 //
 // Bytes: u8 = min(max((int)(pred * 255.0f), 0), 255), fwd_render_out's formula; the pack / gather / store tail is
 // render_store_block (siren_render.hip): a wave owns 32 consecutive pixels = 96 consecutive bytes on a dword boundary,
-// lane d < 24 stores dword d, only the picture's last ragged dword goes out byte by byte.
+// lane d < 24 stores dword d, only the picture's last ragged dword goes out byte by byte.  sf_render16 runs the BITS = 16
+// form: u16 = min(max((int)(pred * 65535.0f), 0), 65535) through render_store_block16, lane d < 48 stores dword d.
 //
 // A render handle (create_fourier(.., render = true), siren_fit.hip) holds the parameters, the weight images, encoding.B
 // and the two coordinate vectors: none of the [D-1][WD][chunk] activation / gradient planes, the slab, gradients, Adam
@@ -20,8 +21,9 @@
 
 namespace {
 
-// sf_render on a FourierNet handle (render or training), after its argument checks: chunked as run_pass_fourier
-int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred) {
+// sf_render / sf_render16 on a FourierNet handle (render or training), after their argument checks: chunked as
+// run_pass_fourier.  out: bits / 8 bytes per sample
+int render_fourier(sf_engine* h, void* out, int bits, float* pred) {
   if (!h->have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
   DevGuard dev_guard(h->cfg.device);
   SF_TRY(refresh_images(h));
@@ -30,10 +32,10 @@ int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred) {
     const Chunk k = chunk_at(c, h->npix, h->chunk_px);
     const double npx = (double)k.n_super * kSuper;
     FfArgs fa = ff_args_base(h, k.pix0);
-    fa.pred = pred; fa.rgb8 = rgb8;
+    fa.pred = pred; fa.rgb8 = (uint8_t*)out;   // (a.rgb16 of the 16-bit form: the same member)
     Launch L(h, K_FF_RENDER, 2.0 * ((double)MS * WD + (double)(D - 2) * WD * WD + 32.0 * WD) * npx,
-             npx * ((pred ? 12.0 : 0.0) + (rgb8 ? 3.0 : 0.0)));
-    SF_TRY(launch_ff(h, fa, k.n_super, kFfRender));
+             npx * ((pred ? 12.0 : 0.0) + (out ? 3.0 * (bits / 8) : 0.0)));
+    SF_TRY(launch_ff(h, fa, k.n_super, bits == 16 ? kFfRender16 : kFfRender));
   }
   return SF_OK;
 }

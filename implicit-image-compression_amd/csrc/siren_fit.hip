@@ -973,13 +973,15 @@ FfArgs ff_args_base(const sf_engine* h, long pix0) {
   for (int l = 0; l < h->D; ++l) { fa.img_f[l] = h->ff_img_f[l]; fa.img_b[l] = h->ff_img_b[l]; fa.off_b[l] = h->off_b[l]; }
   return fa;
 }
-enum FfKernel { kFfEval, kFfTrain, kFfBwd, kFfRender };   // k_ff_fwd<WD, false>, k_ff_fwd<WD, true>, k_ff_bwd<WD>, k_ff_fwd<WD, false, true>
+// k_ff_fwd<WD, false>, k_ff_fwd<WD, true>, k_ff_bwd<WD>, k_ff_fwd<WD, false, true>, k_ff_fwd<WD, false, true, 16>
+enum FfKernel { kFfEval, kFfTrain, kFfBwd, kFfRender, kFfRender16 };
 int launch_ff(sf_engine* h, const FfArgs& a, int n_super, FfKernel which) {
   return with_width(h, [&](auto wd) {
     constexpr int WD = decltype(wd)::value;
     auto go = [&](auto kernel) { return launch(h, kernel, n_super, kFfThreads, kFfLdsBytes, a); };
     return which == kFfEval ? go(k_ff_fwd<WD, false>) : which == kFfTrain ? go(k_ff_fwd<WD, true>)
-           : which == kFfBwd ? go(k_ff_bwd<WD>) : go(k_ff_fwd<WD, false, true>);
+           : which == kFfBwd ? go(k_ff_bwd<WD>) : which == kFfRender ? go(k_ff_fwd<WD, false, true>)
+                             : go(k_ff_fwd<WD, false, true, 16>);
   });
 }
 

@@ -267,7 +267,10 @@ struct FwdArgs {
   float* dbg;              // SF_EXPERIMENT_STAMP builds only
   float* dfac;             // optional [npix][nout]: a training pass with a sine output layer writes d sin(om z)/dz here
                            // (WaveletSiren sub-handles: their dL/dout comes from k_wv_adjoint / k_wv_inject, which apply it)
-  uint8_t* rgb8;           // RENDER kernels only: optional [npix][nout] bytes, min(max((int)(pred * 255), 0), 255)
+  union {                  // RENDER kernels only, optional [npix][nout] samples (4-byte aligned base):
+    uint8_t* rgb8;         //   BITS = 8:  bytes, min(max((int)(pred * 255), 0), 255)
+    uint16_t* rgb16;       //   BITS = 16: native-endian uint16_t, min(max((int)(pred * 65535), 0), 65535)
+  };
 };
 
 // Forward weight image of one hidden layer, as stored in HBM and copied verbatim into LDS:
@@ -335,14 +338,17 @@ DEV void fwd_sse_partial(const FwdArgs& a, float sse, int lane, int wave, int ti
   }
 }
 
-// last-layer accumulator -> fp32 prediction and / or packed bytes of one pixel block (siren_render.hip): the epilogue of the
-// RENDER instantiations, which read no target and write no phases, no dL/dout and no SSE partial
+// last-layer accumulator -> fp32 prediction and / or packed samples of one pixel block (siren_render.hip): the epilogue of the
+// RENDER instantiations, which read no target and write no phases, no dL/dout and no SSE partial.  BITS: 8 (a.rgb8) or 16
+// (a.rgb16) bits per sample
+template <int BITS>
 DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, bool valid, int lane, int h);
 
-// RENDER (inference only, sf_render): TRAIN = false with fwd_render_out in place of the residual epilogue
-template <int WD, typename OP, bool TRAIN, bool S8 = false, bool RENDER = false>
+// RENDER (inference only, sf_render / sf_render16): TRAIN = false with fwd_render_out<BITS> in place of the residual epilogue
+template <int WD, typename OP, bool TRAIN, bool S8 = false, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
   static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
+  static_assert(BITS == 8 || (RENDER && BITS == 16), "BITS: the sample width of a RENDER form, 8 or 16");
   using IM = FwdImg<WD>;
   constexpr int NT = IM::NT, KS = IM::KS, H0 = IM::H0;
   constexpr int SPT = S8 ? 1 : 2;   // phase stores per tile epilogue (what the counted vmcnt waits leave in flight)
@@ -524,7 +530,7 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
   for (int s = 0; s < KS; ++s) acc = OP::mfma(sW[s * 64 + lane], B[s], acc);
 
   if constexpr (RENDER) {
-    fwd_render_out(a, acc, pix, pb, valid, lane, h);
+    fwd_render_out<BITS>(a, acc, pix, pb, valid, lane, h);
     (void)sRed;
   } else {
     fwd_sse_partial(a, fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h), lane, wave, tid, sRed);
@@ -575,9 +581,10 @@ DEV uint32_t pack_h2(_Float16 a, _Float16 b) {
 #ifndef SF_FWD_PD
 #define SF_FWD_PD 4
 #endif
-template <typename OP, bool TRAIN, bool S8, int PD = SF_FWD_PD, bool RENDER = false>
+template <typename OP, bool TRAIN, bool S8, int PD = SF_FWD_PD, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
   static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
+  static_assert(BITS == 8 || (RENDER && BITS == 16), "BITS: the sample width of a RENDER form, 8 or 16");
   constexpr int WD = 256;
   using IM = FwdImg<WD>;
   constexpr int NT = IM::NT, KS = IM::KS, H0 = IM::H0, NG = NT * KS;
@@ -897,7 +904,7 @@ __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
 #ifdef SF_EXPERIMENT_STAMP
     st_pipe += __builtin_amdgcn_s_memtime() - t_x1;
 #endif
-    if constexpr (RENDER) fwd_render_out(a, acc, pix, pb, valid, lane, h);
+    if constexpr (RENDER) fwd_render_out<BITS>(a, acc, pix, pb, valid, lane, h);
     else sse_acc += fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h);
   }
   if constexpr (!RENDER) fwd_sse_partial(a, sse_acc, lane, wave, tid, sRed);

@@ -14,13 +14,22 @@
 // ds_bpermute and stores it, so a wave writes 8 * out_features whole dwords (24 for RGB) in one store instruction.  Only the
 // picture's last, ragged dword is written byte by byte.
 //
+// 16-bit samples (sf_render16, BITS = 16): u16 = min(max((int)(pred * 65535.0f), 0), 65535), the same statement one sample
+// width up - it inverts the loader's raw / (2^16 - 1).  The 32 pixels of a wave are 32 * out_features uint16_t =
+// 16 * out_features whole dwords (48 for RGB), again from a dword boundary: a lane holds its pixel in two registers
+// (channel 0 | channel 1 << 16, channel 2), lane d < 16 * out_features gathers the two samples of dword d with four
+// ds_bpermute and the wave stores them in one store instruction (render_store_block16).  Only a picture with an odd sample
+// count has a ragged last dword: its low half goes out as one 2-byte store.
+//
 // This file is included at the end of siren_fit.hip (one translation unit, as every kernel file of the library).
 
 namespace sf {
 
+template <int BITS>
 DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, bool valid, int lane, int h) {
   const int nout = a.nout;
   uint32_t mine = 0u;   // this lane's pixel: channel c in byte c (lanes of the upper half hold padded rows: never selected)
+  uint32_t mine1 = 0u;  // BITS = 16: channels 0 and 1 in the halves of `mine`, channel 2 here
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     if (c >= nout) break;
@@ -32,12 +41,24 @@ DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, 
     }
     const float p = o * 0.5f + 0.5f;  // siren.py:131
     if (a.pred && h == 0 && valid) a.pred[pix * nout + c] = p;
-    int q = (int)(p * 255.0f);        // v_cvt_i32_f32: toward zero
-    q = q < 0 ? 0 : (q > 255 ? 255 : q);
-    mine |= (uint32_t)q << (8 * c);
+    if constexpr (BITS == 16) {
+      int q = (int)(p * 65535.0f);    // v_cvt_i32_f32: toward zero
+      q = q < 0 ? 0 : (q > 65535 ? 65535 : q);
+      if (c < 2) mine |= (uint32_t)q << (16 * c); else mine1 = (uint32_t)q;
+    } else {
+      int q = (int)(p * 255.0f);        // v_cvt_i32_f32: toward zero
+      q = q < 0 ? 0 : (q > 255 ? 255 : q);
+      mine |= (uint32_t)q << (8 * c);
+    }
   }
-  if (!a.rgb8) return;
-  render_store_block(a.rgb8, a.pix0 + pb * 32, a.npix, nout, mine, lane);   // the block's first pixel: a multiple of 32
+  if constexpr (BITS == 16) {
+    if (!a.rgb16) return;
+    render_store_block16(a.rgb16, a.pix0 + pb * 32, a.npix, nout, mine, mine1, lane);
+  } else {
+    (void)mine1;
+    if (!a.rgb8) return;
+    render_store_block(a.rgb8, a.pix0 + pb * 32, a.npix, nout, mine, lane);   // the block's first pixel: a multiple of 32
+  }
 }
 
 // The byte tail every 32-pixel-per-wave render kernel shares (k_fwd / k_fwd_pipe above, k_ff_fwd's RENDER form in
@@ -68,41 +89,72 @@ DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32
   }
 }
 
+// Sample k (= pixel k / nout, channel k % nout) of a wave's block of 16-bit samples, gathered from the lane that holds the
+// pixel: v0 = channel 0 | channel 1 << 16, v1 = channel 2.  lanes: 32 (the 32-pixel forms) or 64 (k_wv_render); called by
+// all 64 lanes, two ds_bpermute.
+DEV uint32_t render_sample16(uint32_t v0, uint32_t v1, int k, int nout, int lanes) {
+  const int src = nout == 3 ? k / 3 : (nout == 2 ? k >> 1 : k);
+  const int ch = k - src * nout;
+  const uint32_t lo = (uint32_t)__shfl((int)v0, src & (lanes - 1)), hi = (uint32_t)__shfl((int)v1, src & (lanes - 1));
+  return ch == 2 ? hi : (lo >> (16 * ch)) & 0xffffu;
+}
+// Stores dword d of a wave's block of 16-bit samples (samples 2d, 2d + 1 = word) when the output holds both, the low half
+// as one 2-byte store when it holds only the first (the ragged end of an output with an odd sample count), else nothing.
+// blk: the block's first sample, dword aligned; nsamp: samples of the block inside the output.
+DEV void render_store_dword16(uint16_t* blk, int d, int nsamp, uint32_t word) {
+  if (2 * d + 2 <= nsamp) reinterpret_cast<uint32_t*>(blk)[d] = word;
+  else if (2 * d < nsamp) blk[2 * d] = (uint16_t)word;
+}
+
+// render_store_block for 16-bit samples.  mine0 / mine1: the lane's pixel of the block starting at pixel px0 (lanes 0..31;
+// the upper half is never selected).  Called by all 64 lanes; rgb16 + px0 * nout is dword aligned (the entry point checks
+// the base, 32 | px0): lane d < 16 * nout stores dword d.
+DEV void render_store_block16(uint16_t* rgb16, long px0, long npix, int nout, uint32_t mine0, uint32_t mine1, int lane) {
+  const long left = npix - px0;
+  const int nsamp = left >= 32 ? 32 * nout : (left > 0 ? (int)left * nout : 0);   // samples of the block inside the picture
+  const uint32_t s0 = render_sample16(mine0, mine1, 2 * lane, nout, 32);        // (lanes >= 16 * nout gather nothing they store)
+  const uint32_t s1 = render_sample16(mine0, mine1, 2 * lane + 1, nout, 32);
+  if (lane < 16 * nout) render_store_dword16(rgb16 + px0 * nout, lane, nsamp, s0 | (s1 << 16));
+}
+
 }  // namespace sf
 
 namespace {
 
-// the kernel family sf_forward picks for the handle (fwd_is_pipe), in its RENDER form, on n_wg workgroups (fwd_grid)
-int launch_render(sf_engine* h, const FwdArgs& a, int n_wg) {
-  return with_op(h, [&](auto op) {
-    using OP = decltype(op);
-    if (fwd_is_pipe(h)) return launch(h, k_fwd_pipe<OP, false, false, SF_FWD_PD, true>, n_wg, 512, fwd_pipe_lds_bytes(), a);
-    return with_width(h, [&](auto wd) {
-      constexpr int WD = decltype(wd)::value;
-      return launch(h, k_fwd<WD, OP, false, false, true>, n_wg, 512, fwd_lds_bytes(WD), a);
+// the kernel family sf_forward picks for the handle (fwd_is_pipe), in its RENDER form, on n_wg workgroups (fwd_grid);
+// bits: 8 (a.rgb8) or 16 (a.rgb16) per sample
+int launch_render(sf_engine* h, const FwdArgs& a, int n_wg, int bits = 8) {
+  return with_bool(bits == 16, [&](auto wide) {
+    constexpr int BITS = decltype(wide)::value ? 16 : 8;
+    return with_op(h, [&](auto op) {
+      using OP = decltype(op);
+      if (fwd_is_pipe(h))
+        return launch(h, k_fwd_pipe<OP, false, false, SF_FWD_PD, true, BITS>, n_wg, 512, fwd_pipe_lds_bytes(), a);
+      return with_width(h, [&](auto wd) {
+        constexpr int WD = decltype(wd)::value;
+        return launch(h, k_fwd<WD, OP, false, false, true, BITS>, n_wg, 512, fwd_lds_bytes(WD), a);
+      });
     });
   });
 }
 
-int render_fourier(sf_engine* h, uint8_t* rgb8, float* pred);   // fourier_render.hip, included last: the RENDER form of k_ff_fwd
+// fourier_render.hip, included last: the RENDER form of k_ff_fwd (out: bits / 8 bytes per sample)
+int render_fourier(sf_engine* h, void* out, int bits, float* pred);
 
-}  // namespace
-
-extern "C" {
-
-int sf_render_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, true); } SF_CATCH
-
-int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try {
+// sf_render (bits = 8) and sf_render16 (bits = 16): one set of argument checks, one chunk loop
+int render_any(sf_handle* h, void* out, int bits, float* pred) {
+  const std::string fn = bits == 16 ? "sf_render16" : "sf_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
   if (!h) return fail(SF_ERR_INVALID, "null argument");
-  if (!rgb8 && !pred) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev and pred_dev are both NULL");
+  if (!out && !pred) return fail(SF_ERR_INVALID, fn + ": " + on + " and pred_dev are both NULL");
   if (h->wavelet && h->render)
-    return fail(SF_ERR_INVALID, "sf_render: a WaveletSiren render handle (sf_wavelet_render_create) is drawn by sf_wavelet_render");
+    return fail(SF_ERR_INVALID, fn + ": a WaveletSiren render handle (sf_wavelet_render_create) is drawn by sf_wavelet_render" +
+                                    (bits == 16 ? "16" : ""));
   if (h->wide || h->wavelet)
-    return fail(SF_ERR_INVALID, "sf_render: built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create) "
-                                "and FourierNet handles (sf_fourier_create / sf_fourier_render_create)");
-  if (((uintptr_t)rgb8 & 3u) != 0) return fail(SF_ERR_INVALID, "sf_render: rgb8_dev must be 4-byte aligned");
+    return fail(SF_ERR_INVALID, fn + ": built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create) "
+                                     "and FourierNet handles (sf_fourier_create / sf_fourier_render_create)");
+  if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
-  if (h->fourier) return render_fourier(h, rgb8, pred);
+  if (h->fourier) return render_fourier(h, out, bits, pred);
   DevGuard dev_guard(h->cfg.device);
   SF_TRY(refresh_images(h));
   for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
@@ -110,12 +162,21 @@ int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try {
     const int n_super = k.n_super;
     FwdArgs fa = fwd_args_base(h, k.pix0, n_super);
     fa.pred = pred;
-    fa.rgb8 = rgb8;
-    const double out_bytes = (pred ? 4.0 : 0.0) + (rgb8 ? 1.0 : 0.0);
+    fa.rgb8 = (uint8_t*)out;   // (a.rgb16 of the 16-bit forms: the same member)
+    const double out_bytes = (pred ? 4.0 : 0.0) + (out ? bits / 8.0 : 0.0);
     Launch L(h, K_RENDER, flops_fwd_px(h) * n_super * (double)kSuper, n_super * (double)kSuper * h->cfg.out_features * out_bytes);
-    SF_TRY(launch_render(h, fa, fwd_grid(h, n_super)));
+    SF_TRY(launch_render(h, fa, fwd_grid(h, n_super), bits));
   }
   return SF_OK;
-} SF_CATCH
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_render_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, true); } SF_CATCH
+
+int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try { return render_any(h, rgb8, 8, pred); } SF_CATCH
+int sf_render16(sf_handle* h, uint16_t* rgb16, float* pred) try { return render_any(h, rgb16, 16, pred); } SF_CATCH
 
 }  // extern "C"

@@ -18,6 +18,12 @@
 // register, lane d < 48 gathers dword d from three neighbours with four ds_bpermute, and the wave stores 48 whole dwords in
 // one store instruction.  Only the output's last, ragged dword is written byte by byte.
 //
+// 16-bit samples (sf_wavelet_render16, k_wv_render<16>): u16 = min(max((int)(v * 65535.0f), 0), 65535).  The wave's 64
+// pixels are 192 uint16_t = 96 whole dwords from a dword boundary: a lane holds its pixel in two registers (channel 0 |
+// channel 1 << 16, channel 2), gathers dword `lane` and, below lane 32, dword 64 + `lane` (render_sample16,
+// siren_render.hip) and the wave stores them in two store instructions.  Only an output with an odd sample count has a
+// ragged last dword: its low half goes out as one 2-byte store.
+//
 // This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit).
 
 namespace sf {
@@ -32,13 +38,19 @@ struct WvRenderArgs {
   const float* lf;       // [cr * cc][3]
   const float* hf;
   float* pred;           // [npx][3] or null
-  uint8_t* rgb8;         // [npx][3] or null (4-byte aligned)
+  union {                // [npx][3] samples or null (4-byte aligned)
+    uint8_t* rgb8;       //   k_wv_render<8>:  bytes
+    uint16_t* rgb16;     //   k_wv_render<16>: native-endian uint16_t
+  };
 };
 
+template <int BITS>
 __global__ __launch_bounds__(kWvThreads) void k_wv_render(WvRenderArgs a) {
+  static_assert(BITS == 8 || BITS == 16, "BITS: the sample width, 8 or 16");
   const long p = (long)blockIdx.x * kWvThreads + threadIdx.x;
   const int lane = threadIdx.x & 63;
   uint32_t mine = 0u;   // this lane's pixel: channel k in byte k
+  uint32_t mine1 = 0u;  // BITS = 16: channels 0 and 1 in the halves of `mine`, channel 2 here
   if (p < a.npx) {
     const int pr = (int)(p / a.cols);
     const int r = a.row0 + pr, c = a.col0 + (int)(p - (long)pr * a.cols);
@@ -47,12 +59,33 @@ __global__ __launch_bounds__(kWvThreads) void k_wv_render(WvRenderArgs a) {
     const float (&rgb)[3] = px.rgb;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      int q = (int)(rgb[k] * 255.0f);   // v_cvt_i32_f32: toward zero
-      q = q < 0 ? 0 : (q > 255 ? 255 : q);
-      mine |= (uint32_t)q << (8 * k);
+      if constexpr (BITS == 16) {
+        int q = (int)(rgb[k] * 65535.0f);   // v_cvt_i32_f32: toward zero
+        q = q < 0 ? 0 : (q > 65535 ? 65535 : q);
+        if (k < 2) mine |= (uint32_t)q << (16 * k); else mine1 = (uint32_t)q;
+      } else {
+        int q = (int)(rgb[k] * 255.0f);   // v_cvt_i32_f32: toward zero
+        q = q < 0 ? 0 : (q > 255 ? 255 : q);
+        mine |= (uint32_t)q << (8 * k);
+      }
     }
   }
-  if (!a.rgb8) return;   // (uniform)
+  if (!a.rgb8) return;   // (uniform; a.rgb16 is the same member)
+  if constexpr (BITS == 16) {
+    const long p0 = p - lane;               // first pixel of this wave: a multiple of 64
+    const long left = a.npx - p0;
+    const int nsamp = left >= 64 ? 192 : (left > 0 ? (int)left * 3 : 0);   // samples of the wave inside the output
+    uint16_t* blk = a.rgb16 + p0 * 3;       // dword aligned: sf_wavelet_render16 checks the base, 64 | p0
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {  // dwords lane and 64 + lane (all 64 lanes gather: a cross-lane read)
+      const int d = 64 * half + lane;
+      const uint32_t s0 = render_sample16(mine, mine1, 2 * d, 3, 64);   // (d >= 96 gathers nothing it stores)
+      const uint32_t s1 = render_sample16(mine, mine1, 2 * d + 1, 3, 64);
+      if (d < 96) render_store_dword16(blk, d, nsamp, s0 | (s1 << 16));
+    }
+    return;
+  }
+  (void)mine1;
   uint32_t word = 0u;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -139,25 +172,19 @@ int create_wavelet_render(const sf_wavelet_render_config* cfg, sf_handle** out) 
   return SF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int sf_wavelet_render_create(const sf_wavelet_render_config* cfg, sf_handle** out) try {
-  return create_wavelet_render(cfg, out);
-} SF_CATCH
-
-int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, uint8_t* rgb8, float* pred) try {
+// sf_wavelet_render (bits = 8) and sf_wavelet_render16 (bits = 16): one set of argument checks, one pair of chunk loops
+int wavelet_render_any(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, void* out, int bits, float* pred) {
+  const std::string fn = bits == 16 ? "sf_wavelet_render16" : "sf_wavelet_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
   if (!h) return fail(SF_ERR_INVALID, "null argument");
   if (!h->wavelet)
-    return fail(SF_ERR_INVALID, "sf_wavelet_render: not a WaveletSiren handle (sf_wavelet_render_create / sf_wavelet_create)");
-  if (!rgb8 && !pred) return fail(SF_ERR_INVALID, "sf_wavelet_render: rgb8_dev and pred_dev are both NULL");
-  if (((uintptr_t)rgb8 & 3u) != 0) return fail(SF_ERR_INVALID, "sf_wavelet_render: rgb8_dev must be 4-byte aligned");
+    return fail(SF_ERR_INVALID, fn + ": not a WaveletSiren handle (sf_wavelet_render_create / sf_wavelet_create)");
+  if (!out && !pred) return fail(SF_ERR_INVALID, fn + ": " + on + " and pred_dev are both NULL");
+  if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
   const int H = h->cfg.height;
   if (row0 < 0 || row1 > H || row0 >= row1 || col0 < 0 || col1 > H || col0 >= col1)
-    return fail(SF_ERR_INVALID, "sf_wavelet_render: need 0 <= row0 < row1 <= height and 0 <= col0 < col1 <= height");
+    return fail(SF_ERR_INVALID, fn + ": need 0 <= row0 < row1 <= height and 0 <= col0 < col1 <= height");
   if (h->render && (row1 - row0 > h->wv_max_rows || col1 - col0 > h->wv_max_cols))
-    return fail(SF_ERR_INVALID, "sf_wavelet_render: the window is larger than the max_rows x max_cols the handle was created for");
+    return fail(SF_ERR_INVALID, fn + ": the window is larger than the max_rows x max_cols the handle was created for");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   DevGuard dev_guard(h->cfg.device);
   SF_TRY(refresh_images(h));   // (also points the sub-handles at the current stream and profiler)
@@ -192,9 +219,30 @@ int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, in
   a.npx = (long)(row1 - row0) * (col1 - col0);
   a.i0 = i0; a.j0 = j0; a.cc = cc;
   a.lf = p_sub[0]; a.hf = p_sub[1];
-  a.pred = pred; a.rgb8 = rgb8;
-  Launch L(h, K_WV_RENDER, 0, (double)a.npx * ((pred ? 12.0 : 0.0) + (rgb8 ? 3.0 : 0.0)) + (double)nn * 24.0);
-  return launch(h, k_wv_render, (a.npx + kWvThreads - 1) / kWvThreads, kWvThreads, 0, a);
+  a.pred = pred; a.rgb8 = (uint8_t*)out;   // (a.rgb16 of k_wv_render<16>: the same member)
+  Launch L(h, K_WV_RENDER, 0, (double)a.npx * ((pred ? 12.0 : 0.0) + (out ? 3.0 * (bits / 8) : 0.0)) + (double)nn * 24.0);
+  const long n_wg = (a.npx + kWvThreads - 1) / kWvThreads;
+  return bits == 16 ? launch(h, k_wv_render<16>, n_wg, kWvThreads, 0, a) : launch(h, k_wv_render<8>, n_wg, kWvThreads, 0, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_wavelet_render_create(const sf_wavelet_render_config* cfg, sf_handle** out) try {
+  return create_wavelet_render(cfg, out);
+} SF_CATCH
+
+int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, uint8_t* rgb8, float* pred) try {
+  return wavelet_render_any(h, row0, row1, col0, col1, rgb8, 8, pred);
+} SF_CATCH
+
+}  // extern "C"
+
+extern "C" {   // sf_wavelet_render at 16 bits per sample
+
+int sf_wavelet_render16(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, uint16_t* rgb16, float* pred) try {
+  return wavelet_render_any(h, row0, row1, col0, col1, rgb16, 16, pred);
 } SF_CATCH
 
 }  // extern "C"

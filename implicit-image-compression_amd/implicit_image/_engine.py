@@ -113,9 +113,13 @@ _declare("wavelet", {
 })
 # inference-only entry points (csrc/siren_render.hip, wavelet_render.hip, fourier_render.hip)
 _declare("render", {"sf_render_create": [P(sf_config), P(H)], "sf_render": [H, C.c_void_p, F]})
+# (sf_render at 16 bits per sample.  Not in group "render": has_render / has_fourier_render answer for the 8-bit path of a
+# library that has nothing else; RenderEngine.render(bits=16) asks for this symbol itself)
+_declare("core", {"sf_render16": [H, C.c_void_p, F]})
 _declare("wavelet_render", {
     "sf_wavelet_render_create": [P(sf_wavelet_render_config), P(H)],
     "sf_wavelet_render": [H, I32, I32, I32, I32, C.c_void_p, F],
+    "sf_wavelet_render16": [H, I32, I32, I32, I32, C.c_void_p, F],
 })
 _declare("fourier_render", {"sf_fourier_render_create": [P(sf_fourier_config), P(H)]})
 
@@ -131,6 +135,9 @@ def load_library():
             "--offload-arch=gfx950). The SIREN engine has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
     for name, (group, args, restype) in PROTOTYPES.items():
+        if group == "core" and not hasattr(lib, name):
+            raise RuntimeError(f"{_LIB_PATH} has no {name} entry point (built before it was added): rebuild it with "
+                               "`python __graft_entry__.py build`")
         if group == "core" or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.argtypes = args
@@ -143,6 +150,13 @@ def load_library():
 
 def _has(lib, group: str) -> bool:
     return all(hasattr(lib, name) for name, proto in PROTOTYPES.items() if proto[0] == group)
+
+
+def _render_entry(lib, name: str, bits: int):
+    """the entry point `name` (bits = 8) or `name`16 (bits = 16) of a library that has the group; else a ValueError"""
+    if bits not in (8, 16):
+        raise ValueError(f"render: bits must be 8 or 16, got {bits!r}")
+    return getattr(lib, name + ("16" if bits == 16 else ""))
 
 
 def has_feather(lib) -> bool:
@@ -245,11 +259,12 @@ class SirenEngine:
         self._target = None
         self._views = {}
 
-    def _outputs(self, shape, want_u8: bool, want_pred: bool):
-        """(rgb8, pred, their device pointers) of a render call: `shape` uint8 / fp32 on this device, None where not asked"""
+    def _outputs(self, shape, want_u8: bool, want_pred: bool, bits: int = 8):
+        """(samples, pred, their device pointers) of a render call: `shape` uint8 (bits = 8) or uint16 (bits = 16) / fp32 on
+        this device, None where not asked"""
         if not (want_u8 or want_pred):
             raise ValueError("render: ask for bytes, the fp32 prediction, or both")
-        u8 = torch.empty(shape, dtype=torch.uint8, device=self.device) if want_u8 else None
+        u8 = torch.empty(shape, dtype=torch.uint16 if bits == 16 else torch.uint8, device=self.device) if want_u8 else None
         pred = torch.empty(shape, device=self.device) if want_pred else None
         return u8, pred, (u8.data_ptr() if want_u8 else None), (pred.data_ptr() if want_pred else None)
 
@@ -262,12 +277,15 @@ class SirenEngine:
             self._views[key] = torch.as_tensor(_DevView(p.value, cnt.value, typestr), device=self.device)
         return self._views[key]
 
-    def render(self, want_u8: bool = True, want_pred: bool = False):
+    def render(self, want_u8: bool = True, want_pred: bool = False, bits: int = 8):
         """sf_render on this handle's rows, no host sync: (rgb8 [rows, W, C] uint8 or None, pred [rows, W, C] fp32 or None).
-        u8 = min(max((int)(pred * 255), 0), 255); pred is bit-identical to forward()'s."""
+        u8 = min(max((int)(pred * 255), 0), 255); pred is bit-identical to forward()'s.  bits=16: sf_render16, the samples
+        are uint16, min(max((int)(pred * 65535), 0), 65535)."""
         _require(self.lib, has_render, "sf_render entry point", "the render path")
-        u8, pred, u8_p, pred_p = self._outputs((self.row_end - self.row_begin, self.width, self.out_features), want_u8, want_pred)
-        _check(self.lib.sf_render(self.h, u8_p, pred_p))
+        fn = _render_entry(self.lib, "sf_render", bits)
+        u8, pred, u8_p, pred_p = self._outputs((self.row_end - self.row_begin, self.width, self.out_features), want_u8, want_pred,
+                                               bits)
+        _check(fn(self.h, u8_p, pred_p))
         return u8, pred
 
     @property
@@ -487,9 +505,9 @@ class FourierEngine(SirenEngine):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
         _check(self.lib.sf_set_encoding(self.h, _f32_cuda(B.detach().contiguous(), 2 * (self.map_size // 2)).data_ptr()))
 
-    def render(self, want_u8: bool = True, want_pred: bool = False):
+    def render(self, want_u8: bool = True, want_pred: bool = False, bits: int = 8):
         _require(self.lib, *_FOURIER_RENDER)
-        return super().render(want_u8, want_pred)
+        return super().render(want_u8, want_pred, bits)
 
 
 class FourierRenderEngine(FourierEngine):
@@ -528,10 +546,10 @@ class WaveletEngine(SirenEngine):
         """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""
         _check(self.lib.sf_set_coords(self.h, _f32_cuda(rows, self.n).data_ptr(), _f32_cuda(cols, self.n).data_ptr()))
 
-    def render_window(self, r0: int, r1: int, c0: int, c1: int, want_u8: bool = True, want_pred: bool = False):
+    def render_window(self, r0: int, r1: int, c0: int, c1: int, want_u8: bool = True, want_pred: bool = False, bits: int = 8):
         """sf_wavelet_render of pixel rows [r0, r1) x columns [c0, c1) on this handle, no host sync:
-        (rgb8 [r1 - r0, c1 - c0, 3] uint8 or None, pred fp32 or None)"""
-        return _wavelet_render(self, r0, r1, c0, c1, want_u8, want_pred)
+        (rgb8 [r1 - r0, c1 - c0, 3] uint8 or None, pred fp32 or None); bits=16: sf_wavelet_render16, uint16 samples"""
+        return _wavelet_render(self, r0, r1, c0, c1, want_u8, want_pred, bits)
 
     def debug_compose(self, lf: torch.Tensor, hf: torch.Tensor, img: Optional[torch.Tensor] = None):
         """k_wv_compose on [n, n, 3] sub-network predictions: (RGB [H, H, 3], dL/d(Y, Cb, Cr) [H, H, 3] or None)"""
@@ -552,10 +570,11 @@ class WaveletEngine(SirenEngine):
         return lf, hf
 
 
-def _wavelet_render(eng, r0: int, r1: int, c0: int, c1: int, want_u8: bool, want_pred: bool):
+def _wavelet_render(eng, r0: int, r1: int, c0: int, c1: int, want_u8: bool, want_pred: bool, bits: int = 8):
     _require(eng.lib, has_wavelet_render, "sf_wavelet_render entry point", "the WaveletSiren render path")
-    u8, pred, u8_p, pred_p = eng._outputs((max(r1 - r0, 0), max(c1 - c0, 0), 3), want_u8, want_pred)
-    _check(eng.lib.sf_wavelet_render(eng.h, r0, r1, c0, c1, u8_p, pred_p))
+    fn = _render_entry(eng.lib, "sf_wavelet_render", bits)
+    u8, pred, u8_p, pred_p = eng._outputs((max(r1 - r0, 0), max(c1 - c0, 0), 3), want_u8, want_pred, bits)
+    _check(fn(eng.h, r0, r1, c0, c1, u8_p, pred_p))
     return u8, pred
 
 
@@ -580,12 +599,13 @@ class WaveletRenderEngine(WaveletEngine):
     _CREATE = "sf_wavelet_render_create"
 
     def render(self, r0: int = 0, r1: Optional[int] = None, c0: int = 0, c1: Optional[int] = None, want_u8: bool = True,
-               want_pred: bool = False):
+               want_pred: bool = False, bits: int = 8):
         """pixel rows [r0, r1) x columns [c0, c1) of the height x height picture (default: all of it), no host sync:
         (rgb8 [rows, cols, 3] uint8 or None, pred [rows, cols, 3] fp32 or None).  u8 = min(max((int)(pred * 255), 0), 255);
-        pred is bit-identical to WaveletEngine.forward()'s for the same pixels."""
+        pred is bit-identical to WaveletEngine.forward()'s for the same pixels.  bits=16: sf_wavelet_render16, uint16
+        samples, min(max((int)(pred * 65535), 0), 65535)."""
         return _wavelet_render(self, r0, self.height if r1 is None else r1, c0, self.height if c1 is None else c1,
-                               want_u8, want_pred)
+                               want_u8, want_pred, bits)
 
 
 class FeatherEngine:

@@ -82,6 +82,25 @@ def write_ppm(path: str, img) -> None:
         f.write(np.ascontiguousarray(arr).tobytes())
 
 
+def write_ppm16(path: str, img) -> None:
+    """[H, W, 3] integer values 0..65535 (tensor or ndarray, any integer type) -> binary P6 PPM, maxval 65535, big-endian
+    samples: what read_ppm reads back exactly."""
+    import numpy as np
+    if isinstance(img, torch.Tensor):
+        if img.is_floating_point() or img.dtype == torch.bool:
+            raise ValueError(f"write_ppm16 expects integers [H, W, 3], got {img.dtype} {tuple(img.shape)}")
+        arr = img.detach().cpu().to(torch.int64).numpy()
+    else:
+        arr = np.asarray(img)
+    if arr.dtype.kind not in "iu" or arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError(f"write_ppm16 expects integers [H, W, 3], got {arr.dtype} {tuple(arr.shape)}")
+    if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 65535):
+        raise ValueError(f"write_ppm16 expects values 0..65535, got {int(arr.min())}..{int(arr.max())}")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n65535\n" % (arr.shape[1], arr.shape[0]))
+        f.write(np.ascontiguousarray(arr).astype(">u2").tobytes())
+
+
 def load_img(path: str, height: int = 256, width: int = 256, bits: int = 8, plot: bool = False,
              crop_mode: str = "centre-crop", save_gt: bool = False, seed: int = 1234, **kwargs) -> torch.Tensor:
     """[H, W, 3] float32 image in [0,1] (reference signature).  `path` = "synthetic" (or

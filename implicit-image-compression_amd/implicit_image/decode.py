@@ -15,8 +15,13 @@ decode.* keys
                     that resolution (torch.linspace(0, 1, n) per axis, the reference's get_grid)
   decode.rows=a:b decode.cols=c:d   a window of that grid (the coordinate vectors are sliced on the host)
   decode.band_rows  rows rendered per kernel call (default: as many as keep one band's bytes under 256 MiB)
-  decode.out        the PPM to write (default <decode.dir>/decoded.ppm; binary P6, 8 bit)
-  decode.truth      <ppm> or synthetic[:seed]: print loss / PSNR / PSNR_8bit with eval_epoch's formulas
+  decode.out        the PPM to write (default <decode.dir>/decoded.ppm; binary P6, 8 bit, or 16 bit with decode.bits=16)
+  decode.bits       8 | 16 (default 8): bits per sample of the file.  16: u16 = min(max(trunc(pred * 65535), 0), 65535) from
+                    the render kernels' 16-bit epilogue (sf_render16 / sf_wavelet_render16; the torch path: to_u16), written
+                    as P6 with maxval 65535 (big-endian samples, what the loader reads back).  Truncation to 256 levels caps
+                    a file at 10 log10(3 * 255^2) = 52.9 dB against its own fp32 prediction; at 16 bits that is 101 dB
+  decode.truth      <ppm> or synthetic[:seed]: print loss / PSNR / PSNR_8bit with eval_epoch's formulas (decode.bits=16:
+                    and PSNR_16bit, the same formula on 65535 levels)
   decode.device     cuda ordinal (default 0)
   decode.render     auto | kernel | torch (default auto).  auto: what `render_path` answers, below.  torch: the registry
                     model's own forward for any model.  kernel: a render kernel or a ValueError that says why there is
@@ -46,7 +51,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from .config import Cfg, _load_yaml, _parse_scalar, _set_path, _wrap
-from .data import load_img, read_ppm, write_ppm
+from .data import load_img, read_ppm, write_ppm, write_ppm16
 from .models.siren import next_kernel_width
 
 REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
@@ -55,6 +60,7 @@ BAND_BYTES = 256 << 20            # one band's byte output stays under this
 ROW_LIMIT = 1 << 40               # a handle decodes (row, col) exactly while rows * width^2 < 2^40 (sf_create)
 KERNEL_WIDTHS = (32, 64, 128, 256)
 RENDER_MODES = ("auto", "kernel", "torch")
+SAMPLE_BITS = (8, 16)
 FOURIER_MAPS = (64, 128, 256, 512)
 SHAPE_KEYS = ("mlp.depth", "mlp.hidden_size")
 
@@ -185,13 +191,28 @@ def to_u8(pred: torch.Tensor) -> torch.Tensor:
     return (pred.float() * 255).clamp(-1, 256).int().clamp(0, 255).to(torch.uint8)
 
 
+def to_u16(pred: torch.Tensor) -> torch.Tensor:
+    """min(max(trunc(pred * 65535), 0), 65535) as int32: to_u8's statement at 16 bits per sample, the inverse of the loader's
+    raw / (2^16 - 1).  (the product in fp32; the float clamp to [-1, 65536] only keeps huge values inside int32 and changes
+    no result)"""
+    return (pred.float() * 65535).clamp(-1, 65536).int().clamp(0, 65535)
+
+
+def sample_bits(dec: Dict[str, str]) -> int:
+    """decode.bits of the decode.* keys: 8 (default) | 16"""
+    raw = dec.get("bits") or "8"
+    if raw not in [str(b) for b in SAMPLE_BITS]:
+        raise ValueError(f"decode.bits must be one of {', '.join(str(b) for b in SAMPLE_BITS)}, got {raw!r}")
+    return int(raw)
+
+
 def plan_bands(height: int, width: int, channels: int = 3, band_rows: Optional[int] = None,
-               band_bytes: int = BAND_BYTES) -> List[Tuple[int, int]]:
+               band_bytes: int = BAND_BYTES, sample_bytes: int = 1) -> List[Tuple[int, int]]:
     """Row bands [r0, r1) that cover [0, height): each satisfies rows * width^2 < 2^40 (the engine's row decode) and
-    rows * width * channels < band_bytes; band_rows lowers the size further."""
+    rows * width * channels * sample_bytes < band_bytes; band_rows lowers the size further."""
     if height < 1 or width < 1:
         raise ValueError("bad picture size")
-    cap = min((ROW_LIMIT - 1) // (width * width), (band_bytes - 1) // (width * channels))
+    cap = min((ROW_LIMIT - 1) // (width * width), (band_bytes - 1) // (width * channels * sample_bytes))
     if cap < 1:
         raise ValueError(f"width {width}: one row does not fit a band")
     rows = min(height, cap if not band_rows else max(1, min(cap, int(band_rows))))
@@ -313,19 +334,20 @@ def flat_params(sd: Dict[str, torch.Tensor], depth: int) -> torch.Tensor:
     return torch.cat(parts).float().contiguous()
 
 
-def _render_bands(eng, load, bands: List[Tuple[int, int]], row0: int, cols: int, draw, want_pred: bool):
+def _render_bands(eng, load, bands: List[Tuple[int, int]], row0: int, cols: int, draw, want_pred: bool, bits: int = 8):
     """The open / load / assemble / close skeleton of the three kernel renderers, on a handle the caller opened: load(eng)
     puts the parameters (and what else the handle needs) in, draw(a, b) returns (u8, pred) of pixel rows [a, b) on the
-    device; every band is copied to the CPU as it comes and the handle is closed whatever happens.  uint8
-    [rows from row0 to the last band's end, cols, C] (and the fp32 prediction when asked)."""
+    device; every band is copied to the CPU as it comes and the handle is closed whatever happens.  uint8 (bits = 16: int32
+    values 0..65535, widened from the kernel's uint16) [rows from row0 to the last band's end, cols, C] (and the fp32
+    prediction when asked)."""
     try:
         load(eng)
         shape = (bands[-1][1] - row0, cols, eng.out_features)
-        out = torch.empty(shape, dtype=torch.uint8)
+        out = torch.empty(shape, dtype=torch.int32 if bits == 16 else torch.uint8)
         pred = torch.empty(shape) if want_pred else None
         for a, b in bands:
             u8, p = draw(a, b)
-            out[a - row0:b - row0] = u8.cpu()
+            out[a - row0:b - row0] = u8.cpu().to(out.dtype)
             if want_pred:
                 pred[a - row0:b - row0] = p.cpu()
     finally:
@@ -333,7 +355,8 @@ def _render_bands(eng, load, bands: List[Tuple[int, int]], row0: int, cols: int,
     return out, pred
 
 
-def _render_grid(eng, load, rows: torch.Tensor, cols: torch.Tensor, bands: List[Tuple[int, int]], want_pred: bool):
+def _render_grid(eng, load, rows: torch.Tensor, cols: torch.Tensor, bands: List[Tuple[int, int]], want_pred: bool,
+                 bits: int = 8):
     """Row bands of the grid rows x cols on an open sf_render handle (RenderEngine / FourierRenderEngine) made for the first
     band's height: a band is a slice of `rows`, the last, shorter one padded with its final row and cut after the render."""
     nb = bands[0][1] - bands[0][0]
@@ -344,20 +367,21 @@ def _render_grid(eng, load, rows: torch.Tensor, cols: torch.Tensor, bands: List[
         if r1 - r0 < nb:
             rb = torch.cat([rb, rb[-1:].expand(nb - (r1 - r0))])
         eng.set_coords(rb.contiguous().to(eng.device), cols_d)
-        u8, p = eng.render(want_u8=True, want_pred=want_pred)
+        u8, p = eng.render(want_u8=True, want_pred=want_pred, bits=bits)
         return u8[:r1 - r0], (p[:r1 - r0] if want_pred else None)
 
-    return _render_bands(eng, load, bands, 0, cols.numel(), draw, want_pred)
+    return _render_bands(eng, load, bands, 0, cols.numel(), draw, want_pred, bits)
 
 
 def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
-                  want_pred: bool = False, device: int = 0):
+                  want_pred: bool = False, device: int = 0, bits: int = 8):
     """uint8 [h, w, C] on the CPU (and the fp32 prediction when asked) of the grid rows x cols, band by band on ONE render
-    handle: a band is a slice of `rows` (the last, shorter one is padded with its final row and cut after the render)."""
+    handle: a band is a slice of `rows` (the last, shorter one is padded with its final row and cut after the render).
+    bits=16: int32 values 0..65535 from sf_render16."""
     from ._engine import RenderEngine
     m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
     C = int(m.get("output_size", 3))
-    bands = plan_bands(rows.numel(), cols.numel(), C, band_rows)
+    bands = plan_bands(rows.numel(), cols.numel(), C, band_rows, sample_bytes=bits // 8)
     eng = RenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.depth),
                        float(m.get("first_omega_0", 50.0)), float(m.get("hidden_omega_0", 30.0)),
                        bool(m.get("outermost_linear", True)), C, eng_kw.get("compute_dtype", "f16"), device=device,
@@ -368,17 +392,18 @@ def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_r
                 else engine_flat_params(sd, shape, eng.num_params))
         eng.set_params(flat.to(eng.device))
 
-    return _render_grid(eng, load, rows, cols, bands, want_pred)
+    return _render_grid(eng, load, rows, cols, bands, want_pred, bits)
 
 
 def render_fourier(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
-                   want_pred: bool = False, device: int = 0):
+                   want_pred: bool = False, device: int = 0, bits: int = 8):
     """render_kernel for mlp=fourier: uint8 [h, w, 3] on the CPU (and the fp32 prediction when asked) of the grid rows x cols,
     band by band on ONE FourierNet render handle.  Bands come from plan_bands, whose limits are stricter than the
-    height * width < 2^31 the handle needs; the last, shorter band is padded with its final row and cut after the render."""
+    height * width < 2^31 the handle needs; the last, shorter band is padded with its final row and cut after the render.
+    bits=16: int32 values 0..65535 from sf_render16."""
     from ._engine import FourierRenderEngine
     m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
-    bands = plan_bands(rows.numel(), cols.numel(), 3, band_rows)
+    bands = plan_bands(rows.numel(), cols.numel(), 3, band_rows, sample_bytes=bits // 8)
     eng = FourierRenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.get("depth", 8)) - 1,
                               int(m.get("map_size", 128)), 3, device=device,
                               chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
@@ -387,7 +412,7 @@ def render_fourier(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_
         eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(eng.device))
         eng.set_encoding(sd["encoding.B"].float().contiguous().to(eng.device))
 
-    return _render_grid(eng, load, rows, cols, bands, want_pred)
+    return _render_grid(eng, load, rows, cols, bands, want_pred, bits)
 
 
 # ---- WaveletSiren: which coefficients a window needs, bands, the kernel path -----------------------------------
@@ -415,15 +440,15 @@ def wavelet_coeff_span(o0: int, o1: int, H: int) -> Tuple[int, int]:
 
 
 def plan_wavelet_bands(H: int, r: Tuple[int, int], c: Tuple[int, int], band_rows: Optional[int] = None,
-                       band_bytes: int = BAND_BYTES) -> List[Tuple[int, int]]:
-    """Bands [r0, r1) of pixel rows that cover r = [ra, rb): each keeps rows * cols * 3 < band_bytes and its coefficient
+                       band_bytes: int = BAND_BYTES, sample_bytes: int = 1) -> List[Tuple[int, int]]:
+    """Bands [r0, r1) of pixel rows that cover r = [ra, rb): each keeps rows * cols * 3 * sample_bytes < band_bytes and its coefficient
     window within the render sub-handles' row decode, cr * cc^2 < 2^40 (cc: the coefficient columns of the column window
     c); band_rows lowers the size further."""
     cols = c[1] - c[0]
     j0, j1 = wavelet_coeff_span(c[0], c[1], H)
     cc = j1 - j0
     cr_cap = (ROW_LIMIT - 1) // (cc * cc)
-    cap = (band_bytes - 1) // (cols * 3)
+    cap = (band_bytes - 1) // (cols * 3 * sample_bytes)
     if cap < 1 or cr_cap < 4:
         raise ValueError(f"{cols} columns: one row does not fit a band")
     cap = min(cap, 2 * (cr_cap - 3))              # rows pixel rows read at most rows / 2 + 3 coefficient rows
@@ -436,13 +461,14 @@ def plan_wavelet_bands(H: int, r: Tuple[int, int], c: Tuple[int, int], band_rows
 
 
 def render_wavelet(sd, shape: Cfg, H: int, r: Tuple[int, int], c: Tuple[int, int], band_rows: Optional[int] = None,
-                   want_pred: bool = False, device: int = 0):
+                   want_pred: bool = False, device: int = 0, bits: int = 8):
     """uint8 [rows, cols, 3] on the CPU (and the fp32 prediction when asked) of the window r x c of the H x H picture of a
     WaveletSiren, band by band on ONE render handle (max_rows = the band height, max_cols = the window's): every band runs
-    the two sub-networks over the coefficient window it needs and nothing else."""
+    the two sub-networks over the coefficient window it needs and nothing else.  bits=16: int32 values 0..65535 from
+    sf_wavelet_render16."""
     from ._engine import WaveletRenderEngine
     m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
-    bands = plan_wavelet_bands(H, r, c, band_rows)
+    bands = plan_wavelet_bands(H, r, c, band_rows, sample_bytes=bits // 8)
     eng = WaveletRenderEngine(H, padded_width(shape), int(m.depth), float(m.get("first_omega_0", 50.0)),
                               float(m.get("hidden_omega_0", 50.0)), bool(m.get("outermost_linear", True)),
                               eng_kw.get("compute_dtype", "f16"), max_rows=bands[0][1] - bands[0][0], max_cols=c[1] - c[0],
@@ -454,25 +480,34 @@ def render_wavelet(sd, shape: Cfg, H: int, r: Tuple[int, int], c: Tuple[int, int
         eng.set_coords(lin, lin)
 
     return _render_bands(eng, load, bands, r[0], c[1] - c[0],
-                         lambda a, b: eng.render(a, b, c[0], c[1], want_u8=True, want_pred=want_pred), want_pred)
+                         lambda a, b: eng.render(a, b, c[0], c[1], want_u8=True, want_pred=want_pred, bits=bits), want_pred,
+                         bits)
 
 
-def render_torch(sd, shape: Cfg, height: int, width: int, r: Tuple[int, int], c: Tuple[int, int], device: int = 0):
-    """the registry model's own forward on the full height x width grid, cut to the window, bytes by to_u8"""
+def render_torch(sd, shape: Cfg, height: int, width: int, r: Tuple[int, int], c: Tuple[int, int], device: int = 0,
+                 bits: int = 8):
+    """the registry model's own forward on the full height x width grid, cut to the window, bytes by to_u8 (bits=16: int32
+    values 0..65535 by to_u16)"""
     from .data import get_grid
     dev = torch.device("cuda", device)
     model = registry_model(sd, shape).to(dev).eval()
     with torch.no_grad():
         pred = model(get_grid(height, width).to(dev))
     pred = pred[r[0]:r[1], c[0]:c[1]].contiguous()
-    return to_u8(pred).cpu(), pred.cpu()
+    return (to_u16 if bits == 16 else to_u8)(pred).cpu(), pred.cpu()
 
 
-def metrics(pred: torch.Tensor, u8: torch.Tensor, img: torch.Tensor) -> Dict[str, float]:
-    """eval_epoch's figures (train_helper.py:41-59) for a prediction and the bytes written for it"""
+def metrics(pred: torch.Tensor, u8: torch.Tensor, img: torch.Tensor, u16: Optional[torch.Tensor] = None) -> Dict[str, float]:
+    """eval_epoch's figures (train_helper.py:41-59) for a prediction and the bytes written for it; with the 16-bit samples
+    written for it also PSNR_16bit, the same formula on 65535 levels (the squared differences in int64: 65535^2 does not
+    fit int32)"""
     loss = float(((pred.double() - img.double()) ** 2).sum().item() / img.numel())
     mse8 = (((img * 255).int() - u8.int()) ** 2).float().mean()
-    return {"loss": loss, "PSNR": 10 * math.log10(1 / loss), "PSNR_8bit": (10 * torch.log10(255 ** 2 / mse8)).item()}
+    res = {"loss": loss, "PSNR": 10 * math.log10(1 / loss), "PSNR_8bit": (10 * torch.log10(255 ** 2 / mse8)).item()}
+    if u16 is not None:
+        mse16 = (((img * 65535).int().long() - u16.long()) ** 2).double().mean().item()
+        res["PSNR_16bit"] = 10 * math.log10(65535 ** 2 / mse16) if mse16 > 0 else math.inf
+    return res
 
 
 def load_truth(spec: str, height: int, width: int) -> torch.Tensor:
@@ -486,6 +521,7 @@ def load_truth(spec: str, height: int, width: int) -> torch.Tensor:
 def decode(argv: Sequence[str]) -> Dict[str, object]:
     dec, rest = split_overrides(argv)
     mode = render_mode(dec)
+    bits = sample_bits(dec)
     run_dir = dec.get("dir")
     if not run_dir:
         raise ValueError("decode.dir=<run directory written by fit> is required")
@@ -509,23 +545,24 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
     if path == "kernel":
         band_rows = int(dec["band_rows"]) if dec.get("band_rows") else None
         if name == "wavelet_siren":
-            u8, pred = render_wavelet(sd, shape, H, r, c, band_rows, want_pred=bool(truth), device=device)
+            u8, pred = render_wavelet(sd, shape, H, r, c, band_rows, want_pred=bool(truth), device=device, bits=bits)
         else:
             rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
             u8, pred = (render_fourier if name == "fourier" else render_kernel)(
-                sd, shape, rows, cols, band_rows, want_pred=bool(truth), device=device)
+                sd, shape, rows, cols, band_rows, want_pred=bool(truth), device=device, bits=bits)
     else:
-        u8, pred = render_torch(sd, shape, H, W, r, c, device=device)
+        u8, pred = render_torch(sd, shape, H, W, r, c, device=device, bits=bits)
     if u8.shape[-1] != 3:
         raise NotImplementedError(f"PPM holds 3 channels, the model has {u8.shape[-1]}")
     out = dec.get("out") or os.path.join(run_dir, "decoded.ppm")
-    write_ppm(out, u8)
+    (write_ppm16 if bits == 16 else write_ppm)(out, u8)   # (bits = 16: u8 holds the 16-bit samples)
     res = {"out": out, "path": path, "source": source, "height": int(u8.shape[0]), "width": int(u8.shape[1])}
     if truth:
         img = load_truth(truth, H, W)[r[0]:r[1], c[0]:c[1]]
-        res.update(metrics(pred, u8, img))
-        logging.info("Decode | " + " | ".join(f"{k}: {res[k]:.4f}" for k in ("loss", "PSNR", "PSNR_8bit")))
-        print(json.dumps({k: res[k] for k in ("loss", "PSNR", "PSNR_8bit")}))
+        res.update(metrics(pred, to_u8(pred), img, u8) if bits == 16 else metrics(pred, u8, img))
+        keys = ("loss", "PSNR", "PSNR_8bit") + (("PSNR_16bit",) if bits == 16 else ())
+        logging.info("Decode | " + " | ".join(f"{k}: {res[k]:.4f}" for k in keys))
+        print(json.dumps({k: res[k] for k in keys}))
     logging.info(f"decode: wrote {out}")
     return res
 

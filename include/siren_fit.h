@@ -12,6 +12,8 @@
  *   implicit_image/utils/train_helper.py:166-177  optimiser step (torch.optim.Adam, conf/optim/adam.yaml)
  *   implicit_image/pipeline/masking/core.py:271-279,671-702  Masking.step -> apply_mask   -> sf_adam_step
  *   implicit_image/utils/train_helper.py:41-59    eval_epoch (fwd, MSE)                   -> sf_forward
+ *   implicit_image/utils/train_helper.py:52       (pred * 255).int()   -> sf_render / sf_wavelet_render (8-bit samples);
+ *                                                 one sample width up: sf_render16 / sf_wavelet_render16 (pred * 65535)
  *
  * Conventions
  *   - every function returns 0 on success, a negative sf_status otherwise; the message is
@@ -222,9 +224,15 @@ int sf_forward_backward(sf_handle* h, double* sse_out);
  * SF_ERR_STATE.  Either output may be NULL, not both:
  *   pred_dev [npix][out_features] fp32, bit-identical to what sf_forward writes for the same parameters and coordinates;
  *   rgb8_dev [npix][out_features] bytes (4-byte aligned), u8 = min(max((int)(pred * 255.0f), 0), 255): the product in fp32,
- *            truncated toward zero (eval_epoch's (pred * 255).int(), train_helper.py:52), clamped to what a file can hold. */
+ *            truncated toward zero (eval_epoch's (pred * 255).int(), train_helper.py:52), clamped to what a file can hold.
+ * sf_render16 is sf_render at 16 bits per sample - the same handles, refusals, stream and pred_dev, the same kernels with a
+ * 16-bit store epilogue:
+ *   rgb16_dev [npix][out_features] native-endian uint16_t (4-byte aligned: a base that is only 2-byte aligned is refused),
+ *            u16 = min(max((int)(pred * 65535.0f), 0), 65535): the product in fp32, truncated toward zero - the inverse of
+ *            the loader's raw / (2^16 - 1).  A NaN prediction gives 0, as in the byte form. */
 int sf_render_create(const sf_config* cfg, sf_handle** out);
 int sf_render(sf_handle* h, uint8_t* rgb8_dev, float* pred_dev);
+int sf_render16(sf_handle* h, uint16_t* rgb16_dev, float* pred_dev);
 int sf_fourier_render_create(const sf_fourier_config* cfg, sf_handle** out);
 /* Inference only, WaveletSiren (csrc/wavelet_render.hip).  sf_wavelet_render_create validates what sf_wavelet_create
  * validates and allocates the joint parameter vector [LF | HF], two render sub-handles (parameters as views into it, forward
@@ -257,9 +265,13 @@ int sf_wavelet_render_create(const sf_wavelet_render_config* cfg, sf_handle** ou
  *   pred_dev fp32, bit-identical to what sf_forward writes for those pixels on a training handle with the same parameters;
  *   rgb8_dev bytes (4-byte aligned), u8 = min(max((int)(pred * 255.0f), 0), 255) as sf_render.
  * Empty windows, windows outside [0, H) or larger than max_rows x max_cols return SF_ERR_INVALID; a call before
- * sf_set_coords returns SF_ERR_STATE. */
+ * sf_set_coords returns SF_ERR_STATE.
+ * sf_wavelet_render16 is the same call at 16 bits per sample: rgb16_dev native-endian uint16_t (4-byte aligned),
+ * u16 = min(max((int)(pred * 65535.0f), 0), 65535) as sf_render16. */
 int sf_wavelet_render(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, uint8_t* rgb8_dev,
                       float* pred_dev);
+int sf_wavelet_render16(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, uint16_t* rgb16_dev,
+                        float* pred_dev);
 /* Adam (+ mask) on the current gradient with learning rate lr; refreshes the low-precision weight images */
 int sf_adam_step(sf_handle* h, float lr);
 /* n_steps x (forward_backward + adam_step) with learning rates lr[0..n_steps) (host array);

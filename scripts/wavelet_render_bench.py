@@ -9,8 +9,12 @@ Model: conf/mlp/wavelet_siren.yaml (128x8).  Per size, HIP-event time per call a
   (a) WaveletSiren.forward in eval mode (a training handle: sf_forward with pred) + decode.to_u8 on the device - what
       decode.render_torch ran for mlp=wavelet_siren before sf_wavelet_render existed;
   (b) sf_wavelet_render to bytes, full window, on a render handle;
-  (c) k_wv_render alone, from the handle's per-kernel profile (a separate profiled pass of (b)).
-The legs alternate in blocks (a b a b) inside one process, so both see the same device state.  Device memory held by each
+  (c) k_wv_render alone, from the handle's per-kernel profile (a separate profiled pass of (b));
+and at 16 bits per sample (decode.bits=16), under keys of their own,
+  (a16) WaveletSiren.forward (sf_forward with pred) + decode.to_u16 - what a user had for 16 bits before
+        sf_wavelet_render16;
+  (b16) sf_wavelet_render16 to uint16 samples, full window, on the same render handle.
+The legs alternate in blocks (a b a16 b16 a b a16 b16) inside one process, so both see the same device state.  Device memory held by each
 path's handle: torch.cuda.mem_get_info before / after creation in a fresh child process per handle.
 """
 import argparse
@@ -27,7 +31,7 @@ YAML = dict(depth=8, hidden_size=128, wavelet_levels=1, first_omega_0=50.0, hidd
 def time_leg(S, calls, warmup):
     from implicit_image._engine import WaveletRenderEngine
     from implicit_image.data import get_grid
-    from implicit_image.decode import to_u8
+    from implicit_image.decode import to_u8, to_u16
     from implicit_image.models import registry
     torch.manual_seed(0)
     model = registry["wavelet_siren"](**YAML).cuda().eval()
@@ -38,6 +42,7 @@ def time_leg(S, calls, warmup):
     rn.set_coords(lin, lin)
     rn.set_params(flat)
     u8 = torch.empty(S, S, 3, dtype=torch.uint8, device="cuda")
+    u16 = torch.empty(S, S, 3, dtype=torch.int16, device="cuda")       # (uint16 samples; int16 is what every torch converts)
 
     def model_bytes():
         with torch.no_grad():
@@ -46,9 +51,18 @@ def time_leg(S, calls, warmup):
     def render():
         rn.lib.sf_wavelet_render(rn.h, 0, S, 0, S, u8.data_ptr(), None)
 
-    legs = {"model_forward_plus_torch_bytes": model_bytes, "wavelet_render_bytes": render}
+    def model_u16():
+        with torch.no_grad():
+            return to_u16(model(grid))
+
+    def render16():
+        rn.lib.sf_wavelet_render16(rn.h, 0, S, 0, S, u16.data_ptr(), None)
+
+    legs = {"model_forward_plus_torch_bytes": model_bytes, "wavelet_render_bytes": render,
+            "model_forward_plus_torch_u16": model_u16, "wavelet_render16_samples": render16}
     ms = alternate(legs, calls, warmup)
     same = bool(torch.equal(model_bytes(), u8))
+    same16 = bool(torch.equal(model_u16(), u16.to(torch.int32) & 0xFFFF))
     rn.profile(True)
     rn.profile_reset()
     for _ in range(calls):
@@ -57,13 +71,16 @@ def time_leg(S, calls, warmup):
     rn.profile(False)
     rn.close()
     model._unbind()
-    del u8, grid
+    del u8, u16, grid
     torch.cuda.empty_cache()
     r = {k: stats(v) for k, v in ms.items()}
     a, b = r["model_forward_plus_torch_bytes"], r["wavelet_render_bytes"]
     r["profiled_per_call_ms"] = {k: v["total_ms"] / calls for k, v in rep.items() if v["launches"]}
     r["k_wv_render_ms"] = rep["k_wv_render"]["total_ms"] / max(rep["k_wv_render"]["launches"], 1)
     r["bytes_identical"] = same
+    r["samples16_identical"] = same16
+    r["render16_over_model_plus_u16"] = r["wavelet_render16_samples"]["median_ms"] / r["model_forward_plus_torch_u16"]["median_ms"]
+    r["render16_over_render_bytes"] = r["wavelet_render16_samples"]["median_ms"] / b["median_ms"]
     r["render_over_model_plus_bytes"] = b["median_ms"] / a["median_ms"]
     r["render_median_not_above_p90_of_a"] = bool(b["median_ms"] <= a["p90_ms"])
     return r
@@ -88,6 +105,7 @@ def main():
         ap.error("--calls must be at least 20")
     res = {"what": "WaveletSiren 128x8, HIP-event ms per call; (a) WaveletSiren.forward (training handle) + torch byte conversion, "
                    "(b) sf_wavelet_render to bytes on a render handle, full window, (c) k_wv_render from the handle's profile; "
+                   "(a16) WaveletSiren.forward + decode.to_u16, (b16) sf_wavelet_render16 to uint16 samples on that render handle; "
                    "handle memory from torch.cuda.mem_get_info in a fresh process per handle",
            "before": device_note(), "sizes": {}}
     for S in args.sizes:
@@ -96,7 +114,9 @@ def main():
         res["sizes"][str(S)] = r
         print(json.dumps({S: {"a_ms": r["model_forward_plus_torch_bytes"]["median_ms"],
                               "a_p90_ms": r["model_forward_plus_torch_bytes"]["p90_ms"],
-                              "b_ms": r["wavelet_render_bytes"]["median_ms"], "k_wv_render_ms": r["k_wv_render_ms"], **mem}}),
+                              "b_ms": r["wavelet_render_bytes"]["median_ms"], "k_wv_render_ms": r["k_wv_render_ms"],
+                              "a16_ms": r["model_forward_plus_torch_u16"]["median_ms"],
+                              "b16_ms": r["wavelet_render16_samples"]["median_ms"], **mem}}),
               flush=True)
     res["after"] = device_note()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
