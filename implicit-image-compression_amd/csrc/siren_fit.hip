@@ -8,7 +8,6 @@
 #include "siren_kernels.hip"
 #include "siren_s8.hip"
 #include "siren_s8h.hip"
-#include "siren_fwd16.hip"
 #include "siren_wide.hip"
 #include "siren_kmeans.hip"
 #include "fourier_kernels.hip"
@@ -36,33 +35,20 @@ using namespace sf;
 
 // hidden 256, 16-bit scratch (k_bwd): 8 waves (two per SIMD), all weight rows in registers, 5 x 32 KiB ring = 160 KiB: 96 KiB
 // in flight; the P0 variant needs more registers and keeps the 4-wave / 4-slot form
-#ifdef SF_EXPERIMENT_P0W8
-constexpr int kBwd16P0WC = 4;
-#else
 constexpr int kBwd16P0WC = 2;
-#endif
-#ifdef SF_EXPERIMENT_NB4
-constexpr int kBwd16NB = 4;
-#else
 constexpr int kBwd16NB = 5;
-#endif
 constexpr int kBwd16P0NB = 4;
-#ifndef SF_BWD8H_PARK
-#define SF_BWD8H_PARK 4
-#endif
+constexpr int kBwd8hPark = 4;   // k_bwd8h: k-steps of every wave's stationary W^T rows parked in LDS
 
 // Every template kernel of the library, in the order the code object holds them.  The compiler emits instantiations in the
 // order of their first use, so this list - their first use - keeps the device code byte for byte what it was measured as,
 // however the host code below is arranged: a host-only change leaves the sha256 of the device object alone.  A kernel the
-// launch code asks for and this list lacks is still built (behind these); one listed and never launched is built too: today
-// that is k_bwd8<32, 256, 1, 8, true, false, OpF16, 8, 0, 0, true>, the 8-slot last-layer form the 4-slot rings replaced.
-// It can go, with its line here, in a change that is allowed to alter device code.
+// launch code asks for and this list lacks is still built (behind these); one listed and never launched would be built too.
 #define SF_K(...) reinterpret_cast<const void*>(&__VA_ARGS__)
 [[maybe_unused]] static const void* const kKernelOrder[] = {
-    SF_K(k_fwd_pipe16<true, SF_FWD_PD>), SF_K(k_fwd_pipe16<false, SF_FWD_PD>),
-    SF_K(k_fwd_pipe<OpF16, true, true, SF_FWD_PD, false>), SF_K(k_fwd_pipe<OpF16, true, false, SF_FWD_PD, false>),
-    SF_K(k_fwd_pipe<OpF16, false, false, SF_FWD_PD, false>), SF_K(k_fwd_pipe<OpBF16, true, false, SF_FWD_PD, false>),
-    SF_K(k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, false>), SF_K(k_bwd<32, 32, 1, 1, true, true, OpF16, 8>),
+    SF_K(k_fwd_pipe<OpF16, true, true, kFwdPD, false>), SF_K(k_fwd_pipe<OpF16, true, false, kFwdPD, false>),
+    SF_K(k_fwd_pipe<OpF16, false, false, kFwdPD, false>), SF_K(k_fwd_pipe<OpBF16, true, false, kFwdPD, false>),
+    SF_K(k_fwd_pipe<OpBF16, false, false, kFwdPD, false>), SF_K(k_bwd<32, 32, 1, 1, true, true, OpF16, 8>),
     SF_K(k_bwd<32, 32, 1, 1, true, true, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, true, false, OpF16, 8>),
     SF_K(k_bwd<32, 32, 1, 1, true, false, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, false, true, OpF16, 8>),
     SF_K(k_bwd<32, 32, 1, 1, false, true, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, false, false, OpF16, 8>),
@@ -96,7 +82,7 @@ constexpr int kBwd16P0NB = 4;
     SF_K(k_bwd8<32, 256, 1, 8, true, true, OpF16, 8, 0, 0, false>),
     SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 8, 0, 0, false>),
     SF_K(k_bwd8<256, 256, 2, 4, false, true, OpF16, 5, 4, 0, false>),
-    SF_K(k_bwd8<256, 256, 2, 4, false, false, OpF16, 5, 2, 3, false>), SF_K(k_bwd8h<SF_BWD8H_PARK>),
+    SF_K(k_bwd8<256, 256, 2, 4, false, false, OpF16, 5, 2, 3, false>), SF_K(k_bwd8h<kBwd8hPark>),
     SF_K(k_bwd8<32, 32, 1, 1, true, true, OpF16, 8, 0, 0, true>),
     SF_K(k_bwd8<32, 32, 1, 1, true, false, OpF16, 8, 0, 0, true>),
     SF_K(k_bwd8<32, 32, 1, 1, false, true, OpF16, 8, 0, 0, true>),
@@ -110,10 +96,8 @@ constexpr int kBwd16P0NB = 4;
     SF_K(k_bwd8<128, 128, 2, 2, false, true, OpF16, 8, 0, 0, true>),
     SF_K(k_bwd8<128, 128, 2, 2, false, false, OpF16, 8, 0, 0, true>),
     SF_K(k_bwd8<32, 256, 1, 8, true, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 8, 0, 0, true>),
     SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 4, 0, 4, true>),
-    SF_K(k_bwd8<256, 256, 2, 4, false, true, OpF16, 6, 5, 0, true>),
-    SF_K(k_bwd8<256, 256, 2, 4, false, false, OpF16, 5, 2, 4, true>), SF_K(k_dw0_8<32, OpF16, 8>),
+    SF_K(k_dw0_8<32, OpF16, 8>),
     SF_K(k_dw0_8<64, OpF16, 8>), SF_K(k_dw0_8<128, OpF16, 8>), SF_K(k_dw0_8<256, OpF16, 4>), SF_K(k_dw0<32, OpF16>),
     SF_K(k_dw0<32, OpBF16>), SF_K(k_dw0<64, OpF16>), SF_K(k_dw0<64, OpBF16>), SF_K(k_dw0<128, OpF16>),
     SF_K(k_dw0<128, OpBF16>), SF_K(k_fwd<32, OpF16, true, true, false>), SF_K(k_fwd<32, OpF16, true, false, false>),
@@ -126,22 +110,20 @@ constexpr int kBwd16P0NB = 4;
     SF_K(k_fwd<128, OpBF16, false, false, false>), SF_K(k_fwd<256, OpF16, true, true, false>),
     SF_K(k_fwd<256, OpF16, true, false, false>), SF_K(k_fwd<256, OpF16, false, false, false>),
     SF_K(k_fwd<256, OpBF16, true, false, false>), SF_K(k_fwd<256, OpBF16, false, false, false>),
-    SF_K(k_wlayer0<OpF16, true>), SF_K(k_wlayer0<OpF16, false>), SF_K(k_wlayer0<OpBF16, false>), SF_K(k_wgemm3<32>),
-    SF_K(k_wgemm3<64>), SF_K(k_wgemm2<0, OpF16, true, 4, false, false>), SF_K(k_wgemm2<0, OpF16, false, 4, false, false>),
-    SF_K(k_wgemm2<0, OpF16, true, 8, false, false>), SF_K(k_wgemm2<0, OpF16, false, 8, false, false>),
-    SF_K(k_wgemm2<0, OpBF16, false, 8, false, false>), SF_K(k_wgemm<1, OpF16>), SF_K(k_wgemm<1, OpBF16>),
+    SF_K(k_wlayer0<OpF16, true>), SF_K(k_wlayer0<OpF16, false>), SF_K(k_wlayer0<OpBF16, false>),
+    SF_K(k_wgemm2<0, OpF16, true, false, false>), SF_K(k_wgemm2<0, OpF16, false, false, false>),
+    SF_K(k_wgemm2<0, OpBF16, false, false, false>), SF_K(k_wgemm<1, OpF16>), SF_K(k_wgemm<1, OpBF16>),
     SF_K(k_wdw<32, OpF16, false>), SF_K(k_wdw<32, OpBF16, false>), SF_K(k_wdw<256, OpF16, true>),
-    SF_K(k_wdw<256, OpF16, false>), SF_K(k_wdw<256, OpBF16, false>), SF_K(k_wgemm2<2, OpF16, true, 8, false, true>),
-    SF_K(k_wgemm2<2, OpF16, true, 8, true, true>), SF_K(k_wgemm2<2, OpF16, true, 4, false, false>),
-    SF_K(k_wgemm2<2, OpF16, false, 4, false, false>), SF_K(k_wgemm2<2, OpF16, true, 8, false, false>),
-    SF_K(k_wgemm2<2, OpF16, false, 8, false, false>), SF_K(k_wgemm2<2, OpBF16, false, 8, false, false>),
+    SF_K(k_wdw<256, OpF16, false>), SF_K(k_wdw<256, OpBF16, false>), SF_K(k_wgemm2<2, OpF16, true, false, true>),
+    SF_K(k_wgemm2<2, OpF16, true, true, true>), SF_K(k_wgemm2<2, OpF16, true, false, false>),
+    SF_K(k_wgemm2<2, OpF16, false, false, false>), SF_K(k_wgemm2<2, OpBF16, false, false, false>),
     SF_K(k_dw0<256, OpF16>), SF_K(k_dw0<256, OpBF16>), SF_K(k_ff_fwd<32, false, false>), SF_K(k_ff_fwd<32, true, false>),
     SF_K(k_ff_bwd<32>), SF_K(k_ff_fwd<64, false, false>), SF_K(k_ff_fwd<64, true, false>), SF_K(k_ff_bwd<64>),
     SF_K(k_ff_fwd<128, false, false>), SF_K(k_ff_fwd<128, true, false>), SF_K(k_ff_bwd<128>),
     SF_K(k_ff_fwd<256, false, false>), SF_K(k_ff_fwd<256, true, false>), SF_K(k_ff_bwd<256>), SF_K(k_ff_dw<1, true>),
     SF_K(k_ff_dw<2, true>), SF_K(k_ff_dw<4, true>), SF_K(k_ff_dw<1, false>), SF_K(k_ff_dw<2, false>),
-    SF_K(k_ff_dw<4, false>), SF_K(k_fwd_pipe<OpF16, false, false, SF_FWD_PD, true>),
-    SF_K(k_fwd_pipe<OpBF16, false, false, SF_FWD_PD, true>), SF_K(k_fwd<32, OpF16, false, false, true>),
+    SF_K(k_ff_dw<4, false>), SF_K(k_fwd_pipe<OpF16, false, false, kFwdPD, true>),
+    SF_K(k_fwd_pipe<OpBF16, false, false, kFwdPD, true>), SF_K(k_fwd<32, OpF16, false, false, true>),
     SF_K(k_fwd<32, OpBF16, false, false, true>), SF_K(k_fwd<64, OpF16, false, false, true>),
     SF_K(k_fwd<64, OpBF16, false, false, true>), SF_K(k_fwd<128, OpF16, false, false, true>),
     SF_K(k_fwd<128, OpBF16, false, false, true>), SF_K(k_fwd<256, OpF16, false, false, true>),
@@ -231,7 +213,6 @@ struct sf_engine {
   uint16_t *wf = nullptr, *wf_last = nullptr, *wb = nullptr, *wb_last = nullptr;
   f32x4* l0tab = nullptr;
   uint16_t* l0img = nullptr;   // layer 0 as MFMA fragments (hidden 256: k_fwd_pipe)
-  uint16_t *wf16 = nullptr, *wf16_last = nullptr, *l0img16 = nullptr;   // images of the 16x16x32 forward (k_fwd_pipe16)
   float* lsc = nullptr;        // fp8 deltas: link[16] | inv[16] (k_fp8_norms + k_fp8_links), rebuilt with the weight images
   float* biasw = nullptr;   // wide path: pre-scaled fp32 biases of layers 1..D-1
   bool wide = false;        // hidden > 256: layer-at-a-time kernels (siren_wide.hip)
@@ -258,7 +239,6 @@ struct sf_engine {
   float* slab = nullptr;
   int dw_wg = 0;
   float* sse_part = nullptr;
-  long n_sse = 0;
   double* sse_dev = nullptr;
   // graph replay of whole training steps (sf_step): small fits are bound by launch latency, not by the kernels
   hipStream_t gstream = nullptr;
@@ -326,7 +306,7 @@ struct sf_engine {
 namespace {
 
 // Timing scope of one profile record: while it lives, what the handle launches lies between two events (when profiling).
-// Several kernels under one scope are one record (k_fp8_norms + k_fp8_links + k_images + k_images16 under K_IMAGES).
+// Several kernels under one scope are one record (k_fp8_norms + k_fp8_links + k_images under K_IMAGES).
 struct Launch {
   sf_engine* h;
   bool on;
@@ -469,14 +449,11 @@ int launch_fp8_scales(sf_engine* h) {
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 size_t fwd_lds_bytes(int WD) { return (size_t)FwdGeom(WD).PIECES * 1024 + (size_t)WD * 16 + 64; }
-// k_fwd_pipe / k_fwd_pipe16: weight image halves + layer-0 image + SSE partials
+// k_fwd_pipe: weight image halves + layer-0 image + SSE partials
 size_t fwd_pipe_lds_bytes() { return (size_t)FwdGeom(256).PIECES * 1024 + (size_t)(256 / 32) * 1024 + 64; }
 
 // hidden = 256, depth >= 3 run the persistent pipeline kernel (k_fwd_pipe): one workgroup per CU walks the chunk
-bool fwd_is_pipe(const sf_engine* h) {
-  static const bool no_pipe = getenv("SIREN_FIT_FWD_PIPE") && atoi(getenv("SIREN_FIT_FWD_PIPE")) == 0;   // A/B knob
-  return h->WD == 256 && h->D >= 3 && !no_pipe && !h->wide;
-}
+bool fwd_is_pipe(const sf_engine* h) { return h->WD == 256 && h->D >= 3 && !h->wide; }
 // forward workgroups of a chunk with n_super 256-pixel groups (= the chunk's SSE partials)
 int fwd_grid(const sf_engine* h, int n_super) { return fwd_is_pipe(h) && n_super > h->dw_wg ? h->dw_wg : n_super; }
 
@@ -484,15 +461,6 @@ int fwd_grid(const sf_engine* h, int n_super) { return fwd_is_pipe(h) && n_super
 int launch_fwd_pipe(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
   const size_t lds = fwd_pipe_lds_bytes();
   const bool f16 = h->cfg.compute_dtype == SF_F16;
-  // The 16x16x32 re-tile of the pipeline (siren_fwd16.hip) is built, parity-tested and measured 3 % SLOWER than k_fwd_pipe on
-  // the same box (+9 % clock, +11 % cycles: DESIGN.md section 4c): it runs only when SIREN_FIT_FWD16=1 asks for it.
-  static const bool use16 = getenv("SIREN_FIT_FWD16") && atoi(getenv("SIREN_FIT_FWD16")) == 1;
-  if (f16 && h->wf16 && use16 && (!train || h->s8)) {   // phase-byte scratch or evaluation
-    FwdArgs b = a;
-    b.wf = reinterpret_cast<const u32x4*>(h->wf16); b.wf_last = reinterpret_cast<const u32x4*>(h->wf16_last);
-    b.l0img = reinterpret_cast<const u32x4*>(h->l0img16);
-    return train ? launch(h, k_fwd_pipe16<true>, n_wg, 512, lds, b) : launch(h, k_fwd_pipe16<false>, n_wg, 512, lds, b);
-  }
   if (f16 && train && h->s8) return launch(h, k_fwd_pipe<OpF16, true, true>, n_wg, 512, lds, a);
   return with_op(h, [&](auto op) {
     using OP = decltype(op);
@@ -569,6 +537,7 @@ int launch_bwd(sf_engine* h, bool last, bool p0, const BwdLayerArgs& a, int n_wg
 struct Ring8 { int NB, PARK, NBP; };
 template <int WD, bool LAST, bool P0, bool D8>
 constexpr Ring8 bwd8_ring() {
+  static_assert(WD != 256 || !D8 || LAST, "fp8 deltas, width 256, below the last layer: k_bwd8h (launch_bwd8)");
   if (WD != 256) return {8, 0, 0};
   // Ring depths / parked W^T k-steps of the 256-wide 8-wave forms are the combinations hipcc allocates WITHOUT a scratch
   // reload inside the block loop (a reload's vmcnt(0) also waits for every LDS-DMA in flight, i.e. it serialises the loop on
@@ -584,11 +553,8 @@ constexpr Ring8 bwd8_ring() {
   // last layer: 3 MFMAs per block, bound by the latency of a step once its delta output is bytes - rings of 4 slots
   // (72 KiB) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
   // HBM-bound at 5.4 TB/s and the shallower rings cost 0.3 ms: format 12 keeps one workgroup per CU)
-  if (LAST) return P0 ? Ring8{8, 0, 0} : Ring8{4, 0, 4};
-  // hidden: 5 delta slots (40 KiB) + 4 phase slots (32) + X16 (32) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
-  //         (the round-2 kernel: launch_bwd8 runs k_bwd8h instead unless SIREN_FIT_BWD8H=0)
-  // layer 1 (P0, no phase ring): 6 delta slots (48) + X16 (32) + sines (32) + 5 parked (40) + layer-0 table = 156 KiB
-  return P0 ? Ring8{6, 5, 0} : Ring8{5, 2, 4};
+  // (every layer below the last runs k_bwd8h: launch_bwd8)
+  return P0 ? Ring8{8, 0, 0} : Ring8{4, 0, 4};
 }
 template <int WD, bool LAST, bool P0, bool D8>
 int launch_bwd8_k(sf_engine* h, const Bwd8Args& a, int n_wg) {
@@ -599,19 +565,21 @@ int launch_bwd8_k(sf_engine* h, const Bwd8Args& a, int n_wg) {
   return launch(h, k_bwd8<T::JW, T::IW, T::WR, T::WC, LAST, P0, OpF16, NB, PARK, NBP, D8>, n_wg, T::WR * T::WC * 64, lds, a);
 }
 int launch_bwd8h(sf_engine* h, const Bwd8Args& a, int n_wg) {
-  constexpr size_t lds = bwd8h_lds_bytes<SF_BWD8H_PARK>();
+  constexpr size_t lds = bwd8h_lds_bytes<kBwd8hPark>();
   static_assert(lds <= 160 * 1024, "k_bwd8h LDS budget");
-  return launch(h, k_bwd8h<SF_BWD8H_PARK>, n_wg, 512, lds, a);
+  return launch(h, k_bwd8h<kBwd8hPark>, n_wg, 512, lds, a);
 }
 int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
-  if (h->d8 && h->WD == 256 && !last && !p0) {
-    // hidden layers: the slot-per-MFMA pipeline (siren_s8h.hip); SIREN_FIT_BWD8H=0 selects the round-2 kernel (A/B knob)
-    static const bool old_form = getenv("SIREN_FIT_BWD8H") && atoi(getenv("SIREN_FIT_BWD8H")) == 0;
-    if (!old_form) return launch_bwd8h(h, a, n_wg);
-  }
   return with_width(h, [&](auto wd) {
     return with_bool(last, p0, [&](auto l, auto p) {
-      return with_bool(h->d8, [&](auto d) { return launch_bwd8_k<decltype(wd)::value, decltype(l)::value, decltype(p)::value, decltype(d)::value>(h, a, n_wg); });
+      return with_bool(h->d8, [&](auto d) {
+        constexpr int WD = decltype(wd)::value;
+        constexpr bool LAST = decltype(l)::value, P0 = decltype(p)::value, D8 = decltype(d)::value;
+        // fp8 deltas at width 256, every layer below the last: the slot-per-MFMA pipeline (siren_s8h.hip).  The forward of such
+        // a layer is k_fwd_pipe, which spills layer 0's phase bytes too, so run_pass never asks for the P0 form here.
+        if constexpr (WD == 256 && !LAST && D8) return P0 ? fail(SF_ERR_INVALID, "launch_bwd8: no P0 form below the last layer") : launch_bwd8h(h, a, n_wg);
+        else return launch_bwd8_k<WD, LAST, P0, D8>(h, a, n_wg);
+      });
     });
   });
 }
@@ -641,16 +609,6 @@ int launch_dw_first(sf_engine* h, const Dw0Args& a, int n_wg) {
 // the fixed-order slab reduction of one layer's weight and bias gradient into the flat gradient
 int launch_reduce(sf_engine* h, const ReduceArgs& ra) {
   return launch(h, k_reduce, (ra.rows_out * ra.cols_out + ra.rows_out + 15) / 16, 256, 0, ra);
-}
-
-// rms the chunk's residual is scaled to before the deltas become fp8 (k_bwd8<LAST>: G = 2^floor(log2(target / rms))).
-// 0.25, not the 8 of round 2: e4m3 saturates at 448, and on heavy-tailed content (tests' non-smooth image: 0.1 % outlier
-// pixels) the deltas of the early layers, which grow ~1.5x per layer towards layer 0, reached rms 41 at target 8 with 0.3 %
-// of them clipped - 1.6 dB of PSNR lost at 1000 steps.  Swept on that fit (SIREN_FIT_FP8_TARGET, profiles/r03_fp8_target.txt):
-// 8: -1.6 dB, 2: +0.1, 0.5 and 0.125: inside the reference's own 8- vs 2-thread range, 1/32: -0.9 dB (underflow).
-float fp8_target() {
-  static const float t = getenv("SIREN_FIT_FP8_TARGET") ? (float)atof(getenv("SIREN_FIT_FP8_TARGET")) : kFp8Target;
-  return t;
 }
 
 // WaveletSiren: the sub-handles launch on the handle's current stream (graph capture swaps it) and report to its profiler
@@ -708,54 +666,30 @@ int refresh_images_wide(sf_engine* h) {
   return SF_OK;
 }
 
-// persistent grid of the wide GEMMs: per_cu workgroups per CU, a multiple of 8 * n_ob (so XCD and output block are loop
+// persistent grid of the wide GEMMs: one workgroup per CU, a multiple of 8 * n_ob (so XCD and output block are loop
 // invariants), at most one workgroup per tile
-unsigned wgemm_grid(const sf_engine* h, int per_cu, int n_ob, unsigned tiles) {
-  const unsigned pg = (unsigned)(per_cu * h->dw_wg / (8 * n_ob) * (8 * n_ob));
+unsigned wgemm_grid(const sf_engine* h, int n_ob, unsigned tiles) {
+  const unsigned pg = (unsigned)(h->dw_wg / (8 * n_ob) * (8 * n_ob));
   return pg == 0 || pg > tiles ? tiles : pg;
 }
 template <int MODE>
 int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob) {
-  const bool f16 = h->cfg.compute_dtype == SF_F16;
   WGemmArgs b = a;
   b.n_super = n_super; b.n_ob = n_ob;
-  auto tiles = [&](int units) { return (unsigned)((units + 7) / 8 * 8 * n_ob); };
-  const unsigned grid = tiles(n_super);
+  const unsigned grid = (unsigned)((n_super + 7) / 8 * 8 * n_ob);
   if constexpr (MODE == 1) {
     return with_op(h, [&](auto op) { return launch(h, k_wgemm<1, decltype(op)>, grid, 512, (size_t)4 * 4 * 1024 + 64, b); });
   } else {
     if constexpr (MODE == 2) {
       if (h->d8) {   // fp8 deltas (format 8): out always, in for every launch below the last layer's
         const size_t lds8 = (size_t)4 * 32 * 1024;
-        const unsigned pg8 = wgemm_grid(h, 1, n_ob, grid);
-        return a.fscale ? launch(h, k_wgemm2<2, OpF16, true, 8, false, true>, pg8, 512, lds8, b)
-                        : launch(h, k_wgemm2<2, OpF16, true, 8, true, true>, pg8, 512, lds8, b);
+        const unsigned pg8 = wgemm_grid(h, n_ob, grid);
+        return a.fscale ? launch(h, k_wgemm2<2, OpF16, true, false, true>, pg8, 512, lds8, b)
+                        : launch(h, k_wgemm2<2, OpF16, true, true, true>, pg8, 512, lds8, b);
       }
     }
-    if constexpr (MODE == 0) {
-      // k_wgemm3 (epilogue pipelined under the next tile, stores spread evenly) is correct and measured EQUAL to the tile loop below
-      // (DESIGN.md section 4b): opt-in
-      static const bool g3 = getenv("SIREN_FIT_WGEMM3") && atoi(getenv("SIREN_FIT_WGEMM3")) == 1;
-      if (g3 && f16 && h->s8 && (a.ks_in == 32 || a.ks_in == 64)) {   // forward hidden layers with the epilogue pipelined under the next tile
-        b.n_super = 2 * n_super;                            // 128-pixel units
-        b.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
-        const size_t lds3 = (size_t)4 * 24 * 1024 + 1024;
-        const unsigned pg = wgemm_grid(h, 1, n_ob, tiles(b.n_super));
-        return a.ks_in == 32 ? launch(h, k_wgemm3<32>, pg, 512, lds3, b) : launch(h, k_wgemm3<64>, pg, 512, lds3, b);
-      }
-    }
-    static const bool w4 = getenv("SIREN_FIT_WGEMM4") && atoi(getenv("SIREN_FIT_WGEMM4")) == 1;   // A/B knob: four-wave workgroups, two per CU
-    if (w4 && f16 && a.ks_in >= 8) {
-      b.n_super = 2 * n_super;                              // 128-pixel units
-      const size_t lds4 = (size_t)3 * 24 * 1024;
-      const unsigned pg = wgemm_grid(h, 2, n_ob, tiles(b.n_super));
-      return h->s8 ? launch(h, k_wgemm2<MODE, OpF16, true, 4>, pg, 256, lds4, b) : launch(h, k_wgemm2<MODE, OpF16, false, 4>, pg, 256, lds4, b);
-    }
-#ifdef SF_WEXP_STAMP
-    b.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
-#endif
     const size_t lds = (size_t)4 * 32 * 1024;
-    const unsigned pgrid = wgemm_grid(h, 1, n_ob, grid);    // persistent: one workgroup per CU
+    const unsigned pgrid = wgemm_grid(h, n_ob, grid);    // persistent: one workgroup per CU
     if (h->s8 && (MODE == 0 || b.Pprev))                    // phase bytes (format 12; fp16 only: sf_create)
       return launch(h, k_wgemm2<MODE, OpF16, true>, pgrid, 512, lds, b);
     return with_op(h, [&](auto op) { return launch(h, k_wgemm2<MODE, decltype(op)>, pgrid, 512, lds, b); });
@@ -815,7 +749,7 @@ int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
     const int n_wg = (int)(n_pb < (long)h->dw_wg ? n_pb : (long)h->dw_wg);
     if (h->d8)   // fp8 deltas: this chunk's power-of-two factor from its own residual
       SF_TRY(launch(h, k_wchunk_scale, 1, 256, 0, h->sse_part + sse_off - n_super, n_super,
-                    1.0 / ((double)h->cfg.out_features * (double)k.px), gscale(h), h->gpre, fp8_target(), h->scale_dev));
+                    1.0 / ((double)h->cfg.out_features * (double)k.px), gscale(h), h->gpre, kFp8Target, h->scale_dev));
     for (int l = D - 1; l >= 1; --l) {
       const bool last = l == D - 1;
       const bool dl8 = h->d8 && !last;                      // this layer's incoming deltas are fp8 byte pieces
@@ -950,15 +884,6 @@ int refresh_images(sf_engine* h) {
     a.link = h->lsc;
   }
   SF_TRY(launch(h, k_images, (n + 255) / 256, 256, 0, a));
-  if (h->wf16) {
-    Img16Args b;
-    memset(&b, 0, sizeof(b));
-    b.params = h->params; b.depth = h->D; b.out_features = h->cfg.out_features;
-    for (int l = 0; l < h->D; ++l) { b.off_w[l] = h->off_w[l]; b.off_b[l] = h->off_b[l]; }
-    b.wscale = a.wscale; b.hscale = a.hscale; b.sc_first = a.sc_first;
-    b.wf = h->wf16; b.wf_last = h->wf16_last; b.l0img = h->l0img16;
-    SF_TRY(launch(h, k_images16, (n + 255) / 256, 256, 0, b));
-  }
   h->images_dirty = false;
   return SF_OK;
 }
@@ -1086,9 +1011,6 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = 
     fa.pred = pred;
     fa.sse_part = h->sse_part + sse_off;
     const int n_fwd_wg = fwd_grid(h, k.n_super);
-#ifdef SF_EXPERIMENT_STAMP
-    fa.dbg = h->sse_part + h->n_sse;   // 64 spare floats behind the partials
-#endif
     sse_off += n_fwd_wg;
     if (phases & kPassFwd) {
       Launch L(h, K_FWD, flops_fwd_px(h) * npx,
@@ -1133,18 +1055,14 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = 
       if (l > 0 && h->s8) {
         // layer 1: with fp8 deltas at width 256 the pipeline forward also spills layer 0's phase bytes, so this layer runs the
         // hidden-layer kernel (k_bwd8h) like the others; else the form that re-derives the layer-0 phases from the coordinates
-        static const bool l1_old = getenv("SIREN_FIT_BWD8H") && atoi(getenv("SIREN_FIT_BWD8H")) == 0;
-        const bool l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h) && !l1_old, p0 = l - 1 == 0 && !(l0_bytes && !last);
+        const bool l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h), p0 = l - 1 == 0 && !(l0_bytes && !last);
         Bwd8Args ba;
         fill_layer(ba, l);
         ba.sse_part = fa.sse_part; ba.n_part = n_fwd_wg;
         ba.inv_chunk_values = 1.0 / ((double)h->cfg.out_features * (double)k.px);
         ba.n_values = (double)h->cfg.out_features * h->n_total;
-        ba.res_scale = kResScale; ba.target = fp8_target(); ba.scale_out = h->scale_dev;
+        ba.res_scale = kResScale; ba.target = kFp8Target; ba.scale_out = h->scale_dev;
         ba.zeros = reinterpret_cast<const u32x4*>(h->pad8); ba.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
-#ifdef SF_EXPERIMENT_STAMP
-        ba.dbg = h->sse_part + h->n_sse;
-#endif
         // hidden 256: the last-layer kernel keeps two workgroups per CU (its slab rows are 32 wide: the slab has room)
         if (last && !p0 && WD == 256 && h->d8) ra.n_wg = (int)std::min<long>((n_pb + PBS - 1) / PBS, 2L * h->dw_wg);
         const double db = h->d8 ? 1.0 : 2.0;   // bytes per delta
@@ -1334,7 +1252,6 @@ long chunked_sse_parts(const sf_engine* h) {
   return round_super(h->npix) / kSuper + (h->npix + h->chunk_px - 1) / h->chunk_px + 8;
 }
 int alloc_sse(sf_engine* h, long n_sse) {
-  h->n_sse = n_sse;
   SF_TRY(dev_alloc(h, h->sse_part, (size_t)(n_sse + 64) * 4));
   return dev_alloc(h, h->sse_dev, 8);
 }
@@ -1463,7 +1380,6 @@ static int create_handle(const sf_config* cfg, sf_handle** out, bool render, boo
   set_scratch_strides(h);
 
   h->dw_wg = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (const char* e = getenv("SIREN_FIT_BWD_WGS")) { const int v = atoi(e); if (v >= 8 && v <= h->dw_wg) h->dw_wg = v; }   // experiment knob
 
   if (render) {   // parameters, forward weight images, layer-0 table / image, the two coordinate vectors
     if (!sub_network) {
@@ -1485,11 +1401,6 @@ static int create_handle(const sf_config* cfg, sf_handle** out, bool render, boo
     SF_TRY(dev_alloc(h, h->biasw, ((size_t)(D - 2) * WD + 32) * 4));
   } else {
     SF_TRY(dev_alloc(h, h->wb_last, (size_t)WD / 32 * 64 * 16));
-  }
-  if (WD == 256 && D >= 3 && !h->wide && cfg->compute_dtype == SF_F16 && getenv("SIREN_FIT_FWD16") && atoi(getenv("SIREN_FIT_FWD16")) == 1) {
-    SF_TRY(dev_alloc(h, h->wf16, (size_t)(D - 2) * FwdGeom(WD).PIECES * 1024));
-    SF_TRY(dev_alloc(h, h->wf16_last, (size_t)(WD / 16 + 1) * 1024));
-    SF_TRY(dev_alloc(h, h->l0img16, (size_t)(WD / 32) * 1024));
   }
   SF_TRY(dev_alloc(h, h->Pbuf, (size_t)(D - 1) * h->p_stride * 16));
   SF_TRY(dev_alloc(h, h->Dbuf, (size_t)(D - 1) * h->d_stride * 16));
@@ -1740,55 +1651,6 @@ int sf_destroy(sf_handle* h) try {
   if (!h) return SF_OK;
   DevGuard dev_guard(h->cfg.device);
   hipStreamSynchronize(h->stream);
-#ifdef SF_WEXP_STAMP
-  if (h->wide) {
-    float dbg[64];
-    hipMemcpy(dbg, h->pad8 + 8192, sizeof(dbg), hipMemcpyDeviceToHost);
-    for (int m = 0; m < 2; ++m)
-      for (int i = 0; i < 4; ++i)
-        if (dbg[m * 32 + i * 4 + 3] > 0)
-          fprintf(stderr, "k_wgemm2<%d> stamp wg%d wave%d, cycles per tile: all %.0f, waits at the chunk barriers %.0f, epilogue %.0f (%.0f tiles), core clock %.0f MHz\n", m ? 2 : 0,
-                  i >> 1 ? 200 : 3, i & 1 ? 5 : 0, dbg[m * 32 + i * 4], dbg[m * 32 + i * 4 + 1], dbg[m * 32 + i * 4 + 2], dbg[m * 32 + i * 4 + 3], dbg[m * 32 + 16 + i]);
-  }
-#endif
-#ifdef SF_EXPERIMENT_STAMP
-  if (!h->wide) {
-    float dbg[64];
-    hipMemcpy(dbg, h->sse_part + h->n_sse, sizeof(dbg), hipMemcpyDeviceToHost);
-    for (int i = 0; i < 8; ++i)
-      if (dbg[32 + i * 4 + 3] > 0)
-        fprintf(stderr, "k_bwd8 %s stamp wg%d wave%d, cycles per block: barrier at the top %.0f, phase X %.0f, phase W + epilogue %.0f (%.0f blocks)\n",
-                i >= 4 ? "layer-1 form" : "hidden form", (i >> 1) & 1 ? 200 : 3, i & 1 ? 5 : 0, dbg[32 + i * 4], dbg[32 + i * 4 + 1], dbg[32 + i * 4 + 2], dbg[32 + i * 4 + 3]);
-#ifdef SF_EXPERIMENT_STAMP2
-    for (int w = 0; w < 2; ++w) {
-      fprintf(stderr, "k_bwd8h slot stamps wg3 wave%d: X slots", w ? 5 : 0);
-      for (int i = 0; i < 16; ++i) fprintf(stderr, " %.0f", dbg[w * 32 + i]);
-      fprintf(stderr, " | W+E slots");
-      for (int i = 16; i < 32; ++i) fprintf(stderr, " %.0f", dbg[w * 32 + i]);
-      fprintf(stderr, "\n");
-    }
-#else
-    if (h->WD == 256)   // k_fwd_pipe
-      for (int i = 0; i < 4; ++i)
-        fprintf(stderr, "k_fwd_pipe stamp wg%d wave%d, cycles per 256-pixel group: layer 0 %.0f, wait for X1 %.0f, pipeline %.0f (barriers: mid %.0f end %.0f), %.0f, all %.0f; groups %.0f\n",
-                i >> 1 ? 200 : 3, i & 1 ? 5 : 0, dbg[i * 8], dbg[i * 8 + 1], dbg[i * 8 + 2], dbg[i * 8 + 3], dbg[i * 8 + 4], dbg[i * 8 + 5], dbg[i * 8 + 6], dbg[i * 8 + 7]);
-    else
-    for (int i = 0; i < 4; ++i)
-      fprintf(stderr, "k_fwd stamp wg%d wave%d: hidden-layer loop %.0f cycles, barrier 1 (half X) %.0f, barrier 2 (half Y) %.0f, %d layers\n",
-              i >> 1 ? 9000 : 3, i & 1 ? 5 : 0, dbg[i * 4], dbg[i * 4 + 1], dbg[i * 4 + 2], (int)dbg[i * 4 + 3]);
-#endif
-  }
-  if (h->wide) {
-    unsigned long long dbg[32];
-    const size_t sw = 256;
-    hipMemcpy(dbg, (char*)h->slab + (size_t)h->dw_wg * (sw * sw + sw) * 4, sizeof(dbg), hipMemcpyDeviceToHost);
-    for (int i = 0; i < 8; ++i)
-      if (dbg[i * 4 + 3])
-        fprintf(stderr, "stamp wg(x%d,y%d) wave%d: per block wait %.0f stage %.0f compute %.0f cycles (100 MHz ticks x?) nblk %llu\n",
-                (i >> 2) ? 5 : 0, ((i >> 1) & 1) ? 9 : 0, (i & 1) ? 7 : 0, (double)dbg[i * 4] / dbg[i * 4 + 3],
-                (double)dbg[i * 4 + 1] / dbg[i * 4 + 3], (double)dbg[i * 4 + 2] / dbg[i * 4 + 3], dbg[i * 4 + 3]);
-  }
-#endif
   for (auto& r : h->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
   for (sf_engine* s : h->wv_sub) if (s) sf_destroy(s);

@@ -21,20 +21,13 @@
 //   S16      2  x 16 KiB   fp16 sin(phase)    written by the X epilogue in step k, tr-read in step k+1 (W)
 // (included by siren_fit.hip after siren_kernels.hip)
 
-#ifndef SF_BWD8_PF
-#define SF_BWD8_PF 3      // B pieces read ahead in the 4-wave form (register ring of PF + 1)
-#endif
-#ifndef SF_BWD8_PF8
-#define SF_BWD8_PF8 1     // the same in the 8-wave form
-#endif
-#ifndef SF_BWD8_FB2
-#define SF_BWD8_FB2 0
-#endif
-#ifndef SF_BWD8_FA2
-#define SF_BWD8_FA2 0      // 8-wave form: second delta^T fragment buffer (4 registers it does not have)
-#endif
-
 namespace sf {
+
+constexpr int kBwd8PF = 3;           // B pieces read ahead in the 4-wave form (register ring of PF + 1)
+constexpr int kBwd8PF8 = 1;          // the same in the 8-wave form
+constexpr bool kBwd8Tab = true;      // sine / cosine of a phase byte from a table in LDS (see TAB in k_bwd8)
+constexpr bool kBwd8DbSplit = true;  // bias-gradient row sums split over the column waves (see DBSPLIT in k_bwd8)
+constexpr bool kBwd8FA2In8 = true;   // 8-wave form with fp8 deltas: delta^T fragments double-buffered (see FA2 in k_bwd8)
 
 struct Bwd8Args {
   const u32x4* D;       // LAST: dL/dout, 16-bit float, ONE piece (k-step 0) per pixel block; else fp8 deltas of layer l,
@@ -60,7 +53,7 @@ struct Bwd8Args {
   double n_values;             // out_features * H * W of the full image
   float res_scale, target;
   float* scale_out;
-  float* dbg;                  // SF_EXPERIMENT_STAMP builds only
+  float* dbg;                  // unused, always null: keeps the argument layout the kernels were measured with
   const u32x4* zeros;          // k_bwd8h: 1 KiB of zeros (delta pieces beyond the last block)
   u32x4* dump;                 // k_bwd8h: 8 KiB nobody reads (deltas of the blocks beyond the last)
 };
@@ -133,14 +126,11 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     for (int s = KSR; s < KSX; ++s)
       reinterpret_cast<u32x4*>(sWsp + (x * WSP + s - KSR) * 1024)[lane] = a.wb[((xit0 + x) * KSX + s) * 64 + lane];
   }
-#ifndef SF_BWD8_TAB
-#define SF_BWD8_TAB 1
-#endif
   // A phase byte has 256 values: sin and cos of its decoded phase come from a 1 KiB table in LDS (one ds_read_b32 per value:
   // the pair as two 16-bit floats) instead of v_cvt_f32_ubyte + v_fma + v_sin + v_cos per value - the X epilogue is what
   // bounds phase W (VALU issue of two waves per SIMD).  The sine is the value the table-free form wrote to S16 bit for bit;
   // the cosine is rounded to 16 bits before it meets the accumulator (whose product is rounded to 8 or 16 bits anyway).
-  constexpr bool TAB = SF_BWD8_TAB && !P0 && std::is_same<OP, OpF16>::value;
+  constexpr bool TAB = kBwd8Tab && !P0 && std::is_same<OP, OpF16>::value;
   uint32_t* const sTab = reinterpret_cast<uint32_t*>(wsp0 + (size_t)NW * XT * WSP * 1024);
   if (TAB) {
     for (int i = tid; i < 256; i += NW * 64) {
@@ -190,10 +180,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   for (int x = 0; x < WJ; ++x)
 #pragma unroll
     for (int y = 0; y < WI; ++y) acc[x][y] = f32x16{};
-#ifndef SF_BWD8_DBSPLIT
-#define SF_BWD8_DBSPLIT 1
-#endif
-  constexpr bool DBSPLIT = IN8 && SF_BWD8_DBSPLIT;   // bias-gradient row sums split over the column waves (IN8 form only: registers)
+  constexpr bool DBSPLIT = IN8 && kBwd8DbSplit;   // bias-gradient row sums split over the column waves (IN8 form only: registers)
   float dbs[WJ];
 #pragma unroll
   for (int x = 0; x < WJ; ++x) dbs[x] = 0.f;
@@ -234,14 +221,10 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     x1 = ((float)col * a.inv_wm1 - 0.5f) * 2.0f;
   };
 
-  constexpr int PF = NW <= 4 ? (KSX >= 4 ? SF_BWD8_PF : 1) : SF_BWD8_PF8;
+  constexpr int PF = NW <= 4 ? (KSX >= 4 ? kBwd8PF : 1) : kBwd8PF8;
   constexpr int NXB = PF + 1;
   constexpr int ESUB = 8;                       // epilogue slices per row tile: (q, quarter) groups of 2 values
-  constexpr bool FB2 = SF_BWD8_FB2 && NW <= 4;  // both pixel k-steps of the activation fragments resident
-#ifndef SF_BWD8_FA2_IN8
-#define SF_BWD8_FA2_IN8 1
-#endif
-  constexpr bool FA2 = SF_BWD8_FA2 || NW <= 4 || (IN8 && SF_BWD8_FA2_IN8);  // delta^T fragments double-buffered
+  constexpr bool FA2 = NW <= 4 || (IN8 && kBwd8FA2In8);  // delta^T fragments double-buffered
   constexpr int NWC = 2 * WJ;                   // W chunks per step
   constexpr int NE = XT * ESUB;                 // epilogue slices per step
   // ---- LDS addressing --------------------------------------------------------------------------------------
@@ -336,12 +319,8 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     if ((v & 1) == 0) ep_sn = sn;
     else *(__attribute__((address_space(3))) u32x2*)(uintptr_t)((q ? bSx : bS) + x * 2048 + q * 1024 + 4 * (v - 1)) = u32x2{ep_sn, sn};
     if (v == 3) {   // bytes 8q .. 8q+7 of this lane's piece element
-#ifndef SF_EXPERIMENT_NO_STORE
       if (D8) reinterpret_cast<u32x2*>(&a.Dout[((pb_begin + k * pb_step) * IT + it) * 64 + lane])[q] = u32x2{ep_d[x].x, ep_d[x].y};
       else store_stream(&a.Dout[((pb_begin + k * pb_step) * KSI + ks) * 64 + lane], ep_d[x]);
-#else
-      asm volatile("" ::"v"(ep_d[x]));
-#endif
     }
   };
   auto w_mma_chunk = [&](int x, const u32x4& fa, const u32x4* fb) {
@@ -369,15 +348,9 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   // latency; the 8-wave form has neither the registers nor the need (its SIMD partner fills the gap): PF = 1.
   // W: 2*WJ chunks of WI MFMAs; the VALU epilogue of the X tiles (XT*ESUB slices of 2 values) rides along.
   typedef typename RawFrag<IN8>::type raw_t;
-#ifdef SF_EXPERIMENT_STAMP
-  unsigned long long st_bar = 0, st_x = 0, st_w = 0, st_n = 0;
-#endif
   auto step = [&](int kx, bool do_c, bool do_x, bool do_w) {
-#ifdef SF_EXPERIMENT_STAMP
-    const unsigned long long t_s0 = __builtin_amdgcn_s_memtime();
-#endif
     u32x4 xb[NXB];
-    u32x4 fb[FB2 ? 2 : 1][WI];
+    u32x4 fb[WI];                 // activation fragments of one pixel k-step
     raw_t fa[2];
     f32x16 g[XT];
     // wave-uniform buffer offsets of this step (SGPRs): ring slots of the deltas of block kx (X) and of block kx-1 (W, this
@@ -419,8 +392,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
       for (int c = 0; c < PF && c < XT * KSX; ++c) xb[c % NXB] = x_load(c % KSX);
     }
     if (do_w && (!do_x || XT * KSX <= PF)) {
-      wb_load(0, fb[0]); fa[0] = wa_load(0, 0);
-      if (FB2) wb_load(1, fb[FB2 ? 1 : 0]);
+      wb_load(0, fb); fa[0] = wa_load(0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
     if (do_x) {
@@ -434,8 +406,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
           const int i = x * KSX + c;
           if (i + PF < XT * KSX) xb[(i + PF) % NXB] = x_load((i + PF) % KSX);
           else if (do_w && i + PF == XT * KSX) {     // first W operands ride behind the last B piece
-            wb_load(0, fb[0]); fa[0] = wa_load(0, 0);
-            if (FB2) wb_load(1, fb[FB2 ? 1 : 0]);
+            wb_load(0, fb); fa[0] = wa_load(0, 0);
           }
           g[x] = OP::mfma(w_of(x, c), xb[i % NXB], g[x]);
           if (CVX && do_c) {
@@ -444,16 +415,12 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
             if (i == 10) *(lds_v4*)(uintptr_t)(cv_dst + 1024u) = fp8x8_to_f16(cv_raw.z, cv_raw.w);
           }
           if (PF == 0 && do_w && i + 1 == XT * KSX) {   // no read-ahead: the first W operands follow the last X MFMA
-            wb_load(0, fb[0]); fa[0] = wa_load(0, 0);
-            if (FB2) wb_load(1, fb[FB2 ? 1 : 0]);
+            wb_load(0, fb); fa[0] = wa_load(0, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     }
-#ifdef SF_EXPERIMENT_STAMP
-    const unsigned long long t_s1 = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
@@ -464,13 +431,13 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
             if (x + 1 < WJ) fa[(i + 1) & 1] = wa_load(kk, x + 1);
             else if (kk == 0) fa[(i + 1) & 1] = wa_load(1, 0);
           }
-          w_mma_chunk(x, frag_of(fa[FA2 ? (i & 1) : 0]), fb[FB2 ? kk : 0]);
+          w_mma_chunk(x, frag_of(fa[FA2 ? (i & 1) : 0]), fb);
           if (!FA2) {   // single fragment buffer: the next one is requested once the MFMAs of this chunk have issued
             if (x + 1 < WJ) fa[0] = wa_load(kk, x + 1);
             else if (kk == 0) fa[0] = wa_load(1, 0);
           }
-          // 8-wave form: the fragments of the second pixel k-step replace the first once their last MFMA has issued
-          if (!FB2 && kk == 0 && x + 1 == WJ) wb_load(1, fb[0]);
+          // the fragments of the second pixel k-step replace the first once their last MFMA has issued
+          if (kk == 0 && x + 1 == WJ) wb_load(1, fb);
         }
         if (do_x) {
 #pragma unroll
@@ -479,10 +446,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#ifdef SF_EXPERIMENT_STAMP
-    const unsigned long long t_s2 = __builtin_amdgcn_s_memtime();
-    if (do_x && do_w) { st_x += t_s1 - t_s0; st_w += t_s2 - t_s1; st_n += 1; }
-#endif
   };
 
   if (nblk > 0) {
@@ -511,13 +474,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     asm volatile("" ::: "memory");
     if (nblk > 1) step(0, true, true, false); else step(0, false, true, false);
     for (int k = 1; k + 1 < nblk; ++k) {
-#ifdef SF_EXPERIMENT_STAMP
-      const unsigned long long t_b0 = __builtin_amdgcn_s_memtime();
-#endif
       if (k >= YS && k - 1 + AX < nblk) bar_dma<YS * (GD + GP + S_ST)>(); else bar_all();
-#ifdef SF_EXPERIMENT_STAMP
-      st_bar += __builtin_amdgcn_s_memtime() - t_b0;
-#endif
       if (k + AD < nblk) stageD(k + AD);
       if (k + AP < nblk) stageP(k + AP);
       asm volatile("" ::: "memory");
@@ -530,12 +487,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     bar_lds();
     step(nblk, false, false, true);
   }
-#if defined(SF_EXPERIMENT_STAMP) && !defined(SF_EXPERIMENT_STAMP2)
-  if (a.dbg && !LAST && lane == 0 && (wave == 0 || wave == 5) && (blockIdx.x == 3 || blockIdx.x == 200) && st_n) {
-    float* o = a.dbg + 32 + ((blockIdx.x == 3 ? 0 : 2) + (wave == 0 ? 0 : 1)) * 4 + (P0 ? 16 : 0);
-    o[0] = (float)st_bar / (float)st_n; o[1] = (float)st_x / (float)st_n; o[2] = (float)st_w / (float)st_n; o[3] = (float)st_n;
-  }
-#endif
   float* slab = a.slab + (size_t)blockIdx.x * (JW * IW + JW);
   const int cl = lane & 31, hh = lane >> 5;
 #pragma unroll

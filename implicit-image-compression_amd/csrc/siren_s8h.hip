@@ -39,9 +39,7 @@
 
 namespace sf {
 
-#ifndef SF_BWD8H_LD
-#define SF_BWD8H_LD 2      // slots between a table lookup and the value that uses it
-#endif
+constexpr int kBwd8hLD = 2;      // slots between a table lookup and the value that uses it
 
 template <int PARK>
 constexpr size_t bwd8h_lds_bytes() { return (size_t)(1 + 5 * 8 + 4 * 8 + 3 * 16 + 8 * PARK) * 1024; }
@@ -53,7 +51,7 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
   typedef OpF16 OP;
   constexpr int KS = 16, NT = 8, NBD = 5, NBP = 4, WJ = 4, WI = 2;
   constexpr int AD = 3, AP = 3;                  // blocks requested ahead (deltas / phases)
-  constexpr int LD = SF_BWD8H_LD, NTAB = 2 * (LD + 1);   // table ring of phase X: LD + 1 pairs in flight
+  constexpr int LD = kBwd8hLD, NTAB = 2 * (LD + 1);   // table ring of phase X: LD + 1 pairs in flight
   constexpr int KSR = KS - PARK;
   constexpr uint32_t oRD = 1024, oRP = oRD + NBD * 8192, oS16 = oRP + NBP * 8192, oWP = oS16 + 3 * 16384;
   static_assert(LD >= 1 && LD <= 4 && PARK >= 0 && PARK <= 4, "slot plan");
@@ -131,15 +129,6 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
     return u32x4{a0.x, a0.y, a1.x, a1.y};
   };
 
-#ifdef SF_EXPERIMENT_STAMP
-  unsigned long long st_bar = 0, st_x = 0, st_w = 0, st_n = 0;
-#endif
-#ifdef SF_EXPERIMENT_STAMP2
-  unsigned st2[32];
-#pragma unroll
-  for (int i = 0; i < 32; ++i) st2[i] = 0u;
-  unsigned st2_n = 0;
-#endif
   // ---- the two phases of a block, 16 slots each -----------------------------------------------------------------------
   //   phase X(k)            16 MFMAs of the data-gradient product (one dependent chain); B operand = the bytes of D(k),
   //                         converted in registers one slot ahead
@@ -182,9 +171,6 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
     } else {
       adr = (t & 3) == 3 ? (w >> 24) << 2 : (((w >> (8 * (t & 3))) & 0xffu) << 2);
     }
-#ifdef SF_EXP_NOLOOKUP     // timing-only: no table read
-    return adr | 0x3c000000u;
-#endif
     return *(lds_cu32*)(uintptr_t)adr;
   };
   struct WOps { uint32_t a, b1, b2; };      // base registers of the operand fragments of a phase W
@@ -220,15 +206,9 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
     u32x4 pw;                                      // the sixteen phase bytes of this lane
     uint32_t tab[NTAB];                            // table pairs in flight
     uint32_t sp[4];                                // sines of a k-step, as 16-bit pairs
-#ifdef SF_BWD8H_XPRIO
-    __builtin_amdgcn_s_setprio(SF_BWD8H_XPRIO);
-#endif
     bq[0] = fp8x8_to_f16(raw[0].x, raw[0].y);
     pw = *(lds_cv4*)(uintptr_t)base(aLN, uEp);
     slot_end();
-#ifdef SF_EXPERIMENT_STAMP2
-    unsigned st2_t = (unsigned)__builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
       if (j == 2 && dma == 1) stageD(dsrc, rslot);
@@ -259,24 +239,14 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
           asm volatile("" : "+v"(sn), "+v"(cs));
           cp[i] = cs;
           sp[i] = sn;
-#ifndef SF_EXP_NOSINW
           if (i == 3) *(lds_v4*)(uintptr_t)base(aL1, uEs) = u32x4{sp[0], sp[1], sp[2], sp[3]};
-#endif
         }
       }
       if (j == 5) pwh = u32x2{pw.z, pw.w};
       // (S waves only: the N waves' next phase W reads sines the S waves are still writing in this half)
-#ifdef SF_EXP_NPRE   // timing-only (races with the S waves' sine writes)
-      if (j == KS - 4)
-#else
-      if (ROLE == 1 && j == KS - 4)
-#endif
-      { wo.b1 = base(aT1, w_uni_s(wsbuf)); wo.b2 = base(aT2, w_uni_s(wsbuf)); wb_load(wo, 0, fb[0]); }
+      if (ROLE == 1 && j == KS - 4) { wo.b1 = base(aT1, w_uni_s(wsbuf)); wo.b2 = base(aT2, w_uni_s(wsbuf)); wb_load(wo, 0, fb[0]); }
       if (j == KS - 2) { wo.a = base(aT8, w_uni_d(wdslot)); fa8[0] = wa_load(wo, 0, 0); fa8[1] = wa_load(wo, 0, 1); }
       slot_end();
-#ifdef SF_EXPERIMENT_STAMP2
-      { const unsigned tn = (unsigned)__builtin_amdgcn_s_memtime(); st2[j] += tn - st2_t; st2_t = tn; }
-#endif
     }
   };
   // W(kw) + E(ke): odst = where this wave's piece of the deltas of block ke goes (the dump for blocks outside the chunk).
@@ -288,15 +258,7 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
     asm volatile("" : "=v"(ep_d));
     uint32_t tab[LD + 2];              // table pairs of values 8..15 in flight (the pair of value t-1 is still read in slot t)
     uint32_t sp[3] = {0u, 0u, 0u};
-#ifdef SF_EXPERIMENT_STAMP2
-    unsigned st2_t = (unsigned)__builtin_amdgcn_s_memtime();
-#endif
-#ifdef SF_BWD8H_WPRIO
-    __builtin_amdgcn_s_setprio(SF_BWD8H_WPRIO);
-#endif
-#ifndef SF_EXP_NPRE
     if (ROLE == 0) { wo.b1 = base(aT1, w_uni_s(wsbuf)); wo.b2 = base(aT2, w_uni_s(wsbuf)); wb_load(wo, 0, fb[0]); }   // (N waves: S16(kw) was completed in the half before)
-#endif
     fa = fp8x8_to_f16(fa8[0].x, fa8[0].y);
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
@@ -306,12 +268,7 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
       if (y == 0 && i + 2 < 8) fa8[i & 1] = wa_load(wo, (i + 2) >> 2, (i + 2) & 3);   // (the bytes of chunk i + 2: three slots before their conversion)
       if (i == 1 && y == 1) wb_load(wo, 1, fb[1]);
       acc[x][y] = OP::mfma(fa, fb[kk][y], acc[x][y]);
-#ifndef SF_EXP_NODOT
-      if (x == DBX)
-#else
-      if (false)
-#endif
-      {   // bias gradient: row sums of delta^T (two v_dot2_f32_f16 against (1, 1) per slot)
+      if (x == DBX) {   // bias gradient: row sums of delta^T (two v_dot2_f32_f16 against (1, 1) per slot)
         const h2 one2 = __builtin_bit_cast(h2, ones_h2);
         const uint32_t f0 = y == 0 ? fa.x : fa.z, f1 = y == 0 ? fa.y : fa.w;
         dbs = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, f0), one2, dbs, false);
@@ -337,26 +294,17 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
           if (t >= 9) {
             const uint32_t sn = __builtin_amdgcn_perm(e, tab[(t - 1) % (LD + 2)], 0x05040100u);      // (sin t-1, sin t)
             if (t < 15) sp[(t - 9) >> 1] = sn;
-#ifndef SF_EXP_NOSINW
             else *(lds_v4*)(uintptr_t)base(aL1x, uEs + 1024u) = u32x4{sp[0], sp[1], sp[2], sn};
-#endif
           }
         } else {
           asm volatile("" : "+v"(sv));   // formed in its own slot
           sv_even = sv;
         }
         if (t == 15) {
-#ifndef SF_EXPERIMENT_NO_STORE
           odst[lane] = ep_d;
-#else
-          asm volatile("" ::"v"(ep_d));
-#endif
         }
       }
       slot_end();
-#ifdef SF_EXPERIMENT_STAMP2
-      { const unsigned tn = (unsigned)__builtin_amdgcn_s_memtime(); st2[16 + t] += tn - st2_t; st2_t = tn; }
-#endif
     }
   };
 
@@ -404,30 +352,12 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
       const u32x4* const dsrc = k + AD < nblk ? pD : a.zeros;
       // E(k) of the N waves, E(k - 1) of the S waves: blocks outside the chunk go to the dump
       u32x4* const odst = (unsigned)(ROLE == 0 ? k : k - 1) < (unsigned)nblk ? pO : dump;
-#ifdef SF_EXPERIMENT_STAMP
-      const unsigned long long t_b0 = __builtin_amdgcn_s_memtime();
-#endif
       if (ROLE == 1) bar_dma<6>(); else bar_lds();
-#ifdef SF_EXPERIMENT_STAMP
-      const unsigned long long t_b1 = __builtin_amdgcn_s_memtime();
-#endif
       if (ROLE == 0) phaseX(d_0, 2, pP, pm1, pc, s_0, d_m1, s_m1, wo);                    // X(k) + sines(k); P(k+3); operands of W(k-1) requested
       else phaseW(odst, s_m1, 0u, 2, pP, pm1, d_0, wo);                                   // W(k-2) + E(k-1); P(k+3); bytes of X(k) requested
-#ifdef SF_EXPERIMENT_STAMP
-      const unsigned long long t_b2 = __builtin_amdgcn_s_memtime();
-#endif
       if (ROLE == 0) bar_dma<5>(); else bar_lds();
-#ifdef SF_EXPERIMENT_STAMP
-      const unsigned long long t_b3 = __builtin_amdgcn_s_memtime();
-#endif
       if (ROLE == 0) phaseW(odst, s_0, s_m1, 1, dsrc, d_m2, d_p1, wo);                    // W(k-1) + E(k); D(k+3); bytes of X(k+1) requested
       else phaseX(d_0, 1, dsrc, d_m2, pc, s_0, d_m1, s_m1, wo);                           // X(k) + sines(k); D(k+3); operands of W(k-1) requested
-#ifdef SF_EXPERIMENT_STAMP
-      { const unsigned long long t_b4 = __builtin_amdgcn_s_memtime(); st_bar += (t_b1 - t_b0) + (t_b3 - t_b2); st_x += t_b2 - t_b1; st_w += t_b4 - t_b3; st_n += 1; }
-#endif
-#ifdef SF_EXPERIMENT_STAMP2
-      st2_n += 1;
-#endif
       { const uint32_t t = d_m2; d_m2 = d_m1; d_m1 = d_0; d_0 = d_p1; d_p1 = d_p2; d_p2 = t; }
       { const uint32_t t = s_m1; s_m1 = s_0; s_0 = s_p1; s_p1 = t; }
       pc = (pc + 8192u) & 0x6000u;
@@ -437,19 +367,6 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
     }
     bar_all();     // no LDS-DMA of this workgroup is in flight when its LDS is handed on
   }
-#ifdef SF_EXPERIMENT_STAMP2
-  if (a.dbg && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x == 3 && st2_n) {
-    float* o = a.dbg + (wave == 0 ? 0 : 32);
-#pragma unroll
-    for (int i = 0; i < 32; ++i) o[i] = (float)st2[i] / (float)st2_n;
-  }
-#endif
-#if defined(SF_EXPERIMENT_STAMP) && !defined(SF_EXPERIMENT_STAMP2)
-  if (a.dbg && lane == 0 && (wave == 0 || wave == 5) && (blockIdx.x == 3 || blockIdx.x == 200) && st_n) {
-    float* o = a.dbg + 32 + ((blockIdx.x == 3 ? 0 : 2) + (wave == 0 ? 0 : 1)) * 4;
-    o[0] = (float)st_bar / (float)st_n; o[1] = (float)st_x / (float)st_n; o[2] = (float)st_w / (float)st_n; o[3] = (float)st_n;
-  }
-#endif
   float* slab = a.slab + (size_t)blockIdx.x * (256 * 256 + 256);
   const int cl = lane & 31, hh = lane >> 5;
 #pragma unroll

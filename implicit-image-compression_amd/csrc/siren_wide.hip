@@ -19,14 +19,6 @@
 
 namespace sf {
 
-#ifdef SF_WEXP_NOSTORE   // timing-only: the GEMM epilogues compute their values and drop them
-#define WST(dst, val) do { auto v_ = (val); asm volatile("" ::"v"(v_)); } while (0)
-#elif defined(SF_WEXP_NTSTORE)   // A/B: non-temporal epilogue stores
-#define WST(dst, val) __builtin_nontemporal_store((val), &(dst))
-#else
-#define WST(dst, val) (dst) = (val)
-#endif
-
 // ---------------------------------------------------------------------------------------------------------
 // blocked A image: [ob][chunk c][tile ot][s4][lane][8] ; chunk = 4 k-steps ; OT tiles of 32 rows per block
 // element (ob, c, ot, s4, lane=(r,h), j) = M[(ob*OT + ot)*32 + r][16*(4c + s4) + PI(h, j)] * scale   (0 outside)
@@ -149,7 +141,7 @@ struct WGemmArgs {
   int ks_out;
   int kp_out;            // P8: phase-byte pieces per pixel block (= width / 32) of Out (MODE 0) / Pprev (MODE 2)
   const u32x4* Pprev;    // MODE 2: phases of the layer whose delta is produced (same geometry as Out)
-  u32x4* dump;           // k_wgemm3: 8 KiB the first tile's (empty) epilogue is stored to
+  u32x4* dump;           // unused, always null: keeps the argument layout the kernels were measured with
   const float* fscale;   // MODE 2, fp8 out: *fscale multiplies the outgoing deltas (the chunk factor, last layer's launch); nullptr: 1
   // MODE 1 (last layer)
   const float* img; float* pred; float gscale; float* sse_part; u32x4* Dlast; long pix0, npix;
@@ -292,20 +284,16 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
 // L2 -> CU bytes by a third.  Chunk = 2 k-steps: 16 A pieces + 16 B pieces = 32 KiB per slot, 4 slots, staged
 // three chunks ahead (4 LDS-DMA instructions per wave per chunk, counted vmcnt).
 // P8: the phases are bytes (scratch_format 12, see k_wlayer0): one piece per (pixel block, 32-neuron tile) instead of two.
-// NWV = 4 (round 3): the same tile plan with FOUR waves per workgroup - 256 neurons x 128 pixels, 24 KiB per chunk, a ring
-// of three - so that TWO workgroups share a CU (2 x 72 KiB of LDS, 2 waves per SIMD as before): they drift apart, and the
-// epilogue of one (128 sines per thread, matrix pipe idle) runs beside the main loop of the other.  a.n_super then counts
-// 128-pixel units.
 // IN8 / OUT8 (MODE 2, scratch_format 8 on the wide path, round 3): the incoming / outgoing deltas are fp8 e4m3 byte pieces, one
 // per (pixel block, 32-neuron tile) in the phase-byte layout: a B chunk of two k-steps is ONE piece per pixel block (converted
 // in registers, exact), a tile's sixteen outgoing values leave in one store.  Scales: csrc/siren_kernels.hip k_fp8_links.
-template <int MODE, typename OP, bool P8 = false, int NWV = 8, bool IN8 = false, bool OUT8 = false>
-__global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs a) {
+template <int MODE, typename OP, bool P8 = false, bool IN8 = false, bool OUT8 = false>
+__global__ __launch_bounds__(512, 1) void k_wgemm2(WGemmArgs a) {
   static_assert(MODE == 0 || MODE == 2, "last layer: k_wgemm<1>");
-  static_assert(NWV == 8 || NWV == 4, "waves per workgroup");
   static_assert(MODE == 2 || (!IN8 && !OUT8), "fp8 deltas: the data-gradient product only");
+  constexpr int NWV = 8;                                         // waves per workgroup
   constexpr int OT = 8, TW = 4, PBW = 2, NPB = NWV;              // pixel blocks per workgroup: two per wave pair
-  constexpr int NB = NWV == 8 ? 4 : 3, PD = NB - 1, SLOT = (16 + 2 * NPB) * 1024;
+  constexpr int NB = 4, PD = NB - 1, SLOT = (16 + 2 * NPB) * 1024;
   constexpr int GA = 16 / NWV, GB = (IN8 ? NPB : 2 * NPB) / NWV, G = GA + GB;   // LDS-DMA instructions per wave and chunk
   constexpr int NEP = MODE == 0 ? TW * PBW * (P8 ? 3 : 4) : TW * PBW * (OUT8 ? 1 : 2);   // epilogue stores per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -326,9 +314,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
   const bool pipe = n2 >= 4;                             // cross-tile prefetch (the K = 32 last-layer product: plain waits)
   static_assert(PD == 2 || PD == 3, "the wait plan below");
   auto stage = [&](int tsb, int c) {
-#ifdef SF_WEXP_NODMA   // timing-only: nothing is staged (the products run on whatever the LDS holds)
-    return;
-#endif
     char* base = smem + (c % NB) * SLOT;
     const long pbg = (long)tsb * NPB;
 #pragma unroll
@@ -350,9 +335,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
   // the same, one LDS-DMA instruction at a time (i-th of this wave's G): issued BETWEEN MFMAs an instruction costs its wave ~60
   // issue cycles, four in a burst behind a barrier 150-200 each (k_wdw's measurement)
   auto stage_piece = [&](int tsb, int c, int i) __attribute__((always_inline)) {
-#ifdef SF_WEXP_NODMA
-    return;
-#endif
     char* base = smem + (c % NB) * SLOT;
     const long pbg = (long)tsb * NPB;
     if (i < GA) {
@@ -381,16 +363,8 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
     }
   }
   asm volatile("" ::"v"(init[0][0]), "v"(init[TW - 1][15]));   // bias loads retire before the first DMA is issued
-#ifdef SF_WEXP_STAGGER   // A/B: workgroups start 1/16 of a tile apart (breaks the convoy in which every CU stores at the same time)
-  // (workgroup q = blockIdx.x >> 3 of an XCD goes to CU q mod 32: the second workgroup of a CU is q + 32 - it gets half a tile more)
-  for (int i = 0; i < (int)((((blockIdx.x >> 3) & 15) + 8 * ((blockIdx.x >> 8) & 1)) & 15) * SF_WEXP_STAGGER; ++i) __builtin_amdgcn_s_sleep(32);
-#endif
   for (int c = 0; c < PD && c < n2; ++c) stage(sb, c);
   bool first = true;
-#ifdef SF_WEXP_STAMP   // timing-only build: where a wave's tile goes (waits at the chunk barriers / products / epilogue), in cycles
-  unsigned long long st_wait = 0, st_epi = 0, st_tiles = 0;
-  const unsigned long long st_begin = __builtin_amdgcn_s_memtime(), st_rt0 = __builtin_amdgcn_s_memrealtime();   // core cycles, 100 MHz ticks
-#endif
   while (true) {
     const long pb0 = (long)sb * NPB + pw;
     f32x16 acc[TW][PBW];
@@ -407,24 +381,12 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
     auto admit = [&](int c, bool burst) __attribute__((always_inline)) {   // chunk c landed and its slot's predecessor is free; burst: request chunk c + PD here
       // vmcnt is in-order: "chunk c landed" = all but the younger operations done; younger are the DMA of chunks
       // c+1, c+2 and - in the first PD steps of a tile that follows another - that tile's NEP epilogue stores
-#ifdef SF_WEXP_STAMP
-      const unsigned long long st_w0 = __builtin_amdgcn_s_memtime();
-#endif
       // (in flight behind chunk c: min(PD - 1, n2 - 1 - c) chunks of G instructions each)
       if (!pipe) bar_all();
-#ifndef SF_WEXP_LAXWAIT
       else if (c + 1 >= n2) bar_all();
       else if (PD == 3 && c + 2 >= n2) bar_dma<G>();
-#endif
-#ifdef SF_WEXP_LAXWAIT   // timing-only (RACY): no wait ever requires the previous tile's stores to have retired
-      else bar_dma<(PD - 1) * G + NEP>();
-#else
       else if (first || c >= PD) bar_dma<(PD - 1) * G>();
       else bar_dma<(PD - 1) * G + NEP>();
-#endif
-#ifdef SF_WEXP_STAMP
-      st_wait += __builtin_amdgcn_s_memtime() - st_w0;
-#endif
       if (burst && c + PD < n2) stage(sb, c + PD);
       asm volatile("" ::: "memory");
       if (MODE == 2 && c == n2 - 1) {
@@ -444,13 +406,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
     struct Frags { u32x4 fa[TW]; u32x4 b[PBW]; };
     u32x4 braw[PBW];                                       // IN8: the byte pieces of the current chunk (both k-steps)
     auto frag_load = [&](int c, int s2, Frags& f) __attribute__((always_inline)) {
-#ifdef SF_WEXP_NOLDS   // timing-only: the fragments are never read from LDS (opaque register values)
-#pragma unroll
-      for (int t = 0; t < TW; ++t) asm volatile("" : "+v"(f.fa[t]));
-#pragma unroll
-      for (int p = 0; p < PBW; ++p) asm volatile("" : "+v"(f.b[p]));
-      return;
-#endif
       const u32x4* sA = reinterpret_cast<const u32x4*>(smem + (c % NB) * SLOT) + lane;
       const u32x4* sB = sA + 16 * 64;
       if constexpr (IN8) {
@@ -518,10 +473,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
       }
     }
     (void)f1;
-#ifdef SF_WEXP_STAMP
-    asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[TW - 1][PBW - 1][15]));
-    const unsigned long long st_e0 = __builtin_amdgcn_s_memtime();
-#endif
     const int sbn = sb + sb_step;
     const bool more = sbn < a.n_super;
     if (pipe && more) {
@@ -529,14 +480,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
       for (int c = 0; c < PD; ++c) stage(sbn, c);
       asm volatile("" ::: "memory");
     }
-#ifdef SF_WEXP_NOEPI   // timing-only: no epilogue at all (the accumulators are consumed by an empty asm)
-    if (true) {
-#pragma unroll
-      for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int p = 0; p < PBW; ++p) asm volatile("" ::"v"(acc[t][p]));
-    } else
-#endif
     if (MODE == 0) {
 #pragma unroll
       for (int t = 0; t < TW; ++t)
@@ -558,13 +501,13 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
               pb8[2 * qq] = phase_byte4(tv, av);
               pb8[2 * qq + 1] = phase_byte4(tv + 4, av + 4);
             } else {
-              WST(a.Out[pidx], (u32x4{pack_phase2(ph[0], ph[1]), pack_phase2(ph[2], ph[3]), pack_phase2(ph[4], ph[5]),
-                                  pack_phase2(ph[6], ph[7])}));
+              a.Out[pidx] = u32x4{pack_phase2(ph[0], ph[1]), pack_phase2(ph[2], ph[3]), pack_phase2(ph[4], ph[5]),
+                                  pack_phase2(ph[6], ph[7])};
             }
-            WST(a.OutAct[pidx], (u32x4{OP::pack2(av[0], av[1]), OP::pack2(av[2], av[3]), OP::pack2(av[4], av[5]),
-                                   OP::pack2(av[6], av[7])}));
+            a.OutAct[pidx] = u32x4{OP::pack2(av[0], av[1]), OP::pack2(av[2], av[3]), OP::pack2(av[4], av[5]),
+                                   OP::pack2(av[6], av[7])};
           }
-          if constexpr (P8) WST(a.Out[((pb0 + p) * a.kp_out + 8 * ob + (t0 + t)) * 64 + lane], (u32x4{pb8[0], pb8[1], pb8[2], pb8[3]}));
+          if constexpr (P8) a.Out[((pb0 + p) * a.kp_out + 8 * ob + (t0 + t)) * 64 + lane] = u32x4{pb8[0], pb8[1], pb8[2], pb8[3]};
         }
     } else {
       float fsc = 1.0f;
@@ -604,16 +547,12 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
 #pragma unroll
               for (int j2 = 0; j2 < 4; ++j2)
                 o[j2] = OP::pack2(acc[t][p][8 * qq + 2 * j2] * c[2 * j2], acc[t][p][8 * qq + 2 * j2 + 1] * c[2 * j2 + 1]);
-              WST(a.Out[pidx], (o));
+              a.Out[pidx] = o;
             }
           }
-          if constexpr (OUT8) WST(a.Out[((pb0 + p) * a.kp_out + 8 * ob + (t0 + t)) * 64 + lane], (u32x4{o8[0], o8[1], o8[2], o8[3]}));
+          if constexpr (OUT8) a.Out[((pb0 + p) * a.kp_out + 8 * ob + (t0 + t)) * 64 + lane] = u32x4{o8[0], o8[1], o8[2], o8[3]};
         }
     }
-#ifdef SF_WEXP_STAMP
-    st_epi += __builtin_amdgcn_s_memtime() - st_e0;
-    st_tiles += 1;
-#endif
     if (!more) break;
     if (!pipe) {
       bar_lds();
@@ -622,215 +561,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void k_wgemm2(WGemmArgs
     sb = sbn;
     first = false;
   }
-#ifdef SF_WEXP_STAMP
-  if (a.dump && lane == 0 && (wave == 0 || wave == 5) && (blockIdx.x == 3 || blockIdx.x == 200) && st_tiles) {
-    float* o = reinterpret_cast<float*>(a.dump) + (MODE == 0 ? 0 : 32) + ((blockIdx.x == 3 ? 0 : 2) + (wave == 0 ? 0 : 1)) * 4;
-    const float nt = (float)st_tiles;
-    o[0] = (float)(__builtin_amdgcn_s_memtime() - st_begin) / nt; o[1] = (float)st_wait / nt; o[2] = (float)st_epi / nt; o[3] = nt;
-    reinterpret_cast<float*>(a.dump)[(MODE == 0 ? 16 : 48) + (blockIdx.x == 3 ? 0 : 2) + (wave == 0 ? 0 : 1)] =
-        (float)(__builtin_amdgcn_s_memtime() - st_begin) / (float)(__builtin_amdgcn_s_memrealtime() - st_rt0) * 100.0f;   // core MHz over the launch
-  }
-#endif
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// k_wgemm3 (round 3): the forward hidden GEMM of k_wgemm2<0, .., P8> with its epilogue PIPELINED UNDER THE NEXT TILE.
-// An experiment that is kept because of what it rules out (opt-in: SIREN_FIT_WGEMM3=1).  Timing-only builds say the epilogue
-// stores of the wide GEMMs cost their full drain time (15 of 57 ms at 512x8, profiles/r03_wide_store_ablation.txt); the
-// suspicion was the BURST - with the epilogue at the end of a 256 x 256 tile every wave issues its 24 stores back to back,
-// whereas k_fwd_pipe and k_bwd8h, which do not pay for their stores, let them leave one at a time between MFMAs.  So here:
-//   tile = 256 neurons x 128 pixels (wave = 4 row tiles x ONE pixel block: 64 accumulator registers, two sets);
-//   the operand ring streams CONTINUOUSLY across tiles (chunk g of the workgroup's whole sequence, 24 KiB: 16 A + 8 B pieces);
-//   while tile T accumulates in one set, the other set - tile T-1 - is drained: VPK values per k-step (sine, phase byte, pack),
-//   an activation store every 8 values, a phase-byte store every 16: 12 stores spread over the tile's k-steps.
-//   Every step is the full step (k_bwd8h's rule): the first tile drains zeros into a.dump, requests beyond the last tile re-read
-//   its chunks, the last tile is drained once more at the end - so the store pattern is periodic and every vmcnt is a constant.
-// RESULT: bit-identical to the tile loop and no faster (forward 20.3 against 20.0 ms per step at 512x8; with the fragments of both
-// loops double-buffered 20.5 against 18.6): it is not the burst, and the smaller tile pays more than the hidden epilogue returns.
-// KSI = k-steps of the layer (32 at width 512, 64 at 1024).  fp16 operands, phase bytes (scratch formats 12 / 8).
-// ---------------------------------------------------------------------------------------------------------
-template <int V> struct IntC { static constexpr int value = V; };
-template <int KSI>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_wgemm3(WGemmArgs a) {   // (two waves per SIMD, 256 VGPRs: left to itself hipcc spills the drained accumulator set to reach three)
-  typedef OpF16 OP;
-  constexpr int OT = 8, TW = 4, NPB = 4, NB = 4, PD = 3, SLOT = 24 * 1024, N2 = KSI / 2;
-  constexpr int G = 3;                                   // LDS-DMA instructions per wave and chunk: 24 pieces / 8 waves
-  constexpr int VPK = 64 / KSI;                          // epilogue values per k-step (2 at width 512, 1 at 1024)
-  static_assert(KSI == 32 || KSI == 64, "widths 512 / 1024");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sBias = reinterpret_cast<float*>(smem + NB * SLOT);      // this output block's 256 biases
-  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int xcd = blockIdx.x & 7, q0 = blockIdx.x >> 3;
-  const int ob = q0 % a.n_ob;
-  const int sb_step = (gridDim.x >> 3) / a.n_ob * 8;
-  const int sb0 = (q0 / a.n_ob) * 8 + xcd;               // first 128-pixel unit of this workgroup
-  if (sb0 >= a.n_super) return;
-  const int n_tiles = (a.n_super - sb0 + sb_step - 1) / sb_step;
-  const int t0 = TW * (wave & 1), pbw = wave >> 1;
-  const u32x4* Ablk = a.A + (size_t)ob * a.a_block_pieces * 64;
-  if (tid < 256) sBias[tid] = a.bias[ob * 256 + tid];
-  // chunk g of the workgroup's sequence = chunk g % N2 of tile g / N2 (beyond the last tile: the last tile again)
-  auto stage = [&](int ti, int c, int slot) {
-    if (ti >= n_tiles) ti = n_tiles - 1;
-    char* base = smem + slot * SLOT;
-    const long pbg = (long)(sb0 + ti * sb_step) * NPB;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int pc = wave + 8 * i, ot = pc >> 1, s2 = pc & 1;
-      glds16s(Ablk + ((size_t)((c >> 1) * OT + ot) * 4 + 2 * (c & 1) + s2) * 64, (uint32_t)lane * 16u, base + pc * 1024);
-    }
-    glds16s(a.Bin + ((pbg + (wave >> 1)) * KSI + 2 * c + (wave & 1)) * 64, (uint32_t)lane * 16u, base + (16 + wave) * 1024);
-  };
-  f32x16 accA[TW], accB[TW];
-#pragma unroll
-  for (int t = 0; t < TW; ++t) { accA[t] = f32x16{}; accB[t] = f32x16{}; }
-  static_assert(N2 % NB == 0 && PD < N2, "ring slots are compile-time inside a tile");
-  for (int c = 0; c <= PD; ++c) stage(0, c, c);
-  // the counted waits below assume the store pattern of a tile BEFORE the first one: with the first four chunks (and the bias
-  // table) landed here they hold from step 0 (the later chunks of tile 0 are requested behind real - dumped - stores)
-  bar_all();
-  u32x4* const dumpw = a.dump + wave * 64 + lane;
-  // epilogue value v (tile v >> 4, register v & 15) of accumulator set `prv`: sine -> 16-bit pair, phase byte; an activation
-  // piece leaves after every 8 values, the tile's phase piece after 16.  (The running state is plain scalars selected by
-  // switches on what are constants after unrolling: a struct with arrays here ended up in scratch memory, with a vmcnt(0)
-  // in front of every reload.)
-  float e_av = 0.f;
-  uint32_t e_a0 = 0u, e_a1 = 0u, e_a2 = 0u, e_a3 = 0u, e_p0 = 0u, e_p1 = 0u, e_p2 = 0u, e_p3 = 0u;
-  auto put_byte = [&](uint32_t& w, int byte, float tt, float sv) __attribute__((always_inline)) {
-    switch (byte) {
-      case 0: phase_byte<0>(w, tt, sv); break;
-      case 1: phase_byte<1>(w, tt, sv); break;
-      case 2: phase_byte<2>(w, tt, sv); break;
-      default: phase_byte<3>(w, tt, sv); break;
-    }
-  };
-  auto epi_value = [&](const f32x16 (&prv)[TW], int v, long pbp, bool to_dump) __attribute__((always_inline)) {
-    const int t = v >> 4, e = v & 15;
-    const float tt = prv[t][e];
-    const float sv = __builtin_amdgcn_sinf(tt);
-    switch (e >> 2) {
-      case 0: put_byte(e_p0, e & 3, tt, sv); break;
-      case 1: put_byte(e_p1, e & 3, tt, sv); break;
-      case 2: put_byte(e_p2, e & 3, tt, sv); break;
-      default: put_byte(e_p3, e & 3, tt, sv); break;
-    }
-    if (e & 1) {
-      const uint32_t w = OP::pack2(e_av, sv);
-      switch ((e & 7) >> 1) {
-        case 0: e_a0 = w; break;
-        case 1: e_a1 = w; break;
-        case 2: e_a2 = w; break;
-        default: e_a3 = w; break;
-      }
-    } else {
-      e_av = sv;
-    }
-    if ((e & 7) == 7) {
-      u32x4* dst = to_dump ? dumpw : a.OutAct + ((pbp * KSI + 16 * ob + 2 * (t0 + t) + (e >> 3)) * 64 + lane);
-      *dst = u32x4{e_a0, e_a1, e_a2, e_a3};
-    }
-    if (e == 15) {
-      u32x4* dst = to_dump ? dumpw : a.Out + ((pbp * (KSI / 2) + 8 * ob + (t0 + t)) * 64 + lane);
-      *dst = u32x4{e_p0, e_p1, e_p2, e_p3};
-    }
-  };
-  // stores issued in half-step hs = 2 c + s2 of a tile (taken modulo the tile: the pattern is the same in every tile)
-  auto stores_half = [](int hs) constexpr -> int {
-    const int hh = ((hs % (2 * N2)) + 2 * N2) % (2 * N2);
-    int n = 0;
-    for (int u = 0; u < VPK; ++u) {
-      const int e = ((hh * VPK + u) & 15);
-      n += ((e & 7) == 7) + (e == 15);
-    }
-    return n;
-  };
-  // The operand fragments are double-buffered across half-steps (as in k_wgemm2): f0 holds k-step (c, 0), f1 k-step (c, 1); the
-  // barrier that admits chunk c + 1 sits between the two half-steps of chunk c, where chunk c + 1 + PD is requested too.
-  struct Frags { u32x4 fa[TW]; u32x4 b; };
-  Frags f0, f1;
-  auto frag_load = [&](int c, int s2, Frags& f) __attribute__((always_inline)) {
-    const u32x4* sA = reinterpret_cast<const u32x4*>(smem + (c % NB) * SLOT) + lane;
-    f.b = sA[(16 + pbw * 2 + s2) * 64];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) f.fa[t] = sA[((t0 + t) * 2 + s2) * 64];
-  };
-  // one tile: `cur` accumulates (its bias first), `prv` - the tile before - is drained into pixel block pbp (or the dump).
-  // The chunk loop is unrolled sixteen chunks at a time through a compile-time part index (a 32-chunk body is not unrolled
-  // by hipcc, and an accumulator register indexed at run time goes to scratch memory).
-  auto tile_part = [&](auto part_tag, f32x16 (&cur)[TW], const f32x16 (&prv)[TW], int ti, long pbp, bool to_dump) __attribute__((always_inline)) {
-    constexpr int PART = decltype(part_tag)::value;
-#pragma unroll
-    for (int ci = 0; ci < 16; ++ci) {
-      const int c = 16 * PART + ci;
-      frag_load(c, 1, f1);                               // under the MFMAs of half-step (c, 0)
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int t = 0; t < TW; ++t) cur[t] = OP::mfma(f0.fa[t], f0.b, cur[t]);
-#pragma unroll
-      for (int u = 0; u < VPK; ++u) epi_value(prv, (2 * c) * VPK + u, pbp, to_dump);
-      __builtin_amdgcn_sched_barrier(0);
-      {   // admit chunk c + 1 (of this tile or the first of the next): younger than its DMA are the DMA of the PD - 1 chunks
-          // requested since and the stores of the 2 PD half-steps (c - PD, 1) .. (c, 0)
-        int nst = 0;
-        for (int hs = 2 * (c + 1) - 2 * PD - 1; hs <= 2 * c; ++hs) nst += stores_half(hs);
-        switch (nst) {                                   // (a constant per c after unrolling)
-          case 0: bar_dma<(PD - 1) * G + 0>(); break;
-          case 1: bar_dma<(PD - 1) * G + 1>(); break;
-          case 2: bar_dma<(PD - 1) * G + 2>(); break;
-          case 3: bar_dma<(PD - 1) * G + 3>(); break;
-          case 4: bar_dma<(PD - 1) * G + 4>(); break;
-          case 5: bar_dma<(PD - 1) * G + 5>(); break;
-          default: bar_dma<(PD - 1) * G + 6>(); break;
-        }
-        const int cn = c + 1 + PD;                       // chunk requested here: into the slot chunk c has just left
-        if (cn < N2) stage(ti, cn, cn % NB); else stage(ti + 1, cn - N2, cn % NB);
-        asm volatile("" ::: "memory");
-        frag_load(c + 1, 0, f0);                         // under the MFMAs of half-step (c, 1); (chunk N2 = chunk 0 of the next tile: same slot)
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int t = 0; t < TW; ++t) cur[t] = OP::mfma(f1.fa[t], f1.b, cur[t]);
-#pragma unroll
-      for (int u = 0; u < VPK; ++u) epi_value(prv, (2 * c + 1) * VPK + u, pbp, to_dump);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  auto tile = [&](f32x16 (&cur)[TW], const f32x16 (&prv)[TW], int ti, long pbp, bool to_dump) __attribute__((always_inline)) {
-#pragma unroll
-    for (int t = 0; t < TW; ++t)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(&sBias[(t0 + t) * 32 + 8 * q4 + 4 * h]);
-        cur[t][4 * q4 + 0] = b.x; cur[t][4 * q4 + 1] = b.y; cur[t][4 * q4 + 2] = b.z; cur[t][4 * q4 + 3] = b.w;
-      }
-    tile_part(IntC<0>{}, cur, prv, ti, pbp, to_dump);
-    if constexpr (N2 > 16) tile_part(IntC<1>{}, cur, prv, ti, pbp, to_dump);
-  };
-  frag_load(0, 0, f0);
-  // tiles alternate between the two accumulator sets
-  long pb_prev = 0;
-  int ti = 0;
-  for (; ti + 1 < n_tiles; ti += 2) {
-    tile(accA, accB, ti, pb_prev, ti == 0);
-    pb_prev = (long)(sb0 + ti * sb_step) * NPB + pbw;
-    tile(accB, accA, ti + 1, pb_prev, false);
-    pb_prev = (long)(sb0 + (ti + 1) * sb_step) * NPB + pbw;
-  }
-  const bool odd = ti < n_tiles;
-  if (odd) {
-    tile(accA, accB, ti, pb_prev, ti == 0);
-    pb_prev = (long)(sb0 + ti * sb_step) * NPB + pbw;
-  }
-  // drain the last tile (a burst, once per workgroup)
-  auto drain = [&](const f32x16 (&prv)[TW]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int t = 0; t < TW; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) epi_value(prv, 16 * t + e, pb_prev, false);
-  };
-  if (odd) drain(accA); else drain(accB);
-  bar_all();      // no LDS-DMA of this workgroup is in flight when its LDS is handed on
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -894,16 +624,9 @@ __global__ __launch_bounds__(512) void k_wdw(WDwArgs a) {
     return fp8x8_to_f16((uint32_t)r.x, (uint32_t)r.y);
   };
   for (int k = 0; k < PD && k < nblk; ++k) stage(k);
-#ifdef SF_EXPERIMENT_STAMP   // timing-only build: where one wave's block step goes (wait / DMA issue / compute)
-  unsigned long long st_wait = 0, st_stage = 0, st_comp = 0, st_t = __builtin_amdgcn_s_memtime();
-#define SF_STAMP(acc_) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); acc_ += n_ - st_t; st_t = n_; } while (0)
-#else
-#define SF_STAMP(acc_) do {} while (0)
-#endif
   for (int k = 0; k < nblk; ++k) {
     // block k landed (blocks k+1, k+2 stay in flight), everyone finished block k-1 (whose slot is refilled next)
     if (G > 0 && k + PD - 1 < nblk) bar_dma<(PD - 1) * G>(); else bar_all();
-    SF_STAMP(st_wait);
     // The LDS-DMA of block k+PD is issued BETWEEN the MFMAs of this block, one piece per group of MFMAs: an
     // LDS-DMA instruction costs its wave ~150-200 issue cycles in a burst and ~60 among MFMAs.
     const bool do_stage = k + PD < nblk;
@@ -922,7 +645,6 @@ __global__ __launch_bounds__(512) void k_wdw(WDwArgs a) {
     };
     if (G == 0 && do_stage) stage(k + PD);
     asm volatile("" ::: "memory");
-    SF_STAMP(st_stage);
     char* sD = smem + (k % NB) * BLK;
     char* sP = sD + KSJ * 1024;
 #pragma unroll
@@ -952,18 +674,7 @@ __global__ __launch_bounds__(512) void k_wdw(WDwArgs a) {
         }
       }
     }
-#ifdef SF_EXPERIMENT_STAMP
-    asm volatile("s_nop 0" :: "v"(acc[0][0][0]));   // MFMA results of this step consumed -> chain finished
-#endif
-    SF_STAMP(st_comp);
   }
-#ifdef SF_EXPERIMENT_STAMP
-  if (JW == 256 && lane == 0 && (wave == 0 || wave == 7) && (blockIdx.x == 0 || blockIdx.x == 5) && (blockIdx.y == 0 || blockIdx.y == 9)) {
-    unsigned long long* dbg = reinterpret_cast<unsigned long long*>(a.slab + (size_t)gridDim.y * gridDim.x * (JW * 256 + JW));
-    const int slot = ((blockIdx.x != 0) * 2 + (blockIdx.y != 0)) * 2 + (wave != 0);
-    dbg[slot * 4 + 0] = st_wait; dbg[slot * 4 + 1] = st_stage; dbg[slot * 4 + 2] = st_comp; dbg[slot * 4 + 3] = nblk;
-  }
-#endif
   float* slab = a.slab + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (JW * 256 + JW);
   const int cl = lane & 31, hh = lane >> 5;
 #pragma unroll

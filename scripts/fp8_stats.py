@@ -1,5 +1,5 @@
 """Per-layer statistics of the fp8 (e4m3) hidden deltas of a format-8 fit: rms in fp8 units, share of saturated (+-448), zero
-and subnormal (< 2^-6) bytes - evidence for the choice of the per-chunk scale target (SIREN_FIT_FP8_TARGET).
+and subnormal (< 2^-6) bytes - evidence for the choice of the per-chunk scale target (kFp8Target).
 usage: python scripts/fp8_stats.py [smooth|nonsmooth] [steps,steps,...]"""
 import os, sys, math
 import numpy as np, torch
@@ -18,7 +18,7 @@ gh, gw = so.grid_vectors(H, W)
 eng.set_coords(gh.cuda(), gw.cuda()); eng.set_params(torch.tensor(so.flatten(p)).cuda()); eng.set_target(img.cuda().contiguous())
 lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().cuda()
 done = 0
-print("target", os.environ.get("SIREN_FIT_FP8_TARGET", "default"), kind)
+print(kind)
 for mk in marks:
     if mk > done:
         eng.step([3e-4 * 0.5 ** (t // 200) for t in range(done, mk)]); done = mk

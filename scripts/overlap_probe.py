@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Probe: do a forward-heavy and a backward-heavy phase overlap usefully on one GPU?  Two independent engines on
 two streams step concurrently (their k_fwd / k_bwd phases drift against each other); compare the aggregate
-Mpix-iters/s with one engine alone.  SIREN_FIT_BWD_WGS limits the persistent backward grids."""
+Mpix-iters/s with one engine alone."""
 import os
 import sys
 import threading

@@ -74,6 +74,23 @@ def test_no_exception_crosses_the_c_abi():
     assert set(entry) - set(guarded) <= {"sf_abi_version", "sf_last_error"}, set(entry) - set(guarded)
 
 
+def test_kernel_sources_have_one_build_and_no_switches():
+    """csrc/*.hip is one build: no preprocessor conditional (a -D on the build line cannot select a timing-only or otherwise
+    different kernel) and no environment variable read by the library (nothing outside sf_config changes what it computes)."""
+    import glob
+    import re
+    csrc = os.path.dirname(_engine._LIB_PATH)
+    hips = sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    assert len(hips) >= 10
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b")
+    for path in hips:
+        bad = [(i + 1, l) for i, l in enumerate(open(path).read().splitlines()) if cond.match(l)]
+        assert not bad, (os.path.basename(path), bad[:5])
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        if os.path.isfile(path) and not path.endswith(".so"):
+            assert "getenv" not in open(path, errors="replace").read(), os.path.basename(path)
+
+
 def test_model_init_matches_reference(golden):
     for name, hidden, depth in (("grads_64x4_32", 64, 4), ("grads_256x8_32", 256, 8)):
         torch.manual_seed(0)

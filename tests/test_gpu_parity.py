@@ -277,7 +277,7 @@ def test_engine_equals_its_numerics_model(golden, name, hidden, depth, dtype, fm
     that flips moves one sine by up to 2.5e-2; measured 2.9e-3 at 256x8 on 1 280 pixels).  At hidden = 256 layer 0
     runs on the matrix pipe as a split-fp16 product (k_fwd_pipe, kL0Split): as accurate as the model's fp32 FMAs
     (6e-7 vs 8e-7 revolutions against float64) but not bit-identical to them, which costs a few more flips than the
-    VALU layer 0 of the other widths (measured with SIREN_FIT_FWD_PIPE=0: 1.7e-3 / 4e-4 / 2.3e-3).  Format 8 is held to the model only at depth 4: an fp8 rounding that flips is a 6 % change of that
+    VALU layer 0 of the other widths (measured through k_fwd at width 256, which commit d0b07ef could still select at this depth: 1.7e-3 / 4e-4 / 2.3e-3).  Format 8 is held to the model only at depth 4: an fp8 rounding that flips is a 6 % change of that
     delta, which flips more roundings in the next layer - at depth 8 engine and model decorrelate to the level of the
     fp8 noise itself (measured 2.3e-2, = model vs fp32), which test_forward_and_gradients_vs_reference_golden bounds."""
     from oracle import engine_model as em
