@@ -314,17 +314,15 @@ def registry_model(sd, shape: Cfg):
 
 def engine_flat_params(sd, shape: Cfg, num_params: int) -> torch.Tensor:
     """The flat parameter vector of an engine handle with num_params slots: the model's tensors in flat order, scattered
-    through the model's own _padded_index (zeros in the padding) when the engine runs a wider network - what
-    Siren._sync_to_engine hands a training handle."""
+    by the model's own engine_flat (zeros in the padding) when the engine runs a wider network - what the model's
+    _sync_to_engine hands a training handle."""
     model = registry_model(sd, shape)
     logical = torch.cat([p.data.reshape(-1).float() for p in model._param_list()])
     if not model._padded:
         if logical.numel() != num_params:
             raise ValueError(f"the state dict holds {logical.numel()} parameters, the engine handle {num_params}")
         return logical.contiguous()
-    flat = torch.zeros(num_params)
-    flat[model._padded_index(torch.device("cpu"))] = logical
-    return flat
+    return model.engine_flat(logical, num_params, torch.device("cpu"))
 
 
 def flat_params(sd: Dict[str, torch.Tensor], depth: int) -> torch.Tensor:

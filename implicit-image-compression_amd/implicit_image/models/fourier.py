@@ -3,13 +3,14 @@
 
 `encoding.B` is a frozen Parameter handed to the engine once per bind; every `layers.{2k}.{weight,bias}`
 (the nn.Linear layers of the Sequential) is, once bound, a zero-copy view of the engine's flat fp32 state,
-as in `Siren`.  forward() runs the fused HIP kernels; there is no PyTorch arithmetic fallback.
+as in `Siren` (models/binding.py).  forward() runs the fused HIP kernels; there is no PyTorch arithmetic fallback.
 """
 import numpy as np
 import torch
 from torch import nn
 
-from .siren import Siren, next_kernel_width
+from .binding import EngineBound
+from .siren import next_kernel_width
 
 # the reference's Masking puts the frozen encoding.B into its mask_dict and its first update_connections() fails on
 # B.grad being None (reference pipeline/masking/funcs/grow.py:87): there is no reference behaviour to reproduce
@@ -31,16 +32,17 @@ class Encoding(nn.Module):
         raise RuntimeError("Encoding is evaluated by the fused engine; call FourierNet.forward(grid)")
 
 
-class FourierNet(Siren):
+class FourierNet(EngineBound):
     # engine widths: Small_Dense's int(hidden * sqrt(density)) runs zero-padded to the next one (padded neurons have zero
     # weights and bias, output relu(0) = 0 and receive exactly zero gradients)
     WIDTHS = (32, 64, 128, 256)
     mask_unsupported = MASKING_UNSUPPORTED
+    _WHO = "Siren"                 # (the wording a CPU grid has always been refused with)
 
     def __init__(self, input_size: int = 2, output_size: int = 3, depth: int = 8, hidden_size: int = 128,
                  map_size: int = 128, map_scale: float = 10.0, small_dense_density: float = 1.0,
                  compute_dtype: str = "f16", chunk_pixels: int = 0, **kwargs):
-        nn.Module.__init__(self)
+        super().__init__()
         if compute_dtype != "f16":
             raise NotImplementedError("FourierNet runs fp16 MFMA operands only (engine.compute_dtype=f16)")
         hidden_size = int(hidden_size * np.sqrt(small_dense_density))   # Small_Dense (reference fourier.py:40)
@@ -56,8 +58,6 @@ class FourierNet(Siren):
         self.cfg = dict(input_size=input_size, output_size=output_size, depth=depth, hidden_size=hidden_size,
                         map_size=int(map_size), map_scale=float(map_scale), n_linear=n_linear,
                         compute_dtype=compute_dtype, chunk_pixels=chunk_pixels, scratch_format=16)
-        self.pre_pass_callbacks = []
-        self.post_backward_callbacks = []
         self._engine_width = next_kernel_width(hidden_size, self.WIDTHS)
         if self._engine_width is None:
             raise NotImplementedError(f"hidden_size {hidden_size} > 256 is not supported for FourierNet by the gfx950 engine")
@@ -65,15 +65,9 @@ class FourierNet(Siren):
             raise NotImplementedError("FourierNet on the gfx950 engine: input_size 2, output_size 3, map_size 64 / 128 / "
                                       f"256 / 512 and 2..12 Linear layers (got {input_size}, {output_size}, {map_size}, {n_linear})")
         self._padded = self._engine_width != hidden_size
-        self._adam = ((0.9, 0.999), 1e-8)
-        self._pad_index = None
-        self._engine = None
-        self._engine_key = None
-        self._grid_key = None
-        self._target_key = None
         self._enc_key = None
 
-    # ---- engine binding (shared with Siren; these hooks differ) ----------------------------------
+    # ---- engine binding (models/binding.py; these hooks differ) -----------------------------------
     def set_scratch_format(self, fmt: int):
         """FourierNet has one scratch format (16-bit); nothing to switch."""
 
@@ -107,20 +101,5 @@ class FourierNet(Siren):
         fans = [c["map_size"]] + [c["hidden_size"]] * (c["n_linear"] - 1) + [c["output_size"]]
         return [(fans[l], fans[l + 1], l > 0, l < c["n_linear"] - 1) for l in range(c["n_linear"])]
 
-    def __deepcopy__(self, memo):
-        c = self.cfg
-        new = FourierNet(c["input_size"], c["output_size"], c["depth"], c["hidden_size"], c["map_size"], c["map_scale"],
-                         compute_dtype=c["compute_dtype"], chunk_pixels=c["chunk_pixels"])
-        new.to(next(self.parameters()).device)
-        new._adam = self._adam
-        with torch.no_grad():
-            for a, b in zip(new._param_list(), self._param_list()):
-                a.copy_(b)
-            new.encoding.B.copy_(self.encoding.B)
-        new.train(self.training)
-        return new
-
-    def forward(self, grid: torch.Tensor) -> torch.Tensor:
-        """[H, W, 2] grid -> [H, W, 3] prediction in [0, 1] (reference fourier.py:63-72)."""
-        pred, _ = self.engine(grid).forward(want_pred=True, want_sse=False)
-        return pred
+    def _copy_extras(self, new):
+        new.encoding.B.copy_(self.encoding.B)

@@ -10,9 +10,9 @@ from typing import Optional
 
 import numpy as np
 import torch
-from torch import nn
 
 from ..data import get_grid
+from .binding import EngineBound
 from .siren import Siren
 
 # the reference's Masking.add_module runs a FLOP-counting forward on a 1x1 grid: 3x3 coefficients, a 2x2 inverse DWT
@@ -35,14 +35,15 @@ def check_image(h: int, w: int):
             f"{2 * coeff_len(h) - 4}x{2 * coeff_len(w) - 4} and torch.cat with the {h}x{w} Cb / Cr fails")
 
 
-class WaveletSiren(Siren):
+class WaveletSiren(EngineBound):
+    WIDTHS = Siren.WIDTHS          # the sub-networks' (the constructor refuses what the narrow kernel path cannot run)
     mask_unsupported = MASKING_UNSUPPORTED
 
     def __init__(self, input_size: int = 2, output_size: int = 3, depth: int = 8, hidden_size: int = 64,
                  wavelet_levels: int = 1, first_omega_0: float = 50.0, hidden_omega_0: float = 50.0,
                  outermost_linear: bool = True, simulate_quantization: bool = False, small_dense_density: float = 1.0,
                  compute_dtype: str = "f16", chunk_pixels: int = 0, scratch_format: int = 0, **kwargs):
-        nn.Module.__init__(self)
+        super().__init__()
         if compute_dtype != "f16":
             raise NotImplementedError("WaveletSiren runs fp16 MFMA operands only (engine.compute_dtype=f16)")
         if scratch_format not in (0, 16):
@@ -66,23 +67,15 @@ class WaveletSiren(Siren):
                         wavelet_levels=wavelet_levels, first_omega_0=float(first_omega_0),
                         hidden_omega_0=float(hidden_omega_0), outermost_linear=bool(outermost_linear),
                         compute_dtype=compute_dtype, chunk_pixels=chunk_pixels, scratch_format=16)
-        self.pre_pass_callbacks = []
-        self.post_backward_callbacks = []
         self._engine_width = self.LF_siren._engine_width
         if self._engine_width > 256:
             raise NotImplementedError(f"hidden_size {hidden_size} > 256 is not supported for WaveletSiren by the gfx950 "
                                       "engine (the narrow kernel path only)")
         self._padded = self._engine_width != hidden_size
-        self._adam = ((0.9, 0.999), 1e-8)
-        self._pad_index = None
-        self._engine = None
-        self._engine_key = None
-        self._grid_key = None
-        self._target_key = None
         self._image_h = None
         self._coeff_grid = None
 
-    # ---- engine binding (shared with Siren; these hooks differ) ----------------------------------------------------
+    # ---- engine binding (models/binding.py; these hooks differ) ------------------------------------------------------
     def set_scratch_format(self, fmt: int):
         """WaveletSiren has one scratch format (16-bit); nothing to switch."""
 
@@ -93,11 +86,9 @@ class WaveletSiren(Siren):
         wp, D = self._engine_width, self.cfg["depth"]
         return 3 * wp + (D - 2) * (wp * wp + wp) + 3 * wp + 3
 
-    def _padded_index(self, device):
-        if self._pad_index is None or self._pad_index.device != device:
-            self._pad_index = torch.cat([self.LF_siren._padded_index(device),
-                                         self.HF_siren._padded_index(device) + self._sub_engine_params()])
-        return self._pad_index
+    def _layer_fans(self):
+        """LF's layers, then HF's: the joint [LF | HF] pad index (HF starts _sub_engine_params() slots in)"""
+        return self.LF_siren._layer_fans() + self.HF_siren._layer_fans()
 
     def _new_engine(self, H: int, w: int, row_begin: int, row_end: int, device: int):
         from .._engine import WaveletEngine
@@ -120,8 +111,7 @@ class WaveletSiren(Siren):
         if row_begin or (row_end and row_end != h) or (full_height and full_height != h):
             raise NotImplementedError(PIXEL_SPLIT_UNSUPPORTED)
         check_image(h, w)
-        if not grid.is_cuda:
-            raise RuntimeError("WaveletSiren runs on the gfx950 engine only: move model, grid and image to 'cuda'")
+        self._check_device(grid)
         self.shape_probe(h, w)
         if self.LF_h != coeff_len(h):   # the reference keeps the first coefficient size (LF_h is cached)
             raise NotImplementedError(f"WaveletSiren was first run on a {2 * self.LF_h - 4}x{2 * self.LF_h - 4} image: the "
@@ -130,23 +120,7 @@ class WaveletSiren(Siren):
         n = coeff_len(h)
         if self._coeff_grid is None or self._coeff_grid.device != grid.device or self._coeff_grid.shape[0] != n:
             self._coeff_grid = get_grid(n, n, device=grid.device)   # LF_grid = HF_grid (wavelet_siren.py:76-80)
-        return Siren.engine(self, self._coeff_grid, img)
+        return super().engine(self._coeff_grid, img)
 
-    def __deepcopy__(self, memo):
-        c = self.cfg
-        new = WaveletSiren(c["input_size"], c["output_size"], c["depth"], c["hidden_size"], c["wavelet_levels"],
-                           c["first_omega_0"], c["hidden_omega_0"], c["outermost_linear"],
-                           compute_dtype=c["compute_dtype"], chunk_pixels=c["chunk_pixels"])
-        new.to(next(self.parameters()).device)
-        new._adam = self._adam
+    def _copy_extras(self, new):
         new.LF_h = self.LF_h
-        with torch.no_grad():
-            for a, b in zip(new._param_list(), self._param_list()):
-                a.copy_(b)
-        new.train(self.training)
-        return new
-
-    def forward(self, grid: torch.Tensor) -> torch.Tensor:
-        """[H, W, 2] grid -> [H, W, 3] RGB prediction (reference wavelet_siren.py:66-106; no clamp)."""
-        pred, _ = self.engine(grid).forward(want_pred=True, want_sse=False)
-        return pred

@@ -17,6 +17,7 @@ import torch.nn as nn
 from torch import Tensor
 from torch.nn import Parameter
 
+from ...models.binding import EngineBound
 from ...models.siren import Siren
 
 DEPLOY_UNSUPPORTED = ("FeatherNet.deploy() (the reference's forward-hook weight caching) is not built: its bias index "
@@ -26,8 +27,9 @@ DEEPCOPY_UNSUPPORTED = ("a trained FeatherNet cannot be deep-copied: in the refe
                         "deepcopy protocol\"), so Feathermap works with quant=none only")
 
 
-class FeatherNet(nn.Module):
+class FeatherNet(EngineBound):
     """Reference constructor; `module` must be a Siren (the engine's model)."""
+    _SYNC_PER_OPTIM = False               # _carry_in syncs (and materialises) once, whatever the number of optimisers
 
     def __init__(self, module: nn.Module, compress: float = 0.5, exclude: tuple = (nn.BatchNorm2d), clone: bool = True,
                  verbose: bool = False) -> None:
@@ -56,15 +58,7 @@ class FeatherNet(nn.Module):
         self._V1 = Parameter(torch.Tensor(self._size_n, self._size_m))
         self._V2 = Parameter(torch.Tensor(self._size_m, self._size_n))
         self._V = None
-        self._norm_V()
-        self._adam = ((0.9, 0.999), 1e-8)
-        self._padded = False                  # the feather vector is never padded (the engine maps it onto padded W)
-        self.pre_pass_callbacks = []
-        self.post_backward_callbacks = []
-        self._engine = None
-        self._engine_key = None
-        self._grid_key = None
-        self._target_key = None
+        self._norm_V()                        # (_padded stays False: the engine maps the feather vector onto padded W)
 
     # ---- the reference's structure ---------------------------------------------------------------
     def _unregister_params(self) -> None:
@@ -138,16 +132,10 @@ class FeatherNet(nn.Module):
     def __deepcopy__(self, memo):
         raise NotImplementedError(DEEPCOPY_UNSUPPORTED)
 
-    # ---- engine seams (the ones Siren offers: EngineAdam, train_epoch, train_steps, eval_epoch) -------------
+    # ---- engine binding (models/binding.py; these hooks differ) --------------------------------------------
     @property
     def cfg(self):
         return self.module.cfg
-
-    def set_scratch_format(self, fmt: int):
-        self.module.set_scratch_format(fmt)
-
-    def set_adam_hparams(self, betas, eps: float):
-        self._adam = (tuple(betas), float(eps))
 
     def _param_list(self):
         """the feather vector's Parameters in its flat order (= named_parameters(): _V1, _V2, then the scalers)"""
@@ -162,67 +150,37 @@ class FeatherNet(nn.Module):
         """The Siren's engine with the feather state attached, bound to this model (made on first use, re-made when the
         image size, the Adam hyper-parameters or the scratch format change; the feather moments and step count carry
         over to a re-made handle of the same image size)."""
+        return super().engine(grid, img)
+
+    def _engine_key_of(self, H: int, w: int, row_begin: int, row_end: int, device):
+        return (H, w, device, self._adam, self.cfg["scratch_format"])
+
+    def _new_engine(self, H: int, w: int, row_begin: int, row_end: int, device: int):
         from ..._engine import FeatherEngine
-        if not grid.is_cuda:
-            raise RuntimeError("FeatherNet runs on the gfx950 engine only: move model, grid and image to 'cuda'")
-        h, w, _ = grid.shape
-        key = (h, w, grid.device.index, self._adam, self.module.cfg["scratch_format"])
-        if self._engine is None or self._engine_key != key:
-            carry = None
-            if self._engine is not None:
-                old = self._engine
-                carry = (old.view("exp_avg").clone(), old.view("exp_avg_sq").clone(), old.adam_steps, (old.height, old.width))
-                self._unbind()
-            self.module._adam = self._adam
-            base = self.module._new_engine(h, w, 0, 0, grid.device.index or 0)
-            try:
-                base.feather_attach(self._size_n, self._size_m, *self._logical_sizes())
-            except Exception:
-                base.close()
-                raise
-            eng = FeatherEngine(base)
-            self._engine, self._engine_key, self._grid_key, self._target_key = eng, key, None, None
-            if carry is not None and carry[3] == (h, w):
-                eng.view("exp_avg").copy_(carry[0])
-                eng.view("exp_avg_sq").copy_(carry[1])
-                eng.adam_steps = carry[2]
-            self._sync_to_engine()
-            for opt in list(getattr(self, "_engine_optims", ())):
-                opt._bound = None
-                opt._bind_state(eng)
-        eng = self._engine
-        gkey = (grid.data_ptr(), tuple(grid.shape))
-        if self._grid_key != gkey:
-            from ...data import grid_vectors
-            rows, cols = grid_vectors(grid)
-            eng.set_coords(rows.float(), cols.float())
-            self._grid_key = gkey
-        if img is not None:
-            tkey = (img.data_ptr(), tuple(img.shape), img._version)
-            if self._target_key != tkey:
-                eng.set_target(img.contiguous().float())
-                self._target_key = tkey
-        for cb in list(self.pre_pass_callbacks):
-            cb()
+        self.module._adam = self._adam
+        base = self.module._new_engine(H, w, 0, 0, device)
+        try:
+            base.feather_attach(self._size_n, self._size_m, *self._logical_sizes())
+        except Exception:
+            base.close()
+            raise
+        return FeatherEngine(base)
+
+    def _carry_out(self, old):
+        return (old.view("exp_avg").clone(), old.view("exp_avg_sq").clone(), old.adam_steps, (old.height, old.width))
+
+    def _carry_in(self, eng, carry):
+        if carry is not None and carry[3] == (eng.height, eng.width):
+            eng.view("exp_avg").copy_(carry[0])
+            eng.view("exp_avg_sq").copy_(carry[1])
+            eng.adam_steps = carry[2]
         self._sync_to_engine()
-        return eng
 
     def _sync_to_engine(self):
-        """(Re)bind every Parameter (and .grad) to its slice of the feather vector - code that replaced `.data` is
-        copied in - then materialise W: in-place edits through the views are invisible to the engine, so always."""
+        """(Re)bind every Parameter (and .grad) to its slice of the feather vector, then materialise W: in-place edits
+        through the views are invisible to the engine, so always."""
         eng = self._engine
-        flat, grads = eng.view("params"), eng.view("grads")
-        off = 0
-        for p in self._param_list():
-            n = p.numel()
-            dst = flat[off:off + n].view(p.shape)
-            if p.data.data_ptr() != dst.data_ptr():
-                dst.copy_(p.data.to(dst.dtype))
-                p.data = dst
-            g = grads[off:off + n].view(p.shape)
-            if p.grad is None or p.grad.data_ptr() != g.data_ptr():
-                p.grad = g
-            off += n
+        self._bind_params(eng)
         eng.feather_materialise()
         dense = eng.base.view("params")
         wp, depth = self.module._engine_width, len(self.module.layers)
@@ -235,24 +193,13 @@ class FeatherNet(nn.Module):
             lin.bias = dense[ob:ob + lin.out_features]
 
     def _unbind(self):
-        for p in self._param_list():
-            p.data = p.data.clone()
-            p.grad = None
         for layer in self.module.layers:
             layer.linear.weight = layer.linear.weight.clone()
             layer.linear.bias = layer.linear.bias.clone()
-        self._engine.base.close()
-        self._engine = None
+        super()._unbind()
 
     def download_grads(self):
         """after a backward: the feather gradient (dV1, dV2, dscalers) of the engine's dL/dW, so `.grad` is current
         (the optimiser step then reuses it)"""
         if self._engine is not None:
             self._engine.feather_adjoint()
-
-    def download_params(self):
-        return None
-
-    def forward(self, x: Tensor) -> Tensor:
-        pred, _ = self.engine(x).forward(want_pred=True, want_sse=False)
-        return pred

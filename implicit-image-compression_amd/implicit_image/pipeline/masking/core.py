@@ -152,7 +152,7 @@ class Masking:
 
     def _push_masks(self):
         """Hand the current masks to the engine."""
-        eng = getattr(self.module, "_engine", None)
+        eng = self.module.bound_engine
         if eng is None:
             return
         self.module.set_engine_masks(self.flat_mask())
@@ -182,7 +182,7 @@ class Masking:
     def step(self, scaler=None):
         """Optimiser step, then masks, then prune-rate decay (core.py:671-702).  `scaler` is accepted
         for signature parity; GradScaler is an exact no-op on the fp32 path."""
-        eng = getattr(self.module, "_engine", None)
+        eng = self.module.bound_engine
         if eng is not None and self._pushed_engine is not eng:
             self._push_masks()                  # engine was created after add_module()
         self.optimizer.step()

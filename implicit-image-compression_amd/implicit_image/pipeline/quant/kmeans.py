@@ -103,7 +103,7 @@ class KmeansQuant:
     def kmeans_modify_weights(self):
         """forward-pre-hook of the reference, for every quantised layer in module order (kmeans.py:66-72)."""
         import os
-        eng = getattr(self.model, "_engine", None)
+        eng = self.model.bound_engine
         if os.environ.get("SIREN_FIT_NATIVE_KMEANS", "1") == "0":       # A/B knob: the torch host mirror
             eng = None
         for m in self._targets:

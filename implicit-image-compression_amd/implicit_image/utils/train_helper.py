@@ -38,13 +38,10 @@ class EngineAdam(Optimizer):
         model.set_adam_hparams(tuple(float(b) for b in betas), float(eps))   # sf_config.beta1/beta2/eps of the engine
         super().__init__(model._param_list(), dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
         self._bound = None
-        import weakref
-        if not hasattr(model, "_engine_optims"):
-            model._engine_optims = weakref.WeakSet()     # Siren.engine() rebinds these when it re-creates the handle
-        model._engine_optims.add(self)
+        model.register_optimizer(self)        # engine() rebinds it when it re-creates the handle
 
     def _bind_state(self, eng):
-        if getattr(self.model, "_padded", False):     # padded widths: logical copies, refreshed after every step
+        if self.model._padded:     # padded widths: logical copies, refreshed after every step
             for p, m, v in zip(self.model._param_list(), self.model._gather_from_engine("exp_avg"),
                                self.model._gather_from_engine("exp_avg_sq")):
                 st = self.state[p]
@@ -69,13 +66,13 @@ class EngineAdam(Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        eng = getattr(self.model, "_engine", None)
+        eng = self.model.bound_engine
         if eng is None:
             raise RuntimeError("EngineAdam.step() before any forward/backward: the engine is created by train_epoch")
-        if not getattr(self.model, "_padded", False):
+        if not self.model._padded:
             self._bind_state(eng)
         eng.adam_step(float(self.param_groups[0]["lr"]))
-        if getattr(self.model, "_padded", False):
+        if self.model._padded:
             self.model.download_params()
             self._bind_state(eng)
         for p in self.model._param_list():
@@ -109,7 +106,7 @@ def setup_mask(model: Module, optim: Optimizer, masking_cfg=None) -> Masking:
     """Masking instance wrapping `model`, or None for dense fits (reference :89-129)."""
     if not masking_cfg or _cfg_get(masking_cfg, "dense"):
         return None
-    if getattr(model, "mask_unsupported", None):      # FourierNet: the reference itself fails here (models/fourier.py)
+    if model.mask_unsupported:      # FourierNet: the reference itself fails here (models/fourier.py)
         raise NotImplementedError(model.mask_unsupported)
     schedule = _cfg_get(masking_cfg, "decay_schedule")
     if schedule not in decay_registry:
@@ -135,7 +132,7 @@ def setup_mask(model: Module, optim: Optimizer, masking_cfg=None) -> Masking:
     # ONE rule, the engine's own (sf_set_masks moves every auto handle to 16 when a mask is set): an auto model is created
     # with format 16 here, so the engine never allocates the 8-bit scratch first only to free it at the first mask push.
     # An EXPLICIT 8 or 12 stays as given on both sides (topology updates with it are unsupported: DESIGN.md section 2).
-    if hasattr(model, "set_scratch_format") and model.cfg.get("scratch_format", 0) == 0:
+    if model.cfg.get("scratch_format", 0) == 0:
         model.set_scratch_format(16)
     model.train()
     mask.add_module(model)
@@ -160,7 +157,7 @@ def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
     sse = eng.forward_backward(sync=True)
     loss = sse / (img.shape[0] * img.shape[1] * img.shape[2])
     model.download_grads()             # no-op unless the width is zero-padded
-    for cb in list(getattr(model, "post_backward_callbacks", ())):
+    for cb in list(model.post_backward_callbacks):
         cb()
     if mask:
         mask.step(kwargs.get("scaler"))
@@ -184,8 +181,7 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     mask: Masking = kwargs.get("mask")
     lr_scheduler = kwargs.get("lr_scheduler")
     pbar = kwargs.get("pbar")
-    bulk = (n > 1 and isinstance(optim, EngineAdam) and not getattr(model, "_padded", False)
-            and not getattr(model, "post_backward_callbacks", None)
+    bulk = (n > 1 and isinstance(optim, EngineAdam) and not model._padded and not model.post_backward_callbacks
             and kwargs.get("criterion", F.mse_loss) is F.mse_loss and kwargs.get("preconditioner") is None
             and (mask is None or (mask.dense_gradients and mask.prune_rate_decay.mode != "cumulative"
                                   and getattr(optim, "applies_engine_mask", False))))
