@@ -13,21 +13,22 @@
 // lane d < 24 stores dword d, only the picture's last ragged dword goes out byte by byte.  sf_render16 runs the BITS = 16
 // form: u16 = min(max((int)(pred * 65535.0f), 0), 65535) through render_store_block16, lane d < 48 stores dword d.
 //
-// A render handle (create_fourier(.., render = true), siren_fit.hip) holds the parameters, the weight images, encoding.B
+// A render handle (create_fourier(.., render = true), fourier_host.hip) holds the parameters, the weight images, encoding.B
 // and the two coordinate vectors: none of the [D-1][WD][chunk] activation / gradient planes, the slab, gradients, Adam
 // moments, mask or SSE partials of sf_fourier_create.
 //
-// This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit).
+// This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit); ff_args_base, launch_ff
+// and create_fourier are fourier_host.hip's.
 
 namespace {
 
 // sf_render / sf_render16 on a FourierNet handle (render or training), after their argument checks: chunked as
 // run_pass_fourier.  out: bits / 8 bytes per sample
 int render_fourier(sf_engine* h, void* out, int bits, float* pred) {
-  if (!h->have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
+  if (!h->ff.have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
   DevGuard dev_guard(h->cfg.device);
   SF_TRY(refresh_images(h));
-  const int WD = h->WD, D = h->D, MS = h->MS;
+  const int WD = h->WD, D = h->D, MS = h->ff.MS;
   for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
     const Chunk k = chunk_at(c, h->npix, h->chunk_px);
     const double npx = (double)k.n_super * kSuper;

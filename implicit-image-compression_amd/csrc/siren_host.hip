@@ -1,0 +1,486 @@
+// siren_host.hip — SIREN handles of hidden width <= 256 on the host: the forward, backward, layer-0 and reduction launchers
+// (kernels: siren_kernels.hip, siren_s8.hip, siren_s8h.hip), weight images, the pass, the scratch formats, and create_handle
+// behind sf_create, sf_render_create (siren_render.hip) and the WaveletSiren sub-handles.  Included by siren_fit.hip.
+
+namespace {
+
+// 8-bit scratch: dL/dout is stored as residual * 2^10 in fp16 (residuals of 6e-8 .. 64 stay normal numbers); the
+// adaptive part of the gradient pre-scale is applied by k_bwd8<LAST> (siren_s8.hip)
+static constexpr float kResScale = 1024.0f;
+
+// per-layer fp8 delta scales (link[16] | inv[16] | norms in h->lsc), rebuilt with the weight images
+int launch_fp8_scales(sf_engine* h) {
+  Fp8ScaleArgs f = zeroed<Fp8ScaleArgs>();
+  f.params = h->params; f.depth = h->D; f.WD = h->WD; f.out_features = h->cfg.out_features;
+  for (int l = 0; l < h->D; ++l) f.off_w[l] = h->off_w[l];
+  f.om_first = h->cfg.first_omega_0; f.om_hidden = h->cfg.hidden_omega_0; f.link = h->lsc; f.inv = h->lsc + 16;
+  f.nrm = reinterpret_cast<double*>(h->lsc + 32);
+  SF_TRY(launch(h, k_fp8_norms, h->D - 1, 1024, 0, f));
+  return launch(h, k_fp8_links, 1, 64, 0, f);
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------
+size_t fwd_lds_bytes(int WD) { return (size_t)FwdGeom(WD).PIECES * 1024 + (size_t)WD * 16 + 64; }
+// k_fwd_pipe: weight image halves + layer-0 image + SSE partials
+size_t fwd_pipe_lds_bytes() { return (size_t)FwdGeom(256).PIECES * 1024 + (size_t)(256 / 32) * 1024 + 64; }
+
+// hidden = 256, depth >= 3 run the persistent pipeline kernel (k_fwd_pipe): one workgroup per CU walks the chunk
+bool fwd_is_pipe(const sf_engine* h) { return h->WD == 256 && h->D >= 3 && !h->wide; }
+// forward workgroups of a chunk with n_super 256-pixel groups (= the chunk's SSE partials)
+int fwd_grid(const sf_engine* h, int n_super) { return fwd_is_pipe(h) && n_super > h->dw_wg ? h->dw_wg : n_super; }
+
+// hidden = 256, depth >= 3: the hand-scheduled software pipeline over all layers (k_fwd_pipe)
+int launch_fwd_pipe(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
+  const size_t lds = fwd_pipe_lds_bytes();
+  const bool f16 = h->cfg.compute_dtype == SF_F16;
+  if (f16 && train && h->s8) return launch(h, k_fwd_pipe<OpF16, true, true>, n_wg, 512, lds, a);
+  return with_op(h, [&](auto op) {
+    using OP = decltype(op);
+    return train ? launch(h, k_fwd_pipe<OP, true, false>, n_wg, 512, lds, a) : launch(h, k_fwd_pipe<OP, false, false>, n_wg, 512, lds, a);
+  });
+}
+// the forward of a chunk on n_wg workgroups (fwd_grid): phase bytes (fp16 operands only), training or evaluation form
+int launch_fwd(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
+  if (fwd_is_pipe(h)) return launch_fwd_pipe(h, a, n_wg, train);
+  return with_width(h, [&](auto wd) {
+    constexpr int WD = decltype(wd)::value;
+    const size_t lds = fwd_lds_bytes(WD);
+    if (h->cfg.compute_dtype == SF_F16 && train && h->s8) return launch(h, k_fwd<WD, OpF16, true, true>, n_wg, 512, lds, a);
+    return with_op(h, [&](auto op) {
+      using OP = decltype(op);
+      return train ? launch(h, k_fwd<WD, OP, true>, n_wg, 512, lds, a) : launch(h, k_fwd<WD, OP, false>, n_wg, 512, lds, a);
+    });
+  });
+}
+
+// what every forward of a SIREN handle (width <= 256) is given for the chunk that starts at local pixel pix0: coordinates,
+// geometry, weight images and scales; the caller adds its outputs (scratch, target, prediction, partials)
+FwdArgs fwd_args_base(const sf_engine* h, long pix0, int n_super) {
+  FwdArgs fa = zeroed<FwdArgs>();
+  fill_pixels(h, pix0, fa);
+  fa.gh = h->gh; fa.gw = h->gw; fa.depth = h->D;
+  fa.l0tab = h->l0tab; fa.l0img = reinterpret_cast<const u32x4*>(h->l0img);
+  fa.wf = reinterpret_cast<const u32x4*>(h->wf);
+  fa.wf_last = reinterpret_cast<const u32x4*>(h->wf_last);
+  fa.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  fa.sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
+  fa.sc_last = 1.0f / h->wscale;
+  if (!h->cfg.outermost_linear) { fa.last_om = h->cfg.hidden_omega_0; fa.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
+  fa.nout = h->cfg.out_features;
+  fa.n_super = n_super;
+  return fa;
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------
+// The one tile table of the fused layer backward, <JW, IW, WR, WC> of (width, last): the last layer's out_features (<= 3,
+// padded to 32) rows against one wave per 32 inputs; a hidden layer's WD x WD block on 1, 2, 4 or 8 waves.
+template <int WD, bool LAST>
+struct BwdTile {
+  static constexpr int JW = LAST ? 32 : WD, IW = WD;
+  static constexpr int WR = LAST || WD == 32 ? 1 : 2, WC = LAST ? WD / 32 : WD == 32 ? 1 : WD / 64;
+};
+
+// 16-bit scratch (k_bwd).  Ring depths are chosen to fill the 160 KiB of LDS.
+template <int WD, bool LAST, bool P0, typename OP>
+int launch_bwd16(sf_engine* h, const BwdLayerArgs& a, int n_wg) {
+  using T = BwdTile<WD, LAST>;
+  constexpr bool H256 = WD == 256 && !LAST;
+  constexpr int WC = H256 && P0 ? kBwd16P0WC : T::WC, NB = H256 ? (P0 ? kBwd16P0NB : kBwd16NB) : 8;   // (the constants at the kernel list)
+  // NB-slot block ring + (when the stationary weight rows do not fit in registers) their parked part
+  // + (P0) the layer-0 table
+  constexpr int JW = T::JW, IW = T::IW, WR = T::WR, NWV = WR * WC, XT = (IW / 32) / NWV, KSX = LAST ? 1 : JW / 16;
+  constexpr int WSP = (XT * KSX > 24) ? (P0 ? 3 : 4) : 0;
+  const size_t lds = (size_t)NB * (JW / 16 + IW / 16) * 1024 + (size_t)NWV * XT * WSP * 1024 + (P0 ? (size_t)IW * 16 : 0);
+  return launch(h, k_bwd<JW, IW, WR, WC, LAST, P0, OP, NB>, n_wg, NWV * 64, lds, a);
+}
+// fused backward of one layer: last = the out_features(<=3, padded to 32)-row layer; p0 = its input layer is
+// layer 0, whose phases are re-derived from the coordinates.
+int launch_bwd(sf_engine* h, bool last, bool p0, const BwdLayerArgs& a, int n_wg) {
+  return with_width(h, [&](auto wd) {
+    return with_bool(last, p0, [&](auto l, auto p) {
+      return with_op(h, [&](auto op) { return launch_bwd16<decltype(wd)::value, decltype(l)::value, decltype(p)::value, decltype(op)>(h, a, n_wg); });
+    });
+  });
+}
+
+// 8-bit scratch path (siren_s8.hip, k_bwd8): fp16 operands only.  D8: fp8 deltas (scratch_format 8); else phase bytes with
+// 16-bit float deltas (scratch_format 12).  Ring depth NB, parked W^T k-steps PARK and phase-ring depth NBP:
+struct Ring8 { int NB, PARK, NBP; };
+template <int WD, bool LAST, bool P0, bool D8>
+constexpr Ring8 bwd8_ring() {
+  static_assert(WD != 256 || !D8 || LAST, "fp8 deltas, width 256, below the last layer: k_bwd8h (launch_bwd8)");
+  if (WD != 256) return {8, 0, 0};
+  // Ring depths / parked W^T k-steps of the 256-wide 8-wave forms are the combinations hipcc allocates WITHOUT a scratch
+  // reload inside the block loop (a reload's vmcnt(0) also waits for every LDS-DMA in flight, i.e. it serialises the loop on
+  // HBM latency): DESIGN.md section 4.
+  if (!D8) {
+    if (LAST) return {8, 0, 0};
+    // hidden: 5 delta slots (80 KiB) + 3 phase slots (24) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
+    // layer 1 (P0, no phase ring): 5 delta slots + sines + 4 parked k-steps + layer-0 table = 148 KiB
+    return P0 ? Ring8{5, 4, 0} : Ring8{5, 2, 3};
+  }
+  // 8 waves (two per SIMD); the ring slots hold the fp8 bytes (8 KiB per block): phase W converts in registers, phase X
+  // reads a 16-bit image expanded once per block (2 x 16 KiB).
+  // last layer: 3 MFMAs per block, bound by the latency of a step once its delta output is bytes - rings of 4 slots
+  // (72 KiB) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
+  // HBM-bound at 5.4 TB/s and the shallower rings cost 0.3 ms: format 12 keeps one workgroup per CU)
+  // (every layer below the last runs k_bwd8h: launch_bwd8)
+  return P0 ? Ring8{8, 0, 0} : Ring8{4, 0, 4};
+}
+template <int WD, bool LAST, bool P0, bool D8>
+int launch_bwd8_k(sf_engine* h, const Bwd8Args& a, int n_wg) {
+  using T = BwdTile<WD, LAST>;
+  constexpr int NB = bwd8_ring<WD, LAST, P0, D8>().NB, PARK = bwd8_ring<WD, LAST, P0, D8>().PARK, NBP = bwd8_ring<WD, LAST, P0, D8>().NBP;
+  constexpr size_t lds = bwd8_lds_bytes<T::JW, T::IW, T::WR * T::WC, LAST, P0, NB, PARK, NBP, D8>();
+  static_assert(lds <= 160 * 1024, "k_bwd8 LDS budget");
+  return launch(h, k_bwd8<T::JW, T::IW, T::WR, T::WC, LAST, P0, OpF16, NB, PARK, NBP, D8>, n_wg, T::WR * T::WC * 64, lds, a);
+}
+int launch_bwd8h(sf_engine* h, const Bwd8Args& a, int n_wg) {
+  constexpr size_t lds = bwd8h_lds_bytes<kBwd8hPark>();
+  static_assert(lds <= 160 * 1024, "k_bwd8h LDS budget");
+  return launch(h, k_bwd8h<kBwd8hPark>, n_wg, 512, lds, a);
+}
+int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
+  return with_width(h, [&](auto wd) {
+    return with_bool(last, p0, [&](auto l, auto p) {
+      return with_bool(h->d8, [&](auto d) {
+        constexpr int WD = decltype(wd)::value;
+        constexpr bool LAST = decltype(l)::value, P0 = decltype(p)::value, D8 = decltype(d)::value;
+        // fp8 deltas at width 256, every layer below the last: the slot-per-MFMA pipeline (siren_s8h.hip).  The forward of such
+        // a layer is k_fwd_pipe, which spills layer 0's phase bytes too, so run_pass never asks for the P0 form here.
+        if constexpr (WD == 256 && !LAST && D8) return P0 ? fail(SF_ERR_INVALID, "launch_bwd8: no P0 form below the last layer") : launch_bwd8h(h, a, n_wg);
+        else return launch_bwd8_k<WD, LAST, P0, D8>(h, a, n_wg);
+      });
+    });
+  });
+}
+
+// weight gradient of layer 0 (no data gradient needed): contraction of delta_0 with the coordinates
+template <int JW>
+int launch_dw0(sf_engine* h, const Dw0Args& a, int n_wg) {
+  const size_t lds = (size_t)8 * (JW / 16) * 1024 + 512;   // ring + coordinate table
+  return with_op(h, [&](auto op) { return launch(h, k_dw0<JW, decltype(op)>, n_wg, JW * 2, lds, a); });
+}
+// ... from fp8 deltas: two MFMAs per wave and block behind a workgroup barrier: bound by the latency of a step.  At width
+// 256 a 4-slot ring (64.5 KiB) lets two workgroups share a CU.
+constexpr int dw0_8_ring(int JW) { return JW == 256 ? 4 : 8; }
+template <int JW>
+int launch_dw0_8(sf_engine* h, const Dw0Args& a, int n_wg) {
+  constexpr int NB = dw0_8_ring(JW);
+  const size_t lds = (size_t)(NB * (JW / 32) + 2 * (JW / 16)) * 1024 + 512;   // byte ring + two fp16 images + coordinate table
+  return launch(h, k_dw0_8<JW, OpF16, NB>, n_wg, JW * 2, lds, a);
+}
+template <int JW>
+int launch_dw_first_t(sf_engine* h, const Dw0Args& a, int n_wg) {
+  return h->d8 ? launch_dw0_8<JW>(h, a, n_wg) : launch_dw0<JW>(h, a, n_wg);
+}
+int launch_dw_first(sf_engine* h, const Dw0Args& a, int n_wg) {
+  return with_width(h, [&](auto wd) { return launch_dw_first_t<decltype(wd)::value>(h, a, n_wg); });
+}
+// the fixed-order slab reduction of one layer's weight and bias gradient into the flat gradient
+int launch_reduce(sf_engine* h, const ReduceArgs& ra) {
+  return launch(h, k_reduce, (ra.rows_out * ra.cols_out + ra.rows_out + 15) / 16, 256, 0, ra);
+}
+
+// algorithmic GEMM FLOPs per pixel: forward 2*P_w, backward 4*P_w - 4*WD
+double flops_fwd_px(const sf_engine* h) {
+  const double W = h->WD;
+  return 2.0 * (2 * W + (h->D - 2) * W * W + h->cfg.out_features * W);
+}
+
+// the 16-bit weight images, the layer-0 table / image (and, format 8, the per-layer delta scales) of a width <= 256
+int refresh_images_siren(sf_engine* h) {
+  ImgArgs a = zeroed<ImgArgs>();
+  a.params = h->params;
+  a.depth = h->D;
+  a.WD = h->WD;
+  a.out_features = h->cfg.out_features;
+  for (int l = 0; l < h->D; ++l) {
+    a.off_w[l] = h->off_w[l];
+    a.off_b[l] = h->off_b[l];
+  }
+  a.wscale = h->wscale;
+  a.hscale = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
+  a.om_first = h->cfg.first_omega_0; a.om_hidden = h->cfg.hidden_omega_0;
+  a.fwd_is_f16 = h->cfg.compute_dtype == SF_F16;
+  a.wf = h->wf; a.wf_last = h->wf_last; a.wb = h->wb; a.wb_last = h->wb_last;
+  a.l0tab = h->l0tab;
+  a.l0img = h->l0img; a.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  long n = (long)(h->D - 2) * h->WD * h->WD;
+  const long n_min = (long)h->WD / 16 * 64 * 8;  // also covers the small tables
+  if (n < n_min) n = n_min;
+  if (n < 1024) n = 1024;
+  Launch L(h, K_IMAGES, 0, (double)n * 8);
+  if (h->d8 && h->lsc) {   // per-layer delta scales first: k_images folds them into the backward images
+    SF_TRY(launch_fp8_scales(h));
+    a.link = h->lsc;
+  }
+  SF_TRY(launch(h, k_images, (n + 255) / 256, 256, 0, a));
+  h->images_dirty = false;
+  return SF_OK;
+}
+
+// One pass of a SIREN handle of width <= 256 (run_pass has checked the handle's state): per chunk k_fwd -> k_bwd(last) ->
+// k_bwd(hidden l = depth-2 .. 1) -> k_dw0, each followed by the fixed-order slab reduction into the flat fp32 gradient.
+int run_pass_siren(sf_engine* h, bool train, float* pred, bool want_sse, int phases, long c_begin, long c_end) {
+  SF_TRY(refresh_images(h));
+  const int WD = h->WD, D = h->D;
+  long sse_off = 0;
+  for (long c = c_begin; c < (c_end < 0 ? n_chunks(h->npix, h->chunk_px) : c_end); ++c) {
+    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+    const long n_pb = k.n_pb;
+    const double npx = n_pb * 32.0;
+    FwdArgs fa = fwd_args_base(h, k.pix0, k.n_super);
+    fa.P = h->Pbuf; fa.p_stride = h->p_stride; fa.Dlast = h->Dlast;
+    fa.dfac = train ? h->wv.dfac_out : nullptr;
+    fa.img = h->img;
+    fa.gscale = h->d8 ? kResScale : gscale(h);
+    fa.pred = pred;
+    fa.sse_part = h->sse_part + sse_off;
+    const int n_fwd_wg = fwd_grid(h, k.n_super);
+    sse_off += n_fwd_wg;
+    if (phases & kPassFwd) {
+      Launch L(h, K_FWD, flops_fwd_px(h) * npx,
+               npx * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
+      SF_TRY(launch_fwd(h, fa, n_fwd_wg, train));
+    }
+    if (!train || !(phases & kPassBwd)) continue;
+    // backward, last layer first; every layer kernel is followed by the fixed-order slab reduction
+    const int PBS = 2;   // k_dw stages two pixel blocks at a time; k_bwd accepts any block count
+    int n_wg = (int)((n_pb + PBS - 1) / PBS);
+    if (n_wg > h->dw_wg) n_wg = h->dw_wg;
+    long pb_per_wg = (n_pb + n_wg - 1) / n_wg;
+    pb_per_wg = (pb_per_wg + PBS - 1) / PBS * PBS;
+    n_wg = (int)((n_pb + pb_per_wg - 1) / pb_per_wg);
+    const size_t img_pieces = (size_t)WD * WD / 8;
+    // what Bwd8Args and BwdLayerArgs share for layer l >= 1: deltas in and out, phases of the layer below, the backward image
+    auto fill_layer = [&](auto& ba, int l) {
+      const bool last = l == D - 1;
+      fill_grid(h, k.pix0, ba);
+      ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
+      ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
+      ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
+      ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
+                   : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
+      ba.n_pb = n_pb; ba.slab = h->slab; ba.l0tab = h->l0tab; ba.sc_first = fa.sc_first;
+    };
+    for (int l = D - 1; l >= 0; --l) {
+      const bool last = l == D - 1;
+      const double rows = last ? h->cfg.out_features : WD;
+      ReduceArgs ra = zeroed<ReduceArgs>();
+      ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
+      if (h->d8) {   // last layer: dW from the statically scaled residual; layers below: the chunk's adaptive pre-scale
+        ra.scale = (float)(1.0 / ((double)kResScale * (double)h->cfg.out_features * h->n_total));
+        ra.scale_dev = last ? nullptr : h->scale_dev;
+        ra.scale2_dev = (last || !h->lsc) ? nullptr : h->lsc + 16 + l;
+      }
+      ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l];
+      // a layer above 0: rows x WD weight gradient from slabs of (last: 32, else WD) rows
+      ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD; ra.rows_out = (int)rows; ra.cols_out = WD; ra.mode = 0;
+      if (l > 0 && h->s8) {
+        // layer 1: with fp8 deltas at width 256 the pipeline forward also spills layer 0's phase bytes, so this layer runs the
+        // hidden-layer kernel (k_bwd8h) like the others; else the form that re-derives the layer-0 phases from the coordinates
+        const bool l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h), p0 = l - 1 == 0 && !(l0_bytes && !last);
+        Bwd8Args ba = zeroed<Bwd8Args>();
+        fill_layer(ba, l);
+        ba.sse_part = fa.sse_part; ba.n_part = n_fwd_wg;
+        ba.inv_chunk_values = 1.0 / ((double)h->cfg.out_features * (double)k.px);
+        ba.n_values = (double)h->cfg.out_features * h->n_total;
+        ba.res_scale = kResScale; ba.target = kFp8Target; ba.scale_out = h->scale_dev;
+        ba.zeros = reinterpret_cast<const u32x4*>(h->pad8); ba.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
+        // hidden 256: the last-layer kernel keeps two workgroups per CU (its slab rows are 32 wide: the slab has room)
+        if (last && !p0 && WD == 256 && h->d8) ra.n_wg = (int)std::min<long>((n_pb + PBS - 1) / PBS, 2L * h->dw_wg);
+        const double db = h->d8 ? 1.0 : 2.0;   // bytes per delta
+        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
+                 npx * ((last ? 32.0 : WD * db) + WD * db + (p0 ? 0.0 : WD * 1.0)));
+        SF_TRY(launch_bwd8(h, last, p0, ba, ra.n_wg));
+      } else if (l > 0) {
+        const bool p0 = l - 1 == 0;
+        BwdLayerArgs ba = zeroed<BwdLayerArgs>();
+        fill_layer(ba, l);
+        ba.pb_per_wg = (int)pb_per_wg;
+        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
+                 npx * ((last ? 64.0 : WD * 2.0) + WD * (p0 ? 2.0 : 4.0)));
+        SF_TRY(launch_bwd(h, last, p0, ba, n_wg));
+      } else {
+        Dw0Args da = zeroed<Dw0Args>();
+        fill_grid(h, k.pix0, da);
+        da.D = h->Dbuf; da.ks_total = WD / 16; da.ks_off = 0; da.n_pb = n_pb; da.slab = h->slab;
+        const long cap0 = (h->d8 && WD == 256) ? 2L * h->dw_wg : (long)h->dw_wg;      // k_dw0_8<256>: two workgroups per CU
+        ra.n_wg = (int)(n_pb < cap0 ? n_pb : cap0);
+        ra.slab_rows = WD; ra.slab_cols = 32; ra.rows_out = WD; ra.cols_out = 2; ra.mode = 1;
+        Launch L(h, K_DW_FIRST, 4.0 * WD * npx, WD * (h->d8 ? 1.0 : 2.0) * npx);
+        SF_TRY(launch_dw_first(h, da, ra.n_wg));
+      }
+      const int n = ra.rows_out * ra.cols_out + ra.rows_out;
+      Launch L(h, K_REDUCE, 0, (double)n_wg * n * 4.0);
+      if (l > 0 && !last)   // slab layout == flat gradient layout [W | b]
+        SF_TRY(launch(h, k_reduce_vec, (n / 4 + 7) / 8, 256, 0, h->slab, n_wg, n, n / 4, h->grads + h->off_w[l], ra.accumulate,
+                      ra.scale, ra.scale_dev, ra.scale2_dev));
+      else SF_TRY(launch_reduce(h, ra));
+    }
+  }
+  if ((want_sse || train) && !h->wv.ext_dout) SF_TRY(launch_sse_reduce(h, sse_off));
+  return SF_OK;
+}
+
+// what the forward reads, on a training and on a render handle alike: the forward weight images (width <= 256; the wide
+// path has its own blocked images), the layer-0 table / image and the two coordinate vectors
+int alloc_forward_inputs(sf_engine* h) {
+  const int WD = h->WD, D = h->D;
+  if (!h->wide) {
+    SF_TRY(dev_alloc(h, h->wf, (size_t)(D - 2 > 0 ? D - 2 : 1) * FwdGeom(WD).PIECES * 1024));
+    SF_TRY(dev_alloc(h, h->wf_last, (size_t)(WD / 16 + 1) * 1024));
+  }
+  SF_TRY(dev_alloc(h, h->l0tab, (size_t)WD * 16));
+  if (WD == 256) SF_TRY(dev_alloc(h, h->l0img, (size_t)(WD / 32) * 1024));
+  SF_TRY(dev_alloc(h, h->gh, (size_t)h->cfg.height * 4));
+  return dev_alloc(h, h->gw, (size_t)h->cfg.width * 4);
+}
+
+// layer strides of the phase / delta scratch for the handle's current format
+void set_scratch_strides(sf_engine* h) {
+  const long chunk = h->chunk_px;
+  const int WD = h->WD;
+  h->p_stride = chunk / 32 * (h->s8 ? WD / 32 : WD / 16) * 64 + 37 * 64;
+  h->d_stride = chunk / 32 * (h->d8 ? WD / 32 : WD / 16) * 64 + 37 * 64;
+  h->a_stride = chunk / 32 * (WD / 16) * 64 + 37 * 64;
+}
+// sf_create and sf_render_create (siren_render.hip): one validation, one geometry; a render handle allocates the forward's
+// inputs only.  sub_network: the handle is one of the two SIRENs of a WaveletSiren handle, which points params / grads / m /
+// v / mask at slices of its own joint vectors - nothing is allocated for them here
+int create_handle(const sf_config* cfg, sf_handle** out, bool render, bool sub_network = false) {
+  auto check = [&](Grid& g) -> int {
+    if (cfg->out_features < 1 || cfg->out_features > 3) return fail(SF_ERR_INVALID, "out_features must be 1..3");
+    if (cfg->depth < 2 || cfg->depth > 16) return fail(SF_ERR_INVALID, "depth must be 2..16");
+    if (cfg->hidden != 32 && cfg->hidden != 64 && cfg->hidden != 128 && cfg->hidden != 256 && cfg->hidden != 512 &&
+        cfg->hidden != 1024)
+      return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128, 256, 512 or 1024 in this build");
+    if (cfg->hidden > 256 && cfg->depth < 3) return fail(SF_ERR_INVALID, "hidden > 256 needs depth >= 3");
+    if (render && cfg->hidden > 256)
+      return fail(SF_ERR_INVALID, "sf_render_create: the render kernel is not built for the wide path (hidden 512 / 1024): "
+                                  "run the model's own forward on the host side");
+    if (cfg->compute_dtype != SF_BF16 && cfg->compute_dtype != SF_F16)
+      return fail(SF_ERR_INVALID, "compute_dtype must be SF_BF16 or SF_F16");
+    if (cfg->height < 1 || cfg->width < 1) return fail(SF_ERR_INVALID, "bad image size");
+    if (cfg->scratch_format != 0 && cfg->scratch_format != 8 && cfg->scratch_format != 12 && cfg->scratch_format != 16)
+      return fail(SF_ERR_INVALID, "scratch_format must be 0 (auto), 8, 12 or 16");
+    if ((cfg->scratch_format == 8 || cfg->scratch_format == 12) && cfg->compute_dtype != SF_F16)
+      return fail(SF_ERR_INVALID, "scratch_format 8 / 12 need compute_dtype SF_F16");
+    int r0 = cfg->row_begin, r1 = cfg->row_end;
+    if (r0 == 0 && r1 == 0) r1 = cfg->height;
+    if (r0 < 0 || r1 > cfg->height || r0 >= r1) return fail(SF_ERR_INVALID, "bad row range");
+    // the layer-0 / layer-1 gradient kernels decode (row, col) of a local pixel p as row = (p * ceil(2^40 / W)) >> 40,
+    // exact while p * W < 2^40, i.e. local_rows * W^2 < 2^40 (an unsharded 8192 x 8192 grid sits at 2^39)
+    if ((double)(r1 - r0) * (double)cfg->width * (double)cfg->width >= 1099511627776.0)
+      return fail(SF_ERR_INVALID, "grid too large for one handle: (row_end - row_begin) * width^2 must stay below 2^40 "
+                                  "(shard the rows over more handles)");
+    g = {cfg->height, cfg->width, r0, r1};
+    return SF_OK;
+  };
+  auto init = [&](sf_engine* h, const Grid& g) -> int {
+    h->cfg = *cfg;
+    h->cfg.row_begin = g.row_begin;
+    h->cfg.row_end = g.row_end;
+    adam_defaults(h);
+    h->D = cfg->depth;
+    h->WD = cfg->hidden;
+    h->wide = cfg->hidden > 256;
+    {
+      // auto (fp16 operands, hidden <= 256): phase bytes always; fp8 deltas (format 8) when the image has >= 2^20 pixels - a
+      // gradient then sums the zero-mean fp8 rounding over >= 10^6 terms (within the 0.05 dB criterion on every reference
+      // fixture even at 2^16 pixels) and the backward kernels are bandwidth-bound; smaller fits are
+      // launch-latency-bound and keep 16-bit deltas (format 12).  A masked fit is moved to format 16 by sf_set_masks.
+      int fmt = cfg->scratch_format;
+      h->fmt_auto = fmt == 0;
+      const bool mega = (double)cfg->height * (double)cfg->width >= 1048576.0;
+      // (wider than 256: the layer-at-a-time kernels take the byte formats where bandwidth matters - from 2^20 pixels; fp8 deltas up to
+      // width 512, where a reference-minted fixture at 2^20 pixels pins them (tests/golden/plateau_ns_512x4_1024.npz: -0.0002 dB);
+      // phase bytes only above)
+      if (fmt == 0) fmt = cfg->compute_dtype != SF_F16 ? 16 : h->wide ? (mega ? (cfg->hidden <= 512 ? 8 : 12) : 16) : (mega ? 8 : 12);
+      if (render) { fmt = 16; h->fmt_auto = false; }   // no scratch at all: nothing of the byte formats applies
+      h->cfg.scratch_format = fmt;
+      h->s8 = fmt == 8 || fmt == 12;
+      h->d8 = fmt == 8;
+    }
+    layer_offsets(h, 2);   // named_parameters() order (siren.py:90-118)
+    // fp16 forward images are scaled by 2^8 so that small weights stay normal numbers
+    h->wscale = cfg->compute_dtype == SF_F16 ? 256.0f : 1.0f;
+    // fp16 backward operands: dL/dout = resid/(3N) is pre-scaled by 2^k ~ 4*3N so the deltas sit around 1
+    // (fp16 normal range 6e-5..65504); every gradient is multiplied back by 2^-k in the slab reduction
+    if (cfg->compute_dtype == SF_F16) h->gpre = (float)exp2(ceil(log2((double)cfg->out_features * (double)cfg->height * (double)cfg->width)) + 2.0);
+    // chunking
+    // default: 4 Mi pixels at width <= 256 (29 GB of scratch at 256x8); the same scratch budget for wider layers
+    const long chunk = chunk_pixels(cfg->chunk_pixels > 0 ? cfg->chunk_pixels : (1L << 22) / (h->wide ? cfg->hidden / 256 : 1), h->npix);
+    h->chunk_px = chunk;
+    const int WD = h->WD, D = h->D;
+    // layer stride of the scratch tensors, padded so that the three streams a kernel touches at once are
+    // not a power of two apart (HBM channel aliasing)
+    // (8-bit scratch: one piece per 32-neuron tile instead of one per 16-neuron k-step)
+    set_scratch_strides(h);
+
+    if (!sub_network) SF_TRY(alloc_state(h, !render));
+    SF_TRY(alloc_forward_inputs(h));
+    if (render) return SF_OK;   // parameters, forward weight images, layer-0 table / image, the two coordinate vectors
+    const size_t img_elems = (size_t)(D - 2 > 0 ? D - 2 : 1) * WD * WD;
+    SF_TRY(dev_alloc(h, h->wb, img_elems * 2));
+    if (h->wide) {   // blocked images of siren_wide.hip
+      SF_TRY(dev_alloc(h, h->wf, img_elems * 2));
+      SF_TRY(dev_alloc(h, h->wf_last, (size_t)(WD / 16) * 1024));
+      SF_TRY(dev_alloc(h, h->wb_last, (size_t)(WD / 256) * 32 * 1024));
+      SF_TRY(dev_alloc(h, h->biasw, ((size_t)(D - 2) * WD + 32) * 4));
+    } else {
+      SF_TRY(dev_alloc(h, h->wb_last, (size_t)WD / 32 * 64 * 16));
+    }
+    SF_TRY(dev_alloc(h, h->Pbuf, (size_t)(D - 1) * h->p_stride * 16));
+    SF_TRY(dev_alloc(h, h->Dbuf, (size_t)(D - 1) * h->d_stride * 16));
+    if (h->wide) SF_TRY(dev_alloc(h, h->Abuf, (size_t)(D - 1) * h->a_stride * 16));
+    SF_TRY(dev_alloc(h, h->Dlast, (size_t)chunk / 32 * 2 * 64 * 16));
+    { const size_t sw = WD > 256 ? 256 : WD; SF_TRY(dev_alloc(h, h->slab, (size_t)h->dw_wg * (sw * sw + sw) * 4 + 4096)); }
+    SF_TRY(alloc_sse(h, chunked_sse_parts(h)));
+    SF_TRY(dev_alloc(h, h->scale_dev, 16));
+    SF_TRY(dev_alloc(h, h->pad8, 16384));
+    SF_TRY(dev_alloc(h, h->lsc, 32 * 4 + 16 * 8));
+    if (hipMemset(h->pad8, 0, 16384) != hipSuccess) return fail(SF_ERR_NOMEM, "hipMemset failed");
+    const float sc[2] = {(float)((double)h->gpre / ((double)cfg->out_features * h->n_total)), 1.0f / h->gpre};
+    if (hipMemcpy(h->scale_dev, sc, sizeof(sc), hipMemcpyHostToDevice) != hipSuccess) return fail(SF_ERR_HIP, "hipMemcpy(scale) failed");
+    return SF_OK;
+  };
+  return create_with(cfg, out, &sf_config::in_features, Model::Siren, render, check, init);
+}
+
+// An auto-format handle that receives a mask leaves the 8-bit scratch: fp8 deltas under one scale per chunk underflow in
+// a 90 %-sparse network, and topology updates rank small gradients that phase bytes blur.
+// (the new buffers are allocated BEFORE anything of the handle changes: a failed hipMalloc leaves the handle exactly as it
+//  was - format, strides and scratch - and returns SF_ERR_NOMEM)
+int switch_scratch_format(sf_engine* h, int fmt) {
+  hipStreamSynchronize(h->ctx->stream);
+  const sf_config cfg0 = h->cfg;
+  const bool s8_0 = h->s8, d8_0 = h->d8;
+  h->cfg.scratch_format = fmt;
+  h->s8 = fmt == 8 || fmt == 12;
+  h->d8 = fmt == 8;
+  set_scratch_strides(h);
+  u32x4 *newP = nullptr, *newD = nullptr;
+  if (dev_alloc(h, newP, (size_t)(h->D - 1) * h->p_stride * 16) || dev_alloc(h, newD, (size_t)(h->D - 1) * h->d_stride * 16)) {
+    dev_free(h, newP);
+    (void)hipGetLastError();
+    h->cfg = cfg0; h->s8 = s8_0; h->d8 = d8_0;
+    set_scratch_strides(h);
+    return fail(SF_ERR_NOMEM, "hipMalloc failed while moving the scratch to format 16 (the handle keeps its format)");
+  }
+  if (h->graph.exec) { hipGraphExecDestroy(h->graph.exec); h->graph.exec = nullptr; }
+  dev_free(h, h->Pbuf);
+  dev_free(h, h->Dbuf);
+  h->Pbuf = newP; h->Dbuf = newD;
+  h->images_dirty = true;      // (the backward images carry the fp8 per-layer scales only under format 8)
+  return SF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, false); } SF_CATCH
+
+}  // extern "C"

@@ -21,7 +21,8 @@
 // ds_bpermute and the wave stores them in one store instruction (render_store_block16).  Only a picture with an odd sample
 // count has a ragged last dword: its low half goes out as one 2-byte store.
 //
-// This file is included at the end of siren_fit.hip (one translation unit, as every kernel file of the library).
+// This file is included at the end of siren_fit.hip (one translation unit, as every kernel file of the library); the host
+// part builds on siren_host.hip (create_handle, fwd_args_base, the forward geometry).
 
 namespace sf {
 
@@ -146,15 +147,19 @@ int render_any(sf_handle* h, void* out, int bits, float* pred) {
   const std::string fn = bits == 16 ? "sf_render16" : "sf_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
   if (!h) return fail(SF_ERR_INVALID, "null argument");
   if (!out && !pred) return fail(SF_ERR_INVALID, fn + ": " + on + " and pred_dev are both NULL");
-  if (h->wavelet && h->render)
+  if (h->model == Model::Wavelet && h->render)
     return fail(SF_ERR_INVALID, fn + ": a WaveletSiren render handle (sf_wavelet_render_create) is drawn by sf_wavelet_render" +
                                     (bits == 16 ? "16" : ""));
-  if (h->wide || h->wavelet)
+  if (h->wide || h->model == Model::Wavelet)
     return fail(SF_ERR_INVALID, fn + ": built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create) "
                                      "and FourierNet handles (sf_fourier_create / sf_fourier_render_create)");
   if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
-  if (h->fourier) return render_fourier(h, out, bits, pred);
+  switch (h->model) {
+    case Model::Siren: break;
+    case Model::Fourier: return render_fourier(h, out, bits, pred);
+    case Model::Wavelet: __builtin_unreachable();   // refused above
+  }
   DevGuard dev_guard(h->cfg.device);
   SF_TRY(refresh_images(h));
   for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {

@@ -24,7 +24,8 @@
 // siren_render.hip) and the wave stores them in two store instructions.  Only an output with an odd sample count has a
 // ragged last dword: its low half goes out as one 2-byte store.
 //
-// This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit).
+// This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit); the creator builds on
+// wavelet_host.hip.
 
 namespace sf {
 
@@ -137,69 +138,68 @@ void wv_coeff_span(int o0, int o1, int H, int* lo, int* hi) {
 }
 
 int create_wavelet_render(const sf_wavelet_render_config* cfg, sf_handle** out) {
-  if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (cfg->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
-  SF_TRY(wavelet_check_network(cfg));
-  SF_TRY(wavelet_check_image(cfg->height, cfg->height, cfg->chunk_pixels));
-  const int H = cfg->height, n = (H + 5) / 2;
-  const int max_rows = cfg->max_rows ? cfg->max_rows : H, max_cols = cfg->max_cols ? cfg->max_cols : H;
-  if (max_rows < 1 || max_rows > H || max_cols < 1 || max_cols > H)
-    return fail(SF_ERR_INVALID, "sf_wavelet_render_create: max_rows / max_cols must be 0 (the whole picture) or 1 .. height");
-  // the largest coefficient window of any max_rows x max_cols pixel window (the span's length depends on where it sits)
-  auto max_span = [&](int len) {
-    int best = 0;
-    for (int o = 0; o + len <= H; ++o) {
-      int lo, hi;
-      wv_coeff_span(o, o + len, H, &lo, &hi);
-      best = std::max(best, hi - lo);
-    }
-    return best;
+  HandlePtr sub[2];
+  int max_rows = 0, max_cols = 0, cr = 0, cc = 0;   // the largest pixel window, and the largest coefficient window of any such
+  auto check = [&](Grid& g) -> int {
+    SF_TRY(wavelet_check_network(cfg));
+    SF_TRY(wavelet_check_image(cfg->height, cfg->height, cfg->chunk_pixels));
+    const int H = cfg->height;
+    max_rows = cfg->max_rows ? cfg->max_rows : H; max_cols = cfg->max_cols ? cfg->max_cols : H;
+    if (max_rows < 1 || max_rows > H || max_cols < 1 || max_cols > H)
+      return fail(SF_ERR_INVALID, "sf_wavelet_render_create: max_rows / max_cols must be 0 (the whole picture) or 1 .. height");
+    auto max_span = [&](int len) {   // (the span's length depends on where it sits)
+      int best = 0;
+      for (int o = 0; o + len <= H; ++o) {
+        int lo, hi;
+        wv_coeff_span(o, o + len, H, &lo, &hi);
+        best = std::max(best, hi - lo);
+      }
+      return best;
+    };
+    cr = max_span(max_rows); cc = max_span(max_cols);
+    g = {H, H, 0, H};
+    return wavelet_subs(wavelet_sub_config(cfg, cr, cc), true, sub);
   };
-  const int cr = max_span(max_rows), cc = max_span(max_cols);
-  HandlePtr owner;
-  SF_TRY(wavelet_begin(wavelet_sub_config(cfg, cr, cc), true, H, owner));
-  DevGuard dev_guard(cfg->device);
-  sf_engine* h = owner.get();
-  h->wv_max_rows = max_rows; h->wv_max_cols = max_cols;
-  SF_TRY(dev_alloc(h, h->params, h->P * 4));
-  SF_TRY(dev_alloc(h, h->wv_pred, (size_t)2 * cr * cc * 3 * 4));   // the one pair of coefficient buffers
-  SF_TRY(dev_alloc(h, h->gh, (size_t)n * 4));   // the caller's FULL coefficient-grid vectors
-  SF_TRY(dev_alloc(h, h->gw, (size_t)n * 4));
-  for (int s = 0; s < 2; ++s) h->wv_sub[s]->params = h->params + s * h->wv_sub[s]->P;   // the two halves of the joint vector
-  hipMemsetAsync(h->params, 0, h->P * 4, h->stream);
-  *out = owner.release();
-  return SF_OK;
+  auto init = [&](sf_engine* h, const Grid& g) -> int {
+    wavelet_begin(h, sub, g.height);
+    h->wv.max_rows = max_rows; h->wv.max_cols = max_cols;
+    SF_TRY(alloc_state(h, false));
+    SF_TRY(dev_alloc(h, h->wv.pred, (size_t)2 * cr * cc * 3 * 4));   // the one pair of coefficient buffers
+    SF_TRY(dev_alloc(h, h->gh, (size_t)h->wv.n * 4));   // the caller's FULL coefficient-grid vectors
+    SF_TRY(dev_alloc(h, h->gw, (size_t)h->wv.n * 4));
+    for (int s = 0; s < 2; ++s) h->wv.sub[s]->params = h->params + s * h->wv.sub[s]->P;   // the two halves of the joint vector
+    return SF_OK;
+  };
+  return create_with(cfg, out, (int32_t sf_wavelet_render_config::*)nullptr, Model::Wavelet, true, check, init);
 }
 
 // sf_wavelet_render (bits = 8) and sf_wavelet_render16 (bits = 16): one set of argument checks, one pair of chunk loops
 int wavelet_render_any(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, void* out, int bits, float* pred) {
   const std::string fn = bits == 16 ? "sf_wavelet_render16" : "sf_wavelet_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
   if (!h) return fail(SF_ERR_INVALID, "null argument");
-  if (!h->wavelet)
+  if (h->model != Model::Wavelet)
     return fail(SF_ERR_INVALID, fn + ": not a WaveletSiren handle (sf_wavelet_render_create / sf_wavelet_create)");
   if (!out && !pred) return fail(SF_ERR_INVALID, fn + ": " + on + " and pred_dev are both NULL");
   if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
   const int H = h->cfg.height;
   if (row0 < 0 || row1 > H || row0 >= row1 || col0 < 0 || col1 > H || col0 >= col1)
     return fail(SF_ERR_INVALID, fn + ": need 0 <= row0 < row1 <= height and 0 <= col0 < col1 <= height");
-  if (h->render && (row1 - row0 > h->wv_max_rows || col1 - col0 > h->wv_max_cols))
+  if (h->render && (row1 - row0 > h->wv.max_rows || col1 - col0 > h->wv.max_cols))
     return fail(SF_ERR_INVALID, fn + ": the window is larger than the max_rows x max_cols the handle was created for");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   DevGuard dev_guard(h->cfg.device);
-  SF_TRY(refresh_images(h));   // (also points the sub-handles at the current stream and profiler)
-  wv_sync(h);
+  SF_TRY(refresh_images(h));
   int i0, i1, j0, j1;
   wv_coeff_span(row0, row1, H, &i0, &i1);
   wv_coeff_span(col0, col1, H, &j0, &j1);
   const int cr = i1 - i0, cc = j1 - j0;
   const long nn = (long)cr * cc;
   // the full coordinate vectors: a render handle keeps them itself, a training handle in its sub-networks
-  const float* gh = h->render ? h->gh : h->wv_sub[0]->gh;
-  const float* gw = h->render ? h->gw : h->wv_sub[0]->gw;
-  float* const p_sub[2] = {h->wv_pred, h->wv_pred + nn * 3};
+  const float* gh = h->render ? h->gh : h->wv.sub[0]->gh;
+  const float* gw = h->render ? h->gw : h->wv.sub[0]->gw;
+  float* const p_sub[2] = {h->wv.pred, h->wv.pred + nn * 3};
   for (int s = 0; s < 2; ++s) {
-    sf_engine* e = h->wv_sub[s];
+    sf_engine* e = h->wv.sub[s];
     for (long c = 0; c < n_chunks(nn, e->chunk_px); ++c) {
       const Chunk k = chunk_at(c, nn, e->chunk_px);
       const int n_super = k.n_super;
@@ -212,9 +212,8 @@ int wavelet_render_any(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, i
       SF_TRY(launch_render(e, fa, fwd_grid(e, n_super)));
     }
   }
-  WvRenderArgs a;
-  memset(&a, 0, sizeof(a));
-  a.H = H; a.n = h->wv_n; a.up = h->wv_up;
+  WvRenderArgs a = zeroed<WvRenderArgs>();
+  a.H = H; a.n = h->wv.n; a.up = h->wv.up;
   a.row0 = row0; a.col0 = col0; a.cols = col1 - col0;
   a.npx = (long)(row1 - row0) * (col1 - col0);
   a.i0 = i0; a.j0 = j0; a.cc = cc;

@@ -1,6 +1,8 @@
 """Child of tests/test_gpu_launch_plan.py: every launch path of the engine runs once, eagerly and with profiling on, in ONE
 fresh process; per case the per-kernel launch counts with their flops / bytes figures (profile_report), the loss and a
-sha256 of the gradient or of the rendered bytes go into the JSON the parent reads.
+sha256 of the gradient or of the rendered bytes go into the JSON the parent reads.  One more case runs with profiling off
+(graph replay needs that): sf_step on a WaveletSiren handle, eagerly and replayed, whose sub-handles launch through the
+handle's own launch context - on the capturing stream while a step is captured.
 Usage: _launch_plan_child.py OUT.json        (SIREN_FIT_LIB=<another build> records that build's plan)"""
 import hashlib
 import json
@@ -118,6 +120,27 @@ def wavelet_render():
     return rendered(eng)
 
 
+STEP_LRS = (1e-3, 5e-4, 2.5e-4)
+
+
+def wavelet_step():
+    """64x3 at H = 2 (9 coefficients, one chunk, as wavelet_64x3_H2_one_chunk): sf_step with three learning rates and
+    want_loss from the same parameters on two fresh handles, eager and with set_graph_replay(True); the three losses and
+    the sha256 of the parameters after them"""
+    res = {}
+    for mode in ("eager", "replay"):
+        eng = E.WaveletEngine(2, 2, 64, 3)
+        rows = cols = torch.linspace(0, 1, eng.n).cuda()
+        eng.set_coords(rows, cols)
+        eng.set_params(torch.cat([siren_flat(64, 3)] * 2))
+        eng.set_target(so.synthetic_image(2, 2, seed=3).cuda().contiguous())
+        eng.set_graph_replay(mode == "replay")
+        losses = eng.step(list(STEP_LRS), want_loss=True)
+        res[mode] = {"losses": losses, "sha256_params": sha(eng.get_params())}
+        eng.close()
+    return res
+
+
 def cases():
     out = []
     for hidden in (32, 64, 128, 256):
@@ -149,7 +172,9 @@ def main():
     for name, fn in cases():
         res[name] = fn()
         print(name, res[name]["sha256"][:12], flush=True)
-    json.dump({"lib": os.path.basename(E._LIB_PATH), "cases": res}, open(sys.argv[1], "w"), indent=1, sort_keys=True)
+    step = wavelet_step()
+    print("wavelet_step", step["eager"]["sha256_params"][:12], step["replay"]["sha256_params"][:12], flush=True)
+    json.dump({"lib": os.path.basename(E._LIB_PATH), "cases": res, "wavelet_step": step}, open(sys.argv[1], "w"), indent=1, sort_keys=True)
 
 
 if __name__ == "__main__":

@@ -66,12 +66,17 @@ def test_no_exception_crosses_the_c_abi():
     assert lib.sf_debug_throw(1) == -1 and b"sf_debug_throw" in lib.sf_last_error()         # std::runtime_error -> SF_ERR_INVALID
     assert lib.sf_debug_throw(2) == -1 and b"unexpected exception" in lib.sf_last_error()   # anything else
     assert lib.sf_debug_throw(3) == 0
+    import glob
     import re
-    src = open(os.path.join(os.path.dirname(_engine._LIB_PATH), "siren_fit.hip")).read()
-    body = src[src.index('extern "C" {'):src.index('}  // extern "C"')]
-    entry = re.findall(r"^(?:int|const char\*) (sf_\w+)\(", body, flags=re.M)
-    guarded = re.findall(r"^int (sf_\w+)\([^{]*\) try \{", body, flags=re.M)
+    entry, guarded = [], []
+    for path in sorted(glob.glob(os.path.join(os.path.dirname(_engine._LIB_PATH), "*.hip"))):   # every file with entry points
+        src = open(path).read()
+        for body in re.findall(r'^extern "C" \{.*?^\}  // extern "C"', src, flags=re.M | re.S):
+            entry += re.findall(r"^(?:int|const char\*) (sf_\w+)\(", body, flags=re.M)
+            guarded += re.findall(r"^int (sf_\w+)\([^{]*\) try \{", body, flags=re.M)
     assert set(entry) - set(guarded) <= {"sf_abi_version", "sf_last_error"}, set(entry) - set(guarded)
+    # the scan saw every entry point the header declares, once: a file split cannot lose one from it
+    assert sorted(entry) == sorted(_engine.exported_symbols())
 
 
 def test_kernel_sources_have_one_build_and_no_switches():

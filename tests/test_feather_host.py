@@ -117,7 +117,8 @@ def test_feather_symbols_are_declared_exported_and_guarded():
     if os.path.exists(lib):
         cdll = ctypes.CDLL(lib)
         assert all(hasattr(cdll, n) for n in names)
-    src = open(os.path.join(PKG, "csrc", "siren_fit.hip")).read()
+    src = open(os.path.join(PKG, "csrc", "feather_host.hip")).read()
+    assert '#include "feather_host.hip"' in open(os.path.join(PKG, "csrc", "siren_fit.hip")).read()
     for n in names:   # every entry point is a function-try-block inside extern "C"
         assert re.search(n + r"\([^)]*\)\s*try\s*\{", src), n
 

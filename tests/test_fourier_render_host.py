@@ -41,8 +41,13 @@ def test_symbols_and_build_list():
     prereq = next(l for l in mk.splitlines() if l.startswith("libsiren_fit.so:"))
     assert "fourier_render.hip" in prereq.split()
     fit = open(os.path.join(CSRC, "siren_fit.hip")).read()
+    included = [l.split('"')[1] for l in fit.splitlines() if l.startswith('#include "') and not l.startswith('#include "../')]
+    for name in included:                                        # every file of the one translation unit is a prerequisite
+        assert name in prereq.split(), name
+    assert {"engine.h", "siren_host.hip", "wide_host.hip", "fourier_host.hip", "wavelet_host.hip", "feather_host.hip"} <= set(included)
+    assert included[-3:] == ["siren_render.hip", "wavelet_render.hip", "fourier_render.hip"]    # the render kernels come last
     assert fit.rstrip().endswith('#include "fourier_render.hip"')
-    assert '"k_wv_render", "k_ff_render"}' in fit                # appended to the profile name list
+    assert '"k_wv_render", "k_ff_render"}' in open(os.path.join(CSRC, "engine.h")).read()   # appended to the profile name list
 
 
 def test_has_fourier_render_looks_for_the_symbol():

@@ -16,7 +16,13 @@ Cases (all eager, profiling on, one sf_forward + one sf_forward_backward, render
     chunk_pixels is) and, for the two-pass path (k_wv_inject), at H = 30 with chunk_pixels 256: the smallest even H whose
     17 x 17 coefficient grid passes the smallest chunk of 256
   render handles: sf_render_create 64x3 and 256x4, sf_fourier_render_create 64, sf_wavelet_render_create 64x3 (H = 30)
-  Feathermap: an attached 64x3 handle, with one sf_adam_step after the two passes"""
+  Feathermap: an attached 64x3 handle, with one sf_adam_step after the two passes
+
+One more case runs with profiling off: sf_step with three learning rates and want_loss on a WaveletSiren 64x3 handle at
+H = 2, eagerly and with set_graph_replay(True), from the same parameters.  The sub-handles launch through the handle's own
+launch context, so a captured step puts their kernels on the capturing stream.  The three losses and the sha256 of the
+parameters of both runs equal, exactly, what the library of the commit before the host split recorded (golden key
+"wavelet_step_64x3_H2", through the same child and SIREN_FIT_LIB)."""
 import json
 import os
 import subprocess
@@ -31,12 +37,22 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "launch_plan.json")
 REL = 1e-12      # flops / bytes are host doubles: only the order of a sum may move them
 
 
-def test_launch_plan_matches_golden(tmp_path):
-    out = tmp_path / "launch_plan.json"
+STEP_KEY = "wavelet_step_64x3_H2"
+
+
+@pytest.fixture(scope="module")
+def child(tmp_path_factory):
+    """the one run of the child that both tests read"""
+    out = tmp_path_factory.mktemp("launch_plan") / "launch_plan.json"
     r = subprocess.run([sys.executable, CHILD, str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
     assert r.returncode == 0, r.stdout.decode()[-4000:]
-    got = {name: c["plan"] for name, c in json.load(open(out))["cases"].items()}
+    return json.load(open(out))
+
+
+def test_launch_plan_matches_golden(child):
+    got = {name: c["plan"] for name, c in child["cases"].items()}
     want = json.load(open(GOLDEN))
+    del want[STEP_KEY]
     assert sorted(got) == sorted(want)
     bad = []
     for name in sorted(want):
@@ -51,3 +67,12 @@ def test_launch_plan_matches_golden(tmp_path):
                 if abs(g[f] - w[f]) > REL * abs(w[f]):
                     bad.append((name, k, f, g[f], w[f]))
     assert not bad, bad[:20]
+
+
+def test_wavelet_step_replay_equals_eager_and_golden(child):
+    want = json.load(open(GOLDEN))[STEP_KEY]
+    got = child["wavelet_step"]
+    print("eager", got["eager"], "replay", got["replay"], "golden", want)
+    assert len(want["losses"]) == 3
+    assert got["replay"] == got["eager"]
+    assert got["eager"] == want
