@@ -217,14 +217,11 @@ __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
         const float z = o[0][t];
         const float sg = 1.0f / (1.0f + __expf(-z));
         if (valid && a.pred) a.pred[p * 3 + t] = sg;
+        const uint32_t q = render_quant<BITS>(sg);
         if constexpr (BITS == 16) {
-          int q = (int)(sg * 65535.0f);   // v_cvt_i32_f32: toward zero
-          q = q < 0 ? 0 : (q > 65535 ? 65535 : q);
-          if (t < 2) mine |= (uint32_t)q << (16 * t); else mine1 = (uint32_t)q;
+          if (t < 2) mine |= q << (16 * t); else mine1 = q;
         } else {
-          int q = (int)(sg * 255.0f);   // v_cvt_i32_f32: toward zero
-          q = q < 0 ? 0 : (q > 255 ? 255 : q);
-          mine |= (uint32_t)q << (8 * t);
+          mine |= q << (8 * t);
         }
       }
     }

@@ -86,12 +86,9 @@ int launch_bwd16(sf_engine* h, const BwdLayerArgs& a, int n_wg) {
   using T = BwdTile<WD, LAST>;
   constexpr bool H256 = WD == 256 && !LAST;
   constexpr int WC = H256 && P0 ? kBwd16P0WC : T::WC, NB = H256 ? (P0 ? kBwd16P0NB : kBwd16NB) : 8;   // (the constants at the kernel list)
-  // NB-slot block ring + (when the stationary weight rows do not fit in registers) their parked part
-  // + (P0) the layer-0 table
-  constexpr int JW = T::JW, IW = T::IW, WR = T::WR, NWV = WR * WC, XT = (IW / 32) / NWV, KSX = LAST ? 1 : JW / 16;
-  constexpr int WSP = (XT * KSX > 24) ? (P0 ? 3 : 4) : 0;
-  const size_t lds = (size_t)NB * (JW / 16 + IW / 16) * 1024 + (size_t)NWV * XT * WSP * 1024 + (P0 ? (size_t)IW * 16 : 0);
-  return launch(h, k_bwd<JW, IW, WR, WC, LAST, P0, OP, NB>, n_wg, NWV * 64, lds, a);
+  constexpr int JW = T::JW, IW = T::IW, WR = T::WR, NWV = WR * WC;
+  static_assert(!H256 || P0 || BwdLds<JW, IW, NWV, LAST, P0, NB>::bytes == 160 * 1024, "hidden 256: 5 x 32 KiB ring");
+  return launch(h, k_bwd<JW, IW, WR, WC, LAST, P0, OP, NB>, n_wg, NWV * 64, BwdLds<JW, IW, NWV, LAST, P0, NB>::bytes, a);
 }
 // fused backward of one layer: last = the out_features(<=3, padded to 32)-row layer; p0 = its input layer is
 // layer 0, whose phases are re-derived from the coordinates.
@@ -122,23 +119,30 @@ constexpr Ring8 bwd8_ring() {
   // 8 waves (two per SIMD); the ring slots hold the fp8 bytes (8 KiB per block): phase W converts in registers, phase X
   // reads a 16-bit image expanded once per block (2 x 16 KiB).
   // last layer: 3 MFMAs per block, bound by the latency of a step once its delta output is bytes - rings of 4 slots
-  // (72 KiB) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
+  // (72 KiB + the 1 KiB sin/cos table) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
   // HBM-bound at 5.4 TB/s and the shallower rings cost 0.3 ms: format 12 keeps one workgroup per CU)
   // (every layer below the last runs k_bwd8h: launch_bwd8)
   return P0 ? Ring8{8, 0, 0} : Ring8{4, 0, 4};
 }
+// the LDS layout of k_bwd8 for (width, last, p0, d8) with the rings above
+template <int WD, bool LAST, bool P0, bool D8>
+struct Bwd8Of {
+  using T = BwdTile<WD, LAST>;
+  static constexpr Ring8 R = bwd8_ring<WD, LAST, P0, D8>();
+  using Lds = Bwd8Lds<T::JW, T::IW, T::WR * T::WC, LAST, P0, R.NB, R.PARK, R.NBP, D8>;
+};
+static_assert(Bwd8Of<256, false, false, false>::Lds::bytes == 153 * 1024, "format 12, hidden layer");
+static_assert(Bwd8Of<256, false, true, false>::Lds::bytes == 148 * 1024, "format 12, layer 1 (P0)");
+static_assert(2 * Bwd8Of<256, true, false, true>::Lds::bytes == 146 * 1024, "format 8, last layer: 73 KiB, two workgroups per CU");
 template <int WD, bool LAST, bool P0, bool D8>
 int launch_bwd8_k(sf_engine* h, const Bwd8Args& a, int n_wg) {
   using T = BwdTile<WD, LAST>;
-  constexpr int NB = bwd8_ring<WD, LAST, P0, D8>().NB, PARK = bwd8_ring<WD, LAST, P0, D8>().PARK, NBP = bwd8_ring<WD, LAST, P0, D8>().NBP;
-  constexpr size_t lds = bwd8_lds_bytes<T::JW, T::IW, T::WR * T::WC, LAST, P0, NB, PARK, NBP, D8>();
-  static_assert(lds <= 160 * 1024, "k_bwd8 LDS budget");
-  return launch(h, k_bwd8<T::JW, T::IW, T::WR, T::WC, LAST, P0, OpF16, NB, PARK, NBP, D8>, n_wg, T::WR * T::WC * 64, lds, a);
+  constexpr Ring8 R = Bwd8Of<WD, LAST, P0, D8>::R;
+  return launch(h, k_bwd8<T::JW, T::IW, T::WR, T::WC, LAST, P0, OpF16, R.NB, R.PARK, R.NBP, D8>, n_wg, T::WR * T::WC * 64,
+                Bwd8Of<WD, LAST, P0, D8>::Lds::bytes, a);
 }
 int launch_bwd8h(sf_engine* h, const Bwd8Args& a, int n_wg) {
-  constexpr size_t lds = bwd8h_lds_bytes<kBwd8hPark>();
-  static_assert(lds <= 160 * 1024, "k_bwd8h LDS budget");
-  return launch(h, k_bwd8h<kBwd8hPark>, n_wg, 512, lds, a);
+  return launch(h, k_bwd8h<kBwd8hPark>, n_wg, 512, Bwd8hLds<kBwd8hPark>::bytes, a);
 }
 int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
   return with_width(h, [&](auto wd) {
@@ -158,17 +162,16 @@ int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
 // weight gradient of layer 0 (no data gradient needed): contraction of delta_0 with the coordinates
 template <int JW>
 int launch_dw0(sf_engine* h, const Dw0Args& a, int n_wg) {
-  const size_t lds = (size_t)8 * (JW / 16) * 1024 + 512;   // ring + coordinate table
-  return with_op(h, [&](auto op) { return launch(h, k_dw0<JW, decltype(op)>, n_wg, JW * 2, lds, a); });
+  return with_op(h, [&](auto op) { return launch(h, k_dw0<JW, decltype(op)>, n_wg, JW * 2, Dw0Lds<JW>::bytes, a); });
 }
 // ... from fp8 deltas: two MFMAs per wave and block behind a workgroup barrier: bound by the latency of a step.  At width
 // 256 a 4-slot ring (64.5 KiB) lets two workgroups share a CU.
 constexpr int dw0_8_ring(int JW) { return JW == 256 ? 4 : 8; }
+static_assert(2 * Dw0Lds8<256, dw0_8_ring(256)>::bytes == 129 * 1024, "64.5 KiB per workgroup");
 template <int JW>
 int launch_dw0_8(sf_engine* h, const Dw0Args& a, int n_wg) {
   constexpr int NB = dw0_8_ring(JW);
-  const size_t lds = (size_t)(NB * (JW / 32) + 2 * (JW / 16)) * 1024 + 512;   // byte ring + two fp16 images + coordinate table
-  return launch(h, k_dw0_8<JW, OpF16, NB>, n_wg, JW * 2, lds, a);
+  return launch(h, k_dw0_8<JW, OpF16, NB>, n_wg, JW * 2, Dw0Lds8<JW, NB>::bytes, a);
 }
 template <int JW>
 int launch_dw_first_t(sf_engine* h, const Dw0Args& a, int n_wg) {

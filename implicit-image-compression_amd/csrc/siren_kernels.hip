@@ -33,6 +33,14 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef __attribute__((ext_vector_type(2))) int i32x2;
+typedef f16x2 h2;
+// the same in LDS (kernels that address LDS explicitly: one base register + the immediate of a ds_* instruction)
+typedef __attribute__((address_space(3))) const u32x4 lds_cv4;
+typedef __attribute__((address_space(3))) u32x4 lds_v4;
+typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
+typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 #define DEV __device__ __forceinline__
 
@@ -74,8 +82,6 @@ DEV void store_stream(u32x4* p, u32x4 v) {
 DEV uint32_t pack_phase2(float f0, float f1) {  // two fractions in [0,1) -> two unorm16 (x*65535, RNE)
   return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pknorm_u16(f0, f1));
 }
-DEV float bf16_lo(uint32_t u) { return __builtin_bit_cast(float, u << 16); }
-DEV float bf16_hi(uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
 constexpr float kInv65535 = 1.0f / 65535.0f;
 
@@ -112,6 +118,12 @@ DEV uint32_t phase_byte4(const float* t, const float* after) {
 constexpr float kPhaseEps = 1.0f / 65536.0f;
 template <int BYTE>
 DEV float phase_rev8(uint32_t p) { return __builtin_fmaf((float)((p >> (8 * BYTE)) & 0xffu), 1.0f / 256.0f, kPhaseEps); }
+// entry u of the sin/cos table of the phase bytes (k_bwd8, k_bwd8h): the pair of the decoded phase as two 16-bit floats
+template <typename OP>
+DEV uint32_t phase_tab_entry(int u) {
+  const float r = __builtin_fmaf((float)u, 1.0f / 256.0f, kPhaseEps);
+  return OP::pack2(__builtin_amdgcn_sinf(r), __builtin_amdgcn_cosf(r));
+}
 
 // Delta byte: OCP fp8 e4m3 (3-bit significand, 2^-9 .. 448), SATURATING (the plain conversion returns NaN beyond
 // +-448: isa_probe).  Deltas carry one power-of-two scale per pixel chunk, derived by k_bwd8<LAST> from the chunk's
@@ -134,7 +146,6 @@ DEV uint32_t fp8x4_sat(float a, float b, float c, float d) {
 }
 // 8 fp8 (two dwords) -> 8 fp16 (one B-operand / piece element of 16 bytes)
 DEV u32x4 fp8x8_to_f16(uint32_t lo, uint32_t hi) {
-  typedef __attribute__((ext_vector_type(2))) _Float16 h2;
   const h2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true);
   const h2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true);
   return u32x4{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, c),
@@ -158,6 +169,11 @@ DEV void bar_all() {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+}
+// end of a hand-cut slot (k_fwd_pipe, k_bwd8h): nothing moves across, neither memory operations (compiler) nor instructions (scheduler)
+DEV void slot_end() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
 }
 // barrier that waits for this wave's LDS-DMA but leaves its N YOUNGEST vector-memory operations (the
 // epilogue stores issued AFTER the DMA) in flight: vmcnt counts loads, stores and LDS-DMA in issue order
@@ -257,6 +273,21 @@ struct FwdImg {
   static __host__ __device__ constexpr int bias_piece(int nt) { return nt < H0 ? H0 * KS : X_PIECES + H1 * KS; }
   static __host__ __device__ constexpr int bias_off(int nt) { return (nt < H0 ? nt : nt - H0) * 32; }
 };
+
+// accumulator of a 32-neuron tile initialised with its biases: lane half h takes bias[8 q4 + 4 h + 0..3] into registers 4 q4 + 0..3
+DEV f32x16 bias_acc(const float* bias, int h) {
+  f32x16 acc;
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) {
+    const f32x4 b = *reinterpret_cast<const f32x4*>(&bias[8 * q4 + 4 * h]);
+    acc[4 * q4 + 0] = b.x; acc[4 * q4 + 1] = b.y; acc[4 * q4 + 2] = b.z; acc[4 * q4 + 3] = b.w;
+  }
+  return acc;
+}
+// phase of a layer-0 neuron, in revolutions, at the pixel (x0, x1): t = its entry {w0, w1, b, 0} of the layer-0 table
+DEV float l0_phase(f32x4 t, float x0, float x1, float sc_first) {
+  return __builtin_fmaf(t.y, x1, __builtin_fmaf(t.x, x0, t.z)) * sc_first;
+}
 
 // last-layer accumulator -> prediction, residual and dL/dout piece of one pixel block; returns this lane's squared residual
 template <typename OP, bool TRAIN, bool S8>
@@ -362,9 +393,7 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
     float av[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const f32x4 t = sL0[16 * s + pi_perm(h, j)];
-      const float z = __builtin_fmaf(t.y, x1, __builtin_fmaf(t.x, x0, t.z));
-      av[j] = __builtin_amdgcn_sinf(z * a.sc_first);
+      av[j] = __builtin_amdgcn_sinf(l0_phase(sL0[16 * s + pi_perm(h, j)], x0, x1, a.sc_first));
     }
     B[s] = u32x4{OP::pack2(av[0], av[1]), OP::pack2(av[2], av[3]), OP::pack2(av[4], av[5]), OP::pack2(av[6], av[7])};
     // layer-0 phases are NOT spilled: k_bwd re-derives them from the coordinates (2 FMAs per value)
@@ -374,13 +403,7 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
   // (tile_epi).  The two are software-pipelined: the epilogue of tile k-1 (pure VALU + 2 stores) is issued
   // in the shadow of the MFMAs of tile k: per MFMA ~4 VALU (mul, fract, sin, half a pack + half a pknorm).
   auto tile_mma = [&](int nt) -> f32x16 {
-    f32x16 acc;
-    const float* bias = reinterpret_cast<const float*>(sW + IM::bias_piece(nt) * 64) + IM::bias_off(nt);
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-      const f32x4 b = *reinterpret_cast<const f32x4*>(&bias[8 * q4 + 4 * h]);
-      acc[4 * q4 + 0] = b.x; acc[4 * q4 + 1] = b.y; acc[4 * q4 + 2] = b.z; acc[4 * q4 + 3] = b.w;
-    }
+    f32x16 acc = bias_acc(reinterpret_cast<const float*>(sW + IM::bias_piece(nt) * 64) + IM::bias_off(nt), h);
     const u32x4* wt = sW + IM::tile_piece(nt) * 64 + lane;
 #pragma unroll
     for (int s = 0; s < KS; ++s) acc = OP::mfma(wt[s * 64], B[s], acc);
@@ -459,15 +482,7 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
 
   // ---- last layer (out_features <= 3, padded to one 32-row tile) + residual ---------------------
   if (a.depth > 2) bar_dma<TRAIN ? SPT * (IM::H1 + 1) : 0>(); else bar_dma<0>();
-  f32x16 acc;
-  {
-    const float* bias = reinterpret_cast<const float*>(sW + KS * 64);
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-      const f32x4 b = *reinterpret_cast<const f32x4*>(&bias[8 * q4 + 4 * h]);
-      acc[4 * q4 + 0] = b.x; acc[4 * q4 + 1] = b.y; acc[4 * q4 + 2] = b.z; acc[4 * q4 + 3] = b.w;
-    }
-  }
+  f32x16 acc = bias_acc(reinterpret_cast<const float*>(sW + KS * 64), h);
 #pragma unroll
   for (int s = 0; s < KS; ++s) acc = OP::mfma(sW[s * 64 + lane], B[s], acc);
 
@@ -516,7 +531,6 @@ DEV void split_f16(float x, float lo_scale, _Float16& hi, _Float16& lo) {
   lo = (_Float16)((x - (float)hi) * lo_scale);
 }
 DEV uint32_t pack_h2(_Float16 a, _Float16 b) {
-  typedef __attribute__((ext_vector_type(2))) _Float16 h2;
   return __builtin_bit_cast(uint32_t, h2{a, b});
 }
 
@@ -581,15 +595,9 @@ __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
   float sse_acc = 0.f;
   bar_dma<0>();                                   // layer-0 image staged (and the first group's fetch has landed)
 
-  auto slot_end = [&]() {   // nothing moves across: neither memory operations (compiler) nor instructions (scheduler)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
   // Explicit LDS addressing: five per-lane base registers, everything else is the 16-bit immediate of the read.  (Left
   // to itself hipcc gave every piece beyond the first 64 KiB its own loop-invariant address register - 56 of them - and
   // spilled what the pipeline needs.)  The empty asm makes a base opaque, so constants are not folded back into it.
-  typedef __attribute__((address_space(3))) const u32x4 lds_cv4;
-  typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
   __builtin_assume(wave >= 0 && wave < kWavesFwd);
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
   const uint32_t lane16 = (uint32_t)lane * 16u;
@@ -838,9 +846,25 @@ DEV int tr_addr(int tile, int kk, int u, int lane) {
 DEV int tr_lane_base(int lane) { return tr_addr(0, 0, 0, lane); }
 
 DEV u32x4 ds_read_tr_pair(const char* base, int off0, int off1) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
   const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off0));
   const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off1));
+  const u32x2 a0 = __builtin_bit_cast(u32x2, r0), a1 = __builtin_bit_cast(u32x2, r1);
+  return u32x4{a0.x, a0.y, a1.x, a1.y};
+}
+// Lane part of the address of a transposed BYTE read (fp8 delta pieces).  ds_read_b64_tr_b8 works on groups of 16 lanes; lane
+// t of a group supplies the address of an 8-byte row, result lane i < 8 receives byte i of the rows of lanes 0, 2, .., 14 and
+// lane 8 + i byte i of the rows of lanes 1, 3, .., 15 (scripts/probes/trb8.hip).  With lane t pointing at bytes 8q .. 8q+7 of
+// piece lane (h' = t & 1, pixel 8 hq + (t >> 1)) - q = group & 1, hq = group >> 1 - the wave receives an A fragment of the
+// 16-pixel k-step whose row r = lane & 31 is neuron nu8(r) of the tile and whose elements are the pixels 8 hq + 0..7 in order.
+// (pixel slot ^ 8 h': byte pieces sit in LDS with slot i holding the element of lane i ^ 8 (i >> 5), see lsw8 in k_bwd8)
+DEV uint32_t tr8_lane_base(int lane) {
+  return 16u * (32u * (uint32_t)(lane & 1) + ((8u * (uint32_t)(lane >> 5) + (uint32_t)((lane & 15) >> 1)) ^ (8u * (uint32_t)(lane & 1)))) +
+         8u * (uint32_t)((lane >> 4) & 1);
+}
+// the same from LDS byte addresses: base registers of the two half-reads + an immediate (k_bwd8, k_bwd8h)
+DEV u32x4 tr_pair(uint32_t b1, uint32_t b2, int imm) {
+  const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(b1 + imm));
+  const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(b2 + imm));
   const u32x2 a0 = __builtin_bit_cast(u32x2, r0), a1 = __builtin_bit_cast(u32x2, r1);
   return u32x4{a0.x, a0.y, a1.x, a1.y};
 }
@@ -849,6 +873,29 @@ DEV u32x4 ds_read_tr_frag(const char* blk, int trb, int tile, int kk) {
   const int a0 = trb + tile * 2048 + kk * 256;
   return ds_read_tr_pair(blk, a0, a0 ^ 64);
 }
+
+// coordinates of local pixel p (clamped to the last one) as the gradient kernels re-derive them: (row, col) by the magic
+// division, linspace(0, 1, n)[i] ~ i / (n - 1), then (x - 0.5) * 2 (siren.py:128)
+template <typename Args>
+DEV void pixel_coords(const Args& a, long p, float& x0, float& x1) {
+  if (p >= a.npix) p = a.npix - 1;
+  const unsigned row = (unsigned)(((unsigned long long)p * a.w_magic) >> 40);
+  const unsigned col = (unsigned)(p - (long)row * a.W);
+  x0 = ((float)(row + (unsigned)a.row_begin) * a.inv_hm1 - 0.5f) * 2.0f;
+  x1 = ((float)col * a.inv_wm1 - 0.5f) * 2.0f;
+}
+// one sample of a prediction value p (the render epilogues): min(max((int)(p * (2^BITS - 1)), 0), 2^BITS - 1), the product
+// in fp32, truncated toward zero (v_cvt_i32_f32)
+template <int BITS>
+DEV uint32_t render_quant(float p) {
+  constexpr int kMax = BITS == 16 ? 65535 : 255;
+  int q = (int)(p * (float)kMax);
+  q = q < 0 ? 0 : (q > kMax ? kMax : q);
+  return (uint32_t)q;
+}
+// The dynamic LDS of a workgroup is 160 KiB at most; every kernel family states its layout ONCE, in a geometry struct
+// (byte offsets for the kernel, `bytes` for its launcher) that checks itself against this.
+constexpr size_t kLdsMax = 160 * 1024;
 
 // ---------------------------------------------------------------------------------------------
 // k_bwd: one layer of the backward pass, data-gradient and weight-gradient fused so that every
@@ -880,9 +927,27 @@ struct BwdLayerArgs {
   float sc_first;               // first_omega_0 / (2 pi)
 };
 
+// P0 forms (k_bwd, k_bwd8): the layer-0 table {w0, w1, b, 0} per neuron, copied into LDS by the whole workgroup
+DEV void l0_table_copy(f32x4* dst, const f32x4* l0tab, int n, int tid, int nthreads) {
+  for (int i = tid; i < n; i += nthreads) dst[i] = l0tab[i];
+}
+// LDS of k_bwd: [NB ring slots of BLK bytes: delta pieces, phase pieces][the parked W^T k-steps: NW waves x XT row tiles x
+// WSP pieces][P0: the layer-0 table]
+template <int JW, int IW, int NW, bool LAST, bool P0, int NB>
+struct BwdLds {
+  static constexpr int KSJ = JW / 16, KSI = IW / 16, KSX = LAST ? 1 : KSJ, XT = (IW / 32) / NW;
+  // W^T k-steps [0, KSR) of a wave's rows stay in registers, WSP are parked (the widest configuration needs the 32 registers:
+  // 256 accumulator + 128 weight registers leave too few; P0: the layer-0 table takes 4 KiB of LDS)
+  static constexpr int KSR = (XT * KSX > 24) ? KSX - (P0 ? 3 : 4) : KSX, WSP = KSX - KSR;
+  static constexpr int BLK = (KSJ + KSI) * 1024;       // bytes per ring slot: delta pieces then phase pieces
+  static constexpr size_t oWsp = (size_t)NB * BLK, oL0 = oWsp + (size_t)NW * XT * WSP * 1024, bytes = oL0 + (P0 ? (size_t)IW * 16 : 0);
+  static_assert(bytes <= kLdsMax, "k_bwd LDS budget");
+};
+
 template <int JW, int IW, int WAVES_R, int WAVES_C, bool LAST, bool P0, typename OP, int NB>
 __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
   constexpr int NW = WAVES_R * WAVES_C;
+  using L = BwdLds<JW, IW, NW, LAST, P0, NB>;
   constexpr int JT = JW / 32, IT = IW / 32;
   constexpr int WJ = JT / WAVES_R, WI = IT / WAVES_C;
   constexpr int KSJ = JW / 16, KSI = IW / 16;
@@ -893,7 +958,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
   // loaded HBM latency is several microseconds, so the bytes in flight per CU (PD * BLK) set the streaming
   // rate long before the instruction schedule does (measured: 2 blocks in flight = 10 GB/s per CU).
   constexpr int PD = NB - 2;
-  constexpr int BLK = (KSJ + KSI) * 1024;     // bytes per ring slot: delta pieces then phase pieces
   constexpr int G_MIN = KSJ / NW + (P0 ? 0 : KSI / NW);  // LDS-DMA instructions every wave issues per block (lower bound)
   constexpr int S_ST = 2 * XT;                // delta stores per wave per block
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -905,11 +969,8 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
   const int lsw = sw_lane(lane, 0);      // slot of this lane's register image in an even piece; odd: lsw ^ 8
   const uint32_t lswb = (uint32_t)lsw * 16u;   // the same as a byte offset; odd: lswb ^ 128
 
-  // stationary W^T rows of this wave: k-steps [0, KSR) in registers, [KSR, KSX) parked in LDS behind the ring
-  // (the widest configuration needs the 32 registers: 256 accumulator + 128 weight registers leave too few)
-  constexpr int KSR = (XT * KSX > 24) ? KSX - (P0 ? 3 : 4) : KSX;   // (P0: the layer-0 table takes 4 KiB of LDS)
-  constexpr int WSP = KSX - KSR;                // spilled k-steps per row tile
-  char* sWsp = smem + NB * BLK + (size_t)wave * XT * WSP * 1024;
+  constexpr int BLK = L::BLK, KSR = L::KSR, WSP = L::WSP;   // W^T k-steps [0, KSR) in registers, WSP parked behind the ring
+  char* sWsp = smem + L::oWsp + (size_t)wave * XT * WSP * 1024;
   u32x4 wreg[XT][KSR];
 #pragma unroll
   for (int x = 0; x < XT; ++x) {
@@ -941,39 +1002,11 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
     if (!P0)
       for (int pc = wave; pc < KSI; pc += NW) glds16s(a.P + (pb * KSI + pc) * 64, lswb ^ ((pc & 1) << 7), base + (KSJ + pc) * 1024);
   };
-  // the same pieces one at a time, to be issued BETWEEN the MFMAs of a step (an LDS-DMA instruction costs its wave
-  // ~150-200 issue cycles inside a burst of them, ~60 with MFMAs in flight): piece i of this wave for block k
-  constexpr int GD = KSJ / NW, GP = GD + (P0 ? 0 : KSI / NW);
-  // (k_wdw issues its pieces that way; here both placements tried - X chunks and W chunks - pushed the 256-register
-  //  8-wave build into scratch spills INSIDE the steady loop, whose reloads then drain the DMA queue, so the burst
-  //  at the top of the step stays)
-  constexpr bool SPREAD = false && (KSJ % NW == 0) && (P0 || KSI % NW == 0) && GP <= 2 * WJ;
-  auto stage_piece = [&](int k, int i) {
-    // past the last block the SAME ring slot is refilled with the last block again: the slot is free (its block
-    // was consumed NB - PD steps ago), the bytes are never read, and the steady loop stays branch-free
-    char* base = smem + (k % NB) * BLK;
-    const long pb = pb_begin + (long)(k < nblk ? k : nblk - 1) * pb_step;
-    if (i < GD) {
-      const int pc = wave + NW * i;
-      glds16s(a.D + (pb * KSJ + pc) * 64, lswb ^ ((pc & 1) << 7), base + pc * 1024);
-    } else {
-      const int pc = wave + NW * (i - GD);
-      glds16s(a.P + (pb * KSI + pc) * 64, lswb ^ ((pc & 1) << 7), base + (KSJ + pc) * 1024);
-    }
-  };
   // P0: layer-0 table in LDS (behind the parked weights) and this lane's pixel coordinates per block
-  const f32x4* sL0 = reinterpret_cast<const f32x4*>(smem + NB * BLK + (size_t)NW * XT * WSP * 1024);
-  if (P0) {
-    f32x4* dst = reinterpret_cast<f32x4*>(smem + NB * BLK + (size_t)NW * XT * WSP * 1024);
-    for (int i = tid; i < IW; i += NW * 64) dst[i] = a.l0tab[i];
-  }
+  const f32x4* sL0 = reinterpret_cast<const f32x4*>(smem + L::oL0);
+  if (P0) l0_table_copy(reinterpret_cast<f32x4*>(smem + L::oL0), a.l0tab, IW, tid, NW * 64);
   auto pixel_xy = [&](int k, float& x0, float& x1) {
-    long p = a.pix0 + (pb_begin + (long)k * pb_step) * 32 + (lane & 31);
-    if (p >= a.npix) p = a.npix - 1;
-    const unsigned row = (unsigned)(((unsigned long long)p * a.w_magic) >> 40);
-    const unsigned col = (unsigned)(p - (long)row * a.W);
-    x0 = ((float)(row + (unsigned)a.row_begin) * a.inv_hm1 - 0.5f) * 2.0f;
-    x1 = ((float)col * a.inv_wm1 - 0.5f) * 2.0f;
+    pixel_coords(a, a.pix0 + (pb_begin + (long)k * pb_step) * 32 + (lane & 31), x0, x1);
   };
 
   for (int k = 0; k < PD && k < nblk; ++k) stage(k);
@@ -1020,8 +1053,8 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
       float r0, r1;
       if (P0) {   // phase of layer 0 from the coordinates: neurons 16*ks + PI(h, 2*j2), +1
         const f32x4 t0 = sL0[16 * ks + pi_perm(lane >> 5, 2 * j2)], t1 = sL0[16 * ks + pi_perm(lane >> 5, 2 * j2 + 1)];
-        r0 = __builtin_fmaf(t0.y, ep_x1, __builtin_fmaf(t0.x, ep_x0, t0.z)) * a.sc_first;
-        r1 = __builtin_fmaf(t1.y, ep_x1, __builtin_fmaf(t1.x, ep_x0, t1.z)) * a.sc_first;
+        r0 = l0_phase(t0, ep_x0, ep_x1, a.sc_first);
+        r1 = l0_phase(t1, ep_x0, ep_x1, a.sc_first);
       } else {
         r0 = phase_rev_lo(ep_p[j2]); r1 = phase_rev_hi(ep_p[j2]);
       }
@@ -1053,7 +1086,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
       dbs[x] += tsum;
     }
   };
-  auto step = [&](int kx, bool do_x, bool do_w, bool do_s) {   // do_s: issue the LDS-DMA of block kx+PD inside the X chunks
+  auto step = [&](int kx, bool do_x, bool do_w) {
     u32x4 xb[2][XS];            // X B-operand pieces, double-buffered
     u32x4 fb[2][WI], fa[2];     // W operands: activation fragments per k-step (2 sets), delta^T fragment (2 sets)
     f32x16 gp = {}, gc = {};
@@ -1091,7 +1124,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
           if (x + 1 < WJ) fa[(i + 1) & 1] = wa_load(kx - 1, kk, x + 1);
           else if (kk == 0) { wb_load(kx - 1, 1, fb[1]); fa[(i + 1) & 1] = wa_load(kx - 1, 1, 0); }
           w_mma_chunk(x, fa[i & 1], fb[kk]);
-          if (SPREAD && do_s && i < GP) stage_piece(kx + PD, i);   // W chunks: fewest live registers of the step
         }
         if (do_x && kk == 0) {
 #pragma unroll
@@ -1106,17 +1138,17 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
     bar_all();                          // block 0 landed
     if (PD < nblk) stage(PD);
     asm volatile("" ::: "memory");
-    step(0, true, false, false);
+    step(0, true, false);
     for (int k = 1; k < nblk; ++k) {
       // block k landed (requested PD steps ago; younger in the in-order vmcnt queue: the delta stores of the PD
       // steps since, and the DMA of blocks k+1 .. k+PD-1) and every wave finished step k-1
       if (k >= PD && k + PD - 1 < nblk) bar_dma<PD * S_ST + (PD - 1) * G_MIN>(); else bar_all();
-      if (!SPREAD && k + PD < nblk) stage(k + PD);
+      if (k + PD < nblk) stage(k + PD);
       asm volatile("" ::: "memory");
-      step(k, true, true, true);
+      step(k, true, true);
     }
     bar_lds();
-    step(nblk, false, true, false);
+    step(nblk, false, true);
   }
   float* slab = a.slab + (size_t)blockIdx.x * (JW * IW + JW);
   const int cl = lane & 31, hh = lane >> 5;
@@ -1155,9 +1187,24 @@ struct Dw0Args {
                             // gradient term; the forward uses the exact vectors).  No loads in the DMA loop.
 };
 
+// slab write-out of one accumulator tile (32 rows x 32 columns) at (row0, col0) of a slab with row length ld (k_dw0, k_dw0_8)
+DEV void slab_store_tile(float* slab, int ld, int row0, int col0, f32x16 acc, int lane) {
+  const int cl = lane & 31, hh = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) slab[(size_t)(row0 + rho(t, hh)) * ld + col0 + cl] = acc[t];
+}
+// LDS of k_dw0: [ring of NB delta blocks][coordinate table [2][4][32] of 16-bit values]
+template <int JW>
+struct Dw0Lds {
+  static constexpr int NB = 8, BLK = (JW / 16) * 1024;
+  static constexpr size_t oXY = (size_t)NB * BLK, bytes = oXY + 512;
+  static_assert(bytes <= kLdsMax, "k_dw0 LDS budget");
+};
+
 template <int JW, typename OP>
 __global__ __launch_bounds__(JW * 2) void k_dw0(Dw0Args a) {
-  constexpr int NW = JW / 32, KSJ = JW / 16, NB = 8, PD = NB - 2, BLK = KSJ * 1024;   // 96 KiB in flight at JW = 256
+  using L = Dw0Lds<JW>;
+  constexpr int NW = JW / 32, KSJ = JW / 16, NB = L::NB, PD = NB - 2, BLK = L::BLK;   // 96 KiB in flight at JW = 256
   constexpr int G_MIN = KSJ / NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1176,15 +1223,11 @@ __global__ __launch_bounds__(JW * 2) void k_dw0(Dw0Args a) {
   // B operand = coordinates of the block's 32 pixels as 16-bit columns {x0_hi, x0_lo, x1_hi, x1_lo}.  Wave 0
   // builds a [4][32] table per block (one pixel per lane, one integer division), double-buffered by block
   // parity behind the ring; every wave then reads its fragment with one ds_read_b128 per k-step.
-  uint16_t* sXY = reinterpret_cast<uint16_t*>(smem + NB * BLK);          // [2][4][32]
+  uint16_t* sXY = reinterpret_cast<uint16_t*>(smem + L::oXY);          // [2][4][32]
   auto build_xy = [&](int k) {
     if (wave == 0 && lane < 32) {
-      long p = a.pix0 + (pb_begin + (long)k * pb_step) * 32 + lane;
-      if (p >= a.npix) p = a.npix - 1;
-      const unsigned row = (unsigned)(((unsigned long long)p * a.w_magic) >> 40);
-      const unsigned col = (unsigned)(p - (long)row * a.W);
-      const float x0 = ((float)(row + (unsigned)a.row_begin) * a.inv_hm1 - 0.5f) * 2.0f;
-      const float x1 = ((float)col * a.inv_wm1 - 0.5f) * 2.0f;
+      float x0, x1;
+      pixel_coords(a, a.pix0 + (pb_begin + (long)k * pb_step) * 32 + lane, x0, x1);
       const uint32_t h0 = OP::pack2(x0, 0.f), h1 = OP::pack2(x1, 0.f);
       uint16_t* t = sXY + (k & 1) * 128 + lane;
       t[0] = (uint16_t)h0;
@@ -1219,8 +1262,7 @@ __global__ __launch_bounds__(JW * 2) void k_dw0(Dw0Args a) {
   }
   float* slab = a.slab + (size_t)blockIdx.x * (JW * 32 + JW);
   const int cl = lane & 31, hh = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < 16; ++t) slab[(size_t)(32 * wave + rho(t, hh)) * 32 + cl] = acc[t];
+  slab_store_tile(slab, 32, 32 * wave, 0, acc, lane);
   const float tsum = dbs + __shfl_xor(dbs, 32);
   if (hh == 0) slab[JW * 32 + 32 * wave + cl] = tsum;
 }

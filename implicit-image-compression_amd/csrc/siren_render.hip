@@ -42,14 +42,11 @@ DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, 
     }
     const float p = o * 0.5f + 0.5f;  // siren.py:131
     if (a.pred && h == 0 && valid) a.pred[pix * nout + c] = p;
+    const uint32_t q = render_quant<BITS>(p);
     if constexpr (BITS == 16) {
-      int q = (int)(p * 65535.0f);    // v_cvt_i32_f32: toward zero
-      q = q < 0 ? 0 : (q > 65535 ? 65535 : q);
-      if (c < 2) mine |= (uint32_t)q << (16 * c); else mine1 = (uint32_t)q;
+      if (c < 2) mine |= q << (16 * c); else mine1 = q;
     } else {
-      int q = (int)(p * 255.0f);        // v_cvt_i32_f32: toward zero
-      q = q < 0 ? 0 : (q > 255 ? 255 : q);
-      mine |= (uint32_t)q << (8 * c);
+      mine |= q << (8 * c);
     }
   }
   if constexpr (BITS == 16) {

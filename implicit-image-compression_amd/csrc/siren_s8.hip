@@ -14,20 +14,14 @@
 // code already reads (lane-linear for the data-gradient B operand, ds_read_b64_tr_b16 for both weight-gradient
 // operands), one block ahead of its use, by the wave that also issued its DMA (8 conversions per wave and block).
 //
-// LDS of one workgroup (256 x 256 layer, 160 KiB):
-//   ring D   NB x  8 KiB   fp8 delta pieces   block k+NB is requested in step k, converted in step k+NB-1
-//   ring P   NB x  8 KiB   phase-byte pieces  block k+NB-1 is requested in step k, decoded in step k+NB-1
-//   D16      3  x 16 KiB   fp16 deltas        written in step k-1 (C), B operand in step k (X), tr-read in step k+1 (W)
-//   S16      2  x 16 KiB   fp16 sin(phase)    written by the X epilogue in step k, tr-read in step k+1 (W)
+// LDS of one workgroup: Bwd8Lds below (the layout, once, for the kernel and its launcher; the sizes of the 256-wide forms
+// are asserted where their rings are chosen: bwd8_ring, siren_host.hip).
 // (included by siren_fit.hip after siren_kernels.hip)
 
 namespace sf {
 
 constexpr int kBwd8PF = 3;           // B pieces read ahead in the 4-wave form (register ring of PF + 1)
 constexpr int kBwd8PF8 = 1;          // the same in the 8-wave form
-constexpr bool kBwd8Tab = true;      // sine / cosine of a phase byte from a table in LDS (see TAB in k_bwd8)
-constexpr bool kBwd8DbSplit = true;  // bias-gradient row sums split over the column waves (see DBSPLIT in k_bwd8)
-constexpr bool kBwd8FA2In8 = true;   // 8-wave form with fp8 deltas: delta^T fragments double-buffered (see FA2 in k_bwd8)
 
 struct Bwd8Args {
   const u32x4* D;       // LAST: dL/dout, 16-bit float, ONE piece (k-step 0) per pixel block; else fp8 deltas of layer l,
@@ -66,16 +60,35 @@ DEV u32x4 frag_of(u32x2 r) { return fp8x8_to_f16(r.x, r.y); }
 // row r of an A fragment read with ds_read_b64_tr_b8 through tr8 lane bases = this neuron of the 32-neuron tile
 SF_HOSTDEV int nu8(int r) { return 16 * (r >> 4) + pi_perm((r >> 3) & 1, r & 7); }
 
+// LDS of k_bwd8 (IN8 = D8 && !LAST: the deltas the layer reads are fp8 bytes), in this order:
+//   ring D   NB  x DPC KiB   delta pieces of a block: fp8 bytes (IN8), dL/dout + its zero k-step (LAST) or 16-bit k-steps
+//   ring P   NBP x PPC KiB   phase-byte pieces (none in the P0 form)
+//   X16      2   x KSJ KiB   IN8 only: 16-bit images of a block's deltas (B operand of phase X)
+//   S16      2   x KSI KiB   fp16 sin(phase): written by the X epilogue of step k, tr-read by phase W of step k+1
+//   WP, T    the parked W^T k-steps (NW x XT x PARK KiB); the sin/cos table (1 KiB) or, P0, the layer-0 table (IW x 16 bytes)
+template <int JW, int IW, int NW, bool LAST, bool P0, int NB, int PARK = 0, int NBP_ = 0, bool D8 = true>
+struct Bwd8Lds {
+  static constexpr int JT = JW / 32, IT = IW / 32, KSJ = JW / 16, KSI = IW / 16, XT = IT / NW;
+  static constexpr bool IN8 = D8 && !LAST;
+  static constexpr int NBP = NBP_ > 0 ? NBP_ : NB;                      // slots of the phase ring (NB: slots of the delta ring)
+  static constexpr int DPC = IN8 ? JT : (LAST ? 2 : KSJ);               // 1 KiB pieces per block in ring D
+  static constexpr int PPC = P0 ? 0 : IT;                               // 1 KiB pieces per block in ring P
+  static constexpr uint32_t oRP = NB * DPC * 1024, oX16 = oRP + NBP * PPC * 1024, oS16 = oX16 + (IN8 ? 2 : 0) * KSJ * 1024;
+  static constexpr uint32_t oWsp = oS16 + 2 * KSI * 1024, oTab = oWsp + NW * XT * PARK * 1024;
+  static constexpr size_t bytes = (size_t)oTab + (P0 ? (size_t)IW * 16 : 1024);
+  static_assert(bytes <= kLdsMax, "k_bwd8 LDS budget");
+};
+
 template <int JW, int IW, int WAVES_R, int WAVES_C, bool LAST, bool P0, typename OP, int NB, int PARK = 0, int NBP_ = 0, bool D8 = true>
 __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   constexpr int NW = WAVES_R * WAVES_C;
+  using L = Bwd8Lds<JW, IW, NW, LAST, P0, NB, PARK, NBP_, D8>;
   constexpr int JT = JW / 32, IT = IW / 32;
   constexpr int WJ = JT / WAVES_R, WI = IT / WAVES_C;
   constexpr int KSJ = JW / 16, KSI = IW / 16;
   constexpr int KSX = LAST ? 1 : KSJ;
   constexpr int XT = IT / NW;
   static_assert(IT % NW == 0, "phase-X tiling needs NW <= IT");
-  constexpr int NBP = NBP_ > 0 ? NBP_ : NB;     // slots of the phase ring (NB: slots of the delta ring)
 
   // D8 = false (scratch_format 12): deltas stay 16-bit floats (round-1 F-layout: one piece per k-step) - the ring slot
   // IS the image both products read (X lane-linear at step k, W transposed at step k+1), nothing is converted, and only
@@ -87,19 +100,17 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   // expanded ONCE, one step ahead, into a 16-bit image (X16, two buffers) that all waves read lane-linearly - converting
   // in registers there cost 8 x 64 conversions per block instead of 64 and made the kernel VALU-bound.  The LAST layer
   // reads the 16-bit dL/dout piece k_fwd wrote, exactly as with D8 = false; only what it WRITES is fp8.
-  constexpr bool IN8 = D8 && !LAST;
-  constexpr int DPC = IN8 ? JT : (LAST ? 2 : KSJ);               // 1 KiB pieces per block in ring D
+  constexpr bool IN8 = L::IN8;
+  constexpr int NBP = L::NBP, DPC = L::DPC, PPC = L::PPC;                // ring P slots, 1 KiB pieces per block in ring D / ring P
   constexpr int DDMA = IN8 ? JT : (LAST ? 1 : KSJ);              // of which the DMA fills (LAST: the second is the zero k-step)
   constexpr int TSTR = IN8 ? 1024 : 2048;                        // bytes of a 32-neuron tile inside a ring slot
-  constexpr int PPC = P0 ? 0 : IT;            // 1 KiB pieces per block in ring P
   constexpr int GD = DDMA / NW, GP = PPC / NW; // LDS-DMA instructions EVERY wave issues per block (lower bounds)
   constexpr int S_ST = 2 * XT;                // delta stores per wave per block (one 8-byte half element per k-step of a row tile)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const rD = smem;
-  char* const rP = rD + NB * DPC * 1024;
-  char* const x16 = rP + NBP * PPC * 1024;                       // IN8: two 16-bit images of a block's deltas (B operand of phase X)
-  char* const s16 = x16 + (IN8 ? 2 : 0) * KSJ * 1024;
-  char* const wsp0 = s16 + 2 * KSI * 1024;
+  char* const rP = smem + L::oRP;
+  char* const x16 = smem + L::oX16;
+  char* const s16 = smem + L::oS16;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -114,9 +125,8 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
 
   // stationary W^T rows of this wave (as k_bwd): k-steps [0, KSR) in registers, the rest parked in LDS
   // (one wave per SIMD has 512 registers: nothing is parked then)
-  constexpr int KSR = KSX - PARK;               // PARK k-steps of every row tile live in LDS behind the buffers
-  constexpr int WSP = PARK;
-  char* sWsp = wsp0 + (size_t)wave * XT * WSP * 1024;
+  constexpr int KSR = KSX - PARK, WSP = PARK;   // PARK k-steps of every row tile live in LDS behind the buffers
+  char* sWsp = smem + L::oWsp + (size_t)wave * XT * WSP * 1024;
   u32x4 wreg[XT][KSR];
 #pragma unroll
   for (int x = 0; x < XT; ++x) {
@@ -130,26 +140,19 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   // the pair as two 16-bit floats) instead of v_cvt_f32_ubyte + v_fma + v_sin + v_cos per value - the X epilogue is what
   // bounds phase W (VALU issue of two waves per SIMD).  The sine is the value the table-free form wrote to S16 bit for bit;
   // the cosine is rounded to 16 bits before it meets the accumulator (whose product is rounded to 8 or 16 bits anyway).
-  constexpr bool TAB = kBwd8Tab && !P0 && std::is_same<OP, OpF16>::value;
-  uint32_t* const sTab = reinterpret_cast<uint32_t*>(wsp0 + (size_t)NW * XT * WSP * 1024);
+  constexpr bool TAB = !P0 && std::is_same<OP, OpF16>::value;
+  uint32_t* const sTab = reinterpret_cast<uint32_t*>(smem + L::oTab);
   if (TAB) {
-    for (int i = tid; i < 256; i += NW * 64) {
-      const float r = __builtin_fmaf((float)i, 1.0f / 256.0f, kPhaseEps);
-      sTab[i] = OP::pack2(__builtin_amdgcn_sinf(r), __builtin_amdgcn_cosf(r));
-    }
+    for (int i = tid; i < 256; i += NW * 64) sTab[i] = phase_tab_entry<OP>(i);
   }
-  const f32x4* sL0 = reinterpret_cast<const f32x4*>(wsp0 + (size_t)NW * XT * WSP * 1024);
-  if (P0) {
-    f32x4* dst = reinterpret_cast<f32x4*>(wsp0 + (size_t)NW * XT * WSP * 1024);
-    for (int i = tid; i < IW; i += NW * 64) dst[i] = a.l0tab[i];
-  }
+  const f32x4* sL0 = reinterpret_cast<const f32x4*>(smem + L::oTab);
+  if (P0) l0_table_copy(reinterpret_cast<f32x4*>(smem + L::oTab), a.l0tab, IW, tid, NW * 64);
   float dfac = 1.0f;   // LAST: chunk pre-scale / res_scale (power of two)
   if (LAST) {   // the zero k-step of dL/dout (padded neurons 16..31) lives in LDS only: second piece of every slot
     for (int b = wave; b < NB; b += NW) reinterpret_cast<u32x4*>(rD + (b * DPC + 1) * 1024)[lane] = u32x4{0u, 0u, 0u, 0u};
   }
   if (LAST && D8) {
     // chunk SSE: thread t sums partials t, t + NW*64, ... in double; threads are combined in index order
-    if (D8) {
     double* red = reinterpret_cast<double*>(s16);     // NW*64 doubles <= 4 KiB, free until the first X epilogue
     double ps = 0.0;
     for (int i = tid; i < a.n_part; i += NW * 64) ps += (double)a.sse_part[i];
@@ -172,7 +175,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
       a.scale_out[1] = (float)(1.0 / (G * a.n_values));
     }
     __syncthreads();
-    }
   }
 
   f32x16 acc[WJ][WI];
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   for (int x = 0; x < WJ; ++x)
 #pragma unroll
     for (int y = 0; y < WI; ++y) acc[x][y] = f32x16{};
-  constexpr bool DBSPLIT = IN8 && kBwd8DbSplit;   // bias-gradient row sums split over the column waves (IN8 form only: registers)
+  constexpr bool DBSPLIT = IN8;   // bias-gradient row sums split over the column waves (IN8 form only: registers)
   float dbs[WJ];
 #pragma unroll
   for (int x = 0; x < WJ; ++x) dbs[x] = 0.f;
@@ -213,18 +215,13 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     }
   };
   auto pixel_xy = [&](int k, float& x0, float& x1) {
-    long p = a.pix0 + (pb_begin + (long)k * pb_step) * 32 + (lane & 31);
-    if (p >= a.npix) p = a.npix - 1;
-    const unsigned row = (unsigned)(((unsigned long long)p * a.w_magic) >> 40);
-    const unsigned col = (unsigned)(p - (long)row * a.W);
-    x0 = ((float)(row + (unsigned)a.row_begin) * a.inv_hm1 - 0.5f) * 2.0f;
-    x1 = ((float)col * a.inv_wm1 - 0.5f) * 2.0f;
+    pixel_coords(a, a.pix0 + (pb_begin + (long)k * pb_step) * 32 + (lane & 31), x0, x1);
   };
 
   constexpr int PF = NW <= 4 ? (KSX >= 4 ? kBwd8PF : 1) : kBwd8PF8;
   constexpr int NXB = PF + 1;
   constexpr int ESUB = 8;                       // epilogue slices per row tile: (q, quarter) groups of 2 values
-  constexpr bool FA2 = NW <= 4 || (IN8 && kBwd8FA2In8);  // delta^T fragments double-buffered
+  constexpr bool FA2 = NW <= 4 || IN8;  // delta^T fragments double-buffered
   constexpr int NWC = 2 * WJ;                   // W chunks per step
   constexpr int NE = XT * ESUB;                 // epilogue slices per step
   // ---- LDS addressing --------------------------------------------------------------------------------------
@@ -237,26 +234,8 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   const uint32_t aLN = (uint32_t)lane * 16u;                         // lane-linear piece element
   const uint32_t aT1 = (uint32_t)trb, aT2 = aT1 ^ 64u;               // transposed-read lane bases (half-read 0 / 1)
   const uint32_t smem0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const uint32_t aTab = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + (uint32_t)((NB * DPC + NBP * PPC + (IN8 ? 2 : 0) * KSJ + 2 * KSI + NW * XT * WSP) * 1024);
-  const uint32_t oRP = NB * DPC * 1024, oX16 = oRP + NBP * PPC * 1024, oS16 = oX16 + (IN8 ? 2 : 0) * KSJ * 1024;
-  // transposed byte reads (IN8): ds_read_b64_tr_b8 works on groups of 16 lanes; lane t of a group supplies the address of
-  // an 8-byte row, result lane i < 8 receives byte i of the rows of lanes 0, 2, .., 14 and lane 8 + i byte i of the rows of
-  // lanes 1, 3, .., 15 (scripts/probes/trb8.hip).  With lane t pointing at bytes 8q .. 8q+7 of piece lane (h' = t & 1,
-  // pixel 8 hq + (t >> 1)) - q = group & 1, hq = group >> 1 - the wave receives an A fragment of the 16-pixel k-step whose
-  // row r = lane & 31 is neuron nu8(r) of the tile and whose elements are the pixels 8 hq + 0..7 in order.
-  const uint32_t aT8 = 16u * (32u * (uint32_t)(lane & 1) + ((8u * (uint32_t)(lane >> 5) + (uint32_t)((lane & 15) >> 1)) ^ (8u * (uint32_t)(lane & 1)))) +
-                       8u * (uint32_t)((lane >> 4) & 1);   // (pixel slot ^ 8 h': the lsw8 swizzle of the byte pieces)
-  typedef __attribute__((address_space(3))) const u32x4 lds_cv4;
-  typedef __attribute__((address_space(3))) u32x4 lds_v4;
-  typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
-  typedef __attribute__((address_space(3))) uint32_t lds_u32;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  auto tr_pair = [&](uint32_t b1, uint32_t b2, int imm) -> u32x4 {     // fragment = two transposed 8-byte reads
-    const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(b1 + imm));
-    const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(b2 + imm));
-    const u32x2 a0 = __builtin_bit_cast(u32x2, r0), a1 = __builtin_bit_cast(u32x2, r1);
-    return u32x4{a0.x, a0.y, a1.x, a1.y};
-  };
+  const uint32_t aTab = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + L::oTab;
+  const uint32_t aT8 = tr8_lane_base(lane);                          // transposed byte reads (IN8)
   auto w_of = [&](int x, int s) -> u32x4 {
     return s < KSR ? wreg[x][s < KSR ? s : 0]
                    : reinterpret_cast<const u32x4*>(sWsp + (x * WSP + (s >= KSR ? s - KSR : 0)) * 1024)[lane];
@@ -276,23 +255,17 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     float r0 = 0.f, r1 = 0.f;
     if (P0) {
       const f32x4 ta = sL0[16 * ks + pi_perm(lane >> 5, 2 * v)], tb = sL0[16 * ks + pi_perm(lane >> 5, 2 * v + 1)];
-      r0 = __builtin_fmaf(ta.y, ep_x1, __builtin_fmaf(ta.x, ep_x0, ta.z)) * a.sc_first;
-      r1 = __builtin_fmaf(tb.y, ep_x1, __builtin_fmaf(tb.x, ep_x0, tb.z)) * a.sc_first;
+      r0 = l0_phase(ta, ep_x0, ep_x1, a.sc_first);
+      r1 = l0_phase(tb, ep_x0, ep_x1, a.sc_first);
     } else {
       // 8 phase bytes of k-step q in one 8-byte read per 4 slices (a dword per 2 slices is a 4-way bank conflict at
       // the 16-byte lane stride of a piece; 8 bytes are 2-way)
       if (v == 0) ep_pw2 = *(__attribute__((address_space(3))) const u32x2*)(uintptr_t)(bP + x * 1024 + 8 * q);
-      if constexpr (!TAB) {
-        const uint32_t pw = (v >> 1) ? ep_pw2.y : ep_pw2.x;
-        if (v & 1) { r0 = phase_rev8<2>(pw); r1 = phase_rev8<3>(pw); }
-        else { r0 = phase_rev8<0>(pw); r1 = phase_rev8<1>(pw); }
-      }
     }
     const int t0 = 8 * q + 2 * v;
     float c0, c1;
     uint32_t sn;
     if constexpr (TAB) {
-      typedef __attribute__((ext_vector_type(2))) _Float16 h2;
       const uint32_t pw = (v >> 1) ? ep_pw2.y : ep_pw2.x;
       const int b0 = (v & 1) ? 2 : 0;
       const uint32_t e0 = *(lds_cu32*)(uintptr_t)(aTab + (((pw >> (8 * b0)) & 0xffu) << 2));
@@ -330,7 +303,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     // the wc == 0 waves write theirs out): a wave-uniform branch here splits the step into basic blocks and costs
     // the register allocator more than the four instructions do
     // (element-wise: hipcc 7.2 folds a `for e: fdot2(bit_cast(fa[e]), ..)` loop into four uses of fa[0])
-    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
     const h2 one2 = __builtin_bit_cast(h2, ones_h2);
     const uint32_t f0 = fa.x, f1 = fa.y, f2 = fa.z, f3 = fa.w;
     if (!DBSPLIT || (x % WAVES_C) == wc) {   // DBSPLIT: the WAVES_C waves that hold the same delta^T fragments share the row tiles
@@ -355,11 +327,11 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     f32x16 g[XT];
     // wave-uniform buffer offsets of this step (SGPRs): ring slots of the deltas of block kx (X) and of block kx-1 (W, this
     // wave's row tiles)
-    const uint32_t uX = IN8 ? smem0 + oX16 + (uint32_t)(kx & 1) * (KSJ * 1024) : smem0 + (uint32_t)(kx % NB) * (DPC * 1024);
+    const uint32_t uX = IN8 ? smem0 + L::oX16 + (uint32_t)(kx & 1) * (KSJ * 1024) : smem0 + (uint32_t)(kx % NB) * (DPC * 1024);
     const uint32_t uWd = smem0 + (uint32_t)((kx + NB - 1) % NB) * (DPC * 1024) + (uint32_t)(wr * WJ) * (uint32_t)TSTR;
-    const uint32_t uWs = smem0 + oS16 + (uint32_t)((kx + 1) & 1) * (KSI * 1024) + (uint32_t)(wc * WI) * 2048u;  // S16 of block kx-1, this wave's column tiles
-    const uint32_t uEs = smem0 + oS16 + (uint32_t)(kx & 1) * (KSI * 1024) + (uint32_t)xit0 * 2048u;             // S16 of block kx, this wave's X tiles
-    const uint32_t uEp = smem0 + oRP + (uint32_t)(kx % NBP) * (PPC * 1024) + (uint32_t)xit0 * 1024u;             // phase pieces of block kx
+    const uint32_t uWs = smem0 + L::oS16 + (uint32_t)((kx + 1) & 1) * (KSI * 1024) + (uint32_t)(wc * WI) * 2048u;  // S16 of block kx-1, this wave's column tiles
+    const uint32_t uEs = smem0 + L::oS16 + (uint32_t)(kx & 1) * (KSI * 1024) + (uint32_t)xit0 * 2048u;             // S16 of block kx, this wave's X tiles
+    const uint32_t uEp = smem0 + L::oRP + (uint32_t)(kx % NBP) * (PPC * 1024) + (uint32_t)xit0 * 1024u;             // phase pieces of block kx
     // C(kx+1) rides in the shadow of phase X (sixteen dependent MFMAs with little else to issue): raw bytes read behind
     // chunk 1, the two converted pieces written behind chunks 6 and 10.  (At the top of the step, with both waves of every
     // SIMD in it at once, it was a serial LDS round trip.)
@@ -367,7 +339,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     if (do_c && !(CVX && do_x)) convert(kx + 1);
     u32x4 cv_raw;
     const uint32_t cv_src = smem0 + (uint32_t)((kx + 1) % NB) * (DPC * 1024) + (uint32_t)wave * 1024u + aLN;
-    const uint32_t cv_dst = smem0 + oX16 + (uint32_t)((kx + 1) & 1) * (KSJ * 1024) + (uint32_t)wave * 2048u + (uint32_t)lsw8 * 16u;
+    const uint32_t cv_dst = smem0 + L::oX16 + (uint32_t)((kx + 1) & 1) * (KSJ * 1024) + (uint32_t)wave * 2048u + (uint32_t)lsw8 * 16u;
     if (P0 && do_x) pixel_xy(kx, ep_x0, ep_x1);
     const uint32_t bX0 = (IN8 ? aLN : aL1) + uX, bX1 = (IN8 ? aLN : aL1x) + uX;   // (X16 is stored lane-linearly: no swizzle)
     auto x_load = [&](int c) -> u32x4 { return *(lds_cv4*)(uintptr_t)(((c & 1) ? bX1 : bX0) + c * 1024); };
@@ -375,7 +347,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
     // A fragment (delta^T) of row tile x, pixel k-step kk (phase W)
     auto wa_load = [&](int kk, int x) -> raw_t {
       if constexpr (IN8) {
-        typedef __attribute__((ext_vector_type(2))) int i32x2;
         const i32x2 r = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2*)(uintptr_t)(bWa1 + x * TSTR + kk * 256));
         return u32x2{(uint32_t)r.x, (uint32_t)r.y};
       } else {
@@ -413,9 +384,6 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
             if (i == 1) cv_raw = *(lds_cv4*)(uintptr_t)cv_src;
             if (i == 6) *(lds_v4*)(uintptr_t)cv_dst = fp8x8_to_f16(cv_raw.x, cv_raw.y);
             if (i == 10) *(lds_v4*)(uintptr_t)(cv_dst + 1024u) = fp8x8_to_f16(cv_raw.z, cv_raw.w);
-          }
-          if (PF == 0 && do_w && i + 1 == XT * KSX) {   // no read-ahead: the first W operands follow the last X MFMA
-            wb_load(0, fb); fa[0] = wa_load(0, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -505,28 +473,27 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   }
 }
 
-// LDS bytes of k_bwd8 (host side of the same layout)
-template <int JW, int IW, int NW, bool LAST, bool P0, int NB, int PARK = 0, int NBP_ = 0, bool D8 = true>
-constexpr size_t bwd8_lds_bytes() {
-  constexpr int JT = JW / 32, IT = IW / 32, KSJ = JW / 16, KSI = IW / 16, KSX = LAST ? 1 : KSJ, XT = IT / NW;
-  constexpr int DPC = (D8 && !LAST) ? JT : (LAST ? 2 : KSJ), PPC = P0 ? 0 : IT;
-  constexpr int WSP = PARK;
-  constexpr int NBP = NBP_ > 0 ? NBP_ : NB;
-  return (size_t)(NB * DPC + NBP * PPC + ((D8 && !LAST) ? 2 * KSJ : 0) + 2 * KSI + NW * XT * WSP) * 1024 + (P0 ? (size_t)IW * 16 : 1024);   // P0: layer-0 table; else the sin/cos table of the phase bytes
-}
-
 // ---------------------------------------------------------------------------------------------
 // k_dw0_8: weight gradient of layer 0 from fp8 deltas (k_dw0 of siren_kernels.hip with the byte pieces expanded
 // to the 16-bit image one block ahead).  Ring: 8 slots of JW/32 KiB; D16: 2 x JW/16 KiB.
 // ---------------------------------------------------------------------------------------------
+// LDS of k_dw0_8: [ring of NB blocks of fp8 pieces][two 16-bit images of a block][coordinate table, as k_dw0]
+template <int JW, int NB>
+struct Dw0Lds8 {
+  static constexpr int JT = JW / 32, KSJ = JW / 16;
+  static constexpr size_t oD16 = (size_t)NB * JT * 1024, oXY = oD16 + 2 * KSJ * 1024, bytes = oXY + 512;
+  static_assert(bytes <= kLdsMax, "k_dw0_8 LDS budget");
+};
+
 template <int JW, typename OP, int NB = 8>
 __global__ __launch_bounds__(JW * 2) void k_dw0_8(Dw0Args a) {
+  using L = Dw0Lds8<JW, NB>;
   constexpr int NW = JW / 32, JT = JW / 32, KSJ = JW / 16;
   constexpr int GD = JT / NW;   // = 1
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const rD = smem;
-  char* const d16 = rD + NB * JT * 1024;
-  uint16_t* sXY = reinterpret_cast<uint16_t*>(d16 + 2 * KSJ * 1024);          // [2][4][32]
+  char* const d16 = smem + L::oD16;
+  uint16_t* sXY = reinterpret_cast<uint16_t*>(smem + L::oXY);          // [2][4][32]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long pb_begin = blockIdx.x, pb_step = gridDim.x;
@@ -551,12 +518,8 @@ __global__ __launch_bounds__(JW * 2) void k_dw0_8(Dw0Args a) {
   };
   auto build_xy = [&](int k) {
     if (wave == 0 && lane < 32) {
-      long p = a.pix0 + (pb_begin + (long)k * pb_step) * 32 + lane;
-      if (p >= a.npix) p = a.npix - 1;
-      const unsigned row = (unsigned)(((unsigned long long)p * a.w_magic) >> 40);
-      const unsigned col = (unsigned)(p - (long)row * a.W);
-      const float x0 = ((float)(row + (unsigned)a.row_begin) * a.inv_hm1 - 0.5f) * 2.0f;
-      const float x1 = ((float)col * a.inv_wm1 - 0.5f) * 2.0f;
+      float x0, x1;
+      pixel_coords(a, a.pix0 + (pb_begin + (long)k * pb_step) * 32 + lane, x0, x1);
       const uint32_t h0 = OP::pack2(x0, 0.f), h1 = OP::pack2(x1, 0.f);
       uint16_t* t = sXY + (k & 1) * 128 + lane;
       t[0] = (uint16_t)h0;
@@ -596,8 +559,7 @@ __global__ __launch_bounds__(JW * 2) void k_dw0_8(Dw0Args a) {
   }
   float* slab = a.slab + (size_t)blockIdx.x * (JW * 32 + JW);
   const int cl = lane & 31, hh = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < 16; ++t) slab[(size_t)(32 * wave + rho(t, hh)) * 32 + cl] = acc[t];
+  slab_store_tile(slab, 32, 32 * wave, 0, acc, lane);
   const float tsum = dbs + __shfl_xor(dbs, 32);
   if (hh == 0) slab[JW * 32 + 32 * wave + cl] = tsum;
 }

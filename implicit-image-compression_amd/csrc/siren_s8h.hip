@@ -41,26 +41,28 @@ namespace sf {
 
 constexpr int kBwd8hLD = 2;      // slots between a table lookup and the value that uses it
 
+// the LDS layout above: ring depths and byte offsets (the kernel addresses LDS absolutely: the table is at address 0)
 template <int PARK>
-constexpr size_t bwd8h_lds_bytes() { return (size_t)(1 + 5 * 8 + 4 * 8 + 3 * 16 + 8 * PARK) * 1024; }
+struct Bwd8hLds {
+  static constexpr int NBD = 5, NBP = 4;
+  static constexpr uint32_t oRD = 1024, oRP = oRD + NBD * 8192, oS16 = oRP + NBP * 8192, oWP = oS16 + 3 * 16384;
+  static constexpr size_t bytes = (size_t)oWP + 8 * PARK * 1024;
+  static_assert(bytes <= kLdsMax, "k_bwd8h LDS budget");
+};
+static_assert(Bwd8hLds<3>::bytes == 145 * 1024, "the figure in the header");
 
 // DBX: the row tile (0..3) whose bias-gradient sums this instantiation takes (= the wave's column index wc)
 // ROLE: 0 = waves 0-3 ("N": X | W + E), 1 = waves 4-7 ("S", their SIMD partners: W + E | X)
 template <int PARK, int DBX, int ROLE>
 __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, const int lane) {
   typedef OpF16 OP;
-  constexpr int KS = 16, NT = 8, NBD = 5, NBP = 4, WJ = 4, WI = 2;
+  using L = Bwd8hLds<PARK>;
+  constexpr int KS = 16, NT = 8, WJ = 4, WI = 2;
   constexpr int AD = 3, AP = 3;                  // blocks requested ahead (deltas / phases)
   constexpr int LD = kBwd8hLD, NTAB = 2 * (LD + 1);   // table ring of phase X: LD + 1 pairs in flight
   constexpr int KSR = KS - PARK;
-  constexpr uint32_t oRD = 1024, oRP = oRD + NBD * 8192, oS16 = oRP + NBP * 8192, oWP = oS16 + 3 * 16384;
+  constexpr uint32_t oRD = L::oRD, oRP = L::oRP, oS16 = L::oS16, oWP = L::oWP;
   static_assert(LD >= 1 && LD <= 4 && PARK >= 0 && PARK <= 4, "slot plan");
-  typedef __attribute__((address_space(3))) const u32x4 lds_cv4;
-  typedef __attribute__((address_space(3))) u32x4 lds_v4;
-  typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-  typedef __attribute__((ext_vector_type(2))) int i32x2;
 
   const int wr = wave >> 2, wc = wave & 3;
   // lane patterns of the LDS accesses (everything else is a wave-uniform offset or a 16-bit immediate)
@@ -71,13 +73,7 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
   const uint32_t aL8 = (uint32_t)(lane ^ ((lane >> 5) << 3)) * 16u;
   const uint32_t aL1 = (uint32_t)sw_lane(lane, 0) * 16u, aL1x = aL1 ^ 128u;     // swizzled 16-bit piece element, even / odd k-step
   const uint32_t aT1 = (uint32_t)tr_lane_base(lane), aT2 = aT1 ^ 64u;           // transposed 16-bit reads (sines)
-  // transposed byte reads: ds_read_b64_tr_b8 works on groups of 16 lanes; lane t of a group supplies the address of an
-  // 8-byte row, result lane i < 8 receives byte i of the rows of lanes 0, 2, .., 14 and lane 8 + i byte i of the rows of
-  // lanes 1, 3, .., 15.  With lane t pointing at bytes 8q .. 8q+7 of piece lane (h' = t & 1, pixel 8 hq + (t >> 1)) -
-  // q = group & 1, hq = group >> 1 - the wave receives an A fragment of the 16-pixel k-step whose row r = lane & 31 is
-  // neuron nu8(r) of the tile and whose elements are the pixels 8 hq + 0..7 in order.
-  const uint32_t aT8 = 16u * (32u * (uint32_t)(lane & 1) + ((8u * (uint32_t)(lane >> 5) + (uint32_t)((lane & 15) >> 1)) ^ (8u * (uint32_t)(lane & 1)))) +
-                       8u * (uint32_t)((lane >> 4) & 1);
+  const uint32_t aT8 = tr8_lane_base(lane);                                     // transposed byte reads (deltas)
   uint32_t aWP = aLN + oWP + (uint32_t)(wave * PARK) * 1024u;                   // parked W_l^T k-steps of this wave
   asm volatile("" : "+v"(aWP));
 
@@ -90,10 +86,7 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
     *(lds_v4*)(uintptr_t)(aWP + (uint32_t)(s - KSR) * 1024u) = a.wb[(wave * KS + s) * 64 + lane];
   {   // sin/cos table of the phase bytes (decode: u / 256 + kPhaseEps revolutions), entry u at LDS byte 4 u
     const int tid = wave * 64 + lane;
-    if (tid < 256) {
-      const float r = __builtin_fmaf((float)tid, 1.0f / 256.0f, kPhaseEps);
-      *(__attribute__((address_space(3))) uint32_t*)(uintptr_t)(4u * (uint32_t)tid) = OP::pack2(__builtin_amdgcn_sinf(r), __builtin_amdgcn_cosf(r));
-    }
+    if (tid < 256) *(__attribute__((address_space(3))) uint32_t*)(uintptr_t)(4u * (uint32_t)tid) = phase_tab_entry<OP>(tid);
   }
 
   f32x16 acc[WJ][WI];
@@ -118,16 +111,6 @@ __device__ __forceinline__ void bwd8h_body(const Bwd8Args& a, const int wave, co
   u32x4* const pO0 = a.Dout + (pb_begin * NT + wave) * 64;
   auto stageD = [&](const u32x4* src, uint32_t off) { glds16o(src, aL8, oRD + off + (uint32_t)wave * 1024u); };        // off = ring slot * 8 KiB
   auto stageP = [&](const u32x4* src, uint32_t off) { glds16o(src, aLN, oRP + off + (uint32_t)wave * 1024u); };
-  auto slot_end = [&]() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto tr_pair = [&](uint32_t b1, uint32_t b2, int imm) -> u32x4 {
-    const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(b1 + imm));
-    const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(b2 + imm));
-    const u32x2 a0 = __builtin_bit_cast(u32x2, r0), a1 = __builtin_bit_cast(u32x2, r1);
-    return u32x4{a0.x, a0.y, a1.x, a1.y};
-  };
 
   // ---- the two phases of a block, 16 slots each -----------------------------------------------------------------------
   //   phase X(k)            16 MFMAs of the data-gradient product (one dependent chain); B operand = the bytes of D(k),

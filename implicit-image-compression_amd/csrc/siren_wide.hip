@@ -153,15 +153,34 @@ struct WGemmArgs {
 // k_wgemm<1>: the last layer (32 padded output rows) + residual.  Workgroup = 8 waves = 256 pixels, one
 // 32-pixel block per wave; the [32 x WD] weight image streams through a 4-slot LDS ring (4 k-steps per chunk),
 // the activations are prefetched two chunks ahead into registers.  (Hidden layers: k_wgemm2 below.)
+// LDS of k_wgemm: [ring of NB chunks of OT tiles x 4 k-steps][8 SSE partials]
+template <int MODE>
+struct WGemmLds {
+  static constexpr int OT = MODE == 1 ? 1 : 8, NB = 4, CH = OT * 4 * 1024;   // 32-row tiles per chunk, ring slots, bytes per chunk
+  static constexpr size_t oRed = (size_t)NB * CH, bytes = oRed + 64;
+  static_assert(bytes <= kLdsMax, "k_wgemm LDS budget");
+};
+// LDS of k_wgemm2: a ring of NB slots, each 16 A pieces + two k-steps of NPB pixel blocks (fp8 input fills half of those)
+struct WGemm2Lds {
+  static constexpr int NPB = 8, NB = 4, SLOT = (16 + 2 * NPB) * 1024, bytes = NB * SLOT;
+  static_assert(bytes <= kLdsMax, "k_wgemm2 LDS budget");
+};
+// LDS of k_wdw: a ring of NB blocks of KSJ delta pieces (D8: one per 32-neuron tile) + KSI activation pieces
+template <int JW, bool D8>
+struct WDwLds {
+  static constexpr int KSJ = D8 ? JW / 32 : JW / 16, KSI = 16, NB = 4, BLK = (KSJ + KSI) * 1024, bytes = NB * BLK;
+  static_assert(bytes <= kLdsMax, "k_wdw LDS budget");
+};
+
 template <int MODE, typename OP>
 __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
   static_assert(MODE == 1, "hidden layers and the data gradient run k_wgemm2");
-  constexpr int OT = MODE == 1 ? 1 : 8;       // 32-row tiles per LDS chunk
+  using L = WGemmLds<MODE>;
   constexpr int TW = MODE == 1 ? 1 : 4;       // tiles per wave
   constexpr int PBW = MODE == 1 ? 1 : 2;      // pixel blocks per wave
-  constexpr int NB = 4, CH = OT * 4 * 1024;   // ring slots, bytes per chunk
+  constexpr int OT = L::OT, NB = L::NB, CH = L::CH;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sRed = reinterpret_cast<float*>(smem + NB * CH);
+  float* sRed = reinterpret_cast<float*>(smem + L::oRed);
   const int tid = threadIdx.x, lane = tid & 63, m = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // XCD-aware 1-D grid: consecutive workgroup ids go to consecutive XCDs (8), each with its own L2.  The n_ob
@@ -292,8 +311,10 @@ __global__ __launch_bounds__(512, 1) void k_wgemm2(WGemmArgs a) {
   static_assert(MODE == 0 || MODE == 2, "last layer: k_wgemm<1>");
   static_assert(MODE == 2 || (!IN8 && !OUT8), "fp8 deltas: the data-gradient product only");
   constexpr int NWV = 8;                                         // waves per workgroup
-  constexpr int OT = 8, TW = 4, PBW = 2, NPB = NWV;              // pixel blocks per workgroup: two per wave pair
-  constexpr int NB = 4, PD = NB - 1, SLOT = (16 + 2 * NPB) * 1024;
+  using L = WGemm2Lds;
+  constexpr int OT = 8, TW = 4, PBW = 2, NPB = L::NPB;           // pixel blocks per workgroup: two per wave pair
+  static_assert(NPB == NWV, "one pixel block per wave");
+  constexpr int NB = L::NB, PD = NB - 1, SLOT = L::SLOT;
   constexpr int GA = 16 / NWV, GB = (IN8 ? NPB : 2 * NPB) / NWV, G = GA + GB;   // LDS-DMA instructions per wave and chunk
   constexpr int NEP = MODE == 0 ? TW * PBW * (P8 ? 3 : 4) : TW * PBW * (OUT8 ? 1 : 2);   // epilogue stores per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -583,7 +604,8 @@ __global__ __launch_bounds__(512) void k_wdw(WDwArgs a) {
   static_assert(!D8 || JW == 256, "byte deltas: hidden layers");
   constexpr int WAVES_R = JW == 256 ? 2 : 1, WAVES_C = 8 / WAVES_R, NW = 8;
   constexpr int JT = JW / 32, IT = 8, WJ = JT / WAVES_R, WI = IT / WAVES_C;
-  constexpr int KSJ = D8 ? JW / 32 : JW / 16, KSI = 16, NB = 4, PD = 3, BLK = (KSJ + KSI) * 1024;   // (KSJ: delta pieces per block)
+  using L = WDwLds<JW, D8>;
+  constexpr int KSJ = L::KSJ, KSI = L::KSI, NB = L::NB, PD = 3, BLK = L::BLK;   // (KSJ: delta pieces per block)
   constexpr int G = KSJ % NW == 0 ? KSJ / NW + KSI / NW : 0;   // LDS-DMA instructions per wave per block (0: uneven)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -597,8 +619,7 @@ __global__ __launch_bounds__(512) void k_wdw(WDwArgs a) {
   const int ksd_off = (D8 ? 8 : 16) * jb, ksp_off = 16 * ib;
   // byte pieces: LDS slot i holds the element of lane i ^ 8 (i >> 5); transposed byte reads: see k_bwd8h
   const uint32_t aL8 = (uint32_t)(lane ^ ((lane >> 5) << 3)) * 16u;
-  const uint32_t aT8 = 16u * (32u * (uint32_t)(lane & 1) + ((8u * (uint32_t)(lane >> 5) + (uint32_t)((lane & 15) >> 1)) ^ (8u * (uint32_t)(lane & 1)))) +
-                       8u * (uint32_t)((lane >> 4) & 1);
+  const uint32_t aT8 = tr8_lane_base(lane);
   const long pb_begin = blockIdx.x, pb_step = gridDim.x;
   const int nblk = (int)((a.n_pb - pb_begin + pb_step - 1) / pb_step);
   f32x16 acc[WJ][WI];
@@ -618,7 +639,6 @@ __global__ __launch_bounds__(512) void k_wdw(WDwArgs a) {
       glds16s(a.P + (pb * a.ksp_total + ksp_off + pc) * 64, (uint32_t)sw_lane(lane, pc & 1) * 16u, base + (KSJ + pc) * 1024);
   };
   auto d8_frag = [&](const char* sD, int tile, int kk) -> u32x4 {
-    typedef __attribute__((ext_vector_type(2))) int i32x2;
     const uint32_t adr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)sD + aT8 + (uint32_t)(tile * 1024 + kk * 256);
     const i32x2 r = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2*)(uintptr_t)adr);
     return fp8x8_to_f16((uint32_t)r.x, (uint32_t)r.y);

@@ -87,7 +87,6 @@ __device__ __forceinline__ float wv_bilinear_weight(int o, int i, float up, int 
 
 __device__ __forceinline__ uint32_t wv_pack_f16(float a, float b) {
   typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) _Float16 h2;
   f2 v = {a, b};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h2));
 }

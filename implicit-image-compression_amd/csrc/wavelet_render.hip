@@ -60,14 +60,11 @@ __global__ __launch_bounds__(kWvThreads) void k_wv_render(WvRenderArgs a) {
     const float (&rgb)[3] = px.rgb;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
+      const uint32_t q = render_quant<BITS>(rgb[k]);
       if constexpr (BITS == 16) {
-        int q = (int)(rgb[k] * 65535.0f);   // v_cvt_i32_f32: toward zero
-        q = q < 0 ? 0 : (q > 65535 ? 65535 : q);
-        if (k < 2) mine |= (uint32_t)q << (16 * k); else mine1 = (uint32_t)q;
+        if (k < 2) mine |= q << (16 * k); else mine1 = q;
       } else {
-        int q = (int)(rgb[k] * 255.0f);   // v_cvt_i32_f32: toward zero
-        q = q < 0 ? 0 : (q > 255 ? 255 : q);
-        mine |= (uint32_t)q << (8 * k);
+        mine |= q << (8 * k);
       }
     }
   }

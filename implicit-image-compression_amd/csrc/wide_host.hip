@@ -53,17 +53,16 @@ int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob) {
   b.n_super = n_super; b.n_ob = n_ob;
   const unsigned grid = (unsigned)((n_super + 7) / 8 * 8 * n_ob);
   if constexpr (MODE == 1) {
-    return with_op(h, [&](auto op) { return launch(h, k_wgemm<1, decltype(op)>, grid, 512, (size_t)4 * 4 * 1024 + 64, b); });
+    return with_op(h, [&](auto op) { return launch(h, k_wgemm<1, decltype(op)>, grid, 512, WGemmLds<1>::bytes, b); });
   } else {
     if constexpr (MODE == 2) {
       if (h->d8) {   // fp8 deltas (format 8): out always, in for every launch below the last layer's
-        const size_t lds8 = (size_t)4 * 32 * 1024;
         const unsigned pg8 = wgemm_grid(h, n_ob, grid);
-        return a.fscale ? launch(h, k_wgemm2<2, OpF16, true, false, true>, pg8, 512, lds8, b)
-                        : launch(h, k_wgemm2<2, OpF16, true, true, true>, pg8, 512, lds8, b);
+        return a.fscale ? launch(h, k_wgemm2<2, OpF16, true, false, true>, pg8, 512, WGemm2Lds::bytes, b)
+                        : launch(h, k_wgemm2<2, OpF16, true, true, true>, pg8, 512, WGemm2Lds::bytes, b);
       }
     }
-    const size_t lds = (size_t)4 * 32 * 1024;
+    const size_t lds = WGemm2Lds::bytes;
     const unsigned pgrid = wgemm_grid(h, n_ob, grid);    // persistent: one workgroup per CU
     if (h->s8 && (MODE == 0 || b.Pprev))                    // phase bytes (format 12; fp16 only: sf_create)
       return launch(h, k_wgemm2<MODE, OpF16, true>, pgrid, 512, lds, b);
@@ -139,11 +138,10 @@ int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
         {
           Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx, npx * ((last ? 64.0 : WD * 2.0) + WD * 2.0));
           const dim3 grid(gx, nby);
-          const size_t lds = (size_t)4 * ((last ? 2 : 16) + 16) * 1024;
-          if (dl8) SF_TRY(launch(h, k_wdw<256, OpF16, true>, grid, 512, (size_t)4 * (8 + 16) * 1024, a));
+          if (dl8) SF_TRY(launch(h, k_wdw<256, OpF16, true>, grid, 512, WDwLds<256, true>::bytes, a));
           else SF_TRY(with_op(h, [&](auto op) {
             using OP = decltype(op);
-            return last ? launch(h, k_wdw<32, OP>, grid, 512, lds, a) : launch(h, k_wdw<256, OP>, grid, 512, lds, a);
+            return last ? launch(h, k_wdw<32, OP>, grid, 512, WDwLds<32, false>::bytes, a) : launch(h, k_wdw<256, OP>, grid, 512, WDwLds<256, false>::bytes, a);
           }));
         }
         WReduceArgs r = zeroed<WReduceArgs>();

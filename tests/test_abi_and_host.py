@@ -81,7 +81,9 @@ def test_no_exception_crosses_the_c_abi():
 
 def test_kernel_sources_have_one_build_and_no_switches():
     """csrc/*.hip is one build: no preprocessor conditional (a -D on the build line cannot select a timing-only or otherwise
-    different kernel) and no environment variable read by the library (nothing outside sf_config changes what it computes)."""
+    different kernel) and no environment variable read by the library (nothing outside sf_config changes what it computes).
+    Nor a switch in the source itself: no file-scope `constexpr bool k... = true|false;` and no condition that starts from a
+    literal (`false && ...`, `true || ...`) - a branch behind a constant that cannot change is deleted, not parked."""
     import glob
     import re
     csrc = os.path.dirname(_engine._LIB_PATH)
@@ -90,6 +92,12 @@ def test_kernel_sources_have_one_build_and_no_switches():
     cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b")
     for path in hips:
         bad = [(i + 1, l) for i, l in enumerate(open(path).read().splitlines()) if cond.match(l)]
+        assert not bad, (os.path.basename(path), bad[:5])
+    flag = re.compile(r"^(static\s+|inline\s+)*constexpr\s+bool\s+k\w*\s*=\s*(true|false)\s*;")   # column 0: file or namespace scope
+    literal = re.compile(r"\bfalse\s*&&|\btrue\s*\|\|")
+    for path in hips + sorted(glob.glob(os.path.join(csrc, "*.h"))):
+        lines = open(path).read().splitlines()
+        bad = [(i + 1, l) for i, l in enumerate(lines) if flag.match(l) or literal.search(l.split("//")[0])]
         assert not bad, (os.path.basename(path), bad[:5])
     for path in sorted(glob.glob(os.path.join(csrc, "*"))):
         if os.path.isfile(path) and not path.endswith(".so"):
