@@ -4,29 +4,19 @@ repr of the others, a sha256 of tensor content where the host alone determines i
 bool / int observations of the binding (pointers inside the engine's views, the optimiser's moments, what a re-made handle
 carried over).  No float computed on the device goes into the output, so the parent compares it for equality with
 tests/golden/binding_trace.json, which this same file wrote on the binding as it stood before models/binding.py.
-Uses only names both sides have.  Usage: _binding_trace_child.py OUT.json"""
+Uses only names both sides have."""
 import copy
-import hashlib
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import torch
 
-import torch  # noqa: E402
-
-from oracle import siren_oracle as so  # noqa: E402
+from _gpu_child import child_main
+from _gpu_fixtures import sha
+from oracle import siren_oracle as so
 
 LOG = []                       # the running scenario's entries: handle calls and step observations, in order
 HANDLES = []                   # every handle a _new_engine made in this scenario (raw, not the proxy)
 SHA_ALWAYS = set()             # methods whose tensor arguments are hashed in this scenario
 SHA_ONCE = set()               # ... hashed at their first call only
-
-
-def sha(t):
-    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
 def describe(v, hashed):
@@ -287,8 +277,7 @@ def scenario_e():
     step("E2 train_epoch", bound=bound(m), optim_bound=optim_bound(m, opt), handles=len(HANDLES), closes=calls("close"))
 
 
-def main():
-    out = sys.argv[1]
+def case_binding_trace():
     torch.cuda.init()
     from implicit_image.models.fourier import FourierNet
     from implicit_image.models.siren import Siren
@@ -304,9 +293,8 @@ def main():
         torch.cuda.synchronize()
         res[name] = list(LOG)
         print(name, len(LOG), "entries,", len(HANDLES), "handles", flush=True)
-    with open(out, "w") as f:
-        json.dump(res, f, indent=0, sort_keys=True)
+    return res
 
 
 if __name__ == "__main__":
-    main()
+    child_main({"binding_trace": case_binding_trace})

@@ -1,16 +1,11 @@
 """Child of tests/test_gpu_engine_attrs.py: builds each of the six engine classes once, at the smallest shapes, in ONE fresh
 process and writes what a caller can see of it: every public plain attribute, and what render hands back for each
-want_u8 / want_pred combination (the parent runs this under a time limit and compares the JSON with
-tests/golden/engine_attrs.json).  Usage: _engine_attrs_child.py OUT.json"""
+want_u8 / want_pred combination (the parent compares the JSON with tests/golden/engine_attrs.json)."""
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import torch
 
-import torch  # noqa: E402
+from _gpu_child import child_main
 
 PLAIN = (int, float, bool, str)
 WANTS = [(True, False), (False, True), (True, True), (False, False)]       # (want_u8, want_pred); the last is illegal
@@ -88,8 +83,7 @@ def cases():
             ("WaveletRenderEngine", lambda: E.WaveletRenderEngine(30, 64, 3, max_rows=7), wavelet_like)]
 
 
-def main():
-    out = sys.argv[1]
+def case_engine_attrs():
     torch.cuda.init()
     res = {}
     for name, make, use in cases():
@@ -99,9 +93,8 @@ def main():
         eng.close()
         res[name] = rec
         print(name, json.dumps(rec["attrs"]), flush=True)
-    with open(out, "w") as f:
-        json.dump(res, f, indent=1, sort_keys=True)
+    return res
 
 
 if __name__ == "__main__":
-    main()
+    child_main({"engine_attrs": case_engine_attrs})

@@ -1,27 +1,18 @@
-"""Child of tests/test_gpu_feather.py: one Feathermap GPU case per process (the parent runs it under a time limit and
-reads the JSON it writes).  Usage: _feather_child.py CASE OUT.json [WORKDIR]"""
+"""Child of tests/test_gpu_feather.py: one Feathermap GPU case per process."""
 import json
-import math
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import _feather_ref as fr  # noqa: E402
-from oracle import siren_oracle as so  # noqa: E402  (test infrastructure: grid and image formulas)
+from _gpu_child import ROOT, child_main, run
+from _gpu_fixtures import golden, relerr
+import _feather_ref as fr
+from oracle import siren_oracle as so  # (test infrastructure: grid and image formulas)
 
 SMALL = dict(depth=4, hidden_size=64, first_omega_0=50, hidden_omega_0=30, outermost_linear=True)
 YAML = dict(depth=8, hidden_size=128, first_omega_0=50, hidden_omega_0=30, outermost_linear=True)
-
-
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"), allow_pickle=False)
 
 
 def model(seed=0, density=0.2, scratch_format=0, **kw):
@@ -29,11 +20,6 @@ def model(seed=0, density=0.2, scratch_format=0, **kw):
     from implicit_image.pipeline.feathermap import FeatherNet
     torch.manual_seed(seed)
     return FeatherNet(Siren(scratch_format=scratch_format, **kw), compress=density).cuda()
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def layout(m, eng):
@@ -217,17 +203,13 @@ def case_fit(workdir):
     env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "implicit-image-compression_amd"))
     args = ["masking=Feathermap", "quant=none", "img.height=128", "img.width=128", "train.num_steps=300",
             "train.log_steps=100", "mlp.hidden_size=64", "mlp.depth=4"]
-    r = subprocess.run([sys.executable, "-m", "implicit_image.fit"] + args, cwd=workdir, env=env,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=400)
-    log = r.stdout.decode()
-    if r.returncode != 0:
-        raise RuntimeError(log[-3000:])
-    run = None
+    log = run([sys.executable, "-m", "implicit_image.fit"] + args, timeout=400, cwd=workdir, env=env)
+    found = None
     for dp, _, files in os.walk(os.path.join(workdir, "outputs")):
         if "model.pth" in files:
-            run = dp
-    res = json.load(open(os.path.join(run, "result.json")))
-    sd = torch.load(os.path.join(run, "model.pth"))["state_dict"]
+            found = dp
+    res = json.load(open(os.path.join(found, "result.json")))
+    sd = torch.load(os.path.join(found, "model.pth"))["state_dict"]
     from implicit_image.data import get_grid, load_img
     from implicit_image.config import load_config
     from implicit_image.utils.train_helper import eval_epoch
@@ -239,13 +221,6 @@ def case_fit(workdir):
     return {"keys": list(sd), "res": res, "reload_psnr": psnr, "log_has_psnr": "PSNR" in log}
 
 
-def main():
-    case, out = sys.argv[1], sys.argv[2]
-    fn = {"parity": case_parity, "traj": case_traj, "steps": case_steps, "state": case_state, "plateau": case_plateau}
-    r = case_fit(sys.argv[3]) if case == "fit" else fn[case]()
-    with open(out, "w") as f:
-        json.dump(r, f)
-
-
 if __name__ == "__main__":
-    main()
+    child_main({"parity": case_parity, "traj": case_traj, "steps": case_steps, "state": case_state, "plateau": case_plateau,
+                "fit": case_fit})

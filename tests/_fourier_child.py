@@ -1,41 +1,21 @@
-"""Child of tests/test_gpu_fourier.py: one FourierNet GPU case per process (the parent runs it under a time limit and
-reads the JSON it writes).  Usage: _fourier_child.py CASE OUT.json [WORKDIR]"""
-import hashlib
-import json
-import math
+"""Child of tests/test_gpu_fourier.py: one FourierNet GPU case per process."""
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from oracle import siren_oracle as so  # noqa: E402  (test infrastructure: grid and image formulas)
+from _gpu_child import ROOT, child_main
+from _gpu_fixtures import golden, relerr, sha
+from oracle import siren_oracle as so  # (test infrastructure: grid and image formulas)
 
 SMALL = dict(depth=4, hidden_size=64, map_size=128, map_scale=10.0)
 YAML = dict(depth=8, hidden_size=128, map_size=256, map_scale=16.0)
-
-
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"), allow_pickle=False)
 
 
 def model(seed=0, **kw):
     from implicit_image.models import registry
     torch.manual_seed(seed)
     return registry["fourier"](**kw).cuda()
-
-
-def sha(t):
-    return hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def case_parity():
@@ -173,14 +153,6 @@ def case_fit(workdir):
             "container_bytes": os.path.getsize(os.path.join(out_dir, "model_quantized", "compressed_weights.data"))}
 
 
-def main():
-    case, out = sys.argv[1], sys.argv[2]
-    fn = {"parity": case_parity, "steps": case_steps, "padded": case_padded, "masks": case_masks,
-          "plateau": case_plateau}.get(case)
-    res = fn() if fn else case_fit(sys.argv[3])
-    json.dump(res, open(out, "w"), indent=1)
-    print(json.dumps(res)[:4000])
-
-
 if __name__ == "__main__":
-    main()
+    child_main({"parity": case_parity, "steps": case_steps, "padded": case_padded, "masks": case_masks,
+                "plateau": case_plateau, "fit": case_fit})

@@ -1,15 +1,12 @@
-"""Child of tests/test_gpu_fourier_render.py: one FourierNet render-path GPU case per process (the parent runs it under a
-time limit and reads the JSON it writes).  Usage: _fourier_render_child.py CASE OUT.json [WORKDIR]"""
+"""Child of tests/test_gpu_fourier_render.py: one FourierNet render-path GPU case per process."""
 import itertools
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import torch
 
-import torch  # noqa: E402
+from _gpu_child import ROOT, child_main
+from _gpu_fixtures import (Guarded, fourier_params, handle_memory, launches, recorder, refused_training_calls,
+                           working_calls)
 
 HIDDEN = (32, 64, 128, 256)
 MAPS = (64, 512)
@@ -26,18 +23,6 @@ def shapes():
     return list(itertools.product(hm, N_LINEAR, PICTURES, CHUNKS))
 
 
-def random_params(hidden, n_linear, map_size, gen):
-    """seeded uniform weights of He scale (the ReLU activations stay of order one at every depth), small biases, the output
-    layer four times larger so that the sigmoid spreads over many byte levels"""
-    parts = []
-    for l in range(n_linear):
-        fin = map_size if l == 0 else hidden
-        fout = 3 if l == n_linear - 1 else hidden
-        scale = (6.0 / fin) ** 0.5 * (4.0 if l == n_linear - 1 else 1.0)
-        parts += [((torch.rand(fout * fin, generator=gen) * 2 - 1) * scale), (torch.rand(fout, generator=gen) * 2 - 1) * 0.1]
-    return torch.cat(parts).float().contiguous()
-
-
 def case_bitid():
     """a training handle and a render handle with the same parameters, encoding and coordinates, on every shape"""
     from implicit_image import decode as dec
@@ -46,7 +31,7 @@ def case_bitid():
     rows = []
     for ((hid, ms), nl, (H, W), chunk) in shapes():
         gen = torch.Generator().manual_seed(1000 * hid + 10 * ms + nl)
-        flat = random_params(hid, nl, ms, gen).cuda()
+        flat = fourier_params(hid, nl, ms, gen).cuda()
         B = (torch.randn(2, ms // 2, generator=gen) * MAP_SCALE).cuda()
         gh, gw = torch.linspace(0, 1, H).cuda(), torch.linspace(0, 1, W).cuda()
         tr = FourierEngine(H, W, hid, nl, ms, chunk_pixels=chunk)
@@ -57,11 +42,10 @@ def case_bitid():
             e.set_coords(gh, gw)
         ref, _ = tr.forward(want_pred=True, want_sse=False)
         # both outputs, the byte buffer followed by a 16-byte guard
-        nbytes = H * W * 3
-        buf = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+        buf = Guarded(H * W * 3, 8, GUARD)
         pred = torch.full((H, W, 3), float("nan"), device="cuda")
-        rc = lib.sf_render(rn.h, buf.data_ptr(), pred.data_ptr())
-        u8 = buf[:nbytes].reshape(H, W, 3)
+        rc = lib.sf_render(rn.h, buf.ptr(), pred.data_ptr())
+        u8 = buf.samples((H, W, 3))
         u8_only, _ = rn.render(want_u8=True, want_pred=False)
         _, pred_only = rn.render(want_u8=False, want_pred=True)
         u8_tr, pred_tr = tr.render(want_u8=True, want_pred=True)         # the same kernel on the training handle
@@ -71,7 +55,7 @@ def case_bitid():
                          pred_equal=bool(torch.equal(pred, ref)), u8_equal=bool(torch.equal(u8, dec.to_u8(ref))),
                          u8_only_equal=bool(torch.equal(u8_only, u8)), pred_only_equal=bool(torch.equal(pred_only, ref)),
                          train_pred_equal=bool(torch.equal(pred_tr, ref)), train_u8_equal=bool(torch.equal(u8_tr, u8)),
-                         guard_intact=bool((buf[nbytes:] == 0xA5).all()),
+                         guard_intact=buf.guard_intact(),
                          levels=int(u8.unique().numel()), pmin=float(ref.min()), pmax=float(ref.max())))
         tr.close()
         rn.close()
@@ -110,13 +94,7 @@ def case_refuse():
     import ctypes as C
     from implicit_image import _engine as E
     lib = E.load_library()
-    out = {}
-
-    def rec(name, rc):
-        out[name] = {"rc": int(rc), "msg": lib.sf_last_error().decode() if rc else ""}
-
-    def launches(eng):
-        return int(sum(v["launches"] for v in eng.profile_report().values()))
+    out, rec = recorder(lib)
     H = W = 64
     u8 = torch.zeros(H * W * 3 + 4, dtype=torch.uint8, device="cuda")
     lin = torch.linspace(0, 1, 64).cuda()
@@ -138,40 +116,10 @@ def case_refuse():
     rec("sf_render_both_null", lib.sf_render(eng.h, None, None))
     rec("sf_render_misaligned", lib.sf_render(eng.h, u8.data_ptr() + 1, None))
     rec("sf_wavelet_render", lib.sf_wavelet_render(eng.h, 0, 64, 0, 64, u8.data_ptr(), None))
-    # the training entry points (tests/test_gpu_render.py: TRAINING_CALLS)
     buf = torch.zeros(eng.num_params, device="cuda")
-    lr = (C.c_float * 1)(1e-3)
-    sse = C.c_double()
-    step = C.c_int64()
-    p, n = C.c_void_p(), C.c_int64()
-    li = (C.c_int32 * 4)(64, 64, 64, 3)
-    rec("sf_forward_backward", lib.sf_forward_backward(eng.h, C.byref(sse)))
-    rec("sf_forward", lib.sf_forward(eng.h, None, None))
-    rec("sf_step", lib.sf_step(eng.h, lr, 1, None))
-    rec("sf_adam_step", lib.sf_adam_step(eng.h, 1e-3))
-    rec("sf_set_masks", lib.sf_set_masks(eng.h, buf.data_ptr()))
-    rec("sf_get_grads", lib.sf_get_grads(eng.h, buf.data_ptr()))
-    rec("sf_set_grads", lib.sf_set_grads(eng.h, buf.data_ptr()))
-    rec("sf_get_adam_state", lib.sf_get_adam_state(eng.h, buf.data_ptr(), buf.data_ptr(), C.byref(step)))
-    rec("sf_set_adam_state", lib.sf_set_adam_state(eng.h, buf.data_ptr(), buf.data_ptr(), 0))
-    rec("sf_kmeans_fit", lib.sf_kmeans_fit(eng.h, buf.data_ptr(), 16, buf.data_ptr(), 3, 1, 1e-4, buf.data_ptr(), 4, None, None, None))
-    rec("sf_feather_attach", lib.sf_feather_attach(eng.h, 8, 8, 3, li, li))
-    rec("sf_feather_state_ptr", lib.sf_feather_state_ptr(eng.h, 0, C.byref(p), C.byref(n)))
-    rec("sf_feather_materialise", lib.sf_feather_materialise(eng.h))
-    rec("sf_feather_adjoint", lib.sf_feather_adjoint(eng.h))
-    rec("sf_debug_scratch", lib.sf_debug_scratch(eng.h, 0, C.byref(p), C.byref(n)))
-    rec("sf_state_ptr_grads", lib.sf_state_ptr(eng.h, 1, C.byref(p)))
-    rec("sf_set_target", lib.sf_set_target(eng.h, buf.data_ptr()))
+    refused_training_calls(rec, lib, eng, buf, feather_layers=3, render_to=None, set_target=True)
     out["launches_state_b"] = launches(eng)
-    # what must keep working
-    rec("ok_sf_state_ptr_params", lib.sf_state_ptr(eng.h, 0, C.byref(p)))
-    rec("ok_sf_set_params", lib.sf_set_params(eng.h, buf.data_ptr()))
-    rec("ok_sf_get_params", lib.sf_get_params(eng.h, buf.data_ptr()))
-    rec("ok_sf_params_changed", lib.sf_params_changed(eng.h))
-    rec("ok_sf_num_params", lib.sf_num_params(eng.h, C.byref(n)))
-    out["num_params"] = int(n.value)
-    w, b = C.c_int64(), C.c_int64()
-    rec("ok_sf_param_offset", lib.sf_param_offset(eng.h, 1, C.byref(w), C.byref(b)))
+    out["num_params"] = working_calls(rec, lib, eng, buf, offset_layer=1, set_and_count=True)[2]
     rec("ok_sf_render", lib.sf_render(eng.h, u8.data_ptr(), None))
     rep = eng.profile_report()
     out["k_ff_render_launches"] = int(rep["k_ff_render"]["launches"])
@@ -199,17 +147,11 @@ MEM = dict(height=1024, width=1024, hidden=128, n_linear=7, map_size=256)
 
 
 def case_mem(kind):
-    """device memory one 128 x 7-Linear, map 256 handle at 1024x1024 takes (fresh process: nothing else allocates in between)"""
+    """device memory one 128 x 7-Linear, map 256 handle at 1024x1024 takes"""
     from implicit_image._engine import FourierEngine, FourierRenderEngine
-    torch.cuda.init()
-    torch.zeros(1, device="cuda")
-    torch.cuda.synchronize()
-    free0, _ = torch.cuda.mem_get_info()
-    eng = (FourierRenderEngine if kind == "render" else FourierEngine)(**MEM)
-    torch.cuda.synchronize()
-    free1, _ = torch.cuda.mem_get_info()
+    taken, eng = handle_memory(lambda: (FourierRenderEngine if kind == "render" else FourierEngine)(**MEM))
     eng.close()
-    return {"taken": int(free0 - free1)}
+    return {"taken": taken}
 
 
 def case_e2e(workdir):
@@ -250,17 +192,5 @@ def case_e2e(workdir):
     return out
 
 
-def main():
-    case, out = sys.argv[1], sys.argv[2]
-    if case in ("mem_train", "mem_render"):
-        res = case_mem(case[4:])
-    elif case == "e2e":
-        res = case_e2e(sys.argv[3])
-    else:
-        res = {"bitid": case_bitid, "windows": case_windows, "refuse": case_refuse}[case]()
-    json.dump(res, open(out, "w"), indent=1)
-    print(json.dumps(res)[:6000])
-
-
 if __name__ == "__main__":
-    main()
+    child_main({"bitid": case_bitid, "windows": case_windows, "refuse": case_refuse, "mem": case_mem, "e2e": case_e2e})

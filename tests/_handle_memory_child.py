@@ -1,17 +1,9 @@
 """Child of tests/test_gpu_handle_memory.py: every creator's handle is built, used and destroyed in ONE fresh process, and
-the device memory free before each create is compared with what is free after that handle's destroy (the parent runs this
-under a time limit and reads the JSON it writes).  Usage: _handle_memory_child.py OUT.json"""
-import json
-import os
-import sys
+the device memory free before each create is compared with what is free after that handle's destroy."""
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
-
-import torch  # noqa: E402
-
-from oracle import siren_oracle as so  # noqa: E402
+from _gpu_child import child_main
+from oracle import siren_oracle as so
 
 LR = [3e-4, 3e-4]
 
@@ -145,8 +137,7 @@ CASES = [("sf_create", use_siren), ("sf_create+sf_feather_attach", use_feather),
          ("sf_wavelet_create", use_wavelet), ("sf_render_create", use_render), ("sf_wavelet_render_create", use_wavelet_render)]
 
 
-def main():
-    out = sys.argv[1]
+def case_handle_memory():
     torch.cuda.init()
     torch.zeros(1, device="cuda")
     rows = []
@@ -157,8 +148,8 @@ def main():
             free0, free1, info = fn()
             rows.append(dict(round=rnd, creator=name, free_before=free0, free_after=free1, shortfall=free0 - free1, **info))
             print(rows[-1], flush=True)
-    json.dump({"cases": rows}, open(out, "w"), indent=1)
+    return {"cases": rows}
 
 
 if __name__ == "__main__":
-    main()
+    child_main({"handle_memory": case_handle_memory})

@@ -3,24 +3,15 @@ fresh process; per case the per-kernel launch counts with their flops / bytes fi
 sha256 of the gradient or of the rendered bytes go into the JSON the parent reads.  One more case runs with profiling off
 (graph replay needs that): sf_step on a WaveletSiren handle, eagerly and replayed, whose sub-handles launch through the
 handle's own launch context - on the capturing stream while a step is captured.
-Usage: _launch_plan_child.py OUT.json        (SIREN_FIT_LIB=<another build> records that build's plan)"""
-import hashlib
-import json
+(SIREN_FIT_LIB=<another build> records that build's plan)"""
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import torch
 
-import torch  # noqa: E402
-
-from implicit_image import _engine as E  # noqa: E402
-from oracle import siren_oracle as so  # noqa: E402
-
-
-def sha(t):
-    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+from _gpu_child import child_main
+from _gpu_fixtures import sha
+from implicit_image import _engine as E
+from oracle import siren_oracle as so
 
 
 def plan(eng):
@@ -165,7 +156,7 @@ def cases():
     return out
 
 
-def main():
+def case_launch_plan():
     torch.cuda.init()
     torch.zeros(1, device="cuda")
     res = {}
@@ -174,8 +165,8 @@ def main():
         print(name, res[name]["sha256"][:12], flush=True)
     step = wavelet_step()
     print("wavelet_step", step["eager"]["sha256_params"][:12], step["replay"]["sha256_params"][:12], flush=True)
-    json.dump({"lib": os.path.basename(E._LIB_PATH), "cases": res, "wavelet_step": step}, open(sys.argv[1], "w"), indent=1, sort_keys=True)
+    return {"lib": os.path.basename(E._LIB_PATH), "cases": res, "wavelet_step": step}
 
 
 if __name__ == "__main__":
-    main()
+    child_main({"launch_plan": case_launch_plan})

@@ -1,23 +1,21 @@
 """Child of tests/test_gpu_host_state.py::test_pixel_split_two_real_engines: one rank of a two-rank pixel-split fit with a
 REAL SirenEngine (row shard) on cuda:0, gloo collectives (RCCL refuses two ranks on one device).  RANK / WORLD_SIZE /
-MASTER_* come from the environment and are set before anything touches the GPU.  Writes {losses, params sha256, grads}."""
+MASTER_* come from the environment and are set before anything touches the GPU.  Writes {losses, params sha256, grads}
+to r<RANK>.json in the directory it is given."""
 import hashlib
 import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
-    sys.path.insert(0, p)
+import torch
+import torch.distributed as dist
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.distributed as dist  # noqa: E402
+import _gpu_child  # noqa: F401  (the repository root and the package directory on sys.path)
 
 
 def main():
-    out = sys.argv[1]
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    out = os.path.join(sys.argv[1], f"r{rank}.json")
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from implicit_image._engine import SirenEngine
     from implicit_image.parallel import PixelSplitFit, shard_rows

@@ -1,53 +1,17 @@
-"""Child of tests/test_gpu_render16.py: one 16-bit render GPU case per process (the parent runs it under a time limit and
-reads the JSON it writes).  Usage: _render16_child.py CASE OUT.json [WORKDIR]"""
+"""Child of tests/test_gpu_render16.py: one 16-bit render GPU case per process."""
 import itertools
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import torch
 
-import torch  # noqa: E402
-
-from oracle import siren_oracle as so  # noqa: E402
+from _gpu_child import ROOT, child_main
+from _gpu_fixtures import Guarded, fourier_params, launches, recorder, siren_params, u8_ref, u16_ref, wavelet_params
+from oracle import siren_oracle as so
 
 FORMS = [(32, 2), (256, 2), (256, 3)]                # k_fwd<32>, k_fwd<256>, k_fwd_pipe
 PICTURES = [(1, 1), (5, 7), (33, 31), (64, 64)]      # 5x7: a ragged block, an odd sample count at out_features 1 and 3
 CHUNKS = (0, 256)
 GUARD = 64                                           # sentinel bytes behind every sample buffer
-FILL = 0xA5
-
-
-def u16_ref(pred):
-    """min(max(trunc(pred * 65535), 0), 65535) as int32, written out independently of implicit_image.decode.to_u16"""
-    q = torch.trunc(pred.float() * 65535.0)
-    return torch.minimum(torch.maximum(q, torch.zeros_like(q)), torch.full_like(q, 65535.0)).to(torch.int32)
-
-
-def u8_ref(pred):
-    q = torch.trunc(pred.float() * 255.0)
-    return torch.minimum(torch.maximum(q, torch.zeros_like(q)), torch.full_like(q, 255.0)).to(torch.uint8)
-
-
-class Out16:
-    """a device buffer of n 16-bit samples followed by GUARD sentinel bytes (torch.empty is 4-byte aligned and more)"""
-
-    def __init__(self, n):
-        self.n = n
-        self.buf = torch.full((2 * n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-        assert self.buf.data_ptr() % 4 == 0
-
-    def ptr(self):
-        return self.buf.data_ptr()
-
-    def samples(self, shape):
-        """the samples widened to int32 (through int16: every torch build converts that type on the device)"""
-        return (self.buf[:2 * self.n].view(torch.int16).to(torch.int32) & 0xFFFF).reshape(shape)
-
-    def guard_intact(self):
-        return bool((self.buf[2 * self.n:] == FILL).all())
 
 
 def check16(call16, call8, shape):
@@ -55,38 +19,31 @@ def check16(call16, call8, shape):
     call8(bytes_ptr, pred_ptr) are the two entry points on that handle."""
     from implicit_image.decode import to_u8, to_u16
     n = shape[0] * shape[1] * shape[2]
-    both, alone = Out16(n), Out16(n)
+    both, alone = Guarded(n, 16, GUARD), Guarded(n, 16, GUARD)
     pred16 = torch.full(shape, float("nan"), device="cuda")
     pred8 = torch.full(shape, float("nan"), device="cuda")
-    u8 = torch.full((n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    u8_after = torch.full((n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    rcs = [call8(u8.data_ptr(), pred8.data_ptr()), call16(both.ptr(), pred16.data_ptr()), call16(alone.ptr(), None),
-           call8(u8_after.data_ptr(), None)]
+    u8, u8_after = Guarded(n, 8, GUARD), Guarded(n, 8, GUARD)
+    rcs = [call8(u8.ptr(), pred8.data_ptr()), call16(both.ptr(), pred16.data_ptr()), call16(alone.ptr(), None),
+           call8(u8_after.ptr(), None)]
     torch.cuda.synchronize()
-    s = both.samples(shape)
+    s, after = both.samples(shape), u8_after.samples(shape)
     return dict(rc=[int(r) for r in rcs], finite=bool(torch.isfinite(pred16).all()),
                 equals_to_u16=bool(torch.equal(s, to_u16(pred16))), equals_formula=bool(torch.equal(s, u16_ref(pred16))),
                 alone_equal=bool(torch.equal(alone.samples(shape), s)),
                 pred_bit_identical=bool(torch.equal(pred16.view(torch.int32), pred8.view(torch.int32))),
                 guard_intact=both.guard_intact() and alone.guard_intact(),
-                u8_after_equal=bool(torch.equal(u8_after[:n].reshape(shape), to_u8(pred16))
-                                    and torch.equal(u8_after[:n], u8[:n]) and torch.equal(u8_after[:n].reshape(shape), u8_ref(pred16))),
-                u8_guard_intact=bool((u8_after[n:] == FILL).all()),
+                u8_after_equal=bool(torch.equal(after, to_u8(pred16)) and torch.equal(after, u8.samples(shape))
+                                    and torch.equal(after, u8_ref(pred16))),
+                u8_guard_intact=u8_after.guard_intact(),
                 levels=int(s.unique().numel()), lo=int((s == 0).sum()), hi=int((s == 65535).sum()))
-
-
-def siren_flat(hidden, depth, nout, seed, last_scale):
-    p = so.siren_init(hidden, depth, seed=seed)
-    # zero output bias and a scaled output layer: 0.5 + 0.5 * scale * (W h) leaves [0, 1] on both sides (a linear last layer)
-    p[-2], p[-1] = p[-2][:nout] * last_scale, p[-1][:nout] * 0.0
-    return torch.tensor(so.flatten(p))
 
 
 def case_siren():
     from implicit_image._engine import RenderEngine, SirenEngine
     rows = []
     for (hid, dep), nout, lin, (H, W), chunk in itertools.product(FORMS, (1, 2, 3), (True, False), PICTURES, CHUNKS):
-        flat = siren_flat(hid, dep, nout, seed=hid + dep, last_scale=40.0).cuda()
+        # zero output bias and a scaled output layer: 0.5 + 0.5 * scale * (W h) leaves [0, 1] on both sides (a linear last layer)
+        flat = siren_params(hid, dep, nout, seed=hid + dep, last_scale=40.0, bias_scale=0.0).cuda()
         gh, gw = so.grid_vectors(H, W)
         for kind, cls in (("render", RenderEngine), ("train", SirenEngine)):
             eng = cls(H, W, hid, dep, outermost_linear=lin, out_features=nout, chunk_pixels=chunk)
@@ -103,17 +60,6 @@ def case_siren():
             rows.append(row)
             eng.close()
     return {"cases": rows}
-
-
-def fourier_params(hidden, n_linear, map_size, gen):
-    """seeded uniform weights of He scale, small biases, the output layer four times larger: the sigmoid spreads over levels"""
-    parts = []
-    for l in range(n_linear):
-        fin = map_size if l == 0 else hidden
-        fout = 3 if l == n_linear - 1 else hidden
-        scale = (6.0 / fin) ** 0.5 * (4.0 if l == n_linear - 1 else 1.0)
-        parts += [((torch.rand(fout * fin, generator=gen) * 2 - 1) * scale), (torch.rand(fout, generator=gen) * 2 - 1) * 0.1]
-    return torch.cat(parts).float().contiguous()
 
 
 def case_fourier():
@@ -151,22 +97,12 @@ WAVELET_WINDOWS = {
 }
 
 
-def wavelet_flat(last_scale, seed, **kw):
-    from implicit_image.models import registry
-    torch.manual_seed(seed)
-    m = registry["wavelet_siren"](**kw)
-    with torch.no_grad():
-        for sub in (m.LF_siren, m.HF_siren):
-            sub.layers[-1].linear.weight.mul_(last_scale)
-            sub.layers[-1].linear.bias.zero_()
-    return torch.cat([p.data.reshape(-1).float() for p in m._param_list()]).contiguous()
-
-
 def case_wavelet():
     from implicit_image._engine import WaveletEngine, WaveletRenderEngine
     rows = []
     for (hid, dep), H in itertools.product(((32, 2), (256, 3)), sorted(WAVELET_WINDOWS)):
-        flat = wavelet_flat(400.0, seed=hid + dep, depth=dep, hidden_size=hid, first_omega_0=50.0, hidden_omega_0=30.0).cuda()
+        flat = wavelet_params(400.0, seed=hid + dep, rescale=True, depth=dep, hidden_size=hid, first_omega_0=50.0,
+                              hidden_omega_0=30.0).cuda()
         tr = WaveletEngine(H, H, hid, dep, 50.0, 30.0, True)
         rn = WaveletRenderEngine(H, hid, dep, 50.0, 30.0, True)
         lin_v = torch.linspace(0, 1, tr.n).cuda()
@@ -192,13 +128,7 @@ def case_refuse():
     """argument and state checks only: every call below returns an error code before anything reaches the device"""
     from implicit_image import _engine as E
     lib = E.load_library()
-    out = {}
-
-    def rec(name, rc):
-        out[name] = {"rc": int(rc), "msg": lib.sf_last_error().decode() if rc else ""}
-
-    def launches(eng):
-        return int(sum(v["launches"] for v in eng.profile_report().values()))
+    out, rec = recorder(lib)
     buf = torch.zeros(64 * 64 * 3 * 2 + 8, dtype=torch.uint8, device="cuda")
     ptr = buf.data_ptr()
     lin = torch.linspace(0, 1, 64).cuda()
@@ -324,15 +254,5 @@ def case_e2e(workdir):
     return out
 
 
-def main():
-    case, out = sys.argv[1], sys.argv[2]
-    if case == "e2e":
-        res = case_e2e(sys.argv[3])
-    else:
-        res = {"siren": case_siren, "fourier": case_fourier, "wavelet": case_wavelet, "refuse": case_refuse}[case]()
-    json.dump(res, open(out, "w"), indent=1)
-    print(json.dumps(res)[:6000])
-
-
 if __name__ == "__main__":
-    main()
+    child_main({"siren": case_siren, "fourier": case_fourier, "wavelet": case_wavelet, "refuse": case_refuse, "e2e": case_e2e})

@@ -1,38 +1,15 @@
-"""Child of tests/test_gpu_render.py: one render-path GPU case per process (the parent runs it under a time limit and
-reads the JSON it writes).  Usage: _render_child.py CASE OUT.json [WORKDIR]"""
+"""Child of tests/test_gpu_render.py: one render-path GPU case per process."""
 import itertools
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from oracle import siren_oracle as so  # noqa: E402
+from _gpu_child import ROOT, child_main
+from _gpu_fixtures import golden, handle_memory, recorder, refused_training_calls, siren_params, u8_ref, working_calls
+from oracle import siren_oracle as so
 
 SHAPES = [(32, 3), (64, 4), (128, 6), (256, 8), (256, 2)]
 SIZES = [(67, 45, 0), (256, 256, 0), (1031, 517, 65536)]      # (H, W, chunk_pixels): ragged last group; several chunks
-
-
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"), allow_pickle=False)
-
-
-def u8_ref(pred):
-    """min(max(trunc(pred * 255), 0), 255), written out independently of implicit_image.decode.to_u8"""
-    q = torch.trunc(pred.float() * 255.0)
-    return torch.minimum(torch.maximum(q, torch.zeros_like(q)), torch.full_like(q, 255.0)).to(torch.uint8)
-
-
-def init_flat(hidden, depth, nout, seed, last_scale=1.0):
-    p = so.siren_init(hidden, depth, seed=seed)
-    # (scaled set: zero output bias, so that 0.5 + 0.5 * scale * (W h) swings to both sides of [0, 1] in every channel)
-    p[-2], p[-1] = p[-2][:nout] * last_scale, p[-1][:nout] * (1.0 if last_scale == 1.0 else 0.0)
-    return torch.tensor(so.flatten(p))
 
 
 def case_bitid():
@@ -48,7 +25,9 @@ def case_bitid():
         for e in (tr, rn):
             e.set_coords(gh.cuda(), gw.cuda())
         for scale in (1.0, 400.0):
-            flat = init_flat(hid, dep, nout, seed=hid + dep, last_scale=scale).cuda()
+            # (scaled set: zero output bias, so that 0.5 + 0.5 * scale * (W h) swings to both sides of [0, 1] in every channel)
+            flat = siren_params(hid, dep, nout, seed=hid + dep, last_scale=scale,
+                                bias_scale=1.0 if scale == 1.0 else 0.0).cuda()
             tr.set_params(flat)
             rn.set_params(flat)
             ref, _ = tr.forward(want_pred=True, want_sse=False)
@@ -115,38 +94,10 @@ def case_refuse():
     lib = E.load_library()
     eng = E.RenderEngine(64, 64, 64, 4)
     buf = torch.zeros(eng.num_params, device="cuda")
-    out = {}
-
-    def rec(name, rc):
-        out[name] = {"rc": int(rc), "msg": lib.sf_last_error().decode() if rc else ""}
-    lr = (C.c_float * 1)(1e-3)
-    sse = C.c_double()
-    step = C.c_int64()
-    p, n = C.c_void_p(), C.c_int64()
-    li = (C.c_int32 * 4)(64, 64, 64, 3)
-    rec("sf_forward_backward", lib.sf_forward_backward(eng.h, C.byref(sse)))
-    rec("sf_forward", lib.sf_forward(eng.h, None, None))
-    rec("sf_step", lib.sf_step(eng.h, lr, 1, None))
-    rec("sf_adam_step", lib.sf_adam_step(eng.h, 1e-3))
-    rec("sf_set_masks", lib.sf_set_masks(eng.h, buf.data_ptr()))
-    rec("sf_get_grads", lib.sf_get_grads(eng.h, buf.data_ptr()))
-    rec("sf_set_grads", lib.sf_set_grads(eng.h, buf.data_ptr()))
-    rec("sf_get_adam_state", lib.sf_get_adam_state(eng.h, buf.data_ptr(), buf.data_ptr(), C.byref(step)))
-    rec("sf_set_adam_state", lib.sf_set_adam_state(eng.h, buf.data_ptr(), buf.data_ptr(), 0))
-    rec("sf_kmeans_fit", lib.sf_kmeans_fit(eng.h, buf.data_ptr(), 16, buf.data_ptr(), 3, 1, 1e-4, buf.data_ptr(), 4, None, None, None))
-    rec("sf_feather_attach", lib.sf_feather_attach(eng.h, 8, 8, 4, li, li))
-    rec("sf_feather_state_ptr", lib.sf_feather_state_ptr(eng.h, 0, C.byref(p), C.byref(n)))
-    rec("sf_feather_materialise", lib.sf_feather_materialise(eng.h))
-    rec("sf_feather_adjoint", lib.sf_feather_adjoint(eng.h))
-    rec("sf_debug_scratch", lib.sf_debug_scratch(eng.h, 0, C.byref(p), C.byref(n)))
-    rec("sf_state_ptr_grads", lib.sf_state_ptr(eng.h, 1, C.byref(p)))
+    out, rec = recorder(lib)
+    refused_training_calls(rec, lib, eng, buf, feather_layers=4, render_to=None, set_target=False)
     rec("sf_render_both_null", lib.sf_render(eng.h, None, None))
-    # what must keep working
-    rec("ok_sf_state_ptr_params", lib.sf_state_ptr(eng.h, 0, C.byref(p)))
-    rec("ok_sf_get_params", lib.sf_get_params(eng.h, buf.data_ptr()))
-    rec("ok_sf_params_changed", lib.sf_params_changed(eng.h))
-    w, b = C.c_int64(), C.c_int64()
-    rec("ok_sf_param_offset", lib.sf_param_offset(eng.h, 1, C.byref(w), C.byref(b)))
+    working_calls(rec, lib, eng, buf, offset_layer=1, set_and_count=False)
     rec("ok_sf_profile_enable", lib.sf_profile_enable(eng.h, 0))
     eng.close()
     cfg = E.sf_config(E.SF_ABI_VERSION, 64, 64, 0, 0, 2, 3, 512, 4, 50.0, 30.0, 1, 1, 0.9, 0.999, 1e-8, 0, None, 0, 0)
@@ -158,16 +109,10 @@ def case_refuse():
 
 
 def case_mem(kind):
-    """device memory one 256x8 handle at 2048x2048 takes (fresh process: nothing else allocates in between)"""
+    """device memory one 256x8 handle at 2048x2048 takes"""
     from implicit_image._engine import RenderEngine, SirenEngine
-    torch.cuda.init()
-    torch.zeros(1, device="cuda")
-    torch.cuda.synchronize()
-    free0, _ = torch.cuda.mem_get_info()
-    eng = (RenderEngine if kind == "render" else SirenEngine)(2048, 2048, 256, 8)
-    torch.cuda.synchronize()
-    free1, _ = torch.cuda.mem_get_info()
-    out = {"taken": int(free0 - free1)}
+    taken, eng = handle_memory(lambda: (RenderEngine if kind == "render" else SirenEngine)(2048, 2048, 256, 8))
+    out = {"taken": taken}
     if kind == "train":
         out["scratch"] = {k: int(eng.debug_scratch(k).numel()) for k in ("phases", "deltas", "dlast")}
     eng.close()
@@ -228,17 +173,6 @@ def case_e2e(workdir):
     return out
 
 
-def main():
-    case, out = sys.argv[1], sys.argv[2]
-    if case in ("mem_train", "mem_render"):
-        res = case_mem(case[4:])
-    elif case == "e2e":
-        res = case_e2e(sys.argv[3])
-    else:
-        res = {"bitid": case_bitid, "oracle": case_oracle, "windows": case_windows, "refuse": case_refuse}[case]()
-    json.dump(res, open(out, "w"), indent=1)
-    print(json.dumps(res)[:3000])
-
-
 if __name__ == "__main__":
-    main()
+    child_main({"bitid": case_bitid, "oracle": case_oracle, "windows": case_windows, "refuse": case_refuse, "mem": case_mem,
+                "e2e": case_e2e})

@@ -1,37 +1,23 @@
-"""Child of tests/test_gpu_wavelet.py: one WaveletSiren GPU case per process (the parent runs it under a time limit and
-reads the JSON it writes).  Usage: _wavelet_child.py CASE OUT.json [WORKDIR]"""
-import json
+"""Child of tests/test_gpu_wavelet.py: one WaveletSiren GPU case per process."""
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
+import torch
+import torch.nn.functional as F
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import _wavelet_ref as wr  # noqa: E402
-from oracle import siren_oracle as so  # noqa: E402  (test infrastructure: grid and image formulas)
+from _gpu_child import ROOT, child_main
+from _gpu_fixtures import golden, relerr
+import _wavelet_ref as wr
+from oracle import siren_oracle as so  # (test infrastructure: grid and image formulas)
 
 SMALL = dict(depth=4, hidden_size=64, first_omega_0=50.0, hidden_omega_0=30.0)
 YAML = dict(depth=8, hidden_size=128, wavelet_levels=1, first_omega_0=50.0, hidden_omega_0=30.0, outermost_linear=True)
-
-
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"), allow_pickle=False)
 
 
 def model(seed=0, **kw):
     from implicit_image.models import registry
     torch.manual_seed(seed)
     return registry["wavelet_siren"](**kw).cuda()
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def case_kernels():
@@ -212,8 +198,5 @@ def case_fit(workdir):
 
 
 if __name__ == "__main__":
-    case, out_path = sys.argv[1], sys.argv[2]
-    fn = globals()["case_" + case]
-    res = fn(sys.argv[3]) if case == "fit" else fn()
-    with open(out_path, "w") as f:
-        json.dump(res, f)
+    child_main({"kernels": case_kernels, "parity": case_parity, "traj": case_traj, "steps": case_steps, "chunk": case_chunk,
+                "padded": case_padded, "plateau": case_plateau, "fit": case_fit})

@@ -1,15 +1,11 @@
-"""Child of tests/test_gpu_wavelet_render.py: one WaveletSiren render-path GPU case per process (the parent runs it under a
-time limit and reads the JSON it writes).  Usage: _wavelet_render_child.py CASE OUT.json [WORKDIR]"""
-import json
+"""Child of tests/test_gpu_wavelet_render.py: one WaveletSiren render-path GPU case per process."""
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from _gpu_child import ROOT, child_main
+from _gpu_fixtures import (golden, handle_memory, launches, recorder, refused_training_calls, u8_ref, wavelet_params,
+                           working_calls)
 
 # (hidden, depth, outermost_linear, first_omega_0, hidden_omega_0, H, chunk_pixels): every forward kernel - k_fwd<32 | 64 |
 # 128 | 256> and k_fwd_pipe (256, depth >= 3) - depths 2 / 3 / 8 / 16, both output layers, both omegas, the smallest
@@ -33,30 +29,6 @@ SMALL = dict(depth=4, hidden_size=64, first_omega_0=50.0, hidden_omega_0=30.0)
 YAML = dict(depth=8, hidden_size=128, wavelet_levels=1, first_omega_0=50.0, hidden_omega_0=30.0, outermost_linear=True)
 
 
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"), allow_pickle=False)
-
-
-def u8_ref(pred):
-    """min(max(trunc(pred * 255), 0), 255), written out independently of implicit_image.decode.to_u8"""
-    q = torch.trunc(pred.float() * 255.0)
-    return torch.minimum(torch.maximum(q, torch.zeros_like(q)), torch.full_like(q, 255.0)).to(torch.uint8)
-
-
-def init_flat(last_scale=1.0, seed=0, **kw):
-    """[LF | HF] of a seed-`seed` registry model (kernel widths: no padding); last_scale != 1 scales both output layers
-    and zeroes their biases, so that the coefficients - and with them the picture - swing to both sides of [0, 1]"""
-    from implicit_image.models import registry
-    torch.manual_seed(seed)
-    m = registry["wavelet_siren"](**kw)
-    with torch.no_grad():
-        if last_scale != 1.0:
-            for sub in (m.LF_siren, m.HF_siren):
-                sub.layers[-1].linear.weight.mul_(last_scale)
-                sub.layers[-1].linear.bias.zero_()
-    return torch.cat([p.data.reshape(-1).float() for p in m._param_list()]).contiguous()
-
-
 def engines(hid, dep, lin, fo, ho, H, chunk, **rkw):
     from implicit_image._engine import WaveletEngine, WaveletRenderEngine
     tr = WaveletEngine(H, H, hid, dep, fo, ho, lin, chunk_pixels=chunk)
@@ -75,8 +47,8 @@ def case_bitid():
     for hid, dep, lin, fo, ho, H, chunk in BITID:
         tr, rn = engines(hid, dep, lin, fo, ho, H, chunk)
         for scale in (1.0, 400.0):
-            flat = init_flat(scale, seed=hid + dep, depth=dep, hidden_size=hid, first_omega_0=fo, hidden_omega_0=ho,
-                             outermost_linear=lin).cuda()
+            flat = wavelet_params(scale, seed=hid + dep, rescale=scale != 1.0, depth=dep, hidden_size=hid, first_omega_0=fo,
+                                  hidden_omega_0=ho, outermost_linear=lin).cuda()
             tr.set_params(flat)
             rn.set_params(flat)
             ref, _ = tr.forward(want_pred=True, want_sse=False)
@@ -107,7 +79,8 @@ def case_ragged():
     for H, wins in ((10, [(2, 7, 1, 8), (0, 1, 0, 1), (9, 10, 3, 10), (0, 10, 0, 10), (3, 6, 0, 3)]),
                     (64, [(5, 28, 7, 30), (0, 64, 0, 63), (63, 64, 0, 64), (1, 64, 1, 64)])):
         tr, rn = engines(64, 3, True, 50.0, 30.0, H, 0)
-        flat = init_flat(400.0, seed=3, depth=3, hidden_size=64, first_omega_0=50.0, hidden_omega_0=30.0).cuda()
+        flat = wavelet_params(400.0, seed=3, rescale=True, depth=3, hidden_size=64, first_omega_0=50.0,
+                              hidden_omega_0=30.0).cuda()
         tr.set_params(flat)
         rn.set_params(flat)
         full, _ = tr.forward(want_pred=True, want_sse=False)
@@ -140,7 +113,8 @@ def case_windows():
     out = {"windows": []}
     for (hid, dep, H) in ((64, 4, 128), (256, 3, 250), (64, 3, 10)):
         tr, rn = engines(hid, dep, True, 50.0, 30.0, H, 0)
-        flat = init_flat(1.0, seed=1, depth=dep, hidden_size=hid, first_omega_0=50.0, hidden_omega_0=30.0).cuda()
+        flat = wavelet_params(1.0, seed=1, rescale=False, depth=dep, hidden_size=hid, first_omega_0=50.0,
+                              hidden_omega_0=30.0).cuda()
         rn.set_params(flat)
         tr.set_params(flat)
         fu8, fpred = rn.render(want_u8=True, want_pred=True)
@@ -193,7 +167,7 @@ def case_reference():
     g = golden("wavelet_grads")
     out = {}
     for tag, kw in (("small", SMALL), ("yaml", YAML)):
-        flat = init_flat(1.0, seed=0, **kw).cuda()
+        flat = wavelet_params(1.0, seed=0, rescale=False, **kw).cuda()
         eng = WaveletRenderEngine(64, kw["hidden_size"], kw["depth"], kw["first_omega_0"], kw["hidden_omega_0"], True)
         lin_v = torch.linspace(0, 1, eng.n).cuda()
         eng.set_coords(lin_v, lin_v)
@@ -215,37 +189,12 @@ def case_refuse():
     eng = E.WaveletRenderEngine(64, 64, 4)
     buf = torch.zeros(eng.num_params, device="cuda")
     u8 = torch.zeros(64 * 64 * 3 + 8, dtype=torch.uint8, device="cuda")
-    out = {}
-
-    def rec(name, rc):
-        out[name] = {"rc": int(rc), "msg": lib.sf_last_error().decode() if rc else ""}
+    out, rec = recorder(lib)
     eng.profile(True)
     rec("before_set_coords", lib.sf_wavelet_render(eng.h, 0, 64, 0, 64, u8.data_ptr(), None))
     lin_v = torch.linspace(0, 1, eng.n).cuda()
     rec("ok_sf_set_coords", lib.sf_set_coords(eng.h, lin_v.data_ptr(), lin_v.data_ptr()))
-    lr = (C.c_float * 1)(1e-3)
-    sse = C.c_double()
-    step = C.c_int64()
-    p, n = C.c_void_p(), C.c_int64()
-    li = (C.c_int32 * 4)(64, 64, 64, 3)
-    rec("sf_forward_backward", lib.sf_forward_backward(eng.h, C.byref(sse)))
-    rec("sf_forward", lib.sf_forward(eng.h, None, None))
-    rec("sf_step", lib.sf_step(eng.h, lr, 1, None))
-    rec("sf_adam_step", lib.sf_adam_step(eng.h, 1e-3))
-    rec("sf_set_masks", lib.sf_set_masks(eng.h, buf.data_ptr()))
-    rec("sf_get_grads", lib.sf_get_grads(eng.h, buf.data_ptr()))
-    rec("sf_set_grads", lib.sf_set_grads(eng.h, buf.data_ptr()))
-    rec("sf_get_adam_state", lib.sf_get_adam_state(eng.h, buf.data_ptr(), buf.data_ptr(), C.byref(step)))
-    rec("sf_set_adam_state", lib.sf_set_adam_state(eng.h, buf.data_ptr(), buf.data_ptr(), 0))
-    rec("sf_kmeans_fit", lib.sf_kmeans_fit(eng.h, buf.data_ptr(), 16, buf.data_ptr(), 3, 1, 1e-4, buf.data_ptr(), 4, None, None, None))
-    rec("sf_feather_attach", lib.sf_feather_attach(eng.h, 8, 8, 4, li, li))
-    rec("sf_feather_state_ptr", lib.sf_feather_state_ptr(eng.h, 0, C.byref(p), C.byref(n)))
-    rec("sf_feather_materialise", lib.sf_feather_materialise(eng.h))
-    rec("sf_feather_adjoint", lib.sf_feather_adjoint(eng.h))
-    rec("sf_debug_scratch", lib.sf_debug_scratch(eng.h, 0, C.byref(p), C.byref(n)))
-    rec("sf_state_ptr_grads", lib.sf_state_ptr(eng.h, 1, C.byref(p)))
-    rec("sf_render", lib.sf_render(eng.h, u8.data_ptr(), None))
-    rec("sf_set_target", lib.sf_set_target(eng.h, buf.data_ptr()))
+    refused_training_calls(rec, lib, eng, buf, feather_layers=4, render_to=u8.data_ptr(), set_target=True)
     # sf_wavelet_render's own argument checks
     rec("wr_both_null", lib.sf_wavelet_render(eng.h, 0, 64, 0, 64, None, None))
     rec("wr_misaligned", lib.sf_wavelet_render(eng.h, 0, 64, 0, 64, u8.data_ptr() + 1, None))
@@ -260,17 +209,8 @@ def case_refuse():
     fou = E.FourierEngine(64, 64, 64, 3, 64)
     rec("wr_fourier_handle", lib.sf_wavelet_render(fou.h, 0, 64, 0, 64, u8.data_ptr(), None))
     fou.close()
-    rep = eng.profile_report()
-    out["launches_after_refusals"] = int(sum(v["launches"] for v in rep.values()))
-    # what must keep working
-    rec("ok_sf_state_ptr_params", lib.sf_state_ptr(eng.h, 0, C.byref(p)))
-    rec("ok_sf_set_params", lib.sf_set_params(eng.h, buf.data_ptr()))
-    rec("ok_sf_get_params", lib.sf_get_params(eng.h, buf.data_ptr()))
-    rec("ok_sf_params_changed", lib.sf_params_changed(eng.h))
-    rec("ok_sf_num_params", lib.sf_num_params(eng.h, C.byref(n)))
-    w, b = C.c_int64(), C.c_int64()
-    rec("ok_sf_param_offset", lib.sf_param_offset(eng.h, 5, C.byref(w), C.byref(b)))
-    out["param_offset_hf_layer1"] = [int(w.value), int(b.value), int(n.value)]
+    out["launches_after_refusals"] = launches(eng)
+    out["param_offset_hf_layer1"] = working_calls(rec, lib, eng, buf, offset_layer=5, set_and_count=True)
     rec("ok_sf_wavelet_render", lib.sf_wavelet_render(eng.h, 0, 64, 0, 64, u8.data_ptr(), None))
     rep = eng.profile_report()
     out["k_wv_render_launches"] = int(rep["k_wv_render"]["launches"])
@@ -293,16 +233,11 @@ def case_refuse():
 
 
 def case_mem(kind):
-    """device memory one yaml-model (128x8) handle at 2048x2048 takes (fresh process: nothing else allocates in between)"""
+    """device memory one yaml-model (128x8) handle at 2048x2048 takes"""
     from implicit_image._engine import SirenEngine, WaveletEngine, WaveletRenderEngine
-    torch.cuda.init()
-    torch.zeros(1, device="cuda")
-    torch.cuda.synchronize()
-    free0, _ = torch.cuda.mem_get_info()
-    eng = WaveletRenderEngine(2048, 128, 8) if kind == "render" else WaveletEngine(2048, 2048, 128, 8)
-    torch.cuda.synchronize()
-    free1, _ = torch.cuda.mem_get_info()
-    out = {"taken": int(free0 - free1), "n": eng.n}
+    taken, eng = handle_memory(lambda: WaveletRenderEngine(2048, 128, 8) if kind == "render"
+                               else WaveletEngine(2048, 2048, 128, 8))
+    out = {"taken": taken, "n": eng.n}
     eng.close()
     if kind == "train":   # what one sub-network's phase + delta scratch is: a plain SIREN handle of the same grid and format
         sub = SirenEngine(1026, 1026, 128, 8, scratch_format=16)
@@ -365,18 +300,6 @@ def case_e2e(workdir):
     return out
 
 
-def main():
-    case, out = sys.argv[1], sys.argv[2]
-    if case in ("mem_train", "mem_render"):
-        res = case_mem(case[4:])
-    elif case == "e2e":
-        res = case_e2e(sys.argv[3])
-    else:
-        res = {"bitid": case_bitid, "ragged": case_ragged, "windows": case_windows, "reference": case_reference,
-               "refuse": case_refuse}[case]()
-    json.dump(res, open(out, "w"), indent=1)
-    print(json.dumps(res)[:6000])
-
-
 if __name__ == "__main__":
-    main()
+    child_main({"bitid": case_bitid, "ragged": case_ragged, "windows": case_windows, "reference": case_reference,
+                "refuse": case_refuse, "mem": case_mem, "e2e": case_e2e})

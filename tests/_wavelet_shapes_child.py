@@ -1,24 +1,18 @@
 """Child of tests/test_gpu_wavelet_shapes.py: one WaveletSiren GPU case per process, at the widths, depths, output layers,
-omegas, image sizes and chunkings the models of test_gpu_wavelet.py leave out.  The parent runs it under a time limit and
-reads the JSON it writes.  Usage: _wavelet_shapes_child.py CASE ARG OUT.json
+omegas, image sizes and chunkings the models of test_gpu_wavelet.py leave out.
 
 Every comparison is on the engine's flat layout ([LF | HF] at the engine width, zero-padded when Small_Dense narrows the
 model): the engine's own parameters go into the CPU references, so padded rows / columns are checked too."""
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
+import torch
+import torch.nn.functional as F
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import _wavelet_ref as wr  # noqa: E402
-from oracle import siren_oracle as so  # noqa: E402  (test infrastructure: grid and image formulas)
+from _gpu_child import ROOT, child_main
+from _gpu_fixtures import relerr
+import _wavelet_ref as wr
+from oracle import siren_oracle as so  # (test infrastructure: grid and image formulas)
 
 # tag -> (WaveletSiren kwargs, image side H): the table of tests/golden/make_golden_wavelet.py, which minted
 # wavelet_shapes.npz from it
@@ -54,11 +48,6 @@ def model(kw, seed=0, **extra):
     from implicit_image.models import registry
     torch.manual_seed(seed)
     return registry["wavelet_siren"](**kw, **extra).cuda()
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def names_of(m):
@@ -252,14 +241,6 @@ def case_replay(arg):
             "losses": res[0][0]}
 
 
-def main():
-    case, arg, out = sys.argv[1], sys.argv[2], sys.argv[3]
-    fn = {"shape": case_shape, "kernels": case_kernels, "twopass": case_twopass, "natural": case_natural,
-          "replay": case_replay}[case]
-    res = fn(arg)
-    json.dump(res, open(out, "w"), indent=1)
-    print(json.dumps(res)[:4000])
-
-
 if __name__ == "__main__":
-    main()
+    child_main({"shape": case_shape, "kernels": case_kernels, "twopass": case_twopass, "natural": case_natural,
+                "replay": case_replay})

@@ -2,14 +2,14 @@
 writes the last timed step's state as float .npy files under a 64 MB cap."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _gpu_child import ROOT, run
+
 DUMPED = ("params", "grads", "exp_avg", "exp_avg_sq", "loss")
 
 
@@ -54,10 +54,9 @@ def test_dump_outputs_files_dtypes_and_cap(tmp_path, n):
 
 @pytest.mark.gpu
 def test_plain_bench_run_and_dump(tmp_path):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "256", "--steps", "3", "--warmup", "1",
-                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    stdout = run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "256", "--steps", "3", "--warmup", "1",
+                  "--dump-outputs", str(tmp_path)], timeout=300, split=True)
+    line = json.loads(stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
         assert k in line
     assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0

@@ -3,20 +3,15 @@ from it, the four config structs against their C declarations, and the one width
 import ctypes as C
 import os
 import re
-import sys
 
 import pytest
 
+from implicit_image import _engine
+from implicit_image import decode as dec
+from implicit_image.config import _wrap
+from implicit_image.models import registry
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-from implicit_image import _engine  # noqa: E402
-from implicit_image import decode as dec  # noqa: E402
-from implicit_image.config import _wrap  # noqa: E402
-from implicit_image.models import registry  # noqa: E402
-
 HEADER = open(os.path.join(ROOT, "include", "siren_fit.h")).read()
 GROUPS = {"feather": _engine.has_feather, "wavelet": _engine.has_wavelet, "render": _engine.has_render,
           "wavelet_render": _engine.has_wavelet_render, "fourier_render": _engine.has_fourier_render}

@@ -1,21 +1,16 @@
 """Host side of the FourierNet render path, no GPU needed: the C ABI's declarations and build list, the decode.render
 key, which models have a render kernel, the padded parameter layout, and the refusal before the device."""
 import os
-import sys
 
 import pytest
 import torch
 
+from implicit_image import _engine
+from implicit_image import decode as dec
+from implicit_image.config import _wrap
+from implicit_image.models import registry
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-from implicit_image import _engine  # noqa: E402
-from implicit_image import decode as dec  # noqa: E402
-from implicit_image.config import _wrap  # noqa: E402
-from implicit_image.models import registry  # noqa: E402
-
 CSRC = os.path.join(ROOT, "implicit-image-compression_amd", "csrc")
 
 

@@ -6,22 +6,18 @@ as it stood BEFORE models/binding.py (each family with its own copy of the proto
 arguments of the calls that merge had to keep.  No float computed on the device is in the trace: the comparison is exact."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import ROOT, run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_binding_trace_child.py")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "binding_trace.json")
 
 
 def test_binding_call_trace_equals_the_recorded_one(tmp_path):
-    out = tmp_path / "binding_trace.json"
-    r = subprocess.run([sys.executable, CHILD, str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    got, want = json.load(open(out)), json.load(open(GOLDEN))
+    got = run_case("_binding_trace_child.py", "binding_trace", tmp_path=tmp_path, timeout=120)
+    want = json.load(open(GOLDEN))
     assert sorted(got) == sorted(want) == ["A", "B", "C", "D", "E"]
     for name in sorted(want):
         for i, (g, w) in enumerate(zip(got[name], want[name])):

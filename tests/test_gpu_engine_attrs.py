@@ -1,27 +1,22 @@
 """What each of the six engine classes shows a caller, on an MI355X: every public plain attribute and the shapes / dtypes
 (or the refusal) of render for each want_u8 / want_pred combination, against tests/golden/engine_attrs.json.  The golden
 was written by the same child (tests/_engine_attrs_child.py) on the binding as it stood before its constructors and
-prototype tables were merged into one path, so it pins what that merge had to keep.  One child process under a time
-limit."""
+prototype tables were merged into one path, so it pins what that merge had to keep."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import ROOT, run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_engine_attrs_child.py")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "engine_attrs.json")
 CLASSES = ["SirenEngine", "RenderEngine", "FourierEngine", "FourierRenderEngine", "WaveletEngine", "WaveletRenderEngine"]
 
 
 def test_engine_attributes_and_render_outputs(tmp_path):
-    out = tmp_path / "engine_attrs.json"
-    r = subprocess.run([sys.executable, CHILD, str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    got, want = json.load(open(out)), json.load(open(GOLDEN))
+    got = run_case("_engine_attrs_child.py", "engine_attrs", tmp_path=tmp_path, timeout=60)
+    want = json.load(open(GOLDEN))
     assert sorted(got) == sorted(want) == sorted(CLASSES)
     for name in CLASSES:
         g, w = got[name], want[name]

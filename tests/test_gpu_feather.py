@@ -1,29 +1,18 @@
 """Feathermap (masking=Feathermap) on the gfx950 engine against reference-minted fixtures
-(tests/golden/make_golden_feather.py) and fp64 products.  Every case runs in a child process (tests/_feather_child.py)
-under its own time limit."""
+(tests/golden/make_golden_feather.py) and fp64 products.  One case of tests/_feather_child.py per child process."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from _gpu_child import run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_feather_child.py")
-
-
-def run_case(case, tmp_path, timeout):
-    out = tmp_path / f"{case}.json"
-    args = [sys.executable, CHILD, case, str(out)] + ([str(tmp_path)] if case == "fit" else [])
-    r = subprocess.run(args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
+CHILD = "_feather_child.py"
 
 
 def test_materialise_adjoint_forward_and_gradients(tmp_path):
-    r = run_case("parity", tmp_path, 300)
+    r = run_case(CHILD, "parity", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     for tag in ("small", "padded96", "yaml"):
         assert r[f"fp64_{tag}/mat_rel"] <= 1e-6, tag
@@ -44,13 +33,13 @@ def test_materialise_adjoint_forward_and_gradients(tmp_path):
 
 
 def test_twenty_step_trajectory_follows_the_reference(tmp_path):
-    r = run_case("traj", tmp_path, 300)
+    r = run_case(CHILD, "traj", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert r["max_rel"] < 5e-3
 
 
 def test_train_steps_eager_replay_and_reruns_are_bit_identical(tmp_path):
-    r = run_case("steps", tmp_path, 300)
+    r = run_case(CHILD, "steps", tmp_path=tmp_path, timeout=300)
     assert r["eager_vs_bulk"] == [True, True]
     assert r["bulk_rerun"] == [True, True]
     assert r["replay_vs_eager"] == [True, True]
@@ -58,7 +47,7 @@ def test_train_steps_eager_replay_and_reruns_are_bit_identical(tmp_path):
 
 
 def test_host_edits_and_a_rebuilt_handle_keep_the_state(tmp_path):
-    r = run_case("state", tmp_path, 300)
+    r = run_case(CHILD, "state", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert r["edit_pred_maxabs"] < 3e-4
     assert r["rebuilt"] and r["carried"] == [True, True, True, True] and r["optim_bound_to_new"]
@@ -70,7 +59,7 @@ def test_plateau_psnr_within_0p05_db_of_the_reference(tmp_path, golden):
     13.0826 / 13.0827, non-smooth 12.9625 / 12.9626 dB.  Measured on an MI355X at format 16: 13.0997 (+0.017) and 12.9671
     (+0.005); the engine's auto format (12 at this size) measured -0.064 and -0.267 dB, hence the default."""
     g = golden("feather_plateau")
-    r = run_case("plateau", tmp_path, 600)
+    r = run_case(CHILD, "plateau", tmp_path=tmp_path, timeout=600)
     print(json.dumps(r, indent=1))
     for name in ("synthetic", "nonsmooth"):
         ref = float(g[f"{name}/t8/psnr"])
@@ -81,7 +70,7 @@ def test_plateau_psnr_within_0p05_db_of_the_reference(tmp_path, golden):
 
 
 def test_make_fit_feathermap_saves_the_reference_keys(tmp_path, golden):
-    r = run_case("fit", tmp_path, 600)
+    r = run_case(CHILD, "fit", tmp_path=tmp_path, timeout=600)
     print(json.dumps(r, indent=1))
     assert r["keys"] == [k[len("small/"):] for k in golden("feather_init").files if k.startswith("small/") and k != "small/nm"]
     assert r["log_has_psnr"]

@@ -1,24 +1,14 @@
 """FourierNet (mlp=fourier) on the gfx950 engine against reference-minted fixtures (tests/golden/make_golden_fourier.py).
-Every case runs in a child process (tests/_fourier_child.py) under its own time limit."""
+One case of tests/_fourier_child.py per child process."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from _gpu_child import run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_fourier_child.py")
-
-
-def run_case(case, tmp_path, timeout):
-    out = tmp_path / f"{case}.json"
-    args = [sys.executable, CHILD, case, str(out)] + ([str(tmp_path)] if case == "fit" else [])
-    r = subprocess.run(args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
+CHILD = "_fourier_child.py"
 
 
 def test_forward_and_gradients_match_the_reference(tmp_path):
@@ -26,7 +16,7 @@ def test_forward_and_gradients_match_the_reference(tmp_path):
     reference's fp32) and rounded up about 2x.  Measured: prediction 3.3e-5 (64x4) / 5.5e-6 (yaml) max abs; loss 1.4e-6 /
     1.3e-7 relative; 64x4 gradients max |err| / max |ref| 0.0146 (layers.2.weight, the fp16 operands of g and h);
     yaml per-tensor gradient norms 0.0028 relative."""
-    r = run_case("parity", tmp_path, 300)
+    r = run_case(CHILD, "parity", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert r["small_pred_maxabs"] < 1e-4 and r["yaml_pred_maxabs"] < 1e-4
     assert r["small_loss_rel"] < 1e-5 and r["yaml_loss_rel"] < 1e-5
@@ -38,7 +28,7 @@ def test_forward_and_gradients_match_the_reference(tmp_path):
 
 
 def test_train_steps_eager_replay_and_reruns_are_bit_identical(tmp_path):
-    r = run_case("steps", tmp_path, 300)
+    r = run_case(CHILD, "steps", tmp_path=tmp_path, timeout=300)
     assert r["eager_vs_bulk"] == [True, True]
     assert r["bulk_rerun"] == [True, True]
     assert r["replay_vs_eager"] == [True, True]
@@ -46,7 +36,7 @@ def test_train_steps_eager_replay_and_reruns_are_bit_identical(tmp_path):
 
 
 def test_small_dense_width_runs_zero_padded(tmp_path):
-    r = run_case("padded", tmp_path, 300)
+    r = run_case(CHILD, "padded", tmp_path=tmp_path, timeout=300)
     assert r["hidden"] == 90 and r["width"] == 128
     print(json.dumps(r, indent=1))
     # measured: prediction 1.5e-5 max abs, loss 3.4e-7 relative, gradients max |err| / max |ref| 0.054 (fp16 operands of
@@ -56,7 +46,7 @@ def test_small_dense_width_runs_zero_padded(tmp_path):
 
 
 def test_engine_masks_hold_pruned_weights_at_zero(tmp_path):
-    r = run_case("masks", tmp_path, 300)
+    r = run_case(CHILD, "masks", tmp_path=tmp_path, timeout=300)
     assert r["n_pruned"] > 1000 and r["pruned_nonzero"] == 0 and r["kept_nonzero"] > 0
     assert r["losses"][-1] < r["losses"][0]
 
@@ -66,7 +56,7 @@ def test_plateau_psnr_within_0p05_db_of_the_reference(tmp_path, golden):
     synthetic 27.880 / 27.891 dB (spread 0.011), non-smooth 18.819 / 18.783 dB (spread 0.036): inside the 0.05 dB bound.
     Engine measured on an MI355X: 27.890 (+0.010) and 18.816 (-0.003)."""
     g = golden("fourier_plateau")
-    r = run_case("plateau", tmp_path, 600)
+    r = run_case(CHILD, "plateau", tmp_path=tmp_path, timeout=600)
     print(json.dumps(r, indent=1))
     for name in ("synthetic", "nonsmooth"):
         ref = float(g[f"{name}/t8/psnr"])
@@ -74,7 +64,7 @@ def test_plateau_psnr_within_0p05_db_of_the_reference(tmp_path, golden):
 
 
 def test_make_fit_fourier_with_kmeans_and_plain_container(tmp_path):
-    r = run_case("fit", tmp_path, 600)
+    r = run_case(CHILD, "fit", tmp_path=tmp_path, timeout=600)
     print(json.dumps(r, indent=1))
     assert r["keys"][0] == "encoding.B" and r["keys"][1:3] == ["layers.0.weight", "layers.0.bias"]
     assert r["keys"][-1] == "layers.4.bias"   # depth 4: three Linear layers at Sequential indices 0, 2, 4

@@ -1,33 +1,21 @@
 """The inference-only FourierNet render path (sf_fourier_render_create / sf_render on FourierNet handles,
-csrc/fourier_render.hip) and `decode decode.render=kernel` on an MI355X.  Every case runs in a child process
-(tests/_fourier_render_child.py) under its own time limit."""
+csrc/fourier_render.hip) and `decode decode.render=kernel` on an MI355X.  One case of tests/_fourier_render_child.py per
+child process."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _fourier_render_child as child  # noqa: E402  (the shape lists only: nothing touches the device at import)
-from test_gpu_render import TRAINING_CALLS  # noqa: E402
+import _fourier_render_child as child  # (the shape lists only: nothing touches the device at import)
+from _gpu_child import run_case
+from _gpu_fixtures import TRAINING_CALLS
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_fourier_render_child.py")
-
-
-def run_case(case, tmp_path, timeout):
-    out = tmp_path / f"{case}.json"
-    args = [sys.executable, CHILD, case, str(out)] + ([str(tmp_path)] if case == "e2e" else [])
-    r = subprocess.run(args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
+CHILD = "_fourier_render_child.py"
 
 
 @pytest.fixture(scope="module")
 def bitid(tmp_path_factory):
-    return run_case("bitid", tmp_path_factory.mktemp("fourier_bitid"), 300)["cases"]
+    return run_case(CHILD, "bitid", tmp_path=tmp_path_factory.mktemp("fourier_bitid"), timeout=300)["cases"]
 
 
 def test_every_shape_ran(bitid):
@@ -65,7 +53,7 @@ def test_render_bytes_equal_to_u8_of_the_prediction(bitid):
 def test_windows_and_bands_equal_the_full_render(tmp_path):
     """rows=32:96 cols=16:80 of a 128x128 grid == that region of the full 128x128 render, bytes and pred; band_rows=7 == one
     band"""
-    r = run_case("windows", tmp_path, 120)
+    r = run_case(CHILD, "windows", tmp_path=tmp_path, timeout=120)
     print(r)
     assert r["shape"] == [128, 128, 3]
     assert r["window_equal"] and r["window_pred_equal"]
@@ -74,10 +62,10 @@ def test_windows_and_bands_equal_the_full_render(tmp_path):
 
 
 def test_render_handle_refusals(tmp_path):
-    """every training call of tests/test_gpu_render.py on a FourierNet render handle: -1 with "render handle" in the
+    """every training call (TRAINING_CALLS) on a FourierNet render handle: -1 with "render handle" in the
     message; sf_render before sf_set_encoding / sf_set_coords: SF_ERR_STATE (-4); both outputs NULL, an unaligned byte
     pointer and sf_wavelet_render: -1.  The handle's profile counts no launch over all of them."""
-    r = run_case("refuse", tmp_path, 120)
+    r = run_case(CHILD, "refuse", tmp_path=tmp_path, timeout=120)
     for name in TRAINING_CALLS + ["sf_set_target"]:
         assert r[name]["rc"] == -1, (name, r[name])
         assert "render handle" in r[name]["msg"], (name, r[name])
@@ -101,8 +89,8 @@ def test_render_handle_memory(tmp_path):
     """128 hidden, 7 Linear layers, map 256 at 1024x1024, each handle in a fresh process: the render handle takes less
     device memory than the training handle by at least the ffH + ffG + ffZ planes of sf_fourier_create,
     2 (D - 1) WD chunk 2 + 8 chunk bytes with chunk = 2^20, and its own footprint is under 64 MiB."""
-    tr = run_case("mem_train", tmp_path, 120)
-    rn = run_case("mem_render", tmp_path, 120)
+    tr = run_case(CHILD, "mem", "train", tmp_path=tmp_path, timeout=120)
+    rn = run_case(CHILD, "mem", "render", tmp_path=tmp_path, timeout=120)
     m = child.MEM
     chunk = m["height"] * m["width"]
     planes = 2 * (m["n_linear"] - 1) * m["hidden"] * chunk * 2 + 8 * chunk
@@ -118,7 +106,7 @@ def test_fit_then_decode_kernel_against_torch(tmp_path):
     decode.truth=synthetic the three printed figures are equal - at the fitted size, at decode.height=96 decode.width=80,
     for a window with decode.band_rows=5, and for a Small_Dense density-0.5 fit (width 90 zero-padded to 128).
     decode.render=auto still reports "torch" for the run."""
-    r = run_case("e2e", tmp_path, 600)
+    r = run_case(CHILD, "e2e", tmp_path=tmp_path, timeout=600)
     print(json.dumps(r, indent=1))
     pairs = [r["none"]["fitted"], r["none"]["resized"], r["none"]["window"], r["small_dense"]["fitted"]]
     for c in pairs:

@@ -4,22 +4,20 @@ Every fourier_kernels.hip path is run here: widths 32 and 256 (k_ff_fwd / k_ff_b
 the one Fourier kernel that spills), layer 0 staged in several LDS slices with a partial last one (map 512 at WD 128 /
 256, map 256 at WD 256), map 64 (k_ff_dw<2, true>, one partial slice at WD 256), k_ff_dw<1, false> (WD 32), 2 and 12
 Linear layers, Small_Dense widths zero-padded to 64 and 256, multi-chunk passes and grids of 1, 300 x 1 and 1 x 300
-pixels.  Each case runs in a child process (tests/_fourier_shapes_child.py) under its own time limit.
+pixels.  One case of tests/_fourier_shapes_child.py per child process.
 
 Three references: the rounding model (_fourier_ref.engine_model_loss_and_grads: the kernels' fp16 rounding points,
 fp64 elsewhere) is the tight one; the fp64 mirror bounds the whole fp16 error; fourier_shapes.npz is the reference's
 own fp32 output.  Bars are literal: measured on an MI355X and rounded up about 2x.  Gradient errors are per tensor,
 max |err| / max |ref|."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_fourier_shapes_child.py")
+CHILD = "_fourier_shapes_child.py"
 TAGS = ["h32_m64_d3", "h45p_m512_d13", "h128_m512_d4", "h256_m256_d4", "h256_m512_d8", "h198p_m64_d5"]
 
 # Measured on an MI355X (worst tensor of the 24x20 seed-0 pass), engine vs fp64 mirror / engine vs rounding model:
@@ -39,18 +37,10 @@ MODEL_GRAD = {"h32_m64_d3": 1e-5, "h45p_m512_d13": 5e-4, "h128_m512_d4": 7e-2, "
 MASK_FLIP = {"h128_m512_d4"}
 
 
-def run_case(case, arg, tmp_path, timeout):
-    out = tmp_path / f"{case}_{arg}.json"
-    r = subprocess.run([sys.executable, CHILD, case, arg, str(out)], cwd=ROOT, stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
-
-
 @pytest.mark.parametrize("tag", TAGS)
 def test_shape_against_rounding_model_fp64_and_reference(tag, tmp_path):
     """seed-0 model, ragged 24x20 grid (480 pixels: two workgroups, the second partial)."""
-    r = run_case("shape", tag, tmp_path, 300)
+    r = run_case(CHILD, "shape", tag, tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     if tag not in MASK_FLIP:
         assert MODEL_GRAD[tag] * 10 <= FP64_GRAD[tag]
@@ -78,7 +68,7 @@ def test_shape_against_rounding_model_fp64_and_reference(tag, tmp_path):
 def test_chunked_passes_match_the_unchunked_handle(tag, tmp_path):
     """37x29 = 1073 pixels at chunk_pixels 256 (five chunks, the last of 49 pixels) and 768 (768 + 305): the chunk's
     pix0 in the forward and in k_ff_dw<*, true>'s recomputed encoding, gradients accumulated over chunks, sse_off."""
-    r = run_case("chunks", tag, tmp_path, 300)
+    r = run_case(CHILD, "chunks", tag, tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     # measured: prediction and SSE bit-identical to the unchunked handle, gradients within 1.4e-7 (768: the slab split
     # over pixels differs); against the model 1.1e-5 / 8.1e-8 / 8.4e-6 (h32) and 7.7e-3 (h256_m512_d8: a ReLU flip as
@@ -95,7 +85,7 @@ def test_chunked_passes_match_the_unchunked_handle(tag, tmp_path):
 @pytest.mark.parametrize("tag", ["h32_m64_d3", "h256_m256_d4"])
 def test_tiny_grids(tag, tmp_path):
     """1x1, 1x300 and 300x1: one partial workgroup, a single row or column of coordinates"""
-    r = run_case("tiny", tag, tmp_path, 300)
+    r = run_case(CHILD, "tiny", tag, tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     # measured against the model: prediction <= 1.4e-5, SSE <= 5.2e-7, gradients <= 3.5e-5; against fp64: prediction
     # <= 6.1e-5, loss <= 7.2e-5 (1x1: three values), gradients <= 2.5e-2
@@ -109,7 +99,7 @@ def test_twenty_step_trajectory_follows_fp64_adam(tmp_path):
     """256x8 / map 512 / scale 16, 24x20: 20 train_epoch steps at lr 3e-4 against torch.optim.Adam on the fp64 mirror.
     Measured 3.7e-5 worst loss-relative difference.  (At lr 1e-3 this fit is chaotic by step 15: the reference's own
     fp32 run leaves the fp64 one by 23 % at step 20, so that lr tests nothing.)"""
-    r = run_case("traj", "h256_m512_d8", tmp_path, 300)
+    r = run_case(CHILD, "traj", "h256_m512_d8", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert r["losses"][-1] < r["losses"][0]
     assert r["max_rel"] < 1e-4

@@ -1,20 +1,16 @@
-"""sf_destroy gives back every byte a handle took, for every creator, on an MI355X.  The cases run in one child process
-(tests/_handle_memory_child.py) under a time limit."""
-import json
+"""sf_destroy gives back every byte a handle took, for every creator, on an MI355X.  The cases of
+tests/_handle_memory_child.py run in one child process."""
 import math
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_handle_memory_child.py")
 
 # What a create .. destroy cycle may leave behind that is not the handle's: the largest shortfall the same child shows
 # against the library of the commit before the owned list (SIREN_FIT_LIB=<that build> python tests/_handle_memory_child.py
-# OUT.json), which freed every buffer by hand - so whatever it leaves is the runtime's own pools, not a leak - plus one
+# handle_memory OUT.json), which freed every buffer by hand - so whatever it leaves is the runtime's own pools, not a leak - plus one
 # allocation granule (hipMalloc hands out device memory in 2 MiB blocks).
 # NOT YET MEASURED: no MI355X run could be had when this test was written, so the figure stands at 0, the least it can
 # be, and the bound is one granule.  A measured figure can only widen it; put it here with the date of the run.
@@ -33,10 +29,8 @@ def test_destroy_returns_what_the_handle_took(tmp_path):
     format 8 to 16), three more steps (longer step tables, a new graph) and sf_kmeans_fit; a second SIREN handle takes
     sf_feather_attach.  After every destroy torch.cuda.mem_get_info() reports the free memory read before that handle's
     create, within SLACK.  The child's first round (the process's first use of each kernel) is not measured."""
-    out = tmp_path / "handle_memory.json"
-    r = subprocess.run([sys.executable, CHILD, str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    cases = [c for c in json.load(open(out))["cases"] if c["round"] == 1]
+    got = run_case("_handle_memory_child.py", "handle_memory", tmp_path=tmp_path, timeout=60)
+    cases = [c for c in got["cases"] if c["round"] == 1]
     for c in cases:
         print(c)
     assert [c["creator"] for c in cases] == CREATORS

@@ -4,15 +4,15 @@ of a masked fit, and the per-image sharding entry with two real processes.  Inde
 golden vectors the reference itself produced (tests/golden/masking_*.npz, kmeans_64x64.npz)."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+from _gpu_child import ROOT, TESTS, run_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class Cfg(dict):
@@ -208,10 +208,7 @@ def test_per_image_sharding_two_processes(tmp_path):
                IIC_CONF=os.path.join(ROOT, "conf"))
     args = [sys.executable, "-m", "implicit_image.fit", "img.height=64", "img.width=64", "img.seed=3,4", "mlp.hidden_size=64",
             "mlp.depth=4", "train.num_steps=60", "train.log_steps=60", "masking=none", "quant=none"]
-    procs = [subprocess.Popen(args, cwd=tmp_path, env=dict(env, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-             for r in range(2)]
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), outs
+    outs = run_ranks(args, [dict(env, RANK=str(r)) for r in range(2)], timeout=300, cwd=tmp_path)
     found = sorted(str(p.relative_to(tmp_path)) for p in tmp_path.rglob("result.json"))
     assert len(found) == 2 and any("img.seed=3" in f for f in found) and any("img.seed=4" in f for f in found), found
     res = [json.load(open(tmp_path / f)) for f in found]
@@ -271,11 +268,8 @@ def test_pixel_split_two_real_engines(tmp_path):
     single-handle run within the shard-composition bound (fp32 summation order of two row blocks: 1e-5 relative)."""
     port = 29600 + (os.getpid() % 1000)
     env = dict(os.environ, WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), LOCAL_RANK="0")
-    child = os.path.join(ROOT, "tests", "_pixel_split_child.py")
-    procs = [subprocess.Popen([sys.executable, child, str(tmp_path / f"r{r}.json")], env=dict(env, RANK=str(r)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(2)]
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), outs
+    run_ranks([sys.executable, os.path.join(TESTS, "_pixel_split_child.py"), str(tmp_path)],
+              [dict(env, RANK=str(r)) for r in range(2)], timeout=300)
     res = [json.load(open(tmp_path / f"r{r}.json")) for r in range(2)]
     assert res[0]["rows"] == [0, 32] and res[1]["rows"] == [32, 64]
     assert res[0]["params_sha256"] == res[1]["params_sha256"]                      # replicas stay bit-identical

@@ -1,8 +1,8 @@
 """The launch plan of the engine is pinned: which kernels a pass launches, how often, and the flops / bytes each launch is
-charged, for every launch path.  The cases run in one child process (tests/_launch_plan_child.py) under a time limit and
-are compared with tests/golden/launch_plan.json, which was recorded by the same child against the library of the commit
-before the launch layer was folded into one launcher (SIREN_FIT_LIB=<that build> python tests/_launch_plan_child.py OUT.json;
-the "cases" -> name -> "plan" part of OUT.json is the golden).
+charged, for every launch path.  The cases of tests/_launch_plan_child.py run in one child process and are compared with
+tests/golden/launch_plan.json, which was recorded by the same child against the library of the commit before the launch
+layer was folded into one launcher (SIREN_FIT_LIB=<that build> python tests/_launch_plan_child.py launch_plan OUT.json; the
+"cases" -> name -> "plan" part of OUT.json is the golden).
 
 Cases (all eager, profiling on, one sf_forward + one sf_forward_backward, render handles one sf_render):
   SIREN on 40 x 52 (2080 pixels, chunk_pixels 1024: two full chunks and a ragged one): hidden 32 / 64 / 128 / 256, depth
@@ -25,14 +25,12 @@ parameters of both runs equal, exactly, what the library of the commit before th
 "wavelet_step_64x3_H2", through the same child and SIREN_FIT_LIB)."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import ROOT, run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_launch_plan_child.py")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "launch_plan.json")
 REL = 1e-12      # flops / bytes are host doubles: only the order of a sum may move them
 
@@ -43,10 +41,7 @@ STEP_KEY = "wavelet_step_64x3_H2"
 @pytest.fixture(scope="module")
 def child(tmp_path_factory):
     """the one run of the child that both tests read"""
-    out = tmp_path_factory.mktemp("launch_plan") / "launch_plan.json"
-    r = subprocess.run([sys.executable, CHILD, str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
+    return run_case("_launch_plan_child.py", "launch_plan", tmp_path=tmp_path_factory.mktemp("launch_plan"), timeout=60)
 
 
 def test_launch_plan_matches_golden(child):

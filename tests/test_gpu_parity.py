@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_fixtures import siren_engine as _engine
 from oracle import siren_oracle as so
 
 pytestmark = pytest.mark.gpu
@@ -34,19 +35,6 @@ FORMATS = (16, 12, 8)      # sf_config.scratch_format; 0 / auto (fp16 operands, 
 
 def _rel(a, b):
     return float(np.linalg.norm(np.asarray(a) - np.asarray(b)) / np.linalg.norm(np.asarray(b)))
-
-
-def _engine(H, W, hidden, depth, dtype="f16", params=None, img=None, **kw):
-    from implicit_image._engine import SirenEngine
-    eng = SirenEngine(H, W, hidden, depth, compute_dtype=dtype, **kw)
-    gh, gw = so.grid_vectors(H, W)
-    eng.set_coords(gh.cuda(), gw.cuda())
-    if params is not None:
-        eng.set_params(torch.tensor(so.flatten(params)).cuda())
-    if img is not None:
-        r0, r1 = eng.row_begin, eng.row_end
-        eng.set_target(img[r0:r1].contiguous().cuda())
-    return eng
 
 
 @pytest.mark.parametrize("name,hidden,depth", [("grads_64x4_32", 64, 4), ("grads_256x8_32", 256, 8),

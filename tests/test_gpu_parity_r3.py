@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_fixtures import siren_engine as _engine
 from oracle import siren_oracle as so
 
 pytestmark = pytest.mark.gpu
@@ -29,18 +30,6 @@ NS1024_BOUND = {16: 0.05, 12: 0.05, 8: 0.05}   # BASELINE.json's criterion (meas
 
 def _sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def _engine(H, W, hidden, depth, dtype="f16", params=None, img=None, **kw):
-    from implicit_image._engine import SirenEngine
-    eng = SirenEngine(H, W, hidden, depth, compute_dtype=dtype, **kw)
-    gh, gw = so.grid_vectors(H, W)
-    eng.set_coords(gh.cuda(), gw.cuda())
-    if params is not None:
-        eng.set_params(torch.tensor(so.flatten(params)).cuda())
-    if img is not None:
-        eng.set_target(img[eng.row_begin:eng.row_end].contiguous().cuda())
-    return eng
 
 
 def _fit(d, fmt, img, lr_of_step):

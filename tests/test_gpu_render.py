@@ -1,28 +1,19 @@
 """The inference-only render path (sf_render_create / sf_render, csrc/siren_render.hip) and `decode` on an MI355X.
-Every case runs in a child process (tests/_render_child.py) under its own time limit."""
+One case of tests/_render_child.py per child process."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import run_case
+from _gpu_fixtures import TRAINING_CALLS
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_render_child.py")
-
-
-def run_case(case, tmp_path, timeout):
-    out = tmp_path / f"{case}.json"
-    args = [sys.executable, CHILD, case, str(out)] + ([str(tmp_path)] if case == "e2e" else [])
-    r = subprocess.run(args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
+CHILD = "_render_child.py"
 
 
 @pytest.fixture(scope="module")
 def bitid(tmp_path_factory):
-    return run_case("bitid", tmp_path_factory.mktemp("bitid"), 600)["cases"]
+    return run_case(CHILD, "bitid", tmp_path=tmp_path_factory.mktemp("bitid"), timeout=600)["cases"]
 
 
 def test_render_pred_is_bit_identical_to_the_training_forward(bitid):
@@ -52,7 +43,7 @@ def test_render_bytes_equal_the_conversion_of_the_kernels_own_prediction(bitid):
 def test_render_of_the_container_fixture_against_the_fp64_oracle(tmp_path):
     """tests/golden/container_64x4.npz rendered at 64x64: max |pred - oracle.forward| < 5e-4 (smoke()'s bound for this
     shape), and the byte image differs from the oracle's by at most one level anywhere."""
-    r = run_case("oracle", tmp_path, 120)
+    r = run_case(CHILD, "oracle", tmp_path=tmp_path, timeout=120)
     print(r)
     assert r["max_abs"] < 5e-4
     assert r["max_levels"] <= 1
@@ -60,21 +51,16 @@ def test_render_of_the_container_fixture_against_the_fp64_oracle(tmp_path):
 
 def test_windows_and_bands_equal_the_full_render(tmp_path):
     """rows=32:96 cols=16:80 of a 128x128 grid == that region of the full 128x128 render; band_rows=7 == one band"""
-    r = run_case("windows", tmp_path, 180)
+    r = run_case(CHILD, "windows", tmp_path=tmp_path, timeout=180)
     print(r)
     assert r["window_equal"] and r["window_pred_equal"]
     assert r["band_equal"] and r["band_pred_equal"]
     assert r["distinct_levels"] > 16          # a picture, not a constant
 
 
-TRAINING_CALLS = ["sf_forward_backward", "sf_forward", "sf_step", "sf_adam_step", "sf_set_masks", "sf_get_grads", "sf_set_grads",
-                  "sf_get_adam_state", "sf_set_adam_state", "sf_kmeans_fit", "sf_feather_attach", "sf_feather_state_ptr",
-                  "sf_feather_materialise", "sf_feather_adjoint", "sf_debug_scratch", "sf_state_ptr_grads"]
-
-
 def test_render_handle_refuses_training_calls_and_the_wide_path(tmp_path):
     """argument checks that return SF_ERR_INVALID (-1) with a message; nothing is launched"""
-    r = run_case("refuse", tmp_path, 120)
+    r = run_case(CHILD, "refuse", tmp_path=tmp_path, timeout=120)
     for name in TRAINING_CALLS:
         assert r[name]["rc"] == -1, (name, r[name])
         assert "render handle" in r[name]["msg"], (name, r[name])
@@ -89,8 +75,8 @@ def test_render_handle_memory(tmp_path):
     """256x8 at 2048x2048, each handle in a fresh process: the render handle takes less device memory than the training
     handle by at least Pbuf + Dbuf + Dlast (sizes as sf_debug_scratch reports them), and its own footprint (it allocates
     no output buffer) is under 64 MiB."""
-    tr = run_case("mem_train", tmp_path, 180)
-    rn = run_case("mem_render", tmp_path, 180)
+    tr = run_case(CHILD, "mem", "train", tmp_path=tmp_path, timeout=180)
+    rn = run_case(CHILD, "mem", "render", tmp_path=tmp_path, timeout=180)
     scratch = sum(tr["scratch"].values())
     print({"train": tr, "render": rn, "scratch": scratch})
     assert scratch > (1 << 30)                # the 8-bit scratch of 4 Mi pixels x 7 layers x 256 is several GiB
@@ -105,7 +91,7 @@ def test_fit_then_decode_end_to_end(tmp_path):
     the clamp changes nothing and the figure is also eval_epoch's own ('Quant PSNR 8bit' of the fit, which evaluates the
     quantised model before the fp16 container: compared to 0.5 dB only, the weights differ by the fp16 rounding).
     Fallback: mlp=fourier from model.pth gives a 64x64 file equal to the torch conversion of the model's own forward."""
-    r = run_case("e2e", tmp_path, 900)
+    r = run_case(CHILD, "e2e", tmp_path=tmp_path, timeout=900)
     print(json.dumps(r, indent=1))
     for tag in ("none", "rigl"):
         c = r[tag]

@@ -1,27 +1,16 @@
 """16 bits per sample on the render kernels (sf_render16 / sf_wavelet_render16, decode.bits=16) on an MI355X.
 u16 = min(max((int)(pred * 65535.0f), 0), 65535), the product in fp32 and truncated toward zero.  Every comparison is exact
-(torch.equal on values widened to int32).  Every case runs in a child process (tests/_render16_child.py) under its own time
-limit."""
+(torch.equal on values widened to int32).  One case of tests/_render16_child.py per child process."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_render16_child.py")
+CHILD = "_render16_child.py"
 CHECKS = ("equals_to_u16", "equals_formula", "alone_equal", "pred_bit_identical", "guard_intact", "u8_after_equal",
           "u8_guard_intact", "finite")
-
-
-def run_case(case, tmp_path, timeout):
-    out = tmp_path / f"{case}.json"
-    args = [sys.executable, CHILD, case, str(out)] + ([str(tmp_path)] if case == "e2e" else [])
-    r = subprocess.run(args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
 
 
 def check_rows(rows):
@@ -38,7 +27,7 @@ def test_siren_samples_on_every_kernel_form(tmp_path):
     handle and on a training handle.  The output layer is scaled by 40 with a zero bias: a linear output swings over about
     [-1.5, 3] (the fp64 oracle's range for these seeds), so both clamps are hit and a thousand pixels spread over more
     levels than a byte has."""
-    rows = run_case("siren", tmp_path, 600)["cases"]
+    rows = run_case(CHILD, "siren", tmp_path=tmp_path, timeout=600)["cases"]
     assert len(rows) == 3 * 3 * 2 * 4 * 2 * 2
     check_rows(rows)
     assert all("pred_is_forward" in c for c in rows if c["handle"] == "train")
@@ -49,7 +38,7 @@ def test_siren_samples_on_every_kernel_form(tmp_path):
 
 def test_fourier_samples(tmp_path):
     """hidden 32 and 256, map 64, 3 Linear layers, the same pictures and chunkings, render and training handle"""
-    rows = run_case("fourier", tmp_path, 300)["cases"]
+    rows = run_case(CHILD, "fourier", tmp_path=tmp_path, timeout=300)["cases"]
     assert len(rows) == 2 * 4 * 2 * 2
     check_rows(rows)
     assert all(c["levels"] > 256 for c in rows if c["H"] * c["W"] >= 1000)
@@ -58,7 +47,7 @@ def test_fourier_samples(tmp_path):
 def test_wavelet_samples_full_picture_and_windows(tmp_path):
     """32x2 and 256x3 at H = 6, 10, 64: the full picture and windows with odd origins and sizes, one pixel, an odd pixel
     count that is no multiple of 64, on a render handle and on a training handle; pred equals that region of sf_forward's"""
-    rows = run_case("wavelet", tmp_path, 300)["cases"]
+    rows = run_case(CHILD, "wavelet", tmp_path=tmp_path, timeout=300)["cases"]
     assert len(rows) == 2 * (3 + 4 + 5) * 2
     check_rows(rows)
     assert all("pred_is_forward" in c for c in rows)
@@ -67,7 +56,7 @@ def test_wavelet_samples_full_picture_and_windows(tmp_path):
 
 def test_argument_errors_are_answered_before_any_launch(tmp_path):
     """return codes (SF_ERR_INVALID -1, SF_ERR_STATE -4) and messages; nothing is launched by a refused call"""
-    r = run_case("refuse", tmp_path, 180)
+    r = run_case(CHILD, "refuse", tmp_path=tmp_path, timeout=180)
     print(json.dumps(r, indent=1))
 
     def refused(name, rc, *words):
@@ -105,7 +94,7 @@ def test_fit_then_decode_16_bits_end_to_end(tmp_path):
     file is P6 / 65535 and read_ppm of it equals the 16-bit conversion of the fitted model's own forward on the grid;
     decode.render=torch decode.bits=16 writes the same file; with decode.truth PSNR_16bit is there and finite;
     decode.bits=8 is a run without the key, file and figures."""
-    r = run_case("e2e", tmp_path, 900)
+    r = run_case(CHILD, "e2e", tmp_path=tmp_path, timeout=900)
     print(json.dumps(r, indent=1))
     assert sorted(r) == ["fourier", "siren", "wavelet_siren"]
     for name, c in r.items():

@@ -1,30 +1,20 @@
 """WaveletSiren (mlp=wavelet_siren) on the gfx950 engine against the fp64 mirror (tests/_wavelet_ref.py) and
-reference-minted fixtures (tests/golden/make_golden_wavelet.py).  Every case runs in a child process
-(tests/_wavelet_child.py) under its own time limit."""
+reference-minted fixtures (tests/golden/make_golden_wavelet.py).  One case of tests/_wavelet_child.py per child
+process."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_wavelet_child.py")
-
-
-def run_case(case, tmp_path, timeout):
-    out = tmp_path / f"{case}.json"
-    args = [sys.executable, CHILD, case, str(out)] + ([str(tmp_path)] if case == "fit" else [])
-    r = subprocess.run(args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
+CHILD = "_wavelet_child.py"
 
 
 def test_compose_and_adjoint_kernels_match_the_fp64_mirror(tmp_path):
     """k_wv_compose and k_wv_adjoint at H = 8, 64, 100, 256 on random inputs (fp32 arithmetic against fp64), and
     <A x, y> = <x, A^T y> for the engine's adjoint"""
-    r = run_case("kernels", tmp_path, 300)
+    r = run_case(CHILD, "kernels", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     for H, v in r.items():
         assert v["pred_rel"] < 1e-6 and v["g_rel"] < 1e-6, (H, v)
@@ -36,7 +26,7 @@ def test_forward_and_gradients_match_the_reference(tmp_path):
     """seed-0 models on the 64x64 fixture image (fp16 MFMA operands against the reference's fp32).  Bars: measured on an
     MI355X and rounded up about 2x.  Measured: prediction 6.6e-5 (64x4) / 7.1e-5 (yaml) max abs; loss 6.6e-6 / 4.7e-6
     relative; 64x4 gradients max |err| / max |ref| 6.1e-4; yaml per-tensor gradient norms 1.9e-4 relative."""
-    r = run_case("parity", tmp_path, 300)
+    r = run_case(CHILD, "parity", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert r["draws_rel"] == 0.0
     assert r["small_pred_maxabs"] < 1.5e-4 and r["yaml_pred_maxabs"] < 1.5e-4
@@ -51,7 +41,7 @@ def test_forward_and_gradients_match_the_reference(tmp_path):
 def test_twenty_step_trajectory_follows_the_reference(tmp_path):
     """64x4, 20 steps of Adam lr 1e-3.  Measured: losses 2.3e-4 relative at most; parameters at most 0.11 of Adam's step
     budget lr * steps apart (elements whose gradient is near zero follow the sign of the fp16 noise)."""
-    r = run_case("traj", tmp_path, 300)
+    r = run_case(CHILD, "traj", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert max(r["loss_rel"]) < 5e-4
     assert r["param_maxabs_over_budget"] < 0.25
@@ -70,7 +60,7 @@ def test_plateau_psnr_against_the_reference(tmp_path, golden):
     30.461)."""
     import numpy as np
     g = golden("wavelet_plateau")
-    r = run_case("plateau", tmp_path, 600)
+    r = run_case(CHILD, "plateau", tmp_path=tmp_path, timeout=600)
     print(json.dumps({k: v["psnr"] for k, v in r.items()}))
     ref = float(g["synthetic/t8/psnr"])
     assert abs(r["synthetic"]["psnr"] - ref) <= 0.05, (r["synthetic"]["psnr"], ref)
@@ -84,7 +74,7 @@ def test_two_pass_chunking_agrees_with_one_chunk(tmp_path):
     """chunk_pixels 1024: the two-pass path (inference forward, compose / adjoint into fp32, per-chunk training forward,
     inject, backward).  Each chunk's dL/dout rounds to fp16 exactly as in the one-pass path; only the order in which the
     chunks' weight gradients are summed differs."""
-    r = run_case("chunk", tmp_path, 300)
+    r = run_case(CHILD, "chunk", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     for H, v in r.items():
         assert v["first_loss_equal"], (H, v)
@@ -93,7 +83,7 @@ def test_two_pass_chunking_agrees_with_one_chunk(tmp_path):
 
 
 def test_train_steps_eager_replay_and_reruns_are_bit_identical(tmp_path):
-    r = run_case("steps", tmp_path, 300)
+    r = run_case(CHILD, "steps", tmp_path=tmp_path, timeout=300)
     assert r["eager_vs_bulk"] == [True, True]
     assert r["bulk_rerun"] == [True, True]
     assert r["replay_vs_eager"] == [True, True]
@@ -101,7 +91,7 @@ def test_train_steps_eager_replay_and_reruns_are_bit_identical(tmp_path):
 
 
 def test_small_dense_width_runs_zero_padded(tmp_path):
-    r = run_case("padded", tmp_path, 300)
+    r = run_case(CHILD, "padded", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert r["hidden"] == 45 and r["width"] == 64 and r["n_padding"] > 0
     # measured: prediction 4.0e-5 max abs, loss 3.3e-7 relative, gradients max |err| / max |ref| 1.8e-4 (fp64 mirror)
@@ -110,7 +100,7 @@ def test_small_dense_width_runs_zero_padded(tmp_path):
 
 
 def test_make_fit_wavelet_siren(tmp_path):
-    r = run_case("fit", tmp_path, 600)
+    r = run_case(CHILD, "fit", tmp_path=tmp_path, timeout=600)
     print(json.dumps(r, indent=1))
     assert r["finite"] and r["PSNR"] > 20
     assert r["keys"][0] == "LF_siren.layers.0.linear.weight" and r["keys"][-1] == "HF_siren.layers.7.linear.bias"

@@ -1,32 +1,20 @@
 """The inference-only WaveletSiren path (sf_wavelet_render_create / sf_wavelet_render, csrc/wavelet_render.hip) and `decode`
-of WaveletSiren / zero-padded fits on an MI355X.  Every case runs in a child process (tests/_wavelet_render_child.py) under
-its own time limit.  No tolerance unless one is named."""
+of WaveletSiren / zero-padded fits on an MI355X.  One case of tests/_wavelet_render_child.py per child process.  No
+tolerance unless one is named."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import run_case
+from _gpu_fixtures import TRAINING_CALLS
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_wavelet_render_child.py")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_gpu_render import TRAINING_CALLS  # noqa: E402
-
-
-def run_case(case, tmp_path, timeout):
-    out = tmp_path / f"{case}.json"
-    args = [sys.executable, CHILD, case, str(out)] + ([str(tmp_path)] if case == "e2e" else [])
-    r = subprocess.run(args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
+CHILD = "_wavelet_render_child.py"
 
 
 @pytest.fixture(scope="module")
 def bitid(tmp_path_factory):
-    return run_case("bitid", tmp_path_factory.mktemp("wv_bitid"), 600)["cases"]
+    return run_case(CHILD, "bitid", tmp_path=tmp_path_factory.mktemp("wv_bitid"), timeout=600)["cases"]
 
 
 def test_render_pred_is_bit_identical_to_the_training_forward(bitid):
@@ -57,7 +45,7 @@ def test_ragged_outputs_and_the_guard_region(tmp_path):
     """byte counts that are no multiple of 4 (a 5 x 7 window of a 10 x 10 picture: 105 bytes; 1 x 1: 3 bytes), windows whose
     first pixel is no multiple of 64, on both kinds of handle, with and without pred: bytes and pred equal that region of
     the training forward, and the 256 bytes behind the output stay untouched."""
-    r = run_case("ragged", tmp_path, 300)["cases"]
+    r = run_case(CHILD, "ragged", tmp_path=tmp_path, timeout=300)["cases"]
     assert any(c["nbytes"] % 4 for c in r) and any(c["nbytes"] == 105 for c in r) and any(c["nbytes"] == 3 for c in r)
     for c in r:
         for k in ("render_pred", "render_nopred", "train_pred", "train_nopred"):
@@ -70,7 +58,7 @@ def test_windows_and_bands_equal_the_full_render(tmp_path):
     single-row and single-column window of a 10 x 10 picture: pred and bytes equal that region of the full render, on a
     render handle and on a training handle.  decode's band loop with band_rows=7 equals one band (full picture and a
     window); a handle created with max_rows = 7 draws 7 rows and refuses 8 with SF_ERR_INVALID."""
-    r = run_case("windows", tmp_path, 400)
+    r = run_case(CHILD, "windows", tmp_path=tmp_path, timeout=400)
     assert len(r["windows"]) == 9 + 9 + 20
     bad = [w for w in r["windows"] if not (w["pred_equal"] and w["u8_equal"] and w["train_pred_equal"] and w["train_u8_equal"])]
     assert not bad, bad[:4]
@@ -84,7 +72,7 @@ def test_render_against_the_reference_predictions(tmp_path):
     """tests/golden/wavelet_grads.npz (minted by the reference: the seed-0 64x4 and yaml models on 64 x 64):
     max |render pred - reference pred| < 1.5e-4, the bound tests/test_gpu_wavelet.py holds the training forward to
     (measured there 6.6e-5 / 7.1e-5); the byte picture differs from to_u8(reference pred) by at most one level."""
-    r = run_case("reference", tmp_path, 180)
+    r = run_case(CHILD, "reference", tmp_path=tmp_path, timeout=180)
     print(r)
     for tag in ("small", "yaml"):
         assert r[tag]["max_abs"] < 1.5e-4, r
@@ -92,10 +80,10 @@ def test_render_against_the_reference_predictions(tmp_path):
 
 
 def test_refusals(tmp_path):
-    """every training call of tests/test_gpu_render.py plus sf_render and sf_set_target on a WaveletSiren render handle:
+    """every training call (TRAINING_CALLS) plus sf_render and sf_set_target on a WaveletSiren render handle:
     SF_ERR_INVALID and 'render handle' in the message; sf_wavelet_render's own argument checks; nothing is launched by a
     refused call (the handle's profile counts no launch); the calls that must keep working return 0"""
-    r = run_case("refuse", tmp_path, 180)
+    r = run_case(CHILD, "refuse", tmp_path=tmp_path, timeout=180)
     for name in TRAINING_CALLS + ["sf_render", "sf_set_target"]:
         assert r[name]["rc"] == -1, (name, r[name])
         assert "render handle" in r[name]["msg"], (name, r[name])
@@ -120,8 +108,8 @@ def test_render_handle_memory(tmp_path):
     than 64 MiB (the allowance of test_gpu_render.py::test_render_handle_memory) + 24 B x n^2 (the two coefficient buffers);
     the training handle takes at least the two sub-networks' phase + delta scratch more, counted as twice what
     sf_debug_scratch reports for a plain SIREN training handle of 128x8, scratch format 16, on a 1026 x 1026 grid."""
-    tr = run_case("mem_train", tmp_path, 240)
-    rn = run_case("mem_render", tmp_path, 240)
+    tr = run_case(CHILD, "mem", "train", tmp_path=tmp_path, timeout=240)
+    rn = run_case(CHILD, "mem", "render", tmp_path=tmp_path, timeout=240)
     scratch = 2 * sum(tr["sub_scratch"].values())
     print({"train": tr, "render": rn, "two_sub_scratch": scratch})
     assert rn["n"] == 1026
@@ -136,7 +124,7 @@ def test_fit_then_decode_end_to_end(tmp_path):
     byte for byte; PSNR_8bit as printed equals decode.metrics on those bytes; decode.height=128 decode.width=128 equals a
     fresh registry model with the state dict on the 128 x 128 grid; a window in bands of 7 rows equals that region.  A SIREN
     fit whose Small_Dense width is 181 (hidden 256, density 0.5) decodes on the kernel path to its own model's bytes."""
-    r = run_case("e2e", tmp_path, 900)
+    r = run_case(CHILD, "e2e", tmp_path=tmp_path, timeout=900)
     print(json.dumps(r, indent=1))
     for tag in ("none", "small_dense"):
         c = r[tag]

@@ -5,8 +5,7 @@ Every sub-network kernel path a WaveletSiren reaches runs here with its dL/dout 
 and 256 with a sine output layer (outermost_linear=False), 256 at depth 2 (k_fwd<256>) and at depth >= 3 (k_fwd_pipe),
 Small_Dense 181 zero-padded to 256, depth 16, first / hidden omega 30 / 50, images of 2 x 2 (n = 3 > H: Cb / Cr
 down-sampled), 4 x 4 (bilinear scale exactly 1) and 6 x 6, the two-pass path at 11 chunks, on the pipe and with a sine
-output, and 4096 x 4096 with default chunking.  Each case runs in a child process (tests/_wavelet_shapes_child.py) under
-its own time limit.
+output, and 4096 x 4096 with default chunking.  One case of tests/_wavelet_shapes_child.py per child process.
 
 Three references: the rounding model (_wavelet_ref.engine_model_loss_and_grads: the engine's fp16 rounding points,
 oracle/engine_model.py's scratch-16 chain per sub-network); the fp64 mirror, which bounds the whole fp16 error;
@@ -24,15 +23,13 @@ it is no closer than fp64 (7.7e-4 vs 6.1e-4), because the floor dominates a 27-v
 place.  It takes the same dfac and pre-scale as the engine, so a missing or wrong factor is off by 0.4 .. 1.0 in every
 tensor against it and against fp64 alike."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _gpu_child import run_case
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "_wavelet_shapes_child.py")
+CHILD = "_wavelet_shapes_child.py"
 TAGS = ["h32_d3_s24", "h64_d2_s10", "h128_d5_sin_s40", "h256_d2_s30", "h256_d6_s64", "h256_d4_sin_om_s48",
         "h181p_d4_s48", "h32_d16_s20"]
 TINY = ["h64_d3_s2", "h64_d3_s4", "h64_d3_s6"]
@@ -51,14 +48,6 @@ FP64_GRAD = {"h32_d3_s24": 3e-3, "h64_d2_s10": 7e-4, "h128_d5_sin_s40": 2.5e-3, 
              "h64_d3_s2": 1.3e-3, "h64_d3_s4": 1.2e-3, "h64_d3_s6": 1.4e-3}
 # (10x separation: only where no hidden layer holds an fp16 rounding that can flip)
 SEPARATED = {"h256_d2_s30", "h64_d2_s10"}
-
-
-def run_case(case, arg, tmp_path, timeout):
-    out = tmp_path / f"{case}_{arg}.json"
-    r = subprocess.run([sys.executable, CHILD, case, arg, str(out)], cwd=ROOT, stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, timeout=timeout)
-    assert r.returncode == 0, r.stdout.decode()[-4000:]
-    return json.load(open(out))
 
 
 def check_shape(tag, r):
@@ -87,7 +76,7 @@ def check_shape(tag, r):
 @pytest.mark.parametrize("tag", TAGS)
 def test_shape_against_rounding_model_fp64_and_reference(tag, tmp_path):
     """seed-0 model on synthetic_image(H, H, seed 5)"""
-    r = run_case("shape", tag, tmp_path, 300)
+    r = run_case(CHILD, "shape", tag, tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     check_shape(tag, r)
     if r["padded"]:
@@ -100,7 +89,7 @@ def test_shape_against_rounding_model_fp64_and_reference(tag, tmp_path):
 @pytest.mark.parametrize("tag", TINY)
 def test_tiny_images(tag, tmp_path):
     """64x3 at H = 2 (n = 3: Cb / Cr down-sampled), 4 (scale 1) and 6"""
-    r = run_case("shape", tag, tmp_path, 300)
+    r = run_case(CHILD, "shape", tag, tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     check_shape(tag, r)
 
@@ -108,7 +97,7 @@ def test_tiny_images(tag, tmp_path):
 def test_compose_and_adjoint_kernels_at_tiny_images(tmp_path):
     """k_wv_compose / k_wv_adjoint at H = 2, 4, 6 on random inputs against the fp64 mirror, and <A x, y> = <x, A^T y>.
     Measured: <= 1.1e-7 relative, dot identity <= 1.5e-8."""
-    r = run_case("kernels", "x", tmp_path, 300)
+    r = run_case(CHILD, "kernels", "x", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     for H, v in r.items():
         assert v["pred_rel"] < 1e-6 and v["g_rel"] < 1e-6, (H, v)
@@ -121,7 +110,7 @@ def test_two_pass_path_against_fp64_and_the_model(tag, tmp_path):
     """64x4 at 100 x 100, chunk 256 (2704 coefficients, 11 chunks, the last of 144); 256x4 at 64 x 64, chunk 1024 (the
     pipe's inference and training kernels both feed the pass); the sine-output 256x4 at 48 x 48, chunk 256 (dfac written by
     each chunk's training forward, applied by k_wv_inject)"""
-    r = run_case("twopass", tag, tmp_path, 300)
+    r = run_case(CHILD, "twopass", tag, tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     sine = "sin" in tag
     # against the one-chunk handle: measured prediction, SSE and eval SSE bit-identical, gradients <= 2.8e-7
@@ -139,7 +128,7 @@ def test_natural_two_pass_size_4096(tmp_path):
     """32x3 at 4096 x 4096 with default chunking (4 202 500 coefficients: 4 Mi + 8196).  Measured: gradients 1.9e-3
     against the fp64 mirror run on the device (worst tensor), loss 4.1e-6 relative; the engine's SSE (65 536 partials
     through k_sse_reduce, eval and training alike) 2.0e-11 from the fp64 sum over its own prediction."""
-    r = run_case("natural", "x", tmp_path, 600)
+    r = run_case(CHILD, "natural", "x", tmp_path=tmp_path, timeout=600)
     print(json.dumps(r, indent=1))
     assert r["n2"] == 4202500
     assert r["sse_eval_eq_train"]
@@ -152,7 +141,7 @@ def test_natural_two_pass_size_4096(tmp_path):
 def test_graph_replay_on_a_multi_chunk_fit_is_the_eager_path(tmp_path):
     """set_graph_replay(True) with 1156 coefficients in chunks of 256: train_steps falls back to eager launches; losses
     and parameters after 10 steps are bit-identical to the run without replay"""
-    r = run_case("replay", "x", tmp_path, 300)
+    r = run_case(CHILD, "replay", "x", tmp_path=tmp_path, timeout=300)
     print(json.dumps(r, indent=1))
     assert r["losses_equal"] and r["params_equal"]
     assert r["losses"][-1] < r["losses"][0]

@@ -2,22 +2,17 @@
 path and plans bands, the padded parameter layout, and the C ABI's declarations."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from implicit_image import _engine
+from implicit_image import decode as dec
+from implicit_image.config import _wrap
+from implicit_image.models import registry
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-from implicit_image import _engine  # noqa: E402
-from implicit_image import decode as dec  # noqa: E402
-from implicit_image.config import _wrap  # noqa: E402
-from implicit_image.models import registry  # noqa: E402
-
 CSRC = os.path.join(ROOT, "implicit-image-compression_amd", "csrc")
 
 
