@@ -159,7 +159,9 @@ struct sf_engine {
   double* sse_dev = nullptr;
   // render handle (sf_render_create, siren_render.hip; sf_fourier_render_create, fourier_render.hip; sf_wavelet_render_create,
   // wavelet_render.hip): parameters, forward images and coordinates only - no gradient, no optimiser state, no mask, no
-  // backward scratch; every training entry point refuses it
+  // backward scratch; every training entry point refuses it.  sf_feather_render_attach (feather_host.hip) adds the feather
+  // vector of a Feathermap fit to a SIREN one (fth.p, fth.args): its parameters are then what sf_feather_render_load
+  // materialises, and sf_set_params / sf_params_changed are refused
   bool render = false;
   // graph replay of whole training steps (sf_step): small fits are bound by launch latency, not by the kernels
   struct Graph {
@@ -187,10 +189,12 @@ struct sf_engine {
     int dw_wgs = 0;               // max weight-gradient workgroups along the pixels (slab rows)
   } ff;
   // Feathermap (sf_feather_attach, feather_host.hip): the weights are materialised from [V1 | V2 | scalers], and
-  // sf_adam_step runs adjoint -> Adam on the feather vector -> materialise instead of Adam on W
+  // sf_adam_step runs adjoint -> Adam on the feather vector -> materialise instead of Adam on W.  A render handle
+  // (sf_feather_render_attach) holds args and p alone: every other pointer stays null and nothing launched on it reads one
   struct Feather {
     bool attached = false;
     bool fresh = false;           // g holds the adjoint of the current dL/dW (cleared by every training pass)
+    bool loaded = false;          // render handle: sf_feather_render_load has materialised W at least once
     FthArgs args;
     long nf = 0;                  // 2 n m + 2 D
     float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
@@ -483,5 +487,11 @@ int refuse_render(const char* fn) {
                                                 "only - no gradient, optimiser state, mask or backward scratch");
 }
 #define SF_NO_RENDER(h, fn) do { if ((h) && (h)->render) return refuse_render(fn); } while (0)
+// writing W on a render handle with a feather state (sf_feather_render_attach): W is what the feather vector materialises to
+int refuse_feather_render(const char* fn) {
+  return fail(SF_ERR_INVALID, std::string(fn) + ": the parameters of a feather render handle (sf_feather_render_attach) belong "
+                                                "to its feather vector - load that with sf_feather_render_load");
+}
+#define SF_NO_FEATHER_RENDER(h, fn) do { if ((h) && (h)->render && (h)->fth.attached) return refuse_feather_render(fn); } while (0)
 
 }  // namespace

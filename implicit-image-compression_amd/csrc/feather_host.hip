@@ -1,5 +1,7 @@
 // feather_host.hip — Feathermap (structured multi-hashing, feather_kernels.hip) on the host: materialisation and adjoint as
-// the Adam step of siren_fit.hip calls them, and the four sf_feather_* entry points.  Included by siren_fit.hip.
+// the Adam step of siren_fit.hip calls them, the four sf_feather_* entry points of a training handle, and the two of a
+// render handle (sf_feather_render_attach / sf_feather_render_load: the feather vector and k_fth_mat<true>, nothing of the
+// adjoint).  Included by siren_fit.hip.
 
 namespace {
 
@@ -9,8 +11,35 @@ int feather_materialise(sf_engine* h) {
   const FthArgs& a = h->fth.args;
   const dim3 grid((unsigned)((a.rows_used + kFthTile - 1) / kFthTile), (unsigned)((a.n + kFthTile - 1) / kFthTile));
   Launch L(h, K_FTH_MAT, 2.0 * a.rows_used * a.n * a.m, 4.0 * (2.0 * a.n * a.m + 2.0 * a.P));
-  SF_TRY(launch(h, k_fth_mat, grid, 256, 0, a));
+  SF_TRY(with_bool(h->render, [&](auto render) { return launch(h, k_fth_mat<decltype(render)::value>, grid, 256, 0, a); }));
   h->images_dirty = true;
+  return SF_OK;
+}
+
+// What sf_feather_attach and sf_feather_render_attach share, under the caller's name fn: the depth, the logical layer sizes
+// against the handle's, the segments of V.view(-1) on the handle's flat layout, n and m.  Fills a.seg, n, m, P, rows_used.
+int feather_geometry(const sf_engine* h, const std::string& fn, int64_t n, int64_t m, int32_t n_layers,
+                     const int32_t* logical_out, const int32_t* logical_in, FthArgs& a) {
+  if (n_layers != h->D) return fail(SF_ERR_INVALID, fn + ": n_layers must equal the handle's depth");
+  const int D = h->D;
+  long P = 0;
+  for (int l = 0; l < D; ++l) {
+    const int in_p = l == 0 ? h->cfg.in_features : h->WD, out_p = l == D - 1 ? h->cfg.out_features : h->WD;
+    const int in = logical_in[l], outn = logical_out[l];
+    if (in < 1 || outn < 1 || in > in_p || outn > out_p || (l == 0 && in != in_p) || (l == D - 1 && outn != out_p))
+      return fail(SF_ERR_INVALID, fn + ": logical layer sizes do not fit the handle");
+    a.seg.start[2 * l] = P; a.seg.base[2 * l] = h->off_w[l]; a.seg.cols[2 * l] = in; a.seg.stride[2 * l] = in_p;
+    P += (long)in * outn;
+    a.seg.start[2 * l + 1] = P; a.seg.base[2 * l + 1] = h->off_b[l]; a.seg.cols[2 * l + 1] = outn;
+    a.seg.stride[2 * l + 1] = outn;
+    P += outn;
+  }
+  a.seg.nseg = 2 * D;
+  a.seg.start[2 * D] = P;
+  if (n < 1 || m < 1 || n > 46340 || m > n || n * n < P)
+    return fail(SF_ERR_INVALID, fn + ": need 1 <= m <= n <= 46340 and n^2 >= the parameter count");
+  a.n = (int)n; a.m = (int)m; a.P = P;
+  a.rows_used = (int)((P + n - 1) / n);
   return SF_OK;
 }
 
@@ -48,27 +77,10 @@ int sf_feather_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, cons
   if (h->cfg.row_begin != 0 || h->cfg.row_end != h->cfg.height)
     return fail(SF_ERR_INVALID, "sf_feather_attach: Feathermap fits the whole image (no pixel split)");
   if (h->has_mask) return fail(SF_ERR_INVALID, "sf_feather_attach: the handle has a mask (Feathermap is dense)");
-  if (n_layers != h->D) return fail(SF_ERR_INVALID, "sf_feather_attach: n_layers must equal the handle's depth");
   FthArgs a = zeroed<FthArgs>();
+  SF_TRY(feather_geometry(h, "sf_feather_attach", n, m, n_layers, logical_out, logical_in, a));
   const int D = h->D;
-  long P = 0;
-  for (int l = 0; l < D; ++l) {
-    const int in_p = l == 0 ? h->cfg.in_features : h->WD, out_p = l == D - 1 ? h->cfg.out_features : h->WD;
-    const int in = logical_in[l], outn = logical_out[l];
-    if (in < 1 || outn < 1 || in > in_p || outn > out_p || (l == 0 && in != in_p) || (l == D - 1 && outn != out_p))
-      return fail(SF_ERR_INVALID, "sf_feather_attach: logical layer sizes do not fit the handle");
-    a.seg.start[2 * l] = P; a.seg.base[2 * l] = h->off_w[l]; a.seg.cols[2 * l] = in; a.seg.stride[2 * l] = in_p;
-    P += (long)in * outn;
-    a.seg.start[2 * l + 1] = P; a.seg.base[2 * l + 1] = h->off_b[l]; a.seg.cols[2 * l + 1] = outn;
-    a.seg.stride[2 * l + 1] = outn;
-    P += outn;
-  }
-  a.seg.nseg = 2 * D;
-  a.seg.start[2 * D] = P;
-  if (n < 1 || m < 1 || n > 46340 || m > n || n * n < P)
-    return fail(SF_ERR_INVALID, "sf_feather_attach: need 1 <= m <= n <= 46340 and n^2 >= the parameter count");
-  a.n = (int)n; a.m = (int)m; a.P = P;
-  a.rows_used = (int)((P + n - 1) / n);
+  const long P = a.P;
   std::vector<long> chunks;
   std::vector<int> chunk0;
   for (int k = 0; k < a.seg.nseg; ++k) {
@@ -135,6 +147,51 @@ int sf_feather_adjoint(sf_handle* h) try {
   if (!h->fth.attached) return fail(SF_ERR_STATE, "sf_feather_adjoint: no feather state (sf_feather_attach)");
   DevGuard dev_guard(h->cfg.device);
   return feather_adjoint(h);
+} SF_CATCH
+
+// ---- inference: the feather vector on a render handle ---------------------------------------------------------------
+int sf_feather_render_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, const int32_t* logical_out,
+                             const int32_t* logical_in) try {
+  if (!h || !logical_out || !logical_in) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->render)
+    return fail(SF_ERR_INVALID, "sf_feather_render_attach: a training handle takes sf_feather_attach; this call is for a "
+                                "handle from sf_render_create");
+  switch (h->model) {
+    case Model::Siren: break;
+    case Model::Fourier:
+    case Model::Wavelet:
+      return fail(SF_ERR_INVALID, "sf_feather_render_attach: Feathermap runs on SIREN render handles (sf_render_create) only");
+  }
+  if (h->fth.attached) return fail(SF_ERR_INVALID, "sf_feather_render_attach: the handle already has a feather state");
+  FthArgs a = zeroed<FthArgs>();
+  SF_TRY(feather_geometry(h, "sf_feather_render_attach", n, m, n_layers, logical_out, logical_in, a));
+  const long nf = 2 * n * m + 2L * h->D;
+  DevGuard dev_guard(h->cfg.device);
+  if (dev_alloc(h, h->fth.p, nf * 4)) {
+    (void)hipGetLastError();
+    return fail(SF_ERR_NOMEM, "hipMalloc failed (feather vector)");
+  }
+  HIPCHK(hipMemsetAsync(h->fth.p, 0, nf * 4, h->ctx->stream));
+  HIPCHK(hipMemsetAsync(h->params, 0, h->P * 4, h->ctx->stream));   // padded slots stay exactly 0
+  a.fp = h->fth.p; a.W = h->params;   // (every other pointer stays null: k_fth_mat<true> reads fp and writes W)
+  h->fth.args = a;
+  h->fth.nf = nf;
+  h->fth.attached = true;
+  h->fth.loaded = false;
+  h->images_dirty = true;
+  return SF_OK;
+} SF_CATCH
+
+int sf_feather_render_load(sf_handle* h, const float* feather_dev) try {
+  if (!h || !feather_dev) return fail(SF_ERR_INVALID, "null argument");
+  if (!h->render || !h->fth.attached)
+    return fail(SF_ERR_STATE, "sf_feather_render_load: no feather state (sf_feather_render_attach on a handle from "
+                              "sf_render_create)");
+  DevGuard dev_guard(h->cfg.device);
+  HIPCHK(hipMemcpyAsync(h->fth.p, feather_dev, h->fth.nf * 4, hipMemcpyDeviceToDevice, h->ctx->stream));
+  SF_TRY(feather_materialise(h));
+  h->fth.loaded = true;
+  return SF_OK;
 } SF_CATCH
 
 }  // extern "C"

@@ -14,7 +14,8 @@
 // k slices staged in LDS, each output summed over k in ascending order by one thread.  The scalar gradients are summed
 // in fixed 64 Ki-element chunks (k_fth_grad) whose partials are added in chunk order (last block of k_fth_dv).
 //
-//   k_fth_mat    V = V1 V2 (rows that hold logical entries only); writes V[0, P) and W = scaler * V into the engine
+//   k_fth_mat    V = V1 V2 (rows that hold logical entries only); writes V[0, P) and W = scaler * V into the engine;
+//                its RENDER form (sf_feather_render_load) writes W alone: the unscaled V is the adjoint's operand only
 //   k_fth_grad   G = scaler * dL/dW mapped onto V's layout (the tail stays 0), plus per-chunk partials of dscaler
 //   k_fth_dv     dV1 = G V2^T and dV2 = V1^T G into the feather gradient; one extra block reduces the partials
 // (included by siren_fit.hip after siren_kernels.hip: DEV, k_adam)
@@ -42,7 +43,7 @@ struct FthArgs {
   int rows_used;                // ceil(P / n): rows of V that hold logical entries
   const float* fp;              // feather parameters [V1 n*m | V2 m*n | scalers nseg]
   float* fg;                    // feather gradient, same layout
-  float* V;                     // [P] unscaled V of the last materialisation
+  float* V;                     // [P] unscaled V of the last materialisation (never touched by k_fth_mat<true>)
   float* G;                     // [n*n] scaler * dL/dW on V's layout (tail zero)
   float* W;                     // engine flat parameters
   const float* dW;              // engine flat gradient
@@ -125,7 +126,9 @@ DEV void fth_tile(const float* A, long sar, long sak, const float* B, long sbk, 
   }
 }
 
-// grid: (ceil(rows_used / 64), ceil(n / 64)), 256 threads
+// grid: (ceil(rows_used / 64), ceil(n / 64)), 256 threads.  RENDER: the inference form - the same product, mapping and one
+// multiply by the scalar, so W is bit-identical; it reads a.fp and a.seg and writes a.W, nothing else of a
+template <bool RENDER>
 __global__ void __launch_bounds__(256) k_fth_mat(FthArgs a) {
   __shared__ __attribute__((aligned(16))) float As[kFthKT * kFthPitch];
   __shared__ __attribute__((aligned(16))) float Bs[kFthKT * kFthPitch];
@@ -144,7 +147,7 @@ __global__ void __launch_bounds__(256) k_fth_mat(FthArgs a) {
       const long e = (long)r * n + c;
       if (r < n && c < n && e < a.P) {
         const int k = fth_seg_of(s, a.seg.nseg, e);
-        a.V[e] = acc[i][j];
+        if constexpr (!RENDER) a.V[e] = acc[i][j];
         a.W[fth_engine_index(s, k, e)] = s.scal[k] * acc[i][j];
       }
     }

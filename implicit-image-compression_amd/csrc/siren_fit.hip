@@ -113,7 +113,7 @@ constexpr int kBwd8hPark = 4;   // k_bwd8h: k-steps of every wave's stationary W
     SF_K(k_fwd<64, OpBF16, false, false, true>), SF_K(k_fwd<128, OpF16, false, false, true>),
     SF_K(k_fwd<128, OpBF16, false, false, true>), SF_K(k_fwd<256, OpF16, false, false, true>),
     SF_K(k_fwd<256, OpBF16, false, false, true>), SF_K(k_ff_fwd<32, false, true>), SF_K(k_ff_fwd<64, false, true>),
-    SF_K(k_ff_fwd<128, false, true>), SF_K(k_ff_fwd<256, false, true>),
+    SF_K(k_ff_fwd<128, false, true>), SF_K(k_ff_fwd<256, false, true>), SF_K(k_fth_mat<false>), SF_K(k_fth_mat<true>),
 };
 #undef SF_K
 
@@ -210,6 +210,7 @@ static int copy_out(sf_engine* h, float* dst, const float* src) {
   return SF_OK;
 }
 int sf_set_params(sf_handle* h, const float* p) try {
+  SF_NO_FEATHER_RENDER(h, "sf_set_params");
   int rc = copy_in(h, h ? h->params : nullptr, p);
   if (!rc) h->images_dirty = true;
   return rc;
@@ -296,6 +297,7 @@ int sf_debug_scratch(sf_handle* h, int32_t which, void** p, int64_t* bytes) try 
 
 int sf_params_changed(sf_handle* h) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_FEATHER_RENDER(h, "sf_params_changed");
   h->images_dirty = true;
   return SF_OK;
 } SF_CATCH

@@ -151,6 +151,8 @@ int render_any(sf_handle* h, void* out, int bits, float* pred) {
     return fail(SF_ERR_INVALID, fn + ": built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create) "
                                      "and FourierNet handles (sf_fourier_create / sf_fourier_render_create)");
   if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
+  if (h->render && h->fth.attached && !h->fth.loaded)
+    return fail(SF_ERR_STATE, fn + ": sf_feather_render_load has not been called (the handle has a feather state and no weights yet)");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   switch (h->model) {
     case Model::Siren: break;

@@ -106,6 +106,8 @@ _declare("feather", {
     "sf_feather_attach": [H, I64, I64, I32, P(I32), P(I32)],
     "sf_feather_state_ptr": [H, I32, P(C.c_void_p), P(I64)],
     "sf_feather_materialise": [H], "sf_feather_adjoint": [H],
+    "sf_feather_render_attach": [H, I64, I64, I32, P(I32), P(I32)],
+    "sf_feather_render_load": [H, F],
 })
 _declare("wavelet", {
     "sf_wavelet_create": [P(sf_wavelet_config), P(H)],
@@ -472,7 +474,7 @@ class RenderEngine(SirenEngine):
     gradient, optimiser state, mask or backward scratch.  set_params / get_params / set_coords / render / the profiling
     calls work; every training call raises with the library's message.  set_coords takes any two vectors (a window of a
     grid is a slice of its linspace vectors); hidden 512 / 1024 is refused (no render kernel on the wide path; FourierNet
-    has FourierRenderEngine, WaveletSiren has WaveletRenderEngine)."""
+    has FourierRenderEngine, WaveletSiren has WaveletRenderEngine, a Feathermap fit FeatherRenderEngine)."""
 
     def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
                  hidden_omega_0: float = 30.0, outermost_linear: bool = True, out_features: int = 3,
@@ -481,6 +483,35 @@ class RenderEngine(SirenEngine):
                          compute_dtype, device, row_begin, row_end, chunk_pixels)
 
     _CREATE, _CREATE_NEEDS = "sf_render_create", (has_render, "sf_render_create entry point", "the render path")
+
+
+class FeatherRenderEngine(RenderEngine):
+    """Inference-only handle of a Feathermap fit (sf_render_create + sf_feather_render_attach): what RenderEngine holds plus
+    the feather vector [V1 | V2 | scalers] of feather_elems floats - no gradient, moments, unscaled V or adjoint scratch.
+    load_feather materialises W = scaler * (V1 V2) with the training handle's own fixed-order product, so get_params and
+    render are bit-identical to a FeatherNet training handle's with the same vector.  n, m: the sides of V1 [n, m] and
+    V2 [m, n]; logical_out / logical_in: each Linear's logical size (hidden is the engine width, which may be padded).
+    set_params raises with the library's message: the parameters belong to the feather vector."""
+
+    def __init__(self, height: int, width: int, hidden: int, depth: int, n: int, m: int, logical_out: Sequence[int],
+                 logical_in: Sequence[int], first_omega_0: float = 50.0, hidden_omega_0: float = 30.0,
+                 outermost_linear: bool = True, out_features: int = 3, compute_dtype: str = "f16", device: int = 0,
+                 row_begin: int = 0, row_end: int = 0, chunk_pixels: int = 0):
+        _require(load_library(), has_feather, "sf_feather_render_* entry points", "the Feathermap render path")
+        super().__init__(height, width, hidden, depth, first_omega_0, hidden_omega_0, outermost_linear, out_features,
+                         compute_dtype, device, row_begin, row_end, chunk_pixels)
+        D = len(logical_out)
+        try:
+            _check(self.lib.sf_feather_render_attach(self.h, n, m, D, (C.c_int32 * D)(*logical_out),
+                                                     (C.c_int32 * D)(*logical_in)))
+        except Exception:
+            self.close()
+            raise
+        self.feather_elems = 2 * n * m + 2 * D
+
+    def load_feather(self, flat: torch.Tensor):
+        """sf_feather_render_load: [V1 | V2 | scalers] (fp32, on the device, copied), then W; no host sync"""
+        _check(self.lib.sf_feather_render_load(self.h, _f32_cuda(flat, self.feather_elems).data_ptr()))
 
 
 _FOURIER_RENDER = (has_fourier_render, "sf_fourier_render_create entry point", "the FourierNet render path")

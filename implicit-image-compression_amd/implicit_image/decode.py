@@ -39,6 +39,12 @@ mlp=fourier of engine width <= 256 has a render kernel too (sf_render on an sf_f
 form of k_ff_fwd, `render_fourier`): windows are slices of the coordinate vectors, decode.band_rows applies, and no
 activation plane or full fp32 prediction is allocated.  `render_path` still answers torch for it, so it runs under
 decode.render=kernel only; the bytes of the two paths are the same.
+
+A masking=Feathermap run (model.pth holds the feather vector [V1 | V2 | scalers], not the network) goes its own way:
+`load_feather` reads and checks the vector, and at engine width <= 256 one FeatherRenderEngine takes it
+(sf_feather_render_load: W = scaler * (V1 V2) by the engine's own fixed-order product, then sf_render), so the picture is
+bit for bit the one whose PSNR `fit` logged.  Every decode.* key above applies.  decode.render=torch, or width 512 / 1024,
+rebuilds the FeatherNet and runs its own forward; there is no container for such a run (decode.source=container raises).
 """
 import json
 import logging
@@ -184,6 +190,104 @@ def load_weights(run_dir: str, shape: Cfg, source: Optional[str] = None) -> Tupl
     return sd, used
 
 
+# ---- Feathermap: the feather vector of model.pth -------------------------------------------------------------
+def is_feather(shape: Cfg) -> bool:
+    return shape.get("masking_name") == "Feathermap"
+
+
+def _feather_layers(shape: Cfg) -> Tuple[List[int], List[int]]:
+    """(logical_out, logical_in) of every Linear of the SIREN of `shape`"""
+    m = shape.mlp
+    fans = [int(m.get("input_size", 2))] + [engine_width(shape)] * (int(m.depth) - 1) + [int(m.get("output_size", 3))]
+    return fans[1:], fans[:-1]
+
+
+def feather_keys(depth: int) -> List[str]:
+    """the state-dict keys of a FeatherNet over a SIREN of `depth` layers, in named_parameters() order"""
+    return ["_V1", "_V2"] + [f"module.layers.{l}.linear.{kind}_p" for l in range(depth) for kind in ("weight", "bias")]
+
+
+def load_feather(run_dir: str, shape: Cfg, source: Optional[str] = None) -> "OrderedDict[str, torch.Tensor]":
+    """The fp32 CPU state dict of a masking=Feathermap run's model.pth: _V1 [n, m], _V2 [m, n] and one scalar per weight /
+    bias tensor, checked against decode.json's key list and against the network of `shape` (n = ceil(sqrt(P))).  A tensor
+    that is missing or of another shape raises a ValueError that names it."""
+    if source not in (None, "", "container", "pth"):
+        raise ValueError(f"decode.source must be container or pth, got {source!r}")
+    if source == "container":
+        raise FileNotFoundError("decode.source=container: a masking=Feathermap run has no container (fit writes model.pth, the "
+                                "feather vector in fp32, and nothing under model_quantized/)")
+    pth = os.path.join(run_dir, "model.pth")
+    if not os.path.exists(pth):
+        raise FileNotFoundError(f"{pth} not found (a masking=Feathermap run is decoded from model.pth)")
+    blob = torch.load(pth, map_location="cpu")
+    sd = blob["state_dict"] if isinstance(blob, dict) and "state_dict" in blob else blob
+    sd = OrderedDict((k, v.detach().float().cpu()) for k, v in sd.items())
+    for k in feather_keys(int(shape.mlp.depth)):
+        if k not in sd:
+            raise ValueError(f"pth: the feather vector has no tensor {k}")
+    want = shape.get("state_dict_keys")
+    if want and sorted(want) != sorted(sd.keys()):
+        raise ValueError(f"pth: tensors {sorted(sd.keys())} do not match the fit's state dict {sorted(want)}")
+    for k in feather_keys(int(shape.mlp.depth))[2:]:
+        if sd[k].numel() != 1:
+            raise ValueError(f"pth: {k} has shape {tuple(sd[k].shape)}, a scalar was expected")
+    feather_geometry(shape, sd)
+    return sd
+
+
+def feather_geometry(shape: Cfg, sd) -> Tuple[int, int, List[int], List[int]]:
+    """(n, m, logical_out, logical_in) as sf_feather_render_attach takes them: V1 is [n, m], V2 [m, n], and n must be
+    ceil(sqrt(P)) for the P weights and biases of the SIREN of `shape` (feathernet.py:186); else a ValueError naming the
+    tensor"""
+    outs, ins = _feather_layers(shape)
+    P = sum(o * i + o for o, i in zip(outs, ins))
+    n = math.isqrt(P - 1) + 1                      # ceil(sqrt(P)), in integers
+    v1, v2 = tuple(sd["_V1"].shape), tuple(sd["_V2"].shape)
+    if len(v1) != 2 or v1[0] != n or not 1 <= v1[1] <= n:
+        raise ValueError(f"_V1 has shape {v1}: the network of decode.json has {P} weights and biases, so V1 is [{n}, m] with "
+                         f"1 <= m <= {n}")
+    m = v1[1]
+    if v2 != (m, n):
+        raise ValueError(f"_V2 has shape {v2}, [{m}, {n}] was expected (the transpose of _V1's {v1})")
+    return n, m, outs, ins
+
+
+def feather_flat(sd, depth: int) -> torch.Tensor:
+    """[V1 | V2 | scalers]: the feather vector in FeatherNet.named_parameters() order, flat fp32"""
+    return torch.cat([sd[k].reshape(-1) for k in feather_keys(depth)]).float().contiguous()
+
+
+def feather_model(sd, shape: Cfg):
+    """the FeatherNet of `shape` with `sd` loaded, on the CPU: the registry SIREN under compress = (2 m - 1) / n, which
+    ceil(compress * n / 2) turns back into m"""
+    from .models import registry
+    from .pipeline.feathermap import FeatherNet
+    n, m, _, _ = feather_geometry(shape, sd)
+    with torch.random.fork_rng(devices=[]):       # the constructors draw an initialisation nobody needs
+        net = FeatherNet(registry["siren"](**dict(shape.mlp), **dict(shape.get("engine") or {})), compress=(2 * m - 1) / n)
+    assert (net._size_n, net._size_m) == (n, m), ((net._size_n, net._size_m), (n, m))
+    net.load_state_dict(sd)
+    return net
+
+
+def render_feather(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
+                   want_pred: bool = False, device: int = 0, bits: int = 8):
+    """render_kernel for a masking=Feathermap run: uint8 [h, w, C] on the CPU (and the fp32 prediction when asked) of the
+    grid rows x cols, band by band on ONE FeatherRenderEngine that materialised the weights once.  bits=16: int32 values
+    0..65535 from sf_render16."""
+    from ._engine import FeatherRenderEngine
+    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
+    C = int(m.get("output_size", 3))
+    n, fm, outs, ins = feather_geometry(shape, sd)
+    bands = plan_bands(rows.numel(), cols.numel(), C, band_rows, sample_bytes=bits // 8)
+    eng = FeatherRenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.depth), n, fm, outs, ins,
+                              float(m.get("first_omega_0", 50.0)), float(m.get("hidden_omega_0", 30.0)),
+                              bool(m.get("outermost_linear", True)), C, eng_kw.get("compute_dtype", "f16"), device=device,
+                              chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
+    return _render_grid(eng, lambda e: e.load_feather(feather_flat(sd, int(m.depth)).to(e.device)), rows, cols, bands,
+                        want_pred, bits)
+
+
 # ---- bytes ------------------------------------------------------------------------------------------------
 def to_u8(pred: torch.Tensor) -> torch.Tensor:
     """min(max(trunc(pred * 255), 0), 255) as uint8: eval_epoch's (pred * 255).int(), clamped to what a file can hold.
@@ -259,6 +363,8 @@ def render_path(shape: Cfg, height: Optional[int] = None, width: Optional[int] =
         return "kernel", f"WaveletSiren {wp}x{shape.mlp.depth}{pad}: sf_wavelet_render"
     if wp not in KERNEL_WIDTHS:
         return "torch", f"SIREN width {w} is on the wide path: no render kernel"
+    if is_feather(shape):
+        return "kernel", f"Feathermap {wp}x{shape.mlp.depth}{pad}: sf_feather_render_load + sf_render"
     return "kernel", f"SIREN {wp}x{shape.mlp.depth}{pad}: sf_render"
 
 
@@ -488,7 +594,7 @@ def render_torch(sd, shape: Cfg, height: int, width: int, r: Tuple[int, int], c:
     values 0..65535 by to_u16)"""
     from .data import get_grid
     dev = torch.device("cuda", device)
-    model = registry_model(sd, shape).to(dev).eval()
+    model = (feather_model if is_feather(shape) else registry_model)(sd, shape).to(dev).eval()
     with torch.no_grad():
         pred = model(get_grid(height, width).to(dev))
     pred = pred[r[0]:r[1], c[0]:c[1]].contiguous()
@@ -528,7 +634,10 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
     W = int(dec.get("width") or shape.img.get("width") or 0)
     if mode == "kernel":                           # no render kernel: refused before a file is read or the device touched
         choose_path(shape, mode, H, W)
-    sd, source = load_weights(run_dir, shape, dec.get("source"))
+    if is_feather(shape):                          # model.pth holds the feather vector, not the network
+        sd, source = load_feather(run_dir, shape, dec.get("source")), "pth"
+    else:
+        sd, source = load_weights(run_dir, shape, dec.get("source"))
     if H < 1 or W < 1:
         raise ValueError("output size unknown: pass decode.height=... decode.width=... (or img.height / img.width)")
     r, c = _span(dec.get("rows"), H, "rows"), _span(dec.get("cols"), W, "cols")
@@ -546,7 +655,7 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
             u8, pred = render_wavelet(sd, shape, H, r, c, band_rows, want_pred=bool(truth), device=device, bits=bits)
         else:
             rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
-            u8, pred = (render_fourier if name == "fourier" else render_kernel)(
+            u8, pred = (render_feather if is_feather(shape) else render_fourier if name == "fourier" else render_kernel)(
                 sd, shape, rows, cols, band_rows, want_pred=bool(truth), device=device, bits=bits)
     else:
         u8, pred = render_torch(sd, shape, H, W, r, c, device=device, bits=bits)
@@ -554,7 +663,7 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
         raise NotImplementedError(f"PPM holds 3 channels, the model has {u8.shape[-1]}")
     out = dec.get("out") or os.path.join(run_dir, "decoded.ppm")
     (write_ppm16 if bits == 16 else write_ppm)(out, u8)   # (bits = 16: u8 holds the 16-bit samples)
-    res = {"out": out, "path": path, "source": source, "height": int(u8.shape[0]), "width": int(u8.shape[1])}
+    res = {"out": out, "path": path, "why": why, "source": source, "height": int(u8.shape[0]), "width": int(u8.shape[1])}
     if truth:
         img = load_truth(truth, H, W)[r[0]:r[1], c[0]:c[1]]
         res.update(metrics(pred, to_u8(pred), img, u8) if bits == 16 else metrics(pred, u8, img))

@@ -303,6 +303,21 @@ int sf_feather_state_ptr(sf_handle* h, int32_t which, float** dev_ptr, int64_t* 
 int sf_feather_materialise(sf_handle* h);
 /* dV1, dV2 and the scalar gradients from the current dL/dW into the feather gradient (sf_adam_step reuses them) */
 int sf_feather_adjoint(sf_handle* h);
+/* Inference only: the feather vector on a render handle.  sf_feather_render_attach works on a SIREN handle from
+ * sf_render_create (a training handle - which takes sf_feather_attach -, a FourierNet or WaveletSiren render handle, a second
+ * attach and any bad size return SF_ERR_INVALID).  It validates what sf_feather_attach validates (n_layers, the logical sizes,
+ * 1 <= m <= n <= 46340, n^2 >= P), allocates the feather vector (2 n m + 2 depth floats) and nothing else - no gradient,
+ * moments, unscaled V, G, partials or chunk tables - and zeroes the parameters, so padded slots stay exactly 0.
+ * sf_feather_render_load copies the vector on the handle's stream and materialises W = scaler * (V1 V2) with the inference
+ * form of the training handle's kernel (the same fixed-order product, no store of the unscaled V): W, and with it the
+ * picture, is bit-identical to a training handle's with the same vector.  No host synchronisation; before attach it returns
+ * SF_ERR_STATE.  On an attached handle sf_render / sf_render16 before the first load return SF_ERR_STATE, sf_set_params and
+ * sf_params_changed return SF_ERR_INVALID (the parameters belong to the feather vector), and sf_get_params (W),
+ * sf_state_ptr(0), sf_set_coords, sf_num_params, sf_param_offset, the profiling calls (the materialisation counts under
+ * k_feather_mat) and sf_destroy work as on any render handle. */
+int sf_feather_render_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layers, const int32_t* logical_out,
+                             const int32_t* logical_in);
+int sf_feather_render_load(sf_handle* h, const float* feather_dev /* [2 n m + 2 depth] fp32, copied */);
 
 /* measurement: per-kernel HIP-event timing on the handle's stream */
 int sf_profile_enable(sf_handle* h, int32_t on);

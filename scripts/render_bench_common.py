@@ -1,5 +1,6 @@
-"""What the three render bench scripts (render_bench.py, wavelet_render_bench.py, fourier_render_bench.py) share: the device
-note, HIP-event timing and its statistics, the alternating-block leg runner and the fresh-process handle-memory probe."""
+"""What the four render bench scripts (render_bench.py, wavelet_render_bench.py, fourier_render_bench.py,
+feather_render_bench.py) share: the device note, HIP-event timing and its statistics, the alternating-block leg runner and
+the fresh-process handle-memory probe."""
 import json
 import os
 import statistics
