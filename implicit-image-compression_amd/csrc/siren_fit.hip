@@ -5,6 +5,7 @@
 // One sf_engine == one per-image fit on one HIP stream.  A training step is, per pixel chunk:
 //   k_fwd -> k_bwd(last) -> k_bwd(hidden l = depth-2 .. 1) -> k_dw0, each followed by the fixed-order slab
 //   reduction into the flat fp32 gradient; then k_adam (+mask) and k_images (16-bit weight images).
+// Every `interval` steps of a masked fit the topology changes: sf_mask_update (siren_mask.hip), two more launches.
 // The sequence mirrors one `train_epoch` of the reference (implicit_image/utils/train_helper.py:132-185)
 // for the full-batch grid (implicit_image/compress.py:137-138).
 #include "siren_kernels.hip"
@@ -15,6 +16,7 @@
 #include "fourier_kernels.hip"
 #include "feather_kernels.hip"
 #include "wavelet_kernels.hip"
+#include "siren_mask.hip"
 
 #include "engine.h"
 
@@ -587,6 +589,48 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
   SF_TRY(launch(h, k_km_finish, 1, kKmMaxK, 0, centers_dev, K, h->km_ws, centroids_dev, centroids_cap, n_centroids_dev));
   if (labels_dev || new_weight_dev)
     SF_TRY(launch(h, k_km_predict, blocks, 256, 0, w_dev, n, centroids_dev, h->km_ws, (long long*)labels_dev, new_weight_dev));
+  return SF_OK;
+} SF_CATCH
+
+/* one RigL topology update of the masked layers on the handle's stream: two launches, no host synchronisation
+ * (siren_mask.hip states what it computes) */
+int sf_mask_update(sf_handle* h, const sf_mask_update_args* a) try {
+  if (!h || !a || !a->layers) return fail(SF_ERR_INVALID, "null argument");
+  if (a->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
+  SF_NO_RENDER(h, "sf_mask_update");
+  switch (h->model) {
+    case Model::Siren: break;
+    case Model::Fourier: return fail(SF_ERR_INVALID, "sf_mask_update: a FourierNet handle takes no mask");
+    case Model::Wavelet: return fail(SF_ERR_INVALID, "sf_mask_update: topology updates of a WaveletSiren handle stay on the host");
+  }
+  if (h->fth.attached) return fail(SF_ERR_INVALID, "sf_mask_update: a Feathermap handle is dense (masking.dense: True)");
+  if (!h->has_mask) return fail(SF_ERR_STATE, "sf_mask_update: sf_set_masks has not been called");
+  if (a->growth != 0 && a->growth != 1) return fail(SF_ERR_INVALID, "sf_mask_update: growth must be 0 (none) or 1 (absolute gradient)");
+  if (a->n_layers < 1 || a->n_layers > h->D || a->n_layers > kMaskMaxLayers)
+    return fail(SF_ERR_INVALID, "sf_mask_update: n_layers must be 1 .. depth");
+  static_assert(sizeof(MaskRow) == sizeof(sf_mask_layer_stats), "MaskRow is sf_mask_layer_stats");
+  MaskArgs k = zeroed<MaskArgs>();
+  double bytes = 0;
+  for (int j = 0; j < a->n_layers; ++j) {
+    const int l = a->layers[j];
+    if (l < 0 || l >= h->D || (j > 0 && l <= a->layers[j - 1]))
+      return fail(SF_ERR_INVALID, "sf_mask_update: layers must be ascending indices in [0, depth)");
+    k.off[j] = h->off_w[l];
+    k.n[j] = (int)(h->off_b[l] - h->off_w[l]);
+    bytes += (double)k.n[j] * 4;
+  }
+  DevGuard dev_guard(h->cfg.device);
+  if (!a->stats_dev && !h->mask_rows) SF_TRY(dev_alloc(h, h->mask_rows, sizeof(MaskRow) * (kMaskMaxLayers + 1)));
+  k.w = h->params; k.g = h->grads; k.m = h->m; k.v = h->v; k.k = h->mask;
+  k.rows = a->stats_dev ? reinterpret_cast<MaskRow*>(a->stats_dev) : h->mask_rows;
+  k.L = a->n_layers; k.rate = a->prune_rate; k.growth = a->growth; k.dense = a->dense_gradients != 0;
+  {
+    Launch L(h, K_MASK, 0, bytes * 12);   // (about a dozen L2-resident reads of every masked layer)
+    SF_TRY(launch(h, k_mask_count, k.L, kMaskThreads, 0, k));
+    SF_TRY(launch(h, k_mask_update, k.L, kMaskThreads, 0, k));
+  }
+  h->images_dirty = true;
+  h->fth.fresh = false;
   return SF_OK;
 } SF_CATCH
 

@@ -61,6 +61,20 @@ class sf_wavelet_render_config(C.Structure):
     ]
 
 
+class sf_mask_layer_stats(C.Structure):
+    _fields_ = [("live_before", C.c_int64), ("dead_before", C.c_int64), ("nnz_before", C.c_int64), ("removed", C.c_int64),
+                ("live_after", C.c_int64), ("dead_after", C.c_int64), ("nnz_after", C.c_int64), ("prune_rate", C.c_double)]
+
+
+class sf_mask_update_args(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("n_layers", C.c_int32), ("layers", C.POINTER(C.c_int32)),
+                ("prune_rate", C.c_double), ("growth", C.c_int32), ("dense_gradients", C.c_int32),
+                ("stats_dev", C.c_void_p)]
+
+
+MASK_STATS_WORDS = C.sizeof(sf_mask_layer_stats) // 8      # a statistics row as int64 words (the last one: a double)
+MASK_GROWTH = {"none": 0, "absolute-gradient": 1}
+
 _lib = None
 
 H, F, I32, I64, P = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER      # H: sf_handle*, F: device float*
@@ -124,6 +138,9 @@ _declare("wavelet_render", {
     "sf_wavelet_render16": [H, I32, I32, I32, I32, C.c_void_p, F],
 })
 _declare("fourier_render", {"sf_fourier_render_create": [P(sf_fourier_config), P(H)]})
+# (the RigL topology update on the device, csrc/siren_mask.hip.  In "core" like sf_render16: has_mask_update asks for the
+# symbol itself, Masking routes by it)
+_declare("core", {"sf_mask_update": [H, P(sf_mask_update_args)]})
 
 
 def load_library():
@@ -180,6 +197,11 @@ def has_wavelet_render(lib) -> bool:
 def has_fourier_render(lib) -> bool:
     """sf_fourier_render_create, and with it sf_render on FourierNet handles (csrc/fourier_render.hip)"""
     return has_render(lib) and _has(lib, "fourier_render")
+
+
+def has_mask_update(lib) -> bool:
+    """sf_mask_update: Masking.update_connections() on the device (csrc/siren_mask.hip)"""
+    return hasattr(lib, "sf_mask_update")
 
 
 def _require(lib, has, entry: str, since: str):
@@ -346,6 +368,22 @@ class SirenEngine:
         _check(self.lib.sf_kmeans_fit(self.h, w.data_ptr(), w.numel(), centers.data_ptr(), K, iter_limit, tol, cent.data_ptr(), K + 1,
                                       ncent.data_ptr(), labels.data_ptr(), new_w.data_ptr()))
         return cent, ncent, labels.reshape(weight.shape), new_w.reshape(weight.shape)
+
+    def mask_update(self, layers: Sequence[int], prune_rate: float, growth: int, dense_gradients: bool,
+                    stats: Optional[torch.Tensor] = None):
+        """sf_mask_update on this handle's stream, no host sync: one RigL topology update of the weights of `layers`
+        (ascending engine layer indices) in the handle's params / grads / moments / masks.  stats: int64
+        [len(layers) + 1, MASK_STATS_WORDS] on the device or None - a sf_mask_layer_stats per layer (the last word is the
+        bits of the double prune rate) and the status row."""
+        _require(self.lib, has_mask_update, "sf_mask_update entry point", "the device topology update")
+        n = len(layers)
+        if stats is not None and not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous()
+                                      and stats.numel() == (n + 1) * MASK_STATS_WORDS):
+            raise ValueError(f"mask_update: stats must be a contiguous int64 CUDA tensor of {(n + 1) * MASK_STATS_WORDS} words")
+        args = sf_mask_update_args(abi_version=SF_ABI_VERSION, n_layers=n, layers=(C.c_int32 * max(n, 1))(*layers),
+                                   prune_rate=float(prune_rate), growth=int(growth), dense_gradients=int(bool(dense_gradients)),
+                                   stats_dev=None if stats is None else stats.data_ptr())
+        _check(self.lib.sf_mask_update(self.h, C.byref(args)))
 
     def params_changed(self):
         _check(self.lib.sf_params_changed(self.h))
@@ -531,6 +569,7 @@ class FourierEngine(SirenEngine):
         self.map_size = map_size
 
     _CREATE = "sf_fourier_create"
+    mask_update = None          # sf_mask_update refuses a FourierNet handle: Masking keeps such a model on the host path
 
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
@@ -572,6 +611,7 @@ class WaveletEngine(SirenEngine):
         self.n = (height + 5) // 2
 
     _CREATE = "sf_wavelet_create"
+    mask_update = None          # sf_mask_update refuses a WaveletSiren handle: its topology updates stay on the host
 
     def set_coords(self, rows: torch.Tensor, cols: torch.Tensor):
         """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""

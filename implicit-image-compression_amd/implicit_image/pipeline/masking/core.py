@@ -10,8 +10,14 @@ Supported registry keys: sparse_init erdos-renyi(-kernel) | random | resume; pru
 global-magnitude; growth_mode absolute-gradient | momentum | random | none; redistribution_mode none |
 nonzero | momentum | grad; decay cosine | linear | magnitude-prune.  (The struct-* modes act on 4-D conv
 kernels and have no meaning for a SIREN; lottery-ticket init loads a pickle and is not provided.)
+
+`update_connections()` of the configuration RigL ships with (magnitude pruning, absolute-gradient or no growth, no
+redistribution) runs on the device when the model is engine-bound: one `sf_mask_update` call, no read-back (DESIGN.md
+section 12).  `stats`, `name2prune_rate`, `adjustments` and `adjusted_growth` are then completed on their first read.
 """
 import logging
+import os
+import struct
 from dataclasses import dataclass, field
 from typing import Dict
 
@@ -42,13 +48,16 @@ class LayerStats:
 class Masking:
     def __init__(self, optimizer, prune_rate_decay, density: float = 0.2, sparse_init: str = "random",
                  dense_gradients: bool = False, prune_mode: str = "magnitude", growth_mode: str = "momentum",
-                 redistribution_mode: str = "momentum", input_size=(1, 3, 32, 32)):
+                 redistribution_mode: str = "momentum", input_size=(1, 3, 32, 32), device_update: str = "auto"):
         assert sparse_init in init_registry, f"Sparse init {sparse_init} not found. Available {init_registry.keys()}"
         assert growth_mode in grow_registry or growth_mode == "none", \
             f"Available growth modes: {','.join(grow_registry.keys())}"
         assert prune_mode in prune_registry, f"Available prune modes: {','.join(prune_registry.keys())}"
         assert redistribution_mode in redistribute_registry, \
             f"Available redistribute modes: {','.join(redistribute_registry.keys())}"
+        assert device_update in ("auto", "off"), "device_update: 'auto' (sf_mask_update where it applies) or 'off'"
+        self.device_update = device_update
+        self._pending = []                      # device updates whose statistics rows have not been read yet
         self.optimizer, self.prune_rate_decay = optimizer, prune_rate_decay
         self.density, self.sparse_init, self.dense_gradients = density, sparse_init, dense_gradients
         self.prune_mode, self.growth_mode, self.redistribution_mode = prune_mode, growth_mode, redistribution_mode
@@ -58,14 +67,54 @@ class Masking:
         self.mask_step = 0
         self.baseline_nonzero = 0
         self.total_params = 0
-        self.adjusted_growth = 0
-        self.adjustments = []
-        self.name2prune_rate = {}
-        self.stats = LayerStats()
+        self._adjusted_growth = 0
+        self._adjustments = []
+        self._name2prune_rate = {}
+        self._stats = LayerStats()
         self._pushed_engine = None
         # global growth/prune state (core.py:151-156)
         self.prune_threshold, self.growth_threshold = 0.001, 0.001
         self.growth_increment, self.increment, self.tolerance = 0.2, 0.2, 1e-6
+
+    # ---- bookkeeping a device update completes on its first read --------------------------------
+    def _lazy(attr):
+        def get(self):
+            self._complete()
+            return getattr(self, attr)
+
+        def put(self, value):
+            self._complete()
+            setattr(self, attr, value)
+        return property(get, put)
+
+    stats = _lazy("_stats")
+    name2prune_rate = _lazy("_name2prune_rate")
+    adjustments = _lazy("_adjustments")
+    adjusted_growth = _lazy("_adjusted_growth")
+    del _lazy
+
+    def _complete(self):
+        """The host-side bookkeeping of every pending device update, oldest first, from ONE copy of its statistics rows:
+        exactly the values, and the float sequence, of truncate_weights() below."""
+        while self._pending:
+            rows, names = self._pending.pop(0)
+            rows = rows.cpu().tolist()
+            assert not rows[len(names)][0], "Total variance is zero!"
+            live, dead, nnz = {}, {}, {}
+            for pname, row in zip(names, rows):
+                self._name2prune_rate[pname] = struct.unpack("<d", struct.pack("<q", row[7]))[0]
+                live[pname], dead[pname], nnz[pname] = row[4], row[5], row[6]
+            total_nonzero_new = sum(live.values())
+            self._adjustments.append(self.baseline_nonzero - total_nonzero_new)
+            self._adjusted_growth = (0.25 * self._adjusted_growth + 0.75 * self._adjustments[-1]
+                                     + np.mean(self._adjustments))
+            norm = 0.0
+            for v in nnz.values():              # (summed in layer order, as gather_statistics does)
+                norm += v
+            assert norm, "Total variance is zero!"
+            self._stats = LayerStats(variance_dict={k: v / norm for k, v in nnz.items()}, nonzeros_dict=live,
+                                     zeros_dict=dead, total_variance=norm, total_nonzero=sum(live.values()),
+                                     total_zero=sum(dead.values()))
 
     # ---- properties -------------------------------------------------------------------------
     @property
@@ -261,7 +310,54 @@ class Masking:
         self.adjusted_growth = 0.25 * self.adjusted_growth + 0.75 * self.adjustments[-1] + np.mean(self.adjustments)
         self.gather_statistics()
 
+    def _device_plan(self):
+        """(engine, layer indices, [(name, flat offset, shape)]) when this update can run as sf_mask_update, else None: an
+        engine with the entry point under an unpadded model, every masked parameter the weight of an engine layer living
+        in the engine's own vectors (data, gradient and - where the moments are masked too - Adam state), the modes RigL
+        ships with, and SIREN_FIT_DEVICE_MASK not "0" (an A/B knob, like SIREN_FIT_NATIVE_KMEANS)."""
+        from ... import _engine
+        eng = self.module.bound_engine
+        if (self.device_update != "auto" or eng is None or os.environ.get("SIREN_FIT_DEVICE_MASK") == "0"
+                or self.module._padded or self.prune_mode != "magnitude"
+                or self.growth_mode not in _engine.MASK_GROWTH or self.redistribution_mode not in ("none", "nonzero")
+                or not callable(getattr(eng, "mask_update", None)) or not _engine.has_mask_update(eng.lib)):
+            return None
+        views = [eng.view("params"), eng.view("grads")]
+        if not self.dense_gradients:
+            views += [eng.view("exp_avg"), eng.view("exp_avg_sq")]
+        masked = {id(par): pname for pname, par, _ in self._masked()}
+        layers, slices, off = [], [], 0
+        for pos, par in enumerate(self.module._param_list()):
+            pname, n = masked.pop(id(par), None), par.numel()
+            if pname is not None:
+                st = self.optimizer.state.get(par, {}) if not self.dense_gradients else {}
+                held = [par.data, par.grad] + [st[k] for k in ("exp_avg", "exp_avg_sq") if k in st]
+                if (pos % 2 or par.device != eng.device or eng.param_offsets(pos // 2) != (off, off + n)
+                        or any(t is None or t.data_ptr() != v[off:].data_ptr() for t, v in zip(held, views))):
+                    return None
+                layers.append(pos // 2)
+                slices.append((pname, off, par.shape))
+            off += n
+        return None if masked or not layers else (eng, layers, slices)
+
+    @torch.no_grad()
+    def _device_update(self, eng, layers, slices):
+        """update_connections() as one sf_mask_update: nothing is read back here."""
+        from ... import _engine
+        self._push_masks()                      # mask_dict is the truth (callers replace its entries)
+        rows = torch.empty(len(layers) + 1, _engine.MASK_STATS_WORDS, dtype=torch.int64, device=eng.device)
+        eng.mask_update(layers, self.prune_rate, _engine.MASK_GROWTH[self.growth_mode], self.dense_gradients, rows)
+        flat = eng.view("masks")
+        for pname, off, shape in slices:        # own tensors, never views: a re-made handle frees the old mask vector
+            del self.mask_dict[pname]
+            self.mask_dict[pname] = flat[off:off + shape.numel()].view(shape).clone()
+        self.mask_step += 1
+        self._pending.append((rows, [pname for pname, _, _ in slices]))
+
     def update_connections(self):
+        plan = self._device_plan()
+        if plan is not None:
+            return self._device_update(*plan)
         self.truncate_weights()
 
     # ---- checkpoint surface (core.py:495-506, 660-669) -----------------------------------------

@@ -11,6 +11,8 @@
  *   implicit_image/utils/train_helper.py:147-161  mse_loss + backward (autograd) /
  *   implicit_image/utils/train_helper.py:166-177  optimiser step (torch.optim.Adam, conf/optim/adam.yaml)
  *   implicit_image/pipeline/masking/core.py:271-279,671-702  Masking.step -> apply_mask   -> sf_adam_step
+ *   implicit_image/pipeline/masking/core.py:713-801 (+ funcs/prune.py:24-51, funcs/grow.py:58-97, core.py:250-269)
+ *                                                 update_connections of RigL              -> sf_mask_update
  *   implicit_image/utils/train_helper.py:41-59    eval_epoch (fwd, MSE)                   -> sf_forward
  *   implicit_image/utils/train_helper.py:52       (pred * 255).int()   -> sf_render / sf_wavelet_render (8-bit samples);
  *                                                 one sample width up: sf_render16 / sf_wavelet_render16 (pred * 65535)
@@ -188,6 +190,45 @@ int sf_debug_scratch(sf_handle* h, int32_t which, void** dev_ptr, int64_t* bytes
 int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_dev, int32_t K, int32_t iter_limit, float tol,
                   float* centroids_dev, int32_t centroids_cap, int32_t* n_centroids_dev, int64_t* labels_dev,
                   float* new_weight_dev);
+/* One RigL topology update (Masking.update_connections of the reference: pipeline/masking/core.py:713-801 with
+ * funcs/prune.py:24-51 magnitude_prune, funcs/grow.py:58-97 abs_grad_growth, core.py:250-269 adjust_prune_rate) on the
+ * handle's stream: two launches whatever the depth, NO device-to-host copy and no host synchronisation (csrc/siren_mask.hip).
+ * The state is the handle's flat fp32 vectors: params w, grads g, Adam m and v, masks k (0/1, sf_set_masks).
+ *   layers [n_layers]  host array: the engine layer indices, ascending, whose WEIGHT is masked (biases never are;
+ *                      sparse_init=random leaves the first layer out)
+ *   prune_rate         the current rate r of the decay schedule
+ *   growth             0 none, 1 absolute gradient
+ *   dense_gradients    0: the moments and the gradient are masked too
+ *   stats_dev          device, n_layers rows + one status row, may be NULL
+ * Per masked layer j, a flat slice of n elements (counts are exact integers, rate arithmetic is IEEE double):
+ *   1. live = #{k == 1}, dead = #{k == 0}, nnz = #{w != 0};  S = sum of nnz over the listed layers
+ *   2. share = nnz / S, frac_dead = dead / n;  rate = min(frac_dead, r) if frac_dead < 0.2 && (1.0 / n_layers) / share < 1.0,
+ *      else r
+ *   3. drop = ceil(rate * live)
+ *   4. drop > 0: the dead + drop elements smallest in (|w_i|, i), lexicographically, get k_i = 0;  removed = live - sum k
+ *   5. growth 1, unless every k_i of the layer is 1 after pruning: c_i = |g_i| * (1 - k_i) as an fp32 product; the `removed`
+ *      elements largest in c_i, ties to the lower index, get k_i = 1 and w_i = +0.0
+ *   6. w_i *= k_i (a product, as on the host: a pruned negative weight becomes -0.0); dense_gradients == 0: also m_i *= k_i,
+ *      v_i *= k_i, g_i *= k_i.  The weight images are marked dirty
+ *   7. row j: live, dead, nnz before; removed; live, dead, nnz after; rate
+ * S == 0 leaves the state untouched and sets live_before of the status row (row n_layers, otherwise all zero) to 1.
+ * Ties: the host's torch.sort orders equal keys arbitrarily; here the lower index comes first.  The two agree whenever the
+ * value at the selection boundary is unique.
+ * SF_ERR_INVALID / SF_ERR_STATE, before anything is launched: a null pointer, a wrong abi_version, a render handle, a
+ * FourierNet or WaveletSiren handle, a handle with Feathermap attached, no masks set (SF_ERR_STATE), a layer index out of
+ * range or not ascending, a growth mode other than 0 or 1.  Hidden 512 / 1024 handles are supported (the same flat layout). */
+typedef struct sf_mask_layer_stats {
+  int64_t live_before, dead_before, nnz_before, removed, live_after, dead_after, nnz_after;
+  double prune_rate;
+} sf_mask_layer_stats;
+typedef struct sf_mask_update_args {
+  int32_t abi_version, n_layers;
+  const int32_t* layers;
+  double prune_rate;
+  int32_t growth, dense_gradients;
+  sf_mask_layer_stats* stats_dev;
+} sf_mask_update_args;
+int sf_mask_update(sf_handle* h, const sf_mask_update_args* a);
 /* test aid for the "never throws" promise above: raises inside the library on purpose (0: std::bad_alloc -> SF_ERR_NOMEM,
  * 1: std::runtime_error, 2: a non-std exception -> SF_ERR_INVALID); every entry point is a function-try-block */
 int sf_debug_throw(int32_t kind);

@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""Host time of one RigL topology update - Masking.update_connections() followed by a device synchronise - on one MI355X:
+the parent commit's host path against sf_mask_update (csrc/siren_mask.hip), and the wall time of the default masked fit.
+
+    python scripts/mask_update_bench.py --parent <tree of the parent commit, library built in place>
+                                        [--updates 24] [--fit-runs 3] [--out profiles/mask_update_bench.json]
+
+Three sides per shape, each in a worker process of its own (two trees cannot be imported into one interpreter), driven
+in turn so that the sides alternate update by update and all see the same device state:
+    parent       the parent tree's update_connections()
+    head_device  this tree, the device route
+    head_host    this tree with SIREN_FIT_DEVICE_MASK=0: a check that the untouched host path did not move
+Every worker builds the model (RigL as conf/masking/RigL.yaml, density 0.5), trains `interval` = 20 steps before each update,
+as the fit does, synchronises, and times update_connections() + torch.cuda.synchronize() with the host clock; the first
+--warmup updates are dropped.  Reported: median, min and max per side.  The device route is accepted at a shape when its
+median lies below the parent's by more than the parent's own min - max spread there.
+
+Then `python -m implicit_image.fit masking=RigL quant=none train.num_steps=2000` at the first two shapes, parent against
+head, alternating, --fit-runs runs each: the `seconds` of result.json (the fit loop's wall time).
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [(64, 4, 256), (256, 8, 512), (256, 8, 1024), (512, 8, 512)]       # hidden, depth, image side
+INTERVAL = 20
+
+
+def tree_env(tree, knob=None):
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(tree, "implicit-image-compression_amd"), tree]))
+    env.pop("SIREN_FIT_DEVICE_MASK", None)
+    if knob is not None:
+        env["SIREN_FIT_DEVICE_MASK"] = knob
+    return env
+
+
+def worker(hidden, depth, side):
+    """reads one line per update from stdin, answers with the milliseconds of that update"""
+    import torch
+    from implicit_image.data import get_grid
+    from implicit_image.models import registry
+    from implicit_image.utils.train_helper import get_optimizer_lr_scheduler, setup_mask, train_steps
+    from oracle import siren_oracle as so
+
+    class Cfg(dict):
+        __getattr__ = dict.get
+    mcfg = Cfg(name="RigL", density=0.5, sparse_init="erdos-renyi-kernel", dense_gradients=True,
+               growth_mode="absolute-gradient", prune_mode="magnitude", redistribution_mode="none", dense=False,
+               prune_rate=0.1, decay_schedule="cosine", end_when=1500, interval=INTERVAL)
+    torch.manual_seed(0)
+    model = registry["siren"](depth=depth, hidden_size=hidden, first_omega_0=50, hidden_omega_0=30).to("cuda")
+    optim, sched = get_optimizer_lr_scheduler(model, Cfg(name="adam", lr=3e-4))
+    mask = setup_mask(model, optim, mcfg)
+    grid, img = get_grid(side, side).cuda(), so.synthetic_image(side, side, seed=3).cuda().contiguous()
+    print("ready", flush=True)
+    for _ in sys.stdin:
+        train_steps(model, optim, grid, img, INTERVAL, lr_scheduler=sched, mask=mask)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        mask.update_connections()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        pending = len(getattr(mask, "_pending", []))
+        density = mask.stats.total_density          # (outside the timed span: where the fit's log line reads it)
+        print(json.dumps({"ms": ms, "device": pending, "density": density}), flush=True)
+
+
+def stats(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
+
+
+def time_shape(trees, shape, updates, warmup):
+    procs = {}
+    for name, (tree, knob) in trees.items():
+        procs[name] = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", *map(str, shape)], env=tree_env(tree, knob),
+                                       cwd=tree, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+    try:
+        for name, p in procs.items():
+            line = p.stdout.readline().strip()
+            if line != "ready":
+                raise RuntimeError(f"{name}: worker did not start ({line!r})")
+        got = {name: [] for name in procs}
+        for _ in range(warmup + updates):
+            for name, p in procs.items():
+                p.stdin.write("go\n")
+                p.stdin.flush()
+                line = p.stdout.readline()
+                if not line:
+                    raise RuntimeError(f"{name}: worker ended (exit status {p.poll()})")
+                got[name].append(json.loads(line))
+    finally:
+        for p in procs.values():
+            p.stdin.close()
+        for p in procs.values():
+            if p.wait(timeout=60):
+                raise RuntimeError("a worker failed")
+    res = {name: stats([r["ms"] for r in rs[warmup:]]) for name, rs in got.items()}
+    for name, rs in got.items():
+        res[name]["device_updates"] = sum(r["device"] for r in rs)
+        res[name]["density_last"] = rs[-1]["density"]
+    par, dev = res["parent"], res["head_device"]
+    res["parent_spread_ms"] = par["max_ms"] - par["min_ms"]
+    res["accepted"] = bool(dev["median_ms"] < par["median_ms"] - res["parent_spread_ms"])
+    res["parent_over_device"] = par["median_ms"] / dev["median_ms"]
+    return res
+
+
+def time_fit(trees, shape, runs):
+    hidden, depth, side = shape
+    over = ["masking=RigL", "quant=none", "train.num_steps=2000", f"img.height={side}", f"img.width={side}",
+            f"mlp.hidden_size={hidden}", f"mlp.depth={depth}"]
+    got = {name: [] for name in trees}
+    for _ in range(runs):
+        for name, (tree, knob) in trees.items():
+            with tempfile.TemporaryDirectory() as tmp:
+                env = dict(tree_env(tree, knob), IIC_CONF=os.path.join(tree, "conf"))
+                subprocess.run([sys.executable, "-m", "implicit_image.fit"] + over, cwd=tmp, env=env, check=True,
+                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+                found = [os.path.join(dp, "result.json") for dp, _, fs in os.walk(tmp) if "result.json" in fs]
+                got[name].append(json.load(open(found[0])))
+    return {name: dict(stats([r["seconds"] * 1e3 for r in rs]), PSNR=[r["PSNR"] for r in rs]) for name, rs in got.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", help="a checkout of the parent commit with its library built in place")
+    ap.add_argument("--updates", type=int, default=24)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--fit-runs", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mask_update_bench.json"))
+    ap.add_argument("--worker", nargs=3, type=int, metavar=("HIDDEN", "DEPTH", "SIDE"))
+    args = ap.parse_args()
+    if args.worker:
+        return worker(*args.worker)
+    if not args.parent or not os.path.exists(os.path.join(args.parent, "implicit-image-compression_amd", "csrc", "libsiren_fit.so")):
+        ap.error("--parent: a tree of the parent commit with libsiren_fit.so built in place")
+    if args.updates < 20:
+        ap.error("--updates must be at least 20")
+    parent = os.path.abspath(args.parent)
+    trees = {"parent": (parent, None), "head_device": (ROOT, None), "head_host": (ROOT, "0")}
+    res = {"what": "host ms of Masking.update_connections() + torch.cuda.synchronize(), 20 training steps before each update, "
+                   "the three sides alternating update by update in worker processes of their own; then the fit loop's "
+                   "seconds (as ms) of the default masked fit at 2000 steps, parent against head, alternating",
+           "config": "RigL (conf/masking/RigL.yaml), density 0.5", "shapes": {}, "fit": {}}
+    for shape in SHAPES:
+        tag = f"{shape[0]}x{shape[1]}@{shape[2]}"
+        r = res["shapes"][tag] = time_shape(trees, shape, args.updates, args.warmup)
+        print(json.dumps({tag: {k: (round(v["median_ms"], 3), round(v["min_ms"], 3), round(v["max_ms"], 3))
+                                for k, v in r.items() if isinstance(v, dict)}, "accepted": r["accepted"]}), flush=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+    for shape in SHAPES[:2]:
+        tag = f"{shape[0]}x{shape[1]}@{shape[2]}"
+        r = res["fit"][tag] = time_fit({k: trees[k] for k in ("parent", "head_device")}, shape, args.fit_runs)
+        print(json.dumps({"fit " + tag: {k: round(v["median_ms"], 1) for k, v in r.items()}}), flush=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
