@@ -20,74 +20,42 @@
 
 #include "engine.h"
 
-// hidden 256, 16-bit scratch (k_bwd): 8 waves (two per SIMD), all weight rows in registers, 5 x 32 KiB ring = 160 KiB: 96 KiB
-// in flight; the P0 variant needs more registers and keeps the 4-wave / 4-slot form
-constexpr int kBwd16P0WC = 2;
-constexpr int kBwd16NB = 5;
-constexpr int kBwd16P0NB = 4;
-constexpr int kBwd8hPark = 4;   // k_bwd8h: k-steps of every wave's stationary W^T rows parked in LDS
-
 // Every template kernel of the library, in the order the code object holds them.  The compiler emits instantiations in the
 // order of their first use, so this list - their first use - keeps the device code byte for byte what it was measured as,
 // however the host code below is arranged: a host-only change leaves the sha256 of the device object alone.  A kernel the
 // launch code asks for and this list lacks is still built (behind these); one listed and never launched would be built too.
+// A row names a kernel by its case; the geometry of a case is stated once, beside the kernel (BwdCase, Bwd8Case, Dw0Lds8).
 #define SF_K(...) reinterpret_cast<const void*>(&__VA_ARGS__)
 [[maybe_unused]] static const void* const kKernelOrder[] = {
-    SF_K(k_fwd_pipe<OpF16, true, true, kFwdPD, false>), SF_K(k_fwd_pipe<OpF16, true, false, kFwdPD, false>),
-    SF_K(k_fwd_pipe<OpF16, false, false, kFwdPD, false>), SF_K(k_fwd_pipe<OpBF16, true, false, kFwdPD, false>),
-    SF_K(k_fwd_pipe<OpBF16, false, false, kFwdPD, false>), SF_K(k_bwd<32, 32, 1, 1, true, true, OpF16, 8>),
-    SF_K(k_bwd<32, 32, 1, 1, true, true, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, true, false, OpF16, 8>),
-    SF_K(k_bwd<32, 32, 1, 1, true, false, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, false, true, OpF16, 8>),
-    SF_K(k_bwd<32, 32, 1, 1, false, true, OpBF16, 8>), SF_K(k_bwd<32, 32, 1, 1, false, false, OpF16, 8>),
-    SF_K(k_bwd<32, 32, 1, 1, false, false, OpBF16, 8>), SF_K(k_bwd<32, 64, 1, 2, true, true, OpF16, 8>),
-    SF_K(k_bwd<32, 64, 1, 2, true, true, OpBF16, 8>), SF_K(k_bwd<32, 64, 1, 2, true, false, OpF16, 8>),
-    SF_K(k_bwd<32, 64, 1, 2, true, false, OpBF16, 8>), SF_K(k_bwd<64, 64, 2, 1, false, true, OpF16, 8>),
-    SF_K(k_bwd<64, 64, 2, 1, false, true, OpBF16, 8>), SF_K(k_bwd<64, 64, 2, 1, false, false, OpF16, 8>),
-    SF_K(k_bwd<64, 64, 2, 1, false, false, OpBF16, 8>), SF_K(k_bwd<32, 128, 1, 4, true, true, OpF16, 8>),
-    SF_K(k_bwd<32, 128, 1, 4, true, true, OpBF16, 8>), SF_K(k_bwd<32, 128, 1, 4, true, false, OpF16, 8>),
-    SF_K(k_bwd<32, 128, 1, 4, true, false, OpBF16, 8>), SF_K(k_bwd<128, 128, 2, 2, false, true, OpF16, 8>),
-    SF_K(k_bwd<128, 128, 2, 2, false, true, OpBF16, 8>), SF_K(k_bwd<128, 128, 2, 2, false, false, OpF16, 8>),
-    SF_K(k_bwd<128, 128, 2, 2, false, false, OpBF16, 8>), SF_K(k_bwd<32, 256, 1, 8, true, true, OpF16, 8>),
-    SF_K(k_bwd<32, 256, 1, 8, true, true, OpBF16, 8>), SF_K(k_bwd<32, 256, 1, 8, true, false, OpF16, 8>),
-    SF_K(k_bwd<32, 256, 1, 8, true, false, OpBF16, 8>),
-    SF_K(k_bwd<256, 256, 2, kBwd16P0WC, false, true, OpF16, kBwd16P0NB>),
-    SF_K(k_bwd<256, 256, 2, kBwd16P0WC, false, true, OpBF16, kBwd16P0NB>),
-    SF_K(k_bwd<256, 256, 2, 4, false, false, OpF16, kBwd16NB>),
-    SF_K(k_bwd<256, 256, 2, 4, false, false, OpBF16, kBwd16NB>),
-    SF_K(k_bwd8<32, 32, 1, 1, true, true, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 32, 1, 1, true, false, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 32, 1, 1, false, true, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 32, 1, 1, false, false, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 64, 1, 2, true, true, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 64, 1, 2, true, false, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<64, 64, 2, 1, false, true, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<64, 64, 2, 1, false, false, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 128, 1, 4, true, true, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 128, 1, 4, true, false, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<128, 128, 2, 2, false, true, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<128, 128, 2, 2, false, false, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 256, 1, 8, true, true, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 8, 0, 0, false>),
-    SF_K(k_bwd8<256, 256, 2, 4, false, true, OpF16, 5, 4, 0, false>),
-    SF_K(k_bwd8<256, 256, 2, 4, false, false, OpF16, 5, 2, 3, false>), SF_K(k_bwd8h<kBwd8hPark>),
-    SF_K(k_bwd8<32, 32, 1, 1, true, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 32, 1, 1, true, false, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 32, 1, 1, false, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 32, 1, 1, false, false, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 64, 1, 2, true, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 64, 1, 2, true, false, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<64, 64, 2, 1, false, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<64, 64, 2, 1, false, false, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 128, 1, 4, true, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 128, 1, 4, true, false, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<128, 128, 2, 2, false, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<128, 128, 2, 2, false, false, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 256, 1, 8, true, true, OpF16, 8, 0, 0, true>),
-    SF_K(k_bwd8<32, 256, 1, 8, true, false, OpF16, 4, 0, 4, true>),
-    SF_K(k_dw0_8<32, OpF16, 8>),
-    SF_K(k_dw0_8<64, OpF16, 8>), SF_K(k_dw0_8<128, OpF16, 8>), SF_K(k_dw0_8<256, OpF16, 4>), SF_K(k_dw0<32, OpF16>),
-    SF_K(k_dw0<32, OpBF16>), SF_K(k_dw0<64, OpF16>), SF_K(k_dw0<64, OpBF16>), SF_K(k_dw0<128, OpF16>),
-    SF_K(k_dw0<128, OpBF16>), SF_K(k_fwd<32, OpF16, true, true, false>), SF_K(k_fwd<32, OpF16, true, false, false>),
+    SF_K(k_fwd_pipe<OpF16, true, true, false>), SF_K(k_fwd_pipe<OpF16, true, false, false>),
+    SF_K(k_fwd_pipe<OpF16, false, false, false>), SF_K(k_fwd_pipe<OpBF16, true, false, false>),
+    SF_K(k_fwd_pipe<OpBF16, false, false, false>), SF_K(k_bwd<32, true, true, OpF16>),
+    SF_K(k_bwd<32, true, true, OpBF16>), SF_K(k_bwd<32, true, false, OpF16>), SF_K(k_bwd<32, true, false, OpBF16>),
+    SF_K(k_bwd<32, false, true, OpF16>), SF_K(k_bwd<32, false, true, OpBF16>), SF_K(k_bwd<32, false, false, OpF16>),
+    SF_K(k_bwd<32, false, false, OpBF16>), SF_K(k_bwd<64, true, true, OpF16>), SF_K(k_bwd<64, true, true, OpBF16>),
+    SF_K(k_bwd<64, true, false, OpF16>), SF_K(k_bwd<64, true, false, OpBF16>), SF_K(k_bwd<64, false, true, OpF16>),
+    SF_K(k_bwd<64, false, true, OpBF16>), SF_K(k_bwd<64, false, false, OpF16>), SF_K(k_bwd<64, false, false, OpBF16>),
+    SF_K(k_bwd<128, true, true, OpF16>), SF_K(k_bwd<128, true, true, OpBF16>), SF_K(k_bwd<128, true, false, OpF16>),
+    SF_K(k_bwd<128, true, false, OpBF16>), SF_K(k_bwd<128, false, true, OpF16>),
+    SF_K(k_bwd<128, false, true, OpBF16>), SF_K(k_bwd<128, false, false, OpF16>),
+    SF_K(k_bwd<128, false, false, OpBF16>), SF_K(k_bwd<256, true, true, OpF16>), SF_K(k_bwd<256, true, true, OpBF16>),
+    SF_K(k_bwd<256, true, false, OpF16>), SF_K(k_bwd<256, true, false, OpBF16>), SF_K(k_bwd<256, false, true, OpF16>),
+    SF_K(k_bwd<256, false, true, OpBF16>), SF_K(k_bwd<256, false, false, OpF16>),
+    SF_K(k_bwd<256, false, false, OpBF16>), SF_K(k_bwd8<32, true, true, false>), SF_K(k_bwd8<32, true, false, false>),
+    SF_K(k_bwd8<32, false, true, false>), SF_K(k_bwd8<32, false, false, false>), SF_K(k_bwd8<64, true, true, false>),
+    SF_K(k_bwd8<64, true, false, false>), SF_K(k_bwd8<64, false, true, false>), SF_K(k_bwd8<64, false, false, false>),
+    SF_K(k_bwd8<128, true, true, false>), SF_K(k_bwd8<128, true, false, false>),
+    SF_K(k_bwd8<128, false, true, false>), SF_K(k_bwd8<128, false, false, false>),
+    SF_K(k_bwd8<256, true, true, false>), SF_K(k_bwd8<256, true, false, false>),
+    SF_K(k_bwd8<256, false, true, false>), SF_K(k_bwd8<256, false, false, false>), SF_K(k_bwd8h<kBwd8hPark>),
+    SF_K(k_bwd8<32, true, true, true>), SF_K(k_bwd8<32, true, false, true>), SF_K(k_bwd8<32, false, true, true>),
+    SF_K(k_bwd8<32, false, false, true>), SF_K(k_bwd8<64, true, true, true>), SF_K(k_bwd8<64, true, false, true>),
+    SF_K(k_bwd8<64, false, true, true>), SF_K(k_bwd8<64, false, false, true>), SF_K(k_bwd8<128, true, true, true>),
+    SF_K(k_bwd8<128, true, false, true>), SF_K(k_bwd8<128, false, true, true>), SF_K(k_bwd8<128, false, false, true>),
+    SF_K(k_bwd8<256, true, true, true>), SF_K(k_bwd8<256, true, false, true>), SF_K(k_dw0_8<32>), SF_K(k_dw0_8<64>),
+    SF_K(k_dw0_8<128>), SF_K(k_dw0_8<256>), SF_K(k_dw0<32, OpF16>), SF_K(k_dw0<32, OpBF16>), SF_K(k_dw0<64, OpF16>),
+    SF_K(k_dw0<64, OpBF16>), SF_K(k_dw0<128, OpF16>), SF_K(k_dw0<128, OpBF16>),
+    SF_K(k_fwd<32, OpF16, true, true, false>), SF_K(k_fwd<32, OpF16, true, false, false>),
     SF_K(k_fwd<32, OpF16, false, false, false>), SF_K(k_fwd<32, OpBF16, true, false, false>),
     SF_K(k_fwd<32, OpBF16, false, false, false>), SF_K(k_fwd<64, OpF16, true, true, false>),
     SF_K(k_fwd<64, OpF16, true, false, false>), SF_K(k_fwd<64, OpF16, false, false, false>),
@@ -99,23 +67,24 @@ constexpr int kBwd8hPark = 4;   // k_bwd8h: k-steps of every wave's stationary W
     SF_K(k_fwd<256, OpBF16, true, false, false>), SF_K(k_fwd<256, OpBF16, false, false, false>),
     SF_K(k_wlayer0<OpF16, true>), SF_K(k_wlayer0<OpF16, false>), SF_K(k_wlayer0<OpBF16, false>),
     SF_K(k_wgemm2<0, OpF16, true, false, false>), SF_K(k_wgemm2<0, OpF16, false, false, false>),
-    SF_K(k_wgemm2<0, OpBF16, false, false, false>), SF_K(k_wgemm<1, OpF16>), SF_K(k_wgemm<1, OpBF16>),
+    SF_K(k_wgemm2<0, OpBF16, false, false, false>), SF_K(k_wgemm<OpF16>), SF_K(k_wgemm<OpBF16>),
     SF_K(k_wdw<32, OpF16, false>), SF_K(k_wdw<32, OpBF16, false>), SF_K(k_wdw<256, OpF16, true>),
     SF_K(k_wdw<256, OpF16, false>), SF_K(k_wdw<256, OpBF16, false>), SF_K(k_wgemm2<2, OpF16, true, false, true>),
     SF_K(k_wgemm2<2, OpF16, true, true, true>), SF_K(k_wgemm2<2, OpF16, true, false, false>),
     SF_K(k_wgemm2<2, OpF16, false, false, false>), SF_K(k_wgemm2<2, OpBF16, false, false, false>),
-    SF_K(k_dw0<256, OpF16>), SF_K(k_dw0<256, OpBF16>), SF_K(k_ff_fwd<32, false, false>), SF_K(k_ff_fwd<32, true, false>),
-    SF_K(k_ff_bwd<32>), SF_K(k_ff_fwd<64, false, false>), SF_K(k_ff_fwd<64, true, false>), SF_K(k_ff_bwd<64>),
-    SF_K(k_ff_fwd<128, false, false>), SF_K(k_ff_fwd<128, true, false>), SF_K(k_ff_bwd<128>),
-    SF_K(k_ff_fwd<256, false, false>), SF_K(k_ff_fwd<256, true, false>), SF_K(k_ff_bwd<256>), SF_K(k_ff_dw<1, true>),
-    SF_K(k_ff_dw<2, true>), SF_K(k_ff_dw<4, true>), SF_K(k_ff_dw<1, false>), SF_K(k_ff_dw<2, false>),
-    SF_K(k_ff_dw<4, false>), SF_K(k_fwd_pipe<OpF16, false, false, kFwdPD, true>),
-    SF_K(k_fwd_pipe<OpBF16, false, false, kFwdPD, true>), SF_K(k_fwd<32, OpF16, false, false, true>),
-    SF_K(k_fwd<32, OpBF16, false, false, true>), SF_K(k_fwd<64, OpF16, false, false, true>),
-    SF_K(k_fwd<64, OpBF16, false, false, true>), SF_K(k_fwd<128, OpF16, false, false, true>),
-    SF_K(k_fwd<128, OpBF16, false, false, true>), SF_K(k_fwd<256, OpF16, false, false, true>),
-    SF_K(k_fwd<256, OpBF16, false, false, true>), SF_K(k_ff_fwd<32, false, true>), SF_K(k_ff_fwd<64, false, true>),
-    SF_K(k_ff_fwd<128, false, true>), SF_K(k_ff_fwd<256, false, true>), SF_K(k_fth_mat<false>), SF_K(k_fth_mat<true>),
+    SF_K(k_dw0<256, OpF16>), SF_K(k_dw0<256, OpBF16>), SF_K(k_ff_fwd<32, false, false>),
+    SF_K(k_ff_fwd<32, true, false>), SF_K(k_ff_bwd<32>), SF_K(k_ff_fwd<64, false, false>),
+    SF_K(k_ff_fwd<64, true, false>), SF_K(k_ff_bwd<64>), SF_K(k_ff_fwd<128, false, false>),
+    SF_K(k_ff_fwd<128, true, false>), SF_K(k_ff_bwd<128>), SF_K(k_ff_fwd<256, false, false>),
+    SF_K(k_ff_fwd<256, true, false>), SF_K(k_ff_bwd<256>), SF_K(k_ff_dw<1, true>), SF_K(k_ff_dw<2, true>),
+    SF_K(k_ff_dw<4, true>), SF_K(k_ff_dw<1, false>), SF_K(k_ff_dw<2, false>), SF_K(k_ff_dw<4, false>),
+    SF_K(k_fwd_pipe<OpF16, false, false, true>), SF_K(k_fwd_pipe<OpBF16, false, false, true>),
+    SF_K(k_fwd<32, OpF16, false, false, true>), SF_K(k_fwd<32, OpBF16, false, false, true>),
+    SF_K(k_fwd<64, OpF16, false, false, true>), SF_K(k_fwd<64, OpBF16, false, false, true>),
+    SF_K(k_fwd<128, OpF16, false, false, true>), SF_K(k_fwd<128, OpBF16, false, false, true>),
+    SF_K(k_fwd<256, OpF16, false, false, true>), SF_K(k_fwd<256, OpBF16, false, false, true>),
+    SF_K(k_ff_fwd<32, false, true>), SF_K(k_ff_fwd<64, false, true>), SF_K(k_ff_fwd<128, false, true>),
+    SF_K(k_ff_fwd<256, false, true>), SF_K(k_fth_mat<false>), SF_K(k_fth_mat<true>),
 };
 #undef SF_K
 

@@ -72,78 +72,23 @@ FwdArgs fwd_args_base(const sf_engine* h, long pix0, int n_super) {
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------
-// The one tile table of the fused layer backward, <JW, IW, WR, WC> of (width, last): the last layer's out_features (<= 3,
-// padded to 32) rows against one wave per 32 inputs; a hidden layer's WD x WD block on 1, 2, 4 or 8 waves.
-template <int WD, bool LAST>
-struct BwdTile {
-  static constexpr int JW = LAST ? 32 : WD, IW = WD;
-  static constexpr int WR = LAST || WD == 32 ? 1 : 2, WC = LAST ? WD / 32 : WD == 32 ? 1 : WD / 64;
-};
-
-// 16-bit scratch (k_bwd).  Ring depths are chosen to fill the 160 KiB of LDS.
-template <int WD, bool LAST, bool P0, typename OP>
-int launch_bwd16(sf_engine* h, const BwdLayerArgs& a, int n_wg) {
-  using T = BwdTile<WD, LAST>;
-  constexpr bool H256 = WD == 256 && !LAST;
-  constexpr int WC = H256 && P0 ? kBwd16P0WC : T::WC, NB = H256 ? (P0 ? kBwd16P0NB : kBwd16NB) : 8;   // (the constants at the kernel list)
-  constexpr int JW = T::JW, IW = T::IW, WR = T::WR, NWV = WR * WC;
-  static_assert(!H256 || P0 || BwdLds<JW, IW, NWV, LAST, P0, NB>::bytes == 160 * 1024, "hidden 256: 5 x 32 KiB ring");
-  return launch(h, k_bwd<JW, IW, WR, WC, LAST, P0, OP, NB>, n_wg, NWV * 64, BwdLds<JW, IW, NWV, LAST, P0, NB>::bytes, a);
-}
-// fused backward of one layer: last = the out_features(<=3, padded to 32)-row layer; p0 = its input layer is
-// layer 0, whose phases are re-derived from the coordinates.
+// fused backward of one layer, 16-bit scratch (k_bwd; its cases and their geometry: BwdCase, siren_kernels.hip): last = the
+// out_features(<=3, padded to 32)-row layer; p0 = its input layer is layer 0, whose phases are re-derived from the coordinates.
 int launch_bwd(sf_engine* h, bool last, bool p0, const BwdLayerArgs& a, int n_wg) {
   return with_width(h, [&](auto wd) {
     return with_bool(last, p0, [&](auto l, auto p) {
-      return with_op(h, [&](auto op) { return launch_bwd16<decltype(wd)::value, decltype(l)::value, decltype(p)::value, decltype(op)>(h, a, n_wg); });
+      return with_op(h, [&](auto op) {
+        constexpr int WD = decltype(wd)::value;
+        constexpr bool LAST = decltype(l)::value, P0 = decltype(p)::value;
+        using C = BwdCase<WD, LAST, P0>;
+        return launch(h, k_bwd<WD, LAST, P0, decltype(op)>, n_wg, C::threads, C::Lds::bytes, a);
+      });
     });
   });
 }
 
-// 8-bit scratch path (siren_s8.hip, k_bwd8): fp16 operands only.  D8: fp8 deltas (scratch_format 8); else phase bytes with
-// 16-bit float deltas (scratch_format 12).  Ring depth NB, parked W^T k-steps PARK and phase-ring depth NBP:
-struct Ring8 { int NB, PARK, NBP; };
-template <int WD, bool LAST, bool P0, bool D8>
-constexpr Ring8 bwd8_ring() {
-  static_assert(WD != 256 || !D8 || LAST, "fp8 deltas, width 256, below the last layer: k_bwd8h (launch_bwd8)");
-  if (WD != 256) return {8, 0, 0};
-  // Ring depths / parked W^T k-steps of the 256-wide 8-wave forms are the combinations hipcc allocates WITHOUT a scratch
-  // reload inside the block loop (a reload's vmcnt(0) also waits for every LDS-DMA in flight, i.e. it serialises the loop on
-  // HBM latency): DESIGN.md section 4.
-  if (!D8) {
-    if (LAST) return {8, 0, 0};
-    // hidden: 5 delta slots (80 KiB) + 3 phase slots (24) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
-    // layer 1 (P0, no phase ring): 5 delta slots + sines + 4 parked k-steps + layer-0 table = 148 KiB
-    return P0 ? Ring8{5, 4, 0} : Ring8{5, 2, 3};
-  }
-  // 8 waves (two per SIMD); the ring slots hold the fp8 bytes (8 KiB per block): phase W converts in registers, phase X
-  // reads a 16-bit image expanded once per block (2 x 16 KiB).
-  // last layer: 3 MFMAs per block, bound by the latency of a step once its delta output is bytes - rings of 4 slots
-  // (72 KiB + the 1 KiB sin/cos table) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
-  // HBM-bound at 5.4 TB/s and the shallower rings cost 0.3 ms: format 12 keeps one workgroup per CU)
-  // (every layer below the last runs k_bwd8h: launch_bwd8)
-  return P0 ? Ring8{8, 0, 0} : Ring8{4, 0, 4};
-}
-// the LDS layout of k_bwd8 for (width, last, p0, d8) with the rings above
-template <int WD, bool LAST, bool P0, bool D8>
-struct Bwd8Of {
-  using T = BwdTile<WD, LAST>;
-  static constexpr Ring8 R = bwd8_ring<WD, LAST, P0, D8>();
-  using Lds = Bwd8Lds<T::JW, T::IW, T::WR * T::WC, LAST, P0, R.NB, R.PARK, R.NBP, D8>;
-};
-static_assert(Bwd8Of<256, false, false, false>::Lds::bytes == 153 * 1024, "format 12, hidden layer");
-static_assert(Bwd8Of<256, false, true, false>::Lds::bytes == 148 * 1024, "format 12, layer 1 (P0)");
-static_assert(2 * Bwd8Of<256, true, false, true>::Lds::bytes == 146 * 1024, "format 8, last layer: 73 KiB, two workgroups per CU");
-template <int WD, bool LAST, bool P0, bool D8>
-int launch_bwd8_k(sf_engine* h, const Bwd8Args& a, int n_wg) {
-  using T = BwdTile<WD, LAST>;
-  constexpr Ring8 R = Bwd8Of<WD, LAST, P0, D8>::R;
-  return launch(h, k_bwd8<T::JW, T::IW, T::WR, T::WC, LAST, P0, OpF16, R.NB, R.PARK, R.NBP, D8>, n_wg, T::WR * T::WC * 64,
-                Bwd8Of<WD, LAST, P0, D8>::Lds::bytes, a);
-}
-int launch_bwd8h(sf_engine* h, const Bwd8Args& a, int n_wg) {
-  return launch(h, k_bwd8h<kBwd8hPark>, n_wg, 512, Bwd8hLds<kBwd8hPark>::bytes, a);
-}
+// 8-bit scratch path (k_bwd8; its cases: Bwd8Case, siren_s8.hip): fp16 operands only.  h->d8: fp8 deltas (scratch_format 8);
+// else phase bytes with 16-bit float deltas (scratch_format 12).
 int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
   return with_width(h, [&](auto wd) {
     return with_bool(last, p0, [&](auto l, auto p) {
@@ -152,8 +97,13 @@ int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
         constexpr bool LAST = decltype(l)::value, P0 = decltype(p)::value, D8 = decltype(d)::value;
         // fp8 deltas at width 256, every layer below the last: the slot-per-MFMA pipeline (siren_s8h.hip).  The forward of such
         // a layer is k_fwd_pipe, which spills layer 0's phase bytes too, so run_pass never asks for the P0 form here.
-        if constexpr (WD == 256 && !LAST && D8) return P0 ? fail(SF_ERR_INVALID, "launch_bwd8: no P0 form below the last layer") : launch_bwd8h(h, a, n_wg);
-        else return launch_bwd8_k<WD, LAST, P0, D8>(h, a, n_wg);
+        if constexpr (WD == 256 && !LAST && D8) {
+          return P0 ? fail(SF_ERR_INVALID, "launch_bwd8: no P0 form below the last layer")
+                    : launch(h, k_bwd8h<kBwd8hPark>, n_wg, 512, Bwd8hLds<kBwd8hPark>::bytes, a);
+        } else {
+          using C = Bwd8Case<WD, LAST, P0, D8>;
+          return launch(h, k_bwd8<WD, LAST, P0, D8>, n_wg, C::threads, C::Lds::bytes, a);
+        }
       });
     });
   });
@@ -164,14 +114,10 @@ template <int JW>
 int launch_dw0(sf_engine* h, const Dw0Args& a, int n_wg) {
   return with_op(h, [&](auto op) { return launch(h, k_dw0<JW, decltype(op)>, n_wg, JW * 2, Dw0Lds<JW>::bytes, a); });
 }
-// ... from fp8 deltas: two MFMAs per wave and block behind a workgroup barrier: bound by the latency of a step.  At width
-// 256 a 4-slot ring (64.5 KiB) lets two workgroups share a CU.
-constexpr int dw0_8_ring(int JW) { return JW == 256 ? 4 : 8; }
-static_assert(2 * Dw0Lds8<256, dw0_8_ring(256)>::bytes == 129 * 1024, "64.5 KiB per workgroup");
+// ... from fp8 deltas (k_dw0_8; ring depth: Dw0Lds8, siren_s8.hip)
 template <int JW>
 int launch_dw0_8(sf_engine* h, const Dw0Args& a, int n_wg) {
-  constexpr int NB = dw0_8_ring(JW);
-  return launch(h, k_dw0_8<JW, OpF16, NB>, n_wg, JW * 2, Dw0Lds8<JW, NB>::bytes, a);
+  return launch(h, k_dw0_8<JW>, n_wg, JW * 2, Dw0Lds8<JW>::bytes, a);
 }
 template <int JW>
 int launch_dw_first_t(sf_engine* h, const Dw0Args& a, int n_wg) {

@@ -535,8 +535,9 @@ DEV uint32_t pack_h2(_Float16 a, _Float16 b) {
 }
 
 constexpr int kFwdPD = 4;   // k_fwd_pipe: slots a weight fragment is read ahead of its MFMA
-template <typename OP, bool TRAIN, bool S8, int PD = kFwdPD, bool RENDER = false, int BITS = 8>
+template <typename OP, bool TRAIN, bool S8, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
+  constexpr int PD = kFwdPD;
   static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
   static_assert(BITS == 8 || (RENDER && BITS == 16), "BITS: the sample width of a RENDER form, 8 or 16");
   constexpr int WD = 256;
@@ -943,11 +944,32 @@ struct BwdLds {
   static constexpr size_t oWsp = (size_t)NB * BLK, oL0 = oWsp + (size_t)NW * XT * WSP * 1024, bytes = oL0 + (P0 ? (size_t)IW * 16 : 0);
   static_assert(bytes <= kLdsMax, "k_bwd LDS budget");
 };
+// The one tile table of the fused layer backward (k_bwd, k_bwd8), <JW, IW, WR, WC> of (width, last): the last layer's
+// out_features (<= 3, padded to 32) rows against one wave per 32 inputs; a hidden layer's WD x WD block on 1, 2, 4 or 8 waves.
+template <int WD, bool LAST>
+struct BwdTile {
+  static constexpr int JW = LAST ? 32 : WD, IW = WD;
+  static constexpr int WR = LAST || WD == 32 ? 1 : 2, WC = LAST ? WD / 32 : WD == 32 ? 1 : WD / 64;
+};
+// The cases of k_bwd (16-bit scratch) and the geometry of each: the tile, the ring depth NB, block threads and LDS layout.
+// Ring depths are chosen to fill the 160 KiB of LDS.  Hidden 256: 8 waves (two per SIMD), all weight rows in registers,
+// 5 x 32 KiB ring = 160 KiB: 96 KiB in flight; the P0 variant needs more registers and keeps the 4-wave / 4-slot form.
+template <int WD, bool LAST, bool P0>
+struct BwdCase {
+  using T = BwdTile<WD, LAST>;
+  static constexpr bool H256 = WD == 256 && !LAST;
+  static constexpr int JW = T::JW, IW = T::IW, WR = T::WR, WC = H256 && P0 ? 2 : T::WC, NB = H256 ? (P0 ? 4 : 5) : 8;
+  static constexpr int threads = WR * WC * 64;
+  using Lds = BwdLds<JW, IW, WR * WC, LAST, P0, NB>;
+  static_assert(!H256 || P0 || Lds::bytes == 160 * 1024, "hidden 256: 5 x 32 KiB ring");
+};
 
-template <int JW, int IW, int WAVES_R, int WAVES_C, bool LAST, bool P0, typename OP, int NB>
-__global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd(BwdLayerArgs a) {
+template <int WD, bool LAST, bool P0, typename OP>
+__global__ __launch_bounds__((BwdCase<WD, LAST, P0>::threads)) void k_bwd(BwdLayerArgs a) {
+  using C = BwdCase<WD, LAST, P0>;
+  constexpr int JW = C::JW, IW = C::IW, WAVES_R = C::WR, WAVES_C = C::WC, NB = C::NB;
   constexpr int NW = WAVES_R * WAVES_C;
-  using L = BwdLds<JW, IW, NW, LAST, P0, NB>;
+  using L = typename C::Lds;
   constexpr int JT = JW / 32, IT = IW / 32;
   constexpr int WJ = JT / WAVES_R, WI = IT / WAVES_C;
   constexpr int KSJ = JW / 16, KSI = IW / 16;

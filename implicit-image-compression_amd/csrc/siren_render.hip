@@ -127,7 +127,7 @@ int launch_render(sf_engine* h, const FwdArgs& a, int n_wg, int bits = 8) {
     return with_op(h, [&](auto op) {
       using OP = decltype(op);
       if (fwd_is_pipe(h))
-        return launch(h, k_fwd_pipe<OP, false, false, kFwdPD, true, BITS>, n_wg, 512, fwd_pipe_lds_bytes(), a);
+        return launch(h, k_fwd_pipe<OP, false, false, true, BITS>, n_wg, 512, fwd_pipe_lds_bytes(), a);
       return with_width(h, [&](auto wd) {
         constexpr int WD = decltype(wd)::value;
         return launch(h, k_fwd<WD, OP, false, false, true, BITS>, n_wg, 512, fwd_lds_bytes(WD), a);

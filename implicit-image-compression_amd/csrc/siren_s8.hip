@@ -14,8 +14,8 @@
 // code already reads (lane-linear for the data-gradient B operand, ds_read_b64_tr_b16 for both weight-gradient
 // operands), one block ahead of its use, by the wave that also issued its DMA (8 conversions per wave and block).
 //
-// LDS of one workgroup: Bwd8Lds below (the layout, once, for the kernel and its launcher; the sizes of the 256-wide forms
-// are asserted where their rings are chosen: bwd8_ring, siren_host.hip).
+// LDS of one workgroup: Bwd8Lds below (the layout, once, for the kernel and its launcher).  Which cases of k_bwd8<WD, LAST,
+// P0, D8> exist and the tile and rings each gets: Bwd8Case / bwd8_ring below, where the sizes of the 256-wide forms are asserted.
 // (included by siren_fit.hip after siren_kernels.hip)
 
 namespace sf {
@@ -66,7 +66,7 @@ SF_HOSTDEV int nu8(int r) { return 16 * (r >> 4) + pi_perm((r >> 3) & 1, r & 7);
 //   X16      2   x KSJ KiB   IN8 only: 16-bit images of a block's deltas (B operand of phase X)
 //   S16      2   x KSI KiB   fp16 sin(phase): written by the X epilogue of step k, tr-read by phase W of step k+1
 //   WP, T    the parked W^T k-steps (NW x XT x PARK KiB); the sin/cos table (1 KiB) or, P0, the layer-0 table (IW x 16 bytes)
-template <int JW, int IW, int NW, bool LAST, bool P0, int NB, int PARK = 0, int NBP_ = 0, bool D8 = true>
+template <int JW, int IW, int NW, bool LAST, bool P0, int NB, int PARK, int NBP_, bool D8>
 struct Bwd8Lds {
   static constexpr int JT = JW / 32, IT = IW / 32, KSJ = JW / 16, KSI = IW / 16, XT = IT / NW;
   static constexpr bool IN8 = D8 && !LAST;
@@ -78,11 +78,49 @@ struct Bwd8Lds {
   static constexpr size_t bytes = (size_t)oTab + (P0 ? (size_t)IW * 16 : 1024);
   static_assert(bytes <= kLdsMax, "k_bwd8 LDS budget");
 };
+// The cases of k_bwd8 and the geometry of each: fp16 operands only.  D8: fp8 deltas (scratch_format 8); else phase bytes
+// with 16-bit float deltas (scratch_format 12).  The tile is k_bwd's (BwdTile); ring depth NB, parked W^T k-steps PARK and
+// phase-ring depth NBP (0: NB):
+struct Ring8 { int NB, PARK, NBP; };
+template <int WD, bool LAST, bool P0, bool D8>
+constexpr Ring8 bwd8_ring() {
+  if (WD != 256) return {8, 0, 0};
+  // Ring depths / parked W^T k-steps of the 256-wide 8-wave forms are the combinations hipcc allocates WITHOUT a scratch
+  // reload inside the block loop (a reload's vmcnt(0) also waits for every LDS-DMA in flight, i.e. it serialises the loop on
+  // HBM latency): DESIGN.md section 4.
+  if (!D8) {
+    if (LAST) return {8, 0, 0};
+    // hidden: 5 delta slots (80 KiB) + 3 phase slots (24) + sines (32) + 2 parked k-steps (16) + sin/cos table (1) = 153 KiB
+    // layer 1 (P0, no phase ring): 5 delta slots + sines + 4 parked k-steps + layer-0 table = 148 KiB
+    return P0 ? Ring8{5, 4, 0} : Ring8{5, 2, 3};
+  }
+  // 8 waves (two per SIMD); the ring slots hold the fp8 bytes (8 KiB per block): phase W converts in registers, phase X
+  // reads a 16-bit image expanded once per block (2 x 16 KiB).
+  // last layer: 3 MFMAs per block, bound by the latency of a step once its delta output is bytes - rings of 4 slots
+  // (72 KiB + the 1 KiB sin/cos table) let two workgroups share a CU (2.30 instead of 2.60 ms per step; with 16-bit deltas the kernel is
+  // HBM-bound at 5.4 TB/s and the shallower rings cost 0.3 ms: format 12 keeps one workgroup per CU)
+  return P0 ? Ring8{8, 0, 0} : Ring8{4, 0, 4};
+}
+template <int WD, bool LAST, bool P0, bool D8>
+struct Bwd8Case {
+  static_assert(WD != 256 || !D8 || LAST, "fp8 deltas, width 256, below the last layer: k_bwd8h (siren_s8h.hip)");
+  using T = BwdTile<WD, LAST>;
+  static constexpr Ring8 R = bwd8_ring<WD, LAST, P0, D8>();
+  static constexpr int JW = T::JW, IW = T::IW, WR = T::WR, WC = T::WC, NB = R.NB, PARK = R.PARK, NBP = R.NBP;
+  static constexpr int threads = WR * WC * 64;
+  using Lds = Bwd8Lds<JW, IW, WR * WC, LAST, P0, NB, PARK, NBP, D8>;
+};
+static_assert(Bwd8Case<256, false, false, false>::Lds::bytes == 153 * 1024, "format 12, hidden layer");
+static_assert(Bwd8Case<256, false, true, false>::Lds::bytes == 148 * 1024, "format 12, layer 1 (P0)");
+static_assert(2 * Bwd8Case<256, true, false, true>::Lds::bytes == 146 * 1024, "format 8, last layer: 73 KiB, two workgroups per CU");
 
-template <int JW, int IW, int WAVES_R, int WAVES_C, bool LAST, bool P0, typename OP, int NB, int PARK = 0, int NBP_ = 0, bool D8 = true>
-__global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
+template <int WD, bool LAST, bool P0, bool D8>
+__global__ __launch_bounds__((Bwd8Case<WD, LAST, P0, D8>::threads)) void k_bwd8(Bwd8Args a) {
+  using C = Bwd8Case<WD, LAST, P0, D8>;
+  using L = typename C::Lds;
+  using OP = OpF16;
+  constexpr int JW = C::JW, IW = C::IW, WAVES_R = C::WR, WAVES_C = C::WC, NB = C::NB, PARK = C::PARK;
   constexpr int NW = WAVES_R * WAVES_C;
-  using L = Bwd8Lds<JW, IW, NW, LAST, P0, NB, PARK, NBP_, D8>;
   constexpr int JT = JW / 32, IT = IW / 32;
   constexpr int WJ = JT / WAVES_R, WI = IT / WAVES_C;
   constexpr int KSJ = JW / 16, KSI = IW / 16;
@@ -140,7 +178,7 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
   // the pair as two 16-bit floats) instead of v_cvt_f32_ubyte + v_fma + v_sin + v_cos per value - the X epilogue is what
   // bounds phase W (VALU issue of two waves per SIMD).  The sine is the value the table-free form wrote to S16 bit for bit;
   // the cosine is rounded to 16 bits before it meets the accumulator (whose product is rounded to 8 or 16 bits anyway).
-  constexpr bool TAB = !P0 && std::is_same<OP, OpF16>::value;
+  constexpr bool TAB = !P0;
   uint32_t* const sTab = reinterpret_cast<uint32_t*>(smem + L::oTab);
   if (TAB) {
     for (int i = tid; i < 256; i += NW * 64) sTab[i] = phase_tab_entry<OP>(i);
@@ -475,19 +513,24 @@ __global__ __launch_bounds__(WAVES_R* WAVES_C * 64) void k_bwd8(Bwd8Args a) {
 
 // ---------------------------------------------------------------------------------------------
 // k_dw0_8: weight gradient of layer 0 from fp8 deltas (k_dw0 of siren_kernels.hip with the byte pieces expanded
-// to the 16-bit image one block ahead).  Ring: 8 slots of JW/32 KiB; D16: 2 x JW/16 KiB.
+// to the 16-bit image one block ahead).  Ring: NB slots of JW/32 KiB; D16: 2 x JW/16 KiB.  fp16 operands only.
 // ---------------------------------------------------------------------------------------------
 // LDS of k_dw0_8: [ring of NB blocks of fp8 pieces][two 16-bit images of a block][coordinate table, as k_dw0]
-template <int JW, int NB>
+// Two MFMAs per wave and block behind a workgroup barrier: bound by the latency of a step.  NB = 8; at width 256 a 4-slot
+// ring (64.5 KiB) lets two workgroups share a CU.
+template <int JW>
 struct Dw0Lds8 {
-  static constexpr int JT = JW / 32, KSJ = JW / 16;
+  static constexpr int JT = JW / 32, KSJ = JW / 16, NB = JW == 256 ? 4 : 8;
   static constexpr size_t oD16 = (size_t)NB * JT * 1024, oXY = oD16 + 2 * KSJ * 1024, bytes = oXY + 512;
   static_assert(bytes <= kLdsMax, "k_dw0_8 LDS budget");
 };
+static_assert(2 * Dw0Lds8<256>::bytes == 129 * 1024, "64.5 KiB per workgroup");
 
-template <int JW, typename OP, int NB = 8>
+template <int JW>
 __global__ __launch_bounds__(JW * 2) void k_dw0_8(Dw0Args a) {
-  using L = Dw0Lds8<JW, NB>;
+  using L = Dw0Lds8<JW>;
+  using OP = OpF16;
+  constexpr int NB = L::NB;
   constexpr int NW = JW / 32, JT = JW / 32, KSJ = JW / 16;
   constexpr int GD = JT / NW;   // = 1
   extern __shared__ __attribute__((aligned(16))) char smem[];

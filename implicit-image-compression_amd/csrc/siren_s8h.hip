@@ -1,7 +1,8 @@
 // siren_s8h.hip — k_bwd8h: the backward of one 256 x 256 HIDDEN layer from 8-bit scratch (phase bytes + fp8 deltas,
 // sf_config.scratch_format = 8) as a hand-cut software pipeline, one "slot" per MFMA (round 3).
 //
-// Arithmetic: that of k_bwd8<256, 256, 2, 4, false, false, OpF16, .., D8 = true> (siren_s8.hip), bit for bit - the
+// Arithmetic: that of k_bwd8 (siren_s8.hip) for a hidden layer of width 256 with fp8 deltas - the case <256, false, false, true>,
+// which Bwd8Case refuses in favour of this kernel - bit for bit: the
 // autograd backward of implicit_image/models/siren.py:56-68 for one hidden layer l:
 //     delta_{l-1} = (W_l^T delta_l) * omega cos(phi_{l-1})        phase X + epilogue E  (fp8 out)
 //     dW_l       += delta_l^T sin(phi_{l-1}),  db_l += sum delta_l   phase W
@@ -40,6 +41,7 @@
 namespace sf {
 
 constexpr int kBwd8hLD = 2;      // slots between a table lookup and the value that uses it
+constexpr int kBwd8hPark = 4;    // k-steps of every wave's stationary W^T rows parked in LDS (153 KiB in all)
 
 // the LDS layout above: ring depths and byte offsets (the kernel addresses LDS absolutely: the table is at address 0)
 template <int PARK>
@@ -50,6 +52,7 @@ struct Bwd8hLds {
   static_assert(bytes <= kLdsMax, "k_bwd8h LDS budget");
 };
 static_assert(Bwd8hLds<3>::bytes == 145 * 1024, "the figure in the header");
+static_assert(Bwd8hLds<kBwd8hPark>::bytes == 153 * 1024, "the kernel as built");
 
 // DBX: the row tile (0..3) whose bias-gradient sums this instantiation takes (= the wave's column index wc)
 // ROLE: 0 = waves 0-3 ("N": X | W + E), 1 = waves 4-7 ("S", their SIMD partners: W + E | X)

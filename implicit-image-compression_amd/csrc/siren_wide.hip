@@ -2,12 +2,14 @@
 //
 // The fused kernels of siren_kernels.hip keep a whole activation vector per pixel in registers and a
 // whole 256x256 weight gradient per workgroup; neither fits beyond width 256.  Wide networks therefore run
-// layer by layer with the activations (phases) and deltas in HBM, still in F-layout, through three kernels:
+// layer by layer with the activations (phases) and deltas in HBM, still in F-layout, through these kernels:
 //   k_wlayer0   phases and activations of layer 0 from the coordinates (elementwise)
-//   k_wgemm     Out^T[256-neuron block x 256 pixels per workgroup] = A-block * B, A (weights) streamed through
-//               an LDS ring by LDS-DMA, B (input pieces) read from HBM/L2 into registers two chunks ahead.
+//   k_wgemm2    Out^T[256-neuron block x 256 pixels per workgroup] = A-block * B, A (weights) and B (input pieces) streamed
+//               through an LDS ring by LDS-DMA.
 //               MODE 0: forward hidden layer (B = activation, epilogue -> phase AND activation),
-//               MODE 1: forward last layer + residual/loss, MODE 2: backward data (B = delta, epilogue x cos(phase))
+//               MODE 2: backward data (B = delta, epilogue x cos(phase))
+//   k_wgemm     (MODE 1 of the same argument struct) forward last layer + residual/loss: 32 padded output rows, B read from
+//               HBM/L2 into registers two chunks ahead
 //   k_wdw       weight gradient blocks: delta^T * activation, both operands read transposed from an LDS ring
 // Unlike the fused width-256 path, each hidden layer keeps BOTH its phase (unorm16, for cos in the backward)
 // and its activation sin(phase) (16-bit float, the GEMM operand) in HBM: every value is an operand of WD/256
@@ -150,13 +152,12 @@ struct WGemmArgs {
   int n_super, n_ob;     // 256-pixel super-blocks of the chunk, output blocks; grid = roundup(n_super, 8) * n_ob
 };
 
-// k_wgemm<1>: the last layer (32 padded output rows) + residual.  Workgroup = 8 waves = 256 pixels, one
+// k_wgemm: the last layer (32 padded output rows) + residual.  Workgroup = 8 waves = 256 pixels, one
 // 32-pixel block per wave; the [32 x WD] weight image streams through a 4-slot LDS ring (4 k-steps per chunk),
 // the activations are prefetched two chunks ahead into registers.  (Hidden layers: k_wgemm2 below.)
 // LDS of k_wgemm: [ring of NB chunks of OT tiles x 4 k-steps][8 SSE partials]
-template <int MODE>
 struct WGemmLds {
-  static constexpr int OT = MODE == 1 ? 1 : 8, NB = 4, CH = OT * 4 * 1024;   // 32-row tiles per chunk, ring slots, bytes per chunk
+  static constexpr int OT = 1, NB = 4, CH = OT * 4 * 1024;   // 32-row tiles per chunk, ring slots, bytes per chunk
   static constexpr size_t oRed = (size_t)NB * CH, bytes = oRed + 64;
   static_assert(bytes <= kLdsMax, "k_wgemm LDS budget");
 };
@@ -172,12 +173,11 @@ struct WDwLds {
   static_assert(bytes <= kLdsMax, "k_wdw LDS budget");
 };
 
-template <int MODE, typename OP>
+template <typename OP>
 __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
-  static_assert(MODE == 1, "hidden layers and the data gradient run k_wgemm2");
-  using L = WGemmLds<MODE>;
-  constexpr int TW = MODE == 1 ? 1 : 4;       // tiles per wave
-  constexpr int PBW = MODE == 1 ? 1 : 2;      // pixel blocks per wave
+  using L = WGemmLds;
+  constexpr int TW = 1;       // tiles per wave
+  constexpr int PBW = 1;      // pixel blocks per wave
   constexpr int OT = L::OT, NB = L::NB, CH = L::CH;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sRed = reinterpret_cast<float*>(smem + L::oRed);
@@ -190,8 +190,8 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
   const int ob = q % a.n_ob;
   const int sb = (q / a.n_ob) * 8 + xcd;                                // 256-pixel super-block
   if (sb >= a.n_super) return;                                          // grid padding (whole workgroup leaves)
-  const int t0 = MODE == 1 ? 0 : TW * (wave & 1);                       // first tile of this wave inside the block
-  const long pb0 = (long)sb * kWavesFwd + (MODE == 1 ? wave : 2 * (wave >> 1));
+  const int t0 = 0;                                                     // first tile of this wave inside the block
+  const long pb0 = (long)sb * kWavesFwd + wave;
   const u32x4* Ablk = a.A + (size_t)ob * a.a_block_pieces * 64;
   auto stage = [&](int c) {
     char* base = smem + (c % NB) * CH;
@@ -201,20 +201,18 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
 #pragma unroll
   for (int t = 0; t < TW; ++t) {
     f32x16 init = f32x16{};
-    if (MODE != 2) {
 #pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(&a.bias[(ob * OT + t0 + t) * 32 + 8 * q4 + 4 * h]);
-        init[4 * q4 + 0] = b.x; init[4 * q4 + 1] = b.y; init[4 * q4 + 2] = b.z; init[4 * q4 + 3] = b.w;
-      }
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const f32x4 b = *reinterpret_cast<const f32x4*>(&a.bias[(ob * OT + t0 + t) * 32 + 8 * q4 + 4 * h]);
+      init[4 * q4 + 0] = b.x; init[4 * q4 + 1] = b.y; init[4 * q4 + 2] = b.z; init[4 * q4 + 3] = b.w;
     }
 #pragma unroll
     for (int p = 0; p < PBW; ++p) acc[t][p] = init;
   }
   float tgt[3] = {0.f, 0.f, 0.f};
   const long pix = a.pix0 + pb0 * 32 + m;
-  const bool valid = MODE == 1 && pix < a.npix;
-  if (MODE == 1 && a.img && h == 0 && valid) {
+  const bool valid = pix < a.npix;
+  if (a.img && h == 0 && valid) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) if (c < a.nout) tgt[c] = a.img[pix * a.nout + c];
   }
@@ -308,7 +306,7 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
 // in registers, exact), a tile's sixteen outgoing values leave in one store.  Scales: csrc/siren_kernels.hip k_fp8_links.
 template <int MODE, typename OP, bool P8 = false, bool IN8 = false, bool OUT8 = false>
 __global__ __launch_bounds__(512, 1) void k_wgemm2(WGemmArgs a) {
-  static_assert(MODE == 0 || MODE == 2, "last layer: k_wgemm<1>");
+  static_assert(MODE == 0 || MODE == 2, "last layer: k_wgemm");
   static_assert(MODE == 2 || (!IN8 && !OUT8), "fp8 deltas: the data-gradient product only");
   constexpr int NWV = 8;                                         // waves per workgroup
   using L = WGemm2Lds;

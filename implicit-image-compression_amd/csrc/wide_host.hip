@@ -53,7 +53,7 @@ int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob) {
   b.n_super = n_super; b.n_ob = n_ob;
   const unsigned grid = (unsigned)((n_super + 7) / 8 * 8 * n_ob);
   if constexpr (MODE == 1) {
-    return with_op(h, [&](auto op) { return launch(h, k_wgemm<1, decltype(op)>, grid, 512, WGemmLds<1>::bytes, b); });
+    return with_op(h, [&](auto op) { return launch(h, k_wgemm<decltype(op)>, grid, 512, WGemmLds::bytes, b); });
   } else {
     if constexpr (MODE == 2) {
       if (h->d8) {   // fp8 deltas (format 8): out always, in for every launch below the last layer's
