@@ -540,8 +540,8 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
                   float* new_weight_dev) try {
   if (!h || !w_dev || !centers_dev || !centroids_dev) return fail(SF_ERR_INVALID, "null argument");
   SF_NO_RENDER(h, "sf_kmeans_fit");
-  if (n <= 0 || K < 1 || K >= kKmMaxK || centroids_cap < K + 1 || iter_limit < 0)
-    return fail(SF_ERR_INVALID, "sf_kmeans_fit: need n > 0, 1 <= K < 512, centroids_cap >= K + 1");
+  if (n <= 0 || K < 2 || K >= kKmMaxK || centroids_cap < K + 1 || iter_limit < 0)
+    return fail(SF_ERR_INVALID, "sf_kmeans_fit: need n > 0, 2 <= K < 512, centroids_cap >= K + 1, iter_limit >= 0");
   DevGuard dev_guard(h->cfg.device);
   if (!h->km_ws) {
     if (dev_alloc(h, h->km_ws, sizeof(KmWs))) return fail(SF_ERR_NOMEM, "hipMalloc failed (k-means workspace)");

@@ -24,22 +24,28 @@ constexpr int kKmMaxK = 512;      // 2^bits <= 512 (the reference's slurm script
 struct KmWs {                     // device workspace of a handle (zeroed at allocation)
   long long sums[kKmMaxK];
   int counts[kKmMaxK];
-  int done;                       // 1 once (sum |dc|)^2 < tol: later iterations leave the centres alone
+  int done;                       // 1 once (sum |dc|)^2 < tol: later iterations leave the centres alone; 2: the call is empty
   int n_cent;                     // centroids after {0} U centres -> unique
   double scale;                   // fixed-point unit of the segment sums: 2^e with n * max|w| * 2^e < 2^61
   float sorted[kKmMaxK + 1];
 };
 
-// one thread: fixed-point scale from the initial guess (linspace(min, max): its ends bound every weight), state cleared
+// one thread: fixed-point scale from the initial guess, state cleared.  PRECONDITION (include/siren_fit.h): every non-zero
+// weight is at most max(|centers[0]|, |centers[K-1]|) in magnitude - the ends of linspace(min, max, K) bound every weight
+// for K >= 2 (K = 1 is refused: its one centre is the minimum alone); with it n * max|w| * scale < 2^61 and no segment sum
+// can overflow.  A guess whose end is not finite (linspace(inf, -inf): a tensor without a non-zero weight) marks the call
+// EMPTY: k_km_assign / k_km_update then change nothing and k_km_finish writes the one centroid +0.0.
 __global__ void k_km_init(const float* centers, int K, long n, KmWs* ws) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const float m = fmaxf(fabsf(centers[0]), fabsf(centers[K - 1]));
+    const float lo = fabsf(centers[0]), hi = fabsf(centers[K - 1]);
+    const bool empty = !(lo < __builtin_inff()) || !(hi < __builtin_inff());         // (NaN compares false)
+    const float m = fmaxf(lo, hi);
     int e = 0;
     frexpf(m > 0.f ? m : 1.f, &e);                               // m < 2^e
     int ln = 0;
     while ((1L << ln) < n + 1) ++ln;                             // n < 2^ln
     ws->scale = ldexp(1.0, 60 - ln - e);
-    ws->done = 0;
+    ws->done = empty ? 2 : 0;
   }
   for (int i = threadIdx.x; i < kKmMaxK; i += blockDim.x) { ws->sums[i] = 0; ws->counts[i] = 0; }
 }
@@ -100,12 +106,13 @@ __global__ __launch_bounds__(kKmMaxK) void k_km_update(float* centers, int K, Km
   }
 }
 
-// {0} U centres -> unique (ascending) -> ordered by |c| (ties: the smaller value first) -> centroids_out (zero padded)
+// {0} U centres -> unique (ascending) -> ordered by |c| (ties: the smaller value first) -> centroids_out (zero padded);
+// an empty call (done == 2, k_km_init): {0} alone
 __global__ __launch_bounds__(kKmMaxK) void k_km_finish(const float* centers, int K, KmWs* ws, float* cent_out, int n_out, int* n_cent_out) {
   __shared__ float v[kKmMaxK + 1];
   __shared__ float u[kKmMaxK + 1];
   __shared__ int nu;
-  const int t = threadIdx.x, m = K + 1;
+  const int t = threadIdx.x, m = ws->done == 2 ? 1 : K + 1;                   // (done is rewritten after the last barrier only)
   for (int i = t; i < m; i += blockDim.x) v[i] = i == 0 ? 0.0f : centers[i - 1];
   __syncthreads();
   // rank sort ascending (distinct positions for equal values by index), m <= 513

@@ -355,11 +355,14 @@ class SirenEngine:
         _check(self.lib.sf_debug_scratch(self.h, {"phases": 0, "deltas": 1, "dlast": 2, "slabs": 3}[which], C.byref(p), C.byref(n)))
         return torch.as_tensor(_DevView(p.value, n.value, "|u1"), device=self.device)
 
-    def kmeans_fit(self, weight: torch.Tensor, guess: torch.Tensor, iter_limit: int = 5, tol: float = 1e-4):
+    def kmeans_fit(self, weight: torch.Tensor, guess: torch.Tensor, iter_limit: int = 5, tol: float = 1e-4,
+                   centres_out: Optional[torch.Tensor] = None):
         """sf_kmeans_fit on this handle's stream, no host sync: (centroids [K+1, zero padded], n_centroids [device int32],
-        labels [int64, weight's shape], new_weight)."""
+        labels [int64, weight's shape], new_weight).  The guess is left as it is; centres_out (float32 [K] on the device)
+        receives what the call leaves in centers_dev, the Lloyd centres."""
         w = _f32_cuda(weight.reshape(-1))
-        centers = _f32_cuda(guess.reshape(-1)).clone()
+        guess = _f32_cuda(guess.reshape(-1))
+        centers = guess.clone() if centres_out is None else _f32_cuda(centres_out, guess.numel()).copy_(guess)
         K = centers.numel()
         cent = torch.empty(K + 1, device=self.device)
         ncent = torch.empty(1, dtype=torch.int32, device=self.device)

@@ -54,23 +54,34 @@ def kmeans_predict(x: torch.Tensor, cluster_centers: torch.Tensor) -> torch.Tens
 def find_centroids_native(weight: torch.Tensor, n_clusters: int, eng):
     """The same on the engine's stream WITHOUT a host synchronisation (sf_kmeans_fit, csrc/siren_kmeans.hip): returns
     (centroids zero-padded to n_clusters entries, n_centroids as a device int32, labels, new_weight).  The initial guess is
-    torch.linspace over masked min / max, so it is bit-identical to the torch path's."""
+    torch.linspace over masked min / max, so it is bit-identical to the torch path's.  Without a non-zero weight that is
+    linspace(inf, -inf), no finite entry: k_km_init takes the non-finite ends for an empty call (no host read here)."""
     w = weight.detach().float().contiguous()
+    return eng.kmeans_fit(w, native_guess(w, n_clusters - 1))
+
+
+def native_guess(w: torch.Tensor, n_centres: int) -> torch.Tensor:
+    """linspace(min, max, n_centres) over the non-zero entries of w without indexing by a mask (no host read for a size)"""
     nz = w != 0
     inf = torch.tensor(float("inf"), device=w.device)
     mn = torch.where(nz, w, inf).min()
     mx = torch.where(nz, w, -inf).max()
-    guess = torch.linspace(mn, mx, n_clusters - 1, device=w.device, dtype=w.dtype)
-    return eng.kmeans_fit(w, guess)
+    return torch.linspace(mn, mx, n_centres, device=w.device, dtype=w.dtype)
 
 
 def find_centroids(weight: torch.Tensor, n_clusters: int):
     """(centroids, labels, new_weight) of one weight tensor (kmeans.py:110-150): linspace(min,max)
     guess over the NON-ZERO weights with n_clusters-1 centres, 0 prepended, torch.unique, sorted by
-    |c|, labels = nearest centroid of every weight (zeros included)."""
+    |c|, labels = nearest centroid of every weight (zeros included).  A tensor without a non-zero weight (a layer
+    RigL has pruned away) gets the one centroid +0.0 and every label 0, where the reference raises on the empty
+    .min() (sf_kmeans_fit returns the same)."""
     shape = weight.shape
     w = weight.reshape(-1, 1)
     nz = w[w != 0].reshape(-1, 1)
+    if nz.numel() == 0:
+        centroids = torch.zeros(1, device=w.device, dtype=w.dtype)
+        labels = torch.zeros(shape, device=w.device, dtype=torch.int64)
+        return centroids, labels, centroids[labels]
     guess = torch.linspace(nz.min(), nz.max(), n_clusters - 1, device=w.device, dtype=w.dtype).reshape(-1, 1)
     _, centroids = kmeans_fit(nz, guess)
     centroids = torch.cat((torch.zeros_like(centroids)[:1], centroids))
@@ -107,9 +118,10 @@ class KmeansQuant:
         if os.environ.get("SIREN_FIT_NATIVE_KMEANS", "1") == "0":       # A/B knob: the torch host mirror
             eng = None
         for m in self._targets:
-            if eng is not None and m.weight.is_cuda and self.n_clusters <= 512:
+            if eng is not None and m.weight.is_cuda and 4 <= self.n_clusters <= 512:
                 # native path: five small kernels per layer on the engine's stream, no host sync; the centroid tensor keeps
-                # its full 2^bits length (zero padded) until update_weights() trims it to the count the device reports
+                # its full 2^bits length (zero padded) until update_weights() trims it to the count the device reports.
+                # (bits = 1 is one centre: its guess does not bracket the weights, sf_kmeans_fit refuses it)
                 centroids, m.n_centroids, labels, new_weight = find_centroids_native(m.weight.data, self.n_clusters, eng)
             else:
                 centroids, labels, new_weight = find_centroids(m.weight.data, self.n_clusters)

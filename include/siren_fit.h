@@ -186,7 +186,15 @@ int sf_debug_scratch(sf_handle* h, int32_t which, void** dev_ptr, int64_t* bytes
  *   centroids_dev [cap]  out: {0} U centres -> unique -> ordered by |c|, zero padded (cap >= K + 1)
  *   n_centroids_dev      out (device int, may be NULL): how many of them are real
  *   labels_dev [n]       out (may be NULL): argmin of the squared distance, first index wins (int64, as torch.argmin)
- *   new_weight_dev [n]   out (may be NULL): centroids[labels] */
+ *   new_weight_dev [n]   out (may be NULL): centroids[labels]
+ * Needs n > 0, 2 <= K < 512, cap >= K + 1, iter_limit >= 0 (SF_ERR_INVALID otherwise, nothing is launched).
+ * PRECONDITION: every non-zero weight is at most max(|centers[0]|, |centers[K-1]|) in magnitude.  The 64-bit fixed-point
+ * unit of the segment sums is sized from those two ends; the linspace guess gives it for K >= 2 (for K = 1 the guess is the
+ * minimum alone, which is why K = 1 is refused).  A guess that does not bracket the weights overflows the sums.
+ * EMPTY CALL: a guess whose first or last entry is not finite - torch.linspace(inf, -inf, K), what the masked min / max
+ * give for a tensor without a non-zero weight - is decided on the device, without a host read: centers_dev is left as it
+ * is, centroids = {+0.0} (n_centroids 1, zero padded), every label 0, every new weight +0.0.  (The reference raises on
+ * the empty .min(); INTEGRATION.md section 4 records the departure.) */
 int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_dev, int32_t K, int32_t iter_limit, float tol,
                   float* centroids_dev, int32_t centroids_cap, int32_t* n_centroids_dev, int64_t* labels_dev,
                   float* new_weight_dev);
