@@ -28,23 +28,21 @@ decode.* keys
                     none for this model and picture (`kernel_available`), raised before the device is touched; this is
                     how mlp=fourier decodes on its render kernel
 
-SIREN of engine width 32 / 64 / 128 / 256 runs the engine's render kernel (sf_render: bytes straight from the last-layer
-epilogue, no training state on the device), and mlp=wavelet_siren of those widths on an even, square picture runs
-sf_wavelet_render (the render forward of both sub-networks over the coefficient window a band of pixel rows needs, then
-k_wv_render).  A Small_Dense width the engine zero-pads (90 -> 128, 181 -> 256) runs at the padded width.  Everything else -
-mlp=fourier, SIREN 512 / 1024 - builds the registry model, loads the state dict, runs its own forward and converts with the
-same formula in torch.  `render_path` decides and the log names the path that ran.
+Four model families decode; `family` looks a run's up once from its shape.  Each has a render kernel at engine width 32 /
+64 / 128 / 256 (a Small_Dense width the engine zero-pads, 90 -> 128, runs at the padded width): bytes straight from the last
+epilogue, no training state or activation plane on the device.  `_render` does that job for all four: the family's CPU
+model builds and fills the handle (models/binding.py); a band is a slice of the coordinate vectors or, for WaveletSiren,
+a pixel window.  Without a kernel (width 512 / 1024, a WaveletSiren picture that is not even and square) or under
+decode.render=torch the same model runs its own forward on the device, bytes by the same formula in torch.  The log names the path.
 
-mlp=fourier of engine width <= 256 has a render kernel too (sf_render on an sf_fourier_render_create handle: the RENDER
-form of k_ff_fwd, `render_fourier`): windows are slices of the coordinate vectors, decode.band_rows applies, and no
-activation plane or full fp32 prediction is allocated.  `render_path` still answers torch for it, so it runs under
-decode.render=kernel only; the bytes of the two paths are the same.
+  family          auto runs   kernel runs                           engine class          entry points
+  siren           kernel      sf_render                             RenderEngine          render_kernel, load_weights
+  feather         kernel      sf_feather_render_load + sf_render    FeatherRenderEngine   render_feather, load_feather
+  fourier         torch       sf_render (RENDER form of k_ff_fwd)   FourierRenderEngine   render_fourier, load_weights
+  wavelet_siren   kernel      sf_wavelet_render                     WaveletRenderEngine   render_wavelet, load_weights
 
-A masking=Feathermap run (model.pth holds the feather vector [V1 | V2 | scalers], not the network) goes its own way:
-`load_feather` reads and checks the vector, and at engine width <= 256 one FeatherRenderEngine takes it
-(sf_feather_render_load: W = scaler * (V1 V2) by the engine's own fixed-order product, then sf_render), so the picture is
-bit for bit the one whose PSNR `fit` logged.  Every decode.* key above applies.  decode.render=torch, or width 512 / 1024,
-rebuilds the FeatherNet and runs its own forward; there is no container for such a run (decode.source=container raises).
+feather is SIREN under masking=Feathermap: model.pth holds the feather vector [V1 | V2 | scalers] and there is no container;
+the handle forms W = scaler * (V1 V2) by the engine's own fixed-order product: bit for bit the picture `fit` logged the PSNR of.
 """
 import json
 import logging
@@ -52,22 +50,23 @@ import math
 import os
 import sys
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from .config import Cfg, _load_yaml, _parse_scalar, _set_path, _wrap
-from .data import load_img, read_ppm, write_ppm, write_ppm16
-from .models.siren import next_kernel_width
+from .data import get_grid, load_img, read_ppm, write_ppm, write_ppm16
+from .models import registry
+from .models.fourier import MAP_SIZES as FOURIER_MAPS, engine_takes as fourier_engine_takes
+from .models.siren import KERNEL_WIDTHS, Siren, layer_sizes, next_kernel_width
+from .models.wavelet_siren import check_image
 
 REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 DECODE_JSON = "decode.json"
 BAND_BYTES = 256 << 20            # one band's byte output stays under this
 ROW_LIMIT = 1 << 40               # a handle decodes (row, col) exactly while rows * width^2 < 2^40 (sf_create)
-KERNEL_WIDTHS = (32, 64, 128, 256)
 RENDER_MODES = ("auto", "kernel", "torch")
 SAMPLE_BITS = (8, 16)
-FOURIER_MAPS = (64, 128, 256, 512)
 SHAPE_KEYS = ("mlp.depth", "mlp.hidden_size")
 
 
@@ -91,14 +90,6 @@ def write_decode_json(out_dir: str, cfg, state_dict_keys: Sequence[str]) -> str:
     return path
 
 
-def read_decode_json(run_dir: str) -> Optional[dict]:
-    path = os.path.join(run_dir, DECODE_JSON)
-    if not os.path.exists(path):
-        return None
-    with open(path) as f:
-        return json.load(f)
-
-
 def split_overrides(argv: Sequence[str]) -> Tuple[Dict[str, str], List[str]]:
     """decode.* keys (raw strings: `a:b` ranges are not YAML scalars) and the fit-style overrides"""
     dec, rest = {}, []
@@ -117,15 +108,15 @@ def resolve_shape(run_dir: str, overrides: Sequence[str] = (), conf_dir: Optiona
     """decode.json of the run directory with `key=value` overrides on top (overrides win; `mlp=fourier` /
     `entropy_coding=lzma` select a conf/ group file as in fit).  Without decode.json the overrides must name the network."""
     conf_dir = conf_dir or os.environ.get("IIC_CONF", os.path.join(REPO, "conf"))
-    rec = read_decode_json(run_dir)
-    given = set()
-    if rec is None:
+    path, given = os.path.join(run_dir, DECODE_JSON), set()
+    missing_file = not os.path.exists(path)
+    if not missing_file:
+        with open(path) as f:
+            rec = json.load(f)
+    else:
         rec = {"mlp": {"name": "siren", "first_omega_0": 50, "hidden_omega_0": 30, "outermost_linear": True},
                "img": {}, "entropy_coding": {"stream_name": "plain"}, "engine": {}, "masking_name": None,
                "small_dense_density": None, "state_dict_keys": None}
-        missing_file = True
-    else:
-        missing_file = False
     for ov in overrides:
         key, _, val = ov.partition("=")
         key = key.lstrip("+")
@@ -147,41 +138,50 @@ def resolve_shape(run_dir: str, overrides: Sequence[str] = (), conf_dir: Optiona
         need = [k for k in SHAPE_KEYS if k not in given]
         if need:
             raise FileNotFoundError(
-                f"{os.path.join(run_dir, DECODE_JSON)} not found (a run written before `fit` recorded the model shape, or by the "
+                f"{path} not found (a run written before `fit` recorded the model shape, or by the "
                 f"reference): pass {' '.join(k + '=...' for k in need)} (and mlp=<name>, mlp.first_omega_0=..., "
                 "mlp.hidden_omega_0=..., img.height=... img.width=... when they differ from the defaults) on the command line")
     return _wrap(rec)
 
 
 # ---- weights ----------------------------------------------------------------------------------------------
+def _check_source(source: Optional[str]):
+    if source not in (None, "", "container", "pth"):
+        raise ValueError(f"decode.source must be container or pth, got {source!r}")
+
+
+def _fp32(sd) -> "OrderedDict[str, torch.Tensor]":
+    return OrderedDict((k, v.detach().float().cpu()) for k, v in sd.items())
+
+
+def read_pth(path: str) -> "OrderedDict[str, torch.Tensor]":
+    """model.pth as `fit` saves it (the state dict, or a dict that holds it under 'state_dict'), fp32 on the CPU"""
+    blob = torch.load(path, map_location="cpu")
+    return _fp32(blob["state_dict"] if isinstance(blob, dict) and "state_dict" in blob else blob)
+
+
 def load_weights(run_dir: str, shape: Cfg, source: Optional[str] = None) -> Tuple["OrderedDict[str, torch.Tensor]", str]:
     """(fp32 state dict on the CPU, 'container' | 'pth').  The container is preferred when the run has one."""
     from .pipeline import entropy_coding
-    if shape.get("masking_name") == "Feathermap":
+    if is_feather(shape):
         from .pipeline.feathermap.feathernet import DEPLOY_UNSUPPORTED
         raise NotImplementedError("a masking=Feathermap run saves no deployable weights (model.pth holds the feather vector, not "
                                   f"the network): {DEPLOY_UNSUPPORTED}")
     qdir = os.path.join(run_dir, "model_quantized")
     have_q = os.path.exists(os.path.join(qdir, "meta_data.json")) and os.path.exists(os.path.join(qdir, "compressed_weights.data"))
     pth = os.path.join(run_dir, "model.pth")
-    if source not in (None, "", "container", "pth"):
-        raise ValueError(f"decode.source must be container or pth, got {source!r}")
+    _check_source(source)
     if source == "container" and not have_q:
         raise FileNotFoundError(f"decode.source=container: {qdir} holds no compressed_weights.data / meta_data.json")
     if source == "pth" and not os.path.exists(pth):
         raise FileNotFoundError(f"decode.source=pth: {pth} not found")
     if source == "container" or (not source and have_q):
         ec = dict(shape.get("entropy_coding") or {})
-        stream = ec.pop("stream_name", "plain")
-        sd = entropy_coding.decompress_state_dict(qdir, stream_name=stream, **ec)
-        used = "container"
+        sd, used = _fp32(entropy_coding.decompress_state_dict(qdir, stream_name=ec.pop("stream_name", "plain"), **ec)), "container"
     elif os.path.exists(pth):
-        blob = torch.load(pth, map_location="cpu")
-        sd = blob["state_dict"] if isinstance(blob, dict) and "state_dict" in blob else blob
-        used = "pth"
+        sd, used = read_pth(pth), "pth"
     else:
         raise FileNotFoundError(f"{run_dir} holds neither model_quantized/ nor model.pth")
-    sd = OrderedDict((k, v.detach().float().cpu()) for k, v in sd.items())
     want = shape.get("state_dict_keys")
     if want:   # the dense names the fit recorded (a quantised copy adds centroids / labeled_weight, which come back as weight)
         dense = [k for k in want if "centroids" not in k and "labeled_weight" not in k]
@@ -195,13 +195,6 @@ def is_feather(shape: Cfg) -> bool:
     return shape.get("masking_name") == "Feathermap"
 
 
-def _feather_layers(shape: Cfg) -> Tuple[List[int], List[int]]:
-    """(logical_out, logical_in) of every Linear of the SIREN of `shape`"""
-    m = shape.mlp
-    fans = [int(m.get("input_size", 2))] + [engine_width(shape)] * (int(m.depth) - 1) + [int(m.get("output_size", 3))]
-    return fans[1:], fans[:-1]
-
-
 def feather_keys(depth: int) -> List[str]:
     """the state-dict keys of a FeatherNet over a SIREN of `depth` layers, in named_parameters() order"""
     return ["_V1", "_V2"] + [f"module.layers.{l}.linear.{kind}_p" for l in range(depth) for kind in ("weight", "bias")]
@@ -211,17 +204,14 @@ def load_feather(run_dir: str, shape: Cfg, source: Optional[str] = None) -> "Ord
     """The fp32 CPU state dict of a masking=Feathermap run's model.pth: _V1 [n, m], _V2 [m, n] and one scalar per weight /
     bias tensor, checked against decode.json's key list and against the network of `shape` (n = ceil(sqrt(P))).  A tensor
     that is missing or of another shape raises a ValueError that names it."""
-    if source not in (None, "", "container", "pth"):
-        raise ValueError(f"decode.source must be container or pth, got {source!r}")
+    _check_source(source)
     if source == "container":
         raise FileNotFoundError("decode.source=container: a masking=Feathermap run has no container (fit writes model.pth, the "
                                 "feather vector in fp32, and nothing under model_quantized/)")
     pth = os.path.join(run_dir, "model.pth")
     if not os.path.exists(pth):
         raise FileNotFoundError(f"{pth} not found (a masking=Feathermap run is decoded from model.pth)")
-    blob = torch.load(pth, map_location="cpu")
-    sd = blob["state_dict"] if isinstance(blob, dict) and "state_dict" in blob else blob
-    sd = OrderedDict((k, v.detach().float().cpu()) for k, v in sd.items())
+    sd = read_pth(pth)
     for k in feather_keys(int(shape.mlp.depth)):
         if k not in sd:
             raise ValueError(f"pth: the feather vector has no tensor {k}")
@@ -236,10 +226,11 @@ def load_feather(run_dir: str, shape: Cfg, source: Optional[str] = None) -> "Ord
 
 
 def feather_geometry(shape: Cfg, sd) -> Tuple[int, int, List[int], List[int]]:
-    """(n, m, logical_out, logical_in) as sf_feather_render_attach takes them: V1 is [n, m], V2 [m, n], and n must be
-    ceil(sqrt(P)) for the P weights and biases of the SIREN of `shape` (feathernet.py:186); else a ValueError naming the
-    tensor"""
-    outs, ins = _feather_layers(shape)
+    """(n, m, logical_out, logical_in) as sf_feather_render_attach takes them, from a shape alone (no model yet): V1 is
+    [n, m], V2 [m, n], and n must be ceil(sqrt(P)) for the P weights and biases of the SIREN of `shape`
+    (feathernet.py:186); else a ValueError naming the tensor"""
+    mlp = shape.mlp
+    outs, ins = layer_sizes(int(mlp.get("input_size", 2)), engine_width(shape), int(mlp.depth), int(mlp.get("output_size", 3)))
     P = sum(o * i + o for o, i in zip(outs, ins))
     n = math.isqrt(P - 1) + 1                      # ceil(sqrt(P)), in integers
     v1, v2 = tuple(sd["_V1"].shape), tuple(sd["_V2"].shape)
@@ -260,7 +251,6 @@ def feather_flat(sd, depth: int) -> torch.Tensor:
 def feather_model(sd, shape: Cfg):
     """the FeatherNet of `shape` with `sd` loaded, on the CPU: the registry SIREN under compress = (2 m - 1) / n, which
     ceil(compress * n / 2) turns back into m"""
-    from .models import registry
     from .pipeline.feathermap import FeatherNet
     n, m, _, _ = feather_geometry(shape, sd)
     with torch.random.fork_rng(devices=[]):       # the constructors draw an initialisation nobody needs
@@ -268,24 +258,6 @@ def feather_model(sd, shape: Cfg):
     assert (net._size_n, net._size_m) == (n, m), ((net._size_n, net._size_m), (n, m))
     net.load_state_dict(sd)
     return net
-
-
-def render_feather(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
-                   want_pred: bool = False, device: int = 0, bits: int = 8):
-    """render_kernel for a masking=Feathermap run: uint8 [h, w, C] on the CPU (and the fp32 prediction when asked) of the
-    grid rows x cols, band by band on ONE FeatherRenderEngine that materialised the weights once.  bits=16: int32 values
-    0..65535 from sf_render16."""
-    from ._engine import FeatherRenderEngine
-    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
-    C = int(m.get("output_size", 3))
-    n, fm, outs, ins = feather_geometry(shape, sd)
-    bands = plan_bands(rows.numel(), cols.numel(), C, band_rows, sample_bytes=bits // 8)
-    eng = FeatherRenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.depth), n, fm, outs, ins,
-                              float(m.get("first_omega_0", 50.0)), float(m.get("hidden_omega_0", 30.0)),
-                              bool(m.get("outermost_linear", True)), C, eng_kw.get("compute_dtype", "f16"), device=device,
-                              chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
-    return _render_grid(eng, lambda e: e.load_feather(feather_flat(sd, int(m.depth)).to(e.device)), rows, cols, bands,
-                        want_pred, bits)
 
 
 # ---- bytes ------------------------------------------------------------------------------------------------
@@ -333,58 +305,85 @@ def _span(spec: Optional[str], n: int, what: str) -> Tuple[int, int]:
     return lo, hi
 
 
-# ---- the two paths ----------------------------------------------------------------------------------------
+# ---- the families and the two paths ------------------------------------------------------------------------
 def engine_width(shape: Cfg) -> int:
-    import numpy as np
-    return int(shape.mlp.hidden_size * np.sqrt(shape.get("small_dense_density") or 1.0))   # siren.py:88
+    return int(shape.mlp.hidden_size * math.sqrt(shape.get("small_dense_density") or 1.0))   # siren.py:88
 
 
 def padded_width(shape: Cfg) -> Optional[int]:
     """the width the engine runs the network at: the logical width, or the next kernel width when it zero-pads (the
     models' own rule, Siren._engine_width); None above 1024"""
-    return next_kernel_width(engine_width(shape), KERNEL_WIDTHS + (512, 1024))
+    return next_kernel_width(engine_width(shape), Siren.WIDTHS)
 
 
-def render_path(shape: Cfg, height: Optional[int] = None, width: Optional[int] = None) -> Tuple[str, str]:
-    """('kernel' | 'torch', why): the one place that decides how a model is rendered.  height / width: the picture to draw
-    (default: the fitted size), which matters to WaveletSiren only"""
-    name = shape.mlp.get("name", "siren")
-    if name not in ("siren", "wavelet_siren"):
-        return "torch", f"mlp={name} has no render kernel"
+class Family(NamedTuple):
+    """what `decode` needs to know of a model family; `family` is the one place that tells them apart"""
+    available: Callable          # (shape, H, W) -> (is there a render kernel for this model and picture, why)
+    auto_kernel: bool            # decode.render=auto runs the kernel when there is one
+    load: Callable               # (run_dir, shape, decode.source) -> (fp32 CPU state dict, 'container' | 'pth')
+    model: Callable              # (state dict, shape) -> the CPU model, which also builds and fills the render handle
+    windowed: bool = False       # a band is a pixel window of an even, square picture, not a slice of coordinate vectors
+
+
+def _narrow(shape: Cfg) -> Tuple[int, Optional[int], str]:
+    """(logical width, the kernel width it renders at or None, the note a why string carries when the two differ)"""
     w, wp = engine_width(shape), padded_width(shape)
-    pad = "" if wp == w else f" (width {w} zero-padded)"
-    if name == "wavelet_siren":
-        img = shape.get("img") or {}
-        H, W = int(height or img.get("height") or 0), int(width or img.get("width") or 0)
-        if wp not in KERNEL_WIDTHS:
-            return "torch", f"WaveletSiren width {w} is above 256: no render kernel"
-        if H != W or H < 2 or H % 2:
-            return "torch", f"WaveletSiren needs an even, square picture (got {H}x{W}): no render kernel"
-        return "kernel", f"WaveletSiren {wp}x{shape.mlp.depth}{pad}: sf_wavelet_render"
-    if wp not in KERNEL_WIDTHS:
-        return "torch", f"SIREN width {w} is on the wide path: no render kernel"
-    if is_feather(shape):
-        return "kernel", f"Feathermap {wp}x{shape.mlp.depth}{pad}: sf_feather_render_load + sf_render"
-    return "kernel", f"SIREN {wp}x{shape.mlp.depth}{pad}: sf_render"
+    return w, (wp if wp in KERNEL_WIDTHS else None), ("" if wp == w else f" (width {w} zero-padded)")
+
+
+def _siren_kernel(shape: Cfg, H: int, W: int, what: str = "SIREN", entry: str = "sf_render") -> Tuple[bool, str]:
+    w, wp, pad = _narrow(shape)
+    if wp is None:
+        return False, f"SIREN width {w} is on the wide path: no render kernel"
+    return True, f"{what} {wp}x{shape.mlp.depth}{pad}: {entry}"
+
+
+def _wavelet_kernel(shape: Cfg, H: int, W: int) -> Tuple[bool, str]:
+    w, wp, pad = _narrow(shape)
+    if wp is None:
+        return False, f"WaveletSiren width {w} is above 256: no render kernel"
+    if H != W or H < 2 or H % 2:
+        return False, f"WaveletSiren needs an even, square picture (got {H}x{W}): no render kernel"
+    return True, f"WaveletSiren {wp}x{shape.mlp.depth}{pad}: sf_wavelet_render"
+
+
+def _fourier_kernel(shape: Cfg, H: int, W: int) -> Tuple[bool, str]:
+    m, (w, wp, pad) = shape.mlp, _narrow(shape)
+    n_linear, ms = int(m.get("depth", 8)) - 1, int(m.get("map_size", 128))
+    fin, fout = m.get("input_size", 2), m.get("output_size", 3)
+    if wp is None:
+        return False, f"FourierNet width {w} is above 256: no render kernel"
+    if not fourier_engine_takes(int(fin), int(fout), ms, n_linear):         # FourierNet's own constructor rule
+        return False, (f"FourierNet with map_size {ms}, {n_linear} Linear layers, input_size {fin}, output_size {fout}: the "
+                       f"engine takes map_size {' / '.join(map(str, FOURIER_MAPS))}, 2..12 layers, 2 -> 3")
+    return True, f"FourierNet {wp}x{n_linear} map {ms}{pad}: sf_render"
+
+
+def family(shape: Cfg) -> Family:
+    """siren, feather (SIREN under masking=Feathermap), fourier or wavelet_siren; any other mlp.name fails at the registry"""
+    name = shape.mlp.get("name", "siren")
+    if name == "siren" and is_feather(shape):     # model.pth holds the feather vector, not the network
+        return Family(lambda *a: _siren_kernel(*a, "Feathermap", "sf_feather_render_load + sf_render"), True,
+                      lambda *a: (load_feather(*a), "pth"), feather_model)
+    return {"siren": Family(_siren_kernel, True, load_weights, registry_model),
+            "fourier": Family(_fourier_kernel, False, load_weights, registry_model),
+            "wavelet_siren": Family(_wavelet_kernel, True, load_weights, registry_model, windowed=True),
+            }.get(name, Family(lambda *a: (False, f"mlp={name} has no render kernel"), False, load_weights, registry_model))
 
 
 def kernel_available(shape: Cfg, height: Optional[int] = None, width: Optional[int] = None) -> Tuple[bool, str]:
-    """(is there a render kernel for this model and picture, why): what decode.render=kernel asks.  SIREN and WaveletSiren:
-    render_path's answer; FourierNet: the shapes sf_fourier_render_create takes.  No device is touched."""
-    name = shape.mlp.get("name", "siren")
-    if name != "fourier":
-        path, why = render_path(shape, height, width)
-        return path == "kernel", why
-    m = shape.mlp
-    w, wp = engine_width(shape), padded_width(shape)
-    n_linear, ms = int(m.get("depth", 8)) - 1, int(m.get("map_size", 128))
-    if wp not in KERNEL_WIDTHS:
-        return False, f"FourierNet width {w} is above 256: no render kernel"
-    if ms not in FOURIER_MAPS or not 2 <= n_linear <= 12 or int(m.get("input_size", 2)) != 2 or int(m.get("output_size", 3)) != 3:
-        return False, (f"FourierNet with map_size {ms}, {n_linear} Linear layers, input_size {m.get('input_size', 2)}, "
-                       f"output_size {m.get('output_size', 3)}: the engine takes map_size 64 / 128 / 256 / 512, 2..12 layers, 2 -> 3")
-    pad = "" if wp == w else f" (width {w} zero-padded)"
-    return True, f"FourierNet {wp}x{n_linear} map {ms}{pad}: sf_render"
+    """(is there a render kernel for this model and picture, why): what decode.render=kernel asks.  height / width: the
+    picture to draw (default: the fitted size), which matters to WaveletSiren only.  No device is touched."""
+    img = shape.get("img") or {}
+    return family(shape).available(shape, int(height or img.get("height") or 0), int(width or img.get("width") or 0))
+
+
+def render_path(shape: Cfg, height: Optional[int] = None, width: Optional[int] = None) -> Tuple[str, str]:
+    """('kernel' | 'torch', why) of decode.render=auto: the kernel when there is one, unless the family's default has not moved"""
+    if not family(shape).auto_kernel:
+        return "torch", f"mlp={shape.mlp.get('name', 'siren')} has no render kernel"
+    ok, why = kernel_available(shape, height, width)
+    return ("kernel" if ok else "torch"), why
 
 
 def render_mode(dec: Dict[str, str]) -> str:
@@ -399,17 +398,16 @@ def choose_path(shape: Cfg, mode: str, height: int, width: int) -> Tuple[str, st
     """('kernel' | 'torch', why) for a decode.render mode; kernel without a render kernel raises ValueError"""
     if mode == "torch":
         return "torch", "decode.render=torch"
-    if mode == "kernel":
-        ok, why = kernel_available(shape, height, width)
-        if not ok:
-            raise ValueError(f"decode.render=kernel: {why}")
-        return "kernel", why
-    return render_path(shape, height, width)
+    if mode == "auto":
+        return render_path(shape, height, width)
+    ok, why = kernel_available(shape, height, width)
+    if not ok:
+        raise ValueError(f"decode.render=kernel: {why}")
+    return "kernel", why
 
 
 def registry_model(sd, shape: Cfg):
     """the registry model of `shape` with `sd` loaded, on the CPU (names, shapes and the padding rule; no engine yet)"""
-    from .models import registry
     m = dict(shape.mlp)
     with torch.random.fork_rng(devices=[]):       # the constructor draws an initialisation nobody needs
         model = registry[m.get("name", "siren")](**m, small_dense_density=shape.get("small_dense_density") or 1.0,
@@ -419,36 +417,47 @@ def registry_model(sd, shape: Cfg):
 
 
 def engine_flat_params(sd, shape: Cfg, num_params: int) -> torch.Tensor:
-    """The flat parameter vector of an engine handle with num_params slots: the model's tensors in flat order, scattered
-    by the model's own engine_flat (zeros in the padding) when the engine runs a wider network - what the model's
-    _sync_to_engine hands a training handle."""
-    model = registry_model(sd, shape)
-    logical = torch.cat([p.data.reshape(-1).float() for p in model._param_list()])
-    if not model._padded:
-        if logical.numel() != num_params:
-            raise ValueError(f"the state dict holds {logical.numel()} parameters, the engine handle {num_params}")
-        return logical.contiguous()
-    return model.engine_flat(logical, num_params, torch.device("cpu"))
+    """what the model of `shape` hands a handle with num_params slots (zeros in the padding of a wider engine), on the CPU"""
+    return registry_model(sd, shape)._flat_for(num_params, torch.device("cpu"))
 
 
 def flat_params(sd: Dict[str, torch.Tensor], depth: int) -> torch.Tensor:
-    parts = []
-    for l in range(depth):
-        parts += [sd[f"layers.{l}.linear.weight"].reshape(-1), sd[f"layers.{l}.linear.bias"].reshape(-1)]
-    return torch.cat(parts).float().contiguous()
+    """a SIREN state dict in the engine's flat order, by its key names alone"""
+    keys = [f"layers.{l}.linear.{kind}" for l in range(depth) for kind in ("weight", "bias")]
+    return torch.cat([sd[k].reshape(-1) for k in keys]).float().contiguous()
 
 
-def _render_bands(eng, load, bands: List[Tuple[int, int]], row0: int, cols: int, draw, want_pred: bool, bits: int = 8):
-    """The open / load / assemble / close skeleton of the three kernel renderers, on a handle the caller opened: load(eng)
-    puts the parameters (and what else the handle needs) in, draw(a, b) returns (u8, pred) of pixel rows [a, b) on the
-    device; every band is copied to the CPU as it comes and the handle is closed whatever happens.  uint8 (bits = 16: int32
-    values 0..65535, widened from the kernel's uint16) [rows from row0 to the last band's end, cols, C] (and the fp32
-    prediction when asked)."""
+# ---- the kernel path --------------------------------------------------------------------------------------
+def _render(sd, shape: Cfg, rows, cols, band_rows: Optional[int], want_pred: bool, device: int, bits: int,
+            side: Optional[int] = None):
+    """The whole kernel job of the four renderers: build the CPU model, plan the bands, open ONE render handle through the
+    model (sized for the first band), let the model fill it, draw band by band, copy each band to the CPU as it comes, and
+    close the handle whatever happens.  rows / cols: the coordinate vectors of the grid; with `side` (a windowed family)
+    the pixel spans (a, b) of its side x side picture.  uint8 (bits = 16: int32 values 0..65535, widened from the kernel's
+    uint16) [rows, cols, C] on the CPU (and the fp32 prediction when asked)."""
+    model = family(shape).model(sd, shape)
+    n_cols = cols.numel() if side is None else cols[1] - cols[0]
+    bands = (plan_bands(rows.numel(), n_cols, model.cfg["output_size"], band_rows, sample_bytes=bits // 8) if side is None
+             else plan_wavelet_bands(side, rows, cols, band_rows, sample_bytes=bits // 8))
+    row0, nb = bands[0][0], bands[0][1] - bands[0][0]
+    eng = model._new_render_engine(nb, n_cols, device, side)
+    cols_d = cols.float().contiguous().to(eng.device) if side is None else None
+
+    def draw(a, b):
+        if side is not None:                       # a window of the picture, over the coefficients its rows need
+            return eng.render(a, b, cols[0], cols[1], want_u8=True, want_pred=want_pred, bits=bits)
+        rb = rows[a:b].float()                     # a slice of `rows`; a shorter (last) band is padded with its final row
+        if b - a < nb:
+            rb = torch.cat([rb, rb[-1:].expand(nb - (b - a))])
+        eng.set_coords(rb.contiguous().to(eng.device), cols_d)
+        u8, p = eng.render(want_u8=True, want_pred=want_pred, bits=bits)
+        return u8[:b - a], (p[:b - a] if want_pred else None)      # and cut after the render
+
     try:
-        load(eng)
-        shape = (bands[-1][1] - row0, cols, eng.out_features)
-        out = torch.empty(shape, dtype=torch.int32 if bits == 16 else torch.uint8)
-        pred = torch.empty(shape) if want_pred else None
+        model._load_render_engine(eng)
+        size = (bands[-1][1] - row0, n_cols, eng.out_features)
+        out = torch.empty(size, dtype=torch.int32 if bits == 16 else torch.uint8)
+        pred = torch.empty(size) if want_pred else None
         for a, b in bands:
             u8, p = draw(a, b)
             out[a - row0:b - row0] = u8.cpu().to(out.dtype)
@@ -459,64 +468,15 @@ def _render_bands(eng, load, bands: List[Tuple[int, int]], row0: int, cols: int,
     return out, pred
 
 
-def _render_grid(eng, load, rows: torch.Tensor, cols: torch.Tensor, bands: List[Tuple[int, int]], want_pred: bool,
-                 bits: int = 8):
-    """Row bands of the grid rows x cols on an open sf_render handle (RenderEngine / FourierRenderEngine) made for the first
-    band's height: a band is a slice of `rows`, the last, shorter one padded with its final row and cut after the render."""
-    nb = bands[0][1] - bands[0][0]
-    cols_d = cols.float().contiguous().to(eng.device)
-
-    def draw(r0, r1):
-        rb = rows[r0:r1].float()
-        if r1 - r0 < nb:
-            rb = torch.cat([rb, rb[-1:].expand(nb - (r1 - r0))])
-        eng.set_coords(rb.contiguous().to(eng.device), cols_d)
-        u8, p = eng.render(want_u8=True, want_pred=want_pred, bits=bits)
-        return u8[:r1 - r0], (p[:r1 - r0] if want_pred else None)
-
-    return _render_bands(eng, load, bands, 0, cols.numel(), draw, want_pred, bits)
-
-
 def render_kernel(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
                   want_pred: bool = False, device: int = 0, bits: int = 8):
     """uint8 [h, w, C] on the CPU (and the fp32 prediction when asked) of the grid rows x cols, band by band on ONE render
-    handle: a band is a slice of `rows` (the last, shorter one is padded with its final row and cut after the render).
-    bits=16: int32 values 0..65535 from sf_render16."""
-    from ._engine import RenderEngine
-    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
-    C = int(m.get("output_size", 3))
-    bands = plan_bands(rows.numel(), cols.numel(), C, band_rows, sample_bytes=bits // 8)
-    eng = RenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.depth),
-                       float(m.get("first_omega_0", 50.0)), float(m.get("hidden_omega_0", 30.0)),
-                       bool(m.get("outermost_linear", True)), C, eng_kw.get("compute_dtype", "f16"), device=device,
-                       chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
-
-    def load(eng):
-        flat = (flat_params(sd, int(m.depth)) if padded_width(shape) == engine_width(shape)
-                else engine_flat_params(sd, shape, eng.num_params))
-        eng.set_params(flat.to(eng.device))
-
-    return _render_grid(eng, load, rows, cols, bands, want_pred, bits)
+    handle of the family of `shape` (plan_bands is stricter than the height * width < 2^31 a handle needs); bits: _render"""
+    return _render(sd, shape, rows, cols, band_rows, want_pred, device, bits)
 
 
-def render_fourier(sd, shape: Cfg, rows: torch.Tensor, cols: torch.Tensor, band_rows: Optional[int] = None,
-                   want_pred: bool = False, device: int = 0, bits: int = 8):
-    """render_kernel for mlp=fourier: uint8 [h, w, 3] on the CPU (and the fp32 prediction when asked) of the grid rows x cols,
-    band by band on ONE FourierNet render handle.  Bands come from plan_bands, whose limits are stricter than the
-    height * width < 2^31 the handle needs; the last, shorter band is padded with its final row and cut after the render.
-    bits=16: int32 values 0..65535 from sf_render16."""
-    from ._engine import FourierRenderEngine
-    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
-    bands = plan_bands(rows.numel(), cols.numel(), 3, band_rows, sample_bytes=bits // 8)
-    eng = FourierRenderEngine(bands[0][1] - bands[0][0], cols.numel(), padded_width(shape), int(m.get("depth", 8)) - 1,
-                              int(m.get("map_size", 128)), 3, device=device,
-                              chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
-
-    def load(eng):
-        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(eng.device))
-        eng.set_encoding(sd["encoding.B"].float().contiguous().to(eng.device))
-
-    return _render_grid(eng, load, rows, cols, bands, want_pred, bits)
+# (a Feathermap run, sd as load_feather returns it, and mlp=fourier under their own names: `shape` tells, not the caller)
+render_feather = render_fourier = render_kernel
 
 
 # ---- WaveletSiren: which coefficients a window needs, bands, the kernel path -----------------------------------
@@ -566,35 +526,17 @@ def plan_wavelet_bands(H: int, r: Tuple[int, int], c: Tuple[int, int], band_rows
 
 def render_wavelet(sd, shape: Cfg, H: int, r: Tuple[int, int], c: Tuple[int, int], band_rows: Optional[int] = None,
                    want_pred: bool = False, device: int = 0, bits: int = 8):
-    """uint8 [rows, cols, 3] on the CPU (and the fp32 prediction when asked) of the window r x c of the H x H picture of a
-    WaveletSiren, band by band on ONE render handle (max_rows = the band height, max_cols = the window's): every band runs
-    the two sub-networks over the coefficient window it needs and nothing else.  bits=16: int32 values 0..65535 from
-    sf_wavelet_render16."""
-    from ._engine import WaveletRenderEngine
-    m, eng_kw = shape.mlp, dict(shape.get("engine") or {})
-    bands = plan_wavelet_bands(H, r, c, band_rows, sample_bytes=bits // 8)
-    eng = WaveletRenderEngine(H, padded_width(shape), int(m.depth), float(m.get("first_omega_0", 50.0)),
-                              float(m.get("hidden_omega_0", 50.0)), bool(m.get("outermost_linear", True)),
-                              eng_kw.get("compute_dtype", "f16"), max_rows=bands[0][1] - bands[0][0], max_cols=c[1] - c[0],
-                              device=device, chunk_pixels=int(eng_kw.get("chunk_pixels", 0) or 0))
-
-    def load(eng):
-        eng.set_params(engine_flat_params(sd, shape, eng.num_params).to(eng.device))
-        lin = torch.linspace(0, 1, eng.n).to(eng.device)      # LF_grid = HF_grid = get_grid(n, n) (wavelet_siren.py:76-80)
-        eng.set_coords(lin, lin)
-
-    return _render_bands(eng, load, bands, r[0], c[1] - c[0],
-                         lambda a, b: eng.render(a, b, c[0], c[1], want_u8=True, want_pred=want_pred, bits=bits), want_pred,
-                         bits)
+    """render_kernel for the window r x c of the H x H picture of a WaveletSiren, on ONE render handle (max_rows = the band
+    height, max_cols = the window's): every band runs the two sub-networks over the coefficient window it needs, no more"""
+    return _render(sd, shape, r, c, band_rows, want_pred, device, bits, side=H)
 
 
 def render_torch(sd, shape: Cfg, height: int, width: int, r: Tuple[int, int], c: Tuple[int, int], device: int = 0,
                  bits: int = 8):
-    """the registry model's own forward on the full height x width grid, cut to the window, bytes by to_u8 (bits=16: int32
-    values 0..65535 by to_u16)"""
-    from .data import get_grid
+    """the family's CPU model, moved to the device: its own forward on the full height x width grid, cut to the window,
+    bytes by to_u8 (bits=16: int32 values 0..65535 by to_u16)"""
     dev = torch.device("cuda", device)
-    model = (feather_model if is_feather(shape) else registry_model)(sd, shape).to(dev).eval()
+    model = family(shape).model(sd, shape).to(dev).eval()
     with torch.no_grad():
         pred = model(get_grid(height, width).to(dev))
     pred = pred[r[0]:r[1], c[0]:c[1]].contiguous()
@@ -632,31 +574,22 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
     shape = resolve_shape(run_dir, rest)
     H = int(dec.get("height") or shape.img.get("height") or 0)
     W = int(dec.get("width") or shape.img.get("width") or 0)
+    fam = family(shape)
     if mode == "kernel":                           # no render kernel: refused before a file is read or the device touched
         choose_path(shape, mode, H, W)
-    if is_feather(shape):                          # model.pth holds the feather vector, not the network
-        sd, source = load_feather(run_dir, shape, dec.get("source")), "pth"
-    else:
-        sd, source = load_weights(run_dir, shape, dec.get("source"))
+    sd, source = fam.load(run_dir, shape, dec.get("source"))
     if H < 1 or W < 1:
         raise ValueError("output size unknown: pass decode.height=... decode.width=... (or img.height / img.width)")
     r, c = _span(dec.get("rows"), H, "rows"), _span(dec.get("cols"), W, "cols")
-    device = int(dec.get("device") or 0)
-    truth = dec.get("truth")
-    name = shape.mlp.get("name", "siren")
-    if name == "wavelet_siren":
-        from .models.wavelet_siren import check_image
+    device, truth = int(dec.get("device") or 0), dec.get("truth")
+    if fam.windowed:
         check_image(H, W)                          # the "even, square" refusal, before anything touches the device
     path, why = choose_path(shape, mode, H, W)
     logging.info(f"decode: weights from {source}; {path} path ({why}); {r[1] - r[0]}x{c[1] - c[0]} of a {H}x{W} grid")
     if path == "kernel":
         band_rows = int(dec["band_rows"]) if dec.get("band_rows") else None
-        if name == "wavelet_siren":
-            u8, pred = render_wavelet(sd, shape, H, r, c, band_rows, want_pred=bool(truth), device=device, bits=bits)
-        else:
-            rows, cols = torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]]
-            u8, pred = (render_feather if is_feather(shape) else render_fourier if name == "fourier" else render_kernel)(
-                sd, shape, rows, cols, band_rows, want_pred=bool(truth), device=device, bits=bits)
+        rows, cols = (r, c) if fam.windowed else (torch.linspace(0, 1, H)[r[0]:r[1]], torch.linspace(0, 1, W)[c[0]:c[1]])
+        u8, pred = _render(sd, shape, rows, cols, band_rows, bool(truth), device, bits, side=H if fam.windowed else None)
     else:
         u8, pred = render_torch(sd, shape, H, W, r, c, device=device, bits=bits)
     if u8.shape[-1] != 3:

@@ -6,10 +6,12 @@ handle's flat fp32 state, so optimiser / masking / quantisation code that pokes 
 `named_parameters()` sees live engine state.  A logical width the kernels are not instantiated for runs zero-padded to the
 next one: its Parameters stay ordinary tensors, scattered into the handle before every pass and gathered back after a step.
 
-A subclass supplies `cfg`, `_param_list()`, `_layer_fans()`, `_engine_width`, `_padded` and `_new_engine(H, w, row_begin,
-row_end, device)`; what else differs goes into the small hooks below.  Consumers (EngineAdam, train_epoch, Masking,
-KmeansQuant, decode) use `bound_engine`, `register_optimizer`, `mask_unsupported`, the two callback lists, `_padded` and
-`engine_flat`.
+A subclass supplies `cfg`, `_param_list()`, `_layer_fans()`, `_engine_width`, `_padded`, `_new_engine(H, w, row_begin,
+row_end, device)` and, for `make decode`, `_new_render_engine(rows, cols, device, side)`: the inference-only handle from the
+same `cfg`, a render call of which draws up to rows x cols samples (side: the whole picture's, for WaveletSiren), and which
+`_load_render_engine(eng)` fills.  What else differs goes into the small hooks below.  Consumers (EngineAdam, train_epoch,
+Masking, KmeansQuant, decode) use `bound_engine`, `register_optimizer`, `mask_unsupported`, the two callback lists,
+`_padded`, `engine_flat` and the two render hooks.
 """
 import weakref
 from typing import Optional
@@ -150,12 +152,24 @@ class EngineBound(nn.Module):
                 p.grad = g
             off += n
 
+    def _load_render_engine(self, eng):
+        """put this model's state into the handle its _new_render_engine made (a family with more than flat parameters adds it)"""
+        eng.set_params(self._flat_for(eng.num_params, eng.device))
+
+    def _flat_for(self, num_params: int, device) -> torch.Tensor:
+        """`_param_list()` as the flat vector of a handle with num_params slots on `device`, zero-padded by engine_flat"""
+        logical = torch.cat([p.data.reshape(-1).float() for p in self._param_list()])
+        if self._padded:
+            return self.engine_flat(logical, num_params, device)
+        if logical.numel() != num_params:
+            raise ValueError(f"the state dict holds {logical.numel()} parameters, the engine handle {num_params}")
+        return logical.contiguous().to(device)
+
     def _sync_to_engine(self):
         """Hand the handle the current parameters.  Padded widths: they are scattered into the engine every pass."""
         eng = self._engine
         if self._padded:
-            logical = torch.cat([p.data.reshape(-1).float() for p in self._param_list()])
-            eng.set_params(self.engine_flat(logical, eng.num_params, eng.device))
+            eng.set_params(self._flat_for(eng.num_params, eng.device))
             return
         self._bind_params(eng)
         eng.params_changed()   # in-place edits through the views are invisible to the engine: always refresh

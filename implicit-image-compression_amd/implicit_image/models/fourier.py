@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from .binding import EngineBound
-from .siren import next_kernel_width
+from .siren import KERNEL_WIDTHS, next_kernel_width
 
 # the reference's Masking puts the frozen encoding.B into its mask_dict and its first update_connections() fails on
 # B.grad being None (reference pipeline/masking/funcs/grow.py:87): there is no reference behaviour to reproduce
@@ -18,6 +18,12 @@ MASKING_UNSUPPORTED = ("mask-based sparsity (RigL / SNFS / SET / Pruning) is not
                        "Masking registers the frozen encoding.B and its first update_connections() fails with "
                        "AttributeError ('NoneType' object has no attribute 'dtype', pipeline/masking/funcs/grow.py:87). "
                        "Use masking=none or masking=Small_Dense")
+MAP_SIZES = (64, 128, 256, 512)    # the encoding sizes k_ff_fwd is instantiated for
+
+
+def engine_takes(input_size: int, output_size: int, map_size: int, n_linear: int) -> bool:
+    """what the engine accepts besides the width: the constructor and decode's availability rule both ask here"""
+    return input_size == 2 and output_size == 3 and map_size in MAP_SIZES and 2 <= n_linear <= 12
 
 
 class Encoding(nn.Module):
@@ -35,7 +41,7 @@ class Encoding(nn.Module):
 class FourierNet(EngineBound):
     # engine widths: Small_Dense's int(hidden * sqrt(density)) runs zero-padded to the next one (padded neurons have zero
     # weights and bias, output relu(0) = 0 and receive exactly zero gradients)
-    WIDTHS = (32, 64, 128, 256)
+    WIDTHS = KERNEL_WIDTHS
     mask_unsupported = MASKING_UNSUPPORTED
     _WHO = "Siren"                 # (the wording a CPU grid has always been refused with)
 
@@ -61,7 +67,7 @@ class FourierNet(EngineBound):
         self._engine_width = next_kernel_width(hidden_size, self.WIDTHS)
         if self._engine_width is None:
             raise NotImplementedError(f"hidden_size {hidden_size} > 256 is not supported for FourierNet by the gfx950 engine")
-        if input_size != 2 or output_size != 3 or map_size not in (64, 128, 256, 512) or not 2 <= n_linear <= 12:
+        if not engine_takes(input_size, output_size, map_size, n_linear):
             raise NotImplementedError("FourierNet on the gfx950 engine: input_size 2, output_size 3, map_size 64 / 128 / "
                                       f"256 / 512 and 2..12 Linear layers (got {input_size}, {output_size}, {map_size}, {n_linear})")
         self._padded = self._engine_width != hidden_size
@@ -78,12 +84,23 @@ class FourierNet(EngineBound):
                 out += [m.weight, m.bias]
         return out
 
+    def _handle(self, cls, H: int, w: int, device: int, **more):
+        c = self.cfg
+        return cls(H, w, self._engine_width, c["n_linear"], c["map_size"], c["output_size"], device=device,
+                   chunk_pixels=c["chunk_pixels"], **more)
+
     def _new_engine(self, H: int, w: int, row_begin: int, row_end: int, device: int):
         from .._engine import FourierEngine
-        c = self.cfg
         self._enc_key = None
-        return FourierEngine(H, w, self._engine_width, c["n_linear"], c["map_size"], c["output_size"], device=device,
-                             chunk_pixels=c["chunk_pixels"], betas=self._adam[0], eps=self._adam[1])
+        return self._handle(FourierEngine, H, w, device, betas=self._adam[0], eps=self._adam[1])
+
+    def _new_render_engine(self, rows: int, cols: int, device: int, side=None):
+        from .._engine import FourierRenderEngine
+        return self._handle(FourierRenderEngine, rows, cols, device)
+
+    def _load_render_engine(self, eng):
+        super()._load_render_engine(eng)
+        eng.set_encoding(self.encoding.B.data.float().contiguous().to(eng.device))
 
     def engine(self, grid: torch.Tensor, img=None, row_begin: int = 0, row_end: int = 0, full_height=None):
         if row_begin or (row_end and row_end != grid.shape[0]) or (full_height and full_height != grid.shape[0]):

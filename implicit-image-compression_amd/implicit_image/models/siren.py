@@ -13,12 +13,20 @@ from torch import nn
 
 from .binding import EngineBound
 
+KERNEL_WIDTHS = (32, 64, 128, 256)     # fused chain kernels: the widths with a render kernel; all FourierNet / WaveletSiren run
+
 
 def next_kernel_width(hidden: int, widths) -> Optional[int]:
     """The width the engine runs a network of logical width `hidden` at: the narrowest of `widths` (ascending: the widths
     the kernels are instantiated for) that holds it, None above the last.  The one statement of the zero-padding rule:
     Siren, FourierNet and decode.padded_width call it, each with its own widths."""
     return next((w for w in widths if w >= hidden), None)
+
+
+def layer_sizes(input_size: int, hidden: int, depth: int, output_size: int):
+    """(logical_out, logical_in) of every Linear of a SIREN, for Siren, FeatherNet and decode (from a shape, before a model)"""
+    fans = [input_size] + [hidden] * (depth - 1) + [output_size]
+    return fans[1:], fans[:-1]
 
 
 class SineLayer(nn.Module):
@@ -51,7 +59,7 @@ class Siren(EngineBound):
     # revolutions (siren_kernels.hip), a padded neuron outputs sin(2 pi / 65536), the weights it feeds get a small gradient
     # and Adam moves those slots of the ENGINE's vector.  Nothing accumulates: the logical parameters are scattered into a
     # zeroed vector before every pass (EngineBound._sync_to_engine) and only logical slots are gathered back
-    WIDTHS = (32, 64, 128, 256, 512, 1024)
+    WIDTHS = KERNEL_WIDTHS + (512, 1024)
 
     def __init__(self, input_size: int = 2, output_size: int = 3, depth: int = 8, hidden_size: int = 128,
                  first_omega_0: float = 50.0, hidden_omega_0: float = 50.0, outermost_linear: bool = True,
@@ -86,16 +94,23 @@ class Siren(EngineBound):
             out += [layer.linear.weight, layer.linear.bias]
         return out
 
+    def _handle(self, cls, H: int, w: int, device: int, **more):
+        """a handle of class `cls` for H x w pixels: the one mapping from `cfg`, whatever the handle is for"""
+        c = self.cfg
+        return cls(H, w, hidden=self._engine_width, depth=c["depth"], first_omega_0=c["first_omega_0"],
+                   hidden_omega_0=c["hidden_omega_0"], outermost_linear=c["outermost_linear"], out_features=c["output_size"],
+                   compute_dtype=c["compute_dtype"], device=device, chunk_pixels=c["chunk_pixels"], **more)
+
     def _new_engine(self, H: int, w: int, row_begin: int, row_end: int, device: int):
         from .._engine import SirenEngine
-        c = self.cfg
-        return SirenEngine(H, w, self._engine_width, c["depth"], c["first_omega_0"], c["hidden_omega_0"],
-                           c["outermost_linear"], c["output_size"], c["compute_dtype"],
-                           device=device, row_begin=row_begin, row_end=row_end,
-                           chunk_pixels=c["chunk_pixels"], betas=self._adam[0], eps=self._adam[1],
-                           scratch_format=c["scratch_format"])
+        return self._handle(SirenEngine, H, w, device, row_begin=row_begin, row_end=row_end, betas=self._adam[0],
+                            eps=self._adam[1], scratch_format=self.cfg["scratch_format"])
+
+    def _new_render_engine(self, rows: int, cols: int, device: int, side=None):
+        from .._engine import RenderEngine
+        return self._handle(RenderEngine, rows, cols, device)
 
     def _layer_fans(self):
         c = self.cfg
-        fans = [c["input_size"]] + [c["hidden_size"]] * (c["depth"] - 1) + [c["output_size"]]
-        return [(fans[l], fans[l + 1], l > 0, l < c["depth"] - 1) for l in range(c["depth"])]
+        outs, ins = layer_sizes(c["input_size"], c["hidden_size"], c["depth"], c["output_size"])
+        return [(ins[l], outs[l], l > 0, l < c["depth"] - 1) for l in range(c["depth"])]

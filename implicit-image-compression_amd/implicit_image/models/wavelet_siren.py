@@ -97,6 +97,18 @@ class WaveletSiren(EngineBound):
                              c["hidden_omega_0"], c["outermost_linear"], device=device, chunk_pixels=c["chunk_pixels"],
                              betas=self._adam[0], eps=self._adam[1], wavelet_levels=c["wavelet_levels"])
 
+    def _new_render_engine(self, rows: int, cols: int, device: int, side: Optional[int] = None):
+        from .._engine import WaveletRenderEngine
+        c = self.cfg
+        return WaveletRenderEngine(side, self._engine_width, c["depth"], c["first_omega_0"], c["hidden_omega_0"],
+                                   c["outermost_linear"], c["compute_dtype"], max_rows=rows, max_cols=cols, device=device,
+                                   chunk_pixels=c["chunk_pixels"])
+
+    def _load_render_engine(self, eng):
+        super()._load_render_engine(eng)
+        lin = torch.linspace(0, 1, eng.n).to(eng.device)      # LF_grid = HF_grid = get_grid(n, n) (wavelet_siren.py:76-80)
+        eng.set_coords(lin, lin)
+
     def shape_probe(self, h: int, w: int):
         """The reference's first forward: a DWT of torch.rand(1, 1, h, w) from the CPU generator fixes the coefficient
         size (wavelet_siren.py:70-74); the draw is repeated so that the generator state matches."""

@@ -18,7 +18,7 @@ from torch import Tensor
 from torch.nn import Parameter
 
 from ...models.binding import EngineBound
-from ...models.siren import Siren
+from ...models.siren import Siren, layer_sizes
 
 DEPLOY_UNSUPPORTED = ("FeatherNet.deploy() (the reference's forward-hook weight caching) is not built: its bias index "
                       "ranges differ from the training layout (feathernet.py:58-66, LoadLayer.__get_index_range)")
@@ -142,9 +142,8 @@ class FeatherNet(EngineBound):
         return [p for _, p in self.named_parameters()]
 
     def _logical_sizes(self):
-        outs = [layer.linear.out_features for layer in self.module.layers]
-        ins = [layer.linear.in_features for layer in self.module.layers]
-        return outs, ins
+        c = self.cfg
+        return layer_sizes(c["input_size"], c["hidden_size"], c["depth"], c["output_size"])
 
     def engine(self, grid: torch.Tensor, img: torch.Tensor = None):
         """The Siren's engine with the feather state attached, bound to this model (made on first use, re-made when the
@@ -165,6 +164,16 @@ class FeatherNet(EngineBound):
             base.close()
             raise
         return FeatherEngine(base)
+
+    def _new_render_engine(self, rows: int, cols: int, device: int, side=None):
+        from ..._engine import FeatherRenderEngine
+        outs, ins = self._logical_sizes()
+        return self.module._handle(FeatherRenderEngine, rows, cols, device, n=self._size_n, m=self._size_m, logical_out=outs,
+                                   logical_in=ins)
+
+    def _load_render_engine(self, eng):
+        """the feather vector [V1 | V2 | scalers] in named_parameters() order; the handle materialises W from it"""
+        eng.load_feather(torch.cat([p.data.reshape(-1) for p in self._param_list()]).float().contiguous().to(eng.device))
 
     def _carry_out(self, old):
         return (old.view("exp_avg").clone(), old.view("exp_avg_sq").clone(), old.adam_steps, (old.height, old.width))
