@@ -218,9 +218,8 @@ struct sf_engine {
     float* gl = nullptr;          // two-pass only: [2][n*n][3] fp32 dL/dout of the sub-networks
     float* dfac = nullptr;        // outermost_linear=False only: [2][n*n][3] d sin(om z)/dz of the sub-networks' outputs
     int max_rows = 0, max_cols = 0;   // render handle: the largest pixel window one call draws
-    // on a sub-handle (a Model::Siren handle):
-    bool ext_dout = false;        // the training forward runs without a target, dL/dout comes from k_wv_adjoint
-    float* dfac_out = nullptr;    // sine output layer: its slice of dfac (FwdArgs::dfac of training forwards)
+    // on a sub-handle (a Model::Siren handle), sine output layer: its slice of dfac (FwdArgs::dfac of training forwards)
+    float* dfac_out = nullptr;
   } wv;
 };
 
@@ -334,16 +333,20 @@ Chunk chunk_at(long c, long npix, long chunk_px) {
   k.n_pb = (long)k.n_super * kWavesFwd;
   return k;
 }
+// The pixels a handle's kernels walk: the two coordinate vectors, the row length, the pixel count.  Its own grid, or
+// (sf_wavelet_render on a sub-handle) the coefficient window of one call
+struct PixelView { const float *gh, *gw; int W; long npix; };
+PixelView own_view(const sf_engine* h) { return {h->gh, h->gw, h->cfg.width, h->npix}; }
 // pixel geometry of the chunk at local pixel pix0, for any argument struct that decodes (row, col) from a pixel index
 template <typename Args>
-void fill_pixels(const sf_engine* h, long pix0, Args& a) {
-  a.pix0 = pix0; a.npix = h->npix; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin;
-  a.w_magic = ((1ULL << 40) + (unsigned long long)h->cfg.width - 1) / (unsigned long long)h->cfg.width;
+void fill_pixels(const sf_engine* h, const PixelView& v, long pix0, Args& a) {
+  a.pix0 = pix0; a.npix = v.npix; a.W = v.W; a.row_begin = h->cfg.row_begin;
+  a.w_magic = ((1ULL << 40) + (unsigned long long)v.W - 1) / (unsigned long long)v.W;
 }
 // ... and for the backward structs, which also re-derive the coordinates from (row, col)
 template <typename Args>
 void fill_grid(const sf_engine* h, long pix0, Args& a) {
-  fill_pixels(h, pix0, a);
+  fill_pixels(h, own_view(h), pix0, a);
   a.inv_hm1 = h->cfg.height > 1 ? 1.0f / (float)(h->cfg.height - 1) : 0.f;
   a.inv_wm1 = h->cfg.width > 1 ? 1.0f / (float)(h->cfg.width - 1) : 0.f;
 }
@@ -477,11 +480,11 @@ int alloc_sse(sf_engine* h, long n_sse) {
   return dev_alloc(h, h->sse_dev, 8);
 }
 
-// the model dispatch of siren_fit.hip.  phases (WaveletSiren sub-handles only; every other pass runs both): bit 0 the
-// forward of each chunk, bit 1 the backward; chunks [c_begin, c_end) (c_end < 0: to the last)
-enum { kPassFwd = 1, kPassBwd = 2, kPassAll = 3 };
+// the model dispatch of siren_fit.hip: the weight images, the one loop over a handle's chunks (forward; if train, backward;
+// the SSE reduction), and the pass - its checks, the images, then that loop or run_pass_wavelet
 int refresh_images(sf_engine* h);
-int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases = kPassAll, long c_begin = 0, long c_end = -1);
+int run_chunks(sf_engine* h, bool train, float* pred, bool want_sse);
+int run_pass(sf_engine* h, bool train, float* pred, bool want_sse);
 
 // training entry points on a render handle: an argument error, before anything is touched
 int refuse_render(const char* fn) {

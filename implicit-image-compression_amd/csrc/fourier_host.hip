@@ -1,4 +1,4 @@
-// fourier_host.hip — FourierNet on the host (kernels: fourier_kernels.hip): weight images, the pass, the creator of training
+// fourier_host.hip — FourierNet on the host (kernels: fourier_kernels.hip): weight images, a chunk's forward and backward, the creator of training
 // and render handles (fourier_render.hip), sf_fourier_create / sf_set_encoding.  Included by siren_fit.hip.
 
 namespace {
@@ -46,77 +46,86 @@ int launch_ff(sf_engine* h, const FfArgs& a, int n_super, FfKernel which) {
   });
 }
 
-int run_pass_fourier(sf_engine* h, bool train, float* pred, bool want_sse) {
-  if (!h->ff.have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
-  SF_TRY(refresh_images(h));
+// ... and for the forward and the backward of a training handle's chunk: the planes, the target, the outputs
+FfArgs ff_chunk_args(const sf_engine* h, const Chunk& k, float* pred, float* sse_part) {
+  FfArgs fa = ff_args_base(h, k.pix0);
+  fa.H = h->ff.H; fa.G = h->ff.G; fa.Z = h->ff.Z;
+  fa.tgt = h->img; fa.pred = pred; fa.sse_part = sse_part;
+  fa.gscale = gscale(h);
+  return fa;
+}
+
+// The forward of chunk c (k_ff_fwd), training or evaluation form: the prediction to pred (or null), the chunk's SSE partials
+// to sse_part; n_part: how many it wrote (one per 256-pixel group)
+int fourier_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
   const int WD = h->WD, D = h->D, MS = h->ff.MS;
-  long sse_off = 0;
-  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
-    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
-    const int n_super = k.n_super;
-    const double npx = (double)n_super * kSuper;
-    FfArgs fa = ff_args_base(h, k.pix0);
-    fa.H = h->ff.H; fa.G = h->ff.G; fa.Z = h->ff.Z;
-    fa.tgt = h->img; fa.pred = pred; fa.sse_part = h->sse_part + sse_off;
-    fa.gscale = gscale(h);
-    sse_off += n_super;
-    const double f_hidden = (double)(D - 2) * WD * WD;
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  const double npx = (double)k.n_super * kSuper;
+  const FfArgs fa = ff_chunk_args(h, k, pred, sse_part);
+  const double f_hidden = (double)(D - 2) * WD * WD;
+  n_part = k.n_super;
+  Launch L(h, K_FWD, 2.0 * ((double)MS * WD + f_hidden + 32.0 * WD) * npx,
+           npx * (12.0 + (train ? (D - 1) * WD * 2.0 + 6.0 : 0.0)));
+  return launch_ff(h, fa, k.n_super, train ? kFfTrain : kFfEval);
+}
+
+// The backward of chunk c after its training forward (which ran with the same sse_part and no prediction: the kernels receive
+// the forward's argument struct): k_ff_bwd, then k_ff_dw per layer, last first, each followed by the slab reduction
+int fourier_bwd_chunk(sf_engine* h, long c, float* sse_part) {
+  const int WD = h->WD, D = h->D, MS = h->ff.MS;
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  const int n_super = k.n_super;
+  const double npx = (double)n_super * kSuper;
+  const FfArgs fa = ff_chunk_args(h, k, nullptr, sse_part);
+  const double f_hidden = (double)(D - 2) * WD * WD;
+  {
+    Launch L(h, K_BWD_HIDDEN, 2.0 * (f_hidden + 16.0 * WD) * npx, npx * (6.0 + (D - 1) * WD * 4.0));
+    SF_TRY(launch_ff(h, fa, n_super, kFfBwd));
+  }
+  // weight gradients, last layer first: per-workgroup slabs over contiguous pixel ranges, then k_reduce*
+  int gx = (int)(npx / kSuper);
+  if (gx > h->ff.dw_wgs) gx = h->ff.dw_wgs;
+  long ppw = ((long)npx + gx - 1) / gx;
+  ppw = (ppw + 15) / 16 * 16;
+  gx = (int)(((long)npx + ppw - 1) / ppw);
+  for (int l = D - 1; l >= 0; --l) {
+    const bool last = l == D - 1;
+    FfDwArgs da = zeroed<FfDwArgs>();
+    da.rows = last ? h->cfg.out_features : WD;
+    da.A = last ? h->ff.Z : h->ff.G + (size_t)l * WD * h->chunk_px;
+    da.Bm = l == 0 ? nullptr : h->ff.H + (size_t)(l - 1) * WD * h->chunk_px;
+    da.in = l == 0 ? MS : WD;
+    da.n_it = da.in / 32;
+    const int NI = da.n_it < 4 ? da.n_it : 4;
+    da.n_groups = ((da.rows + 31) / 32) * (da.n_it / NI);
+    da.cp = h->chunk_px; da.n_px = (long)npx; da.ppw = ppw; da.slab = h->slab; da.e = fa;
     {
-      Launch L(h, K_FWD, 2.0 * ((double)MS * WD + f_hidden + 32.0 * WD) * npx,
-               npx * (12.0 + (train ? (D - 1) * WD * 2.0 + 6.0 : 0.0)));
-      SF_TRY(launch_ff(h, fa, n_super, train ? kFfTrain : kFfEval));
+      Launch L(h, l == 0 ? K_DW_FIRST : last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * 32.0 * ((da.rows + 31) / 32) * da.in * npx,
+               npx * 2.0 * (32.0 * ((da.rows + 31) / 32) + (l == 0 ? 0.0 : da.in)));
+      const dim3 grid(gx, (da.n_groups + 3) / 4);
+      SF_TRY(with_bool(l == 0, [&](auto e0) {
+        constexpr bool E0 = decltype(e0)::value;
+        return NI == 1 ? launch(h, k_ff_dw<1, E0>, grid, 256, 0, da) : NI == 2 ? launch(h, k_ff_dw<2, E0>, grid, 256, 0, da)
+                                                                               : launch(h, k_ff_dw<4, E0>, grid, 256, 0, da);
+      }));
     }
-    if (!train) continue;
-    {
-      Launch L(h, K_BWD_HIDDEN, 2.0 * (f_hidden + 16.0 * WD) * npx, npx * (6.0 + (D - 1) * WD * 4.0));
-      SF_TRY(launch_ff(h, fa, n_super, kFfBwd));
-    }
-    // weight gradients, last layer first: per-workgroup slabs over contiguous pixel ranges, then k_reduce*
-    int gx = (int)(npx / kSuper);
-    if (gx > h->ff.dw_wgs) gx = h->ff.dw_wgs;
-    long ppw = ((long)npx + gx - 1) / gx;
-    ppw = (ppw + 15) / 16 * 16;
-    gx = (int)(((long)npx + ppw - 1) / ppw);
-    for (int l = D - 1; l >= 0; --l) {
-      const bool last = l == D - 1;
-      FfDwArgs da = zeroed<FfDwArgs>();
-      da.rows = last ? h->cfg.out_features : WD;
-      da.A = last ? h->ff.Z : h->ff.G + (size_t)l * WD * h->chunk_px;
-      da.Bm = l == 0 ? nullptr : h->ff.H + (size_t)(l - 1) * WD * h->chunk_px;
-      da.in = l == 0 ? MS : WD;
-      da.n_it = da.in / 32;
-      const int NI = da.n_it < 4 ? da.n_it : 4;
-      da.n_groups = ((da.rows + 31) / 32) * (da.n_it / NI);
-      da.cp = h->chunk_px; da.n_px = (long)npx; da.ppw = ppw; da.slab = h->slab; da.e = fa;
-      {
-        Launch L(h, l == 0 ? K_DW_FIRST : last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * 32.0 * ((da.rows + 31) / 32) * da.in * npx,
-                 npx * 2.0 * (32.0 * ((da.rows + 31) / 32) + (l == 0 ? 0.0 : da.in)));
-        const dim3 grid(gx, (da.n_groups + 3) / 4);
-        SF_TRY(with_bool(l == 0, [&](auto e0) {
-          constexpr bool E0 = decltype(e0)::value;
-          return NI == 1 ? launch(h, k_ff_dw<1, E0>, grid, 256, 0, da) : NI == 2 ? launch(h, k_ff_dw<2, E0>, grid, 256, 0, da)
-                                                                                 : launch(h, k_ff_dw<4, E0>, grid, 256, 0, da);
-        }));
-      }
-      const long n = (long)da.rows * da.in + da.rows;
-      Launch L(h, K_REDUCE, 0, (double)gx * n * 4.0);
-      if (!last) {   // slab layout [W rows*in | b rows] == flat gradient layout of the layer
-        const int n4 = (int)(n / 4);
-        SF_TRY(launch(h, k_reduce_vec, (n4 + 7) / 8, 256, 0, h->slab, gx, n, n4, h->grads + h->off_w[l], c > 0, 1.0f / h->gpre,
-                      nullptr, nullptr));
-      } else {
-        ReduceArgs ra = zeroed<ReduceArgs>();
-        ra.slab = h->slab; ra.n_wg = gx; ra.slab_rows = da.rows; ra.slab_cols = da.in; ra.rows_out = da.rows; ra.cols_out = da.in;
-        ra.mode = 0; ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l]; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
-        SF_TRY(launch_reduce(h, ra));
-      }
+    const long n = (long)da.rows * da.in + da.rows;
+    Launch L(h, K_REDUCE, 0, (double)gx * n * 4.0);
+    if (!last) {   // slab layout [W rows*in | b rows] == flat gradient layout of the layer
+      const int n4 = (int)(n / 4);
+      SF_TRY(launch(h, k_reduce_vec, (n4 + 7) / 8, 256, 0, h->slab, gx, n, n4, h->grads + h->off_w[l], c > 0, 1.0f / h->gpre,
+                    nullptr, nullptr));
+    } else {
+      ReduceArgs ra = zeroed<ReduceArgs>();
+      ra.slab = h->slab; ra.n_wg = gx; ra.slab_rows = da.rows; ra.slab_cols = da.in; ra.rows_out = da.rows; ra.cols_out = da.in;
+      ra.mode = 0; ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l]; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
+      SF_TRY(launch_reduce(h, ra));
     }
   }
-  if (want_sse || train) SF_TRY(launch_sse_reduce(h, sse_off));
   return SF_OK;
 }
 
-// FourierNet handle: the same sf_engine, run by fourier_kernels.hip (run_pass_fourier); every other entry point is shared.
+// FourierNet handle: the same sf_engine, run by fourier_kernels.hip (the two chunk functions above); every other entry point is shared.
 // sf_fourier_create and sf_fourier_render_create (fourier_render.hip): one validation, one geometry; a render handle
 // allocates the parameters, the weight images (forward and backward: k_ff_images writes both, a few MB at most),
 // encoding.B and the two coordinate vectors

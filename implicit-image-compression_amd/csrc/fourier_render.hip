@@ -23,7 +23,7 @@
 namespace {
 
 // sf_render / sf_render16 on a FourierNet handle (render or training), after their argument checks: chunked as
-// run_pass_fourier.  out: bits / 8 bytes per sample
+// a FourierNet pass.  out: bits / 8 bytes per sample
 int render_fourier(sf_engine* h, void* out, int bits, float* pred) {
   if (!h->ff.have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
   DevGuard dev_guard(h->cfg.device);

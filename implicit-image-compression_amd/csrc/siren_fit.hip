@@ -107,19 +107,46 @@ int refresh_images(sf_engine* h) {
   __builtin_unreachable();
 }
 
-int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, int phases, long c_begin, long c_end) {
+// The chunk loop of every training / evaluation pass of a SIREN or FourierNet handle (its images are current): per chunk the
+// model's forward and, if train, its backward, the chunks' SSE partials one after the other in h->sse_part; then their
+// fixed-order reduction.  (A WaveletSiren handle runs its two SIREN sub-handles instead: run_pass_wavelet.)
+int run_chunks(sf_engine* h, bool train, float* pred, bool want_sse) {
+  long sse_off = 0;
+  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
+    float* const part = h->sse_part + sse_off;
+    int n_part = 0;
+    switch (h->model) {
+      case Model::Siren:
+        SF_TRY(h->wide ? wide_fwd_chunk(h, c, train, pred, part, n_part) : siren_fwd_chunk(h, c, train, pred, part, n_part));
+        if (train) SF_TRY(h->wide ? wide_bwd_chunk(h, c, part, n_part) : siren_bwd_chunk(h, c, part, n_part));
+        break;
+      case Model::Fourier:
+        SF_TRY(fourier_fwd_chunk(h, c, train, pred, part, n_part));
+        if (train) SF_TRY(fourier_bwd_chunk(h, c, part));
+        break;
+      case Model::Wavelet: __builtin_unreachable();   // run_pass
+    }
+    sse_off += n_part;
+  }
+  if (want_sse || train) SF_TRY(launch_sse_reduce(h, sse_off));
+  return SF_OK;
+}
+
+int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
   if (h->render) return fail(SF_ERR_INVALID, "a render handle (sf_render_create) runs sf_render only");
   if (train) h->fth.fresh = false;
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
-  if (((train && !h->wv.ext_dout) || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
-  switch (h->model) {
+  if ((train || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
+  switch (h->model) {   // the model's own checks, before anything is launched
     case Model::Wavelet: return run_pass_wavelet(h, train, pred, want_sse);
-    case Model::Fourier: return run_pass_fourier(h, train, pred, want_sse);
+    case Model::Fourier:
+      if (!h->ff.have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
+      break;
     case Model::Siren:
       if (train && (!h->Pbuf || !h->Dbuf)) return fail(SF_ERR_STATE, "the handle has no backward scratch");   // (never a null store on the GPU)
-      return h->wide ? run_pass_wide(h, train, pred, want_sse) : run_pass_siren(h, train, pred, want_sse, phases, c_begin, c_end);
   }
-  __builtin_unreachable();
+  SF_TRY(refresh_images(h));
+  return run_chunks(h, train, pred, want_sse);
 }
 
 int read_sse(sf_engine* h, double* out) {
@@ -168,33 +195,28 @@ int sf_param_offset(const sf_handle* h, int32_t layer, int64_t* w, int64_t* b) t
   return SF_OK;
 } SF_CATCH
 
-static int copy_in(sf_engine* h, float* dst, const float* src) {
-  if (!h || !src) return fail(SF_ERR_INVALID, "null argument");
-  DevGuard dev_guard(h->cfg.device);
-  HIPCHK(hipMemcpyAsync(dst, src, h->P * 4, hipMemcpyDeviceToDevice, h->ctx->stream));
-  return SF_OK;
-}
-static int copy_out(sf_engine* h, float* dst, const float* src) {
-  if (!h || !dst) return fail(SF_ERR_INVALID, "null argument");
+// one flat fp32 vector of the handle (P values) to or from the caller's device buffer, on the handle's stream
+static int copy_state(sf_engine* h, float* dst, const float* src) {
+  if (!h || !dst || !src) return fail(SF_ERR_INVALID, "null argument");
   DevGuard dev_guard(h->cfg.device);
   HIPCHK(hipMemcpyAsync(dst, src, h->P * 4, hipMemcpyDeviceToDevice, h->ctx->stream));
   return SF_OK;
 }
 int sf_set_params(sf_handle* h, const float* p) try {
   SF_NO_FEATHER_RENDER(h, "sf_set_params");
-  int rc = copy_in(h, h ? h->params : nullptr, p);
+  int rc = copy_state(h, h ? h->params : nullptr, p);
   if (!rc) h->images_dirty = true;
   return rc;
 } SF_CATCH
-int sf_get_params(sf_handle* h, float* p) try { return copy_out(h, p, h ? h->params : nullptr); } SF_CATCH
+int sf_get_params(sf_handle* h, float* p) try { return copy_state(h, p, h ? h->params : nullptr); } SF_CATCH
 int sf_get_grads(sf_handle* h, float* p) try {
   SF_NO_RENDER(h, "sf_get_grads");
-  return copy_out(h, p, h ? h->grads : nullptr);
+  return copy_state(h, p, h ? h->grads : nullptr);
 } SF_CATCH
 int sf_set_grads(sf_handle* h, const float* p) try {
   SF_NO_RENDER(h, "sf_set_grads");
   if (h) h->fth.fresh = false;
-  return copy_in(h, h ? h->grads : nullptr, p);
+  return copy_state(h, h ? h->grads : nullptr, p);
 } SF_CATCH
 int sf_set_masks(sf_handle* h, const float* p) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
@@ -206,7 +228,7 @@ int sf_set_masks(sf_handle* h, const float* p) try {
     const int rs = switch_scratch_format(h, 16);
     if (rs) return rs;
   }
-  int rc = copy_in(h, h->mask, p);
+  int rc = copy_state(h, h->mask, p);
   if (!rc) h->has_mask = true;
   return rc;
 } SF_CATCH
@@ -214,8 +236,8 @@ int sf_get_adam_state(sf_handle* h, float* m, float* v, int64_t* step) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
   SF_NO_RENDER(h, "sf_get_adam_state");
   DevGuard dev_guard(h->cfg.device);
-  if (m) { int rc = copy_out(h, m, h->m); if (rc) return rc; }
-  if (v) { int rc = copy_out(h, v, h->v); if (rc) return rc; }
+  if (m) { int rc = copy_state(h, m, h->m); if (rc) return rc; }
+  if (v) { int rc = copy_state(h, v, h->v); if (rc) return rc; }
   if (step) *step = h->step;
   return SF_OK;
 } SF_CATCH
@@ -223,8 +245,8 @@ int sf_set_adam_state(sf_handle* h, const float* m, const float* v, int64_t step
   if (!h || step < 0) return fail(SF_ERR_INVALID, "bad argument");
   SF_NO_RENDER(h, "sf_set_adam_state");
   DevGuard dev_guard(h->cfg.device);
-  if (m) { int rc = copy_in(h, h->m, m); if (rc) return rc; }
-  if (v) { int rc = copy_in(h, h->v, v); if (rc) return rc; }
+  if (m) { int rc = copy_state(h, h->m, m); if (rc) return rc; }
+  if (v) { int rc = copy_state(h, h->v, v); if (rc) return rc; }
   h->step = step;
   return SF_OK;
 } SF_CATCH
@@ -328,9 +350,7 @@ int sf_forward(sf_handle* h, float* pred, double* sse_out) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
   DevGuard dev_guard(h->cfg.device);
   const bool want = sse_out != nullptr;
-  const float* keep = h->img;
   int rc = run_pass(h, false, pred, want);
-  h->img = keep;
   if (rc) return rc;
   if (want) return read_sse(h, sse_out);
   return SF_OK;

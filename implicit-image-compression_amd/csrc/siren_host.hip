@@ -1,5 +1,5 @@
 // siren_host.hip — SIREN handles of hidden width <= 256 on the host: the forward, backward, layer-0 and reduction launchers
-// (kernels: siren_kernels.hip, siren_s8.hip, siren_s8h.hip), weight images, the pass, the scratch formats, and create_handle
+// (kernels: siren_kernels.hip, siren_s8.hip, siren_s8h.hip), weight images, the forward and the backward of a chunk, the scratch formats, and create_handle
 // behind sf_create, sf_render_create (siren_render.hip) and the WaveletSiren sub-handles.  Included by siren_fit.hip.
 
 namespace {
@@ -55,10 +55,10 @@ int launch_fwd(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
 
 // what every forward of a SIREN handle (width <= 256) is given for the chunk that starts at local pixel pix0: coordinates,
 // geometry, weight images and scales; the caller adds its outputs (scratch, target, prediction, partials)
-FwdArgs fwd_args_base(const sf_engine* h, long pix0, int n_super) {
+FwdArgs fwd_args_base(const sf_engine* h, const PixelView& v, long pix0, int n_super) {
   FwdArgs fa = zeroed<FwdArgs>();
-  fill_pixels(h, pix0, fa);
-  fa.gh = h->gh; fa.gw = h->gw; fa.depth = h->D;
+  fill_pixels(h, v, pix0, fa);
+  fa.gh = v.gh; fa.gw = v.gw; fa.depth = h->D;
   fa.l0tab = h->l0tab; fa.l0img = reinterpret_cast<const u32x4*>(h->l0img);
   fa.wf = reinterpret_cast<const u32x4*>(h->wf);
   fa.wf_last = reinterpret_cast<const u32x4*>(h->wf_last);
@@ -96,7 +96,7 @@ int launch_bwd8(sf_engine* h, bool last, bool p0, const Bwd8Args& a, int n_wg) {
         constexpr int WD = decltype(wd)::value;
         constexpr bool LAST = decltype(l)::value, P0 = decltype(p)::value, D8 = decltype(d)::value;
         // fp8 deltas at width 256, every layer below the last: the slot-per-MFMA pipeline (siren_s8h.hip).  The forward of such
-        // a layer is k_fwd_pipe, which spills layer 0's phase bytes too, so run_pass never asks for the P0 form here.
+        // a layer is k_fwd_pipe, which spills layer 0's phase bytes too, so siren_bwd_chunk never asks for the P0 form here.
         if constexpr (WD == 256 && !LAST && D8) {
           return P0 ? fail(SF_ERR_INVALID, "launch_bwd8: no P0 form below the last layer")
                     : launch(h, k_bwd8h<kBwd8hPark>, n_wg, 512, Bwd8hLds<kBwd8hPark>::bytes, a);
@@ -169,107 +169,108 @@ int refresh_images_siren(sf_engine* h) {
   return SF_OK;
 }
 
-// One pass of a SIREN handle of width <= 256 (run_pass has checked the handle's state): per chunk k_fwd -> k_bwd(last) ->
-// k_bwd(hidden l = depth-2 .. 1) -> k_dw0, each followed by the fixed-order slab reduction into the flat fp32 gradient.
-int run_pass_siren(sf_engine* h, bool train, float* pred, bool want_sse, int phases, long c_begin, long c_end) {
-  SF_TRY(refresh_images(h));
+// The forward of chunk c of a SIREN handle of width <= 256, training or evaluation form (k_fwd / k_fwd_pipe): the prediction
+// to pred (or null), the chunk's SSE partials to sse_part; n_part: how many it wrote (fwd_grid)
+int siren_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
   const int WD = h->WD, D = h->D;
-  long sse_off = 0;
-  for (long c = c_begin; c < (c_end < 0 ? n_chunks(h->npix, h->chunk_px) : c_end); ++c) {
-    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
-    const long n_pb = k.n_pb;
-    const double npx = n_pb * 32.0;
-    FwdArgs fa = fwd_args_base(h, k.pix0, k.n_super);
-    fa.P = h->Pbuf; fa.p_stride = h->p_stride; fa.Dlast = h->Dlast;
-    fa.dfac = train ? h->wv.dfac_out : nullptr;
-    fa.img = h->img;
-    fa.gscale = h->d8 ? kResScale : gscale(h);
-    fa.pred = pred;
-    fa.sse_part = h->sse_part + sse_off;
-    const int n_fwd_wg = fwd_grid(h, k.n_super);
-    sse_off += n_fwd_wg;
-    if (phases & kPassFwd) {
-      Launch L(h, K_FWD, flops_fwd_px(h) * npx,
-               npx * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
-      SF_TRY(launch_fwd(h, fa, n_fwd_wg, train));
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  const double npx = k.n_pb * 32.0;
+  FwdArgs fa = fwd_args_base(h, own_view(h), k.pix0, k.n_super);
+  fa.P = h->Pbuf; fa.p_stride = h->p_stride; fa.Dlast = h->Dlast;
+  fa.dfac = train ? h->wv.dfac_out : nullptr;
+  fa.img = h->img;
+  fa.gscale = h->d8 ? kResScale : gscale(h);
+  fa.pred = pred;
+  fa.sse_part = sse_part;
+  n_part = fwd_grid(h, k.n_super);
+  Launch L(h, K_FWD, flops_fwd_px(h) * npx,
+           npx * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
+  return launch_fwd(h, fa, n_part, train);
+}
+
+// The backward of chunk c after its training forward: k_bwd(last) -> k_bwd(hidden l = depth-2 .. 1) -> k_dw0, each followed by
+// the fixed-order slab reduction into the flat fp32 gradient (accumulating from the second chunk on).  sse_part, n_part: the
+// forward's partials of this chunk, from which the fp8 form of k_bwd8 takes the chunk's scale
+int siren_bwd_chunk(sf_engine* h, long c, const float* sse_part, int n_part) {
+  const int WD = h->WD, D = h->D;
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  const long n_pb = k.n_pb;
+  const double npx = n_pb * 32.0;
+  const float sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  // backward, last layer first; every layer kernel is followed by the fixed-order slab reduction
+  const int PBS = 2;   // k_dw stages two pixel blocks at a time; k_bwd accepts any block count
+  int n_wg = (int)((n_pb + PBS - 1) / PBS);
+  if (n_wg > h->dw_wg) n_wg = h->dw_wg;
+  long pb_per_wg = (n_pb + n_wg - 1) / n_wg;
+  pb_per_wg = (pb_per_wg + PBS - 1) / PBS * PBS;
+  n_wg = (int)((n_pb + pb_per_wg - 1) / pb_per_wg);
+  const size_t img_pieces = (size_t)WD * WD / 8;
+  // what Bwd8Args and BwdLayerArgs share for layer l >= 1: deltas in and out, phases of the layer below, the backward image
+  auto fill_layer = [&](auto& ba, int l) {
+    const bool last = l == D - 1;
+    fill_grid(h, k.pix0, ba);
+    ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
+    ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
+    ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
+    ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
+                 : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
+    ba.n_pb = n_pb; ba.slab = h->slab; ba.l0tab = h->l0tab; ba.sc_first = sc_first;
+  };
+  for (int l = D - 1; l >= 0; --l) {
+    const bool last = l == D - 1;
+    const double rows = last ? h->cfg.out_features : WD;
+    ReduceArgs ra = zeroed<ReduceArgs>();
+    ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
+    if (h->d8) {   // last layer: dW from the statically scaled residual; layers below: the chunk's adaptive pre-scale
+      ra.scale = (float)(1.0 / ((double)kResScale * (double)h->cfg.out_features * h->n_total));
+      ra.scale_dev = last ? nullptr : h->scale_dev;
+      ra.scale2_dev = (last || !h->lsc) ? nullptr : h->lsc + 16 + l;
     }
-    if (!train || !(phases & kPassBwd)) continue;
-    // backward, last layer first; every layer kernel is followed by the fixed-order slab reduction
-    const int PBS = 2;   // k_dw stages two pixel blocks at a time; k_bwd accepts any block count
-    int n_wg = (int)((n_pb + PBS - 1) / PBS);
-    if (n_wg > h->dw_wg) n_wg = h->dw_wg;
-    long pb_per_wg = (n_pb + n_wg - 1) / n_wg;
-    pb_per_wg = (pb_per_wg + PBS - 1) / PBS * PBS;
-    n_wg = (int)((n_pb + pb_per_wg - 1) / pb_per_wg);
-    const size_t img_pieces = (size_t)WD * WD / 8;
-    // what Bwd8Args and BwdLayerArgs share for layer l >= 1: deltas in and out, phases of the layer below, the backward image
-    auto fill_layer = [&](auto& ba, int l) {
-      const bool last = l == D - 1;
-      fill_grid(h, k.pix0, ba);
-      ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
-      ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
-      ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
-      ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
-                   : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
-      ba.n_pb = n_pb; ba.slab = h->slab; ba.l0tab = h->l0tab; ba.sc_first = fa.sc_first;
-    };
-    for (int l = D - 1; l >= 0; --l) {
-      const bool last = l == D - 1;
-      const double rows = last ? h->cfg.out_features : WD;
-      ReduceArgs ra = zeroed<ReduceArgs>();
-      ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
-      if (h->d8) {   // last layer: dW from the statically scaled residual; layers below: the chunk's adaptive pre-scale
-        ra.scale = (float)(1.0 / ((double)kResScale * (double)h->cfg.out_features * h->n_total));
-        ra.scale_dev = last ? nullptr : h->scale_dev;
-        ra.scale2_dev = (last || !h->lsc) ? nullptr : h->lsc + 16 + l;
-      }
-      ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l];
-      // a layer above 0: rows x WD weight gradient from slabs of (last: 32, else WD) rows
-      ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD; ra.rows_out = (int)rows; ra.cols_out = WD; ra.mode = 0;
-      if (l > 0 && h->s8) {
-        // layer 1: with fp8 deltas at width 256 the pipeline forward also spills layer 0's phase bytes, so this layer runs the
-        // hidden-layer kernel (k_bwd8h) like the others; else the form that re-derives the layer-0 phases from the coordinates
-        const bool l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h), p0 = l - 1 == 0 && !(l0_bytes && !last);
-        Bwd8Args ba = zeroed<Bwd8Args>();
-        fill_layer(ba, l);
-        ba.sse_part = fa.sse_part; ba.n_part = n_fwd_wg;
-        ba.inv_chunk_values = 1.0 / ((double)h->cfg.out_features * (double)k.px);
-        ba.n_values = (double)h->cfg.out_features * h->n_total;
-        ba.res_scale = kResScale; ba.target = kFp8Target; ba.scale_out = h->scale_dev;
-        ba.zeros = reinterpret_cast<const u32x4*>(h->pad8); ba.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
-        // hidden 256: the last-layer kernel keeps two workgroups per CU (its slab rows are 32 wide: the slab has room)
-        if (last && !p0 && WD == 256 && h->d8) ra.n_wg = (int)std::min<long>((n_pb + PBS - 1) / PBS, 2L * h->dw_wg);
-        const double db = h->d8 ? 1.0 : 2.0;   // bytes per delta
-        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
-                 npx * ((last ? 32.0 : WD * db) + WD * db + (p0 ? 0.0 : WD * 1.0)));
-        SF_TRY(launch_bwd8(h, last, p0, ba, ra.n_wg));
-      } else if (l > 0) {
-        const bool p0 = l - 1 == 0;
-        BwdLayerArgs ba = zeroed<BwdLayerArgs>();
-        fill_layer(ba, l);
-        ba.pb_per_wg = (int)pb_per_wg;
-        Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
-                 npx * ((last ? 64.0 : WD * 2.0) + WD * (p0 ? 2.0 : 4.0)));
-        SF_TRY(launch_bwd(h, last, p0, ba, n_wg));
-      } else {
-        Dw0Args da = zeroed<Dw0Args>();
-        fill_grid(h, k.pix0, da);
-        da.D = h->Dbuf; da.ks_total = WD / 16; da.ks_off = 0; da.n_pb = n_pb; da.slab = h->slab;
-        const long cap0 = (h->d8 && WD == 256) ? 2L * h->dw_wg : (long)h->dw_wg;      // k_dw0_8<256>: two workgroups per CU
-        ra.n_wg = (int)(n_pb < cap0 ? n_pb : cap0);
-        ra.slab_rows = WD; ra.slab_cols = 32; ra.rows_out = WD; ra.cols_out = 2; ra.mode = 1;
-        Launch L(h, K_DW_FIRST, 4.0 * WD * npx, WD * (h->d8 ? 1.0 : 2.0) * npx);
-        SF_TRY(launch_dw_first(h, da, ra.n_wg));
-      }
-      const int n = ra.rows_out * ra.cols_out + ra.rows_out;
-      Launch L(h, K_REDUCE, 0, (double)n_wg * n * 4.0);
-      if (l > 0 && !last)   // slab layout == flat gradient layout [W | b]
-        SF_TRY(launch(h, k_reduce_vec, (n / 4 + 7) / 8, 256, 0, h->slab, n_wg, n, n / 4, h->grads + h->off_w[l], ra.accumulate,
-                      ra.scale, ra.scale_dev, ra.scale2_dev));
-      else SF_TRY(launch_reduce(h, ra));
+    ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l];
+    // a layer above 0: rows x WD weight gradient from slabs of (last: 32, else WD) rows
+    ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD; ra.rows_out = (int)rows; ra.cols_out = WD; ra.mode = 0;
+    if (l > 0 && h->s8) {
+      // layer 1: with fp8 deltas at width 256 the pipeline forward also spills layer 0's phase bytes, so this layer runs the
+      // hidden-layer kernel (k_bwd8h) like the others; else the form that re-derives the layer-0 phases from the coordinates
+      const bool l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h), p0 = l - 1 == 0 && !(l0_bytes && !last);
+      Bwd8Args ba = zeroed<Bwd8Args>();
+      fill_layer(ba, l);
+      ba.sse_part = sse_part; ba.n_part = n_part;
+      ba.inv_chunk_values = 1.0 / ((double)h->cfg.out_features * (double)k.px);
+      ba.n_values = (double)h->cfg.out_features * h->n_total;
+      ba.res_scale = kResScale; ba.target = kFp8Target; ba.scale_out = h->scale_dev;
+      ba.zeros = reinterpret_cast<const u32x4*>(h->pad8); ba.dump = reinterpret_cast<u32x4*>(h->pad8 + 8192);
+      // hidden 256: the last-layer kernel keeps two workgroups per CU (its slab rows are 32 wide: the slab has room)
+      if (last && !p0 && WD == 256 && h->d8) ra.n_wg = (int)std::min<long>((n_pb + PBS - 1) / PBS, 2L * h->dw_wg);
+      const double db = h->d8 ? 1.0 : 2.0;   // bytes per delta
+      Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
+               npx * ((last ? 32.0 : WD * db) + WD * db + (p0 ? 0.0 : WD * 1.0)));
+      SF_TRY(launch_bwd8(h, last, p0, ba, ra.n_wg));
+    } else if (l > 0) {
+      const bool p0 = l - 1 == 0;
+      BwdLayerArgs ba = zeroed<BwdLayerArgs>();
+      fill_layer(ba, l);
+      ba.pb_per_wg = (int)pb_per_wg;
+      Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
+               npx * ((last ? 64.0 : WD * 2.0) + WD * (p0 ? 2.0 : 4.0)));
+      SF_TRY(launch_bwd(h, last, p0, ba, n_wg));
+    } else {
+      Dw0Args da = zeroed<Dw0Args>();
+      fill_grid(h, k.pix0, da);
+      da.D = h->Dbuf; da.ks_total = WD / 16; da.ks_off = 0; da.n_pb = n_pb; da.slab = h->slab;
+      const long cap0 = (h->d8 && WD == 256) ? 2L * h->dw_wg : (long)h->dw_wg;      // k_dw0_8<256>: two workgroups per CU
+      ra.n_wg = (int)(n_pb < cap0 ? n_pb : cap0);
+      ra.slab_rows = WD; ra.slab_cols = 32; ra.rows_out = WD; ra.cols_out = 2; ra.mode = 1;
+      Launch L(h, K_DW_FIRST, 4.0 * WD * npx, WD * (h->d8 ? 1.0 : 2.0) * npx);
+      SF_TRY(launch_dw_first(h, da, ra.n_wg));
     }
+    const int n = ra.rows_out * ra.cols_out + ra.rows_out;
+    Launch L(h, K_REDUCE, 0, (double)n_wg * n * 4.0);
+    if (l > 0 && !last)   // slab layout == flat gradient layout [W | b]
+      SF_TRY(launch(h, k_reduce_vec, (n / 4 + 7) / 8, 256, 0, h->slab, n_wg, n, n / 4, h->grads + h->off_w[l], ra.accumulate,
+                    ra.scale, ra.scale_dev, ra.scale2_dev));
+    else SF_TRY(launch_reduce(h, ra));
   }
-  if ((want_sse || train) && !h->wv.ext_dout) SF_TRY(launch_sse_reduce(h, sse_off));
   return SF_OK;
 }
 

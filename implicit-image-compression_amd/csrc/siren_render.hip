@@ -121,7 +121,7 @@ namespace {
 
 // the kernel family sf_forward picks for the handle (fwd_is_pipe), in its RENDER form, on n_wg workgroups (fwd_grid);
 // bits: 8 (a.rgb8) or 16 (a.rgb16) per sample
-int launch_render(sf_engine* h, const FwdArgs& a, int n_wg, int bits = 8) {
+int launch_render(sf_engine* h, const FwdArgs& a, int n_wg, int bits) {
   return with_bool(bits == 16, [&](auto wide) {
     constexpr int BITS = decltype(wide)::value ? 16 : 8;
     return with_op(h, [&](auto op) {
@@ -136,10 +136,28 @@ int launch_render(sf_engine* h, const FwdArgs& a, int n_wg, int bits = 8) {
   });
 }
 
+// The render loop of a SIREN handle of width <= 256 (its images are current): the RENDER forward of every chunk, to pred and /
+// or to samples of `bits` bits at out (either may be null).  window: the pixels drawn when they are not the handle's own grid
+// (sf_wavelet_render: a coefficient window on a sub-handle)
+int render_chunks(sf_engine* h, void* out, int bits, float* pred, const PixelView* window = nullptr) {
+  const PixelView v = window ? *window : own_view(h);
+  for (long c = 0; c < n_chunks(v.npix, h->chunk_px); ++c) {
+    const Chunk k = chunk_at(c, v.npix, h->chunk_px);
+    const int n_super = k.n_super;
+    FwdArgs fa = fwd_args_base(h, v, k.pix0, n_super);
+    fa.pred = pred;
+    fa.rgb8 = (uint8_t*)out;   // (a.rgb16 of the 16-bit forms: the same member)
+    const double out_bytes = (pred ? 4.0 : 0.0) + (out ? bits / 8.0 : 0.0);
+    Launch L(h, K_RENDER, flops_fwd_px(h) * n_super * (double)kSuper, n_super * (double)kSuper * h->cfg.out_features * out_bytes);
+    SF_TRY(launch_render(h, fa, fwd_grid(h, n_super), bits));
+  }
+  return SF_OK;
+}
+
 // fourier_render.hip, included last: the RENDER form of k_ff_fwd (out: bits / 8 bytes per sample)
 int render_fourier(sf_engine* h, void* out, int bits, float* pred);
 
-// sf_render (bits = 8) and sf_render16 (bits = 16): one set of argument checks, one chunk loop
+// sf_render (bits = 8) and sf_render16 (bits = 16): one set of argument checks
 int render_any(sf_handle* h, void* out, int bits, float* pred) {
   const std::string fn = bits == 16 ? "sf_render16" : "sf_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
   if (!h) return fail(SF_ERR_INVALID, "null argument");
@@ -161,17 +179,7 @@ int render_any(sf_handle* h, void* out, int bits, float* pred) {
   }
   DevGuard dev_guard(h->cfg.device);
   SF_TRY(refresh_images(h));
-  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
-    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
-    const int n_super = k.n_super;
-    FwdArgs fa = fwd_args_base(h, k.pix0, n_super);
-    fa.pred = pred;
-    fa.rgb8 = (uint8_t*)out;   // (a.rgb16 of the 16-bit forms: the same member)
-    const double out_bytes = (pred ? 4.0 : 0.0) + (out ? bits / 8.0 : 0.0);
-    Launch L(h, K_RENDER, flops_fwd_px(h) * n_super * (double)kSuper, n_super * (double)kSuper * h->cfg.out_features * out_bytes);
-    SF_TRY(launch_render(h, fa, fwd_grid(h, n_super), bits));
-  }
-  return SF_OK;
+  return render_chunks(h, out, bits, pred);
 }
 
 }  // namespace

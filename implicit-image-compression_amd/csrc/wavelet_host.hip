@@ -19,14 +19,19 @@ int refresh_images_wavelet(sf_engine* h) {
 // Two passes (more than one chunk): inference forward of both over every chunk -> compose -> adjoint into an fp32 buffer
 //   -> per chunk and sub-network: training forward, k_wv_inject, backward.
 // Then the fixed-order reduction of the compose partials into the handle's SSE.
+// The sub-networks run through the SIREN chunk functions (siren_host.hip) and, for the inference forwards, the chunk loop; they
+// launch through this handle's context, their weight images are refreshed here with this handle's, and the SSE partials
+// their forwards write (they have no target: nothing reads them) go to the start of their own sse_part.
 int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
   SF_TRY(refresh_images(h));
   sf_engine* const sub[2] = {h->wv.sub[0], h->wv.sub[1]};
   const long nn = sub[0]->npix, HH = h->npix;
   const bool one = nn <= sub[0]->chunk_px;
   float* const p_sub[2] = {h->wv.pred, h->wv.pred + nn * 3};
+  int n_part[2] = {0, 0};
   for (int s = 0; s < 2; ++s)
-    SF_TRY(train && one ? run_pass(sub[s], true, p_sub[s], false, kPassFwd) : run_pass(sub[s], false, p_sub[s], false));
+    SF_TRY(train && one ? siren_fwd_chunk(sub[s], 0, true, p_sub[s], sub[s]->sse_part, n_part[s])
+                        : run_chunks(sub[s], false, p_sub[s], false));
   WvArgs a = zeroed<WvArgs>();
   a.H = h->cfg.height; a.n = h->wv.n; a.up = h->wv.up;
   a.lf = p_sub[0]; a.hf = p_sub[1];
@@ -49,18 +54,18 @@ int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
       SF_TRY(launch(h, k_wv_adjoint, wv_grid(nn), kWvThreads, 0, a));
     }
     if (one) {
-      for (int s = 0; s < 2; ++s) SF_TRY(run_pass(sub[s], true, nullptr, false, kPassBwd));
+      for (int s = 0; s < 2; ++s) SF_TRY(siren_bwd_chunk(sub[s], 0, sub[s]->sse_part, n_part[s]));
     } else {
       for (long c = 0; c < n_chunks(nn, sub[0]->chunk_px); ++c) {
         const Chunk k = chunk_at(c, nn, sub[0]->chunk_px);
         for (int s = 0; s < 2; ++s) {
-          SF_TRY(run_pass(sub[s], true, nullptr, false, kPassFwd, c, c + 1));
+          SF_TRY(siren_fwd_chunk(sub[s], c, true, nullptr, sub[s]->sse_part, n_part[s]));
           {
             Launch L(h, K_WV_INJECT, 0, (double)k.px * 28.0);
             SF_TRY(launch(h, k_wv_inject, wv_grid(k.px), kWvThreads, 0, h->wv.gl + (size_t)s * nn * 3, sub[s]->wv.dfac_out, k.pix0,
                           k.px, sub[s]->Dlast));
           }
-          SF_TRY(run_pass(sub[s], true, nullptr, false, kPassBwd, c, c + 1));
+          SF_TRY(siren_bwd_chunk(sub[s], c, sub[s]->sse_part, n_part[s]));
         }
       }
     }
@@ -156,7 +161,7 @@ int sf_wavelet_create(const sf_wavelet_config* cfg, sf_handle** out) try {
     const int64_t P0 = h->wv.sub[0]->P;
     // the sub-networks' dL/dout pre-scale comes from the 3 H^2 values of the full image (what the loss mean divides by)
     const float gpre = (float)exp2(ceil(log2(3.0 * h->n_total)) + 2.0);
-    for (sf_engine* s : h->wv.sub) { s->gpre = gpre; s->wv.ext_dout = true; }
+    for (sf_engine* s : h->wv.sub) s->gpre = gpre;
     SF_TRY(alloc_state(h, true));
     SF_TRY(dev_alloc(h, h->wv.pred, (size_t)2 * nn * 3 * 4));
     SF_TRY(dev_alloc(h, h->wv.g, (size_t)h->npix * 3 * 4));

@@ -170,7 +170,7 @@ int create_wavelet_render(const sf_wavelet_render_config* cfg, sf_handle** out) 
   return create_with(cfg, out, (int32_t sf_wavelet_render_config::*)nullptr, Model::Wavelet, true, check, init);
 }
 
-// sf_wavelet_render (bits = 8) and sf_wavelet_render16 (bits = 16): one set of argument checks, one pair of chunk loops
+// sf_wavelet_render (bits = 8) and sf_wavelet_render16 (bits = 16): one set of argument checks; the sub-networks are drawn by render_chunks
 int wavelet_render_any(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, int32_t col1, void* out, int bits, float* pred) {
   const std::string fn = bits == 16 ? "sf_wavelet_render16" : "sf_wavelet_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
   if (!h) return fail(SF_ERR_INVALID, "null argument");
@@ -195,20 +195,9 @@ int wavelet_render_any(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, i
   const float* gh = h->render ? h->gh : h->wv.sub[0]->gh;
   const float* gw = h->render ? h->gw : h->wv.sub[0]->gw;
   float* const p_sub[2] = {h->wv.pred, h->wv.pred + nn * 3};
-  for (int s = 0; s < 2; ++s) {
-    sf_engine* e = h->wv.sub[s];
-    for (long c = 0; c < n_chunks(nn, e->chunk_px); ++c) {
-      const Chunk k = chunk_at(c, nn, e->chunk_px);
-      const int n_super = k.n_super;
-      FwdArgs fa = fwd_args_base(e, k.pix0, n_super);
-      // the sub-grid of this window: its rows / columns are slices of the full vectors, its row length is cc
-      fa.gh = gh + i0; fa.gw = gw + j0; fa.row_begin = 0; fa.W = cc; fa.npix = nn;
-      fa.w_magic = ((1ULL << 40) + (unsigned long long)cc - 1) / (unsigned long long)cc;
-      fa.pred = p_sub[s];
-      Launch L(e, K_RENDER, flops_fwd_px(e) * n_super * (double)kSuper, n_super * (double)kSuper * 3 * 4.0);
-      SF_TRY(launch_render(e, fa, fwd_grid(e, n_super)));
-    }
-  }
+  // the sub-grid of this window: its rows / columns are slices of the full vectors, its row length is cc
+  const PixelView window = {gh + i0, gw + j0, cc, nn};
+  for (int s = 0; s < 2; ++s) SF_TRY(render_chunks(h->wv.sub[s], nullptr, 8, p_sub[s], &window));
   WvRenderArgs a = zeroed<WvRenderArgs>();
   a.H = H; a.n = h->wv.n; a.up = h->wv.up;
   a.row0 = row0; a.col0 = col0; a.cols = col1 - col0;

@@ -1,5 +1,5 @@
-// wide_host.hip — SIREN handles of hidden 512 / 1024 on the host: weight images and the pass over the layer-at-a-time
-// kernels of siren_wide.hip.  Included by siren_fit.hip after siren_host.hip, whose layer-0 and reduction launchers it shares.
+// wide_host.hip — SIREN handles of hidden 512 / 1024 on the host: weight images, a chunk's forward and backward over the
+// layer-at-a-time kernels of siren_wide.hip.  Included by siren_fit.hip after siren_host.hip, whose layer-0 and reduction launchers it shares.
 
 namespace {
 
@@ -69,119 +69,126 @@ int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob) {
     return with_op(h, [&](auto op) { return launch(h, k_wgemm2<MODE, decltype(op)>, pgrid, 512, lds, b); });
   }
 }
-int run_pass_wide(sf_engine* h, bool train, float* pred, bool want_sse) {
-  SF_TRY(refresh_images(h));
+
+// The forward of chunk c, layer at a time (k_wlayer0, k_wgemm2<0> per hidden layer, k_wgemm), training or evaluation form: the
+// prediction to pred (or null), the chunk's SSE partials to sse_part; n_part: how many it wrote (one per 256-pixel group)
+int wide_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
   const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
-  const bool f16 = h->cfg.compute_dtype == SF_F16;
   const float sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
   const float sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
   const size_t blk_pieces = (size_t)(KS / 4) * 32;   // pieces of one [256 x WD] block of a hidden image
-  long sse_off = 0;
-  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
-    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
-    const int n_super = k.n_super;
-    const long n_pb = k.n_pb;
-    const double npx = n_pb * 32.0;
-    // ---- forward ----
-    {
-      WL0Args a = zeroed<WL0Args>();
-      a.gh = h->gh; a.gw = h->gw; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin; a.pix0 = k.pix0; a.npix = h->npix;
-      a.l0tab = h->l0tab; a.sc_first = sc_first; a.KS = KS; a.n_pieces = n_pb * KS; a.P = h->Pbuf; a.Act = h->Abuf;
-      Launch L(h, K_FWD, 4.0 * WD * npx, npx * (WD * (h->s8 ? 3.0 : 4.0)));
-      if (h->s8) SF_TRY(launch(h, k_wlayer0<OpF16, true>, (a.n_pieces / 2 + 3) / 4, 256, 0, a));
-      else SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op)>, (a.n_pieces + 3) / 4, 256, 0, a); }));
-    }
-    for (int l = 1; l <= D - 2; ++l) {
-      WGemmArgs a = zeroed<WGemmArgs>();
-      a.A = reinterpret_cast<const u32x4*>(h->wf + (size_t)(l - 1) * WD * WD);
-      a.a_block_pieces = (long)blk_pieces; a.n_chunk = KS / 4;
-      a.Bin = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ks_in = KS;
-      a.bias = h->biasw + (size_t)(l - 1) * WD; a.sc = sc_hidden;
-      a.Out = h->Pbuf + (size_t)l * h->p_stride; a.OutAct = h->Abuf + (size_t)l * h->a_stride; a.ks_out = KS; a.kp_out = WD / 32;
-      Launch L(h, K_FWD, 2.0 * WD * WD * npx, npx * (WD * ((h->s8 ? 3.0 : 4.0) + 2.0 * NBLK)));
-      SF_TRY(launch_wgemm<0>(h, a, n_super, NBLK));
-    }
-    {
-      WGemmArgs a = zeroed<WGemmArgs>();
-      a.A = reinterpret_cast<const u32x4*>(h->wf_last);
-      a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
-      a.Bin = h->Abuf + (size_t)(D - 2) * h->a_stride; a.ks_in = KS;
-      a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
-      a.img = h->img; a.pred = pred; a.nout = h->cfg.out_features;
-      a.gscale = gscale(h);
-      a.sse_part = h->sse_part + sse_off; a.Dlast = train ? h->Dlast : nullptr; a.pix0 = k.pix0; a.npix = h->npix;
-      if (!h->cfg.outermost_linear) { a.last_om = h->cfg.hidden_omega_0; a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
-      sse_off += n_super;
-      Launch L(h, K_FWD, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + 12.0 + 64.0));
-      SF_TRY(launch_wgemm<1>(h, a, n_super, 1));
-    }
-    if (!train) continue;
-    // ---- backward ----
-    const int n_wg = (int)(n_pb < (long)h->dw_wg ? n_pb : (long)h->dw_wg);
-    if (h->d8)   // fp8 deltas: this chunk's power-of-two factor from its own residual
-      SF_TRY(launch(h, k_wchunk_scale, 1, 256, 0, h->sse_part + sse_off - n_super, n_super,
-                    1.0 / ((double)h->cfg.out_features * (double)k.px), gscale(h), h->gpre, kFp8Target, h->scale_dev));
-    for (int l = D - 1; l >= 1; --l) {
-      const bool last = l == D - 1;
-      const bool dl8 = h->d8 && !last;                      // this layer's incoming deltas are fp8 byte pieces
-      const u32x4* Dl = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
-      const u32x4* Pprev = h->Pbuf + (size_t)(l - 1) * h->p_stride;
-      const double rows = last ? h->cfg.out_features : WD;
-      {   // weight gradient: every [256 x 256] (last layer: [32 x 256]) block in one launch, blockIdx.y = block
-        const int nby = (last ? 1 : NBLK) * NBLK;
-        int gx = h->dw_wg / nby / 8 * 8;            // multiple of 8: same-pixel workgroups share an XCD
-        if (gx < 8) gx = 8;
-        if ((long)gx > n_pb) gx = (int)n_pb;
-        WDwArgs a = zeroed<WDwArgs>();
-        a.D = Dl; a.ksd_total = last ? 2 : (dl8 ? WD / 32 : KS); a.P = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ksp_total = KS; a.nblk_i = NBLK;
-        a.n_pb = n_pb; a.slab = h->slab;
-        {
-          Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx, npx * ((last ? 64.0 : WD * 2.0) + WD * 2.0));
-          const dim3 grid(gx, nby);
-          if (dl8) SF_TRY(launch(h, k_wdw<256, OpF16, true>, grid, 512, WDwLds<256, true>::bytes, a));
-          else SF_TRY(with_op(h, [&](auto op) {
-            using OP = decltype(op);
-            return last ? launch(h, k_wdw<32, OP>, grid, 512, WDwLds<32, false>::bytes, a) : launch(h, k_wdw<256, OP>, grid, 512, WDwLds<256, false>::bytes, a);
-          }));
-        }
-        WReduceArgs r = zeroed<WReduceArgs>();
-        r.slab = h->slab; r.n_wg = gx; r.slab_rows = last ? 32 : 256; r.rows_out = last ? h->cfg.out_features : 256;
-        r.nblk_i = NBLK; r.gW = h->grads + h->off_w[l]; r.ldw = WD; r.gb = h->grads + h->off_b[l];
-        r.accumulate = c > 0; r.scale = 1.0f / h->gpre;
-        if (dl8) { r.s1 = h->scale_dev; r.s2 = h->lsc + 16 + l; }
-        const int n = r.rows_out * 256 + r.rows_out;
-        Launch L(h, K_REDUCE, 0, (double)gx * nby * n * 4.0);
-        SF_TRY(launch(h, k_wreduce, dim3((n + 255) / 256, nby), 256, 0, r));
-      }
-      // data gradient: delta_{l-1} = (delta_l W_l) * omega cos(P_{l-1})
-      WGemmArgs a = zeroed<WGemmArgs>();
-      a.A = last ? reinterpret_cast<const u32x4*>(h->wb_last) : reinterpret_cast<const u32x4*>(h->wb + (size_t)(l - 1) * WD * WD);
-      a.a_block_pieces = last ? 32 : (long)blk_pieces; a.n_chunk = last ? 1 : KS / 4;
-      a.Bin = Dl; a.ks_in = last ? 2 : KS;
-      a.Out = h->Dbuf + (size_t)(l - 1) * h->d_stride; a.ks_out = KS; a.kp_out = WD / 32; a.Pprev = Pprev;
-      a.fscale = (h->d8 && last) ? h->scale_dev : nullptr;
-      Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx,
-               npx * ((last ? 64.0 : WD * 2.0 * NBLK) + WD * (h->s8 ? 3.0 : 4.0)));
-      SF_TRY(launch_wgemm<2>(h, a, n_super, NBLK));
-    }
-    for (int jb = 0; jb < NBLK; ++jb) {   // layer 0: contraction of delta_0 with the coordinates
-      Dw0Args da = zeroed<Dw0Args>();
-      fill_grid(h, k.pix0, da);
-      da.D = h->Dbuf; da.ks_total = KS; da.ks_off = 16 * jb; da.n_pb = n_pb; da.slab = h->slab;
-      {
-        Launch L(h, K_DW_FIRST, 4.0 * 256 * npx, (h->d8 ? 256.0 : 512.0) * npx);
-        SF_TRY(launch_dw_first_t<256>(h, da, n_wg));
-      }
-      ReduceArgs ra = zeroed<ReduceArgs>();
-      ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre; ra.scale_dev = nullptr;
-      if (h->d8) { ra.scale_dev = h->scale_dev; ra.scale2_dev = h->lsc + 16; }     // 1 / (chunk factor * gpre), 1 / cumulative layer scale
-      ra.gW = h->grads + h->off_w[0] + 512 * jb; ra.gb = h->grads + h->off_b[0] + 256 * jb;
-      ra.slab_rows = 256; ra.slab_cols = 32; ra.rows_out = 256; ra.cols_out = 2; ra.mode = 1;
-      Launch L(h, K_REDUCE, 0, (double)n_wg * (256 * 3) * 4.0);
-      SF_TRY(launch_reduce(h, ra));
-    }
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  const int n_super = k.n_super;
+  const long n_pb = k.n_pb;
+  const double npx = n_pb * 32.0;
+  {
+    WL0Args a = zeroed<WL0Args>();
+    a.gh = h->gh; a.gw = h->gw; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin; a.pix0 = k.pix0; a.npix = h->npix;
+    a.l0tab = h->l0tab; a.sc_first = sc_first; a.KS = KS; a.n_pieces = n_pb * KS; a.P = h->Pbuf; a.Act = h->Abuf;
+    Launch L(h, K_FWD, 4.0 * WD * npx, npx * (WD * (h->s8 ? 3.0 : 4.0)));
+    if (h->s8) SF_TRY(launch(h, k_wlayer0<OpF16, true>, (a.n_pieces / 2 + 3) / 4, 256, 0, a));
+    else SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op)>, (a.n_pieces + 3) / 4, 256, 0, a); }));
   }
-  if (want_sse || train) SF_TRY(launch_sse_reduce(h, sse_off));
+  for (int l = 1; l <= D - 2; ++l) {
+    WGemmArgs a = zeroed<WGemmArgs>();
+    a.A = reinterpret_cast<const u32x4*>(h->wf + (size_t)(l - 1) * WD * WD);
+    a.a_block_pieces = (long)blk_pieces; a.n_chunk = KS / 4;
+    a.Bin = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ks_in = KS;
+    a.bias = h->biasw + (size_t)(l - 1) * WD; a.sc = sc_hidden;
+    a.Out = h->Pbuf + (size_t)l * h->p_stride; a.OutAct = h->Abuf + (size_t)l * h->a_stride; a.ks_out = KS; a.kp_out = WD / 32;
+    Launch L(h, K_FWD, 2.0 * WD * WD * npx, npx * (WD * ((h->s8 ? 3.0 : 4.0) + 2.0 * NBLK)));
+    SF_TRY(launch_wgemm<0>(h, a, n_super, NBLK));
+  }
+  {
+    WGemmArgs a = zeroed<WGemmArgs>();
+    a.A = reinterpret_cast<const u32x4*>(h->wf_last);
+    a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
+    a.Bin = h->Abuf + (size_t)(D - 2) * h->a_stride; a.ks_in = KS;
+    a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
+    a.img = h->img; a.pred = pred; a.nout = h->cfg.out_features;
+    a.gscale = gscale(h);
+    a.sse_part = sse_part; a.Dlast = train ? h->Dlast : nullptr; a.pix0 = k.pix0; a.npix = h->npix;
+    if (!h->cfg.outermost_linear) { a.last_om = h->cfg.hidden_omega_0; a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
+    n_part = n_super;
+    Launch L(h, K_FWD, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + 12.0 + 64.0));
+    SF_TRY(launch_wgemm<1>(h, a, n_super, 1));
+  }
+  return SF_OK;
+}
+
+// The backward of chunk c after its training forward: per layer, last first, k_wdw (weight gradient, every block in one launch)
+// -> k_wreduce -> k_wgemm2<2> (data gradient); then layer 0 in 256-neuron blocks (k_dw0 -> k_reduce).  sse_part, n_part: the
+// forward's partials of this chunk, from which k_wchunk_scale forms the chunk's fp8 factor
+int wide_bwd_chunk(sf_engine* h, long c, const float* sse_part, int n_part) {
+  const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
+  const size_t blk_pieces = (size_t)(KS / 4) * 32;
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  const int n_super = k.n_super;
+  const long n_pb = k.n_pb;
+  const double npx = n_pb * 32.0;
+  const int n_wg = (int)(n_pb < (long)h->dw_wg ? n_pb : (long)h->dw_wg);
+  if (h->d8)   // fp8 deltas: this chunk's power-of-two factor from its own residual
+    SF_TRY(launch(h, k_wchunk_scale, 1, 256, 0, sse_part, n_part,
+                  1.0 / ((double)h->cfg.out_features * (double)k.px), gscale(h), h->gpre, kFp8Target, h->scale_dev));
+  for (int l = D - 1; l >= 1; --l) {
+    const bool last = l == D - 1;
+    const bool dl8 = h->d8 && !last;                      // this layer's incoming deltas are fp8 byte pieces
+    const u32x4* Dl = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
+    const u32x4* Pprev = h->Pbuf + (size_t)(l - 1) * h->p_stride;
+    const double rows = last ? h->cfg.out_features : WD;
+    {   // weight gradient: every [256 x 256] (last layer: [32 x 256]) block in one launch, blockIdx.y = block
+      const int nby = (last ? 1 : NBLK) * NBLK;
+      int gx = h->dw_wg / nby / 8 * 8;            // multiple of 8: same-pixel workgroups share an XCD
+      if (gx < 8) gx = 8;
+      if ((long)gx > n_pb) gx = (int)n_pb;
+      WDwArgs a = zeroed<WDwArgs>();
+      a.D = Dl; a.ksd_total = last ? 2 : (dl8 ? WD / 32 : KS); a.P = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ksp_total = KS; a.nblk_i = NBLK;
+      a.n_pb = n_pb; a.slab = h->slab;
+      {
+        Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx, npx * ((last ? 64.0 : WD * 2.0) + WD * 2.0));
+        const dim3 grid(gx, nby);
+        if (dl8) SF_TRY(launch(h, k_wdw<256, OpF16, true>, grid, 512, WDwLds<256, true>::bytes, a));
+        else SF_TRY(with_op(h, [&](auto op) {
+          using OP = decltype(op);
+          return last ? launch(h, k_wdw<32, OP>, grid, 512, WDwLds<32, false>::bytes, a) : launch(h, k_wdw<256, OP>, grid, 512, WDwLds<256, false>::bytes, a);
+        }));
+      }
+      WReduceArgs r = zeroed<WReduceArgs>();
+      r.slab = h->slab; r.n_wg = gx; r.slab_rows = last ? 32 : 256; r.rows_out = last ? h->cfg.out_features : 256;
+      r.nblk_i = NBLK; r.gW = h->grads + h->off_w[l]; r.ldw = WD; r.gb = h->grads + h->off_b[l];
+      r.accumulate = c > 0; r.scale = 1.0f / h->gpre;
+      if (dl8) { r.s1 = h->scale_dev; r.s2 = h->lsc + 16 + l; }
+      const int n = r.rows_out * 256 + r.rows_out;
+      Launch L(h, K_REDUCE, 0, (double)gx * nby * n * 4.0);
+      SF_TRY(launch(h, k_wreduce, dim3((n + 255) / 256, nby), 256, 0, r));
+    }
+    // data gradient: delta_{l-1} = (delta_l W_l) * omega cos(P_{l-1})
+    WGemmArgs a = zeroed<WGemmArgs>();
+    a.A = last ? reinterpret_cast<const u32x4*>(h->wb_last) : reinterpret_cast<const u32x4*>(h->wb + (size_t)(l - 1) * WD * WD);
+    a.a_block_pieces = last ? 32 : (long)blk_pieces; a.n_chunk = last ? 1 : KS / 4;
+    a.Bin = Dl; a.ks_in = last ? 2 : KS;
+    a.Out = h->Dbuf + (size_t)(l - 1) * h->d_stride; a.ks_out = KS; a.kp_out = WD / 32; a.Pprev = Pprev;
+    a.fscale = (h->d8 && last) ? h->scale_dev : nullptr;
+    Launch L(h, last ? K_BWD_LAST : K_BWD_HIDDEN, 2.0 * rows * WD * npx,
+             npx * ((last ? 64.0 : WD * 2.0 * NBLK) + WD * (h->s8 ? 3.0 : 4.0)));
+    SF_TRY(launch_wgemm<2>(h, a, n_super, NBLK));
+  }
+  for (int jb = 0; jb < NBLK; ++jb) {   // layer 0: contraction of delta_0 with the coordinates
+    Dw0Args da = zeroed<Dw0Args>();
+    fill_grid(h, k.pix0, da);
+    da.D = h->Dbuf; da.ks_total = KS; da.ks_off = 16 * jb; da.n_pb = n_pb; da.slab = h->slab;
+    {
+      Launch L(h, K_DW_FIRST, 4.0 * 256 * npx, (h->d8 ? 256.0 : 512.0) * npx);
+      SF_TRY(launch_dw_first_t<256>(h, da, n_wg));
+    }
+    ReduceArgs ra = zeroed<ReduceArgs>();
+    ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre; ra.scale_dev = nullptr;
+    if (h->d8) { ra.scale_dev = h->scale_dev; ra.scale2_dev = h->lsc + 16; }     // 1 / (chunk factor * gpre), 1 / cumulative layer scale
+    ra.gW = h->grads + h->off_w[0] + 512 * jb; ra.gb = h->grads + h->off_b[0] + 256 * jb;
+    ra.slab_rows = 256; ra.slab_cols = 32; ra.rows_out = 256; ra.cols_out = 2; ra.mode = 1;
+    Launch L(h, K_REDUCE, 0, (double)n_wg * (256 * 3) * 4.0);
+    SF_TRY(launch_reduce(h, ra));
+  }
   return SF_OK;
 }
 

@@ -84,13 +84,13 @@ def rendered(eng, **kw):
     return finish(eng, {"sha256": sha(u8), "sha256_pred": sha(pred)})
 
 
-def render(hidden, depth):
+def render(hidden, depth, **kw):
     H, W = 40, 52
     rows, cols = (t.cuda() for t in so.grid_vectors(H, W))
     eng = E.RenderEngine(H, W, hidden, depth, chunk_pixels=1024)
     eng.set_coords(rows, cols)
     eng.set_params(siren_flat(hidden, depth))
-    return rendered(eng)
+    return rendered(eng, **kw)
 
 
 def fourier_render():
@@ -103,12 +103,12 @@ def fourier_render():
     return rendered(eng)
 
 
-def wavelet_render():
+def wavelet_render(**kw):
     eng = E.WaveletRenderEngine(30, 64, 3, chunk_pixels=256)
     rows = cols = torch.linspace(0, 1, eng.n).cuda()
     eng.set_coords(rows, cols)
     eng.set_params(torch.cat([siren_flat(64, 3)] * 2))
-    return rendered(eng)
+    return rendered(eng, **kw)
 
 
 STEP_LRS = (1e-3, 5e-4, 2.5e-4)
@@ -152,6 +152,9 @@ def cases():
     out.append(("render_256x4_40x52", lambda: render(256, 4)))
     out.append(("fourier_render_64x3_ms64_40x52", fourier_render))
     out.append(("wavelet_render_64x3_H30", wavelet_render))
+    out.append(("render16_64x3_40x52", lambda: render(64, 3, bits=16)))
+    # pixel rows 6 .. 21, columns 9 .. 29 of H = 30 read the 10 x 13 coefficient window at (3, 4) of the 17 x 17 grid
+    out.append(("wavelet_render16_window_64x3_H30", lambda: wavelet_render(r0=6, r1=22, c0=9, c1=30, bits=16)))
     out.append(("feather_64x3_fmt16_40x52", lambda: siren(40, 52, 64, 3, 16, feather=True)))
     return out
 

@@ -15,7 +15,9 @@ Cases (all eager, profiling on, one sf_forward + one sf_forward_backward, render
   WaveletSiren 64x3 at H = 2 (the smallest image the creator accepts; its 9 coefficients are one chunk whatever
     chunk_pixels is) and, for the two-pass path (k_wv_inject), at H = 30 with chunk_pixels 256: the smallest even H whose
     17 x 17 coefficient grid passes the smallest chunk of 256
-  render handles: sf_render_create 64x3 and 256x4, sf_fourier_render_create 64, sf_wavelet_render_create 64x3 (H = 30)
+  render handles: sf_render_create 64x3 and 256x4, sf_fourier_render_create 64, sf_wavelet_render_create 64x3 (H = 30);
+    at 16 bits per sample sf_render16 on the 64x3 handle and sf_wavelet_render16 of a pixel window whose coefficient
+    window starts inside the grid and is narrower than it (golden: the library before the passes shared one chunk loop)
   Feathermap: an attached 64x3 handle, with one sf_adam_step after the two passes
 
 One more case runs with profiling off: sf_step with three learning rates and want_loss on a WaveletSiren 64x3 handle at

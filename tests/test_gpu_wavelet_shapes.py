@@ -1,6 +1,6 @@
 """WaveletSiren at the shapes test_gpu_wavelet.py leaves out, against fp64, a rounding model and the reference.
 
-Every sub-network kernel path a WaveletSiren reaches runs here with its dL/dout injected from outside (ext_dout): widths
+Every sub-network kernel path a WaveletSiren reaches runs here with its dL/dout injected from outside (k_wv_adjoint): widths
 32 (k_fwd<32>, one partial tile), 64 at depth 2 (layer 1 is both the last layer and the layer-0 re-derivation layer), 128
 and 256 with a sine output layer (outermost_linear=False), 256 at depth 2 (k_fwd<256>) and at depth >= 3 (k_fwd_pipe),
 Small_Dense 181 zero-padded to 256, depth 16, first / hidden omega 30 / 50, images of 2 x 2 (n = 3 > H: Cb / Cr
