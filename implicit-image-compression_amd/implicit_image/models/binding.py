@@ -10,8 +10,9 @@ A subclass supplies `cfg`, `_param_list()`, `_layer_fans()`, `_engine_width`, `_
 row_end, device)` and, for `make decode`, `_new_render_engine(rows, cols, device, side)`: the inference-only handle from the
 same `cfg`, a render call of which draws up to rows x cols samples (side: the whole picture's, for WaveletSiren), and which
 `_load_render_engine(eng)` fills.  What else differs goes into the small hooks below.  Consumers (EngineAdam, train_epoch,
-Masking, KmeansQuant, decode) use `bound_engine`, `register_optimizer`, `mask_unsupported`, the two callback lists,
-`_padded`, `engine_flat` and the two render hooks.
+train_steps, Masking, KmeansQuant, decode) use the public names alone: `bound_engine`, `register_optimizer`, `mask_unsupported`,
+the two callback lists, `state_is_live`, `adam_moments`, the hooks around the optimiser's device step, `download_grads`,
+`set_engine_masks`, `engine_flat` and the two render hooks.  Which layout a model runs in (`_padded`) is read in this file only.
 """
 import weakref
 from typing import Optional
@@ -56,6 +57,27 @@ class EngineBound(nn.Module):
     def register_optimizer(self, optim):
         """`optim` (an EngineAdam on this model) is rebound to every handle engine() re-makes"""
         self._engine_optims.add(optim)
+
+    @property
+    def state_is_live(self) -> bool:
+        """are the Parameters, their .grad and the Adam moments zero-copy views of the handle's vectors (a padded width: no)"""
+        return not self._padded
+
+    def adam_moments(self):
+        """[(exp_avg, exp_avg_sq)] per parameter of `_param_list()`, as an optimiser holds them: live slices, else logical clones"""
+        pairs = zip(self._state_slices("exp_avg"), self._state_slices("exp_avg_sq"))
+        return [(m.clone(), v.clone()) if self._padded else (m, v) for m, v in pairs]
+
+    def before_optimizer_step(self, take_moments):
+        """The two hooks around an optimiser's device step; `take_moments(eng, again=False)` makes it hold adam_moments(), once
+        per handle unless `again`.  Live state is bound before; a padded width gathers parameters and fresh clones after."""
+        if not self._padded:
+            take_moments(self._engine)
+
+    def after_optimizer_step(self, take_moments):
+        if self._padded:
+            self.download_params()
+            take_moments(self._engine, again=True)
 
     def set_scratch_format(self, fmt: int):
         """sf_config.scratch_format of the engine (0 auto / 8 / 12 / 16); a live engine of another format is rebuilt on
@@ -113,11 +135,9 @@ class EngineBound(nn.Module):
             self._engine_key, self._grid_key, self._target_key = key, None, None
             self._carry_in(new, carry)
             for opt in list(self._engine_optims):
-                opt._bound = None
-                if not self._padded:
-                    if self._SYNC_PER_OPTIM:
-                        self._sync_to_engine()
-                    opt._bind_state(new)
+                if self._SYNC_PER_OPTIM and not self._padded:
+                    self._sync_to_engine()
+                opt.handle_changed()
         eng = self._engine
         gkey = (grid.data_ptr(), tuple(grid.shape))
         if self._grid_key != gkey:
@@ -220,9 +240,12 @@ class EngineBound(nn.Module):
         flat[self._padded_index(device)] = logical.to(device).float()
         return flat
 
-    def _gather_from_engine(self, which: str):
-        """padded widths only: logical slices of an engine state vector ('params' | 'grads' | 'exp_avg' | ...)"""
-        flat = self._engine.view(which)[self._padded_index(self._engine.device)]
+    def _state_slices(self, which: str):
+        """an engine state vector ('params' | 'grads' | 'exp_avg' | ...) as one tensor per parameter of `_param_list()`:
+        views of it when the state is live, slices of one logical gather of it when padded"""
+        flat = self._engine.view(which)
+        if self._padded:
+            flat = flat[self._padded_index(self._engine.device)]
         out, off = [], 0
         for p in self._param_list():
             out.append(flat[off:off + p.numel()].view(p.shape))
@@ -232,23 +255,19 @@ class EngineBound(nn.Module):
     def download_grads(self):
         """after a backward: make `.grad` current (bound views are; a padded width gathers its logical slices)"""
         if self._padded:
-            for p, g in zip(self._param_list(), self._gather_from_engine("grads")):
+            for p, g in zip(self._param_list(), self._state_slices("grads")):
                 p.grad = g.clone()
 
     def download_params(self):
         if self._padded:
-            with torch.no_grad():
-                for p, v in zip(self._param_list(), self._gather_from_engine("params")):
-                    p.data.copy_(v)
+            for p, v in zip(self._param_list(), self._state_slices("params")):
+                p.data.copy_(v)
 
     def set_engine_masks(self, flat_logical: torch.Tensor):
         """0/1 mask per logical parameter element -> engine (scattered into the wider layout when padded)."""
         eng = self._engine
         self._has_engine_mask = True
-        if self._padded:
-            eng.set_masks(self.engine_flat(flat_logical, eng.num_params, eng.device))
-        else:
-            eng.set_masks(flat_logical.contiguous())
+        eng.set_masks(self.engine_flat(flat_logical, eng.num_params, eng.device) if self._padded else flat_logical.contiguous())
 
     # ---- copies ---------------------------------------------------------------------------------
     def _ctor_args(self) -> dict:

@@ -231,19 +231,33 @@ class Masking:
     def step(self, scaler=None):
         """Optimiser step, then masks, then prune-rate decay (core.py:671-702).  `scaler` is accepted
         for signature parity; GradScaler is an exact no-op on the fp32 path."""
-        eng = self.module.bound_engine
-        if eng is not None and self._pushed_engine is not eng:
-            self._push_masks()                  # engine was created after add_module()
+        self.push_masks_once()                  # engine was created after add_module()
         self.optimizer.step()
-        if eng is None or not getattr(self.optimizer, "applies_engine_mask", False):
+        if self.module.bound_engine is None or not getattr(self.optimizer, "applies_engine_mask", False):
             self.apply_mask()                   # otherwise fused into the engine's Adam kernel
         if not self.dense_gradients:
             self.reset_momentum()
-        if self.prune_rate_decay.mode == "cumulative":
-            self.prune_rate_decay.step(self.mask_step, 1 - self.stats.total_density)
-        else:
-            self.prune_rate_decay.step(self.mask_step)
-        self.mask_step += 1
+        self.count_steps(1)
+
+    def push_masks_once(self):
+        """make sure the module's engine, if it has one, holds these masks"""
+        if self._pushed_engine is not self.module.bound_engine:
+            self._push_masks()                  # (which has nothing to do without an engine)
+
+    def count_steps(self, n: int):
+        """what `n` steps leave to do once optimiser and masks are done: prune-rate decay by mode, the step counter"""
+        for _ in range(n):
+            if self.prune_rate_decay.mode == "cumulative":
+                self.prune_rate_decay.step(self.mask_step, 1 - self.stats.total_density)
+            else:
+                self.prune_rate_decay.step(self.mask_step)
+            self.mask_step += 1
+
+    @property
+    def steps_need_no_host(self) -> bool:
+        """may n steps run back to back, count_steps(n) after them: no moment is reset here, no sparsity read, no mask applied"""
+        return bool(self.dense_gradients and self.prune_rate_decay.mode != "cumulative"
+                    and getattr(self.optimizer, "applies_engine_mask", False))
 
     # ---- topology update (core.py:425-464, 250-269, 713-801) ----------------------------------
     def gather_statistics(self):
@@ -318,7 +332,7 @@ class Masking:
         from ... import _engine
         eng = self.module.bound_engine
         if (self.device_update != "auto" or eng is None or os.environ.get("SIREN_FIT_DEVICE_MASK") == "0"
-                or self.module._padded or self.prune_mode != "magnitude"
+                or not self.module.state_is_live or self.prune_mode != "magnitude"
                 or self.growth_mode not in _engine.MASK_GROWTH or self.redistribution_mode not in ("none", "nonzero")
                 or not callable(getattr(eng, "mask_update", None)) or not _engine.has_mask_update(eng.lib)):
             return None

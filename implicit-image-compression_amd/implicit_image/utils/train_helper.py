@@ -9,6 +9,7 @@
 One `train_epoch` is one full-batch fit step executed by the HIP engine: forward + MSE + backward
 (sf_forward_backward) and Adam(+mask) (sf_adam_step through the optimiser facade).
 """
+import ctypes
 import math
 from typing import Dict, Tuple
 
@@ -40,44 +41,43 @@ class EngineAdam(Optimizer):
         self._bound = None
         model.register_optimizer(self)        # engine() rebinds it when it re-creates the handle
 
-    def _bind_state(self, eng):
-        if self.model._padded:     # padded widths: logical copies, refreshed after every step
-            for p, m, v in zip(self.model._param_list(), self.model._gather_from_engine("exp_avg"),
-                               self.model._gather_from_engine("exp_avg_sq")):
-                st = self.state[p]
-                st.setdefault("step", torch.tensor(0.0))
-                st["exp_avg"], st["exp_avg_sq"] = m.clone(), v.clone()
-            return
-        if self._bound is eng:
-            return
-        m, v = eng.view("exp_avg"), eng.view("exp_avg_sq")
-        off = 0
+    def _bind_state(self, eng, again=False):
+        """state[p]["exp_avg" / "exp_avg_sq"]: the model's moments on `eng`, taken once per handle unless `again` (the binding's
+        hooks around the device step say when: models/binding.py)"""
+        if self._bound is not eng or again:
+            for p, (m, v) in zip(self.model._param_list(), self.model.adam_moments()):
+                self.state[p].setdefault("step", torch.tensor(0.0))
+                self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"] = m, v
+            self._bound = eng
+
+    def handle_changed(self):
+        """the model's engine() re-made its handle: what is held belongs to the old one"""
+        self._bound = None
+        self.prepare()
+
+    def prepare(self):
+        """the binding's share before the device step(s) -> the handle they run on"""
+        eng = self.model.bound_engine
+        if eng is None:
+            raise RuntimeError("EngineAdam.step() before any forward/backward: the engine is created by train_epoch")
+        self.model.before_optimizer_step(self._bind_state)
+        return eng
+
+    def count_steps(self, n: int):
+        """the host's bookkeeping of `n` device steps: state[p]["step"], and the mark lr_scheduler.step() looks for"""
+        self._opt_called = True              # (what the scheduler's wrapper around Optimizer.step() records)
         for p in self.model._param_list():
-            n = p.numel()
-            st = self.state[p]
-            st.setdefault("step", torch.tensor(0.0))
-            st["exp_avg"] = m[off:off + n].view(p.shape)
-            st["exp_avg_sq"] = v[off:off + n].view(p.shape)
-            off += n
-        self._bound = eng
+            self.state[p]["step"] += n
 
     def zero_grad(self, set_to_none: bool = True):
         return None
 
     @torch.no_grad()
     def step(self, closure=None):
-        eng = self.model.bound_engine
-        if eng is None:
-            raise RuntimeError("EngineAdam.step() before any forward/backward: the engine is created by train_epoch")
-        if not self.model._padded:
-            self._bind_state(eng)
+        eng = self.prepare()
         eng.adam_step(float(self.param_groups[0]["lr"]))
-        if self.model._padded:
-            self.model.download_params()
-            self._bind_state(eng)
-        for p in self.model._param_list():
-            self.state[p]["step"] += 1
-        return None
+        self.model.after_optimizer_step(self._bind_state)
+        self.count_steps(1)
 
 
 def get_device(device_str: str) -> torch.device:
@@ -155,7 +155,8 @@ def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
     optim.zero_grad()
     eng = model.engine(grid, img)
     sse = eng.forward_backward(sync=True)
-    loss = sse / (img.shape[0] * img.shape[1] * img.shape[2])
+    # a float's value, as `.item()` of the reference's float32 loss is and as sf_step reports a step's: (float)(sse / n)
+    loss = ctypes.c_float(sse / (img.shape[0] * img.shape[1] * img.shape[2])).value
     model.download_grads()             # no-op unless the width is zero-padded
     for cb in list(model.post_backward_callbacks):
         cb()
@@ -181,30 +182,25 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     mask: Masking = kwargs.get("mask")
     lr_scheduler = kwargs.get("lr_scheduler")
     pbar = kwargs.get("pbar")
-    bulk = (n > 1 and isinstance(optim, EngineAdam) and not model._padded and not model.post_backward_callbacks
-            and kwargs.get("criterion", F.mse_loss) is F.mse_loss and kwargs.get("preconditioner") is None
-            and (mask is None or (mask.dense_gradients and mask.prune_rate_decay.mode != "cumulative"
-                                  and getattr(optim, "applies_engine_mask", False))))
+    bulk = (n > 1 and model.state_is_live and not model.post_backward_callbacks and isinstance(optim, EngineAdam)
+            and (mask is None or mask.steps_need_no_host)
+            and kwargs.get("criterion", F.mse_loss) is F.mse_loss and kwargs.get("preconditioner") is None)
     if not bulk:
         return [train_epoch(model, optim, grid, img, **kwargs) for _ in range(n)]
     model.train()
-    eng = model.engine(grid, img)
-    optim._bind_state(eng)
-    if mask is not None and mask._pushed_engine is not eng:
-        mask._push_masks()
+    model.engine(grid, img)
+    eng = optim.prepare()
+    if mask is not None:
+        mask.push_masks_once()
+    optim.count_steps(n)                     # (first: the scheduler looks for the optimiser's mark at its first step)
     lrs = []
     for _ in range(n):                       # the schedule is host-side bookkeeping: run it ahead
         lrs.append(float(optim.param_groups[0]["lr"]))
         if lr_scheduler:
-            optim._opt_called = True         # what the scheduler's wrapper around Optimizer.step() records
             lr_scheduler.step()
     losses = eng.step(lrs, want_loss=True)
-    for p in model._param_list():
-        optim.state[p]["step"] += n
     if mask is not None:
-        for _ in range(n):                   # prune-rate decay + step counter of Masking.step (core.py:690-702)
-            mask.prune_rate_decay.step(mask.mask_step)
-            mask.mask_step += 1
+        mask.count_steps(n)
     if pbar:
         pbar.update(n)
     return losses

@@ -296,5 +296,54 @@ def case_binding_trace():
     return res
 
 
+def case_step_paths():
+    """train_steps(n = 4) on a Siren against four train_epoch calls on a deep copy of it made before the first step, both under
+    lr 3e-4 with StepLR(2, 0.5), at width 32 (live state) and 20 (padded to 32), without masks and under RigL at density 0.5
+    with dense and with sparse gradients: everything a step leaves behind on either side, and which calls on a handle ran"""
+    from implicit_image import _engine
+    from implicit_image.models.siren import Siren
+    from implicit_image.utils.train_helper import EngineAdam, setup_mask, train_epoch, train_steps
+    torch.cuda.init()
+    ran = {"step": 0, "forward_backward": 0}
+    for name in ran:
+        def counted(self, *args, _name=name, _plain=getattr(_engine.SirenEngine, name), **kwargs):
+            ran[_name] += 1
+            return _plain(self, *args, **kwargs)
+        setattr(_engine.SirenEngine, name, counted)
+    grid, img = data(16, 16)
+    masks = {"none": None, "dense": RIGL, "sparse": Cfg(RIGL, dense_gradients=False)}
+    res = {}
+    for hidden in (32, 20):
+        for tag, mcfg in masks.items():
+            torch.manual_seed(0)
+            first = Siren(depth=3, hidden_size=hidden).cuda()
+            sides = []
+            for m in (first, copy.deepcopy(first)):
+                torch.manual_seed(1)                             # the masks' initial draw: the same on both sides
+                opt = EngineAdam(m, lr=3e-4)
+                sched = torch.optim.lr_scheduler.StepLR(opt, 2, gamma=0.5)
+                sides.append((m, opt, sched, setup_mask(m, opt, mcfg) if mcfg else None))
+            out, calls_of = [], []
+            for bulk, (m, opt, sched, mask) in zip((True, False), sides):
+                before = dict(ran)
+                if bulk:
+                    losses = train_steps(m, opt, grid, img, 4, lr_scheduler=sched, mask=mask)
+                else:
+                    losses = [train_epoch(m, opt, grid, img, lr_scheduler=sched, mask=mask) for _ in range(4)]
+                torch.cuda.synchronize()
+                calls_of.append({k: ran[k] - before[k] for k in ran})
+                out.append({"losses": [float(x) for x in losses], "optim_step": [float(opt.state[p]["step"]) for p in m._param_list()],
+                            "lr": float(opt.param_groups[0]["lr"]), "last_epoch": int(sched.last_epoch),
+                            "mask_step": None if mask is None else int(mask.mask_step),
+                            "prune_rate": None if mask is None else float(mask.prune_rate)})
+            (a, _, _, ka), (b, _, _, kb) = sides
+            res[f"{hidden}_{tag}"] = {
+                "live": bool(a.state_is_live), "train_steps": out[0], "train_epochs": out[1], "calls": calls_of,
+                "params_equal": [bool(torch.equal(p.data, q.data)) for p, q in zip(a._param_list(), b._param_list())],
+                "masks_equal": ka is None or all(bool(torch.equal(ka.mask_dict[n], kb.mask_dict[n])) for n in ka.mask_dict),
+                "density": None if ka is None else float(ka.flat_mask().mean().item())}
+    return res
+
+
 if __name__ == "__main__":
-    child_main({"binding_trace": case_binding_trace})
+    child_main({"binding_trace": case_binding_trace, "step_paths": case_step_paths})

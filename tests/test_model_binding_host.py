@@ -1,8 +1,12 @@
 """Host tests of the model <-> engine binding (implicit_image/models/binding.py): the class relations, the binding state in
-one place, the one __deepcopy__ and the one logical -> engine-flat scatter.  No GPU."""
+one place, who may read it, a step's bookkeeping (n steps at once against n times one), the one __deepcopy__ and the one
+logical -> engine-flat scatter.  No GPU."""
 import copy
 import os
 import re
+import warnings
+from collections import defaultdict
+from types import SimpleNamespace
 
 import pytest
 import torch
@@ -88,6 +92,112 @@ def test_binding_state_is_written_in_one_file_only():
         txt = open(os.path.join(PKG, rel)).read()
         assert not guess.search(txt), (rel, guess.search(txt).group(0))
         assert "_engine_optims" not in txt and 'hasattr(model, "set_scratch_format")' not in txt, rel
+
+
+def test_consumers_do_not_read_the_binding_state_nor_each_others():
+    """the consumers ask the binding's public surface (state_is_live, adam_moments, the step hooks), the step drivers ask
+    Masking's (push_masks_once, count_steps), and the binding reaches an optimiser through handle_changed() alone"""
+    binding = ["._padded", "._pad_index", "._padded_index", "._gather_from_engine", "._state_slices"]
+    masking = ["._pushed_engine", "._push_masks"]                      # Masking's own: its module alone may name them
+    core = os.path.join("pipeline", "masking", "core.py")
+    for rel in (os.path.join("utils", "train_helper.py"), core, os.path.join("pipeline", "quant", "kmeans.py"), "decode.py", "fit.py"):
+        txt = open(os.path.join(PKG, rel)).read()
+        for name in binding + ([] if rel == core else masking):
+            assert name not in txt, (rel, name)
+    txt = open(os.path.join(PKG, "models", "binding.py")).read()
+    assert "._bound" not in txt and "._bind_state" not in txt
+
+
+# ---- a step's bookkeeping: n at once == n times one == n steps ---------------------------------------------------------
+class Cfg(dict):
+    __getattr__ = dict.get
+
+
+RIGL = dict(name="RigL", density=0.5, sparse_init="erdos-renyi-kernel", dense_gradients=True, growth_mode="absolute-gradient",
+            prune_mode="magnitude", redistribution_mode="none", dense=False, prune_rate=0.3, end_when=3)      # (frozen from step 3 on)
+DECAYS = {"cosine": RIGL, "linear": RIGL,
+          "magnitude-prune": dict(name="Pruning", density=1.0, sparse_init="random", final_density=0.5, dense_gradients=True,
+                                  growth_mode="none", prune_mode="global-magnitude", redistribution_mode="none", dense=False,
+                                  start_when=2, end_when=60, interval=1)}
+
+
+def test_every_decay_schedule_is_covered():
+    from implicit_image.pipeline.masking import decay_registry
+    assert sorted(DECAYS) == sorted(decay_registry)
+
+
+@pytest.mark.parametrize("schedule", sorted(DECAYS))
+def test_masking_counts_n_steps_as_n_times_one_and_as_n_step_calls(schedule):
+    from implicit_image.utils.train_helper import setup_mask
+    torch.manual_seed(0)
+    stub = SimpleNamespace(state=defaultdict(dict), step=lambda: None)
+    a = setup_mask(Siren(depth=3, hidden_size=32), stub, Cfg(DECAYS[schedule], decay_schedule=schedule))
+    b, c = copy.deepcopy(a), copy.deepcopy(a)
+    cumulative = schedule == "magnitude-prune"
+    assert a.prune_rate_decay.mode == ("cumulative" if cumulative else "current") and a.steps_need_no_host is False
+    stub.applies_engine_mask = True                                 # (b and c keep the stub without it)
+    assert a.steps_need_no_host is not cumulative
+    a.dense_gradients = False
+    assert a.steps_need_no_host is False
+    a.count_steps(5)
+    rates = []
+    for _ in range(5):
+        b.count_steps(1)
+        c.step()
+        rates.append(c.prune_rate)
+    assert a.mask_step == b.mask_step == c.mask_step == 5
+    assert a.prune_rate == b.prune_rate == c.prune_rate
+    assert vars(a.prune_rate_decay) == vars(b.prune_rate_decay) == vars(c.prune_rate_decay)
+    assert len(set(rates)) > 1                                      # the schedule did move in these five steps
+
+
+class HostHandle:
+    """what EngineAdam asks of a handle, on CPU vectors"""
+    device = torch.device("cpu")
+
+    def __init__(self, num_params):
+        self.vecs = {w: torch.zeros(num_params) for w in ("params", "exp_avg", "exp_avg_sq")}
+        self.lrs = []
+
+    def view(self, which):
+        return self.vecs[which]
+
+    def adam_step(self, lr):
+        self.lrs.append(lr)
+
+
+@pytest.mark.parametrize("hidden", [32, 20], ids=["live", "padded"])
+def test_engine_adam_counts_n_steps_as_n_times_one_and_as_n_step_calls(hidden):
+    from implicit_image.utils.train_helper import EngineAdam
+
+    def make():
+        torch.manual_seed(0)
+        m = Siren(depth=3, hidden_size=hidden)
+        opt = EngineAdam(m, lr=3e-4)
+        m._engine = HostHandle(int(m._padded_index(torch.device("cpu")).max()) + 1)
+        return m, opt, torch.optim.lr_scheduler.StepLR(opt, 2, gamma=0.5)
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        (ma, a, sa), (mb, b, sb), (mc, c, sc) = make(), make(), make()
+        assert ma.state_is_live is (hidden == 32)
+        a._bind_state(ma.bound_engine)
+        a.count_steps(5)
+        b._bind_state(mb.bound_engine)
+        for _ in range(5):
+            sa.step()
+            b.count_steps(1)
+            sb.step()
+            c.step()
+            sc.step()
+    assert [str(w.message) for w in seen] == []
+    for m, opt, sched in ((ma, a, sa), (mb, b, sb), (mc, c, sc)):
+        assert [float(opt.state[p]["step"]) for p in m._param_list()] == [5.0] * 6
+        assert opt.param_groups[0]["lr"] == 3e-4 * 0.5 * 0.5 and sched.last_epoch == 5
+        for p, (mom, var) in zip(m._param_list(), m.adam_moments()):
+            st = opt.state[p]
+            assert st["exp_avg"].shape == st["exp_avg_sq"].shape == p.shape
+            assert (st["exp_avg"].data_ptr() == mom.data_ptr() and st["exp_avg_sq"].data_ptr() == var.data_ptr()) is m.state_is_live
+    assert mc.bound_engine.lrs == [3e-4, 3e-4, 1.5e-4, 1.5e-4, 7.5e-5]
 
 
 # ---- __deepcopy__ -----------------------------------------------------------------------------------------------------
