@@ -1,19 +1,10 @@
-import os, sys, time, json, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
-from implicit_image.models import Siren
+"""SIREN 256x8 at SIZE^2 (default 2048): step time and per-kernel ms against the pixel chunk size."""
+import sys
+from _common import kernel_table, timed_steps, timing_engine
 H = W = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
-torch.manual_seed(0)
-init = torch.cat([q.detach().reshape(-1) for q in Siren(depth=8, hidden_size=256, first_omega_0=50., hidden_omega_0=30.).parameters()]).cuda()
-img = torch.rand(H, W, 3, device="cuda")
 for chunk in [16384, 32768, 65536, 131072, 262144, 1 << 20, 1 << 22]:
     if chunk > H * W: break
-    eng = SirenEngine(H, W, 256, 8, compute_dtype="f16", chunk_pixels=chunk)
-    eng.set_params(init); eng.set_coords(torch.linspace(0, 1, H).cuda(), torch.linspace(0, 1, W).cuda()); eng.set_target(img)
-    eng.step([3e-4] * 2); torch.cuda.synchronize()
-    eng.profile(True); eng.profile_reset()
-    t0 = time.perf_counter(); eng.step([3e-4] * 4); torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 4
-    rep = eng.profile_report()
-    print(f"chunk {chunk:8d}: {dt*1e3:8.2f} ms/step {H*W/dt/1e6:7.1f} Mpix/s | " + " ".join(f"{k[2:]}={v['total_ms']/4:.2f}" for k, v in rep.items() if v['launches'] and v['total_ms']/4 > 0.05), flush=True)
+    eng = timing_engine(H, 256, 8, chunk=chunk)
+    dt = timed_steps(eng, 4, 2, profile=True)
+    print(f"chunk {chunk:8d}: {dt*1e3:8.2f} ms/step {H*W/dt/1e6:7.1f} Mpix/s | " + " ".join(f"{k[2:]}={v['total_ms']:.2f}" for k, v in kernel_table(eng, 4).items() if v['total_ms'] > 0.05), flush=True)
     eng.close()

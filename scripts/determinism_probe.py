@@ -1,8 +1,7 @@
 """Two forward_backward passes from the same state: per-layer bitwise equality of the gradients (race detector)."""
-import os, sys, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import sys, torch
+import _common  # noqa: F401  (path setup)
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so
 from bench import device_image
 fmts = [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "12,8,16").split(",")]
@@ -10,10 +9,7 @@ sizes = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else "1024,2048,4096"
 hid, dep = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (256, 8)
 for fmt in fmts:
     for H in sizes:
-        p = so.siren_init(hid, dep, seed=0)
-        eng = SirenEngine(H, H, hid, dep, compute_dtype="f16", scratch_format=fmt)
-        eng.set_coords(torch.linspace(0, 1, H).cuda(), torch.linspace(0, 1, H).cuda())
-        eng.set_params(torch.tensor(so.flatten(p)).cuda())
+        eng = siren_engine(H, H, hid, dep, "f16", so.siren_init(hid, dep, seed=0), scratch_format=fmt)
         eng.set_target(device_image(H, H, torch.device("cuda")))
         gs, hs = [], []
         for _ in range(3):

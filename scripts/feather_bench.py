@@ -8,19 +8,15 @@ Writes profiles/feather_bench.json and prints it.
 import argparse
 import json
 import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import torch
+import torch.nn.functional as F
+from _common import ROOT, time_loop
 
-from implicit_image.data import get_grid, synthetic_image  # noqa: E402
-from implicit_image.models.siren import Siren  # noqa: E402
-from implicit_image.pipeline.feathermap import FeatherNet  # noqa: E402
-from implicit_image.utils.train_helper import EngineAdam  # noqa: E402
+from implicit_image.data import get_grid, synthetic_image
+from implicit_image.models.siren import Siren
+from implicit_image.pipeline.feathermap import FeatherNet
+from implicit_image.utils.train_helper import EngineAdam
 
 SHAPES = [(256, 8, 4096, False), (1024, 12, 1024, False), (128, 8, 256, True)]   # hidden, depth, image edge, torch eager
 KERNELS = ("k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat")
@@ -38,11 +34,7 @@ def time_engine(hidden, depth, S, feather, steps, grid, img):
     EngineAdam(m, lr=3e-4)
     eng = m.engine(grid, img)
     eng.step([3e-4] * 2)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    eng.step([3e-4] * steps)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / steps
+    ms = time_loop(lambda: eng.step([3e-4] * steps), 1, "host") / steps
     eng.profile(True)
     eng.profile_reset()
     eng.step([3e-4] * 2)
@@ -70,12 +62,7 @@ def time_torch(hidden, depth, steps, grid, img):
         opt.step()
     for _ in range(2):
         step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
+    return time_loop(step, steps, "host")
 
 
 def main():

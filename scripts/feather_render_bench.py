@@ -20,7 +20,7 @@ import os
 
 import torch
 
-from render_bench_common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
+from _common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
 
 HIDDEN, DEPTH, DENSITY = 128, 8, 0.2
 N, M = 316, 32

@@ -9,18 +9,14 @@ FLOPs per pixel-iteration (~6.3e5 at 128 x 8 / map 256): forward 2 P_w, backward
 import argparse
 import json
 import math
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd")):
-    sys.path.insert(0, p)
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import torch
+import torch.nn.functional as F
+from _common import time_loop
 
-from implicit_image.data import get_grid, synthetic_image  # noqa: E402
-from implicit_image.models import registry  # noqa: E402
+from implicit_image.data import get_grid, synthetic_image
+from implicit_image.models import registry
 
 CFG = dict(depth=8, hidden_size=128, map_size=256, map_scale=16.0)
 PEAK = 2.5e15   # dense fp16 MFMA, MI355X
@@ -39,13 +35,7 @@ def time_engine(S, steps, warm=2):
     grid, img = get_grid(S, S).cuda(), synthetic_image(S, S, seed=5).cuda()
     eng = m.engine(grid, img)
     eng.step([3e-4] * warm)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    eng.step([3e-4] * steps)
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / steps
+    ms = time_loop(lambda: eng.step([3e-4] * steps), 1, "event") / steps
     eng.profile(True)
     eng.profile_reset()
     eng.step([3e-4] * 2)
@@ -93,14 +83,7 @@ def time_torch(S, steps, warm=2):
 
     for _ in range(warm):
         step()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        step()
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / steps
+    ms = time_loop(step, steps, "event")
     del m, opt, grid, img
     torch.cuda.empty_cache()
     return ms

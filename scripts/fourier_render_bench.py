@@ -22,7 +22,7 @@ import os
 
 import torch
 
-from render_bench_common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
+from _common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
 
 YAML = dict(depth=8, hidden_size=128, map_size=256, map_scale=16.0)
 N_LINEAR = YAML["depth"] - 1

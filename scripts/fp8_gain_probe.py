@@ -1,18 +1,15 @@
 """Does the weight norm predict the layer-to-layer growth of the hidden deltas?  gain_l = omega * sqrt(0.5 * ||W_l||_F^2 / n_in)
 (independent delta components) against the measured rms ratio of the fp8 deltas, during a fit of the non-smooth image."""
-import os, sys, math
+import sys, math
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import _common  # noqa: F401  (path setup)
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so
 kind = sys.argv[1] if len(sys.argv) > 1 else "nonsmooth"
 H = W = 256
 img = so.nonsmooth_image(H, W) if kind == "nonsmooth" else so.synthetic_image(H, W, seed=5)
 p = so.siren_init(256, 8, seed=0)
-eng = SirenEngine(H, W, 256, 8, compute_dtype="f16", scratch_format=8)
-gh, gw = so.grid_vectors(H, W)
-eng.set_coords(gh.cuda(), gw.cuda()); eng.set_params(torch.tensor(so.flatten(p)).cuda()); eng.set_target(img.cuda().contiguous())
+eng = siren_engine(H, W, 256, 8, "f16", p, img, scratch_format=8)
 lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().cuda()
 done = 0
 for mk in (0, 50, 100, 200, 400, 1000):

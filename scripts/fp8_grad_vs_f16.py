@@ -1,18 +1,11 @@
 """Per-layer accuracy of the format-8 gradient against the format-16 one on the same weights, over the first steps of the non-smooth fit\n(evidence that the per-layer fp8 scales leave the early gradients as accurate as the single scale did: <= 1.3 % per layer)."""
-import os, sys, math
-import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import numpy as np
+import _common  # noqa: F401  (path setup)
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so
 H = W = 256
 img = so.nonsmooth_image(H, W); p = so.siren_init(256, 8, seed=0)
-gh, gw = so.grid_vectors(H, W)
-def mk(fmt):
-    e = SirenEngine(H, W, 256, 8, compute_dtype="f16", scratch_format=fmt)
-    e.set_coords(gh.cuda(), gw.cuda()); e.set_params(torch.tensor(so.flatten(p)).cuda()); e.set_target(img.cuda().contiguous())
-    return e
-e16, e8 = mk(16), mk(8)
+e16, e8 = (siren_engine(H, W, 256, 8, "f16", p, img, scratch_format=fmt) for fmt in (16, 8))
 for it in range(0, 12):
     e16.forward_backward(); e8.set_params(e16.get_params()); e8.forward_backward()
     g16, g8 = e16.get_grads().cpu().numpy(), e8.get_grads().cpu().numpy()

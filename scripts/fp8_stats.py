@@ -1,11 +1,10 @@
 """Per-layer statistics of the fp8 (e4m3) hidden deltas of a format-8 fit: rms in fp8 units, share of saturated (+-448), zero
 and subnormal (< 2^-6) bytes - evidence for the choice of the per-chunk scale target (kFp8Target).
 usage: python scripts/fp8_stats.py [smooth|nonsmooth] [steps,steps,...]"""
-import os, sys, math
-import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import sys
+import torch
+import _common  # noqa: F401  (path setup)
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so
 
 kind = sys.argv[1] if len(sys.argv) > 1 else "nonsmooth"
@@ -13,9 +12,7 @@ marks = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else "0,100,400,1000"
 H = W = 256
 img = so.nonsmooth_image(H, W) if kind == "nonsmooth" else so.synthetic_image(H, W, seed=5)
 p = so.siren_init(256, 8, seed=0)
-eng = SirenEngine(H, W, 256, 8, compute_dtype="f16", scratch_format=8)
-gh, gw = so.grid_vectors(H, W)
-eng.set_coords(gh.cuda(), gw.cuda()); eng.set_params(torch.tensor(so.flatten(p)).cuda()); eng.set_target(img.cuda().contiguous())
+eng = siren_engine(H, W, 256, 8, "f16", p, img, scratch_format=8)
 lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().cuda()
 done = 0
 print(kind)

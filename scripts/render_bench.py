@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from render_bench_common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
+from _common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
 
 MODELS = [(256, 8), (128, 8)]
 

@@ -1,8 +1,7 @@
 """Engine (8-bit and 16-bit scratch) vs its numerics model vs the fp32 oracle: relative L2 gradient errors."""
-import os, sys, numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import numpy as np
+import _common  # noqa: F401  (path setup)
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so, engine_model as em
 
 def rel(a, b): return float(np.linalg.norm(a - b) / np.linalg.norm(b))
@@ -16,9 +15,7 @@ for (H, W, hid, dep, seed) in [(32, 40, 64, 4, 0), (32, 40, 256, 8, 0), (48, 56,
     g32 = so.flatten(g32)
     row = [f"{H}x{W} {hid}x{dep}"]
     for scratch in (16, 12, 8):
-        eng = SirenEngine(H, W, hid, dep, compute_dtype="f16", scratch_format=scratch)
-        gh, gw = so.grid_vectors(H, W)
-        eng.set_coords(gh.cuda(), gw.cuda()); eng.set_params(torch.tensor(so.flatten(p)).cuda()); eng.set_target(img.cuda().contiguous())
+        eng = siren_engine(H, W, hid, dep, "f16", p, img, scratch_format=scratch)
         sse_e = eng.forward_backward()
         g = eng.get_grads().cpu().numpy()
         _, sse_m, gm, _ = em.loss_and_grads(p, grid, img, scratch=scratch)   # (12: modelled as 16 below, phases differ)

@@ -1,18 +1,12 @@
 """8-bit vs 16-bit scratch on large grids: gradient agreement (relative L2, per layer) and loss curves."""
-import os, sys, numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import torch
+import _common  # noqa: F401  (path setup)
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so
-sys.path.insert(0, ROOT)
 from bench import device_image
 
 def mk(H, W, scratch, chunk=0):
-    p = so.siren_init(256, 8, seed=0)
-    eng = SirenEngine(H, W, 256, 8, compute_dtype="f16", scratch_format=scratch, chunk_pixels=chunk)
-    eng.set_coords(torch.linspace(0, 1, H).cuda(), torch.linspace(0, 1, W).cuda())
-    eng.set_params(torch.tensor(so.flatten(p)).cuda())
-    return eng
+    return siren_engine(H, W, 256, 8, "f16", so.siren_init(256, 8, seed=0), scratch_format=scratch, chunk_pixels=chunk)
 
 for (H, chunk) in [(1024, 0), (2048, 0), (2048, 1 << 20), (4096, 0)]:
     img = device_image(H, H, torch.device("cuda"))

@@ -1,7 +1,6 @@
-import os, sys, numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import os, numpy as np, torch
+from _common import ROOT
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so
 d = np.load(os.path.join(ROOT, "tests/golden/rigl_256x8_48.npz"))
 p = so.siren_init(256, 8, seed=0)
@@ -13,9 +12,7 @@ img = torch.tensor(d["img"]); H = W = 48
 grid = so.get_grid(H, W)
 _, _, g32 = so.loss_and_grads(p, grid, img)
 for fmt in (16, 12, 8):
-    eng = SirenEngine(H, W, 256, 8, compute_dtype="f16", scratch_format=fmt)
-    gh, gw = so.grid_vectors(H, W)
-    eng.set_coords(gh.cuda(), gw.cuda()); eng.set_params(torch.tensor(so.flatten(p)).cuda()); eng.set_target(img.cuda().contiguous())
+    eng = siren_engine(H, W, 256, 8, "f16", p, img, scratch_format=fmt)
     eng.forward_backward()
     g = eng.get_grads().cpu()
     w_off, _ = eng.param_offsets(7)

@@ -10,15 +10,10 @@ fp16-autocast eager of the same model (the tests' torch mirror, tests/_wavelet_r
 import argparse
 import json
 import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "implicit-image-compression_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
-
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import torch
+import torch.nn.functional as F
+from _common import ROOT, time_loop
 
 YAML = dict(depth=8, hidden_size=128, wavelet_levels=1, first_omega_0=50.0, hidden_omega_0=30.0, outermost_linear=True)
 
@@ -32,11 +27,11 @@ def engine_leg(S, steps, warmup):
     m = registry["wavelet_siren"](**YAML).cuda()
     optim, sched = get_optimizer_lr_scheduler(m, dict(name="adam", lr=3e-4))
     train_steps(m, optim, grid, img, warmup, lr_scheduler=sched)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    losses = train_steps(m, optim, grid, img, steps, lr_scheduler=sched)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
+    losses = []
+
+    def timed_call():
+        losses[:] = train_steps(m, optim, grid, img, steps, lr_scheduler=sched)
+    ms = time_loop(timed_call, 1, "host") / steps
     eng = m.engine(grid, img)
     eng.profile(True)
     eng.profile_reset()
@@ -77,12 +72,7 @@ def torch_leg(S, steps, warmup, autocast):
 
     for _ in range(warmup):
         step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
+    ms = time_loop(step, steps, "host")
     del flat, opt
     torch.cuda.empty_cache()
     return {"ms_per_step": ms}

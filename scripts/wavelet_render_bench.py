@@ -23,7 +23,7 @@ import os
 
 import torch
 
-from render_bench_common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
+from _common import ROOT, alternate, device_note, handle_memory, print_handle_bytes, stats
 
 YAML = dict(depth=8, hidden_size=128, wavelet_levels=1, first_omega_0=50.0, hidden_omega_0=30.0, outermost_linear=True)
 

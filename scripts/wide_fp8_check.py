@@ -1,16 +1,12 @@
 """Wide path (hidden 512 / 1024) with fp8 deltas (scratch_format 8) against formats 12 / 16 and the fp32 oracle: per-tensor gradient
 error on small grids, PSNR after 60 steps (the wide parity case), and - optionally - the bench shapes."""
-import os, sys, math
-import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "implicit-image-compression_amd"))
-from implicit_image._engine import SirenEngine
+import math
+import numpy as np
+import _common  # noqa: F401  (path setup)
+from _gpu_fixtures import siren_engine
 from oracle import siren_oracle as so
 def mk(H, W, hidden, depth, p, img, fmt, chunk=0):
-    e = SirenEngine(H, W, hidden, depth, compute_dtype="f16", scratch_format=fmt, chunk_pixels=chunk)
-    gh, gw = so.grid_vectors(H, W)
-    e.set_coords(gh.cuda(), gw.cuda()); e.set_params(torch.tensor(so.flatten(p)).cuda()); e.set_target(img.cuda().contiguous())
-    return e
+    return siren_engine(H, W, hidden, depth, "f16", p, img, scratch_format=fmt, chunk_pixels=chunk)
 for (H, W, hidden, depth, chunk) in [(40, 52, 512, 5, 0), (9, 33, 1024, 3, 0), (48, 48, 1024, 4, 1024), (24, 40, 512, 8, 0), (128, 128, 512, 6, 0)]:
     p = so.siren_init(hidden, depth, seed=3); img = so.synthetic_image(H, W, seed=5); grid = so.get_grid(H, W)
     loss, sse_ref, grads = so.loss_and_grads(p, grid, img); ref = so.flatten(grads)
