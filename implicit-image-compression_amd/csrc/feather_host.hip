@@ -162,6 +162,9 @@ int sf_feather_render_attach(sf_handle* h, int64_t n, int64_t m, int32_t n_layer
     case Model::Wavelet:
       return fail(SF_ERR_INVALID, "sf_feather_render_attach: Feathermap runs on SIREN render handles (sf_render_create) only");
   }
+  if (h->wide)
+    return fail(SF_ERR_INVALID, "sf_feather_render_attach: a wide render handle (sf_wide_render_create) takes dense parameters; "
+                                "the Feathermap render path is built for hidden 32 .. 256 (sf_render_create)");
   if (h->fth.attached) return fail(SF_ERR_INVALID, "sf_feather_render_attach: the handle already has a feather state");
   FthArgs a = zeroed<FthArgs>();
   SF_TRY(feather_geometry(h, "sf_feather_render_attach", n, m, n_layers, logical_out, logical_in, a));

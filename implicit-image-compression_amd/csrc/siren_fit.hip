@@ -85,6 +85,10 @@
     SF_K(k_fwd<256, OpF16, false, false, true>), SF_K(k_fwd<256, OpBF16, false, false, true>),
     SF_K(k_ff_fwd<32, false, true>), SF_K(k_ff_fwd<64, false, true>), SF_K(k_ff_fwd<128, false, true>),
     SF_K(k_ff_fwd<256, false, true>), SF_K(k_fth_mat<false>), SF_K(k_fth_mat<true>),
+    SF_K(k_wlayer0<OpF16, false, true>), SF_K(k_wlayer0<OpBF16, false, true>),
+    SF_K(k_wgemm2<0, OpF16, false, false, false, true>), SF_K(k_wgemm2<0, OpBF16, false, false, false, true>),
+    SF_K(k_wgemm<OpF16, true, 8>), SF_K(k_wgemm<OpF16, true, 16>), SF_K(k_wgemm<OpBF16, true, 8>),
+    SF_K(k_wgemm<OpBF16, true, 16>),
 };
 #undef SF_K
 

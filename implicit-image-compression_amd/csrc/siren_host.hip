@@ -298,8 +298,10 @@ void set_scratch_strides(sf_engine* h) {
 }
 // sf_create and sf_render_create (siren_render.hip): one validation, one geometry; a render handle allocates the forward's
 // inputs only.  sub_network: the handle is one of the two SIRENs of a WaveletSiren handle, which points params / grads / m /
-// v / mask at slices of its own joint vectors - nothing is allocated for them here
-int create_handle(const sf_config* cfg, sf_handle** out, bool render, bool sub_network = false) {
+// v / mask at slices of its own joint vectors - nothing is allocated for them here.  wide_render: the caller is
+// sf_wide_render_create (siren_render.hip), the one creator that takes hidden 512 / 1024 for a render handle: the blocked forward
+// images of the wide path and TWO activation planes, which the layers use in turn
+int create_handle(const sf_config* cfg, sf_handle** out, bool render, bool sub_network = false, bool wide_render = false) {
   auto check = [&](Grid& g) -> int {
     if (cfg->out_features < 1 || cfg->out_features > 3) return fail(SF_ERR_INVALID, "out_features must be 1..3");
     if (cfg->depth < 2 || cfg->depth > 16) return fail(SF_ERR_INVALID, "depth must be 2..16");
@@ -307,7 +309,7 @@ int create_handle(const sf_config* cfg, sf_handle** out, bool render, bool sub_n
         cfg->hidden != 1024)
       return fail(SF_ERR_INVALID, "hidden must be 32, 64, 128, 256, 512 or 1024 in this build");
     if (cfg->hidden > 256 && cfg->depth < 3) return fail(SF_ERR_INVALID, "hidden > 256 needs depth >= 3");
-    if (render && cfg->hidden > 256)
+    if (render && cfg->hidden > 256 && !wide_render)
       return fail(SF_ERR_INVALID, "sf_render_create: the render kernel is not built for the wide path (hidden 512 / 1024): "
                                   "run the model's own forward on the host side");
     if (cfg->compute_dtype != SF_BF16 && cfg->compute_dtype != SF_F16)
@@ -361,7 +363,9 @@ int create_handle(const sf_config* cfg, sf_handle** out, bool render, bool sub_n
     if (cfg->compute_dtype == SF_F16) h->gpre = (float)exp2(ceil(log2((double)cfg->out_features * (double)cfg->height * (double)cfg->width)) + 2.0);
     // chunking
     // default: 4 Mi pixels at width <= 256 (29 GB of scratch at 256x8); the same scratch budget for wider layers
-    const long chunk = chunk_pixels(cfg->chunk_pixels > 0 ? cfg->chunk_pixels : (1L << 22) / (h->wide ? cfg->hidden / 256 : 1), h->npix);
+    // (a wide render handle: 2^18 pixels at 512, 2^17 at 1024 - 256 MiB per activation plane)
+    const long chunk_auto = render && h->wide ? (1L << 18) / (cfg->hidden / 512) : (1L << 22) / (h->wide ? cfg->hidden / 256 : 1);
+    const long chunk = chunk_pixels(cfg->chunk_pixels > 0 ? cfg->chunk_pixels : chunk_auto, h->npix);
     h->chunk_px = chunk;
     const int WD = h->WD, D = h->D;
     // layer stride of the scratch tensors, padded so that the three streams a kernel touches at once are
@@ -371,14 +375,22 @@ int create_handle(const sf_config* cfg, sf_handle** out, bool render, bool sub_n
 
     if (!sub_network) SF_TRY(alloc_state(h, !render));
     SF_TRY(alloc_forward_inputs(h));
-    if (render) return SF_OK;   // parameters, forward weight images, layer-0 table / image, the two coordinate vectors
     const size_t img_elems = (size_t)(D - 2 > 0 ? D - 2 : 1) * WD * WD;
-    SF_TRY(dev_alloc(h, h->wb, img_elems * 2));
-    if (h->wide) {   // blocked images of siren_wide.hip
+    auto alloc_wide_forward = [&]() -> int {   // blocked forward images of siren_wide.hip and the pre-scaled biases
       SF_TRY(dev_alloc(h, h->wf, img_elems * 2));
       SF_TRY(dev_alloc(h, h->wf_last, (size_t)(WD / 16) * 1024));
+      return dev_alloc(h, h->biasw, ((size_t)(D - 2) * WD + 32) * 4);
+    };
+    // a render handle: parameters, forward weight images, layer-0 table / image, the two coordinate vectors; wide: and two
+    // activation planes - layer l reads plane (l - 1) & 1 and writes plane l & 1 (wide_render_chunks, wide_host.hip)
+    if (render) {
+      if (h->wide) { SF_TRY(alloc_wide_forward()); SF_TRY(dev_alloc(h, h->Abuf, (size_t)2 * h->a_stride * 16)); }
+      return SF_OK;
+    }
+    SF_TRY(dev_alloc(h, h->wb, img_elems * 2));
+    if (h->wide) {   // ... and the backward ones
+      SF_TRY(alloc_wide_forward());
       SF_TRY(dev_alloc(h, h->wb_last, (size_t)(WD / 256) * 32 * 1024));
-      SF_TRY(dev_alloc(h, h->biasw, ((size_t)(D - 2) * WD + 32) * 4));
     } else {
       SF_TRY(dev_alloc(h, h->wb_last, (size_t)WD / 32 * 64 * 16));
     }

@@ -182,6 +182,26 @@ int render_any(sf_handle* h, void* out, int bits, float* pred) {
   return render_chunks(h, out, bits, pred);
 }
 
+// sf_wide_render (bits = 8) and sf_wide_render16 (bits = 16): render_any's argument checks for the one kind of handle that
+// sf_wide_render_create makes; any other handle is sent to the entry point that draws it
+int wide_render_any(sf_handle* h, void* out, int bits, float* pred) {
+  const std::string fn = bits == 16 ? "sf_wide_render16" : "sf_wide_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
+  if (!h) return fail(SF_ERR_INVALID, "null argument");
+  if (!out && !pred) return fail(SF_ERR_INVALID, fn + ": " + on + " and pred_dev are both NULL");
+  if (!(h->model == Model::Siren && h->wide && h->render)) {
+    const char* use = h->model == Model::Wavelet ? "sf_wavelet_render draws a WaveletSiren handle"
+                      : h->model == Model::Fourier ? "sf_render draws a FourierNet handle"
+                      : h->wide ? "a training handle of hidden 512 / 1024 (sf_create) evaluates through sf_forward"
+                                : "sf_render draws a SIREN handle of hidden width 32 .. 256";
+    return fail(SF_ERR_INVALID, fn + ": built for the wide render handle of sf_wide_render_create (hidden 512 / 1024); " + use);
+  }
+  if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
+  if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
+  DevGuard dev_guard(h->cfg.device);
+  SF_TRY(refresh_images(h));
+  return wide_render_chunks(h, out, bits, pred);
+}
+
 }  // namespace
 
 extern "C" {
@@ -190,5 +210,16 @@ int sf_render_create(const sf_config* cfg, sf_handle** out) try { return create_
 
 int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try { return render_any(h, rgb8, 8, pred); } SF_CATCH
 int sf_render16(sf_handle* h, uint16_t* rgb16, float* pred) try { return render_any(h, rgb16, 16, pred); } SF_CATCH
+
+int sf_wide_render_create(const sf_config* cfg, sf_handle** out) try {
+  if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if ((cfg->hidden != 512 && cfg->hidden != 1024) || cfg->depth < 3)
+    return fail(SF_ERR_INVALID, "sf_wide_render_create: built for hidden 512 / 1024 with depth >= 3 (the layer-at-a-time kernels); "
+                                "sf_render_create makes the render handle of hidden 32 .. 256");
+  return create_handle(cfg, out, true, false, true);
+} SF_CATCH
+int sf_wide_render(sf_handle* h, uint8_t* rgb8, float* pred) try { return wide_render_any(h, rgb8, 8, pred); } SF_CATCH
+int sf_wide_render16(sf_handle* h, uint16_t* rgb16, float* pred) try { return wide_render_any(h, rgb16, 16, pred); } SF_CATCH
 
 }  // extern "C"

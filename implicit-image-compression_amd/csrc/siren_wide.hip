@@ -11,6 +11,8 @@
 //   k_wgemm     (MODE 1 of the same argument struct) forward last layer + residual/loss: 32 padded output rows, B read from
 //               HBM/L2 into registers two chunks ahead
 //   k_wdw       weight gradient blocks: delta^T * activation, both operands read transposed from an LDS ring
+// Inference (sf_wide_render, wide_host.hip) runs the RENDER forms of k_wlayer0, k_wgemm2<0> and k_wgemm: activations only,
+// through two planes of a chunk, and the prediction / samples from the last layer's epilogue (fwd_render_out, siren_render.hip).
 // Unlike the fused width-256 path, each hidden layer keeps BOTH its phase (unorm16, for cos in the backward)
 // and its activation sin(phase) (16-bit float, the GEMM operand) in HBM: every value is an operand of WD/256
 // workgroups per product, so decoding phases inside the GEMM loops would repeat the transcendental WD/256 times
@@ -87,8 +89,10 @@ struct WL0Args {
 // P8 (scratch_format 12 on the wide path, round 3): the phases are spilled as BYTES, one 1 KiB piece per (pixel block, 32-neuron
 // tile) - byte 8 q + j of lane (h, m) = neuron 32 tile + 16 q + PI(h, j), the layout of the width-256 path - so a wave takes
 // TWO k-steps (one tile): two activation pieces and one phase piece.  a.KS stays the number of 16-neuron k-steps.
-template <typename OP2, bool P8 = false>
+// RENDER (inference only, sf_wide_render): the activation piece alone - nothing reads a phase without a backward, a.P is null.
+template <typename OP2, bool P8 = false, bool RENDER = false>
 __global__ __launch_bounds__(256) void k_wlayer0(WL0Args a) {
+  static_assert(!(RENDER && P8), "a render handle has no phase scratch of any format");
   constexpr int SPW = P8 ? 2 : 1;                      // k-steps per wave
   const long unit = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (unit * SPW >= a.n_pieces) return;
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(256) void k_wlayer0(WL0Args a) {
     if constexpr (P8) {
       pb8[2 * q] = phase_byte4(tv, av);
       pb8[2 * q + 1] = phase_byte4(tv + 4, av + 4);
-    } else {
+    } else if constexpr (!RENDER) {
       a.P[piece * 64 + lane] = u32x4{pack_phase2(ph[0], ph[1]), pack_phase2(ph[2], ph[3]), pack_phase2(ph[4], ph[5]),
                                      pack_phase2(ph[6], ph[7])};
     }
@@ -150,11 +154,17 @@ struct WGemmArgs {
   int nout;              // out_features (1..3): channel count and stride of img / pred
   float last_om, last_om_rev;   // sine output layer (outermost_linear=False), 0 otherwise
   int n_super, n_ob;     // 256-pixel super-blocks of the chunk, output blocks; grid = roundup(n_super, 8) * n_ob
+  union {                // k_wgemm RENDER only, optional [npix][nout] samples (4-byte aligned base), as FwdArgs:
+    uint8_t* rgb8;       //   BITS = 8
+    uint16_t* rgb16;     //   BITS = 16
+  };
 };
 
 // k_wgemm: the last layer (32 padded output rows) + residual.  Workgroup = 8 waves = 256 pixels, one
 // 32-pixel block per wave; the [32 x WD] weight image streams through a 4-slot LDS ring (4 k-steps per chunk),
 // the activations are prefetched two chunks ahead into registers.  (Hidden layers: k_wgemm2 below.)
+// RENDER (inference only, sf_wide_render / sf_wide_render16): no target fetch, residual, SSE partial or dL/dout; the epilogue is
+// fwd_render_out<BITS> (siren_render.hip), the one of the width <= 256 render kernels: pred and / or samples of BITS bits.
 // LDS of k_wgemm: [ring of NB chunks of OT tiles x 4 k-steps][8 SSE partials]
 struct WGemmLds {
   static constexpr int OT = 1, NB = 4, CH = OT * 4 * 1024;   // 32-row tiles per chunk, ring slots, bytes per chunk
@@ -173,7 +183,7 @@ struct WDwLds {
   static_assert(bytes <= kLdsMax, "k_wdw LDS budget");
 };
 
-template <typename OP>
+template <typename OP, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
   using L = WGemmLds;
   constexpr int TW = 1;       // tiles per wave
@@ -212,9 +222,11 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
   float tgt[3] = {0.f, 0.f, 0.f};
   const long pix = a.pix0 + pb0 * 32 + m;
   const bool valid = pix < a.npix;
-  if (a.img && h == 0 && valid) {
+  if constexpr (!RENDER) {
+    if (a.img && h == 0 && valid) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) if (c < a.nout) tgt[c] = a.img[pix * a.nout + c];
+      for (int c = 0; c < 3; ++c) if (c < a.nout) tgt[c] = a.img[pix * a.nout + c];
+    }
   }
   asm volatile("" ::"v"(tgt[0]), "v"(tgt[1]), "v"(tgt[2]), "v"(acc[0][0][0]));
   // B pieces are prefetched TWO chunks ahead into registers, right behind the LDS-DMA of the same chunk: vmcnt
@@ -258,7 +270,12 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
       for (int i = 0; i < 4; ++i) { r0[p][i] = r1[p][i]; r1[p][i] = r2[p][i]; }
   }
   // ---- epilogue: residual, SSE partial, dL/dout ----
-  {
+  if constexpr (RENDER) {   // a wave owns the 32 consecutive pixels of its block, lanes h == 0 hold them; 32 divides px0
+    FwdArgs fa = {};      // fwd_render_out's view of this kernel's arguments: the one epilogue of every SIREN render kernel
+    fa.sc_last = a.sc; fa.last_om_rev = a.last_om_rev; fa.nout = a.nout; fa.pred = a.pred; fa.rgb8 = a.rgb8;
+    fa.pix0 = a.pix0; fa.npix = a.npix;
+    fwd_render_out<BITS>(fa, acc[0][0], pix, pb0, valid, lane, h);
+  } else {
     float sse = 0.f, d[3] = {0.f, 0.f, 0.f};
     if (h == 0 && valid) {
 #pragma unroll
@@ -304,9 +321,12 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
 // IN8 / OUT8 (MODE 2, scratch_format 8 on the wide path, round 3): the incoming / outgoing deltas are fp8 e4m3 byte pieces, one
 // per (pixel block, 32-neuron tile) in the phase-byte layout: a B chunk of two k-steps is ONE piece per pixel block (converted
 // in registers, exact), a tile's sixteen outgoing values leave in one store.  Scales: csrc/siren_kernels.hip k_fp8_links.
-template <int MODE, typename OP, bool P8 = false, bool IN8 = false, bool OUT8 = false>
+// RENDER (MODE 0, inference only, sf_wide_render): the epilogue writes the activation alone (a.Out is null): half the stores of
+// the 16-bit training form, which NEP - and through it the first PD waits of every tile after a workgroup's first - counts.
+template <int MODE, typename OP, bool P8 = false, bool IN8 = false, bool OUT8 = false, bool RENDER = false>
 __global__ __launch_bounds__(512, 1) void k_wgemm2(WGemmArgs a) {
   static_assert(MODE == 0 || MODE == 2, "last layer: k_wgemm");
+  static_assert(!RENDER || (MODE == 0 && !P8), "render: the forward product, no phase of any format");
   static_assert(MODE == 2 || (!IN8 && !OUT8), "fp8 deltas: the data-gradient product only");
   constexpr int NWV = 8;                                         // waves per workgroup
   using L = WGemm2Lds;
@@ -314,7 +334,7 @@ __global__ __launch_bounds__(512, 1) void k_wgemm2(WGemmArgs a) {
   static_assert(NPB == NWV, "one pixel block per wave");
   constexpr int NB = L::NB, PD = NB - 1, SLOT = L::SLOT;
   constexpr int GA = 16 / NWV, GB = (IN8 ? NPB : 2 * NPB) / NWV, G = GA + GB;   // LDS-DMA instructions per wave and chunk
-  constexpr int NEP = MODE == 0 ? TW * PBW * (P8 ? 3 : 4) : TW * PBW * (OUT8 ? 1 : 2);   // epilogue stores per wave
+  constexpr int NEP = MODE == 0 ? TW * PBW * (RENDER ? 2 : P8 ? 3 : 4) : TW * PBW * (OUT8 ? 1 : 2);   // epilogue stores per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -519,7 +539,7 @@ __global__ __launch_bounds__(512, 1) void k_wgemm2(WGemmArgs a) {
             if constexpr (P8) {
               pb8[2 * qq] = phase_byte4(tv, av);
               pb8[2 * qq + 1] = phase_byte4(tv + 4, av + 4);
-            } else {
+            } else if constexpr (!RENDER) {
               a.Out[pidx] = u32x4{pack_phase2(ph[0], ph[1]), pack_phase2(ph[2], ph[3]), pack_phase2(ph[4], ph[5]),
                                   pack_phase2(ph[6], ph[7])};
             }

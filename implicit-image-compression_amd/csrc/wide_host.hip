@@ -1,11 +1,12 @@
-// wide_host.hip — SIREN handles of hidden 512 / 1024 on the host: weight images, a chunk's forward and backward over the
-// layer-at-a-time kernels of siren_wide.hip.  Included by siren_fit.hip after siren_host.hip, whose layer-0 and reduction launchers it shares.
+// wide_host.hip — SIREN handles of hidden 512 / 1024 on the host: weight images, a chunk's forward and backward and the render
+// loop of a wide render handle over the layer-at-a-time kernels of siren_wide.hip.  Included by siren_fit.hip after siren_host.hip, whose layer-0 and reduction launchers it shares.
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // wide path (hidden 512 / 1024): layer-at-a-time kernels of siren_wide.hip
 // ---------------------------------------------------------------------------------------------------------
+// (a render handle has the forward images and the tables only: no transposed image, no fp8 scale)
 int refresh_images_wide(sf_engine* h) {
   const int WD = h->WD, D = h->D, NBLK = WD / 256, KS = WD / 16;
   const bool f16 = h->cfg.compute_dtype == SF_F16;
@@ -33,10 +34,10 @@ int refresh_images_wide(sf_engine* h) {
   };
   for (int l = 1; l <= D - 2; ++l) {
     SF_TRY(image(l, false, 8, NBLK, KS / 4, (float)((double)h->cfg.hidden_omega_0 / kTwoPi), h->wf + (size_t)(l - 1) * WD * WD));
-    SF_TRY(image(l, true, 8, NBLK, KS / 4, l - 1 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb + (size_t)(l - 1) * WD * WD));
+    if (!h->render) SF_TRY(image(l, true, 8, NBLK, KS / 4, l - 1 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb + (size_t)(l - 1) * WD * WD));
   }
   SF_TRY(image(D - 1, false, 1, 1, KS / 4, h->wscale, h->wf_last));
-  SF_TRY(image(D - 1, true, 8, NBLK, 1, D - 2 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb_last));
+  if (!h->render) SF_TRY(image(D - 1, true, 8, NBLK, 1, D - 2 == 0 ? h->cfg.first_omega_0 : h->cfg.hidden_omega_0, h->wb_last));
   h->images_dirty = false;
   return SF_OK;
 }
@@ -47,14 +48,26 @@ unsigned wgemm_grid(const sf_engine* h, int n_ob, unsigned tiles) {
   const unsigned pg = (unsigned)(h->dw_wg / (8 * n_ob) * (8 * n_ob));
   return pg == 0 || pg > tiles ? tiles : pg;
 }
+// (render_bits: 0, or the sample width of a render handle's launch - the RENDER forms of MODE 0 and 1)
 template <int MODE>
-int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob) {
+int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob, int render_bits = 0) {
   WGemmArgs b = a;
   b.n_super = n_super; b.n_ob = n_ob;
   const unsigned grid = (unsigned)((n_super + 7) / 8 * 8 * n_ob);
   if constexpr (MODE == 1) {
+    if (render_bits)
+      return with_bool(render_bits == 16, [&](auto wide) {
+        constexpr int BITS = decltype(wide)::value ? 16 : 8;
+        return with_op(h, [&](auto op) { return launch(h, k_wgemm<decltype(op), true, BITS>, grid, 512, WGemmLds::bytes, b); });
+      });
     return with_op(h, [&](auto op) { return launch(h, k_wgemm<decltype(op)>, grid, 512, WGemmLds::bytes, b); });
   } else {
+    if constexpr (MODE == 0) {
+      if (render_bits)
+        return with_op(h, [&](auto op) {
+          return launch(h, k_wgemm2<0, decltype(op), false, false, false, true>, wgemm_grid(h, n_ob, grid), 512, WGemm2Lds::bytes, b);
+        });
+    }
     if constexpr (MODE == 2) {
       if (h->d8) {   // fp8 deltas (format 8): out always, in for every launch below the last layer's
         const unsigned pg8 = wgemm_grid(h, n_ob, grid);
@@ -112,6 +125,48 @@ int wide_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_par
     n_part = n_super;
     Launch L(h, K_FWD, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + 12.0 + 64.0));
     SF_TRY(launch_wgemm<1>(h, a, n_super, 1));
+  }
+  return SF_OK;
+}
+
+// The render loop of a wide render handle (sf_wide_render_create; its images are current): per chunk k_wlayer0, D - 2 hidden
+// products and the last layer, all in their RENDER forms - activations only, through the handle's two planes in turn (layer l
+// reads plane (l - 1) & 1 and writes plane l & 1), then pred and / or samples of `bits` bits at out (either may be null)
+int wide_render_chunks(sf_engine* h, void* out, int bits, float* pred) {
+  const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
+  const size_t blk_pieces = (size_t)(KS / 4) * 32;
+  auto plane = [&](int l) { return h->Abuf + (size_t)(l & 1) * h->a_stride; };
+  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
+    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+    const double npx = k.n_pb * 32.0;
+    {
+      WL0Args a = zeroed<WL0Args>();
+      a.gh = h->gh; a.gw = h->gw; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin; a.pix0 = k.pix0; a.npix = h->npix;
+      a.l0tab = h->l0tab; a.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi); a.KS = KS; a.n_pieces = k.n_pb * KS;
+      a.Act = plane(0);
+      Launch L(h, K_RENDER, 4.0 * WD * npx, npx * WD * 2.0);
+      SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op), false, true>, (a.n_pieces + 3) / 4, 256, 0, a); }));
+    }
+    for (int l = 1; l <= D - 2; ++l) {
+      WGemmArgs a = zeroed<WGemmArgs>();
+      a.A = reinterpret_cast<const u32x4*>(h->wf + (size_t)(l - 1) * WD * WD);
+      a.a_block_pieces = (long)blk_pieces; a.n_chunk = KS / 4;
+      a.Bin = plane(l - 1); a.ks_in = KS;
+      a.bias = h->biasw + (size_t)(l - 1) * WD;
+      a.OutAct = plane(l); a.ks_out = KS; a.kp_out = WD / 32;
+      Launch L(h, K_RENDER, 2.0 * WD * WD * npx, npx * (WD * (2.0 + 2.0 * NBLK)));
+      SF_TRY(launch_wgemm<0>(h, a, k.n_super, NBLK, bits));
+    }
+    WGemmArgs a = zeroed<WGemmArgs>();
+    a.A = reinterpret_cast<const u32x4*>(h->wf_last);
+    a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
+    a.Bin = plane(D - 2); a.ks_in = KS;
+    a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
+    a.pred = pred; a.rgb8 = (uint8_t*)out; a.nout = h->cfg.out_features; a.pix0 = k.pix0; a.npix = h->npix;
+    if (!h->cfg.outermost_linear) a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
+    const double out_bytes = (pred ? 4.0 : 0.0) + (out ? bits / 8.0 : 0.0);
+    Launch L(h, K_RENDER, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + h->cfg.out_features * out_bytes));
+    SF_TRY(launch_wgemm<1>(h, a, k.n_super, 1, bits));
   }
   return SF_OK;
 }

@@ -138,6 +138,13 @@ _declare("wavelet_render", {
     "sf_wavelet_render16": [H, I32, I32, I32, I32, C.c_void_p, F],
 })
 _declare("fourier_render", {"sf_fourier_render_create": [P(sf_fourier_config), P(H)]})
+# (the render handle of SIREN 512 / 1024: the RENDER forms of the layer-at-a-time kernels, csrc/siren_wide.hip.  In "core" like
+# sf_render16 and sf_mask_update: has_wide_render asks for the three symbols themselves)
+_declare("core", {
+    "sf_wide_render_create": [P(sf_config), P(H)],
+    "sf_wide_render": [H, C.c_void_p, F],
+    "sf_wide_render16": [H, C.c_void_p, F],
+})
 # (the RigL topology update on the device, csrc/siren_mask.hip.  In "core" like sf_render16: has_mask_update asks for the
 # symbol itself, Masking routes by it)
 _declare("core", {"sf_mask_update": [H, P(sf_mask_update_args)]})
@@ -197,6 +204,11 @@ def has_wavelet_render(lib) -> bool:
 def has_fourier_render(lib) -> bool:
     """sf_fourier_render_create, and with it sf_render on FourierNet handles (csrc/fourier_render.hip)"""
     return has_render(lib) and _has(lib, "fourier_render")
+
+
+def has_wide_render(lib) -> bool:
+    """sf_wide_render_create / sf_wide_render / sf_wide_render16: SIREN 512 / 1024 on a render handle"""
+    return all(hasattr(lib, n) for n in ("sf_wide_render_create", "sf_wide_render", "sf_wide_render16"))
 
 
 def has_mask_update(lib) -> bool:
@@ -514,7 +526,7 @@ class RenderEngine(SirenEngine):
     """Inference-only handle (sf_render_create): parameters, forward weight images and the two coordinate vectors - no
     gradient, optimiser state, mask or backward scratch.  set_params / get_params / set_coords / render / the profiling
     calls work; every training call raises with the library's message.  set_coords takes any two vectors (a window of a
-    grid is a slice of its linspace vectors); hidden 512 / 1024 is refused (no render kernel on the wide path; FourierNet
+    grid is a slice of its linspace vectors); hidden 512 / 1024 is refused (WideRenderEngine is that handle; FourierNet
     has FourierRenderEngine, WaveletSiren has WaveletRenderEngine, a Feathermap fit FeatherRenderEngine)."""
 
     def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
@@ -524,6 +536,26 @@ class RenderEngine(SirenEngine):
                          compute_dtype, device, row_begin, row_end, chunk_pixels)
 
     _CREATE, _CREATE_NEEDS = "sf_render_create", (has_render, "sf_render_create entry point", "the render path")
+
+
+class WideRenderEngine(RenderEngine):
+    """Inference-only handle of a SIREN of hidden 512 / 1024 (sf_wide_render_create): parameters, the blocked forward weight
+    images, the layer-0 table, the two coordinate vectors and two activation planes of chunk_pixels x hidden 16-bit values
+    that the layers use in turn - none of the per-layer phase / activation / delta planes, transposed images, gradient,
+    optimiser state or mask of a training handle.  chunk_pixels = 0: 2^18 pixels at 512, 2^17 at 1024.  Everything
+    RenderEngine says holds; render() is sf_wide_render / sf_wide_render16, pred bit-identical to SirenEngine.forward()'s."""
+
+    _CREATE = "sf_wide_render_create"
+    _CREATE_NEEDS = (has_wide_render, "sf_wide_render_create entry point", "the wide render path")
+
+    def render(self, want_u8: bool = True, want_pred: bool = False, bits: int = 8):
+        """sf_wide_render (bits=16: sf_wide_render16) on this handle's rows, no host sync: SirenEngine.render's signature
+        and return"""
+        fn = _render_entry(self.lib, "sf_wide_render", bits)
+        u8, pred, u8_p, pred_p = self._outputs((self.row_end - self.row_begin, self.width, self.out_features), want_u8, want_pred,
+                                               bits)
+        _check(fn(self.h, u8_p, pred_p))
+        return u8, pred
 
 
 class FeatherRenderEngine(RenderEngine):

@@ -23,20 +23,25 @@ decode.* keys
   decode.truth      <ppm> or synthetic[:seed]: print loss / PSNR / PSNR_8bit with eval_epoch's formulas (decode.bits=16:
                     and PSNR_16bit, the same formula on 65535 levels)
   decode.device     cuda ordinal (default 0)
-  decode.render     auto | kernel | torch (default auto).  auto: what `render_path` answers, below.  torch: the registry
+  decode.render     auto | kernel | wide | torch (default auto).  auto: what `render_path` answers, below.  torch: the registry
                     model's own forward for any model.  kernel: a render kernel or a ValueError that says why there is
                     none for this model and picture (`kernel_available`), raised before the device is touched; this is
-                    how mlp=fourier decodes on its render kernel
+                    how mlp=fourier decodes on its render kernel.  wide: the wide render handle of a plain SIREN whose
+                    engine width is 512 or 1024 (depth >= 3), or a ValueError that says what decodes the model instead,
+                    raised as early; auto and kernel leave those widths where they were
 
 Four model families decode; `family` looks a run's up once from its shape.  Each has a render kernel at engine width 32 /
 64 / 128 / 256 (a Small_Dense width the engine zero-pads, 90 -> 128, runs at the padded width): bytes straight from the last
 epilogue, no training state or activation plane on the device.  `_render` does that job for all four: the family's CPU
 model builds and fills the handle (models/binding.py); a band is a slice of the coordinate vectors or, for WaveletSiren,
-a pixel window.  Without a kernel (width 512 / 1024, a WaveletSiren picture that is not even and square) or under
-decode.render=torch the same model runs its own forward on the device, bytes by the same formula in torch.  The log names the path.
+a pixel window.  Without a kernel (a WaveletSiren picture that is not even and square) or under decode.render=torch the
+same model runs its own forward on the device, bytes by the same formula in torch; so does a SIREN of width 512 / 1024 -
+through a full training handle - unless decode.render=wide asks for its render handle (two activation planes of a chunk and
+the forward images; the same `_render`, bands and windows).  The log names the path.
 
   family          auto runs   kernel runs                           engine class          entry points
   siren           kernel      sf_render                             RenderEngine          render_kernel, load_weights
+  siren 512/1024  torch       sf_wide_render (decode.render=wide)   WideRenderEngine      render_kernel, load_weights
   feather         kernel      sf_feather_render_load + sf_render    FeatherRenderEngine   render_feather, load_feather
   fourier         torch       sf_render (RENDER form of k_ff_fwd)   FourierRenderEngine   render_fourier, load_weights
   wavelet_siren   kernel      sf_wavelet_render                     WaveletRenderEngine   render_wavelet, load_weights
@@ -65,7 +70,8 @@ REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)),
 DECODE_JSON = "decode.json"
 BAND_BYTES = 256 << 20            # one band's byte output stays under this
 ROW_LIMIT = 1 << 40               # a handle decodes (row, col) exactly while rows * width^2 < 2^40 (sf_create)
-RENDER_MODES = ("auto", "kernel", "torch")
+RENDER_MODES = ("auto", "kernel", "wide", "torch")
+WIDE_WIDTHS = tuple(w for w in Siren.WIDTHS if w not in KERNEL_WIDTHS)      # the layer-at-a-time kernels: 512, 1024
 SAMPLE_BITS = (8, 16)
 SHAPE_KEYS = ("mlp.depth", "mlp.hidden_size")
 
@@ -386,8 +392,25 @@ def render_path(shape: Cfg, height: Optional[int] = None, width: Optional[int] =
     return ("kernel" if ok else "torch"), why
 
 
+def wide_available(shape: Cfg) -> Tuple[bool, str]:
+    """(does decode.render=wide draw this model, why / what draws it instead): a plain SIREN whose engine width is 512 or
+    1024 with depth >= 3, on the wide render handle.  No device is touched."""
+    name = shape.mlp.get("name", "siren")
+    if name != "siren" or is_feather(shape):
+        what = "Feathermap" if name == "siren" else {"fourier": "FourierNet", "wavelet_siren": "WaveletSiren"}.get(name, f"mlp={name}")
+        return False, f"the wide render is SIREN only ({what} decodes under decode.render=auto, kernel or torch)"
+    w, wp = engine_width(shape), padded_width(shape)
+    if wp in KERNEL_WIDTHS:
+        return False, f"SIREN width {w} has the render kernel of the narrow path: use decode.render=kernel"
+    if wp not in WIDE_WIDTHS:
+        return False, f"SIREN width {w} is above 1024: no engine runs it"
+    if int(shape.mlp.depth) < 3:
+        return False, f"SIREN width {w} needs depth >= 3 on the wide path (got {shape.mlp.depth})"
+    return True, f"SIREN {wp}x{shape.mlp.depth}{'' if wp == w else f' (width {w} zero-padded)'}: sf_wide_render"
+
+
 def render_mode(dec: Dict[str, str]) -> str:
-    """decode.render of the decode.* keys: auto (default) | kernel | torch"""
+    """decode.render of the decode.* keys: auto (default) | kernel | wide | torch"""
     mode = dec.get("render") or "auto"
     if mode not in RENDER_MODES:
         raise ValueError(f"decode.render must be one of {', '.join(RENDER_MODES)}, got {mode!r}")
@@ -395,9 +418,15 @@ def render_mode(dec: Dict[str, str]) -> str:
 
 
 def choose_path(shape: Cfg, mode: str, height: int, width: int) -> Tuple[str, str]:
-    """('kernel' | 'torch', why) for a decode.render mode; kernel without a render kernel raises ValueError"""
+    """('kernel' | 'torch', why) for a decode.render mode; kernel without a render kernel, and wide for anything but a plain
+    SIREN of engine width 512 / 1024, raise ValueError"""
     if mode == "torch":
         return "torch", "decode.render=torch"
+    if mode == "wide":
+        ok, why = wide_available(shape)
+        if not ok:
+            raise ValueError(f"decode.render=wide: {why}")
+        return "kernel", why
     if mode == "auto":
         return render_path(shape, height, width)
     ok, why = kernel_available(shape, height, width)
@@ -575,7 +604,7 @@ def decode(argv: Sequence[str]) -> Dict[str, object]:
     H = int(dec.get("height") or shape.img.get("height") or 0)
     W = int(dec.get("width") or shape.img.get("width") or 0)
     fam = family(shape)
-    if mode == "kernel":                           # no render kernel: refused before a file is read or the device touched
+    if mode in ("kernel", "wide"):                 # no render kernel: refused before a file is read or the device touched
         choose_path(shape, mode, H, W)
     sd, source = fam.load(run_dir, shape, dec.get("source"))
     if H < 1 or W < 1:

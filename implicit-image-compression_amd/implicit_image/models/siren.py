@@ -107,8 +107,9 @@ class Siren(EngineBound):
                             eps=self._adam[1], scratch_format=self.cfg["scratch_format"])
 
     def _new_render_engine(self, rows: int, cols: int, device: int, side=None):
-        from .._engine import RenderEngine
-        return self._handle(RenderEngine, rows, cols, device)
+        """the render handle of this model's engine width: the fused chain kernels up to 256, the layer-at-a-time ones above"""
+        from .._engine import RenderEngine, WideRenderEngine
+        return self._handle(WideRenderEngine if self._engine_width > 256 else RenderEngine, rows, cols, device)
 
     def _layer_fans(self):
         c = self.cfg

@@ -260,7 +260,7 @@ int sf_forward_backward(sf_handle* h, double* sse_out);
  * sf_render_create takes sf_create's config and validation (height / width: the picture to render, any size) for hidden
  * 32 / 64 / 128 / 256 and allocates the parameters, the forward weight images, the layer-0 table / image and the two
  * coordinate vectors - no gradient, Adam moments, mask, phase / delta scratch or slabs (hidden 512 / 1024: SF_ERR_INVALID,
- * the render kernel is not built for the wide path).  On such a handle sf_set_params, sf_get_params, sf_params_changed,
+ * the render kernel is not built for the wide path; sf_wide_render_create below makes that handle).  On such a handle sf_set_params, sf_get_params, sf_params_changed,
  * sf_set_coords (any two vectors: a window of a grid is a slice of them), sf_num_params, sf_param_offset, sf_state_ptr(0),
  * sf_destroy and the profiling calls work; every training entry point returns SF_ERR_INVALID.
  * sf_fourier_render_create (csrc/fourier_render.hip) is the same for FourierNet: sf_fourier_create's config, validation and
@@ -283,6 +283,21 @@ int sf_render_create(const sf_config* cfg, sf_handle** out);
 int sf_render(sf_handle* h, uint8_t* rgb8_dev, float* pred_dev);
 int sf_render16(sf_handle* h, uint16_t* rgb16_dev, float* pred_dev);
 int sf_fourier_render_create(const sf_fourier_config* cfg, sf_handle** out);
+/* Inference only, SIREN of hidden 512 / 1024 (the RENDER forms of the layer-at-a-time kernels, csrc/siren_wide.hip).
+ * sf_wide_render_create takes sf_create's config and validation for hidden 512 / 1024 with depth >= 3 (any other width:
+ * SF_ERR_INVALID, sf_render_create makes that handle) and allocates the parameters, the blocked forward weight images with
+ * their biases, the layer-0 table, the two coordinate vectors and TWO activation planes of chunk_pixels x hidden 16-bit
+ * values, which the layers use in turn - no gradient, Adam moments, mask, transposed images, phase / delta planes, per-layer
+ * activation planes or slabs.  chunk_pixels = 0 means 2^18 pixels at hidden 512 and 2^17 at 1024 (256 MiB per plane);
+ * scratch_format is ignored.  On such a handle the calls listed for sf_render_create work and every training entry point,
+ * sf_render, sf_render16 and sf_feather_render_attach return SF_ERR_INVALID.
+ * sf_wide_render / sf_wide_render16 are sf_render / sf_render16 for this handle: rows [row_begin, row_end) on the handle's
+ * stream, no host synchronisation, pred_dev bit-identical to what sf_forward writes on a training handle of any
+ * scratch_format with the same parameters and coordinates, the samples by the same formulas, the same NULL, alignment and
+ * sf_set_coords checks.  Any other handle returns SF_ERR_INVALID with the entry point that draws it in the message. */
+int sf_wide_render_create(const sf_config* cfg, sf_handle** out);
+int sf_wide_render(sf_handle* h, uint8_t* rgb8_dev, float* pred_dev);
+int sf_wide_render16(sf_handle* h, uint16_t* rgb16_dev, float* pred_dev);
 /* Inference only, WaveletSiren (csrc/wavelet_render.hip).  sf_wavelet_render_create validates what sf_wavelet_create
  * validates and allocates the joint parameter vector [LF | HF], two render sub-handles (parameters as views into it, forward
  * weight images, layer-0 table / image), the two FULL coefficient-grid vectors and ONE pair of fp32 coefficient buffers

@@ -2,7 +2,7 @@
 (the repository root, the package and tests/, for tests/_gpu_fixtures.siren_engine: the oracle-initialised engine), and it
 never touches the device.
 
-    SIREN timing scripts:  timing_engine, timed_steps, kernel_table, lib_name
+    SIREN timing scripts:  siren_init_params, timing_engine, timed_steps, kernel_table, lib_name
     model benches:         time_loop
     render benches:        device_note, timed, stats, alternate, print_handle_bytes, handle_memory"""
 import json
@@ -21,6 +21,14 @@ import torch  # noqa: E402
 LR = 3e-4
 
 
+def siren_init_params(hidden, depth):
+    """the seed-0 Siren(depth, hidden, 50, 30) initialisation as the engine's flat vector, on the device"""
+    from implicit_image.models import Siren
+    torch.manual_seed(0)
+    return torch.cat([q.detach().reshape(-1) for q in Siren(depth=depth, hidden_size=hidden, first_omega_0=50.0,
+                                                              hidden_omega_0=30.0).parameters()]).cuda()
+
+
 def timing_engine(size, hidden, depth, *, fmt=0, chunk=0, dtype="f16", init="siren", target=None):
     """a SirenEngine at size (an edge, or (H, W)) on the current stream, ready to step: parameters by `init`, the two linspace
     coordinate vectors, and `target` or a torch.rand image.
@@ -28,13 +36,11 @@ def timing_engine(size, hidden, depth, *, fmt=0, chunk=0, dtype="f16", init="sir
           "randn0.01"   normal, sigma 0.01   } small random weights: the step runs at another (higher) clock than from the
           "uniform0.03" uniform in +-0.03    } SIREN init (stream_probe.py); for launch counts and counter passes"""
     from implicit_image._engine import SirenEngine
-    from implicit_image.models import Siren
     H, W = (size, size) if isinstance(size, int) else size
     eng = SirenEngine(H, W, hidden, depth, compute_dtype=dtype, scratch_format=fmt, chunk_pixels=chunk)
     torch.manual_seed(0)
     if init == "siren":
-        params = torch.cat([q.detach().reshape(-1) for q in Siren(depth=depth, hidden_size=hidden, first_omega_0=50.0,
-                                                                  hidden_omega_0=30.0).parameters()]).cuda()
+        params = siren_init_params(hidden, depth)
     else:
         params = {"randn0.01": lambda n: torch.randn(n, device="cuda") * 0.01,
                   "uniform0.03": lambda n: (torch.rand(n, device="cuda") * 2 - 1) * 0.03}[init](eng.num_params)
