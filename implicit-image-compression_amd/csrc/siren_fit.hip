@@ -5,7 +5,8 @@
 // One sf_engine == one per-image fit on one HIP stream.  A training step is, per pixel chunk:
 //   k_fwd -> k_bwd(last) -> k_bwd(hidden l = depth-2 .. 1) -> k_dw0, each followed by the fixed-order slab
 //   reduction into the flat fp32 gradient; then k_adam (+mask) and k_images (16-bit weight images).
-// Every `interval` steps of a masked fit the topology changes: sf_mask_update (siren_mask.hip), two more launches.
+// Every `interval` steps of a masked fit the topology changes: sf_mask_update (siren_mask.hip), two more launches, or
+// sf_mask_prune_global (same file), six.
 // The sequence mirrors one `train_epoch` of the reference (implicit_image/utils/train_helper.py:132-185)
 // for the full-batch grid (implicit_image/compress.py:137-138).
 #include "siren_kernels.hip"
@@ -88,7 +89,7 @@
     SF_K(k_wlayer0<OpF16, false, true>), SF_K(k_wlayer0<OpBF16, false, true>),
     SF_K(k_wgemm2<0, OpF16, false, false, false, true>), SF_K(k_wgemm2<0, OpBF16, false, false, false, true>),
     SF_K(k_wgemm<OpF16, true, 8>), SF_K(k_wgemm<OpF16, true, 16>), SF_K(k_wgemm<OpBF16, true, 8>),
-    SF_K(k_wgemm<OpBF16, true, 16>),
+    SF_K(k_wgemm<OpBF16, true, 16>), SF_K(k_prune_file<false>), SF_K(k_prune_file<true>),
 };
 #undef SF_K
 
@@ -621,6 +622,68 @@ int sf_mask_update(sf_handle* h, const sf_mask_update_args* a) try {
     Launch L(h, K_MASK, 0, bytes * 12);   // (about a dozen L2-resident reads of every masked layer)
     SF_TRY(launch(h, k_mask_count, k.L, kMaskThreads, 0, k));
     SF_TRY(launch(h, k_mask_update, k.L, kMaskThreads, 0, k));
+  }
+  h->images_dirty = true;
+  h->fth.fresh = false;
+  return SF_OK;
+} SF_CATCH
+
+/* one global-magnitude topology update (masking=Pruning) of the masked layers on the handle's stream: six launches whatever
+ * the depth and the number of trials, no host synchronisation (siren_mask.hip states what it computes) */
+int sf_mask_prune_global(sf_handle* h, const sf_mask_prune_global_args* a) try {
+  if (!h || !a || !a->layers) return fail(SF_ERR_INVALID, "null argument");
+  if (a->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
+  SF_NO_RENDER(h, "sf_mask_prune_global");
+  switch (h->model) {
+    case Model::Siren: break;
+    case Model::Fourier: return fail(SF_ERR_INVALID, "sf_mask_prune_global: a FourierNet handle takes no mask");
+    case Model::Wavelet: return fail(SF_ERR_INVALID, "sf_mask_prune_global: topology updates of a WaveletSiren handle stay on the host");
+  }
+  if (h->fth.attached) return fail(SF_ERR_INVALID, "sf_mask_prune_global: a Feathermap handle is dense (masking.dense: True)");
+  if (!h->has_mask) return fail(SF_ERR_STATE, "sf_mask_prune_global: sf_set_masks has not been called");
+  if (!(std::isfinite(a->threshold) && a->threshold > 0.0))
+    return fail(SF_ERR_INVALID, "sf_mask_prune_global: threshold must be finite and > 0");
+  if (!(a->increment > 0.0 && a->increment < 1.0)) return fail(SF_ERR_INVALID, "sf_mask_prune_global: increment must lie in (0, 1)");
+  if (!(std::isfinite(a->tolerance) && a->tolerance >= 0.0))
+    return fail(SF_ERR_INVALID, "sf_mask_prune_global: tolerance must be finite and >= 0");
+  if (a->target < 0) return fail(SF_ERR_INVALID, "sf_mask_prune_global: target must be >= 0");
+  if (a->n_layers < 1 || a->n_layers > h->D || a->n_layers > kMaskMaxLayers)
+    return fail(SF_ERR_INVALID, "sf_mask_prune_global: n_layers must be 1 .. depth");
+  PruneArgs p = zeroed<PruneArgs>();
+  MaskArgs& k = p.m;
+  double bytes = 0;
+  int n_max = 0;
+  for (int j = 0; j < a->n_layers; ++j) {
+    const int l = a->layers[j];
+    if (l < 0 || l >= h->D || (j > 0 && l <= a->layers[j - 1]))
+      return fail(SF_ERR_INVALID, "sf_mask_prune_global: layers must be ascending indices in [0, depth)");
+    k.off[j] = h->off_w[l];
+    k.n[j] = (int)(h->off_b[l] - h->off_w[l]);
+    n_max = std::max(n_max, k.n[j]);
+    bytes += (double)k.n[j] * 4;
+  }
+  if (h->P > 0x7fffffff) return fail(SF_ERR_INVALID, "sf_mask_prune_global: more than 2^31 - 1 parameters");
+  DevGuard dev_guard(h->cfg.device);
+  if (!a->stats_dev && !h->mask_rows) SF_TRY(dev_alloc(h, h->mask_rows, sizeof(MaskRow) * (kMaskMaxLayers + 1)));
+  if (!h->prune_ws) SF_TRY(dev_alloc(h, h->prune_ws, sizeof(PruneWs)));
+  if (!h->prune_keys) SF_TRY(dev_alloc(h, h->prune_keys, (size_t)h->P * 4));
+  k.w = h->params; k.g = h->grads; k.m = h->m; k.v = h->v; k.k = h->mask;
+  k.rows = a->stats_dev ? reinterpret_cast<MaskRow*>(a->stats_dev) : h->mask_rows;
+  k.L = a->n_layers; k.rate = a->prune_rate; k.dense = a->dense_gradients != 0;
+  p.ws = h->prune_ws; p.keys = h->prune_keys; p.cap = (int)h->P;
+  p.target = a->target; p.threshold = a->threshold; p.increment = a->increment; p.tolerance = a->tolerance;
+  // strides per layer: 16 elements per thread of the largest layer, at most four workgroups per compute unit in all
+  const int per_layer = std::max(1, std::min((n_max + kMaskThreads * 16 - 1) / (kMaskThreads * 16), 4 * h->dw_wg / k.L));
+  const dim3 grid(k.L, per_layer);
+  {
+    Launch L(h, K_MASK_PRUNE, 0, bytes * 12);   // (the weights three times, the keys, the five state vectors once)
+    HIPCHK(hipMemsetAsync(h->prune_ws->hist, 0, sizeof(h->prune_ws->hist), h->ctx->stream));
+    SF_TRY(launch(h, k_mask_count, k.L, kMaskThreads, 0, k));
+    SF_TRY(launch(h, k_prune_file<false>, grid, kMaskThreads, 0, p));
+    SF_TRY(launch(h, k_prune_scan, 1, kMaskThreads, 0, p));
+    SF_TRY(launch(h, k_prune_file<true>, grid, kMaskThreads, 0, p));
+    SF_TRY(launch(h, k_prune_search, 1, kMaskThreads, 0, p));
+    SF_TRY(launch(h, k_prune_apply, grid, kMaskThreads, 0, p));
   }
   h->images_dirty = true;
   h->fth.fresh = false;

@@ -312,4 +312,267 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_update(MaskArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// sf_mask_prune_global — the global-magnitude update of masking=Pruning on the device, no host synchronisation.
+//
+// Reference being replaced: funcs/prune.py:54-104 global_magnitude_prune (one |w| threshold over all masked layers, nudged
+// multiplicatively until the number of weights it removes is within `tolerance` of the target or the count has stalled ten
+// times) inside core.py:713-801 truncate_weights with growth_mode none.  The host mirror sorts every masked weight and reads
+// one count back per trial - hundreds of blocking reads per update.  Here: six launches whatever the depth and however
+// many trials the search takes.
+//
+// The contract (counts exact integers; threshold arithmetic IEEE double, round to nearest, no contraction):
+//   1. per listed layer j: live_j, dead_j, nnz_j as step 1 above; S = sum nnz_j, alive = sum live_j.  S == 0: status 1,
+//      nothing else is touched
+//   2. rate_j as step 2 above with r = prune_rate (bookkeeping only)
+//   3. target <= 0: no search - the masks keep their values, removed = 0, trials = 0, the threshold is unchanged
+//   4. slack = target * tolerance; step = increment; removed = previous = stalled = 0
+//      while |removed - target| > slack:
+//        a. removed = alive - #{ i in the listed layers : |w_i| > f32(threshold) }   (an fp32 comparison over every element,
+//           dead ones included; f32: the double rounded to nearest-even); trials += 1
+//        b. stalled = stalled + 1 if removed == previous else 0
+//        c. stalled == 10: break
+//        d. previous = removed
+//        e. removed > target * (1.0 + tolerance): threshold *= 1.0 - step; step *= 0.99
+//           else removed < target * (1.0 - tolerance): threshold *= 1.0 + step; step *= 0.99
+//      a 4097th trial is never evaluated (kPruneTrialCap): status 2, nothing else is touched
+//   5. a search ran: k_i = |w_i| > f32(threshold) ? 1 : 0 with the final threshold
+//   6. w_i *= k_i (a product); dense_gradients == 0: also m_i *= k_i, v_i *= k_i, g_i *= k_i
+//   7. row j: the counts before, removed = live_before - live_after, the counts after, rate_j;
+//      status row: status, trials, alive, the search's last `removed`, target, 0, 0, bits of the final threshold (double)
+//
+// bits(|w|) orders like |w|, so "how many keys exceed the threshold's key" needs no sort: k_prune_file<false> counts the keys by
+// their top 16 bits (integer atomics), k_prune_scan turns the counts into bucket offsets, k_prune_file<true> files every key
+// under its bucket (in any order: only counts are taken), and k_prune_search - one workgroup - runs the trials: the
+// buckets above the threshold's come from the prefix, the threshold's own bucket is counted cooperatively, and a trial
+// whose fp32 threshold did not move reuses the last count.  Keys 0 (never above a threshold) and NaN (never above one in
+// an fp32 comparison) are filed nowhere.  One lane does the double arithmetic of a trial; the loop's continue / stop
+// decision is one LDS word that every thread reads behind a barrier, so every barrier is reached by every thread.
+// k_prune_apply (steps 5 - 7) adds its integer counts to the rows with 64-bit integer atomics.
+
+constexpr int kPruneTrialCap = 4096;
+constexpr int kPruneBins = 1 << 16;               // key >> 15: the 8 exponent bits and the top 8 mantissa bits
+constexpr unsigned kPruneInf = 0x7f800000u;
+
+struct PruneCtl {                 // what the search leaves for k_prune_apply
+  int mode;                       // 0 nothing is touched (S == 0, cap reached), 1 no search: the masks keep their values, 2 a search ran
+  unsigned tkey;                  // bits of f32(final threshold)
+};
+
+struct PruneWs {                  // the scratch of one handle (allocated on the first sf_mask_prune_global)
+  int hist[kPruneBins];           // keys per bucket; the cursors of k_prune_file<true> afterwards
+  int start[kPruneBins + 1];      // exclusive prefix of hist: bucket b is keys[start[b] .. start[b + 1])
+  PruneCtl ctl;
+};
+
+struct PruneArgs {
+  MaskArgs m;                     // w, g, m, v, k, rows, off, n, L, rate, dense (growth unused)
+  PruneWs* ws;
+  unsigned* keys;                 // cap entries
+  int cap;
+  int pad;
+  long long target;
+  double threshold, increment, tolerance;
+};
+
+__device__ __forceinline__ bool prune_filed(unsigned key) { return key != 0u && key <= kPruneInf; }
+
+// blockIdx.x: the layer, blockIdx.y: a stride over its elements.  SCATTER false: hist[bucket] += 1; true: the key goes to
+// the next free slot of its bucket (hist holds the cursors, k_prune_scan set them to the bucket starts)
+template <bool SCATTER>
+__global__ __launch_bounds__(kMaskThreads) void k_prune_file(PruneArgs a) {
+  const int j = blockIdx.x, n = a.m.n[j];
+  const float* __restrict__ w = a.m.w + a.m.off[j];
+  for (int i = blockIdx.y * kMaskThreads + threadIdx.x; i < n; i += gridDim.y * kMaskThreads) {
+    const unsigned key = __float_as_uint(w[i]) & 0x7fffffffu;
+    if (!prune_filed(key)) continue;
+    const int pos = atomicAdd(&a.ws->hist[key >> 15], 1);
+    if (SCATTER && pos >= 0 && pos < a.cap) a.keys[pos] = key;
+  }
+}
+
+// exclusive prefix of the 65 536 bucket counts -> start (and into hist, as the scatter's cursors); one workgroup
+__global__ __launch_bounds__(kMaskThreads) void k_prune_scan(PruneArgs a) {
+  __shared__ int part[kMaskThreads];
+  constexpr int kPer = kPruneBins / kMaskThreads;
+  const int t = threadIdx.x;
+  int* hist = a.ws->hist;
+  int sum = 0;
+  for (int i = 0; i < kPer; ++i) sum += hist[t * kPer + i];
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < kMaskThreads; d <<= 1) {                // (Hillis-Steele, inclusive)
+    const int add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int run = part[t] - sum;
+  for (int i = 0; i < kPer; ++i) {
+    const int c = hist[t * kPer + i];
+    a.ws->start[t * kPer + i] = run;
+    hist[t * kPer + i] = run;
+    run += c;
+  }
+  if (t == kMaskThreads - 1) a.ws->start[kPruneBins] = run;
+}
+
+struct PruneLds {
+  int go;                         // the loop's decision: 1 another trial is evaluated (never written after the loop)
+  int touch;                      // after the loop: the state is updated (a status of 0 with something to do)
+  int recount;                    // ... and its fp32 threshold differs from the last one's
+  unsigned tkey;
+  int lo, hi;                     // the threshold's bucket in keys
+  int cnt;                        // keys of that bucket above the threshold
+  long long above;                // keys in the buckets above it
+};
+
+// steps 2 - 4 and the status row; one workgroup
+__global__ __launch_bounds__(kMaskThreads) void k_prune_search(PruneArgs a) {
+  __shared__ PruneLds s;
+  const int t = threadIdx.x, lane = t & 63, L = a.m.L;
+  MaskRow* rows = a.m.rows;
+  const int* start = a.ws->start;
+  long long S = 0, alive = 0;
+  for (int l = 0; l < L; ++l) { S += rows[l].nnz_before; alive += rows[l].live_before; }
+  const long long target = a.target;
+  const int mode = S == 0 ? 0 : target <= 0 ? 1 : 2;
+  // the search's state lives in thread 0
+  const double tgt = (double)target, tol = a.tolerance;
+  const double slack = __dmul_rn(tgt, tol);
+  const double hi_bound = __dmul_rn(tgt, __dadd_rn(1.0, tol)), lo_bound = __dmul_rn(tgt, __dsub_rn(1.0, tol));
+  double thr = a.threshold, step = a.increment;
+  long long removed = 0, previous = 0, last_count = 0;
+  int stalled = 0, trials = 0, status = S == 0 ? 1 : 0;
+  unsigned last_tkey = 0xffffffffu;
+  auto aim = [&]() {                                          // (thread 0) the next trial's threshold as a key and a bucket
+    const unsigned tkey = __float_as_uint(__double2float_rn(thr));
+    s.tkey = tkey;
+    s.recount = tkey != last_tkey;
+    if (tkey != last_tkey) {
+      const int b = (int)(tkey >> 15);                        // (thr > 0: the sign bit is clear, b < kPruneBins)
+      s.lo = start[b];
+      s.hi = start[b + 1];
+      s.above = (long long)start[kPruneBins] - start[b + 1];
+      if (tkey > kPruneInf) { s.lo = s.hi = 0; s.above = 0; }  // (unreachable for a finite double; nothing exceeds a NaN)
+    }
+    s.cnt = 0;
+  };
+  if (t == 0) {
+    s.go = mode == 2 && fabs((double)(removed - target)) > slack;
+    if (s.go) aim();
+  }
+  for (int it = 0; it <= kPruneTrialCap; ++it) {
+    __syncthreads();
+    if (!s.go) break;                                         // (one LDS word, read by every thread behind the barrier)
+    if (s.recount) {
+      const unsigned tkey = s.tkey;
+      const int hi = s.hi;
+      int c = 0;
+      for (int i = s.lo + t; i < hi; i += kMaskThreads) c += a.keys[i] > tkey;
+      for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
+      if (lane == 0 && c) atomicAdd(&s.cnt, c);
+    }
+    __syncthreads();
+    if (t == 0) {
+      if (trials == kPruneTrialCap) {                         // the cap: the search is abandoned
+        status = 2;
+        s.go = 0;
+      } else {
+        if (s.recount) { last_count = s.above + s.cnt; last_tkey = s.tkey; }
+        removed = alive - last_count;                                                        // a.
+        ++trials;
+        stalled = removed == previous ? stalled + 1 : 0;                                     // b.
+        if (stalled == 10) {                                                                 // c.
+          s.go = 0;
+        } else {
+          previous = removed;                                                                // d.
+          const double r = (double)removed;
+          if (r > hi_bound) { thr = __dmul_rn(thr, __dsub_rn(1.0, step)); step = __dmul_rn(step, 0.99); }        // e.
+          else if (r < lo_bound) { thr = __dmul_rn(thr, __dadd_rn(1.0, step)); step = __dmul_rn(step, 0.99); }
+          s.go = fabs((double)(removed - target)) > slack;
+          if (s.go) aim();
+        }
+      }
+    }
+  }
+  // (every thread left the loop at its first barrier)
+  const bool touch = mode != 0 && status == 0;                // (thread 0 only knows status; the others use ctl below)
+  if (t == 0) {
+    a.ws->ctl.mode = touch ? mode : 0;
+    a.ws->ctl.tkey = __float_as_uint(__double2float_rn(thr));
+    MaskRow z;
+    z.live_before = status;
+    z.dead_before = trials;
+    z.nnz_before = alive;
+    z.removed = removed;
+    z.live_after = target;
+    z.dead_after = 0;
+    z.nnz_after = 0;
+    z.prune_rate = status == 0 ? thr : a.threshold;
+    rows[L] = z;
+    s.touch = touch;
+  }
+  __syncthreads();
+  if (t < L && s.touch) {                                        // 2. the rates; the "after" counts restart for k_prune_apply
+    const long long dead0 = rows[t].dead_before, nnz0 = rows[t].nnz_before;
+    const double share = (double)nnz0 / (double)S, frac_dead = (double)dead0 / (double)a.m.n[t];
+    const bool capped = frac_dead < 0.2 && (1.0 / (double)L) / share < 1.0;
+    rows[t].prune_rate = capped ? fmin(frac_dead, a.m.rate) : a.m.rate;
+    rows[t].removed = rows[t].live_before;
+    rows[t].live_after = rows[t].dead_after = rows[t].nnz_after = 0;
+  }
+}
+
+// steps 5 - 7 for a stride (blockIdx.y) of layer blockIdx.x
+__global__ __launch_bounds__(kMaskThreads) void k_prune_apply(PruneArgs a) {
+  __shared__ int acc[3];
+  const int mode = a.ws->ctl.mode;
+  if (mode == 0) return;                                      // (uniform over the grid)
+  const unsigned tkey = a.ws->ctl.tkey;
+  const int j = blockIdx.x, n = a.m.n[j], t = threadIdx.x, lane = t & 63;
+  float* w = a.m.w + a.m.off[j];
+  float* g = a.m.g + a.m.off[j];
+  float* m = a.m.m + a.m.off[j];
+  float* v = a.m.v + a.m.off[j];
+  float* k = a.m.k + a.m.off[j];
+  const bool sparse_grads = a.m.dense == 0;
+  if (t < 3) acc[t] = 0;
+  __syncthreads();
+  int live = 0, dead = 0, nnz = 0;
+  for (int i = blockIdx.y * kMaskThreads + t; i < n; i += gridDim.y * kMaskThreads) {
+    float wv = w[i], kv = k[i];
+    if (mode == 2) {
+      const unsigned key = __float_as_uint(wv) & 0x7fffffffu;
+      kv = key > tkey && key <= kPruneInf ? 1.0f : 0.0f;
+      k[i] = kv;
+    }
+    wv = __fmul_rn(wv, kv);
+    w[i] = wv;
+    if (sparse_grads) {
+      m[i] = __fmul_rn(m[i], kv);
+      v[i] = __fmul_rn(v[i], kv);
+      g[i] = __fmul_rn(g[i], kv);
+    }
+    live += kv == 1.0f;
+    dead += kv == 0.0f;
+    nnz += wv != 0.0f;
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    live += __shfl_down(live, d);
+    dead += __shfl_down(dead, d);
+    nnz += __shfl_down(nnz, d);
+  }
+  if (lane == 0) { atomicAdd(&acc[0], live); atomicAdd(&acc[1], dead); atomicAdd(&acc[2], nnz); }
+  __syncthreads();
+  if (t == 0) {
+    MaskRow& r = a.m.rows[j];
+    using u64 = unsigned long long;
+    atomicAdd(reinterpret_cast<u64*>(&r.live_after), (u64)acc[0]);
+    atomicAdd(reinterpret_cast<u64*>(&r.dead_after), (u64)acc[1]);
+    atomicAdd(reinterpret_cast<u64*>(&r.nnz_after), (u64)acc[2]);
+    atomicAdd(reinterpret_cast<u64*>(&r.removed), (u64)(-(long long)acc[0]));
+  }
+}
+
 }  // namespace sf

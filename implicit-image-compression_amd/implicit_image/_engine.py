@@ -72,6 +72,12 @@ class sf_mask_update_args(C.Structure):
                 ("stats_dev", C.c_void_p)]
 
 
+class sf_mask_prune_global_args(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("n_layers", C.c_int32), ("layers", C.POINTER(C.c_int32)),
+                ("target", C.c_int64), ("prune_rate", C.c_double), ("threshold", C.c_double), ("increment", C.c_double),
+                ("tolerance", C.c_double), ("dense_gradients", C.c_int32), ("stats_dev", C.c_void_p)]
+
+
 MASK_STATS_WORDS = C.sizeof(sf_mask_layer_stats) // 8      # a statistics row as int64 words (the last one: a double)
 MASK_GROWTH = {"none": 0, "absolute-gradient": 1}
 
@@ -148,6 +154,8 @@ _declare("core", {
 # (the RigL topology update on the device, csrc/siren_mask.hip.  In "core" like sf_render16: has_mask_update asks for the
 # symbol itself, Masking routes by it)
 _declare("core", {"sf_mask_update": [H, P(sf_mask_update_args)]})
+# (the global-magnitude update of masking=Pruning on the device, same file; has_mask_prune_global asks for the symbol itself)
+_declare("core", {"sf_mask_prune_global": [H, P(sf_mask_prune_global_args)]})
 
 
 def load_library():
@@ -214,6 +222,11 @@ def has_wide_render(lib) -> bool:
 def has_mask_update(lib) -> bool:
     """sf_mask_update: Masking.update_connections() on the device (csrc/siren_mask.hip)"""
     return hasattr(lib, "sf_mask_update")
+
+
+def has_mask_prune_global(lib) -> bool:
+    """sf_mask_prune_global: the global-magnitude update of masking=Pruning on the device (csrc/siren_mask.hip)"""
+    return hasattr(lib, "sf_mask_prune_global")
 
 
 def _require(lib, has, entry: str, since: str):
@@ -399,6 +412,24 @@ class SirenEngine:
                                    prune_rate=float(prune_rate), growth=int(growth), dense_gradients=int(bool(dense_gradients)),
                                    stats_dev=None if stats is None else stats.data_ptr())
         _check(self.lib.sf_mask_update(self.h, C.byref(args)))
+
+    def mask_prune_global(self, layers: Sequence[int], target: int, prune_rate: float, threshold: float, increment: float,
+                          tolerance: float, dense_gradients: bool, stats: Optional[torch.Tensor] = None):
+        """sf_mask_prune_global on this handle's stream, no host sync: one global-magnitude topology update of the weights of
+        `layers` - the threshold search from `threshold` towards `target` removed weights, the masks |w| > threshold, the
+        products.  stats: int64 [len(layers) + 1, MASK_STATS_WORDS] on the device or None - a sf_mask_layer_stats per layer and
+        the status row (status, trials, alive, removed, target, 0, 0, the bits of the final threshold)."""
+        _require(self.lib, has_mask_prune_global, "sf_mask_prune_global entry point", "the device global pruning update")
+        n = len(layers)
+        if stats is not None and not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous()
+                                      and stats.numel() == (n + 1) * MASK_STATS_WORDS):
+            raise ValueError(f"mask_prune_global: stats must be a contiguous int64 CUDA tensor of {(n + 1) * MASK_STATS_WORDS} words")
+        args = sf_mask_prune_global_args(abi_version=SF_ABI_VERSION, n_layers=n, layers=(C.c_int32 * max(n, 1))(*layers),
+                                         target=int(target), prune_rate=float(prune_rate), threshold=float(threshold),
+                                         increment=float(increment), tolerance=float(tolerance),
+                                         dense_gradients=int(bool(dense_gradients)),
+                                         stats_dev=None if stats is None else stats.data_ptr())
+        _check(self.lib.sf_mask_prune_global(self.h, C.byref(args)))
 
     def params_changed(self):
         _check(self.lib.sf_params_changed(self.h))
@@ -605,6 +636,7 @@ class FourierEngine(SirenEngine):
 
     _CREATE = "sf_fourier_create"
     mask_update = None          # sf_mask_update refuses a FourierNet handle: Masking keeps such a model on the host path
+    mask_prune_global = None    # (sf_mask_prune_global likewise)
 
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
@@ -647,6 +679,7 @@ class WaveletEngine(SirenEngine):
 
     _CREATE = "sf_wavelet_create"
     mask_update = None          # sf_mask_update refuses a WaveletSiren handle: its topology updates stay on the host
+    mask_prune_global = None    # (sf_mask_prune_global likewise)
 
     def set_coords(self, rows: torch.Tensor, cols: torch.Tensor):
         """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""

@@ -14,8 +14,12 @@ kernels and have no meaning for a SIREN; lottery-ticket init loads a pickle and 
 `update_connections()` of the configuration RigL ships with (magnitude pruning, absolute-gradient or no growth, no
 redistribution) runs on the device when the model is engine-bound: one `sf_mask_update` call, no read-back (DESIGN.md
 section 12).  `stats`, `name2prune_rate`, `adjustments` and `adjusted_growth` are then completed on their first read.
+The configuration Pruning ships with (global-magnitude pruning, no growth, no redistribution) runs on the device in the same
+way: one `sf_mask_prune_global` call - the threshold search included - and `prune_threshold` joins the attributes that are
+completed on their first read (the next global update reads it, so it completes the one before with one transfer).
 """
 import logging
+import math
 import os
 import struct
 from dataclasses import dataclass, field
@@ -73,17 +77,19 @@ class Masking:
         self._stats = LayerStats()
         self._pushed_engine = None
         # global growth/prune state (core.py:151-156)
-        self.prune_threshold, self.growth_threshold = 0.001, 0.001
+        self._prune_threshold, self.growth_threshold = 0.001, 0.001
         self.growth_increment, self.increment, self.tolerance = 0.2, 0.2, 1e-6
 
     # ---- bookkeeping a device update completes on its first read --------------------------------
     def _lazy(attr):
         def get(self):
-            self._complete()
+            if self._pending:                   # (the host path's threshold search reads and writes one of these per trial)
+                self._complete()
             return getattr(self, attr)
 
         def put(self, value):
-            self._complete()
+            if self._pending:
+                self._complete()
             setattr(self, attr, value)
         return property(get, put)
 
@@ -91,20 +97,27 @@ class Masking:
     name2prune_rate = _lazy("_name2prune_rate")
     adjustments = _lazy("_adjustments")
     adjusted_growth = _lazy("_adjusted_growth")
+    prune_threshold = _lazy("_prune_threshold")
     del _lazy
 
     def _complete(self):
         """The host-side bookkeeping of every pending device update, oldest first, from ONE copy of its statistics rows:
         exactly the values, and the float sequence, of truncate_weights() below."""
         while self._pending:
-            rows, names = self._pending.pop(0)
+            rows, names, global_prune = self._pending.pop(0)
             rows = rows.cpu().tolist()
-            assert not rows[len(names)][0], "Total variance is zero!"
+            status = rows[len(names)]
+            if global_prune and status[0] == 2:
+                raise RuntimeError(f"sf_mask_prune_global: the threshold search did not end within {status[1]} trials")
+            assert not status[0], "Total variance is zero!"
             live, dead, nnz = {}, {}, {}
             for pname, row in zip(names, rows):
                 self._name2prune_rate[pname] = struct.unpack("<d", struct.pack("<q", row[7]))[0]
                 live[pname], dead[pname], nnz[pname] = row[4], row[5], row[6]
             total_nonzero_new = sum(live.values())
+            if global_prune:                    # (truncate_weights: total_nonzero before the update - what the search removed)
+                total_nonzero_new = status[2] - status[3]
+                self._prune_threshold = struct.unpack("<d", struct.pack("<q", status[7]))[0]
             self._adjustments.append(self.baseline_nonzero - total_nonzero_new)
             self._adjusted_growth = (0.25 * self._adjusted_growth + 0.75 * self._adjustments[-1]
                                      + np.mean(self._adjustments))
@@ -336,6 +349,11 @@ class Masking:
                 or self.growth_mode not in _engine.MASK_GROWTH or self.redistribution_mode not in ("none", "nonzero")
                 or not callable(getattr(eng, "mask_update", None)) or not _engine.has_mask_update(eng.lib)):
             return None
+        return self._engine_slices(eng)
+
+    def _engine_slices(self, eng):
+        """(engine, layer indices, [(name, flat offset, shape)]) when every masked parameter is the weight of an engine layer
+        living in the engine's own vectors, else None"""
         views = [eng.view("params"), eng.view("grads")]
         if not self.dense_gradients:
             views += [eng.view("exp_avg"), eng.view("exp_avg_sq")]
@@ -361,17 +379,47 @@ class Masking:
         self._push_masks()                      # mask_dict is the truth (callers replace its entries)
         rows = torch.empty(len(layers) + 1, _engine.MASK_STATS_WORDS, dtype=torch.int64, device=eng.device)
         eng.mask_update(layers, self.prune_rate, _engine.MASK_GROWTH[self.growth_mode], self.dense_gradients, rows)
+        self._adopt_engine_masks(eng, slices)
+        self.mask_step += 1
+        self._pending.append((rows, [pname for pname, _, _ in slices], False))
+
+    def _device_plan_global(self):
+        """_device_plan() for the modes Pruning ships with: global-magnitude pruning without growth, on an engine that has
+        sf_mask_prune_global."""
+        from ... import _engine
+        eng = self.module.bound_engine
+        if (self.device_update != "auto" or eng is None or os.environ.get("SIREN_FIT_DEVICE_MASK") == "0"
+                or not self.module.state_is_live or self.prune_mode != "global-magnitude" or self.growth_mode != "none"
+                or self.redistribution_mode not in ("none", "nonzero")
+                or not callable(getattr(eng, "mask_prune_global", None)) or not _engine.has_mask_prune_global(eng.lib)):
+            return None
+        return self._engine_slices(eng)
+
+    @torch.no_grad()
+    def _device_update_global(self, eng, layers, slices):
+        """update_connections() as one sf_mask_prune_global: nothing is read back here unless the update before this one is
+        still pending - the search starts from the threshold that one left."""
+        from ... import _engine
+        threshold = self.prune_threshold        # (completes a pending update: one transfer)
+        self._push_masks()
+        target = math.ceil(self.prune_rate * self.baseline_nonzero)
+        rows = torch.empty(len(layers) + 1, _engine.MASK_STATS_WORDS, dtype=torch.int64, device=eng.device)
+        eng.mask_prune_global(layers, target, self.prune_rate, threshold, self.increment, self.tolerance,
+                              self.dense_gradients, rows)
+        self._adopt_engine_masks(eng, slices)
+        self.mask_step += 1
+        self._pending.append((rows, [pname for pname, _, _ in slices], True))
+
+    def _adopt_engine_masks(self, eng, slices):
         flat = eng.view("masks")
         for pname, off, shape in slices:        # own tensors, never views: a re-made handle frees the old mask vector
             del self.mask_dict[pname]
             self.mask_dict[pname] = flat[off:off + shape.numel()].view(shape).clone()
-        self.mask_step += 1
-        self._pending.append((rows, [pname for pname, _, _ in slices]))
 
     def update_connections(self):
-        plan = self._device_plan()
+        plan = self._device_plan_global() if self.global_prune else self._device_plan()
         if plan is not None:
-            return self._device_update(*plan)
+            return self._device_update_global(*plan) if self.global_prune else self._device_update(*plan)
         self.truncate_weights()
 
     # ---- checkpoint surface (core.py:495-506, 660-669) -----------------------------------------

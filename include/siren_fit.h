@@ -237,6 +237,59 @@ typedef struct sf_mask_update_args {
   sf_mask_layer_stats* stats_dev;
 } sf_mask_update_args;
 int sf_mask_update(sf_handle* h, const sf_mask_update_args* a);
+/* One global-magnitude topology update (masking=Pruning: Masking.update_connections of the reference with
+ * funcs/prune.py:54-104 global_magnitude_prune and growth_mode none) on the handle's stream: six launches whatever the depth
+ * and however many trials the threshold search takes, NO device-to-host copy and no host synchronisation (csrc/siren_mask.hip).
+ * The state is the handle's flat fp32 vectors, as for sf_mask_update.
+ *   layers [n_layers]  host array: the engine layer indices, ascending, whose WEIGHT is masked
+ *   target             ceil(prune_rate * baseline_nonzero): how many live weights the threshold should remove
+ *   prune_rate         the current rate r of the decay schedule (bookkeeping of step 2 only)
+ *   threshold          the threshold the search starts from (Masking.prune_threshold)
+ *   increment          the first relative nudge (Masking.increment), tolerance: the relative slack (Masking.tolerance)
+ *   dense_gradients    0: the moments and the gradient are masked too
+ *   stats_dev          device, n_layers rows + one status row, may be NULL
+ * Counts are exact integers; all threshold arithmetic is IEEE double, round to nearest, no FMA contraction, no fast-math:
+ *   1. per listed layer j: live_j = #{k == 1}, dead_j = #{k == 0}, nnz_j = #{w != 0}; S = sum nnz_j, alive = sum live_j.
+ *      S == 0 leaves the state untouched and sets status 1
+ *   2. rate_j: step 2 of sf_mask_update with r = prune_rate
+ *   3. target <= 0: no search - the masks keep their values, removed = 0, trials = 0, the threshold is unchanged; steps 6 and 7 run
+ *   4. slack = target * tolerance; step = increment; removed = previous = stalled = 0
+ *      while |removed - target| > slack:
+ *        a. removed = alive - #{ i in the listed layers : |w_i| > f32(threshold) }; trials += 1
+ *           (f32: the double rounded to fp32, to nearest-even; an fp32 `>` over every element, dead ones included)
+ *        b. stalled = stalled + 1 if removed == previous else 0
+ *        c. if stalled == 10: break                (before any nudge)
+ *        d. previous = removed
+ *        e. if   removed > target * (1.0 + tolerance): threshold *= 1.0 - step; step *= 0.99
+ *           elif removed < target * (1.0 - tolerance): threshold *= 1.0 + step; step *= 0.99
+ *      (target converts to double exactly.)  The loop evaluates at most 4096 trials (kPruneTrialCap): a search that would
+ *      evaluate one more sets status 2 and leaves masks, state and threshold untouched.  The loop itself stalls long before
+ *      
+ *   5. a search ran: k_i = |w_i| > f32(threshold) ? 1 : 0 for every element of the listed layers, with the final threshold
+ *   6. w_i *= k_i (a product: a pruned negative weight becomes -0.0); dense_gradients == 0: also m_i *= k_i, v_i *= k_i,
+ *      g_i *= k_i.  The weight images are marked dirty
+ *   7. row j: live, dead, nnz before; removed = live_before - live_after; live, dead, nnz after; rate_j.
+ *      The status row (row n_layers), as eight 64-bit words in the order of the sf_mask_layer_stats fields:
+ *        [0] live_before = status (0 done, 1 S == 0, 2 trial cap)   [1] dead_before = trials   [2] nnz_before = alive
+ *        [3] removed = the last count the search evaluated (0 without a search: what the host function returns)
+ *        [4] live_after = target   [5] dead_after = 0   [6] nnz_after = 0
+ *        [7] prune_rate = the final threshold, a double (status 1 or 2: the threshold passed in)
+ *      With status 1 or 2 rows 0 .. n_layers - 1 hold the counts before, copied to the counts after, removed 0, rate 0.
+ * There is no tie rule: the mask is a function of each value alone, so the device result equals the host path's bit for bit.
+ * SF_ERR_INVALID / SF_ERR_STATE, before anything is launched: everything sf_mask_update refuses (a null pointer, a wrong
+ * abi_version, a render handle, a FourierNet or WaveletSiren handle, a handle with Feathermap attached, no masks set
+ * (SF_ERR_STATE), a layer index out of range or not ascending), a threshold that is not finite and > 0, an increment outside
+ * (0, 1), a negative or non-finite tolerance, a negative target.  The first call allocates 4 bytes per parameter of key
+ * scratch on the handle (freed with it). */
+typedef struct sf_mask_prune_global_args {
+  int32_t abi_version, n_layers;
+  const int32_t* layers;
+  int64_t target;
+  double prune_rate, threshold, increment, tolerance;
+  int32_t dense_gradients;
+  sf_mask_layer_stats* stats_dev;
+} sf_mask_prune_global_args;
+int sf_mask_prune_global(sf_handle* h, const sf_mask_prune_global_args* a);
 /* test aid for the "never throws" promise above: raises inside the library on purpose (0: std::bad_alloc -> SF_ERR_NOMEM,
  * 1: std::runtime_error, 2: a non-std exception -> SF_ERR_INVALID); every entry point is a function-try-block */
 int sf_debug_throw(int32_t kind);

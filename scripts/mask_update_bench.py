@@ -17,8 +17,16 @@ median lies below the parent's by more than the parent's own min - max spread th
 
 Then `python -m implicit_image.fit masking=RigL quant=none train.num_steps=2000` at the first two shapes, parent against
 head, alternating, --fit-runs runs each: the `seconds` of result.json (the fit loop's wall time).
+
+    python scripts/mask_update_bench.py --config pruning --parent <tree> [--out profiles/prune_global_bench.json]
+
+The same for masking=Pruning (conf/masking/Pruning.yaml: global-magnitude pruning, an update every 10 steps) and
+sf_mask_prune_global: 10 training steps before each update, the trial count of every device update from its status row, the
+fit at the first shape with PSNR compared to the last bit; the three sides run in every one of their six orders in turn.  In this mode every worker and every fit runs under a `timeout` of
+its own, and the script stops at the first failure.
 """
 import argparse
+import itertools
 import json
 import os
 import statistics
@@ -30,6 +38,9 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(64, 4, 256), (256, 8, 512), (256, 8, 1024), (512, 8, 512)]       # hidden, depth, image side
 INTERVAL = 20
+PRUNE_SHAPES = [(64, 4, 256), (256, 8, 512), (512, 8, 512)]
+PRUNE_INTERVAL = 10
+WORKER_LIMIT, FIT_LIMIT = 900, 600                                            # seconds, --config pruning
 
 
 def tree_env(tree, knob=None):
@@ -40,7 +51,7 @@ def tree_env(tree, knob=None):
     return env
 
 
-def worker(hidden, depth, side):
+def worker(hidden, depth, side, pruning=False):
     """reads one line per update from stdin, answers with the milliseconds of that update"""
     import torch
     from implicit_image.data import get_grid
@@ -53,6 +64,12 @@ def worker(hidden, depth, side):
     mcfg = Cfg(name="RigL", density=0.5, sparse_init="erdos-renyi-kernel", dense_gradients=True,
                growth_mode="absolute-gradient", prune_mode="magnitude", redistribution_mode="none", dense=False,
                prune_rate=0.1, decay_schedule="cosine", end_when=1500, interval=INTERVAL)
+    interval = INTERVAL
+    if pruning:
+        mcfg = Cfg(name="Pruning", density=1.0, sparse_init="random", final_density=0.5, dense_gradients=True,
+                   growth_mode="none", prune_mode="global-magnitude", redistribution_mode="none", dense=False,
+                   decay_schedule="magnitude-prune", start_when=5, end_when=1500, interval=PRUNE_INTERVAL)
+        interval = PRUNE_INTERVAL
     torch.manual_seed(0)
     model = registry["siren"](depth=depth, hidden_size=hidden, first_omega_0=50, hidden_omega_0=30).to("cuda")
     optim, sched = get_optimizer_lr_scheduler(model, Cfg(name="adam", lr=3e-4))
@@ -60,25 +77,30 @@ def worker(hidden, depth, side):
     grid, img = get_grid(side, side).cuda(), so.synthetic_image(side, side, seed=3).cuda().contiguous()
     print("ready", flush=True)
     for _ in sys.stdin:
-        train_steps(model, optim, grid, img, INTERVAL, lr_scheduler=sched, mask=mask)
+        train_steps(model, optim, grid, img, interval, lr_scheduler=sched, mask=mask)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         mask.update_connections()
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3
-        pending = len(getattr(mask, "_pending", []))
+        pending = getattr(mask, "_pending", [])
+        trials = int(pending[-1][0][-1, 1]) if pruning and pending else None      # (the status row of sf_mask_prune_global)
+        pending = len(pending)
         density = mask.stats.total_density          # (outside the timed span: where the fit's log line reads it)
-        print(json.dumps({"ms": ms, "device": pending, "density": density}), flush=True)
+        print(json.dumps({"ms": ms, "device": pending, "density": density, "trials": trials}), flush=True)
 
 
 def stats(ms):
     return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
 
 
-def time_shape(trees, shape, updates, warmup):
+def time_shape(trees, shape, updates, warmup, pruning=False):
     procs = {}
     for name, (tree, knob) in trees.items():
-        procs[name] = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", *map(str, shape)], env=tree_env(tree, knob),
+        limit = ["timeout", "-k", "10", str(WORKER_LIMIT)] if pruning else []
+        mode = ["--config", "pruning"] if pruning else []
+        procs[name] = subprocess.Popen(limit + [sys.executable, os.path.abspath(__file__), *mode, "--worker", *map(str, shape)],
+                                       env=tree_env(tree, knob),
                                        cwd=tree, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
     try:
         for name, p in procs.items():
@@ -86,8 +108,13 @@ def time_shape(trees, shape, updates, warmup):
             if line != "ready":
                 raise RuntimeError(f"{name}: worker did not start ({line!r})")
         got = {name: [] for name in procs}
-        for _ in range(warmup + updates):
-            for name, p in procs.items():
+        for u in range(warmup + updates):
+            order = list(procs)
+            if pruning:                         # every order of the sides in turn, so that no side always follows the same one
+                orders = list(itertools.permutations(order))
+                order = orders[u % len(orders)]
+            for name in order:
+                p = procs[name]
                 p.stdin.write("go\n")
                 p.stdin.flush()
                 line = p.stdout.readline()
@@ -104,6 +131,14 @@ def time_shape(trees, shape, updates, warmup):
     for name, rs in got.items():
         res[name]["device_updates"] = sum(r["device"] for r in rs)
         res[name]["density_last"] = rs[-1]["density"]
+        if pruning and any(r.get("trials") is not None for r in rs):
+            res[name]["trials"] = [r["trials"] for r in rs]
+    if pruning:                                 # update by update (every side sees the same sequence of searches): the cost follows the
+        for name, rs in got.items():            # trial count, so the sides are also compared pairwise
+            res[name]["ms"] = [round(r["ms"], 4) for r in rs[warmup:]]
+        for name in ("head_device", "head_host"):
+            ratios = [a / b for a, b in zip(res[name]["ms"], res["parent"]["ms"])]
+            res[name]["paired_ratio_to_parent"] = {"median": statistics.median(ratios), "min": min(ratios), "max": max(ratios)}
     par, dev = res["parent"], res["head_device"]
     res["parent_spread_ms"] = par["max_ms"] - par["min_ms"]
     res["accepted"] = bool(dev["median_ms"] < par["median_ms"] - res["parent_spread_ms"])
@@ -111,16 +146,17 @@ def time_shape(trees, shape, updates, warmup):
     return res
 
 
-def time_fit(trees, shape, runs):
+def time_fit(trees, shape, runs, masking="RigL"):
     hidden, depth, side = shape
-    over = ["masking=RigL", "quant=none", "train.num_steps=2000", f"img.height={side}", f"img.width={side}",
+    limit = ["timeout", "-k", "10", str(FIT_LIMIT)] if masking == "Pruning" else []
+    over = [f"masking={masking}", "quant=none", "train.num_steps=2000", f"img.height={side}", f"img.width={side}",
             f"mlp.hidden_size={hidden}", f"mlp.depth={depth}"]
     got = {name: [] for name in trees}
     for _ in range(runs):
         for name, (tree, knob) in trees.items():
             with tempfile.TemporaryDirectory() as tmp:
                 env = dict(tree_env(tree, knob), IIC_CONF=os.path.join(tree, "conf"))
-                subprocess.run([sys.executable, "-m", "implicit_image.fit"] + over, cwd=tmp, env=env, check=True,
+                subprocess.run(limit + [sys.executable, "-m", "implicit_image.fit"] + over, cwd=tmp, env=env, check=True,
                                stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
                 found = [os.path.join(dp, "result.json") for dp, _, fs in os.walk(tmp) if "result.json" in fs]
                 got[name].append(json.load(open(found[0])))
@@ -133,11 +169,15 @@ def main():
     ap.add_argument("--updates", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fit-runs", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mask_update_bench.json"))
+    ap.add_argument("--config", choices=("rigl", "pruning"), default="rigl")
+    ap.add_argument("--out")
     ap.add_argument("--worker", nargs=3, type=int, metavar=("HIDDEN", "DEPTH", "SIDE"))
     args = ap.parse_args()
+    pruning = args.config == "pruning"
     if args.worker:
-        return worker(*args.worker)
+        return worker(*args.worker, pruning=pruning)
+    if not args.out:
+        args.out = os.path.join(ROOT, "profiles", "prune_global_bench.json" if pruning else "mask_update_bench.json")
     if not args.parent or not os.path.exists(os.path.join(args.parent, "implicit-image-compression_amd", "csrc", "libsiren_fit.so")):
         ap.error("--parent: a tree of the parent commit with libsiren_fit.so built in place")
     if args.updates < 20:
@@ -148,17 +188,24 @@ def main():
                    "the three sides alternating update by update in worker processes of their own; then the fit loop's "
                    "seconds (as ms) of the default masked fit at 2000 steps, parent against head, alternating",
            "config": "RigL (conf/masking/RigL.yaml), density 0.5", "shapes": {}, "fit": {}}
-    for shape in SHAPES:
+    shapes, fit_shapes, masking = SHAPES, SHAPES[:2], "RigL"
+    if pruning:
+        shapes, fit_shapes, masking = PRUNE_SHAPES, PRUNE_SHAPES[:1], "Pruning"
+        res["what"] = res["what"].replace("20 training steps", "10 training steps")
+        res["config"] = "Pruning (conf/masking/Pruning.yaml); trials: the threshold search's trial count per device update"
+    for shape in shapes:
         tag = f"{shape[0]}x{shape[1]}@{shape[2]}"
-        r = res["shapes"][tag] = time_shape(trees, shape, args.updates, args.warmup)
+        r = res["shapes"][tag] = time_shape(trees, shape, args.updates, args.warmup, pruning)
         print(json.dumps({tag: {k: (round(v["median_ms"], 3), round(v["min_ms"], 3), round(v["max_ms"], 3))
                                 for k, v in r.items() if isinstance(v, dict)}, "accepted": r["accepted"]}), flush=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
-    for shape in SHAPES[:2]:
+    for shape in fit_shapes:
         tag = f"{shape[0]}x{shape[1]}@{shape[2]}"
-        r = res["fit"][tag] = time_fit({k: trees[k] for k in ("parent", "head_device")}, shape, args.fit_runs)
-        print(json.dumps({"fit " + tag: {k: round(v["median_ms"], 1) for k, v in r.items()}}), flush=True)
+        r = res["fit"][tag] = time_fit({k: trees[k] for k in ("parent", "head_device")}, shape, args.fit_runs, masking)
+        r["psnr_equal"] = len({p for side in ("parent", "head_device") for p in r[side]["PSNR"]}) == 1
+        print(json.dumps({"fit " + tag: {k: round(v["median_ms"], 1) for k, v in r.items() if isinstance(v, dict)},
+                          "psnr_equal": r["psnr_equal"]}), flush=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
 
