@@ -1,12 +1,12 @@
 // siren_fit.hip — the one translation unit of the library: the kernel files, the host core (engine.h), one host file per
-// model, the model-independent entry points of the C ABI (include/siren_fit.h), the three render paths - in this order,
+// model and one for the topology updates (mask_host.hip), the model-independent entry points of the C ABI (include/siren_fit.h), the three render paths - in this order,
 // which is the order of the non-template kernels in the code object.
 //
 // One sf_engine == one per-image fit on one HIP stream.  A training step is, per pixel chunk:
 //   k_fwd -> k_bwd(last) -> k_bwd(hidden l = depth-2 .. 1) -> k_dw0, each followed by the fixed-order slab
 //   reduction into the flat fp32 gradient; then k_adam (+mask) and k_images (16-bit weight images).
-// Every `interval` steps of a masked fit the topology changes: sf_mask_update (siren_mask.hip), two more launches, or
-// sf_mask_prune_global (same file), six.
+// Every `interval` steps of a masked fit the topology changes: sf_mask_update (kernels siren_mask.hip, host mask_host.hip),
+// two more launches, or sf_mask_prune_global (same files), six.
 // The sequence mirrors one `train_epoch` of the reference (implicit_image/utils/train_helper.py:132-185)
 // for the full-batch grid (implicit_image/compress.py:137-138).
 #include "siren_kernels.hip"
@@ -98,6 +98,7 @@
 #include "fourier_host.hip"
 #include "wavelet_host.hip"
 #include "feather_host.hip"
+#include "mask_host.hip"
 
 namespace {
 
@@ -583,110 +584,6 @@ int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_de
   SF_TRY(launch(h, k_km_finish, 1, kKmMaxK, 0, centers_dev, K, h->km_ws, centroids_dev, centroids_cap, n_centroids_dev));
   if (labels_dev || new_weight_dev)
     SF_TRY(launch(h, k_km_predict, blocks, 256, 0, w_dev, n, centroids_dev, h->km_ws, (long long*)labels_dev, new_weight_dev));
-  return SF_OK;
-} SF_CATCH
-
-/* one RigL topology update of the masked layers on the handle's stream: two launches, no host synchronisation
- * (siren_mask.hip states what it computes) */
-int sf_mask_update(sf_handle* h, const sf_mask_update_args* a) try {
-  if (!h || !a || !a->layers) return fail(SF_ERR_INVALID, "null argument");
-  if (a->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
-  SF_NO_RENDER(h, "sf_mask_update");
-  switch (h->model) {
-    case Model::Siren: break;
-    case Model::Fourier: return fail(SF_ERR_INVALID, "sf_mask_update: a FourierNet handle takes no mask");
-    case Model::Wavelet: return fail(SF_ERR_INVALID, "sf_mask_update: topology updates of a WaveletSiren handle stay on the host");
-  }
-  if (h->fth.attached) return fail(SF_ERR_INVALID, "sf_mask_update: a Feathermap handle is dense (masking.dense: True)");
-  if (!h->has_mask) return fail(SF_ERR_STATE, "sf_mask_update: sf_set_masks has not been called");
-  if (a->growth != 0 && a->growth != 1) return fail(SF_ERR_INVALID, "sf_mask_update: growth must be 0 (none) or 1 (absolute gradient)");
-  if (a->n_layers < 1 || a->n_layers > h->D || a->n_layers > kMaskMaxLayers)
-    return fail(SF_ERR_INVALID, "sf_mask_update: n_layers must be 1 .. depth");
-  static_assert(sizeof(MaskRow) == sizeof(sf_mask_layer_stats), "MaskRow is sf_mask_layer_stats");
-  MaskArgs k = zeroed<MaskArgs>();
-  double bytes = 0;
-  for (int j = 0; j < a->n_layers; ++j) {
-    const int l = a->layers[j];
-    if (l < 0 || l >= h->D || (j > 0 && l <= a->layers[j - 1]))
-      return fail(SF_ERR_INVALID, "sf_mask_update: layers must be ascending indices in [0, depth)");
-    k.off[j] = h->off_w[l];
-    k.n[j] = (int)(h->off_b[l] - h->off_w[l]);
-    bytes += (double)k.n[j] * 4;
-  }
-  DevGuard dev_guard(h->cfg.device);
-  if (!a->stats_dev && !h->mask_rows) SF_TRY(dev_alloc(h, h->mask_rows, sizeof(MaskRow) * (kMaskMaxLayers + 1)));
-  k.w = h->params; k.g = h->grads; k.m = h->m; k.v = h->v; k.k = h->mask;
-  k.rows = a->stats_dev ? reinterpret_cast<MaskRow*>(a->stats_dev) : h->mask_rows;
-  k.L = a->n_layers; k.rate = a->prune_rate; k.growth = a->growth; k.dense = a->dense_gradients != 0;
-  {
-    Launch L(h, K_MASK, 0, bytes * 12);   // (about a dozen L2-resident reads of every masked layer)
-    SF_TRY(launch(h, k_mask_count, k.L, kMaskThreads, 0, k));
-    SF_TRY(launch(h, k_mask_update, k.L, kMaskThreads, 0, k));
-  }
-  h->images_dirty = true;
-  h->fth.fresh = false;
-  return SF_OK;
-} SF_CATCH
-
-/* one global-magnitude topology update (masking=Pruning) of the masked layers on the handle's stream: six launches whatever
- * the depth and the number of trials, no host synchronisation (siren_mask.hip states what it computes) */
-int sf_mask_prune_global(sf_handle* h, const sf_mask_prune_global_args* a) try {
-  if (!h || !a || !a->layers) return fail(SF_ERR_INVALID, "null argument");
-  if (a->abi_version != SF_ABI_VERSION) return fail(SF_ERR_INVALID, "abi_version mismatch");
-  SF_NO_RENDER(h, "sf_mask_prune_global");
-  switch (h->model) {
-    case Model::Siren: break;
-    case Model::Fourier: return fail(SF_ERR_INVALID, "sf_mask_prune_global: a FourierNet handle takes no mask");
-    case Model::Wavelet: return fail(SF_ERR_INVALID, "sf_mask_prune_global: topology updates of a WaveletSiren handle stay on the host");
-  }
-  if (h->fth.attached) return fail(SF_ERR_INVALID, "sf_mask_prune_global: a Feathermap handle is dense (masking.dense: True)");
-  if (!h->has_mask) return fail(SF_ERR_STATE, "sf_mask_prune_global: sf_set_masks has not been called");
-  if (!(std::isfinite(a->threshold) && a->threshold > 0.0))
-    return fail(SF_ERR_INVALID, "sf_mask_prune_global: threshold must be finite and > 0");
-  if (!(a->increment > 0.0 && a->increment < 1.0)) return fail(SF_ERR_INVALID, "sf_mask_prune_global: increment must lie in (0, 1)");
-  if (!(std::isfinite(a->tolerance) && a->tolerance >= 0.0))
-    return fail(SF_ERR_INVALID, "sf_mask_prune_global: tolerance must be finite and >= 0");
-  if (a->target < 0) return fail(SF_ERR_INVALID, "sf_mask_prune_global: target must be >= 0");
-  if (a->n_layers < 1 || a->n_layers > h->D || a->n_layers > kMaskMaxLayers)
-    return fail(SF_ERR_INVALID, "sf_mask_prune_global: n_layers must be 1 .. depth");
-  PruneArgs p = zeroed<PruneArgs>();
-  MaskArgs& k = p.m;
-  double bytes = 0;
-  int n_max = 0;
-  for (int j = 0; j < a->n_layers; ++j) {
-    const int l = a->layers[j];
-    if (l < 0 || l >= h->D || (j > 0 && l <= a->layers[j - 1]))
-      return fail(SF_ERR_INVALID, "sf_mask_prune_global: layers must be ascending indices in [0, depth)");
-    k.off[j] = h->off_w[l];
-    k.n[j] = (int)(h->off_b[l] - h->off_w[l]);
-    n_max = std::max(n_max, k.n[j]);
-    bytes += (double)k.n[j] * 4;
-  }
-  if (h->P > 0x7fffffff) return fail(SF_ERR_INVALID, "sf_mask_prune_global: more than 2^31 - 1 parameters");
-  DevGuard dev_guard(h->cfg.device);
-  if (!a->stats_dev && !h->mask_rows) SF_TRY(dev_alloc(h, h->mask_rows, sizeof(MaskRow) * (kMaskMaxLayers + 1)));
-  if (!h->prune_ws) SF_TRY(dev_alloc(h, h->prune_ws, sizeof(PruneWs)));
-  if (!h->prune_keys) SF_TRY(dev_alloc(h, h->prune_keys, (size_t)h->P * 4));
-  k.w = h->params; k.g = h->grads; k.m = h->m; k.v = h->v; k.k = h->mask;
-  k.rows = a->stats_dev ? reinterpret_cast<MaskRow*>(a->stats_dev) : h->mask_rows;
-  k.L = a->n_layers; k.rate = a->prune_rate; k.dense = a->dense_gradients != 0;
-  p.ws = h->prune_ws; p.keys = h->prune_keys; p.cap = (int)h->P;
-  p.target = a->target; p.threshold = a->threshold; p.increment = a->increment; p.tolerance = a->tolerance;
-  // strides per layer: 16 elements per thread of the largest layer, at most four workgroups per compute unit in all
-  const int per_layer = std::max(1, std::min((n_max + kMaskThreads * 16 - 1) / (kMaskThreads * 16), 4 * h->dw_wg / k.L));
-  const dim3 grid(k.L, per_layer);
-  {
-    Launch L(h, K_MASK_PRUNE, 0, bytes * 12);   // (the weights three times, the keys, the five state vectors once)
-    HIPCHK(hipMemsetAsync(h->prune_ws->hist, 0, sizeof(h->prune_ws->hist), h->ctx->stream));
-    SF_TRY(launch(h, k_mask_count, k.L, kMaskThreads, 0, k));
-    SF_TRY(launch(h, k_prune_file<false>, grid, kMaskThreads, 0, p));
-    SF_TRY(launch(h, k_prune_scan, 1, kMaskThreads, 0, p));
-    SF_TRY(launch(h, k_prune_file<true>, grid, kMaskThreads, 0, p));
-    SF_TRY(launch(h, k_prune_search, 1, kMaskThreads, 0, p));
-    SF_TRY(launch(h, k_prune_apply, grid, kMaskThreads, 0, p));
-  }
-  h->images_dirty = true;
-  h->fth.fresh = false;
   return SF_OK;
 } SF_CATCH
 

@@ -29,7 +29,9 @@
 // registers and kept out of the histogram.  Every count is an integer (LDS integer atomics commute): the result does not
 // depend on the order in which waves arrive.  Every loop runs a trip count derived from n and the wave index, so every
 // barrier is reached by every thread of the workgroup.
-// (included by siren_fit.hip)
+// A device helper that holds a barrier or a wave-wide ballot is left early only on a condition that is uniform over the
+// workgroup (the wave), and says so.
+// (included by siren_fit.hip; the two entry points are in mask_host.hip)
 
 namespace sf {
 
@@ -66,8 +68,59 @@ struct MaskLds {
   int done;
   MaskSel sel;
   int wave_cnt[kMaskWaves];
-  int acc[4];
+  int acc[4];                     // live, dead, non-zero after the update; the live weights the prune removed
 };
+
+struct MaskLayer {                // the state of one masked layer
+  float *w, *g, *m, *v, *k;
+  int n;
+};
+
+__device__ __forceinline__ MaskLayer mask_layer(const MaskArgs& a, int j) {
+  const long long o = a.off[j];
+  return {a.w + o, a.g + o, a.m + o, a.v + o, a.k + o, a.n[j]};
+}
+
+// step 2 of the contract: the rate of layer j (n elements) of L, from the counts of its row; S the non-zeros of all layers
+__device__ __forceinline__ double mask_rate(const MaskRow* rows, int j, int n, int L, long long S, double r) {
+  const double share = (double)rows[j].nnz_before / (double)S, frac_dead = (double)rows[j].dead_before / (double)n;
+  const bool capped = frac_dead < 0.2 && (1.0 / (double)L) / share < 1.0;
+  return capped ? fmin(frac_dead, r) : r;
+}
+
+// The count-and-commit form of every kernel that counts: a lane tallies its own elements, the wave adds its lanes up once,
+// and lane 0 adds the wave's sums to acc[0 .. 2] (live, dead, non-zero) in LDS.  The caller zeroes acc behind a barrier
+// before and reads it behind one after; every lane of a wave reaches commit (a wave-wide shuffle).
+struct MaskTally {
+  int live, dead, nnz;
+  __device__ __forceinline__ void add(float wv, float kv) {
+    live += kv == 1.0f;
+    dead += kv == 0.0f;
+    nnz += wv != 0.0f;
+  }
+  __device__ __forceinline__ void commit(int* acc, int lane) {
+    for (int d = 32; d > 0; d >>= 1) {
+      live += __shfl_down(live, d);
+      dead += __shfl_down(dead, d);
+      nnz += __shfl_down(nnz, d);
+    }
+    if (lane == 0) { atomicAdd(&acc[0], live); atomicAdd(&acc[1], dead); atomicAdd(&acc[2], nnz); }
+  }
+};
+
+// step 6 of the contract for element i, whose weight wv, gradient gv (read only with sparse gradients) and new mask value kv
+// the caller holds, and its share of the counts of step 7.  Products: a pruned negative weight becomes -0.0.
+__device__ __forceinline__ void mask_apply(const MaskLayer& p, int i, float wv, float gv, float kv, bool sparse_grads,
+                                           MaskTally& c) {
+  wv = __fmul_rn(wv, kv);
+  p.w[i] = wv;
+  if (sparse_grads) {
+    p.m[i] = __fmul_rn(p.m[i], kv);
+    p.v[i] = __fmul_rn(p.v[i], kv);
+    p.g[i] = __fmul_rn(gv, kv);
+  }
+  c.add(wv, kv);
+}
 
 // one wave-wide addition per distinct digit of a 64-element step (the top digit of a float takes a handful of values)
 __device__ __forceinline__ void mask_hist_add(int* hist, unsigned digit, bool valid, int lane) {
@@ -81,11 +134,26 @@ __device__ __forceinline__ void mask_hist_add(int* hist, unsigned digit, bool va
   }
 }
 
-// key of element i: prune, the bits of |w|; grow, the complement of the bits of |g| * (1 - k) - smallest key first both times
+// key of an element: prune, the bits of |w|; grow, the complement of the bits of |g| * (1 - k) - smallest key first both times
+template <bool GROW>
+__device__ __forceinline__ unsigned mask_key(float x, float k) {
+  if (GROW) return ~__float_as_uint(__fmul_rn(fabsf(x), __fsub_rn(1.0f, k)));
+  return __float_as_uint(x) & 0x7fffffffu;
+}
 template <bool GROW>
 __device__ __forceinline__ unsigned mask_key(const float* x, const float* k, int i) {
-  if (GROW) return ~__float_as_uint(__fmul_rn(fabsf(x[i]), __fsub_rn(1.0f, k[i])));
-  return __float_as_uint(x[i]) & 0x7fffffffu;
+  return mask_key<GROW>(x[i], GROW ? k[i] : 0.0f);
+}
+
+// The tie-ranked pick of one 64-element step of a wave's segment: every key below the boundary, and the boundary's ties up to
+// rank sel.take (all: every tie).  run: the ties before this step, advanced by the step's.  A wave-wide ballot: every lane
+// of the wave calls it, `in` false where the lane has no element.
+__device__ __forceinline__ bool mask_pick(unsigned key, bool in, const MaskSel& sel, bool all, int& run, int lane) {
+  const bool tie = in && key == sel.T;
+  const unsigned long long tb = __ballot(tie);
+  const int rank = run + __popcll(tb & ((1ull << lane) - 1ull));
+  run += __popcll(tb);
+  return in && (key < sel.T || (tie && (all || rank < sel.take)));
 }
 
 // The K-th smallest key of n (1 <= K <= n) and the number of its ties inside the selection -> s.sel.  x: the weights
@@ -170,37 +238,21 @@ __device__ int mask_tie_base(const float* x, const float* k, int n, int seg, Mas
 // live / dead / non-zero counts of every masked layer -> its row (the "after" fields start as a copy); status row cleared
 __global__ __launch_bounds__(kMaskThreads) void k_mask_count(MaskArgs a) {
   __shared__ int acc[3];
-  const int j = blockIdx.x, t = threadIdx.x, lane = t & 63;
-  const int n = a.n[j];
-  const float* __restrict__ w = a.w + a.off[j];
-  const float* __restrict__ k = a.k + a.off[j];
+  const int j = blockIdx.x, t = threadIdx.x;
+  const MaskLayer p = mask_layer(a, j);
   if (t < 3) acc[t] = 0;
   __syncthreads();
-  int live = 0, dead = 0, nnz = 0;
-  for (int base = t - lane; base < n; base += kMaskThreads) {
-    const int i = base + lane;
-    const bool in = i < n;
-    const float kv = in ? k[i] : -1.0f, wv = in ? w[i] : 0.0f;
-    live += __popcll(__ballot(kv == 1.0f));
-    dead += __popcll(__ballot(kv == 0.0f));
-    nnz += __popcll(__ballot(wv != 0.0f));
-  }
-  if (lane == 0) { atomicAdd(&acc[0], live); atomicAdd(&acc[1], dead); atomicAdd(&acc[2], nnz); }
+  MaskTally c{};
+  for (int i = t; i < p.n; i += kMaskThreads) c.add(p.w[i], p.k[i]);
+  c.commit(acc, t & 63);
   __syncthreads();
   if (t == 0) {
-    MaskRow r;
+    MaskRow r{};
     r.live_before = r.live_after = acc[0];
     r.dead_before = r.dead_after = acc[1];
     r.nnz_before = r.nnz_after = acc[2];
-    r.removed = 0;
-    r.prune_rate = 0.0;
     a.rows[j] = r;
-    if (j == 0) {
-      MaskRow z;
-      z.live_before = z.dead_before = z.nnz_before = z.removed = z.live_after = z.dead_after = z.nnz_after = 0;
-      z.prune_rate = 0.0;
-      a.rows[a.L] = z;
-    }
+    if (j == 0) a.rows[a.L] = MaskRow{};
   }
 }
 
@@ -208,20 +260,16 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_count(MaskArgs a) {
 __global__ __launch_bounds__(kMaskThreads) void k_mask_update(MaskArgs a) {
   __shared__ MaskLds s;
   const int j = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int n = a.n[j];
-  float* w = a.w + a.off[j];
-  float* g = a.g + a.off[j];
-  float* k = a.k + a.off[j];
+  const MaskLayer p = mask_layer(a, j);
+  const int n = p.n;
   long long S = 0;
   for (int l = 0; l < a.L; ++l) S += a.rows[l].nnz_before;
   if (S == 0) {                                               // (uniform over the grid: nothing is touched)
     if (j == 0 && t == 0) a.rows[a.L].live_before = 1;
     return;
   }
-  const long long live0 = a.rows[j].live_before, dead0 = a.rows[j].dead_before, nnz0 = a.rows[j].nnz_before;
-  const double share = (double)nnz0 / (double)S, frac_dead = (double)dead0 / (double)n;
-  const bool capped = frac_dead < 0.2 && (1.0 / (double)a.L) / share < 1.0;
-  const double rate = capped ? fmin(frac_dead, a.rate) : a.rate;
+  const long long live0 = a.rows[j].live_before, dead0 = a.rows[j].dead_before;
+  const double rate = mask_rate(a.rows, j, n, a.L, S, a.rate);
   const double dropd = ceil(rate * (double)live0);
   const int seg = ((n + kMaskWaves - 1) / kMaskWaves + 63) / 64 * 64;
   const int end = min(n, (wave + 1) * seg);
@@ -232,82 +280,57 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_update(MaskArgs a) {
   int removed = 0;
   if (dropd > 0.0) {
     const int K = (int)fmin((double)dead0 + dropd, (double)n);
-    mask_select<false>(w, k, n, K, s);
-    const int before = mask_tie_base<false>(w, k, n, seg, s);
+    mask_select<false>(p.w, p.k, n, K, s);
+    int run = mask_tie_base<false>(p.w, p.k, n, seg, s), gone = 0;
     const MaskSel sel = s.sel;
     const bool all = sel.take >= sel.ties;
-    int run = before, gone = 0;
     for (int base = wave * seg; base < end; base += 64) {
       const int i = base + lane;
       const bool in = i < end;
-      const unsigned key = in ? mask_key<false>(w, k, i) : 0xffffffffu;
-      const bool tie = in && key == sel.T;
-      const unsigned long long tb = __ballot(tie);
-      const int rank = run + __popcll(tb & ((1ull << lane) - 1ull));
-      run += __popcll(tb);
-      const bool pick = in && (key < sel.T || (tie && (all || rank < sel.take)));
-      const bool was_live = pick && k[i] == 1.0f;
-      if (pick) k[i] = 0.0f;
+      const bool pick = mask_pick(in ? mask_key<false>(p.w, p.k, i) : 0xffffffffu, in, sel, all, run, lane);
+      const bool was_live = pick && p.k[i] == 1.0f;
+      if (pick) p.k[i] = 0.0f;
       gone += __popcll(__ballot(was_live));
     }
-    if (lane == 0 && gone) atomicAdd(&s.acc[0], gone);
+    if (lane == 0 && gone) atomicAdd(&s.acc[3], gone);
     __syncthreads();                                          // (the new k of every wave is visible to the growth below)
-    removed = s.acc[0];
+    removed = s.acc[3];
   }
 
   // 5. grow
   const bool grow = a.growth == 1 && removed > 0;   // (removed > 0: not every k of the layer is 1)
-  int before = 0;
+  int run = 0;
   if (grow) {
-    mask_select<true>(g, k, n, min(removed, n), s);
-    before = mask_tie_base<true>(g, k, n, seg, s);
+    mask_select<true>(p.g, p.k, n, min(removed, n), s);
+    run = mask_tie_base<true>(p.g, p.k, n, seg, s);
   }
   const MaskSel sel = s.sel;
   const bool all = sel.take >= sel.ties;
 
   // 5. (the picks) + 6. apply + the counts of 7.
   const bool sparse_grads = a.dense == 0;
-  float* m = a.m + a.off[j];
-  float* v = a.v + a.off[j];
-  int run = before, live = 0, dead = 0, nnz = 0;
+  MaskTally c{};
   for (int base = wave * seg; base < end; base += 64) {
     const int i = base + lane;
     const bool in = i < end;
-    float kv = in ? k[i] : -1.0f, wv = in ? w[i] : 0.0f;
-    const float gv = in ? g[i] : 0.0f;
-    if (grow) {
-      const unsigned key = in ? ~__float_as_uint(__fmul_rn(fabsf(gv), __fsub_rn(1.0f, kv))) : 0xffffffffu;
-      const bool tie = in && key == sel.T;
-      const unsigned long long tb = __ballot(tie);
-      const int rank = run + __popcll(tb & ((1ull << lane) - 1ull));
-      run += __popcll(tb);
-      if (in && (key < sel.T || (tie && (all || rank < sel.take)))) {
-        kv = 1.0f;
-        wv = 0.0f;
-        k[i] = 1.0f;
-      }
+    float kv = in ? p.k[i] : -1.0f, wv = in ? p.w[i] : 0.0f;
+    const float gv = in ? p.g[i] : 0.0f;
+    // (grow is uniform over the workgroup: every lane of the wave reaches the pick's ballot or none does)
+    if (grow && mask_pick(in ? mask_key<true>(gv, kv) : 0xffffffffu, in, sel, all, run, lane)) {
+      kv = 1.0f;
+      wv = 0.0f;
+      p.k[i] = 1.0f;
     }
-    if (in) {
-      wv = __fmul_rn(wv, kv);
-      w[i] = wv;
-      if (sparse_grads) {
-        m[i] = __fmul_rn(m[i], kv);
-        v[i] = __fmul_rn(v[i], kv);
-        g[i] = __fmul_rn(gv, kv);
-      }
-    }
-    live += __popcll(__ballot(kv == 1.0f));
-    dead += __popcll(__ballot(kv == 0.0f));
-    nnz += __popcll(__ballot(in && wv != 0.0f));
+    if (in) mask_apply(p, i, wv, gv, kv, sparse_grads, c);
   }
-  if (lane == 0) { atomicAdd(&s.acc[1], live); atomicAdd(&s.acc[2], dead); atomicAdd(&s.acc[3], nnz); }
+  c.commit(s.acc, lane);
   __syncthreads();
   if (t == 0) {
     MaskRow& r = a.rows[j];
     r.removed = removed;
-    r.live_after = s.acc[1];
-    r.dead_after = s.acc[2];
-    r.nnz_after = s.acc[3];
+    r.live_after = s.acc[0];
+    r.dead_after = s.acc[1];
+    r.nnz_after = s.acc[2];
     r.prune_rate = rate;
   }
 }
@@ -381,10 +404,9 @@ __device__ __forceinline__ bool prune_filed(unsigned key) { return key != 0u && 
 // the next free slot of its bucket (hist holds the cursors, k_prune_scan set them to the bucket starts)
 template <bool SCATTER>
 __global__ __launch_bounds__(kMaskThreads) void k_prune_file(PruneArgs a) {
-  const int j = blockIdx.x, n = a.m.n[j];
-  const float* __restrict__ w = a.m.w + a.m.off[j];
-  for (int i = blockIdx.y * kMaskThreads + threadIdx.x; i < n; i += gridDim.y * kMaskThreads) {
-    const unsigned key = __float_as_uint(w[i]) & 0x7fffffffu;
+  const MaskLayer p = mask_layer(a.m, blockIdx.x);
+  for (int i = blockIdx.y * kMaskThreads + threadIdx.x; i < p.n; i += gridDim.y * kMaskThreads) {
+    const unsigned key = mask_key<false>(p.w, p.k, i);
     if (!prune_filed(key)) continue;
     const int pos = atomicAdd(&a.ws->hist[key >> 15], 1);
     if (SCATTER && pos >= 0 && pos < a.cap) a.keys[pos] = key;
@@ -501,24 +523,19 @@ __global__ __launch_bounds__(kMaskThreads) void k_prune_search(PruneArgs a) {
   if (t == 0) {
     a.ws->ctl.mode = touch ? mode : 0;
     a.ws->ctl.tkey = __float_as_uint(__double2float_rn(thr));
-    MaskRow z;
+    MaskRow z{};
     z.live_before = status;
     z.dead_before = trials;
     z.nnz_before = alive;
     z.removed = removed;
     z.live_after = target;
-    z.dead_after = 0;
-    z.nnz_after = 0;
     z.prune_rate = status == 0 ? thr : a.threshold;
     rows[L] = z;
     s.touch = touch;
   }
   __syncthreads();
   if (t < L && s.touch) {                                        // 2. the rates; the "after" counts restart for k_prune_apply
-    const long long dead0 = rows[t].dead_before, nnz0 = rows[t].nnz_before;
-    const double share = (double)nnz0 / (double)S, frac_dead = (double)dead0 / (double)a.m.n[t];
-    const bool capped = frac_dead < 0.2 && (1.0 / (double)L) / share < 1.0;
-    rows[t].prune_rate = capped ? fmin(frac_dead, a.m.rate) : a.m.rate;
+    rows[t].prune_rate = mask_rate(rows, t, a.m.n[t], L, S, a.m.rate);
     rows[t].removed = rows[t].live_before;
     rows[t].live_after = rows[t].dead_after = rows[t].nnz_after = 0;
   }
@@ -530,40 +547,23 @@ __global__ __launch_bounds__(kMaskThreads) void k_prune_apply(PruneArgs a) {
   const int mode = a.ws->ctl.mode;
   if (mode == 0) return;                                      // (uniform over the grid)
   const unsigned tkey = a.ws->ctl.tkey;
-  const int j = blockIdx.x, n = a.m.n[j], t = threadIdx.x, lane = t & 63;
-  float* w = a.m.w + a.m.off[j];
-  float* g = a.m.g + a.m.off[j];
-  float* m = a.m.m + a.m.off[j];
-  float* v = a.m.v + a.m.off[j];
-  float* k = a.m.k + a.m.off[j];
+  const int j = blockIdx.x, t = threadIdx.x;
+  const MaskLayer p = mask_layer(a.m, j);
   const bool sparse_grads = a.m.dense == 0;
   if (t < 3) acc[t] = 0;
   __syncthreads();
-  int live = 0, dead = 0, nnz = 0;
-  for (int i = blockIdx.y * kMaskThreads + t; i < n; i += gridDim.y * kMaskThreads) {
-    float wv = w[i], kv = k[i];
+  MaskTally c{};
+  for (int i = blockIdx.y * kMaskThreads + t; i < p.n; i += gridDim.y * kMaskThreads) {
+    const float wv = p.w[i];
+    float kv = p.k[i];
     if (mode == 2) {
-      const unsigned key = __float_as_uint(wv) & 0x7fffffffu;
+      const unsigned key = mask_key<false>(wv, kv);
       kv = key > tkey && key <= kPruneInf ? 1.0f : 0.0f;
-      k[i] = kv;
+      p.k[i] = kv;
     }
-    wv = __fmul_rn(wv, kv);
-    w[i] = wv;
-    if (sparse_grads) {
-      m[i] = __fmul_rn(m[i], kv);
-      v[i] = __fmul_rn(v[i], kv);
-      g[i] = __fmul_rn(g[i], kv);
-    }
-    live += kv == 1.0f;
-    dead += kv == 0.0f;
-    nnz += wv != 0.0f;
+    mask_apply(p, i, wv, sparse_grads ? p.g[i] : 0.0f, kv, sparse_grads, c);
   }
-  for (int d = 32; d > 0; d >>= 1) {
-    live += __shfl_down(live, d);
-    dead += __shfl_down(dead, d);
-    nnz += __shfl_down(nnz, d);
-  }
-  if (lane == 0) { atomicAdd(&acc[0], live); atomicAdd(&acc[1], dead); atomicAdd(&acc[2], nnz); }
+  c.commit(acc, t & 63);
   __syncthreads();
   if (t == 0) {
     MaskRow& r = a.m.rows[j];

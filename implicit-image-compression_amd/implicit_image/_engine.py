@@ -403,15 +403,8 @@ class SirenEngine:
         (ascending engine layer indices) in the handle's params / grads / moments / masks.  stats: int64
         [len(layers) + 1, MASK_STATS_WORDS] on the device or None - a sf_mask_layer_stats per layer (the last word is the
         bits of the double prune rate) and the status row."""
-        _require(self.lib, has_mask_update, "sf_mask_update entry point", "the device topology update")
-        n = len(layers)
-        if stats is not None and not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous()
-                                      and stats.numel() == (n + 1) * MASK_STATS_WORDS):
-            raise ValueError(f"mask_update: stats must be a contiguous int64 CUDA tensor of {(n + 1) * MASK_STATS_WORDS} words")
-        args = sf_mask_update_args(abi_version=SF_ABI_VERSION, n_layers=n, layers=(C.c_int32 * max(n, 1))(*layers),
-                                   prune_rate=float(prune_rate), growth=int(growth), dense_gradients=int(bool(dense_gradients)),
-                                   stats_dev=None if stats is None else stats.data_ptr())
-        _check(self.lib.sf_mask_update(self.h, C.byref(args)))
+        self._mask_call("sf_mask_update", sf_mask_update_args, has_mask_update, "the device topology update", layers, stats,
+                        prune_rate=float(prune_rate), growth=int(growth), dense_gradients=int(bool(dense_gradients)))
 
     def mask_prune_global(self, layers: Sequence[int], target: int, prune_rate: float, threshold: float, increment: float,
                           tolerance: float, dense_gradients: bool, stats: Optional[torch.Tensor] = None):
@@ -419,17 +412,21 @@ class SirenEngine:
         `layers` - the threshold search from `threshold` towards `target` removed weights, the masks |w| > threshold, the
         products.  stats: int64 [len(layers) + 1, MASK_STATS_WORDS] on the device or None - a sf_mask_layer_stats per layer and
         the status row (status, trials, alive, removed, target, 0, 0, the bits of the final threshold)."""
-        _require(self.lib, has_mask_prune_global, "sf_mask_prune_global entry point", "the device global pruning update")
+        self._mask_call("sf_mask_prune_global", sf_mask_prune_global_args, has_mask_prune_global,
+                        "the device global pruning update", layers, stats, target=int(target), prune_rate=float(prune_rate),
+                        threshold=float(threshold), increment=float(increment), tolerance=float(tolerance),
+                        dense_gradients=int(bool(dense_gradients)))
+
+    def _mask_call(self, entry, args_type, has, what, layers, stats, **fields):
+        """one topology update entry point: the library has it, `stats` is a statistics table for `layers`, the call"""
+        _require(self.lib, has, f"{entry} entry point", what)
         n = len(layers)
         if stats is not None and not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous()
                                       and stats.numel() == (n + 1) * MASK_STATS_WORDS):
-            raise ValueError(f"mask_prune_global: stats must be a contiguous int64 CUDA tensor of {(n + 1) * MASK_STATS_WORDS} words")
-        args = sf_mask_prune_global_args(abi_version=SF_ABI_VERSION, n_layers=n, layers=(C.c_int32 * max(n, 1))(*layers),
-                                         target=int(target), prune_rate=float(prune_rate), threshold=float(threshold),
-                                         increment=float(increment), tolerance=float(tolerance),
-                                         dense_gradients=int(bool(dense_gradients)),
-                                         stats_dev=None if stats is None else stats.data_ptr())
-        _check(self.lib.sf_mask_prune_global(self.h, C.byref(args)))
+            raise ValueError(f"{entry[3:]}: stats must be a contiguous int64 CUDA tensor of {(n + 1) * MASK_STATS_WORDS} words")
+        args = args_type(abi_version=SF_ABI_VERSION, n_layers=n, layers=(C.c_int32 * max(n, 1))(*layers),
+                         stats_dev=None if stats is None else stats.data_ptr(), **fields)
+        _check(getattr(self.lib, entry)(self.h, C.byref(args)))
 
     def params_changed(self):
         _check(self.lib.sf_params_changed(self.h))

@@ -22,6 +22,7 @@ import logging
 import math
 import os
 import struct
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Dict
 
@@ -47,6 +48,16 @@ class LayerStats:
     def total_density(self) -> float:
         tot = self.total_zero + self.total_nonzero
         return self.total_nonzero / tot if tot else 0.0
+
+
+# The device routes of update_connections() by what differs between them: the prune mode and the growth modes a route covers,
+# the engine method with the _engine predicate for its library symbol, and the Masking method that gives the call's own
+# arguments (between `layers` and `dense_gradients, stats`).
+DeviceRoute = namedtuple("DeviceRoute", "name prune_mode growth_modes method has args")
+DevicePlan = namedtuple("DevicePlan", "route eng layers slices")
+RIGL_ROUTE = DeviceRoute("rigl", "magnitude", ("none", "absolute-gradient"), "mask_update", "has_mask_update", "_rigl_args")
+GLOBAL_ROUTE = DeviceRoute("global", "global-magnitude", ("none",), "mask_prune_global", "has_mask_prune_global", "_global_args")
+DEVICE_ROUTES = (RIGL_ROUTE, GLOBAL_ROUTE)
 
 
 class Masking:
@@ -104,7 +115,8 @@ class Masking:
         """The host-side bookkeeping of every pending device update, oldest first, from ONE copy of its statistics rows:
         exactly the values, and the float sequence, of truncate_weights() below."""
         while self._pending:
-            rows, names, global_prune = self._pending.pop(0)
+            rows, names, route = self._pending.pop(0)
+            global_prune = route is GLOBAL_ROUTE
             rows = rows.cpu().tolist()
             status = rows[len(names)]
             if global_prune and status[0] == 2:
@@ -338,22 +350,25 @@ class Masking:
         self.gather_statistics()
 
     def _device_plan(self):
-        """(engine, layer indices, [(name, flat offset, shape)]) when this update can run as sf_mask_update, else None: an
-        engine with the entry point under an unpadded model, every masked parameter the weight of an engine layer living
-        in the engine's own vectors (data, gradient and - where the moments are masked too - Adam state), the modes RigL
-        ships with, and SIREN_FIT_DEVICE_MASK not "0" (an A/B knob, like SIREN_FIT_NATIVE_KMEANS)."""
+        """A DevicePlan when this update can run as one call of a device route, else None: an engine with the route's entry
+        point under an unpadded model, every masked parameter the weight of an engine layer living in the engine's own
+        vectors (data, gradient and - where the moments are masked too - Adam state), the modes of a row of DEVICE_ROUTES
+        without a redistribution statistic, and SIREN_FIT_DEVICE_MASK not "0" (an A/B knob, like SIREN_FIT_NATIVE_KMEANS)."""
         from ... import _engine
         eng = self.module.bound_engine
         if (self.device_update != "auto" or eng is None or os.environ.get("SIREN_FIT_DEVICE_MASK") == "0"
-                or not self.module.state_is_live or self.prune_mode != "magnitude"
-                or self.growth_mode not in _engine.MASK_GROWTH or self.redistribution_mode not in ("none", "nonzero")
-                or not callable(getattr(eng, "mask_update", None)) or not _engine.has_mask_update(eng.lib)):
+                or not self.module.state_is_live or self.redistribution_mode not in ("none", "nonzero")):
             return None
-        return self._engine_slices(eng)
+        for route in DEVICE_ROUTES:
+            if (self.prune_mode == route.prune_mode and self.growth_mode in route.growth_modes
+                    and callable(getattr(eng, route.method, None)) and getattr(_engine, route.has)(eng.lib)):
+                found = self._engine_slices(eng)
+                return found and DevicePlan(route, eng, *found)
+        return None
 
     def _engine_slices(self, eng):
-        """(engine, layer indices, [(name, flat offset, shape)]) when every masked parameter is the weight of an engine layer
-        living in the engine's own vectors, else None"""
+        """(layer indices, [(name, flat offset, shape)]) when every masked parameter is the weight of an engine layer living in
+        the engine's own vectors, else None"""
         views = [eng.view("params"), eng.view("grads")]
         if not self.dense_gradients:
             views += [eng.view("exp_avg"), eng.view("exp_avg_sq")]
@@ -370,45 +385,30 @@ class Masking:
                 layers.append(pos // 2)
                 slices.append((pname, off, par.shape))
             off += n
-        return None if masked or not layers else (eng, layers, slices)
+        return None if masked or not layers else (layers, slices)
+
+    def _rigl_args(self):
+        from ... import _engine
+        return self.prune_rate, _engine.MASK_GROWTH[self.growth_mode]
+
+    def _global_args(self):
+        threshold = self.prune_threshold        # (first: it completes a pending update - the search starts where that one ended)
+        target = math.ceil(self.prune_rate * self.baseline_nonzero)
+        return target, self.prune_rate, threshold, self.increment, self.tolerance
 
     @torch.no_grad()
-    def _device_update(self, eng, layers, slices):
-        """update_connections() as one sf_mask_update: nothing is read back here."""
+    def _device_update(self, plan):
+        """update_connections() as one call of the route's entry point: nothing is read back here, unless the global route
+        finds the update before this one still pending."""
         from ... import _engine
+        route, eng, layers, slices = plan
+        args = getattr(self, route.args)()
         self._push_masks()                      # mask_dict is the truth (callers replace its entries)
         rows = torch.empty(len(layers) + 1, _engine.MASK_STATS_WORDS, dtype=torch.int64, device=eng.device)
-        eng.mask_update(layers, self.prune_rate, _engine.MASK_GROWTH[self.growth_mode], self.dense_gradients, rows)
+        getattr(eng, route.method)(layers, *args, self.dense_gradients, rows)
         self._adopt_engine_masks(eng, slices)
         self.mask_step += 1
-        self._pending.append((rows, [pname for pname, _, _ in slices], False))
-
-    def _device_plan_global(self):
-        """_device_plan() for the modes Pruning ships with: global-magnitude pruning without growth, on an engine that has
-        sf_mask_prune_global."""
-        from ... import _engine
-        eng = self.module.bound_engine
-        if (self.device_update != "auto" or eng is None or os.environ.get("SIREN_FIT_DEVICE_MASK") == "0"
-                or not self.module.state_is_live or self.prune_mode != "global-magnitude" or self.growth_mode != "none"
-                or self.redistribution_mode not in ("none", "nonzero")
-                or not callable(getattr(eng, "mask_prune_global", None)) or not _engine.has_mask_prune_global(eng.lib)):
-            return None
-        return self._engine_slices(eng)
-
-    @torch.no_grad()
-    def _device_update_global(self, eng, layers, slices):
-        """update_connections() as one sf_mask_prune_global: nothing is read back here unless the update before this one is
-        still pending - the search starts from the threshold that one left."""
-        from ... import _engine
-        threshold = self.prune_threshold        # (completes a pending update: one transfer)
-        self._push_masks()
-        target = math.ceil(self.prune_rate * self.baseline_nonzero)
-        rows = torch.empty(len(layers) + 1, _engine.MASK_STATS_WORDS, dtype=torch.int64, device=eng.device)
-        eng.mask_prune_global(layers, target, self.prune_rate, threshold, self.increment, self.tolerance,
-                              self.dense_gradients, rows)
-        self._adopt_engine_masks(eng, slices)
-        self.mask_step += 1
-        self._pending.append((rows, [pname for pname, _, _ in slices], True))
+        self._pending.append((rows, [pname for pname, _, _ in slices], route))
 
     def _adopt_engine_masks(self, eng, slices):
         flat = eng.view("masks")
@@ -417,9 +417,9 @@ class Masking:
             self.mask_dict[pname] = flat[off:off + shape.numel()].view(shape).clone()
 
     def update_connections(self):
-        plan = self._device_plan_global() if self.global_prune else self._device_plan()
+        plan = self._device_plan()
         if plan is not None:
-            return self._device_update_global(*plan) if self.global_prune else self._device_update(*plan)
+            return self._device_update(plan)
         self.truncate_weights()
 
     # ---- checkpoint surface (core.py:495-506, 660-669) -----------------------------------------

@@ -2,14 +2,13 @@
 CPU), against the host path of Masking.update_connections(), against the real reference's captured update
 (tests/golden/masking_rigl.npz), its refusals, its launch count and a whole `fit`.  One case per process."""
 import ctypes as C
-import json
 import os
 
-import numpy as np
 import torch
 
-from _gpu_child import ROOT, child_main
-from _gpu_fixtures import golden, launches, recorder
+from _gpu_child import child_main
+from _gpu_fixtures import launches, recorder
+from _mask_fixtures import KNOB, RIGL, Cfg, bits, fit_on_both_routes, flat_state, load_captured, seeded_sides, slices_of, update_captured
 from _mask_update_ref import WORDS, bits_rate, mask_update_ref
 from implicit_image import _engine as E
 from oracle import siren_oracle as so
@@ -17,23 +16,6 @@ from oracle import siren_oracle as so
 HANDLES = [(32, 3), (64, 4), (256, 3), (512, 3)]           # layers of 64 .. 262 144 elements: below one workgroup, several
 DENSITY = (0.5, 0.3, 0.6, 0.5)                             # 64-element steps per wave, the metric width's layer, the wide path
 HOST_SHAPES = [(64, 4, 32), (256, 4, 64), (512, 3, 64)]    # hidden, depth, image side
-KNOB = "SIREN_FIT_DEVICE_MASK"
-
-
-class Cfg(dict):
-    __getattr__ = dict.get
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def slices_of(eng, layers):
-    out = []
-    for l in layers:
-        w, b = eng.param_offsets(l)
-        out.append((w, b - w))
-    return out
 
 
 # ---- 5. the ABI against the restatement ------------------------------------------------------------------------------------
@@ -106,25 +88,11 @@ def case_abi(which):
 # ---- 6. against the host path ----------------------------------------------------------------------------------------------
 def case_host(which, density, dense):
     from implicit_image.data import get_grid
-    from implicit_image.models import registry
-    from implicit_image.utils.train_helper import get_optimizer_lr_scheduler, setup_mask, train_epoch
+    from implicit_image.utils.train_helper import train_epoch
     hidden, depth, side = HOST_SHAPES[int(which)]
-    mcfg = Cfg(name="RigL", density=float(density), sparse_init="erdos-renyi-kernel", dense_gradients=dense == "1",
-               growth_mode="absolute-gradient", prune_mode="magnitude", redistribution_mode="none", dense=False,
-               prune_rate=0.1, decay_schedule="cosine", end_when=1500, interval=20)
     grid, img = get_grid(side, side).cuda(), so.synthetic_image(side, side, seed=3).cuda().contiguous()
-    sides = []
-    for _ in range(2):
-        torch.manual_seed(0)
-        m = registry["siren"](depth=depth, hidden_size=hidden, first_omega_0=50, hidden_omega_0=30).to("cuda")
-        optim, sched = get_optimizer_lr_scheduler(m, Cfg(name="adam", lr=3e-4))
-        sides.append((m, optim, sched, setup_mask(m, optim, mcfg)))
+    sides = seeded_sides(Cfg(RIGL, density=float(density), dense_gradients=dense == "1"), hidden, depth)
     out = {"updates": [], "tied": [], "device_updates": [0, 0]}
-
-    def flat_state(m, mask):
-        eng = m.bound_engine
-        return [eng.view(w).clone().cpu() for w in ("params", "grads", "exp_avg", "exp_avg_sq")] + [mask.flat_mask().cpu()]
-
     for u in range(4):
         losses = [[train_epoch(m, optim, grid, img, lr_scheduler=sched, mask=mask) for _ in range(3)]
                   for m, optim, sched, mask in sides]
@@ -158,60 +126,13 @@ def case_host(which, density, dense):
 
 # ---- 7. against the real reference -----------------------------------------------------------------------------------------
 def case_golden(upd):
-    from implicit_image.data import get_grid
-    from implicit_image.models import registry
-    from implicit_image.utils.train_helper import get_optimizer_lr_scheduler, setup_mask
-    d = golden("masking_rigl")
-    mcfg = Cfg(name="RigL", density=0.5, sparse_init="erdos-renyi-kernel", dense_gradients=True,
-               growth_mode="absolute-gradient", prune_mode="magnitude", redistribution_mode="none", dense=False,
-               prune_rate=0.1, decay_schedule="cosine", end_when=60, interval=5)
-    torch.manual_seed(0)
-    m = registry["siren"](depth=4, hidden_size=64, first_omega_0=50, hidden_omega_0=30).to("cuda")
-    optim, _ = get_optimizer_lr_scheduler(m, Cfg(name="adam", lr=3e-4))
-    mask = setup_mask(m, optim, mcfg)
-    names = [str(n) for n in d["mask_names"]]
-
-    def mask_bits():
-        return np.packbits(np.concatenate([mask.mask_dict[n].cpu().numpy().ravel().astype(np.uint8) for n in names]))
-
-    def copy_flat(dsts, flat):
-        off = 0
-        for t in dsts:
-            t.copy_(torch.tensor(flat[off:off + t.numel()]).view(t.shape))
-            off += t.numel()
-    out = {"init_equal": bool(np.array_equal(mask_bits(), d["mask_init"]))}
-    eng = m.engine(get_grid(16, 16).cuda())
-    optim._bind_state(eng)
-    params = m._param_list()
-    pre, post = f"u{upd}_", f"a{upd}_"
-    with torch.no_grad():
-        copy_flat([p.data for p in params], d[pre + "w"])
-        copy_flat([p.grad for p in params], d[pre + "g"])
-        copy_flat([optim.state[p]["exp_avg"] for p in params], d[pre + "m"])
-        copy_flat([optim.state[p]["exp_avg_sq"] for p in params], d[pre + "v"])
-    mb, off = np.unpackbits(d[pre + "mask"]), 0
-    for n in names:
-        sh = mask.mask_dict[n].shape
-        mask.mask_dict[n] = torch.tensor(mb[off:off + sh.numel()].astype(np.float32)).view(sh).cuda()
-        off += sh.numel()
-    mask.mask_step = int(d[pre + "mask_step"])
-    mask.adjusted_growth = float(d[pre + "adjusted_growth"])
-    mask.adjustments = list(d[pre + "adjustments"])
-    mask.stats.total_nonzero, mask.stats.total_zero = int(d[pre + "total_nonzero"]), int(d[pre + "total_zero"])
+    c = load_captured("masking_rigl", Cfg(RIGL, end_when=60, interval=5), upd)
+    mask, d = c.mask, c.d
     for s_ in range(mask.mask_step):
         mask.prune_rate_decay.step(s_)
-    out["rate_error"] = abs(mask.prune_rate - float(d[pre + "rate"]))
-    mask.update_connections()
-    out["device_updates"] = len(mask._pending)
-    got_w = np.concatenate([p.detach().cpu().numpy().ravel() for p in params])
-    got_m = np.concatenate([optim.state[p]["exp_avg"].cpu().numpy().ravel() for p in params])
-    out.update(mask_equal=bool(np.array_equal(mask_bits(), d[post + "mask"])),
-               w_equal=bool(np.array_equal(got_w.view(np.int32), d[post + "w"].view(np.int32))),
-               m_equal=bool(np.array_equal(got_m.view(np.int32), d[post + "m"].view(np.int32))),
-               nnz_equal=[int(mask.mask_dict[n].sum().item()) for n in names] == d[post + "nnz"].tolist(),
-               mask_step_equal=mask.mask_step == int(d[post + "mask_step"]),
-               growth_error=abs(mask.adjusted_growth - float(d[post + "adjusted_growth"])),
-               density_error=abs(mask.stats.total_density - float(d[post + "density"])))
+    c.out["rate_error"] = abs(mask.prune_rate - float(d[c.pre + "rate"]))
+    out = update_captured(c)
+    out["growth_error"] = abs(mask.adjusted_growth - float(d[c.post + "adjusted_growth"]))
     return out
 
 
@@ -279,32 +200,9 @@ def case_launches():
 
 # ---- 10. a whole fit -------------------------------------------------------------------------------------------------------
 def case_e2e(workdir):
-    from implicit_image.config import load_config
-    from implicit_image.fit import fit_one
     over = ["masking=RigL", "quant=none", "img.height=64", "img.width=64", "mlp.hidden_size=64", "mlp.depth=4",
             "train.num_steps=60", "train.log_steps=20", "masking.interval=10"]
-    out, calls, plain = {}, [0], E.SirenEngine.mask_update
-
-    def counted(self, *a, **kw):
-        calls[0] += 1
-        return plain(self, *a, **kw)
-    E.SirenEngine.mask_update = counted
-    for side, knob in (("host", "0"), ("device", "1")):
-        os.environ[KNOB] = knob
-        calls[0] = 0
-        cfg = load_config(os.path.join(ROOT, "conf"), over)
-        run_dir = os.path.join(workdir, side)
-        res = fit_one(cfg, torch.device("cuda", 0), run_dir)
-        sd = torch.load(os.path.join(run_dir, "model.pth"), weights_only=True)["state_dict"]
-        weights = torch.cat([v.reshape(-1) for k, v in sd.items() if k.endswith("weight")])
-        saved = json.load(open(os.path.join(run_dir, "result.json")))
-        out[side] = {"device_updates": calls[0], "PSNR": saved["PSNR"], "loss": saved["loss"], "PSNR_8bit": saved["PSNR_8bit"],
-                     "density": float((weights != 0).float().mean()), "returned_psnr": res["PSNR"]}
-    os.environ.pop(KNOB)
-    a, b = (open(os.path.join(workdir, s, "model.pth"), "rb").read() for s in ("host", "device"))
-    out["pth_equal"] = a == b
-    out["pth_bytes"] = len(a)
-    return out
+    return fit_on_both_routes(workdir, over, "mask_update")
 
 
 if __name__ == "__main__":

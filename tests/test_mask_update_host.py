@@ -9,6 +9,8 @@ import pytest
 import torch
 from torch import nn
 
+import _mask_fixtures
+from _mask_fixtures import RIGL, Cfg
 from _mask_update_ref import WORDS, bits_rate, mask_update_ref
 from implicit_image import _engine
 from implicit_image.models import registry
@@ -18,15 +20,6 @@ from implicit_image.utils.train_helper import setup_mask
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (64, 96, 192, 1000, 4096)
 DENSITY = (0.5, 0.3, 0.6, 0.5, 0.9)            # the last layer: under 20 % sparse with the largest share - the rate cap
-
-
-class Cfg(dict):
-    __getattr__ = dict.get
-
-
-RIGL = Cfg(name="RigL", density=0.5, sparse_init="erdos-renyi-kernel", dense_gradients=True, growth_mode="absolute-gradient",
-           prune_mode="magnitude", redistribution_mode="none", dense=False, prune_rate=0.1, decay_schedule="cosine",
-           end_when=1500, interval=20)
 
 
 def test_entry_point_is_declared_exported_and_bound():
@@ -129,37 +122,13 @@ def test_restatement_reports_an_all_zero_network():
 
 
 # ---- routing -----------------------------------------------------------------------------------------------------------
-class FakeEngine:
-    """what Masking asks of an engine, on CPU tensors; mask_update is the restatement"""
-    device = torch.device("cpu")
-
-    def __init__(self, model):
-        self.lib = SimpleNamespace(sf_mask_update=None)
-        self.sizes = [p.numel() for p in model._param_list()]
-        self.num_params = sum(self.sizes)
-        self.vecs = {w: torch.zeros(self.num_params) for w in ("params", "grads", "exp_avg", "exp_avg_sq", "masks")}
-        self.updates = 0
-        self.quiet = False
-
-    def view(self, which):
-        return self.vecs[which]
-
-    def param_offsets(self, layer):
-        off = sum(self.sizes[:2 * layer])
-        return off, off + self.sizes[2 * layer]
-
-    def set_masks(self, flat):
-        self.vecs["masks"].copy_(flat)
-
-    def params_changed(self):
-        pass
+class FakeEngine(_mask_fixtures.FakeEngine):
+    """mask_update is the restatement"""
 
     def mask_update(self, layers, prune_rate, growth, dense_gradients, stats):
         self.quiet = True
-        slices = [(self.param_offsets(l)[0], self.sizes[2 * l]) for l in layers]
-        v = self.vecs
-        rows, _ = mask_update_ref(v["params"], v["grads"], v["exp_avg"], v["exp_avg_sq"], v["masks"], slices, prune_rate,
-                                  growth, dense_gradients)
+        state, slices = self.state_and_slices(layers)
+        rows, _ = mask_update_ref(*state, slices, prune_rate, growth, dense_gradients)
         stats.copy_(rows)
         self.updates += 1
         self.quiet = False
@@ -244,6 +213,37 @@ def test_ineligible_configurations_take_the_host_path(monkeypatch, why):
     if why == "knob":
         monkeypatch.setenv("SIREN_FIT_DEVICE_MASK", "1")
         assert mask._device_plan() is not None
+
+
+class BothRoutesEngine(FakeEngine):
+    def mask_prune_global(self, *a):
+        raise AssertionError("a plan calls nothing")
+
+
+# prune_mode, growth_mode -> the route under redistribution_mode grad, momentum, none, nonzero.  Worked out once from the two
+# conditions this table replaced (a plan method per route), before they were folded into one.
+ROUTE_TABLE = {
+    ("global-magnitude", "absolute-gradient"): (None, None, None, None),
+    ("global-magnitude", "momentum"): (None, None, None, None),
+    ("global-magnitude", "none"): (None, None, "global", "global"),
+    ("global-magnitude", "random"): (None, None, None, None),
+    ("magnitude", "absolute-gradient"): (None, None, "rigl", "rigl"),
+    ("magnitude", "momentum"): (None, None, None, None),
+    ("magnitude", "none"): (None, None, "rigl", "rigl"),
+    ("magnitude", "random"): (None, None, None, None),
+}
+
+
+def test_route_table_over_every_registered_mode():
+    from implicit_image.pipeline.masking import grow_registry, prune_registry, redistribute_registry
+    assert sorted(redistribute_registry) == ["grad", "momentum", "none", "nonzero"]
+    assert sorted(ROUTE_TABLE) == sorted((p, g) for p in prune_registry for g in set(grow_registry) | {"none"})
+    for (prune, growth), row in ROUTE_TABLE.items():
+        for redistribution, want in zip(sorted(redistribute_registry), row):
+            _, _, mask, _ = rigl_model(bind=BothRoutesEngine, prune_mode=prune, growth_mode=growth,
+                                       redistribution_mode=redistribution)
+            plan = mask._device_plan()
+            assert (plan and plan.route.name) == want, (prune, growth, redistribution)
 
 
 def test_device_route_reads_nothing_back(monkeypatch):

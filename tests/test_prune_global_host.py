@@ -11,22 +11,15 @@ import numpy as np
 import pytest
 import torch
 
+import _mask_fixtures
+from _mask_fixtures import PRUNING, Cfg
 from _prune_global_ref import ALIVE, REMOVED, STATUS, TRIAL_CAP, TRIALS, prune_global_ref, threshold_bits, threshold_of
 from implicit_image import _engine
 from implicit_image.models import registry
+from implicit_image.pipeline.masking.core import GLOBAL_ROUTE
 from implicit_image.utils.train_helper import setup_mask
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-class Cfg(dict):
-    __getattr__ = dict.get
-
-
-# conf/masking/Pruning.yaml's keys on a schedule short enough that six updates three steps apart prune something every time
-PRUNING = Cfg(name="Pruning", density=1.0, sparse_init="random", final_density=0.5, dense_gradients=True, growth_mode="none",
-              prune_mode="global-magnitude", redistribution_mode="none", dense=False, decay_schedule="magnitude-prune",
-              start_when=0, end_when=40, interval=3)
 
 
 def test_entry_point_is_declared_exported_and_bound():
@@ -276,41 +269,20 @@ def test_edge_pruned_negative_weights_become_minus_zero():
 
 
 # ---- routing ---------------------------------------------------------------------------------------------------------------
-class FakeEngine:
-    """what Masking asks of an engine, on CPU tensors; mask_prune_global is the restatement"""
-    device = torch.device("cpu")
+class FakeEngine(_mask_fixtures.FakeEngine):
+    """mask_prune_global is the restatement"""
 
     def __init__(self, model):
-        self.lib = SimpleNamespace(sf_mask_update=None, sf_mask_prune_global=None)
-        self.sizes = [p.numel() for p in model._param_list()]
-        self.num_params = sum(self.sizes)
-        self.vecs = {w: torch.zeros(self.num_params) for w in ("params", "grads", "exp_avg", "exp_avg_sq", "masks")}
-        self.updates = 0
-        self.quiet = False
+        super().__init__(model)
         self.trials = []
-
-    def view(self, which):
-        return self.vecs[which]
-
-    def param_offsets(self, layer):
-        off = sum(self.sizes[:2 * layer])
-        return off, off + self.sizes[2 * layer]
-
-    def set_masks(self, flat_mask):
-        self.vecs["masks"].copy_(flat_mask)
-
-    def params_changed(self):
-        pass
 
     def mask_update(self, *a):
         raise AssertionError("the per-layer update is not the route of global pruning")
 
     def mask_prune_global(self, layers, target, prune_rate, threshold, increment, tolerance, dense_gradients, stats):
         self.quiet = True
-        slices = [(self.param_offsets(l)[0], self.sizes[2 * l]) for l in layers]
-        v = self.vecs
-        rows = prune_global_ref(v["params"], v["grads"], v["exp_avg"], v["exp_avg_sq"], v["masks"], slices, target, prune_rate,
-                                threshold, increment, tolerance, dense_gradients)
+        state, slices = self.state_and_slices(layers)
+        rows = prune_global_ref(*state, slices, target, prune_rate, threshold, increment, tolerance, dense_gradients)
         stats.copy_(rows)
         self.trials.append(int(rows[-1, TRIALS]))
         self.updates += 1
@@ -324,7 +296,7 @@ class NoGlobalEngine(FakeEngine):
 def test_device_route_equals_the_host_path_over_five_updates():
     ma, oa, ka, eng = pruning_model(bind=FakeEngine, device_update="auto")
     mb, ob, kb, _ = pruning_model(device_update="auto")
-    assert ka._device_plan() is None and ka._device_plan_global() is not None and kb._device_plan_global() is None
+    assert ka._device_plan().route == GLOBAL_ROUTE and kb._device_plan() is None
     for u in range(5):
         train_a_little(ma, oa, ka, 100 + u)
         train_a_little(mb, ob, kb, 100 + u)
@@ -359,7 +331,7 @@ def test_ineligible_configurations_take_the_host_path(monkeypatch, why):
     if why == "old_library":
         eng.lib = SimpleNamespace(sf_mask_update=None)
     train_a_little(m, optim, mask, 5)
-    assert mask._device_plan_global() is None and mask._device_plan() is None
+    assert mask._device_plan() is None
     if why == "growth":
         # the host path is taken - and, as in the reference, cannot finish: global pruning fills no per-layer removed_dict,
         # so truncate_weights() finds no regrowth budget for the first layer and raises; the engine is never called
@@ -373,7 +345,7 @@ def test_ineligible_configurations_take_the_host_path(monkeypatch, why):
     assert any(not torch.equal(before[n], mask.mask_dict[n]) for n in before)
     if why == "knob":
         monkeypatch.setenv("SIREN_FIT_DEVICE_MASK", "1")
-        assert mask._device_plan_global() is not None
+        assert mask._device_plan().route == GLOBAL_ROUTE
 
 
 def test_device_route_reads_back_only_a_pending_update(monkeypatch):
