@@ -1,11 +1,12 @@
-// mask_host.hip — the topology updates of a masked fit (siren_mask.hip states what they compute) on the host: the two entry
-// points sf_mask_update and sf_mask_prune_global, and what they share under the caller's name - the refusals, the walk over
+// mask_host.hip — the topology updates of a masked fit (siren_mask.hip states what they compute) on the host: the three entry
+// points sf_mask_update, sf_mask_prune_global and sf_mask_update_snfs, and what they share under the caller's name - the refusals, the walk over
 // the layers, the state pointers, the epilogue.  An entry point keeps its own argument checks and its launches; the order
 // of the checks is: the shared refusals, its own, the layers.  Included by siren_fit.hip.
 
 namespace {
 
 static_assert(sizeof(MaskRow) == sizeof(sf_mask_layer_stats), "MaskRow is sf_mask_layer_stats");
+static_assert(sizeof(SnfsRow) == sizeof(sf_mask_snfs_stats), "SnfsRow is sf_mask_snfs_stats");
 
 // what every topology update refuses before it looks at its own arguments (A: an argument struct of the ABI)
 template <class A>
@@ -44,11 +45,13 @@ int mask_layers(const sf_engine* h, const A* a, const std::string& fn, MaskArgs&
   return SF_OK;
 }
 
-// the handle's state and the statistics rows - the caller's, or the handle's own (allocated on first use) - into k
-int mask_bind(sf_engine* h, void* stats_dev, MaskArgs& k) {
-  if (!stats_dev && !h->mask_rows) SF_TRY(dev_alloc(h, h->mask_rows, sizeof(MaskRow) * (kMaskMaxLayers + 1)));
+// the handle's state into k, and the statistics rows - the caller's, or the handle's own (`own`, allocated on first use) -
+// into rows
+template <class Row>
+int mask_bind(sf_engine* h, void* stats_dev, Row*& own, MaskArgs& k, Row*& rows) {
+  if (!stats_dev && !own) SF_TRY(dev_alloc(h, own, sizeof(Row) * (kMaskMaxLayers + 1)));
   k.w = h->params; k.g = h->grads; k.m = h->m; k.v = h->v; k.k = h->mask;
-  k.rows = stats_dev ? reinterpret_cast<MaskRow*>(stats_dev) : h->mask_rows;
+  rows = stats_dev ? reinterpret_cast<Row*>(stats_dev) : own;
   return SF_OK;
 }
 
@@ -72,7 +75,7 @@ int sf_mask_update(sf_handle* h, const sf_mask_update_args* a) try {
   int n_max;
   SF_TRY(mask_layers(h, a, fn, k, bytes, n_max));
   DevGuard dev_guard(h->cfg.device);
-  SF_TRY(mask_bind(h, a->stats_dev, k));
+  SF_TRY(mask_bind(h, a->stats_dev, h->mask_rows, k, k.rows));
   k.growth = a->growth;
   {
     Launch L(h, K_MASK, 0, bytes * 12);   // (about a dozen L2-resident reads of every masked layer)
@@ -101,7 +104,7 @@ int sf_mask_prune_global(sf_handle* h, const sf_mask_prune_global_args* a) try {
   SF_TRY(mask_layers(h, a, fn, k, bytes, n_max));
   if (h->P > 0x7fffffff) return fail(SF_ERR_INVALID, "sf_mask_prune_global: more than 2^31 - 1 parameters");
   DevGuard dev_guard(h->cfg.device);
-  SF_TRY(mask_bind(h, a->stats_dev, k));
+  SF_TRY(mask_bind(h, a->stats_dev, h->mask_rows, k, k.rows));
   if (!h->prune_ws) SF_TRY(dev_alloc(h, h->prune_ws, sizeof(PruneWs)));
   if (!h->prune_keys) SF_TRY(dev_alloc(h, h->prune_keys, (size_t)h->P * 4));
   p.ws = h->prune_ws; p.keys = h->prune_keys; p.cap = (int)h->P;
@@ -118,6 +121,37 @@ int sf_mask_prune_global(sf_handle* h, const sf_mask_prune_global_args* a) try {
     SF_TRY(launch(h, k_prune_file<true>, grid, kMaskThreads, 0, p));
     SF_TRY(launch(h, k_prune_search, 1, kMaskThreads, 0, p));
     SF_TRY(launch(h, k_prune_apply, grid, kMaskThreads, 0, p));
+  }
+  mask_done(h);
+  return SF_OK;
+} SF_CATCH
+
+/* one SNFS topology update (momentum growth, momentum redistribution) of the masked layers on the handle's stream: three
+ * launches whatever the depth and the number of water-filling rounds, no host synchronisation */
+int sf_mask_update_snfs(sf_handle* h, const sf_mask_update_snfs_args* a) try {
+  const char* fn = "sf_mask_update_snfs";
+  SF_TRY(mask_refuse(h, a, fn));
+  if (a->growth != 1 && a->growth != 2)
+    return fail(SF_ERR_INVALID, "sf_mask_update_snfs: growth must be 1 (absolute gradient) or 2 (momentum)");
+  if (a->statistic != 0 && a->statistic != 1)
+    return fail(SF_ERR_INVALID, "sf_mask_update_snfs: statistic must be 0 (non-zero count) or 1 (momentum)");
+  if (!(std::isfinite(a->adjusted_growth) && a->adjusted_growth >= 0.0))
+    return fail(SF_ERR_INVALID, "sf_mask_update_snfs: adjusted_growth must be finite and >= 0");
+  SnfsArgs p = zeroed<SnfsArgs>();
+  MaskArgs& k = p.m;
+  double bytes;
+  int n_max;
+  SF_TRY(mask_layers(h, a, fn, k, bytes, n_max));
+  DevGuard dev_guard(h->cfg.device);
+  SF_TRY(mask_bind(h, a->stats_dev, h->snfs_rows, k, p.rows));
+  k.growth = a->growth;
+  p.adjusted_growth = a->adjusted_growth;
+  p.statistic = a->statistic;
+  {
+    Launch L(h, K_MASK_SNFS, 0, bytes * 20);   // (about twenty L2-resident reads of every masked layer)
+    SF_TRY(launch(h, k_snfs_stat, k.L, kMaskThreads, 0, p));
+    SF_TRY(launch(h, k_snfs_prune, k.L, kMaskThreads, 0, p));
+    SF_TRY(launch(h, k_snfs_grow, k.L, kMaskThreads, 0, p));
   }
   mask_done(h);
   return SF_OK;

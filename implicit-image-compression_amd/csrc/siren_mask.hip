@@ -1,4 +1,5 @@
-// siren_mask.hip — the RigL topology update on the device, no host synchronisation (sf_mask_update).
+// siren_mask.hip — the RigL topology update on the device, no host synchronisation (sf_mask_update); below
+// it the SNFS update (sf_mask_update_snfs) and the global-magnitude update (sf_mask_prune_global), each under its own header.
 //
 // Reference being replaced (paths relative to the reference tree, implicit_image/pipeline/masking/):
 //   core.py:425-464   gather_statistics: live / dead counts of every mask, the non-zero share of every layer
@@ -23,7 +24,7 @@
 //
 // Selection is an exact radix select, not a sort: bits(a) orders like a for a non-negative float a, so four 8-bit histogram
 // passes from the top digit find the boundary key and how many of its ties belong to the selection; one more pass ranks
-// those ties by index (each wave owns a contiguous segment: a ballot prefix inside a 64-element step, a running count
+// those ties by index (each wave owns a contiguous segment, mask_seg: a ballot prefix inside a 64-element step, a running count
 // along the segment, a scan over the waves) and only when the boundary splits a group of ties.  Growth is the same code on
 // the complemented key.  The one key that piles up - |w| = 0 of the dead weights, c = 0 of the live ones - is counted in
 // registers and kept out of the histogram.  Every count is an integer (LDS integer atomics commute): the result does not
@@ -31,7 +32,7 @@
 // barrier is reached by every thread of the workgroup.
 // A device helper that holds a barrier or a wave-wide ballot is left early only on a condition that is uniform over the
 // workgroup (the wave), and says so.
-// (included by siren_fit.hip; the two entry points are in mask_host.hip)
+// (included by siren_fit.hip; the three entry points are in mask_host.hip)
 
 namespace sf {
 
@@ -81,11 +82,15 @@ __device__ __forceinline__ MaskLayer mask_layer(const MaskArgs& a, int j) {
   return {a.w + o, a.g + o, a.m + o, a.v + o, a.k + o, a.n[j]};
 }
 
-// step 2 of the contract: the rate of layer j (n elements) of L, from the counts of its row; S the non-zeros of all layers
-__device__ __forceinline__ double mask_rate(const MaskRow* rows, int j, int n, int L, long long S, double r) {
-  const double share = (double)rows[j].nnz_before / (double)S, frac_dead = (double)rows[j].dead_before / (double)n;
+// step 2 of the contract: the rate of a layer of n elements, `dead` of them masked out, one of L, that holds `share` of
+// the statistic (sf_mask_update, sf_mask_prune_global: of the non-zeros; sf_mask_update_snfs: of its redistribution statistic)
+__device__ __forceinline__ double mask_rate(double share, long long dead, int n, int L, double r) {
+  const double frac_dead = (double)dead / (double)n;
   const bool capped = frac_dead < 0.2 && (1.0 / (double)L) / share < 1.0;
   return capped ? fmin(frac_dead, r) : r;
+}
+__device__ __forceinline__ double mask_rate(const MaskRow* rows, int j, int n, int L, long long S, double r) {
+  return mask_rate((double)rows[j].nnz_before / (double)S, rows[j].dead_before, n, L, r);
 }
 
 // The count-and-commit form of every kernel that counts: a lane tallies its own elements, the wave adds its lanes up once,
@@ -140,10 +145,40 @@ __device__ __forceinline__ unsigned mask_key(float x, float k) {
   if (GROW) return ~__float_as_uint(__fmul_rn(fabsf(x), __fsub_rn(1.0f, k)));
   return __float_as_uint(x) & 0x7fffffffu;
 }
-template <bool GROW>
-__device__ __forceinline__ unsigned mask_key(const float* x, const float* k, int i) {
-  return mask_key<GROW>(x[i], GROW ? k[i] : 0.0f);
+
+// Adam's momentum of one weight as Masking.get_momentum_for_weight forms it, m / (sqrt(v) + 1e-8): three IEEE fp32
+// operations, each rounded to nearest.  Written as operators under `fp contract(off)` and with sqrtf, not as the _rn
+// intrinsics: the toolchain's __fsqrt_rn is the approximate hardware square root (one ulp), and its _rn arithmetic forms are
+// plain operators that the translation unit's default contraction may fuse with a neighbour.
+__device__ __forceinline__ float mask_momentum(float m, float v) {
+#pragma clang fp contract(off)
+  const float root = sqrtf(v);
+  const float den = root + 1e-8f;
+  return m / den;
 }
+
+// The key sources of the selection helpers below: key(i) of element i, smallest first.  kHeavy: the one key that piles up
+// (it is counted in registers, not in the histogram) - the smallest possible key when pruning, the largest when growing.
+struct KeyAbsW {                  // prune: the bits of |w|
+  const float* w;
+  static constexpr unsigned kHeavy = 0u;
+  static constexpr bool kGrow = false;
+  __device__ __forceinline__ unsigned key(int i) const { return mask_key<false>(w[i], 0.0f); }
+};
+struct KeyGrad {                  // grow by |gradient|: the complement of the bits of |g| * (1 - k)
+  const float *g, *k;
+  static constexpr unsigned kHeavy = 0xffffffffu;
+  static constexpr bool kGrow = true;
+  __device__ __forceinline__ unsigned key(int i) const { return mask_key<true>(g[i], k[i]); }
+};
+struct KeyMom {                   // grow by |momentum|: the complement of the bits of |mom * (1 - k)|, mom from m and v on the fly
+  const float *m, *v, *k;
+  static constexpr unsigned kHeavy = 0xffffffffu;
+  static constexpr bool kGrow = true;
+  __device__ __forceinline__ unsigned key(int i) const {
+    return ~(__float_as_uint(__fmul_rn(mask_momentum(m[i], v[i]), __fsub_rn(1.0f, k[i]))) & 0x7fffffffu);
+  }
+};
 
 // The tie-ranked pick of one 64-element step of a wave's segment: every key below the boundary, and the boundary's ties up to
 // rank sel.take (all: every tie).  run: the ties before this step, advanced by the step's.  A wave-wide ballot: every lane
@@ -156,11 +191,12 @@ __device__ __forceinline__ bool mask_pick(unsigned key, bool in, const MaskSel& 
   return in && (key < sel.T || (tie && (all || rank < sel.take)));
 }
 
-// The K-th smallest key of n (1 <= K <= n) and the number of its ties inside the selection -> s.sel.  x: the weights
-// (prune) or the gradients (grow).  H, the heavy key, is the smallest possible key when pruning and the largest when growing.
-template <bool GROW>
-__device__ void mask_select(const float* x, const float* k, int n, int K, MaskLds& s) {
-  const unsigned H = GROW ? 0xffffffffu : 0u;
+// The K-th smallest key of n (1 <= K <= n) and the number of its ties inside the selection -> s.sel.  src: the key source
+// (KeyAbsW, KeyGrad, KeyMom).
+template <class Src>
+__device__ void mask_select(const Src& src, int n, int K, MaskLds& s) {
+  constexpr unsigned H = Src::kHeavy;
+  constexpr bool GROW = Src::kGrow;
   const int t = threadIdx.x, lane = t & 63;
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
@@ -174,7 +210,7 @@ __device__ void mask_select(const float* x, const float* k, int n, int K, MaskLd
       for (int base = t - lane; base < n; base += kMaskThreads) {
         const int i = base + lane;
         const bool in = i < n;
-        const unsigned key = in ? mask_key<GROW>(x, k, i) : H;
+        const unsigned key = in ? src.key(i) : H;
         if (pass == 0) {
           heavy += in && key == H;
           mask_hist_add(s.hist, key >> 24, in && key != H, lane);
@@ -217,8 +253,8 @@ __device__ void mask_select(const float* x, const float* k, int n, int K, MaskLd
 
 // Ranks of the boundary's ties: when the selection takes only some of them, wave_base = how many lie in the segments of
 // the waves before this one.  Every wave owns the contiguous segment [wave * seg, (wave + 1) * seg) of the layer.
-template <bool GROW>
-__device__ int mask_tie_base(const float* x, const float* k, int n, int seg, MaskLds& s) {
+template <class Src>
+__device__ int mask_tie_base(const Src& src, int n, int seg, MaskLds& s) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const MaskSel sel = s.sel;
   if (sel.take >= sel.ties) return 0;                         // (uniform: every tie is selected, no rank is needed)
@@ -226,7 +262,7 @@ __device__ int mask_tie_base(const float* x, const float* k, int n, int seg, Mas
   const int end = min(n, (wave + 1) * seg);
   for (int base = wave * seg; base < end; base += 64) {
     const int i = base + lane;
-    cnt += __popcll(__ballot(i < end && mask_key<GROW>(x, k, i) == sel.T));
+    cnt += __popcll(__ballot(i < end && src.key(i) == sel.T));
   }
   if (lane == 0) s.wave_cnt[wave] = cnt;
   __syncthreads();
@@ -256,10 +292,78 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_count(MaskArgs a) {
   }
 }
 
+// every wave owns the contiguous segment [wave * seg, (wave + 1) * seg) of a layer of n elements, seg a multiple of 64
+__device__ __forceinline__ int mask_seg(int n) { return ((n + kMaskWaves - 1) / kMaskWaves + 63) / 64 * 64; }
+
+// steps 3 and 4 of the contract for the layer p, live0 of its elements live and dead0 masked out: -> removed.  The caller
+// zeroed s.acc[3] behind a barrier.  (Left early only on the rate: uniform over the workgroup.)
+__device__ int mask_prune(const MaskLayer& p, long long live0, long long dead0, double rate, int seg, MaskLds& s) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = p.n;
+  const double dropd = ceil(rate * (double)live0);
+  if (!(dropd > 0.0)) return 0;
+  const int end = min(n, (wave + 1) * seg);
+  const int K = (int)fmin((double)dead0 + dropd, (double)n);
+  const KeyAbsW src{p.w};
+  mask_select(src, n, K, s);
+  int run = mask_tie_base(src, n, seg, s), gone = 0;
+  const MaskSel sel = s.sel;
+  const bool all = sel.take >= sel.ties;
+  for (int base = wave * seg; base < end; base += 64) {
+    const int i = base + lane;
+    const bool in = i < end;
+    const bool pick = mask_pick(in ? src.key(i) : 0xffffffffu, in, sel, all, run, lane);
+    const bool was_live = pick && p.k[i] == 1.0f;
+    if (pick) p.k[i] = 0.0f;
+    gone += __popcll(__ballot(was_live));
+  }
+  if (lane == 0 && gone) atomicAdd(&s.acc[3], gone);
+  __syncthreads();                                            // (the new k of every wave is visible to the growth that follows)
+  return s.acc[3];
+}
+
+// bits of |mom_i| of the SNFS statistic (sf_mask_update_snfs, below)
+__device__ __forceinline__ unsigned snfs_abs_mom(float m, float v) { return __float_as_uint(mask_momentum(m, v)) & 0x7fffffffu; }
+
+// Step 5 (budget > 0: the `budget` elements smallest in src's key get k = 1, and w = +0.0 where zero_grown), step 6 and the
+// counts of step 7 -> s.acc[0 .. 2], which the caller zeroed behind a barrier and reads behind one.  seen(i): what the caller
+// wants of element i once its state is final (k_mask_update: nothing).  (budget: uniform over the workgroup.)
+template <class Src, class Seen>
+__device__ void mask_grow_apply(const MaskLayer& p, const Src& src, int budget, bool zero_grown, bool sparse_grads, int seg,
+                                MaskLds& s, Seen seen) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = p.n;
+  const int end = min(n, (wave + 1) * seg);
+  const bool grow = budget > 0;
+  int run = 0;
+  if (grow) {
+    mask_select(src, n, min(budget, n), s);
+    run = mask_tie_base(src, n, seg, s);
+  }
+  const MaskSel sel = s.sel;
+  const bool all = sel.take >= sel.ties;
+  MaskTally c{};
+  for (int base = wave * seg; base < end; base += 64) {
+    const int i = base + lane;
+    const bool in = i < end;
+    float kv = in ? p.k[i] : -1.0f, wv = in ? p.w[i] : 0.0f;
+    const float gv = in ? p.g[i] : 0.0f;
+    // (grow is uniform over the workgroup: every lane of the wave reaches the pick's ballot or none does)
+    if (grow && mask_pick(in ? src.key(i) : 0xffffffffu, in, sel, all, run, lane)) {
+      kv = 1.0f;
+      if (zero_grown) wv = 0.0f;
+      p.k[i] = 1.0f;
+    }
+    if (in) {
+      mask_apply(p, i, wv, gv, kv, sparse_grads, c);
+      seen(i);
+    }
+  }
+  c.commit(s.acc, lane);
+}
+
 // steps 2 - 7 of the contract for layer blockIdx.x
 __global__ __launch_bounds__(kMaskThreads) void k_mask_update(MaskArgs a) {
   __shared__ MaskLds s;
-  const int j = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int j = blockIdx.x, t = threadIdx.x;
   const MaskLayer p = mask_layer(a, j);
   const int n = p.n;
   long long S = 0;
@@ -268,62 +372,13 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_update(MaskArgs a) {
     if (j == 0 && t == 0) a.rows[a.L].live_before = 1;
     return;
   }
-  const long long live0 = a.rows[j].live_before, dead0 = a.rows[j].dead_before;
   const double rate = mask_rate(a.rows, j, n, a.L, S, a.rate);
-  const double dropd = ceil(rate * (double)live0);
-  const int seg = ((n + kMaskWaves - 1) / kMaskWaves + 63) / 64 * 64;
-  const int end = min(n, (wave + 1) * seg);
+  const int seg = mask_seg(n);
   if (t < 4) s.acc[t] = 0;
   __syncthreads();
-
-  // 4. prune
-  int removed = 0;
-  if (dropd > 0.0) {
-    const int K = (int)fmin((double)dead0 + dropd, (double)n);
-    mask_select<false>(p.w, p.k, n, K, s);
-    int run = mask_tie_base<false>(p.w, p.k, n, seg, s), gone = 0;
-    const MaskSel sel = s.sel;
-    const bool all = sel.take >= sel.ties;
-    for (int base = wave * seg; base < end; base += 64) {
-      const int i = base + lane;
-      const bool in = i < end;
-      const bool pick = mask_pick(in ? mask_key<false>(p.w, p.k, i) : 0xffffffffu, in, sel, all, run, lane);
-      const bool was_live = pick && p.k[i] == 1.0f;
-      if (pick) p.k[i] = 0.0f;
-      gone += __popcll(__ballot(was_live));
-    }
-    if (lane == 0 && gone) atomicAdd(&s.acc[3], gone);
-    __syncthreads();                                          // (the new k of every wave is visible to the growth below)
-    removed = s.acc[3];
-  }
-
-  // 5. grow
-  const bool grow = a.growth == 1 && removed > 0;   // (removed > 0: not every k of the layer is 1)
-  int run = 0;
-  if (grow) {
-    mask_select<true>(p.g, p.k, n, min(removed, n), s);
-    run = mask_tie_base<true>(p.g, p.k, n, seg, s);
-  }
-  const MaskSel sel = s.sel;
-  const bool all = sel.take >= sel.ties;
-
-  // 5. (the picks) + 6. apply + the counts of 7.
-  const bool sparse_grads = a.dense == 0;
-  MaskTally c{};
-  for (int base = wave * seg; base < end; base += 64) {
-    const int i = base + lane;
-    const bool in = i < end;
-    float kv = in ? p.k[i] : -1.0f, wv = in ? p.w[i] : 0.0f;
-    const float gv = in ? p.g[i] : 0.0f;
-    // (grow is uniform over the workgroup: every lane of the wave reaches the pick's ballot or none does)
-    if (grow && mask_pick(in ? mask_key<true>(gv, kv) : 0xffffffffu, in, sel, all, run, lane)) {
-      kv = 1.0f;
-      wv = 0.0f;
-      p.k[i] = 1.0f;
-    }
-    if (in) mask_apply(p, i, wv, gv, kv, sparse_grads, c);
-  }
-  c.commit(s.acc, lane);
+  const int removed = mask_prune(p, a.rows[j].live_before, a.rows[j].dead_before, rate, seg, s);      // 3., 4.
+  // 5. (growth 1, removed > 0: not every k of the layer is 1), 6. and the counts of 7.
+  mask_grow_apply(p, KeyGrad{p.g, p.k}, a.growth == 1 ? removed : 0, true, a.dense == 0, seg, s, [](int) {});
   __syncthreads();
   if (t == 0) {
     MaskRow& r = a.rows[j];
@@ -332,6 +387,270 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_update(MaskArgs a) {
     r.dead_after = s.acc[1];
     r.nnz_after = s.acc[2];
     r.prune_rate = rate;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sf_mask_update_snfs — the update of masking=SNFS on the device (magnitude pruning, growth by |momentum| or |gradient|, the
+// regrowth redistributed by the mean |momentum| of the live weights), no host synchronisation.
+//
+// Reference being replaced: core.py:713-801 truncate_weights with core.py:425-464 gather_statistics,
+// funcs/redistribute.py:18-37 momentum_redistribution, core.py:299-360 calc_redistributed_densities, funcs/grow.py:25-55
+// momentum_growth, core.py:474-493 get_momentum_for_weight.  Three launches whatever the depth and however many rounds the
+// water-filling takes, one workgroup per masked layer.
+//
+// The contract (counts exact integers; every double operation IEEE round to nearest, none contracted; mom_i =
+// m_i / (sqrt(v_i) + 1e-8f) as three fp32 operations rounded to nearest, mask_momentum above):
+//   1. live_j, dead_j, nnz_j as step 1 of sf_mask_update                                                      (k_snfs_stat)
+//   2. statistic 0: stat_j = (double)nnz_j.  statistic 1, a_i = |mom_i|: amax_j = the largest a_i over EVERY element of the
+//      layer (an integer max on the bits); a non-finite a_i or live_j == 0 -> status 3.  e: amax_j < 2^e (frexp; of 1.0 when
+//      amax_j == 0), ln the least with n + 1 <= 2^ln, s = 60 - ln - e; A_j = sum over k_i == 1 of llrint((double)a_i * 2^s), a
+//      64-bit integer sum (it cannot overflow: every term is at most 2^(60 - ln), there are fewer than 2^ln);
+//      stat_j = ((double)A_j * 2^-s) / (double)live_j.  An integer sum: any order gives the same bits
+//      norm = sum of stat_j in layer order from 0.0; status 3 if any layer asked for it, else status 1 if norm == 0: the
+//      state is untouched.  share_j = stat_j / norm                                                          (k_snfs_prune)
+//   3. rate_j: step 2 of sf_mask_update with share_j; drop_j = ceil(rate_j * live_j); the prune of step 4 there -> removed_j
+//   4. statistic 0: budget_j = removed_j.  statistic 1 (calc_redistributed_densities): R = sum removed_j,
+//      pool = (double)R + adjusted_growth, cap_j = 0.99 * (double)(dead_j + removed_j), budget_j = rint(share_j * pool) (half to
+//      even), share = 0; at most 1000 rounds of { excess = 0; for j ascending: want = budget_j + share; if want > cap_j:
+//      excess += want - cap_j, want = cap_j; budget_j = want; then share = excess / (double)L; stop unless excess > 0 }.
+//      grown_j = (int)budget_j, truncated.  Thread 0 of EVERY workgroup of k_snfs_grow runs these doubles from the same rows:
+//      the same operations in the same order, so the same bits                                                (k_snfs_grow)
+//   5. grown_j > 0.  growth 2: c_i = |mom_i * (1 - k_i)| (an fp32 product, k after the prune), the grown_j elements largest
+//      in c_i, ties to the lower index, get k_i = 1; w_i is NOT written (a weight pruned in 3 and grown here keeps its
+//      value).  growth 1: step 5 of sf_mask_update with grown_j in place of removed (w_i = +0.0)
+//   6. step 6 of sf_mask_update
+//   7. row j (SnfsRow, 12 words): the eight words of sf_mask_update's row; stat_j; budget_j, the double before truncation;
+//      grown_j; stat_after_j = step 2 over the state steps 5 and 6 left (statistic 1: NaN when no weight is live)
+//      status row: [0] status (0, 1, 3) [1] rounds [2] R [3] sum grown_j [7] pool [8] norm [11] the norm after: the sum of
+//      the stat_after_j that are not NaN, in layer order; every other word 0.  Status 1 or 3: rows j hold the counts before,
+//      copied to the counts after, and zeros; the status row its status and zeros.
+// The norm after needs every layer's row: the workgroup that finishes last (an arrival count in word [6] of the status row,
+// device-scope atomics and fences, put back to 0) sums them.  No float is ever added atomically.
+
+constexpr unsigned kMaskInf = 0x7f800000u;
+
+struct SnfsRow {                  // sf_mask_snfs_stats (include/siren_fit.h); row [n_layers] is the status row
+  long long live_before, dead_before, nnz_before, removed, live_after, dead_after, nnz_after;
+  double prune_rate, stat_before, budget;
+  long long grown;                // (between k_snfs_stat and k_snfs_grow: 1 where the layer asks for status 3)
+  double stat_after;
+};
+
+struct SnfsArgs {
+  MaskArgs m;                     // w, g, m, v, k, off, n, L, rate, growth, dense (rows unused)
+  SnfsRow* rows;
+  double adjusted_growth;
+  int statistic;
+};
+
+struct SnfsLds {
+  unsigned amax;                  // bits of the largest |mom| of the layer
+  unsigned long long A;           // the fixed-point sum
+  double budget[kMaskMaxLayers], cap[kMaskMaxLayers];
+  int grown[kMaskMaxLayers];
+};
+
+// the wave's largest value -> LDS (an integer max: any order gives the same word); every lane of the wave calls it
+__device__ __forceinline__ void snfs_commit_max(unsigned amax, unsigned* dst, int lane) {
+  for (int d = 32; d > 0; d >>= 1) amax = max(amax, (unsigned)__shfl_down((int)amax, d));
+  if (lane == 0 && amax) atomicMax(dst, amax);
+}
+
+// Step 2's statistic of the layer p whose largest |mom| has the bits amax (finite) and that has live > 0 live weights.
+// Every thread of the workgroup calls it (barriers); q.A was zeroed behind a barrier.
+__device__ double snfs_stat(const MaskLayer& p, unsigned amax, long long live, SnfsLds& q) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x, lane = t & 63;
+  const float top = __uint_as_float(amax);
+  int e = 0, ln = 0;
+  frexpf(top > 0.f ? top : 1.f, &e);                             // top < 2^e
+  while ((1L << ln) < (long)p.n + 1) ++ln;                       // n < 2^ln
+  const int sh = 60 - ln - e;
+  const double scale = ldexp(1.0, sh);
+  long long sum = 0;
+  for (int i = t; i < p.n; i += kMaskThreads) {
+    if (p.k[i] != 1.0f) continue;
+    const double a = (double)__uint_as_float(snfs_abs_mom(p.m[i], p.v[i]));
+    sum += __double2ll_rn(a * scale);                            // (a power of two: the product is exact)
+  }
+  for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d);
+  if (lane == 0 && sum) atomicAdd(&q.A, (unsigned long long)sum);
+  __syncthreads();
+  const double total = (double)(long long)q.A;
+  const double unscaled = total * ldexp(1.0, -sh);
+  return unscaled / (double)live;
+}
+
+// steps 1 and 2 (the statistic) for layer blockIdx.x -> its row; the status row cleared
+__global__ __launch_bounds__(kMaskThreads) void k_snfs_stat(SnfsArgs a) {
+  __shared__ SnfsLds q;
+  __shared__ int acc[3];
+  const int j = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const MaskLayer p = mask_layer(a.m, j);
+  const bool stat = a.statistic == 1;
+  if (t < 3) acc[t] = 0;
+  if (t == 0) { q.amax = 0; q.A = 0; }
+  __syncthreads();
+  MaskTally c{};
+  unsigned amax = 0;
+  for (int i = t; i < p.n; i += kMaskThreads) {
+    c.add(p.w[i], p.k[i]);
+    if (stat) amax = max(amax, snfs_abs_mom(p.m[i], p.v[i]));
+  }
+  c.commit(acc, lane);
+  snfs_commit_max(amax, &q.amax, lane);
+  __syncthreads();
+  const long long live = acc[0];
+  const bool bad = stat && (q.amax >= kMaskInf || live == 0);
+  double value = (double)acc[2];
+  if (stat && !bad) value = snfs_stat(p, q.amax, live, q);      // (uniform over the workgroup)
+  if (t == 0) {
+    SnfsRow r{};
+    r.live_before = r.live_after = live;
+    r.dead_before = r.dead_after = acc[1];
+    r.nnz_before = r.nnz_after = acc[2];
+    r.stat_before = bad ? 0.0 : value;
+    r.grown = bad;
+    a.rows[j] = r;
+    if (j == 0) a.rows[a.m.L] = SnfsRow{};
+  }
+}
+
+// the norm and the status of step 2, the shares, step 3 for layer blockIdx.x
+__global__ __launch_bounds__(kMaskThreads) void k_snfs_prune(SnfsArgs a) {
+  __shared__ MaskLds s;
+  const int j = blockIdx.x, t = threadIdx.x, L = a.m.L;
+  const MaskLayer p = mask_layer(a.m, j);
+  SnfsRow* rows = a.rows;
+  bool bad = false;
+  double norm = 0.0;
+  {
+#pragma clang fp contract(off)
+    for (int l = 0; l < L; ++l) {
+      bad |= rows[l].grown != 0;
+      norm = norm + rows[l].stat_before;
+    }
+  }
+  const int status = bad ? 3 : norm == 0.0 ? 1 : 0;
+  if (status) {                                               // (uniform over the grid: nothing is touched)
+    if (j == 0 && t == 0) rows[L].live_before = status;
+    return;
+  }
+  const double share = rows[j].stat_before / norm;
+  const double rate = mask_rate(share, rows[j].dead_before, p.n, L, a.m.rate);
+  if (t < 4) s.acc[t] = 0;
+  __syncthreads();
+  const int removed = mask_prune(p, rows[j].live_before, rows[j].dead_before, rate, mask_seg(p.n), s);
+  if (t == 0) {                                               // (fields no other workgroup of this kernel reads)
+    rows[j].removed = removed;
+    rows[j].prune_rate = rate;
+    if (j == 0) rows[L].stat_before = norm;
+  }
+}
+
+// step 4 (thread 0): the budgets of all L layers from the rows -> q.budget, q.grown; block 0 also fills the status row
+__device__ void snfs_budgets(const SnfsArgs& a, SnfsLds& q, bool report) {
+#pragma clang fp contract(off)
+  const int L = a.m.L;
+  SnfsRow* rows = a.rows;
+  long long R = 0, total = 0;
+  for (int l = 0; l < L; ++l) R += rows[l].removed;
+  const double pool = (double)R + a.adjusted_growth;
+  int rounds = 0;
+  if (a.statistic == 0) {
+    for (int l = 0; l < L; ++l) q.budget[l] = (double)rows[l].removed;
+  } else {
+    const double norm = rows[L].stat_before;
+    for (int l = 0; l < L; ++l) {
+      const double share_l = rows[l].stat_before / norm;
+      const double asked = share_l * pool;
+      q.budget[l] = rint(asked);
+      q.cap[l] = 0.99 * (double)(rows[l].dead_before + rows[l].removed);
+    }
+    double share = 0.0;
+    while (rounds < 1000) {
+      double excess = 0.0;
+      for (int l = 0; l < L; ++l) {
+        double want = q.budget[l] + share;
+        const double c = q.cap[l];
+        if (want > c) {
+          const double over = want - c;
+          excess = excess + over;
+          want = c;
+        }
+        q.budget[l] = want;
+      }
+      share = excess / (double)L;
+      ++rounds;
+      if (!(excess > 0.0)) break;
+    }
+  }
+  for (int l = 0; l < L; ++l) {
+    q.grown[l] = (int)q.budget[l];
+    total += q.grown[l];
+  }
+  if (report) {
+    SnfsRow& z = rows[L];
+    z.dead_before = rounds;
+    z.nnz_before = R;
+    z.removed = total;
+    z.prune_rate = pool;
+  }
+}
+
+// steps 4 - 7 for layer blockIdx.x
+__global__ __launch_bounds__(kMaskThreads) void k_snfs_grow(SnfsArgs a) {
+  __shared__ MaskLds s;
+  __shared__ SnfsLds q;
+  const int j = blockIdx.x, t = threadIdx.x, lane = t & 63, L = a.m.L;
+  const MaskLayer p = mask_layer(a.m, j);
+  SnfsRow* rows = a.rows;
+  if (rows[L].live_before != 0) {                             // (status 1 or 3, uniform over the grid: nothing is touched)
+    if (t == 0) { rows[j].stat_before = 0.0; rows[j].grown = 0; }
+    return;
+  }
+  const bool stat = a.statistic == 1;
+  if (t < 4) s.acc[t] = 0;
+  if (t == 0) {
+    q.amax = 0; q.A = 0;
+    snfs_budgets(a, q, j == 0);
+  }
+  __syncthreads();
+  const int grown = q.grown[j], seg = mask_seg(p.n);
+  const bool sparse_grads = a.m.dense == 0;
+  unsigned amax = 0;                                          // the lane's largest |mom| bits over the state the pass leaves
+  auto seen = [&](int i) { if (stat) amax = max(amax, snfs_abs_mom(p.m[i], p.v[i])); };
+  if (a.m.growth == 2) mask_grow_apply(p, KeyMom{p.m, p.v, p.k}, grown, false, sparse_grads, seg, s, seen);
+  else mask_grow_apply(p, KeyGrad{p.g, p.k}, grown, true, sparse_grads, seg, s, seen);
+  snfs_commit_max(amax, &q.amax, lane);
+  __syncthreads();                                            // (the counts, the largest |mom|, the state every wave left)
+  const long long live = s.acc[0];
+  double after = (double)s.acc[2];
+  if (stat) after = live == 0 ? __longlong_as_double(0x7ff8000000000000ll) : snfs_stat(p, q.amax, live, q);      // (uniform)
+  if (t == 0) {
+    SnfsRow& r = rows[j];
+    r.live_after = live;
+    r.dead_after = s.acc[1];
+    r.nnz_after = s.acc[2];
+    r.budget = q.budget[j];
+    r.grown = grown;
+    using u64 = unsigned long long;
+    __hip_atomic_store(reinterpret_cast<u64*>(&r.stat_after), (u64)__double_as_longlong(after), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the norm after: the workgroup that arrives last sums every layer's stat_after in layer order
+    __threadfence();
+    u64* arrived = reinterpret_cast<u64*>(&rows[L].nnz_after);
+    if (atomicAdd(arrived, (u64)1) == (u64)(L - 1)) {
+#pragma clang fp contract(off)
+      __threadfence();
+      double norm = 0.0;
+      for (int l = 0; l < L; ++l) {
+        const double v = __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<u64*>(&rows[l].stat_after), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (v == v) norm = norm + v;
+      }
+      rows[L].stat_after = norm;
+      __hip_atomic_store(arrived, (u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
 }
 
@@ -406,7 +725,7 @@ template <bool SCATTER>
 __global__ __launch_bounds__(kMaskThreads) void k_prune_file(PruneArgs a) {
   const MaskLayer p = mask_layer(a.m, blockIdx.x);
   for (int i = blockIdx.y * kMaskThreads + threadIdx.x; i < p.n; i += gridDim.y * kMaskThreads) {
-    const unsigned key = mask_key<false>(p.w, p.k, i);
+    const unsigned key = mask_key<false>(p.w[i], 0.0f);
     if (!prune_filed(key)) continue;
     const int pos = atomicAdd(&a.ws->hist[key >> 15], 1);
     if (SCATTER && pos >= 0 && pos < a.cap) a.keys[pos] = key;

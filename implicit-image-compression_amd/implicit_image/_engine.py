@@ -78,8 +78,21 @@ class sf_mask_prune_global_args(C.Structure):
                 ("tolerance", C.c_double), ("dense_gradients", C.c_int32), ("stats_dev", C.c_void_p)]
 
 
+class sf_mask_snfs_stats(C.Structure):
+    _fields_ = sf_mask_layer_stats._fields_ + [("stat_before", C.c_double), ("budget", C.c_double), ("grown", C.c_int64),
+                                               ("stat_after", C.c_double)]
+
+
+class sf_mask_update_snfs_args(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("n_layers", C.c_int32), ("layers", C.POINTER(C.c_int32)),
+                ("prune_rate", C.c_double), ("adjusted_growth", C.c_double), ("growth", C.c_int32), ("statistic", C.c_int32),
+                ("dense_gradients", C.c_int32), ("stats_dev", C.c_void_p)]
+
+
 MASK_STATS_WORDS = C.sizeof(sf_mask_layer_stats) // 8      # a statistics row as int64 words (the last one: a double)
-MASK_GROWTH = {"none": 0, "absolute-gradient": 1}
+MASK_SNFS_STATS_WORDS = C.sizeof(sf_mask_snfs_stats) // 8  # ... of sf_mask_update_snfs (words 7, 8, 9 and 11: doubles)
+MASK_GROWTH = {"none": 0, "absolute-gradient": 1, "momentum": 2}
+MASK_STATISTIC = {"none": 0, "nonzero": 0, "momentum": 1}
 
 _lib = None
 
@@ -156,6 +169,8 @@ _declare("core", {
 _declare("core", {"sf_mask_update": [H, P(sf_mask_update_args)]})
 # (the global-magnitude update of masking=Pruning on the device, same file; has_mask_prune_global asks for the symbol itself)
 _declare("core", {"sf_mask_prune_global": [H, P(sf_mask_prune_global_args)]})
+# (the update of masking=SNFS on the device, same file; has_mask_update_snfs asks for the symbol itself)
+_declare("core", {"sf_mask_update_snfs": [H, P(sf_mask_update_snfs_args)]})
 
 
 def load_library():
@@ -227,6 +242,11 @@ def has_mask_update(lib) -> bool:
 def has_mask_prune_global(lib) -> bool:
     """sf_mask_prune_global: the global-magnitude update of masking=Pruning on the device (csrc/siren_mask.hip)"""
     return hasattr(lib, "sf_mask_prune_global")
+
+
+def has_mask_update_snfs(lib) -> bool:
+    """sf_mask_update_snfs: the momentum-growth, momentum-redistribution update of masking=SNFS on the device"""
+    return hasattr(lib, "sf_mask_update_snfs")
 
 
 def _require(lib, has, entry: str, since: str):
@@ -417,13 +437,24 @@ class SirenEngine:
                         threshold=float(threshold), increment=float(increment), tolerance=float(tolerance),
                         dense_gradients=int(bool(dense_gradients)))
 
-    def _mask_call(self, entry, args_type, has, what, layers, stats, **fields):
-        """one topology update entry point: the library has it, `stats` is a statistics table for `layers`, the call"""
+    def mask_update_snfs(self, layers: Sequence[int], prune_rate: float, adjusted_growth: float, growth: int, statistic: int,
+                         dense_gradients: bool, stats: Optional[torch.Tensor] = None):
+        """sf_mask_update_snfs on this handle's stream, no host sync: one SNFS topology update of the weights of `layers` -
+        the redistribution statistic, the prune, the regrowth budgets, the growth (MASK_GROWTH), the products.  stats: int64
+        [len(layers) + 1, MASK_SNFS_STATS_WORDS] on the device or None - a sf_mask_snfs_stats per layer and the status row
+        (status, rounds, removed in all, grown in all, ..., the pool, the norm before, ..., the norm after)."""
+        self._mask_call("sf_mask_update_snfs", sf_mask_update_snfs_args, has_mask_update_snfs, "the device SNFS update", layers,
+                        stats, words=MASK_SNFS_STATS_WORDS, prune_rate=float(prune_rate), adjusted_growth=float(adjusted_growth),
+                        growth=int(growth), statistic=int(statistic), dense_gradients=int(bool(dense_gradients)))
+
+    def _mask_call(self, entry, args_type, has, what, layers, stats, words=MASK_STATS_WORDS, **fields):
+        """one topology update entry point: the library has it, `stats` is a statistics table of `words`-word rows for
+        `layers`, the call"""
         _require(self.lib, has, f"{entry} entry point", what)
         n = len(layers)
         if stats is not None and not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous()
-                                      and stats.numel() == (n + 1) * MASK_STATS_WORDS):
-            raise ValueError(f"{entry[3:]}: stats must be a contiguous int64 CUDA tensor of {(n + 1) * MASK_STATS_WORDS} words")
+                                      and stats.numel() == (n + 1) * words):
+            raise ValueError(f"{entry[3:]}: stats must be a contiguous int64 CUDA tensor of {(n + 1) * words} words")
         args = args_type(abi_version=SF_ABI_VERSION, n_layers=n, layers=(C.c_int32 * max(n, 1))(*layers),
                          stats_dev=None if stats is None else stats.data_ptr(), **fields)
         _check(getattr(self.lib, entry)(self.h, C.byref(args)))
@@ -634,6 +665,7 @@ class FourierEngine(SirenEngine):
     _CREATE = "sf_fourier_create"
     mask_update = None          # sf_mask_update refuses a FourierNet handle: Masking keeps such a model on the host path
     mask_prune_global = None    # (sf_mask_prune_global likewise)
+    mask_update_snfs = None     # (sf_mask_update_snfs likewise)
 
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
@@ -677,6 +709,7 @@ class WaveletEngine(SirenEngine):
     _CREATE = "sf_wavelet_create"
     mask_update = None          # sf_mask_update refuses a WaveletSiren handle: its topology updates stay on the host
     mask_prune_global = None    # (sf_mask_prune_global likewise)
+    mask_update_snfs = None     # (sf_mask_update_snfs likewise)
 
     def set_coords(self, rows: torch.Tensor, cols: torch.Tensor):
         """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""

@@ -17,6 +17,13 @@ section 12).  `stats`, `name2prune_rate`, `adjustments` and `adjusted_growth` ar
 The configuration Pruning ships with (global-magnitude pruning, no growth, no redistribution) runs on the device in the same
 way: one `sf_mask_prune_global` call - the threshold search included - and `prune_threshold` joins the attributes that are
 completed on their first read (the next global update reads it, so it completes the one before with one transfer).
+The configuration SNFS ships with (magnitude pruning, momentum growth, momentum redistribution) runs on the device as one
+`sf_mask_update_snfs` call, and so does every other pairing of magnitude pruning with momentum or absolute-gradient growth
+under redistribution momentum, none or nonzero that the RigL route does not cover.  With the momentum statistic the call takes
+`adjusted_growth` by value, so reading it completes the update before (one transfer); while it is negative the update runs
+on the host (the pool of regrown weights would be smaller than what was removed: the reference's negative-slice case).  The
+statistic of that route is an exact fixed-point sum, not torch's fp32 mean: the two routes agree to about 1e-7 relative in
+`stats.variance_dict` and, away from rounding and tie boundaries, bit for bit in everything else.
 """
 import logging
 import math
@@ -50,14 +57,23 @@ class LayerStats:
         return self.total_nonzero / tot if tot else 0.0
 
 
-# The device routes of update_connections() by what differs between them: the prune mode and the growth modes a route covers,
-# the engine method with the _engine predicate for its library symbol, and the Masking method that gives the call's own
-# arguments (between `layers` and `dense_gradients, stats`).
-DeviceRoute = namedtuple("DeviceRoute", "name prune_mode growth_modes method has args")
+# The device routes of update_connections() by what differs between them: the prune mode, the growth modes and the
+# redistribution modes a route covers (the first row that covers all three takes the update), the engine method with the
+# _engine predicate for its library symbol, the Masking method that gives the call's own arguments (between `layers` and
+# `dense_gradients, stats`; None: not this time, the update runs on the host), and the _engine name of its row width.
+DeviceRoute = namedtuple("DeviceRoute", "name prune_mode growth_modes redistribution_modes method has args words")
 DevicePlan = namedtuple("DevicePlan", "route eng layers slices")
-RIGL_ROUTE = DeviceRoute("rigl", "magnitude", ("none", "absolute-gradient"), "mask_update", "has_mask_update", "_rigl_args")
-GLOBAL_ROUTE = DeviceRoute("global", "global-magnitude", ("none",), "mask_prune_global", "has_mask_prune_global", "_global_args")
-DEVICE_ROUTES = (RIGL_ROUTE, GLOBAL_ROUTE)
+RIGL_ROUTE = DeviceRoute("rigl", "magnitude", ("none", "absolute-gradient"), ("none", "nonzero"), "mask_update",
+                         "has_mask_update", "_rigl_args", "MASK_STATS_WORDS")
+SNFS_ROUTE = DeviceRoute("snfs", "magnitude", ("absolute-gradient", "momentum"), ("momentum", "none", "nonzero"),
+                         "mask_update_snfs", "has_mask_update_snfs", "_snfs_args", "MASK_SNFS_STATS_WORDS")
+GLOBAL_ROUTE = DeviceRoute("global", "global-magnitude", ("none",), ("none", "nonzero"), "mask_prune_global",
+                           "has_mask_prune_global", "_global_args", "MASK_STATS_WORDS")
+DEVICE_ROUTES = (RIGL_ROUTE, SNFS_ROUTE, GLOBAL_ROUTE)
+
+
+def _as_double(word: int) -> float:
+    return struct.unpack("<d", struct.pack("<q", word))[0]
 
 
 class Masking:
@@ -116,26 +132,32 @@ class Masking:
         exactly the values, and the float sequence, of truncate_weights() below."""
         while self._pending:
             rows, names, route = self._pending.pop(0)
-            global_prune = route is GLOBAL_ROUTE
+            global_prune, snfs = route is GLOBAL_ROUTE, route is SNFS_ROUTE
             rows = rows.cpu().tolist()
             status = rows[len(names)]
             if global_prune and status[0] == 2:
                 raise RuntimeError(f"sf_mask_prune_global: the threshold search did not end within {status[1]} trials")
+            if snfs and status[0] == 3:
+                raise RuntimeError("sf_mask_update_snfs: a masked layer has no redistribution statistic (no live weight, or "
+                                   "a momentum that is not finite)")
             assert not status[0], "Total variance is zero!"
             live, dead, nnz = {}, {}, {}
             for pname, row in zip(names, rows):
-                self._name2prune_rate[pname] = struct.unpack("<d", struct.pack("<q", row[7]))[0]
+                self._name2prune_rate[pname] = _as_double(row[7])
                 live[pname], dead[pname], nnz[pname] = row[4], row[5], row[6]
+                if snfs:                        # (gather_statistics after the update: the route's statistic, not the non-zeros)
+                    nnz[pname] = _as_double(row[11])
             total_nonzero_new = sum(live.values())
             if global_prune:                    # (truncate_weights: total_nonzero before the update - what the search removed)
                 total_nonzero_new = status[2] - status[3]
-                self._prune_threshold = struct.unpack("<d", struct.pack("<q", status[7]))[0]
+                self._prune_threshold = _as_double(status[7])
             self._adjustments.append(self.baseline_nonzero - total_nonzero_new)
             self._adjusted_growth = (0.25 * self._adjusted_growth + 0.75 * self._adjustments[-1]
                                      + np.mean(self._adjustments))
             norm = 0.0
-            for v in nnz.values():              # (summed in layer order, as gather_statistics does)
-                norm += v
+            for v in nnz.values():              # (summed in layer order, NaN statistics skipped, as gather_statistics does)
+                if not np.isnan(v):
+                    norm += v
             assert norm, "Total variance is zero!"
             self._stats = LayerStats(variance_dict={k: v / norm for k, v in nnz.items()}, nonzeros_dict=live,
                                      zeros_dict=dead, total_variance=norm, total_nonzero=sum(live.values()),
@@ -352,15 +374,16 @@ class Masking:
     def _device_plan(self):
         """A DevicePlan when this update can run as one call of a device route, else None: an engine with the route's entry
         point under an unpadded model, every masked parameter the weight of an engine layer living in the engine's own
-        vectors (data, gradient and - where the moments are masked too - Adam state), the modes of a row of DEVICE_ROUTES
-        without a redistribution statistic, and SIREN_FIT_DEVICE_MASK not "0" (an A/B knob, like SIREN_FIT_NATIVE_KMEANS)."""
+        vectors (data, gradient and - where the moments are masked too - Adam state), the prune, growth and redistribution
+        modes of a row of DEVICE_ROUTES, and SIREN_FIT_DEVICE_MASK not "0" (an A/B knob, like SIREN_FIT_NATIVE_KMEANS)."""
         from ... import _engine
         eng = self.module.bound_engine
         if (self.device_update != "auto" or eng is None or os.environ.get("SIREN_FIT_DEVICE_MASK") == "0"
-                or not self.module.state_is_live or self.redistribution_mode not in ("none", "nonzero")):
+                or not self.module.state_is_live):
             return None
         for route in DEVICE_ROUTES:
             if (self.prune_mode == route.prune_mode and self.growth_mode in route.growth_modes
+                    and self.redistribution_mode in route.redistribution_modes
                     and callable(getattr(eng, route.method, None)) and getattr(_engine, route.has)(eng.lib)):
                 found = self._engine_slices(eng)
                 return found and DevicePlan(route, eng, *found)
@@ -396,19 +419,31 @@ class Masking:
         target = math.ceil(self.prune_rate * self.baseline_nonzero)
         return target, self.prune_rate, threshold, self.increment, self.tolerance
 
+    def _snfs_args(self):
+        from ... import _engine
+        statistic, growth = _engine.MASK_STATISTIC[self.redistribution_mode], 0.0
+        if statistic:                           # (the pool needs it: reading it completes a pending update, one transfer)
+            growth = float(self.adjusted_growth)
+            if growth < 0:                      # not this time: a pool below what was removed is the host path's business
+                return None
+        return self.prune_rate, growth, _engine.MASK_GROWTH[self.growth_mode], statistic
+
     @torch.no_grad()
-    def _device_update(self, plan):
-        """update_connections() as one call of the route's entry point: nothing is read back here, unless the global route
-        finds the update before this one still pending."""
+    def _device_update(self, plan) -> bool:
+        """update_connections() as one call of the route's entry point, unless its argument step says "not this time"
+        (False).  Nothing is read back here, unless the argument step finds the update before this one still pending."""
         from ... import _engine
         route, eng, layers, slices = plan
         args = getattr(self, route.args)()
+        if args is None:
+            return False
         self._push_masks()                      # mask_dict is the truth (callers replace its entries)
-        rows = torch.empty(len(layers) + 1, _engine.MASK_STATS_WORDS, dtype=torch.int64, device=eng.device)
+        rows = torch.empty(len(layers) + 1, getattr(_engine, route.words), dtype=torch.int64, device=eng.device)
         getattr(eng, route.method)(layers, *args, self.dense_gradients, rows)
         self._adopt_engine_masks(eng, slices)
         self.mask_step += 1
         self._pending.append((rows, [pname for pname, _, _ in slices], route))
+        return True
 
     def _adopt_engine_masks(self, eng, slices):
         flat = eng.view("masks")
@@ -418,9 +453,8 @@ class Masking:
 
     def update_connections(self):
         plan = self._device_plan()
-        if plan is not None:
-            return self._device_update(plan)
-        self.truncate_weights()
+        if plan is None or not self._device_update(plan):
+            self.truncate_weights()
 
     # ---- checkpoint surface (core.py:495-506, 660-669) -----------------------------------------
     def state_dict(self):

@@ -290,6 +290,71 @@ typedef struct sf_mask_prune_global_args {
   sf_mask_layer_stats* stats_dev;
 } sf_mask_prune_global_args;
 int sf_mask_prune_global(sf_handle* h, const sf_mask_prune_global_args* a);
+/* One SNFS topology update (masking=SNFS: Masking.update_connections of the reference with magnitude_prune, growth by
+ * |momentum| (funcs/grow.py:25-55) or |gradient|, and the regrowth redistributed by a per-layer statistic: core.py:425-464
+ * gather_statistics, funcs/redistribute.py:18-37, core.py:299-360 calc_redistributed_densities) on the handle's stream: three
+ * launches whatever the depth and however many rounds the redistribution takes, NO device-to-host copy and no host
+ * synchronisation (csrc/siren_mask.hip).  The state is the handle's flat fp32 vectors, as for sf_mask_update.
+ *   layers [n_layers]  host array: the engine layer indices, ascending, whose WEIGHT is masked
+ *   prune_rate         the current rate r of the decay schedule
+ *   adjusted_growth    Masking.adjusted_growth: what the pool of regrown weights holds beyond the weights removed, >= 0
+ *   growth             1 absolute gradient, 2 momentum
+ *   statistic          0 the non-zero count (redistribution none / nonzero), 1 the mean |momentum| of the live weights
+ *   dense_gradients    0: the moments and the gradient are masked too
+ *   stats_dev          device, n_layers rows + one status row of sf_mask_snfs_stats, may be NULL
+ * Counts are exact integers; every double operation is IEEE round to nearest and none is contracted into an FMA;
+ * mom_i = m_i / (sqrt(v_i) + 1e-8f) is three fp32 operations, each rounded to nearest (get_momentum_for_weight under Adam).
+ *   1. per listed layer j (n elements): live_j, dead_j, nnz_j as step 1 of sf_mask_update
+ *   2. statistic 0: stat_j = (double)nnz_j.  statistic 1, with a_i = |mom_i|:
+ *        amax_j = the largest a_i over EVERY element of the layer (an integer max on the bits); a non-finite a_i, or
+ *        live_j == 0, gives status 3 and leaves the state untouched (the host's round(nan) raises)
+ *        e: amax_j < 2^e (frexp; that of 1.0 when amax_j == 0); ln: the least with n + 1 <= 2^ln; s = 60 - ln - e
+ *        A_j = sum over k_i == 1 of llrint((double)a_i * 2^s), a 64-bit integer: no order of summation changes it, and it
+ *        cannot overflow (every term is at most 2^(60 - ln) and there are fewer than 2^ln of them)
+ *        stat_j = ((double)A_j * 2^-s) / (double)live_j
+ *      norm = sum of stat_j in layer order from 0.0; norm == 0 gives status 1 and leaves the state untouched (the host's
+ *      "Total variance is zero!"); status 3 comes first.  share_j = stat_j / norm
+ *   3. rate_j: step 2 of sf_mask_update with this share_j; drop_j = ceil(rate_j * live_j); the prune of step 4 there: the
+ *      dead_j + drop_j elements smallest in (|w_i|, i) get k_i = 0 -> removed_j
+ *   4. statistic 0: budget_j = removed_j.  statistic 1 (calc_redistributed_densities, literally): R = sum removed_j,
+ *      pool = (double)R + adjusted_growth, cap_j = 0.99 * (double)(dead_j + removed_j), budget_j = rint(share_j * pool), half to
+ *      even, share = 0; then at most 1000 rounds: excess = 0; for j ascending { want = budget_j + share; if want > cap_j
+ *      { excess += want - cap_j; want = cap_j }; budget_j = want }; share = excess / (double)n_layers; the loop ends after a
+ *      round whose excess is not > 0.  Each of these is one double operation, in this order.  grown_j = (int)budget_j, truncated
+ *   5. grown_j > 0.  growth 2: c_i = |mom_i * (1 - k_i)| as an fp32 product with k after the prune; the grown_j elements
+ *      largest in c_i, ties to the lower index, get k_i = 1.  w_i is NOT written: a weight pruned in step 3 and grown here
+ *      keeps its value, as momentum_growth leaves it.  growth 1: step 5 of sf_mask_update with grown_j in place of removed
+ *      (w_i = +0.0)
+ *   6. step 6 of sf_mask_update: w_i *= k_i; dense_gradients == 0: also m_i, v_i, g_i.  The weight images are marked dirty
+ *   7. row j: the eight words of sf_mask_layer_stats with the same meaning; stat_before = stat_j; budget = budget_j, the
+ *      double before truncation; grown = grown_j; stat_after = step 2's statistic over the state steps 5 and 6 left (statistic
+ *      1: NaN when no weight of the layer is live; gather_statistics leaves such a layer out of the norm).
+ *      The status row (row n_layers), as twelve 64-bit words in the order of the sf_mask_snfs_stats fields:
+ *        [0] status (0 done, 1 norm == 0, 3 no statistic)   [1] the rounds of step 4 (0 with statistic 0)   [2] R
+ *        [3] sum of grown_j   [7] pool, a double   [8] norm, a double   [11] the norm after: the stat_after that are not NaN
+ *        summed in layer order, a double; every other word 0
+ *      With status 1 or 3 rows 0 .. n_layers - 1 hold the counts before, copied to the counts after, and zeros; the status
+ *      row holds the status and zeros.
+ * With growth 1 and statistic 0 the five state vectors equal sf_mask_update's bit for bit.  Ties are broken as there.
+ * SF_ERR_INVALID / SF_ERR_STATE, before anything is launched: everything sf_mask_update refuses, a growth other than 1 or
+ * 2, a statistic other than 0 or 1, an adjusted_growth that is negative or not finite. */
+typedef struct sf_mask_snfs_stats {
+  int64_t live_before, dead_before, nnz_before, removed, live_after, dead_after, nnz_after;
+  double prune_rate;
+  double stat_before, budget;
+  int64_t grown;
+  double stat_after;
+} sf_mask_snfs_stats;
+typedef struct sf_mask_update_snfs_args {
+  int32_t abi_version, n_layers;
+  const int32_t* layers;
+  double prune_rate, adjusted_growth;
+  int32_t growth;            /* 1 absolute gradient, 2 momentum */
+  int32_t statistic;         /* 0 non-zero count, 1 momentum */
+  int32_t dense_gradients;
+  sf_mask_snfs_stats* stats_dev;
+} sf_mask_update_snfs_args;
+int sf_mask_update_snfs(sf_handle* h, const sf_mask_update_snfs_args* a);
 /* test aid for the "never throws" promise above: raises inside the library on purpose (0: std::bad_alloc -> SF_ERR_NOMEM,
  * 1: std::runtime_error, 2: a non-std exception -> SF_ERR_INVALID); every entry point is a function-try-block */
 int sf_debug_throw(int32_t kind);
