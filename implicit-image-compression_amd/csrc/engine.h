@@ -257,6 +257,8 @@ struct Launch {
   Launch(const Launch&) = delete;
   Launch& operator=(const Launch&) = delete;
 };
+// bytes a render launch is charged per output sample: 4 for the fp32 prediction, bits / 8 for the sample, each when asked for
+double render_sample_bytes(const void* out, int bits, const float* pred) { return (pred ? 4.0 : 0.0) + (out ? bits / 8.0 : 0.0); }
 
 int prof_flush(LaunchCtx* c) {
   if (c->recs.empty()) return SF_OK;

@@ -127,11 +127,6 @@ DEV float ff_block_sum(float v, float* sh) {
   return s;
 }
 
-// the byte tail of the render kernels (siren_render.hip): lane d gathers dword d of the wave's 32-pixel block and stores it
-DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32_t mine, int lane);
-// its 16-bit form: the lane's pixel in two registers (channel 0 | channel 1 << 16, channel 2), lane d stores dword d
-DEV void render_store_block16(uint16_t* rgb16, long px0, long npix, int nout, uint32_t mine0, uint32_t mine1, int lane);
-
 template <int WD, bool TRAIN, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
   static_assert(!(TRAIN && RENDER), "the render form spills nothing");
@@ -209,31 +204,19 @@ __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
   if constexpr (RENDER) {
     // no target, no residual, no dz, no Z store, no workgroup sum: the sigmoid of k_ff_fwd<WD, false>, then bytes (BITS = 8)
     // or 16-bit samples (BITS = 16)
-    uint32_t mine = 0u;   // this lane's pixel: channel t in byte t (the upper lane half holds padded rows: never selected)
-    uint32_t mine1 = 0u;  // BITS = 16: channels 0 and 1 in the halves of `mine`, channel 2 here
+    RenderPx<BITS> mine;   // this lane's pixel (the upper lane half holds padded rows: never selected)
     if (hh == 0) {
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         const float z = o[0][t];
         const float sg = 1.0f / (1.0f + __expf(-z));
         if (valid && a.pred) a.pred[p * 3 + t] = sg;
-        const uint32_t q = render_quant<BITS>(sg);
-        if constexpr (BITS == 16) {
-          if (t < 2) mine |= q << (16 * t); else mine1 = q;
-        } else {
-          mine |= q << (8 * t);
-        }
+        mine.put(t, sg);
       }
     }
-    // (all 64 lanes: the gather is a cross-lane read.)  pix0 is a multiple of 256 and the wave's first pixel one of 32:
-    // the 96-byte (192-byte) block starts on a dword; pixels >= npix store nothing
+    // (all 64 lanes: the gather is a cross-lane read.)  pix0 is a multiple of 256: the wave's first pixel is one of 32
     const long px0 = a.pix0 + (long)blockIdx.x * 256 + wave * 32;
-    if constexpr (BITS == 16) {
-      if (a.rgb16) render_store_block16(a.rgb16, px0, a.npix, 3, mine, mine1, lane);
-    } else {
-      (void)mine1;
-      if (a.rgb8) render_store_block(a.rgb8, px0, a.npix, 3, mine, lane);
-    }
+    if (a.rgb8) render_store<BITS, 32>(a.rgb8, px0, a.npix, 3, mine, lane);   // (a.rgb16: the same member)
   } else {
     __shared__ float sh_sse[kFfThreads / 64];
     float sse = 0.f;

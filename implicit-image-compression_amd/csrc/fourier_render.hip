@@ -8,10 +8,9 @@
 // bit-identical to sf_forward's on a FourierNet training handle (tests/test_gpu_fourier_render.py), and a window or a
 // band is bit-identical to that region of the full picture: pixel (r, c) sees rows[r], cols[c] whatever the grid.
 //
-// Bytes: u8 = min(max((int)(pred * 255.0f), 0), 255), fwd_render_out's formula; the pack / gather / store tail is
-// render_store_block (siren_render.hip): a wave owns 32 consecutive pixels = 96 consecutive bytes on a dword boundary,
-// lane d < 24 stores dword d, only the picture's last ragged dword goes out byte by byte.  sf_render16 runs the BITS = 16
-// form: u16 = min(max((int)(pred * 65535.0f), 0), 65535) through render_store_block16, lane d < 48 stores dword d.
+// Bytes: u8 = min(max((int)(pred * 255.0f), 0), 255), fwd_render_out's formula; sf_render16 runs the BITS = 16 form:
+// u16 = min(max((int)(pred * 65535.0f), 0), 65535).  How a wave packs, gathers and stores the samples of its 32 pixels: the
+// sample tail, beside render_store in siren_kernels.hip.
 //
 // A render handle (create_fourier(.., render = true), fourier_host.hip) holds the parameters, the weight images, encoding.B
 // and the two coordinate vectors: none of the [D-1][WD][chunk] activation / gradient planes, the slab, gradients, Adam
@@ -35,7 +34,7 @@ int render_fourier(sf_engine* h, void* out, int bits, float* pred) {
     FfArgs fa = ff_args_base(h, k.pix0);
     fa.pred = pred; fa.rgb8 = (uint8_t*)out;   // (a.rgb16 of the 16-bit form: the same member)
     Launch L(h, K_FF_RENDER, 2.0 * ((double)MS * WD + (double)(D - 2) * WD * WD + 32.0 * WD) * npx,
-             npx * ((pred ? 12.0 : 0.0) + (out ? 3.0 * (bits / 8) : 0.0)));
+             npx * 3.0 * render_sample_bytes(out, bits, pred));
     SF_TRY(launch_ff(h, fa, k.n_super, bits == 16 ? kFfRender16 : kFfRender));
   }
   return SF_OK;

@@ -18,6 +18,7 @@
 //   k_adam     Adam + mask (torch.optim.Adam op order), k_images: rebuild the 16-bit weight images.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "layout.h"
 
@@ -893,6 +894,74 @@ DEV uint32_t render_quant(float p) {
   int q = (int)(p * (float)kMax);
   q = q < 0 ? 0 : (q > kMax ? kMax : q);
   return (uint32_t)q;
+}
+// ---- the sample tail of every render kernel: quantise and pack, gather, store ----
+// (RenderPx: fwd_render_out, siren_render.hip - k_fwd, k_fwd_pipe, k_wgemm -, the RENDER branch of k_ff_fwd and k_wv_render;
+// render_store: the last two - fwd_render_out keeps the earlier 32-pixel functions beside it, which do the same)
+// A wave owns PX consecutive pixels (32: the MFMA kernels, whose upper lane half holds padded rows; 64: k_wv_render) from a
+// pixel index that PX divides, so its PX * nout samples start on a dword boundary of a 4-byte aligned output (the entry
+// points check the base).  Every lane packs its own pixel into registers (RenderPx), lane d gathers the samples of dword d
+// of the block from the lanes that hold them (ds_bpermute) and the wave stores whole dwords: 8 * nout (BITS = 8) or
+// 16 * nout (BITS = 16) of them at PX = 32, twice that at PX = 64 - where 16-bit RGB is 96 dwords, two rounds of a lane.
+// Only the output's last dword can be partial (a byte count that 4 does not divide, an odd count of 16-bit samples): its
+// samples go out singly, as bytes or one 2-byte store.  Nothing is written at or beyond sample npix * nout.
+
+// a lane's pixel as packed samples.  BITS = 8: channel c in byte c of v0; BITS = 16: channels 0 and 1 in the halves of v0,
+// channel 2 in v1
+template <int BITS>
+struct RenderPx {
+  static_assert(BITS == 8 || BITS == 16, "BITS: the sample width, 8 or 16");
+  uint32_t v0 = 0u, v1 = 0u;
+  DEV void put(int c, float p) {
+    const uint32_t q = render_quant<BITS>(p);
+    if constexpr (BITS == 16) {
+      if (c < 2) v0 |= q << (16 * c); else v1 = q;
+    } else {
+      v0 |= q << (8 * c);
+    }
+  }
+};
+// sample k (= pixel k / nout, channel k % nout) of a wave's block of PX pixels, from the lane that holds the pixel.  A
+// cross-lane read: called by all 64 lanes (k beyond the block reads some lane's value, which nobody stores)
+template <int BITS, int PX>
+DEV uint32_t render_sample(const RenderPx<BITS>& px, int k, int nout) {
+  const int src = nout == 3 ? k / 3 : (nout == 2 ? k >> 1 : k);
+  const int ch = k - src * nout;
+  const uint32_t lo = (uint32_t)__shfl((int)px.v0, src & (PX - 1));
+  if constexpr (BITS == 16) {
+    const uint32_t hi = (uint32_t)__shfl((int)px.v1, src & (PX - 1));
+    return ch == 2 ? hi : (lo >> (16 * ch)) & 0xffffu;
+  } else {
+    return (lo >> (8 * ch)) & 0xffu;
+  }
+}
+// Stores the wave's block: PX pixels from pixel px0 (PX | px0) of an output of npix pixels x nout samples of BITS bits at
+// `out` (4-byte aligned).  px: this lane's pixel (lanes 0 .. PX - 1).  Called by all 64 lanes
+template <int BITS, int PX>
+DEV void render_store(void* out, long px0, long npix, int nout, const RenderPx<BITS>& px, int lane) {
+  static_assert(PX == 32 || PX == 64, "PX: the pixels a wave owns");
+  using T = std::conditional_t<BITS == 16, uint16_t, uint8_t>;
+  constexpr int SPD = 32 / BITS;                                // samples per dword
+  const long left = npix - px0;
+  const int nsamp = left >= PX ? PX * nout : (left > 0 ? (int)left * nout : 0);   // samples of the block inside the output
+  const int ndw = PX * nout / SPD;                              // dwords of a whole block (PX * nout: a multiple of SPD)
+  T* blk = static_cast<T*>(out) + px0 * nout;
+#pragma unroll
+  for (int round = 0; round < (PX * 3 / SPD + 63) / 64; ++round) {   // (nout <= 3: two rounds at PX = 64, BITS = 16 only)
+    const int d = 64 * round + lane;
+    uint32_t word = 0u;
+#pragma unroll
+    for (int j = 0; j < SPD; ++j) word |= render_sample<BITS, PX>(px, SPD * d + j, nout) << (BITS * j);
+    if (d < ndw) {                                              // (only the store sits behind the lane guard)
+      if (SPD * d + SPD <= nsamp) {
+        reinterpret_cast<uint32_t*>(blk)[d] = word;
+      } else {
+#pragma unroll
+        for (int j = 0; j < SPD - 1; ++j)                       // a partial dword never holds its last sample
+          if (SPD * d + j < nsamp) blk[SPD * d + j] = (T)(word >> (BITS * j));
+      }
+    }
+  }
 }
 // The dynamic LDS of a workgroup is 160 KiB at most; every kernel family states its layout ONCE, in a geometry struct
 // (byte offsets for the kernel, `bytes` for its launcher) that checks itself against this.

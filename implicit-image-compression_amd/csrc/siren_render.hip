@@ -8,61 +8,23 @@
 // same MFMA chain, the same v_sin_f32 - so sf_render's pred is bit-identical to sf_forward's (tests/test_gpu_render.py).
 //
 // Bytes: u8 = min(max((int)(pred * 255.0f), 0), 255), the product in fp32 and truncated toward zero - the reference's
-// (pred * 255).int() (implicit_image/utils/train_helper.py:52, eval_epoch), clamped to what a file can hold.  A wave owns
-// 32 consecutive pixels = 32 * out_features consecutive bytes, which start on a dword boundary (32 divides the pixel
-// index): every lane packs its own pixel's bytes into one register, lane d gathers dword d of the block with four
-// ds_bpermute and stores it, so a wave writes 8 * out_features whole dwords (24 for RGB) in one store instruction.  Only the
-// picture's last, ragged dword is written byte by byte.
-//
-// 16-bit samples (sf_render16, BITS = 16): u16 = min(max((int)(pred * 65535.0f), 0), 65535), the same statement one sample
-// width up - it inverts the loader's raw / (2^16 - 1).  The 32 pixels of a wave are 32 * out_features uint16_t =
-// 16 * out_features whole dwords (48 for RGB), again from a dword boundary: a lane holds its pixel in two registers
-// (channel 0 | channel 1 << 16, channel 2), lane d < 16 * out_features gathers the two samples of dword d with four
-// ds_bpermute and the wave stores them in one store instruction (render_store_block16).  Only a picture with an odd sample
-// count has a ragged last dword: its low half goes out as one 2-byte store.
+// (pred * 255).int() (implicit_image/utils/train_helper.py:52, eval_epoch), clamped to what a file can hold.  16-bit samples
+// (sf_render16, BITS = 16): u16 = min(max((int)(pred * 65535.0f), 0), 65535), the same statement one sample width up - it
+// inverts the loader's raw / (2^16 - 1).  How a wave packs, gathers and stores the samples of its 32 pixels: the sample
+// tail, beside render_store in siren_kernels.hip.
 //
 // This file is included at the end of siren_fit.hip (one translation unit, as every kernel file of the library); the host
 // part builds on siren_host.hip (create_handle, fwd_args_base, the forward geometry).
 
 namespace sf {
 
-template <int BITS>
-DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, bool valid, int lane, int h) {
-  const int nout = a.nout;
-  uint32_t mine = 0u;   // this lane's pixel: channel c in byte c (lanes of the upper half hold padded rows: never selected)
-  uint32_t mine1 = 0u;  // BITS = 16: channels 0 and 1 in the halves of `mine`, channel 2 here
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if (c >= nout) break;
-    // exactly fwd_residual's prediction
-    float o = acc[c] * a.sc_last;
-    if (a.last_om_rev != 0.f) {
-      const float tt = o * a.last_om_rev;
-      o = __builtin_amdgcn_sinf(tt);
-    }
-    const float p = o * 0.5f + 0.5f;  // siren.py:131
-    if (a.pred && h == 0 && valid) a.pred[pix * nout + c] = p;
-    const uint32_t q = render_quant<BITS>(p);
-    if constexpr (BITS == 16) {
-      if (c < 2) mine |= q << (16 * c); else mine1 = q;
-    } else {
-      mine |= q << (8 * c);
-    }
-  }
-  if constexpr (BITS == 16) {
-    if (!a.rgb16) return;
-    render_store_block16(a.rgb16, a.pix0 + pb * 32, a.npix, nout, mine, mine1, lane);
-  } else {
-    (void)mine1;
-    if (!a.rgb8) return;
-    render_store_block(a.rgb8, a.pix0 + pb * 32, a.npix, nout, mine, lane);   // the block's first pixel: a multiple of 32
-  }
-}
-
-// The byte tail every 32-pixel-per-wave render kernel shares (k_fwd / k_fwd_pipe above, k_ff_fwd's RENDER form in
-// fourier_kernels.hip).  mine: the lane's pixel of the block starting at pixel px0, channel c in byte c (lanes 0..31; the
-// upper half is never selected).  Called by all 64 lanes; rgb8 + px0 * nout is dword aligned (the entry point checks the
-// base, 32 | px0).
+// The 32-pixel stores of fwd_render_out below (k_fwd, k_fwd_pipe, k_wgemm): what render_store<BITS, 32> (siren_kernels.hip,
+// where the tail is explained) does, as it was written before that template.  This one call site keeps them: with the
+// template here a Feathermap decode leg measured above the parent's spread twice, so the device
+// code of these kernels is byte for byte the parent's.
+// The byte form.  mine: the lane's pixel of the block starting at pixel px0, channel c in byte c (lanes 0..31; the upper half
+// is never selected).  Called by all 64 lanes; rgb8 + px0 * nout is dword aligned (the entry point checks the base,
+// 32 | px0).
 DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32_t mine, int lane) {
   const long left = npix - px0;
   const int nbytes = left >= 32 ? 32 * nout : (left > 0 ? (int)left * nout : 0);   // bytes of the block inside the picture
@@ -88,8 +50,8 @@ DEV void render_store_block(uint8_t* rgb8, long px0, long npix, int nout, uint32
 }
 
 // Sample k (= pixel k / nout, channel k % nout) of a wave's block of 16-bit samples, gathered from the lane that holds the
-// pixel: v0 = channel 0 | channel 1 << 16, v1 = channel 2.  lanes: 32 (the 32-pixel forms) or 64 (k_wv_render); called by
-// all 64 lanes, two ds_bpermute.
+// pixel: v0 = channel 0 | channel 1 << 16, v1 = channel 2.  lanes: the pixels of the block (32); called by all 64 lanes, two
+// ds_bpermute.
 DEV uint32_t render_sample16(uint32_t v0, uint32_t v1, int k, int nout, int lanes) {
   const int src = nout == 3 ? k / 3 : (nout == 2 ? k >> 1 : k);
   const int ch = k - src * nout;
@@ -113,6 +75,29 @@ DEV void render_store_block16(uint16_t* rgb16, long px0, long npix, int nout, ui
   const uint32_t s0 = render_sample16(mine0, mine1, 2 * lane, nout, 32);        // (lanes >= 16 * nout gather nothing they store)
   const uint32_t s1 = render_sample16(mine0, mine1, 2 * lane + 1, nout, 32);
   if (lane < 16 * nout) render_store_dword16(rgb16 + px0 * nout, lane, nsamp, s0 | (s1 << 16));
+}
+
+template <int BITS>
+DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, bool valid, int lane, int h) {
+  const int nout = a.nout;
+  RenderPx<BITS> mine;   // this lane's pixel (lanes of the upper half hold padded rows: never selected)
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (c >= nout) break;
+    // exactly fwd_residual's prediction
+    float o = acc[c] * a.sc_last;
+    if (a.last_om_rev != 0.f) {
+      const float tt = o * a.last_om_rev;
+      o = __builtin_amdgcn_sinf(tt);
+    }
+    const float p = o * 0.5f + 0.5f;  // siren.py:131
+    if (a.pred && h == 0 && valid) a.pred[pix * nout + c] = p;
+    mine.put(c, p);
+  }
+  if (!a.rgb8) return;   // (a.rgb16: the same member)
+  const long px0 = a.pix0 + pb * 32;   // the block's first pixel: a multiple of 32
+  if constexpr (BITS == 16) render_store_block16(a.rgb16, px0, a.npix, nout, mine.v0, mine.v1, lane);
+  else render_store_block(a.rgb8, px0, a.npix, nout, mine.v0, lane);
 }
 
 }  // namespace sf
@@ -147,8 +132,8 @@ int render_chunks(sf_engine* h, void* out, int bits, float* pred, const PixelVie
     FwdArgs fa = fwd_args_base(h, v, k.pix0, n_super);
     fa.pred = pred;
     fa.rgb8 = (uint8_t*)out;   // (a.rgb16 of the 16-bit forms: the same member)
-    const double out_bytes = (pred ? 4.0 : 0.0) + (out ? bits / 8.0 : 0.0);
-    Launch L(h, K_RENDER, flops_fwd_px(h) * n_super * (double)kSuper, n_super * (double)kSuper * h->cfg.out_features * out_bytes);
+    Launch L(h, K_RENDER, flops_fwd_px(h) * n_super * (double)kSuper,
+             n_super * (double)kSuper * h->cfg.out_features * render_sample_bytes(out, bits, pred));
     SF_TRY(launch_render(h, fa, fwd_grid(h, n_super), bits));
   }
   return SF_OK;
@@ -157,49 +142,38 @@ int render_chunks(sf_engine* h, void* out, int bits, float* pred, const PixelVie
 // fourier_render.hip, included last: the RENDER form of k_ff_fwd (out: bits / 8 bytes per sample)
 int render_fourier(sf_engine* h, void* out, int bits, float* pred);
 
-// sf_render (bits = 8) and sf_render16 (bits = 16): one set of argument checks
-int render_any(sf_handle* h, void* out, int bits, float* pred) {
-  const std::string fn = bits == 16 ? "sf_render16" : "sf_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
+// sf_render / sf_render16 (wide = false) and sf_wide_render / sf_wide_render16 (wide = true) at bits = 8 / 16: one set of
+// argument checks.  The entry points differ in the handles they refuse - the wide ones draw the one kind of handle that
+// sf_wide_render_create makes and send any other to the entry point that draws it - and in the draw
+int render_any(sf_handle* h, void* out, int bits, float* pred, bool wide) {
+  const std::string fn = std::string(wide ? "sf_wide_render" : "sf_render") + (bits == 16 ? "16" : "");
+  const std::string on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
   if (!h) return fail(SF_ERR_INVALID, "null argument");
   if (!out && !pred) return fail(SF_ERR_INVALID, fn + ": " + on + " and pred_dev are both NULL");
-  if (h->model == Model::Wavelet && h->render)
-    return fail(SF_ERR_INVALID, fn + ": a WaveletSiren render handle (sf_wavelet_render_create) is drawn by sf_wavelet_render" +
-                                    (bits == 16 ? "16" : ""));
-  if (h->wide || h->model == Model::Wavelet)
-    return fail(SF_ERR_INVALID, fn + ": built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create) "
-                                     "and FourierNet handles (sf_fourier_create / sf_fourier_render_create)");
+  if (wide) {
+    if (!(h->model == Model::Siren && h->wide && h->render)) {
+      const char* use = h->model == Model::Wavelet ? "sf_wavelet_render draws a WaveletSiren handle"
+                        : h->model == Model::Fourier ? "sf_render draws a FourierNet handle"
+                        : h->wide ? "a training handle of hidden 512 / 1024 (sf_create) evaluates through sf_forward"
+                                  : "sf_render draws a SIREN handle of hidden width 32 .. 256";
+      return fail(SF_ERR_INVALID, fn + ": built for the wide render handle of sf_wide_render_create (hidden 512 / 1024); " + use);
+    }
+  } else {
+    if (h->model == Model::Wavelet && h->render)
+      return fail(SF_ERR_INVALID, fn + ": a WaveletSiren render handle (sf_wavelet_render_create) is drawn by sf_wavelet_render" +
+                                      (bits == 16 ? "16" : ""));
+    if (h->wide || h->model == Model::Wavelet)
+      return fail(SF_ERR_INVALID, fn + ": built for SIREN handles of hidden width 32 .. 256 (sf_create / sf_render_create) "
+                                       "and FourierNet handles (sf_fourier_create / sf_fourier_render_create)");
+  }
   if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
-  if (h->render && h->fth.attached && !h->fth.loaded)
+  if (h->render && h->fth.attached && !h->fth.loaded)   // (never a wide handle: sf_feather_render_attach refuses it)
     return fail(SF_ERR_STATE, fn + ": sf_feather_render_load has not been called (the handle has a feather state and no weights yet)");
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
-  switch (h->model) {
-    case Model::Siren: break;
-    case Model::Fourier: return render_fourier(h, out, bits, pred);
-    case Model::Wavelet: __builtin_unreachable();   // refused above
-  }
+  if (h->model == Model::Fourier) return render_fourier(h, out, bits, pred);   // (wide = false: refused above otherwise)
   DevGuard dev_guard(h->cfg.device);
   SF_TRY(refresh_images(h));
-  return render_chunks(h, out, bits, pred);
-}
-
-// sf_wide_render (bits = 8) and sf_wide_render16 (bits = 16): render_any's argument checks for the one kind of handle that
-// sf_wide_render_create makes; any other handle is sent to the entry point that draws it
-int wide_render_any(sf_handle* h, void* out, int bits, float* pred) {
-  const std::string fn = bits == 16 ? "sf_wide_render16" : "sf_wide_render", on = bits == 16 ? "rgb16_dev" : "rgb8_dev";
-  if (!h) return fail(SF_ERR_INVALID, "null argument");
-  if (!out && !pred) return fail(SF_ERR_INVALID, fn + ": " + on + " and pred_dev are both NULL");
-  if (!(h->model == Model::Siren && h->wide && h->render)) {
-    const char* use = h->model == Model::Wavelet ? "sf_wavelet_render draws a WaveletSiren handle"
-                      : h->model == Model::Fourier ? "sf_render draws a FourierNet handle"
-                      : h->wide ? "a training handle of hidden 512 / 1024 (sf_create) evaluates through sf_forward"
-                                : "sf_render draws a SIREN handle of hidden width 32 .. 256";
-    return fail(SF_ERR_INVALID, fn + ": built for the wide render handle of sf_wide_render_create (hidden 512 / 1024); " + use);
-  }
-  if (((uintptr_t)out & 3u) != 0) return fail(SF_ERR_INVALID, fn + ": " + on + " must be 4-byte aligned");
-  if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
-  DevGuard dev_guard(h->cfg.device);
-  SF_TRY(refresh_images(h));
-  return wide_render_chunks(h, out, bits, pred);
+  return wide ? wide_render_chunks(h, out, bits, pred) : render_chunks(h, out, bits, pred);
 }
 
 }  // namespace
@@ -208,8 +182,8 @@ extern "C" {
 
 int sf_render_create(const sf_config* cfg, sf_handle** out) try { return create_handle(cfg, out, true); } SF_CATCH
 
-int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try { return render_any(h, rgb8, 8, pred); } SF_CATCH
-int sf_render16(sf_handle* h, uint16_t* rgb16, float* pred) try { return render_any(h, rgb16, 16, pred); } SF_CATCH
+int sf_render(sf_handle* h, uint8_t* rgb8, float* pred) try { return render_any(h, rgb8, 8, pred, false); } SF_CATCH
+int sf_render16(sf_handle* h, uint16_t* rgb16, float* pred) try { return render_any(h, rgb16, 16, pred, false); } SF_CATCH
 
 int sf_wide_render_create(const sf_config* cfg, sf_handle** out) try {
   if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
@@ -219,7 +193,7 @@ int sf_wide_render_create(const sf_config* cfg, sf_handle** out) try {
                                 "sf_render_create makes the render handle of hidden 32 .. 256");
   return create_handle(cfg, out, true, false, true);
 } SF_CATCH
-int sf_wide_render(sf_handle* h, uint8_t* rgb8, float* pred) try { return wide_render_any(h, rgb8, 8, pred); } SF_CATCH
-int sf_wide_render16(sf_handle* h, uint16_t* rgb16, float* pred) try { return wide_render_any(h, rgb16, 16, pred); } SF_CATCH
+int sf_wide_render(sf_handle* h, uint8_t* rgb8, float* pred) try { return render_any(h, rgb8, 8, pred, true); } SF_CATCH
+int sf_wide_render16(sf_handle* h, uint16_t* rgb16, float* pred) try { return render_any(h, rgb16, 16, pred, true); } SF_CATCH
 
 }  // extern "C"

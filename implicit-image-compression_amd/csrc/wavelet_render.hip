@@ -12,17 +12,10 @@
 //      sf_forward writes on a WaveletSiren training handle, and a window is bit-identical to that region of the full
 //      picture: coefficient (i, j) sees rows[i], cols[j] whatever the window (tests/test_gpu_wavelet_render.py).
 //
-// Bytes: u8 = min(max((int)(v * 255.0f), 0), 255), the product in fp32 and truncated toward zero (fwd_render_out,
-// decode.to_u8).  A wave owns 64 consecutive pixels of the dense rows x cols output = 192 consecutive bytes, which start on
-// a dword boundary (64 divides the wave's first pixel index): every lane packs its own pixel's three bytes into one
-// register, lane d < 48 gathers dword d from three neighbours with four ds_bpermute, and the wave stores 48 whole dwords in
-// one store instruction.  Only the output's last, ragged dword is written byte by byte.
-//
-// 16-bit samples (sf_wavelet_render16, k_wv_render<16>): u16 = min(max((int)(v * 65535.0f), 0), 65535).  The wave's 64
-// pixels are 192 uint16_t = 96 whole dwords from a dword boundary: a lane holds its pixel in two registers (channel 0 |
-// channel 1 << 16, channel 2), gathers dword `lane` and, below lane 32, dword 64 + `lane` (render_sample16,
-// siren_render.hip) and the wave stores them in two store instructions.  Only an output with an odd sample count has a
-// ragged last dword: its low half goes out as one 2-byte store.
+// Bytes: u8 = min(max((int)(v * 255.0f), 0), 255), the product in fp32 and truncated toward zero (render_quant,
+// decode.to_u8); 16-bit samples (sf_wavelet_render16, k_wv_render<16>): u16 = min(max((int)(v * 65535.0f), 0), 65535).  A wave
+// owns 64 consecutive pixels of the dense rows x cols output; how it packs, gathers and stores their samples: the sample
+// tail, beside render_store in siren_kernels.hip.
 //
 // This file is included at the end of siren_fit.hip, after siren_render.hip (one translation unit); the creator builds on
 // wavelet_host.hip.
@@ -50,61 +43,18 @@ __global__ __launch_bounds__(kWvThreads) void k_wv_render(WvRenderArgs a) {
   static_assert(BITS == 8 || BITS == 16, "BITS: the sample width, 8 or 16");
   const long p = (long)blockIdx.x * kWvThreads + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  uint32_t mine = 0u;   // this lane's pixel: channel k in byte k
-  uint32_t mine1 = 0u;  // BITS = 16: channels 0 and 1 in the halves of `mine`, channel 2 here
+  RenderPx<BITS> mine;   // this lane's pixel
   if (p < a.npx) {
     const int pr = (int)(p / a.cols);
     const int r = a.row0 + pr, c = a.col0 + (int)(p - (long)pr * a.cols);
     // (no target: no fetch, no residual; pred, when asked for, is the plain 12-byte store of k_wv_compose)
     const WvPixel px = wv_compose_pixel(a.lf, a.hf, nullptr, a.pred, nullptr, 0.f, p, r, c, a.n, a.up, a.i0, a.j0, a.cc);
-    const float (&rgb)[3] = px.rgb;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const uint32_t q = render_quant<BITS>(rgb[k]);
-      if constexpr (BITS == 16) {
-        if (k < 2) mine |= q << (16 * k); else mine1 = q;
-      } else {
-        mine |= q << (8 * k);
-      }
-    }
+    for (int k = 0; k < 3; ++k) mine.put(k, px.rgb[k]);
   }
   if (!a.rgb8) return;   // (uniform; a.rgb16 is the same member)
-  if constexpr (BITS == 16) {
-    const long p0 = p - lane;               // first pixel of this wave: a multiple of 64
-    const long left = a.npx - p0;
-    const int nsamp = left >= 64 ? 192 : (left > 0 ? (int)left * 3 : 0);   // samples of the wave inside the output
-    uint16_t* blk = a.rgb16 + p0 * 3;       // dword aligned: sf_wavelet_render16 checks the base, 64 | p0
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {  // dwords lane and 64 + lane (all 64 lanes gather: a cross-lane read)
-      const int d = 64 * half + lane;
-      const uint32_t s0 = render_sample16(mine, mine1, 2 * d, 3, 64);   // (d >= 96 gathers nothing it stores)
-      const uint32_t s1 = render_sample16(mine, mine1, 2 * d + 1, 3, 64);
-      if (d < 96) render_store_dword16(blk, d, nsamp, s0 | (s1 << 16));
-    }
-    return;
-  }
-  (void)mine1;
-  uint32_t word = 0u;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int k = 4 * lane + j;           // byte k of the wave's 192 = pixel k / 3, channel k % 3
-    const int src = k / 3, ch = k - src * 3;
-    const uint32_t v = (uint32_t)__shfl((int)mine, src & 63);   // (lanes >= 48 gather nothing they store)
-    word |= ((v >> (8 * ch)) & 0xffu) << (8 * j);
-  }
-  const long p0 = p - lane;               // first pixel of this wave: a multiple of 64
-  const long left = a.npx - p0;
-  const int nbytes = left >= 64 ? 192 : (left > 0 ? (int)left * 3 : 0);   // bytes of the wave inside the output
-  if (lane < 48) {
-    uint8_t* blk = a.rgb8 + p0 * 3;       // dword aligned: sf_wavelet_render checks the base, 64 | p0
-    if (4 * lane + 4 <= nbytes) {
-      reinterpret_cast<uint32_t*>(blk)[lane] = word;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (4 * lane + j < nbytes) blk[4 * lane + j] = (uint8_t)(word >> (8 * j));
-    }
-  }
+  // (all 64 lanes: the gather is a cross-lane read.)  The wave's first pixel is a multiple of 64
+  render_store<BITS, 64>(a.rgb8, p - lane, a.npx, 3, mine, lane);
 }
 
 }  // namespace sf
@@ -205,7 +155,7 @@ int wavelet_render_any(sf_handle* h, int32_t row0, int32_t row1, int32_t col0, i
   a.i0 = i0; a.j0 = j0; a.cc = cc;
   a.lf = p_sub[0]; a.hf = p_sub[1];
   a.pred = pred; a.rgb8 = (uint8_t*)out;   // (a.rgb16 of k_wv_render<16>: the same member)
-  Launch L(h, K_WV_RENDER, 0, (double)a.npx * ((pred ? 12.0 : 0.0) + (out ? 3.0 * (bits / 8) : 0.0)) + (double)nn * 24.0);
+  Launch L(h, K_WV_RENDER, 0, (double)a.npx * 3.0 * render_sample_bytes(out, bits, pred) + (double)nn * 24.0);
   const long n_wg = (a.npx + kWvThreads - 1) / kWvThreads;
   return bits == 16 ? launch(h, k_wv_render<16>, n_wg, kWvThreads, 0, a) : launch(h, k_wv_render<8>, n_wg, kWvThreads, 0, a);
 }

@@ -83,91 +83,81 @@ int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob, int re
   }
 }
 
-// The forward of chunk c, layer at a time (k_wlayer0, k_wgemm2<0> per hidden layer, k_wgemm), training or evaluation form: the
-// prediction to pred (or null), the chunk's SSE partials to sse_part; n_part: how many it wrote (one per 256-pixel group)
-int wide_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
+// What the last layer of a wide forward walk writes: the prediction (or null) and either the training / evaluation outputs -
+// the chunk's SSE partials and, if train, dL/dout - or samples of `bits` bits at `samples` (or null)
+struct WideOut { float* pred; float* sse_part; bool train; void* samples; int bits; };
+
+// The forward walk of chunk k, layer at a time: k_wlayer0, k_wgemm2<0> per hidden layer, k_wgemm.  o.bits = 0: the training /
+// evaluation forms under K_FWD - layer l writes its own phase and activation planes.  o.bits = 8 / 16: the RENDER forms
+// under K_RENDER - activations only, through the handle's two planes in turn (layer l reads plane (l - 1) & 1 and writes
+// plane l & 1)
+int wide_fwd_walk(sf_engine* h, const Chunk& k, const WideOut& o) {
   const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
-  const float sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
-  const float sc_hidden = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
+  const bool render = o.bits != 0;
+  const int id = render ? K_RENDER : K_FWD;
+  const double phase_bytes = render ? 0.0 : (h->s8 ? 1.0 : 2.0);   // charged per phase value; a RENDER form stores none
   const size_t blk_pieces = (size_t)(KS / 4) * 32;   // pieces of one [256 x WD] block of a hidden image
-  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
   const int n_super = k.n_super;
-  const long n_pb = k.n_pb;
-  const double npx = n_pb * 32.0;
+  const double npx = k.n_pb * 32.0;
+  auto act = [&](int l) { return h->Abuf + (size_t)(render ? l & 1 : l) * h->a_stride; };
   {
     WL0Args a = zeroed<WL0Args>();
     a.gh = h->gh; a.gw = h->gw; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin; a.pix0 = k.pix0; a.npix = h->npix;
-    a.l0tab = h->l0tab; a.sc_first = sc_first; a.KS = KS; a.n_pieces = n_pb * KS; a.P = h->Pbuf; a.Act = h->Abuf;
-    Launch L(h, K_FWD, 4.0 * WD * npx, npx * (WD * (h->s8 ? 3.0 : 4.0)));
-    if (h->s8) SF_TRY(launch(h, k_wlayer0<OpF16, true>, (a.n_pieces / 2 + 3) / 4, 256, 0, a));
-    else SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op)>, (a.n_pieces + 3) / 4, 256, 0, a); }));
+    a.l0tab = h->l0tab; a.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi); a.KS = KS; a.n_pieces = k.n_pb * KS;
+    if (!render) a.P = h->Pbuf;
+    a.Act = act(0);
+    Launch L(h, id, 4.0 * WD * npx, npx * (WD * (2.0 + phase_bytes)));
+    const long n_wg = (a.n_pieces + 3) / 4;
+    if (render) SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op), false, true>, n_wg, 256, 0, a); }));
+    else if (h->s8) SF_TRY(launch(h, k_wlayer0<OpF16, true>, (a.n_pieces / 2 + 3) / 4, 256, 0, a));
+    else SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op)>, n_wg, 256, 0, a); }));
   }
   for (int l = 1; l <= D - 2; ++l) {
     WGemmArgs a = zeroed<WGemmArgs>();
     a.A = reinterpret_cast<const u32x4*>(h->wf + (size_t)(l - 1) * WD * WD);
     a.a_block_pieces = (long)blk_pieces; a.n_chunk = KS / 4;
-    a.Bin = h->Abuf + (size_t)(l - 1) * h->a_stride; a.ks_in = KS;
-    a.bias = h->biasw + (size_t)(l - 1) * WD; a.sc = sc_hidden;
-    a.Out = h->Pbuf + (size_t)l * h->p_stride; a.OutAct = h->Abuf + (size_t)l * h->a_stride; a.ks_out = KS; a.kp_out = WD / 32;
-    Launch L(h, K_FWD, 2.0 * WD * WD * npx, npx * (WD * ((h->s8 ? 3.0 : 4.0) + 2.0 * NBLK)));
-    SF_TRY(launch_wgemm<0>(h, a, n_super, NBLK));
+    a.Bin = act(l - 1); a.ks_in = KS;
+    a.bias = h->biasw + (size_t)(l - 1) * WD;
+    if (!render) {
+      a.sc = (float)((double)h->cfg.hidden_omega_0 / kTwoPi / (double)h->wscale);
+      a.Out = h->Pbuf + (size_t)l * h->p_stride;
+    }
+    a.OutAct = act(l); a.ks_out = KS; a.kp_out = WD / 32;
+    Launch L(h, id, 2.0 * WD * WD * npx, npx * (WD * (2.0 + phase_bytes + 2.0 * NBLK)));
+    SF_TRY(launch_wgemm<0>(h, a, n_super, NBLK, o.bits));
   }
-  {
-    WGemmArgs a = zeroed<WGemmArgs>();
-    a.A = reinterpret_cast<const u32x4*>(h->wf_last);
-    a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
-    a.Bin = h->Abuf + (size_t)(D - 2) * h->a_stride; a.ks_in = KS;
-    a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
-    a.img = h->img; a.pred = pred; a.nout = h->cfg.out_features;
-    a.gscale = gscale(h);
-    a.sse_part = sse_part; a.Dlast = train ? h->Dlast : nullptr; a.pix0 = k.pix0; a.npix = h->npix;
-    if (!h->cfg.outermost_linear) { a.last_om = h->cfg.hidden_omega_0; a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi); }
-    n_part = n_super;
-    Launch L(h, K_FWD, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + 12.0 + 64.0));
-    SF_TRY(launch_wgemm<1>(h, a, n_super, 1));
+  WGemmArgs a = zeroed<WGemmArgs>();
+  a.A = reinterpret_cast<const u32x4*>(h->wf_last);
+  a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
+  a.Bin = act(D - 2); a.ks_in = KS;
+  a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
+  a.pred = o.pred; a.nout = h->cfg.out_features; a.pix0 = k.pix0; a.npix = h->npix;
+  if (!h->cfg.outermost_linear) a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
+  if (render) {
+    a.rgb8 = (uint8_t*)o.samples;   // (a.rgb16 of the 16-bit form: the same member)
+  } else {
+    a.img = h->img; a.gscale = gscale(h);
+    a.sse_part = o.sse_part; a.Dlast = o.train ? h->Dlast : nullptr;
+    if (!h->cfg.outermost_linear) a.last_om = h->cfg.hidden_omega_0;
   }
-  return SF_OK;
+  const double out_bytes = render ? h->cfg.out_features * render_sample_bytes(o.samples, o.bits, o.pred) : 12.0 + 64.0;
+  Launch L(h, id, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + out_bytes));
+  return launch_wgemm<1>(h, a, n_super, 1, o.bits);
 }
 
-// The render loop of a wide render handle (sf_wide_render_create; its images are current): per chunk k_wlayer0, D - 2 hidden
-// products and the last layer, all in their RENDER forms - activations only, through the handle's two planes in turn (layer l
-// reads plane (l - 1) & 1 and writes plane l & 1), then pred and / or samples of `bits` bits at out (either may be null)
+// The forward of chunk c, training or evaluation form: the prediction to pred (or null), the chunk's SSE partials to sse_part;
+// n_part: how many it wrote (one per 256-pixel group)
+int wide_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  n_part = k.n_super;
+  return wide_fwd_walk(h, k, {pred, sse_part, train, nullptr, 0});
+}
+
+// The render loop of a wide render handle (sf_wide_render_create; its images are current): every chunk's RENDER walk, to pred
+// and / or to samples of `bits` bits at out (either may be null)
 int wide_render_chunks(sf_engine* h, void* out, int bits, float* pred) {
-  const int WD = h->WD, D = h->D, KS = WD / 16, NBLK = WD / 256;
-  const size_t blk_pieces = (size_t)(KS / 4) * 32;
-  auto plane = [&](int l) { return h->Abuf + (size_t)(l & 1) * h->a_stride; };
-  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
-    const Chunk k = chunk_at(c, h->npix, h->chunk_px);
-    const double npx = k.n_pb * 32.0;
-    {
-      WL0Args a = zeroed<WL0Args>();
-      a.gh = h->gh; a.gw = h->gw; a.W = h->cfg.width; a.row_begin = h->cfg.row_begin; a.pix0 = k.pix0; a.npix = h->npix;
-      a.l0tab = h->l0tab; a.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi); a.KS = KS; a.n_pieces = k.n_pb * KS;
-      a.Act = plane(0);
-      Launch L(h, K_RENDER, 4.0 * WD * npx, npx * WD * 2.0);
-      SF_TRY(with_op(h, [&](auto op) { return launch(h, k_wlayer0<decltype(op), false, true>, (a.n_pieces + 3) / 4, 256, 0, a); }));
-    }
-    for (int l = 1; l <= D - 2; ++l) {
-      WGemmArgs a = zeroed<WGemmArgs>();
-      a.A = reinterpret_cast<const u32x4*>(h->wf + (size_t)(l - 1) * WD * WD);
-      a.a_block_pieces = (long)blk_pieces; a.n_chunk = KS / 4;
-      a.Bin = plane(l - 1); a.ks_in = KS;
-      a.bias = h->biasw + (size_t)(l - 1) * WD;
-      a.OutAct = plane(l); a.ks_out = KS; a.kp_out = WD / 32;
-      Launch L(h, K_RENDER, 2.0 * WD * WD * npx, npx * (WD * (2.0 + 2.0 * NBLK)));
-      SF_TRY(launch_wgemm<0>(h, a, k.n_super, NBLK, bits));
-    }
-    WGemmArgs a = zeroed<WGemmArgs>();
-    a.A = reinterpret_cast<const u32x4*>(h->wf_last);
-    a.a_block_pieces = (long)KS; a.n_chunk = KS / 4;
-    a.Bin = plane(D - 2); a.ks_in = KS;
-    a.bias = h->biasw + (size_t)(D - 2) * WD; a.sc = 1.0f / h->wscale;
-    a.pred = pred; a.rgb8 = (uint8_t*)out; a.nout = h->cfg.out_features; a.pix0 = k.pix0; a.npix = h->npix;
-    if (!h->cfg.outermost_linear) a.last_om_rev = (float)((double)h->cfg.hidden_omega_0 / kTwoPi);
-    const double out_bytes = (pred ? 4.0 : 0.0) + (out ? bits / 8.0 : 0.0);
-    Launch L(h, K_RENDER, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + h->cfg.out_features * out_bytes));
-    SF_TRY(launch_wgemm<1>(h, a, k.n_super, 1, bits));
-  }
+  for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c)
+    SF_TRY(wide_fwd_walk(h, chunk_at(c, h->npix, h->chunk_px), {pred, nullptr, false, out, bits}));
   return SF_OK;
 }
 

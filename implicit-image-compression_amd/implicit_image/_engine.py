@@ -288,8 +288,10 @@ class SirenEngine:
     """One per-image fit on one HIP stream (one sf_handle)."""
 
     STATE = {"params": 0, "grads": 1, "exp_avg": 2, "exp_avg_sq": 3, "masks": 4}
-    # the create entry point of this class and, when it belongs to an optional group, what _require says without it
+    # the create entry point of this class and, when it belongs to an optional group, what _require says without it; the
+    # entry point render() draws with
     _CREATE, _CREATE_NEEDS = "sf_create", None
+    _RENDER = "sf_render"
 
     def __init__(self, height: int, width: int, hidden: int, depth: int, first_omega_0: float = 50.0,
                  hidden_omega_0: float = 30.0, outermost_linear: bool = True, out_features: int = 3,
@@ -346,16 +348,20 @@ class SirenEngine:
             self._views[key] = torch.as_tensor(_DevView(p.value, cnt.value, typestr), device=self.device)
         return self._views[key]
 
-    def render(self, want_u8: bool = True, want_pred: bool = False, bits: int = 8):
-        """sf_render on this handle's rows, no host sync: (rgb8 [rows, W, C] uint8 or None, pred [rows, W, C] fp32 or None).
-        u8 = min(max((int)(pred * 255), 0), 255); pred is bit-identical to forward()'s.  bits=16: sf_render16, the samples
-        are uint16, min(max((int)(pred * 65535), 0), 65535)."""
-        _require(self.lib, has_render, "sf_render entry point", "the render path")
-        fn = _render_entry(self.lib, "sf_render", bits)
-        u8, pred, u8_p, pred_p = self._outputs((self.row_end - self.row_begin, self.width, self.out_features), want_u8, want_pred,
-                                               bits)
-        _check(fn(self.h, u8_p, pred_p))
+    def _draw(self, name: str, shape, want_u8: bool, want_pred: bool, bits: int, *window):
+        """The one render call: entry point `name` (bits = 16: `name`16), the outputs of `shape`, the call (`window`: the
+        arguments between the handle and the outputs), no host sync: (samples or None, pred or None)"""
+        fn = _render_entry(self.lib, name, bits)
+        u8, pred, u8_p, pred_p = self._outputs(shape, want_u8, want_pred, bits)
+        _check(fn(self.h, *window, u8_p, pred_p))
         return u8, pred
+
+    def render(self, want_u8: bool = True, want_pred: bool = False, bits: int = 8):
+        """type(self)._RENDER (sf_render) on this handle's rows, no host sync: (rgb8 [rows, W, C] uint8 or None, pred
+        [rows, W, C] fp32 or None).  u8 = min(max((int)(pred * 255), 0), 255); pred is bit-identical to forward()'s.
+        bits=16: sf_render16, the samples are uint16, min(max((int)(pred * 65535), 0), 65535)."""
+        _require(self.lib, has_render, "sf_render entry point", "the render path")
+        return self._draw(self._RENDER, (self.row_end - self.row_begin, self.width, self.out_features), want_u8, want_pred, bits)
 
     @property
     def scratch_format(self) -> int:
@@ -606,15 +612,7 @@ class WideRenderEngine(RenderEngine):
 
     _CREATE = "sf_wide_render_create"
     _CREATE_NEEDS = (has_wide_render, "sf_wide_render_create entry point", "the wide render path")
-
-    def render(self, want_u8: bool = True, want_pred: bool = False, bits: int = 8):
-        """sf_wide_render (bits=16: sf_wide_render16) on this handle's rows, no host sync: SirenEngine.render's signature
-        and return"""
-        fn = _render_entry(self.lib, "sf_wide_render", bits)
-        u8, pred, u8_p, pred_p = self._outputs((self.row_end - self.row_begin, self.width, self.out_features), want_u8, want_pred,
-                                               bits)
-        _check(fn(self.h, u8_p, pred_p))
-        return u8, pred
+    _RENDER = "sf_wide_render"
 
 
 class FeatherRenderEngine(RenderEngine):
@@ -741,10 +739,7 @@ class WaveletEngine(SirenEngine):
 
 def _wavelet_render(eng, r0: int, r1: int, c0: int, c1: int, want_u8: bool, want_pred: bool, bits: int = 8):
     _require(eng.lib, has_wavelet_render, "sf_wavelet_render entry point", "the WaveletSiren render path")
-    fn = _render_entry(eng.lib, "sf_wavelet_render", bits)
-    u8, pred, u8_p, pred_p = eng._outputs((max(r1 - r0, 0), max(c1 - c0, 0), 3), want_u8, want_pred, bits)
-    _check(fn(eng.h, r0, r1, c0, c1, u8_p, pred_p))
-    return u8, pred
+    return eng._draw("sf_wavelet_render", (max(r1 - r0, 0), max(c1 - c0, 0), 3), want_u8, want_pred, bits, r0, r1, c0, c1)
 
 
 class WaveletRenderEngine(WaveletEngine):

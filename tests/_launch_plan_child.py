@@ -84,10 +84,10 @@ def rendered(eng, **kw):
     return finish(eng, {"sha256": sha(u8), "sha256_pred": sha(pred)})
 
 
-def render(hidden, depth, **kw):
+def render(hidden, depth, cls=E.RenderEngine, **kw):
     H, W = 40, 52
     rows, cols = (t.cuda() for t in so.grid_vectors(H, W))
-    eng = E.RenderEngine(H, W, hidden, depth, chunk_pixels=1024)
+    eng = cls(H, W, hidden, depth, chunk_pixels=1024)
     eng.set_coords(rows, cols)
     eng.set_params(siren_flat(hidden, depth))
     return rendered(eng, **kw)
@@ -155,6 +155,9 @@ def cases():
     out.append(("render16_64x3_40x52", lambda: render(64, 3, bits=16)))
     # pixel rows 6 .. 21, columns 9 .. 29 of H = 30 read the 10 x 13 coefficient window at (3, 4) of the 17 x 17 grid
     out.append(("wavelet_render16_window_64x3_H30", lambda: wavelet_render(r0=6, r1=22, c0=9, c1=30, bits=16)))
+    # the wide render handle: at depth 4 the last layer reads the plane that layer 0 wrote (the two planes wrap)
+    out.append(("wide_render_512x3_40x52", lambda: render(512, 3, E.WideRenderEngine)))
+    out.append(("wide_render16_1024x4_40x52", lambda: render(1024, 4, E.WideRenderEngine, bits=16)))
     out.append(("feather_64x3_fmt16_40x52", lambda: siren(40, 52, 64, 3, 16, feather=True)))
     return out
 

@@ -18,6 +18,8 @@ Cases (all eager, profiling on, one sf_forward + one sf_forward_backward, render
   render handles: sf_render_create 64x3 and 256x4, sf_fourier_render_create 64, sf_wavelet_render_create 64x3 (H = 30);
     at 16 bits per sample sf_render16 on the 64x3 handle and sf_wavelet_render16 of a pixel window whose coefficient
     window starts inside the grid and is narrower than it (golden: the library before the passes shared one chunk loop)
+  wide render handles (sf_wide_render_create) on 40 x 52, chunk_pixels 1024: 512x3 at 8 bits per sample and 1024x4 at 16,
+    where the two activation planes wrap (golden: the library before the wide forward and the render loop shared one walk)
   Feathermap: an attached 64x3 handle, with one sf_adam_step after the two passes
 
 One more case runs with profiling off: sf_step with three learning rates and want_loss on a WaveletSiren 64x3 handle at
