@@ -66,14 +66,17 @@ static constexpr double kTwoPi = 6.283185307179586476925286766559;
 //  the hidden layers', so it gets its own line in the per-kernel report)
 // (k_feather_*: the Feathermap update of sf_adam_step on a handle with sf_feather_attach, feather_kernels.hip)
 enum KernelId { K_FWD = 0, K_BWD_HIDDEN, K_BWD_LAST, K_DW_FIRST, K_REDUCE, K_SSE, K_ADAM, K_IMAGES, K_BWD_L1,
-                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_MASK, K_MASK_PRUNE, K_MASK_SNFS, K_RENDER, K_WV_RENDER, K_FF_RENDER, K_COUNT };
+                K_FTH_GRAD, K_FTH_DV, K_FTH_ADAM, K_FTH_MAT, K_WV_COMPOSE, K_WV_ADJOINT, K_WV_INJECT, K_MASK, K_MASK_PRUNE, K_MASK_SNFS,
+                K_KMQ_GUESS, K_KMQ_ASSIGN, K_KMQ_UPDATE, K_KMQ_FINISH, K_KMQ_PREDICT, K_KMQ_NUDGE, K_RENDER, K_WV_RENDER, K_FF_RENDER, K_COUNT };
 // (k_wv_*: the image-space composition of a WaveletSiren handle and its adjoint, wavelet_kernels.hip)
 // (k_mask_update: the two kernels of one sf_mask_update, siren_mask.hip; k_mask_prune_global: the kernels of one
 //  sf_mask_prune_global, same file; k_mask_snfs: the three kernels of one sf_mask_update_snfs, same file)
+// (k_kmq_*: the batched kernels of the quantise phase, siren_quant.hip - one record per launch, so the profile counts launches)
 static const char* kKernelNames[K_COUNT] = {"k_fwd",    "k_bwd_hidden", "k_bwd_last", "k_dw_first",
                                             "k_reduce", "k_sse",        "k_adam",     "k_images", "k_bwd_layer1",
                                             "k_feather_grad", "k_feather_dv", "k_feather_adam", "k_feather_mat",
                                             "k_wv_compose", "k_wv_adjoint", "k_wv_inject", "k_mask_update", "k_mask_prune_global", "k_mask_snfs",
+                                            "k_kmq_guess", "k_kmq_assign", "k_kmq_update", "k_kmq_finish", "k_kmq_predict", "k_kmq_nudge",
                                             "k_render", "k_wv_render", "k_ff_render"};
 
 struct ProfRec {
@@ -145,6 +148,7 @@ struct sf_engine {
   long d_stride = 0;      // pieces per layer in the delta scratch (p_stride: phases)
   long a_stride = 0;      // wide path: pieces per layer in the activation scratch (always 16-bit)
   KmWs* km_ws = nullptr;        // sf_kmeans_fit workspace (allocated on first use)
+  KmWs* kmq_ws = nullptr;       // sf_quant_pass: one workspace row per layer (allocated on first use)
   MaskRow* mask_rows = nullptr; // sf_mask_update without stats_dev: its statistics rows (allocated on first use)
   SnfsRow* snfs_rows = nullptr; // sf_mask_update_snfs without stats_dev: its statistics rows (allocated on first use)
   PruneWs* prune_ws = nullptr;  // sf_mask_prune_global: bucket counts, offsets, the search's answer (allocated on first use)

@@ -18,6 +18,7 @@
 #include "feather_kernels.hip"
 #include "wavelet_kernels.hip"
 #include "siren_mask.hip"
+#include "siren_quant.hip"
 
 #include "engine.h"
 
@@ -372,8 +373,9 @@ int sf_forward_backward(sf_handle* h, double* sse_out) try {
   return SF_OK;
 } SF_CATCH
 
-// one optimiser step on the gradient the handle holds, then the weight images of the new parameters
-static int adam_step(sf_engine* h, float lr) {
+// one optimiser step on the gradient the handle holds, then the weight images of the new parameters (refresh = false: they
+// stay marked dirty - the caller rewrites the weights before the next pass, which refreshes them)
+static int adam_step(sf_engine* h, float lr, bool refresh = true) {
   h->step += 1;
   AdamArgs a = zeroed<AdamArgs>();
   if (h->ctx->replay) { a.tab = h->graph.step_tab; a.iter = h->graph.iter_dev; }
@@ -402,7 +404,7 @@ static int adam_step(sf_engine* h, float lr) {
     SF_TRY(launch(h, k_adam, (h->P + 255) / 256, 256, 0, a));
   }
   h->images_dirty = true;
-  return refresh_images(h);
+  return refresh ? refresh_images(h) : SF_OK;
 }
 int sf_adam_step(sf_handle* h, float lr) try {
   if (!h) return fail(SF_ERR_INVALID, "null argument");
@@ -597,6 +599,7 @@ int sf_debug_throw(int32_t kind) try {
 
 }  // extern "C"
 
+#include "quant_host.hip"
 #include "siren_render.hip"
 #include "wavelet_render.hip"
 #include "fourier_render.hip"

@@ -15,11 +15,13 @@
 //     order in which workgroups arrive, unlike float atomics), divided in double and rounded once to float - the exact mean,
 //     where torch_scatter's sequential float sum carries ~1e-7 of rounding: centroid VALUES stay "parity unpinned" at that
 //     third-party boundary, labels are pinned by golden vectors (tests/golden/kmeans_*.npz).
+// Every kernel is a call of a device function (km_init / km_assign / km_update / km_finish / km_predict): the batched kernels of
+// the quantise phase (siren_quant.hip) call the same ones per layer, so both give the same bits.
 // (included by siren_fit.hip)
 
 namespace sf {
 
-constexpr int kKmMaxK = 512;      // 2^bits <= 512 (the reference's slurm scripts go to bits = 9)
+constexpr int kKmMaxK = 512;     // 2^bits <= 512 (the reference's slurm scripts go to bits = 9)
 
 struct KmWs {                     // device workspace of a handle (zeroed at allocation)
   long long sums[kKmMaxK];
@@ -35,8 +37,8 @@ struct KmWs {                     // device workspace of a handle (zeroed at all
 // for K >= 2 (K = 1 is refused: its one centre is the minimum alone); with it n * max|w| * scale < 2^61 and no segment sum
 // can overflow.  A guess whose end is not finite (linspace(inf, -inf): a tensor without a non-zero weight) marks the call
 // EMPTY: k_km_assign / k_km_update then change nothing and k_km_finish writes the one centroid +0.0.
-__global__ void k_km_init(const float* centers, int K, long n, KmWs* ws) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
+__device__ __forceinline__ void km_init(const float* centers, int K, long n, KmWs* ws) {
+  if (threadIdx.x == 0) {
     const float lo = fabsf(centers[0]), hi = fabsf(centers[K - 1]);
     const bool empty = !(lo < __builtin_inff()) || !(hi < __builtin_inff());         // (NaN compares false)
     const float m = fmaxf(lo, hi);
@@ -49,10 +51,12 @@ __global__ void k_km_init(const float* centers, int K, long n, KmWs* ws) {
   }
   for (int i = threadIdx.x; i < kKmMaxK; i += blockDim.x) { ws->sums[i] = 0; ws->counts[i] = 0; }
 }
+__global__ void k_km_init(const float* centers, int K, long n, KmWs* ws) { km_init(centers, K, n, ws); }
 
 // labels of the non-zero weights against the current centres + fixed-point segment sums
-__global__ __launch_bounds__(256) void k_km_assign(const float* __restrict__ w, long n, const float* __restrict__ centers, int K,
-                                                   KmWs* ws) {
+// (block `bid` of `nblk` blocks of 256 threads walks the tensor: the callers' grids differ, the sums do not depend on them)
+__device__ __forceinline__ void km_assign(const float* __restrict__ w, long n, const float* __restrict__ centers, int K, KmWs* ws,
+                                          long bid, long nblk) {
   if (ws->done) return;
   const double scale = ws->scale;
   __shared__ float sc[kKmMaxK];
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(256) void k_km_assign(const float* __restrict__ w, 
   __shared__ int scnt[kKmMaxK];
   for (int i = threadIdx.x; i < K; i += blockDim.x) { sc[i] = centers[i]; ssum[i] = 0ull; scnt[i] = 0; }
   __syncthreads();
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+  for (long i = bid * blockDim.x + threadIdx.x; i < n; i += nblk * blockDim.x) {
     const float x = w[i];
     if (x == 0.0f) continue;                                     // kmeans.py:123 (zeros are excluded from the fit)
     int best = 0;
@@ -81,9 +85,13 @@ __global__ __launch_bounds__(256) void k_km_assign(const float* __restrict__ w, 
     }
   }
 }
+__global__ __launch_bounds__(256) void k_km_assign(const float* __restrict__ w, long n, const float* __restrict__ centers, int K,
+                                                   KmWs* ws) {
+  km_assign(w, n, centers, K, ws, blockIdx.x, gridDim.x);
+}
 
 // new centres = segment means (empty bins -> 0, as scatter_mean), convergence test, accumulators cleared
-__global__ __launch_bounds__(kKmMaxK) void k_km_update(float* centers, int K, KmWs* ws, float tol) {
+__device__ __forceinline__ void km_update(float* centers, int K, KmWs* ws, float tol) {
   const double inv_scale = 1.0 / ws->scale;
   __shared__ float sh[kKmMaxK];
   const int t = threadIdx.x;
@@ -105,10 +113,11 @@ __global__ __launch_bounds__(kKmMaxK) void k_km_update(float* centers, int K, Km
     if (s * s < tol) ws->done = 1;
   }
 }
+__global__ __launch_bounds__(kKmMaxK) void k_km_update(float* centers, int K, KmWs* ws, float tol) { km_update(centers, K, ws, tol); }
 
 // {0} U centres -> unique (ascending) -> ordered by |c| (ties: the smaller value first) -> centroids_out (zero padded);
 // an empty call (done == 2, k_km_init): {0} alone
-__global__ __launch_bounds__(kKmMaxK) void k_km_finish(const float* centers, int K, KmWs* ws, float* cent_out, int n_out, int* n_cent_out) {
+__device__ __forceinline__ void km_finish(const float* centers, int K, KmWs* ws, float* cent_out, int n_out, int* n_cent_out) {
   __shared__ float v[kKmMaxK + 1];
   __shared__ float u[kKmMaxK + 1];
   __shared__ int nu;
@@ -142,15 +151,19 @@ __global__ __launch_bounds__(kKmMaxK) void k_km_finish(const float* centers, int
   for (int i = c + t; i < n_out; i += blockDim.x) cent_out[i] = 0.0f;
   if (t == 0) { ws->n_cent = c; if (n_cent_out) *n_cent_out = c; ws->done = 0; }
 }
+__global__ __launch_bounds__(kKmMaxK) void k_km_finish(const float* centers, int K, KmWs* ws, float* cent_out, int n_out, int* n_cent_out) {
+  km_finish(centers, K, ws, cent_out, n_out, n_cent_out);
+}
 
 // labels of ALL weights against the final centroids (+ the codebook weights), kmeans.py:139-146
-__global__ __launch_bounds__(256) void k_km_predict(const float* __restrict__ w, long n, const float* __restrict__ cent, const KmWs* ws,
-                                                    long long* labels, float* new_w) {
+// (w and new_w may be the same buffer: an element is read, then written, by one thread)
+__device__ __forceinline__ void km_predict(const float* w, long n, const float* __restrict__ cent, const KmWs* ws, long long* labels,
+                                           float* new_w, long bid, long nblk) {
   __shared__ float sc[kKmMaxK + 1];
   const int c = ws->n_cent;
   for (int i = threadIdx.x; i < c; i += blockDim.x) sc[i] = cent[i];
   __syncthreads();
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+  for (long i = bid * blockDim.x + threadIdx.x; i < n; i += nblk * blockDim.x) {
     const float x = w[i];
     int best = 0;
     float bd = __fmul_rn(__fsub_rn(x, sc[0]), __fsub_rn(x, sc[0]));
@@ -162,6 +175,10 @@ __global__ __launch_bounds__(256) void k_km_predict(const float* __restrict__ w,
     if (labels) labels[i] = best;
     if (new_w) new_w[i] = sc[best];
   }
+}
+__global__ __launch_bounds__(256) void k_km_predict(const float* __restrict__ w, long n, const float* __restrict__ cent, const KmWs* ws,
+                                                    long long* labels, float* new_w) {
+  km_predict(w, n, cent, ws, labels, new_w, blockIdx.x, gridDim.x);
 }
 
 }  // namespace sf

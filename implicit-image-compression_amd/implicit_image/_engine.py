@@ -89,6 +89,16 @@ class sf_mask_update_snfs_args(C.Structure):
                 ("dense_gradients", C.c_int32), ("stats_dev", C.c_void_p)]
 
 
+class sf_quant_layer(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("centers_dev", C.c_void_p), ("centroids_dev", C.c_void_p),
+                ("n_centroids_dev", C.c_void_p), ("labels_dev", C.c_void_p)]
+
+
+class sf_quant_args(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("n_layers", C.c_int32), ("layers", C.POINTER(sf_quant_layer)),
+                ("K", C.c_int32), ("iter_limit", C.c_int32), ("tol", C.c_float), ("nudge_lr", C.c_float)]
+
+
 MASK_STATS_WORDS = C.sizeof(sf_mask_layer_stats) // 8      # a statistics row as int64 words (the last one: a double)
 MASK_SNFS_STATS_WORDS = C.sizeof(sf_mask_snfs_stats) // 8  # ... of sf_mask_update_snfs (words 7, 8, 9 and 11: doubles)
 MASK_GROWTH = {"none": 0, "absolute-gradient": 1, "momentum": 2}
@@ -171,6 +181,12 @@ _declare("core", {"sf_mask_update": [H, P(sf_mask_update_args)]})
 _declare("core", {"sf_mask_prune_global": [H, P(sf_mask_prune_global_args)]})
 # (the update of masking=SNFS on the device, same file; has_mask_update_snfs asks for the symbol itself)
 _declare("core", {"sf_mask_update_snfs": [H, P(sf_mask_update_snfs_args)]})
+# (the quantise phase on the device, csrc/siren_quant.hip; has_quant_step asks for the symbols themselves, KmeansQuant routes by it)
+_declare("core", {
+    "sf_quant_pass": [H, P(sf_quant_args)],
+    "sf_quant_nudge": [H, P(sf_quant_args)],
+    "sf_quant_step": [H, P(sf_quant_args), P(C.c_float), I32, P(C.c_float)],
+})
 
 
 def load_library():
@@ -247,6 +263,11 @@ def has_mask_prune_global(lib) -> bool:
 def has_mask_update_snfs(lib) -> bool:
     """sf_mask_update_snfs: the momentum-growth, momentum-redistribution update of masking=SNFS on the device"""
     return hasattr(lib, "sf_mask_update_snfs")
+
+
+def has_quant_step(lib) -> bool:
+    """sf_quant_pass / sf_quant_nudge / sf_quant_step: the quantise phase on the device (csrc/siren_quant.hip)"""
+    return all(hasattr(lib, n) for n in ("sf_quant_pass", "sf_quant_nudge", "sf_quant_step"))
 
 
 def _require(lib, has, entry: str, since: str):
@@ -422,6 +443,49 @@ class SirenEngine:
         _check(self.lib.sf_kmeans_fit(self.h, w.data_ptr(), w.numel(), centers.data_ptr(), K, iter_limit, tol, cent.data_ptr(), K + 1,
                                       ncent.data_ptr(), labels.data_ptr(), new_w.data_ptr()))
         return cent, ncent, labels.reshape(weight.shape), new_w.reshape(weight.shape)
+
+    def quant_args(self, layers: Sequence[int], centres, centroids, n_centroids, labels, K: int, iter_limit: int = 5,
+                   tol: float = 1e-4, nudge_lr: float = 0.0) -> sf_quant_args:
+        """the argument struct of quant_pass / quant_nudge / quant_step: `layers` (ascending engine layer indices) with, per
+        layer, the caller's device buffers - centres float32 [K], centroids float32 [K + 1], n_centroids int32 [1] (or None),
+        labels int64 [the layer's weight count].  The struct keeps the buffers alive."""
+        if not (len(layers) == len(centres) == len(centroids) == len(n_centroids) == len(labels)):
+            raise ValueError("quant_args: one buffer of each kind per layer")
+        rows = (sf_quant_layer * max(len(layers), 1))()
+        for j, l in enumerate(layers):
+            w, b = self.param_offsets(l)
+            lab, nc = labels[j], n_centroids[j]
+            if not (lab.is_cuda and lab.dtype == torch.int64 and lab.is_contiguous() and lab.numel() == b - w):
+                raise ValueError(f"quant_args: labels of layer {l} must be a contiguous int64 CUDA tensor of {b - w} elements")
+            if nc is not None and not (nc.is_cuda and nc.dtype == torch.int32 and nc.numel() >= 1):
+                raise ValueError("quant_args: n_centroids must be an int32 CUDA tensor")
+            rows[j] = sf_quant_layer(layer=l, centers_dev=_f32_cuda(centres[j], K).data_ptr(),
+                                     centroids_dev=_f32_cuda(centroids[j], K + 1).data_ptr(),
+                                     n_centroids_dev=None if nc is None else nc.data_ptr(), labels_dev=lab.data_ptr())
+        args = sf_quant_args(abi_version=SF_ABI_VERSION, n_layers=len(layers), layers=rows, K=K, iter_limit=iter_limit, tol=tol,
+                             nudge_lr=nudge_lr)
+        args._keep = (rows, list(centres), list(centroids), list(n_centroids), list(labels))
+        return args
+
+    def quant_pass(self, args: sf_quant_args):
+        """sf_quant_pass on this handle's stream, no host sync: per listed layer the guess, the Lloyd iterations, the
+        centroids and labels into the caller's buffers, the codebook weights into the handle's params"""
+        _require(self.lib, has_quant_step, "sf_quant_pass entry point", "the device quantise phase")
+        _check(self.lib.sf_quant_pass(self.h, C.byref(args)))
+
+    def quant_nudge(self, args: sf_quant_args):
+        """sf_quant_nudge, no host sync: centroids[k] -= nudge_lr * (sum of the handle's grads over the weights labelled k)"""
+        _require(self.lib, has_quant_step, "sf_quant_nudge entry point", "the device quantise phase")
+        _check(self.lib.sf_quant_nudge(self.h, C.byref(args)))
+
+    def quant_step(self, args: sf_quant_args, lrs: Sequence[float], want_loss: bool = False):
+        """sf_quant_step: len(lrs) x (pass, forward_backward, nudge, Adam) in one call; the losses (one read at the end) or None"""
+        _require(self.lib, has_quant_step, "sf_quant_step entry point", "the device quantise phase")
+        n = len(lrs)
+        arr = (C.c_float * max(n, 1))(*lrs)
+        out = (C.c_float * max(n, 1))() if want_loss else None
+        _check(self.lib.sf_quant_step(self.h, C.byref(args), arr, n, out))
+        return list(out)[:n] if want_loss else None
 
     def mask_update(self, layers: Sequence[int], prune_rate: float, growth: int, dense_gradients: bool,
                     stats: Optional[torch.Tensor] = None):
@@ -664,6 +728,7 @@ class FourierEngine(SirenEngine):
     mask_update = None          # sf_mask_update refuses a FourierNet handle: Masking keeps such a model on the host path
     mask_prune_global = None    # (sf_mask_prune_global likewise)
     mask_update_snfs = None     # (sf_mask_update_snfs likewise)
+    quant_step = None           # sf_quant_step refuses this handle: KmeansQuant keeps such a model on the host path
 
     def set_encoding(self, B: torch.Tensor):
         """encoding.B [2, map_size/2] (fp32, copied into the engine)"""
@@ -708,6 +773,7 @@ class WaveletEngine(SirenEngine):
     mask_update = None          # sf_mask_update refuses a WaveletSiren handle: its topology updates stay on the host
     mask_prune_global = None    # (sf_mask_prune_global likewise)
     mask_update_snfs = None     # (sf_mask_update_snfs likewise)
+    quant_step = None           # sf_quant_step refuses this handle: KmeansQuant keeps such a model on the host path
 
     def set_coords(self, rows: torch.Tensor, cols: torch.Tensor):
         """rows / cols: the linspace(0, 1, n) vectors of the coefficient grid (n = (H + 5) // 2)"""

@@ -104,8 +104,13 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
             quantized_model.engine(grid, img)
             quantized_model.set_engine_masks(mask.flat_mask())
         with Quantize(quantized_model, q_optim, qcfg) as q:
-            for i in range(qcfg.num_steps):
-                train_epoch(quantized_model, q_optim, grid, img, lr_scheduler=q_sched)
+            i = -1
+            while i + 1 < qcfg.num_steps:
+                # as above: the steps up to the next logging boundary in one train_steps() call, which is sf_quant_step when
+                # the quantiser has a device plan and the train_epoch() loop otherwise
+                first = i + 1
+                i = min(first + qcfg.log_steps - 1 - first % qcfg.log_steps, qcfg.num_steps - 1)
+                train_steps(quantized_model, q_optim, grid, img, i - first + 1, lr_scheduler=q_sched)
                 if (i + 1) % qcfg.log_steps == 0:
                     _, l, p, p8 = eval_epoch(quantized_model, grid, img)
                     logging.info(f"Quant | Step: {i + 1} | loss: {l:.4f} | PSNR: {p:.4f} | PSNR_8bit: {p8:.4f}")

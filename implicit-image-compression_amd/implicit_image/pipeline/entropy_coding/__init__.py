@@ -3,7 +3,7 @@ parsers.py:20-64).
 
 Wire format (unchanged): `compressed_weights.data` = the state-dict tensors in state-dict order, each
 as raw little-endian ndarray.tobytes() pushed through the stream writer; quantised layers contribute
-`centroids` (float) + `labeled_weight` (uint8 labels) instead of `weight`; `meta_data.json` maps the
+`centroids` (float) + `labeled_weight` (uint8 labels; uint16 once a label exceeds 255, quant.bits=9) instead of `weight`; `meta_data.json` maps the
 write order to {shape, dtype, name} (sorted keys, indent 2).  Writers: plain, lzma (one independent LZMA
 blob per tensor; the reported size counts sys.getsizeof of every blob, parsers.py:56), zstd only when the
 `zstandard` module is importable (it is not, offline).  `huffman` is unimplemented in the reference."""
@@ -78,9 +78,11 @@ def linear_state_dict(model: nn.Module) -> Dict[str, torch.Tensor]:
             if f"{name}.labeled_weight" not in state_dict:
                 raise KeyError("Please run .update() before compressing weights")
             labels = state_dict[f"{name}.labeled_weight"]
-            if labels.max() > 2 ** 8:
-                raise NotImplementedError("more than 256 centroids: the reference asks for torch.uint16 here")
-            state_dict[f"{name}.labeled_weight"] = labels.to(torch.uint8)
+            # a label above 255 does not fit a byte: uint16 (little-endian in the stream, "dtype": "uint16" in the meta data).
+            # The reference's rule is `max > 2 ** 8`; at a maximum of exactly 256 it writes uint8 and the label wraps to 0 -
+            # uint16 there is a stated departure
+            wide = labels.numel() > 0 and int(labels.max()) > 255
+            state_dict[f"{name}.labeled_weight"] = labels.to(torch.uint16 if wide else torch.uint8)
     return state_dict
 
 

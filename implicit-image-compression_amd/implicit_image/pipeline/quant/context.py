@@ -13,7 +13,9 @@ class Quantize:
             raise NotImplementedError(f"quant '{name}': only KMeans is provided (QAT needs torch.quantization modules)")
         get = self.quant_conf.get
         skip_ll = get("skip_ll", ["layers.0.linear", "layers.7.linear"])
-        self.compress = KmeansQuant(self.model, self.optim, bits=get("bits"), skip_ll=skip_ll)
+        # (the override grammar reads a bare `off` as YAML's false and `on` as true)
+        phase = {False: "off", True: "auto", None: "auto"}.get(get("device_phase", "auto"), get("device_phase", "auto"))
+        self.compress = KmeansQuant(self.model, self.optim, bits=get("bits"), skip_ll=skip_ll, device_phase=phase)
         return self
 
     def __exit__(self, exc_type, exc, tb):

@@ -9,7 +9,14 @@ Engine coupling: the reference hangs a forward-pre-hook on every nn.Linear; the 
 never calls those modules, so `KmeansQuant` registers ONE model-level callback that re-clusters all
 non-skipped layers in module order right before every engine pass (Siren.engine()), and one
 post-backward callback for the centroid nudge (kmeans.py:163-181).
+
+Device route (`device_phase: auto`, conf/quant/kmeans.yaml): on an unpadded SIREN whose handle has sf_quant_pass /
+sf_quant_nudge / sf_quant_step (csrc/siren_quant.hip) the two callbacks are one batched call each over persistent per-layer
+buffers - no torch op and no host read per layer -, and train_steps() hands whole runs of quantise-phase steps to
+sf_quant_step.  The pass gives the bits of the step-by-step path; the nudge sums in 64-bit fixed point where scatter_add_
+uses float atomics, so it is deterministic run to run and within rounding of the host path's.
 """
+import os
 from typing import List, Sequence
 
 import torch
@@ -93,8 +100,13 @@ def find_centroids(weight: torch.Tensor, n_clusters: int):
 
 
 class KmeansQuant:
-    def __init__(self, model: nn.Module, optim, bits: int = 5, skip_ll: Sequence[str] = ("layers.0.linear", "layers.7.linear")):
+    def __init__(self, model: nn.Module, optim, bits: int = 5, skip_ll: Sequence[str] = ("layers.0.linear", "layers.7.linear"),
+                 device_phase: str = "auto"):
+        assert device_phase in ("auto", "off"), "device_phase: 'auto' (sf_quant_step where it applies) or 'off'"
         self.model, self.optim, self.bits, self.skip_ll = model, optim, bits, list(skip_ll)
+        self.device_phase = device_phase
+        self._plan = None                       # (engine, sf_quant_args over this quantiser's persistent buffers)
+        self._in_bulk = False                   # train_steps is handing the steps to sf_quant_step: the pass runs there
         self._targets: List[nn.Linear] = [m for n, m in model.named_modules()
                                          if isinstance(m, nn.Linear) and n not in self.skip_ll]
         self._pre = self.kmeans_modify_weights
@@ -110,10 +122,69 @@ class KmeansQuant:
     def learning_rate(self) -> float:
         return self.optim.defaults["lr"]
 
+    def device_wanted(self) -> bool:
+        """what device_plan asks before there is a handle: the configuration, the model, the bits, the two knobs"""
+        from ...models.siren import Siren
+        return (self.device_phase == "auto" and isinstance(self.model, Siren) and self.model.state_is_live
+                and 4 <= self.n_clusters <= 512 and bool(self._targets)
+                and os.environ.get("SIREN_FIT_DEVICE_QUANT") != "0" and os.environ.get("SIREN_FIT_NATIVE_KMEANS", "1") != "0")
+
+    def device_plan(self):
+        """(engine, sf_quant_args) when the phase can run through the batched entry points, else None: device_phase "auto",
+        an unpadded SIREN (state_is_live) bound to a handle whose library has them, 4 <= 2^bits <= 512, every quantised Linear
+        the weight of an engine layer, and neither SIREN_FIT_DEVICE_QUANT nor SIREN_FIT_NATIVE_KMEANS "0" (A/B knobs, named
+        like SIREN_FIT_DEVICE_MASK).  The buffers - centres, centroids (zero padded to 2^bits), n_centroids, labels - are made
+        once per handle and are what m.centroids / m.n_centroids / m.labeled_weight then name."""
+        from ... import _engine
+        if not self.device_wanted():
+            return None
+        eng = self.model.bound_engine
+        if eng is None or not callable(eng.quant_step) or not _engine.has_quant_step(eng.lib):
+            return None
+        if self._plan is not None and self._plan[0] is eng:
+            return self._plan
+        weights = [p for p in self.model._param_list()][0::2]
+        layers = []
+        for m in self._targets:
+            idx = [i for i, w in enumerate(weights) if w is m.weight]
+            if len(idx) != 1:
+                return None
+            layers.append(idx[0])
+        if layers != sorted(layers):
+            return None
+        K, dev = self.n_clusters - 1, eng.device
+        centres = [torch.zeros(K, device=dev) for _ in layers]
+        centroids = [torch.zeros(K + 1, device=dev) for _ in layers]
+        counts = [torch.ones(1, dtype=torch.int32, device=dev) for _ in layers]
+        labels = [torch.zeros(m.weight.shape, dtype=torch.int64, device=dev) for m in self._targets]
+        args = eng.quant_args(layers, centres, centroids, counts, labels, K, nudge_lr=self.learning_rate)
+        self._plan = (eng, args)
+        return self._plan
+
+    def _name_buffers(self, args):
+        """the plan's buffers under the names the host path leaves its results in"""
+        _, _, centroids, counts, labels = args._keep
+        for m, c, n, l in zip(self._targets, centroids, counts, labels):
+            m.labeled_weight, m.centroids, m.n_centroids = l, c, n
+
+    def device_steps(self, lrs, want_loss: bool = True):
+        """len(lrs) quantise-phase steps - pass, forward_backward, nudge, Adam - in one sf_quant_step call on the plan's handle"""
+        eng, args = self.device_plan()
+        args.nudge_lr = self.learning_rate
+        losses = eng.quant_step(args, lrs, want_loss=want_loss)
+        self._name_buffers(args)
+        return losses
+
     @torch.no_grad()
     def kmeans_modify_weights(self):
         """forward-pre-hook of the reference, for every quantised layer in module order (kmeans.py:66-72)."""
-        import os
+        if self._in_bulk:
+            return
+        plan = self.device_plan()
+        if plan is not None:                    # one batched call: guess, Lloyd, centroids, labels, the weights into params
+            plan[0].quant_pass(plan[1])
+            self._name_buffers(plan[1])
+            return
         eng = self.model.bound_engine
         if os.environ.get("SIREN_FIT_NATIVE_KMEANS", "1") == "0":       # A/B knob: the torch host mirror
             eng = None
@@ -132,6 +203,11 @@ class KmeansQuant:
     @torch.no_grad()
     def scalar_quantization(self):
         """backward hook (kmeans.py:163-181): centroids -= lr * scatter_add(labels, dL/dW)."""
+        plan = self.device_plan()
+        if plan is not None and all(m.centroids is c for m, c in zip(self._targets, plan[1]._keep[2])):
+            plan[1].nudge_lr = self.learning_rate
+            plan[0].quant_nudge(plan[1])        # in place on the plan's centroid buffers, fixed-point segment sums
+            return
         for m in self._targets:
             dw = torch.zeros_like(m.centroids)
             dw.scatter_add_(0, m.labeled_weight.flatten(), m.weight.grad.flatten())
@@ -150,7 +226,8 @@ class KmeansQuant:
         for m in self._targets:
             centroids, labels = m.centroids, m.labeled_weight
             if getattr(m, "n_centroids", None) is not None:
-                centroids = centroids[:int(m.n_centroids.item())]     # (the one host read of the quantise phase: at its end)
+                centroids = centroids[:int(m.n_centroids.item())].clone()   # (the one host read of the quantise phase: at its end)
+                labels = labels.clone()         # (the device route's buffers are persistent)
                 m.n_centroids = None
             m.centroids = nn.Parameter(centroids, requires_grad=False)
             m.labeled_weight = nn.Parameter(labels, requires_grad=False)

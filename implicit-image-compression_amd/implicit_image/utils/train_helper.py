@@ -18,6 +18,7 @@ from torch.nn import Module, functional as F
 from torch.optim import Optimizer
 
 from ..pipeline.masking import Masking, decay_registry
+from ..pipeline.quant.kmeans import KmeansQuant
 
 
 class EngineAdam(Optimizer):
@@ -171,6 +172,18 @@ def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
     return loss
 
 
+def _quant_phase(model: Module, optim: Optimizer):
+    """the KmeansQuant whose two callbacks are the model's only ones and which steps `optim`, when it wants the device route:
+    the quantise phase as train_steps can hand it to sf_quant_step once the handle is there.  Else None."""
+    pre, post = model.pre_pass_callbacks, model.post_backward_callbacks
+    if len(pre) != 1 or len(post) != 1:
+        return None
+    kq = getattr(post[0], "__self__", None)
+    if not isinstance(kq, KmeansQuant) or getattr(pre[0], "__self__", None) is not kq or kq.optim is not optim:
+        return None
+    return kq if (pre[0] == kq._pre and post[0] == kq._post and kq.device_wanted()) else None
+
+
 def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     """`n` consecutive train_epoch() calls, returned as the list of their losses.
 
@@ -178,13 +191,41 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     When nothing on the host has to look at the state between two steps (no per-layer callbacks, no padded
     width, masks either absent or applied inside the engine's Adam kernel with dense gradients) the n steps go
     to the engine in ONE call (`sf_step`): same kernels in the same order, so the result is bit-identical to
-    the step-by-step loop, but the stream never drains and the losses come back in one read."""
+    the step-by-step loop, but the stream never drains and the losses come back in one read.
+
+    The quantise phase is the second bulk case: when the model's only callbacks are one KmeansQuant's and it has a device
+    plan (pipeline/quant/kmeans.py), the n steps - each with its k-means pass before and its centroid nudge after the
+    backward - are ONE `sf_quant_step` call.  The nudge's learning rate is optim.defaults["lr"], not the scheduled one, as
+    in the reference."""
     mask: Masking = kwargs.get("mask")
     lr_scheduler = kwargs.get("lr_scheduler")
     pbar = kwargs.get("pbar")
-    bulk = (n > 1 and model.state_is_live and not model.post_backward_callbacks and isinstance(optim, EngineAdam)
-            and (mask is None or mask.steps_need_no_host)
-            and kwargs.get("criterion", F.mse_loss) is F.mse_loss and kwargs.get("preconditioner") is None)
+    plain = (model.state_is_live and isinstance(optim, EngineAdam) and kwargs.get("criterion", F.mse_loss) is F.mse_loss
+             and kwargs.get("preconditioner") is None)
+    kq = _quant_phase(model, optim) if (plain and n >= 1 and mask is None) else None
+    if kq is not None:
+        model.train()
+        kq._in_bulk = True                   # (engine() runs the pre-pass callbacks: the pass belongs to sf_quant_step here)
+        try:
+            model.engine(grid, img)
+        finally:
+            kq._in_bulk = False
+        if kq.device_plan() is None:         # (a handle without the entry points: step by step, the callbacks as ever)
+            kq = None
+    if kq is not None:
+        optim.prepare()
+        optim.count_steps(n)
+        lrs = []
+        for _ in range(n):
+            lrs.append(float(optim.param_groups[0]["lr"]))
+            if lr_scheduler:
+                lr_scheduler.step()
+        losses = kq.device_steps(lrs, want_loss=True)
+        if pbar:
+            pbar.update(n)
+        return losses
+    bulk = (n > 1 and plain and not model.post_backward_callbacks
+            and (mask is None or mask.steps_need_no_host))
     if not bulk:
         return [train_epoch(model, optim, grid, img, **kwargs) for _ in range(n)]
     model.train()

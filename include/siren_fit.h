@@ -198,6 +198,49 @@ int sf_debug_scratch(sf_handle* h, int32_t which, void** dev_ptr, int64_t* bytes
 int sf_kmeans_fit(sf_handle* h, const float* w_dev, int64_t n, float* centers_dev, int32_t K, int32_t iter_limit, float tol,
                   float* centroids_dev, int32_t centroids_cap, int32_t* n_centroids_dev, int64_t* labels_dev,
                   float* new_weight_dev);
+/* The quantise phase of a fit on the handle's stream (csrc/siren_quant.hip, quant_host.hip): what KmeansQuant's forward-pre
+ * and backward hooks do per quantised Linear (pipeline/quant/kmeans.py:66-72,110-150,163-181), batched over the layers - one
+ * launch serves all of them - and without a device-to-host copy or a host synchronisation.
+ *   layers [n_layers]    ascending layer indices of the handle, each with its caller-owned device buffers:
+ *     centers_dev [K]        out: the guess, then the Lloyd centres (what the single-tensor call leaves in centers_dev)
+ *     centroids_dev [K + 1]  out: the centroids, zero padded; the nudge updates them in place
+ *     n_centroids_dev        out (device int, may be NULL): how many of them are real
+ *     labels_dev [n]         out: int64 labels of the layer's weights; the nudge reads them
+ *   K = 2^bits - 1, iter_limit, tol: as the single-tensor call takes them; nudge_lr: the learning rate of the nudge
+ * sf_quant_pass: per layer the guess on the device - min / max over the non-zero weights, then the K entries of
+ *   torch.linspace(min, max, K) in ATen's fp32 form: step = (max - min) / (K - 1), entry i = fma(step, i, min) below K / 2 and
+ *   fma(-step, K - 1 - i, max) from there on; a layer without a non-zero weight gets non-finite ends, the EMPTY CALL above -,
+ *   <= iter_limit Lloyd iterations, the centroids, the labels, and the codebook weights centroids[labels] written straight
+ *   into the handle's parameters (the weight images are marked dirty).  The arithmetic is the single-tensor call's, bit for
+ *   bit.  3 + 2 * iter_limit launches whatever n_layers.
+ * sf_quant_nudge: centroids[k] -= nudge_lr * (sum of the handle's dL/dW over the weights labelled k), all K + 1 entries.  The
+ *   segment sums are 64-bit fixed-point integer adds in the unit 2^(60 - ln - e), n < 2^ln, max|g| < 2^e (1 for a zero or
+ *   non-finite maximum): the result does not depend on the order of arrival.  A sum is rounded once to float, then
+ *   c - nudge_lr * dw in fp32 (two roundings).  One launch.
+ * sf_quant_step: n_steps x (pass, forward_backward, nudge, Adam with lr[i]), launch by launch (never the graph replay of
+ *   sf_step); loss_out (host, may be NULL) receives the MSE of every step through the device loss table, read once at the
+ *   end - the call's only synchronisation, none with NULL.
+ * SF_ERR_INVALID before anything is launched or written: a null pointer, a wrong abi_version, a render handle, a FourierNet
+ * or WaveletSiren handle, an attached Feathermap, n_layers outside 1 .. depth, a layer index out of range or not ascending,
+ * K < 2 or K >= 512, iter_limit < 0; sf_quant_step without coordinates or a target: SF_ERR_STATE.  Every hidden width of
+ * sf_create is served (the flat layout is the same at 512 / 1024). */
+typedef struct sf_quant_layer {
+  int32_t layer;
+  float* centers_dev;
+  float* centroids_dev;
+  int32_t* n_centroids_dev;
+  int64_t* labels_dev;
+} sf_quant_layer;
+typedef struct sf_quant_args {
+  int32_t abi_version;      /* SF_ABI_VERSION */
+  int32_t n_layers;
+  const sf_quant_layer* layers;
+  int32_t K, iter_limit;
+  float tol, nudge_lr;
+} sf_quant_args;
+int sf_quant_pass(sf_handle* h, const sf_quant_args* a);
+int sf_quant_nudge(sf_handle* h, const sf_quant_args* a);
+int sf_quant_step(sf_handle* h, const sf_quant_args* a, const float* lr, int32_t n_steps, float* loss_out);
 /* One RigL topology update (Masking.update_connections of the reference: pipeline/masking/core.py:713-801 with
  * funcs/prune.py:24-51 magnitude_prune, funcs/grow.py:58-97 abs_grad_growth, core.py:250-269 adjust_prune_rate) on the
  * handle's stream: two launches whatever the depth, NO device-to-host copy and no host synchronisation (csrc/siren_mask.hip).
