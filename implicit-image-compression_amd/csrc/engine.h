@@ -167,7 +167,9 @@ struct sf_engine {
   float* slab = nullptr;
   int dw_wg = 0;
   float* sse_part = nullptr;
-  double* sse_dev = nullptr;
+  long n_sse = 0;         // partials sse_part holds (alloc_sse)
+  double* sse_dev = nullptr;   // the pass's SSE and, in the word behind it, sf_eval's integer sum (one copy reads both)
+  unsigned long long* sse8_part = nullptr;   // sf_eval: the integer partials of the EVAL forms, n_sse of them (allocated on first use)
   // render handle (sf_render_create, siren_render.hip; sf_fourier_render_create, fourier_render.hip; sf_wavelet_render_create,
   // wavelet_render.hip): parameters, forward images and coordinates only - no gradient, no optimiser state, no mask, no
   // backward scratch; every training entry point refuses it.  sf_feather_render_attach (feather_host.hip) adds the feather
@@ -487,15 +489,23 @@ long chunked_sse_parts(const sf_engine* h) {
   return round_super(h->npix) / kSuper + (h->npix + h->chunk_px - 1) / h->chunk_px + 8;
 }
 int alloc_sse(sf_engine* h, long n_sse) {
-  SF_TRY(dev_alloc(h, h->sse_part, (size_t)(n_sse + 64) * 4));
-  return dev_alloc(h, h->sse_dev, 8);
+  h->n_sse = n_sse + 64;
+  SF_TRY(dev_alloc(h, h->sse_part, (size_t)h->n_sse * 4));
+  return dev_alloc(h, h->sse_dev, 16);
+}
+// sf_eval: where its integer sum lands, and the fixed-order sums of both kinds of partials of an EVAL pass
+unsigned long long* sse8_dev(const sf_engine* h) { return reinterpret_cast<unsigned long long*>(h->sse_dev + 1); }
+int launch_eval_reduce(sf_engine* h, long n_parts) {
+  Launch L(h, K_SSE, 0, (double)n_parts * 12);
+  return launch(h, k_eval_reduce, 1, 256, 0, h->sse_part, h->sse8_part, n_parts, h->sse_dev, sse8_dev(h));
 }
 
 // the model dispatch of siren_fit.hip: the weight images, the one loop over a handle's chunks (forward; if train, backward;
-// the SSE reduction), and the pass - its checks, the images, then that loop or run_pass_wavelet
+// the SSE reduction), and the pass - its checks, the images, then that loop or run_pass_wavelet.  eval8 (sf_eval, never with
+// train or pred): the EVAL forms of the forwards, their integer partials in h->sse8_part beside the SSE partials, both reduced
 int refresh_images(sf_engine* h);
-int run_chunks(sf_engine* h, bool train, float* pred, bool want_sse);
-int run_pass(sf_engine* h, bool train, float* pred, bool want_sse);
+int run_chunks(sf_engine* h, bool train, float* pred, bool want_sse, bool eval8 = false);
+int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, bool eval8 = false);
 
 // training entry points on a render handle: an argument error, before anything is touched
 int refuse_render(const char* fn) {

@@ -34,15 +34,16 @@ FfArgs ff_args_base(const sf_engine* h, long pix0) {
   for (int l = 0; l < h->D; ++l) { fa.img_f[l] = h->ff.img_f[l]; fa.img_b[l] = h->ff.img_b[l]; fa.off_b[l] = h->off_b[l]; }
   return fa;
 }
-// k_ff_fwd<WD, false>, k_ff_fwd<WD, true>, k_ff_bwd<WD>, k_ff_fwd<WD, false, true>, k_ff_fwd<WD, false, true, 16>
-enum FfKernel { kFfEval, kFfTrain, kFfBwd, kFfRender, kFfRender16 };
+// k_ff_fwd<WD, false>, k_ff_fwd<WD, true>, k_ff_bwd<WD>, k_ff_fwd<WD, false, true>, k_ff_fwd<WD, false, true, 16>,
+// k_ff_fwd<WD, false, false, kFfEvalBits> (sf_eval)
+enum FfKernel { kFfEval, kFfTrain, kFfBwd, kFfRender, kFfRender16, kFfEval8 };
 int launch_ff(sf_engine* h, const FfArgs& a, int n_super, FfKernel which) {
   return with_width(h, [&](auto wd) {
     constexpr int WD = decltype(wd)::value;
     auto go = [&](auto kernel) { return launch(h, kernel, n_super, kFfThreads, kFfLdsBytes, a); };
     return which == kFfEval ? go(k_ff_fwd<WD, false>) : which == kFfTrain ? go(k_ff_fwd<WD, true>)
            : which == kFfBwd ? go(k_ff_bwd<WD>) : which == kFfRender ? go(k_ff_fwd<WD, false, true>)
-                             : go(k_ff_fwd<WD, false, true, 16>);
+           : which == kFfRender16 ? go(k_ff_fwd<WD, false, true, 16>) : go(k_ff_fwd<WD, false, false, kFfEvalBits>);
   });
 }
 
@@ -56,17 +57,19 @@ FfArgs ff_chunk_args(const sf_engine* h, const Chunk& k, float* pred, float* sse
 }
 
 // The forward of chunk c (k_ff_fwd), training or evaluation form: the prediction to pred (or null), the chunk's SSE partials
-// to sse_part; n_part: how many it wrote (one per 256-pixel group)
-int fourier_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
+// to sse_part; n_part: how many it wrote (one per 256-pixel group).  sse8_part (sf_eval, with neither train nor pred): the
+// EVAL form, which stores nothing but the two kinds of partials
+int fourier_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part, unsigned long long* sse8_part = nullptr) {
   const int WD = h->WD, D = h->D, MS = h->ff.MS;
   const Chunk k = chunk_at(c, h->npix, h->chunk_px);
   const double npx = (double)k.n_super * kSuper;
-  const FfArgs fa = ff_chunk_args(h, k, pred, sse_part);
+  FfArgs fa = ff_chunk_args(h, k, pred, sse_part);
+  if (sse8_part) fa.sse8_part = sse8_part;
   const double f_hidden = (double)(D - 2) * WD * WD;
   n_part = k.n_super;
   Launch L(h, K_FWD, 2.0 * ((double)MS * WD + f_hidden + 32.0 * WD) * npx,
            npx * (12.0 + (train ? (D - 1) * WD * 2.0 + 6.0 : 0.0)));
-  return launch_ff(h, fa, k.n_super, train ? kFfTrain : kFfEval);
+  return launch_ff(h, fa, k.n_super, sse8_part ? kFfEval8 : train ? kFfTrain : kFfEval);
 }
 
 // The backward of chunk c after its training forward (which ran with the same sse_part and no prediction: the kernels receive

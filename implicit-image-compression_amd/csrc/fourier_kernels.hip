@@ -19,6 +19,8 @@
 //                        dL/dz_out = 2 (s - y) s (1 - s) / (3 H W) (pre-scaled, fp16).  TRAIN spills every ReLU output h_l.
 //                        RENDER (inference only, sf_render / fourier_render.hip): the same chain and sigmoid without
 //                        the target, the residual, dz, the scratch stores and the SSE reduction; fp32 and / or bytes.
+//                        EVAL (sf_eval, BITS = kFfEvalBits): the evaluation form without the prediction store; its SSE
+//                        partial and, beside it, the exact integer partial of the 8-bit figure (eval_sq8).
 //   k_ff_bwd<WD>         data-gradient chain g_{l-1} = (W_l^T g_l) * [h_{l-1} > 0], l = L-1 .. 1, spilling every g_l.
 //   k_ff_dw<NI, E0>      dW_l = g_l h_{l-1}^T and db_l = sum g_l over the workgroup's pixels into a per-workgroup slab
 //                        (E0: layer 0, whose input, the encoding, is recomputed from the coordinates); k_reduce* of
@@ -54,6 +56,7 @@ struct FfArgs {
   union {                             // RENDER only: [npix][3] samples or null (4-byte aligned)
     uint8_t* rgb8;                    //   BITS = 8:  bytes, min(max((int)(pred * 255), 0), 255)
     uint16_t* rgb16;                  //   BITS = 16: native-endian uint16_t, min(max((int)(pred * 65535), 0), 65535)
+    unsigned long long* sse8_part;    // EVAL only, never null: one integer partial (eval_sq8) per workgroup, beside sse_part
   };
   float* sse_part;                    // one partial per workgroup
   float gscale;                       // gpre / (3 H W)
@@ -127,10 +130,15 @@ DEV float ff_block_sum(float v, float* sh) {
   return s;
 }
 
+// EVAL (sf_eval) is the evaluation form with no samples at all, BITS = kFfEvalBits: the kernel has no operand tag to wrap
+// (OpEval), and a further template parameter would rename every existing instantiation
+constexpr int kFfEvalBits = 0;
 template <int WD, bool TRAIN, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
+  constexpr bool EVAL = BITS == kFfEvalBits;
   static_assert(!(TRAIN && RENDER), "the render form spills nothing");
-  static_assert(BITS == 8 || (RENDER && BITS == 16), "BITS: the sample width of the RENDER form, 8 or 16");
+  static_assert(BITS == 8 || (RENDER && BITS == 16) || (EVAL && !TRAIN && !RENDER),
+                "BITS: the sample width of the RENDER form, 8 or 16; kFfEvalBits: the EVAL form");
   constexpr int NT = WD / 32, KS = WD / 16, KSL = ff_ksl(WD);
   extern __shared__ u32x4 lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 31, hh = lane >> 5;
@@ -217,6 +225,28 @@ __global__ __launch_bounds__(kFfThreads) void k_ff_fwd(FfArgs a) {
     // (all 64 lanes: the gather is a cross-lane read.)  pix0 is a multiple of 256: the wave's first pixel is one of 32
     const long px0 = a.pix0 + (long)blockIdx.x * 256 + wave * 32;
     if (a.rgb8) render_store<BITS, 32>(a.rgb8, px0, a.npix, 3, mine, lane);   // (a.rgb16: the same member)
+  } else if constexpr (EVAL) {
+    // the residual and the sum of k_ff_fwd<WD, false> (the same expressions: the same SSE partial), the sigmoid used once
+    // more for the integer partial; no prediction, no dz
+    __shared__ __attribute__((aligned(8))) float sh_sse[2 * (kFfThreads / 64)];   // (then the waves' 64-bit partials)
+    float sse = 0.f;
+    unsigned long long s8 = 0;
+    if (hh == 0 && valid) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const float z = o[0][t];
+        const float sg = 1.0f / (1.0f + __expf(-z));
+        const float tg = a.tgt[p * 3 + t];
+        const float r = sg - tg;
+        // k_ff_fwd<WD, false> forms its sum as r0 * r0, then one fused multiply-add per further channel.  Written out: left
+        // to itself the compiler pairs the three squares here into packed multiplies, which round before the add
+        sse = t == 0 ? r * r : __builtin_fmaf(r, r, sse);
+        s8 += eval_sq8(tg, sg);
+      }
+    }
+    const float s = ff_block_sum(sse, sh_sse);
+    if (threadIdx.x == 0) a.sse_part[blockIdx.x] = s;
+    eval_block_partial<kFfThreads / 64>(s8, sh_sse, a.sse8_part + blockIdx.x);
   } else {
     __shared__ float sh_sse[kFfThreads / 64];
     float sse = 0.f;

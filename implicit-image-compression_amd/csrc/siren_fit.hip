@@ -117,35 +117,37 @@ int refresh_images(sf_engine* h) {
 // The chunk loop of every training / evaluation pass of a SIREN or FourierNet handle (its images are current): per chunk the
 // model's forward and, if train, its backward, the chunks' SSE partials one after the other in h->sse_part; then their
 // fixed-order reduction.  (A WaveletSiren handle runs its two SIREN sub-handles instead: run_pass_wavelet.)
-int run_chunks(sf_engine* h, bool train, float* pred, bool want_sse) {
+int run_chunks(sf_engine* h, bool train, float* pred, bool want_sse, bool eval8) {
   long sse_off = 0;
   for (long c = 0; c < n_chunks(h->npix, h->chunk_px); ++c) {
     float* const part = h->sse_part + sse_off;
+    unsigned long long* const part8 = eval8 ? h->sse8_part + sse_off : nullptr;   // non-null: the EVAL form
     int n_part = 0;
     switch (h->model) {
       case Model::Siren:
-        SF_TRY(h->wide ? wide_fwd_chunk(h, c, train, pred, part, n_part) : siren_fwd_chunk(h, c, train, pred, part, n_part));
+        SF_TRY(h->wide ? wide_fwd_chunk(h, c, train, pred, part, n_part, part8) : siren_fwd_chunk(h, c, train, pred, part, n_part, part8));
         if (train) SF_TRY(h->wide ? wide_bwd_chunk(h, c, part, n_part) : siren_bwd_chunk(h, c, part, n_part));
         break;
       case Model::Fourier:
-        SF_TRY(fourier_fwd_chunk(h, c, train, pred, part, n_part));
+        SF_TRY(fourier_fwd_chunk(h, c, train, pred, part, n_part, part8));
         if (train) SF_TRY(fourier_bwd_chunk(h, c, part));
         break;
       case Model::Wavelet: __builtin_unreachable();   // run_pass
     }
     sse_off += n_part;
   }
+  if (eval8) return launch_eval_reduce(h, sse_off);
   if (want_sse || train) SF_TRY(launch_sse_reduce(h, sse_off));
   return SF_OK;
 }
 
-int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
+int run_pass(sf_engine* h, bool train, float* pred, bool want_sse, bool eval8) {
   if (h->render) return fail(SF_ERR_INVALID, "a render handle (sf_render_create) runs sf_render only");
   if (train) h->fth.fresh = false;
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
   if ((train || want_sse) && !h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
   switch (h->model) {   // the model's own checks, before anything is launched
-    case Model::Wavelet: return run_pass_wavelet(h, train, pred, want_sse);
+    case Model::Wavelet: return run_pass_wavelet(h, train, pred, want_sse, eval8);
     case Model::Fourier:
       if (!h->ff.have_B) return fail(SF_ERR_STATE, "sf_set_encoding has not been called");
       break;
@@ -153,7 +155,7 @@ int run_pass(sf_engine* h, bool train, float* pred, bool want_sse) {
       if (train && (!h->Pbuf || !h->Dbuf)) return fail(SF_ERR_STATE, "the handle has no backward scratch");   // (never a null store on the GPU)
   }
   SF_TRY(refresh_images(h));
-  return run_chunks(h, train, pred, want_sse);
+  return run_chunks(h, train, pred, want_sse, eval8);
 }
 
 int read_sse(sf_engine* h, double* out) {
@@ -277,6 +279,13 @@ int sf_sse_ptr(sf_handle* h, double** p) try {
   return SF_OK;
 } SF_CATCH
 
+int sf_sse8_ptr(sf_handle* h, uint64_t** p) try {
+  if (!h || !p) return fail(SF_ERR_INVALID, "null argument");
+  SF_NO_RENDER(h, "sf_sse8_ptr");
+  *p = reinterpret_cast<uint64_t*>(sse8_dev(h));
+  return SF_OK;
+} SF_CATCH
+
 int sf_debug_scratch(sf_handle* h, int32_t which, void** p, int64_t* bytes) try {
   if (!h || !p || !bytes) return fail(SF_ERR_INVALID, "null argument");
   SF_NO_RENDER(h, "sf_debug_scratch");
@@ -360,6 +369,27 @@ int sf_forward(sf_handle* h, float* pred, double* sse_out) try {
   int rc = run_pass(h, false, pred, want);
   if (rc) return rc;
   if (want) return read_sse(h, sse_out);
+  return SF_OK;
+} SF_CATCH
+
+// eval_epoch's sums in one pass that stores no prediction (include/siren_fit.h): every refusal first, with this entry point's
+// name; then the handle's integer partials (first call), the EVAL forms of the forwards through run_pass, and one copy of the
+// two words behind sse_dev
+int sf_eval(sf_handle* h, double* sse_out, uint64_t* sse8_out) try {
+  if (!h) return fail(SF_ERR_INVALID, "sf_eval: null argument");
+  SF_NO_RENDER(h, "sf_eval");
+  if (!h->have_coords) return fail(SF_ERR_STATE, "sf_eval: sf_set_coords has not been called");
+  if (!h->img) return fail(SF_ERR_STATE, "sf_eval: sf_set_target has not been called");
+  if (h->model == Model::Fourier && !h->ff.have_B) return fail(SF_ERR_STATE, "sf_eval: sf_set_encoding has not been called");
+  DevGuard dev_guard(h->cfg.device);
+  if (!h->sse8_part) SF_TRY(dev_alloc(h, h->sse8_part, (size_t)h->n_sse * 8));   // (before any launch: no EVAL kernel sees a null pointer)
+  SF_TRY(run_pass(h, false, nullptr, true, true));
+  if (!sse_out && !sse8_out) return SF_OK;
+  struct { double sse; uint64_t sse8; } both;   // the two words behind sse_dev: one copy, one synchronise
+  HIPCHK(hipMemcpyAsync(&both, h->sse_dev, sizeof(both), hipMemcpyDeviceToHost, h->ctx->stream));
+  HIPCHK(hipStreamSynchronize(h->ctx->stream));
+  if (sse_out) *sse_out = both.sse;
+  if (sse8_out) *sse8_out = both.sse8;
   return SF_OK;
 } SF_CATCH
 

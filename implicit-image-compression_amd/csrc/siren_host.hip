@@ -30,24 +30,27 @@ bool fwd_is_pipe(const sf_engine* h) { return h->WD == 256 && h->D >= 3 && !h->w
 int fwd_grid(const sf_engine* h, int n_super) { return fwd_is_pipe(h) && n_super > h->dw_wg ? h->dw_wg : n_super; }
 
 // hidden = 256, depth >= 3: the hand-scheduled software pipeline over all layers (k_fwd_pipe)
-int launch_fwd_pipe(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
+int launch_fwd_pipe(sf_engine* h, const FwdArgs& a, int n_wg, bool train, bool eval8) {
   const size_t lds = fwd_pipe_lds_bytes();
   const bool f16 = h->cfg.compute_dtype == SF_F16;
   if (f16 && train && h->s8) return launch(h, k_fwd_pipe<OpF16, true, true>, n_wg, 512, lds, a);
   return with_op(h, [&](auto op) {
     using OP = decltype(op);
+    if (eval8) return launch(h, k_fwd_pipe<OpEval<OP>, false, false>, n_wg, 512, lds, a);
     return train ? launch(h, k_fwd_pipe<OP, true, false>, n_wg, 512, lds, a) : launch(h, k_fwd_pipe<OP, false, false>, n_wg, 512, lds, a);
   });
 }
-// the forward of a chunk on n_wg workgroups (fwd_grid): phase bytes (fp16 operands only), training or evaluation form
-int launch_fwd(sf_engine* h, const FwdArgs& a, int n_wg, bool train) {
-  if (fwd_is_pipe(h)) return launch_fwd_pipe(h, a, n_wg, train);
+// the forward of a chunk on n_wg workgroups (fwd_grid): phase bytes (fp16 operands only), training or evaluation form;
+// eval8 (never with train): the EVAL form, a.sse8_part set
+int launch_fwd(sf_engine* h, const FwdArgs& a, int n_wg, bool train, bool eval8 = false) {
+  if (fwd_is_pipe(h)) return launch_fwd_pipe(h, a, n_wg, train, eval8);
   return with_width(h, [&](auto wd) {
     constexpr int WD = decltype(wd)::value;
     const size_t lds = fwd_lds_bytes(WD);
     if (h->cfg.compute_dtype == SF_F16 && train && h->s8) return launch(h, k_fwd<WD, OpF16, true, true>, n_wg, 512, lds, a);
     return with_op(h, [&](auto op) {
       using OP = decltype(op);
+      if (eval8) return launch(h, k_fwd<WD, OpEval<OP>, false>, n_wg, 512, lds, a);
       return train ? launch(h, k_fwd<WD, OP, true>, n_wg, 512, lds, a) : launch(h, k_fwd<WD, OP, false>, n_wg, 512, lds, a);
     });
   });
@@ -170,8 +173,9 @@ int refresh_images_siren(sf_engine* h) {
 }
 
 // The forward of chunk c of a SIREN handle of width <= 256, training or evaluation form (k_fwd / k_fwd_pipe): the prediction
-// to pred (or null), the chunk's SSE partials to sse_part; n_part: how many it wrote (fwd_grid)
-int siren_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
+// to pred (or null), the chunk's SSE partials to sse_part; n_part: how many it wrote (fwd_grid).  sse8_part (sf_eval, with
+// neither train nor pred): the EVAL form, which stores nothing but the two kinds of partials
+int siren_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part, unsigned long long* sse8_part = nullptr) {
   const int WD = h->WD, D = h->D;
   const Chunk k = chunk_at(c, h->npix, h->chunk_px);
   const double npx = k.n_pb * 32.0;
@@ -182,10 +186,11 @@ int siren_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_pa
   fa.gscale = h->d8 ? kResScale : gscale(h);
   fa.pred = pred;
   fa.sse_part = sse_part;
+  if (sse8_part) fa.sse8_part = sse8_part;
   n_part = fwd_grid(h, k.n_super);
   Launch L(h, K_FWD, flops_fwd_px(h) * npx,
            npx * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
-  return launch_fwd(h, fa, n_part, train);
+  return launch_fwd(h, fa, n_part, train, sse8_part != nullptr);
 }
 
 // The backward of chunk c after its training forward: k_bwd(last) -> k_bwd(hidden l = depth-2 .. 1) -> k_dw0, each followed by

@@ -75,6 +75,44 @@ struct OpF16 {
   }
 };
 
+// EVAL form of a forward kernel (sf_eval): its operand tag wrapped in OpEval.  The arithmetic is the tag's (OpEval<OP> is an
+// OP); the kernel takes the evaluation-only epilogue - no prediction, phase, delta or dL/dout store, the SSE partial of the
+// TRAIN = false form and, beside it, the exact integer partial of the 8-bit figure (fwd_residual_eval, eval_block_partial).
+// A tag and not one more template parameter: the existing instantiations keep their names and their device code.
+template <typename OP>
+struct OpEval : OP {};
+template <typename OP>
+struct IsEval : std::false_type {};
+template <typename OP>
+struct IsEval<OpEval<OP>> : std::true_type {};
+
+// one value of eval_epoch's 8-bit error (train_helper.py: (img * 255).int() - (pred * 255).int(), squared): the products in
+// fp32, truncated toward zero (v_cvt_i32_f32), NOT clamped - this is not render_quant.  The difference and its square are
+// formed in 64 bits, so nothing overflows whatever the prediction is
+DEV unsigned long long eval_sq8(float t, float p) {
+  const long long d = (long long)(int)(t * 255.0f) - (long long)(int)(p * 255.0f);
+  return (unsigned long long)(d * d);
+}
+// The integer partial of a workgroup of NW waves, after its SSE partial: lanes by xor-shuffle, then the waves through the
+// NW floats at sRed (NW <= 8 there: 64 bytes, 8-byte aligned), which the SSE reduction has finished with after the barrier.
+// Integer addition is associative: any order gives the same sum.  Called by every thread of the workgroup
+template <int NW>
+DEV void eval_block_partial(unsigned long long s8, float* sRed, unsigned long long* dst) {
+  static_assert(NW <= 8, "the LDS of the SSE partials holds eight 64-bit words");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s8 += __shfl_xor(s8, o);
+  unsigned long long* sRed8 = reinterpret_cast<unsigned long long*>(sRed);
+  __syncthreads();   // thread 0 has read the float partials
+  if (lane == 0) sRed8[wave] = s8;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < NW; ++w) t += sRed8[w];
+    *dst = t;
+  }
+}
+
 // streaming store of one 16-byte piece element (scratch tensors are written once and read once much later)
 DEV void store_stream(u32x4* p, u32x4 v) {
   *p = v;
@@ -255,6 +293,7 @@ struct FwdArgs {
   union {                  // RENDER kernels only, optional [npix][nout] samples (4-byte aligned base):
     uint8_t* rgb8;         //   BITS = 8:  bytes, min(max((int)(pred * 255), 0), 255)
     uint16_t* rgb16;       //   BITS = 16: native-endian uint16_t, min(max((int)(pred * 65535), 0), 65535)
+    unsigned long long* sse8_part;   // EVAL kernels only, never null: [gridDim.x] per-workgroup sum of eval_sq8 (same index as sse_part)
   };
 };
 
@@ -338,6 +377,26 @@ DEV void fwd_sse_partial(const FwdArgs& a, float sse, int lane, int wave, int ti
   }
 }
 
+// EVAL forms: last-layer accumulator -> this lane's squared residual (returned: the expressions of fwd_residual, so the SSE
+// is the TRAIN = false form's bit for bit) and, into s8, its eval_sq8 values - the prediction formed once for both.  Nothing
+// is stored.  Padded tile rows (c >= nout), the upper lane half and pixels beyond npix add nothing
+DEV float fwd_residual_eval(const FwdArgs& a, const f32x16& acc, const float (&tgt)[3], bool valid, int h, unsigned long long& s8) {
+  float sse = 0.f;
+  if (h == 0 && valid) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (c >= a.nout) break;
+      float o = acc[c] * a.sc_last;
+      if (a.last_om_rev != 0.f) o = __builtin_amdgcn_sinf(o * a.last_om_rev);
+      const float p = o * 0.5f + 0.5f;  // siren.py:131
+      const float r = p - tgt[c];
+      sse += r * r;
+      s8 += eval_sq8(tgt[c], p);
+    }
+  }
+  return sse;
+}
+
 // last-layer accumulator -> fp32 prediction and / or packed samples of one pixel block (siren_render.hip): the epilogue of the
 // RENDER instantiations, which read no target and write no phases, no dL/dout and no SSE partial.  BITS: 8 (a.rgb8) or 16
 // (a.rgb16) bits per sample
@@ -347,7 +406,9 @@ DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, 
 // RENDER (inference only, sf_render / sf_render16): TRAIN = false with fwd_render_out<BITS> in place of the residual epilogue
 template <int WD, typename OP, bool TRAIN, bool S8 = false, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
+  constexpr bool EVAL = IsEval<OP>::value;   // sf_eval: see OpEval
   static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
+  static_assert(!EVAL || (!TRAIN && !S8 && !RENDER), "EVAL is an evaluation form, and not the RENDER one");
   static_assert(BITS == 8 || (RENDER && BITS == 16), "BITS: the sample width of a RENDER form, 8 or 16");
   using IM = FwdImg<WD>;
   constexpr int NT = IM::NT, KS = IM::KS, H0 = IM::H0;
@@ -490,6 +551,10 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
   if constexpr (RENDER) {
     fwd_render_out<BITS>(a, acc, pix, pb, valid, lane, h);
     (void)sRed;
+  } else if constexpr (EVAL) {
+    unsigned long long s8 = 0;
+    fwd_sse_partial(a, fwd_residual_eval(a, acc, tgt, valid, h, s8), lane, wave, tid, sRed);
+    eval_block_partial<kWavesFwd>(s8, sRed, a.sse8_part + blockIdx.x);
   } else {
     fwd_sse_partial(a, fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h), lane, wave, tid, sRed);
   }
@@ -539,7 +604,9 @@ constexpr int kFwdPD = 4;   // k_fwd_pipe: slots a weight fragment is read ahead
 template <typename OP, bool TRAIN, bool S8, bool RENDER = false, int BITS = 8>
 __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
   constexpr int PD = kFwdPD;
+  constexpr bool EVAL = IsEval<OP>::value;   // sf_eval: see OpEval
   static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
+  static_assert(!EVAL || (!TRAIN && !S8 && !RENDER), "EVAL is an evaluation form, and not the RENDER one");
   static_assert(BITS == 8 || (RENDER && BITS == 16), "BITS: the sample width of a RENDER form, 8 or 16");
   constexpr int WD = 256;
   using IM = FwdImg<WD>;
@@ -595,6 +662,7 @@ __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
   };
   Fetch nxt_f = fetch((int)blockIdx.x);
   float sse_acc = 0.f;
+  [[maybe_unused]] unsigned long long s8_acc = 0;   // EVAL: this lane's integer sum over every group the workgroup walks (64 bits: no image overflows it)
   bar_dma<0>();                                   // layer-0 image staged (and the first group's fetch has landed)
 
   // Explicit LDS addressing: five per-lane base registers, everything else is the 16-bit immediate of the read.  (Left
@@ -815,9 +883,11 @@ __global__ __launch_bounds__(512) void k_fwd_pipe(FwdArgs a) {
       output_layer(Ba);
     }
     if constexpr (RENDER) fwd_render_out<BITS>(a, acc, pix, pb, valid, lane, h);
+    else if constexpr (EVAL) sse_acc += fwd_residual_eval(a, acc, tgt, valid, h, s8_acc);
     else sse_acc += fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h);
   }
   if constexpr (!RENDER) fwd_sse_partial(a, sse_acc, lane, wave, tid, sRed);
+  if constexpr (EVAL) eval_block_partial<kWavesFwd>(s8_acc, sRed, a.sse8_part + blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1462,6 +1532,24 @@ __global__ void k_sse_reduce(const float* part, int n, double* out, double* loss
     *out = sh[0];
     if (loss_tab) loss_tab[*iter] = sh[0];
   }
+}
+
+// sf_eval: k_sse_reduce's sum of the SSE partials (the same operations in the same order: the same double) and, beside it,
+// the sum of the integer partials of the EVAL forms.  out8 is the word behind *out
+__global__ void k_eval_reduce(const float* part, const unsigned long long* part8, int n, double* out, unsigned long long* out8) {
+  __shared__ double sh[256];
+  __shared__ unsigned long long sh8[256];
+  double s = 0.0;
+  unsigned long long s8 = 0;
+  for (int i = threadIdx.x; i < n; i += 256) { s += (double)part[i]; s8 += part8[i]; }
+  sh[threadIdx.x] = s;
+  sh8[threadIdx.x] = s8;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { sh[threadIdx.x] += sh[threadIdx.x + o]; sh8[threadIdx.x] += sh8[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { *out = sh[0]; *out8 = sh8[0]; }
 }
 
 // graph replay mode: advances the device-side step index once per replayed step (last node of the graph)

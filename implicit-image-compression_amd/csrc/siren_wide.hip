@@ -157,6 +157,7 @@ struct WGemmArgs {
   union {                // k_wgemm RENDER only, optional [npix][nout] samples (4-byte aligned base), as FwdArgs:
     uint8_t* rgb8;       //   BITS = 8
     uint16_t* rgb16;     //   BITS = 16
+    unsigned long long* sse8_part;   // k_wgemm EVAL only, never null: [n_super] integer partials, as FwdArgs
   };
 };
 
@@ -275,6 +276,22 @@ __global__ __launch_bounds__(512) void k_wgemm(WGemmArgs a) {
     fa.sc_last = a.sc; fa.last_om_rev = a.last_om_rev; fa.nout = a.nout; fa.pred = a.pred; fa.rgb8 = a.rgb8;
     fa.pix0 = a.pix0; fa.npix = a.npix;
     fwd_render_out<BITS>(fa, acc[0][0], pix, pb0, valid, lane, h);
+  } else if constexpr (IsEval<OP>::value) {   // sf_eval (OpEval): the two partials of super-block sb, nothing else
+    static_assert(!RENDER, "EVAL is not the RENDER form");
+    FwdArgs fa = {};      // fwd_residual_eval's view of this kernel's arguments: the one epilogue of every SIREN EVAL kernel
+    fa.sc_last = a.sc; fa.last_om_rev = a.last_om_rev; fa.nout = a.nout;
+    unsigned long long s8 = 0;
+    float sse = fwd_residual_eval(fa, acc[0][0], tgt, valid, h, s8);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sse += __shfl_xor(sse, o);
+    if (lane == 0) sRed[wave] = sse;
+    __syncthreads();
+    if (tid == 0) {
+      float t = 0.f;
+      for (int w = 0; w < kWavesFwd; ++w) t += sRed[w];
+      a.sse_part[sb] = t;
+    }
+    eval_block_partial<kWavesFwd>(s8, sRed, a.sse8_part + sb);
   } else {
     float sse = 0.f, d[3] = {0.f, 0.f, 0.f};
     if (h == 0 && valid) {

@@ -22,7 +22,9 @@ int refresh_images_wavelet(sf_engine* h) {
 // The sub-networks run through the SIREN chunk functions (siren_host.hip) and, for the inference forwards, the chunk loop; they
 // launch through this handle's context, their weight images are refreshed here with this handle's, and the SSE partials
 // their forwards write (they have no target: nothing reads them) go to the start of their own sse_part.
-int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
+// eval8 (sf_eval): the sub-network forwards of an evaluation, then k_wv_compose_eval - no picture is written - and the
+// reduction of both kinds of partials.
+int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse, bool eval8) {
   SF_TRY(refresh_images(h));
   sf_engine* const sub[2] = {h->wv.sub[0], h->wv.sub[1]};
   const long nn = sub[0]->npix, HH = h->npix;
@@ -44,8 +46,10 @@ int run_pass_wavelet(sf_engine* h, bool train, float* pred, bool want_sse) {
   const unsigned n_cwg = wv_grid(HH);
   {
     Launch L(h, K_WV_COMPOSE, 0, (double)HH * 4.0 * (3.0 + (a.img ? 3.0 : 0.0) + (pred ? 3.0 : 0.0) + (train ? 3.0 : 0.0)));
-    SF_TRY(launch(h, k_wv_compose, n_cwg, kWvThreads, 0, a));
+    if (eval8) SF_TRY(launch(h, k_wv_compose_eval, n_cwg, kWvThreads, 0, a, h->sse8_part));
+    else SF_TRY(launch(h, k_wv_compose, n_cwg, kWvThreads, 0, a));
   }
+  if (eval8) return launch_eval_reduce(h, n_cwg);
   if (train) {
     if (one) { a.dl_lf = sub[0]->Dlast; a.dl_hf = sub[1]->Dlast; }
     else { a.gl_lf = h->wv.gl; a.gl_hf = h->wv.gl + nn * 3; }

@@ -12,6 +12,8 @@
 //
 //   k_wv_compose   one thread per output pixel: prediction, residual, per-workgroup SSE partial and the image-space
 //                  gradient dL/d(Y, Cb, Cr) (the colour transform's adjoint folded in)
+//   k_wv_compose_eval  (sf_eval) the same pixel body with no prediction and no gradient store: the SSE partial and the
+//                  exact integer partial of the 8-bit figure
 //   k_wv_adjoint   one thread per coefficient (i, j): transposed synthesis taps over dL/dY, transposed bilinear
 //                  footprint over dL/dCb, dL/dCr; the result times 1/2 (p = z/2 + 1/2) times the sub-networks' fp16
 //                  pre-scale goes straight into each sub-network's dL/dout (Dlast, F-layout) or, when the coefficient
@@ -175,6 +177,34 @@ __global__ __launch_bounds__(kWvThreads) void k_wv_compose(WvArgs a) {
     for (int w = 0; w < kWvThreads / 64; ++w) t += sRed[w];
     a.sse_part[blockIdx.x] = t;
   }
+}
+
+// The EVAL form of k_wv_compose (sf_eval): the same compiled pixel body with no prediction and no gradient store, its SSE
+// partial in the same order, and beside it the workgroup's integer partial of the 8-bit figure (eval_sq8 of the composed RGB
+// the body returns, siren_kernels.hip).  A kernel of its own and not a template argument: k_wv_compose keeps its name
+__global__ __launch_bounds__(kWvThreads) void k_wv_compose_eval(WvArgs a, unsigned long long* sse8_part) {
+  __shared__ __attribute__((aligned(8))) float sRed[2 * (kWvThreads / 64)];   // (then the waves' 64-bit partials)
+  const long p = (long)blockIdx.x * kWvThreads + threadIdx.x;
+  const int H = a.H, n = a.n;
+  float sse = 0.f;
+  unsigned long long s8 = 0;
+  if (p < (long)H * H) {
+    const int r = (int)(p / H), c = (int)(p - (long)r * H);
+    const WvPixel px = wv_compose_pixel(a.lf, a.hf, a.img, nullptr, nullptr, a.gscale, p, r, c, n, a.up, 0, 0, n);
+    sse = px.sse;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s8 += eval_sq8(a.img[p * 3 + k], px.rgb[k]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sse += __shfl_xor(sse, o);
+  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = sse;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int w = 0; w < kWvThreads / 64; ++w) t += sRed[w];
+    a.sse_part[blockIdx.x] = t;
+  }
+  eval_block_partial<kWvThreads / 64>(s8, sRed, sse8_part + blockIdx.x);
 }
 
 // dL/dout of one coefficient into a sub-network's Dlast: lane m of k-step 0 of block q / 32 (neurons 0..2 of lane half 0);

@@ -48,9 +48,10 @@ unsigned wgemm_grid(const sf_engine* h, int n_ob, unsigned tiles) {
   const unsigned pg = (unsigned)(h->dw_wg / (8 * n_ob) * (8 * n_ob));
   return pg == 0 || pg > tiles ? tiles : pg;
 }
-// (render_bits: 0, or the sample width of a render handle's launch - the RENDER forms of MODE 0 and 1)
+// (render_bits: 0, or the sample width of a render handle's launch - the RENDER forms of MODE 0 and 1; eval8: the EVAL form
+// of MODE 1, a.sse8_part set)
 template <int MODE>
-int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob, int render_bits = 0) {
+int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob, int render_bits = 0, bool eval8 = false) {
   WGemmArgs b = a;
   b.n_super = n_super; b.n_ob = n_ob;
   const unsigned grid = (unsigned)((n_super + 7) / 8 * 8 * n_ob);
@@ -60,6 +61,7 @@ int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob, int re
         constexpr int BITS = decltype(wide)::value ? 16 : 8;
         return with_op(h, [&](auto op) { return launch(h, k_wgemm<decltype(op), true, BITS>, grid, 512, WGemmLds::bytes, b); });
       });
+    if (eval8) return with_op(h, [&](auto op) { return launch(h, k_wgemm<OpEval<decltype(op)>>, grid, 512, WGemmLds::bytes, b); });
     return with_op(h, [&](auto op) { return launch(h, k_wgemm<decltype(op)>, grid, 512, WGemmLds::bytes, b); });
   } else {
     if constexpr (MODE == 0) {
@@ -85,7 +87,7 @@ int launch_wgemm(sf_engine* h, const WGemmArgs& a, int n_super, int n_ob, int re
 
 // What the last layer of a wide forward walk writes: the prediction (or null) and either the training / evaluation outputs -
 // the chunk's SSE partials and, if train, dL/dout - or samples of `bits` bits at `samples` (or null)
-struct WideOut { float* pred; float* sse_part; bool train; void* samples; int bits; };
+struct WideOut { float* pred; float* sse_part; bool train; void* samples; int bits; unsigned long long* sse8_part = nullptr; };
 
 // The forward walk of chunk k, layer at a time: k_wlayer0, k_wgemm2<0> per hidden layer, k_wgemm.  o.bits = 0: the training /
 // evaluation forms under K_FWD - layer l writes its own phase and activation planes.  o.bits = 8 / 16: the RENDER forms
@@ -138,19 +140,20 @@ int wide_fwd_walk(sf_engine* h, const Chunk& k, const WideOut& o) {
   } else {
     a.img = h->img; a.gscale = gscale(h);
     a.sse_part = o.sse_part; a.Dlast = o.train ? h->Dlast : nullptr;
+    if (o.sse8_part) a.sse8_part = o.sse8_part;   // the EVAL form of k_wgemm
     if (!h->cfg.outermost_linear) a.last_om = h->cfg.hidden_omega_0;
   }
   const double out_bytes = render ? h->cfg.out_features * render_sample_bytes(o.samples, o.bits, o.pred) : 12.0 + 64.0;
   Launch L(h, id, 2.0 * h->cfg.out_features * WD * npx, npx * (WD * 2.0 + out_bytes));
-  return launch_wgemm<1>(h, a, n_super, 1, o.bits);
+  return launch_wgemm<1>(h, a, n_super, 1, o.bits, o.sse8_part != nullptr);
 }
 
 // The forward of chunk c, training or evaluation form: the prediction to pred (or null), the chunk's SSE partials to sse_part;
 // n_part: how many it wrote (one per 256-pixel group)
-int wide_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part) {
+int wide_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part, unsigned long long* sse8_part = nullptr) {
   const Chunk k = chunk_at(c, h->npix, h->chunk_px);
   n_part = k.n_super;
-  return wide_fwd_walk(h, k, {pred, sse_part, train, nullptr, 0});
+  return wide_fwd_walk(h, k, {pred, sse_part, train, nullptr, 0, sse8_part});
 }
 
 // The render loop of a wide render handle (sf_wide_render_create; its images are current): every chunk's RENDER walk, to pred

@@ -187,6 +187,12 @@ _declare("core", {
     "sf_quant_nudge": [H, P(sf_quant_args)],
     "sf_quant_step": [H, P(sf_quant_args), P(C.c_float), I32, P(C.c_float)],
 })
+# (eval_epoch's three figures on the device, sf_eval in csrc/siren_fit.hip.  In "core" like sf_quant_step: has_eval asks for the
+# symbols themselves, train_helper.eval_metrics routes by it)
+_declare("core", {
+    "sf_eval": [H, P(C.c_double), P(C.c_uint64)],
+    "sf_sse8_ptr": [H, P(C.c_void_p)],
+})
 
 
 def load_library():
@@ -268,6 +274,11 @@ def has_mask_update_snfs(lib) -> bool:
 def has_quant_step(lib) -> bool:
     """sf_quant_pass / sf_quant_nudge / sf_quant_step: the quantise phase on the device (csrc/siren_quant.hip)"""
     return all(hasattr(lib, n) for n in ("sf_quant_pass", "sf_quant_nudge", "sf_quant_step"))
+
+
+def has_eval(lib) -> bool:
+    """sf_eval / sf_sse8_ptr: the sums of an evaluation on the device, no prediction written (csrc/siren_fit.hip)"""
+    return all(hasattr(lib, n) for n in ("sf_eval", "sf_sse8_ptr"))
 
 
 def _require(lib, has, entry: str, since: str):
@@ -420,6 +431,11 @@ class SirenEngine:
     def sse_view(self) -> torch.Tensor:
         """1-element float64 view of the device scalar the last pass wrote its sum of squared residuals to."""
         return self._view("sse", self.lib.sf_sse_ptr, n=1, typestr="<f8")
+
+    def sse8_view(self) -> torch.Tensor:
+        """1-element int64 view of the device word the last eval_sums() wrote its integer sum to."""
+        _require(self.lib, has_eval, "sf_sse8_ptr entry point", "the device evaluation")
+        return self._view("sse8", self.lib.sf_sse8_ptr, n=1, typestr="<i8")
 
     def debug_scratch(self, which: str) -> torch.Tensor:
         """uint8 view of an engine scratch tensor of the last pass: phases | deltas | dlast | slabs (tests only)."""
@@ -579,6 +595,15 @@ class SirenEngine:
         _check(self.lib.sf_forward(self.h, pred.data_ptr() if want_pred else None,
                                    C.byref(sse) if want_sse else None))
         return pred, (sse.value if want_sse else None)
+
+    def eval_sums(self, sync: bool = True):
+        """sf_eval: one evaluation pass that writes no prediction.  (sse, sse8): the double forward() reports and the exact
+        sum of ((img * 255).int() - (pred * 255).int()) ** 2 over this handle's rows, read with one copy.  sync=False: the
+        pass is enqueued and nothing is read - (None, None); the sums are in sse_view() / sse8_view()."""
+        _require(self.lib, has_eval, "sf_eval entry point", "the device evaluation")
+        sse, sse8 = C.c_double(), C.c_uint64()
+        _check(self.lib.sf_eval(self.h, C.byref(sse) if sync else None, C.byref(sse8) if sync else None))
+        return (sse.value, sse8.value) if sync else (None, None)
 
     def forward_backward(self, sync: bool = True) -> Optional[float]:
         sse = C.c_double()

@@ -26,8 +26,8 @@ from .pipeline import entropy_coding
 from .pipeline.feathermap import FeatherNet
 from .pipeline.feathermap.feathernet import DEEPCOPY_UNSUPPORTED
 from .pipeline.quant import Quantize
-from .utils.train_helper import (eval_epoch, get_device, get_optimizer_lr_scheduler, setup_mask, train_epoch,
-                                 train_steps)
+from .utils.train_helper import (device_eval_wanted, eval_epoch, eval_metrics, get_device, get_optimizer_lr_scheduler,
+                                 setup_mask, train_epoch, train_steps)
 
 REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 
@@ -64,6 +64,13 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
         if mcfg.get("interval"):
             mcfg.interval = int(mcfg.interval * mult)
     mask = setup_mask(model, optim, mcfg)                                          # compress.py:127
+    # the three figures of an evaluation; the prediction eval_epoch returns is not used here.  train.device_eval auto: sf_eval
+    # (no picture stored, one read), off: eval_epoch.  Same loss and PSNR; PSNR_8bit exact instead of torch's fp32 mean
+    if device_eval_wanted(cfg.train.get("device_eval", "auto")):
+        evaluate = eval_metrics
+    else:
+        def evaluate(m, g, im):
+            return eval_epoch(m, g, im)[1:]
     t0, last = time.time(), {}
     i = -1
     while i + 1 < num_steps:                                                       # compress.py:137-170
@@ -78,7 +85,7 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
         if mask and i <= mcfg.end_when and i % mcfg.interval == 0:
             mask.update_connections()
         if (i + 1) % cfg.train.log_steps == 0 or i + 1 == num_steps:
-            _, loss, psnr, psnr8 = eval_epoch(model, grid, img)
+            loss, psnr, psnr8 = evaluate(model, grid, img)
             last = {"loss": loss, "PSNR": psnr, "PSNR_8bit": psnr8}
             msg = f"Train | Step: {i + 1} | " + " | ".join(f"{k}: {v:.4f}" for k, v in last.items())
             if mask:
@@ -112,10 +119,10 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
                 i = min(first + qcfg.log_steps - 1 - first % qcfg.log_steps, qcfg.num_steps - 1)
                 train_steps(quantized_model, q_optim, grid, img, i - first + 1, lr_scheduler=q_sched)
                 if (i + 1) % qcfg.log_steps == 0:
-                    _, l, p, p8 = eval_epoch(quantized_model, grid, img)
+                    l, p, p8 = evaluate(quantized_model, grid, img)
                     logging.info(f"Quant | Step: {i + 1} | loss: {l:.4f} | PSNR: {p:.4f} | PSNR_8bit: {p8:.4f}")
         quantized_model = q.convert()
-        _, l, p, p8 = eval_epoch(quantized_model, grid, img)
+        l, p, p8 = evaluate(quantized_model, grid, img)
         last.update({"Quant loss": l, "Quant PSNR": p, "Quant PSNR 8bit": p8})
         if mask is not None:      # what fraction of the masked layers' weights the saved artefact really holds at zero
             zeros = sum(int((w == 0).sum().item()) for n, w in quantized_model.named_parameters() if n in mask.mask_dict)

@@ -2,6 +2,7 @@
 
   train_epoch(model, optim, grid, img, **kwargs) -> float          (:132-185)
   eval_epoch(model, grid, img, **kwargs) -> (pred, loss, PSNR, PSNR_8bit)   (:41-59)
+  eval_metrics(model, grid, img) -> (loss, PSNR, PSNR_8bit)       eval_epoch's figures without its prediction (sf_eval)
   get_optimizer_lr_scheduler(model, optim_cfg, quantize_mode=False)  (:69-86)
   setup_mask(model, optim, masking_cfg)                               (:89-129)
   get_device(device_str)                                               (:62-66)
@@ -17,6 +18,7 @@ import torch
 from torch.nn import Module, functional as F
 from torch.optim import Optimizer
 
+from .. import _engine
 from ..pipeline.masking import Masking, decay_registry
 from ..pipeline.quant.kmeans import KmeansQuant
 
@@ -259,3 +261,30 @@ def eval_epoch(model: Module, grid, img, **kwargs) -> Tuple[torch.Tensor, float,
     mse_8bit = ((img_8bit - pred_8bit) ** 2).float().mean()
     test_PSNR_8bit = 10 * torch.log10(255 ** 2 / mse_8bit)
     return pred, test_loss, test_PSNR, test_PSNR_8bit.item()
+
+
+def device_eval_wanted(setting) -> bool:
+    """train.device_eval (conf/config.yaml): 'auto' -> True, 'off' -> False.  A bare `off` arrives as YAML's false."""
+    text = {False: "off", True: "auto", None: "auto"}.get(setting, setting)
+    if text not in ("auto", "off"):
+        raise ValueError(f"train.device_eval: 'auto' (sf_eval where the handle has it) or 'off', got {setting!r}")
+    return text == "auto"
+
+
+@torch.no_grad()
+def eval_metrics(model: Module, grid, img) -> Tuple[float, float, float]:
+    """(loss, PSNR, PSNR_8bit) of eval_epoch without its prediction: one sf_eval pass (eng.eval_sums()) whose kernels store
+    no picture, no torch arithmetic, no torch allocation, one read.  loss and PSNR are eval_epoch's floats (the same double
+    from the same partials in the same order).  PSNR_8bit is 10 log10(255^2 / (sse8 / n)) in Python doubles from the exact
+    integer sum, where eval_epoch takes torch's fp32 mean and fp32 log10: the two agree to about 1e-5 dB.
+    A library or a handle class without the entry point: eval_epoch(...)[1:]."""
+    model.eval()
+    eng = model.engine(grid, img)             # (as eval_epoch: the pre-pass callbacks of a quantise phase run here)
+    if not (callable(getattr(eng, "eval_sums", None)) and _engine.has_eval(eng.lib)):
+        return eval_epoch(model, grid, img)[1:]
+    sse, sse8 = eng.eval_sums()
+    n = img.numel()
+    test_loss = sse / n
+    test_PSNR = 10 * math.log10(1 / test_loss)
+    test_PSNR_8bit = 10 * math.log10(255 ** 2 / (sse8 / n)) if sse8 else math.inf
+    return test_loss, test_PSNR, test_PSNR_8bit

@@ -414,6 +414,23 @@ int sf_set_target(sf_handle* h, const float* img_dev /*[(row_end-row_begin)*widt
 /* forward only (eval_epoch): pred_dev may be NULL; sse_out (host) = sum of squared residuals over
  * this handle's rows (double), NULL = do not synchronise */
 int sf_forward(sf_handle* h, float* pred_dev, double* sse_out);
+/* one evaluation pass over the handle's rows: no prediction is written.  *sse_out: the double sf_forward reports, bit for
+ * bit.  *sse8_out: sum over the handle's pixels and channels of ((int)(255 t) - (int)(255 p))^2, exact.  Both NULL: the pass is
+ * enqueued and nothing is read; the sums stay where sf_sse_ptr / sf_sse8_ptr point.  Otherwise ONE copy and ONE synchronise.
+ *   - t: the fp32 target, p: the fp32 prediction sf_forward would store; the products in fp32, truncated toward zero and NOT
+ *     clamped - eval_epoch's (x * 255).int() (train_helper.py), not the samples of sf_render.  The squares are summed in
+ *     64-bit integers (per lane, per workgroup, then one fixed-order reduction), so the sum is exact and deterministic;
+ *   - the pass runs the EVAL forms of the forward kernels: they store the two kinds of per-workgroup partials and nothing
+ *     else (the sub-network forwards of a WaveletSiren handle still fill its coefficient predictions, as sf_forward's do).
+ *     The integer partials live in a buffer of the handle, allocated at the first call;
+ *   - every training handle takes it: SIREN of every width (with Feathermap attached, with a pixel-split row range),
+ *     FourierNet, WaveletSiren.  Parameters, gradients, moments, masks and what a following sf_step computes are untouched;
+ *   - refused before anything is allocated or launched, "sf_eval" in the message: a null handle (SF_ERR_INVALID, no GPU
+ *     touched), a render handle (SF_ERR_INVALID), no coordinates, no target, FourierNet without sf_set_encoding
+ *     (SF_ERR_STATE).
+ * sf_sse8_ptr: device address of the integer sum the last sf_eval wrote (the word behind sf_sse_ptr's double). */
+int sf_eval(sf_handle* h, double* sse_out, uint64_t* sse8_out);
+int sf_sse8_ptr(sf_handle* h, uint64_t** dev_ptr);
 /* forward + loss + backward: leaves the dense gradient (already scaled by 1/(3*H*W)) in the
  * engine; sse_out as above */
 int sf_forward_backward(sf_handle* h, double* sse_out);
