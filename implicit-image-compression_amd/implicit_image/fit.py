@@ -6,34 +6,93 @@ Reads conf/ (implicit_image/config.py), builds the registry model, fits with tra
 update_connections / eval_epoch exactly in the reference's order, logs loss / PSNR / PSNR_8bit,
 and saves `model.pth` (fp32 state_dict with the reference's parameter names) in the run directory.
 Comma sweeps expand to a job list; under torch.distributed.run the jobs are sharded over ranks
-(per-image sharding: one fit per GPU, no collectives).
+(per-image sharding: one fit per GPU, no collectives).  With train.pixel_split=true every rank runs every job and fits its
+rows of the one picture (pixel-split: gradient, SSE and evaluation sums all-reduced; rank 0 writes).
 """
+import contextlib
 import copy
 import json
 import logging
 import os
 import sys
+import tempfile
 import time
 
+import numpy as np
 import torch
 
 from .config import Cfg, expand_sweeps, load_config
 from .data import get_grid, load_img
 from .models import registry as model_registry
-from .models.wavelet_siren import check_image as check_wavelet_image
-from .parallel import shard_jobs
+from .models.fourier import PIXEL_SPLIT_UNSUPPORTED as FOURIER_SPLIT_UNSUPPORTED
+from .models.siren import Siren, next_kernel_width
+from .models.wavelet_siren import PIXEL_SPLIT_UNSUPPORTED as WAVELET_SPLIT_UNSUPPORTED, check_image as check_wavelet_image
+from .parallel import SPLIT_BACKENDS, RowSplit, init_split_group, shard_jobs
 from .pipeline import entropy_coding
 from .pipeline.feathermap import FeatherNet
-from .pipeline.feathermap.feathernet import DEEPCOPY_UNSUPPORTED
+from .pipeline.feathermap.feathernet import DEEPCOPY_UNSUPPORTED, PIXEL_SPLIT_UNSUPPORTED as FEATHER_SPLIT_UNSUPPORTED
 from .pipeline.quant import Quantize
-from .utils.train_helper import (device_eval_wanted, eval_epoch, eval_metrics, get_device, get_optimizer_lr_scheduler,
-                                 setup_mask, train_epoch, train_steps)
+from .utils.train_helper import (SPLIT_EVAL_EPOCH_UNSUPPORTED, SPLIT_PADDED_UNSUPPORTED, device_eval_wanted, eval_epoch,
+                                 eval_metrics, get_device, get_optimizer_lr_scheduler, setup_mask, train_epoch, train_steps)
 
 REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 
 
-def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
-    """One fit; returns dict(loss, PSNR, PSNR_8bit, steps, seconds)."""
+def pixel_split_wanted(cfg: Cfg) -> bool:
+    """train.pixel_split (default false): fit ONE picture across the ranks by image rows"""
+    v = cfg.train.get("pixel_split", False)
+    v = {"true": True, "false": False, "on": True, "off": False}.get(v.lower(), v) if isinstance(v, str) else v
+    if not isinstance(v, bool):
+        raise ValueError(f"train.pixel_split: true or false, got {v!r}")
+    return v
+
+
+def split_backend_setting(cfg: Cfg) -> str:
+    """train.split_backend (default auto): auto | nccl | gloo, what parallel.split_backend takes"""
+    v = cfg.train.get("split_backend", "auto")
+    if v not in SPLIT_BACKENDS:
+        raise ValueError(f"train.split_backend: one of {' | '.join(SPLIT_BACKENDS)}, got {v!r}")
+    return v
+
+
+def check_pixel_split(cfg: Cfg, world: int = 1):
+    """What a fit split by rows refuses, from the configuration and the world size alone: before any GPU work and before the
+    process group is touched, and the same on every rank, so no rank waits in a collective for one that raised."""
+    split_backend_setting(cfg)
+    if cfg.mlp.name == "fourier":
+        raise NotImplementedError(f"train.pixel_split with mlp=fourier: {FOURIER_SPLIT_UNSUPPORTED}")
+    if cfg.mlp.name == "wavelet_siren":
+        raise NotImplementedError(f"train.pixel_split with mlp=wavelet_siren: {WAVELET_SPLIT_UNSUPPORTED}")
+    masking = cfg.get("masking") or {}
+    if masking.get("name") == "Feathermap":
+        raise NotImplementedError(f"train.pixel_split: {FEATHER_SPLIT_UNSUPPORTED}")
+    if not device_eval_wanted(cfg.train.get("device_eval", "auto")):
+        raise NotImplementedError(SPLIT_EVAL_EPOCH_UNSUPPORTED)
+    small = masking.get("density") if masking.get("name") == "Small_Dense" else 1.0
+    hidden = int(cfg.mlp.hidden_size * np.sqrt(small))                             # (Siren's own Small_Dense width)
+    if next_kernel_width(hidden, Siren.WIDTHS) != hidden:
+        raise NotImplementedError(f"train.pixel_split with hidden width {hidden}: {SPLIT_PADDED_UNSUPPORTED}")
+    if cfg.img.height < world:
+        raise NotImplementedError(f"train.pixel_split: {cfg.img.height} image rows cannot be shared out over {world} ranks "
+                                  "(every rank needs a row)")
+
+
+def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None, rank: int = None, world: int = None):
+    """One fit; returns dict(loss, PSNR, PSNR_8bit, steps, seconds).
+
+    train.pixel_split: rank `rank` of `world` (default: RANK / WORLD_SIZE, a world of one without them) fits rows
+    shard_rows(H, world, rank) of the picture; the model carries a parallel.RowSplit, under which every step and every
+    evaluation reduces over the ranks (utils/train_helper.py).  Seed, init, mask draw and schedules are the ordinary fit's on
+    every rank, so the replicas stay identical; every rank returns the same dict, rank 0 alone writes into out_dir.  The
+    caller has initialised torch.distributed when world > 1 (main does)."""
+    split = None
+    if pixel_split_wanted(cfg):
+        rank = int(os.environ.get("RANK", "0")) if rank is None else rank
+        world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+        check_pixel_split(cfg, world)                                              # before any GPU work
+        if world > 1 and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+            raise RuntimeError("train.pixel_split with WORLD_SIZE > 1 needs an initialised torch.distributed process group "
+                               "(python -m implicit_image.fit makes one)")
     feather = bool(cfg.get("masking") and cfg.masking.get("name") == "Feathermap")
     if feather and cfg.mlp.name != "siren":
         raise NotImplementedError("masking=Feathermap runs on the SIREN engine only (mlp=siren)")
@@ -52,6 +111,13 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
     model = model_registry[cfg.mlp.name](**cfg.mlp, small_dense_density=small, **eng_kw)   # compress.py:77
     if feather:                                                                    # compress.py:80-81
         model = FeatherNet(model, compress=cfg.masking.density)
+    if pixel_split_wanted(cfg):
+        # this rank's rows of grid and picture alone go to the device; the handle indexes rows absolutely, so the split
+        # carries the row coordinates of the whole grid
+        split = RowSplit(cfg.img.height, rank, world, row_coords=grid[:, 0, 0].contiguous())
+        model.set_row_split(split)
+        grid, img = grid[split.row_begin:split.row_end], img[split.row_begin:split.row_end].contiguous()
+    writes = split is None or split.rank == 0                                      # rank 0 alone writes the artefacts
     model, grid, img = model.to(device), grid.to(device), img.to(device)          # compress.py:84-86
     model.train()
     optim, lr_scheduler = get_optimizer_lr_scheduler(model, cfg.optim)             # compress.py:105
@@ -131,19 +197,23 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None):
             last["Density"] = float(mask.stats.total_density)
         logging.info(f"Post Quant | Train step: {num_steps} | Quant step: {qcfg.num_steps} | Quant PSNR: {p:.4f}")
     if out_dir and cfg.train.save_weights:
-        os.makedirs(out_dir, exist_ok=True)
-        torch.save({"state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}},
-                   os.path.join(out_dir, "model.pth"))                            # compress.py:243-244
+        if writes:
+            os.makedirs(out_dir, exist_ok=True)
+            torch.save({"state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}},
+                       os.path.join(out_dir, "model.pth"))                        # compress.py:243-244
         if quantized_model is not None and cfg.get("entropy_coding"):              # compress.py:249-263
             ec = dict(cfg.entropy_coding)
-            nbytes = entropy_coding.compress_state_dict(quantized_model.half(), os.path.join(out_dir, "model_quantized"),
-                                                        **ec)
+            # (a rank that does not write still reports the byte count: its identical replica, coded into a directory it drops)
+            with (contextlib.nullcontext(out_dir) if writes else tempfile.TemporaryDirectory()) as where:
+                nbytes = entropy_coding.compress_state_dict(quantized_model.half(), os.path.join(where, "model_quantized"),
+                                                            **ec)
             last["Compressed Bytes"] = nbytes
             logging.info(f"Compressed bytes {nbytes}")
-        with open(os.path.join(out_dir, "result.json"), "w") as f:
-            json.dump(last, f)
-        from .decode import write_decode_json                                      # what `make decode` rebuilds the network from
-        write_decode_json(out_dir, cfg, list(model.state_dict().keys()))
+        if writes:
+            with open(os.path.join(out_dir, "result.json"), "w") as f:
+                json.dump(last, f)
+            from .decode import write_decode_json                                  # what `make decode` rebuilds the network from
+            write_decode_json(out_dir, cfg, list(model.state_dict().keys()))
     return last
 
 
@@ -154,18 +224,36 @@ def main(argv=None):
     jobs = expand_sweeps(argv)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    cfgs = [load_config(conf_dir, ov) for ov in jobs]
+    split = [pixel_split_wanted(c) for c in cfgs]
+    grouped = False
+    if any(split):
+        # one picture across the ranks: EVERY job on EVERY rank, in order; what is refused is refused here, on every rank
+        # alike, before the GPU and the process group are touched
+        if not all(split):
+            raise ValueError("train.pixel_split is one setting for the whole sweep: every rank runs every job")
+        for c in cfgs:
+            check_pixel_split(c, world)
+        rank, world, grouped = init_split_group(split_backend_setting(cfgs[0]))
+        if torch.cuda.is_available():
+            local_rank %= torch.cuda.device_count()        # (ranks that share a device: the rehearsal over gloo)
+    else:
+        jobs, cfgs = shard_jobs(jobs, world, rank), shard_jobs(cfgs, world, rank)
     results = []
-    for ov in shard_jobs(jobs, world, rank):
-        cfg = load_config(conf_dir, ov)
-        device = get_device(cfg.device)
-        if device.type == "cuda":
-            device = torch.device("cuda", local_rank)
-            torch.cuda.set_device(device)
-        tag = ",".join(o for o in ov if not o.startswith(("exp_name", "img.name"))) or "default"
-        out_dir = os.path.join("outputs", str(cfg.img.name), str(cfg.exp_name), tag.replace("/", "_"))
-        res = fit_one(cfg, device, out_dir)
-        logging.info(f"[rank {rank}] {tag}: {res}")
-        results.append((tag, res))
+    try:
+        for ov, cfg in zip(jobs, cfgs):
+            device = get_device(cfg.device)
+            if device.type == "cuda":
+                device = torch.device("cuda", local_rank)
+                torch.cuda.set_device(device)
+            tag = ",".join(o for o in ov if not o.startswith(("exp_name", "img.name"))) or "default"
+            out_dir = os.path.join("outputs", str(cfg.img.name), str(cfg.exp_name), tag.replace("/", "_"))
+            res = fit_one(cfg, device, out_dir, rank, world) if any(split) else fit_one(cfg, device, out_dir)
+            logging.info(f"[rank {rank}] {tag}: {res}")
+            results.append((tag, res))
+    finally:
+        if grouped:
+            torch.distributed.destroy_process_group()
     return results
 
 

@@ -47,8 +47,23 @@ class EngineBound(nn.Module):
         self._grid_key = None
         self._target_key = None
         self._engine_optims = weakref.WeakSet()     # engine() rebinds these when it re-makes the handle
+        self._split = None                     # a parallel.RowSplit: engine() then makes a handle of its rows alone
 
     # ---- what consumers use ---------------------------------------------------------------------
+    split_unsupported = None       # the refusal set_row_split raises for a family whose handle has no row ranges
+
+    @property
+    def row_split(self):
+        """the parallel.RowSplit this model is fitted under (train.pixel_split), None for an ordinary fit"""
+        return self._split
+
+    def set_row_split(self, split):
+        """Fit this model on rows [split.row_begin, split.row_end) of a picture of split.full_height rows: engine(grid, img)
+        takes the row range from here, so every consumer that asks for the handle meets the same one.  `grid` / `img` are
+        then those rows (or the full-height grid); the step and evaluation harness reduces over the ranks (train_helper)."""
+        if split is not None and self.split_unsupported:
+            raise NotImplementedError(self.split_unsupported)
+        self._split = split
     @property
     def bound_engine(self):
         """the live engine handle, None while unbound"""
@@ -124,6 +139,9 @@ class EngineBound(nn.Module):
         Adam hyper-parameters or the scratch format change)."""
         self._check_device(grid)
         h, w, _ = grid.shape
+        split = self._split
+        if split is not None and not (row_begin or row_end or full_height):
+            row_begin, row_end, full_height = split.row_begin, split.row_end, split.full_height
         H = full_height or h
         key = self._engine_key_of(H, w, row_begin, row_end, grid.device.index)
         if self._engine is None or self._engine_key != key:
@@ -143,7 +161,15 @@ class EngineBound(nn.Module):
         if self._grid_key != gkey:
             rows, cols = grid_vectors(grid)
             if full_height and full_height != h:
-                raise ValueError("pass the full-height grid in pixel-split mode")
+                # the handle indexes the row vector by absolute row: a grid of the split's rows alone brings the columns, the
+                # split the rows of the whole picture
+                full = None if split is None else split.row_coords
+                if full is None or h != row_end - row_begin or full.numel() != full_height:
+                    raise ValueError("pass the full-height grid in pixel-split mode")
+                full = full.to(rows.device, rows.dtype)
+                if not torch.equal(full[row_begin:row_end], rows):
+                    raise ValueError(f"the grid does not hold rows [{row_begin}, {row_end}) of the split's row coordinates")
+                rows = full
             eng.set_coords(rows.float(), cols.float())
             self._grid_key = gkey
         if img is not None:
@@ -284,6 +310,7 @@ class EngineBound(nn.Module):
         new = type(self)(**self._ctor_args())
         new.to(next(self.parameters()).device)
         new._adam = self._adam
+        new._split = self._split               # (a copy is fitted on the same rows: the quantise phase)
         with torch.no_grad():
             for a, b in zip(new._param_list(), self._param_list()):
                 a.copy_(b)

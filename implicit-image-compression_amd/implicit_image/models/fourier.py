@@ -18,7 +18,8 @@ MASKING_UNSUPPORTED = ("mask-based sparsity (RigL / SNFS / SET / Pruning) is not
                        "Masking registers the frozen encoding.B and its first update_connections() fails with "
                        "AttributeError ('NoneType' object has no attribute 'dtype', pipeline/masking/funcs/grow.py:87). "
                        "Use masking=none or masking=Small_Dense")
-MAP_SIZES = (64, 128, 256, 512)    # the encoding sizes k_ff_fwd is instantiated for
+PIXEL_SPLIT_UNSUPPORTED = "pixel-split (row ranges) is not supported for FourierNet"
+MAP_SIZES = (64, 128, 256, 512)   # the encoding sizes k_ff_fwd is instantiated for
 
 
 def engine_takes(input_size: int, output_size: int, map_size: int, n_linear: int) -> bool:
@@ -43,6 +44,7 @@ class FourierNet(EngineBound):
     # weights and bias, output relu(0) = 0 and receive exactly zero gradients)
     WIDTHS = KERNEL_WIDTHS
     mask_unsupported = MASKING_UNSUPPORTED
+    split_unsupported = PIXEL_SPLIT_UNSUPPORTED
     _WHO = "Siren"                 # (the wording a CPU grid has always been refused with)
 
     def __init__(self, input_size: int = 2, output_size: int = 3, depth: int = 8, hidden_size: int = 128,
@@ -104,7 +106,7 @@ class FourierNet(EngineBound):
 
     def engine(self, grid: torch.Tensor, img=None, row_begin: int = 0, row_end: int = 0, full_height=None):
         if row_begin or (row_end and row_end != grid.shape[0]) or (full_height and full_height != grid.shape[0]):
-            raise NotImplementedError("pixel-split (row ranges) is not supported for FourierNet")
+            raise NotImplementedError(PIXEL_SPLIT_UNSUPPORTED)
         eng = super().engine(grid, img)
         B = self.encoding.B
         key = (id(eng), B.data_ptr(), B._version)

@@ -38,6 +38,7 @@ def check_image(h: int, w: int):
 class WaveletSiren(EngineBound):
     WIDTHS = Siren.WIDTHS          # the sub-networks' (the constructor refuses what the narrow kernel path cannot run)
     mask_unsupported = MASKING_UNSUPPORTED
+    split_unsupported = PIXEL_SPLIT_UNSUPPORTED
 
     def __init__(self, input_size: int = 2, output_size: int = 3, depth: int = 8, hidden_size: int = 64,
                  wavelet_levels: int = 1, first_omega_0: float = 50.0, hidden_omega_0: float = 50.0,

@@ -25,11 +25,14 @@ DEPLOY_UNSUPPORTED = ("FeatherNet.deploy() (the reference's forward-hook weight 
 DEEPCOPY_UNSUPPORTED = ("a trained FeatherNet cannot be deep-copied: in the reference its weights are non-leaf tensors "
                         "and copy.deepcopy fails (\"Only Tensors created explicitly by the user (graph leaves) support the "
                         "deepcopy protocol\"), so Feathermap works with quant=none only")
+PIXEL_SPLIT_UNSUPPORTED = ("masking=Feathermap under pixel-split is not built: the step reduces the handle's dense gradient "
+                           "over the ranks, and the feather vector's gradient (the adjoint of it) is what Adam steps")
 
 
 class FeatherNet(EngineBound):
     """Reference constructor; `module` must be a Siren (the engine's model)."""
     _SYNC_PER_OPTIM = False               # _carry_in syncs (and materialises) once, whatever the number of optimisers
+    split_unsupported = PIXEL_SPLIT_UNSUPPORTED
 
     def __init__(self, module: nn.Module, compress: float = 0.5, exclude: tuple = (nn.BatchNorm2d), clone: bool = True,
                  verbose: bool = False) -> None:

@@ -19,8 +19,16 @@ from torch.nn import Module, functional as F
 from torch.optim import Optimizer
 
 from .. import _engine
+from ..parallel import SseTable, as_float
 from ..pipeline.masking import Masking, decay_registry
 from ..pipeline.quant.kmeans import KmeansQuant
+
+# what a fit split by image rows (train.pixel_split) refuses, here and - before any GPU work - in fit.check_pixel_split
+SPLIT_PADDED_UNSUPPORTED = ("pixel-split with a zero-padded width is not built: the padded layout's Parameters and .grad are "
+                            "gathered copies, not the handle's vectors that the ranks reduce in place and the device topology "
+                            "routes read; use a hidden size the kernels are instantiated for")
+SPLIT_EVAL_EPOCH_UNSUPPORTED = ("train.device_eval=off under pixel-split: eval_epoch needs the whole prediction, a rank holds "
+                                "its rows alone; use train.device_eval=auto")
 
 
 class EngineAdam(Optimizer):
@@ -154,6 +162,8 @@ def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
         raise NotImplementedError("preconditioners (EKFAC) are dead code in the reference and not supported")
     # kwargs 'scaler' / 'context' are accepted and ignored: autocast is never entered by the reference
     # (train_helper.py:141) and GradScaler is an exact no-op on fp32 gradients.
+    if getattr(model, "row_split", None) is not None:
+        return _split_steps(model, optim, grid, img, 1, **kwargs)[0]
     model.train()
     optim.zero_grad()
     eng = model.engine(grid, img)
@@ -172,6 +182,45 @@ def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
     if lr_scheduler:
         lr_scheduler.step()
     return loss
+
+
+def _split_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
+    """`n` steps of a fit split by image rows (model.row_split, a parallel.RowSplit; grid / img: this rank's rows), returned as
+    the list of their losses: (float)(sse / n) of the FULL image, the same on every rank.
+
+    A step is train_epoch's in train_epoch's order, with the reduction where the loss used to be read:
+    forward_backward(sync=False), the in-place all-reduce of the handle's own gradient view and SSE double, download_grads
+    and the post-backward callbacks, mask.step() or optim.step().  Nothing is read per step: every step's reduced SSE is
+    copied into a table on the device, and the table is read once after the last step.  The bulk calls (sf_step,
+    sf_quant_step) are not used: a collective cannot run inside them.  A world of one reduces nothing and is, kernel for
+    kernel, the step-by-step loop the bulk calls are bit-identical to."""
+    if kwargs.get("criterion", F.mse_loss) is not F.mse_loss:
+        raise NotImplementedError("the engine fuses F.mse_loss (reduction='mean'); other criteria are not supported")
+    if kwargs.get("preconditioner") is not None:
+        raise NotImplementedError("preconditioners (EKFAC) are dead code in the reference and not supported")
+    if not model.state_is_live:
+        raise NotImplementedError(SPLIT_PADDED_UNSUPPORTED)
+    split, mask, pbar, lr_scheduler = model.row_split, kwargs.get("mask"), kwargs.get("pbar"), kwargs.get("lr_scheduler")
+    table = SseTable(n)
+    for k in range(n):
+        model.train()
+        optim.zero_grad()
+        eng = model.engine(grid, img)          # (the pre-pass callbacks of a quantise phase run here: sf_quant_pass)
+        eng.forward_backward(sync=False)
+        split.reduce_pass(eng)
+        table.put(k, eng.sse_view())           # before the next pass overwrites it
+        model.download_grads()
+        for cb in list(model.post_backward_callbacks):
+            cb()
+        if mask:
+            mask.step(kwargs.get("scaler"))
+        else:
+            optim.step()
+        if pbar:
+            pbar.update(1)
+        if lr_scheduler:
+            lr_scheduler.step()
+    return [as_float(sse / split.n_values(img)) for sse in table.read()]
 
 
 def _quant_phase(model: Module, optim: Optimizer):
@@ -199,6 +248,8 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     plan (pipeline/quant/kmeans.py), the n steps - each with its k-means pass before and its centroid nudge after the
     backward - are ONE `sf_quant_step` call.  The nudge's learning rate is optim.defaults["lr"], not the scheduled one, as
     in the reference."""
+    if getattr(model, "row_split", None) is not None:      # a fit split by rows: step by step, one read at the end
+        return _split_steps(model, optim, grid, img, n, **kwargs)
     mask: Masking = kwargs.get("mask")
     lr_scheduler = kwargs.get("lr_scheduler")
     pbar = kwargs.get("pbar")
@@ -251,6 +302,8 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
 
 @torch.no_grad()
 def eval_epoch(model: Module, grid, img, **kwargs) -> Tuple[torch.Tensor, float, float, float]:
+    if getattr(model, "row_split", None) is not None:
+        raise NotImplementedError(SPLIT_EVAL_EPOCH_UNSUPPORTED)
     model.eval()
     eng = model.engine(grid, img)
     pred, sse = eng.forward(want_pred=True, want_sse=True)
@@ -278,12 +331,18 @@ def eval_metrics(model: Module, grid, img) -> Tuple[float, float, float]:
     from the same partials in the same order).  PSNR_8bit is 10 log10(255^2 / (sse8 / n)) in Python doubles from the exact
     integer sum, where eval_epoch takes torch's fp32 mean and fp32 log10: the two agree to about 1e-5 dB.
     A library or a handle class without the entry point: eval_epoch(...)[1:]."""
+    split = getattr(model, "row_split", None)
     model.eval()
     eng = model.engine(grid, img)             # (as eval_epoch: the pre-pass callbacks of a quantise phase run here)
     if not (callable(getattr(eng, "eval_sums", None)) and _engine.has_eval(eng.lib)):
         return eval_epoch(model, grid, img)[1:]
-    sse, sse8 = eng.eval_sums()
-    n = img.numel()
+    if split is not None:                     # this rank's rows; the double and the exact integer sum add up over the ranks
+        eng.eval_sums(sync=False)
+        sse, sse8 = split.reduce_eval(eng)
+        n = split.n_values(img)
+    else:
+        sse, sse8 = eng.eval_sums()
+        n = img.numel()
     test_loss = sse / n
     test_PSNR = 10 * math.log10(1 / test_loss)
     test_PSNR_8bit = 10 * math.log10(255 ** 2 / (sse8 / n)) if sse8 else math.inf
