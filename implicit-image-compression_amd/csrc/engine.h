@@ -190,6 +190,18 @@ struct sf_engine {
     int* iter_dev = nullptr;
     int tab_cap = 0;
   } graph;
+  // sf_step_many with this handle as its first member (many_host.hip): the device block of a call - step counter, argument
+  // tables, per-step scalars, loss table - and two pinned staging blocks it is filled from, used in turn (ev[i]: the copy out
+  // of block i has been issued and may still be pending)
+  struct Many {
+    char* dev = nullptr;
+    size_t dev_cap = 0;
+    char* host[2] = {nullptr, nullptr};
+    size_t host_cap[2] = {0, 0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool pending[2] = {false, false};
+    int turn = 0;
+  } many;
   // Model::Fourier (fourier_host.hip, fourier_kernels.hip): D = number of Linear layers, WD = hidden width.  A render handle
   // keeps the parameters, img, B and the two coordinate vectors
   struct Fourier {
@@ -407,6 +419,10 @@ void destroy(sf_engine* h) {
   for (sf_engine* s : h->wv.sub) if (s) destroy(s);
   if (h->graph.exec) hipGraphExecDestroy(h->graph.exec);
   if (h->graph.stream) { hipStreamSynchronize(h->graph.stream); hipStreamDestroy(h->graph.stream); hipEventDestroy(h->graph.ev_in); hipEventDestroy(h->graph.ev_out); }
+  for (int i = 0; i < 2; ++i) {
+    if (h->many.host[i]) hipHostFree(h->many.host[i]);
+    if (h->many.ev[i]) hipEventDestroy(h->many.ev[i]);
+  }
   for (void* p : h->owned) hipFree(p);
   delete h;
 }

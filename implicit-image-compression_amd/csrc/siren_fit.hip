@@ -19,6 +19,7 @@
 #include "wavelet_kernels.hip"
 #include "siren_mask.hip"
 #include "siren_quant.hip"
+#include "siren_many.hip"
 
 #include "engine.h"
 
@@ -91,6 +92,13 @@
     SF_K(k_wgemm2<0, OpF16, false, false, false, true>), SF_K(k_wgemm2<0, OpBF16, false, false, false, true>),
     SF_K(k_wgemm<OpF16, true, 8>), SF_K(k_wgemm<OpF16, true, 16>), SF_K(k_wgemm<OpBF16, true, 8>),
     SF_K(k_wgemm<OpBF16, true, 16>), SF_K(k_prune_file<false>), SF_K(k_prune_file<true>),
+    // sf_step_many (siren_many.hip): behind everything that was there before it
+    SF_K(k_fwd_many<32>), SF_K(k_fwd_many<64>), SF_K(k_fwd_many<128>), SF_K(k_bwd_many<32, true, true>),
+    SF_K(k_bwd_many<32, true, false>), SF_K(k_bwd_many<32, false, true>), SF_K(k_bwd_many<32, false, false>),
+    SF_K(k_bwd_many<64, true, true>), SF_K(k_bwd_many<64, true, false>), SF_K(k_bwd_many<64, false, true>),
+    SF_K(k_bwd_many<64, false, false>), SF_K(k_bwd_many<128, true, true>), SF_K(k_bwd_many<128, true, false>),
+    SF_K(k_bwd_many<128, false, true>), SF_K(k_bwd_many<128, false, false>), SF_K(k_dw0_many<32>), SF_K(k_dw0_many<64>),
+    SF_K(k_dw0_many<128>),
 };
 #undef SF_K
 
@@ -405,20 +413,31 @@ int sf_forward_backward(sf_handle* h, double* sse_out) try {
 
 // one optimiser step on the gradient the handle holds, then the weight images of the new parameters (refresh = false: they
 // stay marked dirty - the caller rewrites the weights before the next pass, which refreshes them)
-static int adam_step(sf_engine* h, float lr, bool refresh = true) {
-  h->step += 1;
+// k_adam on the handle's flat state, without the per-step scalars (adam_scalars, or a device table of them)
+static AdamArgs adam_args(const sf_engine* h) {
   AdamArgs a = zeroed<AdamArgs>();
-  if (h->ctx->replay) { a.tab = h->graph.step_tab; a.iter = h->graph.iter_dev; }
   a.p = h->params; a.g = h->grads; a.m = h->m; a.v = h->v; a.mask = h->has_mask ? h->mask : nullptr;
   a.n = h->P;
   a.beta1 = h->cfg.beta1; a.beta2 = h->cfg.beta2; a.eps = h->cfg.eps;
   // torch forms 1 - beta in double and hands the kernel the rounded float (0.1f, 0.001f); 1.0f - beta in fp32 is
   // 0.100000024 / 0.000999987
   a.omb1 = (float)(1.0 - h->beta1_d); a.omb2 = (float)(1.0 - h->beta2_d);
-  const double bc1 = 1.0 - pow(h->beta1_d, (double)h->step);
-  const double bc2 = 1.0 - pow(h->beta2_d, (double)h->step);
-  a.step_size = (float)((double)lr / bc1);
-  a.bc2_sqrt = (float)sqrt(bc2);
+  return a;
+}
+// {step_size, bc2_sqrt} of the handle's Adam step number t (from 1) at learning rate lr, formed in double as torch does
+static void adam_scalars(const sf_engine* h, double t, float lr, float* out2) {
+  const double bc1 = 1.0 - pow(h->beta1_d, t), bc2 = 1.0 - pow(h->beta2_d, t);
+  out2[0] = (float)((double)lr / bc1);
+  out2[1] = (float)sqrt(bc2);
+}
+static int adam_step(sf_engine* h, float lr, bool refresh = true) {
+  h->step += 1;
+  AdamArgs a = adam_args(h);
+  if (h->ctx->replay) { a.tab = h->graph.step_tab; a.iter = h->graph.iter_dev; }
+  float sc[2];
+  adam_scalars(h, (double)h->step, lr, sc);
+  a.step_size = sc[0];
+  a.bc2_sqrt = sc[1];
   if (h->fth.attached) {   // adjoint -> Adam on [V1 | V2 | scalers] -> materialise: four launches
     if (!h->fth.fresh) SF_TRY(feather_adjoint(h));
     a.p = h->fth.p; a.g = h->fth.g; a.m = h->fth.m; a.v = h->fth.v; a.mask = nullptr; a.n = h->fth.nf;
@@ -479,12 +498,7 @@ static int read_losses(sf_engine* h, int n, float* loss_out) {
 static int step_replay(sf_engine* h, const float* lr, int n, float* loss_out) {
   SF_TRY(graph_prepare(h, n));
   std::vector<float> tab((size_t)n * 2);
-  for (int i = 0; i < n; ++i) {
-    const double t = (double)(h->step + i + 1);
-    const double bc1 = 1.0 - pow(h->beta1_d, t), bc2 = 1.0 - pow(h->beta2_d, t);
-    tab[2 * i] = (float)((double)lr[i] / bc1);
-    tab[2 * i + 1] = (float)sqrt(bc2);
-  }
+  for (int i = 0; i < n; ++i) adam_scalars(h, (double)(h->step + i + 1), lr[i], &tab[2 * i]);
   hipStream_t user = h->ctx->stream;
   HIPCHK(hipEventRecord(h->graph.ev_in, user));
   HIPCHK(hipStreamWaitEvent(h->graph.stream, h->graph.ev_in, 0));
@@ -630,6 +644,7 @@ int sf_debug_throw(int32_t kind) try {
 }  // extern "C"
 
 #include "quant_host.hip"
+#include "many_host.hip"
 #include "siren_render.hip"
 #include "wavelet_render.hip"
 #include "fourier_render.hip"

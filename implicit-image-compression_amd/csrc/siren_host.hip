@@ -141,7 +141,7 @@ double flops_fwd_px(const sf_engine* h) {
 }
 
 // the 16-bit weight images, the layer-0 table / image (and, format 8, the per-layer delta scales) of a width <= 256
-int refresh_images_siren(sf_engine* h) {
+ImgArgs images_args(const sf_engine* h) {
   ImgArgs a = zeroed<ImgArgs>();
   a.params = h->params;
   a.depth = h->D;
@@ -158,10 +158,19 @@ int refresh_images_siren(sf_engine* h) {
   a.wf = h->wf; a.wf_last = h->wf_last; a.wb = h->wb; a.wb_last = h->wb_last;
   a.l0tab = h->l0tab;
   a.l0img = h->l0img; a.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+  return a;
+}
+// threads of k_images: one per element of the hidden images, at least the small tables
+long images_count(const sf_engine* h) {
   long n = (long)(h->D - 2) * h->WD * h->WD;
   const long n_min = (long)h->WD / 16 * 64 * 8;  // also covers the small tables
   if (n < n_min) n = n_min;
   if (n < 1024) n = 1024;
+  return n;
+}
+int refresh_images_siren(sf_engine* h) {
+  ImgArgs a = images_args(h);
+  const long n = images_count(h);
   Launch L(h, K_IMAGES, 0, (double)n * 8);
   if (h->d8 && h->lsc) {   // per-layer delta scales first: k_images folds them into the backward images
     SF_TRY(launch_fp8_scales(h));
@@ -172,13 +181,10 @@ int refresh_images_siren(sf_engine* h) {
   return SF_OK;
 }
 
-// The forward of chunk c of a SIREN handle of width <= 256, training or evaluation form (k_fwd / k_fwd_pipe): the prediction
-// to pred (or null), the chunk's SSE partials to sse_part; n_part: how many it wrote (fwd_grid).  sse8_part (sf_eval, with
-// neither train nor pred): the EVAL form, which stores nothing but the two kinds of partials
-int siren_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part, unsigned long long* sse8_part = nullptr) {
-  const int WD = h->WD, D = h->D;
-  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
-  const double npx = k.n_pb * 32.0;
+// ---- the arguments of a chunk's kernels, each built in one place: siren_fwd_chunk / siren_bwd_chunk launch them one fit at a
+// time, sf_step_many (many_host.hip) files them in tables of B fits -------------------------------------------------------
+// the forward of chunk k (fwd_args_base plus its outputs); sse8_part non-null: the EVAL form
+FwdArgs fwd_chunk_args(const sf_engine* h, const Chunk& k, bool train, float* pred, float* sse_part, unsigned long long* sse8_part) {
   FwdArgs fa = fwd_args_base(h, own_view(h), k.pix0, k.n_super);
   fa.P = h->Pbuf; fa.p_stride = h->p_stride; fa.Dlast = h->Dlast;
   fa.dfac = train ? h->wv.dfac_out : nullptr;
@@ -187,9 +193,86 @@ int siren_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_pa
   fa.pred = pred;
   fa.sse_part = sse_part;
   if (sse8_part) fa.sse8_part = sse8_part;
+  return fa;
+}
+double fwd_chunk_bytes(const sf_engine* h, const Chunk& k, bool train) {
+  return k.n_pb * 32.0 * (4.0 * h->cfg.out_features + (train ? (h->D - 2) * h->WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0));
+}
+// workgroups of the layer kernels of a chunk (at most one per CU) and the pixel blocks each walks
+struct BwdGrid { int n_wg; long pb_per_wg; };
+BwdGrid bwd_grid(const sf_engine* h, const Chunk& k) {
+  const int PBS = 2;   // k_dw stages two pixel blocks at a time; k_bwd accepts any block count
+  int n_wg = (int)((k.n_pb + PBS - 1) / PBS);
+  if (n_wg > h->dw_wg) n_wg = h->dw_wg;
+  long pb_per_wg = (k.n_pb + n_wg - 1) / n_wg;
+  pb_per_wg = (pb_per_wg + PBS - 1) / PBS * PBS;
+  n_wg = (int)((k.n_pb + pb_per_wg - 1) / pb_per_wg);
+  return {n_wg, pb_per_wg};
+}
+// what Bwd8Args and BwdLayerArgs share for layer l >= 1: deltas in and out, phases of the layer below, the backward image
+template <typename Args>
+void fill_bwd_layer(const sf_engine* h, const Chunk& k, int l, Args& ba) {
+  const bool last = l == h->D - 1;
+  const size_t img_pieces = (size_t)h->WD * h->WD / 8;
+  fill_grid(h, k.pix0, ba);
+  ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
+  ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
+  ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
+  ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
+               : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
+  ba.n_pb = k.n_pb; ba.slab = h->slab; ba.l0tab = h->l0tab;
+  ba.sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
+}
+// k_bwd of layer l >= 1 (16-bit scratch)
+BwdLayerArgs bwd_layer_args(const sf_engine* h, const Chunk& k, int l, const BwdGrid& g) {
+  BwdLayerArgs ba = zeroed<BwdLayerArgs>();
+  fill_bwd_layer(h, k, l, ba);
+  ba.pb_per_wg = (int)g.pb_per_wg;
+  return ba;
+}
+double bwd_layer_bytes(const sf_engine* h, const Chunk& k, int l) {
+  return k.n_pb * 32.0 * ((l == h->D - 1 ? 64.0 : h->WD * 2.0) + h->WD * (l - 1 == 0 ? 2.0 : 4.0));
+}
+// k_dw0 / k_dw0_8 and their workgroups
+Dw0Args dw0_args(const sf_engine* h, const Chunk& k) {
+  Dw0Args da = zeroed<Dw0Args>();
+  fill_grid(h, k.pix0, da);
+  da.D = h->Dbuf; da.ks_total = h->WD / 16; da.ks_off = 0; da.n_pb = k.n_pb; da.slab = h->slab;
+  return da;
+}
+int dw0_grid(const sf_engine* h, const Chunk& k) {
+  const long cap0 = (h->d8 && h->WD == 256) ? 2L * h->dw_wg : (long)h->dw_wg;      // k_dw0_8<256>: two workgroups per CU
+  return (int)(k.n_pb < cap0 ? k.n_pb : cap0);
+}
+// the slab reduction of layer l after a kernel of n_wg workgroups, chunk c (accumulating from the second chunk on)
+ReduceArgs reduce_args(const sf_engine* h, long c, int l, int n_wg) {
+  const int WD = h->WD;
+  const bool last = l == h->D - 1;
+  ReduceArgs ra = zeroed<ReduceArgs>();
+  ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
+  if (h->d8) {   // last layer: dW from the statically scaled residual; layers below: the chunk's adaptive pre-scale
+    ra.scale = (float)(1.0 / ((double)kResScale * (double)h->cfg.out_features * h->n_total));
+    ra.scale_dev = last ? nullptr : h->scale_dev;
+    ra.scale2_dev = (last || !h->lsc) ? nullptr : h->lsc + 16 + l;
+  }
+  ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l];
+  // a layer above 0: rows x WD weight gradient from slabs of (last: 32, else WD) rows
+  ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD; ra.rows_out = last ? h->cfg.out_features : WD; ra.cols_out = WD; ra.mode = 0;
+  if (l == 0) { ra.slab_rows = WD; ra.slab_cols = 32; ra.rows_out = WD; ra.cols_out = 2; ra.mode = 1; }
+  return ra;
+}
+// values a reduction of layer l writes; a hidden layer's slab layout is the flat gradient's [W | b]: k_reduce_vec
+int reduce_count(const ReduceArgs& ra) { return ra.rows_out * ra.cols_out + ra.rows_out; }
+bool reduce_is_vec(const sf_engine* h, int l) { return l > 0 && l != h->D - 1; }
+
+// The forward of chunk c of a SIREN handle of width <= 256, training or evaluation form (k_fwd / k_fwd_pipe): the prediction
+// to pred (or null), the chunk's SSE partials to sse_part; n_part: how many it wrote (fwd_grid).  sse8_part (sf_eval, with
+// neither train nor pred): the EVAL form, which stores nothing but the two kinds of partials
+int siren_fwd_chunk(sf_engine* h, long c, bool train, float* pred, float* sse_part, int& n_part, unsigned long long* sse8_part = nullptr) {
+  const Chunk k = chunk_at(c, h->npix, h->chunk_px);
+  const FwdArgs fa = fwd_chunk_args(h, k, train, pred, sse_part, sse8_part);
   n_part = fwd_grid(h, k.n_super);
-  Launch L(h, K_FWD, flops_fwd_px(h) * npx,
-           npx * (4.0 * h->cfg.out_features + (train ? (D - 2) * WD * (h->s8 ? 1.0 : 2.0) + (h->s8 ? 32.0 : 64.0) : 0.0)));
+  Launch L(h, K_FWD, flops_fwd_px(h) * (k.n_pb * 32.0), fwd_chunk_bytes(h, k, train));
   return launch_fwd(h, fa, n_part, train, sse8_part != nullptr);
 }
 
@@ -201,45 +284,20 @@ int siren_bwd_chunk(sf_engine* h, long c, const float* sse_part, int n_part) {
   const Chunk k = chunk_at(c, h->npix, h->chunk_px);
   const long n_pb = k.n_pb;
   const double npx = n_pb * 32.0;
-  const float sc_first = (float)((double)h->cfg.first_omega_0 / kTwoPi);
   // backward, last layer first; every layer kernel is followed by the fixed-order slab reduction
-  const int PBS = 2;   // k_dw stages two pixel blocks at a time; k_bwd accepts any block count
-  int n_wg = (int)((n_pb + PBS - 1) / PBS);
-  if (n_wg > h->dw_wg) n_wg = h->dw_wg;
-  long pb_per_wg = (n_pb + n_wg - 1) / n_wg;
-  pb_per_wg = (pb_per_wg + PBS - 1) / PBS * PBS;
-  n_wg = (int)((n_pb + pb_per_wg - 1) / pb_per_wg);
-  const size_t img_pieces = (size_t)WD * WD / 8;
-  // what Bwd8Args and BwdLayerArgs share for layer l >= 1: deltas in and out, phases of the layer below, the backward image
-  auto fill_layer = [&](auto& ba, int l) {
-    const bool last = l == D - 1;
-    fill_grid(h, k.pix0, ba);
-    ba.D = last ? h->Dlast : h->Dbuf + (size_t)l * h->d_stride;
-    ba.P = h->Pbuf + (size_t)(l - 1) * h->p_stride;
-    ba.Dout = h->Dbuf + (size_t)(l - 1) * h->d_stride;
-    ba.wb = last ? reinterpret_cast<const u32x4*>(h->wb_last)
-                 : reinterpret_cast<const u32x4*>(h->wb) + (size_t)(l - 1) * img_pieces;
-    ba.n_pb = n_pb; ba.slab = h->slab; ba.l0tab = h->l0tab; ba.sc_first = sc_first;
-  };
+  const int PBS = 2;
+  const BwdGrid g = bwd_grid(h, k);
+  const int n_wg = g.n_wg;
   for (int l = D - 1; l >= 0; --l) {
     const bool last = l == D - 1;
     const double rows = last ? h->cfg.out_features : WD;
-    ReduceArgs ra = zeroed<ReduceArgs>();
-    ra.slab = h->slab; ra.n_wg = n_wg; ra.accumulate = c > 0; ra.scale = 1.0f / h->gpre;
-    if (h->d8) {   // last layer: dW from the statically scaled residual; layers below: the chunk's adaptive pre-scale
-      ra.scale = (float)(1.0 / ((double)kResScale * (double)h->cfg.out_features * h->n_total));
-      ra.scale_dev = last ? nullptr : h->scale_dev;
-      ra.scale2_dev = (last || !h->lsc) ? nullptr : h->lsc + 16 + l;
-    }
-    ra.gW = h->grads + h->off_w[l]; ra.gb = h->grads + h->off_b[l];
-    // a layer above 0: rows x WD weight gradient from slabs of (last: 32, else WD) rows
-    ra.slab_rows = last ? 32 : WD; ra.slab_cols = WD; ra.rows_out = (int)rows; ra.cols_out = WD; ra.mode = 0;
+    ReduceArgs ra = reduce_args(h, c, l, n_wg);
     if (l > 0 && h->s8) {
       // layer 1: with fp8 deltas at width 256 the pipeline forward also spills layer 0's phase bytes, so this layer runs the
       // hidden-layer kernel (k_bwd8h) like the others; else the form that re-derives the layer-0 phases from the coordinates
       const bool l0_bytes = h->d8 && WD == 256 && fwd_is_pipe(h), p0 = l - 1 == 0 && !(l0_bytes && !last);
       Bwd8Args ba = zeroed<Bwd8Args>();
-      fill_layer(ba, l);
+      fill_bwd_layer(h, k, l, ba);
       ba.sse_part = sse_part; ba.n_part = n_part;
       ba.inv_chunk_values = 1.0 / ((double)h->cfg.out_features * (double)k.px);
       ba.n_values = (double)h->cfg.out_features * h->n_total;
@@ -253,25 +311,18 @@ int siren_bwd_chunk(sf_engine* h, long c, const float* sse_part, int n_part) {
       SF_TRY(launch_bwd8(h, last, p0, ba, ra.n_wg));
     } else if (l > 0) {
       const bool p0 = l - 1 == 0;
-      BwdLayerArgs ba = zeroed<BwdLayerArgs>();
-      fill_layer(ba, l);
-      ba.pb_per_wg = (int)pb_per_wg;
-      Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx,
-               npx * ((last ? 64.0 : WD * 2.0) + WD * (p0 ? 2.0 : 4.0)));
+      const BwdLayerArgs ba = bwd_layer_args(h, k, l, g);
+      Launch L(h, last ? K_BWD_LAST : (p0 ? K_BWD_L1 : K_BWD_HIDDEN), 4.0 * rows * WD * npx, bwd_layer_bytes(h, k, l));
       SF_TRY(launch_bwd(h, last, p0, ba, n_wg));
     } else {
-      Dw0Args da = zeroed<Dw0Args>();
-      fill_grid(h, k.pix0, da);
-      da.D = h->Dbuf; da.ks_total = WD / 16; da.ks_off = 0; da.n_pb = n_pb; da.slab = h->slab;
-      const long cap0 = (h->d8 && WD == 256) ? 2L * h->dw_wg : (long)h->dw_wg;      // k_dw0_8<256>: two workgroups per CU
-      ra.n_wg = (int)(n_pb < cap0 ? n_pb : cap0);
-      ra.slab_rows = WD; ra.slab_cols = 32; ra.rows_out = WD; ra.cols_out = 2; ra.mode = 1;
+      const Dw0Args da = dw0_args(h, k);
+      ra.n_wg = dw0_grid(h, k);
       Launch L(h, K_DW_FIRST, 4.0 * WD * npx, WD * (h->d8 ? 1.0 : 2.0) * npx);
       SF_TRY(launch_dw_first(h, da, ra.n_wg));
     }
-    const int n = ra.rows_out * ra.cols_out + ra.rows_out;
+    const int n = reduce_count(ra);
     Launch L(h, K_REDUCE, 0, (double)n_wg * n * 4.0);
-    if (l > 0 && !last)   // slab layout == flat gradient layout [W | b]
+    if (reduce_is_vec(h, l))   // slab layout == flat gradient layout [W | b]
       SF_TRY(launch(h, k_reduce_vec, (n / 4 + 7) / 8, 256, 0, h->slab, n_wg, n, n / 4, h->grads + h->off_w[l], ra.accumulate,
                     ra.scale, ra.scale_dev, ra.scale2_dev));
     else SF_TRY(launch_reduce(h, ra));

@@ -404,8 +404,10 @@ template <int BITS>
 DEV void fwd_render_out(const FwdArgs& a, const f32x16& acc, long pix, long pb, bool valid, int lane, int h);
 
 // RENDER (inference only, sf_render / sf_render16): TRAIN = false with fwd_render_out<BITS> in place of the residual epilogue
+// (fwd_body: the kernel's body as a function of its argument struct - k_fwd hands it the kernel argument, k_fwd_many
+//  (siren_many.hip) one row of a table of them)
 template <int WD, typename OP, bool TRAIN, bool S8 = false, bool RENDER = false, int BITS = 8>
-__global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
+DEV void fwd_body(const FwdArgs& a) {
   constexpr bool EVAL = IsEval<OP>::value;   // sf_eval: see OpEval
   static_assert(!RENDER || (!TRAIN && !S8), "RENDER is an evaluation form");
   static_assert(!EVAL || (!TRAIN && !S8 && !RENDER), "EVAL is an evaluation form, and not the RENDER one");
@@ -559,6 +561,8 @@ __global__ __launch_bounds__(512) void k_fwd(FwdArgs a) {
     fwd_sse_partial(a, fwd_residual<OP, TRAIN, S8>(a, acc, tgt, pix, pb, valid, lane, h), lane, wave, tid, sRed);
   }
 }
+template <int WD, typename OP, bool TRAIN, bool S8 = false, bool RENDER = false, int BITS = 8>
+__global__ __launch_bounds__(512) void k_fwd(FwdArgs a) { fwd_body<WD, OP, TRAIN, S8, RENDER, BITS>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // k_fwd_pipe: k_fwd for hidden = 256 and depth >= 3 as ONE software pipeline over all hidden layers.
@@ -1104,7 +1108,7 @@ struct BwdCase {
 };
 
 template <int WD, bool LAST, bool P0, typename OP>
-__global__ __launch_bounds__((BwdCase<WD, LAST, P0>::threads)) void k_bwd(BwdLayerArgs a) {
+DEV void bwd_body(const BwdLayerArgs& a) {
   using C = BwdCase<WD, LAST, P0>;
   constexpr int JW = C::JW, IW = C::IW, WAVES_R = C::WR, WAVES_C = C::WC, NB = C::NB;
   constexpr int NW = WAVES_R * WAVES_C;
@@ -1328,6 +1332,8 @@ __global__ __launch_bounds__((BwdCase<WD, LAST, P0>::threads)) void k_bwd(BwdLay
     }
   }
 }
+template <int WD, bool LAST, bool P0, typename OP>
+__global__ __launch_bounds__((BwdCase<WD, LAST, P0>::threads)) void k_bwd(BwdLayerArgs a) { bwd_body<WD, LAST, P0, OP>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // k_dw0: weight gradient of layer 0 (no data gradient below it): dW_0[j][c] = sum_pixels delta_0[pix][j] * x_c[pix].
@@ -1363,7 +1369,7 @@ struct Dw0Lds {
 };
 
 template <int JW, typename OP>
-__global__ __launch_bounds__(JW * 2) void k_dw0(Dw0Args a) {
+DEV void dw0_body(const Dw0Args& a) {
   using L = Dw0Lds<JW>;
   constexpr int NW = JW / 32, KSJ = JW / 16, NB = L::NB, PD = NB - 2, BLK = L::BLK;   // 96 KiB in flight at JW = 256
   constexpr int G_MIN = KSJ / NW;
@@ -1427,6 +1433,8 @@ __global__ __launch_bounds__(JW * 2) void k_dw0(Dw0Args a) {
   const float tsum = dbs + __shfl_xor(dbs, 32);
   if (hh == 0) slab[JW * 32 + 32 * wave + cl] = tsum;
 }
+template <int JW, typename OP>
+__global__ __launch_bounds__(JW * 2) void k_dw0(Dw0Args a) { dw0_body<JW, OP>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // k_reduce: flat gradient from the slabs, fixed summation order (workgroup 0, 1, 2, ...).
@@ -1449,7 +1457,7 @@ struct ReduceArgs {
 // 256 threads = 16 outputs x 16 slab groups: group g sums slabs g, g+16, ... (independent loads, issued ahead),
 // then the 16 partial sums are combined in fixed order 0..15 => deterministic, and the serial chain per output
 // is n_wg/16 loads instead of n_wg (these launches are pure latency on small fits).
-__global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) {
+DEV void reduce_body(const ReduceArgs& a) {
   __shared__ float sh[16][17];
   const long slab_sz = (long)a.slab_rows * a.slab_cols + a.slab_rows;
   const int nW = a.rows_out * a.cols_out;
@@ -1486,12 +1494,13 @@ __global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) {
     *dst = a.accumulate ? *dst + t : t;
   }
 }
+__global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) { reduce_body(a); }
 
 // Vectorised form for hidden layers, whose slab layout [W rows*cols | b rows] IS the flat-gradient
 // layout: out[i] = sum_w slab[w][i].  256 threads = 8 float4 columns x 32 slab groups; group g sums
 // slabs g, g+32, ... in order, groups are combined 0..31 in order (fixed order => deterministic).
-__global__ __launch_bounds__(256) void k_reduce_vec(const float* slab, int n_wg, long stride, int n4, float* out,
-                                                    int accumulate, float scale, const float* scale_dev, const float* scale2_dev) {
+DEV void reduce_vec_body(const float* slab, int n_wg, long stride, int n4, float* out, int accumulate, float scale,
+                         const float* scale_dev, const float* scale2_dev) {
   if (scale_dev) scale = scale_dev[1];
   if (scale2_dev) scale *= scale2_dev[0];      // (powers of two: exact)
   __shared__ f32x4 sh[32][8];
@@ -1515,10 +1524,14 @@ __global__ __launch_bounds__(256) void k_reduce_vec(const float* slab, int n_wg,
     *o = accumulate ? *o + t : t;
   }
 }
+__global__ __launch_bounds__(256) void k_reduce_vec(const float* slab, int n_wg, long stride, int n4, float* out,
+                                                    int accumulate, float scale, const float* scale_dev, const float* scale2_dev) {
+  reduce_vec_body(slab, n_wg, stride, n4, out, accumulate, scale, scale_dev, scale2_dev);
+}
 
 // sum of the per-workgroup SSE partials in double, fixed order
 // (loss_tab / iter: graph replay mode of sf_step — the per-step value also goes to loss_tab[*iter])
-__global__ void k_sse_reduce(const float* part, int n, double* out, double* loss_tab, const int* iter) {
+DEV void sse_reduce_body(const float* part, int n, double* out, double* loss_tab, const int* iter) {
   __shared__ double sh[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += (double)part[i];
@@ -1532,6 +1545,9 @@ __global__ void k_sse_reduce(const float* part, int n, double* out, double* loss
     *out = sh[0];
     if (loss_tab) loss_tab[*iter] = sh[0];
   }
+}
+__global__ void k_sse_reduce(const float* part, int n, double* out, double* loss_tab, const int* iter) {
+  sse_reduce_body(part, n, out, loss_tab, iter);
 }
 
 // sf_eval: k_sse_reduce's sum of the SSE partials (the same operations in the same order: the same double) and, beside it,
@@ -1567,7 +1583,7 @@ struct AdamArgs {
   const float* tab;   // graph replay mode: {step_size, bc2_sqrt} of step *iter (precomputed on the host in double)
   const int* iter;
 };
-__global__ void k_adam(AdamArgs a) {
+DEV void adam_body(AdamArgs a) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
   if (a.tab) {
@@ -1584,6 +1600,7 @@ __global__ void k_adam(AdamArgs a) {
   if (a.mask) p *= a.mask[i];
   a.p[i] = p; a.m[i] = m; a.v[i] = v;
 }
+__global__ void k_adam(AdamArgs a) { adam_body(a); }
 
 // ---------------------------------------------------------------------------------------------
 // k_images: rebuild every low-precision weight image from the fp32 master parameters
@@ -1677,7 +1694,7 @@ __global__ void k_fp8_links(Fp8ScaleArgs a) {
   }
 }
 
-__global__ void k_images(ImgArgs a) {
+DEV void images_body(const ImgArgs& a) {
   const int WD = a.WD, NT = WD / 32, KS = WD / 16;
   const FwdGeom G(WD);
   const long per_layer = (long)WD * WD;
@@ -1752,5 +1769,6 @@ __global__ void k_images(ImgArgs a) {
     reinterpret_cast<u32x4*>(a.l0img)[gid] = v;
   }
 }
+__global__ void k_images(ImgArgs a) { images_body(a); }
 
 }  // namespace sf

@@ -193,6 +193,10 @@ _declare("core", {
     "sf_eval": [H, P(C.c_double), P(C.c_uint64)],
     "sf_sse8_ptr": [H, P(C.c_void_p)],
 })
+# (n_steps steps of several fits of one shape in one launch per kernel, sf_step_many in csrc/many_host.hip.  In "core" like
+# sf_eval: has_step_many asks for the symbol itself, train_helper.train_steps_many routes by it)
+_declare("core", {"sf_step_many": [P(H), I32, P(C.c_float), I32, P(C.c_float)]})
+STEP_MANY_MAX = 64      # SF_STEP_MANY_MAX
 
 
 def load_library():
@@ -281,6 +285,11 @@ def has_eval(lib) -> bool:
     return all(hasattr(lib, n) for n in ("sf_eval", "sf_sse8_ptr"))
 
 
+def has_step_many(lib) -> bool:
+    """sf_step_many: the training steps of several fits of one shape, one launch per kernel (csrc/many_host.hip)"""
+    return hasattr(lib, "sf_step_many")
+
+
 def _require(lib, has, entry: str, since: str):
     """a library that lacks an optional group: say which entry point is missing and how to get it"""
     if not has(lib):
@@ -314,6 +323,34 @@ def _f32_cuda(t: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
     if n is not None and t.numel() != n:
         raise ValueError(f"expected {n} elements, got {t.numel()}")
     return t
+
+
+def step_many(engines, lrs, want_loss: bool = False):
+    """sf_step_many on the handles of `engines` (SirenEngine, one shape, one stream): lrs[s][b] is the learning rate of step
+    s for member b.  Each member ends where its own step(column b) would, bit for bit.  The losses as a list per member
+    (loss[b][s], one read at the end), or None."""
+    lib = load_library()
+    _require(lib, has_step_many, "sf_step_many entry point", "the batched training step")
+    B, n = len(engines), len(lrs)
+    if any(len(row) != B for row in lrs):
+        raise ValueError(f"step_many: every row of lrs needs {B} learning rates")
+    hs = (C.c_void_p * max(B, 1))(*[e.h for e in engines])
+    arr = (C.c_float * max(n * B, 1))(*[float(v) for row in lrs for v in row])
+    out = (C.c_float * max(n * B, 1))() if want_loss else None
+    _check(lib.sf_step_many(hs, B, arr, n, out))
+    return [[out[s * B + b] for s in range(n)] for b in range(B)] if want_loss else None
+
+
+def step_many_refusal(engines):
+    """what sf_step_many says to these members, without running anything: a call of zero steps makes every check and
+    launches, allocates and changes nothing.  None: it takes them; else the library's message"""
+    lib = load_library()
+    B = len(engines)
+    if any(getattr(e, "h", None) is None for e in engines):
+        return "sf_step_many: a member has no engine handle"
+    hs = (C.c_void_p * max(B, 1))(*[e.h for e in engines])
+    lr = (C.c_float * 1)(0.0)
+    return None if lib.sf_step_many(hs, B, lr, 0, None) == 0 else lib.sf_last_error().decode()
 
 
 class SirenEngine:

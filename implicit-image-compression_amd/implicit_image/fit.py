@@ -33,7 +33,9 @@ from .pipeline.feathermap import FeatherNet
 from .pipeline.feathermap.feathernet import DEEPCOPY_UNSUPPORTED, PIXEL_SPLIT_UNSUPPORTED as FEATHER_SPLIT_UNSUPPORTED
 from .pipeline.quant import Quantize
 from .utils.train_helper import (SPLIT_EVAL_EPOCH_UNSUPPORTED, SPLIT_PADDED_UNSUPPORTED, device_eval_wanted, eval_epoch,
-                                 eval_metrics, get_device, get_optimizer_lr_scheduler, setup_mask, train_epoch, train_steps)
+                                 eval_metrics, get_device, get_optimizer_lr_scheduler, setup_mask, train_epoch, train_steps,
+                                 train_steps_many)
+from .utils import train_helper
 
 REPO = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 
@@ -77,14 +79,33 @@ def check_pixel_split(cfg: Cfg, world: int = 1):
                                   "(every rank needs a row)")
 
 
-def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None, rank: int = None, world: int = None):
-    """One fit; returns dict(loss, PSNR, PSNR_8bit, steps, seconds).
+class _Fit:
+    """One fit between its phases (_setup, the step loop, _finish): what fit_one holds in local variables, so that
+    fit_group can run the same phases for several fits at once.  rng: the CPU and device generator states the fit owns
+    (fit_group swaps them in around every piece of the fit's host work; fit_one never touches them)."""
 
-    train.pixel_split: rank `rank` of `world` (default: RANK / WORLD_SIZE, a world of one without them) fits rows
-    shard_rows(H, world, rank) of the picture; the model carries a parallel.RowSplit, under which every step and every
-    evaluation reduces over the ranks (utils/train_helper.py).  Seed, init, mask draw and schedules are the ordinary fit's on
-    every rank, so the replicas stay identical; every rank returns the same dict, rank 0 alone writes into out_dir.  The
-    caller has initialised torch.distributed when world > 1 (main does)."""
+    def __init__(self, cfg: Cfg, device: torch.device):
+        self.cfg, self.device = cfg, device
+        self.rng = None
+
+    @contextlib.contextmanager
+    def own_random_state(self):
+        """the fit's generators while its host work runs: restored on entry (once there is a state: the set-up seeds them
+        itself), saved on exit"""
+        cuda = self.device.type == "cuda"
+        if self.rng is not None:
+            torch.set_rng_state(self.rng[0])
+            if cuda:
+                torch.cuda.set_rng_state(self.rng[1], self.device)
+        try:
+            yield self
+        finally:
+            self.rng = (torch.get_rng_state(), torch.cuda.get_rng_state(self.device) if cuda else None)
+
+
+def _setup(cfg: Cfg, device: torch.device, rank: int = None, world: int = None) -> _Fit:
+    """everything of a fit before its first step: refusals, seed, picture, grid, model, optimiser, mask, the evaluation route"""
+    f = _Fit(cfg, device)
     split = None
     if pixel_split_wanted(cfg):
         rank = int(os.environ.get("RANK", "0")) if rank is None else rank
@@ -117,48 +138,70 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None, rank: int = Non
         split = RowSplit(cfg.img.height, rank, world, row_coords=grid[:, 0, 0].contiguous())
         model.set_row_split(split)
         grid, img = grid[split.row_begin:split.row_end], img[split.row_begin:split.row_end].contiguous()
-    writes = split is None or split.rank == 0                                      # rank 0 alone writes the artefacts
-    model, grid, img = model.to(device), grid.to(device), img.to(device)          # compress.py:84-86
-    model.train()
-    optim, lr_scheduler = get_optimizer_lr_scheduler(model, cfg.optim)             # compress.py:105
+    f.feather = feather
+    f.writes = split is None or split.rank == 0                                    # rank 0 alone writes the artefacts
+    f.model, f.grid, f.img = model.to(device), grid.to(device), img.to(device)    # compress.py:84-86
+    f.model.train()
+    f.optim, f.lr_scheduler = get_optimizer_lr_scheduler(f.model, cfg.optim)       # compress.py:105
     mult = cfg.train.multiplier
-    num_steps = cfg.train.num_steps * mult                                         # compress.py:110-120
+    f.num_steps = cfg.train.num_steps * mult                                       # compress.py:110-120
     mcfg = copy.deepcopy(cfg.get("masking")) if cfg.get("masking") else None
     if mcfg:
         if mcfg.get("end_when"):
             mcfg.end_when = int(mcfg.end_when * mult)
         if mcfg.get("interval"):
             mcfg.interval = int(mcfg.interval * mult)
-    mask = setup_mask(model, optim, mcfg)                                          # compress.py:127
+    f.mcfg = mcfg
+    f.mask = setup_mask(f.model, f.optim, mcfg)                                    # compress.py:127
     # the three figures of an evaluation; the prediction eval_epoch returns is not used here.  train.device_eval auto: sf_eval
     # (no picture stored, one read), off: eval_epoch.  Same loss and PSNR; PSNR_8bit exact instead of torch's fp32 mean
     if device_eval_wanted(cfg.train.get("device_eval", "auto")):
-        evaluate = eval_metrics
+        f.evaluate = eval_metrics
     else:
         def evaluate(m, g, im):
             return eval_epoch(m, g, im)[1:]
-    t0, last = time.time(), {}
-    i = -1
-    while i + 1 < num_steps:                                                       # compress.py:137-170
-        # the iterations up to the next one that needs the host (topology update / logging) go to the engine
-        # in one call; train_steps() is bit-identical to calling train_epoch() once per iteration
-        first = i + 1
-        i = first
-        while not ((mask and i <= mcfg.end_when and i % mcfg.interval == 0)
-                   or (i + 1) % cfg.train.log_steps == 0 or i + 1 == num_steps):
-            i += 1
-        train_steps(model, optim, grid, img, i - first + 1, lr_scheduler=lr_scheduler, mask=mask)
-        if mask and i <= mcfg.end_when and i % mcfg.interval == 0:
-            mask.update_connections()
-        if (i + 1) % cfg.train.log_steps == 0 or i + 1 == num_steps:
-            loss, psnr, psnr8 = evaluate(model, grid, img)
-            last = {"loss": loss, "PSNR": psnr, "PSNR_8bit": psnr8}
-            msg = f"Train | Step: {i + 1} | " + " | ".join(f"{k}: {v:.4f}" for k, v in last.items())
-            if mask:
-                msg += f" | Prune Rate: {mask.prune_rate:.4f} | Density: {mask.stats.total_density:.4f}"
-            logging.info(msg)
-    last.update(steps=num_steps, seconds=time.time() - t0)
-    if feather:
+        f.evaluate = evaluate
+    f.t0, f.last = time.time(), {}
+    return f
+
+
+def _update_due(f: _Fit, i: int) -> bool:
+    """iteration i ends with a topology update"""
+    return bool(f.mask and i <= f.mcfg.end_when and i % f.mcfg.interval == 0)
+
+
+def _log_due(f: _Fit, i: int) -> bool:
+    return (i + 1) % f.cfg.train.log_steps == 0 or i + 1 == f.num_steps
+
+
+def _next_boundary(f: _Fit, first: int) -> int:
+    """the iterations from `first` up to the next one that needs the host (topology update / logging) go to the engine in
+    one call: the last of them"""
+    i = first
+    while not (_update_due(f, i) or _log_due(f, i)):
+        i += 1
+    return i
+
+
+def _after_steps(f: _Fit, i: int):
+    """what the host does after iteration i: the topology update, the evaluation and its log line"""
+    if _update_due(f, i):
+        f.mask.update_connections()
+    if _log_due(f, i):
+        loss, psnr, psnr8 = f.evaluate(f.model, f.grid, f.img)
+        f.last = {"loss": loss, "PSNR": psnr, "PSNR_8bit": psnr8}
+        msg = f"Train | Step: {i + 1} | " + " | ".join(f"{k}: {v:.4f}" for k, v in f.last.items())
+        if f.mask:
+            msg += f" | Prune Rate: {f.mask.prune_rate:.4f} | Density: {f.mask.stats.total_density:.4f}"
+        logging.info(msg)
+
+
+def _finish(f: _Fit, out_dir: str = None):
+    """everything of a fit after its last step: the quantise phase, the artefacts, the result"""
+    cfg, model, grid, img, mask, evaluate, num_steps, writes = f.cfg, f.model, f.grid, f.img, f.mask, f.evaluate, f.num_steps, f.writes
+    last = f.last
+    last.update(steps=num_steps, seconds=time.time() - f.t0)
+    if f.feather:
         last.update({"Stored Params": model.num_stored(), "Dense Params": model.get_num_WandB()})
     quantized_model = None
     if cfg.get("quant"):                                                           # compress.py:172-240
@@ -210,11 +253,136 @@ def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None, rank: int = Non
             last["Compressed Bytes"] = nbytes
             logging.info(f"Compressed bytes {nbytes}")
         if writes:
-            with open(os.path.join(out_dir, "result.json"), "w") as f:
-                json.dump(last, f)
+            with open(os.path.join(out_dir, "result.json"), "w") as fh:
+                json.dump(last, fh)
             from .decode import write_decode_json                                  # what `make decode` rebuilds the network from
             write_decode_json(out_dir, cfg, list(model.state_dict().keys()))
     return last
+
+
+def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None, rank: int = None, world: int = None):
+    """One fit; returns dict(loss, PSNR, PSNR_8bit, steps, seconds).
+
+    train.pixel_split: rank `rank` of `world` (default: RANK / WORLD_SIZE, a world of one without them) fits rows
+    shard_rows(H, world, rank) of the picture; the model carries a parallel.RowSplit, under which every step and every
+    evaluation reduces over the ranks (utils/train_helper.py).  Seed, init, mask draw and schedules are the ordinary fit's on
+    every rank, so the replicas stay identical; every rank returns the same dict, rank 0 alone writes into out_dir.  The
+    caller has initialised torch.distributed when world > 1 (main does)."""
+    f = _setup(cfg, device, rank, world)
+    i = -1
+    while i + 1 < f.num_steps:                                                     # compress.py:137-170
+        # the iterations up to the next one that needs the host (topology update / logging) go to the engine
+        # in one call; train_steps() is bit-identical to calling train_epoch() once per iteration
+        first = i + 1
+        i = _next_boundary(f, first)
+        train_steps(f.model, f.optim, f.grid, f.img, i - first + 1, lr_scheduler=f.lr_scheduler, mask=f.mask)
+        _after_steps(f, i)
+    return _finish(f, out_dir)
+
+
+# ---- train.batch_jobs: several fits of one shape at once (sf_step_many) -------------------------------------------------------
+BATCH_JOBS_MAX = 64                      # SF_STEP_MANY_MAX
+# what the members of a group may differ in; everything else of their configurations is equal
+GROUP_FREE_KEYS = ("seed", "exp_name", "img.name", "img.path", "img.seed", "optim.lr", "masking.density",
+                   "masking.prune_rate", "masking.sparse_init")
+
+
+def batch_jobs_setting(cfg: Cfg) -> int:
+    """train.batch_jobs (default 1): how many jobs of a sweep a rank fits at once, 1 .. 64"""
+    v = cfg.train.get("batch_jobs", 1)
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= BATCH_JOBS_MAX:
+        raise ValueError(f"train.batch_jobs: an integer from 1 to {BATCH_JOBS_MAX}, got {v!r}")
+    return v
+
+
+def _plain(x):
+    if isinstance(x, dict):
+        return {k: _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_plain(v) for v in x]
+    return x
+
+
+def group_key(cfg: Cfg):
+    """What decides whether two jobs can share a group: None for a job that joins none (not mlp=siren, Feathermap,
+    pixel_split, an engine width that is zero-padded or above 128), else the configuration without GROUP_FREE_KEYS as text"""
+    masking = cfg.get("masking") or {}
+    if cfg.mlp.name != "siren" or masking.get("name") == "Feathermap" or pixel_split_wanted(cfg):
+        return None
+    small = masking.get("density") if masking.get("name") == "Small_Dense" else 1.0
+    hidden = int(cfg.mlp.hidden_size * np.sqrt(small))                             # (Siren's own Small_Dense width)
+    if next_kernel_width(hidden, Siren.WIDTHS) != hidden or hidden > 128:
+        return None
+    rest = _plain(cfg)
+    for dotted in GROUP_FREE_KEYS:
+        d, keys = rest, dotted.split(".")
+        for k in keys[:-1]:
+            d = d.get(k) if isinstance(d, dict) else None
+        if isinstance(d, dict):
+            d.pop(keys[-1], None)
+    return json.dumps(rest, sort_keys=True, default=repr)
+
+
+def group_jobs(cfgs, n: int):
+    """The jobs of a rank (their configurations, in job order) as groups of at most n: lists of job indices, every job in
+    exactly one.  Jobs share a group when group_key gives them the same text; a job goes to the earliest group of its key
+    that has room, else it opens one; a job without a key is a group of its own.  Members stay in job order, groups in the
+    order of their first members.  A pure function of its arguments."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= BATCH_JOBS_MAX:
+        raise ValueError(f"group_jobs: n must be an integer from 1 to {BATCH_JOBS_MAX}, got {n!r}")
+    groups, open_by_key = [], {}
+    for j, cfg in enumerate(cfgs):
+        key = group_key(cfg) if n > 1 else None
+        g = open_by_key.get(key) if key is not None else None
+        if g is None or len(g) >= n:
+            g = []
+            groups.append(g)
+            if key is not None:
+                open_by_key[key] = g
+        g.append(j)
+    return groups
+
+
+def fit_group(cfgs, device: torch.device, out_dirs=None):
+    """The fits of one group (group_jobs) at once; returns their fit_one dicts in order.
+
+    fit_one's loop runs once for all members: the same boundaries (they follow from keys the members share), between them
+    train_steps_many - one sf_step_many call where the members qualify, train_steps per member where not - then each member's
+    topology update and evaluation.  After the loop each member's quantise phase, artefacts and run directory are written by
+    fit_one's own code (_finish), one member after the other.
+    Every member owns the CPU and device generator states its torch.manual_seed(cfg.seed) gave it: they are swapped in before
+    any host work of the member (set-up, topology update, evaluation, quantise phase) and saved after, so every draw falls as
+    in a run of the member alone, and result.json apart from `seconds`, model.pth and the container are byte for byte those
+    of train.batch_jobs=1."""
+    out_dirs = list(out_dirs) if out_dirs is not None else [None] * len(cfgs)
+    fits = []
+    for cfg in cfgs:
+        f = _Fit(cfg, device)                 # (a throw-away holder of the random state while _setup builds the real one)
+        with f.own_random_state():
+            g = _setup(cfg, device)
+        g.rng = f.rng
+        fits.append(g)
+    head = fits[0]
+    if any(g.num_steps != head.num_steps or bool(g.mask) != bool(head.mask) for g in fits):
+        raise ValueError("fit_group: the members differ in their step count or in having a mask (group_jobs keeps such jobs apart)")
+    t0 = time.time()
+    for g in fits:
+        g.t0 = t0
+    i = -1
+    while i + 1 < head.num_steps:
+        first = i + 1
+        i = _next_boundary(head, first)
+        train_steps_many([g.model for g in fits], [g.optim for g in fits], head.grid, [g.img for g in fits], i - first + 1,
+                         lr_schedulers=[g.lr_scheduler for g in fits], masks=[g.mask for g in fits],
+                         scopes=[g.own_random_state for g in fits])
+        for g in fits:
+            with g.own_random_state():
+                _after_steps(g, i)
+    results = []
+    for g, out_dir in zip(fits, out_dirs):
+        with g.own_random_state():
+            results.append(_finish(g, out_dir))
+    return results
 
 
 def main(argv=None):
@@ -226,6 +394,13 @@ def main(argv=None):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     cfgs = [load_config(conf_dir, ov) for ov in jobs]
     split = [pixel_split_wanted(c) for c in cfgs]
+    batch = {batch_jobs_setting(c) for c in cfgs}
+    if len(batch) != 1:
+        raise ValueError("train.batch_jobs is one setting for the whole sweep")
+    batch = batch.pop()
+    if batch > 1 and any(split):                               # before the GPU and the process group are touched
+        raise ValueError("train.batch_jobs > 1 with train.pixel_split=true: a fit split by image rows steps with a collective "
+                         "between its kernels and joins no group; use one or the other")
     grouped = False
     if any(split):
         # one picture across the ranks: EVERY job on EVERY rank, in order; what is refused is refused here, on every rank
@@ -241,16 +416,29 @@ def main(argv=None):
         jobs, cfgs = shard_jobs(jobs, world, rank), shard_jobs(cfgs, world, rank)
     results = []
     try:
-        for ov, cfg in zip(jobs, cfgs):
-            device = get_device(cfg.device)
-            if device.type == "cuda":
-                device = torch.device("cuda", local_rank)
-                torch.cuda.set_device(device)
-            tag = ",".join(o for o in ov if not o.startswith(("exp_name", "img.name"))) or "default"
-            out_dir = os.path.join("outputs", str(cfg.img.name), str(cfg.exp_name), tag.replace("/", "_"))
-            res = fit_one(cfg, device, out_dir, rank, world) if any(split) else fit_one(cfg, device, out_dir)
-            logging.info(f"[rank {rank}] {tag}: {res}")
-            results.append((tag, res))
+        # train.batch_jobs = 1: every job is a group of its own, in job order - the loop this has always been
+        for members in group_jobs(cfgs, batch):
+            tags, out_dirs = [], []
+            for j in members:
+                ov, cfg = jobs[j], cfgs[j]
+                device = get_device(cfg.device)
+                if device.type == "cuda":
+                    device = torch.device("cuda", local_rank)
+                    torch.cuda.set_device(device)
+                tags.append(",".join(o for o in ov if not o.startswith(("exp_name", "img.name"))) or "default")
+                out_dirs.append(os.path.join("outputs", str(cfg.img.name), str(cfg.exp_name), tags[-1].replace("/", "_")))
+            if len(members) == 1:
+                cfg = cfgs[members[0]]
+                done = [fit_one(cfg, device, out_dirs[0], rank, world) if any(split) else fit_one(cfg, device, out_dirs[0])]
+            else:
+                before = dict(train_helper.MANY_STATS)
+                done = fit_group([cfgs[j] for j in members], device, out_dirs)
+                took = {k: v - before[k] for k, v in train_helper.MANY_STATS.items()}
+                logging.info(f"[rank {rank}] group of {len(members)}: {took['steps']} steps each in {took['calls']} sf_step_many "
+                             f"calls, {took['fallbacks']} stretches member by member")
+            for tag, res in zip(tags, done):
+                logging.info(f"[rank {rank}] {tag}: {res}")
+                results.append((tag, res))
     finally:
         if grouped:
             torch.distributed.destroy_process_group()

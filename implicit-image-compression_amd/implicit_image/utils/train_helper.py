@@ -3,6 +3,8 @@
   train_epoch(model, optim, grid, img, **kwargs) -> float          (:132-185)
   eval_epoch(model, grid, img, **kwargs) -> (pred, loss, PSNR, PSNR_8bit)   (:41-59)
   eval_metrics(model, grid, img) -> (loss, PSNR, PSNR_8bit)       eval_epoch's figures without its prediction (sf_eval)
+  train_steps_many(models, optims, grid, imgs, n, lr_schedulers, masks) -> list of loss lists    train_steps for several
+                                                                       fits of one shape at once (sf_step_many)
   get_optimizer_lr_scheduler(model, optim_cfg, quantize_mode=False)  (:69-86)
   setup_mask(model, optim, masking_cfg)                               (:89-129)
   get_device(device_str)                                               (:62-66)
@@ -10,7 +12,9 @@
 One `train_epoch` is one full-batch fit step executed by the HIP engine: forward + MSE + backward
 (sf_forward_backward) and Adam(+mask) (sf_adam_step through the optimiser facade).
 """
+import contextlib
 import ctypes
+import logging
 import math
 from typing import Dict, Tuple
 
@@ -235,6 +239,20 @@ def _quant_phase(model: Module, optim: Optimizer):
     return kq if (pre[0] == kq._pre and post[0] == kq._post and kq.device_wanted()) else None
 
 
+def _plain(model: Module, optim: Optimizer, **kwargs) -> bool:
+    """the engine's own state, optimiser and loss: what both bulk routes of train_steps need"""
+    return (model.state_is_live and isinstance(optim, EngineAdam) and kwargs.get("criterion", F.mse_loss) is F.mse_loss
+            and kwargs.get("preconditioner") is None)
+
+
+def _bulk(model: Module, optim: Optimizer, n: int, **kwargs) -> bool:
+    """train_steps' condition for handing n steps to the engine in one sf_step call: nothing on the host has to look at the
+    state between two steps"""
+    mask = kwargs.get("mask")
+    return (n > 1 and _plain(model, optim, **kwargs) and not model.post_backward_callbacks
+            and (mask is None or mask.steps_need_no_host))
+
+
 def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     """`n` consecutive train_epoch() calls, returned as the list of their losses.
 
@@ -253,8 +271,7 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     mask: Masking = kwargs.get("mask")
     lr_scheduler = kwargs.get("lr_scheduler")
     pbar = kwargs.get("pbar")
-    plain = (model.state_is_live and isinstance(optim, EngineAdam) and kwargs.get("criterion", F.mse_loss) is F.mse_loss
-             and kwargs.get("preconditioner") is None)
+    plain = _plain(model, optim, **kwargs)
     kq = _quant_phase(model, optim) if (plain and n >= 1 and mask is None) else None
     if kq is not None:
         model.train()
@@ -277,9 +294,7 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
         if pbar:
             pbar.update(n)
         return losses
-    bulk = (n > 1 and plain and not model.post_backward_callbacks
-            and (mask is None or mask.steps_need_no_host))
-    if not bulk:
+    if not _bulk(model, optim, n, **kwargs):
         return [train_epoch(model, optim, grid, img, **kwargs) for _ in range(n)]
     model.train()
     model.engine(grid, img)
@@ -297,6 +312,83 @@ def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
         mask.count_steps(n)
     if pbar:
         pbar.update(n)
+    return losses
+
+
+# what train_steps_many did, for callers that report it (fit.py logs it per group; tests read it): batched calls, the steps
+# they took (per member), and groups that went member by member
+MANY_STATS = {"calls": 0, "steps": 0, "fallbacks": 0}
+_many_fallback_logged = set()
+
+
+def train_steps_many(models, optims, grid, imgs, n: int, lr_schedulers=None, masks=None, scopes=None):
+    """train_steps(models[b], optims[b], grid, imgs[b], n, lr_scheduler=lr_schedulers[b], mask=masks[b]) for every member b,
+    returned as the list of their loss lists.
+
+    When every member meets train_steps' own bulk condition (_bulk: the n steps of a member would be ONE sf_step), the library
+    has sf_step_many and the handles pass its checks (one shape, hidden <= 128, fp16 operands, scratch format 16, one chunk,
+    the whole picture, one stream: include/siren_fit.h), the n steps of ALL members are one sf_step_many call: every kernel of
+    a step is launched once for all of them, and each member ends bit for bit where its own sf_step would.  The host
+    bookkeeping per member is train_steps': optim.prepare, mask.push_masks_once, count_steps, the scheduler run ahead.
+    Otherwise train_steps once per member, in order; why is logged once per reason.
+
+    scopes: one callable per member that returns a context manager, entered around that member's host work (fit.py: the
+    member's random state); default: none."""
+    B = len(models)
+    lr_schedulers = list(lr_schedulers) if lr_schedulers is not None else [None] * B
+    masks = list(masks) if masks is not None else [None] * B
+    scopes = list(scopes) if scopes is not None else [contextlib.nullcontext] * B
+    if not (len(optims) == len(imgs) == len(lr_schedulers) == len(masks) == len(scopes) == B):
+        raise ValueError("train_steps_many: one optimiser, picture, scheduler, mask and scope per model")
+
+    def one_by_one(why):
+        if why not in _many_fallback_logged:
+            _many_fallback_logged.add(why)
+            logging.info(f"train_steps_many: member by member ({why})")
+        MANY_STATS["fallbacks"] += 1
+        out = []
+        for b in range(B):
+            with scopes[b]():
+                out.append(train_steps(models[b], optims[b], grid, imgs[b], n, lr_scheduler=lr_schedulers[b], mask=masks[b]))
+        return out
+
+    if B == 0:
+        return []
+    if B == 1:      # measured (profiles/step_many_bench.json): one fit through the tables is slower than its own eager sf_step
+        with scopes[0]():
+            return [train_steps(models[0], optims[0], grid, imgs[0], n, lr_scheduler=lr_schedulers[0], mask=masks[0])]
+    if any(getattr(m, "row_split", None) is not None for m in models):
+        return one_by_one("a fit split by image rows")
+    if not all(_bulk(models[b], optims[b], n, mask=masks[b]) for b in range(B)):
+        return one_by_one("a member's steps need the host between them, or fewer than two steps")
+    if B > _engine.STEP_MANY_MAX:
+        return one_by_one(f"more than {_engine.STEP_MANY_MAX} members")
+    engines = []
+    for b in range(B):
+        with scopes[b]():
+            models[b].train()
+            models[b].engine(grid, imgs[b])
+            engines.append(optims[b].prepare())
+            if masks[b] is not None:
+                masks[b].push_masks_once()
+    if not _engine.has_step_many(engines[0].lib):
+        return one_by_one("the library has no sf_step_many entry point: rebuild it")
+    why = _engine.step_many_refusal(engines)
+    if why is not None:
+        return one_by_one(why)
+    lrs = [[0.0] * B for _ in range(n)]
+    for b in range(B):
+        optims[b].count_steps(n)             # (first: the scheduler looks for the optimiser's mark at its first step)
+        for s in range(n):                   # the schedule is host-side bookkeeping: run it ahead
+            lrs[s][b] = float(optims[b].param_groups[0]["lr"])
+            if lr_schedulers[b]:
+                lr_schedulers[b].step()
+    losses = _engine.step_many(engines, lrs, want_loss=True)
+    for b in range(B):
+        if masks[b] is not None:
+            masks[b].count_steps(n)
+    MANY_STATS["calls"] += 1
+    MANY_STATS["steps"] += n
     return losses
 
 

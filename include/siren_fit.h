@@ -519,6 +519,22 @@ int sf_adam_step(sf_handle* h, float lr);
 /* n_steps x (forward_backward + adam_step) with learning rates lr[0..n_steps) (host array);
  * loss_out (host, may be NULL) receives the MSE of every step (length n_steps) */
 int sf_step(sf_handle* h, const float* lr, int32_t n_steps, float* loss_out);
+/* n_steps training steps of n_fits fits of ONE shape, every kernel of a step launched once for all of them (grid: the single
+ * fit's grid x n_fits; csrc/siren_many.hip).  lr: host [n_steps][n_fits]; loss_out: host [n_steps][n_fits] or NULL.
+ * For every member b the call is sf_step on h[b] with column b of lr and of loss_out, bit for bit: parameters, gradient,
+ * both moments, the step counter, the reported losses, and whatever a later call on the member computes.  The launches per
+ * step do not depend on n_fits; they are eager launches on the members' common stream (no graph capture); the call
+ * synchronises with the host once, to read the losses, and not at all with loss_out NULL.  The argument tables, the per-step
+ * scalars and the step counter live in device memory of h[0]; the profile records of the call are h[0]'s, one per launch.
+ * Members may differ in parameters, target, mask (set or not), step count and learning rate.
+ * Refused before anything is launched, allocated or changed on any handle, with "sf_step_many" and the offending member's
+ * index in the message - SF_ERR_INVALID: a null argument, n_fits < 1 or > SF_STEP_MANY_MAX, n_steps < 0, the same handle
+ * twice, a render handle, a FourierNet or WaveletSiren handle, a Feathermap handle, hidden > 128, compute_dtype other than
+ * SF_F16, a scratch format other than 16 at the time of the call, more than one chunk, a row range other than the whole
+ * picture, members that differ in height, width, hidden, depth, out_features, the omegas, outermost_linear, betas, eps,
+ * device or stream; SF_ERR_STATE: coordinates or target not set. */
+#define SF_STEP_MANY_MAX 64
+int sf_step_many(sf_handle* const* h, int32_t n_fits, const float* lr, int32_t n_steps, float* loss_out);
 /* sf_step execution mode for single-chunk fits: 0 (default) = one stream launch per kernel, 1 = capture one
  * training step into a hipGraph and replay it n_steps times.  Results are bit-identical; which is faster is a
  * property of the runtime (measured on ROCm 7.2 / MI355X: eager 73 us/step vs replay 87 us/step at SIREN 64x4
