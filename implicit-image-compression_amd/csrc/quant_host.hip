@@ -1,7 +1,7 @@
 // quant_host.hip — the quantise phase of a fit (siren_quant.hip states what it computes) on the host: the three entry points
 // sf_quant_pass, sf_quant_nudge and sf_quant_step, and what they share under the caller's name - the refusals, the layer table,
 // the launches.  Every refusal comes before anything is allocated or launched.  Included by siren_fit.hip behind the
-// model-independent entry points (sf_quant_step runs their pass and their Adam step).
+// model-independent entry points (sf_quant_step is their eager_steps with the pass before and the nudge after each step's pass).
 
 namespace {
 
@@ -114,18 +114,9 @@ int sf_quant_step(sf_handle* h, const sf_quant_args* a, const float* lr, int32_t
   if (!h->have_coords) return fail(SF_ERR_STATE, "sf_quant_step: sf_set_coords has not been called");
   if (!h->img) return fail(SF_ERR_STATE, "sf_quant_step: sf_set_target has not been called");
   DevGuard dev_guard(h->cfg.device);
-  const bool table = loss_out && n_steps > 0;
-  if (table) SF_TRY(graph_prepare(h, n_steps));
-  for (int i = 0; i < n_steps; ++i) {
-    SF_TRY(quant_pass(h, k, a->iter_limit, n_max, bytes));
-    h->graph.loss_dst = table ? h->graph.loss_tab + i : nullptr;
-    const int rc = run_pass(h, true, nullptr, true);
-    h->graph.loss_dst = nullptr;
-    if (rc) return rc;
-    SF_TRY(quant_nudge(h, k, bytes));
-    SF_TRY(adam_step(h, lr[i], false));   // (the next pass - of this call, of an eval - rewrites the weights first: one refresh)
-  }
-  return table ? read_losses(h, n_steps, loss_out) : SF_OK;
+  // (refresh = false: the next pass - of this call, of an eval - rewrites the weights first: one refresh)
+  return eager_steps(h, lr, n_steps, loss_out, loss_out && n_steps > 0, false,
+                     [&] { return quant_pass(h, k, a->iter_limit, n_max, bytes); }, [&] { return quant_nudge(h, k, bytes); });
 } SF_CATCH
 
 }  // extern "C"

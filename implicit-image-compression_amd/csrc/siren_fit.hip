@@ -536,18 +536,15 @@ static int step_replay(sf_engine* h, const float* lr, int n, float* loss_out) {
   return SF_OK;
 }
 
-int sf_step(sf_handle* h, const float* lr, int32_t n_steps, float* loss_out) try {
-  if (!h || !lr || n_steps < 0) return fail(SF_ERR_INVALID, "bad argument");
-  SF_NO_RENDER(h, "sf_step");
-  DevGuard dev_guard(h->cfg.device);
-  if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
-  if (!h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
-  if (h->graph.want && n_steps >= 2 && !h->ctx->prof && h->npix <= h->chunk_px) return step_replay(h, lr, n_steps, loss_out);
-  // eager.  With more than one loss to report there is no host sync per step: every step's SSE goes to a device table, read
-  // back once; a single loss is read from the handle's scalar
-  const bool table = loss_out && n_steps > 1;
-  if (table) SF_TRY(graph_prepare(h, n_steps));
-  for (int i = 0; i < n_steps; ++i) {
+// The eager run of n steps, for sf_step and sf_quant_step: per step `before` (if given), the pass, `after` (if given), Adam at
+// lr[i] (refresh: adam_step's).  With `table` there is no host sync per step: every step's SSE goes to a device table, read back
+// once at the end; without it a loss to report is read from the handle's scalar after each pass.
+using StepHook = std::function<int()>;
+static int eager_steps(sf_engine* h, const float* lr, int n, float* loss_out, bool table, bool refresh,
+                       const StepHook& before = nullptr, const StepHook& after = nullptr) {
+  if (table) SF_TRY(graph_prepare(h, n));
+  for (int i = 0; i < n; ++i) {
+    if (before) SF_TRY(before());
     h->graph.loss_dst = table ? h->graph.loss_tab + i : nullptr;
     const int rc = run_pass(h, true, nullptr, true);
     h->graph.loss_dst = nullptr;
@@ -557,9 +554,20 @@ int sf_step(sf_handle* h, const float* lr, int32_t n_steps, float* loss_out) try
       SF_TRY(read_sse(h, &sse));
       loss_out[i] = (float)(sse / ((double)h->cfg.out_features * (double)h->npix));
     }
-    SF_TRY(adam_step(h, lr[i]));
+    if (after) SF_TRY(after());
+    SF_TRY(adam_step(h, lr[i], refresh));
   }
-  return table ? read_losses(h, n_steps, loss_out) : SF_OK;
+  return table ? read_losses(h, n, loss_out) : SF_OK;
+}
+
+int sf_step(sf_handle* h, const float* lr, int32_t n_steps, float* loss_out) try {
+  if (!h || !lr || n_steps < 0) return fail(SF_ERR_INVALID, "bad argument");
+  SF_NO_RENDER(h, "sf_step");
+  DevGuard dev_guard(h->cfg.device);
+  if (!h->have_coords) return fail(SF_ERR_STATE, "sf_set_coords has not been called");
+  if (!h->img) return fail(SF_ERR_STATE, "sf_set_target has not been called");
+  if (h->graph.want && n_steps >= 2 && !h->ctx->prof && h->npix <= h->chunk_px) return step_replay(h, lr, n_steps, loss_out);
+  return eager_steps(h, lr, n_steps, loss_out, loss_out && n_steps > 1, true);   // (a single loss: from the scalar)
 } SF_CATCH
 
 int sf_set_graph_replay(sf_handle* h, int32_t on) try {

@@ -5,6 +5,8 @@
 Reads conf/ (implicit_image/config.py), builds the registry model, fits with train_epoch /
 update_connections / eval_epoch exactly in the reference's order, logs loss / PSNR / PSNR_8bit,
 and saves `model.pth` (fp32 state_dict with the reference's parameter names) in the run directory.
+One loop serves every fit: fit_group (_setup per member, the boundaries, train_steps / train_steps_many, _after_steps,
+_finish); fit_one is the group of one, and main calls fit_group for every group of group_jobs.
 Comma sweeps expand to a job list; under torch.distributed.run the jobs are sharded over ranks
 (per-image sharding: one fit per GPU, no collectives).  With train.pixel_split=true every rank runs every job and fits its
 rows of the one picture (pixel-split: gradient, SSE and evaluation sums all-reduced; rank 0 writes).
@@ -57,6 +59,15 @@ def split_backend_setting(cfg: Cfg) -> str:
     return v
 
 
+def engine_width(cfg: Cfg):
+    """(the Small_Dense density or 1, the hidden width Siren gives the model at it, whether the engine zero-pads that width to
+    the next one its kernels are instantiated for): the configuration-side statement of Siren.__init__'s rule"""
+    masking = cfg.get("masking") or {}
+    small = masking.get("density") if masking.get("name") == "Small_Dense" else 1.0
+    hidden = int(cfg.mlp.hidden_size * np.sqrt(small))
+    return small, hidden, next_kernel_width(hidden, Siren.WIDTHS) != hidden
+
+
 def check_pixel_split(cfg: Cfg, world: int = 1):
     """What a fit split by rows refuses, from the configuration and the world size alone: before any GPU work and before the
     process group is touched, and the same on every rank, so no rank waits in a collective for one that raised."""
@@ -70,9 +81,8 @@ def check_pixel_split(cfg: Cfg, world: int = 1):
         raise NotImplementedError(f"train.pixel_split: {FEATHER_SPLIT_UNSUPPORTED}")
     if not device_eval_wanted(cfg.train.get("device_eval", "auto")):
         raise NotImplementedError(SPLIT_EVAL_EPOCH_UNSUPPORTED)
-    small = masking.get("density") if masking.get("name") == "Small_Dense" else 1.0
-    hidden = int(cfg.mlp.hidden_size * np.sqrt(small))                             # (Siren's own Small_Dense width)
-    if next_kernel_width(hidden, Siren.WIDTHS) != hidden:
+    _, hidden, padded = engine_width(cfg)
+    if padded:
         raise NotImplementedError(f"train.pixel_split with hidden width {hidden}: {SPLIT_PADDED_UNSUPPORTED}")
     if cfg.img.height < world:
         raise NotImplementedError(f"train.pixel_split: {cfg.img.height} image rows cannot be shared out over {world} ranks "
@@ -80,13 +90,14 @@ def check_pixel_split(cfg: Cfg, world: int = 1):
 
 
 class _Fit:
-    """One fit between its phases (_setup, the step loop, _finish): what fit_one holds in local variables, so that
-    fit_group can run the same phases for several fits at once.  rng: the CPU and device generator states the fit owns
-    (fit_group swaps them in around every piece of the fit's host work; fit_one never touches them)."""
+    """One fit between its phases (_setup, the step loop, _finish), so that fit_group can run the phases of several fits at
+    once.  rng: the CPU and device generator states the fit owns; scope: what fit_group enters around every piece of the
+    fit's host work - own_random_state for a member of several, nothing for a fit alone, which never reads or sets a state."""
 
-    def __init__(self, cfg: Cfg, device: torch.device):
+    def __init__(self, cfg: Cfg, device: torch.device, alone: bool = True):
         self.cfg, self.device = cfg, device
         self.rng = None
+        self.scope = contextlib.nullcontext if alone else self.own_random_state
 
     @contextlib.contextmanager
     def own_random_state(self):
@@ -103,9 +114,10 @@ class _Fit:
             self.rng = (torch.get_rng_state(), torch.cuda.get_rng_state(self.device) if cuda else None)
 
 
-def _setup(cfg: Cfg, device: torch.device, rank: int = None, world: int = None) -> _Fit:
-    """everything of a fit before its first step: refusals, seed, picture, grid, model, optimiser, mask, the evaluation route"""
-    f = _Fit(cfg, device)
+def _setup(f: _Fit, rank: int = None, world: int = None):
+    """everything of a fit before its first step, into `f`: refusals, seed, picture, grid, model, optimiser, mask, the
+    evaluation route, the start of its clock"""
+    cfg, device = f.cfg, f.device
     split = None
     if pixel_split_wanted(cfg):
         rank = int(os.environ.get("RANK", "0")) if rank is None else rank
@@ -127,9 +139,8 @@ def _setup(cfg: Cfg, device: torch.device, rank: int = None, world: int = None) 
     torch.manual_seed(cfg.seed)                                                   # compress.py:58
     img = load_img(**cfg.img)                                                      # compress.py:64
     grid = get_grid(cfg.img.height, cfg.img.width)                                 # compress.py:67
-    small = cfg.masking.density if (cfg.get("masking") and cfg.masking.get("name") == "Small_Dense") else 1.0
     eng_kw = dict(cfg.get("engine") or {})
-    model = model_registry[cfg.mlp.name](**cfg.mlp, small_dense_density=small, **eng_kw)   # compress.py:77
+    model = model_registry[cfg.mlp.name](**cfg.mlp, small_dense_density=engine_width(cfg)[0], **eng_kw)   # compress.py:77
     if feather:                                                                    # compress.py:80-81
         model = FeatherNet(model, compress=cfg.masking.density)
     if pixel_split_wanted(cfg):
@@ -162,7 +173,6 @@ def _setup(cfg: Cfg, device: torch.device, rank: int = None, world: int = None) 
             return eval_epoch(m, g, im)[1:]
         f.evaluate = evaluate
     f.t0, f.last = time.time(), {}
-    return f
 
 
 def _update_due(f: _Fit, i: int) -> bool:
@@ -261,23 +271,14 @@ def _finish(f: _Fit, out_dir: str = None):
 
 
 def fit_one(cfg: Cfg, device: torch.device, out_dir: str = None, rank: int = None, world: int = None):
-    """One fit; returns dict(loss, PSNR, PSNR_8bit, steps, seconds).
+    """One fit - the group of one; returns dict(loss, PSNR, PSNR_8bit, steps, seconds).
 
     train.pixel_split: rank `rank` of `world` (default: RANK / WORLD_SIZE, a world of one without them) fits rows
     shard_rows(H, world, rank) of the picture; the model carries a parallel.RowSplit, under which every step and every
     evaluation reduces over the ranks (utils/train_helper.py).  Seed, init, mask draw and schedules are the ordinary fit's on
     every rank, so the replicas stay identical; every rank returns the same dict, rank 0 alone writes into out_dir.  The
     caller has initialised torch.distributed when world > 1 (main does)."""
-    f = _setup(cfg, device, rank, world)
-    i = -1
-    while i + 1 < f.num_steps:                                                     # compress.py:137-170
-        # the iterations up to the next one that needs the host (topology update / logging) go to the engine
-        # in one call; train_steps() is bit-identical to calling train_epoch() once per iteration
-        first = i + 1
-        i = _next_boundary(f, first)
-        train_steps(f.model, f.optim, f.grid, f.img, i - first + 1, lr_scheduler=f.lr_scheduler, mask=f.mask)
-        _after_steps(f, i)
-    return _finish(f, out_dir)
+    return fit_group([cfg], device, [out_dir], rank, world)[0]
 
 
 # ---- train.batch_jobs: several fits of one shape at once (sf_step_many) -------------------------------------------------------
@@ -309,9 +310,8 @@ def group_key(cfg: Cfg):
     masking = cfg.get("masking") or {}
     if cfg.mlp.name != "siren" or masking.get("name") == "Feathermap" or pixel_split_wanted(cfg):
         return None
-    small = masking.get("density") if masking.get("name") == "Small_Dense" else 1.0
-    hidden = int(cfg.mlp.hidden_size * np.sqrt(small))                             # (Siren's own Small_Dense width)
-    if next_kernel_width(hidden, Siren.WIDTHS) != hidden or hidden > 128:
+    _, hidden, padded = engine_width(cfg)
+    if padded or hidden > 128:
         return None
     rest = _plain(cfg)
     for dotted in GROUP_FREE_KEYS:
@@ -343,45 +343,46 @@ def group_jobs(cfgs, n: int):
     return groups
 
 
-def fit_group(cfgs, device: torch.device, out_dirs=None):
-    """The fits of one group (group_jobs) at once; returns their fit_one dicts in order.
+def fit_group(cfgs, device: torch.device, out_dirs=None, rank: int = None, world: int = None):
+    """The fits of one group (group_jobs) at once, their fit_one dicts in order: the one fit loop (compress.py:137-170).
 
-    fit_one's loop runs once for all members: the same boundaries (they follow from keys the members share), between them
-    train_steps_many - one sf_step_many call where the members qualify, train_steps per member where not - then each member's
-    topology update and evaluation.  After the loop each member's quantise phase, artefacts and run directory are written by
-    fit_one's own code (_finish), one member after the other.
-    Every member owns the CPU and device generator states its torch.manual_seed(cfg.seed) gave it: they are swapped in before
-    any host work of the member (set-up, topology update, evaluation, quantise phase) and saved after, so every draw falls as
-    in a run of the member alone, and result.json apart from `seconds`, model.pth and the container are byte for byte those
-    of train.batch_jobs=1."""
+    The iterations up to the next one that needs the host (topology update / logging: the boundaries follow from keys the
+    members share) go to train_steps for a fit alone, else to train_steps_many - one sf_step_many call where the members
+    qualify, train_steps per member where not -, then each member's topology update and evaluation; after the loop each member's
+    quantise phase and artefacts (_finish).  Every member of several owns the generator states its torch.manual_seed(cfg.seed)
+    gave it: they are swapped in before any host work of the member and saved after, so every draw falls as in a run of the
+    member alone, and result.json apart from `seconds` (counted from the last member's set-up), model.pth and the container
+    are byte for byte those of train.batch_jobs=1.  A fit alone enters no such scope.  rank / world: fit_one's."""
     out_dirs = list(out_dirs) if out_dirs is not None else [None] * len(cfgs)
-    fits = []
-    for cfg in cfgs:
-        f = _Fit(cfg, device)                 # (a throw-away holder of the random state while _setup builds the real one)
-        with f.own_random_state():
-            g = _setup(cfg, device)
-        g.rng = f.rng
-        fits.append(g)
+    fits = [_Fit(cfg, device, alone=len(cfgs) == 1) for cfg in cfgs]
+    for f in fits:
+        with f.scope():
+            _setup(f, rank, world)
     head = fits[0]
-    if any(g.num_steps != head.num_steps or bool(g.mask) != bool(head.mask) for g in fits):
+    if any(f.num_steps != head.num_steps or bool(f.mask) != bool(head.mask) for f in fits):
         raise ValueError("fit_group: the members differ in their step count or in having a mask (group_jobs keeps such jobs apart)")
-    t0 = time.time()
-    for g in fits:
-        g.t0 = t0
+    if len(fits) > 1:
+        t0 = time.time()
+        for f in fits:
+            f.t0 = t0
     i = -1
     while i + 1 < head.num_steps:
         first = i + 1
         i = _next_boundary(head, first)
-        train_steps_many([g.model for g in fits], [g.optim for g in fits], head.grid, [g.img for g in fits], i - first + 1,
-                         lr_schedulers=[g.lr_scheduler for g in fits], masks=[g.mask for g in fits],
-                         scopes=[g.own_random_state for g in fits])
-        for g in fits:
-            with g.own_random_state():
-                _after_steps(g, i)
+        if len(fits) == 1:     # (what train_steps_many makes of one member, under this module's name, which observers wrap)
+            train_steps(head.model, head.optim, head.grid, head.img, i - first + 1, lr_scheduler=head.lr_scheduler,
+                        mask=head.mask)
+        else:
+            train_steps_many([f.model for f in fits], [f.optim for f in fits], head.grid, [f.img for f in fits], i - first + 1,
+                             lr_schedulers=[f.lr_scheduler for f in fits], masks=[f.mask for f in fits],
+                             scopes=[f.scope for f in fits])
+        for f in fits:
+            with f.scope():
+                _after_steps(f, i)
     results = []
-    for g, out_dir in zip(fits, out_dirs):
-        with g.own_random_state():
-            results.append(_finish(g, out_dir))
+    for f, out_dir in zip(fits, out_dirs):
+        with f.scope():
+            results.append(_finish(f, out_dir))
     return results
 
 
@@ -427,12 +428,10 @@ def main(argv=None):
                     torch.cuda.set_device(device)
                 tags.append(",".join(o for o in ov if not o.startswith(("exp_name", "img.name"))) or "default")
                 out_dirs.append(os.path.join("outputs", str(cfg.img.name), str(cfg.exp_name), tags[-1].replace("/", "_")))
-            if len(members) == 1:
-                cfg = cfgs[members[0]]
-                done = [fit_one(cfg, device, out_dirs[0], rank, world) if any(split) else fit_one(cfg, device, out_dirs[0])]
-            else:
-                before = dict(train_helper.MANY_STATS)
-                done = fit_group([cfgs[j] for j in members], device, out_dirs)
+            before = dict(train_helper.MANY_STATS)
+            # (rank / world matter to a fit split by rows alone, which every rank runs; a sharded job never looks at them)
+            done = fit_group([cfgs[j] for j in members], device, out_dirs, rank, world)
+            if len(members) > 1:
                 took = {k: v - before[k] for k, v in train_helper.MANY_STATS.items()}
                 logging.info(f"[rank {rank}] group of {len(members)}: {took['steps']} steps each in {took['calls']} sf_step_many "
                              f"calls, {took['fallbacks']} stretches member by member")

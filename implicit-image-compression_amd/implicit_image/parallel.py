@@ -58,6 +58,16 @@ def all_reduce_sum(dist, t: torch.Tensor, group=None):
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
 
 
+def reduced_pass(eng, all_reduce) -> torch.Tensor:
+    """The pass of a split step: forward + backward of the local rows enqueued, the handle's own gradient view and SSE double
+    summed in place by `all_reduce` -> the SSE view, to be read or copied before the next pass overwrites it."""
+    eng.forward_backward(sync=False)
+    sse = eng.sse_view()
+    all_reduce(eng.grad_view())
+    all_reduce(sse)
+    return sse
+
+
 class SseTable:
     """The SSE doubles of a run of steps, kept where the passes wrote them: put() is one device copy per step, read() the one
     transfer at the end of the run."""
@@ -102,10 +112,9 @@ class RowSplit:
         if self._dist is not None:
             all_reduce_sum(self._dist, t, self.group)
 
-    def reduce_pass(self, eng):
-        """after forward_backward(sync=False): the handle's own gradient view and its SSE double, summed over the ranks"""
-        self.all_reduce(eng.grad_view())
-        self.all_reduce(eng.sse_view())
+    def reduce_pass(self, eng) -> torch.Tensor:
+        """reduced_pass over this split's ranks: the pass enqueued, gradient and SSE summed -> the SSE view"""
+        return reduced_pass(eng, self.all_reduce)
 
     def reduce_eval(self, eng) -> Tuple[float, int]:
         """after eval_sums(sync=False): (sse, sse8) of the full image - the double and the exact 64-bit integer sum"""
@@ -157,10 +166,7 @@ class PixelSplitFit:
 
     def step(self, lr: float, want_loss: bool = True):
         """One optimiser step on the full image; returns the global MSE (same on every rank) or None."""
-        self.backend.forward_backward(sync=False)
-        sse = self.backend.sse_view()
-        self._all_reduce(self.backend.grad_view())
-        self._all_reduce(sse)
+        sse = reduced_pass(self.backend, self._all_reduce)
         loss = float(sse.item()) / self.n_values if want_loss else None   # read before the next pass overwrites it
         self.backend.adam_step(lr)
         return loss
@@ -171,10 +177,6 @@ class PixelSplitFit:
         lrs = list(lrs)
         table = SseTable(len(lrs))
         for k, lr in enumerate(lrs):
-            self.backend.forward_backward(sync=False)
-            sse = self.backend.sse_view()
-            self._all_reduce(self.backend.grad_view())
-            self._all_reduce(sse)
-            table.put(k, sse)                   # before the next pass overwrites it
+            table.put(k, reduced_pass(self.backend, self._all_reduce))   # before the next pass overwrites it
             self.backend.adam_step(lr)
         return [s / self.n_values for s in table.read()]

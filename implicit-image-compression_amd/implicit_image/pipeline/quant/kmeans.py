@@ -106,7 +106,7 @@ class KmeansQuant:
         self.model, self.optim, self.bits, self.skip_ll = model, optim, bits, list(skip_ll)
         self.device_phase = device_phase
         self._plan = None                       # (engine, sf_quant_args over this quantiser's persistent buffers)
-        self._in_bulk = False                   # train_steps is handing the steps to sf_quant_step: the pass runs there
+        self._in_bulk = False                   # bind_handle is running engine(): the pass belongs to sf_quant_step
         self._targets: List[nn.Linear] = [m for n, m in model.named_modules()
                                          if isinstance(m, nn.Linear) and n not in self.skip_ll]
         self._pre = self.kmeans_modify_weights
@@ -121,6 +121,20 @@ class KmeansQuant:
     @property
     def learning_rate(self) -> float:
         return self.optim.defaults["lr"]
+
+    def is_whole_phase_of(self, model, optim) -> bool:
+        """are this quantiser's two callbacks `model`'s only pre-pass and post-backward ones, and does it step `optim`"""
+        return (list(model.pre_pass_callbacks) == [self._pre] and list(model.post_backward_callbacks) == [self._post]
+                and self.optim is optim)
+
+    def bind_handle(self, grid, img):
+        """model.engine(grid, img) without the pre-pass (it belongs to the sf_quant_step to come) -> device_plan() on that handle"""
+        self._in_bulk = True
+        try:
+            self.model.engine(grid, img)
+        finally:
+            self._in_bulk = False
+        return self.device_plan()
 
     def device_wanted(self) -> bool:
         """what device_plan asks before there is a handle: the configuration, the model, the bits, the two knobs"""

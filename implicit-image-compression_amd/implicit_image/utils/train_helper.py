@@ -11,9 +11,12 @@
 
 One `train_epoch` is one full-batch fit step executed by the HIP engine: forward + MSE + backward
 (sf_forward_backward) and Adam(+mask) (sf_adam_step through the optimiser facade).
+
+Every way of running n steps is train_epoch called n times, bit for bit, and shares its pieces: _step (the body of a step around
+a route's pass), _run_ahead (the bookkeeping of n steps the device runs alone), _unsupported (what every route refuses).  The
+routes: train_steps' docstring and DESIGN.md section 13.
 """
 import contextlib
-import ctypes
 import logging
 import math
 from typing import Dict, Tuple
@@ -154,27 +157,27 @@ def setup_mask(model: Module, optim: Optimizer, masking_cfg=None) -> Masking:
     return mask
 
 
-def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
-    """One full-batch optimiser step; returns the loss of the step like `train_loss.item()`."""
-    mask: Masking = kwargs.get("mask")
-    pbar = kwargs.get("pbar")
-    lr_scheduler = kwargs.get("lr_scheduler")
-    criterion = kwargs.get("criterion", F.mse_loss)
-    if criterion is not F.mse_loss:
-        raise NotImplementedError("the engine fuses F.mse_loss (reduction='mean'); other criteria are not supported")
+def _unsupported(kwargs):
+    """why the engine cannot take these keyword arguments of a step, else None: the one statement of what every route refuses.
+    'scaler' / 'context' are accepted and ignored: autocast is never entered by the reference (train_helper.py:141) and
+    GradScaler is an exact no-op on fp32 gradients."""
+    if kwargs.get("criterion", F.mse_loss) is not F.mse_loss:
+        return "the engine fuses F.mse_loss (reduction='mean'); other criteria are not supported"
     if kwargs.get("preconditioner") is not None:
-        raise NotImplementedError("preconditioners (EKFAC) are dead code in the reference and not supported")
-    # kwargs 'scaler' / 'context' are accepted and ignored: autocast is never entered by the reference
-    # (train_helper.py:141) and GradScaler is an exact no-op on fp32 gradients (SURVEY.md §8a T3).
-    if getattr(model, "row_split", None) is not None:
-        return _split_steps(model, optim, grid, img, 1, **kwargs)[0]
+        return "preconditioners (EKFAC) are dead code in the reference and not supported"
+    return None
+
+
+def _step(model: Module, optim: Optimizer, grid, img, the_pass, **kwargs):
+    """The one body of a step on the host, around `the_pass(eng)` - what a route does between binding the handle and looking
+    at the gradient - whose result it returns: model.train, zero_grad, engine() (the pre-pass callbacks of a quantise phase run
+    there: sf_quant_pass), the pass, download_grads (a no-op unless the width is zero-padded), the post-backward callbacks,
+    mask.step() or optim.step(), pbar, the scheduler."""
+    mask, pbar, lr_scheduler = kwargs.get("mask"), kwargs.get("pbar"), kwargs.get("lr_scheduler")
     model.train()
     optim.zero_grad()
-    eng = model.engine(grid, img)
-    sse = eng.forward_backward(sync=True)
-    # a float's value, as `.item()` of the reference's float32 loss is and as sf_step reports a step's: (float)(sse / n)
-    loss = ctypes.c_float(sse / (img.shape[0] * img.shape[1] * img.shape[2])).value
-    model.download_grads()             # no-op unless the width is zero-padded
+    out = the_pass(model.engine(grid, img))
+    model.download_grads()
     for cb in list(model.post_backward_callbacks):
         cb()
     if mask:
@@ -185,64 +188,64 @@ def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
         pbar.update(1)
     if lr_scheduler:
         lr_scheduler.step()
-    return loss
+    return out
+
+
+def _run_ahead(optim: Optimizer, lr_scheduler, n: int):
+    """The host's bookkeeping of `n` steps that the device runs without it -> their n learning rates"""
+    optim.count_steps(n)                     # (first: the scheduler looks for the optimiser's mark at its first step)
+    lrs = []
+    for _ in range(n):                       # the schedule is host-side bookkeeping: run it ahead
+        lrs.append(float(optim.param_groups[0]["lr"]))
+        if lr_scheduler:
+            lr_scheduler.step()
+    return lrs
+
+
+def train_epoch(model: Module, optim: Optimizer, grid, img, **kwargs) -> float:
+    """One full-batch optimiser step; returns the loss of the step like `train_loss.item()`."""
+    if getattr(model, "row_split", None) is not None:
+        return _split_steps(model, optim, grid, img, 1, **kwargs)[0]
+    why = _unsupported(kwargs)
+    if why:
+        raise NotImplementedError(why)
+    sse = _step(model, optim, grid, img, lambda eng: eng.forward_backward(sync=True), **kwargs)
+    # a float's value, as `.item()` of the reference's float32 loss is and as sf_step reports a step's: (float)(sse / n)
+    return as_float(sse / (img.shape[0] * img.shape[1] * img.shape[2]))
 
 
 def _split_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
     """`n` steps of a fit split by image rows (model.row_split, a parallel.RowSplit; grid / img: this rank's rows), returned as
     the list of their losses: (float)(sse / n) of the FULL image, the same on every rank.
 
-    A step is train_epoch's in train_epoch's order, with the reduction where the loss used to be read:
-    forward_backward(sync=False), the in-place all-reduce of the handle's own gradient view and SSE double, download_grads
-    and the post-backward callbacks, mask.step() or optim.step().  Nothing is read per step: every step's reduced SSE is
-    copied into a table on the device, and the table is read once after the last step.  The bulk calls (sf_step,
+    A step is train_epoch's (_step) with the reduction where the loss used to be read: split.reduce_pass - the pass enqueued,
+    the in-place all-reduce of the handle's own gradient view and SSE double.  Nothing is read per step: every step's reduced
+    SSE is copied into a table on the device, and the table is read once after the last step.  The bulk calls (sf_step,
     sf_quant_step) are not used: a collective cannot run inside them.  A world of one reduces nothing and is, kernel for
     kernel, the step-by-step loop the bulk calls are bit-identical to."""
-    if kwargs.get("criterion", F.mse_loss) is not F.mse_loss:
-        raise NotImplementedError("the engine fuses F.mse_loss (reduction='mean'); other criteria are not supported")
-    if kwargs.get("preconditioner") is not None:
-        raise NotImplementedError("preconditioners (EKFAC) are dead code in the reference and not supported")
+    why = _unsupported(kwargs)
+    if why:
+        raise NotImplementedError(why)
     if not model.state_is_live:
         raise NotImplementedError(SPLIT_PADDED_UNSUPPORTED)
-    split, mask, pbar, lr_scheduler = model.row_split, kwargs.get("mask"), kwargs.get("pbar"), kwargs.get("lr_scheduler")
-    table = SseTable(n)
+    split, table = model.row_split, SseTable(n)
     for k in range(n):
-        model.train()
-        optim.zero_grad()
-        eng = model.engine(grid, img)          # (the pre-pass callbacks of a quantise phase run here: sf_quant_pass)
-        eng.forward_backward(sync=False)
-        split.reduce_pass(eng)
-        table.put(k, eng.sse_view())           # before the next pass overwrites it
-        model.download_grads()
-        for cb in list(model.post_backward_callbacks):
-            cb()
-        if mask:
-            mask.step(kwargs.get("scaler"))
-        else:
-            optim.step()
-        if pbar:
-            pbar.update(1)
-        if lr_scheduler:
-            lr_scheduler.step()
+        # (the reduced SSE into the table before the next pass overwrites it)
+        _step(model, optim, grid, img, lambda eng: table.put(k, split.reduce_pass(eng)), **kwargs)
     return [as_float(sse / split.n_values(img)) for sse in table.read()]
 
 
 def _quant_phase(model: Module, optim: Optimizer):
     """the KmeansQuant whose two callbacks are the model's only ones and which steps `optim`, when it wants the device route:
     the quantise phase as train_steps can hand it to sf_quant_step once the handle is there.  Else None."""
-    pre, post = model.pre_pass_callbacks, model.post_backward_callbacks
-    if len(pre) != 1 or len(post) != 1:
-        return None
-    kq = getattr(post[0], "__self__", None)
-    if not isinstance(kq, KmeansQuant) or getattr(pre[0], "__self__", None) is not kq or kq.optim is not optim:
-        return None
-    return kq if (pre[0] == kq._pre and post[0] == kq._post and kq.device_wanted()) else None
+    post = model.post_backward_callbacks
+    kq = getattr(post[0], "__self__", None) if len(post) == 1 else None
+    return kq if (isinstance(kq, KmeansQuant) and kq.is_whole_phase_of(model, optim) and kq.device_wanted()) else None
 
 
 def _plain(model: Module, optim: Optimizer, **kwargs) -> bool:
     """the engine's own state, optimiser and loss: what both bulk routes of train_steps need"""
-    return (model.state_is_live and isinstance(optim, EngineAdam) and kwargs.get("criterion", F.mse_loss) is F.mse_loss
-            and kwargs.get("preconditioner") is None)
+    return model.state_is_live and isinstance(optim, EngineAdam) and _unsupported(kwargs) is None
 
 
 def _bulk(model: Module, optim: Optimizer, n: int, **kwargs) -> bool:
@@ -254,62 +257,41 @@ def _bulk(model: Module, optim: Optimizer, n: int, **kwargs) -> bool:
 
 
 def train_steps(model: Module, optim: Optimizer, grid, img, n: int, **kwargs):
-    """`n` consecutive train_epoch() calls, returned as the list of their losses.
+    """`n` consecutive train_epoch() calls, returned as the list of their losses, by the first route that applies.  Every route
+    runs the same kernels in the same order, so each is bit-identical to the step-by-step loop.
 
-    The reference loop (compress.py:137-170) syncs with the device every iteration for `train_loss.item()`.
-    When nothing on the host has to look at the state between two steps (no per-layer callbacks, no padded
-    width, masks either absent or applied inside the engine's Adam kernel with dense gradients) the n steps go
-    to the engine in ONE call (`sf_step`): same kernels in the same order, so the result is bit-identical to
-    the step-by-step loop, but the stream never drains and the losses come back in one read.
+      split          model.row_split is set (train.pixel_split)                          _step per step, a collective in each
+      quantise       n >= 1, _plain, no mask, the model's only callbacks are one         _run_ahead, ONE sf_quant_step (the nudge
+                     KmeansQuant's and it has a device plan on the bound handle          at optim.defaults["lr"], as the reference)
+      bulk           _bulk: nothing on the host looks at the state between two steps     _run_ahead, ONE sf_step
+      step by step   otherwise                                                           train_epoch per step
 
-    The quantise phase is the second bulk case: when the model's only callbacks are one KmeansQuant's and it has a device
-    plan (pipeline/quant/kmeans.py), the n steps - each with its k-means pass before and its centroid nudge after the
-    backward - are ONE `sf_quant_step` call.  The nudge's learning rate is optim.defaults["lr"], not the scheduled one, as
-    in the reference."""
-    if getattr(model, "row_split", None) is not None:      # a fit split by rows: step by step, one read at the end
+    The reference loop (compress.py:137-170) syncs with the device every iteration for `train_loss.item()`; on the two
+    one-call routes the stream never drains and the losses come back in one read."""
+    if getattr(model, "row_split", None) is not None:
         return _split_steps(model, optim, grid, img, n, **kwargs)
     mask: Masking = kwargs.get("mask")
     lr_scheduler = kwargs.get("lr_scheduler")
     pbar = kwargs.get("pbar")
-    plain = _plain(model, optim, **kwargs)
-    kq = _quant_phase(model, optim) if (plain and n >= 1 and mask is None) else None
+    kq = _quant_phase(model, optim) if (_plain(model, optim, **kwargs) and n >= 1 and mask is None) else None
     if kq is not None:
         model.train()
-        kq._in_bulk = True                   # (engine() runs the pre-pass callbacks: the pass belongs to sf_quant_step here)
-        try:
-            model.engine(grid, img)
-        finally:
-            kq._in_bulk = False
-        if kq.device_plan() is None:         # (a handle without the entry points: step by step, the callbacks as ever)
+        if kq.bind_handle(grid, img) is None:      # (a handle without the entry points: step by step, the callbacks as ever)
             kq = None
     if kq is not None:
         optim.prepare()
-        optim.count_steps(n)
-        lrs = []
-        for _ in range(n):
-            lrs.append(float(optim.param_groups[0]["lr"]))
-            if lr_scheduler:
-                lr_scheduler.step()
-        losses = kq.device_steps(lrs, want_loss=True)
-        if pbar:
-            pbar.update(n)
-        return losses
-    if not _bulk(model, optim, n, **kwargs):
+        losses = kq.device_steps(_run_ahead(optim, lr_scheduler, n), want_loss=True)
+    elif not _bulk(model, optim, n, **kwargs):
         return [train_epoch(model, optim, grid, img, **kwargs) for _ in range(n)]
-    model.train()
-    model.engine(grid, img)
-    eng = optim.prepare()
-    if mask is not None:
-        mask.push_masks_once()
-    optim.count_steps(n)                     # (first: the scheduler looks for the optimiser's mark at its first step)
-    lrs = []
-    for _ in range(n):                       # the schedule is host-side bookkeeping: run it ahead
-        lrs.append(float(optim.param_groups[0]["lr"]))
-        if lr_scheduler:
-            lr_scheduler.step()
-    losses = eng.step(lrs, want_loss=True)
-    if mask is not None:
-        mask.count_steps(n)
+    else:
+        model.train()
+        model.engine(grid, img)
+        eng = optim.prepare()
+        if mask is not None:
+            mask.push_masks_once()
+        losses = eng.step(_run_ahead(optim, lr_scheduler, n), want_loss=True)
+        if mask is not None:
+            mask.count_steps(n)
     if pbar:
         pbar.update(n)
     return losses
@@ -329,7 +311,7 @@ def train_steps_many(models, optims, grid, imgs, n: int, lr_schedulers=None, mas
     has sf_step_many and the handles pass its checks (one shape, hidden <= 128, fp16 operands, scratch format 16, one chunk,
     the whole picture, one stream: include/siren_fit.h), the n steps of ALL members are one sf_step_many call: every kernel of
     a step is launched once for all of them, and each member ends bit for bit where its own sf_step would.  The host
-    bookkeeping per member is train_steps': optim.prepare, mask.push_masks_once, count_steps, the scheduler run ahead.
+    bookkeeping per member is train_steps': optim.prepare, mask.push_masks_once, _run_ahead (the member's column of the lrs).
     Otherwise train_steps once per member, in order; why is logged once per reason.
 
     scopes: one callable per member that returns a context manager, entered around that member's host work (fit.py: the
@@ -376,13 +358,8 @@ def train_steps_many(models, optims, grid, imgs, n: int, lr_schedulers=None, mas
     why = _engine.step_many_refusal(engines)
     if why is not None:
         return one_by_one(why)
-    lrs = [[0.0] * B for _ in range(n)]
-    for b in range(B):
-        optims[b].count_steps(n)             # (first: the scheduler looks for the optimiser's mark at its first step)
-        for s in range(n):                   # the schedule is host-side bookkeeping: run it ahead
-            lrs[s][b] = float(optims[b].param_groups[0]["lr"])
-            if lr_schedulers[b]:
-                lr_schedulers[b].step()
+    columns = [_run_ahead(optims[b], lr_schedulers[b], n) for b in range(B)]      # member by member, each its own schedule
+    lrs = [list(row) for row in zip(*columns)]
     losses = _engine.step_many(engines, lrs, want_loss=True)
     for b in range(B):
         if masks[b] is not None:

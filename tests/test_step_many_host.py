@@ -7,6 +7,7 @@ from types import SimpleNamespace
 
 import pytest
 
+from _step_fakes import FakeModel, FakeOptim
 from implicit_image import _engine, fit
 from implicit_image.config import expand_sweeps, load_config
 from implicit_image.utils import train_helper as th
@@ -128,34 +129,6 @@ def test_pixel_split_with_batch_jobs_is_refused_before_the_gpu(monkeypatch):
         fit.main(["train.batch_jobs=2", "train.pixel_split=true", "seed=0,1"])
     with pytest.raises(ValueError, match="train.batch_jobs"):
         fit.main(["train.batch_jobs=0"])
-
-
-class FakeModel:
-    row_split = None
-    state_is_live = True
-    post_backward_callbacks = ()
-
-    def __init__(self, eng):
-        self.eng, self.calls = eng, []
-
-    def train(self):
-        self.calls.append("train")
-
-    def engine(self, grid, img):
-        self.calls.append("engine")
-        return self.eng
-
-
-class FakeOptim:
-    def __init__(self, model):
-        self.model, self.calls = model, []
-
-    def prepare(self):
-        self.calls.append("prepare")
-        return self.model.eng
-
-    def count_steps(self, n):
-        self.calls.append(("count_steps", n))
 
 
 def test_without_the_entry_point_train_steps_many_is_train_steps_per_member(monkeypatch):
